@@ -1,14 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- images/sec of the ViT-B/16 224x224 fp32 forward at batch 256 per GPU (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]   (N > 1: launched by torch.distributed.run)
 
 A step = one forward of one batch of synthetic images already resident in HBM, through the C-ABI
 (vit_engine_forward_device) on this rank's GPU; with N > 1 every rank owns its own batch (weak
 scaling, no data-path collective) and the per-image top-1 records are all-gathered over RCCL at
 the end of each step (the only exchange the north star asks for).  One JSON line on rank 0.
 
-Extra objects in the line:
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, dtype, config);
+the objects below are null in it.  --full adds every check and measurement listed below, each outside the timed region.
+--dump-outputs DIR writes what the last timed step returned to its caller, as float32 / float64 .npy files (rank 0):
+  probs.npy [B][classes], top1_label.npy [B], top1_prob.npy [B], and with N > 1 gathered_top1_label.npy /
+  gathered_top1_prob.npy [N][B] (the RCCL gather).  Above 48 MB of probabilities, a fixed seeded sample of rows is written
+  instead, its row indices in probs_rows.npy.  Weights and images come from fixed seeds: same arguments, same inputs.
+
+Extra objects in the line (--full):
   roofline      the dominant kernel (fp32 MFMA GEMM): algorithmic FLOPs per launch / average launch
                 duration from HIP events recorded on the launch stream during the timed steps.
   golden        every rank's batch starts with the two images of tests/golden/vit_b16_e2e.npz (probabilities written by the
@@ -149,6 +156,31 @@ def replayed_counters(kernel, tag, batch):
                                                ("clock_ghz_rocprof", clock)) if v is not None],
                         live=False)
     return {"traffic": traffic, "mfma_busy_percent_rocprof": busy, "clock_ghz_rocprof": clock, "replayed_from": replayed}
+
+
+DUMP_PROBS_BYTES = 48 << 20   # --dump-outputs: probability rows beyond this are sampled (the whole dump stays under 64 MB)
+
+
+def dump_outputs(np, out_dir, probs, top1, gathered):
+    """What the last timed step handed its caller, as .npy files in out_dir: float32 probabilities and top-1 probabilities,
+    float64 labels (exact), and the gathered records of every rank when there are several."""
+    os.makedirs(out_dir, exist_ok=True)
+    p = probs.cpu().numpy()
+    if p.nbytes > DUMP_PROBS_BYTES:
+        n = DUMP_PROBS_BYTES // (p.shape[1] * p.itemsize)
+        rows = np.sort(np.random.default_rng(0).choice(p.shape[0], n, replace=False))
+        p = p[rows]
+        np.save(os.path.join(out_dir, "probs_rows.npy"), rows.astype(np.float64))
+    out = {"probs": p}
+    rec = top1.cpu()
+    out["top1_label"] = rec[0].numpy().astype(np.float64)
+    out["top1_prob"] = rec[1].numpy().view(np.float32)
+    if gathered is not None:
+        g = gathered.cpu().numpy()
+        out["gathered_top1_label"] = g[:, 0].astype(np.float64)
+        out["gathered_top1_prob"] = np.ascontiguousarray(g[:, 1]).view(np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def clock_limit_probe(binding, torch, dev, cfg, batch, dtype):
@@ -384,7 +416,14 @@ def main() -> None:
     ap.add_argument("--spawn", action="store_true",
                     help="start the rank processes from this process even for --gpus 1 (N > 1 always does when not "
                          "already launched): exercises the launcher and the RCCL gather at world size 1")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: golden / parity / gather checks, roofline pass, CPU baseline, "
+                         "C surface, clock probe and the other configurations (the --no-* switches above select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (probabilities, top-1 records) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.config:
         args.model, args.dtype, args.batch = {1: ("b16", "f32", 256), 2: ("b16", "bf16", 2048), 3: ("b16", "bf16", 2048),
                                               4: ("l16_384", "bf16", 1024)}[args.config]
@@ -492,11 +531,13 @@ def main() -> None:
         step()
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(np, args.dump_outputs, probs, top1, gathered)
     gather_ok = None
     per_rank_ms = None
     tol = 1e-4 if args.dtype == "f32" else 2e-2
     gold = None
-    if golden is not None:  # rows 0-1 of the timed steps' output against the reference's probabilities, on this rank
+    if args.full and golden is not None:  # rows 0-1 of the timed steps' output against the reference's probabilities, on this rank
         got2 = probs[:2].cpu().numpy()
         gold = {"rows": 2, "max_abs_prob_err": float(np.abs(got2 - golden).max()),
                 "top1_match": bool((got2.argmax(1) == golden.argmax(1)).all()), "tolerance": tol,
@@ -508,6 +549,7 @@ def main() -> None:
         per_rank_ms = [round(1e3 * float(x.item()) / args.steps, 3) for x in every]   # clock they hold, and the slowest one is `value`
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if distributed and args.full:
         # the gather, checked outside the timed region: EVERY slot r must hold what rank r says its records are (a broadcast
         # per rank: another collective than the one under test), and -- the batches start with the golden images -- the
         # golden labels in its first two entries
@@ -517,22 +559,6 @@ def main() -> None:
         dist.all_reduce(flags, op=dist.ReduceOp.MIN)   # the worst of all ranks
         if gold:
             gold.update(max_abs_prob_err=float(-flags[0].item()), top1_match=bool(flags[1].item() == 1.0), ranks=world)
-    handover = eng.handover_stats() if args.dtype == "f32" else None   # fp32 GEMM helper pieces of warm-up + timed steps
-    kernel_steps = args.steps
-    if args.lanes == 1 and not args.graph and not args.no_stage_brackets:
-        times = eng.stage_times()
-    else:
-        # kernel-level pass: same batch, same kernels, one lane, every launch bracketed by events on its stream
-        eng.set_lanes(1)
-        eng.set_profile(True)
-        step()
-        fence()
-        eng.reset_stage_times()
-        kernel_steps = max(1, args.kernel_steps)
-        for _ in range(kernel_steps):
-            step()
-        fence()
-        times = eng.stage_times()
 
     ms_per_step = 1e3 * dt / args.steps
     value = world * B * args.steps / dt
@@ -544,32 +570,50 @@ def main() -> None:
     model_tflops = value * gflop_img / 1e3 / world  # per GPU
 
     # ---- roofline of the dominant kernel (per-launch, from the stage brackets) -------------------
-    peak = FP32_MFMA_PEAK_TFLOPS if args.dtype == "f32" else BF16_MFMA_PEAK_TFLOPS
-    dom_name, dom, avg_ms, achieved, gemm_ms, gemm_flop = dominant_kernel(times, cfg, B, args.dtype, kernel_steps, saved, fold=args.ln_fold >= 0 and cfg.embed_dim % 64 == 0)
-    tag = profile_tag(args.dtype, args.model)
-    counters = replayed_counters(dom_name, tag, B)
-    roofline = {
-        "bound": "mfma", "kernel": dom_name, "achieved": round(achieved, 2), "peak": peak,
-        "unit": "TFLOP/s", "frac": round(achieved / peak, 4), **counters,
-        "avg_launch_ms": round(avg_ms, 4), "launches": dom["launches"],
-        "flop_per_launch": dom["flop"] / max(dom["launches"], 1),
-        "all_gemm_tflops": round(gemm_flop / (gemm_ms * 1e-3) / 1e12, 2) if gemm_ms > 0 else None,
-        "whole_model_tflops": round(model_tflops, 2),
-        "whole_model_frac": round(model_tflops / peak, 4),
-        "stage_ms_per_step": {s: round(r["ms"] / kernel_steps, 3) for s, r in times["stages"].items()},
-        # fp32 GEMM helper pieces over warm-up + timed steps: tiles finished from a parked piece / tiles whose owner found none
-        # and computed all of it (lost time, never a wrong result: nothing in the hand-over waits)
-        "gemm_handover": handover,
-        "measured": ("HIP events around every launch during the timed steps" if (args.lanes == 1 and not args.graph and not args.no_stage_brackets) else
-                     f"HIP events around every launch in {kernel_steps} extra steps with lanes=1 right after the timed region "
-                     + (f"(the timed steps run {args.lanes} concurrent lanes, whose kernels overlap)" if args.lanes > 1 else
-                        "(same batch, same kernels; the timed steps themselves carry no instrumentation)")),
-    }
+    roofline = None
+    if args.full:
+        handover = eng.handover_stats() if args.dtype == "f32" else None   # fp32 GEMM helper pieces of warm-up + timed steps
+        kernel_steps = args.steps
+        if args.lanes == 1 and not args.graph and not args.no_stage_brackets:
+            times = eng.stage_times()
+        else:
+            # kernel-level pass: same batch, same kernels, one lane, every launch bracketed by events on its stream
+            eng.set_lanes(1)
+            eng.set_profile(True)
+            step()
+            fence()
+            eng.reset_stage_times()
+            kernel_steps = max(1, args.kernel_steps)
+            for _ in range(kernel_steps):
+                step()
+            fence()
+            times = eng.stage_times()
+        peak = FP32_MFMA_PEAK_TFLOPS if args.dtype == "f32" else BF16_MFMA_PEAK_TFLOPS
+        dom_name, dom, avg_ms, achieved, gemm_ms, gemm_flop = dominant_kernel(times, cfg, B, args.dtype, kernel_steps, saved, fold=args.ln_fold >= 0 and cfg.embed_dim % 64 == 0)
+        tag = profile_tag(args.dtype, args.model)
+        counters = replayed_counters(dom_name, tag, B)
+        roofline = {
+            "bound": "mfma", "kernel": dom_name, "achieved": round(achieved, 2), "peak": peak,
+            "unit": "TFLOP/s", "frac": round(achieved / peak, 4), **counters,
+            "avg_launch_ms": round(avg_ms, 4), "launches": dom["launches"],
+            "flop_per_launch": dom["flop"] / max(dom["launches"], 1),
+            "all_gemm_tflops": round(gemm_flop / (gemm_ms * 1e-3) / 1e12, 2) if gemm_ms > 0 else None,
+            "whole_model_tflops": round(model_tflops, 2),
+            "whole_model_frac": round(model_tflops / peak, 4),
+            "stage_ms_per_step": {s: round(r["ms"] / kernel_steps, 3) for s, r in times["stages"].items()},
+            # fp32 GEMM helper pieces over warm-up + timed steps: tiles finished from a parked piece / tiles whose owner found none
+            # and computed all of it (lost time, never a wrong result: nothing in the hand-over waits)
+            "gemm_handover": handover,
+            "measured": ("HIP events around every launch during the timed steps" if (args.lanes == 1 and not args.graph and not args.no_stage_brackets) else
+                         f"HIP events around every launch in {kernel_steps} extra steps with lanes=1 right after the timed region "
+                         + (f"(the timed steps run {args.lanes} concurrent lanes, whose kernels overlap)" if args.lanes > 1 else
+                            "(same batch, same kernels; the timed steps themselves carry no instrumentation)")),
+        }
 
     # ---- CPU baseline + parity on the sampled image (rank 0, N = 1 only) -------------------------
     cpu = None
     parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import pyoracle as po
         ocfg = po.Config(cfg.img_size, cfg.patch_size, cfg.in_chans, cfg.num_classes, cfg.embed_dim,
                          cfg.depth, cfg.num_heads, cfg.hidden_dim)
@@ -616,7 +660,7 @@ def main() -> None:
 
     # ---- through the C surface (N = 1): host images in, host probability rows out ------------------
     c_surface = None
-    if rank == 0 and world == 1 and not args.no_c_surface:
+    if args.full and rank == 0 and world == 1 and not args.no_c_surface:
         import ctypes as C
         eng.set_profile(False)
         eng.set_lanes(args.lanes)
@@ -642,13 +686,13 @@ def main() -> None:
                      "bit_identical_to_device_path": same}
 
     # ---- how much of the gap to the roofline is clock (N = 1): the dominant GEMM's shape on busy and on quiet operands ------------
-    if rank == 0 and world == 1 and not args.no_clock_probe and not args.prune_last_layer:
+    if args.full and rank == 0 and world == 1 and not args.no_clock_probe and not args.prune_last_layer:
         roofline["clock_limit_probe"] = clock_limit_probe(binding, torch, dev, cfg, B if args.lanes == 1 else B // args.lanes, args.dtype)
 
     # ---- the other single-GPU configurations of BASELINE.json, each as a short timed run of its own (N = 1, headline only) ----------
     others = None
     headline = args.model == "b16" and args.dtype == "f32" and B == 256 and not args.prune_last_layer and not args.graph
-    if rank == 0 and world == 1 and not distributed and headline and not args.no_other_configs:
+    if args.full and rank == 0 and world == 1 and not distributed and headline and not args.no_other_configs:
         eng.close()                       # the headline engine's work is done: its 2 GB go back before the larger batches
         del images, probs
         torch.cuda.empty_cache()
@@ -669,7 +713,7 @@ def main() -> None:
             "data": "synthetic",
             "config": {"workload": workload_name(args.model, args.dtype, B, args.config or (4 if args.model != "b16" else (1 if args.dtype == "f32" else 2))),
                        "batch_per_gpu": B, "global_batch": B * world, "parallelism": f"dp{world}", "lanes_per_gpu": args.lanes,
-                       "top1_gather": ("rccl all_gather, 8 B per image" + ("" if gather_ok else " (MISMATCH)")) if distributed else None,
+                       "top1_gather": ("rccl all_gather, 8 B per image" + ("" if gather_ok is not False else " (MISMATCH)")) if distributed else None,
                        "gflop_per_image": round(gflop_img, 4), "prune_last_layer": bool(args.prune_last_layer), "ln_fold": args.ln_fold >= 0, "device": info["name"], "arch": info["arch"],
                        "compute_units": info["compute_units"], "clock_mhz": info["clock_mhz"]},
             "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "golden": gold, "c_surface": c_surface, "other_configs": others, "ok": ok,

@@ -17,6 +17,9 @@ real-weight run is impossible; these are the partial real-weight checks SURVEY.m
   head    real encoder.ln + heads.head (W148-W151, first HEAD_CLASSES classes):
             layer_norm -> linear_layer  (ViT_seq.c:429-435) on 8 seeded class rows (rows 0-7 of a 197-row seeded tensor).
 
+It also writes tests/golden/real_weights_manifest.json (file name, size and SHA-256 after rounding of each of the 116
+blobs).
+
 Inputs are regenerated from seeds by the tests (synth.uniform); the real tensors that are needed ARE stored (after
 the loader's 1e-6 rounding, Network.c:184-187, applied by THIS repo's load_weights -- asserted equal to round6(raw
 file) here), since the GPU box has no /root/reference.  Data only: tensors and outputs, no reference source.
@@ -24,7 +27,9 @@ file) here), since the GPU box has no /root/reference.  Data only: tensors and o
 from __future__ import annotations
 
 import glob
+import hashlib
 import importlib
+import json
 import os
 import sys
 
@@ -39,6 +44,7 @@ binding = importlib.import_module("vision-transformer-opencl_amd.binding")
 synth = pkg.synth
 NET = "/root/reference/Network"
 OUT = os.path.join(ROOT, "tests", "golden", "real_weights_b16.npz")
+MANIFEST = os.path.join(ROOT, "tests", "golden", "real_weights_manifest.json")
 
 SEED = 20260
 ROWS = [0, 1, 2, 3, 50, 99, 100, 150, 195, 196]
@@ -59,6 +65,42 @@ def activation_inputs(layer: int):
     return outlier_cols(a, [7, 300, 301, 640], 12.0), outlier_cols(x, [5, 381, 759], 30.0)
 
 
+def save_split(out: dict, path: str, small: int = 256 << 10, block: int = 768 << 10) -> None:
+    """np.savez_compressed(path, **out), with every array above `small` bytes cut into row blocks of at most `block`
+    bytes, one block per file <path stem>.partNN.npz under the key <name>.<block> (every committed file stays under
+    1 MiB); the tests put them back together (tests/test_real_weights.py: load_gold)."""
+    kept, blocks = {}, []
+    for k, a in out.items():
+        a = np.asarray(a)
+        if a.nbytes <= small:
+            kept[k] = a
+            continue
+        rows = max(1, block // (a.nbytes // a.shape[0]))
+        blocks += [(f"{k}.{j}", a[s:s + rows]) for j, s in enumerate(range(0, a.shape[0], rows))]
+    for old in glob.glob(path[:-len(".npz")] + ".part*.npz"):
+        os.remove(old)
+    np.savez_compressed(path, **kept)
+    for j, (k, a) in enumerate(blocks):
+        np.savez_compressed(f"{path[:-len('.npz')]}.part{j:02d}.npz", **{k: a})
+
+
+def sha256_f32(a: np.ndarray) -> str:
+    return hashlib.sha256(np.ascontiguousarray(a, np.float32).tobytes()).hexdigest()
+
+
+def write_manifest(W, present):
+    """tests/golden/real_weights_manifest.json: name, size and digest (after the loader's rounding) of every blob the
+    reference ships, so that tests can lay out a tree like it and check the stored tensors without the files."""
+    files = []
+    for i in present:
+        name = os.path.basename(glob.glob(os.path.join(NET, f"Weight_{i}_*.bin"))[0])
+        files.append({"index": i, "name": name, "floats": int(W[i].size), "round6_sha256": sha256_f32(W[i])})
+    head = W[150].reshape(1000, D)[:HEAD_CLASSES]
+    with open(MANIFEST, "w") as f:
+        json.dump({"files": files, "head_w_rows": HEAD_CLASSES, "head_w_rows_round6_sha256": sha256_f32(head)}, f, indent=1)
+        f.write("\n")
+
+
 def main():
     if not po.have_reference() or not os.path.isdir(NET):
         sys.exit("needs /root/reference/Network and oracle/_ref/libvitseq_ref.so (make -C oracle ref)")
@@ -76,6 +118,7 @@ def main():
         assert np.array_equal(W[i], po.round_weights(raw)), i
     missing = sorted(set(range(cfg.n_weights)) - set(present))
     assert all((i - 4) % 12 in (2, 8, 10) for i in missing)  # exactly the in_proj / fc1 / fc2 weights
+    write_manifest(W, present)
     ref = po.Reference()
     out = {"seed": SEED, "rows": np.array(ROWS), "head_classes": HEAD_CLASSES, "present": np.array(present)}
 
@@ -114,8 +157,8 @@ def main():
     zf = np.ascontiguousarray(ref.layer_norm(xf, lw, lb)[:8])
     out["ln_w"], out["ln_b"], out["head_w"], out["head_b"] = lw, lb, hw, hb
     out["final_ln"], out["head_logits"] = zf, ref.linear(zf, hw, hb)
-    np.savez_compressed(OUT, **out)
-    print("wrote", OUT, os.path.getsize(OUT) / 1e6, "MB")
+    save_split(out, OUT)
+    print("wrote", OUT, "and its .part*.npz blocks")
 
 
 if __name__ == "__main__":

@@ -222,12 +222,14 @@ def test_fp32_chunk_is_capped_below_2gib_per_launch():
     assert np.array_equal(got, want)
 
 
-def test_bench_rank_takes_the_rccl_path_at_world_size_one():
+def test_bench_rank_takes_the_rccl_path_at_world_size_one(tmp_path):
     """bench.py --spawn: the parent launches its rank (before touching the GPU), the rank initialises nccl (= RCCL),
-    all-gathers the packed top-1 records through dp.gather_packed on the forward's stream, and prints the JSON line."""
+    all-gathers the packed top-1 records through dp.gather_packed on the forward's stream, and prints the JSON line;
+    --dump-outputs writes the gathered records beside the rank's own."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "VIT_LAUNCH_CHILD")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--spawn", "--steps", "2", "--warmup", "1",
-                        "--batch", "16", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
+                        "--batch", "16", "--no-cpu-baseline", "--full", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -242,6 +244,8 @@ def test_bench_rank_takes_the_rccl_path_at_world_size_one():
     assert rec["roofline"]["gemm_handover"] is not None
     probe = rec["roofline"]["clock_limit_probe"]      # the dominant GEMM's shape on random and on all-zero operands
     assert probe["shape_mnk"] == [16 * 197, 768, 3072] and probe["random_operands_tflops"] > 0 and probe["zero_operands_tflops"] > 0
+    assert np.array_equal(np.load(tmp_path / "gathered_top1_label.npy"), np.load(tmp_path / "top1_label.npy")[None])
+    assert np.array_equal(np.load(tmp_path / "gathered_top1_prob.npy"), np.load(tmp_path / "top1_prob.npy")[None])
 
 
 def test_bench_config3_preset_is_bf16_2048_per_gpu():
@@ -249,7 +253,7 @@ def test_bench_config3_preset_is_bf16_2048_per_gpu():
     parity block too (2e-2, identical top-1), measured on the timed batch itself."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "VIT_LAUNCH_CHILD")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "3", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-c-surface"], capture_output=True, text=True, timeout=900, env=env)
+                        "--no-cpu-baseline", "--no-c-surface", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert rec["dtype"] == "bf16" and rec["config"]["batch_per_gpu"] == 2048 and "configs[3]" in rec["config"]["workload"]
@@ -261,12 +265,12 @@ def test_bench_config3_preset_is_bf16_2048_per_gpu():
 
 
 def test_bench_default_line_carries_the_other_single_gpu_configs():
-    """`python bench.py` as the driver runs it (N = 1, configs[1]) also times BASELINE.json configs[2] and configs[4] after the
+    """`python bench.py --full` (N = 1, configs[1]) also times BASELINE.json configs[2] and configs[4] after the
     headline's timed region and reports them under other_configs, each with its golden block: ViT-B/16 bf16 against the
     reference's own probabilities, ViT-L/16-384 bf16 against tests/golden/vit_l16_384_e2e.npz (2e-2, identical top-1)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "VIT_LAUNCH_CHILD")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                        "--no-c-surface", "--no-clock-probe"], capture_output=True, text=True, timeout=1200, env=env)
+                        "--no-c-surface", "--no-clock-probe", "--full"], capture_output=True, text=True, timeout=1200, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert rec["dtype"] == "f32" and rec["config"]["batch_per_gpu"] == 256 and rec["ok"] is True
@@ -277,6 +281,30 @@ def test_bench_default_line_carries_the_other_single_gpu_configs():
         assert o["dtype"] == "bf16" and o["value"] > 0 and o["ok"] is True
         assert o["golden"]["fixture"] == fixture and o["golden"]["top1_match"] and o["golden"]["max_abs_prob_err"] <= 2e-2
         assert 0 < o["roofline"]["frac"] < 1 and o["roofline"]["kernel"].startswith("gemm_bf16_pp_kernel")
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full) prints the headline fields and nothing that takes work of its own; --dump-outputs writes what
+    the last timed step returned.  The batch opens with the two golden images, so rows 0-1 of the dump must match
+    tests/golden/vit_b16_e2e.npz (1e-4, identical top-1), and the top-1 records must point at each row's maximum."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "VIT_LAUNCH_CHILD")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--batch", "16", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["dtype"] == "f32"
+    assert rec["unit"] == "images/sec" and rec["higher_is_better"] is True and rec["ok"] is True
+    assert abs(rec["value"] - 16 * 1e3 / rec["ms_per_step"]) <= 1e-2 * rec["value"]
+    assert all(rec[k] is None for k in ("roofline", "cpu_baseline", "parity", "golden", "c_surface", "other_configs"))
+    probs = np.load(tmp_path / "probs.npy")
+    label, p1 = np.load(tmp_path / "top1_label.npy"), np.load(tmp_path / "top1_prob.npy")
+    assert probs.dtype == np.float32 and probs.shape == (16, 1000)
+    assert label.dtype == np.float64 and p1.dtype == np.float32 and label.shape == p1.shape == (16,)
+    assert np.array_equal(probs[np.arange(16), label.astype(int)], p1) and np.array_equal(p1, probs.max(1))
+    g = np.load(os.path.join(ROOT, "tests", "golden", "vit_b16_e2e.npz"))
+    assert np.abs(probs[:2] - g["probs"]).max() <= 1e-4 and (probs[:2].argmax(1) == g["probs"].argmax(1)).all()
 
 
 @pytest.mark.parametrize("n_images", [6, 5])

@@ -13,7 +13,7 @@ import os
 import numpy as np
 import pytest
 
-from test_real_weights import GOLD, D, T, activation_inputs, head_input
+from test_real_weights import D, T, activation_inputs, head_input, load_gold
 from vit_amd import binding as B
 from vit_amd import synth
 
@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def g():
-    return np.load(GOLD)
+    return load_gold()
 
 
 def mag(a):

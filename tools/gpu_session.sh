@@ -6,8 +6,8 @@
 #   suite               python -m pytest tests -m gpu -x -q              -> gpu_suite.log
 #   pytest:<tag>:<expr> python -m pytest tests -m gpu -q -k <expr>                -> pytest_<tag>.log
 #   abtest:<tag>:<lib>:<expr>  the same tests against another build of the library, all failures listed -> pytest_<tag>.log
-#   bench               python bench.py (the driver's default line)       -> bench_default.json
-#   bench:<tag>:<args>  python bench.py <args> (',' separates arguments)  -> bench_<tag>.json
+#   bench               python bench.py --full (every object of the line) -> bench_default.json
+#   bench:<tag>:<args>  python bench.py --full <args> (',' separates arguments)  -> bench_<tag>.json
 #   sq:<tag>:<args>     SQ wait / issue counters of `bench.py <args>`     -> attn_issue_<tag>.csv (tools/sq_issue_summary.py)
 #   tool:<tag>:<script>[:<args>]   python tools/<script> <args>, product library     -> <tag>.log
 #   probe:<tag>:<script>[:<args>]  the same against libvit_mi355x_probe.so           -> <tag>.log
@@ -18,7 +18,7 @@ export TMPDIR=/tmp
 R=${VIT_ROUND:-r05}
 O=gpurun_out/$R
 mkdir -p "$O"
-QUIET="--no-cpu-baseline --no-c-surface --no-clock-probe --no-other-configs"
+QUIET="--full --no-cpu-baseline --no-c-surface --no-clock-probe --no-other-configs"
 SQ="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS"
 for step in "$@"; do
     IFS=: read -r kind tag a b c <<< "$step"
@@ -35,7 +35,7 @@ for step in "$@"; do
     bench)
         if [ -z "$tag" ]; then tag=default; fi
         # shellcheck disable=SC2086
-        timeout -k 10 500 python3 bench.py ${a//,/ } > "$O/bench_$tag.json" 2> "$O/bench_$tag.err"
+        timeout -k 10 500 python3 bench.py --full ${a//,/ } > "$O/bench_$tag.json" 2> "$O/bench_$tag.err"
         python3 - "$O/bench_$tag.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().split("\n")[-1])
