@@ -156,15 +156,27 @@ def test_vit_l_geometry_matches_oracle(oracle, cfg):
     eng.close()
 
 
-def test_stage_profile_counts_launches():
+@pytest.mark.parametrize("lanes", [1, 2], ids=["lanes1", "lanes2"])
+@pytest.mark.parametrize("prune", [False, True], ids=["full", "pruned"])
+@pytest.mark.parametrize("ln_fold", [-1, 0], ids=["nofold", "fold"])
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_stage_profile_counts_launches(dtype, ln_fold, prune, lanes):
+    """The launch list of every layer sequence (dtype x LayerNorm fold x pruned last layer), per stage: each stage is issued once
+    per lane; the pruned last layer adds a Q launch, and with the fold a gather of the class rows' statistics (LN)."""
     cfg = synth.VIT_TINY
-    eng = B.Engine(cfg, max_batch=4, profile=True)
+    eng = B.Engine(cfg, max_batch=4, profile=True, dtype=dtype, ln_fold=ln_fold, prune_last_layer=prune, lanes=lanes)
     eng.load_weights(synth.make_weights(cfg, 3))
     eng.forward(synth.make_images(cfg, 4, 1))
     t = eng.stage_times()
     assert t["images"] == 4
-    assert t["stages"]["fc1"]["launches"] == cfg.depth
-    assert t["stages"]["ln"]["launches"] == 2 * cfg.depth + 1
+    if (dtype, ln_fold, prune, lanes) == ("f32", 0, False, 1):  # the default engine
+        assert t["stages"]["fc1"]["launches"] == cfg.depth
+        assert t["stages"]["ln"]["launches"] == 2 * cfg.depth + 1
+    fold = ln_fold >= 0  # VIT_TINY meets the fold's shape rules in both dtypes
+    d = cfg.depth
+    per_lane = {"embed": 1, "ln": 2 * d + 1 + (prune and fold), "qkv": d + prune, "attn": d, "outproj": d, "fc1": d,
+                "fc2": d, "head": 1, "softmax": 1}
+    assert {s: v["launches"] for s, v in t["stages"].items()} == {s: lanes * k for s, k in per_lane.items()}
     assert all(v["ms"] >= 0 for v in t["stages"].values())
     eng.close()
 

@@ -498,111 +498,65 @@ static int stage_end(vit_engine *e, vithip_stream_t s) {
     return rc;
 }
 
-static int gemm(vit_engine *e, vithip_stream_t s, int stage, const float *A, int lda, const float *W,
-                const float *bias, const float *res, float *C, int ldc, int M, int N, int K, int epi) {
-    vithip_gemm_args a;
-    memset(&a, 0, sizeof(a));
-    /* the lane's workspace: launches on one stream are ordered, which is what sharing it needs.  Lane 0 runs on the caller's
-     * stream (whatever it is), lane j on aux_stream[j - 1]. */
-    a.workspace = e->gemm_ws[0];
-    for (int j = 0; j < VIT_MAX_LANES - 1; ++j)
-        if (s == e->aux_stream[j]) a.workspace = e->gemm_ws[j + 1];
-    a.handover_test = e->opt.gemm_handover_test;
-    a.A = A; a.lda = lda; a.W = W; a.ldw = K; a.bias = bias; a.residual = res; a.ldr = ldc;
-    a.C = C; a.ldc = ldc; a.M = M; a.N = N; a.K = K; a.epilogue = epi;
-    a.tile = e->opt.gemm_tile; a.group_m = 0;
-    HIP_TRY(e, stage_begin(e, s, stage));
-    HIP_TRY(e, vithip_gemm_f32(s, &a));
-    HIP_TRY(e, stage_end(e, s));
-    return VIT_OK;
-}
+/* One GEMM of the forward: fp32 operands, or bf16 ones (the encoder layers of a bf16 engine; C of the residual role stays fp32).
+ * The residual role adds in place: C += A . W^T + bias.  ln_rows makes it the consumer of the LayerNorm fold: A holds the
+ * un-normalised rows, W / bias the folded operands, ln_rows a pair per row of A -- fp32 (rstd, mean), bf16 (rstd, mean*rstd).
+ * stats_rows makes a residual GEMM the producer, which leaves the pairs of the rows it stored in stats_rows:
+ *   bf16: always -- its epilogue stores bf16(C) to x16 and the row sums to stats_part, and one small launch (accounted to the
+ *         LayerNorm stage) turns them into the pairs;
+ *   fp32: when its kernel can take the sums in its epilogue (the persistent walk: large batches); otherwise the caller runs the
+ *         statistics pass, so that small batches keep their launch list and the stage profile its meaning.
+ * *stats_ready (optional) says whether it left them. */
+typedef struct {
+    int stage, bf16;
+    const void *A; int lda;
+    const void *W; const float *bias;  /* W [N][K] */
+    void *C; int ldc;
+    int M, N, K;
+    int role;                          /* VITHIP_EPI_BIAS, VITHIP_EPI_BIAS_GELU or VITHIP_EPI_BIAS_RESIDUAL */
+    const float *ln_rows, *ln_colsum;  /* consumer; ln_colsum = column sums of W, NULL for the centred fp32 weights */
+    float *stats_rows, *stats_part;    /* producer */
+    unsigned short *x16;               /* bf16 producer: the bf16 copy of C, leading dimension ldc */
+} gemm_desc;
 
-/* fp32 consumer of the LayerNorm fold: A = the un-normalised rows x, Wf / bias_f / colsum the folded operands, rows = (rstd,
- * mean) per row of A (vithip_gemm_args.ln_rows) */
-static int gemm_fold(vit_engine *e, vithip_stream_t s, int stage, const float *A, int lda, const float *Wf, const float *bias_f,
-                     const float *colsum, const float *rows, float *C, int ldc, int M, int N, int K, int epi) {
-    vithip_gemm_args a;
-    memset(&a, 0, sizeof(a));
-    a.workspace = e->gemm_ws[0];
-    for (int j = 0; j < VIT_MAX_LANES - 1; ++j)
-        if (s == e->aux_stream[j]) a.workspace = e->gemm_ws[j + 1];
-    a.handover_test = e->opt.gemm_handover_test;
-    a.A = A; a.lda = lda; a.W = Wf; a.ldw = K; a.bias = bias_f; a.C = C; a.ldc = ldc; a.M = M; a.N = N; a.K = K; a.epilogue = epi;
-    a.tile = e->opt.gemm_tile; a.group_m = 0;
-    (void)colsum; /* the engine's fp32 weights are the CENTRED ones (vit_engine_load_weights): nothing to subtract in the epilogue */
-    a.ln_rows = rows; a.ln_colsum = NULL;
-    HIP_TRY(e, stage_begin(e, s, stage));
-    HIP_TRY(e, vithip_gemm_f32(s, &a));
+static int gemm(vit_engine *e, vithip_stream_t s, const gemm_desc *g, int *stats_ready) {
+    const float *res = g->role == VITHIP_EPI_BIAS_RESIDUAL ? (const float *)g->C : NULL;
+    const int ldr = g->ln_rows ? 0 : g->ldc; /* read by the residual epilogue only; the fold's consumers pass 0 */
+    int ready;
+    HIP_TRY(e, stage_begin(e, s, g->stage));
+    if (g->bf16) {
+        static const int epi16[] = {[VITHIP_EPI_BIAS] = VITHIP_BF16_EPI_BF16, [VITHIP_EPI_BIAS_GELU] = VITHIP_BF16_EPI_BF16_GELU,
+                                    [VITHIP_EPI_BIAS_RESIDUAL] = VITHIP_BF16_EPI_F32_RESIDUAL};
+        vithip_gemm_bf16_args a;
+        memset(&a, 0, sizeof(a));
+        a.A = g->A; a.lda = g->lda; a.W = g->W; a.ldw = g->K; a.bias = g->bias; a.residual = res; a.ldr = ldr;
+        a.C = g->C; a.ldc = g->ldc; a.M = g->M; a.N = g->N; a.K = g->K; a.epilogue = epi16[g->role];
+        a.ln_rows = g->ln_rows; a.ln_colsum = g->ln_colsum;
+        if ((ready = g->stats_rows != NULL)) { a.x16 = g->x16; a.ldx16 = g->ldc; a.row_partials = g->stats_part; }
+        HIP_TRY(e, vithip_gemm_bf16(s, &a));
+    } else {
+        vithip_gemm_args a;
+        memset(&a, 0, sizeof(a));
+        /* the lane's workspace: launches on one stream are ordered, which is what sharing it needs.  Lane 0 runs on the caller's
+         * stream (whatever it is), lane j on aux_stream[j - 1]. */
+        a.workspace = e->gemm_ws[0];
+        for (int j = 0; j < VIT_MAX_LANES - 1; ++j)
+            if (s == e->aux_stream[j]) a.workspace = e->gemm_ws[j + 1];
+        a.handover_test = e->opt.gemm_handover_test; a.tile = e->opt.gemm_tile;
+        a.A = g->A; a.lda = g->lda; a.W = g->W; a.ldw = g->K; a.bias = g->bias; a.residual = res; a.ldr = ldr;
+        a.C = g->C; a.ldc = g->ldc; a.M = g->M; a.N = g->N; a.K = g->K; a.epilogue = g->role;
+        a.ln_rows = g->ln_rows; a.ln_colsum = g->ln_colsum;
+        a.stats_out = g->stats_rows; a.stats_partials = g->stats_part;
+        if (!(ready = vithip_gemm_f32_stats_in_epilogue(&a))) a.stats_out = a.stats_partials = NULL;
+        HIP_TRY(e, vithip_gemm_f32(s, &a));
+    }
     HIP_TRY(e, stage_end(e, s));
-    return VIT_OK;
-}
-/* fp32 residual GEMM in place (x += A . W^T + b) that also leaves the (rstd, mean) of the rows it stored in `rows` WHEN its
- * kernel can take the sums in its epilogue (the persistent walk: large batches); *took says whether it did -- otherwise the
- * caller runs the statistics pass (rowstats32), so that small batches keep their launch list and the stage profile its meaning */
-static int gemm_res_stats(vit_engine *e, vithip_stream_t s, int stage, const float *A, int lda, const float *W, const float *bias,
-                          float *x, int ldx, int M, int N, int K, float *rows, float *partials, int *took) {
-    vithip_gemm_args a;
-    memset(&a, 0, sizeof(a));
-    a.workspace = e->gemm_ws[0];
-    for (int j = 0; j < VIT_MAX_LANES - 1; ++j)
-        if (s == e->aux_stream[j]) a.workspace = e->gemm_ws[j + 1];
-    a.handover_test = e->opt.gemm_handover_test;
-    a.A = A; a.lda = lda; a.W = W; a.ldw = K; a.bias = bias; a.residual = x; a.ldr = ldx; a.C = x; a.ldc = ldx;
-    a.M = M; a.N = N; a.K = K; a.epilogue = VITHIP_EPI_BIAS_RESIDUAL; a.tile = e->opt.gemm_tile;
-    a.stats_out = rows; a.stats_partials = partials;
-    *took = rows != NULL && vithip_gemm_f32_stats_in_epilogue(&a);
-    if (!*took) a.stats_out = a.stats_partials = NULL;
-    HIP_TRY(e, stage_begin(e, s, stage));
-    HIP_TRY(e, vithip_gemm_f32(s, &a));
-    HIP_TRY(e, stage_end(e, s));
-    return VIT_OK;
-}
-static int rowstats32(vit_engine *e, vithip_stream_t s, const float *x, size_t ldx, float *rows, int n_rows, int D) {
-    HIP_TRY(e, stage_begin(e, s, VIT_STAGE_LN));
-    HIP_TRY(e, vithip_rowstats_f32(s, x, ldx, rows, n_rows, D));
-    HIP_TRY(e, stage_end(e, s));
-    return VIT_OK;
-}
-
-static int gemm16(vit_engine *e, vithip_stream_t s, int stage, const unsigned short *A, int lda, const unsigned short *W,
-                  const float *bias, const float *res, void *C, int ldc, int M, int N, int K, int epi) {
-    vithip_gemm_bf16_args a;
-    memset(&a, 0, sizeof(a));
-    a.A = A; a.lda = lda; a.W = W; a.ldw = K; a.bias = bias; a.residual = res; a.ldr = ldc;
-    a.C = C; a.ldc = ldc; a.M = M; a.N = N; a.K = K; a.epilogue = epi;
-    HIP_TRY(e, stage_begin(e, s, stage));
-    HIP_TRY(e, vithip_gemm_bf16(s, &a));
-    HIP_TRY(e, stage_end(e, s));
-    return VIT_OK;
-}
-
-/* The two GEMM roles of the LayerNorm fold (contiguous rows only).  Consumer: A = un-normalised bf16 rows, W / bias / colsum = the
- * folded operands, rows = (rstd, mean*rstd) per row.  Producer: the residual GEMM also stores bf16(x) and the row sums, which
- * one small launch turns into `rows` for the consumer behind it (accounted to the LayerNorm stage). */
-static int gemm16_ln(vit_engine *e, vithip_stream_t s, int stage, const unsigned short *A, int lda, const unsigned short *Wf,
-                     const float *bias_f, const float *colsum, const float *rows, unsigned short *C, int ldc, int M, int N, int K, int epi) {
-    vithip_gemm_bf16_args a;
-    memset(&a, 0, sizeof(a));
-    a.A = A; a.lda = lda; a.W = Wf; a.ldw = K; a.bias = bias_f; a.C = C; a.ldc = ldc; a.M = M; a.N = N; a.K = K; a.epilogue = epi;
-    a.ln_rows = rows; a.ln_colsum = colsum;
-    HIP_TRY(e, stage_begin(e, s, stage));
-    HIP_TRY(e, vithip_gemm_bf16(s, &a));
-    HIP_TRY(e, stage_end(e, s));
-    return VIT_OK;
-}
-static int gemm16_res_stats(vit_engine *e, vithip_stream_t s, int stage, const unsigned short *A, int lda, const unsigned short *W,
-                            const float *bias, float *x, unsigned short *x16, int ldx, float *partials, float *rows, int M, int N, int K) {
-    vithip_gemm_bf16_args a;
-    memset(&a, 0, sizeof(a));
-    a.A = A; a.lda = lda; a.W = W; a.ldw = K; a.bias = bias; a.residual = x; a.ldr = ldx; a.C = x; a.ldc = ldx;
-    a.M = M; a.N = N; a.K = K; a.epilogue = VITHIP_BF16_EPI_F32_RESIDUAL;
-    a.x16 = x16; a.ldx16 = ldx; a.row_partials = partials;
-    HIP_TRY(e, stage_begin(e, s, stage));
-    HIP_TRY(e, vithip_gemm_bf16(s, &a));
-    HIP_TRY(e, stage_end(e, s));
-    HIP_TRY(e, stage_begin(e, s, VIT_STAGE_LN));
-    HIP_TRY(e, vithip_rowstats_finalize(s, partials, vithip_ln_strips(N), M, N, rows));
-    HIP_TRY(e, stage_end(e, s));
+    if (g->bf16 && ready) {
+        HIP_TRY(e, stage_begin(e, s, VIT_STAGE_LN));
+        HIP_TRY(e, vithip_rowstats_finalize(s, g->stats_part, vithip_ln_strips(g->N), g->M, g->N, g->stats_rows));
+        HIP_TRY(e, stage_end(e, s));
+    }
+    if (stats_ready) *stats_ready = ready;
     return VIT_OK;
 }
 
@@ -631,14 +585,21 @@ static int collect_profile(vit_engine *e) {
  * one lane run beside the other lane's GEMMs.  Launches are issued stage by stage across the lanes so
  * that the queues advance together.
  *
- * The layer loop picks ONE of six layer bodies (fp32 / bf16 with LayerNorm kernels / bf16 with the
- * LayerNorm fold, each in its full and its class-rows-only "pruned last layer" form); every body is a
- * sequence of stages, each stage issued for every lane.
+ * Every encoder layer runs the one step sequence of encoder_layer(), whatever the dtype, the LayerNorm
+ * fold and the class-rows-only "pruned last layer"; each step is issued for every lane.
  */
 typedef struct {
     vithip_stream_t s;
     int off, n; /* first image of the lane inside the chunk, image count */
-    int stats_ready; /* fp32 fold: the residual GEMM in front has left the (rstd, mean) of the lane's token rows (its epilogue took the sums) */
+    int stats_ready; /* fold: the residual GEMM in front has left the pairs of the lane's token rows (see gemm()) */
+    /* the lane's rows of the activation buffers, from its first token row (off * T) on; bf16 activations fill the fp32-sized
+     * allocations of y, qkv and hbuf from their start */
+    float *x;
+    void *y, *qkv, *h;
+    /* LayerNorm fold (NULL without it): the rows in_proj and fc1 read (x itself, or its bf16 copy), the pairs of the token rows
+     * and of the class rows, the residual GEMMs' partial sums */
+    void *xa;
+    float *tok_pairs, *cls_pairs, *partials;
 } vit_lane;
 
 typedef struct {
@@ -646,20 +607,12 @@ typedef struct {
     vit_lane lane[VIT_MAX_LANES];
     int L;                       /* lanes in use for this chunk */
     int T, D, H, NC;
-    /* bf16 views of the activation buffers (bf16 activations half fill the fp32-sized allocations) */
-    unsigned short *y16, *qkv16, *h16;
-    /* LayerNorm fold scratch, in the idle halves: bf16 copy of x (y allocation); row sums, (rstd, mean*rstd) pairs per token
-     * and -- pruned last layer -- per class row (qkv allocation).  A lane uses its own rows of each. */
-    unsigned short *x16;
-    float *ln_part, *ln_rows, *cls_rows;
-    int strips;
 } chunk_ctx;
 
-#define LANES for (int j = 0; j < c->L; ++j)
-#define LN_ (c->lane[j])
-#define ROWS(j) ((size_t)c->lane[j].off * c->T)
-#define PART(j) (c->ln_part + ROWS(j) * (size_t)c->strips * 2)
 #define RUN(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
+
+/* element i of an array of esz-byte elements */
+static void *at(const void *p, size_t i, size_t esz) { return (char *)p + i * esz; }
 
 /* conv_proj + flatten_transpose + class_token + pos_emb (ViT_seq.c:25-101) */
 static int stage_embed(chunk_ctx *c, const float *d_images) {
@@ -672,267 +625,144 @@ static int stage_embed(chunk_ctx *c, const float *d_images) {
     const int pk = cfg->in_chans * cfg->patch_size * cfg->patch_size;
     const int embed16 = e->opt.dtype == VIT_DTYPE_BF16 && pk % 64 == 0 && pk >= 128 && cfg->patch_size % 8 == 0 &&
                         (size_t)pk <= 2 * (size_t)c->H;
-    LANES {
-        HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_EMBED));
+    for (int j = 0; j < c->L; ++j) {
+        const vit_lane *ln = &c->lane[j];
+        HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_EMBED));
         if (embed16)
-            HIP_TRY(e, vithip_patch_embed_bf16(LN_.s, d_images + LN_.off * img, e->w16[1], w[2], w[0], w[3],
-                                               e->x + ROWS(j) * c->D, (unsigned short *)e->hbuf + (size_t)LN_.off * (c->T - 1) * pk,
-                                               LN_.n, cfg->img_size, cfg->patch_size, cfg->in_chans, c->D));
+            HIP_TRY(e, vithip_patch_embed_bf16(ln->s, d_images + ln->off * img, e->w16[1], w[2], w[0], w[3], ln->x,
+                                               (unsigned short *)e->hbuf + (size_t)ln->off * (c->T - 1) * pk,
+                                               ln->n, cfg->img_size, cfg->patch_size, cfg->in_chans, c->D));
         else
-            HIP_TRY(e, vithip_patch_embed_f32(LN_.s, d_images + LN_.off * img, w[1], w[2], w[0], w[3],
-                                              e->x + ROWS(j) * c->D, LN_.n, cfg->img_size, cfg->patch_size, cfg->in_chans, c->D));
-        HIP_TRY(e, stage_end(e, LN_.s));
+            HIP_TRY(e, vithip_patch_embed_f32(ln->s, d_images + ln->off * img, w[1], w[2], w[0], w[3], ln->x, ln->n,
+                                              cfg->img_size, cfg->patch_size, cfg->in_chans, c->D));
+        HIP_TRY(e, stage_end(e, ln->s));
     }
     return VIT_OK;
 }
 
-/* ---- fp32 layer (the reference's arithmetic, ViT_seq.c:276-300) ---- */
-static int layer_f32(chunk_ctx *c, float **lw) {
+/* LayerNorm (ViT_seq.c:103-121) of `rows` rows of x into y (bf16 on bf16 engines) */
+static int layernorm(chunk_ctx *c, vithip_stream_t s, const float *x, size_t ldx, void *y, size_t ldy, const float *gamma,
+                     const float *beta, int rows) {
     vit_engine *e = c->e;
-    const int T = c->T, D = c->D, H = c->H, heads = e->cfg.num_heads;
-    LANES { /* LN1 (ViT_seq.c:281) */
-        HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_LN));
-        HIP_TRY(e, vithip_layernorm_f32(LN_.s, e->x + ROWS(j) * D, (size_t)D, e->y + ROWS(j) * D, (size_t)D, lw[0], lw[1], LN_.n * T, D));
-        HIP_TRY(e, stage_end(e, LN_.s));
-    }
-    LANES /* QKV in_proj (ViT_seq.c:134-147) */
-        RUN(gemm(e, LN_.s, VIT_STAGE_QKV, e->y + ROWS(j) * D, D, lw[2], lw[3], NULL, e->qkv + ROWS(j) * 3 * D, 3 * D, LN_.n * T, 3 * D, D, VITHIP_EPI_BIAS));
-    LANES { /* scores, softmax, P.V (ViT_seq.c:156-215) -> y */
-        HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_ATTN));
-        HIP_TRY(e, vithip_attention_f32(LN_.s, e->qkv + ROWS(j) * 3 * D, e->y + ROWS(j) * D, LN_.n, T, heads));
-        HIP_TRY(e, stage_end(e, LN_.s));
-    }
-    LANES /* out_proj + residual (ViT_seq.c:219-227,286-288): x = x + (y.Wo^T + bo) */
-        RUN(gemm(e, LN_.s, VIT_STAGE_OUTPROJ, e->y + ROWS(j) * D, D, lw[4], lw[5], e->x + ROWS(j) * D, e->x + ROWS(j) * D, D, LN_.n * T, D, D, VITHIP_EPI_BIAS_RESIDUAL));
-    LANES { /* LN2 (ViT_seq.c:291) */
-        HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_LN));
-        HIP_TRY(e, vithip_layernorm_f32(LN_.s, e->x + ROWS(j) * D, (size_t)D, e->y + ROWS(j) * D, (size_t)D, lw[6], lw[7], LN_.n * T, D));
-        HIP_TRY(e, stage_end(e, LN_.s));
-    }
-    LANES /* fc1 + GELU (ViT_seq.c:258-264) */
-        RUN(gemm(e, LN_.s, VIT_STAGE_FC1, e->y + ROWS(j) * D, D, lw[8], lw[9], NULL, e->hbuf + ROWS(j) * H, H, LN_.n * T, H, D, VITHIP_EPI_BIAS_GELU));
-    LANES /* fc2 + residual (ViT_seq.c:266,297-299): x = x + (h.W2^T + b2) */
-        RUN(gemm(e, LN_.s, VIT_STAGE_FC2, e->hbuf + ROWS(j) * H, H, lw[10], lw[11], e->x + ROWS(j) * D, e->x + ROWS(j) * D, D, LN_.n * T, D, H, VITHIP_EPI_BIAS_RESIDUAL));
+    HIP_TRY(e, stage_begin(e, s, VIT_STAGE_LN));
+    if (e->opt.dtype == VIT_DTYPE_BF16) HIP_TRY(e, vithip_layernorm_f32_bf16out(s, x, ldx, y, ldy, gamma, beta, rows, c->D));
+    else HIP_TRY(e, vithip_layernorm_f32(s, x, ldx, y, ldy, gamma, beta, rows, c->D));
+    HIP_TRY(e, stage_end(e, s));
     return VIT_OK;
 }
 
-/* prune_last_layer (vit_engine_options): K and V of every token, everything else for the class rows only.  The class rows of a
- * [n*T][D] buffer are rows 0, T, 2T, ... = a matrix with leading dimension T*D, which every operator takes as it is. */
-static int layer_f32_pruned(chunk_ctx *c, float **lw) {
+/* the fold's statistics pass over `rows` rows of the lane's x (leading dimension ldx): a pair per row into `pairs`; bf16 engines
+ * also write the bf16 copy of the rows, which the consumers read */
+static int row_stats(chunk_ctx *c, const vit_lane *ln, size_t ldx, float *pairs, int rows) {
     vit_engine *e = c->e;
-    const int T = c->T, D = c->D, H = c->H, heads = e->cfg.num_heads;
-    LANES {
-        HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_LN));
-        HIP_TRY(e, vithip_layernorm_f32(LN_.s, e->x + ROWS(j) * D, (size_t)D, e->y + ROWS(j) * D, (size_t)D, lw[0], lw[1], LN_.n * T, D));
-        HIP_TRY(e, stage_end(e, LN_.s));
-    }
-    LANES { /* K and V of every token (in_proj rows D..3D), Q of the class rows only */
-        RUN(gemm(e, LN_.s, VIT_STAGE_QKV, e->y + ROWS(j) * D, D, lw[2] + (size_t)D * D, lw[3] + D, NULL, e->qkv + ROWS(j) * 3 * D + D, 3 * D, LN_.n * T, 2 * D, D, VITHIP_EPI_BIAS));
-        RUN(gemm(e, LN_.s, VIT_STAGE_QKV, e->y + ROWS(j) * D, T * D, lw[2], lw[3], NULL, e->qkv + ROWS(j) * 3 * D, T * 3 * D, LN_.n, D, D, VITHIP_EPI_BIAS));
-    }
-    LANES {
-        HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_ATTN));
-        HIP_TRY(e, vithip_attention_f32_rows(LN_.s, e->qkv + ROWS(j) * 3 * D, e->y + ROWS(j) * D, LN_.n, T, heads, 1));
-        HIP_TRY(e, stage_end(e, LN_.s));
-    }
-    LANES
-        RUN(gemm(e, LN_.s, VIT_STAGE_OUTPROJ, e->y + ROWS(j) * D, T * D, lw[4], lw[5], e->x + ROWS(j) * D, e->x + ROWS(j) * D, T * D, LN_.n, D, D, VITHIP_EPI_BIAS_RESIDUAL));
-    LANES { /* LN2 of the class rows -> compact [n][D] at the head of the lane's y region */
-        HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_LN));
-        HIP_TRY(e, vithip_layernorm_f32(LN_.s, e->x + ROWS(j) * D, (size_t)T * D, e->y + ROWS(j) * D, (size_t)D, lw[6], lw[7], LN_.n, D));
-        HIP_TRY(e, stage_end(e, LN_.s));
-    }
-    LANES
-        RUN(gemm(e, LN_.s, VIT_STAGE_FC1, e->y + ROWS(j) * D, D, lw[8], lw[9], NULL, e->hbuf + ROWS(j) * H, H, LN_.n, H, D, VITHIP_EPI_BIAS_GELU));
-    LANES
-        RUN(gemm(e, LN_.s, VIT_STAGE_FC2, e->hbuf + ROWS(j) * H, H, lw[10], lw[11], e->x + ROWS(j) * D, e->x + ROWS(j) * D, T * D, LN_.n, D, H, VITHIP_EPI_BIAS_RESIDUAL));
+    HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
+    if (e->opt.dtype == VIT_DTYPE_BF16) HIP_TRY(e, vithip_rowstats_bf16(ln->s, ln->x, ldx, ln->xa, ldx, pairs, rows, c->D));
+    else HIP_TRY(e, vithip_rowstats_f32(ln->s, ln->x, ldx, pairs, rows, c->D));
+    HIP_TRY(e, stage_end(e, ln->s));
     return VIT_OK;
 }
 
-/* ---- fp32 layer with the LayerNorm fold (vit_hip_kernels.h, vithip_gemm_args.ln_rows): in_proj and fc1 read the raw rows x with
- * the gamma/beta-folded operands (f32 / ff) and the rows' (rstd, mean); each LayerNorm (ViT_seq.c:281, 291) is one pass
- * that reads x and writes 8 bytes per row.  R32(j) = the pairs of lane j's token rows, C32(j) = of its class rows. ---- */
-#define R32(j) (e->ln_rows32 + ROWS(j) * 2)
-#define C32(j) (e->ln_rows32 + ((size_t)e->opt.max_batch * c->T + (size_t)c->lane[j].off) * 2)
-#define P32(j) (e->ln_part32 + ROWS(j) * (size_t)(c->D / 64) * 2)
-static int layer_f32_folded(chunk_ctx *c, float **lw, const float *f32, const float *ff, int feeds_next) {
+/*
+ * Encoder layer l (ViT_seq.c:276-300): LN1 -> QKV in_proj -> attention -> out_proj + residual -> LN2 -> fc1 + GELU -> fc2 +
+ * residual, each step issued for every lane before the next one starts.  What varies is where rows are and which kernel runs:
+ *   dtype   bf16 engines keep the LN output, qkv, the attention output and the MLP hidden layer in bf16; the residual stream x,
+ *           the LayerNorm statistics, softmax and every accumulation stay fp32.
+ *   fold    the LayerNorm fold (vit_hip_kernels.h, "LayerNorm folding"): in_proj and fc1 read the raw rows (x, or its bf16 copy)
+ *           with the gamma/beta-folded operands (fold_ln_weights) and a pair per row; a LayerNorm becomes a statistics pass,
+ *           or nothing where the residual GEMM in front has left the pairs.  The bf16 Q rows carry the scores' exponent factor.
+ *   pruned  prune_last_layer: K and V of every token, everything else for the class rows only.  The class rows of a [n*T][w]
+ *           buffer are rows 0, T, 2T, ... = a matrix with leading dimension T*w, which every operator takes as it is.
+ */
+static int encoder_layer(chunk_ctx *c, int l) {
     vit_engine *e = c->e;
     const int T = c->T, D = c->D, H = c->H, heads = e->cfg.num_heads;
-    int ln2_ready[VIT_MAX_LANES];
-    LANES /* LN1 (ViT_seq.c:281): its statistics, unless the fc2 in front has left them */
-        if (!LN_.stats_ready) RUN(rowstats32(e, LN_.s, e->x + ROWS(j) * D, (size_t)D, R32(j), LN_.n * T, D));
-    LANES /* QKV in_proj (ViT_seq.c:134-147) on LN1(x) */
-        RUN(gemm_fold(e, LN_.s, VIT_STAGE_QKV, e->x + ROWS(j) * D, D, f32, ff + 3 * D, ff, R32(j), e->qkv + ROWS(j) * 3 * D, 3 * D, LN_.n * T, 3 * D, D, VITHIP_EPI_BIAS));
-    LANES { /* scores, softmax, P.V (ViT_seq.c:156-215) -> y */
-        HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_ATTN));
-        HIP_TRY(e, vithip_attention_f32(LN_.s, e->qkv + ROWS(j) * 3 * D, e->y + ROWS(j) * D, LN_.n, T, heads));
-        HIP_TRY(e, stage_end(e, LN_.s));
+    const int bf16 = e->opt.dtype == VIT_DTYPE_BF16, fold = e->fold, feeds_next = l + 1 < e->cfg.depth;
+    const int pruned = e->opt.prune_last_layer && T <= 224 && !feeds_next;
+    const size_t esz = bf16 ? sizeof(unsigned short) : sizeof(float); /* GEMM weights and activations */
+    float **lw = e->w + 4 + VIT_WEIGHTS_PER_LAYER * l;
+    unsigned short **lw16 = e->w16 + 4 + VIT_WEIGHTS_PER_LAYER * l;
+    const void *w_qkv = bf16 ? (const void *)lw16[2] : lw[2], *w_out = bf16 ? (const void *)lw16[4] : lw[4],
+               *w_fc1 = bf16 ? (const void *)lw16[8] : lw[8], *w_fc2 = bf16 ? (const void *)lw16[10] : lw[10];
+    const float *b_qkv = lw[3], *b_fc1 = lw[9], *cs_qkv = NULL, *cs_fc1 = NULL;
+    if (fold) { /* the folded in_proj and fc1 (fold_ln_weights) */
+        const size_t wl = (size_t)l * (3 * (size_t)D * D + (size_t)H * D);
+        const float *ff = e->wfoldf + (size_t)l * (6 * D + 2 * H);
+        w_qkv = bf16 ? (const void *)(e->wfold16 + wl) : (const void *)(e->wfold32 + wl);
+        w_fc1 = at(w_qkv, 3 * (size_t)D * D, esz);
+        b_qkv = ff + 3 * D; b_fc1 = ff + 6 * D + H;
+        if (bf16) { cs_qkv = ff; cs_fc1 = ff + 6 * D; } /* the fp32 weights are centred: nothing to subtract */
     }
-    LANES /* out_proj + residual (ViT_seq.c:219-227,286-288); the statistics of LN2 (ViT_seq.c:291) on the way when the kernel can */
-        RUN(gemm_res_stats(e, LN_.s, VIT_STAGE_OUTPROJ, e->y + ROWS(j) * D, D, lw[4], lw[5], e->x + ROWS(j) * D, D, LN_.n * T, D, D, R32(j), P32(j), &ln2_ready[j]));
-    LANES
-        if (!ln2_ready[j]) RUN(rowstats32(e, LN_.s, e->x + ROWS(j) * D, (size_t)D, R32(j), LN_.n * T, D));
-    LANES /* fc1 + GELU (ViT_seq.c:258-264) on LN2(x) */
-        RUN(gemm_fold(e, LN_.s, VIT_STAGE_FC1, e->x + ROWS(j) * D, D, f32 + (size_t)3 * D * D, ff + 6 * D + H, ff + 6 * D, R32(j), e->hbuf + ROWS(j) * H, H, LN_.n * T, H, D, VITHIP_EPI_BIAS_GELU));
-    LANES /* fc2 + residual (ViT_seq.c:266,297-299); the statistics of the next layer's LN1 on the way when there is one */
-        RUN(gemm_res_stats(e, LN_.s, VIT_STAGE_FC2, e->hbuf + ROWS(j) * H, H, lw[10], lw[11], e->x + ROWS(j) * D, D, LN_.n * T, D, H,
-                           feeds_next ? R32(j) : NULL, P32(j), &LN_.stats_ready));
-    return VIT_OK;
-}
+    /* the rows the layer computes past K and V: every token row, or the class rows (row step T); and their pairs (fold) */
+    const int r = pruned ? T : 1;
+    int rows[VIT_MAX_LANES], ln2_ready[VIT_MAX_LANES];
+    float *pairs[VIT_MAX_LANES];
+    for (int j = 0; j < c->L; ++j) {
+        rows[j] = pruned ? c->lane[j].n : c->lane[j].n * T;
+        pairs[j] = pruned ? c->lane[j].cls_pairs : c->lane[j].tok_pairs;
+    }
 
-/* the sequence of layer_f32_pruned in folded form: class rows = rows 0, T, 2T, ... */
-static int layer_f32_folded_pruned(chunk_ctx *c, float **lw, const float *f32, const float *ff) {
-    vit_engine *e = c->e;
-    const int T = c->T, D = c->D, H = c->H, heads = e->cfg.num_heads;
-    LANES
-        if (!LN_.stats_ready) RUN(rowstats32(e, LN_.s, e->x + ROWS(j) * D, (size_t)D, R32(j), LN_.n * T, D));
-    LANES { /* K and V of every token (folded in_proj rows D..3D); Q of the class rows, whose pairs are made compact first */
-        RUN(gemm_fold(e, LN_.s, VIT_STAGE_QKV, e->x + ROWS(j) * D, D, f32 + (size_t)D * D, ff + 3 * D + D, ff + D, R32(j), e->qkv + ROWS(j) * 3 * D + D, 3 * D, LN_.n * T, 2 * D, D, VITHIP_EPI_BIAS));
-        HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_LN));
-        HIP_TRY(e, vithip_gather_rows_f32(LN_.s, R32(j), (size_t)2 * T, C32(j), 2, LN_.n, 2));
-        HIP_TRY(e, stage_end(e, LN_.s));
-        RUN(gemm_fold(e, LN_.s, VIT_STAGE_QKV, e->x + ROWS(j) * D, T * D, f32, ff + 3 * D, ff, C32(j), e->qkv + ROWS(j) * 3 * D, T * 3 * D, LN_.n, D, D, VITHIP_EPI_BIAS));
+    for (int j = 0; j < c->L; ++j) { /* LN1 (ViT_seq.c:281); folded: its statistics, unless the fc2 in front has left them */
+        vit_lane *ln = &c->lane[j];
+        if (!fold) RUN(layernorm(c, ln->s, ln->x, D, ln->y, D, lw[0], lw[1], ln->n * T));
+        else if (!ln->stats_ready) RUN(row_stats(c, ln, D, ln->tok_pairs, ln->n * T));
     }
-    LANES {
-        HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_ATTN));
-        HIP_TRY(e, vithip_attention_f32_rows(LN_.s, e->qkv + ROWS(j) * 3 * D, e->y + ROWS(j) * D, LN_.n, T, heads, 1));
-        HIP_TRY(e, stage_end(e, LN_.s));
-    }
-    LANES
-        RUN(gemm(e, LN_.s, VIT_STAGE_OUTPROJ, e->y + ROWS(j) * D, T * D, lw[4], lw[5], e->x + ROWS(j) * D, e->x + ROWS(j) * D, T * D, LN_.n, D, D, VITHIP_EPI_BIAS_RESIDUAL));
-    LANES RUN(rowstats32(e, LN_.s, e->x + ROWS(j) * D, (size_t)T * D, C32(j), LN_.n, D));   /* LN2 of the class rows */
-    LANES
-        RUN(gemm_fold(e, LN_.s, VIT_STAGE_FC1, e->x + ROWS(j) * D, T * D, f32 + (size_t)3 * D * D, ff + 6 * D + H, ff + 6 * D, C32(j), e->hbuf + ROWS(j) * H, H, LN_.n, H, D, VITHIP_EPI_BIAS_GELU));
-    LANES
-        RUN(gemm(e, LN_.s, VIT_STAGE_FC2, e->hbuf + ROWS(j) * H, H, lw[10], lw[11], e->x + ROWS(j) * D, e->x + ROWS(j) * D, T * D, LN_.n, D, H, VITHIP_EPI_BIAS_RESIDUAL));
-    return VIT_OK;
-}
-
-/* ---- bf16 layer with LayerNorm kernels: LN output, qkv, attention output and the MLP hidden layer are bf16; the residual
- * stream x, LayerNorm statistics, softmax and every accumulation stay fp32 ---- */
-static int layer_bf16(chunk_ctx *c, float **lw, unsigned short **lw16) {
-    vit_engine *e = c->e;
-    const int T = c->T, D = c->D, H = c->H, heads = e->cfg.num_heads;
-    LANES {
-        HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_LN));
-        HIP_TRY(e, vithip_layernorm_f32_bf16out(LN_.s, e->x + ROWS(j) * D, (size_t)D, c->y16 + ROWS(j) * D, (size_t)D, lw[0], lw[1], LN_.n * T, D));
-        HIP_TRY(e, stage_end(e, LN_.s));
-    }
-    LANES
-        RUN(gemm16(e, LN_.s, VIT_STAGE_QKV, c->y16 + ROWS(j) * D, D, lw16[2], lw[3], NULL, c->qkv16 + ROWS(j) * 3 * D, 3 * D, LN_.n * T, 3 * D, D, VITHIP_BF16_EPI_BF16));
-    LANES {
-        HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_ATTN));
-        HIP_TRY(e, vithip_attention_bf16io(LN_.s, c->qkv16 + ROWS(j) * 3 * D, c->y16 + ROWS(j) * D, LN_.n, T, heads));
-        HIP_TRY(e, stage_end(e, LN_.s));
-    }
-    LANES
-        RUN(gemm16(e, LN_.s, VIT_STAGE_OUTPROJ, c->y16 + ROWS(j) * D, D, lw16[4], lw[5], e->x + ROWS(j) * D, e->x + ROWS(j) * D, D, LN_.n * T, D, D, VITHIP_BF16_EPI_F32_RESIDUAL));
-    LANES {
-        HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_LN));
-        HIP_TRY(e, vithip_layernorm_f32_bf16out(LN_.s, e->x + ROWS(j) * D, (size_t)D, c->y16 + ROWS(j) * D, (size_t)D, lw[6], lw[7], LN_.n * T, D));
-        HIP_TRY(e, stage_end(e, LN_.s));
-    }
-    LANES
-        RUN(gemm16(e, LN_.s, VIT_STAGE_FC1, c->y16 + ROWS(j) * D, D, lw16[8], lw[9], NULL, c->h16 + ROWS(j) * H, H, LN_.n * T, H, D, VITHIP_BF16_EPI_BF16_GELU));
-    LANES
-        RUN(gemm16(e, LN_.s, VIT_STAGE_FC2, c->h16 + ROWS(j) * H, H, lw16[10], lw[11], e->x + ROWS(j) * D, e->x + ROWS(j) * D, D, LN_.n * T, D, H, VITHIP_BF16_EPI_F32_RESIDUAL));
-    return VIT_OK;
-}
-
-static int layer_bf16_pruned(chunk_ctx *c, float **lw, unsigned short **lw16) {
-    vit_engine *e = c->e;
-    const int T = c->T, D = c->D, H = c->H, heads = e->cfg.num_heads;
-    LANES {
-        HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_LN));
-        HIP_TRY(e, vithip_layernorm_f32_bf16out(LN_.s, e->x + ROWS(j) * D, (size_t)D, c->y16 + ROWS(j) * D, (size_t)D, lw[0], lw[1], LN_.n * T, D));
-        HIP_TRY(e, stage_end(e, LN_.s));
-    }
-    LANES { /* K and V of every token (in_proj rows D..3D), Q of the class rows only */
-        RUN(gemm16(e, LN_.s, VIT_STAGE_QKV, c->y16 + ROWS(j) * D, D, lw16[2] + (size_t)D * D, lw[3] + D, NULL, c->qkv16 + ROWS(j) * 3 * D + D, 3 * D, LN_.n * T, 2 * D, D, VITHIP_BF16_EPI_BF16));
-        RUN(gemm16(e, LN_.s, VIT_STAGE_QKV, c->y16 + ROWS(j) * D, T * D, lw16[2], lw[3], NULL, c->qkv16 + ROWS(j) * 3 * D, T * 3 * D, LN_.n, D, D, VITHIP_BF16_EPI_BF16));
-    }
-    LANES {
-        HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_ATTN));
-        HIP_TRY(e, vithip_attention_bf16io_rows(LN_.s, c->qkv16 + ROWS(j) * 3 * D, c->y16 + ROWS(j) * D, LN_.n, T, heads, 1));
-        HIP_TRY(e, stage_end(e, LN_.s));
-    }
-    LANES
-        RUN(gemm16(e, LN_.s, VIT_STAGE_OUTPROJ, c->y16 + ROWS(j) * D, T * D, lw16[4], lw[5], e->x + ROWS(j) * D, e->x + ROWS(j) * D, T * D, LN_.n, D, D, VITHIP_BF16_EPI_F32_RESIDUAL));
-    LANES { /* LN2 of the class rows -> compact [n][D] at the head of the lane's y region */
-        HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_LN));
-        HIP_TRY(e, vithip_layernorm_f32_bf16out(LN_.s, e->x + ROWS(j) * D, (size_t)T * D, c->y16 + ROWS(j) * D, (size_t)D, lw[6], lw[7], LN_.n, D));
-        HIP_TRY(e, stage_end(e, LN_.s));
-    }
-    LANES
-        RUN(gemm16(e, LN_.s, VIT_STAGE_FC1, c->y16 + ROWS(j) * D, D, lw16[8], lw[9], NULL, c->h16 + ROWS(j) * H, H, LN_.n, H, D, VITHIP_BF16_EPI_BF16_GELU));
-    LANES
-        RUN(gemm16(e, LN_.s, VIT_STAGE_FC2, c->h16 + ROWS(j) * H, H, lw16[10], lw[11], e->x + ROWS(j) * D, e->x + ROWS(j) * D, T * D, LN_.n, D, H, VITHIP_BF16_EPI_F32_RESIDUAL));
-    return VIT_OK;
-}
-
-/* ---- bf16 layer with the LayerNorm fold (vit_hip_kernels.h, "LayerNorm folding"): in_proj and fc1 read the raw bf16 rows x16
- * with the gamma/beta-folded operands (f16 / ff) and the per-row (rstd, mean*rstd) pairs; out_proj and fc2 store bf16(x) and
- * the row sums for the LayerNorm behind them.  `first`: layer 0, whose LN1 has no residual GEMM in front; `feeds_next`: fc2's
- * output is read by another folded layer. ---- */
-static int layer_bf16_folded(chunk_ctx *c, float **lw, unsigned short **lw16, const unsigned short *f16, const float *ff, int first, int feeds_next) {
-    vit_engine *e = c->e;
-    const int T = c->T, D = c->D, H = c->H, heads = e->cfg.num_heads;
-    if (first)
-        LANES { /* one pass for bf16(x) and the row pairs */
-            HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_LN));
-            HIP_TRY(e, vithip_rowstats_bf16(LN_.s, e->x + ROWS(j) * D, (size_t)D, c->x16 + ROWS(j) * D, (size_t)D, c->ln_rows + ROWS(j) * 2, LN_.n * T, D));
-            HIP_TRY(e, stage_end(e, LN_.s));
+    for (int j = 0; j < c->L; ++j) { /* QKV in_proj (ViT_seq.c:134-147) */
+        vit_lane *ln = &c->lane[j];
+        gemm_desc g = {.stage = VIT_STAGE_QKV, .bf16 = bf16, .A = fold ? ln->xa : ln->y, .lda = D, .W = w_qkv, .bias = b_qkv,
+                       .C = ln->qkv, .ldc = 3 * D, .M = ln->n * T, .N = 3 * D, .K = D, .role = VITHIP_EPI_BIAS,
+                       .ln_rows = ln->tok_pairs, .ln_colsum = cs_qkv};
+        if (pruned) { /* K and V of every token (in_proj rows D..3D), then Q of the class rows, whose pairs are gathered first */
+            gemm_desc kv = g;
+            kv.W = at(w_qkv, (size_t)D * D, esz); kv.bias = b_qkv + D; kv.C = at(ln->qkv, D, esz); kv.N = 2 * D;
+            kv.ln_colsum = cs_qkv ? cs_qkv + D : NULL;
+            RUN(gemm(e, ln->s, &kv, NULL));
+            if (fold) {
+                HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
+                HIP_TRY(e, vithip_gather_rows_f32(ln->s, ln->tok_pairs, (size_t)2 * T, ln->cls_pairs, 2, ln->n, 2));
+                HIP_TRY(e, stage_end(e, ln->s));
+            }
+            g.lda = r * D; g.ldc = r * 3 * D; g.M = rows[j]; g.N = D; g.ln_rows = pairs[j];
         }
-    LANES /* LN1 + in_proj */
-        RUN(gemm16_ln(e, LN_.s, VIT_STAGE_QKV, c->x16 + ROWS(j) * D, D, f16, ff + 3 * D, ff, c->ln_rows + ROWS(j) * 2, c->qkv16 + ROWS(j) * 3 * D, 3 * D, LN_.n * T, 3 * D, D, VITHIP_BF16_EPI_BF16));
-    LANES {
-        HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_ATTN));
-        HIP_TRY(e, vithip_attention_bf16io_qscaled(LN_.s, c->qkv16 + ROWS(j) * 3 * D, c->y16 + ROWS(j) * D, LN_.n, T, heads, T));
-        HIP_TRY(e, stage_end(e, LN_.s));
+        RUN(gemm(e, ln->s, &g, NULL));
     }
-    LANES /* out_proj + residual; bf16(x) and row sums for LN2 */
-        RUN(gemm16_res_stats(e, LN_.s, VIT_STAGE_OUTPROJ, c->y16 + ROWS(j) * D, D, lw16[4], lw[5], e->x + ROWS(j) * D, c->x16 + ROWS(j) * D, D, PART(j), c->ln_rows + ROWS(j) * 2, LN_.n * T, D, D));
-    LANES /* LN2 + fc1 + GELU */
-        RUN(gemm16_ln(e, LN_.s, VIT_STAGE_FC1, c->x16 + ROWS(j) * D, D, f16 + 3 * (size_t)D * D, ff + 6 * D + H, ff + 6 * D, c->ln_rows + ROWS(j) * 2, c->h16 + ROWS(j) * H, H, LN_.n * T, H, D, VITHIP_BF16_EPI_BF16_GELU));
-    LANES { /* fc2 + residual; bf16(x) and row sums for the next layer's LN1 */
-        if (feeds_next)
-            RUN(gemm16_res_stats(e, LN_.s, VIT_STAGE_FC2, c->h16 + ROWS(j) * H, H, lw16[10], lw[11], e->x + ROWS(j) * D, c->x16 + ROWS(j) * D, D, PART(j), c->ln_rows + ROWS(j) * 2, LN_.n * T, D, H));
-        else
-            RUN(gemm16(e, LN_.s, VIT_STAGE_FC2, c->h16 + ROWS(j) * H, H, lw16[10], lw[11], e->x + ROWS(j) * D, e->x + ROWS(j) * D, D, LN_.n * T, D, H, VITHIP_BF16_EPI_F32_RESIDUAL));
+    for (int j = 0; j < c->L; ++j) { /* scores, softmax, P.V (ViT_seq.c:156-215) -> y; pruned: for the class rows */
+        const vit_lane *ln = &c->lane[j];
+        HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_ATTN));
+        if (!bf16 && pruned) HIP_TRY(e, vithip_attention_f32_rows(ln->s, ln->qkv, ln->y, ln->n, T, heads, 1));
+        else if (!bf16) HIP_TRY(e, vithip_attention_f32(ln->s, ln->qkv, ln->y, ln->n, T, heads));
+        else if (fold) HIP_TRY(e, vithip_attention_bf16io_qscaled(ln->s, ln->qkv, ln->y, ln->n, T, heads, pruned ? 1 : T));
+        else if (pruned) HIP_TRY(e, vithip_attention_bf16io_rows(ln->s, ln->qkv, ln->y, ln->n, T, heads, 1));
+        else HIP_TRY(e, vithip_attention_bf16io(ln->s, ln->qkv, ln->y, ln->n, T, heads));
+        HIP_TRY(e, stage_end(e, ln->s));
     }
-    return VIT_OK;
-}
-
-/* the sequence of layer_bf16_pruned in folded form: class rows = rows 0, T, 2T, ... */
-static int layer_bf16_folded_pruned(chunk_ctx *c, float **lw, unsigned short **lw16, const unsigned short *f16, const float *ff, int first) {
-    vit_engine *e = c->e;
-    const int T = c->T, D = c->D, H = c->H, heads = e->cfg.num_heads;
-    if (first)
-        LANES {
-            HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_LN));
-            HIP_TRY(e, vithip_rowstats_bf16(LN_.s, e->x + ROWS(j) * D, (size_t)D, c->x16 + ROWS(j) * D, (size_t)D, c->ln_rows + ROWS(j) * 2, LN_.n * T, D));
-            HIP_TRY(e, stage_end(e, LN_.s));
-        }
-    LANES { /* K and V of every token (folded in_proj rows D..3D); Q of the class rows, whose (rstd, mean*rstd) pairs are copied
-             * out of the per-token array first */
-        float *cls = c->cls_rows + (size_t)LN_.off * 2;
-        RUN(gemm16_ln(e, LN_.s, VIT_STAGE_QKV, c->x16 + ROWS(j) * D, D, f16 + (size_t)D * D, ff + 3 * D + D, ff + D, c->ln_rows + ROWS(j) * 2, c->qkv16 + ROWS(j) * 3 * D + D, 3 * D, LN_.n * T, 2 * D, D, VITHIP_BF16_EPI_BF16));
-        HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_LN));
-        HIP_TRY(e, vithip_gather_rows_f32(LN_.s, c->ln_rows + ROWS(j) * 2, (size_t)T * 2, cls, 2, LN_.n, 2));
-        HIP_TRY(e, stage_end(e, LN_.s));
-        RUN(gemm16_ln(e, LN_.s, VIT_STAGE_QKV, c->x16 + ROWS(j) * D, T * D, f16, ff + 3 * D, ff, cls, c->qkv16 + ROWS(j) * 3 * D, T * 3 * D, LN_.n, D, D, VITHIP_BF16_EPI_BF16));
+    for (int j = 0; j < c->L; ++j) { /* out_proj + residual (ViT_seq.c:219-227,286-288): x += y . Wo^T + bo; folded, it also
+                                      * leaves the pairs of LN2 -- except in the pruned fp32 layer, which takes them in a pass */
+        vit_lane *ln = &c->lane[j];
+        gemm_desc g = {.stage = VIT_STAGE_OUTPROJ, .bf16 = bf16, .A = ln->y, .lda = r * D, .W = w_out, .bias = lw[5],
+                       .C = ln->x, .ldc = r * D, .M = rows[j], .N = D, .K = D, .role = VITHIP_EPI_BIAS_RESIDUAL};
+        if (fold && (bf16 || !pruned)) { g.stats_rows = pairs[j]; g.stats_part = ln->partials; g.x16 = bf16 ? ln->xa : NULL; }
+        RUN(gemm(e, ln->s, &g, &ln2_ready[j]));
     }
-    LANES {
-        HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_ATTN));
-        HIP_TRY(e, vithip_attention_bf16io_qscaled(LN_.s, c->qkv16 + ROWS(j) * 3 * D, c->y16 + ROWS(j) * D, LN_.n, T, heads, 1));
-        HIP_TRY(e, stage_end(e, LN_.s));
+    for (int j = 0; j < c->L; ++j) { /* LN2 (ViT_seq.c:291); pruned: of the class rows, into a compact [n][D] at the head of y */
+        const vit_lane *ln = &c->lane[j];
+        if (!fold) RUN(layernorm(c, ln->s, ln->x, (size_t)r * D, ln->y, D, lw[6], lw[7], rows[j]));
+        else if (!ln2_ready[j]) RUN(row_stats(c, ln, (size_t)r * D, pairs[j], rows[j]));
     }
-    LANES
-        RUN(gemm16_res_stats(e, LN_.s, VIT_STAGE_OUTPROJ, c->y16 + ROWS(j) * D, T * D, lw16[4], lw[5], e->x + ROWS(j) * D, c->x16 + ROWS(j) * D, T * D, PART(j), c->cls_rows + (size_t)LN_.off * 2, LN_.n, D, D));
-    LANES
-        RUN(gemm16_ln(e, LN_.s, VIT_STAGE_FC1, c->x16 + ROWS(j) * D, T * D, f16 + 3 * (size_t)D * D, ff + 6 * D + H, ff + 6 * D, c->cls_rows + (size_t)LN_.off * 2, c->h16 + ROWS(j) * H, H, LN_.n, H, D, VITHIP_BF16_EPI_BF16_GELU));
-    LANES
-        RUN(gemm16(e, LN_.s, VIT_STAGE_FC2, c->h16 + ROWS(j) * H, H, lw16[10], lw[11], e->x + ROWS(j) * D, e->x + ROWS(j) * D, T * D, LN_.n, D, H, VITHIP_BF16_EPI_F32_RESIDUAL));
+    for (int j = 0; j < c->L; ++j) { /* fc1 + GELU (ViT_seq.c:258-264) */
+        const vit_lane *ln = &c->lane[j];
+        gemm_desc g = {.stage = VIT_STAGE_FC1, .bf16 = bf16, .A = ln->y, .lda = D, .W = w_fc1, .bias = b_fc1, .C = ln->h, .ldc = H,
+                       .M = rows[j], .N = H, .K = D, .role = VITHIP_EPI_BIAS_GELU};
+        if (fold) { g.A = ln->xa; g.lda = r * D; g.ln_rows = pairs[j]; g.ln_colsum = cs_fc1; }
+        RUN(gemm(e, ln->s, &g, NULL));
+    }
+    for (int j = 0; j < c->L; ++j) { /* fc2 + residual (ViT_seq.c:266,297-299): x += h . W2^T + b2; folded, it also leaves the
+                                      * pairs of the next layer's LN1 when there is one */
+        vit_lane *ln = &c->lane[j];
+        gemm_desc g = {.stage = VIT_STAGE_FC2, .bf16 = bf16, .A = ln->h, .lda = H, .W = w_fc2, .bias = lw[11], .C = ln->x,
+                       .ldc = r * D, .M = rows[j], .N = D, .K = H, .role = VITHIP_EPI_BIAS_RESIDUAL};
+        if (fold && feeds_next) { g.stats_rows = ln->tok_pairs; g.stats_part = ln->partials; g.x16 = bf16 ? ln->xa : NULL; }
+        RUN(gemm(e, ln->s, &g, &ln->stats_ready));
+    }
     return VIT_OK;
 }
 
@@ -942,18 +772,24 @@ static int stage_head(chunk_ctx *c, float *d_probs, int *d_label, float *d_prob)
     vit_engine *e = c->e;
     const int T = c->T, D = c->D, NC = c->NC;
     float **fw = e->w + 4 + VIT_WEIGHTS_PER_LAYER * e->cfg.depth;
-    LANES {
-        HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_LN));
-        HIP_TRY(e, vithip_layernorm_f32(LN_.s, e->x + ROWS(j) * D, (size_t)T * D, e->z + (size_t)LN_.off * D, (size_t)D, fw[0], fw[1], LN_.n, D));
-        HIP_TRY(e, stage_end(e, LN_.s));
+    for (int j = 0; j < c->L; ++j) {
+        const vit_lane *ln = &c->lane[j];
+        HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
+        HIP_TRY(e, vithip_layernorm_f32(ln->s, ln->x, (size_t)T * D, e->z + (size_t)ln->off * D, (size_t)D, fw[0], fw[1], ln->n, D));
+        HIP_TRY(e, stage_end(e, ln->s));
     }
-    LANES
-        RUN(gemm(e, LN_.s, VIT_STAGE_HEAD, e->z + (size_t)LN_.off * D, D, fw[2], fw[3], NULL, e->logits + (size_t)LN_.off * NC, NC, LN_.n, NC, D, VITHIP_EPI_BIAS));
-    LANES {
-        const size_t o = (size_t)LN_.off;
-        HIP_TRY(e, stage_begin(e, LN_.s, VIT_STAGE_SOFTMAX));
-        HIP_TRY(e, vithip_softmax_top1_f32(LN_.s, e->logits + o * NC, NC, d_probs + o * NC, NC, d_label ? d_label + o : NULL, d_prob ? d_prob + o : NULL, LN_.n, NC));
-        HIP_TRY(e, stage_end(e, LN_.s));
+    for (int j = 0; j < c->L; ++j) {
+        const vit_lane *ln = &c->lane[j];
+        const gemm_desc g = {.stage = VIT_STAGE_HEAD, .A = e->z + (size_t)ln->off * D, .lda = D, .W = fw[2], .bias = fw[3],
+                             .C = e->logits + (size_t)ln->off * NC, .ldc = NC, .M = ln->n, .N = NC, .K = D, .role = VITHIP_EPI_BIAS};
+        RUN(gemm(e, ln->s, &g, NULL));
+    }
+    for (int j = 0; j < c->L; ++j) {
+        const vit_lane *ln = &c->lane[j];
+        const size_t o = (size_t)ln->off;
+        HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_SOFTMAX));
+        HIP_TRY(e, vithip_softmax_top1_f32(ln->s, e->logits + o * NC, NC, d_probs + o * NC, NC, d_label ? d_label + o : NULL, d_prob ? d_prob + o : NULL, ln->n, NC));
+        HIP_TRY(e, stage_end(e, ln->s));
     }
     return VIT_OK;
 }
@@ -966,46 +802,45 @@ static int forward_chunk(vit_engine *e, vithip_stream_t s, const float *d_images
     c->T = e->tokens; c->D = cfg->embed_dim; c->H = cfg->hidden_dim; c->NC = cfg->num_classes;
     c->L = e->opt.lanes > VIT_MAX_LANES ? VIT_MAX_LANES : e->opt.lanes;
     if (c->L < 1 || nb < 2 * c->L) c->L = 1;
-    for (int j = 0; j < c->L; ++j) {
-        c->lane[j].off = (int)((long)nb * j / c->L);
-        c->lane[j].n = (int)((long)nb * (j + 1) / c->L) - c->lane[j].off;
-        c->lane[j].s = j == 0 ? s : e->aux_stream[j - 1];
-        c->lane[j].stats_ready = 0;
-    }
+    const int bf16 = e->opt.dtype == VIT_DTYPE_BF16;
     const size_t B = (size_t)e->opt.max_batch, T = (size_t)c->T, D = (size_t)c->D, H = (size_t)c->H;
-    c->y16 = (unsigned short *)e->y; c->qkv16 = (unsigned short *)e->qkv; c->h16 = (unsigned short *)e->hbuf;
-    c->strips = vithip_ln_strips((int)D);
-    c->x16 = c->y16 + B * T * D;
-    c->ln_part = (float *)(c->qkv16 + B * T * 3 * D);
-    c->ln_rows = c->ln_part + (size_t)c->strips * B * T * 2;
-    c->cls_rows = c->ln_rows + B * T * 2;
+    const size_t esz = bf16 ? sizeof(unsigned short) : sizeof(float);
+    /* Where the LayerNorm fold keeps its row statistics.  fp32 engines: ln_rows32 = the pairs of max_batch * T token rows, then
+     * of max_batch class rows; ln_part32 = the partial sums, [D / 64][rows][2] per lane.  bf16 engines: the idle halves of the y
+     * and qkv allocations, which bf16 activations only half fill -- the bf16 copy of x in y's; the partial sums
+     * ([vithip_ln_strips(D)][rows][2] per lane), then the token and the class pairs, in qkv's. */
+    float *pairs = e->ln_rows32, *part = e->ln_part32;
+    size_t strips = D / 64;
+    unsigned short *x16 = NULL;
+    if (bf16) {
+        x16 = (unsigned short *)e->y + B * T * D;
+        strips = (size_t)vithip_ln_strips((int)D);
+        part = (float *)((unsigned short *)e->qkv + B * T * 3 * D);
+        pairs = part + strips * B * T * 2;
+    }
+    for (int j = 0; j < c->L; ++j) {
+        vit_lane *ln = &c->lane[j];
+        memset(ln, 0, sizeof(*ln));
+        ln->off = (int)((long)nb * j / c->L);
+        ln->n = (int)((long)nb * (j + 1) / c->L) - ln->off;
+        ln->s = j == 0 ? s : e->aux_stream[j - 1];
+        const size_t row0 = (size_t)ln->off * T;
+        ln->x = e->x + row0 * D;
+        ln->y = at(e->y, row0 * D, esz); ln->qkv = at(e->qkv, row0 * 3 * D, esz); ln->h = at(e->hbuf, row0 * H, esz);
+        if (e->fold) {
+            ln->xa = bf16 ? (void *)(x16 + row0 * D) : (void *)ln->x;
+            ln->tok_pairs = pairs + row0 * 2;
+            ln->cls_pairs = pairs + (B * T + (size_t)ln->off) * 2;
+            ln->partials = part + row0 * strips * 2;
+        }
+    }
 
     if (c->L > 1) { /* fork: the other lanes start after everything already queued on s */
         HIP_TRY(e, vithip_event_record(e->ev_fork, s));
         for (int j = 1; j < c->L; ++j) HIP_TRY(e, vithip_stream_wait_event(c->lane[j].s, e->ev_fork));
     }
     RUN(stage_embed(c, d_images));
-    const int bf16 = e->opt.dtype == VIT_DTYPE_BF16;
-    const int prune = e->opt.prune_last_layer && c->T <= 224;
-    for (int l = 0; l < cfg->depth; ++l) {
-        float **lw = e->w + 4 + VIT_WEIGHTS_PER_LAYER * l;
-        unsigned short **lw16 = e->w16 + 4 + VIT_WEIGHTS_PER_LAYER * l;
-        const int last_pruned = prune && l == cfg->depth - 1;
-        if (!bf16 && e->fold) {
-            const float *f32 = e->wfold32 + (size_t)l * (3 * D * D + H * D);
-            const float *ff = e->wfoldf + (size_t)l * (6 * D + 2 * H);
-            RUN(last_pruned ? layer_f32_folded_pruned(c, lw, f32, ff) : layer_f32_folded(c, lw, f32, ff, l + 1 < cfg->depth));
-        } else if (!bf16) {
-            RUN(last_pruned ? layer_f32_pruned(c, lw) : layer_f32(c, lw));
-        } else if (e->fold) {
-            const unsigned short *f16 = e->wfold16 + (size_t)l * (3 * D * D + H * D);
-            const float *ff = e->wfoldf + (size_t)l * (6 * D + 2 * H);
-            RUN(last_pruned ? layer_bf16_folded_pruned(c, lw, lw16, f16, ff, l == 0)
-                            : layer_bf16_folded(c, lw, lw16, f16, ff, l == 0, l + 1 < cfg->depth));
-        } else {
-            RUN(last_pruned ? layer_bf16_pruned(c, lw, lw16) : layer_bf16(c, lw, lw16));
-        }
-    }
+    for (int l = 0; l < cfg->depth; ++l) RUN(encoder_layer(c, l));
     RUN(stage_head(c, d_probs, d_label, d_prob));
     for (int j = 1; j < c->L; ++j) { /* join */
         HIP_TRY(e, vithip_event_record(e->ev_join[j - 1], c->lane[j].s));
@@ -1014,10 +849,6 @@ static int forward_chunk(vit_engine *e, vithip_stream_t s, const float *d_images
     e->last_rows = nb;
     return VIT_OK;
 }
-#undef LANES
-#undef LN_
-#undef ROWS
-#undef PART
 #undef RUN
 
 /* Images per forward_chunk call: the workspace holds max_batch, and no lane may exceed lane_cap (see vit_engine_create). */
