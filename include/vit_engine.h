@@ -62,6 +62,10 @@ typedef struct {
                              * so it is a small one; the rest follows behind its compute in pieces of max_batch).  0 = auto (the
                              * measured choice, host/vit_engine.c), otherwise clamped to [1, max_batch].  Rows are bit-identical
                              * whatever the cut. */
+    int fp32_split;  /* fp32 engines: the encoder GEMMs (QKV, out_proj, fc1, fc2 of every layer) on the bf16 matrix pipe through the
+                      * three-piece operand split (vithip_gemm_args.arith = 1); the patch embedding and the head
+                      * stay on fp32 MFMA.  0 = auto (on: every fp32 model shape allows it), 1 = on, -1 = off (fp32 MFMA throughout,
+                      * the arithmetic of earlier versions bit for bit).  Ignored by bf16 engines. */
 } vit_engine_options;
 
 enum { VIT_DTYPE_F32 = 0, VIT_DTYPE_BF16 = 1 };

@@ -128,6 +128,11 @@ typedef struct {
      * (one small launch then finalises them: vithip_gemm_f32_stats_in_epilogue() says whether a call would); any other kernel,
      * or no scratch, and the call runs vithip_rowstats_f32 behind the GEMM. */
     float *stats_out, *stats_partials;
+    /* arithmetic of the contraction: 0 = fp32 operands on v_mfma_f32_32x32x2_f32; 1 = three-piece split: each fp32 operand is
+     * staged as hi + mid + lo bf16 pieces (exact) and the six piece products of rank <= 2 run on v_mfma_f32_32x32x16_bf16,
+     * 6/16 of the fp32 instruction's matrix time, error of the order of an fp32 dot product's.  With 1 the
+     * tile codes 0, 9, 10 and 11 are accepted and give the same bits as each other; 6, 7, 8 and 12 are refused. */
+    int arith;
 } vithip_gemm_args;
 int vithip_gemm_f32(vithip_stream_t stream, const vithip_gemm_args *args);
 int vithip_gemm_f32_stats_in_epilogue(const vithip_gemm_args *args);  /* 1 / 0 (0 also for arguments vithip_gemm_f32 would refuse) */

@@ -22,6 +22,7 @@ i32p = C.POINTER(C.c_int)
 
 STAGES = ("embed", "ln", "qkv", "attn", "outproj", "fc1", "fc2", "head", "softmax")
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL = 0, 1, 2
+ARITH_F32, ARITH_SPLIT3 = 0, 1   # vithip_gemm_args.arith
 
 
 class VitError(RuntimeError):
@@ -49,7 +50,7 @@ class CImageData(C.Structure):  # Network.h:7-13
 class COptions(C.Structure):
     _fields_ = [("device", C.c_int), ("max_batch", C.c_int), ("profile", C.c_int), ("lanes", C.c_int),
                 ("dtype", C.c_int), ("prune_last_layer", C.c_int), ("use_graph", C.c_int), ("gemm_tile", C.c_int), ("ln_fold", C.c_int),
-                ("gemm_handover_test", C.c_int), ("host_first_piece", C.c_int)]
+                ("gemm_handover_test", C.c_int), ("host_first_piece", C.c_int), ("fp32_split", C.c_int)]
 
 
 class CStageTimes(C.Structure):
@@ -68,7 +69,7 @@ class CGemmArgs(C.Structure):
                 ("C", C.c_void_p), ("ldc", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
                 ("epilogue", C.c_int), ("tile", C.c_int), ("group_m", C.c_int), ("workspace", C.c_void_p),
                 ("handover_test", C.c_int), ("ln_rows", C.c_void_p), ("ln_colsum", C.c_void_p),
-                ("stats_out", C.c_void_p), ("stats_partials", C.c_void_p)]
+                ("stats_out", C.c_void_p), ("stats_partials", C.c_void_p), ("arith", C.c_int)]
 
 
 _lib: Optional[C.CDLL] = None
@@ -257,14 +258,16 @@ class DeviceArray:
 
 
 def gemm(A, W, bias, residual=None, epilogue=EPI_BIAS, tile: int = 0, group_m: int = 0, workspace: bool = False,
-         handover_test: int = 0, stats: Optional[dict] = None, ln=None, row_stats: Optional[dict] = None) -> np.ndarray:
+         handover_test: int = 0, stats: Optional[dict] = None, ln=None, row_stats: Optional[dict] = None,
+         arith: int = ARITH_F32) -> np.ndarray:
     """C = epilogue(A . W^T + bias) through vithip_gemm_f32 (tile / group_m: per-call tuning fields, 0 = auto;
     workspace: lend the scratch that enables the helper pieces of the persistent walk; handover_test: see
     vithip_gemm_args; stats: receives the hand-over counters {"taken", "recomputed"} of the launch;
     ln = (rows [M][2], colsum [N] or None): the consumer side of the LayerNorm fold, W / bias being the folded operands (None: the
     CENTRED weight of ln_fold_weights_f32_centered, nothing to subtract);
     row_stats: a dict that receives "rows" = vithip_gemm_args.stats_out [M][2] and "in_epilogue" = what
-    vithip_gemm_f32_stats_in_epilogue said; its key "scratch" (default True) lends stats_partials)."""
+    vithip_gemm_f32_stats_in_epilogue said; its key "scratch" (default True) lends stats_partials);
+    arith: ARITH_F32 (fp32 MFMA) or ARITH_SPLIT3 (the three-piece split on the bf16 matrix pipe; tiles 0, 9, 10, 11)."""
     A, W, bias = _as_f32(A), _as_f32(W), _as_f32(bias)
     M, K = A.shape
     N = W.shape[0]
@@ -278,7 +281,7 @@ def gemm(A, W, bias, residual=None, epilogue=EPI_BIAS, tile: int = 0, group_m: i
     dPart = DeviceArray((max(N // 64, 1), M, 2)) if row_stats is not None and row_stats.get("scratch", True) else None
     args = CGemmArgs(dA.ptr, K, dW.ptr, K, db.ptr, dR.ptr if dR else None, N, dC.ptr, N, M, N, K, epilogue, tile, group_m, ws,
                      handover_test, dRows.ptr if dRows else None, dCs.ptr if dCs else None, dSt.ptr if dSt else None,
-                     dPart.ptr if dPart else None)
+                     dPart.ptr if dPart else None, arith)
     if row_stats is not None:
         row_stats["in_epilogue"] = int(lib().vithip_gemm_f32_stats_in_epilogue(C.byref(args)))
     hip_check(lib().vithip_gemm_f32(None, C.byref(args)), "vithip_gemm_f32")
@@ -597,12 +600,14 @@ class Engine:
 
     def __init__(self, cfg: ModelConfig, max_batch: int = 256, device: int = 0, profile: bool = False,
                  lanes: int = 1, dtype: str = "f32", prune_last_layer: bool = False, use_graph: bool = False,
-                 gemm_tile: int = 0, ln_fold: int = 0, gemm_handover_test: int = 0, host_first_piece: int = 0):
+                 gemm_tile: int = 0, ln_fold: int = 0, gemm_handover_test: int = 0, host_first_piece: int = 0,
+                 fp32_split: int = 0):
         self.cfg = cfg
         self._h = C.c_void_p()
         cc = CConfig.of(cfg)
         opt = COptions(device, max_batch, 1 if profile else 0, lanes, {"f32": 0, "bf16": 1}[dtype],
-                       1 if prune_last_layer else 0, 1 if use_graph else 0, gemm_tile, ln_fold, gemm_handover_test, host_first_piece)
+                       1 if prune_last_layer else 0, 1 if use_graph else 0, gemm_tile, ln_fold, gemm_handover_test, host_first_piece,
+                       fp32_split)
         rc = lib().vit_engine_create(C.byref(self._h), C.byref(cc), C.byref(opt))
         if rc != 0:
             msg = lib().vit_engine_last_error(self._h).decode() if self._h else "allocation failed"

@@ -35,10 +35,10 @@
 #endif
 
 namespace vitgemm {
-int launch_persistent(hipStream_t stream, GemmParams &p, int epilogue, int group_m);  // vit_gemm_persistent.hip
+int launch_persistent(hipStream_t stream, GemmParams &p, int epilogue, int group_m, int arith = ARITH_F32);  // vit_gemm_persistent.hip
 int launch_persistent_stamped(hipStream_t stream, GemmParams &p, int epilogue, int group_m);
 int launch_persistent_switchoff(hipStream_t stream, GemmParams &p, int epilogue, int group_m, int dbg);  // probe build
-int persistent_piece_steps(int M, int N, int K, int slots, int wgs);
+int persistent_piece_steps(int M, int N, int K, int slots, int wgs, int kstep);
 }
 
 namespace {
@@ -59,9 +59,13 @@ unsigned long long *g_gemm_dbg = nullptr;  // stamp buffer of the DBG == 5 probe
 // by construction; they bound what the MFMA + LDS-read stream can reach.
 // BK = K step per LDS tile (32 or 16).  LDS rows are padded to BK + 4 floats: 16-B aligned and
 // conflict-free for ds_read_b128 at both sizes (row strides of 36 and 20 dwords).
-template <int BM, int BN, int WM, int WN, int EPI, int AMODE, int DBG = 0, int BK = 32, bool PIPE = false>
-__global__ __launch_bounds__(256, (BK == 16 ? 3 : 1)) void gemm_f32_nt_kernel(const GemmParams p) {
-    constexpr int LDS_LD = BK + 4;
+// ARITH = ARITH_SPLIT3: the three-piece split on the bf16 matrix pipe (vit_gemm_common.hpp), BK = SPLIT_BK, software-pipelined
+// staging as PIPE below, LDS rows of SPLIT_LD floats.
+template <int BM, int BN, int WM, int WN, int EPI, int AMODE, int DBG = 0, int BK = 32, bool PIPE = false, int ARITH = ARITH_F32>
+__global__ __launch_bounds__(256, (ARITH == ARITH_SPLIT3 ? 2 : BK == 16 ? 3 : 1)) void gemm_f32_nt_kernel(const GemmParams p) {
+    constexpr bool SPLIT = ARITH == ARITH_SPLIT3;
+    static_assert(!SPLIT || (BK == SPLIT_BK && AMODE == A_DENSE && DBG == 0), "split: dense operands, K step 16");
+    constexpr int LDS_LD = SPLIT ? SPLIT_LD : BK + 4;
     constexpr int ROWS_PER_PASS = 256 / (BK / 4);  // tile rows covered by one staging load per thread
     constexpr int WGN = BN / WN;           // waves along N
     constexpr int TM = WM / 32, TN = WN / 32;
@@ -186,7 +190,41 @@ __global__ __launch_bounds__(256, (BK == 16 ? 3 : 1)) void gemm_f32_nt_kernel(co
     const int nk = p.K / BK;
     const int a_frag_off = (wm * WM + r) * LDS_LD + h * 4;
     const int b_frag_off = (wn * WN + r) * LDS_LD + h * 4;
-    if constexpr (PIPE) {
+    if constexpr (SPLIT) {
+        // ---- K loop of the three-piece split: per 16-deep step, the fragments' pieces from buffer `cur`, 6 x TM x TN matrix
+        // instructions with the staged step t+1 split into buffer cur^1 and the loads of step t+2 spread over the first half,
+        // then the one barrier.  (One fragment set: with two workgroups per CU the other one covers the LDS latency.)
+        auto store_split = [&](int buf) {
+            float *As = As0 + buf * BM * LDS_LD, *Bs = Bs0 + buf * BN * LDS_LD;
+#pragma unroll
+            for (int i = 0; i < A_CHUNKS; ++i) split3_store(As + (ld_row + i * ROWS_PER_PASS) * LDS_LD, ld_kc, a_stage[i]);
+#pragma unroll
+            for (int i = 0; i < B_CHUNKS; ++i) split3_store(Bs + (ld_row + i * ROWS_PER_PASS) * LDS_LD, ld_kc, b_stage[i]);
+        };
+        load_global(0);
+        store_split(0);
+        load_global(nk > 1 ? BK : 0);
+        __syncthreads();
+        int cur = 0;
+        for (int kt = 0; kt < nk; ++kt) {
+            // branch-free: past the end the staging re-reads the last step into a buffer nobody reads again
+            const int k_ahead = (kt + 2 < nk ? kt + 2 : nk - 1) * BK;
+            float *An = As0 + (cur ^ 1) * BM * LDS_LD, *Bn = Bs0 + (cur ^ 1) * BN * LDS_LD;
+            split3_step<TM, TN, A_CHUNKS + B_CHUNKS>(acc, As0 + cur * BM * LDS_LD + a_frag_off, Bs0 + cur * BN * LDS_LD + b_frag_off,
+                [&](int q) __attribute__((always_inline)) {
+                    if (q < A_CHUNKS) {
+                        split3_store(An + (ld_row + q * ROWS_PER_PASS) * LDS_LD, ld_kc, a_stage[q]);
+                        a_stage[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, a_boff[q], k_ahead * 4, 0));
+                    } else {
+                        const int qb = q - A_CHUNKS;
+                        split3_store(Bn + (ld_row + qb * ROWS_PER_PASS) * LDS_LD, ld_kc, b_stage[qb]);
+                        b_stage[qb] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, b_boff[qb], k_ahead * 4, 0));
+                    }
+                });
+            __syncthreads();
+            cur ^= 1;
+        }
+    } else if constexpr (PIPE) {
         // ---- software-pipelined K loop ---------------------------------------------------------
         // Per K step: the fragments of chunk c+1 are read while chunk c multiplies; the staged tile
         // t+1 is written to the other LDS buffer and the loads of tile t+2 are issued in the shadow
@@ -346,7 +384,7 @@ __global__ void cls_rows_kernel(const float *cls, const float *pos, float *x, in
     x[(size_t)im * tokens * dim + d] = cls[d] + pos[d];
 }
 
-template <int BM, int BN, int WM, int WN, int AMODE, int BK = 32, bool PIPE = false>
+template <int BM, int BN, int WM, int WN, int AMODE, int BK = 32, bool PIPE = false, int ARITH = ARITH_F32>
 int launch_tile(hipStream_t stream, GemmParams &p, int epilogue) {
     p.tiles_m = (p.M + BM - 1) / BM;
     p.tiles_n = (p.N + BN - 1) / BN;
@@ -356,19 +394,19 @@ int launch_tile(hipStream_t stream, GemmParams &p, int epilogue) {
     } else {
         switch (epilogue) {
             case VITHIP_EPI_BIAS:
-                hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS, A_DENSE, 0, BK, PIPE>), grid, block, 0, stream, p);
+                hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS, A_DENSE, 0, BK, PIPE, ARITH>), grid, block, 0, stream, p);
                 break;
             case VITHIP_EPI_BIAS_GELU:
-                hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_GELU, A_DENSE, 0, BK, PIPE>), grid, block, 0, stream, p);
+                hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_GELU, A_DENSE, 0, BK, PIPE, ARITH>), grid, block, 0, stream, p);
                 break;
             case VITHIP_EPI_BIAS_RESIDUAL:
-                hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_RESIDUAL, A_DENSE, 0, BK, PIPE>), grid, block, 0, stream, p);
+                hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_RESIDUAL, A_DENSE, 0, BK, PIPE, ARITH>), grid, block, 0, stream, p);
                 break;
             case EPI_BIAS_LN:
-                hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WM, WN, EPI_BIAS_LN, A_DENSE, 0, BK, PIPE>), grid, block, 0, stream, p);
+                hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WM, WN, EPI_BIAS_LN, A_DENSE, 0, BK, PIPE, ARITH>), grid, block, 0, stream, p);
                 break;
             case EPI_BIAS_GELU_LN:
-                hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WM, WN, EPI_BIAS_GELU_LN, A_DENSE, 0, BK, PIPE>), grid, block, 0, stream, p);
+                hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WM, WN, EPI_BIAS_GELU_LN, A_DENSE, 0, BK, PIPE, ARITH>), grid, block, 0, stream, p);
                 break;
             default:
                 return static_cast<int>(hipErrorInvalidValue);
@@ -388,8 +426,13 @@ int launch_probe(hipStream_t stream, GemmParams &p) {
 }
 #endif
 
-template <int AMODE>
+template <int AMODE, int ARITH = ARITH_F32>
 int dispatch(hipStream_t stream, GemmParams &p, int epilogue, int tile, int group_m) {
+    // the split (ARITH_SPLIT3) exists for dense operands on the 128x128 walk (9), the 128x128 and 64x64 tiles (10, 11) and auto;
+    // the other codes are refused, and auto takes the 64x64 tile where the fp32 arithmetic takes the 16x16x4 latency tile
+    constexpr bool SPLIT = ARITH == ARITH_SPLIT3;
+    constexpr int BK = SPLIT ? SPLIT_BK : 32;
+    static_assert(!SPLIT || AMODE == A_DENSE, "the patch embedding stays on fp32 MFMA");
     // Tile rows per L2 group of the XCD-aware walk.  Measured per launch at batch 256 (tools/gemm_f32_traffic.py, PMC FETCH_SIZE /
     // WRITE_SIZE passes, round 4), bytes from beyond the L2s over algorithmic: N = 768 (6 tile columns: fc2 / out_proj) 3.11 / 1.58
     // with groups of 8 rows, 2.34 / 1.34 in plain N-fastest order (group 1: the 64 tiles an XCD holds at a time are ~11 whole tile
@@ -401,7 +444,7 @@ int dispatch(hipStream_t stream, GemmParams &p, int epilogue, int tile, int grou
 #ifdef VIT_PROBES
     if (g_gemm_tile) tile = g_gemm_tile;
     if (g_gemm_group) p.group_m = g_gemm_group;
-    if constexpr (AMODE == A_DENSE) {
+    if constexpr (AMODE == A_DENSE && !SPLIT) {
         switch (tile) {  // timing-only probes, never selected by the engine
             case 101: return launch_probe<1>(stream, p);
             case 102: return launch_probe<2>(stream, p);
@@ -437,15 +480,17 @@ int dispatch(hipStream_t stream, GemmParams &p, int epilogue, int tile, int grou
         return launch_tile<128, 64, 64, 32, A_PATCHES, 32, true>(stream, p, epilogue);
     }
     switch (tile) {
-        case 9: return vitgemm::launch_persistent(stream, p, epilogue, p.group_m);   // persistent, cross-tile pipelined
-        case 6: return launch_tile<128, 128, 64, 64, AMODE, 16, true>(stream, p, epilogue);
-        case 7: return launch_tile<256, 128, 128, 64, AMODE, 32, true>(stream, p, epilogue);
-        case 8: return launch_tile<128, 64, 64, 32, AMODE, 32, true>(stream, p, epilogue);
-        case 10: return launch_tile<128, 128, 64, 64, AMODE, 32, true>(stream, p, epilogue);  // pipelined
-        case 11: return launch_tile<64, 64, 32, 32, AMODE, 32, true>(stream, p, epilogue);    // one 32x32 accumulator per wave
-        case 12:  // latency tile: 16x16 per wave on 16x16x4 MFMA (vit_gemm_latency.hip)
-            if (p.K % 128) return static_cast<int>(hipErrorInvalidValue);
-            return vitgemm::launch_gemm_f32_latency(stream, p, epilogue);
+        case 9: return vitgemm::launch_persistent(stream, p, epilogue, p.group_m, ARITH);   // persistent, cross-tile pipelined
+        case 6: case 7: case 8: case 12:
+            if constexpr (SPLIT) return static_cast<int>(hipErrorInvalidValue);
+            else if (tile == 6) return launch_tile<128, 128, 64, 64, AMODE, 16, true>(stream, p, epilogue);
+            else if (tile == 7) return launch_tile<256, 128, 128, 64, AMODE, 32, true>(stream, p, epilogue);
+            else if (tile == 8) return launch_tile<128, 64, 64, 32, AMODE, 32, true>(stream, p, epilogue);
+            // latency tile: 16x16 per wave on 16x16x4 MFMA (vit_gemm_latency.hip)
+            else if (p.K % 128) return static_cast<int>(hipErrorInvalidValue);
+            else return vitgemm::launch_gemm_f32_latency(stream, p, epilogue);
+        case 10: return launch_tile<128, 128, 64, 64, AMODE, BK, true, ARITH>(stream, p, epilogue);  // pipelined
+        case 11: return launch_tile<64, 64, 32, 32, AMODE, BK, true, ARITH>(stream, p, epilogue);    // one 32x32 accumulator per wave
         default: {
             // auto.  Large problems: the persistent walk wins where the epilogue is light on registers (bias, bias+GELU:
             // fc1 22.0 vs 23.0 ms per step); the residual epilogue needs 255 VGPRs there and is faster one tile per
@@ -461,10 +506,10 @@ int dispatch(hipStream_t stream, GemmParams &p, int epilogue, int tile, int grou
             // Fewer than ~160 tiles of 64x64 (one image: QKV 144, out_proj and fc2 48; four images: out_proj / fc2 156): the chain of
             // ONE 32x32 accumulator is the whole GEMM.  32x32 workgroup tiles on v_mfma_f32_16x16x4_f32 (vit_gemm_latency.hip)
             // quadruple the waves and shorten the chain 2.3x, bit-identically: fc2 of one image 61 -> 27 us, out_proj 20 -> 11.
-            if (p.K % 128 == 0 && (long)((p.M + 63) / 64) * ((p.N + 63) / 64) < 160)
+            if (!SPLIT && p.K % 128 == 0 && (long)((p.M + 63) / 64) * ((p.N + 63) / 64) < 160)
                 return vitgemm::launch_gemm_f32_latency(stream, p, epilogue);
             if ((long)((p.M + 127) / 128) * ((p.N + 63) / 64) < 256)
-                return launch_tile<64, 64, 32, 32, AMODE, 32, true>(stream, p, epilogue);
+                return launch_tile<64, 64, 32, 32, AMODE, BK, true, ARITH>(stream, p, epilogue);
             // Round 5 (tools/small_batch_tiles.py: every GEMM of the ViT-B/16 forward at 12 ... 128 images on every tile code): below the
             // persistent walk's range the 64x64 tile beats the 128x64 one at every size measured -- four times the workgroups of a
             // 128x128 walk for the partial last round to spread over (fc2 at 48 images 4.50 -> 3.96 ms per 12 launches, out_proj 1.30 ->
@@ -473,17 +518,17 @@ int dispatch(hipStream_t stream, GemmParams &p, int epilogue, int tile, int grou
             // 12 images 5.2 -> 4.8: the first piece of a host call (vit_engine_forward_host) and every small batch.  Same bits on every
             // tile, so the choice is time only.
             if (epilogue == VITHIP_EPI_BIAS_RESIDUAL) {
-                if (tiles < 1024) return launch_tile<64, 64, 32, 32, AMODE, 32, true>(stream, p, epilogue);
+                if (tiles < 1024) return launch_tile<64, 64, 32, 32, AMODE, BK, true, ARITH>(stream, p, epilogue);
                 // with a workspace the persistent walk hands the first K-steps of the partial last round's tiles to idle
                 // workgroups (fc2 / out_proj at batch 256: 480 -> 448 steps per workgroup); without one the residual
                 // epilogue is marginally faster one tile per workgroup (fc2 21.30 vs 21.43 ms per step)
                 // (also when the caller wants the row statistics of the stored rows: the persistent epilogue takes them on the way)
-                if ((p.row_partials && p.N % 128 == 0) || (p.sk_ws && vitgemm::persistent_piece_steps(p.M, p.N, p.K, p.sk_slots, 0) > 0))
-                    return vitgemm::launch_persistent(stream, p, epilogue, p.group_m);
-                return launch_tile<128, 128, 64, 64, AMODE, 32, true>(stream, p, epilogue);
+                if ((p.row_partials && p.N % 128 == 0) || (p.sk_ws && vitgemm::persistent_piece_steps(p.M, p.N, p.K, p.sk_slots, 0, BK) > 0))
+                    return vitgemm::launch_persistent(stream, p, epilogue, p.group_m, ARITH);
+                return launch_tile<128, 128, 64, 64, AMODE, BK, true, ARITH>(stream, p, epilogue);
             }
-            if (tiles < 1280) return launch_tile<64, 64, 32, 32, AMODE, 32, true>(stream, p, epilogue);
-            return vitgemm::launch_persistent(stream, p, epilogue, p.group_m);
+            if (tiles < 1280) return launch_tile<64, 64, 32, 32, AMODE, BK, true, ARITH>(stream, p, epilogue);
+            return vitgemm::launch_persistent(stream, p, epilogue, p.group_m, ARITH);
         }
     }
 }
@@ -623,6 +668,8 @@ int vithip_gemm_f32(vithip_stream_t stream, const vithip_gemm_args *a) {
     }
     if (a->handover_test < 0 || a->handover_test > 1) return static_cast<int>(hipErrorInvalidValue);
     if (a->tile < 0 || (a->tile > 0 && a->tile < 6) || a->tile > 12 || a->group_m < 0 || a->group_m > 1024) return static_cast<int>(hipErrorInvalidValue);
+    if (a->arith != ARITH_F32 && (a->arith != ARITH_SPLIT3 || (a->tile != 0 && a->tile != 9 && a->tile != 10 && a->tile != 11)))
+        return static_cast<int>(hipErrorInvalidValue);  // the split: auto and tiles 9, 10, 11 only
     int epilogue = a->epilogue;
     if (a->ln_rows || a->ln_colsum) {  // LayerNorm fold, consumer side (ln_colsum NULL: the weight is the CENTRED one, see the header)
         if (!a->ln_rows || (epilogue != VITHIP_EPI_BIAS && epilogue != VITHIP_EPI_BIAS_GELU) ||
@@ -638,7 +685,8 @@ int vithip_gemm_f32(vithip_stream_t stream, const vithip_gemm_args *a) {
             return static_cast<int>(hipErrorInvalidValue);
         if (vithip_gemm_f32_stats_in_epilogue(a)) p.row_partials = a->stats_partials;
     }
-    const int rc = dispatch<A_DENSE>(static_cast<hipStream_t>(stream), p, epilogue, a->tile, a->group_m);
+    const int rc = a->arith == ARITH_SPLIT3 ? dispatch<A_DENSE, ARITH_SPLIT3>(static_cast<hipStream_t>(stream), p, epilogue, a->tile, a->group_m)
+                                            : dispatch<A_DENSE>(static_cast<hipStream_t>(stream), p, epilogue, a->tile, a->group_m);
     if (rc != 0 || !a->stats_out) return rc;
     if (p.stats_in_epilogue) return vithip_rowstats_finalize_f32(stream, a->stats_partials, a->M, a->N, a->stats_out);
     return vithip_rowstats_f32(stream, a->C, (size_t)a->ldc, a->stats_out, a->M, a->N);

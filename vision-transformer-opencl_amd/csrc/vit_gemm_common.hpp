@@ -14,7 +14,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int KALIGN = 32;  // K must be a multiple of this (covers both K steps below)
+constexpr int KALIGN = 32;  // K must be a multiple of this (covers every K step below)
 
 enum { A_DENSE = 0, A_PATCHES = 1 };
 // epilogue codes beyond the public three (vit_hip_kernels.h): the consumer side of the LayerNorm fold (ln_rows / ln_colsum set)
@@ -191,6 +191,79 @@ __device__ __forceinline__ void tile_coords(int tile, int tiles_m, int tiles_n, 
     tm = first + (in_g - tn * rows);
 }
 
+
+// ---- three-piece split: fp32 products on the bf16 matrix pipe (vithip_gemm_args.arith = 1) ----------------
+// Every fp32 operand x (A and W alike) is staged as three bf16 pieces, each rounded to nearest even:
+//     hi = bf16(x),  mid = bf16(x - hi),  lo = bf16(x - hi - mid),   x == hi + mid + lo exactly
+// (both differences are exact in fp32 and the last remainder has at most 8 significant bits).  a . w is then the sum of the
+// six piece products of rank <= 2 (mid.lo, lo.mid and lo.lo, below ~2^-26 |a.w|, are dropped); a bf16 x bf16 product is exact
+// in fp32.  One v_mfma_f32_32x32x16_bf16 per piece pair and 16-deep K step (1/16 of the cycles of v_mfma_f32_32x32x2_f32 per
+// product): 6/16 of the fp32 instruction's matrix time.  It writes the 32x32 accumulator layout of v_mfma_f32_32x32x2_f32, so
+// every epilogue above and below is shared.  Every output adds its K steps in ascending order and, inside a step, the six
+// products small terms first in SPLIT_TERMS order, into one accumulator: every tile shape gives the same bits, and A = I gives
+// W exactly (lo, + mid, + hi: each partial sum exact).
+enum { ARITH_F32 = 0, ARITH_SPLIT3 = 1 };
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+constexpr int SPLIT_BK = 16;  // K step of the split kernels
+// LDS row of the split kernels: [hi 16 x bf16 | mid 16 | lo 16 | 16 bytes of padding] = 28 dwords.  A ds_read_b128 of 16
+// consecutive rows (one piece, one half of the K step) then touches 16 distinct 4-bank slots: conflict-free like the fp32 rows.
+constexpr int SPLIT_LD = 28;  // floats
+// piece pairs (A piece, W piece) in accumulation order; 0 = hi, 1 = mid, 2 = lo
+constexpr int SPLIT_TERM_A[6] = {0, 2, 1, 0, 1, 0};
+constexpr int SPLIT_TERM_W[6] = {2, 0, 1, 1, 0, 0};
+
+__device__ __forceinline__ float bf16_to_f32(__bf16 v) {
+    return __builtin_bit_cast(float, (unsigned)__builtin_bit_cast(unsigned short, v) << 16);
+}
+// four consecutive-k values of one row -> the three pieces of each, written to their planes of the split LDS row `row`
+// (kc = k offset inside the K step, a multiple of 4: one ds_write_b64 per piece)
+__device__ __forceinline__ void split3_store(float *row, int kc, f32x4 x) {
+#pragma unroll
+    for (int piece = 0; piece < 3; ++piece) {
+        bf16x4 b;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) b[e] = (__bf16)x[e];  // v_cvt_pk_bf16_f32: round to nearest even
+        *reinterpret_cast<u32x2 *>(row + piece * 8 + kc / 2) = __builtin_bit_cast(u32x2, b);
+        if (piece < 2) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x[e] = x[e] - bf16_to_f32(b[e]);  // exact
+        }
+    }
+}
+// One 16-deep K step of a wave's TM x TN accumulators from the split LDS tiles As / Bs (at the lane's fragment: row r of the
+// wave's first block, k offset 8h): the three pieces of every fragment, then 6 x TM x TN matrix instructions, term by term (the
+// accumulators of one term are independent of each other).  restage(q), q < NS, is spread over the first half of them: the
+// caller's staging slots (global -> registers -> LDS) of later steps.
+template <int TM, int TN, int NS, typename Restage>
+__device__ __forceinline__ void split3_step(f32x16 (&acc)[TM][TN], const float *As, const float *Bs, Restage &&restage) {
+    bf16x8 a[TM][3], b[TN][3];
+#pragma unroll
+    for (int o = 0; o < 3; ++o) {  // the pieces in the order the first three terms need them: (hi, lo), (lo, hi), (mid, mid)
+        const int pa = SPLIT_TERM_A[o], pb = SPLIT_TERM_W[o];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) a[i][pa] = *reinterpret_cast<const bf16x8 *>(As + i * 32 * SPLIT_LD + pa * 8);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) b[j][pb] = *reinterpret_cast<const bf16x8 *>(Bs + j * 32 * SPLIT_LD + pb * 8);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    constexpr int NM = 6 * TM * TN, NR = NM / 2 > 0 ? NM / 2 : 1;
+#pragma unroll
+    for (int idx = 0; idx < NM; ++idx) {
+        const int t = idx / (TM * TN), i = (idx / TN) % TM, j = idx % TN;
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][SPLIT_TERM_A[t]], b[j][SPLIT_TERM_W[t]], acc[i][j], 0, 0, 0);
+        if (idx < NR) {
+            const int slot_before = (idx * NS) / NR, slot_after = ((idx + 1) * NS) / NR;
+            if (slot_after > slot_before) {
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int q = slot_before; q < slot_after; ++q) restage(q);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    }
+}
 
 // ---- epilogue ---------------------------------------------------------------------------------
 // Stores one workgroup tile.  A lane holds column n of 16 rows per accumulator; each store

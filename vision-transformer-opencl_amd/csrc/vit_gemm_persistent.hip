@@ -47,14 +47,20 @@ constexpr int SK_HEADER_BYTES = 4096, SK_MAX_OWNERS = 1000, SK_STAT_TAKEN = 1016
 // probe build only (libvit_mi355x_probe.so, tile codes 131-136), the product library holds DBG = 0 alone: 1 no epilogue stores,
 // 2 no staging loads inside the K loop, 3 no K-loop barrier, 4 no fragment reads, 5 no staging ds_writes, 6 = 2 + 5.
 // (What such builds measure is mostly the POWER of frozen operand data, not the removed instructions: DESIGN 4.1 item 11.)
-template <int BM, int BN, int WM, int WN, int EPI, bool STAMP = false, bool SK = false, int DBG = 0>
+// ARITH = ARITH_SPLIT3: the three-piece split on the bf16 matrix pipe (vit_gemm_common.hpp): the same walk, hand-over and
+// epilogues, K step SPLIT_BK, LDS rows of SPLIT_LD floats (56 KB at 128 x 128).
+template <int BM, int BN, int WM, int WN, int EPI, bool STAMP = false, bool SK = false, int DBG = 0, int ARITH = ARITH_F32>
 __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const GemmParams p) {
+    constexpr bool SPLIT = ARITH == ARITH_SPLIT3;
+    static_assert(!SPLIT || DBG == 0, "switch-off builds are fp32 only");
+    constexpr int PBK = SPLIT ? SPLIT_BK : vitgemm::PBK;  // K step
+    constexpr int PLD = SPLIT ? SPLIT_LD : vitgemm::PLD;  // LDS row (floats)
     constexpr int ROWS_PER_PASS = 256 / (PBK / 4);
     constexpr int WGN = BN / WN;
     constexpr int TM = WM / 32, TN = WN / 32;
     constexpr int A_CHUNKS = BM * (PBK / 4) / 256;
     constexpr int B_CHUNKS = BN * (PBK / 4) / 256;
-    constexpr int NC = PBK / 8;              // 8-deep chunks per K step
+    constexpr int NC = PBK / 8;              // 8-deep chunks per K step (fp32)
     constexpr int NS = A_CHUNKS + B_CHUNKS;  // staged float4 per thread per K step
     constexpr int NM = 4 * TM * TN;          // MFMAs per chunk
     static_assert((BM / WM) * WGN == 4, "4 waves per workgroup");
@@ -217,33 +223,37 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
 #pragma unroll
         for (int i = 0; i < B_CHUNKS; ++i) b_stage[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, b_src[i], k0 * 4, 0));
     };
+    // a staged float4 -> its LDS row: as it is, or as its three pieces (split)
+    auto stage_write = [&](float *row, f32x4 v) __attribute__((always_inline)) {
+        if constexpr (SPLIT) split3_store(row, ld_kc, v);
+        else *reinterpret_cast<f32x4 *>(row + ld_kc) = v;
+    };
     auto store_step = [&](int buf) {
         float *As = As0 + buf * BM * PLD, *Bs = Bs0 + buf * BN * PLD;
 #pragma unroll
-        for (int i = 0; i < A_CHUNKS; ++i)
-            *reinterpret_cast<f32x4 *>(As + (ld_row + i * ROWS_PER_PASS) * PLD + ld_kc) = a_stage[i];
+        for (int i = 0; i < A_CHUNKS; ++i) stage_write(As + (ld_row + i * ROWS_PER_PASS) * PLD, a_stage[i]);
 #pragma unroll
-        for (int i = 0; i < B_CHUNKS; ++i)
-            *reinterpret_cast<f32x4 *>(Bs + (ld_row + i * ROWS_PER_PASS) * PLD + ld_kc) = b_stage[i];
+        for (int i = 0; i < B_CHUNKS; ++i) stage_write(Bs + (ld_row + i * ROWS_PER_PASS) * PLD, b_stage[i]);
     };
     // one staging slot: write the float4 fetched a step ago, then refetch it for two steps ahead
     auto restage_slot = [&](int q, int buf, int k0) {
         if (q < A_CHUNKS) {
             float *As = As0 + buf * BM * PLD;
-            if (DBG != 5 && DBG != 6) *reinterpret_cast<f32x4 *>(As + (ld_row + q * ROWS_PER_PASS) * PLD + ld_kc) = a_stage[q];
+            if (DBG != 5 && DBG != 6) stage_write(As + (ld_row + q * ROWS_PER_PASS) * PLD, a_stage[q]);
             if (DBG != 2 && DBG != 6) a_stage[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, a_src[q], k0 * 4, 0));
         } else {
             const int qb = q - A_CHUNKS;
             float *Bs = Bs0 + buf * BN * PLD;
-            if (DBG != 5 && DBG != 6) *reinterpret_cast<f32x4 *>(Bs + (ld_row + qb * ROWS_PER_PASS) * PLD + ld_kc) = b_stage[qb];
+            if (DBG != 5 && DBG != 6) stage_write(Bs + (ld_row + qb * ROWS_PER_PASS) * PLD, b_stage[qb]);
             if (DBG != 2 && DBG != 6) b_stage[qb] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, b_src[qb], k0 * 4, 0));
         }
     };
 
     const int a_frag_off = (wm * WM + r) * PLD + h * 4;
     const int b_frag_off = (wn * WN + r) * PLD + h * 4;
-    f32x4 af[2][TM], bf[2][TN];
+    f32x4 af[2][TM], bf[2][TN];  // fp32 only (the split reads its pieces inside split3_step)
     auto read_frags = [&](int buf, int c, int set) {
+        if constexpr (SPLIT) return;
         const float *As = As0 + buf * BM * PLD + a_frag_off + c * 8;
         const float *Bs = Bs0 + buf * BN * PLD + b_frag_off + c * 8;
 #pragma unroll
@@ -374,6 +384,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
     __syncthreads();
     read_frags(0, 0, 0);
     if (DBG == 4) read_frags(0, 1, 1);
+    (void)af; (void)bf;
 
     if constexpr (STAMP) st_loop0 = __builtin_amdgcn_s_memtime();
     int cur = 0;
@@ -391,6 +402,14 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
         }
+        if constexpr (SPLIT) {
+            // one 16-deep step of the split: pieces from buffer `cur`, the staged step g + 1 split into cur^1 and the loads of step
+            // g + 2 in the first half of the matrix instructions, then the one barrier (the fp32 loop's swap point)
+            split3_step<TM, TN, NS>(acc, As0 + cur * BM * PLD + a_frag_off, Bs0 + cur * BN * PLD + b_frag_off,
+                                    [&](int q) __attribute__((always_inline)) { restage_slot(q, cur ^ 1, k_ahead); });
+            advance_load_cursor();
+            __syncthreads();
+        } else
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             if (c + 1 < NC && DBG != 4) read_frags(cur, c + 1, (c + 1) & 1);
@@ -450,7 +469,10 @@ static int persistent_wgs() {
 
 // K-steps of a last-round tile that a helper workgroup runs (0: the hand-over does not pay) for the 128 x 128 persistent walk
 // on a grid of `wgs` workgroups (0: ask the current device) with `slots` parking slots
-int persistent_piece_steps(int M, int N, int K, int slots, int wgs) {
+// (returned in K-steps of `kstep` deep: PBK for fp32, SPLIT_BK for the split.  The choice and the piece's depth in k are made in
+// 32-deep steps for both, so that the split hands over exactly where the fp32 arithmetic does -- QKV at batch 256 included, which
+// stays without pieces)
+int persistent_piece_steps(int M, int N, int K, int slots, int wgs, int kstep) {
     if (wgs <= 0) wgs = persistent_wgs();
     if (wgs <= 0) return 0;
     const int total = ((M + 127) / 128) * ((N + 127) / 128);
@@ -462,10 +484,10 @@ int persistent_piece_steps(int M, int N, int K, int slots, int wgs) {
     // a hand-over costs about 3 K-steps (64 KB out, 64 KB in through uncached memory, the flag): worth it when the walk gets
     // at least 8 steps shorter (measured at batch 256: fc2 -5 %, out_proj -5 % (nk = 24, 8 of 120 saved), fc1 -1.7 %;
     // QKV would save 6 of 336 with six 3-step pieces per helper: off)
-    return (x >= 4 && nk - c * x >= 8) ? x : 0;
+    return (x >= 4 && nk - c * x >= 8) ? x * (PBK / kstep) : 0;
 }
 
-template <int BM, int BN, int WM, int WN>
+template <int BM, int BN, int WM, int WN, int ARITH = ARITH_F32>
 int launch_persistent_tile(hipStream_t stream, GemmParams &p, int epilogue, int group_m) {
     const int wgs = persistent_wgs();
     if (wgs <= 0) return static_cast<int>(hipErrorInvalidDevice);
@@ -476,26 +498,26 @@ int launch_persistent_tile(hipStream_t stream, GemmParams &p, int epilogue, int 
     const dim3 grid(total < wgs ? total : wgs), block(256);
     // helper pieces (see the head of this file): on when the caller lent a workspace, a partial last round exists and the
     // piece is long enough to be worth a 64 KB hand-over (>= 4 K-steps)
-    p.sk_x = (p.sk_ws && BM == 128 && BN == 128) ? persistent_piece_steps(p.M, p.N, p.K, p.sk_slots, wgs) : 0;
+    p.sk_x = (p.sk_ws && BM == 128 && BN == 128) ? persistent_piece_steps(p.M, p.N, p.K, p.sk_slots, wgs, ARITH == ARITH_SPLIT3 ? SPLIT_BK : PBK) : 0;
     if (p.sk_x > 0) {
         switch (epilogue) {
             case VITHIP_EPI_BIAS:
-                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS, false, true>), grid, block, 0, stream, p);
+                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS, false, true, 0, ARITH>), grid, block, 0, stream, p);
                 break;
             case VITHIP_EPI_BIAS_GELU:
-                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_GELU, false, true>), grid, block, 0, stream, p);
+                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_GELU, false, true, 0, ARITH>), grid, block, 0, stream, p);
                 break;
             case VITHIP_EPI_BIAS_RESIDUAL:
-                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_RESIDUAL, false, true>), grid, block, 0, stream, p);
+                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_RESIDUAL, false, true, 0, ARITH>), grid, block, 0, stream, p);
                 break;
             case EPI_BIAS_LN:
-                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_LN, false, true>), grid, block, 0, stream, p);
+                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_LN, false, true, 0, ARITH>), grid, block, 0, stream, p);
                 break;
             case EPI_BIAS_GELU_LN:
-                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_GELU_LN, false, true>), grid, block, 0, stream, p);
+                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_GELU_LN, false, true, 0, ARITH>), grid, block, 0, stream, p);
                 break;
             case EPI_RESIDUAL_STATS:
-                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_RESIDUAL_STATS, false, true>), grid, block, 0, stream, p);
+                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_RESIDUAL_STATS, false, true, 0, ARITH>), grid, block, 0, stream, p);
                 break;
             default:
                 return static_cast<int>(hipErrorInvalidValue);
@@ -504,22 +526,22 @@ int launch_persistent_tile(hipStream_t stream, GemmParams &p, int epilogue, int 
     }
     switch (epilogue) {
         case VITHIP_EPI_BIAS:
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS>), grid, block, 0, stream, p);
+            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS, false, false, 0, ARITH>), grid, block, 0, stream, p);
             break;
         case VITHIP_EPI_BIAS_GELU:
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_GELU>), grid, block, 0, stream, p);
+            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_GELU, false, false, 0, ARITH>), grid, block, 0, stream, p);
             break;
         case VITHIP_EPI_BIAS_RESIDUAL:
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_RESIDUAL>), grid, block, 0, stream, p);
+            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_RESIDUAL, false, false, 0, ARITH>), grid, block, 0, stream, p);
             break;
         case EPI_BIAS_LN:
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_LN>), grid, block, 0, stream, p);
+            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_LN, false, false, 0, ARITH>), grid, block, 0, stream, p);
             break;
         case EPI_BIAS_GELU_LN:
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_GELU_LN>), grid, block, 0, stream, p);
+            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_GELU_LN, false, false, 0, ARITH>), grid, block, 0, stream, p);
             break;
         case EPI_RESIDUAL_STATS:
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_RESIDUAL_STATS>), grid, block, 0, stream, p);
+            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_RESIDUAL_STATS, false, false, 0, ARITH>), grid, block, 0, stream, p);
             break;
         default:
             return static_cast<int>(hipErrorInvalidValue);
@@ -583,12 +605,13 @@ int launch_persistent_switchoff(hipStream_t stream, GemmParams &p, int epilogue,
 #endif
 
 // Entry used by vit_gemm.hip's dispatcher.  Needs at least 4 K steps per tile (K >= 128).
-int launch_persistent(hipStream_t stream, GemmParams &p, int epilogue, int group_m) {
+int launch_persistent(hipStream_t stream, GemmParams &p, int epilogue, int group_m, int arith) {
     // residual GEMM whose caller also wants the row statistics of what it stores: in the epilogue when the columns are whole tiles
     if (epilogue == VITHIP_EPI_BIAS_RESIDUAL && p.row_partials && p.N % 128 == 0) {
         epilogue = EPI_RESIDUAL_STATS;
         p.stats_in_epilogue = 1;
     }
+    if (arith == ARITH_SPLIT3) return launch_persistent_tile<128, 128, 64, 64, ARITH_SPLIT3>(stream, p, epilogue, group_m);
     return launch_persistent_tile<128, 128, 64, 64>(stream, p, epilogue, group_m);
 }
 

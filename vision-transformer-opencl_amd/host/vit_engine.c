@@ -43,6 +43,7 @@ struct vit_engine {
     float **w;                   /* device pointer per weight index */
     unsigned short *wblob16;     /* the bf16 section inside wblob (dtype bf16 only) */
     int fold;                    /* LayerNorm fold active (vit_engine_options.ln_fold) */
+    int split;                   /* encoder GEMMs on the three-piece split (vit_engine_options.fp32_split; fp32 engines) */
     unsigned short *wfold16;     /* per layer [gamma1-folded in_proj 3D x D | gamma2-folded fc1 H x D] (bf16 engines) */
     float *wfold32;              /* the same two operands as fp32 products gamma * W (fp32 engines) */
     float *wfoldf;               /* per layer [colsum qkv 3D | bias qkv 3D | colsum fc1 H | bias fc1 H] */
@@ -137,6 +138,7 @@ void vit_engine_default_options(vit_engine_options *opt) {
     opt->ln_fold = 0;
     opt->gemm_handover_test = 0;
     opt->host_first_piece = 0;
+    opt->fp32_split = 0;
 }
 
 static int fail(vit_engine *e, int code, const char *fmt, ...) {
@@ -257,6 +259,9 @@ int vit_engine_create(vit_engine **out, const vit_config *cfg, const vit_engine_
             HIP_TRY(e, vithip_malloc((void **)&e->wfoldf, L * (6 * D + 2 * H) * sizeof(float)));
         }
     }
+    /* the split runs at every K of the model (K % 32 == 0 is checked for every fp32 GEMM anyway) and every M: whether it is on
+     * depends on the options alone, never on the batch */
+    e->split = e->opt.dtype == VIT_DTYPE_F32 && e->opt.fp32_split >= 0;
     if (e->opt.dtype == VIT_DTYPE_F32 && e->opt.ln_fold >= 0) {
         /* fp32 fold: the consumer epilogue exists in every fp32 GEMM kernel; the row statistics kernel wants whole 64-column strips */
         const int ok = e->cfg.embed_dim % 64 == 0 && e->cfg.embed_dim <= 2048;
@@ -543,6 +548,7 @@ static int gemm(vit_engine *e, vithip_stream_t s, const gemm_desc *g, int *stats
         for (int j = 0; j < VIT_MAX_LANES - 1; ++j)
             if (s == e->aux_stream[j]) a.workspace = e->gemm_ws[j + 1];
         a.handover_test = e->opt.gemm_handover_test; a.tile = e->opt.gemm_tile;
+        a.arith = e->split && g->stage != VIT_STAGE_HEAD; /* every encoder GEMM (the embedding does not come through here) */
         a.A = g->A; a.lda = g->lda; a.W = g->W; a.ldw = g->K; a.bias = g->bias; a.residual = res; a.ldr = ldr;
         a.C = g->C; a.ldc = g->ldc; a.M = g->M; a.N = g->N; a.K = g->K; a.epilogue = g->role;
         a.ln_rows = g->ln_rows; a.ln_colsum = g->ln_colsum;
