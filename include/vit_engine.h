@@ -133,6 +133,27 @@ int vit_engine_sync(vit_engine *e);
 int vit_engine_forward_host(vit_engine *e, const float *const *images, int n, float *const *probs);
 
 /*
+ * The same two forwards from 8-bit pixels, as image decoders produce them: images [S][S][C] uint8, channels interleaved.  The
+ * engine normalises them on the device, in front of the patch embedding of each lane:
+ *     x[c][h][w] = ((float)img[h][w][c] / 255.0f - mean[c]) / std[c]
+ * (torchvision's ToTensor() + Normalize(mean, std); vithip_images_u8_to_f32), so the probabilities are bit-identical to the fp32
+ * forward of the image normalised by that formula on the host, for every option and dtype.  A quarter of the fp32 bytes cross the
+ * host gather and PCIe.  mean / std: HOST arrays of cfg.in_chans floats, read during the call.  VIT_ERR_ARG (the engine stays
+ * usable) for NULL pointers, n <= 0, a non-finite mean or std, a zero std, in_chans > 4 or, device path, d_images not 4-byte
+ * aligned.
+ *
+ * Device path: d_images [n][S][S][C] in HBM, asynchronous on `stream` like vit_engine_forward_device (a graph of use_graph is
+ * keyed on the input kind and the mean / std values too).  The fp32 images live in the engine's staging until the call's
+ * kernels have run.
+ * Host path: images[i] separately allocated [S][S][C] buffers, uploaded as bytes through the pipeline of
+ * vit_engine_forward_host (the first u8 call allocates 2 x max_batch images of byte staging on the device); blocking.
+ */
+int vit_engine_forward_device_u8(vit_engine *e, const unsigned char *d_images, int n, const float *mean, const float *std,
+                                 float *d_probs, int *d_top1_label, float *d_top1_prob, void *stream);
+int vit_engine_forward_host_u8(vit_engine *e, const unsigned char *const *images, int n, const float *mean, const float *std,
+                               float *const *probs);
+
+/*
  * The fp32 GEMMs' helper-piece hand-over (csrc/vit_gemm_persistent.hip) since the last call, summed over the lanes: tiles whose
  * first K-steps came from a helper workgroup / tiles whose owner found no piece when it looked and computed all of it.  The
  * second number is lost time, never a wrong result (nothing in the hand-over waits or gives up).  Synchronises the device.

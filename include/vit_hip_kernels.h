@@ -294,6 +294,18 @@ int vithip_softmax_top1_f32(vithip_stream_t stream, const float *logits, int ld_
                             float *probs, int ld_probs, int *top1_label, float *top1_prob,
                             int rows, int classes);
 
+/*
+ * The model input from 8-bit pixels (csrc/vit_input.hip): src [n][S][S][C] uint8, channels interleaved as image decoders
+ * write them -> dst [n][C][S][S] fp32,
+ *     dst[i][c][h][w] = ((float)src[i][h][w][c] / 255.0f - mean[c]) / std[c]
+ * torchvision's ToTensor() + Normalize(mean, std), every step one fp32 IEEE operation (true divisions): bit for bit what a
+ * CPU computes from the same formula.  mean / std: HOST arrays of chans floats, copied into the launch (a captured graph keeps
+ * the values of its capture).  Needs 1 <= chans <= 4, n >= 1, S % 4 == 0, src 4-byte and dst 16-byte aligned, every mean[c]
+ * finite, every std[c] finite and non-zero; hipErrorInvalidValue otherwise.
+ */
+int vithip_images_u8_to_f32(vithip_stream_t stream, const unsigned char *src, float *dst, int n, int img_size, int chans,
+                            const float *mean, const float *std);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,9 @@ f32p = C.POINTER(C.c_float)
 i32p = C.POINTER(C.c_int)
 
 STAGES = ("embed", "ln", "qkv", "attn", "outproj", "fc1", "fc2", "head", "softmax")
+# torchvision's ImageNet normalisation (transforms.Normalize(mean, std) of its vit_b_16 weights), for the 8-bit input
+IMAGENET_MEAN = (0.485, 0.456, 0.406)
+IMAGENET_STD = (0.229, 0.224, 0.225)
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL = 0, 1, 2
 ARITH_F32, ARITH_SPLIT3 = 0, 1   # vithip_gemm_args.arith
 
@@ -142,6 +145,10 @@ def lib() -> C.CDLL:
         L.vit_engine_forward_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p]
         L.vit_engine_forward_host.argtypes = [C.c_void_p, C.POINTER(f32p), C.c_int, C.POINTER(f32p)]
+        L.vit_engine_forward_device_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, f32p, f32p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p]
+        L.vit_engine_forward_host_u8.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, f32p, f32p, C.POINTER(f32p)]
+        L.vithip_images_u8_to_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, f32p, f32p]
         L.vit_engine_read_logits.argtypes = [C.c_void_p, f32p, C.c_int]
         L.vit_engine_sync.argtypes = [C.c_void_p]
         L.vit_engine_get_stage_times.argtypes = [C.c_void_p, C.POINTER(CStageTimes)]
@@ -584,6 +591,31 @@ def softmax_top1(logits):
     return dp.numpy(), dlab.numpy(), dpr.numpy()
 
 
+def _norm_consts(mean, std, chans: int):
+    """mean / std as the host float arrays of `chans` entries the C-ABI reads (None stays NULL)."""
+    out = []
+    for v in (mean, std):
+        if v is None:
+            out.append(None)
+            continue
+        v = np.ascontiguousarray(v, np.float32).reshape(-1)
+        if v.size != chans:
+            raise ValueError(f"expected {chans} normalisation constants, got {v.size}")
+        out.append((C.c_float * chans)(*v.tolist()))
+    return out
+
+
+def images_u8_to_f32(images, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
+    """vithip_images_u8_to_f32: uint8 images [n][S][S][C] -> [n][C][S][S] fp32, ((float)u / 255 - mean[c]) / std[c]."""
+    images = np.ascontiguousarray(images, np.uint8)
+    n, S, S2, chans = images.shape
+    assert S == S2
+    m, s = _norm_consts(mean, std, chans)
+    ds, dd = DeviceArray.from_numpy(images), DeviceArray((n, chans, S, S))
+    hip_check(lib().vithip_images_u8_to_f32(None, ds.ptr, dd.ptr, n, S, chans, m, s), "vithip_images_u8_to_f32")
+    return dd.numpy()
+
+
 def device_info(device: int = 0) -> dict:
     info = CDeviceInfo()
     hip_check(lib().vithip_get_device_info(device, C.byref(info)), "vithip_get_device_info")
@@ -654,6 +686,25 @@ class Engine:
         self._check(lib().vit_engine_forward_device(self._h, d_images, n, d_probs, d_label or None,
                                                     d_prob or None, stream or None),
                     "vit_engine_forward_device")
+
+    def forward_u8(self, images: np.ndarray, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
+        """Host path from 8-bit pixels: images [n][S][S][C] uint8 (as decoders write them), normalised on the device by
+        ((float)u / 255 - mean[c]) / std[c]; per-image pointers in, per-image rows out."""
+        images = np.ascontiguousarray(images, np.uint8)
+        n = images.shape[0]
+        m, s = _norm_consts(mean, std, self.cfg.in_chans)
+        probs = np.empty((n, self.cfg.num_classes), np.float32)
+        in_ptrs = (C.c_void_p * n)(*[images[i].ctypes.data for i in range(n)])
+        out_ptrs = (f32p * n)(*[probs[i].ctypes.data_as(f32p) for i in range(n)])
+        self._check(lib().vit_engine_forward_host_u8(self._h, in_ptrs, n, m, s, out_ptrs), "vit_engine_forward_host_u8")
+        return probs
+
+    def forward_device_u8(self, d_images: int, n: int, d_probs: int, mean=IMAGENET_MEAN, std=IMAGENET_STD, d_label: int = 0,
+                          d_prob: int = 0, stream: int = 0) -> None:
+        """Device-resident path from 8-bit pixels [n][S][S][C] in HBM (raw addresses), async on `stream`."""
+        m, s = _norm_consts(mean, std, self.cfg.in_chans)
+        self._check(lib().vit_engine_forward_device_u8(self._h, d_images, n, m, s, d_probs, d_label or None, d_prob or None,
+                                                       stream or None), "vit_engine_forward_device_u8")
 
     def sync(self) -> None:
         self._check(lib().vit_engine_sync(self._h), "vit_engine_sync")

@@ -16,6 +16,7 @@
 #include "vit_engine.h"
 
 #include <limits.h>
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -27,6 +28,14 @@
 
 #define VIT_MAX_LANES 4
 #define MAX_EVENTS 4096   /* stage brackets kept in flight before they are read back */
+#define VIT_MAX_U8_CHANS 4 /* vithip_images_u8_to_f32 */
+
+/* What a forward reads, besides where: fp32 images [C][S][S] as the model takes them, or 8-bit pixels [S][S][C] that stage_embed
+ * normalises into fp32 staging in front of the patch embedding.  Zero-filled before use: the graph cache compares it bytewise. */
+typedef struct {
+    int u8;
+    float mean[VIT_MAX_U8_CHANS], std[VIT_MAX_U8_CHANS];
+} vit_input;
 
 struct vit_engine {
     vit_config cfg;
@@ -55,7 +64,7 @@ struct vit_engine {
     int n_cus;                   /* compute units of the device */
     /* use_graph: the captured forward and what it was captured for */
     vithip_graph_t graph;
-    const float *g_images; float *g_probs; int *g_label; float *g_prob; int g_n;
+    const void *g_images; vit_input g_in; float *g_probs; int *g_label; float *g_prob; int g_n;
     unsigned short **w16;        /* per weight index; NULL for tensors that stay fp32 */
     int weights_loaded;
 
@@ -66,6 +75,11 @@ struct vit_engine {
     float *pin_in[2], *pin_out[2];       /* pinned host */
     vithip_stream_t copy_stream;
     vithip_event_t ev_h2d[2], ev_done[2];
+    /* 8-bit input: the host path's byte staging (allocated by the first u8 host call); the device path normalises into
+     * in_stage[0], and ev_in_stage (recorded behind it on the caller's stream) keeps the next host call's uploads behind it */
+    unsigned char *in8_stage[2];
+    vithip_event_t ev_in_stage;
+    int in_stage_pending;
     int last_rows;
 
     /* stage profiling */
@@ -308,8 +322,9 @@ void vit_engine_destroy(vit_engine *e) {
     vithip_free(e->z); vithip_free(e->logits);
     for (int j = 0; j < VIT_MAX_LANES; ++j) vithip_gemm_f32_workspace_destroy(e->gemm_ws[j]);
     if (e->copy_stream) { vithip_stream_sync(e->copy_stream); vithip_stream_destroy(e->copy_stream); }
+    if (e->ev_in_stage) vithip_event_destroy(e->ev_in_stage);
     for (int b = 0; b < 2; ++b) {
-        vithip_free(e->in_stage[b]); vithip_free(e->out_stage[b]);
+        vithip_free(e->in_stage[b]); vithip_free(e->out_stage[b]); vithip_free(e->in8_stage[b]);
         if (e->pin_in[b]) vithip_host_free(e->pin_in[b]);
         if (e->pin_out[b]) vithip_host_free(e->pin_out[b]);
         if (e->ev_h2d[b]) vithip_event_destroy(e->ev_h2d[b]);
@@ -355,6 +370,7 @@ int vit_engine_set_profile(vit_engine *e, int on) {
 static void drop_graph(vit_engine *e) {
     if (e->graph) { vithip_graph_destroy(e->graph); e->graph = NULL; }
     e->g_n = 0; e->g_images = NULL; e->g_probs = NULL; e->g_label = NULL; e->g_prob = NULL;
+    memset(&e->g_in, 0, sizeof(e->g_in));
 }
 
 /* (Re)allocate the device blob for this model and point w[] / w16[] into it (no data yet). */
@@ -620,8 +636,9 @@ typedef struct {
 /* element i of an array of esz-byte elements */
 static void *at(const void *p, size_t i, size_t esz) { return (char *)p + i * esz; }
 
-/* conv_proj + flatten_transpose + class_token + pos_emb (ViT_seq.c:25-101) */
-static int stage_embed(chunk_ctx *c, const float *d_images) {
+/* conv_proj + flatten_transpose + class_token + pos_emb (ViT_seq.c:25-101).  8-bit input: each lane first normalises its own
+ * images into the same rows of f32_stage (one more launch of the embed stage) and embeds from there. */
+static int stage_embed(chunk_ctx *c, const void *d_images, const vit_input *in, float *f32_stage) {
     vit_engine *e = c->e;
     const vit_config *cfg = &e->cfg;
     float **w = e->w;
@@ -633,13 +650,20 @@ static int stage_embed(chunk_ctx *c, const float *d_images) {
                         (size_t)pk <= 2 * (size_t)c->H;
     for (int j = 0; j < c->L; ++j) {
         const vit_lane *ln = &c->lane[j];
+        const float *images = in->u8 ? f32_stage + ln->off * img : (const float *)d_images + ln->off * img;
+        if (in->u8) {
+            HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_EMBED));
+            HIP_TRY(e, vithip_images_u8_to_f32(ln->s, (const unsigned char *)d_images + ln->off * img, f32_stage + ln->off * img,
+                                               ln->n, cfg->img_size, cfg->in_chans, in->mean, in->std));
+            HIP_TRY(e, stage_end(e, ln->s));
+        }
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_EMBED));
         if (embed16)
-            HIP_TRY(e, vithip_patch_embed_bf16(ln->s, d_images + ln->off * img, e->w16[1], w[2], w[0], w[3], ln->x,
+            HIP_TRY(e, vithip_patch_embed_bf16(ln->s, images, e->w16[1], w[2], w[0], w[3], ln->x,
                                                (unsigned short *)e->hbuf + (size_t)ln->off * (c->T - 1) * pk,
                                                ln->n, cfg->img_size, cfg->patch_size, cfg->in_chans, c->D));
         else
-            HIP_TRY(e, vithip_patch_embed_f32(ln->s, d_images + ln->off * img, w[1], w[2], w[0], w[3], ln->x, ln->n,
+            HIP_TRY(e, vithip_patch_embed_f32(ln->s, images, w[1], w[2], w[0], w[3], ln->x, ln->n,
                                               cfg->img_size, cfg->patch_size, cfg->in_chans, c->D));
         HIP_TRY(e, stage_end(e, ln->s));
     }
@@ -800,8 +824,9 @@ static int stage_head(chunk_ctx *c, float *d_probs, int *d_label, float *d_prob)
     return VIT_OK;
 }
 
-static int forward_chunk(vit_engine *e, vithip_stream_t s, const float *d_images, int nb, float *d_probs,
-                         int *d_label, float *d_prob) {
+/* d_images: the chunk's first image, of the kind `in` says; f32_stage: where 8-bit images are normalised to (max_batch images) */
+static int forward_chunk(vit_engine *e, vithip_stream_t s, const void *d_images, const vit_input *in, float *f32_stage, int nb,
+                         float *d_probs, int *d_label, float *d_prob) {
     const vit_config *cfg = &e->cfg;
     chunk_ctx ctx, *c = &ctx;
     c->e = e;
@@ -845,7 +870,7 @@ static int forward_chunk(vit_engine *e, vithip_stream_t s, const float *d_images
         HIP_TRY(e, vithip_event_record(e->ev_fork, s));
         for (int j = 1; j < c->L; ++j) HIP_TRY(e, vithip_stream_wait_event(c->lane[j].s, e->ev_fork));
     }
-    RUN(stage_embed(c, d_images));
+    RUN(stage_embed(c, d_images, in, f32_stage));
     for (int l = 0; l < cfg->depth; ++l) RUN(encoder_layer(c, l));
     RUN(stage_head(c, d_probs, d_label, d_prob));
     for (int j = 1; j < c->L; ++j) { /* join */
@@ -865,21 +890,48 @@ static int chunk_limit(const vit_engine *e) {
     return cap < e->opt.max_batch ? (int)cap : e->opt.max_batch;
 }
 
-int vit_engine_forward_device(vit_engine *e, const float *d_images, int n, float *d_probs,
-                              int *d_top1_label, float *d_top1_prob, void *stream) {
-    if (!e) return VIT_ERR_ARG;
-    if (!d_images || !d_probs || n <= 0) return fail(e, VIT_ERR_ARG, "forward_device: bad arguments (n=%d)", n);
+/* The 8-bit input of a call (vit_engine_forward_device_u8 / _host_u8), its normalisation checked. */
+static int input_u8(vit_engine *e, const char *who, const float *mean, const float *std, vit_input *in) {
+    memset(in, 0, sizeof(*in));
+    in->u8 = 1;
+    if (!mean || !std) return fail(e, VIT_ERR_ARG, "%s: mean and std are required", who);
+    if (e->cfg.in_chans > VIT_MAX_U8_CHANS)
+        return fail(e, VIT_ERR_ARG, "%s: 8-bit input takes at most %d channels (in_chans = %d)", who, VIT_MAX_U8_CHANS, e->cfg.in_chans);
+    for (int c = 0; c < e->cfg.in_chans; ++c) {
+        if (!isfinite(mean[c]) || !isfinite(std[c]) || std[c] == 0.0f)
+            return fail(e, VIT_ERR_ARG, "%s: channel %d: mean (%g) and std (%g) must be finite, std non-zero", who, c, mean[c], std[c]);
+        in->mean[c] = mean[c];
+        in->std[c] = std[c];
+    }
+    return VIT_OK;
+}
+
+/* An 8-bit device-path call normalises into in_stage[0] and uses it until s gets past its kernels: the next host-pointer call's
+ * uploads wait for that (ev_in_stage). */
+static int in_stage_taken(vit_engine *e, const vit_input *in, vithip_stream_t s) {
+    if (!in->u8) return VIT_OK;
+    HIP_TRY(e, vithip_event_record(e->ev_in_stage, s));
+    e->in_stage_pending = 1;
+    return VIT_OK;
+}
+
+/* The device-resident forward of either input kind: chunks of at most chunk_limit() images, the use_graph cache.  8-bit chunks
+ * are normalised into in_stage[0]; chunks run one after the other on s (a chunk's lanes fork behind the previous chunk's join). */
+static int forward_device_in(vit_engine *e, const void *d_images, const vit_input *in, int n, float *d_probs,
+                             int *d_top1_label, float *d_top1_prob, void *stream) {
     if (!e->weights_loaded) return fail(e, VIT_ERR_STATE, "forward before vit_engine_load_weights()");
     vithip_stream_t s = stream ? (vithip_stream_t)stream : e->stream;
-    const size_t img = (size_t)e->cfg.in_chans * e->cfg.img_size * e->cfg.img_size;
+    const size_t img = (size_t)e->cfg.in_chans * e->cfg.img_size * e->cfg.img_size * (in->u8 ? 1 : sizeof(float)); /* bytes */
     const size_t NC = (size_t)e->cfg.num_classes;
     HIP_TRY(e, vithip_set_device(e->opt.device)); /* the current device is per host thread: several engines may share a process */
+    if (in->u8 && !e->ev_in_stage) HIP_TRY(e, vithip_event_create(&e->ev_in_stage));
     const int chunk = chunk_limit(e);
     const int graphable = e->opt.use_graph && !e->opt.profile && e->opt.lanes == 1 && s != NULL;
-    if (graphable && e->graph && e->g_n == n && e->g_images == d_images && e->g_probs == d_probs &&
-        e->g_label == d_top1_label && e->g_prob == d_top1_prob) {
+    /* the key holds the input kind and the normalisation too: both are baked into the captured kernel arguments */
+    if (graphable && e->graph && e->g_n == n && e->g_images == d_images && !memcmp(&e->g_in, in, sizeof(*in)) &&
+        e->g_probs == d_probs && e->g_label == d_top1_label && e->g_prob == d_top1_prob) {
         HIP_TRY(e, vithip_graph_launch(e->graph, s));
-        return VIT_OK;
+        return in_stage_taken(e, in, s);
     }
     if (graphable) {
         if (e->graph) { vithip_graph_destroy(e->graph); e->graph = NULL; }
@@ -887,7 +939,7 @@ int vit_engine_forward_device(vit_engine *e, const float *d_images, int n, float
     }
     for (int done = 0; done < n; done += chunk) {
         const int nb = n - done < chunk ? n - done : chunk;
-        int rc = forward_chunk(e, s, d_images + (size_t)done * img, nb, d_probs + (size_t)done * NC,
+        int rc = forward_chunk(e, s, (const char *)d_images + (size_t)done * img, in, e->in_stage[0], nb, d_probs + (size_t)done * NC,
                                d_top1_label ? d_top1_label + done : NULL,
                                d_top1_prob ? d_top1_prob + done : NULL);
         if (rc) {
@@ -903,10 +955,30 @@ int vit_engine_forward_device(vit_engine *e, const float *d_images, int n, float
     }
     if (graphable) { /* nothing ran yet: the launches above were recorded; instantiate and run them */
         HIP_TRY(e, vithip_graph_end(s, &e->graph));
-        e->g_n = n; e->g_images = d_images; e->g_probs = d_probs; e->g_label = d_top1_label; e->g_prob = d_top1_prob;
+        e->g_n = n; e->g_images = d_images; e->g_in = *in; e->g_probs = d_probs; e->g_label = d_top1_label; e->g_prob = d_top1_prob;
         HIP_TRY(e, vithip_graph_launch(e->graph, s));
     }
-    return VIT_OK;
+    return in_stage_taken(e, in, s);
+}
+
+int vit_engine_forward_device(vit_engine *e, const float *d_images, int n, float *d_probs,
+                              int *d_top1_label, float *d_top1_prob, void *stream) {
+    if (!e) return VIT_ERR_ARG;
+    if (!d_images || !d_probs || n <= 0) return fail(e, VIT_ERR_ARG, "forward_device: bad arguments (n=%d)", n);
+    vit_input in;
+    memset(&in, 0, sizeof(in));
+    return forward_device_in(e, d_images, &in, n, d_probs, d_top1_label, d_top1_prob, stream);
+}
+
+int vit_engine_forward_device_u8(vit_engine *e, const unsigned char *d_images, int n, const float *mean, const float *std,
+                                 float *d_probs, int *d_top1_label, float *d_top1_prob, void *stream) {
+    if (!e) return VIT_ERR_ARG;
+    if (!d_images || !d_probs || n <= 0) return fail(e, VIT_ERR_ARG, "forward_device_u8: bad arguments (n=%d)", n);
+    if ((size_t)d_images & 3) return fail(e, VIT_ERR_ARG, "forward_device_u8: d_images must be 4-byte aligned");
+    vit_input in;
+    const int rc = input_u8(e, "forward_device_u8", mean, std, &in);
+    if (rc) return rc;
+    return forward_device_in(e, d_images, &in, n, d_probs, d_top1_label, d_top1_prob, stream);
 }
 
 int vit_engine_sync(vit_engine *e) {
@@ -927,31 +999,49 @@ static int gather_threads(void) {
     int n = omp_get_num_procs();
     return n < 1 ? 1 : (n > GATHER_THREADS_MAX ? GATHER_THREADS_MAX : n);
 }
-static void gather_images(float *dst, const float *const *images, int first, int count, size_t img) {
+/* the caller's images of a host-pointer call: fp32 [C][S][S] (f32) or 8-bit [S][S][C] (u8) */
+typedef struct {
+    const float *const *f32;
+    const unsigned char *const *u8;
+} host_images;
+static const void *host_image(const host_images *im, int i) { return im->u8 ? (const void *)im->u8[i] : (const void *)im->f32[i]; }
+
+static void gather_images(char *dst, const host_images *images, int first, int count, size_t img_bytes) {
     const int nt = gather_threads();
 #pragma omp parallel for num_threads(nt) schedule(static) if (count >= 4)
-    for (int i = 0; i < count; ++i) memcpy(dst + (size_t)i * img, images[first + i], img * sizeof(float));
+    for (int i = 0; i < count; ++i) memcpy(dst + (size_t)i * img_bytes, host_image(images, first + i), img_bytes);
 }
-static int stage_piece(vit_engine *e, int slot, const float *const *images, int first, int count, size_t img, int sub) {
+/* gather a piece into pin_in[slot] and upload it to dst: in_stage[slot], or in8_stage[slot] for 8-bit images */
+static int stage_piece(vit_engine *e, int slot, void *dst, const host_images *images, int first, int count, size_t img_bytes, int sub) {
     for (int s0 = 0; s0 < count; s0 += sub) {
         const int c = count - s0 < sub ? count - s0 : sub;
-        gather_images(e->pin_in[slot] + (size_t)s0 * img, images, first + s0, c, img);
-        HIP_TRY(e, vithip_memcpy_h2d(e->in_stage[slot] + (size_t)s0 * img, e->pin_in[slot] + (size_t)s0 * img,
-                                     (size_t)c * img * sizeof(float), e->copy_stream));
+        char *pin = (char *)e->pin_in[slot] + (size_t)s0 * img_bytes;
+        gather_images(pin, images, first + s0, c, img_bytes);
+        HIP_TRY(e, vithip_memcpy_h2d((char *)dst + (size_t)s0 * img_bytes, pin, (size_t)c * img_bytes, e->copy_stream));
     }
     HIP_TRY(e, vithip_event_record(e->ev_h2d[slot], e->copy_stream));
     return VIT_OK;
 }
 
-int vit_engine_forward_host(vit_engine *e, const float *const *images, int n, float *const *probs) {
-    if (!e) return VIT_ERR_ARG;
-    if (!images || !probs || n <= 0) return fail(e, VIT_ERR_ARG, "forward_host: bad arguments (n=%d)", n);
+/* The host-pointer forward of either input kind.  8-bit pieces are gathered into pin_in[slot] as bytes, uploaded into
+ * in8_stage[slot] and normalised into in_stage[slot] on the compute stream (stage_embed): the copy stream writes nothing else, so
+ * the ev_h2d / ev_done ordering below covers them as it covers the fp32 pieces. */
+static int forward_host_in(vit_engine *e, const char *who, const host_images *images, const vit_input *in, int n, float *const *probs) {
     if (!e->weights_loaded) return fail(e, VIT_ERR_STATE, "forward before vit_engine_load_weights()");
     const size_t img = (size_t)e->cfg.in_chans * e->cfg.img_size * e->cfg.img_size;
+    const size_t img_bytes = img * (in->u8 ? 1 : sizeof(float));
     const size_t NC = (size_t)e->cfg.num_classes;
     for (int i = 0; i < n; ++i)
-        if (!images[i] || !probs[i]) return fail(e, VIT_ERR_ARG, "forward_host: image or output row %d is NULL", i);
+        if (!host_image(images, i) || !probs[i]) return fail(e, VIT_ERR_ARG, "%s: image or output row %d is NULL", who, i);
     HIP_TRY(e, vithip_set_device(e->opt.device));
+    for (int b = 0; b < 2 && in->u8; ++b)
+        if (!e->in8_stage[b]) HIP_TRY(e, vithip_malloc((void **)&e->in8_stage[b], (size_t)e->opt.max_batch * img));
+    if (e->in_stage_pending) { /* an 8-bit device-path call may still read in_stage[0] */
+        HIP_TRY(e, vithip_stream_wait_event(e->copy_stream, e->ev_in_stage));
+        e->in_stage_pending = 0;
+    }
+    void *up[2]; /* where the pieces are uploaded to */
+    for (int b = 0; b < 2; ++b) up[b] = in->u8 ? (void *)e->in8_stage[b] : (void *)e->in_stage[b];
     /*
      * Pieces of up to max_batch images flow through two staging slots: while the GPU computes piece i,
      * the host gathers the separately allocated images of piece i+1 into pinned memory and the copy
@@ -983,13 +1073,13 @@ int vit_engine_forward_host(vit_engine *e, const float *const *images, int n, fl
 #define PIECE_N(i) ((PIECE_LO((i) + 1) < n ? PIECE_LO((i) + 1) : n) - PIECE_LO(i))
     /* stage piece 0 */
     {
-        int rc0 = stage_piece(e, 0, images, 0, PIECE_N(0), img, np > 1 ? SUB_PIECE_FIRST : SUB_PIECE);
+        int rc0 = stage_piece(e, 0, up[0], images, 0, PIECE_N(0), img_bytes, np > 1 ? SUB_PIECE_FIRST : SUB_PIECE);
         if (rc0) return rc0;
     }
     for (int k = 0; k < np; ++k) {
         const int b = k & 1, nb = PIECE_N(k);
         HIP_TRY(e, vithip_stream_wait_event(e->stream, e->ev_h2d[b]));
-        int rc = forward_chunk(e, e->stream, e->in_stage[b], nb, e->out_stage[b], NULL, NULL);
+        int rc = forward_chunk(e, e->stream, up[b], in, e->in_stage[b], nb, e->out_stage[b], NULL, NULL);
         if (rc) return rc;
         HIP_TRY(e, vithip_memcpy_d2h(e->pin_out[b], e->out_stage[b], (size_t)nb * NC * sizeof(float), e->stream));
         HIP_TRY(e, vithip_event_record(e->ev_done[b], e->stream));
@@ -1001,7 +1091,7 @@ int vit_engine_forward_host(vit_engine *e, const float *const *images, int n, fl
                 memcpy(probs[first + i], e->pin_out[b ^ 1] + (size_t)i * NC, NC * sizeof(float));
         }
         if (k + 1 < np) { /* slot b^1 is free again (its H2D, compute and D2H are complete): refill it */
-            rc = stage_piece(e, b ^ 1, images, PIECE_LO(k + 1), PIECE_N(k + 1), img, SUB_PIECE);
+            rc = stage_piece(e, b ^ 1, up[b ^ 1], images, PIECE_LO(k + 1), PIECE_N(k + 1), img_bytes, SUB_PIECE);
             if (rc) return rc;
         }
     }
@@ -1018,6 +1108,26 @@ int vit_engine_forward_host(vit_engine *e, const float *const *images, int n, fl
         if (rc) return rc;
     }
     return VIT_OK;
+}
+
+int vit_engine_forward_host(vit_engine *e, const float *const *images, int n, float *const *probs) {
+    if (!e) return VIT_ERR_ARG;
+    if (!images || !probs || n <= 0) return fail(e, VIT_ERR_ARG, "forward_host: bad arguments (n=%d)", n);
+    const host_images im = {images, NULL};
+    vit_input in;
+    memset(&in, 0, sizeof(in));
+    return forward_host_in(e, "forward_host", &im, &in, n, probs);
+}
+
+int vit_engine_forward_host_u8(vit_engine *e, const unsigned char *const *images, int n, const float *mean, const float *std,
+                               float *const *probs) {
+    if (!e) return VIT_ERR_ARG;
+    if (!images || !probs || n <= 0) return fail(e, VIT_ERR_ARG, "forward_host_u8: bad arguments (n=%d)", n);
+    const host_images im = {NULL, images};
+    vit_input in;
+    const int rc = input_u8(e, "forward_host_u8", mean, std, &in);
+    if (rc) return rc;
+    return forward_host_in(e, "forward_host_u8", &im, &in, n, probs);
 }
 
 int vit_engine_handover_stats(vit_engine *e, long *taken, long *recomputed) {
