@@ -133,8 +133,19 @@ typedef struct {
      * 6/16 of the fp32 instruction's matrix time, error of the order of an fp32 dot product's.  With 1 the
      * tile codes 0, 9, 10 and 11 are accepted and give the same bits as each other; 6, 7, 8 and 12 are refused. */
     int arith;
+    /* optional, arith = 1 only: W's pieces made ahead of time by vithip_split3_weights_f32(W, ldw, N, K) (16-byte aligned; NULL =
+     * split W on the fly).  The 128x128 persistent walk (tile 9, or auto where it picks the walk) then stages W's pieces straight
+     * from the image and splits only A; every other kernel ignores the field.  The pieces are the ones the on-the-fly split makes,
+     * so the result has the same bits with and without it. */
+    const void *w_split;
 } vithip_gemm_args;
 int vithip_gemm_f32(vithip_stream_t stream, const vithip_gemm_args *args);
+/* Pre-split weight image for vithip_gemm_args.w_split: the hi / mid / lo bf16 pieces of W [N][ldw] (K % 32 == 0, ldw % 4 == 0,
+ * 16-byte aligned), the arithmetic of the on-the-fly split (round to nearest even, +-Inf, NaN and subnormals included).  Layout: one
+ * 12 KB block per 128-row panel and 16-deep K step (panel-major, K steps ascending inside a panel), a block = 3 planes x 128 rows
+ * x 16 bf16; rows past N are zero.  vithip_split3_weights_bytes(N, K) = ceil(N / 128) * 128 * K * 6 (0 for bad arguments). */
+size_t vithip_split3_weights_bytes(int N, int K);
+int vithip_split3_weights_f32(vithip_stream_t stream, const float *W, int ldw, int N, int K, void *out);
 int vithip_gemm_f32_stats_in_epilogue(const vithip_gemm_args *args);  /* 1 / 0 (0 also for arguments vithip_gemm_f32 would refuse) */
 /* ---- LayerNorm folding, fp32: LN(x) . W^T + b = rstd * (x . (gamma*W)^T) - rstd * mean * colsum(gamma*W) + (b + W . beta).
  * Wf[n][k] = gamma[k] * W[n][k] (fp32 product); colsum[n] = sum_k Wf[n][k] and bias_f[n] = bias[n] + sum_k beta[k] * W[n][k], both

@@ -2,15 +2,19 @@
 """The four encoder GEMMs of the batch-256 ViT-B/16 forward (M = 50,432) with vithip_gemm_args.arith = 0 (fp32 MFMA) and 1 (the
 three-piece split on the bf16 pipe), interleaved in one process, HIP events, the engine's call shape (auto tile, workspace lent;
 QKV and fc1 as the LayerNorm fold's consumers with the centred weight).  GPU box only.
-    python3 tools/gemm_f32_split_time.py [rounds]
-One JSON line per GEMM and arithmetic: microseconds per launch (min and median over the rounds) and the speed-up."""
+    python3 tools/gemm_f32_split_time.py [rounds] [--image]
+One JSON line per GEMM and arithmetic: microseconds per launch (min and median over the rounds) and the speed-up.
+--image: the split without the pre-split weight image (arm 1) against the split with it (arm 2, vithip_gemm_args.w_split, what
+the engine passes); "speedup" is then over arm 1."""
 import ctypes as C, importlib, json, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 B = importlib.import_module("vision-transformer-opencl_amd.binding")
 from tools.gemm_probe import timed
-rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 5
+args = [a for a in sys.argv[1:] if a != "--image"]
+rounds = int(args[0]) if args else 5
+arms = (1, 2) if "--image" in sys.argv else (0, 1)   # 0 fp32 MFMA, 1 split, 2 split with the weight image
 M, D, H = 50432, 768, 3072
 rng = np.random.default_rng(0)
 f = lambda *shape, a=1.0: B.DeviceArray.from_numpy(rng.uniform(-a, a, shape).astype(np.float32))
@@ -22,16 +26,17 @@ for name, N, K, epi, A, fold in (("qkv", 3 * D, D, B.EPI_BIAS, x, True), ("out_p
                                  ("fc1", H, D, B.EPI_BIAS_GELU, x, True), ("fc2", D, H, B.EPI_BIAS_RESIDUAL, h, False)):
     W, b, out = f(N, K, a=.03), f(N, a=.1), B.DeviceArray((M, N))
     res = out if epi == B.EPI_BIAS_RESIDUAL else None
-    ms = {0: [], 1: []}
+    img = B.split3_weights_device(W, N, K) if 2 in arms else None
+    ms = {arm: [] for arm in arms}
     for _ in range(rounds):
-        for arith in (0, 1):
+        for arm in arms:
             a = B.CGemmArgs(A.ptr, K, W.ptr, K, b.ptr, res.ptr if res else None, N, out.ptr, N, M, N, K, epi, 0, 0, ws, 0,
-                            rows.ptr if fold else None, None, None, None, arith)
-            ms[arith].append(timed(lambda: B.hip_check(L.vithip_gemm_f32(None, C.byref(a)), "gemm"), reps=6, warm=2))
+                            rows.ptr if fold else None, None, None, None, min(arm, 1), img.ptr if arm == 2 else None)
+            ms[arm].append(timed(lambda: B.hip_check(L.vithip_gemm_f32(None, C.byref(a)), "gemm"), reps=6, warm=2))
     flops = 2.0 * M * N * K
-    for arith in (0, 1):
-        t = float(np.median(ms[arith]))
-        print(json.dumps({"gemm": name, "arith": arith, "us_min": round(min(ms[arith]) * 1e3, 1), "us_median": round(t * 1e3, 1),
-                          "tflops": round(flops / (t * 1e-3) / 1e12, 1),
-                          "speedup": round(float(np.median(ms[0])) / t, 3)}), flush=True)
-    del W, b, out
+    for arm in arms:
+        t = float(np.median(ms[arm]))
+        print(json.dumps({"gemm": name, "arith": min(arm, 1), "w_split": arm == 2, "us_min": round(min(ms[arm]) * 1e3, 1),
+                          "us_median": round(t * 1e3, 1), "tflops": round(flops / (t * 1e-3) / 1e12, 1),
+                          "speedup": round(float(np.median(ms[arms[0]])) / t, 3)}), flush=True)
+    del W, b, out, img

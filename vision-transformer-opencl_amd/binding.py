@@ -72,7 +72,7 @@ class CGemmArgs(C.Structure):
                 ("C", C.c_void_p), ("ldc", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
                 ("epilogue", C.c_int), ("tile", C.c_int), ("group_m", C.c_int), ("workspace", C.c_void_p),
                 ("handover_test", C.c_int), ("ln_rows", C.c_void_p), ("ln_colsum", C.c_void_p),
-                ("stats_out", C.c_void_p), ("stats_partials", C.c_void_p), ("arith", C.c_int)]
+                ("stats_out", C.c_void_p), ("stats_partials", C.c_void_p), ("arith", C.c_int), ("w_split", C.c_void_p)]
 
 
 _lib: Optional[C.CDLL] = None
@@ -181,6 +181,9 @@ def lib() -> C.CDLL:
         for fn in ("vithip_memcpy_h2d", "vithip_memcpy_d2h", "vithip_memcpy_d2d"):
             getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.vithip_gemm_f32.argtypes = [C.c_void_p, C.POINTER(CGemmArgs)]
+        L.vithip_split3_weights_bytes.argtypes = [C.c_int, C.c_int]
+        L.vithip_split3_weights_bytes.restype = C.c_size_t
+        L.vithip_split3_weights_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.vithip_patch_embed_f32.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int] * 5
         L.vithip_layernorm_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                            C.c_void_p, C.c_void_p, C.c_int, C.c_int]
@@ -266,7 +269,7 @@ class DeviceArray:
 
 def gemm(A, W, bias, residual=None, epilogue=EPI_BIAS, tile: int = 0, group_m: int = 0, workspace: bool = False,
          handover_test: int = 0, stats: Optional[dict] = None, ln=None, row_stats: Optional[dict] = None,
-         arith: int = ARITH_F32) -> np.ndarray:
+         arith: int = ARITH_F32, w_split: bool = False) -> np.ndarray:
     """C = epilogue(A . W^T + bias) through vithip_gemm_f32 (tile / group_m: per-call tuning fields, 0 = auto;
     workspace: lend the scratch that enables the helper pieces of the persistent walk; handover_test: see
     vithip_gemm_args; stats: receives the hand-over counters {"taken", "recomputed"} of the launch;
@@ -274,7 +277,8 @@ def gemm(A, W, bias, residual=None, epilogue=EPI_BIAS, tile: int = 0, group_m: i
     CENTRED weight of ln_fold_weights_f32_centered, nothing to subtract);
     row_stats: a dict that receives "rows" = vithip_gemm_args.stats_out [M][2] and "in_epilogue" = what
     vithip_gemm_f32_stats_in_epilogue said; its key "scratch" (default True) lends stats_partials);
-    arith: ARITH_F32 (fp32 MFMA) or ARITH_SPLIT3 (the three-piece split on the bf16 matrix pipe; tiles 0, 9, 10, 11)."""
+    arith: ARITH_F32 (fp32 MFMA) or ARITH_SPLIT3 (the three-piece split on the bf16 matrix pipe; tiles 0, 9, 10, 11);
+    w_split: make W's pre-split image on the device (split3_weights_device) and pass it as vithip_gemm_args.w_split."""
     A, W, bias = _as_f32(A), _as_f32(W), _as_f32(bias)
     M, K = A.shape
     N = W.shape[0]
@@ -289,6 +293,9 @@ def gemm(A, W, bias, residual=None, epilogue=EPI_BIAS, tile: int = 0, group_m: i
     args = CGemmArgs(dA.ptr, K, dW.ptr, K, db.ptr, dR.ptr if dR else None, N, dC.ptr, N, M, N, K, epilogue, tile, group_m, ws,
                      handover_test, dRows.ptr if dRows else None, dCs.ptr if dCs else None, dSt.ptr if dSt else None,
                      dPart.ptr if dPart else None, arith)
+    dImg = split3_weights_device(dW, N, K) if w_split else None
+    if dImg is not None:
+        args.w_split = dImg.ptr
     if row_stats is not None:
         row_stats["in_epilogue"] = int(lib().vithip_gemm_f32_stats_in_epilogue(C.byref(args)))
     hip_check(lib().vithip_gemm_f32(None, C.byref(args)), "vithip_gemm_f32")
@@ -300,6 +307,24 @@ def gemm(A, W, bias, residual=None, epilogue=EPI_BIAS, tile: int = 0, group_m: i
             stats.update(gemm_workspace_stats(ws))
         lib().vithip_gemm_f32_workspace_destroy(C.c_void_p(ws))
     return out
+
+
+def split3_weights_device(dW: "DeviceArray", N: int, K: int, ldw: Optional[int] = None) -> "DeviceArray":
+    """vithip_split3_weights_f32: the pre-split image of the device matrix dW [N][ldw] (vithip_gemm_args.w_split), as a DeviceArray of bytes."""
+    nbytes = int(lib().vithip_split3_weights_bytes(N, K))
+    if nbytes == 0:
+        raise VitError(f"vithip_split3_weights_bytes({N}, {K}): bad shape")
+    out = DeviceArray((nbytes,), np.uint8)
+    hip_check(lib().vithip_split3_weights_f32(None, dW.ptr, K if ldw is None else ldw, N, K, out.ptr), "vithip_split3_weights_f32")
+    return out
+
+
+def split3_weights(W) -> np.ndarray:
+    """The pre-split image of W [N][K] (fp32), copied back: uint16 [ceil(N / 128)][K / 16][3][128][16] bf16 bit patterns."""
+    W = _as_f32(W)
+    N, K = W.shape
+    img = split3_weights_device(DeviceArray.from_numpy(W), N, K).numpy()
+    return img.view(np.uint16).reshape((N + 127) // 128, K // 16, 3, 128, 16)
 
 
 def gemm_workspace() -> int:

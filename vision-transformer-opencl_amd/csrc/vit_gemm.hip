@@ -670,6 +670,8 @@ int vithip_gemm_f32(vithip_stream_t stream, const vithip_gemm_args *a) {
     if (a->tile < 0 || (a->tile > 0 && a->tile < 6) || a->tile > 12 || a->group_m < 0 || a->group_m > 1024) return static_cast<int>(hipErrorInvalidValue);
     if (a->arith != ARITH_F32 && (a->arith != ARITH_SPLIT3 || (a->tile != 0 && a->tile != 9 && a->tile != 10 && a->tile != 11)))
         return static_cast<int>(hipErrorInvalidValue);  // the split: auto and tiles 9, 10, 11 only
+    if (a->w_split && !aligned16(a->w_split)) return static_cast<int>(hipErrorInvalidValue);
+    p.w_split = a->arith == ARITH_SPLIT3 ? a->w_split : nullptr;  // (the fp32 arithmetic has no use for it)
     int epilogue = a->epilogue;
     if (a->ln_rows || a->ln_colsum) {  // LayerNorm fold, consumer side (ln_colsum NULL: the weight is the CENTRED one, see the header)
         if (!a->ln_rows || (epilogue != VITHIP_EPI_BIAS && epilogue != VITHIP_EPI_BIAS_GELU) ||

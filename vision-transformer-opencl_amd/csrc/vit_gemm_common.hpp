@@ -52,6 +52,8 @@ struct GemmParams {
     // stats_in_epilogue: set by the dispatcher when the kernel it chose writes them (the caller then only finalises)
     float *row_partials;
     int stats_in_epilogue;
+    // the pre-split weight image (vithip_gemm_args.w_split; NULL: split W on the fly): read by the 128x128 persistent split walk only
+    const void *w_split;
 };
 
 // erf(x) = sign(x) * (1 - exp(t*q(t))), t = min(|x|, 4), q = degree-7 minimax fit of log(erfc(t))/t
@@ -217,21 +219,52 @@ constexpr int SPLIT_TERM_W[6] = {2, 0, 1, 1, 0, 0};
 __device__ __forceinline__ float bf16_to_f32(__bf16 v) {
     return __builtin_bit_cast(float, (unsigned)__builtin_bit_cast(unsigned short, v) << 16);
 }
+// piece `piece` (0 = hi, 1 = mid, 2 = lo) of four values, taken in this order: x holds what the earlier pieces left of the values
+// and, for pieces 0 and 1, is left holding the remainder for the next one.  The one definition of the pieces: the on-the-fly split
+// of both operands, the image walk's split of A and the weight-image producer (vit_split_weights.hip) all make them here.
+__device__ __forceinline__ u32x2 split3_piece(f32x4 &x, int piece) {
+    bf16x4 b;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) b[e] = (__bf16)x[e];  // v_cvt_pk_bf16_f32: round to nearest even
+    if (piece < 2) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[e] = x[e] - bf16_to_f32(b[e]);  // exact
+    }
+    return __builtin_bit_cast(u32x2, b);
+}
 // four consecutive-k values of one row -> the three pieces of each, written to their planes of the split LDS row `row`
 // (kc = k offset inside the K step, a multiple of 4: one ds_write_b64 per piece)
 __device__ __forceinline__ void split3_store(float *row, int kc, f32x4 x) {
 #pragma unroll
-    for (int piece = 0; piece < 3; ++piece) {
-        bf16x4 b;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) b[e] = (__bf16)x[e];  // v_cvt_pk_bf16_f32: round to nearest even
-        *reinterpret_cast<u32x2 *>(row + piece * 8 + kc / 2) = __builtin_bit_cast(u32x2, b);
-        if (piece < 2) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) x[e] = x[e] - bf16_to_f32(b[e]);  // exact
-        }
-    }
+    for (int piece = 0; piece < 3; ++piece) *reinterpret_cast<u32x2 *>(row + piece * 8 + kc / 2) = split3_piece(x, piece);
 }
+// the same for eight consecutive k (x0 = k 0..3, x1 = k 4..7): piece `piece` of all eight as one 16-byte plane chunk
+__device__ __forceinline__ u32x4 split3_piece8(f32x4 &x0, f32x4 &x1, int piece) {
+    const u32x2 p0 = split3_piece(x0, piece), p1 = split3_piece(x1, piece);
+    return u32x4{p0[0], p0[1], p1[0], p1[1]};
+}
+
+// ---- pre-split weights (vithip_gemm_args.w_split) and the swizzled LDS rows of the walk that reads them --------------------------
+// Image of W [N][K]: one block per (128-row panel, 16-deep K step), panel-major, K steps ascending inside a panel.  A block is
+// 3 planes x 128 rows x 16 bf16; its 16-byte chunk c = plane * 256 + 2 * row + half holds k 8 half .. 8 half + 7 of one plane of
+// one row.  Thread t of the walk's 256 copies chunks t, 256 + t and 512 + t of a K step: lane-linear 16-byte loads, and exactly
+// the (row t / 2, half t % 2) the same thread splits of A.
+constexpr int WIMG_ROWS = 128;
+constexpr int WIMG_BLOCK_BYTES = 3 * WIMG_ROWS * SPLIT_BK * 2;  // 12 KB
+// LDS row of the image walk: 8 slots of 16 bytes, the six (plane, half) chunks s = 2 plane + half at slot s ^ split_swizzle(row).
+// Conflict-free both ways (MI355X LDS banking: ds_write_b128 in 8-lane groups on (a/4) mod 32, ds_read_b128 in 16-lane groups on
+// (a/4) mod 64):
+//   writes: 8 consecutive threads = one aligned quad of rows x both halves; (row & 3) ^ ((row >> 2) & 3) takes 4 distinct values
+//           over a quad, so the 8 chunks of one plane land in the 8 slots of a 32-bank line;
+//   reads:  a fragment read = one (plane, half) of 16 rows distinct mod 16; (row & 1, slot) is distinct over them because the
+//           swizzle is one-to-one on the 8 even and on the 8 odd rows of 16 (bit 3 of the row separates the two rows of each
+//           parity that share bits 0..2 of it).
+// (The on-the-fly split's rows of SPLIT_LD = 28 dwords read conflict-free but take their ds_write_b64 of neighbouring rows onto
+// the same banks: 2.4 conflict cycles per LDS instruction in the r06 counters.)
+constexpr int SPLIT_LD_SW = 32;  // floats
+__device__ __forceinline__ int split_swizzle(int row) { return 2 * ((row & 3) ^ ((row >> 2) & 3)) + ((row >> 3) & 1); }
+// float offset of chunk s of row `row` in a swizzled LDS tile
+__device__ __forceinline__ int split_sw_offset(int row, int s) { return row * SPLIT_LD_SW + 4 * (s ^ split_swizzle(row)); }
 // One 16-deep K step of a wave's TM x TN accumulators from the split LDS tiles As / Bs (at the lane's fragment: row r of the
 // wave's first block, k offset 8h): the three pieces of every fragment, then 6 x TM x TN matrix instructions, term by term (the
 // accumulators of one term are independent of each other).  restage(q), q < NS, is spread over the first half of them: the
@@ -261,6 +294,38 @@ __device__ __forceinline__ void split3_step(f32x16 (&acc)[TM][TN], const float *
                 for (int q = slot_before; q < slot_after; ++q) restage(q);
                 __builtin_amdgcn_sched_barrier(0);
             }
+        }
+    }
+}
+// The same step on swizzled tiles (SPLIT_LD_SW rows): As / Bs point at the lane's row r of the wave's first block, poff[piece] is
+// the lane's float offset of its chunk (2 piece + h) inside that row (the same for every block: blocks are 32 rows apart and the
+// swizzle repeats every 16).  restage(q), q < NS, goes right behind matrix instruction floor(q * NM / NS): spread over the whole
+// step, with the last slot a few instructions ahead of the barrier.
+template <int TM, int TN, int NS, typename Restage>
+__device__ __forceinline__ void split3_step_sw(f32x16 (&acc)[TM][TN], const float *As, const float *Bs, const int (&poff)[3],
+                                               Restage &&restage) {
+    bf16x8 a[TM][3], b[TN][3];
+#pragma unroll
+    for (int o = 0; o < 3; ++o) {
+        const int pa = SPLIT_TERM_A[o], pb = SPLIT_TERM_W[o];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) a[i][pa] = *reinterpret_cast<const bf16x8 *>(As + i * 32 * SPLIT_LD_SW + poff[pa]);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) b[j][pb] = *reinterpret_cast<const bf16x8 *>(Bs + j * 32 * SPLIT_LD_SW + poff[pb]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    constexpr int NM = 6 * TM * TN;
+    static_assert(NS <= NM, "one restage slot per matrix instruction at most");
+#pragma unroll
+    for (int idx = 0; idx < NM; ++idx) {
+        const int t = idx / (TM * TN), i = (idx / TN) % TM, j = idx % TN;
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][SPLIT_TERM_A[t]], b[j][SPLIT_TERM_W[t]], acc[i][j], 0, 0, 0);
+        const int slot_before = (idx * NS + NM - 1) / NM, slot_after = ((idx + 1) * NS + NM - 1) / NM;
+        if (slot_after > slot_before) {
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int q = slot_before; q < slot_after; ++q) restage(q);
+            __builtin_amdgcn_sched_barrier(0);
         }
     }
 }

@@ -49,12 +49,19 @@ constexpr int SK_HEADER_BYTES = 4096, SK_MAX_OWNERS = 1000, SK_STAT_TAKEN = 1016
 // (What such builds measure is mostly the POWER of frozen operand data, not the removed instructions: DESIGN 4.1 item 11.)
 // ARITH = ARITH_SPLIT3: the three-piece split on the bf16 matrix pipe (vit_gemm_common.hpp): the same walk, hand-over and
 // epilogues, K step SPLIT_BK, LDS rows of SPLIT_LD floats (56 KB at 128 x 128).
-template <int BM, int BN, int WM, int WN, int EPI, bool STAMP = false, bool SK = false, int DBG = 0, int ARITH = ARITH_F32>
+// WIMG (split only): W's pieces come ready-made from the weight image p.w_split and A is split in registers -- no vector
+// instruction touches W in the loop.  Staging per thread and K step: 8 consecutive k of one row of A (two 16-byte loads, split
+// into three 16-byte plane chunks) and three 16-byte image chunks of W, all written with ds_write_b128 into swizzled rows of
+// SPLIT_LD_SW floats (64 KB), conflict-free (see split_swizzle).  Six restage slots (A plane, W plane, alternating) spread over
+// all 24 matrix instructions of the step.  The same pieces in the same places of the product: the same bits as WIMG = false.
+template <int BM, int BN, int WM, int WN, int EPI, bool STAMP = false, bool SK = false, int DBG = 0, int ARITH = ARITH_F32,
+          bool WIMG = false>
 __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const GemmParams p) {
     constexpr bool SPLIT = ARITH == ARITH_SPLIT3;
     static_assert(!SPLIT || DBG == 0, "switch-off builds are fp32 only");
+    static_assert(!WIMG || (SPLIT && BM == WIMG_ROWS && BN == WIMG_ROWS && !STAMP), "the weight image feeds the 128x128 split walk");
     constexpr int PBK = SPLIT ? SPLIT_BK : vitgemm::PBK;  // K step
-    constexpr int PLD = SPLIT ? SPLIT_LD : vitgemm::PLD;  // LDS row (floats)
+    constexpr int PLD = WIMG ? SPLIT_LD_SW : SPLIT ? SPLIT_LD : vitgemm::PLD;  // LDS row (floats)
     constexpr int ROWS_PER_PASS = 256 / (PBK / 4);
     constexpr int WGN = BN / WN;
     constexpr int TM = WM / 32, TN = WN / 32;
@@ -62,6 +69,10 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
     constexpr int B_CHUNKS = BN * (PBK / 4) / 256;
     constexpr int NC = PBK / 8;              // 8-deep chunks per K step (fp32)
     constexpr int NS = A_CHUNKS + B_CHUNKS;  // staged float4 per thread per K step
+    constexpr int W_CHUNKS = 3;              // WIMG: image chunks per thread per K step (one per plane)
+    constexpr int NL = WIMG ? A_CHUNKS + W_CHUNKS : NS;  // global loads per thread per K step
+    constexpr int NSL = WIMG ? 6 : NS;                   // restage slots per K step
+    static_assert(!WIMG || (A_CHUNKS == 2 && BM * 2 == 256 && BN * 2 == 256), "WIMG: one 8-deep half row of A and of W per thread");
     constexpr int NM = 4 * TM * TN;          // MFMAs per chunk
     static_assert((BM / WM) * WGN == 4, "4 waves per workgroup");
 
@@ -128,19 +139,36 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
 
     const int ld_row = tid / (PBK / 4);
     const int ld_kc = (tid % (PBK / 4)) * 4;
+    // WIMG: thread t stages row t / 2, k 8 (t % 2) .. 8 (t % 2) + 7 of A and of W; wr_off[plane] = its chunk's place in a tile
+    const int sw_row = tid >> 1, sw_half = tid & 1;
+    int wr_off[3];
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) wr_off[pl] = WIMG ? split_sw_offset(sw_row, 2 * pl + sw_half) : 0;
     // Staging loads are buffer loads: SGPR descriptor + per-thread 32-bit byte offset + SGPR K offset, so
     // stepping through K costs no vector instruction (a 64-bit v_lshl_add per load otherwise -- and fp32
     // VALU time comes out of the matrix pipe's).  Offsets fit 32 bits: the largest operand (fc2's A at
     // batch 256) is 620 MB; the launcher refuses operands >= 2 GB for this kernel.
     const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.A), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.W), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t w_rsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(WIMG ? p.w_split : static_cast<const void *>(p.W)), 0, 0x7fffffff, 0x00020000);
     int a_src[A_CHUNKS];  // byte offsets
-    int b_src[B_CHUNKS];
+    int b_src[WIMG ? W_CHUNKS : B_CHUNKS];
     f32x4 a_stage[A_CHUNKS], b_stage[B_CHUNKS];
+    u32x4 w_stage[WIMG ? W_CHUNKS : 1];  // WIMG: the image chunks in flight
 
     auto set_sources = [&](int tile) {
         int tm, tn;
         tile_coords(tile, p.tiles_m, p.tiles_n, p.group_m, tm, tn);
+        if constexpr (WIMG) {
+            int m = tm * BM + sw_row;
+            m = m < p.M ? m : p.M - 1;
+#pragma unroll
+            for (int i = 0; i < A_CHUNKS; ++i) a_src[i] = (m * p.lda + 8 * sw_half + 4 * i) * 4;
+            // the tile's panel of the image: its blocks follow each other in K (the K step is the loads' scalar offset)
+#pragma unroll
+            for (int q = 0; q < W_CHUNKS; ++q) b_src[q] = tn * nk * WIMG_BLOCK_BYTES + (q * 256 + tid) * 16;
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < A_CHUNKS; ++i) {
             int m = tm * BM + ld_row + i * ROWS_PER_PASS;
@@ -220,6 +248,11 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
         const int k0 = k_l * PBK;
 #pragma unroll
         for (int i = 0; i < A_CHUNKS; ++i) a_stage[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, a_src[i], k0 * 4, 0));
+        if constexpr (WIMG) {
+#pragma unroll
+            for (int q = 0; q < W_CHUNKS; ++q) w_stage[q] = __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, b_src[q], k_l * WIMG_BLOCK_BYTES, 0);
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < B_CHUNKS; ++i) b_stage[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, b_src[i], k0 * 4, 0));
     };
@@ -228,15 +261,44 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
         if constexpr (SPLIT) split3_store(row, ld_kc, v);
         else *reinterpret_cast<f32x4 *>(row + ld_kc) = v;
     };
+    // WIMG: the A chunk of plane `pl` (split off what the earlier planes left of a_stage) / the W image chunk of plane `pl`
+    auto write_a_plane = [&](float *As, int pl) __attribute__((always_inline)) {
+        *reinterpret_cast<u32x4 *>(As + wr_off[pl]) = split3_piece8(a_stage[0], a_stage[1], pl);
+    };
+    auto write_w_plane = [&](float *Bs, int pl) __attribute__((always_inline)) { *reinterpret_cast<u32x4 *>(Bs + wr_off[pl]) = w_stage[pl]; };
     auto store_step = [&](int buf) {
         float *As = As0 + buf * BM * PLD, *Bs = Bs0 + buf * BN * PLD;
+        if constexpr (WIMG) {
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) {
+                write_a_plane(As, pl);
+                write_w_plane(Bs, pl);
+            }
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < A_CHUNKS; ++i) stage_write(As + (ld_row + i * ROWS_PER_PASS) * PLD, a_stage[i]);
 #pragma unroll
         for (int i = 0; i < B_CHUNKS; ++i) stage_write(Bs + (ld_row + i * ROWS_PER_PASS) * PLD, b_stage[i]);
     };
-    // one staging slot: write the float4 fetched a step ago, then refetch it for two steps ahead
+    // one staging slot: write the float4 fetched a step ago, then refetch it for two steps ahead.  WIMG: slot 2 pl = plane pl of A
+    // (after the lo plane, both A loads), slot 2 pl + 1 = plane pl of W and its image load
     auto restage_slot = [&](int q, int buf, int k0) {
+        if constexpr (WIMG) {
+            const int pl = q >> 1;
+            if (q & 1) {
+                write_w_plane(Bs0 + buf * BN * PLD, pl);
+                w_stage[pl] = __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, b_src[pl], (k0 / PBK) * WIMG_BLOCK_BYTES, 0);
+            } else {
+                write_a_plane(As0 + buf * BM * PLD, pl);
+                if (pl == 2) {
+#pragma unroll
+                    for (int i = 0; i < A_CHUNKS; ++i)
+                        a_stage[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, a_src[i], k0 * 4, 0));
+                }
+            }
+            return;
+        }
         if (q < A_CHUNKS) {
             float *As = As0 + buf * BM * PLD;
             if (DBG != 5 && DBG != 6) stage_write(As + (ld_row + q * ROWS_PER_PASS) * PLD, a_stage[q]);
@@ -249,8 +311,11 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
         }
     };
 
-    const int a_frag_off = (wm * WM + r) * PLD + h * 4;
-    const int b_frag_off = (wn * WN + r) * PLD + h * 4;
+    const int a_frag_off = WIMG ? (wm * WM + r) * PLD : (wm * WM + r) * PLD + h * 4;
+    const int b_frag_off = WIMG ? (wn * WN + r) * PLD : (wn * WN + r) * PLD + h * 4;
+    int frag_poff[3];  // WIMG: the lane's chunk (2 piece + h) inside its rows (the swizzle repeats every 16 rows)
+#pragma unroll
+    for (int pc = 0; pc < 3; ++pc) frag_poff[pc] = WIMG ? split_sw_offset(r, 2 * pc + h) - r * PLD : 0;
     f32x4 af[2][TM], bf[2][TN];  // fp32 only (the split reads its pieces inside split3_step)
     auto read_frags = [&](int buf, int c, int set) {
         if constexpr (SPLIT) return;
@@ -395,14 +460,21 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
                 // vmcnt retires in order: once at most FOLD_WAIT = 2 * NS operations are outstanding, everything older than the
                 // restage loads of the last two K-steps is done.  The copy was issued before this tile's first restage load, and a
                 // tile of FOLD_MIN_STEPS steps has issued (FOLD_MIN_STEPS - 1) * NS >= FOLD_WAIT + NS of them by now.
-                constexpr int FOLD_WAIT = 2 * NS, FOLD_MIN_STEPS = 4;
+                // (NL: the global loads a K-step issues -- 4 float4 on the fly, 2 of A + 3 image chunks with WIMG)
+                constexpr int FOLD_WAIT = 2 * NL, FOLD_MIN_STEPS = 4;
                 static_assert(FOLD_WAIT <= 63, "vmcnt is a 6-bit count on gfx950");
-                static_assert((FOLD_MIN_STEPS - 1) * NS >= FOLD_WAIT + NS, "the copy must be older than the loads the wait leaves in flight");
+                static_assert((FOLD_MIN_STEPS - 1) * NL >= FOLD_WAIT + NL, "the copy must be older than the loads the wait leaves in flight");
                 if (kend_c - seg_k0 >= FOLD_MIN_STEPS) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(FOLD_WAIT) : "memory");
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
         }
-        if constexpr (SPLIT) {
+        if constexpr (WIMG) {
+            // as below, on the swizzled tiles: the six restage slots of step g + 1 / g + 2 spread over all the step's matrix instructions
+            split3_step_sw<TM, TN, NSL>(acc, As0 + cur * BM * PLD + a_frag_off, Bs0 + cur * BN * PLD + b_frag_off, frag_poff,
+                                        [&](int q) __attribute__((always_inline)) { restage_slot(q, cur ^ 1, k_ahead); });
+            advance_load_cursor();
+            __syncthreads();
+        } else if constexpr (SPLIT) {
             // one 16-deep step of the split: pieces from buffer `cur`, the staged step g + 1 split into cur^1 and the loads of step
             // g + 2 in the first half of the matrix instructions, then the one barrier (the fp32 loop's swap point)
             split3_step<TM, TN, NS>(acc, As0 + cur * BM * PLD + a_frag_off, Bs0 + cur * BN * PLD + b_frag_off,
@@ -487,7 +559,7 @@ int persistent_piece_steps(int M, int N, int K, int slots, int wgs, int kstep) {
     return (x >= 4 && nk - c * x >= 8) ? x * (PBK / kstep) : 0;
 }
 
-template <int BM, int BN, int WM, int WN, int ARITH = ARITH_F32>
+template <int BM, int BN, int WM, int WN, int ARITH = ARITH_F32, bool WIMG = false>
 int launch_persistent_tile(hipStream_t stream, GemmParams &p, int epilogue, int group_m) {
     const int wgs = persistent_wgs();
     if (wgs <= 0) return static_cast<int>(hipErrorInvalidDevice);
@@ -502,22 +574,22 @@ int launch_persistent_tile(hipStream_t stream, GemmParams &p, int epilogue, int 
     if (p.sk_x > 0) {
         switch (epilogue) {
             case VITHIP_EPI_BIAS:
-                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS, false, true, 0, ARITH>), grid, block, 0, stream, p);
+                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS, false, true, 0, ARITH, WIMG>), grid, block, 0, stream, p);
                 break;
             case VITHIP_EPI_BIAS_GELU:
-                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_GELU, false, true, 0, ARITH>), grid, block, 0, stream, p);
+                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_GELU, false, true, 0, ARITH, WIMG>), grid, block, 0, stream, p);
                 break;
             case VITHIP_EPI_BIAS_RESIDUAL:
-                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_RESIDUAL, false, true, 0, ARITH>), grid, block, 0, stream, p);
+                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_RESIDUAL, false, true, 0, ARITH, WIMG>), grid, block, 0, stream, p);
                 break;
             case EPI_BIAS_LN:
-                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_LN, false, true, 0, ARITH>), grid, block, 0, stream, p);
+                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_LN, false, true, 0, ARITH, WIMG>), grid, block, 0, stream, p);
                 break;
             case EPI_BIAS_GELU_LN:
-                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_GELU_LN, false, true, 0, ARITH>), grid, block, 0, stream, p);
+                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_GELU_LN, false, true, 0, ARITH, WIMG>), grid, block, 0, stream, p);
                 break;
             case EPI_RESIDUAL_STATS:
-                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_RESIDUAL_STATS, false, true, 0, ARITH>), grid, block, 0, stream, p);
+                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_RESIDUAL_STATS, false, true, 0, ARITH, WIMG>), grid, block, 0, stream, p);
                 break;
             default:
                 return static_cast<int>(hipErrorInvalidValue);
@@ -526,22 +598,22 @@ int launch_persistent_tile(hipStream_t stream, GemmParams &p, int epilogue, int 
     }
     switch (epilogue) {
         case VITHIP_EPI_BIAS:
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS, false, false, 0, ARITH>), grid, block, 0, stream, p);
+            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS, false, false, 0, ARITH, WIMG>), grid, block, 0, stream, p);
             break;
         case VITHIP_EPI_BIAS_GELU:
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_GELU, false, false, 0, ARITH>), grid, block, 0, stream, p);
+            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_GELU, false, false, 0, ARITH, WIMG>), grid, block, 0, stream, p);
             break;
         case VITHIP_EPI_BIAS_RESIDUAL:
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_RESIDUAL, false, false, 0, ARITH>), grid, block, 0, stream, p);
+            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_RESIDUAL, false, false, 0, ARITH, WIMG>), grid, block, 0, stream, p);
             break;
         case EPI_BIAS_LN:
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_LN, false, false, 0, ARITH>), grid, block, 0, stream, p);
+            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_LN, false, false, 0, ARITH, WIMG>), grid, block, 0, stream, p);
             break;
         case EPI_BIAS_GELU_LN:
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_GELU_LN, false, false, 0, ARITH>), grid, block, 0, stream, p);
+            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_GELU_LN, false, false, 0, ARITH, WIMG>), grid, block, 0, stream, p);
             break;
         case EPI_RESIDUAL_STATS:
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_RESIDUAL_STATS, false, false, 0, ARITH>), grid, block, 0, stream, p);
+            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_RESIDUAL_STATS, false, false, 0, ARITH, WIMG>), grid, block, 0, stream, p);
             break;
         default:
             return static_cast<int>(hipErrorInvalidValue);
@@ -611,7 +683,11 @@ int launch_persistent(hipStream_t stream, GemmParams &p, int epilogue, int group
         epilogue = EPI_RESIDUAL_STATS;
         p.stats_in_epilogue = 1;
     }
-    if (arith == ARITH_SPLIT3) return launch_persistent_tile<128, 128, 64, 64, ARITH_SPLIT3>(stream, p, epilogue, group_m);
+    if (arith == ARITH_SPLIT3) {
+        // W's pieces from the caller's pre-split image, or split on the fly: the same bits
+        if (p.w_split) return launch_persistent_tile<128, 128, 64, 64, ARITH_SPLIT3, true>(stream, p, epilogue, group_m);
+        return launch_persistent_tile<128, 128, 64, 64, ARITH_SPLIT3>(stream, p, epilogue, group_m);
+    }
     return launch_persistent_tile<128, 128, 64, 64>(stream, p, epilogue, group_m);
 }
 

@@ -55,6 +55,8 @@ struct vit_engine {
     int split;                   /* encoder GEMMs on the three-piece split (vit_engine_options.fp32_split; fp32 engines) */
     unsigned short *wfold16;     /* per layer [gamma1-folded in_proj 3D x D | gamma2-folded fc1 H x D] (bf16 engines) */
     float *wfold32;              /* the same two operands as fp32 products gamma * W (fp32 engines) */
+    unsigned char *wsplit;       /* split engines: per layer the pre-split images (vithip_split3_weights_f32) of [qkv | out_proj | fc1 | fc2] */
+    size_t wsplit_off[4], wsplit_layer; /* byte offset of each image inside a layer's, and a layer's bytes */
     float *wfoldf;               /* per layer [colsum qkv 3D | bias qkv 3D | colsum fc1 H | bias fc1 H] */
     float *ln_rows32;            /* fp32 engines: (rstd, mean) per token row [max_batch * tokens][2], then per class row [max_batch][2] */
     float *ln_part32;            /* ... and the residual GEMMs' scratch for them: [embed_dim / 64][rows][2] per lane (vithip_gemm_args.stats_partials) */
@@ -290,6 +292,17 @@ int vit_engine_create(vit_engine **out, const vit_config *cfg, const vit_engine_
             HIP_TRY(e, vithip_malloc((void **)&e->ln_part32, (D / 64) * B * T * 2 * sizeof(float)));
         }
     }
+    if (e->split) {
+        /* W's pieces, made once per upload (split_weights): the persistent split walk then splits only A.  6 bytes per weight of
+         * the four encoder GEMMs; without the image (K not a multiple of 32) every GEMM splits W on the fly, with the same bits */
+        const size_t b[4] = {vithip_split3_weights_bytes((int)(3 * D), (int)D), vithip_split3_weights_bytes((int)D, (int)D),
+                             vithip_split3_weights_bytes((int)H, (int)D), vithip_split3_weights_bytes((int)D, (int)H)};
+        if (b[0] && b[1] && b[2] && b[3]) {
+            e->wsplit_layer = 0;
+            for (int i = 0; i < 4; ++i) { e->wsplit_off[i] = e->wsplit_layer; e->wsplit_layer += b[i]; }
+            HIP_TRY(e, vithip_malloc((void **)&e->wsplit, (size_t)e->cfg.depth * e->wsplit_layer));
+        }
+    }
     HIP_TRY(e, vithip_stream_create(&e->copy_stream));
     for (int b = 0; b < 2; ++b) {
         HIP_TRY(e, vithip_malloc((void **)&e->in_stage[b], B * img * sizeof(float)));
@@ -333,6 +346,7 @@ void vit_engine_destroy(vit_engine *e) {
     vithip_free(e->wblob);
     vithip_free(e->wfold16);
     vithip_free(e->wfold32);
+    vithip_free(e->wsplit);
     vithip_free(e->ln_rows32);
     vithip_free(e->ln_part32);
     vithip_free(e->wfoldf);
@@ -419,6 +433,27 @@ static int fold_ln_weights(vit_engine *e) {
     return VIT_OK;
 }
 
+/* The pre-split images of every encoder GEMM weight as the GEMMs read them: in_proj and fc1 folded (centred) when the fold is on,
+ * out_proj and fc2 raw.  Runs after fold_ln_weights, i.e. after every upload / replication; 4 launches per layer. */
+static int split_weights(vit_engine *e) {
+    if (!e->wsplit) return VIT_OK;
+    const size_t D = (size_t)e->cfg.embed_dim, H = (size_t)e->cfg.hidden_dim;
+    for (int l = 0; l < e->cfg.depth; ++l) {
+        float **lw = e->w + 4 + VIT_WEIGHTS_PER_LAYER * l;
+        const float *w_qkv = lw[2], *w_fc1 = lw[8];
+        if (e->fold) {
+            w_qkv = e->wfold32 + (size_t)l * (3 * D * D + H * D);
+            w_fc1 = w_qkv + 3 * D * D;
+        }
+        unsigned char *img = e->wsplit + (size_t)l * e->wsplit_layer;
+        HIP_TRY(e, vithip_split3_weights_f32(e->stream, w_qkv, (int)D, (int)(3 * D), (int)D, img + e->wsplit_off[0]));
+        HIP_TRY(e, vithip_split3_weights_f32(e->stream, lw[4], (int)D, (int)D, (int)D, img + e->wsplit_off[1]));
+        HIP_TRY(e, vithip_split3_weights_f32(e->stream, w_fc1, (int)D, (int)H, (int)D, img + e->wsplit_off[2]));
+        HIP_TRY(e, vithip_split3_weights_f32(e->stream, lw[10], (int)H, (int)D, (int)H, img + e->wsplit_off[3]));
+    }
+    return VIT_OK;
+}
+
 int vit_engine_load_weight_image(vit_engine *e, const vit_weight_image *img) {
     if (!e || !img || !img->f32) return e ? fail(e, VIT_ERR_ARG, "null weight image") : VIT_ERR_ARG;
     if (memcmp(&img->cfg, &e->cfg, sizeof(vit_config)) != 0 || img->count != e->n_weights)
@@ -432,6 +467,7 @@ int vit_engine_load_weight_image(vit_engine *e, const vit_weight_image *img) {
     if (bf16 && !img->bf16_elems) /* image without a bf16 section: convert the GEMM-operand region on the device, one launch */
         HIP_TRY(e, vithip_f32_to_bf16(e->stream, e->wblob, e->wblob16, img->gemm_floats));
     if ((rc = fold_ln_weights(e))) return rc;
+    if ((rc = split_weights(e))) return rc;
     HIP_TRY(e, vithip_stream_sync(e->stream));
     e->weights_loaded = 1;
     return VIT_OK;
@@ -473,6 +509,7 @@ int vit_engine_copy_weights(vit_engine *dst, vit_engine *src) {
      * "upload to GPU 0 + broadcast") */
     HIP_TRY(dst, vithip_memcpy_peer(dst->wblob, dst->opt.device, src->wblob, src->opt.device, dst->wblob_bytes, dst->stream));
     if ((rc = fold_ln_weights(dst))) return rc; /* recomputed from the replica's own fp32 tensors: 2 launches per layer */
+    if ((rc = split_weights(dst))) return rc;
     HIP_TRY(dst, vithip_stream_sync(dst->stream));
     dst->weights_loaded = 1;
     return VIT_OK;
@@ -538,6 +575,7 @@ typedef struct {
     const float *ln_rows, *ln_colsum;  /* consumer; ln_colsum = column sums of W, NULL for the centred fp32 weights */
     float *stats_rows, *stats_part;    /* producer */
     unsigned short *x16;               /* bf16 producer: the bf16 copy of C, leading dimension ldc */
+    const void *w_split;               /* split engines: W's pre-split image (vithip_gemm_args.w_split), or NULL */
 } gemm_desc;
 
 static int gemm(vit_engine *e, vithip_stream_t s, const gemm_desc *g, int *stats_ready) {
@@ -565,6 +603,7 @@ static int gemm(vit_engine *e, vithip_stream_t s, const gemm_desc *g, int *stats
             if (s == e->aux_stream[j]) a.workspace = e->gemm_ws[j + 1];
         a.handover_test = e->opt.gemm_handover_test; a.tile = e->opt.gemm_tile;
         a.arith = e->split && g->stage != VIT_STAGE_HEAD; /* every encoder GEMM (the embedding does not come through here) */
+        a.w_split = a.arith ? g->w_split : NULL;
         a.A = g->A; a.lda = g->lda; a.W = g->W; a.ldw = g->K; a.bias = g->bias; a.residual = res; a.ldr = ldr;
         a.C = g->C; a.ldc = g->ldc; a.M = g->M; a.N = g->N; a.K = g->K; a.epilogue = g->role;
         a.ln_rows = g->ln_rows; a.ln_colsum = g->ln_colsum;
@@ -714,6 +753,9 @@ static int encoder_layer(chunk_ctx *c, int l) {
     const void *w_qkv = bf16 ? (const void *)lw16[2] : lw[2], *w_out = bf16 ? (const void *)lw16[4] : lw[4],
                *w_fc1 = bf16 ? (const void *)lw16[8] : lw[8], *w_fc2 = bf16 ? (const void *)lw16[10] : lw[10];
     const float *b_qkv = lw[3], *b_fc1 = lw[9], *cs_qkv = NULL, *cs_fc1 = NULL;
+    const unsigned char *ws = e->wsplit ? e->wsplit + (size_t)l * e->wsplit_layer : NULL; /* pre-split images (split_weights) */
+    const void *ws_qkv = ws ? ws + e->wsplit_off[0] : NULL, *ws_out = ws ? ws + e->wsplit_off[1] : NULL,
+               *ws_fc1 = ws ? ws + e->wsplit_off[2] : NULL, *ws_fc2 = ws ? ws + e->wsplit_off[3] : NULL;
     if (fold) { /* the folded in_proj and fc1 (fold_ln_weights) */
         const size_t wl = (size_t)l * (3 * (size_t)D * D + (size_t)H * D);
         const float *ff = e->wfoldf + (size_t)l * (6 * D + 2 * H);
@@ -740,11 +782,13 @@ static int encoder_layer(chunk_ctx *c, int l) {
         vit_lane *ln = &c->lane[j];
         gemm_desc g = {.stage = VIT_STAGE_QKV, .bf16 = bf16, .A = fold ? ln->xa : ln->y, .lda = D, .W = w_qkv, .bias = b_qkv,
                        .C = ln->qkv, .ldc = 3 * D, .M = ln->n * T, .N = 3 * D, .K = D, .role = VITHIP_EPI_BIAS,
-                       .ln_rows = ln->tok_pairs, .ln_colsum = cs_qkv};
+                       .ln_rows = ln->tok_pairs, .ln_colsum = cs_qkv, .w_split = ws_qkv};
         if (pruned) { /* K and V of every token (in_proj rows D..3D), then Q of the class rows, whose pairs are gathered first */
             gemm_desc kv = g;
             kv.W = at(w_qkv, (size_t)D * D, esz); kv.bias = b_qkv + D; kv.C = at(ln->qkv, D, esz); kv.N = 2 * D;
             kv.ln_colsum = cs_qkv ? cs_qkv + D : NULL;
+            /* the image of rows D.. starts at a panel boundary only when D is a multiple of 128 (panel = 128 rows x K x 6 bytes) */
+            kv.w_split = ws_qkv && D % 128 == 0 ? at(ws_qkv, (size_t)D * D * 6, 1) : NULL;
             RUN(gemm(e, ln->s, &kv, NULL));
             if (fold) {
                 HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
@@ -769,7 +813,7 @@ static int encoder_layer(chunk_ctx *c, int l) {
                                       * leaves the pairs of LN2 -- except in the pruned fp32 layer, which takes them in a pass */
         vit_lane *ln = &c->lane[j];
         gemm_desc g = {.stage = VIT_STAGE_OUTPROJ, .bf16 = bf16, .A = ln->y, .lda = r * D, .W = w_out, .bias = lw[5],
-                       .C = ln->x, .ldc = r * D, .M = rows[j], .N = D, .K = D, .role = VITHIP_EPI_BIAS_RESIDUAL};
+                       .C = ln->x, .ldc = r * D, .M = rows[j], .N = D, .K = D, .role = VITHIP_EPI_BIAS_RESIDUAL, .w_split = ws_out};
         if (fold && (bf16 || !pruned)) { g.stats_rows = pairs[j]; g.stats_part = ln->partials; g.x16 = bf16 ? ln->xa : NULL; }
         RUN(gemm(e, ln->s, &g, &ln2_ready[j]));
     }
@@ -781,7 +825,7 @@ static int encoder_layer(chunk_ctx *c, int l) {
     for (int j = 0; j < c->L; ++j) { /* fc1 + GELU (ViT_seq.c:258-264) */
         const vit_lane *ln = &c->lane[j];
         gemm_desc g = {.stage = VIT_STAGE_FC1, .bf16 = bf16, .A = ln->y, .lda = D, .W = w_fc1, .bias = b_fc1, .C = ln->h, .ldc = H,
-                       .M = rows[j], .N = H, .K = D, .role = VITHIP_EPI_BIAS_GELU};
+                       .M = rows[j], .N = H, .K = D, .role = VITHIP_EPI_BIAS_GELU, .w_split = ws_fc1};
         if (fold) { g.A = ln->xa; g.lda = r * D; g.ln_rows = pairs[j]; g.ln_colsum = cs_fc1; }
         RUN(gemm(e, ln->s, &g, NULL));
     }
@@ -789,7 +833,7 @@ static int encoder_layer(chunk_ctx *c, int l) {
                                       * pairs of the next layer's LN1 when there is one */
         vit_lane *ln = &c->lane[j];
         gemm_desc g = {.stage = VIT_STAGE_FC2, .bf16 = bf16, .A = ln->h, .lda = H, .W = w_fc2, .bias = lw[11], .C = ln->x,
-                       .ldc = r * D, .M = rows[j], .N = D, .K = H, .role = VITHIP_EPI_BIAS_RESIDUAL};
+                       .ldc = r * D, .M = rows[j], .N = D, .K = H, .role = VITHIP_EPI_BIAS_RESIDUAL, .w_split = ws_fc2};
         if (fold && feeds_next) { g.stats_rows = ln->tok_pairs; g.stats_part = ln->partials; g.x16 = bf16 ? ln->xa : NULL; }
         RUN(gemm(e, ln->s, &g, &ln->stats_ready));
     }
