@@ -154,14 +154,60 @@ int vit_engine_forward_host_u8(vit_engine *e, const unsigned char *const *images
                                float *const *probs);
 
 /*
+ * Embedding outputs instead of probabilities.  With x the encoder output (the fp32 residual stream behind the last layer, T =
+ * tokens rows of D = embed_dim per image) and y[i][t] = LayerNorm_final(x[i][t]) (the encoder_ln weights, vithip_layernorm_f32):
+ *
+ *   VIT_FEAT_CLS     out[i] = y[i][0]                                  [n][D]     the operand the classifier head reads
+ *   VIT_FEAT_MEAN    out[i] = 1/(T-1) * sum_{t=1}^{T-1} y[i][t]        [n][D]     mean of the patch tokens (timm global_pool='avg')
+ *   VIT_FEAT_TOKENS  out[i][t] = y[i][t], class row first              [n][T][D]  all tokens (timm forward_features)
+ *
+ * Rows are fp32 for both engine dtypes.  The head GEMM and the softmax are not launched.  CLS is the bits the head of a forward
+ * call reads.  MEAN is one pass over x (vithip_layernorm_pool_f32): the normalised tokens are never stored, and an image's row
+ * has the same bits wherever the image sits in whatever batch.  l2_normalize = 1 (CLS and MEAN only) divides each output row by
+ * max(||row||_2, 1e-12) (torch.nn.functional.normalize).
+ *
+ * The four calls mirror the four forwards: the same images, chunking, lanes, stream rules and blocking behaviour; `out` takes the
+ * place of the probabilities, rows of vit_engine_feature_row_elems() floats (device: one [n][row] array; host: caller-allocated
+ * rows out[i]).  The host calls (re)allocate the pinned output staging for the widest row seen so far: a TOKENS call holds
+ * 2 x max_batch x T x D floats of pinned and of device memory from then on.  If that does not fit, the call returns VIT_ERR_NOMEM,
+ * the staging is back at its classes-sized start and the engine stays usable.
+ * prune_last_layer engines: a CLS call uses the pruned last layer (same bits as unpruned); a MEAN or TOKENS call needs every token
+ * of the last layer and runs it unpruned -- for that call only, not an error.  use_graph: the graph is keyed on the kind of output
+ * too, so forwards and feature calls on the same n and pointers never replay each other's graph.  Profiling: the launches are
+ * accounted to VIT_STAGE_LN.  vit_engine_read_logits() after a features call is an error: nothing wrote logits.
+ * VIT_ERR_ARG (the engine stays usable): NULL pointers, n <= 0, unknown kind, l2_normalize other than 0 / 1, l2_normalize with
+ * TOKENS, and what the matching forward refuses.
+ */
+enum { VIT_FEAT_CLS = 0, VIT_FEAT_MEAN = 1, VIT_FEAT_TOKENS = 2 };
+typedef struct {
+    int kind;          /* VIT_FEAT_* */
+    int l2_normalize;  /* 0 / 1; CLS and MEAN only */
+} vit_feature_spec;
+
+/* floats per output row: D, D or tokens * D; 0 on a bad spec */
+size_t vit_engine_feature_row_elems(const vit_engine *e, const vit_feature_spec *spec);
+int vit_engine_features_device(vit_engine *e, const float *d_images, int n, const vit_feature_spec *spec, float *d_out, void *stream);
+int vit_engine_features_host(vit_engine *e, const float *const *images, int n, const vit_feature_spec *spec, float *const *out);
+int vit_engine_features_device_u8(vit_engine *e, const unsigned char *d_images, int n, const float *mean, const float *std,
+                                  const vit_feature_spec *spec, float *d_out, void *stream);
+int vit_engine_features_host_u8(vit_engine *e, const unsigned char *const *images, int n, const float *mean, const float *std,
+                                const vit_feature_spec *spec, float *const *out);
+
+/*
  * The fp32 GEMMs' helper-piece hand-over (csrc/vit_gemm_persistent.hip) since the last call, summed over the lanes: tiles whose
  * first K-steps came from a helper workgroup / tiles whose owner found no piece when it looked and computed all of it.  The
  * second number is lost time, never a wrong result (nothing in the hand-over waits or gives up).  Synchronises the device.
  */
 int vit_engine_handover_stats(vit_engine *e, long *taken, long *recomputed);
 
-/* Debug/test taps: copy the logits of the most recent chunk (rows = images of that chunk). */
+/* Debug/test taps: copy the logits of the most recent chunk (rows = images of that chunk; an error after a features call). */
 int vit_engine_read_logits(vit_engine *e, float *dst, int rows);
+/* Where a MEAN features chunk of nb <= max_batch images would put things inside the engine's y allocation (max_batch * tokens *
+ * embed_dim floats), for lane `lane` under the current lane setting; launches nothing.  Byte offsets from the allocation's start:
+ * range[0..1] the lane's pooling scratch, [2..3] the lane's rows of y, [4..5] the lane's bf16 copy of x (0, 0 when it has none
+ * there).  Lanes run on independent streams, so a lane's scratch must lie inside its own y rows and clear of every other lane's
+ * ranges (tests/test_gpu_features.py).  Returns the number of lanes the chunk uses, -1 on bad arguments. */
+int vit_engine_debug_pool_scratch(vit_engine *e, int nb, int lane, size_t range[6]);
 
 int vit_engine_get_stage_times(vit_engine *e, vit_stage_times *out);  /* syncs, then reports */
 void vit_engine_reset_stage_times(vit_engine *e);

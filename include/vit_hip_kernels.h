@@ -317,6 +317,27 @@ int vithip_softmax_top1_f32(vithip_stream_t stream, const float *logits, int ld_
 int vithip_images_u8_to_f32(vithip_stream_t stream, const unsigned char *src, float *dst, int n, int img_size, int chans,
                             const float *mean, const float *std);
 
+/*
+ * Embedding outputs (csrc/vit_pool.hip).  LayerNorm and mean over tokens in ONE pass over x; the LayerNorm rows are never stored:
+ *     out[i][0..dim) = gamma * mean_{t in [first_tok, tokens)} ((x_it - mean_it) * inv_std_it) + beta,
+ * row (i, t) at x + (i * tokens + t) * ldx, the row statistics those of vithip_layernorm_f32 to the bit.  gamma / beta are applied
+ * once, to the pooled normalised rows, for every shape (the mean is linear: it is the mean of the LayerNorm rows up to rounding).
+ * Deterministic and position independent: an image's rows are cut into segments of 16 tokens, a workgroup sums one segment in a
+ * fixed order, a second small launch adds the segment sums in index order -- the order depends on (tokens, first_tok, dim) only,
+ * so an image's output row has the same bits at every place of every batch.  No atomics.
+ * l2_normalize = 1: each output row is then divided by max(||row||_2, 1e-12) (vithip_l2_normalize_rows_f32, a third launch).
+ * workspace: vithip_layernorm_pool_f32_workspace_floats(images, tokens, first_tok, dim) floats of device scratch, 16-byte aligned,
+ * owned by the caller and free again when the launches have run (never more than the images * tokens * dim floats of x's own size).
+ * dim % 4 == 0, dim <= 2048, tokens >= 2, 0 <= first_tok < tokens, ldx / ldo >= dim and multiples of 4, pointers 16-byte aligned;
+ * hipErrorInvalidValue otherwise.
+ */
+size_t vithip_layernorm_pool_f32_workspace_floats(int images, int tokens, int first_tok, int dim);
+int vithip_layernorm_pool_f32(vithip_stream_t stream, const float *x, size_t ldx, float *out, size_t ldo, const float *gamma,
+                              const float *beta, int images, int tokens, int first_tok, int dim, int l2_normalize, float *workspace);
+/* x[r][0..dim) /= max(||x[r]||_2, 1e-12) in place (torch.nn.functional.normalize), one workgroup per row: a row's bits do not
+ * depend on the number of rows.  dim % 4 == 0, ldx >= dim and a multiple of 4, x 16-byte aligned. */
+int vithip_l2_normalize_rows_f32(vithip_stream_t stream, float *x, size_t ldx, int rows, int dim);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,19 @@ class COptions(C.Structure):
                 ("gemm_handover_test", C.c_int), ("host_first_piece", C.c_int), ("fp32_split", C.c_int)]
 
 
+class CFeatureSpec(C.Structure):  # vit_feature_spec
+    _fields_ = [("kind", C.c_int), ("l2_normalize", C.c_int)]
+
+
+FEATURE_KINDS = {"cls": 0, "mean": 1, "tokens": 2}  # VIT_FEAT_*
+
+
+def feature_spec(kind, l2_normalize=False) -> CFeatureSpec:
+    """kind: "cls" | "mean" | "tokens" (or a raw VIT_FEAT_* integer, passed through unchecked for the C side to judge)."""
+    k = FEATURE_KINDS[kind] if isinstance(kind, str) else int(kind)
+    return CFeatureSpec(k, int(l2_normalize))
+
+
 class CStageTimes(C.Structure):
     _fields_ = [("ms", C.c_double * len(STAGES)), ("launches", C.c_long * len(STAGES)), ("images", C.c_long)]
 
@@ -148,6 +161,21 @@ def lib() -> C.CDLL:
         L.vit_engine_forward_device_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, f32p, f32p, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_void_p]
         L.vit_engine_forward_host_u8.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, f32p, f32p, C.POINTER(f32p)]
+        if hasattr(L, "vit_engine_features_device"):  # VIT_HIP_LIBRARY may name an earlier build (A/B timing): it has no feature calls
+            L.vit_engine_feature_row_elems.restype = C.c_size_t
+            L.vit_engine_feature_row_elems.argtypes = [C.c_void_p, C.POINTER(CFeatureSpec)]
+            L.vit_engine_features_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(CFeatureSpec), C.c_void_p, C.c_void_p]
+            L.vit_engine_features_host.argtypes = [C.c_void_p, C.POINTER(f32p), C.c_int, C.POINTER(CFeatureSpec), C.POINTER(f32p)]
+            L.vit_engine_features_device_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, f32p, f32p, C.POINTER(CFeatureSpec), C.c_void_p,
+                                                        C.c_void_p]
+            L.vit_engine_features_host_u8.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, f32p, f32p, C.POINTER(CFeatureSpec),
+                                                      C.POINTER(f32p)]
+            L.vithip_layernorm_pool_f32_workspace_floats.restype = C.c_size_t
+            L.vithip_layernorm_pool_f32_workspace_floats.argtypes = [C.c_int] * 4
+            L.vithip_layernorm_pool_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+            L.vithip_l2_normalize_rows_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int]
+            L.vit_engine_debug_pool_scratch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
         L.vithip_images_u8_to_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, f32p, f32p]
         L.vit_engine_read_logits.argtypes = [C.c_void_p, f32p, C.c_int]
         L.vit_engine_sync.argtypes = [C.c_void_p]
@@ -511,6 +539,31 @@ def layernorm(x, gamma, beta) -> np.ndarray:
     return dy.numpy()
 
 
+def layernorm_pool(x, gamma, beta, images: int, tokens: int, first_tok: int = 1, l2_normalize: bool = False) -> np.ndarray:
+    """vithip_layernorm_pool_f32: x [images * tokens][ld >= dim] (dim = len(gamma)) -> [images][dim], the mean over tokens
+    first_tok.. of the LayerNorm rows, optionally L2-normalised.  Columns dim.. of x are padding (ldx > dim)."""
+    x = _as_f32(x)
+    rows, ldx = x.shape
+    dim = int(np.asarray(gamma).size)
+    assert rows == images * tokens and ldx >= dim
+    L = lib()
+    dx, dg, db = DeviceArray.from_numpy(x), DeviceArray.from_numpy(_as_f32(gamma)), DeviceArray.from_numpy(_as_f32(beta))
+    do = DeviceArray((images, dim))
+    ws = DeviceArray((max(1, L.vithip_layernorm_pool_f32_workspace_floats(images, tokens, first_tok, dim)),))
+    hip_check(L.vithip_layernorm_pool_f32(None, dx.ptr, ldx, do.ptr, dim, dg.ptr, db.ptr, images, tokens, first_tok, dim,
+                                          int(l2_normalize), ws.ptr), "vithip_layernorm_pool_f32")
+    return do.numpy()
+
+
+def l2_normalize_rows(x) -> np.ndarray:
+    """vithip_l2_normalize_rows_f32: row / max(||row||_2, 1e-12)."""
+    x = _as_f32(x)
+    rows, dim = x.shape
+    dx = DeviceArray.from_numpy(x)
+    hip_check(lib().vithip_l2_normalize_rows_f32(None, dx.ptr, dim, rows, dim), "vithip_l2_normalize_rows_f32")
+    return dx.numpy()
+
+
 def ln_fold_weights_f32(W, bias, gamma, beta):
     """vithip_ln_fold_weights_f32 -> (Wf [N][K], colsum [N], bias_f [N])."""
     W, bias, gamma, beta = _as_f32(W), _as_f32(bias), _as_f32(gamma), _as_f32(beta)
@@ -730,6 +783,66 @@ class Engine:
         m, s = _norm_consts(mean, std, self.cfg.in_chans)
         self._check(lib().vit_engine_forward_device_u8(self._h, d_images, n, m, s, d_probs, d_label or None, d_prob or None,
                                                        stream or None), "vit_engine_forward_device_u8")
+
+    # ---- embedding outputs (vit_engine_features_*): kind "cls" | "mean" | "tokens", fp32 rows for both dtypes ----
+    def feature_shape(self, n: int, kind="cls", l2_normalize=False) -> tuple:
+        """Shape of the rows n images give: (n, D), or (n, tokens, D) for "tokens"."""
+        spec = feature_spec(kind, l2_normalize)
+        elems = lib().vit_engine_feature_row_elems(self._h, C.byref(spec))
+        if elems == 0:
+            raise VitError(f"bad feature spec (kind={kind!r}, l2_normalize={l2_normalize!r})")
+        D = self.cfg.embed_dim
+        return (n, D) if elems == D else (n, elems // D, D)
+
+    def features(self, images: np.ndarray, kind="cls", l2_normalize=False) -> np.ndarray:
+        """Host path: per-image pointers in, per-image rows out (class token, patch-token mean, or all tokens)."""
+        images = _as_f32(images)
+        n = images.shape[0]
+        spec = feature_spec(kind, l2_normalize)
+        out = np.empty(self.feature_shape(n, kind, l2_normalize), np.float32)
+        in_ptrs = (f32p * n)(*[images[i].ctypes.data_as(f32p) for i in range(n)])
+        out_ptrs = (f32p * n)(*[out[i].ctypes.data_as(f32p) for i in range(n)])
+        self._check(lib().vit_engine_features_host(self._h, in_ptrs, n, C.byref(spec), out_ptrs), "vit_engine_features_host")
+        return out
+
+    def features_u8(self, images: np.ndarray, kind="cls", l2_normalize=False, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
+        """Host path from 8-bit pixels [n][S][S][C] (see forward_u8)."""
+        images = np.ascontiguousarray(images, np.uint8)
+        n = images.shape[0]
+        m, s = _norm_consts(mean, std, self.cfg.in_chans)
+        spec = feature_spec(kind, l2_normalize)
+        out = np.empty(self.feature_shape(n, kind, l2_normalize), np.float32)
+        in_ptrs = (C.c_void_p * n)(*[images[i].ctypes.data for i in range(n)])
+        out_ptrs = (f32p * n)(*[out[i].ctypes.data_as(f32p) for i in range(n)])
+        self._check(lib().vit_engine_features_host_u8(self._h, in_ptrs, n, m, s, C.byref(spec), out_ptrs), "vit_engine_features_host_u8")
+        return out
+
+    def features_device(self, d_images: int, n: int, d_out: int, kind="cls", l2_normalize=False, stream: int = 0) -> None:
+        """Device-resident path: raw HBM addresses, d_out [n][row] fp32, async on `stream`."""
+        spec = feature_spec(kind, l2_normalize)
+        self._check(lib().vit_engine_features_device(self._h, d_images, n, C.byref(spec), d_out, stream or None),
+                    "vit_engine_features_device")
+
+    def features_device_u8(self, d_images: int, n: int, d_out: int, kind="cls", l2_normalize=False, mean=IMAGENET_MEAN,
+                           std=IMAGENET_STD, stream: int = 0) -> None:
+        """Device-resident path from 8-bit pixels [n][S][S][C] in HBM (raw addresses), async on `stream`."""
+        m, s = _norm_consts(mean, std, self.cfg.in_chans)
+        spec = feature_spec(kind, l2_normalize)
+        self._check(lib().vit_engine_features_device_u8(self._h, d_images, n, m, s, C.byref(spec), d_out, stream or None),
+                    "vit_engine_features_device_u8")
+
+    def pool_scratch_layout(self, nb: int) -> list:
+        """vit_engine_debug_pool_scratch for every lane of a MEAN chunk of nb images: per lane a dict of byte ranges inside the y
+        allocation, {"scratch": (lo, hi), "y": (lo, hi), "xa": (lo, hi) or None}.  Launches nothing."""
+        out, lane, lanes = [], 0, 1
+        while lane < lanes:
+            r = (C.c_size_t * 6)()
+            lanes = lib().vit_engine_debug_pool_scratch(self._h, nb, lane, r)
+            if lanes < 1:
+                raise VitError(f"vit_engine_debug_pool_scratch({nb}, {lane}) failed")
+            out.append({"scratch": (r[0], r[1]), "y": (r[2], r[3]), "xa": (r[4], r[5]) if r[5] else None})
+            lane += 1
+        return out
 
     def sync(self) -> None:
         self._check(lib().vit_engine_sync(self._h), "vit_engine_sync")

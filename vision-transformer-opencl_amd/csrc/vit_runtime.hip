@@ -38,9 +38,15 @@ int vithip_get_device_info(int device, vithip_device_info *info) {
     return 0;
 }
 
-int vithip_malloc(void **ptr, size_t bytes) { RET(hipMalloc(ptr, bytes)); }
+// A failed allocation is reported through the return value; the runtime's recorded error is cleared with it, so that the
+// hipGetLastError() check behind a later kernel launch does not find it.
+static int alloc_result(hipError_t e) {
+    if (e != hipSuccess) (void)hipGetLastError();
+    return static_cast<int>(e);
+}
+int vithip_malloc(void **ptr, size_t bytes) { return alloc_result(hipMalloc(ptr, bytes)); }
 int vithip_free(void *ptr) { RET(hipFree(ptr)); }
-int vithip_host_alloc(void **ptr, size_t bytes) { RET(hipHostMalloc(ptr, bytes, hipHostMallocDefault)); }
+int vithip_host_alloc(void **ptr, size_t bytes) { return alloc_result(hipHostMalloc(ptr, bytes, hipHostMallocDefault)); }
 int vithip_host_free(void *ptr) { RET(hipHostFree(ptr)); }
 
 int vithip_memcpy_h2d(void *dst, const void *src, size_t bytes, vithip_stream_t stream) {

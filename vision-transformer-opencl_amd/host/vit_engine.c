@@ -8,6 +8,7 @@
  *   depth x { LN1 -> QKV GEMM -> fused attention -> out_proj GEMM (+bias +residual, in place)
  *             LN2 -> fc1 GEMM (+bias +GELU) -> fc2 GEMM (+bias +residual, in place) }
  *   LN on the class-token rows only -> head GEMM -> softmax + top-1
+ *   (a features call ends instead in the final LN of the rows it returns, or in the fused LN + mean over the patch tokens)
  *
  * Weights are validated and uploaded once (the reference re-uploads them per op per image,
  * e.g. ViT_opencl.c:136,630-631); activations never leave HBM between stages (the reference
@@ -36,6 +37,18 @@ typedef struct {
     int u8;
     float mean[VIT_MAX_U8_CHANS], std[VIT_MAX_U8_CHANS];
 } vit_input;
+
+/* What a forward writes, besides where: probabilities [n][classes] and the optional top-1 records, or the embedding rows `spec`
+ * asks for (stage_features), [n][out_row_elems()].  Zero-filled before use: the graph cache compares it bytewise.  The pointers are
+ * those of the call's (or chunk's) first image. */
+typedef struct {
+    int features;          /* 0: dst = probabilities, label / prob = top-1 (may be NULL); 1: dst = the rows of spec */
+    vit_feature_spec spec;
+    int reserved;          /* keeps the struct free of padding, which a bytewise comparison would read */
+    float *dst;
+    int *label;
+    float *prob;
+} vit_output;
 
 struct vit_engine {
     vit_config cfg;
@@ -66,7 +79,7 @@ struct vit_engine {
     int n_cus;                   /* compute units of the device */
     /* use_graph: the captured forward and what it was captured for */
     vithip_graph_t graph;
-    const void *g_images; vit_input g_in; float *g_probs; int *g_label; float *g_prob; int g_n;
+    const void *g_images; vit_input g_in; vit_output g_out; int g_n;
     unsigned short **w16;        /* per weight index; NULL for tensors that stay fp32 */
     int weights_loaded;
 
@@ -75,6 +88,7 @@ struct vit_engine {
     /* host-pointer path: double-buffered staging so that gather + H2D of piece i+1 overlap compute of piece i */
     float *in_stage[2], *out_stage[2];   /* device */
     float *pin_in[2], *pin_out[2];       /* pinned host */
+    size_t out_row_cap;                  /* floats per image out_stage / pin_out hold: classes, or the widest feature row seen */
     vithip_stream_t copy_stream;
     vithip_event_t ev_h2d[2], ev_done[2];
     /* 8-bit input: the host path's byte staging (allocated by the first u8 host call); the device path normalises into
@@ -304,6 +318,7 @@ int vit_engine_create(vit_engine **out, const vit_config *cfg, const vit_engine_
         }
     }
     HIP_TRY(e, vithip_stream_create(&e->copy_stream));
+    e->out_row_cap = NC;
     for (int b = 0; b < 2; ++b) {
         HIP_TRY(e, vithip_malloc((void **)&e->in_stage[b], B * img * sizeof(float)));
         HIP_TRY(e, vithip_malloc((void **)&e->out_stage[b], B * NC * sizeof(float)));
@@ -383,8 +398,9 @@ int vit_engine_set_profile(vit_engine *e, int on) {
 /* A captured forward holds the old weight addresses in its kernel arguments: drop it with them. */
 static void drop_graph(vit_engine *e) {
     if (e->graph) { vithip_graph_destroy(e->graph); e->graph = NULL; }
-    e->g_n = 0; e->g_images = NULL; e->g_probs = NULL; e->g_label = NULL; e->g_prob = NULL;
+    e->g_n = 0; e->g_images = NULL;
     memset(&e->g_in, 0, sizeof(e->g_in));
+    memset(&e->g_out, 0, sizeof(e->g_out));
 }
 
 /* (Re)allocate the device blob for this model and point w[] / w16[] into it (no data yet). */
@@ -668,6 +684,7 @@ typedef struct {
     vit_lane lane[VIT_MAX_LANES];
     int L;                       /* lanes in use for this chunk */
     int T, D, H, NC;
+    int pruned;                  /* the last layer computes the class rows only: prune_last_layer, unless the chunk's output needs every token */
 } chunk_ctx;
 
 #define RUN(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
@@ -739,14 +756,15 @@ static int row_stats(chunk_ctx *c, const vit_lane *ln, size_t ldx, float *pairs,
  *   fold    the LayerNorm fold (vit_hip_kernels.h, "LayerNorm folding"): in_proj and fc1 read the raw rows (x, or its bf16 copy)
  *           with the gamma/beta-folded operands (fold_ln_weights) and a pair per row; a LayerNorm becomes a statistics pass,
  *           or nothing where the residual GEMM in front has left the pairs.  The bf16 Q rows carry the scores' exponent factor.
- *   pruned  prune_last_layer: K and V of every token, everything else for the class rows only.  The class rows of a [n*T][w]
+ *   pruned  prune_last_layer, for chunks whose output reads the class rows only (chunk_ctx.pruned: probabilities and CLS features;
+ *           MEAN and TOKENS run the layer in full): K and V of every token, everything else for the class rows only.  The class rows of a [n*T][w]
  *           buffer are rows 0, T, 2T, ... = a matrix with leading dimension T*w, which every operator takes as it is.
  */
 static int encoder_layer(chunk_ctx *c, int l) {
     vit_engine *e = c->e;
     const int T = c->T, D = c->D, H = c->H, heads = e->cfg.num_heads;
     const int bf16 = e->opt.dtype == VIT_DTYPE_BF16, fold = e->fold, feeds_next = l + 1 < e->cfg.depth;
-    const int pruned = e->opt.prune_last_layer && T <= 224 && !feeds_next;
+    const int pruned = c->pruned && !feeds_next;
     const size_t esz = bf16 ? sizeof(unsigned short) : sizeof(float); /* GEMM weights and activations */
     float **lw = e->w + 4 + VIT_WEIGHTS_PER_LAYER * l;
     unsigned short **lw16 = e->w16 + 4 + VIT_WEIGHTS_PER_LAYER * l;
@@ -868,15 +886,60 @@ static int stage_head(chunk_ctx *c, float *d_probs, int *d_label, float *d_prob)
     return VIT_OK;
 }
 
-/* d_images: the chunk's first image, of the kind `in` says; f32_stage: where 8-bit images are normalised to (max_batch images) */
-static int forward_chunk(vit_engine *e, vithip_stream_t s, const void *d_images, const vit_input *in, float *f32_stage, int nb,
-                         float *d_probs, int *d_label, float *d_prob) {
+/* floats per image of what `out` writes */
+static size_t out_row_elems(const vit_engine *e, const vit_output *out) {
+    if (!out->features) return (size_t)e->cfg.num_classes;
+    return (out->spec.kind == VIT_FEAT_TOKENS ? (size_t)e->tokens : 1) * (size_t)e->cfg.embed_dim;
+}
+
+/* The embedding rows of the chunk instead of the head: the final LayerNorm of the class rows (exactly the launch stage_head makes,
+ * pointed at the caller's rows), of every row, or fused with the mean over the patch tokens (vithip_layernorm_pool_f32).
+ * The pooling scratch is the head of the lane's OWN rows of y (ln->y: n * T * D elements of 4 or, bf16 engines, 2 bytes), which the
+ * lane's own stream has finished with behind its last layer.  Nothing of another lane may be touched: lanes run on independent
+ * streams and the others may still be in their last layer, reading their y and (fold) the bf16 copy of x in y's upper half.  The
+ * scratch is one [D] fp32 row per 16 tokens, at most n * T * D * 2 bytes for every T >= 2; checked below all the same. */
+static float *pool_scratch(const chunk_ctx *c, const vit_lane *ln, size_t *bytes) {
+    *bytes = vithip_layernorm_pool_f32_workspace_floats(ln->n, c->T, 1, c->D) * sizeof(float);
+    return (float *)ln->y;
+}
+
+static int stage_features(chunk_ctx *c, const vit_output *out) {
+    vit_engine *e = c->e;
+    const size_t T = (size_t)c->T, D = (size_t)c->D;
+    float **fw = e->w + 4 + VIT_WEIGHTS_PER_LAYER * e->cfg.depth;
+    for (int j = 0; j < c->L; ++j) {
+        const vit_lane *ln = &c->lane[j];
+        float *dst = out->dst + (size_t)ln->off * out_row_elems(e, out);
+        HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
+        if (out->spec.kind == VIT_FEAT_CLS)
+            HIP_TRY(e, vithip_layernorm_f32(ln->s, ln->x, T * D, dst, D, fw[0], fw[1], ln->n, c->D));
+        else if (out->spec.kind == VIT_FEAT_TOKENS)
+            HIP_TRY(e, vithip_layernorm_f32(ln->s, ln->x, D, dst, D, fw[0], fw[1], ln->n * c->T, c->D));
+        else {
+            const size_t esz = e->opt.dtype == VIT_DTYPE_BF16 ? sizeof(unsigned short) : sizeof(float);
+            size_t need;
+            float *scratch = pool_scratch(c, ln, &need);
+            if (need == 0 || need > (size_t)ln->n * T * D * esz || ((size_t)scratch & 15))
+                return fail(e, VIT_ERR_STATE, "features: the pooling scratch (%zu bytes) does not fit the lane's own %zu bytes of y", need,
+                            (size_t)ln->n * T * D * esz);
+            HIP_TRY(e, vithip_layernorm_pool_f32(ln->s, ln->x, D, dst, D, fw[0], fw[1], ln->n, c->T, 1, c->D, out->spec.l2_normalize,
+                                                 scratch));
+        }
+        if (out->spec.kind == VIT_FEAT_CLS && out->spec.l2_normalize) HIP_TRY(e, vithip_l2_normalize_rows_f32(ln->s, dst, D, ln->n, c->D));
+        HIP_TRY(e, stage_end(e, ln->s));
+    }
+    return VIT_OK;
+}
+
+/* The chunk's context for nb images written as `out` says: dimensions, whether the last layer is pruned, and the lanes -- their
+ * images, streams and rows of the activation buffers.  Launches nothing. */
+static void chunk_setup(vit_engine *e, vithip_stream_t s, int nb, const vit_output *out, chunk_ctx *c) {
     const vit_config *cfg = &e->cfg;
-    chunk_ctx ctx, *c = &ctx;
     c->e = e;
     c->T = e->tokens; c->D = cfg->embed_dim; c->H = cfg->hidden_dim; c->NC = cfg->num_classes;
     c->L = e->opt.lanes > VIT_MAX_LANES ? VIT_MAX_LANES : e->opt.lanes;
     if (c->L < 1 || nb < 2 * c->L) c->L = 1;
+    c->pruned = e->opt.prune_last_layer && c->T <= 224 && !(out->features && out->spec.kind != VIT_FEAT_CLS);
     const int bf16 = e->opt.dtype == VIT_DTYPE_BF16;
     const size_t B = (size_t)e->opt.max_batch, T = (size_t)c->T, D = (size_t)c->D, H = (size_t)c->H;
     const size_t esz = bf16 ? sizeof(unsigned short) : sizeof(float);
@@ -909,6 +972,15 @@ static int forward_chunk(vit_engine *e, vithip_stream_t s, const void *d_images,
             ln->partials = part + row0 * strips * 2;
         }
     }
+}
+
+/* d_images: the chunk's first image, of the kind `in` says; f32_stage: where 8-bit images are normalised to (max_batch images);
+ * out: what to write, at the chunk's first row */
+static int forward_chunk(vit_engine *e, vithip_stream_t s, const void *d_images, const vit_input *in, float *f32_stage, int nb,
+                         const vit_output *out) {
+    const vit_config *cfg = &e->cfg;
+    chunk_ctx ctx, *c = &ctx;
+    chunk_setup(e, s, nb, out, c);
 
     if (c->L > 1) { /* fork: the other lanes start after everything already queued on s */
         HIP_TRY(e, vithip_event_record(e->ev_fork, s));
@@ -916,12 +988,13 @@ static int forward_chunk(vit_engine *e, vithip_stream_t s, const void *d_images,
     }
     RUN(stage_embed(c, d_images, in, f32_stage));
     for (int l = 0; l < cfg->depth; ++l) RUN(encoder_layer(c, l));
-    RUN(stage_head(c, d_probs, d_label, d_prob));
+    if (out->features) RUN(stage_features(c, out));
+    else RUN(stage_head(c, out->dst, out->label, out->prob));
     for (int j = 1; j < c->L; ++j) { /* join */
         HIP_TRY(e, vithip_event_record(e->ev_join[j - 1], c->lane[j].s));
         HIP_TRY(e, vithip_stream_wait_event(s, e->ev_join[j - 1]));
     }
-    e->last_rows = nb;
+    e->last_rows = out->features ? 0 : nb; /* rows of e->logits the chunk wrote (vit_engine_read_logits) */
     return VIT_OK;
 }
 #undef RUN
@@ -950,6 +1023,36 @@ static int input_u8(vit_engine *e, const char *who, const float *mean, const flo
     return VIT_OK;
 }
 
+/* The two kinds of output descriptor: probabilities + top-1 (the forwards), or the checked feature spec of a features call. */
+static vit_output output_probs(float *probs, int *label, float *prob) {
+    vit_output out;
+    memset(&out, 0, sizeof(out));
+    out.dst = probs; out.label = label; out.prob = prob;
+    return out;
+}
+static int output_features(vit_engine *e, const char *who, const vit_feature_spec *spec, float *dst, vit_output *out) {
+    memset(out, 0, sizeof(*out));
+    if (!spec) return fail(e, VIT_ERR_ARG, "%s: the feature spec is required", who);
+    if (spec->kind != VIT_FEAT_CLS && spec->kind != VIT_FEAT_MEAN && spec->kind != VIT_FEAT_TOKENS)
+        return fail(e, VIT_ERR_ARG, "%s: unknown feature kind %d", who, spec->kind);
+    if (spec->l2_normalize != 0 && spec->l2_normalize != 1)
+        return fail(e, VIT_ERR_ARG, "%s: l2_normalize must be 0 or 1 (got %d)", who, spec->l2_normalize);
+    if (spec->l2_normalize && spec->kind == VIT_FEAT_TOKENS)
+        return fail(e, VIT_ERR_ARG, "%s: l2_normalize applies to the CLS and MEAN rows, not to TOKENS", who);
+    if (spec->kind == VIT_FEAT_MEAN && e->tokens < 2) return fail(e, VIT_ERR_ARG, "%s: MEAN needs at least one patch token", who);
+    out->features = 1;
+    out->spec.kind = spec->kind; out->spec.l2_normalize = spec->l2_normalize;
+    out->dst = dst;
+    return VIT_OK;
+}
+
+size_t vit_engine_feature_row_elems(const vit_engine *e, const vit_feature_spec *spec) {
+    if (!e || !spec || spec->kind < VIT_FEAT_CLS || spec->kind > VIT_FEAT_TOKENS || (spec->l2_normalize != 0 && spec->l2_normalize != 1) ||
+        (spec->l2_normalize && spec->kind == VIT_FEAT_TOKENS))
+        return 0;
+    return (spec->kind == VIT_FEAT_TOKENS ? (size_t)e->tokens : 1) * (size_t)e->cfg.embed_dim;
+}
+
 /* An 8-bit device-path call normalises into in_stage[0] and uses it until s gets past its kernels: the next host-pointer call's
  * uploads wait for that (ev_in_stage). */
 static int in_stage_taken(vit_engine *e, const vit_input *in, vithip_stream_t s) {
@@ -961,19 +1064,18 @@ static int in_stage_taken(vit_engine *e, const vit_input *in, vithip_stream_t s)
 
 /* The device-resident forward of either input kind: chunks of at most chunk_limit() images, the use_graph cache.  8-bit chunks
  * are normalised into in_stage[0]; chunks run one after the other on s (a chunk's lanes fork behind the previous chunk's join). */
-static int forward_device_in(vit_engine *e, const void *d_images, const vit_input *in, int n, float *d_probs,
-                             int *d_top1_label, float *d_top1_prob, void *stream) {
+static int forward_device_in(vit_engine *e, const void *d_images, const vit_input *in, int n, const vit_output *out, void *stream) {
     if (!e->weights_loaded) return fail(e, VIT_ERR_STATE, "forward before vit_engine_load_weights()");
     vithip_stream_t s = stream ? (vithip_stream_t)stream : e->stream;
     const size_t img = (size_t)e->cfg.in_chans * e->cfg.img_size * e->cfg.img_size * (in->u8 ? 1 : sizeof(float)); /* bytes */
-    const size_t NC = (size_t)e->cfg.num_classes;
+    const size_t row = out_row_elems(e, out);
     HIP_TRY(e, vithip_set_device(e->opt.device)); /* the current device is per host thread: several engines may share a process */
     if (in->u8 && !e->ev_in_stage) HIP_TRY(e, vithip_event_create(&e->ev_in_stage));
     const int chunk = chunk_limit(e);
     const int graphable = e->opt.use_graph && !e->opt.profile && e->opt.lanes == 1 && s != NULL;
-    /* the key holds the input kind and the normalisation too: both are baked into the captured kernel arguments */
+    /* the key holds the input kind, the normalisation and the output descriptor too: all are baked into the captured launches */
     if (graphable && e->graph && e->g_n == n && e->g_images == d_images && !memcmp(&e->g_in, in, sizeof(*in)) &&
-        e->g_probs == d_probs && e->g_label == d_top1_label && e->g_prob == d_top1_prob) {
+        !memcmp(&e->g_out, out, sizeof(*out))) {
         HIP_TRY(e, vithip_graph_launch(e->graph, s));
         return in_stage_taken(e, in, s);
     }
@@ -983,9 +1085,11 @@ static int forward_device_in(vit_engine *e, const void *d_images, const vit_inpu
     }
     for (int done = 0; done < n; done += chunk) {
         const int nb = n - done < chunk ? n - done : chunk;
-        int rc = forward_chunk(e, s, (const char *)d_images + (size_t)done * img, in, e->in_stage[0], nb, d_probs + (size_t)done * NC,
-                               d_top1_label ? d_top1_label + done : NULL,
-                               d_top1_prob ? d_top1_prob + done : NULL);
+        vit_output o = *out;
+        o.dst += (size_t)done * row;
+        if (o.label) o.label += done;
+        if (o.prob) o.prob += done;
+        int rc = forward_chunk(e, s, (const char *)d_images + (size_t)done * img, in, e->in_stage[0], nb, &o);
         if (rc) {
             if (graphable) { /* never leave the caller's stream in capture mode: end the capture, discard what it recorded */
                 vithip_graph_t g = NULL;
@@ -999,7 +1103,7 @@ static int forward_device_in(vit_engine *e, const void *d_images, const vit_inpu
     }
     if (graphable) { /* nothing ran yet: the launches above were recorded; instantiate and run them */
         HIP_TRY(e, vithip_graph_end(s, &e->graph));
-        e->g_n = n; e->g_images = d_images; e->g_in = *in; e->g_probs = d_probs; e->g_label = d_top1_label; e->g_prob = d_top1_prob;
+        e->g_n = n; e->g_images = d_images; e->g_in = *in; e->g_out = *out;
         HIP_TRY(e, vithip_graph_launch(e->graph, s));
     }
     return in_stage_taken(e, in, s);
@@ -1011,7 +1115,8 @@ int vit_engine_forward_device(vit_engine *e, const float *d_images, int n, float
     if (!d_images || !d_probs || n <= 0) return fail(e, VIT_ERR_ARG, "forward_device: bad arguments (n=%d)", n);
     vit_input in;
     memset(&in, 0, sizeof(in));
-    return forward_device_in(e, d_images, &in, n, d_probs, d_top1_label, d_top1_prob, stream);
+    const vit_output out = output_probs(d_probs, d_top1_label, d_top1_prob);
+    return forward_device_in(e, d_images, &in, n, &out, stream);
 }
 
 int vit_engine_forward_device_u8(vit_engine *e, const unsigned char *d_images, int n, const float *mean, const float *std,
@@ -1022,7 +1127,32 @@ int vit_engine_forward_device_u8(vit_engine *e, const unsigned char *d_images, i
     vit_input in;
     const int rc = input_u8(e, "forward_device_u8", mean, std, &in);
     if (rc) return rc;
-    return forward_device_in(e, d_images, &in, n, d_probs, d_top1_label, d_top1_prob, stream);
+    const vit_output out = output_probs(d_probs, d_top1_label, d_top1_prob);
+    return forward_device_in(e, d_images, &in, n, &out, stream);
+}
+
+int vit_engine_features_device(vit_engine *e, const float *d_images, int n, const vit_feature_spec *spec, float *d_out, void *stream) {
+    if (!e) return VIT_ERR_ARG;
+    if (!d_images || !d_out || n <= 0) return fail(e, VIT_ERR_ARG, "features_device: bad arguments (n=%d)", n);
+    vit_input in;
+    vit_output out;
+    memset(&in, 0, sizeof(in));
+    const int rc = output_features(e, "features_device", spec, d_out, &out);
+    if (rc) return rc;
+    return forward_device_in(e, d_images, &in, n, &out, stream);
+}
+
+int vit_engine_features_device_u8(vit_engine *e, const unsigned char *d_images, int n, const float *mean, const float *std,
+                                  const vit_feature_spec *spec, float *d_out, void *stream) {
+    if (!e) return VIT_ERR_ARG;
+    if (!d_images || !d_out || n <= 0) return fail(e, VIT_ERR_ARG, "features_device_u8: bad arguments (n=%d)", n);
+    if ((size_t)d_images & 3) return fail(e, VIT_ERR_ARG, "features_device_u8: d_images must be 4-byte aligned");
+    vit_input in;
+    vit_output out;
+    int rc = input_u8(e, "features_device_u8", mean, std, &in);
+    if (!rc) rc = output_features(e, "features_device_u8", spec, d_out, &out);
+    if (rc) return rc;
+    return forward_device_in(e, d_images, &in, n, &out, stream);
 }
 
 int vit_engine_sync(vit_engine *e) {
@@ -1067,17 +1197,60 @@ static int stage_piece(vit_engine *e, int slot, void *dst, const host_images *im
     return VIT_OK;
 }
 
+/* The output staging holds max_batch rows of out_row_cap floats: classes at first, grown to the widest feature row a host call has
+ * asked for (TOKENS: tokens * embed_dim).  Growing waits for everything in flight, frees both slots and allocates them again; if
+ * that fails the call fails with VIT_ERR_NOMEM and the staging is back at its classes-sized start. */
+static int alloc_out_stage(vit_engine *e, size_t bytes) { /* both slots, freed first; a HIP error code, with both slots freed again */
+    int rc = 0;
+    e->out_row_cap = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int b = 0; b < 2; ++b) {
+            vithip_free(e->out_stage[b]); e->out_stage[b] = NULL;
+            if (e->pin_out[b]) vithip_host_free(e->pin_out[b]);
+            e->pin_out[b] = NULL;
+        }
+        if (pass == 1) break; /* the second pass only cleans up after a failure */
+        for (int b = 0; b < 2 && !rc; ++b) {
+            rc = vithip_malloc((void **)&e->out_stage[b], bytes);
+            if (!rc) rc = vithip_host_alloc((void **)&e->pin_out[b], bytes);
+        }
+        if (!rc) break;
+    }
+    return rc;
+}
+static int ensure_out_stage(vit_engine *e, size_t row) {
+    if (row <= e->out_row_cap) return VIT_OK;
+    const size_t bytes = (size_t)e->opt.max_batch * row * sizeof(float);
+    HIP_TRY(e, vithip_device_sync());
+    int rc = alloc_out_stage(e, bytes);
+    if (rc) {
+        /* the wide rows do not fit: put the classes-sized staging back, so that the forwards go on as before this call */
+        const size_t NC = (size_t)e->cfg.num_classes;
+        e->out_row_cap = alloc_out_stage(e, (size_t)e->opt.max_batch * NC * sizeof(float)) ? 0 : NC;
+        return fail(e, VIT_ERR_NOMEM, "no memory for 2 x %zu bytes of pinned and of device output staging (HIP error %d: %s)", bytes,
+                    rc, vithip_error_string(rc));
+    }
+    e->out_row_cap = row;
+    return VIT_OK;
+}
+
 /* The host-pointer forward of either input kind.  8-bit pieces are gathered into pin_in[slot] as bytes, uploaded into
  * in8_stage[slot] and normalised into in_stage[slot] on the compute stream (stage_embed): the copy stream writes nothing else, so
  * the ev_h2d / ev_done ordering below covers them as it covers the fp32 pieces. */
-static int forward_host_in(vit_engine *e, const char *who, const host_images *images, const vit_input *in, int n, float *const *probs) {
+/* out: the kind of output (its pointers unused: the rows go through out_stage / pin_out into rows[i]) */
+static int forward_host_in(vit_engine *e, const char *who, const host_images *images, const vit_input *in, int n, const vit_output *out,
+                           float *const *rows) {
     if (!e->weights_loaded) return fail(e, VIT_ERR_STATE, "forward before vit_engine_load_weights()");
     const size_t img = (size_t)e->cfg.in_chans * e->cfg.img_size * e->cfg.img_size;
     const size_t img_bytes = img * (in->u8 ? 1 : sizeof(float));
-    const size_t NC = (size_t)e->cfg.num_classes;
+    const size_t row = out_row_elems(e, out); /* floats per image of the scatter stage */
     for (int i = 0; i < n; ++i)
-        if (!host_image(images, i) || !probs[i]) return fail(e, VIT_ERR_ARG, "%s: image or output row %d is NULL", who, i);
+        if (!host_image(images, i) || !rows[i]) return fail(e, VIT_ERR_ARG, "%s: image or output row %d is NULL", who, i);
     HIP_TRY(e, vithip_set_device(e->opt.device));
+    {
+        const int rc = ensure_out_stage(e, row);
+        if (rc) return rc;
+    }
     for (int b = 0; b < 2 && in->u8; ++b)
         if (!e->in8_stage[b]) HIP_TRY(e, vithip_malloc((void **)&e->in8_stage[b], (size_t)e->opt.max_batch * img));
     if (e->in_stage_pending) { /* an 8-bit device-path call may still read in_stage[0] */
@@ -1123,16 +1296,18 @@ static int forward_host_in(vit_engine *e, const char *who, const host_images *im
     for (int k = 0; k < np; ++k) {
         const int b = k & 1, nb = PIECE_N(k);
         HIP_TRY(e, vithip_stream_wait_event(e->stream, e->ev_h2d[b]));
-        int rc = forward_chunk(e, e->stream, up[b], in, e->in_stage[b], nb, e->out_stage[b], NULL, NULL);
+        vit_output o = *out;
+        o.dst = e->out_stage[b];
+        int rc = forward_chunk(e, e->stream, up[b], in, e->in_stage[b], nb, &o);
         if (rc) return rc;
-        HIP_TRY(e, vithip_memcpy_d2h(e->pin_out[b], e->out_stage[b], (size_t)nb * NC * sizeof(float), e->stream));
+        HIP_TRY(e, vithip_memcpy_d2h(e->pin_out[b], e->out_stage[b], (size_t)nb * row * sizeof(float), e->stream));
         HIP_TRY(e, vithip_event_record(e->ev_done[b], e->stream));
         if (e->opt.profile) e->pending_images += nb;
         if (k >= 1) { /* piece k-1 (slot b^1) is finished by now or soon: hand its rows back */
             HIP_TRY(e, vithip_event_sync(e->ev_done[b ^ 1]));
             const int first = PIECE_LO(k - 1);
             for (int i = 0; i < PIECE_N(k - 1); ++i)
-                memcpy(probs[first + i], e->pin_out[b ^ 1] + (size_t)i * NC, NC * sizeof(float));
+                memcpy(rows[first + i], e->pin_out[b ^ 1] + (size_t)i * row, row * sizeof(float));
         }
         if (k + 1 < np) { /* slot b^1 is free again (its H2D, compute and D2H are complete): refill it */
             rc = stage_piece(e, b ^ 1, up[b ^ 1], images, PIECE_LO(k + 1), PIECE_N(k + 1), img_bytes, SUB_PIECE);
@@ -1143,7 +1318,7 @@ static int forward_host_in(vit_engine *e, const char *who, const host_images *im
         const int b = (np - 1) & 1, first = PIECE_LO(np - 1);
         HIP_TRY(e, vithip_event_sync(e->ev_done[b]));
         for (int i = 0; i < PIECE_N(np - 1); ++i)
-            memcpy(probs[first + i], e->pin_out[b] + (size_t)i * NC, NC * sizeof(float));
+            memcpy(rows[first + i], e->pin_out[b] + (size_t)i * row, row * sizeof(float));
     }
 #undef PIECE_N
 #undef PIECE_LO
@@ -1160,7 +1335,8 @@ int vit_engine_forward_host(vit_engine *e, const float *const *images, int n, fl
     const host_images im = {images, NULL};
     vit_input in;
     memset(&in, 0, sizeof(in));
-    return forward_host_in(e, "forward_host", &im, &in, n, probs);
+    const vit_output out = output_probs(NULL, NULL, NULL);
+    return forward_host_in(e, "forward_host", &im, &in, n, &out, probs);
 }
 
 int vit_engine_forward_host_u8(vit_engine *e, const unsigned char *const *images, int n, const float *mean, const float *std,
@@ -1171,7 +1347,33 @@ int vit_engine_forward_host_u8(vit_engine *e, const unsigned char *const *images
     vit_input in;
     const int rc = input_u8(e, "forward_host_u8", mean, std, &in);
     if (rc) return rc;
-    return forward_host_in(e, "forward_host_u8", &im, &in, n, probs);
+    const vit_output out = output_probs(NULL, NULL, NULL);
+    return forward_host_in(e, "forward_host_u8", &im, &in, n, &out, probs);
+}
+
+int vit_engine_features_host(vit_engine *e, const float *const *images, int n, const vit_feature_spec *spec, float *const *out) {
+    if (!e) return VIT_ERR_ARG;
+    if (!images || !out || n <= 0) return fail(e, VIT_ERR_ARG, "features_host: bad arguments (n=%d)", n);
+    const host_images im = {images, NULL};
+    vit_input in;
+    vit_output o;
+    memset(&in, 0, sizeof(in));
+    const int rc = output_features(e, "features_host", spec, NULL, &o);
+    if (rc) return rc;
+    return forward_host_in(e, "features_host", &im, &in, n, &o, out);
+}
+
+int vit_engine_features_host_u8(vit_engine *e, const unsigned char *const *images, int n, const float *mean, const float *std,
+                                const vit_feature_spec *spec, float *const *out) {
+    if (!e) return VIT_ERR_ARG;
+    if (!images || !out || n <= 0) return fail(e, VIT_ERR_ARG, "features_host_u8: bad arguments (n=%d)", n);
+    const host_images im = {NULL, images};
+    vit_input in;
+    vit_output o;
+    int rc = input_u8(e, "features_host_u8", mean, std, &in);
+    if (!rc) rc = output_features(e, "features_host_u8", spec, NULL, &o);
+    if (rc) return rc;
+    return forward_host_in(e, "features_host_u8", &im, &in, n, &o, out);
 }
 
 int vit_engine_handover_stats(vit_engine *e, long *taken, long *recomputed) {
@@ -1198,6 +1400,28 @@ int vit_engine_read_logits(vit_engine *e, float *dst, int rows) {
     HIP_TRY(e, vithip_memcpy_d2h(dst, e->logits, (size_t)rows * e->cfg.num_classes * sizeof(float), e->stream));
     HIP_TRY(e, vithip_stream_sync(e->stream));
     return VIT_OK;
+}
+
+int vit_engine_debug_pool_scratch(vit_engine *e, int nb, int lane, size_t range[6]) {
+    if (!e || !range || nb <= 0 || nb > e->opt.max_batch || lane < 0) return -1;
+    vit_feature_spec spec = {VIT_FEAT_MEAN, 0};
+    vit_output out;
+    chunk_ctx c;
+    if (output_features(e, "debug_pool_scratch", &spec, NULL, &out)) return -1;
+    chunk_setup(e, e->stream, nb, &out, &c);
+    if (lane >= c.L) return -1;
+    const vit_lane *ln = &c.lane[lane];
+    const size_t esz = e->opt.dtype == VIT_DTYPE_BF16 ? sizeof(unsigned short) : sizeof(float);
+    const size_t rows = (size_t)ln->n * c.T * c.D;
+    size_t need;
+    const char *base = (const char *)e->y, *scratch = (const char *)pool_scratch(&c, ln, &need);
+    range[0] = (size_t)(scratch - base); range[1] = range[0] + need;
+    range[2] = (size_t)((const char *)ln->y - base); range[3] = range[2] + rows * esz;
+    range[4] = range[5] = 0;
+    if (ln->xa && ln->xa != (void *)ln->x) { /* the fold's bf16 copy of x, in y's upper half */
+        range[4] = (size_t)((const char *)ln->xa - base); range[5] = range[4] + rows * sizeof(unsigned short);
+    }
+    return c.L;
 }
 
 int vit_engine_get_stage_times(vit_engine *e, vit_stage_times *out) {
