@@ -194,6 +194,45 @@ int vit_engine_features_host_u8(vit_engine *e, const unsigned char *const *image
                                 const vit_feature_spec *spec, float *const *out);
 
 /*
+ * The same four calls from decoded images of any size: the engine runs the whole evaluation transform of a ViT checkpoint
+ *     Resize(resize_shorter) -> CenterCrop(cfg.img_size) -> ToTensor() -> Normalize(mean, std)
+ * on the device, in one kernel in front of the patch embedding of each lane (vithip_images_u8_resize_crop_to_f32 in
+ * vit_hip_kernels.h states the arithmetic: Pillow's 8-bit bilinear resize as torchvision runs it, bit for bit).  The outputs are
+ * bit-identical to the matching _u8 call on the bytes that torchvision's Resize + CenterCrop give, for every option and dtype.
+ *
+ * images: a HOST array of n records in all four calls, read during the call only; pixels [height][width][cfg.in_chans] uint8, rows
+ * packed, any address: DEVICE pointers in the _device_ calls, HOST pointers in the _host_ ones.  Everything else mirrors the _u8
+ * calls: chunking, lanes, stream rules, blocking behaviour, outputs, prune_last_layer rules for features; the preprocessing
+ * launches (one per 64 images of a lane) are accounted to VIT_STAGE_EMBED.
+ * use_graph: these calls always run eagerly and leave a captured graph of the other calls alone, neither replayed nor destroyed --
+ * its key would have to hold every pointer and size.
+ * Host path: a piece of the pipeline of vit_engine_forward_host ends at the usual image count or where the next image's
+ * height * width * in_chans bytes (each image's start rounded up to 16) would overflow a staging slot, whichever comes first.  A
+ * slot holds max_batch * in_chans * img_size^2 * 4 bytes (the pinned fp32 staging, and as many bytes of device memory per slot that the
+ * first such call allocates; VIT_ERR_NOMEM if it cannot, and the engine and its other calls go on working): sources that average up to
+ * 4 x the pixels of the crop pass at full max_batch, larger ones in shorter pieces.  Rows are bit-identical whatever the cut.
+ * VIT_ERR_ARG (the engine stays usable, nothing was enqueued): NULL images / pp / outputs, n <= 0, in_chans > 4, a non-finite mean or
+ * std, a zero std, resize_shorter < cfg.img_size (torchvision would pad) or > 4096, a record with NULL pixels, a height or width
+ * outside 1..16384 or a shorter side above 64 x resize_shorter, and (host path) an image that does not fit a slot alone; the message
+ * names the record.
+ */
+typedef struct {
+    const unsigned char *pixels; /* [height][width][in_chans], packed */
+    int height, width;
+} vit_image_u8;
+typedef struct {
+    int resize_shorter;          /* the crop is cfg.img_size */
+    float mean[4], std[4];       /* the first cfg.in_chans are read */
+} vit_preproc;
+int vit_engine_forward_device_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, float *d_probs,
+                                     int *d_top1_label, float *d_top1_prob, void *stream);
+int vit_engine_forward_host_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, float *const *probs);
+int vit_engine_features_device_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, const vit_feature_spec *spec,
+                                      float *d_out, void *stream);
+int vit_engine_features_host_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, const vit_feature_spec *spec,
+                                    float *const *out);
+
+/*
  * The fp32 GEMMs' helper-piece hand-over (csrc/vit_gemm_persistent.hip) since the last call, summed over the lanes: tiles whose
  * first K-steps came from a helper workgroup / tiles whose owner found no piece when it looked and computed all of it.  The
  * second number is lost time, never a wrong result (nothing in the hand-over waits or gives up).  Synchronises the device.

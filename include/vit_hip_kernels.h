@@ -318,6 +318,41 @@ int vithip_images_u8_to_f32(vithip_stream_t stream, const unsigned char *src, fl
                             const float *mean, const float *std);
 
 /*
+ * The model input from decoded 8-bit images of any size (csrc/vit_preproc.hip): torchvision's evaluation transform
+ *     Resize(R) -> CenterCrop(S) -> ToTensor() -> Normalize(mean, std)
+ * in one kernel, bit for bit what torchvision computes on the PIL images a dataset hands it.  images: a HOST array of n records,
+ * read during the call only (the records travel as kernel arguments, 64 per launch; the call is asynchronous on `stream`); pixels:
+ * DEVICE pointer to [height][width][chans] uint8, rows packed, no alignment needed.  dst [n][chans][S][S] fp32, S = img_size.
+ *
+ * Geometry (Resize with an int, CenterCrop): short, long = min, max(height, width); the shorter side becomes R = resize_shorter,
+ * the longer L = (R * long) / short (integer division); width <= height gives a resized image of oh = L, ow = R, otherwise oh = R,
+ * ow = L.  top = rne((oh - S) / 2), left = rne((ow - S) / 2), round half to even.  dst pixel (i, j) is pixel (top + i, left + j) of
+ * the resized image; only those are computed.
+ * Resize (Pillow's Image.resize((ow, oh), BILINEAR), 8 bits per channel).  Per axis (in = source extent, out = resized extent), for
+ * resized index xx, in IEEE double without fused multiply-add:
+ *     scale = (double)in / out; fs = max(scale, 1.0); support = fs; ss = 1.0 / fs; center = (xx + 0.5) * scale;
+ *     xmin = max((int)(center - support + 0.5), 0); xmax = min((int)(center + support + 0.5), in); cnt = xmax - xmin;
+ *     w[x] = 1 - a if a < 1 else 0, a = |(x + xmin - center + 0.5) * ss|; ww = sum of w[x] in index order; w[x] /= ww if ww != 0;
+ *     k[x] = (int)(0.5 + w[x] * 4194304.0)
+ * A pass: acc = 2097152 + sum_x pixel[xmin + x] * k[x] in int32, byte = min(acc >> 22, 255).  The horizontal pass comes first and is
+ * rounded to bytes, the vertical pass runs over those bytes; an axis with in == out is skipped.
+ * Normalise: the byte u of the vertical pass gives dst[c][i][j] = ((float)u / 255.0f - mean[c]) / std[c] (vithip_images_u8_to_f32).
+ *
+ * hipErrorInvalidValue, nothing launched: NULL images / dst / mean / std / pixels, n < 1, chans outside 1..4, img_size < 4 or not a
+ * multiple of 4, resize_shorter < img_size (torchvision would pad) or > 4096, a height or width outside 1..16384, a source whose
+ * shorter side exceeds 64 * resize_shorter, dst not 16-byte aligned, a non-finite mean or std, a zero std.
+ */
+typedef struct {
+    const unsigned char *pixels; /* device, [height][width][chans] */
+    int height, width;
+} vithip_image_u8;
+int vithip_images_u8_resize_crop_to_f32(vithip_stream_t stream, const vithip_image_u8 *images, int n, float *dst, int img_size, int chans,
+                                        int resize_shorter, const float *mean, const float *std);
+/* The launcher's checks of the records and sizes alone, for callers that must know before they enqueue anything: 0 = accepted,
+ * i + 1 = record i is refused, -1 = one of n, img_size, chans, resize_shorter (or a NULL array) is. */
+int vithip_images_u8_resize_crop_check(const vithip_image_u8 *images, int n, int img_size, int chans, int resize_shorter);
+
+/*
  * Embedding outputs (csrc/vit_pool.hip).  LayerNorm and mean over tokens in ONE pass over x; the LayerNorm rows are never stored:
  *     out[i][0..dim) = gamma * mean_{t in [first_tok, tokens)} ((x_it - mean_it) * inv_std_it) + beta,
  * row (i, t) at x + (i * tokens + t) * ldx, the row statistics those of vithip_layernorm_f32 to the bit.  gamma / beta are applied

@@ -63,6 +63,14 @@ class CFeatureSpec(C.Structure):  # vit_feature_spec
 FEATURE_KINDS = {"cls": 0, "mean": 1, "tokens": 2}  # VIT_FEAT_*
 
 
+class CImageU8(C.Structure):  # vit_image_u8 / vithip_image_u8: one decoded image, [height][width][chans] uint8
+    _fields_ = [("pixels", C.c_void_p), ("height", C.c_int), ("width", C.c_int)]
+
+
+class CPreproc(C.Structure):  # vit_preproc: Resize(resize_shorter) -> CenterCrop(cfg.img_size) -> Normalize(mean, std)
+    _fields_ = [("resize_shorter", C.c_int), ("mean", C.c_float * 4), ("std", C.c_float * 4)]
+
+
 def feature_spec(kind, l2_normalize=False) -> CFeatureSpec:
     """kind: "cls" | "mean" | "tokens" (or a raw VIT_FEAT_* integer, passed through unchecked for the C side to judge)."""
     k = FEATURE_KINDS[kind] if isinstance(kind, str) else int(kind)
@@ -177,6 +185,14 @@ def lib() -> C.CDLL:
             L.vithip_l2_normalize_rows_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int]
             L.vit_engine_debug_pool_scratch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
         L.vithip_images_u8_to_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, f32p, f32p]
+        if hasattr(L, "vit_engine_forward_device_images"):  # an earlier build (see above) has no decoded-image calls
+            recs, pp = C.POINTER(CImageU8), C.POINTER(CPreproc)
+            L.vithip_images_u8_resize_crop_to_f32.argtypes = [C.c_void_p, recs, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, f32p, f32p]
+            L.vithip_images_u8_resize_crop_check.argtypes = [recs, C.c_int, C.c_int, C.c_int, C.c_int]
+            L.vit_engine_forward_device_images.argtypes = [C.c_void_p, recs, C.c_int, pp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.vit_engine_forward_host_images.argtypes = [C.c_void_p, recs, C.c_int, pp, C.POINTER(f32p)]
+            L.vit_engine_features_device_images.argtypes = [C.c_void_p, recs, C.c_int, pp, C.POINTER(CFeatureSpec), C.c_void_p, C.c_void_p]
+            L.vit_engine_features_host_images.argtypes = [C.c_void_p, recs, C.c_int, pp, C.POINTER(CFeatureSpec), C.POINTER(f32p)]
         L.vit_engine_read_logits.argtypes = [C.c_void_p, f32p, C.c_int]
         L.vit_engine_sync.argtypes = [C.c_void_p]
         L.vit_engine_get_stage_times.argtypes = [C.c_void_p, C.POINTER(CStageTimes)]
@@ -694,6 +710,51 @@ def images_u8_to_f32(images, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray
     return dd.numpy()
 
 
+def image_records(images):
+    """(ptr, H, W) triples -> the CImageU8 array the C-ABI reads."""
+    images = list(images)
+    return (CImageU8 * len(images))(*[CImageU8(int(p) or None, int(h), int(w)) for p, h, w in images])
+
+
+def host_image_records(images, chans: int):
+    """A list of [H][W][C] uint8 arrays -> (contiguous arrays to keep alive, their CImageU8 records with host pointers)."""
+    keep = []
+    for im in images:
+        im = np.ascontiguousarray(im, np.uint8)
+        if im.ndim == 2:
+            im = im[:, :, None]
+        if im.ndim != 3 or im.shape[2] != chans:
+            raise ValueError(f"expected [H][W][{chans}] uint8 images, got shape {im.shape}")
+        keep.append(im)
+    return keep, image_records((im.ctypes.data, im.shape[0], im.shape[1]) for im in keep)
+
+
+def preproc_params(resize_shorter: int, mean, std, chans: int) -> CPreproc:
+    pp = CPreproc()
+    pp.resize_shorter = int(resize_shorter)
+    for name, v in (("mean", mean), ("std", std)):
+        v = np.ascontiguousarray(v, np.float32).reshape(-1)
+        if v.size != chans:
+            raise ValueError(f"expected {chans} normalisation constants, got {v.size}")
+        for c in range(chans):
+            getattr(pp, name)[c] = float(v[c])
+    return pp
+
+
+def images_u8_resize_crop_to_f32(images, img_size: int, resize_shorter: int, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
+    """vithip_images_u8_resize_crop_to_f32: a list of uint8 images [H][W][C] of any sizes -> [n][C][S][S] fp32, torchvision's
+    Resize(resize_shorter) -> CenterCrop(img_size) -> ToTensor() -> Normalize(mean, std)."""
+    chans = 1 if np.asarray(images[0]).ndim == 2 else np.asarray(images[0]).shape[2]
+    keep, _ = host_image_records(images, chans)
+    m, s = _norm_consts(mean, std, chans)
+    dev = [DeviceArray.from_numpy(im) for im in keep]
+    recs = image_records((d.ptr, im.shape[0], im.shape[1]) for d, im in zip(dev, keep))
+    dd = DeviceArray((len(keep), chans, img_size, img_size))
+    hip_check(lib().vithip_images_u8_resize_crop_to_f32(None, recs, len(keep), dd.ptr, img_size, chans, resize_shorter, m, s),
+              "vithip_images_u8_resize_crop_to_f32")
+    return dd.numpy()
+
+
 def device_info(device: int = 0) -> dict:
     info = CDeviceInfo()
     hip_check(lib().vithip_get_device_info(device, C.byref(info)), "vithip_get_device_info")
@@ -830,6 +891,46 @@ class Engine:
         spec = feature_spec(kind, l2_normalize)
         self._check(lib().vit_engine_features_device_u8(self._h, d_images, n, m, s, C.byref(spec), d_out, stream or None),
                     "vit_engine_features_device_u8")
+
+    # ---- decoded images of any size (vit_engine_*_images): Resize(resize_shorter) -> CenterCrop(img_size) -> Normalize on the device ----
+    def forward_images(self, images, resize_shorter: int, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
+        """Host path: a list of [H][W][C] uint8 arrays of any sizes in, probabilities [n][classes] out."""
+        keep, recs = host_image_records(images, self.cfg.in_chans)
+        n = len(keep)
+        pp = preproc_params(resize_shorter, mean, std, self.cfg.in_chans)
+        probs = np.empty((n, self.cfg.num_classes), np.float32)
+        out_ptrs = (f32p * n)(*[probs[i].ctypes.data_as(f32p) for i in range(n)])
+        self._check(lib().vit_engine_forward_host_images(self._h, recs, n, C.byref(pp), out_ptrs), "vit_engine_forward_host_images")
+        return probs
+
+    def forward_device_images(self, images, d_probs: int, resize_shorter: int, mean=IMAGENET_MEAN, std=IMAGENET_STD, d_label: int = 0,
+                              d_prob: int = 0, stream: int = 0) -> None:
+        """Device-resident path: images = a list of (ptr, H, W), pixels [H][W][C] uint8 in HBM (raw addresses); async on `stream`."""
+        recs = image_records(images)
+        pp = preproc_params(resize_shorter, mean, std, self.cfg.in_chans)
+        self._check(lib().vit_engine_forward_device_images(self._h, recs, len(recs), C.byref(pp), d_probs, d_label or None, d_prob or None,
+                                                           stream or None), "vit_engine_forward_device_images")
+
+    def features_images(self, images, resize_shorter: int, kind="cls", l2_normalize=False, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
+        """Host path: a list of [H][W][C] uint8 arrays of any sizes in, embedding rows out (see features)."""
+        keep, recs = host_image_records(images, self.cfg.in_chans)
+        n = len(keep)
+        pp = preproc_params(resize_shorter, mean, std, self.cfg.in_chans)
+        spec = feature_spec(kind, l2_normalize)
+        out = np.empty(self.feature_shape(n, kind, l2_normalize), np.float32)
+        out_ptrs = (f32p * n)(*[out[i].ctypes.data_as(f32p) for i in range(n)])
+        self._check(lib().vit_engine_features_host_images(self._h, recs, n, C.byref(pp), C.byref(spec), out_ptrs),
+                    "vit_engine_features_host_images")
+        return out
+
+    def features_device_images(self, images, d_out: int, resize_shorter: int, kind="cls", l2_normalize=False, mean=IMAGENET_MEAN,
+                               std=IMAGENET_STD, stream: int = 0) -> None:
+        """Device-resident path: images = a list of (ptr, H, W) in HBM, d_out [n][row] fp32; async on `stream`."""
+        recs = image_records(images)
+        pp = preproc_params(resize_shorter, mean, std, self.cfg.in_chans)
+        spec = feature_spec(kind, l2_normalize)
+        self._check(lib().vit_engine_features_device_images(self._h, recs, len(recs), C.byref(pp), C.byref(spec), d_out, stream or None),
+                    "vit_engine_features_device_images")
 
     def pool_scratch_layout(self, nb: int) -> list:
         """vit_engine_debug_pool_scratch for every lane of a MEAN chunk of nb images: per lane a dict of byte ranges inside the y

@@ -19,6 +19,7 @@
 #include <limits.h>
 #include <math.h>
 #include <stdarg.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <omp.h>
@@ -31,12 +32,20 @@
 #define MAX_EVENTS 4096   /* stage brackets kept in flight before they are read back */
 #define VIT_MAX_U8_CHANS 4 /* vithip_images_u8_to_f32 */
 
-/* What a forward reads, besides where: fp32 images [C][S][S] as the model takes them, or 8-bit pixels [S][S][C] that stage_embed
- * normalises into fp32 staging in front of the patch embedding.  Zero-filled before use: the graph cache compares it bytewise. */
+/* What a forward reads, besides where: fp32 images [C][S][S] as the model takes them, 8-bit pixels [S][S][C] that stage_embed
+ * normalises into fp32 staging in front of the patch embedding, or records of decoded 8-bit images of any size that it resizes,
+ * crops and normalises into the same staging (vithip_images_u8_resize_crop_to_f32).  Zero-filled before use: the graph cache
+ * compares it bytewise. */
+enum { VIT_IN_F32 = 0, VIT_IN_U8 = 1, VIT_IN_IMAGES = 2 };
 typedef struct {
-    int u8;
+    int kind;           /* VIT_IN_* */
+    int resize_shorter; /* VIT_IN_IMAGES */
     float mean[VIT_MAX_U8_CHANS], std[VIT_MAX_U8_CHANS];
 } vit_input;
+_Static_assert(sizeof(vit_image_u8) == sizeof(vithip_image_u8) && offsetof(vit_image_u8, pixels) == offsetof(vithip_image_u8, pixels) &&
+                   offsetof(vit_image_u8, height) == offsetof(vithip_image_u8, height) &&
+                   offsetof(vit_image_u8, width) == offsetof(vithip_image_u8, width),
+               "the engine hands its callers' records to the kernel launcher as they are");
 
 /* What a forward writes, besides where: probabilities [n][classes] and the optional top-1 records, or the embedding rows `spec`
  * asks for (stage_features), [n][out_row_elems()].  Zero-filled before use: the graph cache compares it bytewise.  The pointers are
@@ -94,6 +103,12 @@ struct vit_engine {
     /* 8-bit input: the host path's byte staging (allocated by the first u8 host call); the device path normalises into
      * in_stage[0], and ev_in_stage (recorded behind it on the caller's stream) keeps the next host call's uploads behind it */
     unsigned char *in8_stage[2];
+    /* decoded images of any size (the _images calls): the host path's byte staging, as many bytes per slot as pin_in holds
+     * (allocated by the first such host call); the records of the piece in front of the kernel; the pieces' first images */
+    unsigned char *img_stage[2];
+    vithip_image_u8 *img_recs;   /* max_batch */
+    size_t *img_off;             /* max_batch + 1: byte offsets of a piece's images inside a slot */
+    int *piece_lo; int piece_cap;
     vithip_event_t ev_in_stage;
     int in_stage_pending;
     int last_rows;
@@ -330,7 +345,9 @@ int vit_engine_create(vit_engine **out, const vit_config *cfg, const vit_engine_
 
     e->w = (float **)calloc((size_t)e->n_weights, sizeof(float *));
     e->w16 = (unsigned short **)calloc((size_t)e->n_weights, sizeof(unsigned short *));
-    if (!e->w || !e->w16) return fail(e, VIT_ERR_NOMEM, "out of host memory");
+    e->img_recs = (vithip_image_u8 *)calloc(B, sizeof(vithip_image_u8));
+    e->img_off = (size_t *)calloc(B + 1, sizeof(size_t));
+    if (!e->w || !e->w16 || !e->img_recs || !e->img_off) return fail(e, VIT_ERR_NOMEM, "out of host memory");
     if (e->opt.dtype != VIT_DTYPE_F32 && e->opt.dtype != VIT_DTYPE_BF16)
         return fail(e, VIT_ERR_ARG, "dtype must be VIT_DTYPE_F32 or VIT_DTYPE_BF16");
     if (e->opt.dtype == VIT_DTYPE_BF16 && (e->cfg.embed_dim % 64 || e->cfg.hidden_dim % 64))
@@ -352,7 +369,7 @@ void vit_engine_destroy(vit_engine *e) {
     if (e->copy_stream) { vithip_stream_sync(e->copy_stream); vithip_stream_destroy(e->copy_stream); }
     if (e->ev_in_stage) vithip_event_destroy(e->ev_in_stage);
     for (int b = 0; b < 2; ++b) {
-        vithip_free(e->in_stage[b]); vithip_free(e->out_stage[b]); vithip_free(e->in8_stage[b]);
+        vithip_free(e->in_stage[b]); vithip_free(e->out_stage[b]); vithip_free(e->in8_stage[b]); vithip_free(e->img_stage[b]);
         if (e->pin_in[b]) vithip_host_free(e->pin_in[b]);
         if (e->pin_out[b]) vithip_host_free(e->pin_out[b]);
         if (e->ev_h2d[b]) vithip_event_destroy(e->ev_h2d[b]);
@@ -366,6 +383,7 @@ void vit_engine_destroy(vit_engine *e) {
     vithip_free(e->ln_part32);
     vithip_free(e->wfoldf);
     free(e->w16);
+    free(e->img_recs); free(e->img_off); free(e->piece_lo);
     for (int j = 0; j < VIT_MAX_LANES - 1; ++j) {
         if (e->aux_stream[j]) { vithip_stream_sync(e->aux_stream[j]); vithip_stream_destroy(e->aux_stream[j]); }
         if (e->ev_join[j]) vithip_event_destroy(e->ev_join[j]);
@@ -693,7 +711,9 @@ typedef struct {
 static void *at(const void *p, size_t i, size_t esz) { return (char *)p + i * esz; }
 
 /* conv_proj + flatten_transpose + class_token + pos_emb (ViT_seq.c:25-101).  8-bit input: each lane first normalises its own
- * images into the same rows of f32_stage (one more launch of the embed stage) and embeds from there. */
+ * images into the same rows of f32_stage (one more launch of the embed stage) and embeds from there; decoded images of any size
+ * (d_images = the chunk's records): the lane's slice of the records is resized, cropped and normalised into those rows (one launch
+ * of the embed stage per 64 images). */
 static int stage_embed(chunk_ctx *c, const void *d_images, const vit_input *in, float *f32_stage) {
     vit_engine *e = c->e;
     const vit_config *cfg = &e->cfg;
@@ -706,11 +726,15 @@ static int stage_embed(chunk_ctx *c, const void *d_images, const vit_input *in, 
                         (size_t)pk <= 2 * (size_t)c->H;
     for (int j = 0; j < c->L; ++j) {
         const vit_lane *ln = &c->lane[j];
-        const float *images = in->u8 ? f32_stage + ln->off * img : (const float *)d_images + ln->off * img;
-        if (in->u8) {
+        const float *images = in->kind != VIT_IN_F32 ? f32_stage + ln->off * img : (const float *)d_images + ln->off * img;
+        if (in->kind != VIT_IN_F32) {
             HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_EMBED));
-            HIP_TRY(e, vithip_images_u8_to_f32(ln->s, (const unsigned char *)d_images + ln->off * img, f32_stage + ln->off * img,
-                                               ln->n, cfg->img_size, cfg->in_chans, in->mean, in->std));
+            if (in->kind == VIT_IN_IMAGES)
+                HIP_TRY(e, vithip_images_u8_resize_crop_to_f32(ln->s, (const vithip_image_u8 *)d_images + ln->off, ln->n, f32_stage + ln->off * img,
+                                                               cfg->img_size, cfg->in_chans, in->resize_shorter, in->mean, in->std));
+            else
+                HIP_TRY(e, vithip_images_u8_to_f32(ln->s, (const unsigned char *)d_images + ln->off * img, f32_stage + ln->off * img,
+                                                   ln->n, cfg->img_size, cfg->in_chans, in->mean, in->std));
             HIP_TRY(e, stage_end(e, ln->s));
         }
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_EMBED));
@@ -1010,7 +1034,7 @@ static int chunk_limit(const vit_engine *e) {
 /* The 8-bit input of a call (vit_engine_forward_device_u8 / _host_u8), its normalisation checked. */
 static int input_u8(vit_engine *e, const char *who, const float *mean, const float *std, vit_input *in) {
     memset(in, 0, sizeof(*in));
-    in->u8 = 1;
+    in->kind = VIT_IN_U8;
     if (!mean || !std) return fail(e, VIT_ERR_ARG, "%s: mean and std are required", who);
     if (e->cfg.in_chans > VIT_MAX_U8_CHANS)
         return fail(e, VIT_ERR_ARG, "%s: 8-bit input takes at most %d channels (in_chans = %d)", who, VIT_MAX_U8_CHANS, e->cfg.in_chans);
@@ -1020,6 +1044,26 @@ static int input_u8(vit_engine *e, const char *who, const float *mean, const flo
         in->mean[c] = mean[c];
         in->std[c] = std[c];
     }
+    return VIT_OK;
+}
+
+/* The input of an _images call: decoded 8-bit images of any size and the transform's parameters, everything checked that the kernel
+ * launcher would refuse -- every record, before the call enqueues anything. */
+static int input_images(vit_engine *e, const char *who, const vit_image_u8 *images, int n, const vit_preproc *pp, vit_input *in) {
+    if (!pp) return fail(e, VIT_ERR_ARG, "%s: the preprocessing parameters are required", who);
+    const int rc = input_u8(e, who, pp->mean, pp->std, in);
+    if (rc) return rc;
+    in->kind = VIT_IN_IMAGES;
+    in->resize_shorter = pp->resize_shorter;
+    if (pp->resize_shorter < e->cfg.img_size || pp->resize_shorter > 4096)
+        return fail(e, VIT_ERR_ARG, "%s: resize_shorter = %d must be img_size = %d .. 4096 (a smaller image would have to be padded)", who,
+                    pp->resize_shorter, e->cfg.img_size);
+    const int bad = vithip_images_u8_resize_crop_check((const vithip_image_u8 *)images, n, e->cfg.img_size, e->cfg.in_chans, pp->resize_shorter);
+    if (bad > 0)
+        return fail(e, VIT_ERR_ARG, "%s: image %d (pixels %p, %d x %d): pixels must not be NULL, height and width 1..16384, the shorter side "
+                    "at most 64 x resize_shorter", who, bad - 1, (const void *)images[bad - 1].pixels, images[bad - 1].height, images[bad - 1].width);
+    if (bad) return fail(e, VIT_ERR_ARG, "%s: unsupported geometry (img_size %d, in_chans %d, resize_shorter %d)", who, e->cfg.img_size,
+                         e->cfg.in_chans, pp->resize_shorter);
     return VIT_OK;
 }
 
@@ -1056,23 +1100,27 @@ size_t vit_engine_feature_row_elems(const vit_engine *e, const vit_feature_spec 
 /* An 8-bit device-path call normalises into in_stage[0] and uses it until s gets past its kernels: the next host-pointer call's
  * uploads wait for that (ev_in_stage). */
 static int in_stage_taken(vit_engine *e, const vit_input *in, vithip_stream_t s) {
-    if (!in->u8) return VIT_OK;
+    if (in->kind == VIT_IN_F32) return VIT_OK;
     HIP_TRY(e, vithip_event_record(e->ev_in_stage, s));
     e->in_stage_pending = 1;
     return VIT_OK;
 }
 
-/* The device-resident forward of either input kind: chunks of at most chunk_limit() images, the use_graph cache.  8-bit chunks
- * are normalised into in_stage[0]; chunks run one after the other on s (a chunk's lanes fork behind the previous chunk's join). */
+/* The device-resident forward of every input kind: chunks of at most chunk_limit() images, the use_graph cache.  8-bit chunks
+ * are normalised into in_stage[0]; chunks run one after the other on s (a chunk's lanes fork behind the previous chunk's join).
+ * Decoded images (d_images = the caller's records, a HOST array) run eagerly and leave a captured graph alone: its key would have
+ * to hold every pointer and size. */
 static int forward_device_in(vit_engine *e, const void *d_images, const vit_input *in, int n, const vit_output *out, void *stream) {
     if (!e->weights_loaded) return fail(e, VIT_ERR_STATE, "forward before vit_engine_load_weights()");
     vithip_stream_t s = stream ? (vithip_stream_t)stream : e->stream;
-    const size_t img = (size_t)e->cfg.in_chans * e->cfg.img_size * e->cfg.img_size * (in->u8 ? 1 : sizeof(float)); /* bytes */
+    /* bytes from one image of d_images to the next: fp32 or 8-bit pixels, or a record */
+    const size_t img = in->kind == VIT_IN_IMAGES ? sizeof(vithip_image_u8)
+                                                 : (size_t)e->cfg.in_chans * e->cfg.img_size * e->cfg.img_size * (in->kind == VIT_IN_U8 ? 1 : sizeof(float));
     const size_t row = out_row_elems(e, out);
     HIP_TRY(e, vithip_set_device(e->opt.device)); /* the current device is per host thread: several engines may share a process */
-    if (in->u8 && !e->ev_in_stage) HIP_TRY(e, vithip_event_create(&e->ev_in_stage));
+    if (in->kind != VIT_IN_F32 && !e->ev_in_stage) HIP_TRY(e, vithip_event_create(&e->ev_in_stage));
     const int chunk = chunk_limit(e);
-    const int graphable = e->opt.use_graph && !e->opt.profile && e->opt.lanes == 1 && s != NULL;
+    const int graphable = e->opt.use_graph && !e->opt.profile && e->opt.lanes == 1 && s != NULL && in->kind != VIT_IN_IMAGES;
     /* the key holds the input kind, the normalisation and the output descriptor too: all are baked into the captured launches */
     if (graphable && e->graph && e->g_n == n && e->g_images == d_images && !memcmp(&e->g_in, in, sizeof(*in)) &&
         !memcmp(&e->g_out, out, sizeof(*out))) {
@@ -1155,6 +1203,29 @@ int vit_engine_features_device_u8(vit_engine *e, const unsigned char *d_images, 
     return forward_device_in(e, d_images, &in, n, &out, stream);
 }
 
+int vit_engine_forward_device_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, float *d_probs,
+                                     int *d_top1_label, float *d_top1_prob, void *stream) {
+    if (!e) return VIT_ERR_ARG;
+    if (!images || !d_probs || n <= 0) return fail(e, VIT_ERR_ARG, "forward_device_images: bad arguments (n=%d)", n);
+    vit_input in;
+    const int rc = input_images(e, "forward_device_images", images, n, pp, &in);
+    if (rc) return rc;
+    const vit_output out = output_probs(d_probs, d_top1_label, d_top1_prob);
+    return forward_device_in(e, images, &in, n, &out, stream);
+}
+
+int vit_engine_features_device_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, const vit_feature_spec *spec,
+                                      float *d_out, void *stream) {
+    if (!e) return VIT_ERR_ARG;
+    if (!images || !d_out || n <= 0) return fail(e, VIT_ERR_ARG, "features_device_images: bad arguments (n=%d)", n);
+    vit_input in;
+    vit_output out;
+    int rc = input_images(e, "features_device_images", images, n, pp, &in);
+    if (!rc) rc = output_features(e, "features_device_images", spec, d_out, &out);
+    if (rc) return rc;
+    return forward_device_in(e, images, &in, n, &out, stream);
+}
+
 int vit_engine_sync(vit_engine *e) {
     if (!e) return VIT_ERR_ARG;
     HIP_TRY(e, vithip_stream_sync(e->stream));
@@ -1173,12 +1244,15 @@ static int gather_threads(void) {
     int n = omp_get_num_procs();
     return n < 1 ? 1 : (n > GATHER_THREADS_MAX ? GATHER_THREADS_MAX : n);
 }
-/* the caller's images of a host-pointer call: fp32 [C][S][S] (f32) or 8-bit [S][S][C] (u8) */
+/* the caller's images of a host-pointer call: fp32 [C][S][S] (f32), 8-bit [S][S][C] (u8) or decoded 8-bit images of any size (img) */
 typedef struct {
     const float *const *f32;
     const unsigned char *const *u8;
+    const vit_image_u8 *img;
 } host_images;
-static const void *host_image(const host_images *im, int i) { return im->u8 ? (const void *)im->u8[i] : (const void *)im->f32[i]; }
+static const void *host_image(const host_images *im, int i) {
+    return im->img ? (const void *)im->img[i].pixels : im->u8 ? (const void *)im->u8[i] : (const void *)im->f32[i];
+}
 
 static void gather_images(char *dst, const host_images *images, int first, int count, size_t img_bytes) {
     const int nt = gather_threads();
@@ -1194,6 +1268,75 @@ static int stage_piece(vit_engine *e, int slot, void *dst, const host_images *im
         HIP_TRY(e, vithip_memcpy_h2d((char *)dst + (size_t)s0 * img_bytes, pin, (size_t)c * img_bytes, e->copy_stream));
     }
     HIP_TRY(e, vithip_event_record(e->ev_h2d[slot], e->copy_stream));
+    return VIT_OK;
+}
+
+/* Decoded images of any size: a piece's images lie back to back in a slot, each start rounded up to 16 bytes. */
+static size_t image_slot_bytes(const vit_engine *e, const vit_image_u8 *im) {
+    return ((size_t)im->height * (size_t)im->width * (size_t)e->cfg.in_chans + 15) & ~(size_t)15;
+}
+static size_t image_slot_cap(const vit_engine *e) { /* what pin_in[slot] holds: max_batch fp32 images */
+    return (size_t)e->opt.max_batch * e->cfg.in_chans * e->cfg.img_size * e->cfg.img_size * sizeof(float);
+}
+/* img_off[0..count] = where the images first .. first + count - 1 of a piece lie in its slot, and where they end */
+static void image_offsets(vit_engine *e, const vit_image_u8 *images, int first, int count) {
+    e->img_off[0] = 0;
+    for (int i = 0; i < count; ++i) e->img_off[i + 1] = e->img_off[i] + image_slot_bytes(e, &images[first + i]);
+}
+/* stage_piece for decoded images: gather into pin_in[slot] at their offsets, upload to img_stage[slot] in sub-pieces of `sub` images */
+static int stage_piece_images(vit_engine *e, int slot, const vit_image_u8 *images, int first, int count, int sub) {
+    const int nt = gather_threads();
+    const size_t C = (size_t)e->cfg.in_chans;
+    char *pin = (char *)e->pin_in[slot];
+    image_offsets(e, images, first, count);
+    for (int s0 = 0; s0 < count; s0 += sub) {
+        const int c = count - s0 < sub ? count - s0 : sub;
+#pragma omp parallel for num_threads(nt) schedule(static) if (c >= 4)
+        for (int i = s0; i < s0 + c; ++i)
+            memcpy(pin + e->img_off[i], images[first + i].pixels, (size_t)images[first + i].height * (size_t)images[first + i].width * C);
+        HIP_TRY(e, vithip_memcpy_h2d(e->img_stage[slot] + e->img_off[s0], pin + e->img_off[s0], e->img_off[s0 + c] - e->img_off[s0], e->copy_stream));
+    }
+    HIP_TRY(e, vithip_event_record(e->ev_h2d[slot], e->copy_stream));
+    return VIT_OK;
+}
+/* the records of a staged piece, as the kernel reads them: the images' sizes, their pixels inside img_stage[slot] */
+static const vithip_image_u8 *piece_records(vit_engine *e, int slot, const vit_image_u8 *images, int first, int count) {
+    image_offsets(e, images, first, count);
+    for (int i = 0; i < count; ++i) {
+        e->img_recs[i].pixels = e->img_stage[slot] + e->img_off[i];
+        e->img_recs[i].height = images[first + i].height;
+        e->img_recs[i].width = images[first + i].width;
+    }
+    return e->img_recs;
+}
+
+/* The pieces of a host-pointer call: piece_lo[0..np] = their first images (piece_lo[np] = n).  The first piece has at most first_n
+ * images, every other at most chunk; a piece of decoded images also ends where the next image's bytes would overflow the slot. */
+static int cut_pieces(vit_engine *e, const char *who, const host_images *images, int n, int first_n, int chunk, int *np_out) {
+    if (n + 1 > e->piece_cap) {
+        int *p = (int *)realloc(e->piece_lo, ((size_t)n + 1) * sizeof(int));
+        if (!p) return fail(e, VIT_ERR_NOMEM, "out of host memory");
+        e->piece_lo = p; e->piece_cap = n + 1;
+    }
+    const size_t cap = image_slot_cap(e);
+    int np = 0;
+    e->piece_lo[0] = 0;
+    for (int i = 0; i < n;) {
+        const int limit = np == 0 ? first_n : chunk;
+        int cnt = n - i < limit ? n - i : limit;
+        if (images->img) {
+            size_t bytes = 0;
+            int fit = 0;
+            while (fit < cnt && bytes + image_slot_bytes(e, &images->img[i + fit]) <= cap) bytes += image_slot_bytes(e, &images->img[i + fit++]);
+            if (!fit)
+                return fail(e, VIT_ERR_ARG, "%s: image %d (%d x %d, %zu bytes) does not fit the staging of max_batch = %d fp32 images (%zu bytes)",
+                            who, i, images->img[i].height, images->img[i].width, image_slot_bytes(e, &images->img[i]), e->opt.max_batch, cap);
+            cnt = fit;
+        }
+        i += cnt;
+        e->piece_lo[++np] = i;
+    }
+    *np_out = np;
     return VIT_OK;
 }
 
@@ -1234,39 +1377,20 @@ static int ensure_out_stage(vit_engine *e, size_t row) {
     return VIT_OK;
 }
 
-/* The host-pointer forward of either input kind.  8-bit pieces are gathered into pin_in[slot] as bytes, uploaded into
+/* The host-pointer forward of every input kind.  8-bit pieces are gathered into pin_in[slot] as bytes, uploaded into
  * in8_stage[slot] and normalised into in_stage[slot] on the compute stream (stage_embed): the copy stream writes nothing else, so
- * the ev_h2d / ev_done ordering below covers them as it covers the fp32 pieces. */
+ * the ev_h2d / ev_done ordering below covers them as it covers the fp32 pieces.  Decoded images of any size go the same way through
+ * img_stage[slot], in pieces that the slot's bytes bound as well as the image count (cut_pieces). */
 /* out: the kind of output (its pointers unused: the rows go through out_stage / pin_out into rows[i]) */
 static int forward_host_in(vit_engine *e, const char *who, const host_images *images, const vit_input *in, int n, const vit_output *out,
                            float *const *rows) {
     if (!e->weights_loaded) return fail(e, VIT_ERR_STATE, "forward before vit_engine_load_weights()");
     const size_t img = (size_t)e->cfg.in_chans * e->cfg.img_size * e->cfg.img_size;
-    const size_t img_bytes = img * (in->u8 ? 1 : sizeof(float));
+    const size_t img_bytes = img * (in->kind == VIT_IN_F32 ? sizeof(float) : 1); /* fp32 and 8-bit pieces; decoded images have their own sizes */
+    const int decoded = in->kind == VIT_IN_IMAGES;
     const size_t row = out_row_elems(e, out); /* floats per image of the scatter stage */
     for (int i = 0; i < n; ++i)
         if (!host_image(images, i) || !rows[i]) return fail(e, VIT_ERR_ARG, "%s: image or output row %d is NULL", who, i);
-    HIP_TRY(e, vithip_set_device(e->opt.device));
-    {
-        const int rc = ensure_out_stage(e, row);
-        if (rc) return rc;
-    }
-    for (int b = 0; b < 2 && in->u8; ++b)
-        if (!e->in8_stage[b]) HIP_TRY(e, vithip_malloc((void **)&e->in8_stage[b], (size_t)e->opt.max_batch * img));
-    if (e->in_stage_pending) { /* an 8-bit device-path call may still read in_stage[0] */
-        HIP_TRY(e, vithip_stream_wait_event(e->copy_stream, e->ev_in_stage));
-        e->in_stage_pending = 0;
-    }
-    void *up[2]; /* where the pieces are uploaded to */
-    for (int b = 0; b < 2; ++b) up[b] = in->u8 ? (void *)e->in8_stage[b] : (void *)e->in_stage[b];
-    /*
-     * Pieces of up to max_batch images flow through two staging slots: while the GPU computes piece i,
-     * the host gathers the separately allocated images of piece i+1 into pinned memory and the copy
-     * stream uploads them; the results of piece i-1 are scattered to the caller's rows meanwhile.
-     * Nothing overlaps the gather + upload of the FIRST piece, so it is a small one, uploaded in sub-pieces of 16 images (the copy
-     * of one overlaps the gather of the next), and the rest arrives behind its compute in pieces as large as the workspace allows
-     * (large pieces keep the GEMMs' tile walks long).  Rows are bit-identical whatever the cut.
-     */
     const int chunk = chunk_limit(e);
     /* Round 5: what the first piece has to do is cover, with its compute, the gather + upload of the piece behind it -- and no
      * more than that, because a small piece computes badly (ViT-B/16 fp32, device-resident: 8 images run at 56 % of the 256-image
@@ -1285,43 +1409,80 @@ static int forward_host_in(vit_engine *e, const char *who, const host_images *im
     else if (n >= 64) first_n = (n + 1) / 2;
     if (first_n > chunk) first_n = chunk;
     if (first_n > n) first_n = n;
-    const int np = 1 + (n - first_n + chunk - 1) / chunk;
-#define PIECE_LO(i) ((i) == 0 ? 0 : ((i) >= np ? n : first_n + ((i) - 1) * chunk))
-#define PIECE_N(i) ((PIECE_LO((i) + 1) < n ? PIECE_LO((i) + 1) : n) - PIECE_LO(i))
+    int np = 0;
+    {
+        const int rc = cut_pieces(e, who, images, n, first_n, chunk, &np); /* before anything is enqueued: it may refuse an image */
+        if (rc) return rc;
+    }
+    const int *lo = e->piece_lo; /* piece k = images lo[k] .. lo[k + 1] - 1 */
+    HIP_TRY(e, vithip_set_device(e->opt.device));
+    {
+        const int rc = ensure_out_stage(e, row);
+        if (rc) return rc;
+    }
+    for (int b = 0; b < 2 && in->kind == VIT_IN_U8; ++b)
+        if (!e->in8_stage[b]) HIP_TRY(e, vithip_malloc((void **)&e->in8_stage[b], (size_t)e->opt.max_batch * img));
+    for (int b = 0; b < 2 && decoded; ++b)
+        if (!e->img_stage[b]) {
+            const int rc = vithip_malloc((void **)&e->img_stage[b], image_slot_cap(e));
+            if (rc) {
+                e->img_stage[b] = NULL;
+                return fail(e, VIT_ERR_NOMEM, "no memory for %zu bytes of device staging for decoded images (HIP error %d: %s)", image_slot_cap(e),
+                            rc, vithip_error_string(rc));
+            }
+        }
+    if (e->in_stage_pending) { /* an 8-bit device-path call may still read in_stage[0] */
+        HIP_TRY(e, vithip_stream_wait_event(e->copy_stream, e->ev_in_stage));
+        e->in_stage_pending = 0;
+    }
+    void *up[2]; /* where the pieces are uploaded to */
+    for (int b = 0; b < 2; ++b)
+        up[b] = decoded ? (void *)e->img_stage[b] : in->kind == VIT_IN_U8 ? (void *)e->in8_stage[b] : (void *)e->in_stage[b];
+    /*
+     * Pieces of up to max_batch images flow through two staging slots: while the GPU computes piece i,
+     * the host gathers the separately allocated images of piece i+1 into pinned memory and the copy
+     * stream uploads them; the results of piece i-1 are scattered to the caller's rows meanwhile.
+     * Nothing overlaps the gather + upload of the FIRST piece, so it is a small one, uploaded in sub-pieces of 16 images (the copy
+     * of one overlaps the gather of the next), and the rest arrives behind its compute in pieces as large as the workspace allows
+     * (large pieces keep the GEMMs' tile walks long).  Rows are bit-identical whatever the cut.
+     */
     /* stage piece 0 */
     {
-        int rc0 = stage_piece(e, 0, up[0], images, 0, PIECE_N(0), img_bytes, np > 1 ? SUB_PIECE_FIRST : SUB_PIECE);
+        const int sub = np > 1 ? SUB_PIECE_FIRST : SUB_PIECE;
+        int rc0 = decoded ? stage_piece_images(e, 0, images->img, 0, lo[1], sub) : stage_piece(e, 0, up[0], images, 0, lo[1], img_bytes, sub);
         if (rc0) return rc0;
     }
     for (int k = 0; k < np; ++k) {
-        const int b = k & 1, nb = PIECE_N(k);
+        const int b = k & 1, nb = lo[k + 1] - lo[k];
         HIP_TRY(e, vithip_stream_wait_event(e->stream, e->ev_h2d[b]));
         vit_output o = *out;
         o.dst = e->out_stage[b];
-        int rc = forward_chunk(e, e->stream, up[b], in, e->in_stage[b], nb, &o);
+        /* decoded images: the kernel reads the piece's records, which point into the slot the piece was uploaded to */
+        const void *src = decoded ? (const void *)piece_records(e, b, images->img, lo[k], nb) : up[b];
+        int rc = forward_chunk(e, e->stream, src, in, e->in_stage[b], nb, &o);
         if (rc) return rc;
         HIP_TRY(e, vithip_memcpy_d2h(e->pin_out[b], e->out_stage[b], (size_t)nb * row * sizeof(float), e->stream));
         HIP_TRY(e, vithip_event_record(e->ev_done[b], e->stream));
         if (e->opt.profile) e->pending_images += nb;
         if (k >= 1) { /* piece k-1 (slot b^1) is finished by now or soon: hand its rows back */
             HIP_TRY(e, vithip_event_sync(e->ev_done[b ^ 1]));
-            const int first = PIECE_LO(k - 1);
-            for (int i = 0; i < PIECE_N(k - 1); ++i)
+            const int first = lo[k - 1];
+            for (int i = 0; i < lo[k] - first; ++i)
                 memcpy(rows[first + i], e->pin_out[b ^ 1] + (size_t)i * row, row * sizeof(float));
         }
         if (k + 1 < np) { /* slot b^1 is free again (its H2D, compute and D2H are complete): refill it */
-            rc = stage_piece(e, b ^ 1, up[b ^ 1], images, PIECE_LO(k + 1), PIECE_N(k + 1), img_bytes, SUB_PIECE);
+            const int first = lo[k + 1], cnt = lo[k + 2] - first;
+            rc = decoded ? stage_piece_images(e, b ^ 1, images->img, first, cnt, SUB_PIECE)
+                         : stage_piece(e, b ^ 1, up[b ^ 1], images, first, cnt, img_bytes, SUB_PIECE);
             if (rc) return rc;
         }
     }
     {
-        const int b = (np - 1) & 1, first = PIECE_LO(np - 1);
+        const int b = (np - 1) & 1, first = lo[np - 1];
         HIP_TRY(e, vithip_event_sync(e->ev_done[b]));
-        for (int i = 0; i < PIECE_N(np - 1); ++i)
+        for (int i = 0; i < n - first; ++i)
             memcpy(rows[first + i], e->pin_out[b] + (size_t)i * row, row * sizeof(float));
     }
-#undef PIECE_N
-#undef PIECE_LO
     if (e->opt.profile) {
         int rc = collect_profile(e);
         if (rc) return rc;
@@ -1332,7 +1493,7 @@ static int forward_host_in(vit_engine *e, const char *who, const host_images *im
 int vit_engine_forward_host(vit_engine *e, const float *const *images, int n, float *const *probs) {
     if (!e) return VIT_ERR_ARG;
     if (!images || !probs || n <= 0) return fail(e, VIT_ERR_ARG, "forward_host: bad arguments (n=%d)", n);
-    const host_images im = {images, NULL};
+    const host_images im = {images, NULL, NULL};
     vit_input in;
     memset(&in, 0, sizeof(in));
     const vit_output out = output_probs(NULL, NULL, NULL);
@@ -1343,7 +1504,7 @@ int vit_engine_forward_host_u8(vit_engine *e, const unsigned char *const *images
                                float *const *probs) {
     if (!e) return VIT_ERR_ARG;
     if (!images || !probs || n <= 0) return fail(e, VIT_ERR_ARG, "forward_host_u8: bad arguments (n=%d)", n);
-    const host_images im = {NULL, images};
+    const host_images im = {NULL, images, NULL};
     vit_input in;
     const int rc = input_u8(e, "forward_host_u8", mean, std, &in);
     if (rc) return rc;
@@ -1354,7 +1515,7 @@ int vit_engine_forward_host_u8(vit_engine *e, const unsigned char *const *images
 int vit_engine_features_host(vit_engine *e, const float *const *images, int n, const vit_feature_spec *spec, float *const *out) {
     if (!e) return VIT_ERR_ARG;
     if (!images || !out || n <= 0) return fail(e, VIT_ERR_ARG, "features_host: bad arguments (n=%d)", n);
-    const host_images im = {images, NULL};
+    const host_images im = {images, NULL, NULL};
     vit_input in;
     vit_output o;
     memset(&in, 0, sizeof(in));
@@ -1367,13 +1528,37 @@ int vit_engine_features_host_u8(vit_engine *e, const unsigned char *const *image
                                 const vit_feature_spec *spec, float *const *out) {
     if (!e) return VIT_ERR_ARG;
     if (!images || !out || n <= 0) return fail(e, VIT_ERR_ARG, "features_host_u8: bad arguments (n=%d)", n);
-    const host_images im = {NULL, images};
+    const host_images im = {NULL, images, NULL};
     vit_input in;
     vit_output o;
     int rc = input_u8(e, "features_host_u8", mean, std, &in);
     if (!rc) rc = output_features(e, "features_host_u8", spec, NULL, &o);
     if (rc) return rc;
     return forward_host_in(e, "features_host_u8", &im, &in, n, &o, out);
+}
+
+int vit_engine_forward_host_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, float *const *probs) {
+    if (!e) return VIT_ERR_ARG;
+    if (!images || !probs || n <= 0) return fail(e, VIT_ERR_ARG, "forward_host_images: bad arguments (n=%d)", n);
+    const host_images im = {NULL, NULL, images};
+    vit_input in;
+    const int rc = input_images(e, "forward_host_images", images, n, pp, &in);
+    if (rc) return rc;
+    const vit_output out = output_probs(NULL, NULL, NULL);
+    return forward_host_in(e, "forward_host_images", &im, &in, n, &out, probs);
+}
+
+int vit_engine_features_host_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, const vit_feature_spec *spec,
+                                    float *const *out) {
+    if (!e) return VIT_ERR_ARG;
+    if (!images || !out || n <= 0) return fail(e, VIT_ERR_ARG, "features_host_images: bad arguments (n=%d)", n);
+    const host_images im = {NULL, NULL, images};
+    vit_input in;
+    vit_output o;
+    int rc = input_images(e, "features_host_images", images, n, pp, &in);
+    if (!rc) rc = output_features(e, "features_host_images", spec, NULL, &o);
+    if (rc) return rc;
+    return forward_host_in(e, "features_host_images", &im, &in, n, &o, out);
 }
 
 int vit_engine_handover_stats(vit_engine *e, long *taken, long *recomputed) {
