@@ -233,6 +233,55 @@ int vit_engine_features_host_images(vit_engine *e, const vit_image_u8 *images, i
                                     float *const *out);
 
 /*
+ * The class token's attention over the tokens, in the LAST encoder layer, instead of probabilities: the DINO-style saliency map of a
+ * ViT.  With q[i][h] the class row's query of image i and head h in that layer and k[i][h][t] the key of token t (T = tokens, the
+ * class token's own key first, head_dim = 64):
+ *
+ *     s_t = (q . k_t) / sqrtf(64);   p[i][h][t] = expf(s_t - max_t s) / sum_t expf(s_t - max)          (ViT_seq.c:156-190, query row 0)
+ *
+ *   VIT_ATTN_HEADS      out[i][h][t] = p[i][h][t]                                       [n][heads][T]  every row sums to 1
+ *   VIT_ATTN_HEAD_MEAN  out[i][t] = (p[i][0][t] + p[i][1][t] + ...) / (float)heads      [n][T]         heads added in order, in fp32:
+ *                                                                                       the HEADS bits of the same engine, reduced
+ *
+ * Rows are fp32 for both engine dtypes; the patch tokens are columns 1..T-1 in raster order.  The last layer runs its LayerNorm (or
+ * the fold's statistics) and its QKV GEMM; then each lane runs vithip_cls_attention_* (vit_hip_kernels.h states the arithmetic) on
+ * the Q and K it left.  Nothing else of that layer is launched, nor the final LayerNorm, the head or the softmax.  The map is the
+ * softmax the forward itself uses for the class row: fp32 engines compute it in fp32, bf16 engines from the bf16 q and k of their
+ * forward, with fp32 scores and softmax.  ln_fold and fp32_split select other arithmetic, as they do for probabilities.
+ * An image's rows have the same bits whatever prune_last_layer and lanes are set to, wherever the image sits in whatever batch and
+ * whichever of the six calls delivers the same pixels.  No atomics: calls are reproducible bit for bit.
+ *
+ * The six calls mirror the six features calls: the same images, chunking, lanes, stream rules and blocking behaviour; `out` takes
+ * the place of the feature rows, rows of vit_engine_attention_row_elems() floats (device: one [n][row] array; host: caller-allocated
+ * rows out[i]).  The host calls share the pinned output staging of the features calls and its rule: it is (re)allocated for the
+ * widest row seen so far (HEADS: heads * T floats, wider than the classes-sized start for ViT-B/16); if that does not fit, the call
+ * returns VIT_ERR_NOMEM, the staging is back at its classes-sized start and the engine stays usable.
+ * use_graph: the graph is keyed on the kind of output and the attention kind too, so forwards, feature calls and attention calls
+ * on the same n and pointers never replay each other's graph.  Profiling: the new launches (one per lane and chunk) are accounted
+ * to VIT_STAGE_ATTN.  vit_engine_read_logits() after an attention call is an error: nothing wrote logits.
+ * VIT_ERR_ARG (the engine stays usable, nothing was enqueued): NULL pointers, n <= 0, an unknown kind, reserved != 0, and what the
+ * matching forward refuses.
+ */
+enum { VIT_ATTN_HEADS = 0, VIT_ATTN_HEAD_MEAN = 1 };
+typedef struct {
+    int kind;      /* VIT_ATTN_* */
+    int reserved;  /* must be 0 */
+} vit_attention_spec;
+
+/* floats per output row: heads * tokens or tokens; 0 on a bad spec */
+size_t vit_engine_attention_row_elems(const vit_engine *e, const vit_attention_spec *spec);
+int vit_engine_cls_attention_device(vit_engine *e, const float *d_images, int n, const vit_attention_spec *spec, float *d_out, void *stream);
+int vit_engine_cls_attention_host(vit_engine *e, const float *const *images, int n, const vit_attention_spec *spec, float *const *out);
+int vit_engine_cls_attention_device_u8(vit_engine *e, const unsigned char *d_images, int n, const float *mean, const float *std,
+                                       const vit_attention_spec *spec, float *d_out, void *stream);
+int vit_engine_cls_attention_host_u8(vit_engine *e, const unsigned char *const *images, int n, const float *mean, const float *std,
+                                     const vit_attention_spec *spec, float *const *out);
+int vit_engine_cls_attention_device_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp,
+                                           const vit_attention_spec *spec, float *d_out, void *stream);
+int vit_engine_cls_attention_host_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp,
+                                         const vit_attention_spec *spec, float *const *out);
+
+/*
  * The fp32 GEMMs' helper-piece hand-over (csrc/vit_gemm_persistent.hip) since the last call, summed over the lanes: tiles whose
  * first K-steps came from a helper workgroup / tiles whose owner found no piece when it looked and computed all of it.  The
  * second number is lost time, never a wrong result (nothing in the hand-over waits or gives up).  Synchronises the device.

@@ -373,6 +373,26 @@ int vithip_layernorm_pool_f32(vithip_stream_t stream, const float *x, size_t ldx
  * depend on the number of rows.  dim % 4 == 0, ldx >= dim and a multiple of 4, x 16-byte aligned. */
 int vithip_l2_normalize_rows_f32(vithip_stream_t stream, float *x, size_t ldx, int rows, int dim);
 
+/*
+ * The class token's attention over the tokens of its image (csrc/vit_cls_attention.hip): the softmax row of query 0, stored instead
+ * of multiplied with V.  qkv as vithip_attention_f32 / _bf16io read it: rows = tokens, q_row_stride elements from one token row to
+ * the next (3 * heads * 64 for packed rows), columns [Q | K | V], head h = columns 64h..64h+63 of each.  For image i and head h, with
+ * q = Q[i*tokens][64h..] and k_t = K[i*tokens + t][64h..]:
+ *     s_t = (q . k_t) / sqrtf(64);  p_t = expf(s_t - max_t s) / sum_t expf(s_t - max),  t = 0..tokens-1   (ViT_seq.c:156-190, one row)
+ * in fp32 for both element types (bf16 elements are widened, never rounded again).  Only the Q of the class rows and K are read.
+ *   head_mean = 0: out[i][h][t], a row of heads * tokens floats per image at out + i * ld_out;
+ *   head_mean = 1: out[i][t] = (p[0][t] + p[1][t] + ... in head order) / (float)heads, of exactly the bits head_mean = 0 stores.
+ * q_scaled = 1 (bf16): the Q columns hold VITHIP_QSCALE * q; p_t = exp2f(q . k_t - max) / sum, no further scaling.
+ * Deterministic (no atomics) and position independent: an image's row has the same bits wherever the image sits in whatever batch.
+ * Any tokens >= 1 and heads >= 1; head_dim is 64.  Elements of `out` outside the rows are not touched.
+ * hipErrorInvalidValue: NULL pointers, non-positive sizes, flags other than 0 / 1, q_row_stride < 3 * heads * 64 or not a multiple
+ * of 4 (fp32) / 8 (bf16), ld_out smaller than a row, qkv not 16-byte or out not 4-byte aligned.
+ */
+int vithip_cls_attention_f32(vithip_stream_t stream, const float *qkv, size_t q_row_stride, float *out, size_t ld_out, int n_images,
+                             int tokens, int heads, int head_mean);
+int vithip_cls_attention_bf16(vithip_stream_t stream, const unsigned short *qkv, size_t q_row_stride, float *out, size_t ld_out,
+                              int n_images, int tokens, int heads, int head_mean, int q_scaled);
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,6 +63,13 @@ class CFeatureSpec(C.Structure):  # vit_feature_spec
 FEATURE_KINDS = {"cls": 0, "mean": 1, "tokens": 2}  # VIT_FEAT_*
 
 
+class CAttentionSpec(C.Structure):  # vit_attention_spec
+    _fields_ = [("kind", C.c_int), ("reserved", C.c_int)]
+
+
+ATTENTION_KINDS = {"heads": 0, "head_mean": 1}  # VIT_ATTN_*
+
+
 class CImageU8(C.Structure):  # vit_image_u8 / vithip_image_u8: one decoded image, [height][width][chans] uint8
     _fields_ = [("pixels", C.c_void_p), ("height", C.c_int), ("width", C.c_int)]
 
@@ -75,6 +82,12 @@ def feature_spec(kind, l2_normalize=False) -> CFeatureSpec:
     """kind: "cls" | "mean" | "tokens" (or a raw VIT_FEAT_* integer, passed through unchecked for the C side to judge)."""
     k = FEATURE_KINDS[kind] if isinstance(kind, str) else int(kind)
     return CFeatureSpec(k, int(l2_normalize))
+
+
+def attention_spec(kind, reserved: int = 0) -> CAttentionSpec:
+    """kind: "heads" | "head_mean" (or a raw VIT_ATTN_* integer, passed through unchecked for the C side to judge)."""
+    k = ATTENTION_KINDS[kind] if isinstance(kind, str) else int(kind)
+    return CAttentionSpec(k, int(reserved))
 
 
 class CStageTimes(C.Structure):
@@ -193,6 +206,18 @@ def lib() -> C.CDLL:
             L.vit_engine_forward_host_images.argtypes = [C.c_void_p, recs, C.c_int, pp, C.POINTER(f32p)]
             L.vit_engine_features_device_images.argtypes = [C.c_void_p, recs, C.c_int, pp, C.POINTER(CFeatureSpec), C.c_void_p, C.c_void_p]
             L.vit_engine_features_host_images.argtypes = [C.c_void_p, recs, C.c_int, pp, C.POINTER(CFeatureSpec), C.POINTER(f32p)]
+        if hasattr(L, "vit_engine_cls_attention_device"):  # an earlier build (see above) has no attention calls
+            recs, pp, asp = C.POINTER(CImageU8), C.POINTER(CPreproc), C.POINTER(CAttentionSpec)
+            L.vit_engine_attention_row_elems.restype = C.c_size_t
+            L.vit_engine_attention_row_elems.argtypes = [C.c_void_p, asp]
+            L.vit_engine_cls_attention_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, asp, C.c_void_p, C.c_void_p]
+            L.vit_engine_cls_attention_host.argtypes = [C.c_void_p, C.POINTER(f32p), C.c_int, asp, C.POINTER(f32p)]
+            L.vit_engine_cls_attention_device_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, f32p, f32p, asp, C.c_void_p, C.c_void_p]
+            L.vit_engine_cls_attention_host_u8.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, f32p, f32p, asp, C.POINTER(f32p)]
+            L.vit_engine_cls_attention_device_images.argtypes = [C.c_void_p, recs, C.c_int, pp, asp, C.c_void_p, C.c_void_p]
+            L.vit_engine_cls_attention_host_images.argtypes = [C.c_void_p, recs, C.c_int, pp, asp, C.POINTER(f32p)]
+            L.vithip_cls_attention_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_int] * 4
+            L.vithip_cls_attention_bf16.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_int] * 5
         L.vit_engine_read_logits.argtypes = [C.c_void_p, f32p, C.c_int]
         L.vit_engine_sync.argtypes = [C.c_void_p]
         L.vit_engine_get_stage_times.argtypes = [C.c_void_p, C.POINTER(CStageTimes)]
@@ -638,6 +663,39 @@ def attention_rows(qkv, n_images: int, tokens: int, heads: int, q_rows: int, fil
     return do.numpy()
 
 
+def _cls_attention(fn_name, dq, n_images, tokens, heads, head_mean, ld_out, fill, extra=()):
+    row = tokens if head_mean else heads * tokens
+    ld = row if ld_out is None else int(ld_out)
+    if fill is None:
+        do = DeviceArray((n_images, ld))
+    else:
+        do = DeviceArray.from_numpy(np.full((n_images, ld), fill, np.float32))
+    hip_check(getattr(lib(), fn_name)(None, dq.ptr, 3 * heads * 64, do.ptr, ld, n_images, tokens, heads, int(head_mean), *extra), fn_name)
+    out = do.numpy()
+    if ld_out is not None:
+        return out
+    return out if head_mean else out.reshape(n_images, heads, tokens)
+
+
+def cls_attention(qkv, n_images: int, tokens: int, heads: int, head_mean: bool = False, ld_out: Optional[int] = None,
+                  fill: Optional[float] = None) -> np.ndarray:
+    """vithip_cls_attention_f32: qkv [n_images * tokens][3 * heads * 64] fp32 -> the class rows' softmax [n][heads][tokens], or
+    [n][tokens] with head_mean.  ld_out (>= the row): the raw [n][ld_out] buffer comes back, pre-filled with `fill`, to show what
+    the kernel wrote."""
+    qkv = _as_f32(qkv)
+    assert qkv.shape == (n_images * tokens, 3 * heads * 64)
+    return _cls_attention("vithip_cls_attention_f32", DeviceArray.from_numpy(qkv), n_images, tokens, heads, head_mean, ld_out, fill)
+
+
+def cls_attention_bf16(qkv_bits, n_images: int, tokens: int, heads: int, head_mean: bool = False, q_scaled: bool = False,
+                       ld_out: Optional[int] = None, fill: Optional[float] = None) -> np.ndarray:
+    """vithip_cls_attention_bf16: the same from bf16 bits (uint16); q_scaled: the Q columns hold QSCALE * q.  fp32 out."""
+    qkv_bits = np.ascontiguousarray(qkv_bits, np.uint16)
+    assert qkv_bits.shape == (n_images * tokens, 3 * heads * 64)
+    return _cls_attention("vithip_cls_attention_bf16", DeviceArray.from_numpy(qkv_bits), n_images, tokens, heads, head_mean, ld_out, fill,
+                          (int(q_scaled),))
+
+
 def patch_embed(cfg: ModelConfig, images, conv_w, conv_b, cls, pos) -> np.ndarray:
     images = _as_f32(images)
     n = images.shape[0]
@@ -931,6 +989,75 @@ class Engine:
         spec = feature_spec(kind, l2_normalize)
         self._check(lib().vit_engine_features_device_images(self._h, recs, len(recs), C.byref(pp), C.byref(spec), d_out, stream or None),
                     "vit_engine_features_device_images")
+
+    # ---- the class token's attention over the tokens in the last layer (vit_engine_cls_attention_*): kind "heads" | "head_mean" ----
+    def attention_shape(self, n: int, kind="heads") -> tuple:
+        """Shape of the rows n images give: (n, heads, tokens) for "heads", (n, tokens) for "head_mean"."""
+        spec = attention_spec(kind)
+        elems = lib().vit_engine_attention_row_elems(self._h, C.byref(spec))
+        if elems == 0:
+            raise VitError(f"bad attention spec (kind={kind!r})")
+        heads = self.cfg.num_heads
+        return (n, heads, elems // heads) if spec.kind == ATTENTION_KINDS["heads"] else (n, elems)
+
+    def cls_attention(self, images: np.ndarray, kind="heads") -> np.ndarray:
+        """Host path: per-image pointers in, per-image rows out: softmax of the class query over all tokens, per head or head-averaged."""
+        images = _as_f32(images)
+        n = images.shape[0]
+        spec = attention_spec(kind)
+        out = np.empty(self.attention_shape(n, kind), np.float32)
+        in_ptrs = (f32p * n)(*[images[i].ctypes.data_as(f32p) for i in range(n)])
+        out_ptrs = (f32p * n)(*[out[i].ctypes.data_as(f32p) for i in range(n)])
+        self._check(lib().vit_engine_cls_attention_host(self._h, in_ptrs, n, C.byref(spec), out_ptrs), "vit_engine_cls_attention_host")
+        return out
+
+    def cls_attention_u8(self, images: np.ndarray, kind="heads", mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
+        """Host path from 8-bit pixels [n][S][S][C] (see forward_u8)."""
+        images = np.ascontiguousarray(images, np.uint8)
+        n = images.shape[0]
+        m, s = _norm_consts(mean, std, self.cfg.in_chans)
+        spec = attention_spec(kind)
+        out = np.empty(self.attention_shape(n, kind), np.float32)
+        in_ptrs = (C.c_void_p * n)(*[images[i].ctypes.data for i in range(n)])
+        out_ptrs = (f32p * n)(*[out[i].ctypes.data_as(f32p) for i in range(n)])
+        self._check(lib().vit_engine_cls_attention_host_u8(self._h, in_ptrs, n, m, s, C.byref(spec), out_ptrs),
+                    "vit_engine_cls_attention_host_u8")
+        return out
+
+    def cls_attention_images(self, images, resize_shorter: int, kind="heads", mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
+        """Host path: a list of [H][W][C] uint8 arrays of any sizes in, attention rows out (see cls_attention)."""
+        keep, recs = host_image_records(images, self.cfg.in_chans)
+        n = len(keep)
+        pp = preproc_params(resize_shorter, mean, std, self.cfg.in_chans)
+        spec = attention_spec(kind)
+        out = np.empty(self.attention_shape(n, kind), np.float32)
+        out_ptrs = (f32p * n)(*[out[i].ctypes.data_as(f32p) for i in range(n)])
+        self._check(lib().vit_engine_cls_attention_host_images(self._h, recs, n, C.byref(pp), C.byref(spec), out_ptrs),
+                    "vit_engine_cls_attention_host_images")
+        return out
+
+    def cls_attention_device(self, d_images: int, n: int, d_out: int, kind="heads", stream: int = 0) -> None:
+        """Device-resident path: raw HBM addresses, d_out [n][row] fp32, async on `stream`."""
+        spec = attention_spec(kind)
+        self._check(lib().vit_engine_cls_attention_device(self._h, d_images, n, C.byref(spec), d_out, stream or None),
+                    "vit_engine_cls_attention_device")
+
+    def cls_attention_device_u8(self, d_images: int, n: int, d_out: int, kind="heads", mean=IMAGENET_MEAN, std=IMAGENET_STD,
+                                stream: int = 0) -> None:
+        """Device-resident path from 8-bit pixels [n][S][S][C] in HBM (raw addresses), async on `stream`."""
+        m, s = _norm_consts(mean, std, self.cfg.in_chans)
+        spec = attention_spec(kind)
+        self._check(lib().vit_engine_cls_attention_device_u8(self._h, d_images, n, m, s, C.byref(spec), d_out, stream or None),
+                    "vit_engine_cls_attention_device_u8")
+
+    def cls_attention_device_images(self, images, d_out: int, resize_shorter: int, kind="heads", mean=IMAGENET_MEAN, std=IMAGENET_STD,
+                                    stream: int = 0) -> None:
+        """Device-resident path: images = a list of (ptr, H, W) in HBM, d_out [n][row] fp32; async on `stream`."""
+        recs = image_records(images)
+        pp = preproc_params(resize_shorter, mean, std, self.cfg.in_chans)
+        spec = attention_spec(kind)
+        self._check(lib().vit_engine_cls_attention_device_images(self._h, recs, len(recs), C.byref(pp), C.byref(spec), d_out, stream or None),
+                    "vit_engine_cls_attention_device_images")
 
     def pool_scratch_layout(self, nb: int) -> list:
         """vit_engine_debug_pool_scratch for every lane of a MEAN chunk of nb images: per lane a dict of byte ranges inside the y

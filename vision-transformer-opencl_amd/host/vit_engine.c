@@ -8,7 +8,8 @@
  *   depth x { LN1 -> QKV GEMM -> fused attention -> out_proj GEMM (+bias +residual, in place)
  *             LN2 -> fc1 GEMM (+bias +GELU) -> fc2 GEMM (+bias +residual, in place) }
  *   LN on the class-token rows only -> head GEMM -> softmax + top-1
- *   (a features call ends instead in the final LN of the rows it returns, or in the fused LN + mean over the patch tokens)
+ *   (a features call ends instead in the final LN of the rows it returns, or in the fused LN + mean over the patch tokens;
+ *    an attention call stops the last layer behind its QKV GEMM and stores the class token's softmax row)
  *
  * Weights are validated and uploaded once (the reference re-uploads them per op per image,
  * e.g. ViT_opencl.c:136,630-631); activations never leave HBM between stages (the reference
@@ -47,17 +48,20 @@ _Static_assert(sizeof(vit_image_u8) == sizeof(vithip_image_u8) && offsetof(vit_i
                    offsetof(vit_image_u8, width) == offsetof(vithip_image_u8, width),
                "the engine hands its callers' records to the kernel launcher as they are");
 
-/* What a forward writes, besides where: probabilities [n][classes] and the optional top-1 records, or the embedding rows `spec`
- * asks for (stage_features), [n][out_row_elems()].  Zero-filled before use: the graph cache compares it bytewise.  The pointers are
- * those of the call's (or chunk's) first image. */
+/* What a forward writes, besides where: probabilities [n][classes] and the optional top-1 records, the embedding rows `spec`
+ * asks for (stage_features), or the class token's attention over the tokens in the last layer (stage_cls_attention), [n][out_row_elems()].
+ * Zero-filled before use: the graph cache compares it bytewise.  The pointers are those of the call's (or chunk's) first image. */
+enum { VIT_OUT_PROBS = 0, VIT_OUT_FEATURES = 1, VIT_OUT_ATTENTION = 2 };
 typedef struct {
-    int features;          /* 0: dst = probabilities, label / prob = top-1 (may be NULL); 1: dst = the rows of spec */
+    int kind;              /* VIT_OUT_PROBS: dst = probabilities, label / prob = top-1 (may be NULL); _FEATURES: dst = the rows of spec;
+                            * _ATTENTION: dst = the rows of attn_kind */
     vit_feature_spec spec;
-    int reserved;          /* keeps the struct free of padding, which a bytewise comparison would read */
+    int attn_kind;         /* VIT_ATTN_* (0 otherwise); with it the struct has no padding, which a bytewise comparison would read */
     float *dst;
     int *label;
     float *prob;
 } vit_output;
+_Static_assert(sizeof(vit_output) == 4 * sizeof(int) + 3 * sizeof(void *), "vit_output must stay free of padding: the graph cache compares it bytewise");
 
 struct vit_engine {
     vit_config cfg;
@@ -703,6 +707,7 @@ typedef struct {
     int L;                       /* lanes in use for this chunk */
     int T, D, H, NC;
     int pruned;                  /* the last layer computes the class rows only: prune_last_layer, unless the chunk's output needs every token */
+    int qkv_only;                /* the last layer stops behind its QKV GEMM: the chunk's output is read from its Q and K (attention calls) */
 } chunk_ctx;
 
 #define RUN(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
@@ -783,6 +788,8 @@ static int row_stats(chunk_ctx *c, const vit_lane *ln, size_t ldx, float *pairs,
  *   pruned  prune_last_layer, for chunks whose output reads the class rows only (chunk_ctx.pruned: probabilities and CLS features;
  *           MEAN and TOKENS run the layer in full): K and V of every token, everything else for the class rows only.  The class rows of a [n*T][w]
  *           buffer are rows 0, T, 2T, ... = a matrix with leading dimension T*w, which every operator takes as it is.
+ *   qkv_only  attention calls: the last layer ends behind in_proj, with K of every token and Q of (at least) the class rows in the
+ *           lanes' qkv rows, where stage_cls_attention reads them; pruned or not, those are the same bits.
  */
 static int encoder_layer(chunk_ctx *c, int l) {
     vit_engine *e = c->e;
@@ -841,6 +848,7 @@ static int encoder_layer(chunk_ctx *c, int l) {
         }
         RUN(gemm(e, ln->s, &g, NULL));
     }
+    if (c->qkv_only && !feeds_next) return VIT_OK;
     for (int j = 0; j < c->L; ++j) { /* scores, softmax, P.V (ViT_seq.c:156-215) -> y; pruned: for the class rows */
         const vit_lane *ln = &c->lane[j];
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_ATTN));
@@ -912,7 +920,8 @@ static int stage_head(chunk_ctx *c, float *d_probs, int *d_label, float *d_prob)
 
 /* floats per image of what `out` writes */
 static size_t out_row_elems(const vit_engine *e, const vit_output *out) {
-    if (!out->features) return (size_t)e->cfg.num_classes;
+    if (out->kind == VIT_OUT_PROBS) return (size_t)e->cfg.num_classes;
+    if (out->kind == VIT_OUT_ATTENTION) return (out->attn_kind == VIT_ATTN_HEADS ? (size_t)e->cfg.num_heads : 1) * (size_t)e->tokens;
     return (out->spec.kind == VIT_FEAT_TOKENS ? (size_t)e->tokens : 1) * (size_t)e->cfg.embed_dim;
 }
 
@@ -955,6 +964,27 @@ static int stage_features(chunk_ctx *c, const vit_output *out) {
     return VIT_OK;
 }
 
+/* The class token's attention of the last layer instead of everything behind its in_proj: one launch per lane over the lane's qkv
+ * rows as encoder_layer (qkv_only) left them -- Q of the class rows at row step T, K of every token; bf16 fold engines keep
+ * VITHIP_QSCALE * q there.  Nothing has written those rows since: the fold's statistics live in other allocations (fp32) or in the
+ * upper half of qkv's (bf16; chunk_setup), and the next writer is the next chunk's first in_proj on the same streams. */
+static int stage_cls_attention(chunk_ctx *c, const vit_output *out) {
+    vit_engine *e = c->e;
+    const int heads = e->cfg.num_heads, mean = out->attn_kind == VIT_ATTN_HEAD_MEAN;
+    const size_t row = out_row_elems(e, out), ld = 3 * (size_t)c->D;
+    for (int j = 0; j < c->L; ++j) {
+        const vit_lane *ln = &c->lane[j];
+        float *dst = out->dst + (size_t)ln->off * row;
+        HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_ATTN));
+        if (e->opt.dtype == VIT_DTYPE_BF16)
+            HIP_TRY(e, vithip_cls_attention_bf16(ln->s, (const unsigned short *)ln->qkv, ld, dst, row, ln->n, c->T, heads, mean, e->fold));
+        else
+            HIP_TRY(e, vithip_cls_attention_f32(ln->s, (const float *)ln->qkv, ld, dst, row, ln->n, c->T, heads, mean));
+        HIP_TRY(e, stage_end(e, ln->s));
+    }
+    return VIT_OK;
+}
+
 /* The chunk's context for nb images written as `out` says: dimensions, whether the last layer is pruned, and the lanes -- their
  * images, streams and rows of the activation buffers.  Launches nothing. */
 static void chunk_setup(vit_engine *e, vithip_stream_t s, int nb, const vit_output *out, chunk_ctx *c) {
@@ -963,7 +993,8 @@ static void chunk_setup(vit_engine *e, vithip_stream_t s, int nb, const vit_outp
     c->T = e->tokens; c->D = cfg->embed_dim; c->H = cfg->hidden_dim; c->NC = cfg->num_classes;
     c->L = e->opt.lanes > VIT_MAX_LANES ? VIT_MAX_LANES : e->opt.lanes;
     if (c->L < 1 || nb < 2 * c->L) c->L = 1;
-    c->pruned = e->opt.prune_last_layer && c->T <= 224 && !(out->features && out->spec.kind != VIT_FEAT_CLS);
+    c->pruned = e->opt.prune_last_layer && c->T <= 224 && !(out->kind == VIT_OUT_FEATURES && out->spec.kind != VIT_FEAT_CLS);
+    c->qkv_only = out->kind == VIT_OUT_ATTENTION;
     const int bf16 = e->opt.dtype == VIT_DTYPE_BF16;
     const size_t B = (size_t)e->opt.max_batch, T = (size_t)c->T, D = (size_t)c->D, H = (size_t)c->H;
     const size_t esz = bf16 ? sizeof(unsigned short) : sizeof(float);
@@ -1012,13 +1043,14 @@ static int forward_chunk(vit_engine *e, vithip_stream_t s, const void *d_images,
     }
     RUN(stage_embed(c, d_images, in, f32_stage));
     for (int l = 0; l < cfg->depth; ++l) RUN(encoder_layer(c, l));
-    if (out->features) RUN(stage_features(c, out));
+    if (out->kind == VIT_OUT_FEATURES) RUN(stage_features(c, out));
+    else if (out->kind == VIT_OUT_ATTENTION) RUN(stage_cls_attention(c, out));
     else RUN(stage_head(c, out->dst, out->label, out->prob));
     for (int j = 1; j < c->L; ++j) { /* join */
         HIP_TRY(e, vithip_event_record(e->ev_join[j - 1], c->lane[j].s));
         HIP_TRY(e, vithip_stream_wait_event(s, e->ev_join[j - 1]));
     }
-    e->last_rows = out->features ? 0 : nb; /* rows of e->logits the chunk wrote (vit_engine_read_logits) */
+    e->last_rows = out->kind == VIT_OUT_PROBS ? nb : 0; /* rows of e->logits the chunk wrote (vit_engine_read_logits) */
     return VIT_OK;
 }
 #undef RUN
@@ -1067,7 +1099,8 @@ static int input_images(vit_engine *e, const char *who, const vit_image_u8 *imag
     return VIT_OK;
 }
 
-/* The two kinds of output descriptor: probabilities + top-1 (the forwards), or the checked feature spec of a features call. */
+/* The kinds of output descriptor: probabilities + top-1 (the forwards), the checked feature spec of a features call, or the checked
+ * attention spec of an attention call. */
 static vit_output output_probs(float *probs, int *label, float *prob) {
     vit_output out;
     memset(&out, 0, sizeof(out));
@@ -1084,10 +1117,26 @@ static int output_features(vit_engine *e, const char *who, const vit_feature_spe
     if (spec->l2_normalize && spec->kind == VIT_FEAT_TOKENS)
         return fail(e, VIT_ERR_ARG, "%s: l2_normalize applies to the CLS and MEAN rows, not to TOKENS", who);
     if (spec->kind == VIT_FEAT_MEAN && e->tokens < 2) return fail(e, VIT_ERR_ARG, "%s: MEAN needs at least one patch token", who);
-    out->features = 1;
+    out->kind = VIT_OUT_FEATURES;
     out->spec.kind = spec->kind; out->spec.l2_normalize = spec->l2_normalize;
     out->dst = dst;
     return VIT_OK;
+}
+
+static int output_attention(vit_engine *e, const char *who, const vit_attention_spec *spec, float *dst, vit_output *out) {
+    memset(out, 0, sizeof(*out));
+    if (!spec) return fail(e, VIT_ERR_ARG, "%s: the attention spec is required", who);
+    if (spec->kind != VIT_ATTN_HEADS && spec->kind != VIT_ATTN_HEAD_MEAN) return fail(e, VIT_ERR_ARG, "%s: unknown attention kind %d", who, spec->kind);
+    if (spec->reserved != 0) return fail(e, VIT_ERR_ARG, "%s: vit_attention_spec.reserved must be 0 (got %d)", who, spec->reserved);
+    out->kind = VIT_OUT_ATTENTION;
+    out->attn_kind = spec->kind;
+    out->dst = dst;
+    return VIT_OK;
+}
+
+size_t vit_engine_attention_row_elems(const vit_engine *e, const vit_attention_spec *spec) {
+    if (!e || !spec || (spec->kind != VIT_ATTN_HEADS && spec->kind != VIT_ATTN_HEAD_MEAN) || spec->reserved != 0) return 0;
+    return (spec->kind == VIT_ATTN_HEADS ? (size_t)e->cfg.num_heads : 1) * (size_t)e->tokens;
 }
 
 size_t vit_engine_feature_row_elems(const vit_engine *e, const vit_feature_spec *spec) {
@@ -1226,6 +1275,42 @@ int vit_engine_features_device_images(vit_engine *e, const vit_image_u8 *images,
     return forward_device_in(e, images, &in, n, &out, stream);
 }
 
+int vit_engine_cls_attention_device(vit_engine *e, const float *d_images, int n, const vit_attention_spec *spec, float *d_out, void *stream) {
+    if (!e) return VIT_ERR_ARG;
+    if (!d_images || !d_out || n <= 0) return fail(e, VIT_ERR_ARG, "cls_attention_device: bad arguments (n=%d)", n);
+    vit_input in;
+    vit_output out;
+    memset(&in, 0, sizeof(in));
+    const int rc = output_attention(e, "cls_attention_device", spec, d_out, &out);
+    if (rc) return rc;
+    return forward_device_in(e, d_images, &in, n, &out, stream);
+}
+
+int vit_engine_cls_attention_device_u8(vit_engine *e, const unsigned char *d_images, int n, const float *mean, const float *std,
+                                       const vit_attention_spec *spec, float *d_out, void *stream) {
+    if (!e) return VIT_ERR_ARG;
+    if (!d_images || !d_out || n <= 0) return fail(e, VIT_ERR_ARG, "cls_attention_device_u8: bad arguments (n=%d)", n);
+    if ((size_t)d_images & 3) return fail(e, VIT_ERR_ARG, "cls_attention_device_u8: d_images must be 4-byte aligned");
+    vit_input in;
+    vit_output out;
+    int rc = input_u8(e, "cls_attention_device_u8", mean, std, &in);
+    if (!rc) rc = output_attention(e, "cls_attention_device_u8", spec, d_out, &out);
+    if (rc) return rc;
+    return forward_device_in(e, d_images, &in, n, &out, stream);
+}
+
+int vit_engine_cls_attention_device_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp,
+                                           const vit_attention_spec *spec, float *d_out, void *stream) {
+    if (!e) return VIT_ERR_ARG;
+    if (!images || !d_out || n <= 0) return fail(e, VIT_ERR_ARG, "cls_attention_device_images: bad arguments (n=%d)", n);
+    vit_input in;
+    vit_output out;
+    int rc = input_images(e, "cls_attention_device_images", images, n, pp, &in);
+    if (!rc) rc = output_attention(e, "cls_attention_device_images", spec, d_out, &out);
+    if (rc) return rc;
+    return forward_device_in(e, images, &in, n, &out, stream);
+}
+
 int vit_engine_sync(vit_engine *e) {
     if (!e) return VIT_ERR_ARG;
     HIP_TRY(e, vithip_stream_sync(e->stream));
@@ -1340,8 +1425,8 @@ static int cut_pieces(vit_engine *e, const char *who, const host_images *images,
     return VIT_OK;
 }
 
-/* The output staging holds max_batch rows of out_row_cap floats: classes at first, grown to the widest feature row a host call has
- * asked for (TOKENS: tokens * embed_dim).  Growing waits for everything in flight, frees both slots and allocates them again; if
+/* The output staging holds max_batch rows of out_row_cap floats: classes at first, grown to the widest feature or attention row a
+ * host call has asked for (TOKENS: tokens * embed_dim; HEADS: heads * tokens).  Growing waits for everything in flight, frees both slots and allocates them again; if
  * that fails the call fails with VIT_ERR_NOMEM and the staging is back at its classes-sized start. */
 static int alloc_out_stage(vit_engine *e, size_t bytes) { /* both slots, freed first; a HIP error code, with both slots freed again */
     int rc = 0;
@@ -1559,6 +1644,44 @@ int vit_engine_features_host_images(vit_engine *e, const vit_image_u8 *images, i
     if (!rc) rc = output_features(e, "features_host_images", spec, NULL, &o);
     if (rc) return rc;
     return forward_host_in(e, "features_host_images", &im, &in, n, &o, out);
+}
+
+int vit_engine_cls_attention_host(vit_engine *e, const float *const *images, int n, const vit_attention_spec *spec, float *const *out) {
+    if (!e) return VIT_ERR_ARG;
+    if (!images || !out || n <= 0) return fail(e, VIT_ERR_ARG, "cls_attention_host: bad arguments (n=%d)", n);
+    const host_images im = {images, NULL, NULL};
+    vit_input in;
+    vit_output o;
+    memset(&in, 0, sizeof(in));
+    const int rc = output_attention(e, "cls_attention_host", spec, NULL, &o);
+    if (rc) return rc;
+    return forward_host_in(e, "cls_attention_host", &im, &in, n, &o, out);
+}
+
+int vit_engine_cls_attention_host_u8(vit_engine *e, const unsigned char *const *images, int n, const float *mean, const float *std,
+                                     const vit_attention_spec *spec, float *const *out) {
+    if (!e) return VIT_ERR_ARG;
+    if (!images || !out || n <= 0) return fail(e, VIT_ERR_ARG, "cls_attention_host_u8: bad arguments (n=%d)", n);
+    const host_images im = {NULL, images, NULL};
+    vit_input in;
+    vit_output o;
+    int rc = input_u8(e, "cls_attention_host_u8", mean, std, &in);
+    if (!rc) rc = output_attention(e, "cls_attention_host_u8", spec, NULL, &o);
+    if (rc) return rc;
+    return forward_host_in(e, "cls_attention_host_u8", &im, &in, n, &o, out);
+}
+
+int vit_engine_cls_attention_host_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp,
+                                         const vit_attention_spec *spec, float *const *out) {
+    if (!e) return VIT_ERR_ARG;
+    if (!images || !out || n <= 0) return fail(e, VIT_ERR_ARG, "cls_attention_host_images: bad arguments (n=%d)", n);
+    const host_images im = {NULL, NULL, images};
+    vit_input in;
+    vit_output o;
+    int rc = input_images(e, "cls_attention_host_images", images, n, pp, &in);
+    if (!rc) rc = output_attention(e, "cls_attention_host_images", spec, NULL, &o);
+    if (rc) return rc;
+    return forward_host_in(e, "cls_attention_host_images", &im, &in, n, &o, out);
 }
 
 int vit_engine_handover_stats(vit_engine *e, long *taken, long *recomputed) {
