@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import preproc_model as M
+from engine_helpers import CONFIGS, CONSTS, device_attention, engines, same_bits, weights  # noqa: F401 (fixtures)
 from test_cls_attention_abi import cls_attention_ref, head_mean_ref, oracle_cls_attention
 from test_gpu_preproc import DeviceImages, random_images
 from test_input_u8_model import normalise_u8
@@ -23,8 +24,6 @@ pytestmark = pytest.mark.gpu
 
 VIT_ERR_ARG = 1
 HIP_INVALID = 1  # hipErrorInvalidValue
-CONFIGS = {"tiny": synth.VIT_TINY, "small": synth.VIT_SMALL, "b16": synth.VIT_B16}
-CONSTS = (B.IMAGENET_MEAN, B.IMAGENET_STD)
 KINDS = ("heads", "head_mean")
 RESIZE = {"tiny": 36, "small": 72}
 
@@ -36,11 +35,6 @@ MEASURED = {("f32", "op"): 5.979e-8,      # T = 2, heads = 3: half an ulp of a p
             ("bf16", "op"): 8.091e-8,     # T = 2, heads = 2
             ("f32", "engine"): 7.787e-8,  # ViT-B/16, one image, HEADS (VIT_SMALL, lanes = 2, n = 11: 6.230e-8)
             ("bf16", "engine"): 3.074e-4}  # VIT_TINY, ln_fold = 0, n = 11, HEADS
-
-
-def same_bits(a, b) -> bool:
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
 def check_rows(p, T):
@@ -191,36 +185,6 @@ def test_kernel_refuses_bad_arguments():
 # ---- engines -----------------------------------------------------------------------------------------------------------
 
 @pytest.fixture(scope="module")
-def weights():
-    cache = {}
-
-    def get(name, seed):
-        if (name, seed) not in cache:
-            cache[(name, seed)] = synth.make_weights(CONFIGS[name], seed)
-        return cache[(name, seed)]
-
-    return get
-
-
-@pytest.fixture(scope="module")
-def engines(weights):
-    """Engines by (config name, weight seed, options), created on first use."""
-    cache = {}
-
-    def get(name, seed=1234, **opt):
-        key = (name, seed, tuple(sorted(opt.items())))
-        if key not in cache:
-            eng = B.Engine(CONFIGS[name], **opt)
-            eng.load_weights(weights(name, seed))
-            cache[key] = eng
-        return cache[key]
-
-    yield get
-    for eng in cache.values():
-        eng.close()
-
-
-@pytest.fixture(scope="module")
 def oracle_maps(oracle, weights):
     """(name, n) -> (images, [n][heads][T] float64): the restatement on the live oracle's last-layer q and k, weight seed 21;
     computed once and shared."""
@@ -233,20 +197,6 @@ def oracle_maps(oracle, weights):
         return cache[(name, n)]
 
     return get
-
-
-def device_attention(eng, d_images, n, kind, u8=False, stream=0, d_out=None):
-    d_out = d_out or B.DeviceArray(eng.attention_shape(n, kind))
-    if u8:
-        eng.cls_attention_device_u8(d_images.ptr, n, d_out.ptr, kind, *CONSTS, stream=stream)
-    else:
-        eng.cls_attention_device(d_images.ptr, n, d_out.ptr, kind, stream=stream)
-    eng.sync()
-    got = np.empty(eng.attention_shape(n, kind), np.float32)
-    B.hip_check(B.lib().vithip_device_sync(), "sync")
-    B.hip_check(B.lib().vithip_memcpy_d2h(got.ctypes.data, d_out.ptr, got.nbytes, None), "d2h")
-    B.hip_check(B.lib().vithip_device_sync(), "sync")
-    return got
 
 
 def against_oracle(eng, oracle_maps, name, ns, dtype, what):

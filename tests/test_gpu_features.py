@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import oracle_config
+from engine_helpers import CONFIGS, CONSTS, device_features, engines, same_bits, weights  # noqa: F401 (fixtures)
 from test_features_abi import l2_normalize_f64
 from test_input_u8_model import normalise_u8
 from vit_amd import binding as B
@@ -24,47 +25,10 @@ GOLD = os.path.join(os.path.dirname(__file__), "golden", "vit_b16_e2e.npz")
 LOGIT_REL = 1e-3
 VIT_ERR_ARG = 1
 KINDS = ("cls", "mean", "tokens")
-CONFIGS = {"tiny": synth.VIT_TINY, "small": synth.VIT_SMALL, "b16": synth.VIT_B16}
-CONSTS = (B.IMAGENET_MEAN, B.IMAGENET_STD)
-
-
-def same_bits(a, b) -> bool:
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
 def rel_err(got, ref) -> float:
     return float(np.abs(got - ref).max()) / float(np.abs(ref).max())
-
-
-@pytest.fixture(scope="module")
-def weights():
-    cache = {}
-
-    def get(name, seed):
-        if (name, seed) not in cache:
-            cache[(name, seed)] = synth.make_weights(CONFIGS[name], seed)
-        return cache[(name, seed)]
-
-    return get
-
-
-@pytest.fixture(scope="module")
-def engines(weights):
-    """Engines by (config name, weight seed, options), created on first use."""
-    cache = {}
-
-    def get(name, seed=1234, **opt):
-        key = (name, seed, tuple(sorted(opt.items())))
-        if key not in cache:
-            eng = B.Engine(CONFIGS[name], **opt)
-            eng.load_weights(weights(name, seed))
-            cache[key] = eng
-        return cache[key]
-
-    yield get
-    for eng in cache.values():
-        eng.close()
 
 
 def oracle_tokens(oracle, cfg, imgs, W):
@@ -76,20 +40,6 @@ def oracle_tokens(oracle, cfg, imgs, W):
 def reference(y, kind):
     """The contract's row for `kind` from the normalised tokens y [n][T][D], float64 mean."""
     return {"cls": y[:, 0], "mean": y[:, 1:].mean(1, dtype=np.float64), "tokens": y}[kind]
-
-
-def device_features(eng, d_images, n, kind, l2=False, u8=False, stream=0, d_out=None):
-    d_out = d_out or B.DeviceArray(eng.feature_shape(n, kind, l2))
-    if u8:
-        eng.features_device_u8(d_images.ptr, n, d_out.ptr, kind, l2, *CONSTS, stream=stream)
-    else:
-        eng.features_device(d_images.ptr, n, d_out.ptr, kind, l2, stream=stream)
-    eng.sync()
-    got = np.empty(eng.feature_shape(n, kind, l2), np.float32)
-    B.hip_check(B.lib().vithip_device_sync(), "sync")
-    B.hip_check(B.lib().vithip_memcpy_d2h(got.ctypes.data, d_out.ptr, got.nbytes, None), "d2h")
-    B.hip_check(B.lib().vithip_device_sync(), "sync")
-    return got
 
 
 # ---- 1, 2: fp32 engines against the oracle and the reference's golden class row ----------------------------------------

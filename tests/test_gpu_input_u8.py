@@ -9,6 +9,7 @@ import dataclasses
 import numpy as np
 import pytest
 
+from engine_helpers import cfloats, device_forward, engines, same_bits, weights  # noqa: F401 (fixtures)
 from test_input_u8_model import normalise_u8
 from vit_amd import binding as B
 from vit_amd import synth
@@ -20,11 +21,6 @@ CONSTS_A = (B.IMAGENET_MEAN, B.IMAGENET_STD)
 CONSTS_B = ((0.5, 0.25, 0.125), (0.3, -0.6, 0.9))
 
 
-def same_bits(a, b) -> bool:
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
 def u8_images(cfg, n, seed, chans=None):
     """Random bytes, plus a row of 0 and a row of 255 in every image."""
     c = cfg.in_chans if chans is None else chans
@@ -32,10 +28,6 @@ def u8_images(cfg, n, seed, chans=None):
     imgs[:, 0] = 0
     imgs[:, -1] = 255
     return imgs
-
-
-def cfloats(v):
-    return (C.c_float * len(v))(*v)
 
 
 # ---- the kernel ------------------------------------------------------------------------------------------------------
@@ -75,39 +67,6 @@ def test_kernel_takes_a_source_offset_by_whole_images_and_refuses_bad_arguments(
 
 
 # ---- engines ---------------------------------------------------------------------------------------------------------
-
-@pytest.fixture(scope="module")
-def engines():
-    """Engines by (config name, options), created on first use and sharing one weight set per config."""
-    cache, weights = {}, {}
-
-    def get(cfg_name, **opt):
-        key = (cfg_name, tuple(sorted(opt.items())))
-        if key not in cache:
-            cfg = {"b16": synth.VIT_B16, "tiny": synth.VIT_TINY}[cfg_name]
-            if cfg_name not in weights:
-                weights[cfg_name] = synth.make_weights(cfg, 1234)
-            eng = B.Engine(cfg, **opt)
-            eng.load_weights(weights[cfg_name])
-            cache[key] = eng
-        return cache[key]
-
-    yield get
-    for eng in cache.values():
-        eng.close()
-
-
-def device_forward(eng, d_images, n, u8_consts=None, stream=0):
-    """(probs, top-1 labels, top-1 probs) of one forward_device / forward_device_u8 call on device images d_images."""
-    NC = eng.cfg.num_classes
-    d_p, d_l, d_q = B.DeviceArray((n, NC)), B.DeviceArray((n,), np.int32), B.DeviceArray((n,))
-    if u8_consts is None:
-        eng.forward_device(d_images.ptr, n, d_p.ptr, d_l.ptr, d_q.ptr, stream)
-    else:
-        eng.forward_device_u8(d_images.ptr, n, d_p.ptr, u8_consts[0], u8_consts[1], d_l.ptr, d_q.ptr, stream)
-    eng.sync()
-    return d_p.numpy(), d_l.numpy(), d_q.numpy()
-
 
 def check_device_path(eng, n, seed, consts=CONSTS_A):
     imgs = u8_images(eng.cfg, n, seed)

@@ -10,25 +10,15 @@ import numpy as np
 import pytest
 
 import preproc_model as M
+from engine_helpers import CONSTS, cfloats, engines, same_bits, weights  # noqa: F401 (fixtures)
 from test_input_u8_model import normalise_u8
 from vit_amd import binding as B
-from vit_amd import synth
 
 pytestmark = pytest.mark.gpu
 
 VIT_ERR_ARG = 1
 HIP_INVALID = 1  # hipErrorInvalidValue
 MEAN4, STD4 = (0.485, 0.456, 0.406, 0.5), (0.229, 0.224, 0.225, -0.25)
-CONSTS = (B.IMAGENET_MEAN, B.IMAGENET_STD)
-
-
-def same_bits(a, b) -> bool:
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def cfloats(v):
-    return (C.c_float * len(v))(*v)
 
 
 def random_images(sizes, chans, seed):
@@ -152,27 +142,6 @@ def test_kernel_refuses_bad_arguments_and_writes_nothing():
 
 
 # ---- engines ---------------------------------------------------------------------------------------------------------
-
-@pytest.fixture(scope="module")
-def engines():
-    """Engines by (config name, options), created on first use and sharing one weight set per config."""
-    cache, weights = {}, {}
-
-    def get(cfg_name, **opt):
-        key = (cfg_name, tuple(sorted(opt.items())))
-        if key not in cache:
-            cfg = {"b16": synth.VIT_B16, "tiny": synth.VIT_TINY}[cfg_name]
-            if cfg_name not in weights:
-                weights[cfg_name] = synth.make_weights(cfg, 1234)
-            eng = B.Engine(cfg, **opt)
-            eng.load_weights(weights[cfg_name])
-            cache[key] = eng
-        return cache[key]
-
-    yield get
-    for eng in cache.values():
-        eng.close()
-
 
 def resize_for(cfg):
     return {32: 36, 224: 256}[cfg.img_size]

@@ -176,21 +176,22 @@ def lib() -> C.CDLL:
         L.vit_engine_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(CConfig), C.POINTER(COptions)]
         L.vit_engine_destroy.argtypes = [C.c_void_p]
         L.vit_engine_load_weights.argtypes = [C.c_void_p, C.POINTER(CNetwork), C.c_int]
-        L.vit_engine_forward_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                                C.c_void_p, C.c_void_p]
-        L.vit_engine_forward_host.argtypes = [C.c_void_p, C.POINTER(f32p), C.c_int, C.POINTER(f32p)]
-        L.vit_engine_forward_device_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, f32p, f32p, C.c_void_p, C.c_void_p,
-                                                   C.c_void_p, C.c_void_p]
-        L.vit_engine_forward_host_u8.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, f32p, f32p, C.POINTER(f32p)]
-        if hasattr(L, "vit_engine_features_device"):  # VIT_HIP_LIBRARY may name an earlier build (A/B timing): it has no feature calls
+        # the forward surface, output kind x place x input kind: (engine, images, n) + normalisation + spec + destination
+        norm = {"": [], "_u8": [f32p, f32p], "_images": [C.POINTER(CPreproc)]}
+        spec = {"forward": [], "features": [C.POINTER(CFeatureSpec)], "cls_attention": [C.POINTER(CAttentionSpec)]}
+        for out in spec:
+            for place in ("host", "device"):
+                for kind in norm:
+                    images = C.POINTER(CImageU8) if kind == "_images" else C.c_void_p if place == "device" else \
+                        C.POINTER(C.c_void_p if kind == "_u8" else f32p)
+                    # host: a row per image; device: the rows, a forward's top-1 labels and probabilities, the stream
+                    dst = [C.POINTER(f32p)] if place == "host" else [C.c_void_p] * (4 if out == "forward" else 2)
+                    name = f"vit_engine_{out}_{place}{kind}"
+                    if hasattr(L, name):  # VIT_HIP_LIBRARY may name an earlier build (A/B timing), which lacks the later calls
+                        getattr(L, name).argtypes = [C.c_void_p, images, C.c_int] + norm[kind] + spec[out] + dst
+        if hasattr(L, "vit_engine_features_device"):  # an earlier build (see above) has no feature calls
             L.vit_engine_feature_row_elems.restype = C.c_size_t
             L.vit_engine_feature_row_elems.argtypes = [C.c_void_p, C.POINTER(CFeatureSpec)]
-            L.vit_engine_features_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(CFeatureSpec), C.c_void_p, C.c_void_p]
-            L.vit_engine_features_host.argtypes = [C.c_void_p, C.POINTER(f32p), C.c_int, C.POINTER(CFeatureSpec), C.POINTER(f32p)]
-            L.vit_engine_features_device_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, f32p, f32p, C.POINTER(CFeatureSpec), C.c_void_p,
-                                                        C.c_void_p]
-            L.vit_engine_features_host_u8.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, f32p, f32p, C.POINTER(CFeatureSpec),
-                                                      C.POINTER(f32p)]
             L.vithip_layernorm_pool_f32_workspace_floats.restype = C.c_size_t
             L.vithip_layernorm_pool_f32_workspace_floats.argtypes = [C.c_int] * 4
             L.vithip_layernorm_pool_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
@@ -199,23 +200,12 @@ def lib() -> C.CDLL:
             L.vit_engine_debug_pool_scratch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
         L.vithip_images_u8_to_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, f32p, f32p]
         if hasattr(L, "vit_engine_forward_device_images"):  # an earlier build (see above) has no decoded-image calls
-            recs, pp = C.POINTER(CImageU8), C.POINTER(CPreproc)
+            recs = C.POINTER(CImageU8)
             L.vithip_images_u8_resize_crop_to_f32.argtypes = [C.c_void_p, recs, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, f32p, f32p]
             L.vithip_images_u8_resize_crop_check.argtypes = [recs, C.c_int, C.c_int, C.c_int, C.c_int]
-            L.vit_engine_forward_device_images.argtypes = [C.c_void_p, recs, C.c_int, pp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-            L.vit_engine_forward_host_images.argtypes = [C.c_void_p, recs, C.c_int, pp, C.POINTER(f32p)]
-            L.vit_engine_features_device_images.argtypes = [C.c_void_p, recs, C.c_int, pp, C.POINTER(CFeatureSpec), C.c_void_p, C.c_void_p]
-            L.vit_engine_features_host_images.argtypes = [C.c_void_p, recs, C.c_int, pp, C.POINTER(CFeatureSpec), C.POINTER(f32p)]
         if hasattr(L, "vit_engine_cls_attention_device"):  # an earlier build (see above) has no attention calls
-            recs, pp, asp = C.POINTER(CImageU8), C.POINTER(CPreproc), C.POINTER(CAttentionSpec)
             L.vit_engine_attention_row_elems.restype = C.c_size_t
-            L.vit_engine_attention_row_elems.argtypes = [C.c_void_p, asp]
-            L.vit_engine_cls_attention_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, asp, C.c_void_p, C.c_void_p]
-            L.vit_engine_cls_attention_host.argtypes = [C.c_void_p, C.POINTER(f32p), C.c_int, asp, C.POINTER(f32p)]
-            L.vit_engine_cls_attention_device_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, f32p, f32p, asp, C.c_void_p, C.c_void_p]
-            L.vit_engine_cls_attention_host_u8.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, f32p, f32p, asp, C.POINTER(f32p)]
-            L.vit_engine_cls_attention_device_images.argtypes = [C.c_void_p, recs, C.c_int, pp, asp, C.c_void_p, C.c_void_p]
-            L.vit_engine_cls_attention_host_images.argtypes = [C.c_void_p, recs, C.c_int, pp, asp, C.POINTER(f32p)]
+            L.vit_engine_attention_row_elems.argtypes = [C.c_void_p, C.POINTER(CAttentionSpec)]
             L.vithip_cls_attention_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_int] * 4
             L.vithip_cls_attention_bf16.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_int] * 5
         L.vit_engine_read_logits.argtypes = [C.c_void_p, f32p, C.c_int]
@@ -866,42 +856,69 @@ class Engine:
         L.vit_engine_copy_weights.argtypes = [C.c_void_p, C.c_void_p]
         self._check(L.vit_engine_copy_weights(self._h, other._h), "vit_engine_copy_weights")
 
+    # ---- the forward surface: vit_engine_<out>_<place><inp>, out "forward" | "features" | "cls_attention", inp "" | "_u8" | "_images" ----
+    def _call_args(self, out, inp, kind, l2_normalize, mean, std, resize_shorter) -> list:
+        """What lies between n and the destination in the C call: the normalisation of the input kind, the spec of the output kind."""
+        args = []
+        if inp == "_u8":
+            args += _norm_consts(mean, std, self.cfg.in_chans)
+        elif inp == "_images":
+            args.append(C.byref(preproc_params(resize_shorter, mean, std, self.cfg.in_chans)))
+        if out != "forward":
+            args.append(C.byref(feature_spec(kind, l2_normalize) if out == "features" else attention_spec(kind)))
+        return args
+
+    def _host(self, out, inp, images, kind=None, l2_normalize=False, mean=None, std=None, resize_shorter=None) -> np.ndarray:
+        """A host-path call: per-image pointers (or records) in, per-image rows of a new array out."""
+        if inp == "_images":
+            keep, in_ptrs = host_image_records(images, self.cfg.in_chans)
+        elif inp == "_u8":
+            keep = np.ascontiguousarray(images, np.uint8)
+            in_ptrs = (C.c_void_p * len(keep))(*[im.ctypes.data for im in keep])
+        else:
+            keep = _as_f32(images)
+            in_ptrs = (f32p * len(keep))(*[im.ctypes.data_as(f32p) for im in keep])
+        n = len(keep)
+        args = self._call_args(out, inp, kind, l2_normalize, mean, std, resize_shorter)
+        if out == "forward":
+            shape = (n, self.cfg.num_classes)
+        else:
+            shape = self.feature_shape(n, kind, l2_normalize) if out == "features" else self.attention_shape(n, kind)
+        rows = np.empty(shape, np.float32)
+        out_ptrs = (f32p * n)(*[rows[i].ctypes.data_as(f32p) for i in range(n)])
+        name = f"vit_engine_{out}_host{inp}"
+        self._check(getattr(lib(), name)(self._h, in_ptrs, n, *args, out_ptrs), name)
+        return rows
+
+    def _device(self, out, inp, images, n, dst, kind=None, l2_normalize=False, mean=None, std=None, resize_shorter=None, d_label=0,
+                d_prob=0, stream=0) -> None:
+        """A device-path call: raw HBM addresses (images: a list of (ptr, H, W) for "_images"), async on `stream`."""
+        if inp == "_images":
+            images = image_records(images)
+            n = len(images)
+        args = self._call_args(out, inp, kind, l2_normalize, mean, std, resize_shorter)
+        top1 = [d_label or None, d_prob or None] if out == "forward" else []
+        name = f"vit_engine_{out}_device{inp}"
+        self._check(getattr(lib(), name)(self._h, images, n, *args, dst, *top1, stream or None), name)
+
     def forward(self, images: np.ndarray) -> np.ndarray:
         """Host path (the ViT_opencl-shaped one): per-image pointers in, per-image rows out."""
-        images = _as_f32(images)
-        n = images.shape[0]
-        rows = [images[i] for i in range(n)]
-        probs = np.empty((n, self.cfg.num_classes), np.float32)
-        in_ptrs = (f32p * n)(*[r.ctypes.data_as(f32p) for r in rows])
-        out_ptrs = (f32p * n)(*[probs[i].ctypes.data_as(f32p) for i in range(n)])
-        self._check(lib().vit_engine_forward_host(self._h, in_ptrs, n, out_ptrs), "vit_engine_forward_host")
-        return probs
+        return self._host("forward", "", images)
 
     def forward_device(self, d_images: int, n: int, d_probs: int, d_label: int = 0, d_prob: int = 0,
                        stream: int = 0) -> None:
         """Device-resident path: raw HBM addresses (e.g. torch data_ptr()), async on `stream`."""
-        self._check(lib().vit_engine_forward_device(self._h, d_images, n, d_probs, d_label or None,
-                                                    d_prob or None, stream or None),
-                    "vit_engine_forward_device")
+        self._device("forward", "", d_images, n, d_probs, d_label=d_label, d_prob=d_prob, stream=stream)
 
     def forward_u8(self, images: np.ndarray, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
         """Host path from 8-bit pixels: images [n][S][S][C] uint8 (as decoders write them), normalised on the device by
         ((float)u / 255 - mean[c]) / std[c]; per-image pointers in, per-image rows out."""
-        images = np.ascontiguousarray(images, np.uint8)
-        n = images.shape[0]
-        m, s = _norm_consts(mean, std, self.cfg.in_chans)
-        probs = np.empty((n, self.cfg.num_classes), np.float32)
-        in_ptrs = (C.c_void_p * n)(*[images[i].ctypes.data for i in range(n)])
-        out_ptrs = (f32p * n)(*[probs[i].ctypes.data_as(f32p) for i in range(n)])
-        self._check(lib().vit_engine_forward_host_u8(self._h, in_ptrs, n, m, s, out_ptrs), "vit_engine_forward_host_u8")
-        return probs
+        return self._host("forward", "_u8", images, mean=mean, std=std)
 
     def forward_device_u8(self, d_images: int, n: int, d_probs: int, mean=IMAGENET_MEAN, std=IMAGENET_STD, d_label: int = 0,
                           d_prob: int = 0, stream: int = 0) -> None:
         """Device-resident path from 8-bit pixels [n][S][S][C] in HBM (raw addresses), async on `stream`."""
-        m, s = _norm_consts(mean, std, self.cfg.in_chans)
-        self._check(lib().vit_engine_forward_device_u8(self._h, d_images, n, m, s, d_probs, d_label or None, d_prob or None,
-                                                       stream or None), "vit_engine_forward_device_u8")
+        self._device("forward", "_u8", d_images, n, d_probs, mean=mean, std=std, d_label=d_label, d_prob=d_prob, stream=stream)
 
     # ---- embedding outputs (vit_engine_features_*): kind "cls" | "mean" | "tokens", fp32 rows for both dtypes ----
     def feature_shape(self, n: int, kind="cls", l2_normalize=False) -> tuple:
@@ -915,80 +932,40 @@ class Engine:
 
     def features(self, images: np.ndarray, kind="cls", l2_normalize=False) -> np.ndarray:
         """Host path: per-image pointers in, per-image rows out (class token, patch-token mean, or all tokens)."""
-        images = _as_f32(images)
-        n = images.shape[0]
-        spec = feature_spec(kind, l2_normalize)
-        out = np.empty(self.feature_shape(n, kind, l2_normalize), np.float32)
-        in_ptrs = (f32p * n)(*[images[i].ctypes.data_as(f32p) for i in range(n)])
-        out_ptrs = (f32p * n)(*[out[i].ctypes.data_as(f32p) for i in range(n)])
-        self._check(lib().vit_engine_features_host(self._h, in_ptrs, n, C.byref(spec), out_ptrs), "vit_engine_features_host")
-        return out
+        return self._host("features", "", images, kind, l2_normalize)
 
     def features_u8(self, images: np.ndarray, kind="cls", l2_normalize=False, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
         """Host path from 8-bit pixels [n][S][S][C] (see forward_u8)."""
-        images = np.ascontiguousarray(images, np.uint8)
-        n = images.shape[0]
-        m, s = _norm_consts(mean, std, self.cfg.in_chans)
-        spec = feature_spec(kind, l2_normalize)
-        out = np.empty(self.feature_shape(n, kind, l2_normalize), np.float32)
-        in_ptrs = (C.c_void_p * n)(*[images[i].ctypes.data for i in range(n)])
-        out_ptrs = (f32p * n)(*[out[i].ctypes.data_as(f32p) for i in range(n)])
-        self._check(lib().vit_engine_features_host_u8(self._h, in_ptrs, n, m, s, C.byref(spec), out_ptrs), "vit_engine_features_host_u8")
-        return out
+        return self._host("features", "_u8", images, kind, l2_normalize, mean, std)
 
     def features_device(self, d_images: int, n: int, d_out: int, kind="cls", l2_normalize=False, stream: int = 0) -> None:
         """Device-resident path: raw HBM addresses, d_out [n][row] fp32, async on `stream`."""
-        spec = feature_spec(kind, l2_normalize)
-        self._check(lib().vit_engine_features_device(self._h, d_images, n, C.byref(spec), d_out, stream or None),
-                    "vit_engine_features_device")
+        self._device("features", "", d_images, n, d_out, kind, l2_normalize, stream=stream)
 
     def features_device_u8(self, d_images: int, n: int, d_out: int, kind="cls", l2_normalize=False, mean=IMAGENET_MEAN,
                            std=IMAGENET_STD, stream: int = 0) -> None:
         """Device-resident path from 8-bit pixels [n][S][S][C] in HBM (raw addresses), async on `stream`."""
-        m, s = _norm_consts(mean, std, self.cfg.in_chans)
-        spec = feature_spec(kind, l2_normalize)
-        self._check(lib().vit_engine_features_device_u8(self._h, d_images, n, m, s, C.byref(spec), d_out, stream or None),
-                    "vit_engine_features_device_u8")
+        self._device("features", "_u8", d_images, n, d_out, kind, l2_normalize, mean, std, stream=stream)
 
     # ---- decoded images of any size (vit_engine_*_images): Resize(resize_shorter) -> CenterCrop(img_size) -> Normalize on the device ----
     def forward_images(self, images, resize_shorter: int, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
         """Host path: a list of [H][W][C] uint8 arrays of any sizes in, probabilities [n][classes] out."""
-        keep, recs = host_image_records(images, self.cfg.in_chans)
-        n = len(keep)
-        pp = preproc_params(resize_shorter, mean, std, self.cfg.in_chans)
-        probs = np.empty((n, self.cfg.num_classes), np.float32)
-        out_ptrs = (f32p * n)(*[probs[i].ctypes.data_as(f32p) for i in range(n)])
-        self._check(lib().vit_engine_forward_host_images(self._h, recs, n, C.byref(pp), out_ptrs), "vit_engine_forward_host_images")
-        return probs
+        return self._host("forward", "_images", images, mean=mean, std=std, resize_shorter=resize_shorter)
 
     def forward_device_images(self, images, d_probs: int, resize_shorter: int, mean=IMAGENET_MEAN, std=IMAGENET_STD, d_label: int = 0,
                               d_prob: int = 0, stream: int = 0) -> None:
         """Device-resident path: images = a list of (ptr, H, W), pixels [H][W][C] uint8 in HBM (raw addresses); async on `stream`."""
-        recs = image_records(images)
-        pp = preproc_params(resize_shorter, mean, std, self.cfg.in_chans)
-        self._check(lib().vit_engine_forward_device_images(self._h, recs, len(recs), C.byref(pp), d_probs, d_label or None, d_prob or None,
-                                                           stream or None), "vit_engine_forward_device_images")
+        self._device("forward", "_images", images, None, d_probs, mean=mean, std=std, resize_shorter=resize_shorter, d_label=d_label,
+                     d_prob=d_prob, stream=stream)
 
     def features_images(self, images, resize_shorter: int, kind="cls", l2_normalize=False, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
         """Host path: a list of [H][W][C] uint8 arrays of any sizes in, embedding rows out (see features)."""
-        keep, recs = host_image_records(images, self.cfg.in_chans)
-        n = len(keep)
-        pp = preproc_params(resize_shorter, mean, std, self.cfg.in_chans)
-        spec = feature_spec(kind, l2_normalize)
-        out = np.empty(self.feature_shape(n, kind, l2_normalize), np.float32)
-        out_ptrs = (f32p * n)(*[out[i].ctypes.data_as(f32p) for i in range(n)])
-        self._check(lib().vit_engine_features_host_images(self._h, recs, n, C.byref(pp), C.byref(spec), out_ptrs),
-                    "vit_engine_features_host_images")
-        return out
+        return self._host("features", "_images", images, kind, l2_normalize, mean, std, resize_shorter)
 
     def features_device_images(self, images, d_out: int, resize_shorter: int, kind="cls", l2_normalize=False, mean=IMAGENET_MEAN,
                                std=IMAGENET_STD, stream: int = 0) -> None:
         """Device-resident path: images = a list of (ptr, H, W) in HBM, d_out [n][row] fp32; async on `stream`."""
-        recs = image_records(images)
-        pp = preproc_params(resize_shorter, mean, std, self.cfg.in_chans)
-        spec = feature_spec(kind, l2_normalize)
-        self._check(lib().vit_engine_features_device_images(self._h, recs, len(recs), C.byref(pp), C.byref(spec), d_out, stream or None),
-                    "vit_engine_features_device_images")
+        self._device("features", "_images", images, None, d_out, kind, l2_normalize, mean, std, resize_shorter, stream=stream)
 
     # ---- the class token's attention over the tokens in the last layer (vit_engine_cls_attention_*): kind "heads" | "head_mean" ----
     def attention_shape(self, n: int, kind="heads") -> tuple:
@@ -1002,62 +979,29 @@ class Engine:
 
     def cls_attention(self, images: np.ndarray, kind="heads") -> np.ndarray:
         """Host path: per-image pointers in, per-image rows out: softmax of the class query over all tokens, per head or head-averaged."""
-        images = _as_f32(images)
-        n = images.shape[0]
-        spec = attention_spec(kind)
-        out = np.empty(self.attention_shape(n, kind), np.float32)
-        in_ptrs = (f32p * n)(*[images[i].ctypes.data_as(f32p) for i in range(n)])
-        out_ptrs = (f32p * n)(*[out[i].ctypes.data_as(f32p) for i in range(n)])
-        self._check(lib().vit_engine_cls_attention_host(self._h, in_ptrs, n, C.byref(spec), out_ptrs), "vit_engine_cls_attention_host")
-        return out
+        return self._host("cls_attention", "", images, kind)
 
     def cls_attention_u8(self, images: np.ndarray, kind="heads", mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
         """Host path from 8-bit pixels [n][S][S][C] (see forward_u8)."""
-        images = np.ascontiguousarray(images, np.uint8)
-        n = images.shape[0]
-        m, s = _norm_consts(mean, std, self.cfg.in_chans)
-        spec = attention_spec(kind)
-        out = np.empty(self.attention_shape(n, kind), np.float32)
-        in_ptrs = (C.c_void_p * n)(*[images[i].ctypes.data for i in range(n)])
-        out_ptrs = (f32p * n)(*[out[i].ctypes.data_as(f32p) for i in range(n)])
-        self._check(lib().vit_engine_cls_attention_host_u8(self._h, in_ptrs, n, m, s, C.byref(spec), out_ptrs),
-                    "vit_engine_cls_attention_host_u8")
-        return out
+        return self._host("cls_attention", "_u8", images, kind, mean=mean, std=std)
 
     def cls_attention_images(self, images, resize_shorter: int, kind="heads", mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
         """Host path: a list of [H][W][C] uint8 arrays of any sizes in, attention rows out (see cls_attention)."""
-        keep, recs = host_image_records(images, self.cfg.in_chans)
-        n = len(keep)
-        pp = preproc_params(resize_shorter, mean, std, self.cfg.in_chans)
-        spec = attention_spec(kind)
-        out = np.empty(self.attention_shape(n, kind), np.float32)
-        out_ptrs = (f32p * n)(*[out[i].ctypes.data_as(f32p) for i in range(n)])
-        self._check(lib().vit_engine_cls_attention_host_images(self._h, recs, n, C.byref(pp), C.byref(spec), out_ptrs),
-                    "vit_engine_cls_attention_host_images")
-        return out
+        return self._host("cls_attention", "_images", images, kind, mean=mean, std=std, resize_shorter=resize_shorter)
 
     def cls_attention_device(self, d_images: int, n: int, d_out: int, kind="heads", stream: int = 0) -> None:
         """Device-resident path: raw HBM addresses, d_out [n][row] fp32, async on `stream`."""
-        spec = attention_spec(kind)
-        self._check(lib().vit_engine_cls_attention_device(self._h, d_images, n, C.byref(spec), d_out, stream or None),
-                    "vit_engine_cls_attention_device")
+        self._device("cls_attention", "", d_images, n, d_out, kind, stream=stream)
 
     def cls_attention_device_u8(self, d_images: int, n: int, d_out: int, kind="heads", mean=IMAGENET_MEAN, std=IMAGENET_STD,
                                 stream: int = 0) -> None:
         """Device-resident path from 8-bit pixels [n][S][S][C] in HBM (raw addresses), async on `stream`."""
-        m, s = _norm_consts(mean, std, self.cfg.in_chans)
-        spec = attention_spec(kind)
-        self._check(lib().vit_engine_cls_attention_device_u8(self._h, d_images, n, m, s, C.byref(spec), d_out, stream or None),
-                    "vit_engine_cls_attention_device_u8")
+        self._device("cls_attention", "_u8", d_images, n, d_out, kind, mean=mean, std=std, stream=stream)
 
     def cls_attention_device_images(self, images, d_out: int, resize_shorter: int, kind="heads", mean=IMAGENET_MEAN, std=IMAGENET_STD,
                                     stream: int = 0) -> None:
         """Device-resident path: images = a list of (ptr, H, W) in HBM, d_out [n][row] fp32; async on `stream`."""
-        recs = image_records(images)
-        pp = preproc_params(resize_shorter, mean, std, self.cfg.in_chans)
-        spec = attention_spec(kind)
-        self._check(lib().vit_engine_cls_attention_device_images(self._h, recs, len(recs), C.byref(pp), C.byref(spec), d_out, stream or None),
-                    "vit_engine_cls_attention_device_images")
+        self._device("cls_attention", "_images", images, None, d_out, kind, mean=mean, std=std, resize_shorter=resize_shorter, stream=stream)
 
     def pool_scratch_layout(self, nb: int) -> list:
         """vit_engine_debug_pool_scratch for every lane of a MEAN chunk of nb images: per lane a dict of byte ranges inside the y

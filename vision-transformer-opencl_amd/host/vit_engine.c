@@ -918,11 +918,14 @@ static int stage_head(chunk_ctx *c, float *d_probs, int *d_label, float *d_prob)
     return VIT_OK;
 }
 
-/* floats per image of what `out` writes */
+/* The row width's one home: floats per image of an output kind; `kind` is the VIT_FEAT_* or VIT_ATTN_* of a valid spec */
+static size_t row_elems(const vit_engine *e, int out_kind, int kind) {
+    if (out_kind == VIT_OUT_PROBS) return (size_t)e->cfg.num_classes;
+    if (out_kind == VIT_OUT_ATTENTION) return (kind == VIT_ATTN_HEADS ? (size_t)e->cfg.num_heads : 1) * (size_t)e->tokens;
+    return (kind == VIT_FEAT_TOKENS ? (size_t)e->tokens : 1) * (size_t)e->cfg.embed_dim;
+}
 static size_t out_row_elems(const vit_engine *e, const vit_output *out) {
-    if (out->kind == VIT_OUT_PROBS) return (size_t)e->cfg.num_classes;
-    if (out->kind == VIT_OUT_ATTENTION) return (out->attn_kind == VIT_ATTN_HEADS ? (size_t)e->cfg.num_heads : 1) * (size_t)e->tokens;
-    return (out->spec.kind == VIT_FEAT_TOKENS ? (size_t)e->tokens : 1) * (size_t)e->cfg.embed_dim;
+    return row_elems(e, out->kind, out->kind == VIT_OUT_ATTENTION ? out->attn_kind : out->spec.kind);
 }
 
 /* The embedding rows of the chunk instead of the head: the final LayerNorm of the class rows (exactly the launch stage_head makes,
@@ -1107,15 +1110,30 @@ static vit_output output_probs(float *probs, int *label, float *prob) {
     out.dst = probs; out.label = label; out.prob = prob;
     return out;
 }
+/* Spec validation's one home per spec: NULL for a valid spec, else what is wrong with it, as a format for (who, *arg). */
+static const char *feature_spec_fault(const vit_feature_spec *spec, int *arg) {
+    if (!spec) return "%s: the feature spec is required";
+    *arg = spec->kind;
+    if (spec->kind != VIT_FEAT_CLS && spec->kind != VIT_FEAT_MEAN && spec->kind != VIT_FEAT_TOKENS) return "%s: unknown feature kind %d";
+    *arg = spec->l2_normalize;
+    if (spec->l2_normalize != 0 && spec->l2_normalize != 1) return "%s: l2_normalize must be 0 or 1 (got %d)";
+    if (spec->l2_normalize && spec->kind == VIT_FEAT_TOKENS) return "%s: l2_normalize applies to the CLS and MEAN rows, not to TOKENS";
+    return NULL;
+}
+static const char *attention_spec_fault(const vit_attention_spec *spec, int *arg) {
+    if (!spec) return "%s: the attention spec is required";
+    *arg = spec->kind;
+    if (spec->kind != VIT_ATTN_HEADS && spec->kind != VIT_ATTN_HEAD_MEAN) return "%s: unknown attention kind %d";
+    *arg = spec->reserved;
+    if (spec->reserved != 0) return "%s: vit_attention_spec.reserved must be 0 (got %d)";
+    return NULL;
+}
+
 static int output_features(vit_engine *e, const char *who, const vit_feature_spec *spec, float *dst, vit_output *out) {
+    int arg = 0;
+    const char *fault = feature_spec_fault(spec, &arg);
     memset(out, 0, sizeof(*out));
-    if (!spec) return fail(e, VIT_ERR_ARG, "%s: the feature spec is required", who);
-    if (spec->kind != VIT_FEAT_CLS && spec->kind != VIT_FEAT_MEAN && spec->kind != VIT_FEAT_TOKENS)
-        return fail(e, VIT_ERR_ARG, "%s: unknown feature kind %d", who, spec->kind);
-    if (spec->l2_normalize != 0 && spec->l2_normalize != 1)
-        return fail(e, VIT_ERR_ARG, "%s: l2_normalize must be 0 or 1 (got %d)", who, spec->l2_normalize);
-    if (spec->l2_normalize && spec->kind == VIT_FEAT_TOKENS)
-        return fail(e, VIT_ERR_ARG, "%s: l2_normalize applies to the CLS and MEAN rows, not to TOKENS", who);
+    if (fault) return fail(e, VIT_ERR_ARG, fault, who, arg);
     if (spec->kind == VIT_FEAT_MEAN && e->tokens < 2) return fail(e, VIT_ERR_ARG, "%s: MEAN needs at least one patch token", who);
     out->kind = VIT_OUT_FEATURES;
     out->spec.kind = spec->kind; out->spec.l2_normalize = spec->l2_normalize;
@@ -1124,10 +1142,10 @@ static int output_features(vit_engine *e, const char *who, const vit_feature_spe
 }
 
 static int output_attention(vit_engine *e, const char *who, const vit_attention_spec *spec, float *dst, vit_output *out) {
+    int arg = 0;
+    const char *fault = attention_spec_fault(spec, &arg);
     memset(out, 0, sizeof(*out));
-    if (!spec) return fail(e, VIT_ERR_ARG, "%s: the attention spec is required", who);
-    if (spec->kind != VIT_ATTN_HEADS && spec->kind != VIT_ATTN_HEAD_MEAN) return fail(e, VIT_ERR_ARG, "%s: unknown attention kind %d", who, spec->kind);
-    if (spec->reserved != 0) return fail(e, VIT_ERR_ARG, "%s: vit_attention_spec.reserved must be 0 (got %d)", who, spec->reserved);
+    if (fault) return fail(e, VIT_ERR_ARG, fault, who, arg);
     out->kind = VIT_OUT_ATTENTION;
     out->attn_kind = spec->kind;
     out->dst = dst;
@@ -1135,15 +1153,13 @@ static int output_attention(vit_engine *e, const char *who, const vit_attention_
 }
 
 size_t vit_engine_attention_row_elems(const vit_engine *e, const vit_attention_spec *spec) {
-    if (!e || !spec || (spec->kind != VIT_ATTN_HEADS && spec->kind != VIT_ATTN_HEAD_MEAN) || spec->reserved != 0) return 0;
-    return (spec->kind == VIT_ATTN_HEADS ? (size_t)e->cfg.num_heads : 1) * (size_t)e->tokens;
+    int arg;
+    return e && !attention_spec_fault(spec, &arg) ? row_elems(e, VIT_OUT_ATTENTION, spec->kind) : 0;
 }
 
 size_t vit_engine_feature_row_elems(const vit_engine *e, const vit_feature_spec *spec) {
-    if (!e || !spec || spec->kind < VIT_FEAT_CLS || spec->kind > VIT_FEAT_TOKENS || (spec->l2_normalize != 0 && spec->l2_normalize != 1) ||
-        (spec->l2_normalize && spec->kind == VIT_FEAT_TOKENS))
-        return 0;
-    return (spec->kind == VIT_FEAT_TOKENS ? (size_t)e->tokens : 1) * (size_t)e->cfg.embed_dim;
+    int arg;
+    return e && !feature_spec_fault(spec, &arg) ? row_elems(e, VIT_OUT_FEATURES, spec->kind) : 0;
 }
 
 /* An 8-bit device-path call normalises into in_stage[0] and uses it until s gets past its kernels: the next host-pointer call's
@@ -1206,111 +1222,6 @@ static int forward_device_in(vit_engine *e, const void *d_images, const vit_inpu
     return in_stage_taken(e, in, s);
 }
 
-int vit_engine_forward_device(vit_engine *e, const float *d_images, int n, float *d_probs,
-                              int *d_top1_label, float *d_top1_prob, void *stream) {
-    if (!e) return VIT_ERR_ARG;
-    if (!d_images || !d_probs || n <= 0) return fail(e, VIT_ERR_ARG, "forward_device: bad arguments (n=%d)", n);
-    vit_input in;
-    memset(&in, 0, sizeof(in));
-    const vit_output out = output_probs(d_probs, d_top1_label, d_top1_prob);
-    return forward_device_in(e, d_images, &in, n, &out, stream);
-}
-
-int vit_engine_forward_device_u8(vit_engine *e, const unsigned char *d_images, int n, const float *mean, const float *std,
-                                 float *d_probs, int *d_top1_label, float *d_top1_prob, void *stream) {
-    if (!e) return VIT_ERR_ARG;
-    if (!d_images || !d_probs || n <= 0) return fail(e, VIT_ERR_ARG, "forward_device_u8: bad arguments (n=%d)", n);
-    if ((size_t)d_images & 3) return fail(e, VIT_ERR_ARG, "forward_device_u8: d_images must be 4-byte aligned");
-    vit_input in;
-    const int rc = input_u8(e, "forward_device_u8", mean, std, &in);
-    if (rc) return rc;
-    const vit_output out = output_probs(d_probs, d_top1_label, d_top1_prob);
-    return forward_device_in(e, d_images, &in, n, &out, stream);
-}
-
-int vit_engine_features_device(vit_engine *e, const float *d_images, int n, const vit_feature_spec *spec, float *d_out, void *stream) {
-    if (!e) return VIT_ERR_ARG;
-    if (!d_images || !d_out || n <= 0) return fail(e, VIT_ERR_ARG, "features_device: bad arguments (n=%d)", n);
-    vit_input in;
-    vit_output out;
-    memset(&in, 0, sizeof(in));
-    const int rc = output_features(e, "features_device", spec, d_out, &out);
-    if (rc) return rc;
-    return forward_device_in(e, d_images, &in, n, &out, stream);
-}
-
-int vit_engine_features_device_u8(vit_engine *e, const unsigned char *d_images, int n, const float *mean, const float *std,
-                                  const vit_feature_spec *spec, float *d_out, void *stream) {
-    if (!e) return VIT_ERR_ARG;
-    if (!d_images || !d_out || n <= 0) return fail(e, VIT_ERR_ARG, "features_device_u8: bad arguments (n=%d)", n);
-    if ((size_t)d_images & 3) return fail(e, VIT_ERR_ARG, "features_device_u8: d_images must be 4-byte aligned");
-    vit_input in;
-    vit_output out;
-    int rc = input_u8(e, "features_device_u8", mean, std, &in);
-    if (!rc) rc = output_features(e, "features_device_u8", spec, d_out, &out);
-    if (rc) return rc;
-    return forward_device_in(e, d_images, &in, n, &out, stream);
-}
-
-int vit_engine_forward_device_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, float *d_probs,
-                                     int *d_top1_label, float *d_top1_prob, void *stream) {
-    if (!e) return VIT_ERR_ARG;
-    if (!images || !d_probs || n <= 0) return fail(e, VIT_ERR_ARG, "forward_device_images: bad arguments (n=%d)", n);
-    vit_input in;
-    const int rc = input_images(e, "forward_device_images", images, n, pp, &in);
-    if (rc) return rc;
-    const vit_output out = output_probs(d_probs, d_top1_label, d_top1_prob);
-    return forward_device_in(e, images, &in, n, &out, stream);
-}
-
-int vit_engine_features_device_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, const vit_feature_spec *spec,
-                                      float *d_out, void *stream) {
-    if (!e) return VIT_ERR_ARG;
-    if (!images || !d_out || n <= 0) return fail(e, VIT_ERR_ARG, "features_device_images: bad arguments (n=%d)", n);
-    vit_input in;
-    vit_output out;
-    int rc = input_images(e, "features_device_images", images, n, pp, &in);
-    if (!rc) rc = output_features(e, "features_device_images", spec, d_out, &out);
-    if (rc) return rc;
-    return forward_device_in(e, images, &in, n, &out, stream);
-}
-
-int vit_engine_cls_attention_device(vit_engine *e, const float *d_images, int n, const vit_attention_spec *spec, float *d_out, void *stream) {
-    if (!e) return VIT_ERR_ARG;
-    if (!d_images || !d_out || n <= 0) return fail(e, VIT_ERR_ARG, "cls_attention_device: bad arguments (n=%d)", n);
-    vit_input in;
-    vit_output out;
-    memset(&in, 0, sizeof(in));
-    const int rc = output_attention(e, "cls_attention_device", spec, d_out, &out);
-    if (rc) return rc;
-    return forward_device_in(e, d_images, &in, n, &out, stream);
-}
-
-int vit_engine_cls_attention_device_u8(vit_engine *e, const unsigned char *d_images, int n, const float *mean, const float *std,
-                                       const vit_attention_spec *spec, float *d_out, void *stream) {
-    if (!e) return VIT_ERR_ARG;
-    if (!d_images || !d_out || n <= 0) return fail(e, VIT_ERR_ARG, "cls_attention_device_u8: bad arguments (n=%d)", n);
-    if ((size_t)d_images & 3) return fail(e, VIT_ERR_ARG, "cls_attention_device_u8: d_images must be 4-byte aligned");
-    vit_input in;
-    vit_output out;
-    int rc = input_u8(e, "cls_attention_device_u8", mean, std, &in);
-    if (!rc) rc = output_attention(e, "cls_attention_device_u8", spec, d_out, &out);
-    if (rc) return rc;
-    return forward_device_in(e, d_images, &in, n, &out, stream);
-}
-
-int vit_engine_cls_attention_device_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp,
-                                           const vit_attention_spec *spec, float *d_out, void *stream) {
-    if (!e) return VIT_ERR_ARG;
-    if (!images || !d_out || n <= 0) return fail(e, VIT_ERR_ARG, "cls_attention_device_images: bad arguments (n=%d)", n);
-    vit_input in;
-    vit_output out;
-    int rc = input_images(e, "cls_attention_device_images", images, n, pp, &in);
-    if (!rc) rc = output_attention(e, "cls_attention_device_images", spec, d_out, &out);
-    if (rc) return rc;
-    return forward_device_in(e, images, &in, n, &out, stream);
-}
-
 int vit_engine_sync(vit_engine *e) {
     if (!e) return VIT_ERR_ARG;
     HIP_TRY(e, vithip_stream_sync(e->stream));
@@ -1329,64 +1240,53 @@ static int gather_threads(void) {
     int n = omp_get_num_procs();
     return n < 1 ? 1 : (n > GATHER_THREADS_MAX ? GATHER_THREADS_MAX : n);
 }
-/* the caller's images of a host-pointer call: fp32 [C][S][S] (f32), 8-bit [S][S][C] (u8) or decoded 8-bit images of any size (img) */
-typedef struct {
-    const float *const *f32;
-    const unsigned char *const *u8;
-    const vit_image_u8 *img;
-} host_images;
-static const void *host_image(const host_images *im, int i) {
-    return im->img ? (const void *)im->img[i].pixels : im->u8 ? (const void *)im->u8[i] : (const void *)im->f32[i];
-}
-
-static void gather_images(char *dst, const host_images *images, int first, int count, size_t img_bytes) {
-    const int nt = gather_threads();
-#pragma omp parallel for num_threads(nt) schedule(static) if (count >= 4)
-    for (int i = 0; i < count; ++i) memcpy(dst + (size_t)i * img_bytes, host_image(images, first + i), img_bytes);
-}
-/* gather a piece into pin_in[slot] and upload it to dst: in_stage[slot], or in8_stage[slot] for 8-bit images */
-static int stage_piece(vit_engine *e, int slot, void *dst, const host_images *images, int first, int count, size_t img_bytes, int sub) {
-    for (int s0 = 0; s0 < count; s0 += sub) {
-        const int c = count - s0 < sub ? count - s0 : sub;
-        char *pin = (char *)e->pin_in[slot] + (size_t)s0 * img_bytes;
-        gather_images(pin, images, first + s0, c, img_bytes);
-        HIP_TRY(e, vithip_memcpy_h2d((char *)dst + (size_t)s0 * img_bytes, pin, (size_t)c * img_bytes, e->copy_stream));
+/* The caller's images of a host-pointer call are the input kind plus one pointer: an array of pointers to fp32 [C][S][S] or to 8-bit
+ * [S][S][C] images, or the records of decoded 8-bit images of any size. */
+static const void *host_image(int kind, const void *images, int i) {
+    switch (kind) {
+    case VIT_IN_IMAGES: return ((const vit_image_u8 *)images)[i].pixels;
+    case VIT_IN_U8: return ((const unsigned char *const *)images)[i];
+    default: return ((const float *const *)images)[i];
     }
-    HIP_TRY(e, vithip_event_record(e->ev_h2d[slot], e->copy_stream));
-    return VIT_OK;
 }
-
-/* Decoded images of any size: a piece's images lie back to back in a slot, each start rounded up to 16 bytes. */
-static size_t image_slot_bytes(const vit_engine *e, const vit_image_u8 *im) {
-    return ((size_t)im->height * (size_t)im->width * (size_t)e->cfg.in_chans + 15) & ~(size_t)15;
+/* its bytes as the caller holds it, and in a staging slot: a piece's images lie back to back, each start rounded up to 16 bytes
+ * (fp32 and 8-bit images fill whole 16 bytes anyway: img_size % 4 == 0) */
+static size_t host_image_bytes(const vit_engine *e, int kind, const void *images, int i) {
+    const size_t C = (size_t)e->cfg.in_chans, S = (size_t)e->cfg.img_size;
+    if (kind != VIT_IN_IMAGES) return C * S * S * (kind == VIT_IN_U8 ? 1 : sizeof(float));
+    const vit_image_u8 *im = (const vit_image_u8 *)images + i;
+    return (size_t)im->height * (size_t)im->width * C;
+}
+static size_t image_slot_bytes(const vit_engine *e, int kind, const void *images, int i) {
+    return (host_image_bytes(e, kind, images, i) + 15) & ~(size_t)15;
 }
 static size_t image_slot_cap(const vit_engine *e) { /* what pin_in[slot] holds: max_batch fp32 images */
     return (size_t)e->opt.max_batch * e->cfg.in_chans * e->cfg.img_size * e->cfg.img_size * sizeof(float);
 }
 /* img_off[0..count] = where the images first .. first + count - 1 of a piece lie in its slot, and where they end */
-static void image_offsets(vit_engine *e, const vit_image_u8 *images, int first, int count) {
+static void image_offsets(vit_engine *e, int kind, const void *images, int first, int count) {
     e->img_off[0] = 0;
-    for (int i = 0; i < count; ++i) e->img_off[i + 1] = e->img_off[i] + image_slot_bytes(e, &images[first + i]);
+    for (int i = 0; i < count; ++i) e->img_off[i + 1] = e->img_off[i] + image_slot_bytes(e, kind, images, first + i);
 }
-/* stage_piece for decoded images: gather into pin_in[slot] at their offsets, upload to img_stage[slot] in sub-pieces of `sub` images */
-static int stage_piece_images(vit_engine *e, int slot, const vit_image_u8 *images, int first, int count, int sub) {
+/* gather a piece into pin_in[slot] at its images' offsets and upload it to dst (in_stage[slot], in8_stage[slot] or img_stage[slot])
+ * in sub-pieces of `sub` images */
+static int stage_piece(vit_engine *e, int slot, void *dst, int kind, const void *images, int first, int count, int sub) {
     const int nt = gather_threads();
-    const size_t C = (size_t)e->cfg.in_chans;
     char *pin = (char *)e->pin_in[slot];
-    image_offsets(e, images, first, count);
+    image_offsets(e, kind, images, first, count);
     for (int s0 = 0; s0 < count; s0 += sub) {
         const int c = count - s0 < sub ? count - s0 : sub;
 #pragma omp parallel for num_threads(nt) schedule(static) if (c >= 4)
         for (int i = s0; i < s0 + c; ++i)
-            memcpy(pin + e->img_off[i], images[first + i].pixels, (size_t)images[first + i].height * (size_t)images[first + i].width * C);
-        HIP_TRY(e, vithip_memcpy_h2d(e->img_stage[slot] + e->img_off[s0], pin + e->img_off[s0], e->img_off[s0 + c] - e->img_off[s0], e->copy_stream));
+            memcpy(pin + e->img_off[i], host_image(kind, images, first + i), host_image_bytes(e, kind, images, first + i));
+        HIP_TRY(e, vithip_memcpy_h2d((char *)dst + e->img_off[s0], pin + e->img_off[s0], e->img_off[s0 + c] - e->img_off[s0], e->copy_stream));
     }
     HIP_TRY(e, vithip_event_record(e->ev_h2d[slot], e->copy_stream));
     return VIT_OK;
 }
-/* the records of a staged piece, as the kernel reads them: the images' sizes, their pixels inside img_stage[slot] */
+/* the records of a staged piece of decoded images, as the kernel reads them: the images' sizes, their pixels inside img_stage[slot] */
 static const vithip_image_u8 *piece_records(vit_engine *e, int slot, const vit_image_u8 *images, int first, int count) {
-    image_offsets(e, images, first, count);
+    image_offsets(e, VIT_IN_IMAGES, images, first, count);
     for (int i = 0; i < count; ++i) {
         e->img_recs[i].pixels = e->img_stage[slot] + e->img_off[i];
         e->img_recs[i].height = images[first + i].height;
@@ -1394,10 +1294,16 @@ static const vithip_image_u8 *piece_records(vit_engine *e, int slot, const vit_i
     }
     return e->img_recs;
 }
+/* wait for the piece in slot b and hand its rows back: images first .. first + count - 1 */
+static int scatter_piece(vit_engine *e, int b, float *const *rows, int first, int count, size_t row) {
+    HIP_TRY(e, vithip_event_sync(e->ev_done[b]));
+    for (int i = 0; i < count; ++i) memcpy(rows[first + i], e->pin_out[b] + (size_t)i * row, row * sizeof(float));
+    return VIT_OK;
+}
 
 /* The pieces of a host-pointer call: piece_lo[0..np] = their first images (piece_lo[np] = n).  The first piece has at most first_n
  * images, every other at most chunk; a piece of decoded images also ends where the next image's bytes would overflow the slot. */
-static int cut_pieces(vit_engine *e, const char *who, const host_images *images, int n, int first_n, int chunk, int *np_out) {
+static int cut_pieces(vit_engine *e, const char *who, int kind, const void *images, int n, int first_n, int chunk, int *np_out) {
     if (n + 1 > e->piece_cap) {
         int *p = (int *)realloc(e->piece_lo, ((size_t)n + 1) * sizeof(int));
         if (!p) return fail(e, VIT_ERR_NOMEM, "out of host memory");
@@ -1409,13 +1315,14 @@ static int cut_pieces(vit_engine *e, const char *who, const host_images *images,
     for (int i = 0; i < n;) {
         const int limit = np == 0 ? first_n : chunk;
         int cnt = n - i < limit ? n - i : limit;
-        if (images->img) {
+        if (kind == VIT_IN_IMAGES) {
+            const vit_image_u8 *im = (const vit_image_u8 *)images + i;
             size_t bytes = 0;
             int fit = 0;
-            while (fit < cnt && bytes + image_slot_bytes(e, &images->img[i + fit]) <= cap) bytes += image_slot_bytes(e, &images->img[i + fit++]);
+            while (fit < cnt && bytes + image_slot_bytes(e, kind, images, i + fit) <= cap) bytes += image_slot_bytes(e, kind, images, i + fit++);
             if (!fit)
                 return fail(e, VIT_ERR_ARG, "%s: image %d (%d x %d, %zu bytes) does not fit the staging of max_batch = %d fp32 images (%zu bytes)",
-                            who, i, images->img[i].height, images->img[i].width, image_slot_bytes(e, &images->img[i]), e->opt.max_batch, cap);
+                            who, i, im->height, im->width, image_slot_bytes(e, kind, images, i), e->opt.max_batch, cap);
             cnt = fit;
         }
         i += cnt;
@@ -1467,15 +1374,14 @@ static int ensure_out_stage(vit_engine *e, size_t row) {
  * the ev_h2d / ev_done ordering below covers them as it covers the fp32 pieces.  Decoded images of any size go the same way through
  * img_stage[slot], in pieces that the slot's bytes bound as well as the image count (cut_pieces). */
 /* out: the kind of output (its pointers unused: the rows go through out_stage / pin_out into rows[i]) */
-static int forward_host_in(vit_engine *e, const char *who, const host_images *images, const vit_input *in, int n, const vit_output *out,
+static int forward_host_in(vit_engine *e, const char *who, const void *images, const vit_input *in, int n, const vit_output *out,
                            float *const *rows) {
     if (!e->weights_loaded) return fail(e, VIT_ERR_STATE, "forward before vit_engine_load_weights()");
     const size_t img = (size_t)e->cfg.in_chans * e->cfg.img_size * e->cfg.img_size;
-    const size_t img_bytes = img * (in->kind == VIT_IN_F32 ? sizeof(float) : 1); /* fp32 and 8-bit pieces; decoded images have their own sizes */
-    const int decoded = in->kind == VIT_IN_IMAGES;
+    const int kind = in->kind, decoded = kind == VIT_IN_IMAGES;
     const size_t row = out_row_elems(e, out); /* floats per image of the scatter stage */
     for (int i = 0; i < n; ++i)
-        if (!host_image(images, i) || !rows[i]) return fail(e, VIT_ERR_ARG, "%s: image or output row %d is NULL", who, i);
+        if (!host_image(kind, images, i) || !rows[i]) return fail(e, VIT_ERR_ARG, "%s: image or output row %d is NULL", who, i);
     const int chunk = chunk_limit(e);
     /* Round 5: what the first piece has to do is cover, with its compute, the gather + upload of the piece behind it -- and no
      * more than that, because a small piece computes badly (ViT-B/16 fp32, device-resident: 8 images run at 56 % of the 256-image
@@ -1496,7 +1402,7 @@ static int forward_host_in(vit_engine *e, const char *who, const host_images *im
     if (first_n > n) first_n = n;
     int np = 0;
     {
-        const int rc = cut_pieces(e, who, images, n, first_n, chunk, &np); /* before anything is enqueued: it may refuse an image */
+        const int rc = cut_pieces(e, who, kind, images, n, first_n, chunk, &np); /* before anything is enqueued: it may refuse an image */
         if (rc) return rc;
     }
     const int *lo = e->piece_lo; /* piece k = images lo[k] .. lo[k + 1] - 1 */
@@ -1505,7 +1411,7 @@ static int forward_host_in(vit_engine *e, const char *who, const host_images *im
         const int rc = ensure_out_stage(e, row);
         if (rc) return rc;
     }
-    for (int b = 0; b < 2 && in->kind == VIT_IN_U8; ++b)
+    for (int b = 0; b < 2 && kind == VIT_IN_U8; ++b)
         if (!e->in8_stage[b]) HIP_TRY(e, vithip_malloc((void **)&e->in8_stage[b], (size_t)e->opt.max_batch * img));
     for (int b = 0; b < 2 && decoded; ++b)
         if (!e->img_stage[b]) {
@@ -1522,7 +1428,7 @@ static int forward_host_in(vit_engine *e, const char *who, const host_images *im
     }
     void *up[2]; /* where the pieces are uploaded to */
     for (int b = 0; b < 2; ++b)
-        up[b] = decoded ? (void *)e->img_stage[b] : in->kind == VIT_IN_U8 ? (void *)e->in8_stage[b] : (void *)e->in_stage[b];
+        up[b] = decoded ? (void *)e->img_stage[b] : kind == VIT_IN_U8 ? (void *)e->in8_stage[b] : (void *)e->in_stage[b];
     /*
      * Pieces of up to max_batch images flow through two staging slots: while the GPU computes piece i,
      * the host gathers the separately allocated images of piece i+1 into pinned memory and the copy
@@ -1533,8 +1439,7 @@ static int forward_host_in(vit_engine *e, const char *who, const host_images *im
      */
     /* stage piece 0 */
     {
-        const int sub = np > 1 ? SUB_PIECE_FIRST : SUB_PIECE;
-        int rc0 = decoded ? stage_piece_images(e, 0, images->img, 0, lo[1], sub) : stage_piece(e, 0, up[0], images, 0, lo[1], img_bytes, sub);
+        const int rc0 = stage_piece(e, 0, up[0], kind, images, 0, lo[1], np > 1 ? SUB_PIECE_FIRST : SUB_PIECE);
         if (rc0) return rc0;
     }
     for (int k = 0; k < np; ++k) {
@@ -1543,30 +1448,20 @@ static int forward_host_in(vit_engine *e, const char *who, const host_images *im
         vit_output o = *out;
         o.dst = e->out_stage[b];
         /* decoded images: the kernel reads the piece's records, which point into the slot the piece was uploaded to */
-        const void *src = decoded ? (const void *)piece_records(e, b, images->img, lo[k], nb) : up[b];
+        const void *src = decoded ? (const void *)piece_records(e, b, (const vit_image_u8 *)images, lo[k], nb) : up[b];
         int rc = forward_chunk(e, e->stream, src, in, e->in_stage[b], nb, &o);
         if (rc) return rc;
         HIP_TRY(e, vithip_memcpy_d2h(e->pin_out[b], e->out_stage[b], (size_t)nb * row * sizeof(float), e->stream));
         HIP_TRY(e, vithip_event_record(e->ev_done[b], e->stream));
         if (e->opt.profile) e->pending_images += nb;
-        if (k >= 1) { /* piece k-1 (slot b^1) is finished by now or soon: hand its rows back */
-            HIP_TRY(e, vithip_event_sync(e->ev_done[b ^ 1]));
-            const int first = lo[k - 1];
-            for (int i = 0; i < lo[k] - first; ++i)
-                memcpy(rows[first + i], e->pin_out[b ^ 1] + (size_t)i * row, row * sizeof(float));
-        }
-        if (k + 1 < np) { /* slot b^1 is free again (its H2D, compute and D2H are complete): refill it */
-            const int first = lo[k + 1], cnt = lo[k + 2] - first;
-            rc = decoded ? stage_piece_images(e, b ^ 1, images->img, first, cnt, SUB_PIECE)
-                         : stage_piece(e, b ^ 1, up[b ^ 1], images, first, cnt, img_bytes, SUB_PIECE);
-            if (rc) return rc;
-        }
+        /* piece k-1 (slot b^1) is finished by now or soon: hand its rows back */
+        if (k >= 1 && (rc = scatter_piece(e, b ^ 1, rows, lo[k - 1], lo[k] - lo[k - 1], row))) return rc;
+        /* slot b^1 is free again (its H2D, compute and D2H are complete): refill it */
+        if (k + 1 < np && (rc = stage_piece(e, b ^ 1, up[b ^ 1], kind, images, lo[k + 1], lo[k + 2] - lo[k + 1], SUB_PIECE))) return rc;
     }
     {
-        const int b = (np - 1) & 1, first = lo[np - 1];
-        HIP_TRY(e, vithip_event_sync(e->ev_done[b]));
-        for (int i = 0; i < n - first; ++i)
-            memcpy(rows[first + i], e->pin_out[b] + (size_t)i * row, row * sizeof(float));
+        const int rc = scatter_piece(e, (np - 1) & 1, rows, lo[np - 1], n - lo[np - 1], row);
+        if (rc) return rc;
     }
     if (e->opt.profile) {
         int rc = collect_profile(e);
@@ -1575,113 +1470,152 @@ static int forward_host_in(vit_engine *e, const char *who, const host_images *im
     return VIT_OK;
 }
 
-int vit_engine_forward_host(vit_engine *e, const float *const *images, int n, float *const *probs) {
+/* One call of the public surface: output kind x input kind x place, with the raw arguments of each as the caller gave them. */
+enum { VIT_AT_DEVICE = 0, VIT_AT_HOST = 1 };
+typedef struct {
+    const char *who;        /* the function's name without vit_engine_, for messages */
+    int place;              /* VIT_AT_* */
+    int in_kind;            /* VIT_IN_* */
+    const void *images;     /* device: fp32 or 8-bit pixels; host: an array of pointers to them; VIT_IN_IMAGES: records (a host array) */
+    int n;
+    const float *mean, *std; /* VIT_IN_U8 */
+    const vit_preproc *pp;  /* VIT_IN_IMAGES */
+    int out_kind;           /* VIT_OUT_* */
+    const void *spec;       /* vit_feature_spec (VIT_OUT_FEATURES) or vit_attention_spec (VIT_OUT_ATTENTION) */
+    float *dst;             /* VIT_AT_DEVICE: [n][row] */
+    float *const *rows;     /* VIT_AT_HOST: a row per image */
+    int *label;             /* VIT_AT_DEVICE, VIT_OUT_PROBS: top-1 (may be NULL) */
+    float *prob;
+    void *stream;           /* VIT_AT_DEVICE */
+} vit_call;
+
+/* Every public forward comes through here, so this order decides which message a caller sees: the engine, the pointers and n, the
+ * alignment of device 8-bit pixels, the input, the output spec -- and only then, in the place's forward, whether weights are loaded. */
+static int run_call(vit_engine *e, const vit_call *c) {
+    const int host = c->place == VIT_AT_HOST;
     if (!e) return VIT_ERR_ARG;
-    if (!images || !probs || n <= 0) return fail(e, VIT_ERR_ARG, "forward_host: bad arguments (n=%d)", n);
-    const host_images im = {images, NULL, NULL};
+    if (!c->images || !(host ? (const void *)c->rows : (const void *)c->dst) || c->n <= 0)
+        return fail(e, VIT_ERR_ARG, "%s: bad arguments (n=%d)", c->who, c->n);
+    if (!host && c->in_kind == VIT_IN_U8 && ((size_t)c->images & 3)) return fail(e, VIT_ERR_ARG, "%s: d_images must be 4-byte aligned", c->who);
     vit_input in;
+    vit_output out;
+    int rc = VIT_OK;
     memset(&in, 0, sizeof(in));
-    const vit_output out = output_probs(NULL, NULL, NULL);
-    return forward_host_in(e, "forward_host", &im, &in, n, &out, probs);
+    if (c->in_kind == VIT_IN_U8) rc = input_u8(e, c->who, c->mean, c->std, &in);
+    else if (c->in_kind == VIT_IN_IMAGES) rc = input_images(e, c->who, (const vit_image_u8 *)c->images, c->n, c->pp, &in);
+    if (rc) return rc;
+    if (c->out_kind == VIT_OUT_FEATURES) rc = output_features(e, c->who, (const vit_feature_spec *)c->spec, c->dst, &out);
+    else if (c->out_kind == VIT_OUT_ATTENTION) rc = output_attention(e, c->who, (const vit_attention_spec *)c->spec, c->dst, &out);
+    else out = output_probs(c->dst, c->label, c->prob);
+    if (rc) return rc;
+    return host ? forward_host_in(e, c->who, c->images, &in, c->n, &out, c->rows) : forward_device_in(e, c->images, &in, c->n, &out, c->stream);
+}
+
+int vit_engine_forward_device(vit_engine *e, const float *d_images, int n, float *d_probs,
+                              int *d_top1_label, float *d_top1_prob, void *stream) {
+    return run_call(e, &(vit_call){.who = "forward_device", .place = VIT_AT_DEVICE, .in_kind = VIT_IN_F32, .images = d_images, .n = n,
+                                    .out_kind = VIT_OUT_PROBS, .dst = d_probs, .label = d_top1_label, .prob = d_top1_prob,
+                                    .stream = stream});
+}
+
+int vit_engine_forward_device_u8(vit_engine *e, const unsigned char *d_images, int n, const float *mean, const float *std,
+                                 float *d_probs, int *d_top1_label, float *d_top1_prob, void *stream) {
+    return run_call(e, &(vit_call){.who = "forward_device_u8", .place = VIT_AT_DEVICE, .in_kind = VIT_IN_U8, .images = d_images, .n = n,
+                                    .mean = mean, .std = std, .out_kind = VIT_OUT_PROBS, .dst = d_probs, .label = d_top1_label,
+                                    .prob = d_top1_prob, .stream = stream});
+}
+
+int vit_engine_forward_device_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, float *d_probs,
+                                     int *d_top1_label, float *d_top1_prob, void *stream) {
+    return run_call(e, &(vit_call){.who = "forward_device_images", .place = VIT_AT_DEVICE, .in_kind = VIT_IN_IMAGES, .images = images,
+                                    .n = n, .pp = pp, .out_kind = VIT_OUT_PROBS, .dst = d_probs, .label = d_top1_label,
+                                    .prob = d_top1_prob, .stream = stream});
+}
+
+int vit_engine_features_device(vit_engine *e, const float *d_images, int n, const vit_feature_spec *spec, float *d_out, void *stream) {
+    return run_call(e, &(vit_call){.who = "features_device", .place = VIT_AT_DEVICE, .in_kind = VIT_IN_F32, .images = d_images, .n = n,
+                                    .out_kind = VIT_OUT_FEATURES, .spec = spec, .dst = d_out, .stream = stream});
+}
+
+int vit_engine_features_device_u8(vit_engine *e, const unsigned char *d_images, int n, const float *mean, const float *std,
+                                  const vit_feature_spec *spec, float *d_out, void *stream) {
+    return run_call(e, &(vit_call){.who = "features_device_u8", .place = VIT_AT_DEVICE, .in_kind = VIT_IN_U8, .images = d_images, .n = n,
+                                    .mean = mean, .std = std, .out_kind = VIT_OUT_FEATURES, .spec = spec, .dst = d_out, .stream = stream});
+}
+
+int vit_engine_features_device_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, const vit_feature_spec *spec,
+                                      float *d_out, void *stream) {
+    return run_call(e, &(vit_call){.who = "features_device_images", .place = VIT_AT_DEVICE, .in_kind = VIT_IN_IMAGES, .images = images,
+                                    .n = n, .pp = pp, .out_kind = VIT_OUT_FEATURES, .spec = spec, .dst = d_out, .stream = stream});
+}
+
+int vit_engine_cls_attention_device(vit_engine *e, const float *d_images, int n, const vit_attention_spec *spec, float *d_out, void *stream) {
+    return run_call(e, &(vit_call){.who = "cls_attention_device", .place = VIT_AT_DEVICE, .in_kind = VIT_IN_F32, .images = d_images,
+                                    .n = n, .out_kind = VIT_OUT_ATTENTION, .spec = spec, .dst = d_out, .stream = stream});
+}
+
+int vit_engine_cls_attention_device_u8(vit_engine *e, const unsigned char *d_images, int n, const float *mean, const float *std,
+                                       const vit_attention_spec *spec, float *d_out, void *stream) {
+    return run_call(e, &(vit_call){.who = "cls_attention_device_u8", .place = VIT_AT_DEVICE, .in_kind = VIT_IN_U8, .images = d_images,
+                                    .n = n, .mean = mean, .std = std, .out_kind = VIT_OUT_ATTENTION, .spec = spec, .dst = d_out,
+                                    .stream = stream});
+}
+
+int vit_engine_cls_attention_device_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp,
+                                           const vit_attention_spec *spec, float *d_out, void *stream) {
+    return run_call(e, &(vit_call){.who = "cls_attention_device_images", .place = VIT_AT_DEVICE, .in_kind = VIT_IN_IMAGES,
+                                    .images = images, .n = n, .pp = pp, .out_kind = VIT_OUT_ATTENTION, .spec = spec, .dst = d_out,
+                                    .stream = stream});
+}
+
+int vit_engine_forward_host(vit_engine *e, const float *const *images, int n, float *const *probs) {
+    return run_call(e, &(vit_call){.who = "forward_host", .place = VIT_AT_HOST, .in_kind = VIT_IN_F32, .images = images, .n = n,
+                                    .out_kind = VIT_OUT_PROBS, .rows = probs});
 }
 
 int vit_engine_forward_host_u8(vit_engine *e, const unsigned char *const *images, int n, const float *mean, const float *std,
                                float *const *probs) {
-    if (!e) return VIT_ERR_ARG;
-    if (!images || !probs || n <= 0) return fail(e, VIT_ERR_ARG, "forward_host_u8: bad arguments (n=%d)", n);
-    const host_images im = {NULL, images, NULL};
-    vit_input in;
-    const int rc = input_u8(e, "forward_host_u8", mean, std, &in);
-    if (rc) return rc;
-    const vit_output out = output_probs(NULL, NULL, NULL);
-    return forward_host_in(e, "forward_host_u8", &im, &in, n, &out, probs);
+    return run_call(e, &(vit_call){.who = "forward_host_u8", .place = VIT_AT_HOST, .in_kind = VIT_IN_U8, .images = images, .n = n,
+                                    .mean = mean, .std = std, .out_kind = VIT_OUT_PROBS, .rows = probs});
+}
+
+int vit_engine_forward_host_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, float *const *probs) {
+    return run_call(e, &(vit_call){.who = "forward_host_images", .place = VIT_AT_HOST, .in_kind = VIT_IN_IMAGES, .images = images, .n = n,
+                                    .pp = pp, .out_kind = VIT_OUT_PROBS, .rows = probs});
 }
 
 int vit_engine_features_host(vit_engine *e, const float *const *images, int n, const vit_feature_spec *spec, float *const *out) {
-    if (!e) return VIT_ERR_ARG;
-    if (!images || !out || n <= 0) return fail(e, VIT_ERR_ARG, "features_host: bad arguments (n=%d)", n);
-    const host_images im = {images, NULL, NULL};
-    vit_input in;
-    vit_output o;
-    memset(&in, 0, sizeof(in));
-    const int rc = output_features(e, "features_host", spec, NULL, &o);
-    if (rc) return rc;
-    return forward_host_in(e, "features_host", &im, &in, n, &o, out);
+    return run_call(e, &(vit_call){.who = "features_host", .place = VIT_AT_HOST, .in_kind = VIT_IN_F32, .images = images, .n = n,
+                                    .out_kind = VIT_OUT_FEATURES, .spec = spec, .rows = out});
 }
 
 int vit_engine_features_host_u8(vit_engine *e, const unsigned char *const *images, int n, const float *mean, const float *std,
                                 const vit_feature_spec *spec, float *const *out) {
-    if (!e) return VIT_ERR_ARG;
-    if (!images || !out || n <= 0) return fail(e, VIT_ERR_ARG, "features_host_u8: bad arguments (n=%d)", n);
-    const host_images im = {NULL, images, NULL};
-    vit_input in;
-    vit_output o;
-    int rc = input_u8(e, "features_host_u8", mean, std, &in);
-    if (!rc) rc = output_features(e, "features_host_u8", spec, NULL, &o);
-    if (rc) return rc;
-    return forward_host_in(e, "features_host_u8", &im, &in, n, &o, out);
-}
-
-int vit_engine_forward_host_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, float *const *probs) {
-    if (!e) return VIT_ERR_ARG;
-    if (!images || !probs || n <= 0) return fail(e, VIT_ERR_ARG, "forward_host_images: bad arguments (n=%d)", n);
-    const host_images im = {NULL, NULL, images};
-    vit_input in;
-    const int rc = input_images(e, "forward_host_images", images, n, pp, &in);
-    if (rc) return rc;
-    const vit_output out = output_probs(NULL, NULL, NULL);
-    return forward_host_in(e, "forward_host_images", &im, &in, n, &out, probs);
+    return run_call(e, &(vit_call){.who = "features_host_u8", .place = VIT_AT_HOST, .in_kind = VIT_IN_U8, .images = images, .n = n,
+                                    .mean = mean, .std = std, .out_kind = VIT_OUT_FEATURES, .spec = spec, .rows = out});
 }
 
 int vit_engine_features_host_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, const vit_feature_spec *spec,
                                     float *const *out) {
-    if (!e) return VIT_ERR_ARG;
-    if (!images || !out || n <= 0) return fail(e, VIT_ERR_ARG, "features_host_images: bad arguments (n=%d)", n);
-    const host_images im = {NULL, NULL, images};
-    vit_input in;
-    vit_output o;
-    int rc = input_images(e, "features_host_images", images, n, pp, &in);
-    if (!rc) rc = output_features(e, "features_host_images", spec, NULL, &o);
-    if (rc) return rc;
-    return forward_host_in(e, "features_host_images", &im, &in, n, &o, out);
+    return run_call(e, &(vit_call){.who = "features_host_images", .place = VIT_AT_HOST, .in_kind = VIT_IN_IMAGES, .images = images, .n = n,
+                                    .pp = pp, .out_kind = VIT_OUT_FEATURES, .spec = spec, .rows = out});
 }
 
 int vit_engine_cls_attention_host(vit_engine *e, const float *const *images, int n, const vit_attention_spec *spec, float *const *out) {
-    if (!e) return VIT_ERR_ARG;
-    if (!images || !out || n <= 0) return fail(e, VIT_ERR_ARG, "cls_attention_host: bad arguments (n=%d)", n);
-    const host_images im = {images, NULL, NULL};
-    vit_input in;
-    vit_output o;
-    memset(&in, 0, sizeof(in));
-    const int rc = output_attention(e, "cls_attention_host", spec, NULL, &o);
-    if (rc) return rc;
-    return forward_host_in(e, "cls_attention_host", &im, &in, n, &o, out);
+    return run_call(e, &(vit_call){.who = "cls_attention_host", .place = VIT_AT_HOST, .in_kind = VIT_IN_F32, .images = images, .n = n,
+                                    .out_kind = VIT_OUT_ATTENTION, .spec = spec, .rows = out});
 }
 
 int vit_engine_cls_attention_host_u8(vit_engine *e, const unsigned char *const *images, int n, const float *mean, const float *std,
                                      const vit_attention_spec *spec, float *const *out) {
-    if (!e) return VIT_ERR_ARG;
-    if (!images || !out || n <= 0) return fail(e, VIT_ERR_ARG, "cls_attention_host_u8: bad arguments (n=%d)", n);
-    const host_images im = {NULL, images, NULL};
-    vit_input in;
-    vit_output o;
-    int rc = input_u8(e, "cls_attention_host_u8", mean, std, &in);
-    if (!rc) rc = output_attention(e, "cls_attention_host_u8", spec, NULL, &o);
-    if (rc) return rc;
-    return forward_host_in(e, "cls_attention_host_u8", &im, &in, n, &o, out);
+    return run_call(e, &(vit_call){.who = "cls_attention_host_u8", .place = VIT_AT_HOST, .in_kind = VIT_IN_U8, .images = images, .n = n,
+                                    .mean = mean, .std = std, .out_kind = VIT_OUT_ATTENTION, .spec = spec, .rows = out});
 }
 
 int vit_engine_cls_attention_host_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp,
                                          const vit_attention_spec *spec, float *const *out) {
-    if (!e) return VIT_ERR_ARG;
-    if (!images || !out || n <= 0) return fail(e, VIT_ERR_ARG, "cls_attention_host_images: bad arguments (n=%d)", n);
-    const host_images im = {NULL, NULL, images};
-    vit_input in;
-    vit_output o;
-    int rc = input_images(e, "cls_attention_host_images", images, n, pp, &in);
-    if (!rc) rc = output_attention(e, "cls_attention_host_images", spec, NULL, &o);
-    if (rc) return rc;
-    return forward_host_in(e, "cls_attention_host_images", &im, &in, n, &o, out);
+    return run_call(e, &(vit_call){.who = "cls_attention_host_images", .place = VIT_AT_HOST, .in_kind = VIT_IN_IMAGES, .images = images,
+                                    .n = n, .pp = pp, .out_kind = VIT_OUT_ATTENTION, .spec = spec, .rows = out});
 }
 
 int vit_engine_handover_stats(vit_engine *e, long *taken, long *recomputed) {
