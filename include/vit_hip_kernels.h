@@ -83,8 +83,12 @@ enum { VITHIP_EPI_BIAS = 0, VITHIP_EPI_BIAS_GELU = 1, VITHIP_EPI_BIAS_RESIDUAL =
  * operands).  fp32 in, fp32 MFMA accumulate (v_mfma_f32_32x32x2_f32), fp32 out.
  *   EPI_BIAS_GELU:     y = 0.5*y*(1+erff(y/sqrtf(2)))                 (ViT_seq.c:231-233)
  *   EPI_BIAS_RESIDUAL: y += residual[m][n]; residual may alias C      (ViT_seq.c:286-288,297-299)
- * Requirements: K % 32 == 0; lda, ldw, ldc, ldr % 4 == 0; W must provide ceil(N/32)*32 rows
- * (pad rows are read, never used); all pointers 16-byte aligned.
+ * Requirements, the same for every tile code, both arithmetics and the w_split image (anything else: hipErrorInvalidValue):
+ *   K % 32 == 0; lda, ldw >= K and % 4 == 0, A and W 16-byte aligned (the operands are read 128 bits at a time);
+ *   ldc, ldr >= N, any value: C, residual and bias are accessed one float at a time and need only their natural 4-byte
+ *     alignment (the 10-class head stores with ldc = 10 through a C that is only 4-byte aligned);
+ *   W has exactly N rows: every tile clamps the row index of W to N - 1, nothing behind row N - 1 is read.
+ * Only columns 0..N-1 of rows 0..M-1 of C are written.
  */
 typedef struct {
     const float *A; int lda;
@@ -225,7 +229,8 @@ int vithip_rowstats_bf16(vithip_stream_t stream, const float *x, size_t ldx, uns
 /* strips = vithip_ln_strips(N) = 4 * ceil(N / 256): partials [strips][rows][2] (sum, sum of squares) -> rows_out [rows][2]. */
 int vithip_ln_strips(int N);
 int vithip_rowstats_finalize(vithip_stream_t stream, const float *partials, int strips, int rows, int dim, float *rows_out);
-/* dst[r][0..width) = src[r * src_stride .. + width): a strided row subset made compact (e.g. the pairs of the class rows). */
+/* dst[r * dst_stride .. + width) = src[r * src_stride .. + width): a strided row subset made compact (e.g. the pairs of the class
+ * rows).  rows, width >= 1; both strides >= width; 4-byte alignment suffices. */
 int vithip_gather_rows_f32(vithip_stream_t stream, const float *src, size_t src_stride, float *dst, size_t dst_stride, int rows,
                            int width);
 /* LayerNorm with fp32 statistics and a bf16 store; attention reading bf16 Q/K/V [n*tokens][3*heads*64] and
@@ -282,7 +287,7 @@ int vithip_patch_embed_f32(vithip_stream_t stream, const float *images, const fl
  * y[r][0..dim) = (x[r] - mean) * inv_std * gamma + beta for rows r = 0..rows-1 where row r
  * starts at x + r*ldx (ldx lets the final LayerNorm touch only the class-token rows).
  * mean/var as ViT_seq.c:103-121: var = E[x^2] - mean^2, inv_std = 1/sqrtf((double)var + 1e-6).
- * dim % 4 == 0, dim <= 2048.
+ * dim % 4 == 0, dim <= 2048; ldx, ldy >= dim and % 4 == 0; x, y, gamma, beta 16-byte aligned (vithip_layernorm_f32_bf16out: the same).
  */
 int vithip_layernorm_f32(vithip_stream_t stream, const float *x, size_t ldx, float *y, size_t ldy,
                          const float *gamma, const float *beta, int rows, int dim);

@@ -262,7 +262,9 @@ def lib() -> C.CDLL:
 
 def hip_check(rc: int, what: str = "HIP call") -> None:
     if rc != 0:
-        raise VitError(f"{what}: HIP error {rc} ({lib().vithip_error_string(rc).decode()})")
+        err = VitError(f"{what}: HIP error {rc} ({lib().vithip_error_string(rc).decode()})")
+        err.code = int(rc)   # hipErrorInvalidValue = 1: what a launcher answers to a layout it refuses
+        raise err
 
 
 def _as_f32(a) -> np.ndarray:
@@ -326,9 +328,48 @@ class DeviceArray:
             pass
 
 
+class _PlainBuffer:
+    """A rows x width matrix with leading dimension ld, `offset` elements into its allocation: what the op wrappers below place
+    every operand in.  tests/strided.py's Frame has the same .ptr / .ld / .window() and adds guard rows and a sentinel."""
+
+    def __init__(self, rows, width, ld=None, dtype=np.float32, offset=0, data=None):
+        self.rows, self.width, self.ld = int(rows), int(width), int(width if ld is None else ld)
+        self.dtype, self.offset = np.dtype(dtype), int(offset)
+        img = np.zeros(self.offset + self.rows * self.ld, self.dtype)
+        if data is not None:
+            img[self.offset:].reshape(self.rows, self.ld)[:, :self.width] = np.asarray(data, self.dtype).reshape(self.rows, self.width)
+        self.dev = DeviceArray.from_numpy(img)
+        self.ptr = self.dev.ptr + self.offset * self.dtype.itemsize
+
+    def window(self):
+        return self.dev.numpy()[self.offset:].reshape(self.rows, self.ld)[:, :self.width].copy()
+
+
+class _Plain:
+    """The default `frames` of the op wrappers: exact allocations, no guards (tests pass the module tests/strided.py instead)."""
+
+    @staticmethod
+    def framed(data, ld=None, dtype=None, offset=0):
+        data = np.asarray(data)
+        d2 = data.reshape(1, -1) if data.ndim == 1 else data.reshape(data.shape[0], -1)
+        return _PlainBuffer(d2.shape[0], d2.shape[1], ld, dtype or data.dtype, offset, d2)
+
+    @staticmethod
+    def out_frame(rows, width, ld=None, dtype=np.float32, offset=0, preload=None):
+        return _PlainBuffer(rows, width, ld, dtype, offset, preload)
+
+
+def _note(sink, **frames):
+    """Hand the output frames of a call to the caller's dict (before the launch: a refused call leaves them to be inspected)."""
+    if sink is not None:
+        sink.update({k: v for k, v in frames.items() if v is not None})
+
+
 def gemm(A, W, bias, residual=None, epilogue=EPI_BIAS, tile: int = 0, group_m: int = 0, workspace: bool = False,
          handover_test: int = 0, stats: Optional[dict] = None, ln=None, row_stats: Optional[dict] = None,
-         arith: int = ARITH_F32, w_split: bool = False) -> np.ndarray:
+         arith: int = ARITH_F32, w_split: bool = False, lda: Optional[int] = None, ldw: Optional[int] = None,
+         ldr: Optional[int] = None, ldc: Optional[int] = None, in_place: bool = False, offset: int = 0, frames=None,
+         out: Optional[dict] = None) -> np.ndarray:
     """C = epilogue(A . W^T + bias) through vithip_gemm_f32 (tile / group_m: per-call tuning fields, 0 = auto;
     workspace: lend the scratch that enables the helper pieces of the persistent walk; handover_test: see
     vithip_gemm_args; stats: receives the hand-over counters {"taken", "recomputed"} of the launch;
@@ -337,35 +378,49 @@ def gemm(A, W, bias, residual=None, epilogue=EPI_BIAS, tile: int = 0, group_m: i
     row_stats: a dict that receives "rows" = vithip_gemm_args.stats_out [M][2] and "in_epilogue" = what
     vithip_gemm_f32_stats_in_epilogue said; its key "scratch" (default True) lends stats_partials);
     arith: ARITH_F32 (fp32 MFMA) or ARITH_SPLIT3 (the three-piece split on the bf16 matrix pipe; tiles 0, 9, 10, 11);
-    w_split: make W's pre-split image on the device (split3_weights_device) and pass it as vithip_gemm_args.w_split."""
+    w_split: make W's pre-split image on the device (split3_weights_device) and pass it as vithip_gemm_args.w_split;
+    lda / ldw / ldr / ldc: leading dimensions (default: dense); in_place: C is the residual's buffer (ldr = ldc);
+    offset: C, bias and the residual start this many floats past a 16-byte boundary;
+    frames: who allocates the operands (default: exact buffers; tests/strided.py: guarded, sentinel-filled frames);
+    out: a dict that receives the output frames "C", "stats" and "partials"."""
     A, W, bias = _as_f32(A), _as_f32(W), _as_f32(bias)
     M, K = A.shape
     N = W.shape[0]
-    dA, dW, db = DeviceArray.from_numpy(A), DeviceArray.from_numpy(W), DeviceArray.from_numpy(bias)
-    dC = DeviceArray((M, N))
-    dR = DeviceArray.from_numpy(_as_f32(residual)) if residual is not None else None
+    F = frames or _Plain
+    dA, dW, db = F.framed(A, lda), F.framed(W, ldw), F.framed(bias, offset=offset)
+    if in_place:
+        dC = dR = F.out_frame(M, N, ldc, offset=offset, preload=_as_f32(residual))
+    else:
+        dC = F.out_frame(M, N, ldc, offset=offset)
+        dR = F.framed(_as_f32(residual), ldr, offset=offset) if residual is not None else None
     ws = gemm_workspace() if workspace else None
     dRows = DeviceArray.from_numpy(_as_f32(ln[0])) if ln is not None else None
     dCs = DeviceArray.from_numpy(_as_f32(ln[1])) if ln is not None and ln[1] is not None else None   # None: centred weights
-    dSt = DeviceArray((M, 2)) if row_stats is not None else None
-    dPart = DeviceArray((max(N // 64, 1), M, 2)) if row_stats is not None and row_stats.get("scratch", True) else None
-    args = CGemmArgs(dA.ptr, K, dW.ptr, K, db.ptr, dR.ptr if dR else None, N, dC.ptr, N, M, N, K, epilogue, tile, group_m, ws,
-                     handover_test, dRows.ptr if dRows else None, dCs.ptr if dCs else None, dSt.ptr if dSt else None,
-                     dPart.ptr if dPart else None, arith)
-    dImg = split3_weights_device(dW, N, K) if w_split else None
+    dSt = F.out_frame(M, 2) if row_stats is not None else None
+    dPart = F.out_frame(max(N // 64, 1) * M, 2) if row_stats is not None and row_stats.get("scratch", True) else None
+    _note(out, C=dC, stats=dSt, partials=dPart)
+    args = CGemmArgs(dA.ptr, dA.ld, dW.ptr, dW.ld, db.ptr, dR.ptr if dR else None, dR.ld if dR else N, dC.ptr, dC.ld, M, N, K, epilogue,
+                     tile, group_m, ws, handover_test, dRows.ptr if dRows else None, dCs.ptr if dCs else None,
+                     dSt.ptr if dSt else None, dPart.ptr if dPart else None, arith)
+    dImg = split3_weights_device(dW, N, K, dW.ld) if w_split else None
     if dImg is not None:
         args.w_split = dImg.ptr
     if row_stats is not None:
         row_stats["in_epilogue"] = int(lib().vithip_gemm_f32_stats_in_epilogue(C.byref(args)))
-    hip_check(lib().vithip_gemm_f32(None, C.byref(args)), "vithip_gemm_f32")
-    out = dC.numpy()
+    try:
+        hip_check(lib().vithip_gemm_f32(None, C.byref(args)), "vithip_gemm_f32")
+    except VitError:
+        if ws:
+            lib().vithip_gemm_f32_workspace_destroy(C.c_void_p(ws))
+        raise
+    result = dC.window()
     if row_stats is not None:
-        row_stats["rows"] = dSt.numpy()
+        row_stats["rows"] = dSt.window()
     if ws:
         if stats is not None:
             stats.update(gemm_workspace_stats(ws))
         lib().vithip_gemm_f32_workspace_destroy(C.c_void_p(ws))
-    return out
+    return result
 
 
 def split3_weights_device(dW: "DeviceArray", N: int, K: int, ldw: Optional[int] = None) -> "DeviceArray":
@@ -460,32 +515,39 @@ def f32_to_bf16_device(x: np.ndarray) -> np.ndarray:
 
 
 def gemm_bf16(A_bits, W_bits, bias, residual=None, epilogue=BF16_EPI_BF16, variant: int = 0, ln_rows=None, ln_colsum=None,
-              ln_producer: bool = False):
+              ln_producer: bool = False, lda: Optional[int] = None, ldw: Optional[int] = None, ldr: Optional[int] = None,
+              ldc: Optional[int] = None, in_place: bool = False, ldx16: Optional[int] = None, frames=None, out: Optional[dict] = None):
     """vithip_gemm_bf16 on bf16 bit patterns; returns bf16 bits (uint16) or fp32 for the residual epilogue.
     variant: 0 auto, 1 two-stage kernel, 2 ping-pong kernel (fails for K < 128).
     LayerNorm fold: ln_rows [M][2] + ln_colsum [N] make this the consumer; ln_producer (residual epilogue) also returns
-    (C, bf16(C) bits, row partials [strips][M][2])."""
+    (C, bf16(C) bits, row partials [strips][M][2]).
+    lda / ldw / ldr / ldc / ldx16, in_place, frames, out: as for gemm(); the output frames are "C", "x16" and "partials"."""
     L = lib()
     L.vithip_gemm_bf16.argtypes = [C.c_void_p, C.POINTER(CGemmBf16Args)]
     M, K = A_bits.shape
     N = W_bits.shape[0]
-    dA, dW = DeviceArray.from_numpy(np.ascontiguousarray(A_bits, np.uint16)), DeviceArray.from_numpy(np.ascontiguousarray(W_bits, np.uint16))
-    db = DeviceArray.from_numpy(_as_f32(bias))
+    F = frames or _Plain
+    dA, dW = F.framed(np.ascontiguousarray(A_bits, np.uint16), lda), F.framed(np.ascontiguousarray(W_bits, np.uint16), ldw)
+    db = F.framed(_as_f32(bias))
     out_f32 = epilogue == BF16_EPI_F32_RESIDUAL
-    dC = DeviceArray((M, N), np.float32 if out_f32 else np.uint16)
-    dR = DeviceArray.from_numpy(_as_f32(residual)) if residual is not None else None
+    if in_place:
+        dC = dR = F.out_frame(M, N, ldc, np.float32, preload=_as_f32(residual))
+    else:
+        dC = F.out_frame(M, N, ldc, np.float32 if out_f32 else np.uint16)
+        dR = F.framed(_as_f32(residual), ldr) if residual is not None else None
     dRows = DeviceArray.from_numpy(_as_f32(ln_rows)) if ln_rows is not None else None
     dCs = DeviceArray.from_numpy(_as_f32(ln_colsum)) if ln_colsum is not None else None
     strips = ln_strips(N)
-    dX16 = DeviceArray((M, N), np.uint16) if ln_producer else None
-    dPart = DeviceArray((strips, M, 2), np.float32) if ln_producer else None
-    args = CGemmBf16Args(dA.ptr, K, dW.ptr, K, db.ptr, dR.ptr if dR else None, N, dC.ptr, N, M, N, K, epilogue,
-                         variant, dRows.ptr if dRows else None, dCs.ptr if dCs else None,
-                         dX16.ptr if dX16 else None, N, dPart.ptr if dPart else None)
+    dX16 = F.out_frame(M, N, ldx16, np.uint16) if ln_producer else None
+    dPart = F.out_frame(strips * M, 2) if ln_producer else None
+    _note(out, C=dC, x16=dX16, partials=dPart)
+    args = CGemmBf16Args(dA.ptr, dA.ld, dW.ptr, dW.ld, db.ptr, dR.ptr if dR else None, dR.ld if dR else N, dC.ptr, dC.ld, M, N, K,
+                         epilogue, variant, dRows.ptr if dRows else None, dCs.ptr if dCs else None,
+                         dX16.ptr if dX16 else None, dX16.ld if dX16 else N, dPart.ptr if dPart else None)
     hip_check(L.vithip_gemm_bf16(None, C.byref(args)), "vithip_gemm_bf16")
     if ln_producer:
-        return dC.numpy(), dX16.numpy(), dPart.numpy()
-    return dC.numpy()
+        return dC.window(), dX16.window(), dPart.window().reshape(strips, M, 2)
+    return dC.window()
 
 
 def ln_strips(N: int) -> int:
@@ -504,15 +566,18 @@ def ln_fold_weights(W, bias, gamma, beta):
     return dWf.numpy(), dcs.numpy(), dbf.numpy()
 
 
-def rowstats_bf16(x):
-    """vithip_rowstats_bf16 -> (bf16(x) bits, rows [M][2] = (rstd, mean * rstd))."""
+def rowstats_bf16(x, ldx: Optional[int] = None, ldx16: Optional[int] = None, frames=None, out: Optional[dict] = None):
+    """vithip_rowstats_bf16 -> (bf16(x) bits, rows [M][2] = (rstd, mean * rstd)).  ldx / ldx16, frames, out: as for gemm(); the
+    output frames are "x16" and "rows"."""
     x = _as_f32(x)
     rows, dim = x.shape
     L = lib()
     L.vithip_rowstats_bf16.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
-    dx, d16, dr = DeviceArray.from_numpy(x), DeviceArray((rows, dim), np.uint16), DeviceArray((rows, 2), np.float32)
-    hip_check(L.vithip_rowstats_bf16(None, dx.ptr, dim, d16.ptr, dim, dr.ptr, rows, dim), "vithip_rowstats_bf16")
-    return d16.numpy(), dr.numpy()
+    F = frames or _Plain
+    dx, d16, dr = F.framed(x, ldx), F.out_frame(rows, dim, ldx16, np.uint16), F.out_frame(rows, 2)
+    _note(out, x16=d16, rows=dr)
+    hip_check(L.vithip_rowstats_bf16(None, dx.ptr, dx.ld, d16.ptr, d16.ld, dr.ptr, rows, dim), "vithip_rowstats_bf16")
+    return d16.window(), dr.window()
 
 
 def rowstats_finalize(partials, dim: int):
@@ -526,18 +591,21 @@ def rowstats_finalize(partials, dim: int):
     return dr.numpy()
 
 
-def layernorm_bf16out(x, gamma, beta) -> np.ndarray:
-    """vithip_layernorm_f32_bf16out -> bf16 bits."""
+def layernorm_bf16out(x, gamma, beta, ldx: Optional[int] = None, ldy: Optional[int] = None, frames=None,
+                      out: Optional[dict] = None) -> np.ndarray:
+    """vithip_layernorm_f32_bf16out -> bf16 bits.  ldx / ldy, frames, out: as for gemm(); the output frame is "y"."""
     x = _as_f32(x)
     rows, dim = x.shape
     L = lib()
     L.vithip_layernorm_f32_bf16out.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                                C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-    dx, dg, db = DeviceArray.from_numpy(x), DeviceArray.from_numpy(_as_f32(gamma)), DeviceArray.from_numpy(_as_f32(beta))
-    dy = DeviceArray((rows, dim), np.uint16)
-    hip_check(L.vithip_layernorm_f32_bf16out(None, dx.ptr, dim, dy.ptr, dim, dg.ptr, db.ptr, rows, dim),
+    F = frames or _Plain
+    dx, dg, db = F.framed(x, ldx), F.framed(_as_f32(gamma)), F.framed(_as_f32(beta))
+    dy = F.out_frame(rows, dim, ldy, np.uint16)
+    _note(out, y=dy)
+    hip_check(L.vithip_layernorm_f32_bf16out(None, dx.ptr, dx.ld, dy.ptr, dy.ld, dg.ptr, db.ptr, rows, dim),
               "vithip_layernorm_f32_bf16out")
-    return dy.numpy()
+    return dy.window()
 
 
 QSCALE = 0.18033688011112042  # VITHIP_QSCALE: (1/sqrt(64)) * log2(e)
@@ -561,13 +629,17 @@ def attention_bf16io(qkv_bits, n_images: int, tokens: int, heads: int, f32math: 
     return do.numpy()
 
 
-def layernorm(x, gamma, beta) -> np.ndarray:
+def layernorm(x, gamma, beta, ldx: Optional[int] = None, ldy: Optional[int] = None, frames=None,
+              out: Optional[dict] = None) -> np.ndarray:
+    """vithip_layernorm_f32.  ldx / ldy, frames, out: as for gemm(); the output frame is "y"."""
     x = _as_f32(x)
     rows, dim = x.shape
-    dx, dg, db = DeviceArray.from_numpy(x), DeviceArray.from_numpy(_as_f32(gamma)), DeviceArray.from_numpy(_as_f32(beta))
-    dy = DeviceArray((rows, dim))
-    hip_check(lib().vithip_layernorm_f32(None, dx.ptr, dim, dy.ptr, dim, dg.ptr, db.ptr, rows, dim), "vithip_layernorm_f32")
-    return dy.numpy()
+    F = frames or _Plain
+    dx, dg, db = F.framed(x, ldx), F.framed(_as_f32(gamma)), F.framed(_as_f32(beta))
+    dy = F.out_frame(rows, dim, ldy)
+    _note(out, y=dy)
+    hip_check(lib().vithip_layernorm_f32(None, dx.ptr, dx.ld, dy.ptr, dy.ld, dg.ptr, db.ptr, rows, dim), "vithip_layernorm_f32")
+    return dy.window()
 
 
 def layernorm_pool(x, gamma, beta, images: int, tokens: int, first_tok: int = 1, l2_normalize: bool = False) -> np.ndarray:
@@ -620,15 +692,39 @@ def ln_fold_weights_f32_centered(W, bias, gamma, beta):
     return dWf.numpy(), dcs.numpy(), dbf.numpy()
 
 
-def rowstats_f32(x) -> np.ndarray:
-    """vithip_rowstats_f32 -> [rows][2] = (rstd, mean)."""
+def rowstats_f32(x, ldx: Optional[int] = None, frames=None, out: Optional[dict] = None) -> np.ndarray:
+    """vithip_rowstats_f32 -> [rows][2] = (rstd, mean).  ldx, frames, out: as for gemm(); the output frame is "rows"."""
     x = _as_f32(x)
     rows, dim = x.shape
     L = lib()
     L.vithip_rowstats_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
-    dx, dr = DeviceArray.from_numpy(x), DeviceArray((rows, 2))
-    hip_check(L.vithip_rowstats_f32(None, dx.ptr, dim, dr.ptr, rows, dim), "vithip_rowstats_f32")
-    return dr.numpy()
+    F = frames or _Plain
+    dx, dr = F.framed(x, ldx), F.out_frame(rows, 2)
+    _note(out, rows=dr)
+    hip_check(L.vithip_rowstats_f32(None, dx.ptr, dx.ld, dr.ptr, rows, dim), "vithip_rowstats_f32")
+    return dr.window()
+
+
+def gather_rows(src, src_stride: Optional[int] = None, dst_stride: Optional[int] = None, frames=None, out: Optional[dict] = None,
+                rows: Optional[int] = None, width: Optional[int] = None, null: str = "") -> np.ndarray:
+    """vithip_gather_rows_f32: dst[r][0..width) = src[r * src_stride .. + width).  src [rows][width] is placed with the leading
+    dimension src_stride (its other columns are padding); the output frame is "dst".  rows / width: the counts passed (default:
+    src's shape); null: "src" or "dst" passes that pointer as NULL (refusal tests)."""
+    src = _as_f32(src)
+    L = lib()
+    L.vithip_gather_rows_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int]
+    F = frames or _Plain
+    ds, dd = F.framed(src), F.out_frame(src.shape[0], src.shape[1])
+    if src_stride is not None and src_stride >= src.shape[1]:
+        ds = F.framed(src, src_stride)
+    if dst_stride is not None and dst_stride >= src.shape[1]:
+        dd = F.out_frame(src.shape[0], src.shape[1], dst_stride)
+    _note(out, dst=dd)
+    hip_check(L.vithip_gather_rows_f32(None, None if null == "src" else ds.ptr, ds.ld if src_stride is None else src_stride,
+                                       None if null == "dst" else dd.ptr, dd.ld if dst_stride is None else dst_stride,
+                                       src.shape[0] if rows is None else rows, src.shape[1] if width is None else width),
+              "vithip_gather_rows_f32")
+    return dd.window()
 
 
 def attention(qkv, n_images: int, tokens: int, heads: int) -> np.ndarray:
@@ -641,16 +737,35 @@ def attention(qkv, n_images: int, tokens: int, heads: int) -> np.ndarray:
     return do.numpy()
 
 
-def attention_rows(qkv, n_images: int, tokens: int, heads: int, q_rows: int, fill: float = 0.0) -> np.ndarray:
-    """vithip_attention_f32_rows: the output buffer is pre-filled with `fill` to show which rows are written."""
+def attention_rows(qkv, n_images: int, tokens: int, heads: int, q_rows: int, fill: float = 0.0, frames=None,
+                   out: Optional[dict] = None) -> np.ndarray:
+    """vithip_attention_f32_rows: the output buffer is pre-filled with `fill` to show which rows are written (with `frames`: the
+    frame's sentinel instead, and `out` receives the frame "out")."""
     qkv = _as_f32(qkv)
     D = heads * 64
     L = lib()
     L.vithip_attention_f32_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
-    dq = DeviceArray.from_numpy(qkv)
-    do = DeviceArray.from_numpy(np.full((n_images * tokens, D), fill, np.float32))
+    if frames is None:
+        dq, do = _Plain.framed(qkv), _Plain.out_frame(n_images * tokens, D, preload=np.full((n_images * tokens, D), fill, np.float32))
+    else:
+        dq, do = frames.framed(qkv), frames.out_frame(n_images * tokens, D)
+    _note(out, out=do)
     hip_check(L.vithip_attention_f32_rows(None, dq.ptr, do.ptr, n_images, tokens, heads, q_rows), "vithip_attention_f32_rows")
-    return do.numpy()
+    return do.window()
+
+
+def attention_bf16io_rows(qkv_bits, n_images: int, tokens: int, heads: int, q_rows: int, q_scaled: bool = False, frames=None,
+                          out: Optional[dict] = None) -> np.ndarray:
+    """vithip_attention_bf16io_rows or, q_scaled, vithip_attention_bf16io_qscaled -> bf16 bits [n * tokens][heads * 64]; rows
+    q_rows.. of every image keep what the buffer held (zeros, or the sentinel of `frames`); `out` receives the frame "out"."""
+    F = frames or _Plain
+    name = "vithip_attention_bf16io_qscaled" if q_scaled else "vithip_attention_bf16io_rows"
+    fn = getattr(lib(), name)
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+    dq, do = F.framed(np.ascontiguousarray(qkv_bits, np.uint16)), F.out_frame(n_images * tokens, heads * 64, dtype=np.uint16)
+    _note(out, out=do)
+    hip_check(fn(None, dq.ptr, do.ptr, n_images, tokens, heads, q_rows), name)
+    return do.window()
 
 
 def _cls_attention(fn_name, dq, n_images, tokens, heads, head_mean, ld_out, fill, extra=()):
@@ -721,16 +836,22 @@ def patch_embed_bf16(cfg: ModelConfig, images, conv_w, conv_b, cls, pos, implici
     return dx.numpy().reshape(n, cfg.tokens, cfg.embed_dim)
 
 
-def softmax_top1(logits):
+def softmax_top1(logits, ld_logits: Optional[int] = None, ld_probs: Optional[int] = None, want_label: bool = True,
+                 want_prob: bool = True, frames=None, out: Optional[dict] = None):
+    """vithip_softmax_top1_f32 -> (probs, labels, top-1 probabilities).  ld_logits / ld_probs, frames, out: as for gemm(); the
+    output frames are "probs", "label" and "prob".  want_label / want_prob False: that pointer is passed as NULL (its frame is
+    still made, and must stay untouched); the value returned for it is None."""
     logits = _as_f32(logits)
     rows, classes = logits.shape
-    dl = DeviceArray.from_numpy(logits)
-    dp = DeviceArray((rows, classes))
-    dlab = DeviceArray((rows,), np.int32)
-    dpr = DeviceArray((rows,))
-    hip_check(lib().vithip_softmax_top1_f32(None, dl.ptr, classes, dp.ptr, classes, dlab.ptr, dpr.ptr, rows, classes),
-              "vithip_softmax_top1_f32")
-    return dp.numpy(), dlab.numpy(), dpr.numpy()
+    F = frames or _Plain
+    dl = F.framed(logits, ld_logits)
+    dp = F.out_frame(rows, classes, ld_probs)
+    dlab = F.out_frame(rows, 1, dtype=np.int32)
+    dpr = F.out_frame(rows, 1)
+    _note(out, probs=dp, label=dlab, prob=dpr)
+    hip_check(lib().vithip_softmax_top1_f32(None, dl.ptr, dl.ld, dp.ptr, dp.ld, dlab.ptr if want_label else None,
+                                            dpr.ptr if want_prob else None, rows, classes), "vithip_softmax_top1_f32")
+    return dp.window(), dlab.window().reshape(rows) if want_label else None, dpr.window().reshape(rows) if want_prob else None
 
 
 def _norm_consts(mean, std, chans: int):

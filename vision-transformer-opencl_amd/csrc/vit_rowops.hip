@@ -160,7 +160,8 @@ template <typename OUT>
 int layernorm_dispatch(vithip_stream_t stream, const float *x, size_t ldx, OUT *y, size_t ldy, const float *gamma,
                        const float *beta, int rows, int dim) {
     if (!x || !y || !gamma || !beta || rows <= 0 || dim <= 0) return static_cast<int>(hipErrorInvalidValue);
-    if (dim % 4 || dim > 64 * 4 * LN_MAX_VEC || ldx % 4 || ldy % 4) return static_cast<int>(hipErrorInvalidValue);
+    if (dim % 4 || dim > 64 * 4 * LN_MAX_VEC || ldx % 4 || ldy % 4 || ldx < (size_t)dim || ldy < (size_t)dim)
+        return static_cast<int>(hipErrorInvalidValue);
     if ((reinterpret_cast<size_t>(x) & 15) || (reinterpret_cast<size_t>(y) & 15) ||
         (reinterpret_cast<size_t>(gamma) & 15) || (reinterpret_cast<size_t>(beta) & 15))
         return static_cast<int>(hipErrorInvalidValue);
