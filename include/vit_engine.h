@@ -282,6 +282,63 @@ int vit_engine_cls_attention_host_images(vit_engine *e, const vit_image_u8 *imag
                                          const vit_attention_spec *spec, float *const *out);
 
 /*
+ * Intermediate-layer outputs instead of probabilities: the residual stream behind chosen encoder layers (DINOv2
+ * get_intermediate_layers, timm forward_intermediates).  With x_l the fp32 residual stream behind encoder layer l (T = tokens rows of
+ * D = embed_dim per image; layer 0 is the first layer, so x_l is what the oracle calls stages[l + 1]), f = the FINAL LayerNorm
+ * (encoder_ln, as DINOv2 norm=True applies it to every tapped layer) when norm = 1 and the identity when norm = 0, P = T - 1 and
+ * K = num_layers, the row of image i is K blocks, block j for layer layers[j]:
+ *
+ *   VIT_TAP_CLS      block = f(x_l[i][0])                        [n][K][D]        = [n][K*D], the operand of a linear probe
+ *   VIT_TAP_TOKENS   block[t] = f(x_l[i][t]), class row first    [n][K][T][D]
+ *   VIT_TAP_PATCHES  block[t-1] = f(x_l[i][t]), t = 1..P         [n][K][P][D]
+ *   VIT_TAP_MAP      block[d][t-1] = f(x_l[i][t])[d]             [n][K][D][g][g]  = [n][K*D][g][g], g = img_size / patch_size, patches in
+ *                                                                                 raster order: the channel concatenation of a dense head
+ *
+ * Rows are fp32 for both engine dtypes.  Behind each tapped layer every lane launches vithip_tap_f32 (vit_hip_kernels.h) once, on
+ * its own stream, from its rows of x into its images' blocks; normalised values are the bits vithip_layernorm_f32 gives, so a tap of
+ * the last layer with norm = 1 is the bits of the matching features call (TOKENS, CLS), MAP is the transpose of PATCHES bit for bit,
+ * and block j does not depend on which other layers are tapped.  Layers behind the deepest tap are not launched, nor the final
+ * LayerNorm of the forward, the head or the softmax.  An image's row has the same bits whatever prune_last_layer and lanes are set to,
+ * wherever the image sits in whatever batch and whichever of the six calls delivers the same pixels.  No atomics.
+ *
+ * The six calls mirror the six features calls: the same images, chunking, lanes, stream rules and blocking behaviour; `out` takes the
+ * place of the feature rows, rows of vit_engine_intermediate_row_elems() floats (device: one [n][row] array; host: caller-allocated
+ * rows out[i]).  The host calls share the pinned output staging of the features calls and its rule: it is (re)allocated for the widest
+ * row seen so far (K * T * D floats for TOKENS); if that does not fit, the call returns VIT_ERR_NOMEM, the staging is back at its
+ * classes-sized start and the engine stays usable.
+ * prune_last_layer engines: the last layer runs pruned only when it is tapped and kind = VIT_TAP_CLS (same bits as unpruned); any other
+ * kind that taps it runs it unpruned -- for that call only, not an error.  use_graph: the graph is keyed on the whole spec, so two calls
+ * that differ in one layer never replay each other's graph; the _images calls run eagerly.  Profiling: the tap launches (one per lane,
+ * chunk and tapped layer) are accounted to VIT_STAGE_LN.  vit_engine_read_logits() after an intermediate call is an error: nothing wrote
+ * logits.
+ * VIT_ERR_ARG (the engine stays usable, nothing was enqueued): NULL pointers, n <= 0, an unknown kind, norm other than 0 / 1, num_layers
+ * outside 1..VIT_MAX_TAPS, a layer outside 0..depth-1 or not above the one before it (the message names the entry), reserved != 0, MAP
+ * when img_size / patch_size does not give a square grid of T - 1 patches, and what the matching forward refuses.
+ */
+enum { VIT_TAP_CLS = 0, VIT_TAP_TOKENS = 1, VIT_TAP_PATCHES = 2, VIT_TAP_MAP = 3 };
+#define VIT_MAX_TAPS 32
+typedef struct {
+    int kind;                  /* VIT_TAP_* */
+    int norm;                  /* 1: the final LayerNorm (encoder_ln) applied to every tap, as DINOv2 norm=True; 0: the raw residual stream */
+    int num_layers;            /* 1..VIT_MAX_TAPS */
+    int layers[VIT_MAX_TAPS];  /* strictly increasing, 0 <= l < depth: the output of encoder layer l (oracle stages[l + 1]) */
+    int reserved;              /* must be 0 */
+} vit_intermediate_spec;
+
+/* floats per output row: K * D, K * T * D, K * P * D or K * D * P; 0 on a bad spec */
+size_t vit_engine_intermediate_row_elems(const vit_engine *e, const vit_intermediate_spec *spec);
+int vit_engine_intermediate_device(vit_engine *e, const float *d_images, int n, const vit_intermediate_spec *spec, float *d_out, void *stream);
+int vit_engine_intermediate_host(vit_engine *e, const float *const *images, int n, const vit_intermediate_spec *spec, float *const *out);
+int vit_engine_intermediate_device_u8(vit_engine *e, const unsigned char *d_images, int n, const float *mean, const float *std,
+                                      const vit_intermediate_spec *spec, float *d_out, void *stream);
+int vit_engine_intermediate_host_u8(vit_engine *e, const unsigned char *const *images, int n, const float *mean, const float *std,
+                                    const vit_intermediate_spec *spec, float *const *out);
+int vit_engine_intermediate_device_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp,
+                                          const vit_intermediate_spec *spec, float *d_out, void *stream);
+int vit_engine_intermediate_host_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp,
+                                        const vit_intermediate_spec *spec, float *const *out);
+
+/*
  * The fp32 GEMMs' helper-piece hand-over (csrc/vit_gemm_persistent.hip) since the last call, summed over the lanes: tiles whose
  * first K-steps came from a helper workgroup / tiles whose owner found no piece when it looked and computed all of it.  The
  * second number is lost time, never a wrong result (nothing in the hand-over waits or gives up).  Synchronises the device.

@@ -398,6 +398,30 @@ int vithip_cls_attention_f32(vithip_stream_t stream, const float *qkv, size_t q_
 int vithip_cls_attention_bf16(vithip_stream_t stream, const unsigned short *qkv, size_t q_row_stride, float *out, size_t ld_out,
                               int n_images, int tokens, int heads, int head_mean, int q_scaled);
 
+/*
+ * Rows of the residual stream as an output (csrc/vit_tap.hip): per image the class row, every token, the patch tokens, or the patch
+ * tokens as a channel-major map.  x: [images * tokens] rows of dim floats, ldx floats from one row to the next; r(t) = row
+ * i * tokens + t of x for image i; f = the LayerNorm of vithip_layernorm_f32 with gamma / beta, or the identity when both are NULL;
+ * P = tokens - 1.  Written at out + i * out_image_stride:
+ *   VITHIP_TAP_CLS      [dim]          = f(r(0))
+ *   VITHIP_TAP_TOKENS   [tokens][dim]  = f(r(0..tokens-1)), class row first
+ *   VITHIP_TAP_PATCHES  [P][dim]       = f(r(1..P))
+ *   VITHIP_TAP_MAP      [dim][P]       element [d][t - 1] = f(r(t))[d]: [dim][g][g] for a square grid of g x g patches, raster order
+ * Normalised values are the bits vithip_layernorm_f32 gives for the same row (one device function holds the arithmetic of both,
+ * csrc/vit_layernorm_row.hpp), unnormalised ones the bits of x; MAP is the exact transpose of PATCHES.  Only the block of each
+ * image is written: the floats from its end up to out_image_stride are not touched, so several launches can fill one output row
+ * side by side.  MAP goes through an LDS tile and stores runs of up to 32 tokens per channel (16 above dim 1024), as 16 bytes per lane when P % 4 == 0
+ * and as 4 bytes per lane otherwise; any P >= 1 is correct.  No atomics; results do not depend on the grid.
+ * hipErrorInvalidValue, nothing launched: x or out NULL, exactly one of gamma / beta NULL, a non-positive size, an unknown layout,
+ * PATCHES or MAP with tokens < 2, dim % 4 != 0 or dim > 2048, ldx < dim or ldx % 4 != 0, out_image_stride % 4 != 0 or smaller than the
+ * block, x / out / gamma / beta not 16-byte aligned, images * tokens >= 2^31.
+ */
+enum { VITHIP_TAP_CLS = 0, VITHIP_TAP_TOKENS = 1, VITHIP_TAP_PATCHES = 2, VITHIP_TAP_MAP = 3 };
+int vithip_tap_f32(vithip_stream_t s, const float *x, size_t ldx,          /* [images * tokens] rows, ldx >= dim */
+                   float *out, size_t out_image_stride,                     /* floats from one image's block to the next */
+                   const float *gamma, const float *beta,                   /* both NULL: copy the rows unnormalised */
+                   int images, int tokens, int dim, int layout);
+
 #ifdef __cplusplus
 }
 #endif

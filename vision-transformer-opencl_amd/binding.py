@@ -70,6 +70,16 @@ class CAttentionSpec(C.Structure):  # vit_attention_spec
 ATTENTION_KINDS = {"heads": 0, "head_mean": 1}  # VIT_ATTN_*
 
 
+VIT_MAX_TAPS = 32
+
+
+class CIntermediateSpec(C.Structure):  # vit_intermediate_spec
+    _fields_ = [("kind", C.c_int), ("norm", C.c_int), ("num_layers", C.c_int), ("layers", C.c_int * VIT_MAX_TAPS), ("reserved", C.c_int)]
+
+
+TAP_KINDS = {"cls": 0, "tokens": 1, "patches": 2, "map": 3}  # VIT_TAP_* / VITHIP_TAP_*
+
+
 class CImageU8(C.Structure):  # vit_image_u8 / vithip_image_u8: one decoded image, [height][width][chans] uint8
     _fields_ = [("pixels", C.c_void_p), ("height", C.c_int), ("width", C.c_int)]
 
@@ -88,6 +98,22 @@ def attention_spec(kind, reserved: int = 0) -> CAttentionSpec:
     """kind: "heads" | "head_mean" (or a raw VIT_ATTN_* integer, passed through unchecked for the C side to judge)."""
     k = ATTENTION_KINDS[kind] if isinstance(kind, str) else int(kind)
     return CAttentionSpec(k, int(reserved))
+
+
+def intermediate_spec(layers, kind="cls", norm=True, depth: Optional[int] = None, reserved: int = 0) -> CIntermediateSpec:
+    """layers: the encoder layers to tap, in increasing order; with `depth` given, negative entries count from the last layer as
+    Python indices do (-1 = depth - 1) -- resolved here, the C side takes 0..depth-1 only.  kind: "cls" | "tokens" | "patches" | "map"
+    (or a raw VIT_TAP_* integer); everything else is passed through unchecked for the C side to judge: num_layers is len(layers) even
+    where that exceeds the VIT_MAX_TAPS entries the struct holds."""
+    k = TAP_KINDS[kind] if isinstance(kind, str) else int(kind)
+    ls = [int(l) for l in (layers if hasattr(layers, "__iter__") else [layers])]
+    if depth is not None:
+        ls = [l + depth if l < 0 else l for l in ls]
+    spec = CIntermediateSpec(k, int(norm), len(ls))
+    for j, l in enumerate(ls[:VIT_MAX_TAPS]):
+        spec.layers[j] = l
+    spec.reserved = int(reserved)
+    return spec
 
 
 class CStageTimes(C.Structure):
@@ -178,7 +204,8 @@ def lib() -> C.CDLL:
         L.vit_engine_load_weights.argtypes = [C.c_void_p, C.POINTER(CNetwork), C.c_int]
         # the forward surface, output kind x place x input kind: (engine, images, n) + normalisation + spec + destination
         norm = {"": [], "_u8": [f32p, f32p], "_images": [C.POINTER(CPreproc)]}
-        spec = {"forward": [], "features": [C.POINTER(CFeatureSpec)], "cls_attention": [C.POINTER(CAttentionSpec)]}
+        spec = {"forward": [], "features": [C.POINTER(CFeatureSpec)], "cls_attention": [C.POINTER(CAttentionSpec)],
+                "intermediate": [C.POINTER(CIntermediateSpec)]}
         for out in spec:
             for place in ("host", "device"):
                 for kind in norm:
@@ -208,6 +235,10 @@ def lib() -> C.CDLL:
             L.vit_engine_attention_row_elems.argtypes = [C.c_void_p, C.POINTER(CAttentionSpec)]
             L.vithip_cls_attention_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_int] * 4
             L.vithip_cls_attention_bf16.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_int] * 5
+        if hasattr(L, "vit_engine_intermediate_device"):  # an earlier build (see above) has no intermediate calls
+            L.vit_engine_intermediate_row_elems.restype = C.c_size_t
+            L.vit_engine_intermediate_row_elems.argtypes = [C.c_void_p, C.POINTER(CIntermediateSpec)]
+            L.vithip_tap_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p] + [C.c_int] * 4
         L.vit_engine_read_logits.argtypes = [C.c_void_p, f32p, C.c_int]
         L.vit_engine_sync.argtypes = [C.c_void_p]
         L.vit_engine_get_stage_times.argtypes = [C.c_void_p, C.POINTER(CStageTimes)]
@@ -642,6 +673,36 @@ def layernorm(x, gamma, beta, ldx: Optional[int] = None, ldy: Optional[int] = No
     return dy.window()
 
 
+def tap_block(images: int, tokens: int, dim: int, layout) -> tuple:
+    """Shape of one image's block of vithip_tap_f32 for `layout` ("cls" | "tokens" | "patches" | "map" or a VITHIP_TAP_* integer)."""
+    k = TAP_KINDS[layout] if isinstance(layout, str) else int(layout)
+    return {0: (dim,), 1: (tokens, dim), 2: (tokens - 1, dim), 3: (dim, tokens - 1)}[k]
+
+
+def tap(x, gamma, beta, images: int, tokens: int, layout, ldx: Optional[int] = None, out_image_stride: Optional[int] = None,
+        frames=None, out: Optional[dict] = None, d_out: Optional[int] = None) -> Optional[np.ndarray]:
+    """vithip_tap_f32: x [images * tokens][dim] -> per image the block of `layout`; gamma = beta = None copies the rows unnormalised.
+    ldx, frames, out: as for layernorm(); the output frame "out" has one row per image, a block wide, out_image_stride apart.
+    d_out: a raw device address to write to instead (out_image_stride is then required); nothing is returned."""
+    x = _as_f32(x)
+    rows, dim = x.shape
+    k = TAP_KINDS[layout] if isinstance(layout, str) else int(layout)
+    F = frames or _Plain
+    dx = F.framed(x, ldx)
+    dg = F.framed(_as_f32(gamma)) if gamma is not None else None
+    db = F.framed(_as_f32(beta)) if beta is not None else None
+    args = (dg.ptr if dg else None, db.ptr if db else None, images, tokens, dim, k)
+    if d_out is not None:
+        hip_check(lib().vithip_tap_f32(None, dx.ptr, dx.ld, d_out, out_image_stride, *args), "vithip_tap_f32")
+        hip_check(lib().vithip_device_sync(), "sync")
+        return None
+    shape = tap_block(images, tokens, dim, k)
+    do = F.out_frame(images, int(np.prod(shape)), out_image_stride)
+    _note(out, out=do)
+    hip_check(lib().vithip_tap_f32(None, dx.ptr, dx.ld, do.ptr, do.ld, *args), "vithip_tap_f32")
+    return do.window().reshape((images,) + shape)
+
+
 def layernorm_pool(x, gamma, beta, images: int, tokens: int, first_tok: int = 1, l2_normalize: bool = False) -> np.ndarray:
     """vithip_layernorm_pool_f32: x [images * tokens][ld >= dim] (dim = len(gamma)) -> [images][dim], the mean over tokens
     first_tok.. of the LayerNorm rows, optionally L2-normalised.  Columns dim.. of x are padding (ldx > dim)."""
@@ -977,19 +1038,22 @@ class Engine:
         L.vit_engine_copy_weights.argtypes = [C.c_void_p, C.c_void_p]
         self._check(L.vit_engine_copy_weights(self._h, other._h), "vit_engine_copy_weights")
 
-    # ---- the forward surface: vit_engine_<out>_<place><inp>, out "forward" | "features" | "cls_attention", inp "" | "_u8" | "_images" ----
-    def _call_args(self, out, inp, kind, l2_normalize, mean, std, resize_shorter) -> list:
+    # ---- the forward surface: vit_engine_<out>_<place><inp>, out "forward" | "features" | "cls_attention" | "intermediate", inp "" | "_u8" | "_images" ----
+    def _call_args(self, out, inp, kind, l2_normalize, mean, std, resize_shorter, layers=None, norm=True) -> list:
         """What lies between n and the destination in the C call: the normalisation of the input kind, the spec of the output kind."""
         args = []
         if inp == "_u8":
             args += _norm_consts(mean, std, self.cfg.in_chans)
         elif inp == "_images":
             args.append(C.byref(preproc_params(resize_shorter, mean, std, self.cfg.in_chans)))
-        if out != "forward":
+        if out == "intermediate":
+            args.append(C.byref(intermediate_spec(layers, kind, norm, self.cfg.depth)))
+        elif out != "forward":
             args.append(C.byref(feature_spec(kind, l2_normalize) if out == "features" else attention_spec(kind)))
         return args
 
-    def _host(self, out, inp, images, kind=None, l2_normalize=False, mean=None, std=None, resize_shorter=None) -> np.ndarray:
+    def _host(self, out, inp, images, kind=None, l2_normalize=False, mean=None, std=None, resize_shorter=None, layers=None,
+              norm=True) -> np.ndarray:
         """A host-path call: per-image pointers (or records) in, per-image rows of a new array out."""
         if inp == "_images":
             keep, in_ptrs = host_image_records(images, self.cfg.in_chans)
@@ -1000,9 +1064,11 @@ class Engine:
             keep = _as_f32(images)
             in_ptrs = (f32p * len(keep))(*[im.ctypes.data_as(f32p) for im in keep])
         n = len(keep)
-        args = self._call_args(out, inp, kind, l2_normalize, mean, std, resize_shorter)
+        args = self._call_args(out, inp, kind, l2_normalize, mean, std, resize_shorter, layers, norm)
         if out == "forward":
             shape = (n, self.cfg.num_classes)
+        elif out == "intermediate":
+            shape = self.intermediate_shape(n, layers, kind, norm)
         else:
             shape = self.feature_shape(n, kind, l2_normalize) if out == "features" else self.attention_shape(n, kind)
         rows = np.empty(shape, np.float32)
@@ -1012,12 +1078,12 @@ class Engine:
         return rows
 
     def _device(self, out, inp, images, n, dst, kind=None, l2_normalize=False, mean=None, std=None, resize_shorter=None, d_label=0,
-                d_prob=0, stream=0) -> None:
+                d_prob=0, stream=0, layers=None, norm=True) -> None:
         """A device-path call: raw HBM addresses (images: a list of (ptr, H, W) for "_images"), async on `stream`."""
         if inp == "_images":
             images = image_records(images)
             n = len(images)
-        args = self._call_args(out, inp, kind, l2_normalize, mean, std, resize_shorter)
+        args = self._call_args(out, inp, kind, l2_normalize, mean, std, resize_shorter, layers, norm)
         top1 = [d_label or None, d_prob or None] if out == "forward" else []
         name = f"vit_engine_{out}_device{inp}"
         self._check(getattr(lib(), name)(self._h, images, n, *args, dst, *top1, stream or None), name)
@@ -1123,6 +1189,48 @@ class Engine:
                                     stream: int = 0) -> None:
         """Device-resident path: images = a list of (ptr, H, W) in HBM, d_out [n][row] fp32; async on `stream`."""
         self._device("cls_attention", "_images", images, None, d_out, kind, mean=mean, std=std, resize_shorter=resize_shorter, stream=stream)
+
+    # ---- intermediate layers (vit_engine_intermediate_*): the residual stream behind `layers`, kind "cls" | "tokens" | "patches" | "map" ----
+    def intermediate_shape(self, n: int, layers, kind="cls", norm=True) -> tuple:
+        """Shape of the rows n images give, K = len(layers): (n, K, D) for "cls", (n, K, T, D) for "tokens", (n, K, T - 1, D) for
+        "patches", (n, K, D, g, g) for "map"."""
+        spec = intermediate_spec(layers, kind, norm, self.cfg.depth)
+        elems = lib().vit_engine_intermediate_row_elems(self._h, C.byref(spec))
+        if elems == 0:
+            raise VitError(f"bad intermediate spec (layers={layers!r}, kind={kind!r}, norm={norm!r})")
+        D, T, K = self.cfg.embed_dim, self.cfg.tokens, spec.num_layers
+        g = self.cfg.img_size // self.cfg.patch_size
+        shape = {0: (n, K, D), 1: (n, K, T, D), 2: (n, K, T - 1, D), 3: (n, K, D, g, g)}[spec.kind]
+        assert int(np.prod(shape[1:])) == elems, (shape, elems)
+        return shape
+
+    def intermediate(self, images: np.ndarray, layers, kind="cls", norm=True) -> np.ndarray:
+        """Host path: per-image pointers in, per-image rows out: a block per tapped layer (negative layers count from the last)."""
+        return self._host("intermediate", "", images, kind, layers=layers, norm=norm)
+
+    def intermediate_u8(self, images: np.ndarray, layers, kind="cls", norm=True, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
+        """Host path from 8-bit pixels [n][S][S][C] (see forward_u8)."""
+        return self._host("intermediate", "_u8", images, kind, mean=mean, std=std, layers=layers, norm=norm)
+
+    def intermediate_images(self, images, resize_shorter: int, layers, kind="cls", norm=True, mean=IMAGENET_MEAN,
+                            std=IMAGENET_STD) -> np.ndarray:
+        """Host path: a list of [H][W][C] uint8 arrays of any sizes in, intermediate rows out (see intermediate)."""
+        return self._host("intermediate", "_images", images, kind, mean=mean, std=std, resize_shorter=resize_shorter, layers=layers, norm=norm)
+
+    def intermediate_device(self, d_images: int, n: int, d_out: int, layers, kind="cls", norm=True, stream: int = 0) -> None:
+        """Device-resident path: raw HBM addresses, d_out [n][row] fp32, async on `stream`."""
+        self._device("intermediate", "", d_images, n, d_out, kind, stream=stream, layers=layers, norm=norm)
+
+    def intermediate_device_u8(self, d_images: int, n: int, d_out: int, layers, kind="cls", norm=True, mean=IMAGENET_MEAN,
+                               std=IMAGENET_STD, stream: int = 0) -> None:
+        """Device-resident path from 8-bit pixels [n][S][S][C] in HBM (raw addresses), async on `stream`."""
+        self._device("intermediate", "_u8", d_images, n, d_out, kind, mean=mean, std=std, stream=stream, layers=layers, norm=norm)
+
+    def intermediate_device_images(self, images, d_out: int, resize_shorter: int, layers, kind="cls", norm=True, mean=IMAGENET_MEAN,
+                                   std=IMAGENET_STD, stream: int = 0) -> None:
+        """Device-resident path: images = a list of (ptr, H, W) in HBM, d_out [n][row] fp32; async on `stream`."""
+        self._device("intermediate", "_images", images, None, d_out, kind, mean=mean, std=std, resize_shorter=resize_shorter, stream=stream,
+                     layers=layers, norm=norm)
 
     def pool_scratch_layout(self, nb: int) -> list:
         """vit_engine_debug_pool_scratch for every lane of a MEAN chunk of nb images: per lane a dict of byte ranges inside the y

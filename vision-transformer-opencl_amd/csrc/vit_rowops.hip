@@ -5,24 +5,22 @@
 //   y = (x - mean) * inv_std * gamma + beta.
 // One 64-lane wave per row: the row is read once as float4 (dim <= 2048 stays in registers),
 // the two sums are reduced with wave shuffles, no LDS and no barrier.  HBM-bound by design.
+// The row's arithmetic is csrc/vit_layernorm_row.hpp, which csrc/vit_tap.hip shares bit for bit.
 //
 // softmax_top1 follows ViT_seq.c:304-324 and the argmax of Main.c:62-70 (first maximum wins).
 #include <hip/hip_runtime.h>
 
 #include "vit_hip_kernels.h"
+#include "vit_layernorm_row.hpp"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using vit_ln::f32x4;
+using vit_ln::wave_sum;
 
 constexpr int LN_THREADS = 256;
-constexpr int LN_MAX_VEC = 8;  // float4 per lane: dim <= 64*4*8 = 2048
+constexpr int LN_MAX_VEC = vit_ln::MAX_VEC;  // float4 per lane: dim <= 64*4*8 = 2048
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
@@ -45,21 +43,8 @@ __global__ __launch_bounds__(LN_THREADS) void layernorm_f32_kernel(const float *
     for (int row = wave; row < rows; row += nwaves) {
         const float *src = x + (size_t)row * ldx;
         f32x4 v[NVEC];
-        float s = 0.0f, ss = 0.0f;
-#pragma unroll
-        for (int i = 0; i < NVEC; ++i) {
-            const int c = (i * 64 + lane) * 4;
-            if (c < dim) {
-                v[i] = *reinterpret_cast<const f32x4 *>(src + c);
-                s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-                ss += (v[i][0] * v[i][0] + v[i][1] * v[i][1]) + (v[i][2] * v[i][2] + v[i][3] * v[i][3]);
-            }
-        }
-        s = wave_sum(s);
-        ss = wave_sum(ss);
-        const float mean = s / (float)dim;
-        const float var = ss / (float)dim - mean * mean;
-        const float inv_std = 1.0f / sqrtf((float)((double)var + 1e-6));
+        float mean, inv_std;
+        vit_ln::row_stats<NVEC>(src, dim, lane, v, mean, inv_std);
         OUT *dst = y + (size_t)row * ldy;
 #pragma unroll
         for (int i = 0; i < NVEC; ++i) {
@@ -67,9 +52,7 @@ __global__ __launch_bounds__(LN_THREADS) void layernorm_f32_kernel(const float *
             if (c < dim) {
                 const f32x4 g = *reinterpret_cast<const f32x4 *>(gamma + c);
                 const f32x4 b = *reinterpret_cast<const f32x4 *>(beta + c);
-                f32x4 o;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = (v[i][j] - mean) * inv_std * g[j] + b[j];
+                const f32x4 o = vit_ln::row_affine(v[i], mean, inv_std, g, b);
                 if constexpr (sizeof(OUT) == 4) {
                     *reinterpret_cast<f32x4 *>(dst + c) = o;
                 } else {

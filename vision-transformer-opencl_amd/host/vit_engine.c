@@ -9,7 +9,8 @@
  *             LN2 -> fc1 GEMM (+bias +GELU) -> fc2 GEMM (+bias +residual, in place) }
  *   LN on the class-token rows only -> head GEMM -> softmax + top-1
  *   (a features call ends instead in the final LN of the rows it returns, or in the fused LN + mean over the patch tokens;
- *    an attention call stops the last layer behind its QKV GEMM and stores the class token's softmax row)
+ *    an attention call stops the last layer behind its QKV GEMM and stores the class token's softmax row;
+ *    an intermediate call copies rows of x out behind the layers it taps and stops behind the deepest of them)
  *
  * Weights are validated and uploaded once (the reference re-uploads them per op per image,
  * e.g. ViT_opencl.c:136,630-631); activations never leave HBM between stages (the reference
@@ -49,19 +50,23 @@ _Static_assert(sizeof(vit_image_u8) == sizeof(vithip_image_u8) && offsetof(vit_i
                "the engine hands its callers' records to the kernel launcher as they are");
 
 /* What a forward writes, besides where: probabilities [n][classes] and the optional top-1 records, the embedding rows `spec`
- * asks for (stage_features), or the class token's attention over the tokens in the last layer (stage_cls_attention), [n][out_row_elems()].
+ * asks for (stage_features), the class token's attention over the tokens in the last layer (stage_cls_attention), or the residual
+ * stream behind the layers `tap` names (stage_tap), [n][out_row_elems()].
  * Zero-filled before use: the graph cache compares it bytewise.  The pointers are those of the call's (or chunk's) first image. */
-enum { VIT_OUT_PROBS = 0, VIT_OUT_FEATURES = 1, VIT_OUT_ATTENTION = 2 };
+enum { VIT_OUT_PROBS = 0, VIT_OUT_FEATURES = 1, VIT_OUT_ATTENTION = 2, VIT_OUT_INTERMEDIATE = 3 };
 typedef struct {
     int kind;              /* VIT_OUT_PROBS: dst = probabilities, label / prob = top-1 (may be NULL); _FEATURES: dst = the rows of spec;
-                            * _ATTENTION: dst = the rows of attn_kind */
+                            * _ATTENTION: dst = the rows of attn_kind; _INTERMEDIATE: dst = the rows of tap */
     vit_feature_spec spec;
     int attn_kind;         /* VIT_ATTN_* (0 otherwise); with it the struct has no padding, which a bytewise comparison would read */
+    vit_intermediate_spec tap; /* _INTERMEDIATE: the checked spec, layers[num_layers..] zero (all zero otherwise) */
     float *dst;
     int *label;
     float *prob;
 } vit_output;
-_Static_assert(sizeof(vit_output) == 4 * sizeof(int) + 3 * sizeof(void *), "vit_output must stay free of padding: the graph cache compares it bytewise");
+_Static_assert(sizeof(vit_output) == 4 * sizeof(int) + sizeof(vit_intermediate_spec) + 3 * sizeof(void *) &&
+                   sizeof(vit_intermediate_spec) == (4 + VIT_MAX_TAPS) * sizeof(int) && sizeof(vit_intermediate_spec) % sizeof(void *) == 0,
+               "vit_output must stay free of padding: the graph cache compares it bytewise");
 
 struct vit_engine {
     vit_config cfg;
@@ -785,7 +790,7 @@ static int row_stats(chunk_ctx *c, const vit_lane *ln, size_t ldx, float *pairs,
  *   fold    the LayerNorm fold (vit_hip_kernels.h, "LayerNorm folding"): in_proj and fc1 read the raw rows (x, or its bf16 copy)
  *           with the gamma/beta-folded operands (fold_ln_weights) and a pair per row; a LayerNorm becomes a statistics pass,
  *           or nothing where the residual GEMM in front has left the pairs.  The bf16 Q rows carry the scores' exponent factor.
- *   pruned  prune_last_layer, for chunks whose output reads the class rows only (chunk_ctx.pruned: probabilities and CLS features;
+ *   pruned  prune_last_layer, for chunks whose output reads the class rows only (chunk_ctx.pruned: probabilities, CLS features and CLS taps;
  *           MEAN and TOKENS run the layer in full): K and V of every token, everything else for the class rows only.  The class rows of a [n*T][w]
  *           buffer are rows 0, T, 2T, ... = a matrix with leading dimension T*w, which every operator takes as it is.
  *   qkv_only  attention calls: the last layer ends behind in_proj, with K of every token and Q of (at least) the class rows in the
@@ -924,7 +929,13 @@ static size_t row_elems(const vit_engine *e, int out_kind, int kind) {
     if (out_kind == VIT_OUT_ATTENTION) return (kind == VIT_ATTN_HEADS ? (size_t)e->cfg.num_heads : 1) * (size_t)e->tokens;
     return (kind == VIT_FEAT_TOKENS ? (size_t)e->tokens : 1) * (size_t)e->cfg.embed_dim;
 }
+/* ... and of one tapped layer's block of an intermediate row; `kind` is the VIT_TAP_* of a valid spec */
+static size_t tap_block_elems(const vit_engine *e, int kind) {
+    const size_t T = (size_t)e->tokens;
+    return (kind == VIT_TAP_CLS ? 1 : kind == VIT_TAP_TOKENS ? T : T - 1) * (size_t)e->cfg.embed_dim;
+}
 static size_t out_row_elems(const vit_engine *e, const vit_output *out) {
+    if (out->kind == VIT_OUT_INTERMEDIATE) return (size_t)out->tap.num_layers * tap_block_elems(e, out->tap.kind);
     return row_elems(e, out->kind, out->kind == VIT_OUT_ATTENTION ? out->attn_kind : out->spec.kind);
 }
 
@@ -988,6 +999,24 @@ static int stage_cls_attention(chunk_ctx *c, const vit_output *out) {
     return VIT_OK;
 }
 
+/* Block j of an intermediate call's rows: the residual stream as encoder_layer(layers[j]) has just left it, one vithip_tap_f32 launch
+ * per lane, from the lane's rows of x into block j of its images' rows -- an image's row is the call's blocks side by side, so the
+ * image stride of every launch is the whole row.  norm: through the final LayerNorm's gamma and beta.  A pruned last layer (CLS only)
+ * has updated the class rows of x alone, which is all that CLS reads. */
+static int stage_tap(chunk_ctx *c, const vit_output *out, int j) {
+    vit_engine *e = c->e;
+    float **fw = e->w + 4 + VIT_WEIGHTS_PER_LAYER * e->cfg.depth;
+    const size_t row = out_row_elems(e, out), block = tap_block_elems(e, out->tap.kind);
+    for (int k = 0; k < c->L; ++k) {
+        const vit_lane *ln = &c->lane[k];
+        HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
+        HIP_TRY(e, vithip_tap_f32(ln->s, ln->x, (size_t)c->D, out->dst + (size_t)ln->off * row + (size_t)j * block, row,
+                                  out->tap.norm ? fw[0] : NULL, out->tap.norm ? fw[1] : NULL, ln->n, c->T, c->D, out->tap.kind));
+        HIP_TRY(e, stage_end(e, ln->s));
+    }
+    return VIT_OK;
+}
+
 /* The chunk's context for nb images written as `out` says: dimensions, whether the last layer is pruned, and the lanes -- their
  * images, streams and rows of the activation buffers.  Launches nothing. */
 static void chunk_setup(vit_engine *e, vithip_stream_t s, int nb, const vit_output *out, chunk_ctx *c) {
@@ -996,7 +1025,8 @@ static void chunk_setup(vit_engine *e, vithip_stream_t s, int nb, const vit_outp
     c->T = e->tokens; c->D = cfg->embed_dim; c->H = cfg->hidden_dim; c->NC = cfg->num_classes;
     c->L = e->opt.lanes > VIT_MAX_LANES ? VIT_MAX_LANES : e->opt.lanes;
     if (c->L < 1 || nb < 2 * c->L) c->L = 1;
-    c->pruned = e->opt.prune_last_layer && c->T <= 224 && !(out->kind == VIT_OUT_FEATURES && out->spec.kind != VIT_FEAT_CLS);
+    c->pruned = e->opt.prune_last_layer && c->T <= 224 && !(out->kind == VIT_OUT_FEATURES && out->spec.kind != VIT_FEAT_CLS) &&
+                !(out->kind == VIT_OUT_INTERMEDIATE && out->tap.kind != VIT_TAP_CLS);
     c->qkv_only = out->kind == VIT_OUT_ATTENTION;
     const int bf16 = e->opt.dtype == VIT_DTYPE_BF16;
     const size_t B = (size_t)e->opt.max_batch, T = (size_t)c->T, D = (size_t)c->D, H = (size_t)c->H;
@@ -1045,10 +1075,17 @@ static int forward_chunk(vit_engine *e, vithip_stream_t s, const void *d_images,
         for (int j = 1; j < c->L; ++j) HIP_TRY(e, vithip_stream_wait_event(c->lane[j].s, e->ev_fork));
     }
     RUN(stage_embed(c, d_images, in, f32_stage));
-    for (int l = 0; l < cfg->depth; ++l) RUN(encoder_layer(c, l));
-    if (out->kind == VIT_OUT_FEATURES) RUN(stage_features(c, out));
-    else if (out->kind == VIT_OUT_ATTENTION) RUN(stage_cls_attention(c, out));
-    else RUN(stage_head(c, out->dst, out->label, out->prob));
+    if (out->kind == VIT_OUT_INTERMEDIATE) { /* the layers up to the deepest tap, a block of the rows behind each tapped one; nothing else */
+        for (int l = 0, j = 0; j < out->tap.num_layers; ++l) {
+            RUN(encoder_layer(c, l));
+            if (l == out->tap.layers[j]) RUN(stage_tap(c, out, j++));
+        }
+    } else {
+        for (int l = 0; l < cfg->depth; ++l) RUN(encoder_layer(c, l));
+        if (out->kind == VIT_OUT_FEATURES) RUN(stage_features(c, out));
+        else if (out->kind == VIT_OUT_ATTENTION) RUN(stage_cls_attention(c, out));
+        else RUN(stage_head(c, out->dst, out->label, out->prob));
+    }
     for (int j = 1; j < c->L; ++j) { /* join */
         HIP_TRY(e, vithip_event_record(e->ev_join[j - 1], c->lane[j].s));
         HIP_TRY(e, vithip_stream_wait_event(s, e->ev_join[j - 1]));
@@ -1102,8 +1139,8 @@ static int input_images(vit_engine *e, const char *who, const vit_image_u8 *imag
     return VIT_OK;
 }
 
-/* The kinds of output descriptor: probabilities + top-1 (the forwards), the checked feature spec of a features call, or the checked
- * attention spec of an attention call. */
+/* The kinds of output descriptor: probabilities + top-1 (the forwards), the checked feature spec of a features call, the checked
+ * attention spec of an attention call, or the checked intermediate spec of an intermediate call. */
 static vit_output output_probs(float *probs, int *label, float *prob) {
     vit_output out;
     memset(&out, 0, sizeof(out));
@@ -1150,6 +1187,48 @@ static int output_attention(vit_engine *e, const char *who, const vit_attention_
     out->attn_kind = spec->kind;
     out->dst = dst;
     return VIT_OK;
+}
+
+/* The intermediate spec, checked against the model: NULL, or what is wrong as a format for (who, arg[0], arg[1]). */
+static const char *intermediate_spec_fault(const vit_engine *e, const vit_intermediate_spec *spec, int arg[2]) {
+    arg[0] = arg[1] = 0;
+    if (!spec) return "%s: the intermediate spec is required";
+    arg[0] = spec->kind;
+    if (spec->kind != VIT_TAP_CLS && spec->kind != VIT_TAP_TOKENS && spec->kind != VIT_TAP_PATCHES && spec->kind != VIT_TAP_MAP)
+        return "%s: unknown intermediate kind %d";
+    arg[0] = spec->norm;
+    if (spec->norm != 0 && spec->norm != 1) return "%s: norm must be 0 or 1 (got %d)";
+    arg[0] = spec->num_layers; arg[1] = VIT_MAX_TAPS;
+    if (spec->num_layers < 1 || spec->num_layers > VIT_MAX_TAPS) return "%s: num_layers = %d must be 1..%d";
+    arg[0] = spec->reserved;
+    if (spec->reserved != 0) return "%s: vit_intermediate_spec.reserved must be 0 (got %d)";
+    for (int j = 0; j < spec->num_layers; ++j) {
+        arg[0] = j; arg[1] = spec->layers[j];
+        if (spec->layers[j] < 0 || spec->layers[j] >= e->cfg.depth) return "%s: layers[%d] = %d is not a layer of the model";
+        if (j && spec->layers[j] <= spec->layers[j - 1]) return "%s: layers[%d] = %d is not above the entry before it (strictly increasing)";
+    }
+    const int g = e->cfg.img_size / e->cfg.patch_size;
+    arg[0] = g; arg[1] = e->tokens - 1;
+    if (spec->kind == VIT_TAP_MAP && (g < 1 || g * g != e->tokens - 1)) return "%s: MAP needs a square grid of patches: (img_size / patch_size = %d)^2 is not the model's %d";
+    if (spec->kind == VIT_TAP_PATCHES && e->tokens < 2) return "%s: PATCHES needs at least one patch token";
+    return NULL;
+}
+
+static int output_intermediate(vit_engine *e, const char *who, const vit_intermediate_spec *spec, float *dst, vit_output *out) {
+    int arg[2];
+    const char *fault = intermediate_spec_fault(e, spec, arg);
+    memset(out, 0, sizeof(*out)); /* the unused layers[] entries stay zero: the graph key compares the whole spec */
+    if (fault) return fail(e, VIT_ERR_ARG, fault, who, arg[0], arg[1]);
+    out->kind = VIT_OUT_INTERMEDIATE;
+    out->tap.kind = spec->kind; out->tap.norm = spec->norm; out->tap.num_layers = spec->num_layers;
+    for (int j = 0; j < spec->num_layers; ++j) out->tap.layers[j] = spec->layers[j];
+    out->dst = dst;
+    return VIT_OK;
+}
+
+size_t vit_engine_intermediate_row_elems(const vit_engine *e, const vit_intermediate_spec *spec) {
+    int arg[2];
+    return e && !intermediate_spec_fault(e, spec, arg) ? (size_t)spec->num_layers * tap_block_elems(e, spec->kind) : 0;
 }
 
 size_t vit_engine_attention_row_elems(const vit_engine *e, const vit_attention_spec *spec) {
@@ -1332,7 +1411,7 @@ static int cut_pieces(vit_engine *e, const char *who, int kind, const void *imag
     return VIT_OK;
 }
 
-/* The output staging holds max_batch rows of out_row_cap floats: classes at first, grown to the widest feature or attention row a
+/* The output staging holds max_batch rows of out_row_cap floats: classes at first, grown to the widest feature, attention or intermediate row a
  * host call has asked for (TOKENS: tokens * embed_dim; HEADS: heads * tokens).  Growing waits for everything in flight, frees both slots and allocates them again; if
  * that fails the call fails with VIT_ERR_NOMEM and the staging is back at its classes-sized start. */
 static int alloc_out_stage(vit_engine *e, size_t bytes) { /* both slots, freed first; a HIP error code, with both slots freed again */
@@ -1481,7 +1560,7 @@ typedef struct {
     const float *mean, *std; /* VIT_IN_U8 */
     const vit_preproc *pp;  /* VIT_IN_IMAGES */
     int out_kind;           /* VIT_OUT_* */
-    const void *spec;       /* vit_feature_spec (VIT_OUT_FEATURES) or vit_attention_spec (VIT_OUT_ATTENTION) */
+    const void *spec;       /* vit_feature_spec (VIT_OUT_FEATURES), vit_attention_spec (_ATTENTION) or vit_intermediate_spec (_INTERMEDIATE) */
     float *dst;             /* VIT_AT_DEVICE: [n][row] */
     float *const *rows;     /* VIT_AT_HOST: a row per image */
     int *label;             /* VIT_AT_DEVICE, VIT_OUT_PROBS: top-1 (may be NULL) */
@@ -1506,6 +1585,7 @@ static int run_call(vit_engine *e, const vit_call *c) {
     if (rc) return rc;
     if (c->out_kind == VIT_OUT_FEATURES) rc = output_features(e, c->who, (const vit_feature_spec *)c->spec, c->dst, &out);
     else if (c->out_kind == VIT_OUT_ATTENTION) rc = output_attention(e, c->who, (const vit_attention_spec *)c->spec, c->dst, &out);
+    else if (c->out_kind == VIT_OUT_INTERMEDIATE) rc = output_intermediate(e, c->who, (const vit_intermediate_spec *)c->spec, c->dst, &out);
     else out = output_probs(c->dst, c->label, c->prob);
     if (rc) return rc;
     return host ? forward_host_in(e, c->who, c->images, &in, c->n, &out, c->rows) : forward_device_in(e, c->images, &in, c->n, &out, c->stream);
@@ -1568,6 +1648,25 @@ int vit_engine_cls_attention_device_images(vit_engine *e, const vit_image_u8 *im
                                     .stream = stream});
 }
 
+int vit_engine_intermediate_device(vit_engine *e, const float *d_images, int n, const vit_intermediate_spec *spec, float *d_out, void *stream) {
+    return run_call(e, &(vit_call){.who = "intermediate_device", .place = VIT_AT_DEVICE, .in_kind = VIT_IN_F32, .images = d_images,
+                                    .n = n, .out_kind = VIT_OUT_INTERMEDIATE, .spec = spec, .dst = d_out, .stream = stream});
+}
+
+int vit_engine_intermediate_device_u8(vit_engine *e, const unsigned char *d_images, int n, const float *mean, const float *std,
+                                      const vit_intermediate_spec *spec, float *d_out, void *stream) {
+    return run_call(e, &(vit_call){.who = "intermediate_device_u8", .place = VIT_AT_DEVICE, .in_kind = VIT_IN_U8, .images = d_images,
+                                    .n = n, .mean = mean, .std = std, .out_kind = VIT_OUT_INTERMEDIATE, .spec = spec, .dst = d_out,
+                                    .stream = stream});
+}
+
+int vit_engine_intermediate_device_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp,
+                                          const vit_intermediate_spec *spec, float *d_out, void *stream) {
+    return run_call(e, &(vit_call){.who = "intermediate_device_images", .place = VIT_AT_DEVICE, .in_kind = VIT_IN_IMAGES,
+                                    .images = images, .n = n, .pp = pp, .out_kind = VIT_OUT_INTERMEDIATE, .spec = spec, .dst = d_out,
+                                    .stream = stream});
+}
+
 int vit_engine_forward_host(vit_engine *e, const float *const *images, int n, float *const *probs) {
     return run_call(e, &(vit_call){.who = "forward_host", .place = VIT_AT_HOST, .in_kind = VIT_IN_F32, .images = images, .n = n,
                                     .out_kind = VIT_OUT_PROBS, .rows = probs});
@@ -1616,6 +1715,23 @@ int vit_engine_cls_attention_host_images(vit_engine *e, const vit_image_u8 *imag
                                          const vit_attention_spec *spec, float *const *out) {
     return run_call(e, &(vit_call){.who = "cls_attention_host_images", .place = VIT_AT_HOST, .in_kind = VIT_IN_IMAGES, .images = images,
                                     .n = n, .pp = pp, .out_kind = VIT_OUT_ATTENTION, .spec = spec, .rows = out});
+}
+
+int vit_engine_intermediate_host(vit_engine *e, const float *const *images, int n, const vit_intermediate_spec *spec, float *const *out) {
+    return run_call(e, &(vit_call){.who = "intermediate_host", .place = VIT_AT_HOST, .in_kind = VIT_IN_F32, .images = images, .n = n,
+                                    .out_kind = VIT_OUT_INTERMEDIATE, .spec = spec, .rows = out});
+}
+
+int vit_engine_intermediate_host_u8(vit_engine *e, const unsigned char *const *images, int n, const float *mean, const float *std,
+                                    const vit_intermediate_spec *spec, float *const *out) {
+    return run_call(e, &(vit_call){.who = "intermediate_host_u8", .place = VIT_AT_HOST, .in_kind = VIT_IN_U8, .images = images, .n = n,
+                                    .mean = mean, .std = std, .out_kind = VIT_OUT_INTERMEDIATE, .spec = spec, .rows = out});
+}
+
+int vit_engine_intermediate_host_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp,
+                                        const vit_intermediate_spec *spec, float *const *out) {
+    return run_call(e, &(vit_call){.who = "intermediate_host_images", .place = VIT_AT_HOST, .in_kind = VIT_IN_IMAGES, .images = images,
+                                    .n = n, .pp = pp, .out_kind = VIT_OUT_INTERMEDIATE, .spec = spec, .rows = out});
 }
 
 int vit_engine_handover_stats(vit_engine *e, long *taken, long *recomputed) {
