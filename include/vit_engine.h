@@ -116,6 +116,44 @@ int vit_engine_copy_weights(vit_engine *dst, vit_engine *src);
 int vit_engine_read_weight_image(vit_engine *e, vit_weight_image *img);
 
 /*
+ * A checkpoint at another input size than the one it was trained at: cfg.img_size is the size the engine runs at, and the one tensor
+ * tied to it -- tensor 3, the position embedding [tokens][D] -- is resampled on the device from the checkpoint's own grid
+ * (vithip_pos_resample_f32 in vit_hip_kernels.h states the arithmetic; DESIGN.md the agreement with PyTorch).  Row 0, the class
+ * token's embedding, is copied; the g_src x g_src patch part becomes g_dst x g_dst, g = img_size / patch_size.
+ *   VIT_POS_BICUBIC     torch.nn.functional.interpolate(mode="bicubic", align_corners=False): DINO, DeiT, DINOv2 given a size
+ *   VIT_POS_BICUBIC_AA  the same with antialias=True: the default of timm's resample_abs_pos_embed
+ * Everything else of the forward does not depend on the token count and runs on the same kernels at every size.
+ *
+ * vit_engine_load_weights_resampled: vit_engine_load_weights, except that tensor 3 must have ((src_img_size / patch_size)^2 + 1) * D
+ * floats.  The other tensors take the usual path (one image, one upload); the checkpoint's position embedding goes to a temporary
+ * device buffer and is resampled into the resident tensor 3 in front of the LayerNorm fold and the weight split; the temporary is
+ * freed before the call returns.  fp32 and bf16 engines alike: the position embedding is an fp32 tensor in both.  The resampled
+ * values are NOT rounded to 1e-6: that rounding is the file loader's and the checkpoint has been through it.
+ * With src_img_size == cfg.img_size nothing is resampled and the result is vit_engine_load_weights bit for bit.
+ * vit_engine_read_weight_image afterwards gives an image for the engine's own cfg that holds the resampled tensor, so the cache file
+ * of vit_io.h can store a checkpoint at its serving resolution.
+ * Every check comes before anything is changed: a refused call leaves the resident weights, and a captured graph, in working order.
+ * VIT_ERR_ARG: NULL rs, reserved != 0, an unknown mode, src_img_size not a positive multiple of cfg.patch_size, a grid of more than
+ * 256 patches per side.  VIT_ERR_WEIGHTS: what vit_engine_load_weights refuses, and a tensor 3 of the wrong size (the message names
+ * both grids and both sizes).
+ *
+ * vit_engine_copy_weights_resampled: vit_engine_copy_weights between engines of the same dtype whose configurations are equal in every
+ * field except img_size (anything else: VIT_ERR_ARG).  Every tensor but the position embedding is copied device to device (the
+ * layouts differ behind tensor 3: two ranges and the bf16 section); dst's position embedding is resampled from the one RESIDENT in
+ * src, then the fold and the split are recomputed.  The source is whatever src holds: if src was itself loaded or copied with a
+ * resampling, this is a second resampling of already resampled values, not one from the checkpoint's grid -- copy from the engine
+ * that holds the checkpoint's own embedding.  With equal img_size it is vit_engine_copy_weights (the mode is still checked).
+ */
+enum { VIT_POS_BICUBIC = 0, VIT_POS_BICUBIC_AA = 1 };
+typedef struct {
+    int src_img_size;   /* the checkpoint's input size; its grid is src_img_size / cfg.patch_size */
+    int mode;           /* VIT_POS_* */
+    int reserved;       /* must be 0 */
+} vit_pos_resample;
+int vit_engine_load_weights_resampled(vit_engine *e, const Network *weights, int count, const vit_pos_resample *rs);
+int vit_engine_copy_weights_resampled(vit_engine *dst, vit_engine *src, int mode);
+
+/*
  * Device-resident forward: d_images [n][C][S][S] fp32 -> d_probs [n][classes] fp32, both in
  * HBM, n arbitrary (processed in chunks of max_batch).  Asynchronous on `stream`
  * (a hipStream_t; NULL = the engine's own stream, then call vit_engine_sync()).

@@ -422,6 +422,42 @@ int vithip_tap_f32(vithip_stream_t s, const float *x, size_t ldx,          /* [i
                    const float *gamma, const float *beta,                   /* both NULL: copy the rows unnormalised */
                    int images, int tokens, int dim, int layout);
 
+/*
+ * A position embedding resampled to another patch grid (csrc/vit_pos_resample.hip), so that a checkpoint runs at another input size.
+ * src [1 + g_src^2][dim] -> dst [1 + g_dst^2][dim], device pointers: row 0, the class token's embedding, is copied bit for bit; rows
+ * 1.. are a g_src x g_src raster of dim-vectors, resampled separably to g_dst x g_dst.
+ *   VITHIP_POS_BICUBIC     torch.nn.functional.interpolate(mode="bicubic", align_corners=False, antialias=False): DINO, DeiT, DINOv2
+ *   VITHIP_POS_BICUBIC_AA  the same with antialias=True: the default of timm's resample_abs_pos_embed
+ * An axis (in = source extent, out = destination extent) is a table: per output index o a first source index, a tap count and fp32
+ * weights; the source index of tap k is clamp(first + k, 0, in - 1).  Every operation below is one IEEE fp32 operation, none
+ * contracted into a fused multiply-add; scale = (float)in / (float)out.
+ *   BICUBIC, A = -0.75f:   r = scale * ((float)o + 0.5f) - 0.5f;  b = floorf(r);  t = r - b;  first = (int)b - 1;  4 taps
+ *                          cub1(x) = ((A + 2) * x - (A + 3)) * x * x + 1;   cub2(x) = ((A * x - 5 * A) * x + 8 * A) * x - 4 * A
+ *                          w = { cub2(t + 1), cub1(t), cub1(1 - t), cub2(2 - t) }      (a clamped index may repeat: no taps are merged)
+ *   BICUBIC_AA, A = -0.5f: support = scale >= 1 ? 2.0f * scale : 2.0f;  inv = scale >= 1 ? 1.0f / scale : 1.0f;
+ *                          center = scale * ((float)o + 0.5f);  first = max((int)(center - support + 0.5f), 0);
+ *                          count = min((int)(center + support + 0.5f), in) - first;
+ *                          w[j] = filter(((float)(j + first) - center + 0.5f) * inv), with x := |x|,
+ *                          filter(x) = ((A + 2) * x - (A + 3)) * x * x + 1 for x < 1, (((x - 5) * x + 8) * x - 4) * A for x < 2, else 0;
+ *                          w[j] /= w[0] + w[1] + ... (added in index order)
+ * With (iy_j, wy_j) the taps of output row y and (ix_i, wx_i) those of output column x:
+ *     row_j[d] = sum_i wx_i * src[iy_j][ix_i][d];   dst[y][x][d] = sum_j wy_j * row_j[d]
+ * each accumulator starting at 0.0f, taps in order, multiply then add, each rounded.  tests/pos_resample_model.py restates all of it
+ * in numpy; it agrees with PyTorch's CPU kernels to a few 1e-6 on values in [-1, 1] (their summation order is another).
+ *
+ * vithip_pos_resample_table: the table of one axis, on the host (no device needed).  first / count: out ints each; weights: out rows
+ * of max_taps floats, the entries behind a row's count zero.  Returns the widest tap count of the axis; with all three arrays NULL
+ * it only returns that (to size them).  Negative: an unknown mode, in or out outside 1..256, some but not all arrays NULL, or
+ * max_taps smaller than the widest count (the arrays are then partly written).
+ * vithip_pos_resample_f32: builds the table (the grids are square: one serves both axes), uploads it and launches ONE kernel that
+ * writes every element of dst exactly once.  The table lives for the call only, so unlike the other launchers this one returns when
+ * the kernel has run: it synchronises `stream`.  hipErrorInvalidValue, nothing launched: NULL pointers, a grid outside 1..256, dim
+ * outside 4..2048 or not a multiple of 4, src or dst not 16-byte aligned, an unknown mode.  src and dst must not overlap.
+ */
+enum { VITHIP_POS_BICUBIC = 0, VITHIP_POS_BICUBIC_AA = 1 };
+int vithip_pos_resample_table(int mode, int in, int out, int *first, int *count, float *weights, int max_taps);
+int vithip_pos_resample_f32(vithip_stream_t stream, const float *src, int g_src, float *dst, int g_dst, int dim, int mode);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,6 +80,17 @@ class CIntermediateSpec(C.Structure):  # vit_intermediate_spec
 TAP_KINDS = {"cls": 0, "tokens": 1, "patches": 2, "map": 3}  # VIT_TAP_* / VITHIP_TAP_*
 
 
+class CPosResample(C.Structure):  # vit_pos_resample
+    _fields_ = [("src_img_size", C.c_int), ("mode", C.c_int), ("reserved", C.c_int)]
+
+
+POS_MODES = {"bicubic": 0, "bicubic_aa": 1}  # VIT_POS_* / VITHIP_POS_*
+
+
+def _pos_mode(mode) -> int:
+    return POS_MODES[mode] if isinstance(mode, str) else int(mode)
+
+
 class CImageU8(C.Structure):  # vit_image_u8 / vithip_image_u8: one decoded image, [height][width][chans] uint8
     _fields_ = [("pixels", C.c_void_p), ("height", C.c_int), ("width", C.c_int)]
 
@@ -239,6 +250,11 @@ def lib() -> C.CDLL:
             L.vit_engine_intermediate_row_elems.restype = C.c_size_t
             L.vit_engine_intermediate_row_elems.argtypes = [C.c_void_p, C.POINTER(CIntermediateSpec)]
             L.vithip_tap_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p] + [C.c_int] * 4
+        if hasattr(L, "vit_engine_load_weights_resampled"):  # an earlier build (see above) cannot resample a position embedding
+            L.vit_engine_load_weights_resampled.argtypes = [C.c_void_p, C.POINTER(CNetwork), C.c_int, C.POINTER(CPosResample)]
+            L.vit_engine_copy_weights_resampled.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+            L.vithip_pos_resample_table.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), f32p, C.c_int]
+            L.vithip_pos_resample_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.vit_engine_read_logits.argtypes = [C.c_void_p, f32p, C.c_int]
         L.vit_engine_sync.argtypes = [C.c_void_p]
         L.vit_engine_get_stage_times.argtypes = [C.c_void_p, C.POINTER(CStageTimes)]
@@ -703,6 +719,47 @@ def tap(x, gamma, beta, images: int, tokens: int, layout, ldx: Optional[int] = N
     return do.window().reshape((images,) + shape)
 
 
+def pos_resample_table(mode, n_in: int, n_out: int):
+    """vithip_pos_resample_table (host only, no GPU): the table of one axis as (first [n_out] int32, count [n_out] int32, weights
+    [n_out][widest] float32); the source index of tap k is clamp(first + k, 0, n_in - 1).  VitError when the library refuses."""
+    L, m = lib(), _pos_mode(mode)
+    taps = L.vithip_pos_resample_table(m, n_in, n_out, None, None, None, 0)
+    if taps < 1:
+        raise VitError(f"vithip_pos_resample_table refused mode {m}, {n_in} -> {n_out} ({taps})")
+    first, count = np.empty(n_out, np.int32), np.empty(n_out, np.int32)
+    weights = np.empty((n_out, taps), np.float32)
+    got = L.vithip_pos_resample_table(m, n_in, n_out, first.ctypes.data_as(C.POINTER(C.c_int)), count.ctypes.data_as(C.POINTER(C.c_int)),
+                                      weights.ctypes.data_as(f32p), taps)
+    if got != taps:
+        raise VitError(f"vithip_pos_resample_table: {got} after a sizing call that said {taps}")
+    return first, count, weights
+
+
+def pos_resample(pos, g_dst: int, mode, g_src: Optional[int] = None, guard: int = 0, fill_bits: int = 0, dst_offset: int = 0,
+                 out: Optional[dict] = None) -> np.ndarray:
+    """vithip_pos_resample_f32: pos [1 + g_src^2][dim] -> [1 + g_dst^2][dim] (g_src defaults to the grid pos holds).
+    guard, fill_bits: dst gets `guard` floats either side of it and every float of the allocation is preset to the bit pattern
+    fill_bits; `out` receives the allocation as the call left it under "raw".  dst_offset: floats dst is shifted by (a misaligned
+    destination)."""
+    pos = _as_f32(pos)
+    T, dim = pos.shape
+    if g_src is None:
+        g_src = int(round((T - 1) ** 0.5))
+    n = (1 + g_dst * g_dst) * dim if g_dst > 0 else dim
+    raw = np.full(2 * guard + dst_offset + n, fill_bits, np.uint32).view(np.float32)
+    d_src, d_raw = DeviceArray.from_numpy(pos), DeviceArray.from_numpy(raw)
+    try:
+        hip_check(lib().vithip_pos_resample_f32(None, d_src.ptr, g_src, d_raw.ptr + 4 * (guard + dst_offset), g_dst, dim, _pos_mode(mode)),
+                  "vithip_pos_resample_f32")
+        raw = d_raw.numpy()
+    finally:
+        d_src.free()
+        d_raw.free()
+    if out is not None:
+        out["raw"] = raw
+    return raw[guard + dst_offset:guard + dst_offset + n].reshape(-1, dim).copy()
+
+
 def layernorm_pool(x, gamma, beta, images: int, tokens: int, first_tok: int = 1, l2_normalize: bool = False) -> np.ndarray:
     """vithip_layernorm_pool_f32: x [images * tokens][ld >= dim] (dim = len(gamma)) -> [images][dim], the mean over tokens
     first_tok.. of the LayerNorm rows, optionally L2-normalised.  Columns dim.. of x are padding (ldx > dim)."""
@@ -1021,9 +1078,15 @@ class Engine:
         if rc != 0:
             raise VitError(f"{what} failed ({rc}): {lib().vit_engine_last_error(self._h).decode()}")
 
-    def load_weights(self, weights: Sequence[np.ndarray]) -> None:
+    def load_weights(self, weights: Sequence[np.ndarray], pos_from: Optional[int] = None, pos_mode="bicubic") -> None:
+        """pos_from: the input size the checkpoint was trained at; its position embedding (tensor 3, for that size) is resampled on
+        the device to this engine's cfg.img_size, pos_mode "bicubic" | "bicubic_aa" (vit_engine_load_weights_resampled)."""
         arr, keep = networks_from(weights)
-        self._check(lib().vit_engine_load_weights(self._h, arr, len(weights)), "vit_engine_load_weights")
+        if pos_from is None:
+            self._check(lib().vit_engine_load_weights(self._h, arr, len(weights)), "vit_engine_load_weights")
+            return
+        rs = CPosResample(int(pos_from), _pos_mode(pos_mode), 0)
+        self._check(lib().vit_engine_load_weights_resampled(self._h, arr, len(weights), C.byref(rs)), "vit_engine_load_weights_resampled")
 
     def load_weight_image(self, img: "WeightImage") -> None:
         self._check(lib().vit_engine_load_weight_image(self._h, C.byref(img.c)), "vit_engine_load_weight_image")
@@ -1033,8 +1096,13 @@ class Engine:
         self._check(lib().vit_engine_read_weight_image(self._h, C.byref(img.c)), "vit_engine_read_weight_image")
         return img
 
-    def copy_weights_from(self, other: "Engine") -> None:
+    def copy_weights_from(self, other: "Engine", pos_mode=None) -> None:
+        """pos_mode "bicubic" | "bicubic_aa": `other` may run at another img_size; its resident position embedding is resampled to
+        this engine's (vit_engine_copy_weights_resampled).  None: the plain replication between equal configurations."""
         L = lib()
+        if pos_mode is not None:
+            self._check(L.vit_engine_copy_weights_resampled(self._h, other._h, _pos_mode(pos_mode)), "vit_engine_copy_weights_resampled")
+            return
         L.vit_engine_copy_weights.argtypes = [C.c_void_p, C.c_void_p]
         self._check(L.vit_engine_copy_weights(self._h, other._h), "vit_engine_copy_weights")
 

@@ -497,7 +497,13 @@ static int split_weights(vit_engine *e) {
     return VIT_OK;
 }
 
-int vit_engine_load_weight_image(vit_engine *e, const vit_weight_image *img) {
+static int pos_mode_ok(int mode) { return mode == VIT_POS_BICUBIC || mode == VIT_POS_BICUBIC_AA; }
+/* patches per side the resampling kernel takes (vithip_pos_resample_f32) */
+static int pos_grid_ok(int g) { return g >= 1 && g <= 256; }
+
+/* Upload an image; with d_pos_src (device, [1 + g_src^2][D], the checkpoint's position embedding) the resident tensor 3 is resampled
+ * from it to the engine's own grid, in front of the fold, the split and the sync. */
+static int load_image(vit_engine *e, const vit_weight_image *img, const float *d_pos_src, int g_src, int mode) {
     if (!e || !img || !img->f32) return e ? fail(e, VIT_ERR_ARG, "null weight image") : VIT_ERR_ARG;
     if (memcmp(&img->cfg, &e->cfg, sizeof(vit_config)) != 0 || img->count != e->n_weights)
         return fail(e, VIT_ERR_WEIGHTS, "weight image was built for another model configuration");
@@ -509,12 +515,16 @@ int vit_engine_load_weight_image(vit_engine *e, const vit_weight_image *img) {
     HIP_TRY(e, vithip_memcpy_h2d(e->wblob, img->f32, up, e->stream));
     if (bf16 && !img->bf16_elems) /* image without a bf16 section: convert the GEMM-operand region on the device, one launch */
         HIP_TRY(e, vithip_f32_to_bf16(e->stream, e->wblob, e->wblob16, img->gemm_floats));
+    if (d_pos_src) /* fp32 only: the position embedding is no GEMM operand and has no bf16 copy */
+        HIP_TRY(e, vithip_pos_resample_f32(e->stream, d_pos_src, g_src, e->w[3], e->cfg.img_size / e->cfg.patch_size, e->cfg.embed_dim, mode));
     if ((rc = fold_ln_weights(e))) return rc;
     if ((rc = split_weights(e))) return rc;
     HIP_TRY(e, vithip_stream_sync(e->stream));
     e->weights_loaded = 1;
     return VIT_OK;
 }
+
+int vit_engine_load_weight_image(vit_engine *e, const vit_weight_image *img) { return load_image(e, img, NULL, 0, 0); }
 
 int vit_engine_load_weights(vit_engine *e, const Network *weights, int count) {
     if (!e || !weights) return e ? fail(e, VIT_ERR_ARG, "null weights") : VIT_ERR_ARG;
@@ -552,6 +562,107 @@ int vit_engine_copy_weights(vit_engine *dst, vit_engine *src) {
      * "upload to GPU 0 + broadcast") */
     HIP_TRY(dst, vithip_memcpy_peer(dst->wblob, dst->opt.device, src->wblob, src->opt.device, dst->wblob_bytes, dst->stream));
     if ((rc = fold_ln_weights(dst))) return rc; /* recomputed from the replica's own fp32 tensors: 2 launches per layer */
+    if ((rc = split_weights(dst))) return rc;
+    HIP_TRY(dst, vithip_stream_sync(dst->stream));
+    dst->weights_loaded = 1;
+    return VIT_OK;
+}
+
+int vit_engine_load_weights_resampled(vit_engine *e, const Network *weights, int count, const vit_pos_resample *rs) {
+    if (!e || !weights) return e ? fail(e, VIT_ERR_ARG, "null weights") : VIT_ERR_ARG;
+    if (!rs) return fail(e, VIT_ERR_ARG, "load_weights_resampled: null vit_pos_resample");
+    if (rs->reserved != 0) return fail(e, VIT_ERR_ARG, "load_weights_resampled: reserved must be 0 (got %d)", rs->reserved);
+    if (!pos_mode_ok(rs->mode)) return fail(e, VIT_ERR_ARG, "load_weights_resampled: unknown mode %d", rs->mode);
+    if (rs->src_img_size <= 0 || rs->src_img_size % e->cfg.patch_size)
+        return fail(e, VIT_ERR_ARG, "load_weights_resampled: src_img_size %d is not a positive multiple of patch_size %d", rs->src_img_size,
+                    e->cfg.patch_size);
+    const int g_src = rs->src_img_size / e->cfg.patch_size, g_dst = e->cfg.img_size / e->cfg.patch_size;
+    if (!pos_grid_ok(g_src) || !pos_grid_ok(g_dst))
+        return fail(e, VIT_ERR_ARG, "load_weights_resampled: grids of %d and %d patches per side, the resampling takes 1..256", g_src, g_dst);
+    if (count != e->n_weights)
+        return fail(e, VIT_ERR_WEIGHTS, "expected %d weight tensors for depth %d, got %d", e->n_weights, e->cfg.depth, count);
+    const size_t D = (size_t)e->cfg.embed_dim, pos_src = ((size_t)g_src * g_src + 1) * D, pos_dst = ((size_t)g_dst * g_dst + 1) * D;
+    for (int i = 0; i < count; ++i) {
+        const size_t want = i == 3 ? pos_src : vit_config_weight_size(&e->cfg, i);
+        if (!weights[i].data)
+            return fail(e, VIT_ERR_WEIGHTS, "weight %d is missing (Network[%d].data == NULL; expected %zu floats)", i, i, want);
+        if (weights[i].size != want && i == 3)
+            return fail(e, VIT_ERR_WEIGHTS, "weight 3 (position embedding) has %zu floats, expected %zu for the checkpoint's %d x %d grid "
+                                            "(the engine's own %d x %d grid holds %zu)", weights[i].size, want, g_src, g_src, g_dst, g_dst, pos_dst);
+        if (weights[i].size != want)
+            return fail(e, VIT_ERR_WEIGHTS, "weight %d has %zu floats, expected %zu", i, weights[i].size, want);
+    }
+    if (g_src == g_dst) return vit_engine_load_weights(e, weights, count); /* nothing to resample: the plain load, bit for bit */
+    /* the image is the engine's own layout; its tensor 3 is a placeholder that the kernel overwrites on the device */
+    Network *tmp = (Network *)malloc(sizeof(Network) * (size_t)count);
+    float *blank = (float *)calloc(pos_dst, sizeof(float));
+    float *d_pos = NULL;
+    vit_weight_image img;
+    int rc = (tmp && blank) ? VIT_OK : fail(e, VIT_ERR_NOMEM, "out of host memory");
+    if (!rc) {
+        memcpy(tmp, weights, sizeof(Network) * (size_t)count);
+        tmp[3].data = blank;
+        tmp[3].size = pos_dst;
+        if (vit_weight_image_build(&img, &e->cfg, tmp, count, 0) != 0) rc = fail(e, VIT_ERR_NOMEM, "out of host memory packing the weights");
+    }
+    if (!rc) {
+        int hrc = vithip_set_device(e->opt.device);
+        if (!hrc) hrc = vithip_malloc((void **)&d_pos, pos_src * sizeof(float));
+        if (!hrc) hrc = vithip_memcpy_h2d(d_pos, weights[3].data, pos_src * sizeof(float), e->stream);
+        rc = hrc ? fail(e, VIT_ERR_HIP, "load_weights_resampled: HIP error %d (%s) staging the checkpoint's position embedding", hrc,
+                        vithip_error_string(hrc))
+                 : load_image(e, &img, d_pos, g_src, rs->mode);
+        if (e->stream) vithip_stream_sync(e->stream); /* the staging copy reads the caller's array: not behind this call, whatever failed */
+        vithip_free(d_pos);
+        vit_weight_image_free(&img);
+    }
+    free(tmp); free(blank);
+    return rc;
+}
+
+int vit_engine_copy_weights_resampled(vit_engine *dst, vit_engine *src, int mode) {
+    if (!dst || !src) return VIT_ERR_ARG;
+    if (!pos_mode_ok(mode)) return fail(dst, VIT_ERR_ARG, "copy_weights_resampled: unknown mode %d", mode);
+    if (!src->weights_loaded) return fail(dst, VIT_ERR_STATE, "copy_weights: the source engine has no weights");
+    vit_config same = src->cfg;
+    same.img_size = dst->cfg.img_size;
+    if (memcmp(&dst->cfg, &same, sizeof(vit_config)) != 0 || dst->opt.dtype != src->opt.dtype)
+        return fail(dst, VIT_ERR_ARG, "copy_weights_resampled: engines differ in more than img_size, or in dtype");
+    if (dst->cfg.img_size == src->cfg.img_size) return vit_engine_copy_weights(dst, src);
+    const int g_src = src->cfg.img_size / src->cfg.patch_size, g_dst = dst->cfg.img_size / dst->cfg.patch_size;
+    if (!pos_grid_ok(g_src) || !pos_grid_ok(g_dst))
+        return fail(dst, VIT_ERR_ARG, "copy_weights_resampled: grids of %d and %d patches per side, the resampling takes 1..256", g_src, g_dst);
+    const size_t n = (size_t)dst->n_weights;
+    size_t *off = (size_t *)malloc(sizeof(size_t) * 4 * n);
+    if (!off) return fail(dst, VIT_ERR_NOMEM, "out of host memory");
+    size_t *size = off + n, *soff = off + 2 * n, *ssize = off + 3 * n;
+    size_t gemm_floats = 0, sgemm = 0;
+    const size_t f32_floats = vit_weight_layout(&dst->cfg, off, size, &gemm_floats);
+    const size_t sf32 = vit_weight_layout(&src->cfg, soff, ssize, &sgemm);
+    /* the two layouts differ behind tensor 3 only: [0, off[3]) | tensor 3's slots | an equally long rest | the bf16 section */
+    const size_t head = off[3], spos_floats = ssize[3];
+    size_t rest = f32_floats, srest = sf32; /* where the tensor laid out behind tensor 3 starts */
+    for (size_t i = 0; i < n; ++i) {
+        if (off[i] > head && off[i] < rest) rest = off[i];
+        if (soff[i] > head && soff[i] < srest) srest = soff[i];
+    }
+    const int ok = soff[3] == head && sgemm == gemm_floats && gemm_floats <= head && f32_floats - rest == sf32 - srest;
+    int rc = ok ? alloc_weight_blob(dst, off, f32_floats, gemm_floats) : fail(dst, VIT_ERR_STATE, "copy_weights_resampled: the weight layouts do not line up");
+    free(off);
+    if (rc) return rc;
+    const int dd = dst->opt.device, sd = src->opt.device;
+    float *d_pos = NULL; /* src's position embedding on dst's device: the kernel reads local memory whatever the pair of devices */
+    HIP_TRY(dst, vithip_malloc((void **)&d_pos, spos_floats * sizeof(float)));
+    int hrc = vithip_memcpy_peer(dst->wblob, dd, src->wblob, sd, head * sizeof(float), dst->stream);
+    if (!hrc) hrc = vithip_memset(dst->wblob + head, 0, (rest - head) * sizeof(float), dst->stream); /* slot padding stays zero */
+    if (!hrc) hrc = vithip_memcpy_peer(dst->wblob + rest, dd, src->wblob + srest, sd, (f32_floats - rest) * sizeof(float), dst->stream);
+    if (!hrc && dst->wblob16) hrc = vithip_memcpy_peer(dst->wblob16, dd, src->wblob16, sd, gemm_floats * sizeof(unsigned short), dst->stream);
+    if (!hrc) hrc = vithip_memcpy_peer(d_pos, dd, src->w[3], sd, spos_floats * sizeof(float), dst->stream);
+    if (!hrc) hrc = vithip_pos_resample_f32(dst->stream, d_pos, g_src, dst->w[3], g_dst, dst->cfg.embed_dim, mode);
+    if (dst->stream) vithip_stream_sync(dst->stream);
+    vithip_free(d_pos);
+    if (hrc) return fail(dst, VIT_ERR_HIP, "copy_weights_resampled: HIP error %d (%s)", hrc, vithip_error_string(hrc));
+    if ((rc = fold_ln_weights(dst))) return rc;
     if ((rc = split_weights(dst))) return rc;
     HIP_TRY(dst, vithip_stream_sync(dst->stream));
     dst->weights_loaded = 1;
