@@ -178,7 +178,9 @@ int vit_engine_forward_host(vit_engine *e, const float *const *images, int n, fl
  * forward of the image normalised by that formula on the host, for every option and dtype.  A quarter of the fp32 bytes cross the
  * host gather and PCIe.  mean / std: HOST arrays of cfg.in_chans floats, read during the call.  VIT_ERR_ARG (the engine stays
  * usable) for NULL pointers, n <= 0, a non-finite mean or std, a zero std, in_chans > 4 or, device path, d_images not 4-byte
- * aligned.
+ * aligned -- and, checked before anything is enqueued, for an engine whose img_size is no multiple of 4 (even patch geometries
+ * such as 518 = 37 x 14 or 42: the 8-bit and decoded-image kernels write 16 bytes of a pixel row at a time; the message names
+ * img_size).  That holds for every _u8 and _images call below; the fp32-input calls take any even img_size.
  *
  * Device path: d_images [n][S][S][C] in HBM, asynchronous on `stream` like vit_engine_forward_device (a graph of use_graph is
  * keyed on the input kind and the mean / std values too).  The fp32 images live in the engine's staging until the call's

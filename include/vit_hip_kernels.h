@@ -278,10 +278,25 @@ int vithip_f32_to_bf16(vithip_stream_t stream, const float *src, unsigned short 
  *   x[img][0][:]     = cls[:] + pos[0][:]
  *   x[img][1+p][:]   = conv_bias[:] + sum_{ic,kh,kw} image * conv_w + pos[1+p][:]
  * images: [n][C][S][S]; conv_w: [D][C*P*P]; x: [n][T][D], T = (S/P)^2 + 1.
+ * Two kernels: geometries with P % 4 == 0, S % 4 == 0 and C*P*P % 32 == 0 (images and conv_w 16-byte aligned) take the 16-byte gather
+ * of csrc/vit_gemm.hip; every other geometry goes to vithip_patch_embed_f32_general below and follows its rules.
  */
 int vithip_patch_embed_f32(vithip_stream_t stream, const float *images, const float *conv_w,
                            const float *conv_b, const float *cls, const float *pos, float *x,
                            int n_images, int img_size, int patch_size, int in_chans, int embed_dim);
+/*
+ * The same result for any even geometry (csrc/vit_patch_embed_general.hip; DINOv2's 14 x 14 patches, K = C*P*P = 588): P even, S even,
+ * S % P == 0, C >= 1, D % 4 == 0, n * (S/P)^2 <= 2^24; images and conv_w 8-byte aligned (they are read 8 bytes at a time, straight
+ * from the NCHW images and from conv_w [D][K] as it lies: no staging pass, no workspace).  Anything else (an odd patch or image
+ * included, NULL pointers): hipErrorInvalidValue, nothing launched.  fp32 MFMA with k ascending from a zero accumulator, then + bias,
+ * then + pos: an output row's bits do not depend on the batch or on the image's place in it.  The K tail of the last K step is
+ * zero-filled on chip; nothing is read past the last weight row, the last image or column K of a weight row.  This entry always runs
+ * the general kernel, also at geometries the 16-byte gather takes (there the two agree to rounding, not to the bit: the gather's k
+ * order inside a K step is another).
+ */
+int vithip_patch_embed_f32_general(vithip_stream_t stream, const float *images, const float *conv_w,
+                                   const float *conv_b, const float *cls, const float *pos, float *x,
+                                   int n_images, int img_size, int patch_size, int in_chans, int embed_dim);
 
 /*
  * y[r][0..dim) = (x[r] - mean) * inv_std * gamma + beta for rows r = 0..rows-1 where row r

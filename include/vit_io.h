@@ -119,6 +119,18 @@ void vit_synth_uniform(unsigned long long seed, int index, size_t n, float lo, f
 int vit_synth_weights(const vit_config *cfg, unsigned long long seed, Network network[], int count);
 ImageData *vit_synth_images(const vit_config *cfg, int n, unsigned long long seed);
 
+/*
+ * LayerScale (DINOv2, CaiT: x += ls1 * attn(LN(x)), x += ls2 * mlp(LN(x))) folded into the projection in front of it, on the host, once:
+ * weights[4+12l+4] (out_proj w [D][D]) and [4+12l+5] (b [D]) are scaled per OUTPUT row d by scales[2l][d];
+ * weights[4+12l+10] (fc2 w [D][H]) and [4+12l+11] by scales[2l+1][d]:
+ * W'[d][k] = (float)(s[d] * W[d][k]), b'[d] = (float)(s[d] * b[d]), one fp32 multiply each,
+ * no re-rounding to 1e-6.  In place, once.  The folded tensors are ordinary weights: no kernel and no weight index knows of LayerScale,
+ * and the weight image / cache file built from them holds the folded model.
+ * Returns 0, or nonzero with `weights` untouched: a NULL pointer, count != VIT_WEIGHT_COUNT(depth), scale_count != 2 * depth, any
+ * tensor or scale absent, of the wrong size for cfg, or holding a non-finite value.
+ */
+int vit_weights_fold_layer_scale(const vit_config *cfg, Network weights[], int count, const Network scales[], int scale_count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -291,6 +291,9 @@ def lib() -> C.CDLL:
         L.vithip_split3_weights_bytes.restype = C.c_size_t
         L.vithip_split3_weights_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.vithip_patch_embed_f32.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int] * 5
+        if hasattr(L, "vithip_patch_embed_f32_general"):  # an earlier build (see above) has neither the general embedding nor the fold
+            L.vithip_patch_embed_f32_general.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int] * 5
+            L.vit_weights_fold_layer_scale.argtypes = [C.POINTER(CConfig), C.POINTER(CNetwork), C.c_int, C.POINTER(CNetwork), C.c_int]
         L.vithip_layernorm_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                            C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.vithip_attention_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
@@ -928,6 +931,51 @@ def patch_embed(cfg: ModelConfig, images, conv_w, conv_b, cls, pos) -> np.ndarra
                                            cfg.img_size, cfg.patch_size, cfg.in_chans, cfg.embed_dim),
               "vithip_patch_embed_f32")
     return dx.numpy().reshape(n, cfg.tokens, cfg.embed_dim)
+
+
+def patch_embed_general_raw(images_ptr, conv_w_ptr, conv_b_ptr, cls_ptr, pos_ptr, x_ptr, n: int, img_size: int, patch_size: int,
+                            in_chans: int, embed_dim: int, general: bool = True) -> int:
+    """vithip_patch_embed_f32_general (general=False: the dispatching vithip_patch_embed_f32) on raw device addresses; returns the
+    launcher's code (0, or a hipError_t: 1 = hipErrorInvalidValue) after the stream has drained."""
+    L = lib()
+    fn = L.vithip_patch_embed_f32_general if general else L.vithip_patch_embed_f32
+    rc = int(fn(None, images_ptr, conv_w_ptr, conv_b_ptr, cls_ptr, pos_ptr, x_ptr, n, img_size, patch_size, in_chans, embed_dim))
+    hip_check(L.vithip_device_sync(), "sync")
+    return rc
+
+
+def patch_embed_general(cfg: ModelConfig, images, conv_w, conv_b, cls, pos) -> np.ndarray:
+    """vithip_patch_embed_f32_general: the 8-byte implicit GEMM for any even geometry, always the general kernel."""
+    images = _as_f32(images)
+    n = images.shape[0]
+    d = [DeviceArray.from_numpy(_as_f32(a)) for a in (images, conv_w, conv_b, cls, pos)]
+    dx = DeviceArray((n * cfg.tokens, cfg.embed_dim))
+    hip_check(patch_embed_general_raw(d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, d[4].ptr, dx.ptr, n, cfg.img_size, cfg.patch_size,
+                                      cfg.in_chans, cfg.embed_dim), "vithip_patch_embed_f32_general")
+    return dx.numpy().reshape(n, cfg.tokens, cfg.embed_dim)
+
+
+def fold_layer_scale_raw(cfg: ModelConfig, weights, scales, count: Optional[int] = None, scale_count: Optional[int] = None) -> int:
+    """vit_weights_fold_layer_scale on the arrays themselves, IN PLACE (float32, C-contiguous; None = an absent tensor; weights / scales
+    None = a NULL array); returns the C call's code: 0, or nonzero for a refused call, which has written nothing."""
+    for a in list(weights or []) + list(scales or []):
+        assert a is None or (a.dtype == np.float32 and a.flags.c_contiguous and a.flags.writeable), "float32, C-contiguous, writable"
+    w_arr, _kw = networks_from(weights) if weights is not None else (None, None)
+    s_arr, _ks = networks_from(scales) if scales is not None else (None, None)
+    return int(lib().vit_weights_fold_layer_scale(C.byref(CConfig.of(cfg)), w_arr, len(weights or []) if count is None else count,
+                                                  s_arr, len(scales or []) if scale_count is None else scale_count))
+
+
+def fold_layer_scale(cfg: ModelConfig, weights: Sequence[np.ndarray], scales: Sequence[np.ndarray]) -> list:
+    """LayerScale folded into out_proj and fc2 (vit_weights_fold_layer_scale): scales = [ls1 of layer 0, ls2 of layer 0, ls1 of layer
+    1, ...], each [embed_dim].  Returns the folded tensors as new arrays (the caller's stay as they are): ordinary weights for
+    Engine.load_weights / WeightImage.build."""
+    folded = [np.array(w, dtype=np.float32, order="C") for w in weights]
+    rc = fold_layer_scale_raw(cfg, folded, [np.array(s, dtype=np.float32, order="C").reshape(-1) for s in scales])
+    if rc != 0:
+        raise VitError(f"vit_weights_fold_layer_scale refused the call ({rc}): {len(folded)} tensors and {len(scales)} scales for depth "
+                       f"{cfg.depth}; every tensor and scale must be present, of the model's size and finite")
+    return folded
 
 
 def patch_embed_bf16(cfg: ModelConfig, images, conv_w, conv_b, cls, pos, implicit: bool = False) -> np.ndarray:

@@ -699,9 +699,14 @@ int vithip_patch_embed_f32(vithip_stream_t stream, const float *images, const fl
                            int n_images, int img_size, int patch_size, int in_chans, int embed_dim) {
     if (!images || !conv_w || !conv_b || !cls || !pos || !x || n_images <= 0)
         return static_cast<int>(hipErrorInvalidValue);
-    if (patch_size % 4 || img_size % patch_size) return static_cast<int>(hipErrorInvalidValue);
+    if (patch_size <= 0 || in_chans <= 0) return static_cast<int>(hipErrorInvalidValue);
     const int K = in_chans * patch_size * patch_size;
-    if (K % KALIGN || img_size % 4) return static_cast<int>(hipErrorInvalidValue);
+    // the 16-byte gather below takes patch % 4, img % 4 and K steps of 32; every other even geometry (patch 14: K = 588) goes to the
+    // 8-byte kernel of vit_patch_embed_general.hip, which refuses what it cannot take either
+    if (patch_size % 4 || img_size % 4 || K % KALIGN)
+        return vithip_patch_embed_f32_general(stream, images, conv_w, conv_b, cls, pos, x, n_images, img_size, patch_size, in_chans,
+                                              embed_dim);
+    if (img_size % patch_size) return static_cast<int>(hipErrorInvalidValue);
     if (!aligned16(images) || !aligned16(conv_w)) return static_cast<int>(hipErrorInvalidValue);
     const int G = img_size / patch_size;
     GemmParams p{};

@@ -226,8 +226,10 @@ static int check_config(vit_engine *e) {
         return fail(e, VIT_ERR_ARG, "HIP attention kernel needs head_dim == 64 (got %d/%d)", c->embed_dim, c->num_heads);
     if (c->embed_dim % 32 || c->hidden_dim % 32)
         return fail(e, VIT_ERR_ARG, "embed_dim and hidden_dim must be multiples of 32");
-    if (c->patch_size % 4 || c->img_size % 4 || (c->in_chans * c->patch_size * c->patch_size) % 32)
-        return fail(e, VIT_ERR_ARG, "patch geometry unsupported (patch%%4, img%%4, C*P*P%%32 must be 0)");
+    /* what vithip_patch_embed_f32 takes: the 16-byte gather or, for every other even geometry (patch 14), the general kernel */
+    if (c->patch_size % 2 || c->img_size % 2)
+        return fail(e, VIT_ERR_ARG, "patch geometry unsupported: patch_size %d and img_size %d must both be even", c->patch_size,
+                    c->img_size);
     if (c->embed_dim > 2048) return fail(e, VIT_ERR_ARG, "embed_dim > 2048 unsupported by the LayerNorm kernel");
     return VIT_OK;
 }
@@ -1218,6 +1220,10 @@ static int chunk_limit(const vit_engine *e) {
 static int input_u8(vit_engine *e, const char *who, const float *mean, const float *std, vit_input *in) {
     memset(in, 0, sizeof(*in));
     in->kind = VIT_IN_U8;
+    /* the 8-bit and decoded-image kernels write 16 bytes of a pixel row at a time; an engine with img_size % 4 == 2 takes fp32 input only */
+    if (e->cfg.img_size % 4)
+        return fail(e, VIT_ERR_ARG, "%s: 8-bit and decoded-image input need img_size %% 4 == 0 (img_size = %d): pass fp32 images", who,
+                    e->cfg.img_size);
     if (!mean || !std) return fail(e, VIT_ERR_ARG, "%s: mean and std are required", who);
     if (e->cfg.in_chans > VIT_MAX_U8_CHANS)
         return fail(e, VIT_ERR_ARG, "%s: 8-bit input takes at most %d channels (in_chans = %d)", who, VIT_MAX_U8_CHANS, e->cfg.in_chans);
@@ -1440,7 +1446,7 @@ static const void *host_image(int kind, const void *images, int i) {
     }
 }
 /* its bytes as the caller holds it, and in a staging slot: a piece's images lie back to back, each start rounded up to 16 bytes
- * (fp32 and 8-bit images fill whole 16 bytes anyway: img_size % 4 == 0) */
+ * (fp32 images fill whole 16 bytes anyway: img_size is even; 8-bit ones too: they need img_size % 4 == 0, input_u8) */
 static size_t host_image_bytes(const vit_engine *e, int kind, const void *images, int i) {
     const size_t C = (size_t)e->cfg.in_chans, S = (size_t)e->cfg.img_size;
     if (kind != VIT_IN_IMAGES) return C * S * S * (kind == VIT_IN_U8 ? 1 : sizeof(float));

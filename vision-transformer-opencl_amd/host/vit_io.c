@@ -331,6 +331,39 @@ int vit_synth_weights(const vit_config *cfg, unsigned long long seed, Network ne
     return 0;
 }
 
+/* LayerScale folded into the projections in front of it (vit_io.h).  Every check runs before the first write. */
+static int all_finite(const float *v, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (!isfinite(v[i])) return 0;
+    return 1;
+}
+
+int vit_weights_fold_layer_scale(const vit_config *cfg, Network weights[], int count, const Network scales[], int scale_count) {
+    if (!cfg || !weights || !scales) return -1;
+    if (cfg->depth <= 0 || cfg->embed_dim <= 0 || cfg->hidden_dim <= 0 || cfg->patch_size <= 0 || cfg->img_size <= 0 ||
+        cfg->in_chans <= 0 || cfg->num_classes <= 0)
+        return -1;
+    if (count != VIT_WEIGHT_COUNT(cfg->depth) || scale_count != 2 * cfg->depth) return -1;
+    const size_t D = (size_t)cfg->embed_dim;
+    for (int i = 0; i < count; ++i)
+        if (!weights[i].data || weights[i].size != synth_weight_size(cfg, i) || !all_finite(weights[i].data, weights[i].size)) return -1;
+    for (int i = 0; i < scale_count; ++i)
+        if (!scales[i].data || scales[i].size != D || !all_finite(scales[i].data, D)) return -1;
+    for (int l = 0; l < cfg->depth; ++l) {
+        for (int half = 0; half < 2; ++half) { /* out_proj (w 4, b 5) with ls1, fc2 (w 10, b 11) with ls2 */
+            const float *s = scales[2 * l + half].data;
+            Network *w = &weights[4 + VIT_WEIGHTS_PER_LAYER * l + (half ? 10 : 4)], *b = w + 1;
+            const size_t K = w->size / D;
+            for (size_t d = 0; d < D; ++d) {
+                float *row = w->data + d * K;
+                for (size_t k = 0; k < K; ++k) row[k] = s[d] * row[k];
+                b->data[d] = s[d] * b->data[d];
+            }
+        }
+    }
+    return 0;
+}
+
 ImageData *vit_synth_images(const vit_config *cfg, int n, unsigned long long seed) {
     if (n <= 0) return NULL;
     const size_t per = (size_t)cfg->in_chans * cfg->img_size * cfg->img_size;
