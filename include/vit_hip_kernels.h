@@ -143,6 +143,9 @@ typedef struct {
      * so the result has the same bits with and without it. */
     const void *w_split;
 } vithip_gemm_args;
+/* Non-finite values (NaN, +-Inf, or finite ones whose products overflow) in one row of A reach only that row of C and of stats_out,
+ * whatever the tile, arith, w_split or workspace: every other output has the bits of the same launch on clean data
+ * (tests/test_gpu_isolation.py). */
 int vithip_gemm_f32(vithip_stream_t stream, const vithip_gemm_args *args);
 /* Pre-split weight image for vithip_gemm_args.w_split: the hi / mid / lo bf16 pieces of W [N][ldw] (K % 32 == 0, ldw % 4 == 0,
  * 16-byte aligned), the arithmetic of the on-the-fly split (round to nearest even, +-Inf, NaN and subnormals included).  Layout: one
@@ -206,7 +209,9 @@ typedef struct {
 } vithip_gemm_bf16_args;
 /* C = epilogue(A . W^T + bias) on the bf16 matrix pipe (v_mfma_f32_16x16x32_bf16 in the ping-pong kernel,
  * v_mfma_f32_32x32x16_bf16 in the two-stage one), fp32 accumulate.  BF16_GELU rounds gelu(acc + bias) to bf16 (a
- * polynomial erfc whose error stays below 5 % of half a bf16 ulp); F32_RESIDUAL adds an fp32 residual in fp32. */
+ * polynomial erfc whose error stays below 5 % of half a bf16 ulp); F32_RESIDUAL adds an fp32 residual in fp32.
+ * Non-finite values in one row of A reach only that row of C, x16 and row_partials -- and do reach it: a NaN accumulator comes out
+ * of BF16_GELU as NaN, an infinite one as NaN or Inf -- every other output has the bits of the same launch on clean data. */
 int vithip_gemm_bf16(vithip_stream_t stream, const vithip_gemm_bf16_args *args);
 /* ---- LayerNorm folding (bf16 forward): LN(x) . W^T + b = rstd * (x . (gamma*W)^T) - rstd * mean * colsum(gamma*W) + (b + W . beta),
  * so the normalised activations never exist in memory: the residual GEMM in front stores bf16(x) and row sums, the GEMM
@@ -235,7 +240,9 @@ int vithip_gather_rows_f32(vithip_stream_t stream, const float *src, size_t src_
                            int width);
 /* LayerNorm with fp32 statistics and a bf16 store; attention reading bf16 Q/K/V [n*tokens][3*heads*64] and
  * writing bf16 [n*tokens][heads*64]: both products on bf16 MFMA with fp32 softmax (P rounded to bf16 once);
- * vithip_attention_bf16io_f32math: same I/O, K/V widened to fp32 in LDS and the fp32 kernel's arithmetic (cross-check). */
+ * vithip_attention_bf16io_f32math: same I/O, K/V widened to fp32 in LDS and the fp32 kernel's arithmetic (cross-check).
+ * Non-finite values in one row (LayerNorm) / in one image's rows (both attention entries) reach only that row's / that image's
+ * outputs; all other outputs have the bits of the same launch on clean data. */
 int vithip_layernorm_f32_bf16out(vithip_stream_t stream, const float *x, size_t ldx, unsigned short *y, size_t ldy,
                                  const float *gamma, const float *beta, int rows, int dim);
 int vithip_attention_bf16io(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out,
@@ -243,14 +250,16 @@ int vithip_attention_bf16io(vithip_stream_t stream, const unsigned short *qkv, u
 int vithip_attention_bf16io_f32math(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out,
                                     int n_images, int tokens, int heads);
 /* As vithip_attention_f32 / vithip_attention_bf16io, but only the first q_rows query rows of every image are computed
- * and stored (rows q_rows.. of `out` are left untouched); tokens <= 224.  q_rows = 1 is the class token. */
+ * and stored (rows q_rows.. of `out` are left untouched); tokens <= 224.  q_rows = 1 is the class token.  Non-finite values in one
+ * image's rows reach only that image's outputs; all other outputs have the bits of the same launch on clean data. */
 int vithip_attention_f32_rows(vithip_stream_t stream, const float *qkv, float *out, int n_images, int tokens, int heads,
                               int q_rows);
 int vithip_attention_bf16io_rows(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out, int n_images,
                                  int tokens, int heads, int q_rows);
 /* As vithip_attention_bf16io (q_rows = tokens) / _rows, for Q columns that already hold VITHIP_QSCALE * q.  For the streamed
  * kernel (225..704 tokens) this removes the scale-and-subtract of every score: the score accumulators start at -max; the
- * resident kernel (up to 224) and the chunked one (beyond 704) take the factor 1 in place of VITHIP_QSCALE. */
+ * resident kernel (up to 224) and the chunked one (beyond 704) take the factor 1 in place of VITHIP_QSCALE.  Non-finite values in
+ * one image's rows reach only that image's outputs; all other outputs have the bits of the same launch on clean data. */
 int vithip_attention_bf16io_qscaled(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out, int n_images,
                                     int tokens, int heads, int q_rows);
 /* Patch embedding on the bf16 matrix pipe (same result layout as vithip_patch_embed_f32: x[n][tokens][D] fp32 with
@@ -303,6 +312,7 @@ int vithip_patch_embed_f32_general(vithip_stream_t stream, const float *images, 
  * starts at x + r*ldx (ldx lets the final LayerNorm touch only the class-token rows).
  * mean/var as ViT_seq.c:103-121: var = E[x^2] - mean^2, inv_std = 1/sqrtf((double)var + 1e-6).
  * dim % 4 == 0, dim <= 2048; ldx, ldy >= dim and % 4 == 0; x, y, gamma, beta 16-byte aligned (vithip_layernorm_f32_bf16out: the same).
+ * Non-finite values in one row of x reach only that row of y; all other rows have the bits of the same launch on clean data.
  */
 int vithip_layernorm_f32(vithip_stream_t stream, const float *x, size_t ldx, float *y, size_t ldy,
                          const float *gamma, const float *beta, int rows, int dim);
@@ -313,6 +323,8 @@ int vithip_layernorm_f32(vithip_stream_t stream, const float *x, size_t ldx, flo
  * out: [n*T][D].  scores = q.k / sqrtf(64); row softmax with max subtraction; out = P.V.
  * head_dim must be 64.  Up to 224 tokens K and V of one head stay resident in LDS; longer sequences
  * (ViT-L/16-384: 577) stream K/V through LDS in 224-key chunks with an online softmax.
+ * Non-finite values in one image's rows reach only that image's outputs; all other outputs have the bits of the same launch on
+ * clean data.
  */
 int vithip_attention_f32(vithip_stream_t stream, const float *qkv, float *out,
                          int n_images, int tokens, int heads);
@@ -404,6 +416,7 @@ int vithip_l2_normalize_rows_f32(vithip_stream_t stream, float *x, size_t ldx, i
  *   head_mean = 1: out[i][t] = (p[0][t] + p[1][t] + ... in head order) / (float)heads, of exactly the bits head_mean = 0 stores.
  * q_scaled = 1 (bf16): the Q columns hold VITHIP_QSCALE * q; p_t = exp2f(q . k_t - max) / sum, no further scaling.
  * Deterministic (no atomics) and position independent: an image's row has the same bits wherever the image sits in whatever batch.
+ * Non-finite values in one image's rows reach only that image's row of `out`; all other rows have the bits of the same launch on clean data.
  * Any tokens >= 1 and heads >= 1; head_dim is 64.  Elements of `out` outside the rows are not touched.
  * hipErrorInvalidValue: NULL pointers, non-positive sizes, flags other than 0 / 1, q_row_stride < 3 * heads * 64 or not a multiple
  * of 4 (fp32) / 8 (bf16), ld_out smaller than a row, qkv not 16-byte or out not 4-byte aligned.
@@ -426,7 +439,8 @@ int vithip_cls_attention_bf16(vithip_stream_t stream, const unsigned short *qkv,
  * csrc/vit_layernorm_row.hpp), unnormalised ones the bits of x; MAP is the exact transpose of PATCHES.  Only the block of each
  * image is written: the floats from its end up to out_image_stride are not touched, so several launches can fill one output row
  * side by side.  MAP goes through an LDS tile and stores runs of up to 32 tokens per channel (16 above dim 1024), as 16 bytes per lane when P % 4 == 0
- * and as 4 bytes per lane otherwise; any P >= 1 is correct.  No atomics; results do not depend on the grid.
+ * and as 4 bytes per lane otherwise; any P >= 1 is correct.  No atomics; results do not depend on the grid.  Non-finite values in
+ * one row of x reach only that row's outputs (the MAP's LDS tile included); all others have the bits of the same launch on clean data.
  * hipErrorInvalidValue, nothing launched: x or out NULL, exactly one of gamma / beta NULL, a non-positive size, an unknown layout,
  * PATCHES or MAP with tokens < 2, dim % 4 != 0 or dim > 2048, ldx < dim or ldx % 4 != 0, out_image_stride % 4 != 0 or smaller than the
  * block, x / out / gamma / beta not 16-byte aligned, images * tokens >= 2^31.

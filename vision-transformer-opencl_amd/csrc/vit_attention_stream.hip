@@ -236,7 +236,7 @@ __global__ __launch_bounds__(ST_THREADS) void attention_bf16_stream_kernel(const
                     const int so = krow0 * ld * 2;
                     dma16(rk, Kd + t * 512, kofs, so);
                     dma16(rv, Vd + t * 512, vofs, so);
-                } else {  // rows past the last token: clamped (finite values; those keys are masked / weigh 0)
+                } else {  // rows past the last token: clamped (the image's own last row; those keys are masked / weigh 0)
                     const int lrow = 8 * t + row_l;
                     int srow = krow0 + row_l;
                     srow = srow < tk ? srow : tk - 1;
@@ -347,8 +347,9 @@ __global__ __launch_bounds__(ST_THREADS) void attention_bf16_stream_kernel(const
 
         f32x16 st[2][SUB];  // two score buffers
         [[maybe_unused]] float m_init[2] = {0.0f, 0.0f};  // QS: the reference the buffer's accumulators were initialised with (finite)
-        // scores of sub-chunk k0 of block b -> buffer `buf`.  A sub-chunk is always computed whole: keys past `valid` (a
-        // chunk of 3 tiles, the end of the sequence) hold older, finite data in LDS and are masked to -inf below.
+        // scores of sub-chunk k0 of block b -> buffer `buf`.  The scores of a sub-chunk are always computed whole: keys past
+        // `valid` (a chunk of 3 tiles, the end of the sequence) hold whatever the slot's last four-tile chunk left there --
+        // another item's rows, NaN and Inf included -- and are masked to -inf by a select below, which no value survives.
         auto scores = [&](int buf, int b, int k0) __attribute__((always_inline)) {
             // Row r of a 32-row block (Q or K alike) at r * 128 B, its 16-byte chunk c at position c ^ ((r >> 1) & 7); k-step ks
             // wants chunk 2 ks + h, i.e. position ((h ^ sw) ^ 2 ks): ONE lane register and an XOR per k-step.  Recomputed from the
@@ -511,6 +512,10 @@ __global__ __launch_bounds__(ST_THREADS) void attention_bf16_stream_kernel(const
             read_v(0, 0);
 #pragma unroll
             for (int g = 0; g < 2 * SUB; ++g) {
+                // A 16-key group wholly past `valid` is skipped (wave-uniform), not multiplied by P = 0: its V rows are stale
+                // (see scores) and 0 * NaN = NaN on the matrix pipe.  A partly valid group lies in the sequence's tail tile,
+                // which dma_chunk fills from the image's own last row.
+                if ((k0 + (g >> 1)) * 32 + 16 * (g & 1) >= valid) break;
                 bf16x8 pf;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) pf[j] = (__bf16)st[buf][g >> 1][8 * (g & 1) + j];
@@ -557,9 +562,7 @@ __global__ __launch_bounds__(ST_THREADS) void attention_bf16_stream_kernel(const
     if (item >= n_items) return;  // workgroup-uniform
     const int stride = gridDim.x;
     if (ST_PRIO && wave >= 4) __builtin_amdgcn_s_setprio(1);  // the second-dispatched half loses the issue arbitration otherwise (T5, static form)
-    // the ring starts zeroed: stale rows that a partial sub-chunk multiplies by 0 must be finite from the first step on
-    for (int i = tid; i < 2 * SBUF / 8; i += ST_THREADS) reinterpret_cast<uint4 *>(lds)[i] = uint4{0u, 0u, 0u, 0u};
-    __syncthreads();
+    // (the ring is not cleared: rows of a slot that no DMA of the current chunk wrote are read for masked scores only)
     dma_chunk(item, 0, 0);
     int slot = 0;
 #pragma unroll

@@ -131,6 +131,13 @@ __device__ __forceinline__ void gelu_erf_x8(float (&y)[8]) {
 // rounding that follows, at 6.5 VALU instructions per value (6 + 1 v_pk_fma_f32, v_min, v_max, v_exp_f32 per pair and
 // value) instead of 19 for the fp32-accurate form above
 // (ViT_seq.c:231-233 is the fp32 definition; the bf16 path's parity bar is in tests/test_gpu_bf16.py).
+// max(y, 0) that stays non-finite for a non-finite y: v_min / v_max return their OTHER operand for a NaN, so t and the maximum alone
+// turned a NaN row of the GEMM into finite values.  y * 0 is +-0 for a finite y (max + (+-0) is max bit for bit, +0 + -0 = +0) and
+// NaN for NaN and +-Inf: one v_pk_fma_f32 per pair, off the polynomial's dependent chain.
+__device__ __forceinline__ f32x2 relu_keep_nan(f32x2 y) {
+    return __builtin_elementwise_fma(y, f32x2{0.f, 0.f}, __builtin_elementwise_max(y, f32x2{0.f, 0.f}));
+}
+
 __device__ __forceinline__ f32x2 gelu_bf16_x2(f32x2 y) {
     constexpr float kClamp = 5.656854249492381f;  // 4 sqrt2
     const f32x2 t = f32x2{fminf(__builtin_fabsf(y.x), kClamp), fminf(__builtin_fabsf(y.y), kClamp)};
@@ -140,7 +147,7 @@ __device__ __forceinline__ f32x2 gelu_bf16_x2(f32x2 y) {
 #pragma unroll
     for (int k = 5; k >= 0; --k) q = __builtin_elementwise_fma(q, t, f32x2{c[k], c[k]});
     const f32x2 e = f32x2{__builtin_amdgcn_exp2f(q.x), __builtin_amdgcn_exp2f(q.y)};
-    return __builtin_elementwise_fma(-t, e, __builtin_elementwise_max(y, f32x2{0.f, 0.f}));
+    return __builtin_elementwise_fma(-t, e, relu_keep_nan(y));
 }
 
 // The same values for NP pairs advanced TOGETHER (the scheduling fences keep hipcc from putting the chains back one after the other):
@@ -169,7 +176,7 @@ __device__ __forceinline__ void gelu_bf16_lockstep(f32x2 (&y)[NP]) {
     for (int v = 0; v < NP; ++v) q[v] = f32x2{__builtin_amdgcn_exp2f(q[v].x), __builtin_amdgcn_exp2f(q[v].y)};
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int v = 0; v < NP; ++v) y[v] = __builtin_elementwise_fma(-t[v], q[v], __builtin_elementwise_max(y[v], f32x2{0.f, 0.f}));
+    for (int v = 0; v < NP; ++v) y[v] = __builtin_elementwise_fma(-t[v], q[v], relu_keep_nan(y[v]));
 }
 
 // Workgroup id -> tile id such that ids sharing an XCD (id % 8) get consecutive tiles.
