@@ -12,9 +12,10 @@
  *    an attention call stops the last layer behind its QKV GEMM and stores the class token's softmax row;
  *    an intermediate call copies rows of x out behind the layers it taps and stops behind the deepest of them)
  *
- * Weights are validated and uploaded once (the reference re-uploads them per op per image,
- * e.g. ViT_opencl.c:136,630-631); activations never leave HBM between stages (the reference
- * reads every stage back to the host).
+ * Weights are validated and uploaded once (the reference re-uploads them per op per image, e.g. ViT_opencl.c:136,630-631); every
+ * install route ends in finish_install, which derives the folded and pre-split operands and resolves, per layer, what each GEMM and
+ * LayerNorm reads (vit_layer_ops): the stages index no tensor.  Activations never leave HBM between stages (the reference reads
+ * every stage back to the host).
  */
 #include "vit_engine.h"
 
@@ -68,6 +69,13 @@ _Static_assert(sizeof(vit_output) == 4 * sizeof(int) + sizeof(vit_intermediate_s
                    sizeof(vit_intermediate_spec) == (4 + VIT_MAX_TAPS) * sizeof(int) && sizeof(vit_intermediate_spec) % sizeof(void *) == 0,
                "vit_output must stay free of padding: the graph cache compares it bytewise");
 
+/* The resolved operands of the forward.  A GEMM's: W [N][K] in the engine's GEMM dtype, fp32 bias [N], the column sums of W where
+ * the LayerNorm fold's epilogue subtracts mean * colsum (else NULL), W's pre-split image on split engines (else NULL). */
+typedef struct { const void *W; const float *bias, *colsum; const void *w_split; } vit_gemm_ops;
+typedef struct { const float *ln1_g, *ln1_b, *ln2_g, *ln2_b; vit_gemm_ops qkv, out, fc1, fc2; } vit_layer_ops;
+typedef struct { const float *cls, *conv_w, *conv_b, *pos; const unsigned short *conv_w16; /* bf16 engines */ } vit_embed_ops;
+typedef struct { const float *ln_g, *ln_b; vit_gemm_ops head; } vit_final_ops;
+
 struct vit_engine {
     vit_config cfg;
     vit_engine_options opt;
@@ -84,11 +92,15 @@ struct vit_engine {
     unsigned short *wblob16;     /* the bf16 section inside wblob (dtype bf16 only) */
     int fold;                    /* LayerNorm fold active (vit_engine_options.ln_fold) */
     int split;                   /* encoder GEMMs on the three-piece split (vit_engine_options.fp32_split; fp32 engines) */
-    unsigned short *wfold16;     /* per layer [gamma1-folded in_proj 3D x D | gamma2-folded fc1 H x D] (bf16 engines) */
-    float *wfold32;              /* the same two operands as fp32 products gamma * W (fp32 engines) */
-    unsigned char *wsplit;       /* split engines: per layer the pre-split images (vithip_split3_weights_f32) of [qkv | out_proj | fc1 | fc2] */
+    /* the operands derived from the weights by every install (finish_install); their layout: "derived operands" below */
+    void *wfold;                 /* folded in_proj and fc1: bf16 (bf16 engines) or the fp32 products gamma * W (fp32 engines) */
+    float *wfoldf;               /* their column sums and folded biases */
+    unsigned char *wsplit;       /* split engines: the pre-split images (vithip_split3_weights_f32) of the four encoder GEMM weights */
     size_t wsplit_off[4], wsplit_layer; /* byte offset of each image inside a layer's, and a layer's bytes */
-    float *wfoldf;               /* per layer [colsum qkv 3D | bias qkv 3D | colsum fc1 H | bias fc1 H] */
+    /* what every GEMM and LayerNorm of the forward reads, resolved by every install (resolve_operands): pointers into the above */
+    vit_embed_ops embed;
+    vit_layer_ops *layer;        /* [depth] */
+    vit_final_ops final;
     float *ln_rows32;            /* fp32 engines: (rstd, mean) per token row [max_batch * tokens][2], then per class row [max_batch][2] */
     float *ln_part32;            /* ... and the residual GEMMs' scratch for them: [embed_dim / 64][rows][2] per lane (vithip_gemm_args.stats_partials) */
     int lane_cap;                /* most images one lane may hold (32-bit buffer offsets of the fp32 kernels) */
@@ -130,6 +142,22 @@ struct vit_engine {
     long pending_images;         /* images whose brackets are still in the pool */
     vit_stage_times times;
 };
+
+/* element i of an array of esz-byte elements */
+static void *at(const void *p, size_t i, size_t esz) { return (char *)p + i * esz; }
+
+/* The weight order (ViT_seq.c:366-426): w[0..3] below, then VIT_WEIGHTS_PER_LAYER tensors per layer in the order of LW_*, then the
+ * final LayerNorm's gamma and beta and the head's weight and bias. */
+enum { W_CLS, W_CONV_W, W_CONV_B, W_POS, W_LAYER0 };
+enum { LW_LN1_G, LW_LN1_B, LW_QKV_W, LW_QKV_B, LW_OUT_W, LW_OUT_B, LW_LN2_G, LW_LN2_B, LW_FC1_W, LW_FC1_B, LW_FC2_W, LW_FC2_B };
+_Static_assert(LW_FC2_B + 1 == VIT_WEIGHTS_PER_LAYER, "LW_* names every tensor of a layer");
+
+/* The derived operands' layout, per layer (resolve_operands fills them, and names the slots):
+ *   wfold   [gamma1-folded in_proj 3D x D | gamma2-folded fc1 H x D], elements of the engine's GEMM dtype
+ *   wfoldf  [colsum qkv 3D | bias qkv 3D | colsum fc1 H | bias fc1 H]
+ *   wsplit  the images of [qkv | out_proj | fc1 | fc2] at wsplit_off[0..3], wsplit_layer bytes (vit_engine_create) */
+static size_t fold_w_elems(const vit_config *c) { return (3 * (size_t)c->embed_dim + (size_t)c->hidden_dim) * (size_t)c->embed_dim; }
+static size_t fold_f_elems(const vit_config *c) { return 6 * (size_t)c->embed_dim + 2 * (size_t)c->hidden_dim; }
 
 /* ------------------------------------------------------------------------------------------ */
 
@@ -302,38 +330,32 @@ int vit_engine_create(vit_engine **out, const vit_config *cfg, const vit_engine_
         int rc_ws = ensure_gemm_workspaces(e);
         if (rc_ws) return rc_ws;
     }
-    if (e->opt.dtype == VIT_DTYPE_BF16 && e->opt.ln_fold >= 0) {
-        /* the fold lives in the ping-pong GEMM (two K steps at least); its scratch (bf16 copy of x, row sums) uses the
-         * idle halves of the y and qkv allocations, which bf16 activations only half fill */
-        const int ok = e->cfg.embed_dim >= 128 && e->cfg.hidden_dim >= 128 && e->cfg.embed_dim % 64 == 0 && e->cfg.hidden_dim % 64 == 0;
-        if (!ok && e->opt.ln_fold > 0) return fail(e, VIT_ERR_ARG, "ln_fold needs embed_dim and hidden_dim >= 128 and multiples of 64");
-        e->fold = ok;
-        if (e->fold) {
-            const size_t L = (size_t)e->cfg.depth;
-            HIP_TRY(e, vithip_malloc((void **)&e->wfold16, L * (3 * D * D + H * D) * sizeof(unsigned short) + WEIGHT_TAIL_PAD));
-            HIP_TRY(e, vithip_memset((char *)e->wfold16 + L * (3 * D * D + H * D) * sizeof(unsigned short), 0, WEIGHT_TAIL_PAD, e->stream));
-            HIP_TRY(e, vithip_malloc((void **)&e->wfoldf, L * (6 * D + 2 * H) * sizeof(float)));
-        }
-    }
+    const int bf16 = e->opt.dtype == VIT_DTYPE_BF16, f32 = e->opt.dtype == VIT_DTYPE_F32;
     /* the split runs at every K of the model (K % 32 == 0 is checked for every fp32 GEMM anyway) and every M: whether it is on
      * depends on the options alone, never on the batch */
-    e->split = e->opt.dtype == VIT_DTYPE_F32 && e->opt.fp32_split >= 0;
-    if (e->opt.dtype == VIT_DTYPE_F32 && e->opt.ln_fold >= 0) {
-        /* fp32 fold: the consumer epilogue exists in every fp32 GEMM kernel; the row statistics kernel wants whole 64-column strips */
-        const int ok = e->cfg.embed_dim % 64 == 0 && e->cfg.embed_dim <= 2048;
-        if (!ok && e->opt.ln_fold > 0) return fail(e, VIT_ERR_ARG, "ln_fold (fp32) needs embed_dim to be a multiple of 64, at most 2048");
+    e->split = f32 && e->opt.fp32_split >= 0;
+    if ((bf16 || f32) && e->opt.ln_fold >= 0) {
+        /* bf16: the fold lives in the ping-pong GEMM (two K steps at least); its scratch (bf16 copy of x, row sums) uses the idle
+         * halves of the y and qkv allocations, which bf16 activations only half fill.  fp32: the consumer epilogue exists in every
+         * fp32 GEMM kernel; the row statistics kernel wants whole 64-column strips */
+        const int ok = bf16 ? D >= 128 && H >= 128 && D % 64 == 0 && H % 64 == 0 : D % 64 == 0 && D <= 2048;
+        if (!ok && e->opt.ln_fold > 0)
+            return fail(e, VIT_ERR_ARG, bf16 ? "ln_fold needs embed_dim and hidden_dim >= 128 and multiples of 64"
+                                             : "ln_fold (fp32) needs embed_dim to be a multiple of 64, at most 2048");
         e->fold = ok;
         if (e->fold) {
-            const size_t L = (size_t)e->cfg.depth;
-            HIP_TRY(e, vithip_malloc((void **)&e->wfold32, L * (3 * D * D + H * D) * sizeof(float) + WEIGHT_TAIL_PAD));
-            HIP_TRY(e, vithip_memset((char *)e->wfold32 + L * (3 * D * D + H * D) * sizeof(float), 0, WEIGHT_TAIL_PAD, e->stream));
-            HIP_TRY(e, vithip_malloc((void **)&e->wfoldf, L * (6 * D + 2 * H) * sizeof(float)));
-            HIP_TRY(e, vithip_malloc((void **)&e->ln_rows32, (B * T + B) * 2 * sizeof(float)));
-            HIP_TRY(e, vithip_malloc((void **)&e->ln_part32, (D / 64) * B * T * 2 * sizeof(float)));
+            const size_t wbytes = (size_t)e->cfg.depth * fold_w_elems(&e->cfg) * (bf16 ? sizeof(unsigned short) : sizeof(float));
+            HIP_TRY(e, vithip_malloc(&e->wfold, wbytes + WEIGHT_TAIL_PAD));
+            HIP_TRY(e, vithip_memset((char *)e->wfold + wbytes, 0, WEIGHT_TAIL_PAD, e->stream));
+            HIP_TRY(e, vithip_malloc((void **)&e->wfoldf, (size_t)e->cfg.depth * fold_f_elems(&e->cfg) * sizeof(float)));
+            if (f32) {
+                HIP_TRY(e, vithip_malloc((void **)&e->ln_rows32, (B * T + B) * 2 * sizeof(float)));
+                HIP_TRY(e, vithip_malloc((void **)&e->ln_part32, (D / 64) * B * T * 2 * sizeof(float)));
+            }
         }
     }
     if (e->split) {
-        /* W's pieces, made once per upload (split_weights): the persistent split walk then splits only A.  6 bytes per weight of
+        /* W's pieces, made once per upload (resolve_operands): the persistent split walk then splits only A.  6 bytes per weight of
          * the four encoder GEMMs; without the image (K not a multiple of 32) every GEMM splits W on the fly, with the same bits */
         const size_t b[4] = {vithip_split3_weights_bytes((int)(3 * D), (int)D), vithip_split3_weights_bytes((int)D, (int)D),
                              vithip_split3_weights_bytes((int)H, (int)D), vithip_split3_weights_bytes((int)D, (int)H)};
@@ -356,9 +378,10 @@ int vit_engine_create(vit_engine **out, const vit_config *cfg, const vit_engine_
 
     e->w = (float **)calloc((size_t)e->n_weights, sizeof(float *));
     e->w16 = (unsigned short **)calloc((size_t)e->n_weights, sizeof(unsigned short *));
+    e->layer = (vit_layer_ops *)calloc((size_t)e->cfg.depth, sizeof(vit_layer_ops));
     e->img_recs = (vithip_image_u8 *)calloc(B, sizeof(vithip_image_u8));
     e->img_off = (size_t *)calloc(B + 1, sizeof(size_t));
-    if (!e->w || !e->w16 || !e->img_recs || !e->img_off) return fail(e, VIT_ERR_NOMEM, "out of host memory");
+    if (!e->w || !e->w16 || !e->layer || !e->img_recs || !e->img_off) return fail(e, VIT_ERR_NOMEM, "out of host memory");
     if (e->opt.dtype != VIT_DTYPE_F32 && e->opt.dtype != VIT_DTYPE_BF16)
         return fail(e, VIT_ERR_ARG, "dtype must be VIT_DTYPE_F32 or VIT_DTYPE_BF16");
     if (e->opt.dtype == VIT_DTYPE_BF16 && (e->cfg.embed_dim % 64 || e->cfg.hidden_dim % 64))
@@ -387,13 +410,12 @@ void vit_engine_destroy(vit_engine *e) {
         if (e->ev_done[b]) vithip_event_destroy(e->ev_done[b]);
     }
     vithip_free(e->wblob);
-    vithip_free(e->wfold16);
-    vithip_free(e->wfold32);
+    vithip_free(e->wfold);
     vithip_free(e->wsplit);
     vithip_free(e->ln_rows32);
     vithip_free(e->ln_part32);
     vithip_free(e->wfoldf);
-    free(e->w16);
+    free(e->w16); free(e->layer);
     free(e->img_recs); free(e->img_off); free(e->piece_lo);
     for (int j = 0; j < VIT_MAX_LANES - 1; ++j) {
         if (e->aux_stream[j]) { vithip_stream_sync(e->aux_stream[j]); vithip_stream_destroy(e->aux_stream[j]); }
@@ -454,48 +476,61 @@ static int alloc_weight_blob(vit_engine *e, const size_t *off, size_t f32_floats
     return VIT_OK;
 }
 
-/* LayerNorm fold: Wf = bf16(gamma * W), column sums and beta-folded biases of every layer's in_proj (LN1) and fc1 (LN2), from
- * the resident fp32 tensors.  Runs after every upload / replication; 2 launches per layer. */
-static int fold_ln_weights(vit_engine *e) {
-    if (!e->fold) return VIT_OK;
-    const size_t D = (size_t)e->cfg.embed_dim, H = (size_t)e->cfg.hidden_dim;
+/* Every GEMM's and LayerNorm's operands as the stages read them: the only place that knows where a tensor lies.  bf16 engines read
+ * the encoder GEMM weights (and the conv weight) from w16[].  The derived operands are made here, where they enter the table:
+ *   fold   2 launches per layer, from the resident fp32 tensors: Wf = gamma * W (bf16 engines: rounded to bf16), its column sums
+ *          and the beta-folded biases of in_proj (LN1) and fc1 (LN2), which then stand in for the raw operands;
+ *   split  fp32 engines: W's pieces, 4 launches per layer.
+ * The table points into wblob, which alloc_weight_blob may move: it is rebuilt by every install, never patched. */
+static int resolve_operands(vit_engine *e) {
+    const int bf16 = e->opt.dtype == VIT_DTYPE_BF16, D = e->cfg.embed_dim, H = e->cfg.hidden_dim;
+    const size_t esz = bf16 ? sizeof(unsigned short) : sizeof(float);
+    float **tail = e->w + W_LAYER0 + VIT_WEIGHTS_PER_LAYER * e->cfg.depth;
+    e->embed = (vit_embed_ops){e->w[W_CLS], e->w[W_CONV_W], e->w[W_CONV_B], e->w[W_POS], e->w16[W_CONV_W]};
+    e->final = (vit_final_ops){tail[0], tail[1], {.W = tail[2], .bias = tail[3]}};
     for (int l = 0; l < e->cfg.depth; ++l) {
-        float **lw = e->w + 4 + VIT_WEIGHTS_PER_LAYER * l;
-        float *ff = e->wfoldf + (size_t)l * (6 * D + 2 * H);
-        if (e->opt.dtype == VIT_DTYPE_F32) { /* fp32 products gamma * W; sums in double, rounded once */
-            float *f32 = e->wfold32 + (size_t)l * (3 * D * D + H * D);
-            /* centred weights (vit_hip_kernels.h): the GEMMs deliver x . (gamma W)^T - mean * colsum themselves, their epilogues only scale;
-             * the colsum slots of wfoldf receive what the weights' rounding left of the column sums and are not read again */
-            HIP_TRY(e, vithip_ln_fold_weights_f32_centered(e->stream, lw[2], lw[3], lw[0], lw[1], f32, ff, ff + 3 * D, (int)(3 * D), (int)D));
-            HIP_TRY(e, vithip_ln_fold_weights_f32_centered(e->stream, lw[8], lw[9], lw[6], lw[7], f32 + 3 * D * D, ff + 6 * D, ff + 6 * D + H, (int)H, (int)D));
-            continue;
+        float **lw = e->w + W_LAYER0 + VIT_WEIGHTS_PER_LAYER * l;
+        unsigned short **lw16 = e->w16 + W_LAYER0 + VIT_WEIGHTS_PER_LAYER * l;
+#define GEMM_OPS(k) {bf16 ? (const void *)lw16[k] : (const void *)lw[k], lw[(k) + 1], NULL, NULL} /* a weight, its bias behind it */
+        vit_layer_ops o = {lw[LW_LN1_G], lw[LW_LN1_B], lw[LW_LN2_G], lw[LW_LN2_B],
+                           GEMM_OPS(LW_QKV_W), GEMM_OPS(LW_OUT_W), GEMM_OPS(LW_FC1_W), GEMM_OPS(LW_FC2_W)};
+#undef GEMM_OPS
+        if (e->fold) {
+            void *w_qkv = at(e->wfold, (size_t)l * fold_w_elems(&e->cfg), esz), *w_fc1 = at(w_qkv, 3 * (size_t)D * D, esz);
+            float *cs_qkv = e->wfoldf + (size_t)l * fold_f_elems(&e->cfg), *b_qkv = cs_qkv + 3 * D, *cs_fc1 = b_qkv + 3 * D, *b_fc1 = cs_fc1 + H;
+            if (bf16) { /* in_proj: the Q rows also carry the factor of the scores' exponent (the attention kernels are told: _qscaled) */
+                HIP_TRY(e, vithip_ln_fold_weights_scaled(e->stream, lw[LW_QKV_W], lw[LW_QKV_B], o.ln1_g, o.ln1_b, w_qkv, cs_qkv, b_qkv, 3 * D, D, D, VITHIP_QSCALE));
+                HIP_TRY(e, vithip_ln_fold_weights(e->stream, lw[LW_FC1_W], lw[LW_FC1_B], o.ln2_g, o.ln2_b, w_fc1, cs_fc1, b_fc1, H, D));
+            } else { /* fp32 products, sums in double, rounded once; centred weights (vit_hip_kernels.h): the GEMMs deliver
+                      * x . (gamma W)^T - mean * colsum themselves and their epilogues only scale, so no column sums are passed on:
+                      * their slots receive what the weights' rounding left of the sums and are not read again */
+                HIP_TRY(e, vithip_ln_fold_weights_f32_centered(e->stream, lw[LW_QKV_W], lw[LW_QKV_B], o.ln1_g, o.ln1_b, w_qkv, cs_qkv, b_qkv, 3 * D, D));
+                HIP_TRY(e, vithip_ln_fold_weights_f32_centered(e->stream, lw[LW_FC1_W], lw[LW_FC1_B], o.ln2_g, o.ln2_b, w_fc1, cs_fc1, b_fc1, H, D));
+                cs_qkv = cs_fc1 = NULL;
+            }
+            o.qkv.W = w_qkv; o.qkv.bias = b_qkv; o.qkv.colsum = cs_qkv;
+            o.fc1.W = w_fc1; o.fc1.bias = b_fc1; o.fc1.colsum = cs_fc1;
         }
-        unsigned short *f16 = e->wfold16 + (size_t)l * (3 * D * D + H * D);
-        /* in_proj: the Q rows also carry the factor of the scores' exponent (the attention kernels are told: _qscaled) */
-        HIP_TRY(e, vithip_ln_fold_weights_scaled(e->stream, lw[2], lw[3], lw[0], lw[1], f16, ff, ff + 3 * D, (int)(3 * D), (int)D, (int)D, VITHIP_QSCALE));
-        HIP_TRY(e, vithip_ln_fold_weights(e->stream, lw[8], lw[9], lw[6], lw[7], f16 + 3 * D * D, ff + 6 * D, ff + 6 * D + H, (int)H, (int)D));
+        if (e->wsplit) { /* 4 launches: the image of every encoder GEMM weight as its GEMM reads it, folded (centred) or raw */
+            vit_gemm_ops *g[4] = {&o.qkv, &o.out, &o.fc1, &o.fc2}; /* the order of wsplit_off[] */
+            const int N[4] = {3 * D, D, H, D}, K[4] = {D, D, D, H};
+            for (int i = 0; i < 4; ++i) {
+                void *img = e->wsplit + (size_t)l * e->wsplit_layer + e->wsplit_off[i];
+                HIP_TRY(e, vithip_split3_weights_f32(e->stream, g[i]->W, K[i], N[i], K[i], img));
+                g[i]->w_split = img;
+            }
+        }
+        e->layer[l] = o;
     }
     return VIT_OK;
 }
 
-/* The pre-split images of every encoder GEMM weight as the GEMMs read them: in_proj and fc1 folded (centred) when the fold is on,
- * out_proj and fc2 raw.  Runs after fold_ln_weights, i.e. after every upload / replication; 4 launches per layer. */
-static int split_weights(vit_engine *e) {
-    if (!e->wsplit) return VIT_OK;
-    const size_t D = (size_t)e->cfg.embed_dim, H = (size_t)e->cfg.hidden_dim;
-    for (int l = 0; l < e->cfg.depth; ++l) {
-        float **lw = e->w + 4 + VIT_WEIGHTS_PER_LAYER * l;
-        const float *w_qkv = lw[2], *w_fc1 = lw[8];
-        if (e->fold) {
-            w_qkv = e->wfold32 + (size_t)l * (3 * D * D + H * D);
-            w_fc1 = w_qkv + 3 * D * D;
-        }
-        unsigned char *img = e->wsplit + (size_t)l * e->wsplit_layer;
-        HIP_TRY(e, vithip_split3_weights_f32(e->stream, w_qkv, (int)D, (int)(3 * D), (int)D, img + e->wsplit_off[0]));
-        HIP_TRY(e, vithip_split3_weights_f32(e->stream, lw[4], (int)D, (int)D, (int)D, img + e->wsplit_off[1]));
-        HIP_TRY(e, vithip_split3_weights_f32(e->stream, w_fc1, (int)D, (int)H, (int)D, img + e->wsplit_off[2]));
-        HIP_TRY(e, vithip_split3_weights_f32(e->stream, lw[10], (int)H, (int)D, (int)H, img + e->wsplit_off[3]));
-    }
+/* The tail of every install, behind the last write to wblob: the fold, the split images and the operand table, then the sync. */
+static int finish_install(vit_engine *e) {
+    const int rc = resolve_operands(e);
+    if (rc) return rc;
+    HIP_TRY(e, vithip_stream_sync(e->stream));
+    e->weights_loaded = 1;
     return VIT_OK;
 }
 
@@ -503,8 +538,8 @@ static int pos_mode_ok(int mode) { return mode == VIT_POS_BICUBIC || mode == VIT
 /* patches per side the resampling kernel takes (vithip_pos_resample_f32) */
 static int pos_grid_ok(int g) { return g >= 1 && g <= 256; }
 
-/* Upload an image; with d_pos_src (device, [1 + g_src^2][D], the checkpoint's position embedding) the resident tensor 3 is resampled
- * from it to the engine's own grid, in front of the fold, the split and the sync. */
+/* Upload an image; with d_pos_src (device, [1 + g_src^2][D], the checkpoint's position embedding) the resident position embedding
+ * is resampled from it to the engine's own grid, in front of finish_install. */
 static int load_image(vit_engine *e, const vit_weight_image *img, const float *d_pos_src, int g_src, int mode) {
     if (!e || !img || !img->f32) return e ? fail(e, VIT_ERR_ARG, "null weight image") : VIT_ERR_ARG;
     if (memcmp(&img->cfg, &e->cfg, sizeof(vit_config)) != 0 || img->count != e->n_weights)
@@ -518,56 +553,43 @@ static int load_image(vit_engine *e, const vit_weight_image *img, const float *d
     if (bf16 && !img->bf16_elems) /* image without a bf16 section: convert the GEMM-operand region on the device, one launch */
         HIP_TRY(e, vithip_f32_to_bf16(e->stream, e->wblob, e->wblob16, img->gemm_floats));
     if (d_pos_src) /* fp32 only: the position embedding is no GEMM operand and has no bf16 copy */
-        HIP_TRY(e, vithip_pos_resample_f32(e->stream, d_pos_src, g_src, e->w[3], e->cfg.img_size / e->cfg.patch_size, e->cfg.embed_dim, mode));
-    if ((rc = fold_ln_weights(e))) return rc;
-    if ((rc = split_weights(e))) return rc;
-    HIP_TRY(e, vithip_stream_sync(e->stream));
-    e->weights_loaded = 1;
-    return VIT_OK;
+        HIP_TRY(e, vithip_pos_resample_f32(e->stream, d_pos_src, g_src, e->w[W_POS], e->cfg.img_size / e->cfg.patch_size, e->cfg.embed_dim, mode));
+    return finish_install(e);
 }
 
 int vit_engine_load_weight_image(vit_engine *e, const vit_weight_image *img) { return load_image(e, img, NULL, 0, 0); }
 
-int vit_engine_load_weights(vit_engine *e, const Network *weights, int count) {
-    if (!e || !weights) return e ? fail(e, VIT_ERR_ARG, "null weights") : VIT_ERR_ARG;
+/* A caller's Network[] against the model: the count, then every tensor present and of its size; the position embedding holds
+ * pos_floats (the checkpoint's grid, which need not be the engine's), pos_note says which grid that is (may be NULL). */
+static int check_network(vit_engine *e, const Network *weights, int count, size_t pos_floats, const char *pos_note) {
     if (count != e->n_weights)
         return fail(e, VIT_ERR_WEIGHTS, "expected %d weight tensors for depth %d, got %d", e->n_weights, e->cfg.depth, count);
     for (int i = 0; i < count; ++i) {
-        const size_t want = vit_config_weight_size(&e->cfg, i);
+        const size_t want = i == W_POS ? pos_floats : vit_config_weight_size(&e->cfg, i);
         if (!weights[i].data)
             return fail(e, VIT_ERR_WEIGHTS, "weight %d is missing (Network[%d].data == NULL; expected %zu floats)", i, i, want);
+        if (weights[i].size != want && i == W_POS && pos_note)
+            return fail(e, VIT_ERR_WEIGHTS, "weight 3 (position embedding) has %zu floats, expected %zu %s", weights[i].size, want, pos_note);
         if (weights[i].size != want)
             return fail(e, VIT_ERR_WEIGHTS, "weight %d has %zu floats, expected %zu", i, weights[i].size, want);
     }
-    /* the separately malloc'd tensors of the reference's Network[] (Network.c:147-191) are packed into the device
-     * layout on the host (8 threads), then uploaded with one copy; bf16 operands are converted on the device */
+    return VIT_OK;
+}
+
+/* The separately malloc'd tensors of the reference's Network[] (Network.c:147-191), checked, are packed into the device layout on
+ * the host (8 threads), then uploaded with one copy (load_image); bf16 operands are converted on the device */
+static int load_network(vit_engine *e, const Network *weights, int count, const float *d_pos_src, int g_src, int mode) {
     vit_weight_image img;
     if (vit_weight_image_build(&img, &e->cfg, weights, count, 0) != 0) return fail(e, VIT_ERR_NOMEM, "out of host memory packing the weights");
-    const int rc = vit_engine_load_weight_image(e, &img);
+    const int rc = load_image(e, &img, d_pos_src, g_src, mode);
     vit_weight_image_free(&img);
     return rc;
 }
 
-int vit_engine_copy_weights(vit_engine *dst, vit_engine *src) {
-    if (!dst || !src) return VIT_ERR_ARG;
-    if (!src->weights_loaded) return fail(dst, VIT_ERR_STATE, "copy_weights: the source engine has no weights");
-    if (memcmp(&dst->cfg, &src->cfg, sizeof(vit_config)) != 0 || dst->opt.dtype != src->opt.dtype)
-        return fail(dst, VIT_ERR_ARG, "copy_weights: engines differ in model configuration or dtype");
-    size_t *off = (size_t *)malloc(sizeof(size_t) * (size_t)dst->n_weights);
-    if (!off) return fail(dst, VIT_ERR_NOMEM, "out of host memory");
-    size_t gemm_floats = 0;
-    const size_t f32_floats = vit_weight_layout(&dst->cfg, off, NULL, &gemm_floats);
-    int rc = alloc_weight_blob(dst, off, f32_floats, gemm_floats);
-    free(off);
-    if (rc) return rc;
-    /* device-to-device: on a multi-GPU node this crosses xGMI once per replica instead of PCIe (the in-process form of
-     * "upload to GPU 0 + broadcast") */
-    HIP_TRY(dst, vithip_memcpy_peer(dst->wblob, dst->opt.device, src->wblob, src->opt.device, dst->wblob_bytes, dst->stream));
-    if ((rc = fold_ln_weights(dst))) return rc; /* recomputed from the replica's own fp32 tensors: 2 launches per layer */
-    if ((rc = split_weights(dst))) return rc;
-    HIP_TRY(dst, vithip_stream_sync(dst->stream));
-    dst->weights_loaded = 1;
-    return VIT_OK;
+int vit_engine_load_weights(vit_engine *e, const Network *weights, int count) {
+    if (!e || !weights) return e ? fail(e, VIT_ERR_ARG, "null weights") : VIT_ERR_ARG;
+    const int rc = check_network(e, weights, count, vit_config_weight_size(&e->cfg, W_POS), NULL);
+    return rc ? rc : load_network(e, weights, count, NULL, 0, 0);
 }
 
 int vit_engine_load_weights_resampled(vit_engine *e, const Network *weights, int count, const vit_pos_resample *rs) {
@@ -581,45 +603,83 @@ int vit_engine_load_weights_resampled(vit_engine *e, const Network *weights, int
     const int g_src = rs->src_img_size / e->cfg.patch_size, g_dst = e->cfg.img_size / e->cfg.patch_size;
     if (!pos_grid_ok(g_src) || !pos_grid_ok(g_dst))
         return fail(e, VIT_ERR_ARG, "load_weights_resampled: grids of %d and %d patches per side, the resampling takes 1..256", g_src, g_dst);
-    if (count != e->n_weights)
-        return fail(e, VIT_ERR_WEIGHTS, "expected %d weight tensors for depth %d, got %d", e->n_weights, e->cfg.depth, count);
     const size_t D = (size_t)e->cfg.embed_dim, pos_src = ((size_t)g_src * g_src + 1) * D, pos_dst = ((size_t)g_dst * g_dst + 1) * D;
-    for (int i = 0; i < count; ++i) {
-        const size_t want = i == 3 ? pos_src : vit_config_weight_size(&e->cfg, i);
-        if (!weights[i].data)
-            return fail(e, VIT_ERR_WEIGHTS, "weight %d is missing (Network[%d].data == NULL; expected %zu floats)", i, i, want);
-        if (weights[i].size != want && i == 3)
-            return fail(e, VIT_ERR_WEIGHTS, "weight 3 (position embedding) has %zu floats, expected %zu for the checkpoint's %d x %d grid "
-                                            "(the engine's own %d x %d grid holds %zu)", weights[i].size, want, g_src, g_src, g_dst, g_dst, pos_dst);
-        if (weights[i].size != want)
-            return fail(e, VIT_ERR_WEIGHTS, "weight %d has %zu floats, expected %zu", i, weights[i].size, want);
-    }
+    char note[128];
+    snprintf(note, sizeof(note), "for the checkpoint's %d x %d grid (the engine's own %d x %d grid holds %zu)", g_src, g_src, g_dst, g_dst, pos_dst);
+    int rc = check_network(e, weights, count, pos_src, note);
+    if (rc) return rc;
     if (g_src == g_dst) return vit_engine_load_weights(e, weights, count); /* nothing to resample: the plain load, bit for bit */
     /* the image is the engine's own layout; its tensor 3 is a placeholder that the kernel overwrites on the device */
     Network *tmp = (Network *)malloc(sizeof(Network) * (size_t)count);
     float *blank = (float *)calloc(pos_dst, sizeof(float));
     float *d_pos = NULL;
-    vit_weight_image img;
-    int rc = (tmp && blank) ? VIT_OK : fail(e, VIT_ERR_NOMEM, "out of host memory");
+    rc = (tmp && blank) ? VIT_OK : fail(e, VIT_ERR_NOMEM, "out of host memory");
     if (!rc) {
         memcpy(tmp, weights, sizeof(Network) * (size_t)count);
-        tmp[3].data = blank;
-        tmp[3].size = pos_dst;
-        if (vit_weight_image_build(&img, &e->cfg, tmp, count, 0) != 0) rc = fail(e, VIT_ERR_NOMEM, "out of host memory packing the weights");
-    }
-    if (!rc) {
+        tmp[W_POS].data = blank; tmp[W_POS].size = pos_dst;
         int hrc = vithip_set_device(e->opt.device);
         if (!hrc) hrc = vithip_malloc((void **)&d_pos, pos_src * sizeof(float));
-        if (!hrc) hrc = vithip_memcpy_h2d(d_pos, weights[3].data, pos_src * sizeof(float), e->stream);
+        if (!hrc) hrc = vithip_memcpy_h2d(d_pos, weights[W_POS].data, pos_src * sizeof(float), e->stream);
         rc = hrc ? fail(e, VIT_ERR_HIP, "load_weights_resampled: HIP error %d (%s) staging the checkpoint's position embedding", hrc,
                         vithip_error_string(hrc))
-                 : load_image(e, &img, d_pos, g_src, rs->mode);
+                 : load_network(e, tmp, count, d_pos, g_src, rs->mode);
         if (e->stream) vithip_stream_sync(e->stream); /* the staging copy reads the caller's array: not behind this call, whatever failed */
         vithip_free(d_pos);
-        vit_weight_image_free(&img);
     }
     free(tmp); free(blank);
     return rc;
+}
+
+/* dst's weights from src's, device to device: on a multi-GPU node this crosses xGMI once per replica instead of PCIe (the
+ * in-process form of "upload to GPU 0 + broadcast").  Equal grids: ONE peer copy of the whole blob.  Otherwise the
+ * two layouts differ behind the position embedding only, which is staged on dst's device and resampled into dst's own. */
+static int replicate_weights(vit_engine *dst, vit_engine *src, int mode) {
+    const int g_src = src->cfg.img_size / src->cfg.patch_size, g_dst = dst->cfg.img_size / dst->cfg.patch_size, same = g_src == g_dst;
+    if (!same && (!pos_grid_ok(g_src) || !pos_grid_ok(g_dst)))
+        return fail(dst, VIT_ERR_ARG, "copy_weights_resampled: grids of %d and %d patches per side, the resampling takes 1..256", g_src, g_dst);
+    const size_t n = (size_t)dst->n_weights;
+    size_t *off = (size_t *)malloc(sizeof(size_t) * 4 * n);
+    if (!off) return fail(dst, VIT_ERR_NOMEM, "out of host memory");
+    size_t *size = off + n, *soff = off + 2 * n, *ssize = off + 3 * n;
+    size_t gemm_floats = 0, sgemm = 0;
+    const size_t f32_floats = vit_weight_layout(&dst->cfg, off, size, &gemm_floats);
+    const size_t sf32 = vit_weight_layout(&src->cfg, soff, ssize, &sgemm);
+    /* [0, off[W_POS]) | the position embedding's slots | an equally long rest | the bf16 section */
+    const size_t head = off[W_POS], spos_floats = ssize[W_POS];
+    size_t rest = f32_floats, srest = sf32; /* where the tensor laid out behind the position embedding starts */
+    for (size_t i = 0; i < n; ++i) {
+        if (off[i] > head && off[i] < rest) rest = off[i];
+        if (soff[i] > head && soff[i] < srest) srest = soff[i];
+    }
+    const int ok = same || (soff[W_POS] == head && sgemm == gemm_floats && gemm_floats <= head && f32_floats - rest == sf32 - srest);
+    int rc = ok ? alloc_weight_blob(dst, off, f32_floats, gemm_floats) : fail(dst, VIT_ERR_STATE, "copy_weights_resampled: the weight layouts do not line up");
+    free(off);
+    if (rc) return rc;
+    const int dd = dst->opt.device, sd = src->opt.device;
+    if (same) {
+        HIP_TRY(dst, vithip_memcpy_peer(dst->wblob, dd, src->wblob, sd, dst->wblob_bytes, dst->stream));
+        return finish_install(dst); /* the derived operands are recomputed from the replica's own tensors */
+    }
+    float *d_pos = NULL; /* src's position embedding on dst's device: the kernel reads local memory whatever the pair of devices */
+    HIP_TRY(dst, vithip_malloc((void **)&d_pos, spos_floats * sizeof(float)));
+    int hrc = vithip_memcpy_peer(dst->wblob, dd, src->wblob, sd, head * sizeof(float), dst->stream);
+    if (!hrc) hrc = vithip_memset(dst->wblob + head, 0, (rest - head) * sizeof(float), dst->stream); /* slot padding stays zero */
+    if (!hrc) hrc = vithip_memcpy_peer(dst->wblob + rest, dd, src->wblob + srest, sd, (f32_floats - rest) * sizeof(float), dst->stream);
+    if (!hrc && dst->wblob16) hrc = vithip_memcpy_peer(dst->wblob16, dd, src->wblob16, sd, gemm_floats * sizeof(unsigned short), dst->stream);
+    if (!hrc) hrc = vithip_memcpy_peer(d_pos, dd, src->w[W_POS], sd, spos_floats * sizeof(float), dst->stream);
+    if (!hrc) hrc = vithip_pos_resample_f32(dst->stream, d_pos, g_src, dst->w[W_POS], g_dst, dst->cfg.embed_dim, mode);
+    if (dst->stream) vithip_stream_sync(dst->stream);
+    vithip_free(d_pos);
+    if (hrc) return fail(dst, VIT_ERR_HIP, "copy_weights_resampled: HIP error %d (%s)", hrc, vithip_error_string(hrc));
+    return finish_install(dst);
+}
+
+int vit_engine_copy_weights(vit_engine *dst, vit_engine *src) {
+    if (!dst || !src) return VIT_ERR_ARG;
+    if (!src->weights_loaded) return fail(dst, VIT_ERR_STATE, "copy_weights: the source engine has no weights");
+    if (memcmp(&dst->cfg, &src->cfg, sizeof(vit_config)) != 0 || dst->opt.dtype != src->opt.dtype)
+        return fail(dst, VIT_ERR_ARG, "copy_weights: engines differ in model configuration or dtype");
+    return replicate_weights(dst, src, 0);
 }
 
 int vit_engine_copy_weights_resampled(vit_engine *dst, vit_engine *src, int mode) {
@@ -630,45 +690,7 @@ int vit_engine_copy_weights_resampled(vit_engine *dst, vit_engine *src, int mode
     same.img_size = dst->cfg.img_size;
     if (memcmp(&dst->cfg, &same, sizeof(vit_config)) != 0 || dst->opt.dtype != src->opt.dtype)
         return fail(dst, VIT_ERR_ARG, "copy_weights_resampled: engines differ in more than img_size, or in dtype");
-    if (dst->cfg.img_size == src->cfg.img_size) return vit_engine_copy_weights(dst, src);
-    const int g_src = src->cfg.img_size / src->cfg.patch_size, g_dst = dst->cfg.img_size / dst->cfg.patch_size;
-    if (!pos_grid_ok(g_src) || !pos_grid_ok(g_dst))
-        return fail(dst, VIT_ERR_ARG, "copy_weights_resampled: grids of %d and %d patches per side, the resampling takes 1..256", g_src, g_dst);
-    const size_t n = (size_t)dst->n_weights;
-    size_t *off = (size_t *)malloc(sizeof(size_t) * 4 * n);
-    if (!off) return fail(dst, VIT_ERR_NOMEM, "out of host memory");
-    size_t *size = off + n, *soff = off + 2 * n, *ssize = off + 3 * n;
-    size_t gemm_floats = 0, sgemm = 0;
-    const size_t f32_floats = vit_weight_layout(&dst->cfg, off, size, &gemm_floats);
-    const size_t sf32 = vit_weight_layout(&src->cfg, soff, ssize, &sgemm);
-    /* the two layouts differ behind tensor 3 only: [0, off[3]) | tensor 3's slots | an equally long rest | the bf16 section */
-    const size_t head = off[3], spos_floats = ssize[3];
-    size_t rest = f32_floats, srest = sf32; /* where the tensor laid out behind tensor 3 starts */
-    for (size_t i = 0; i < n; ++i) {
-        if (off[i] > head && off[i] < rest) rest = off[i];
-        if (soff[i] > head && soff[i] < srest) srest = soff[i];
-    }
-    const int ok = soff[3] == head && sgemm == gemm_floats && gemm_floats <= head && f32_floats - rest == sf32 - srest;
-    int rc = ok ? alloc_weight_blob(dst, off, f32_floats, gemm_floats) : fail(dst, VIT_ERR_STATE, "copy_weights_resampled: the weight layouts do not line up");
-    free(off);
-    if (rc) return rc;
-    const int dd = dst->opt.device, sd = src->opt.device;
-    float *d_pos = NULL; /* src's position embedding on dst's device: the kernel reads local memory whatever the pair of devices */
-    HIP_TRY(dst, vithip_malloc((void **)&d_pos, spos_floats * sizeof(float)));
-    int hrc = vithip_memcpy_peer(dst->wblob, dd, src->wblob, sd, head * sizeof(float), dst->stream);
-    if (!hrc) hrc = vithip_memset(dst->wblob + head, 0, (rest - head) * sizeof(float), dst->stream); /* slot padding stays zero */
-    if (!hrc) hrc = vithip_memcpy_peer(dst->wblob + rest, dd, src->wblob + srest, sd, (f32_floats - rest) * sizeof(float), dst->stream);
-    if (!hrc && dst->wblob16) hrc = vithip_memcpy_peer(dst->wblob16, dd, src->wblob16, sd, gemm_floats * sizeof(unsigned short), dst->stream);
-    if (!hrc) hrc = vithip_memcpy_peer(d_pos, dd, src->w[3], sd, spos_floats * sizeof(float), dst->stream);
-    if (!hrc) hrc = vithip_pos_resample_f32(dst->stream, d_pos, g_src, dst->w[3], g_dst, dst->cfg.embed_dim, mode);
-    if (dst->stream) vithip_stream_sync(dst->stream);
-    vithip_free(d_pos);
-    if (hrc) return fail(dst, VIT_ERR_HIP, "copy_weights_resampled: HIP error %d (%s)", hrc, vithip_error_string(hrc));
-    if ((rc = fold_ln_weights(dst))) return rc;
-    if ((rc = split_weights(dst))) return rc;
-    HIP_TRY(dst, vithip_stream_sync(dst->stream));
-    dst->weights_loaded = 1;
-    return VIT_OK;
+    return replicate_weights(dst, src, mode);
 }
 
 int vit_engine_read_weight_image(vit_engine *e, vit_weight_image *img) {
@@ -677,10 +699,9 @@ int vit_engine_read_weight_image(vit_engine *e, vit_weight_image *img) {
     /* an empty image of the right shape (built from a zero-filled model would be wasteful: allocate through the loader) */
     Network *tmp = (Network *)calloc((size_t)e->n_weights, sizeof(Network));
     if (!tmp) return fail(e, VIT_ERR_NOMEM, "out of host memory");
-    size_t *off = (size_t *)malloc(sizeof(size_t) * (size_t)e->n_weights), *size = (size_t *)malloc(sizeof(size_t) * (size_t)e->n_weights);
     size_t gemm_floats = 0;
-    const size_t f32_floats = (off && size) ? vit_weight_layout(&e->cfg, off, size, &gemm_floats) : 0;
-    float *host = f32_floats ? (float *)malloc(e->wblob_bytes) : NULL;
+    const size_t f32_floats = vit_weight_layout(&e->cfg, NULL, NULL, &gemm_floats);
+    float *host = (float *)malloc(e->wblob_bytes);
     int rc = host ? VIT_OK : fail(e, VIT_ERR_NOMEM, "out of host memory");
     if (!rc) {
         rc = vithip_set_device(e->opt.device) || vithip_memcpy_d2h(host, e->wblob, e->wblob_bytes, e->stream) ||
@@ -688,13 +709,13 @@ int vit_engine_read_weight_image(vit_engine *e, vit_weight_image *img) {
         if (rc) rc = fail(e, VIT_ERR_HIP, "read_weight_image: device-to-host copy failed");
     }
     if (!rc) {
-        for (int i = 0; i < e->n_weights; ++i) { tmp[i].data = host + off[i]; tmp[i].size = size[i]; }
+        for (int i = 0; i < e->n_weights; ++i) { tmp[i].data = host + (e->w[i] - e->wblob); tmp[i].size = vit_config_weight_size(&e->cfg, i); }
         const int bf16 = e->opt.dtype == VIT_DTYPE_BF16;
         if (vit_weight_image_build(img, &e->cfg, tmp, e->n_weights, bf16) != 0) rc = fail(e, VIT_ERR_NOMEM, "out of host memory");
         /* the bf16 section is taken from the DEVICE (its own conversion), not re-derived on the host */
         if (!rc && bf16) memcpy(img->bf16, host + f32_floats, gemm_floats * sizeof(unsigned short));
     }
-    free(host); free(off); free(size); free(tmp);
+    free(host); free(tmp);
     return rc;
 }
 
@@ -724,14 +745,13 @@ static int stage_end(vit_engine *e, vithip_stream_t s) {
 typedef struct {
     int stage, bf16;
     const void *A; int lda;
-    const void *W; const float *bias;  /* W [N][K] */
+    vit_gemm_ops ops;                  /* W [N][K], bias; colsum and w_split: the fold's consumers and split engines */
     void *C; int ldc;
     int M, N, K;
     int role;                          /* VITHIP_EPI_BIAS, VITHIP_EPI_BIAS_GELU or VITHIP_EPI_BIAS_RESIDUAL */
-    const float *ln_rows, *ln_colsum;  /* consumer; ln_colsum = column sums of W, NULL for the centred fp32 weights */
+    const float *ln_rows;              /* consumer */
     float *stats_rows, *stats_part;    /* producer */
     unsigned short *x16;               /* bf16 producer: the bf16 copy of C, leading dimension ldc */
-    const void *w_split;               /* split engines: W's pre-split image (vithip_gemm_args.w_split), or NULL */
 } gemm_desc;
 
 static int gemm(vit_engine *e, vithip_stream_t s, const gemm_desc *g, int *stats_ready) {
@@ -744,9 +764,9 @@ static int gemm(vit_engine *e, vithip_stream_t s, const gemm_desc *g, int *stats
                                     [VITHIP_EPI_BIAS_RESIDUAL] = VITHIP_BF16_EPI_F32_RESIDUAL};
         vithip_gemm_bf16_args a;
         memset(&a, 0, sizeof(a));
-        a.A = g->A; a.lda = g->lda; a.W = g->W; a.ldw = g->K; a.bias = g->bias; a.residual = res; a.ldr = ldr;
+        a.A = g->A; a.lda = g->lda; a.W = g->ops.W; a.ldw = g->K; a.bias = g->ops.bias; a.residual = res; a.ldr = ldr;
         a.C = g->C; a.ldc = g->ldc; a.M = g->M; a.N = g->N; a.K = g->K; a.epilogue = epi16[g->role];
-        a.ln_rows = g->ln_rows; a.ln_colsum = g->ln_colsum;
+        a.ln_rows = g->ln_rows; a.ln_colsum = g->ops.colsum;
         if ((ready = g->stats_rows != NULL)) { a.x16 = g->x16; a.ldx16 = g->ldc; a.row_partials = g->stats_part; }
         HIP_TRY(e, vithip_gemm_bf16(s, &a));
     } else {
@@ -759,10 +779,10 @@ static int gemm(vit_engine *e, vithip_stream_t s, const gemm_desc *g, int *stats
             if (s == e->aux_stream[j]) a.workspace = e->gemm_ws[j + 1];
         a.handover_test = e->opt.gemm_handover_test; a.tile = e->opt.gemm_tile;
         a.arith = e->split && g->stage != VIT_STAGE_HEAD; /* every encoder GEMM (the embedding does not come through here) */
-        a.w_split = a.arith ? g->w_split : NULL;
-        a.A = g->A; a.lda = g->lda; a.W = g->W; a.ldw = g->K; a.bias = g->bias; a.residual = res; a.ldr = ldr;
+        a.w_split = a.arith ? g->ops.w_split : NULL;
+        a.A = g->A; a.lda = g->lda; a.W = g->ops.W; a.ldw = g->K; a.bias = g->ops.bias; a.residual = res; a.ldr = ldr;
         a.C = g->C; a.ldc = g->ldc; a.M = g->M; a.N = g->N; a.K = g->K; a.epilogue = g->role;
-        a.ln_rows = g->ln_rows; a.ln_colsum = g->ln_colsum;
+        a.ln_rows = g->ln_rows; a.ln_colsum = g->ops.colsum;
         a.stats_out = g->stats_rows; a.stats_partials = g->stats_part;
         if (!(ready = vithip_gemm_f32_stats_in_epilogue(&a))) a.stats_out = a.stats_partials = NULL;
         HIP_TRY(e, vithip_gemm_f32(s, &a));
@@ -830,9 +850,6 @@ typedef struct {
 
 #define RUN(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
 
-/* element i of an array of esz-byte elements */
-static void *at(const void *p, size_t i, size_t esz) { return (char *)p + i * esz; }
-
 /* conv_proj + flatten_transpose + class_token + pos_emb (ViT_seq.c:25-101).  8-bit input: each lane first normalises its own
  * images into the same rows of f32_stage (one more launch of the embed stage) and embeds from there; decoded images of any size
  * (d_images = the chunk's records): the lane's slice of the records is resized, cropped and normalised into those rows (one launch
@@ -840,7 +857,7 @@ static void *at(const void *p, size_t i, size_t esz) { return (char *)p + i * es
 static int stage_embed(chunk_ctx *c, const void *d_images, const vit_input *in, float *f32_stage) {
     vit_engine *e = c->e;
     const vit_config *cfg = &e->cfg;
-    float **w = e->w;
+    const vit_embed_ops *w = &e->embed;
     const size_t img = (size_t)cfg->in_chans * cfg->img_size * cfg->img_size;
     /* bf16 patch embedding needs K = chans*patch^2 to be a multiple of 64 (two K steps at least) and patch % 8 == 0;
      * its bf16 patch rows live in the (still unused) hidden-layer buffer */
@@ -862,11 +879,11 @@ static int stage_embed(chunk_ctx *c, const void *d_images, const vit_input *in, 
         }
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_EMBED));
         if (embed16)
-            HIP_TRY(e, vithip_patch_embed_bf16(ln->s, images, e->w16[1], w[2], w[0], w[3], ln->x,
+            HIP_TRY(e, vithip_patch_embed_bf16(ln->s, images, w->conv_w16, w->conv_b, w->cls, w->pos, ln->x,
                                                (unsigned short *)e->hbuf + (size_t)ln->off * (c->T - 1) * pk,
                                                ln->n, cfg->img_size, cfg->patch_size, cfg->in_chans, c->D));
         else
-            HIP_TRY(e, vithip_patch_embed_f32(ln->s, images, w[1], w[2], w[0], w[3], ln->x, ln->n,
+            HIP_TRY(e, vithip_patch_embed_f32(ln->s, images, w->conv_w, w->conv_b, w->cls, w->pos, ln->x, ln->n,
                                               cfg->img_size, cfg->patch_size, cfg->in_chans, c->D));
         HIP_TRY(e, stage_end(e, ln->s));
     }
@@ -901,7 +918,7 @@ static int row_stats(chunk_ctx *c, const vit_lane *ln, size_t ldx, float *pairs,
  *   dtype   bf16 engines keep the LN output, qkv, the attention output and the MLP hidden layer in bf16; the residual stream x,
  *           the LayerNorm statistics, softmax and every accumulation stay fp32.
  *   fold    the LayerNorm fold (vit_hip_kernels.h, "LayerNorm folding"): in_proj and fc1 read the raw rows (x, or its bf16 copy)
- *           with the gamma/beta-folded operands (fold_ln_weights) and a pair per row; a LayerNorm becomes a statistics pass,
+ *           with the gamma/beta-folded operands (vit_layer_ops) and a pair per row; a LayerNorm becomes a statistics pass,
  *           or nothing where the residual GEMM in front has left the pairs.  The bf16 Q rows carry the scores' exponent factor.
  *   pruned  prune_last_layer, for chunks whose output reads the class rows only (chunk_ctx.pruned: probabilities, CLS features and CLS taps;
  *           MEAN and TOKENS run the layer in full): K and V of every token, everything else for the class rows only.  The class rows of a [n*T][w]
@@ -915,22 +932,7 @@ static int encoder_layer(chunk_ctx *c, int l) {
     const int bf16 = e->opt.dtype == VIT_DTYPE_BF16, fold = e->fold, feeds_next = l + 1 < e->cfg.depth;
     const int pruned = c->pruned && !feeds_next;
     const size_t esz = bf16 ? sizeof(unsigned short) : sizeof(float); /* GEMM weights and activations */
-    float **lw = e->w + 4 + VIT_WEIGHTS_PER_LAYER * l;
-    unsigned short **lw16 = e->w16 + 4 + VIT_WEIGHTS_PER_LAYER * l;
-    const void *w_qkv = bf16 ? (const void *)lw16[2] : lw[2], *w_out = bf16 ? (const void *)lw16[4] : lw[4],
-               *w_fc1 = bf16 ? (const void *)lw16[8] : lw[8], *w_fc2 = bf16 ? (const void *)lw16[10] : lw[10];
-    const float *b_qkv = lw[3], *b_fc1 = lw[9], *cs_qkv = NULL, *cs_fc1 = NULL;
-    const unsigned char *ws = e->wsplit ? e->wsplit + (size_t)l * e->wsplit_layer : NULL; /* pre-split images (split_weights) */
-    const void *ws_qkv = ws ? ws + e->wsplit_off[0] : NULL, *ws_out = ws ? ws + e->wsplit_off[1] : NULL,
-               *ws_fc1 = ws ? ws + e->wsplit_off[2] : NULL, *ws_fc2 = ws ? ws + e->wsplit_off[3] : NULL;
-    if (fold) { /* the folded in_proj and fc1 (fold_ln_weights) */
-        const size_t wl = (size_t)l * (3 * (size_t)D * D + (size_t)H * D);
-        const float *ff = e->wfoldf + (size_t)l * (6 * D + 2 * H);
-        w_qkv = bf16 ? (const void *)(e->wfold16 + wl) : (const void *)(e->wfold32 + wl);
-        w_fc1 = at(w_qkv, 3 * (size_t)D * D, esz);
-        b_qkv = ff + 3 * D; b_fc1 = ff + 6 * D + H;
-        if (bf16) { cs_qkv = ff; cs_fc1 = ff + 6 * D; } /* the fp32 weights are centred: nothing to subtract */
-    }
+    const vit_layer_ops *o = &e->layer[l];
     /* the rows the layer computes past K and V: every token row, or the class rows (row step T); and their pairs (fold) */
     const int r = pruned ? T : 1;
     int rows[VIT_MAX_LANES], ln2_ready[VIT_MAX_LANES];
@@ -942,20 +944,19 @@ static int encoder_layer(chunk_ctx *c, int l) {
 
     for (int j = 0; j < c->L; ++j) { /* LN1 (ViT_seq.c:281); folded: its statistics, unless the fc2 in front has left them */
         vit_lane *ln = &c->lane[j];
-        if (!fold) RUN(layernorm(c, ln->s, ln->x, D, ln->y, D, lw[0], lw[1], ln->n * T));
+        if (!fold) RUN(layernorm(c, ln->s, ln->x, D, ln->y, D, o->ln1_g, o->ln1_b, ln->n * T));
         else if (!ln->stats_ready) RUN(row_stats(c, ln, D, ln->tok_pairs, ln->n * T));
     }
     for (int j = 0; j < c->L; ++j) { /* QKV in_proj (ViT_seq.c:134-147) */
         vit_lane *ln = &c->lane[j];
-        gemm_desc g = {.stage = VIT_STAGE_QKV, .bf16 = bf16, .A = fold ? ln->xa : ln->y, .lda = D, .W = w_qkv, .bias = b_qkv,
-                       .C = ln->qkv, .ldc = 3 * D, .M = ln->n * T, .N = 3 * D, .K = D, .role = VITHIP_EPI_BIAS,
-                       .ln_rows = ln->tok_pairs, .ln_colsum = cs_qkv, .w_split = ws_qkv};
+        gemm_desc g = {.stage = VIT_STAGE_QKV, .bf16 = bf16, .A = fold ? ln->xa : ln->y, .lda = D, .ops = o->qkv, .C = ln->qkv,
+                       .ldc = 3 * D, .M = ln->n * T, .N = 3 * D, .K = D, .role = VITHIP_EPI_BIAS, .ln_rows = ln->tok_pairs};
         if (pruned) { /* K and V of every token (in_proj rows D..3D), then Q of the class rows, whose pairs are gathered first */
             gemm_desc kv = g;
-            kv.W = at(w_qkv, (size_t)D * D, esz); kv.bias = b_qkv + D; kv.C = at(ln->qkv, D, esz); kv.N = 2 * D;
-            kv.ln_colsum = cs_qkv ? cs_qkv + D : NULL;
+            kv.ops.W = at(g.ops.W, (size_t)D * D, esz); kv.ops.bias = g.ops.bias + D; kv.C = at(ln->qkv, D, esz); kv.N = 2 * D;
+            kv.ops.colsum = g.ops.colsum ? g.ops.colsum + D : NULL;
             /* the image of rows D.. starts at a panel boundary only when D is a multiple of 128 (panel = 128 rows x K x 6 bytes) */
-            kv.w_split = ws_qkv && D % 128 == 0 ? at(ws_qkv, (size_t)D * D * 6, 1) : NULL;
+            kv.ops.w_split = g.ops.w_split && D % 128 == 0 ? at(g.ops.w_split, (size_t)D * D * 6, 1) : NULL;
             RUN(gemm(e, ln->s, &kv, NULL));
             if (fold) {
                 HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
@@ -980,28 +981,28 @@ static int encoder_layer(chunk_ctx *c, int l) {
     for (int j = 0; j < c->L; ++j) { /* out_proj + residual (ViT_seq.c:219-227,286-288): x += y . Wo^T + bo; folded, it also
                                       * leaves the pairs of LN2 -- except in the pruned fp32 layer, which takes them in a pass */
         vit_lane *ln = &c->lane[j];
-        gemm_desc g = {.stage = VIT_STAGE_OUTPROJ, .bf16 = bf16, .A = ln->y, .lda = r * D, .W = w_out, .bias = lw[5],
-                       .C = ln->x, .ldc = r * D, .M = rows[j], .N = D, .K = D, .role = VITHIP_EPI_BIAS_RESIDUAL, .w_split = ws_out};
+        gemm_desc g = {.stage = VIT_STAGE_OUTPROJ, .bf16 = bf16, .A = ln->y, .lda = r * D, .ops = o->out, .C = ln->x,
+                       .ldc = r * D, .M = rows[j], .N = D, .K = D, .role = VITHIP_EPI_BIAS_RESIDUAL};
         if (fold && (bf16 || !pruned)) { g.stats_rows = pairs[j]; g.stats_part = ln->partials; g.x16 = bf16 ? ln->xa : NULL; }
         RUN(gemm(e, ln->s, &g, &ln2_ready[j]));
     }
     for (int j = 0; j < c->L; ++j) { /* LN2 (ViT_seq.c:291); pruned: of the class rows, into a compact [n][D] at the head of y */
         const vit_lane *ln = &c->lane[j];
-        if (!fold) RUN(layernorm(c, ln->s, ln->x, (size_t)r * D, ln->y, D, lw[6], lw[7], rows[j]));
+        if (!fold) RUN(layernorm(c, ln->s, ln->x, (size_t)r * D, ln->y, D, o->ln2_g, o->ln2_b, rows[j]));
         else if (!ln2_ready[j]) RUN(row_stats(c, ln, (size_t)r * D, pairs[j], rows[j]));
     }
     for (int j = 0; j < c->L; ++j) { /* fc1 + GELU (ViT_seq.c:258-264) */
         const vit_lane *ln = &c->lane[j];
-        gemm_desc g = {.stage = VIT_STAGE_FC1, .bf16 = bf16, .A = ln->y, .lda = D, .W = w_fc1, .bias = b_fc1, .C = ln->h, .ldc = H,
-                       .M = rows[j], .N = H, .K = D, .role = VITHIP_EPI_BIAS_GELU, .w_split = ws_fc1};
-        if (fold) { g.A = ln->xa; g.lda = r * D; g.ln_rows = pairs[j]; g.ln_colsum = cs_fc1; }
+        gemm_desc g = {.stage = VIT_STAGE_FC1, .bf16 = bf16, .A = ln->y, .lda = D, .ops = o->fc1, .C = ln->h, .ldc = H,
+                       .M = rows[j], .N = H, .K = D, .role = VITHIP_EPI_BIAS_GELU};
+        if (fold) { g.A = ln->xa; g.lda = r * D; g.ln_rows = pairs[j]; }
         RUN(gemm(e, ln->s, &g, NULL));
     }
     for (int j = 0; j < c->L; ++j) { /* fc2 + residual (ViT_seq.c:266,297-299): x += h . W2^T + b2; folded, it also leaves the
                                       * pairs of the next layer's LN1 when there is one */
         vit_lane *ln = &c->lane[j];
-        gemm_desc g = {.stage = VIT_STAGE_FC2, .bf16 = bf16, .A = ln->h, .lda = H, .W = w_fc2, .bias = lw[11], .C = ln->x,
-                       .ldc = r * D, .M = rows[j], .N = D, .K = H, .role = VITHIP_EPI_BIAS_RESIDUAL, .w_split = ws_fc2};
+        gemm_desc g = {.stage = VIT_STAGE_FC2, .bf16 = bf16, .A = ln->h, .lda = H, .ops = o->fc2, .C = ln->x, .ldc = r * D,
+                       .M = rows[j], .N = D, .K = H, .role = VITHIP_EPI_BIAS_RESIDUAL};
         if (fold && feeds_next) { g.stats_rows = ln->tok_pairs; g.stats_part = ln->partials; g.x16 = bf16 ? ln->xa : NULL; }
         RUN(gemm(e, ln->s, &g, &ln->stats_ready));
     }
@@ -1013,16 +1014,15 @@ static int encoder_layer(chunk_ctx *c, int l) {
 static int stage_head(chunk_ctx *c, float *d_probs, int *d_label, float *d_prob) {
     vit_engine *e = c->e;
     const int T = c->T, D = c->D, NC = c->NC;
-    float **fw = e->w + 4 + VIT_WEIGHTS_PER_LAYER * e->cfg.depth;
     for (int j = 0; j < c->L; ++j) {
         const vit_lane *ln = &c->lane[j];
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
-        HIP_TRY(e, vithip_layernorm_f32(ln->s, ln->x, (size_t)T * D, e->z + (size_t)ln->off * D, (size_t)D, fw[0], fw[1], ln->n, D));
+        HIP_TRY(e, vithip_layernorm_f32(ln->s, ln->x, (size_t)T * D, e->z + (size_t)ln->off * D, (size_t)D, e->final.ln_g, e->final.ln_b, ln->n, D));
         HIP_TRY(e, stage_end(e, ln->s));
     }
     for (int j = 0; j < c->L; ++j) {
         const vit_lane *ln = &c->lane[j];
-        const gemm_desc g = {.stage = VIT_STAGE_HEAD, .A = e->z + (size_t)ln->off * D, .lda = D, .W = fw[2], .bias = fw[3],
+        const gemm_desc g = {.stage = VIT_STAGE_HEAD, .A = e->z + (size_t)ln->off * D, .lda = D, .ops = e->final.head,
                              .C = e->logits + (size_t)ln->off * NC, .ldc = NC, .M = ln->n, .N = NC, .K = D, .role = VITHIP_EPI_BIAS};
         RUN(gemm(e, ln->s, &g, NULL));
     }
@@ -1066,15 +1066,14 @@ static float *pool_scratch(const chunk_ctx *c, const vit_lane *ln, size_t *bytes
 static int stage_features(chunk_ctx *c, const vit_output *out) {
     vit_engine *e = c->e;
     const size_t T = (size_t)c->T, D = (size_t)c->D;
-    float **fw = e->w + 4 + VIT_WEIGHTS_PER_LAYER * e->cfg.depth;
     for (int j = 0; j < c->L; ++j) {
         const vit_lane *ln = &c->lane[j];
         float *dst = out->dst + (size_t)ln->off * out_row_elems(e, out);
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
         if (out->spec.kind == VIT_FEAT_CLS)
-            HIP_TRY(e, vithip_layernorm_f32(ln->s, ln->x, T * D, dst, D, fw[0], fw[1], ln->n, c->D));
+            HIP_TRY(e, vithip_layernorm_f32(ln->s, ln->x, T * D, dst, D, e->final.ln_g, e->final.ln_b, ln->n, c->D));
         else if (out->spec.kind == VIT_FEAT_TOKENS)
-            HIP_TRY(e, vithip_layernorm_f32(ln->s, ln->x, D, dst, D, fw[0], fw[1], ln->n * c->T, c->D));
+            HIP_TRY(e, vithip_layernorm_f32(ln->s, ln->x, D, dst, D, e->final.ln_g, e->final.ln_b, ln->n * c->T, c->D));
         else {
             const size_t esz = e->opt.dtype == VIT_DTYPE_BF16 ? sizeof(unsigned short) : sizeof(float);
             size_t need;
@@ -1082,7 +1081,7 @@ static int stage_features(chunk_ctx *c, const vit_output *out) {
             if (need == 0 || need > (size_t)ln->n * T * D * esz || ((size_t)scratch & 15))
                 return fail(e, VIT_ERR_STATE, "features: the pooling scratch (%zu bytes) does not fit the lane's own %zu bytes of y", need,
                             (size_t)ln->n * T * D * esz);
-            HIP_TRY(e, vithip_layernorm_pool_f32(ln->s, ln->x, D, dst, D, fw[0], fw[1], ln->n, c->T, 1, c->D, out->spec.l2_normalize,
+            HIP_TRY(e, vithip_layernorm_pool_f32(ln->s, ln->x, D, dst, D, e->final.ln_g, e->final.ln_b, ln->n, c->T, 1, c->D, out->spec.l2_normalize,
                                                  scratch));
         }
         if (out->spec.kind == VIT_FEAT_CLS && out->spec.l2_normalize) HIP_TRY(e, vithip_l2_normalize_rows_f32(ln->s, dst, D, ln->n, c->D));
@@ -1118,13 +1117,12 @@ static int stage_cls_attention(chunk_ctx *c, const vit_output *out) {
  * has updated the class rows of x alone, which is all that CLS reads. */
 static int stage_tap(chunk_ctx *c, const vit_output *out, int j) {
     vit_engine *e = c->e;
-    float **fw = e->w + 4 + VIT_WEIGHTS_PER_LAYER * e->cfg.depth;
     const size_t row = out_row_elems(e, out), block = tap_block_elems(e, out->tap.kind);
     for (int k = 0; k < c->L; ++k) {
         const vit_lane *ln = &c->lane[k];
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
         HIP_TRY(e, vithip_tap_f32(ln->s, ln->x, (size_t)c->D, out->dst + (size_t)ln->off * row + (size_t)j * block, row,
-                                  out->tap.norm ? fw[0] : NULL, out->tap.norm ? fw[1] : NULL, ln->n, c->T, c->D, out->tap.kind));
+                                  out->tap.norm ? e->final.ln_g : NULL, out->tap.norm ? e->final.ln_b : NULL, ln->n, c->T, c->D, out->tap.kind));
         HIP_TRY(e, stage_end(e, ln->s));
     }
     return VIT_OK;
