@@ -237,8 +237,9 @@ int vit_engine_features_host_u8(vit_engine *e, const unsigned char *const *image
  * The same four calls from decoded images of any size: the engine runs the whole evaluation transform of a ViT checkpoint
  *     Resize(resize_shorter) -> CenterCrop(cfg.img_size) -> ToTensor() -> Normalize(mean, std)
  * on the device, in one kernel in front of the patch embedding of each lane (vithip_images_u8_resize_crop_to_f32 in
- * vit_hip_kernels.h states the arithmetic: Pillow's 8-bit bilinear resize as torchvision runs it, bit for bit).  The outputs are
- * bit-identical to the matching _u8 call on the bytes that torchvision's Resize + CenterCrop give, for every option and dtype.
+ * vit_hip_kernels.h states the arithmetic: Pillow's 8-bit bilinear resize as torchvision runs it, bit for bit; bicubic instead after
+ * vit_engine_set_resize_filter, below).  The outputs are bit-identical to the matching _u8 call on the bytes that torchvision's
+ * Resize + CenterCrop give, for every option and dtype.
  *
  * images: a HOST array of n records in all four calls, read during the call only; pixels [height][width][cfg.in_chans] uint8, rows
  * packed, any address: DEVICE pointers in the _device_ calls, HOST pointers in the _host_ ones.  Everything else mirrors the _u8
@@ -271,6 +272,22 @@ int vit_engine_features_device_images(vit_engine *e, const vit_image_u8 *images,
                                       float *d_out, void *stream);
 int vit_engine_features_host_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, const vit_feature_spec *spec,
                                     float *const *out);
+
+/*
+ * The resize filter of every _images call of this engine (the eight above and below: forward, features, cls_attention, intermediate,
+ * host and device).  It belongs to a checkpoint's evaluation transform, so it is engine state: VIT_RESIZE_BILINEAR, the default, is
+ * torchvision's own ViT transform; VIT_RESIZE_BICUBIC is Resize(R, interpolation=BICUBIC) on PIL images -- DINOv2, DINO, DeiT, MAE,
+ * timm's vit_* configs -- bit for bit like the bilinear one (vithip_images_u8_resize_crop_to_f32_filter in vit_hip_kernels.h states
+ * the arithmetic).  The outputs are then bit-identical to the matching _u8 call on the bytes that transform gives.
+ * The setter takes effect from the next _images call.  The filter is read on the host when a call enqueues its work (the record check
+ * of the call uses it too) and travels in that call's launches, so changing it between calls needs no synchronisation with work that
+ * is still running; like every other call on an engine it must not run concurrently with another call on the same engine.  The
+ * size limits are those of the bilinear filter.  Every engine has its own filter.  VIT_ERR_ARG for an unknown value (or a NULL
+ * engine): the filter stays what it was.
+ */
+enum { VIT_RESIZE_BILINEAR = 0, VIT_RESIZE_BICUBIC = 1 };
+int vit_engine_set_resize_filter(vit_engine *e, int filter);
+int vit_engine_get_resize_filter(const vit_engine *e);  /* -1 for a NULL engine */
 
 /*
  * The class token's attention over the tokens, in the LAST encoder layer, instead of probabilities: the DINO-style saliency map of a

@@ -383,6 +383,31 @@ int vithip_images_u8_resize_crop_to_f32(vithip_stream_t stream, const vithip_ima
 /* The launcher's checks of the records and sizes alone, for callers that must know before they enqueue anything: 0 = accepted,
  * i + 1 = record i is refused, -1 = one of n, img_size, chans, resize_shorter (or a NULL array) is. */
 int vithip_images_u8_resize_crop_check(const vithip_image_u8 *images, int n, int img_size, int chans, int resize_shorter);
+/*
+ * The same transform with the resize filter chosen: the two entries above are the VITHIP_RESIZE_BILINEAR case of these, to the bit.
+ * VITHIP_RESIZE_BICUBIC is Pillow's Image.resize((ow, oh), BICUBIC) on 8 bits per channel -- torchvision's
+ * Resize(R, interpolation=BICUBIC) on PIL images, the evaluation transform of DINOv2, DINO, DeiT, MAE and timm's vit_* configs -- bit
+ * for bit.  Everything is as stated for bilinear above (IEEE double, no fused multiply-add, true divisions; scale, fs, ss, center, xmin,
+ * xmax and cnt by the same expressions), except:
+ *     support = 2.0 * fs
+ *     w[x] = f((x + xmin - center + 0.5) * ss), with a = -0.5 and t = |argument|:
+ *            f = ((a + 2.0) * t - (a + 3.0)) * t * t + 1     if t < 1.0
+ *            f = (((t - 5) * t + 8) * t - 4) * a             if t < 2.0
+ *            f = 0.0                                         otherwise
+ *     ww = sum of w[x] in index order; w[x] /= ww if ww != 0.0
+ *     k[x] = w[x] < 0 ? (int)(-0.5 + w[x] * 4194304.0) : (int)(0.5 + w[x] * 4194304.0)
+ *     a pass: acc = 2097152 + sum_x pixel[xmin + x] * k[x] in int32, byte = min(max(acc >> 22, 0), 255), the shift arithmetic
+ * The coefficients are signed, so a pass can leave [0, 255] on both sides and both passes clamp on both.  An output index has at most
+ * (int)(4 * fs) + 2 taps (bilinear: (int)(2 * fs) + 2), and the int32 sum cannot overflow: the positive coefficients of an index sum
+ * to less than 1.2 * 2^22.
+ * Size limit: the same for both filters -- a source's shorter side is at most 64 * resize_shorter (the bicubic kernel keeps coefficient
+ * tables of twice the size for it) -- and so are all the other refusals.  An unknown filter: hipErrorInvalidValue, nothing launched,
+ * and -1 from the check.
+ */
+enum { VITHIP_RESIZE_BILINEAR = 0, VITHIP_RESIZE_BICUBIC = 1 };
+int vithip_images_u8_resize_crop_to_f32_filter(vithip_stream_t stream, const vithip_image_u8 *images, int n, float *dst, int img_size,
+                                               int chans, int resize_shorter, int filter, const float *mean, const float *std);
+int vithip_images_u8_resize_crop_check_filter(const vithip_image_u8 *images, int n, int img_size, int chans, int resize_shorter, int filter);
 
 /*
  * Embedding outputs (csrc/vit_pool.hip).  LayerNorm and mean over tokens in ONE pass over x; the LayerNorm rows are never stored:

@@ -3,11 +3,15 @@
 and the host resize it replaces.  One JSON line per measurement.
 
     python3 tools/preproc_time.py [--steps K] [--warmup W] [--images N] [--parts kernel,device,host,cpu] [--dtypes f32,bf16]
+                                  [--filter bilinear,bicubic] [--sources 375x500,1080x1920]
 
 Sources: N images (default 256) of 375 x 500 and of 1080 x 1920 (8 distinct random images of each size, repeated), R = 256, S = 224.
   kernel  device time of the vithip_images_u8_resize_crop_to_f32 launches alone (events around REPS calls back to back, median of K
           windows after W warm-up windows), alternated in the same process with vithip_images_u8_to_f32 on N pre-resized images; both set
           against their bytes-moved floors (source window read + fp32 write, resp. 5 bytes per element, at 6.3 TB/s of HBM);
+          --filter bilinear,bicubic adds a leg "resize_crop_bicubic" (vithip_images_u8_resize_crop_to_f32_filter, Pillow's BICUBIC) to
+          the same alternation and checks its bits against tests/preproc_filter_model.py; the bilinear leg always goes through the
+          entry without a filter, so that VIT_HIP_LIBRARY may name an earlier build (A/B timing of the bilinear kernel);
   device  vit_engine_forward_device_images against vit_engine_forward_device_u8 on the pre-resized bytes, ViT-B/16, per dtype: what
           share of a step the preprocessing is.  The two must give the same bits (checked);
   host    vit_engine_forward_host_images on the full-size sources against vit_engine_forward_host_u8 on the pre-resized bytes (fp32
@@ -37,8 +41,9 @@ REPS = 10
 HBM_BPS = 6.3e12  # achievable HBM rate of the MI355X
 
 
-def window_bytes(h, w):
-    """Bytes of the source that the crop's supports touch (rows x columns x channels): the least one read of it moves."""
+def window_bytes(h, w, support=1.0):
+    """Bytes of the source that the crop's supports touch (rows x columns x channels): the least one read of it moves.  support: the
+    filter's, in units of max(scale, 1): 1 bilinear, 2 bicubic."""
     import preproc_model as M
     oh, ow = M.resized_size(h, w, R)
     top, left = M.crop_origin(oh, ow, S)
@@ -47,7 +52,7 @@ def window_bytes(h, w):
         if inn == out:
             return S
         scale = inn / out
-        sup = max(scale, 1.0)
+        sup = support * max(scale, 1.0)
         lo = max(int((first + 0.5) * scale - sup + 0.5), 0)
         hi = min(int((first + S - 1 + 0.5) * scale + sup + 0.5), inn)
         return hi - lo
@@ -65,8 +70,16 @@ def main():
     ap.add_argument("--images", type=int, default=256)
     ap.add_argument("--parts", default="kernel,device,host,cpu")
     ap.add_argument("--dtypes", default="f32,bf16")
+    ap.add_argument("--filter", default="bilinear", help="bilinear | bilinear,bicubic: the legs of the kernel part")
+    ap.add_argument("--sources", default=",".join(SIZES), help="which of " + ", ".join(SIZES))
     a = ap.parse_args()
     parts, n = a.parts.split(","), a.images
+    filters = a.filter.split(",")
+    if "bilinear" not in filters or set(filters) - {"bilinear", "bicubic"}:
+        sys.exit("--filter: bilinear or bilinear,bicubic")
+    for k in list(SIZES):
+        if k not in a.sources.split(","):
+            del SIZES[k]
 
     pkg = importlib.import_module("vision-transformer-opencl_amd")
     B = importlib.import_module("vision-transformer-opencl_amd.binding")
@@ -109,11 +122,15 @@ def main():
     records = {k: B.image_records(t) for k, t in triples.items()}
     d_u8 = {k: B.DeviceArray.from_numpy(v) for k, v in u8.items()}
     d_f32 = B.DeviceArray((n, CH, S, S))
+    d_cubic = B.DeviceArray((n, CH, S, S)) if "bicubic" in filters else None
 
     if "kernel" in parts:
         for k in SIZES:
             legs = {"resize_crop": lambda k=k: L.vithip_images_u8_resize_crop_to_f32(None, records[k], n, d_f32.ptr, S, CH, R, m, s),
                     "u8_to_f32": lambda k=k: L.vithip_images_u8_to_f32(None, d_u8[k].ptr, d_f32.ptr, n, S, CH, m, s)}
+            if d_cubic is not None:
+                legs["resize_crop_bicubic"] = lambda k=k: L.vithip_images_u8_resize_crop_to_f32_filter(
+                    None, records[k], n, d_cubic.ptr, S, CH, R, B.RESIZE_FILTERS["bicubic"], m, s)
             ms = {leg: [] for leg in legs}
             order = list(legs)
             for step in range(a.warmup + a.steps):
@@ -123,6 +140,11 @@ def main():
                         ms[leg].append(t)
             assert np.array_equal(d_f32.numpy().view(np.uint32), B.images_u8_to_f32(u8[k], mean, std).view(np.uint32))
             floor = {"resize_crop": n * (window_bytes(*SIZES[k]) + CH * S * S * 4) / HBM_BPS * 1e3, "u8_to_f32": n * CH * S * S * 5 / HBM_BPS * 1e3}
+            if d_cubic is not None:
+                import preproc_filter_model as FM
+                want = FM.preprocess(distinct[k], R, S, mean, std, FM.BICUBIC)[pick]
+                assert np.array_equal(d_cubic.numpy().view(np.uint32), want.view(np.uint32))
+                floor["resize_crop_bicubic"] = n * (window_bytes(*SIZES[k], support=2.0) + CH * S * S * 4) / HBM_BPS * 1e3
             for leg in order:
                 med = statistics.median(ms[leg])
                 print(json.dumps(dict({"part": "kernel", "source": k, "images": n, "leg": leg, "calls_per_window": REPS,
@@ -130,6 +152,9 @@ def main():
                       flush=True)
             print(json.dumps({"part": "kernel", "source": k, "resize_crop_over_u8_to_f32": round(statistics.median(ms["resize_crop"]) /
                                                                                                 statistics.median(ms["u8_to_f32"]), 2)}), flush=True)
+            if d_cubic is not None:
+                print(json.dumps({"part": "kernel", "source": k, "bicubic_over_bilinear": round(
+                    statistics.median(ms["resize_crop_bicubic"]) / statistics.median(ms["resize_crop"]), 2)}), flush=True)
 
     def host_timed(fn, sync):
         sync()

@@ -99,6 +99,13 @@ class CPreproc(C.Structure):  # vit_preproc: Resize(resize_shorter) -> CenterCro
     _fields_ = [("resize_shorter", C.c_int), ("mean", C.c_float * 4), ("std", C.c_float * 4)]
 
 
+RESIZE_FILTERS = {"bilinear": 0, "bicubic": 1}  # VIT_RESIZE_* / VITHIP_RESIZE_*
+
+
+def _resize_filter(filter) -> int:
+    return RESIZE_FILTERS[filter] if isinstance(filter, str) else int(filter)
+
+
 def feature_spec(kind, l2_normalize=False) -> CFeatureSpec:
     """kind: "cls" | "mean" | "tokens" (or a raw VIT_FEAT_* integer, passed through unchecked for the C side to judge)."""
     k = FEATURE_KINDS[kind] if isinstance(kind, str) else int(kind)
@@ -241,6 +248,12 @@ def lib() -> C.CDLL:
             recs = C.POINTER(CImageU8)
             L.vithip_images_u8_resize_crop_to_f32.argtypes = [C.c_void_p, recs, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, f32p, f32p]
             L.vithip_images_u8_resize_crop_check.argtypes = [recs, C.c_int, C.c_int, C.c_int, C.c_int]
+        if hasattr(L, "vit_engine_set_resize_filter"):  # an earlier build (see above) resizes bilinearly only
+            recs = C.POINTER(CImageU8)
+            L.vithip_images_u8_resize_crop_to_f32_filter.argtypes = [C.c_void_p, recs, C.c_int, C.c_void_p] + [C.c_int] * 4 + [f32p, f32p]
+            L.vithip_images_u8_resize_crop_check_filter.argtypes = [recs] + [C.c_int] * 5
+            L.vit_engine_set_resize_filter.argtypes = [C.c_void_p, C.c_int]
+            L.vit_engine_get_resize_filter.argtypes = [C.c_void_p]
         if hasattr(L, "vit_engine_cls_attention_device"):  # an earlier build (see above) has no attention calls
             L.vit_engine_attention_row_elems.restype = C.c_size_t
             L.vit_engine_attention_row_elems.argtypes = [C.c_void_p, C.POINTER(CAttentionSpec)]
@@ -1076,17 +1089,18 @@ def preproc_params(resize_shorter: int, mean, std, chans: int) -> CPreproc:
     return pp
 
 
-def images_u8_resize_crop_to_f32(images, img_size: int, resize_shorter: int, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
-    """vithip_images_u8_resize_crop_to_f32: a list of uint8 images [H][W][C] of any sizes -> [n][C][S][S] fp32, torchvision's
-    Resize(resize_shorter) -> CenterCrop(img_size) -> ToTensor() -> Normalize(mean, std)."""
+def images_u8_resize_crop_to_f32(images, img_size: int, resize_shorter: int, mean=IMAGENET_MEAN, std=IMAGENET_STD,
+                                 filter="bilinear") -> np.ndarray:
+    """vithip_images_u8_resize_crop_to_f32_filter: a list of uint8 images [H][W][C] of any sizes -> [n][C][S][S] fp32, torchvision's
+    Resize(resize_shorter) -> CenterCrop(img_size) -> ToTensor() -> Normalize(mean, std); filter: "bilinear" | "bicubic", Pillow's."""
     chans = 1 if np.asarray(images[0]).ndim == 2 else np.asarray(images[0]).shape[2]
     keep, _ = host_image_records(images, chans)
     m, s = _norm_consts(mean, std, chans)
     dev = [DeviceArray.from_numpy(im) for im in keep]
     recs = image_records((d.ptr, im.shape[0], im.shape[1]) for d, im in zip(dev, keep))
     dd = DeviceArray((len(keep), chans, img_size, img_size))
-    hip_check(lib().vithip_images_u8_resize_crop_to_f32(None, recs, len(keep), dd.ptr, img_size, chans, resize_shorter, m, s),
-              "vithip_images_u8_resize_crop_to_f32")
+    hip_check(lib().vithip_images_u8_resize_crop_to_f32_filter(None, recs, len(keep), dd.ptr, img_size, chans, resize_shorter,
+                                                               _resize_filter(filter), m, s), "vithip_images_u8_resize_crop_to_f32_filter")
     return dd.numpy()
 
 
@@ -1381,6 +1395,15 @@ class Engine:
         L = lib()
         L.vit_engine_set_lanes.argtypes = [C.c_void_p, C.c_int]
         self._check(L.vit_engine_set_lanes(self._h, lanes), "vit_engine_set_lanes")
+
+    def set_resize_filter(self, filter) -> None:
+        """vit_engine_set_resize_filter: "bilinear" (the default) | "bicubic", the Resize filter of every *_images call from the next one
+        on; read on the host when a call enqueues, so it may change between calls without a sync."""
+        self._check(lib().vit_engine_set_resize_filter(self._h, _resize_filter(filter)), "vit_engine_set_resize_filter")
+
+    def get_resize_filter(self) -> str:
+        v = lib().vit_engine_get_resize_filter(self._h)
+        return {n: k for k, n in RESIZE_FILTERS.items()}[v]
 
     def set_profile(self, on: bool) -> None:
         self._check(lib().vit_engine_set_profile(self._h, 1 if on else 0), "vit_engine_set_profile")

@@ -5,7 +5,7 @@
 // torchvision's evaluation transform on the images a dataset hands it, i.e. Pillow's Image.resize(..., BILINEAR) on 8 bits per
 // channel, bit for bit (include/vit_hip_kernels.h states the arithmetic; tests/preproc_model.py restates it in numpy):
 //   * per axis a coefficient table in IEEE double (no fused multiply-add, true divisions), turned into 2^22 fixed point;
-//   * a pass is an int32 sum 2^21 + sum pixel * k, shifted right by 22 and clamped to a byte;
+//   * a pass is an int32 sum 2^21 + sum pixel * k, shifted right by 22 and clamped to a byte (from above; bicubic: from below too);
 //   * the horizontal pass is rounded to bytes BEFORE the vertical pass reads it; an axis that keeps its size is skipped;
 //   * the byte of the vertical pass goes through the formula of csrc/vit_input.hip into dst [n][C][S][S].
 // Only the S x S pixels of the crop are computed, and no resized 8-bit image is stored in HBM.
@@ -20,6 +20,12 @@
 // beyond a byte), nothing of the horizontal pass is repeated inside a tile; tiles of one image repeat the rows their vertical supports
 // share (2 * support of ~th * scale rows).  The tile adapts to the scale (tile_shape): its width so that the column coefficients fit
 // their LDS table, its height so that the rows of the horizontal pass fit theirs, for every size the launcher accepts.
+//
+// The filter is a template parameter F next to the channel count: VITHIP_RESIZE_BILINEAR is the kernel above, VITHIP_RESIZE_BICUBIC
+// (Pillow's BICUBIC, the evaluation transform of DINOv2, DINO, DeiT, MAE and timm's vit_* configs; tests/preproc_filter_model.py) has
+// twice the support, signed coefficients (rounded away from zero), a pass that can leave [0, 255] on both sides and therefore
+// clamps on both, and coefficient tables of twice the size, so that both filters take the same sources and the production shapes
+// keep a tile as wide as the crop.  Nothing of the bilinear instantiation depends on the other one.
 //
 // Images of one call differ in size, so each has a record (pointer, sizes, crop origin).  The records travel BY VALUE as kernel
 // arguments, PP_RECS per launch: the call stays asynchronous, borrows the caller's array only for its duration, and needs neither
@@ -42,7 +48,8 @@ constexpr int PP_THREADS = 256;
 constexpr int PP_MAX_CHANS = 4;
 constexpr int PP_RECS = 64;        // images per launch: 64 records of 32 bytes in the kernel arguments
 constexpr int PP_MAX_TILE = 256;   // columns / rows of a tile at most (the xmin / count tables)
-constexpr int PP_KCAP = 1024;      // coefficients per axis of a tile (ints in LDS)
+constexpr int PP_KCAP = 1024;      // coefficients per axis of a tile (ints in LDS), bilinear ...
+constexpr int PP_KCAP_CUBIC = 2048;  // ... and bicubic, which has twice the taps
 constexpr int PP_HBYTES = 32768;   // bytes of the horizontal pass a tile keeps in LDS
 constexpr int PP_MAX_GRID_X = 4096;
 constexpr int PP_PRECISION = 22;
@@ -63,12 +70,14 @@ struct pp_consts {
     float mean[PP_MAX_CHANS], std[PP_MAX_CHANS];
 };
 
-// most taps an output index of this axis can have: xmax - xmin < 2 * support + 1
-__host__ __device__ inline int tap_bound(int in, int out) {
+__host__ __device__ constexpr int kcap_of(int filter) { return filter == VITHIP_RESIZE_BICUBIC ? PP_KCAP_CUBIC : PP_KCAP; }
+
+// most taps an output index of this axis can have: xmax - xmin < 2 * support + 1, support = fs (bilinear) or 2 * fs (bicubic)
+__host__ __device__ inline int tap_bound(int in, int out, int filter) {
     if (in == out) return 1;
     const double scale = (double)in / (double)out;
     const double fs = scale < 1.0 ? 1.0 : scale;
-    return (int)(2.0 * fs) + 2;
+    return filter == VITHIP_RESIZE_BICUBIC ? (int)(4.0 * fs) + 2 : (int)(2.0 * fs) + 2;
 }
 
 struct pp_tile {
@@ -77,15 +86,18 @@ struct pp_tile {
     int rows;    // source rows the LDS image holds for this width
 };
 
-// The tile of one image.  Width: the column coefficients fit PP_KCAP, and at least cy + 1 rows of that width fit PP_HBYTES.  Height:
-// th output rows read at most (th - 1) * scale + cy source rows, which must fit too, as must the row coefficients.  The launcher
-// bounds the scale (a source's shorter side is at most 64 x resize_shorter), so cx, cy <= 162 and every limit leaves tw >= 4, th >= 1.
-__host__ __device__ inline pp_tile tile_shape(const pp_rec &r, int S, int C) {
+// The tile of one image.  Width: the column coefficients fit the filter's table (kcap_of), and at least cy + 1 rows of that width fit
+// PP_HBYTES.  Height: th output rows read at most (th - 1) * scale + cy source rows, which must fit too, as must the row coefficients.
+// The launcher bounds the scale (a source's shorter side is at most 64 x resize_shorter, so the scale of either axis stays below
+// 64 * (R + 1) / R <= 80), so cx, cy <= 162 (bilinear) or 322 (bicubic: 2048 / 322 = 6 columns, 32768 / (323 * 4) = 25 columns) and
+// every limit leaves tw >= 4, th >= 1.
+__host__ __device__ inline pp_tile tile_shape(const pp_rec &r, int S, int C, int filter) {
+    const int kcap = kcap_of(filter);
     pp_tile t;
-    t.cx = tap_bound(r.w, r.ow);
-    t.cy = tap_bound(r.h, r.oh);
+    t.cx = tap_bound(r.w, r.ow, filter);
+    t.cy = tap_bound(r.h, r.oh, filter);
     int tw = S < PP_MAX_TILE ? S : PP_MAX_TILE;
-    int lim = (PP_KCAP / t.cx) & ~3;
+    int lim = (kcap / t.cx) & ~3;
     if (tw > lim) tw = lim;
     lim = (PP_HBYTES / ((t.cy + 1) * C)) & ~3;
     if (tw > lim) tw = lim;
@@ -96,7 +108,7 @@ __host__ __device__ inline pp_tile tile_shape(const pp_rec &r, int S, int C) {
     const double fit = (double)(t.rows - t.cy - 1) / scale;
     int th = fit < 0.0 ? 1 : (fit > (double)PP_MAX_TILE ? PP_MAX_TILE : 1 + (int)fit);
     if (th > PP_MAX_TILE) th = PP_MAX_TILE;
-    if (th > PP_KCAP / t.cy) th = PP_KCAP / t.cy;
+    if (th > kcap / t.cy) th = kcap / t.cy;
     if (th > S) th = S;
     if (th < 1) th = 1;
     t.th = th;
@@ -105,7 +117,21 @@ __host__ __device__ inline pp_tile tile_shape(const pp_rec &r, int S, int C) {
 
 __host__ __device__ inline int tiles_of(const pp_tile &t, int S) { return ((S + t.tw - 1) / t.tw) * ((S + t.th - 1) / t.th); }
 
-// Pillow's precompute_coeffs + normalize_coeffs_8bpc for output index xx of one axis (bilinear: support = max(scale, 1)).
+// Pillow's filters: the weight of a tap at signed distance d (in units of the filter's scale) from the centre
+template <int F>
+__device__ inline double filter_weight(double d) {
+    const double t = fabs(d);
+    if (F == VITHIP_RESIZE_BICUBIC) {  // Keys' cubic, a = -0.5
+        const double a = -0.5;
+        if (t < 1.0) return ((a + 2.0) * t - (a + 3.0)) * t * t + 1;
+        if (t < 2.0) return (((t - 5) * t + 8) * t - 4) * a;
+        return 0.0;
+    }
+    return t < 1.0 ? 1.0 - t : 0.0;
+}
+
+// Pillow's precompute_coeffs + normalize_coeffs_8bpc for output index xx of one axis (support = max(scale, 1), bicubic twice that).
+template <int F>
 __device__ inline void coefficients(int in, int out, int xx, int bound, int *k, int *pmin, int *pcnt) {
     if (in == out) {  // the axis is skipped: the byte passes through
         *pmin = xx;
@@ -115,7 +141,7 @@ __device__ inline void coefficients(int in, int out, int xx, int bound, int *k, 
     }
     const double scale = (double)in / (double)out;
     const double fs = scale < 1.0 ? 1.0 : scale;
-    const double support = fs, ss = 1.0 / fs;
+    const double support = F == VITHIP_RESIZE_BICUBIC ? 2.0 * fs : fs, ss = 1.0 / fs;
     const double center = ((double)xx + 0.5) * scale;
     int xmin = (int)(center - support + 0.5);
     if (xmin < 0) xmin = 0;
@@ -125,29 +151,32 @@ __device__ inline void coefficients(int in, int out, int xx, int bound, int *k, 
     if (cnt > bound) cnt = bound;  // never taken (tap_bound); keeps the table writes inside the tile's slot whatever happens
     if (cnt < 0) cnt = 0;
     double ww = 0.0;
+    for (int x = 0; x < cnt; ++x) ww += filter_weight<F>(((double)(x + xmin) - center + 0.5) * ss);
     for (int x = 0; x < cnt; ++x) {
-        const double a = fabs(((double)(x + xmin) - center + 0.5) * ss);
-        ww += a < 1.0 ? 1.0 - a : 0.0;
-    }
-    for (int x = 0; x < cnt; ++x) {
-        const double a = fabs(((double)(x + xmin) - center + 0.5) * ss);
-        double w = a < 1.0 ? 1.0 - a : 0.0;
+        double w = filter_weight<F>(((double)(x + xmin) - center + 0.5) * ss);
         if (ww != 0.0) w /= ww;
-        k[x] = (int)(0.5 + w * 4194304.0);
+        k[x] = F == VITHIP_RESIZE_BICUBIC && w < 0.0 ? (int)(-0.5 + w * 4194304.0) : (int)(0.5 + w * 4194304.0);
     }
     *pmin = xmin;
     *pcnt = cnt;
 }
 
+// the byte of a pass: bilinear sums cannot fall below 0, bicubic ones can
+template <int F>
+__device__ inline int clamp_byte(int v) {
+    if (F == VITHIP_RESIZE_BICUBIC && v < 0) return 0;
+    return v > 255 ? 255 : v;
+}
+
 // grid: x over the tiles of an image (a workgroup loops when an image has more), y over the records of the launch
-template <int C>
+template <int C, int F>
 __global__ __launch_bounds__(PP_THREADS) void images_u8_resize_crop_kernel(pp_batch batch, float *__restrict__ dst, int S, pp_consts nk) {
     __shared__ unsigned int hb[PP_HBYTES / 4];  // horizontal pass: [row][channel][tw bytes]
-    __shared__ int kx[PP_KCAP], ky[PP_KCAP];
+    __shared__ int kx[kcap_of(F)], ky[kcap_of(F)];
     __shared__ int xmin[PP_MAX_TILE], xcnt[PP_MAX_TILE], ymin[PP_MAX_TILE], ycnt[PP_MAX_TILE];
 
     const pp_rec rec = batch.r[blockIdx.y];
-    const pp_tile t = tile_shape(rec, S, C);
+    const pp_tile t = tile_shape(rec, S, C, F);
     const int tiles_x = (S + t.tw - 1) / t.tw, ntiles = tiles_of(t, S);
     const int twq = t.tw / 4;  // dwords per channel row of the LDS image
     float *const out = dst + (size_t)blockIdx.y * C * S * S;
@@ -159,8 +188,8 @@ __global__ __launch_bounds__(PP_THREADS) void images_u8_resize_crop_kernel(pp_ba
 
         // 1. coefficients of the tile's columns and rows
         for (int e = tid; e < tw + th; e += PP_THREADS) {
-            if (e < tw) coefficients(rec.w, rec.ow, rec.left + j0 + e, t.cx, kx + e * t.cx, xmin + e, xcnt + e);
-            else coefficients(rec.h, rec.oh, rec.top + i0 + (e - tw), t.cy, ky + (e - tw) * t.cy, ymin + (e - tw), ycnt + (e - tw));
+            if (e < tw) coefficients<F>(rec.w, rec.ow, rec.left + j0 + e, t.cx, kx + e * t.cx, xmin + e, xcnt + e);
+            else coefficients<F>(rec.h, rec.oh, rec.top + i0 + (e - tw), t.cy, ky + (e - tw) * t.cy, ymin + (e - tw), ycnt + (e - tw));
         }
         __syncthreads();
 
@@ -181,7 +210,7 @@ __global__ __launch_bounds__(PP_THREADS) void images_u8_resize_crop_kernel(pp_ba
                 int acc = 1 << (PP_PRECISION - 1);
                 for (int x = 0; x < n; ++x) acc += (int)s[x * C] * k[x];
                 acc >>= PP_PRECISION;
-                packed |= (unsigned int)(acc > 255 ? 255 : acc) << (8 * p);
+                packed |= (unsigned int)clamp_byte<F>(acc) << (8 * p);
             }
             hb[(r * C + c) * twq + q] = packed;
         }
@@ -204,8 +233,7 @@ __global__ __launch_bounds__(PP_THREADS) void images_u8_resize_crop_kernel(pp_ba
             f32x4 v;
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
-                const int b = acc[p] >> PP_PRECISION;
-                const float u = (float)(b > 255 ? 255 : b);
+                const float u = (float)clamp_byte<F>(acc[p] >> PP_PRECISION);
                 v[p] = (u / 255.0f - nk.mean[c]) / nk.std[c];
             }
             *reinterpret_cast<f32x4 *>(out + ((size_t)c * S + (i0 + i)) * S + j0 + 4 * q) = v;
@@ -215,8 +243,11 @@ __global__ __launch_bounds__(PP_THREADS) void images_u8_resize_crop_kernel(pp_ba
 }
 
 template <int C>
-int launch(hipStream_t s, const pp_batch &b, int count, int grid_x, float *dst, int S, const pp_consts &nk) {
-    hipLaunchKernelGGL(images_u8_resize_crop_kernel<C>, dim3(grid_x, count), dim3(PP_THREADS), 0, s, b, dst, S, nk);
+int launch(hipStream_t s, const pp_batch &b, int count, int grid_x, float *dst, int S, const pp_consts &nk, int filter) {
+    if (filter == VITHIP_RESIZE_BICUBIC)
+        hipLaunchKernelGGL((images_u8_resize_crop_kernel<C, VITHIP_RESIZE_BICUBIC>), dim3(grid_x, count), dim3(PP_THREADS), 0, s, b, dst, S, nk);
+    else
+        hipLaunchKernelGGL((images_u8_resize_crop_kernel<C, VITHIP_RESIZE_BILINEAR>), dim3(grid_x, count), dim3(PP_THREADS), 0, s, b, dst, S, nk);
     return static_cast<int>(hipGetLastError());
 }
 
@@ -246,7 +277,8 @@ bool make_record(const vithip_image_u8 &im, int S, int R, pp_rec *r) {
 
 extern "C" {
 
-int vithip_images_u8_resize_crop_check(const vithip_image_u8 *images, int n, int img_size, int chans, int resize_shorter) {
+int vithip_images_u8_resize_crop_check_filter(const vithip_image_u8 *images, int n, int img_size, int chans, int resize_shorter, int filter) {
+    if (filter != VITHIP_RESIZE_BILINEAR && filter != VITHIP_RESIZE_BICUBIC) return -1;
     if (!images || n < 1 || chans < 1 || chans > PP_MAX_CHANS || img_size < 4 || img_size % 4 || resize_shorter < img_size ||
         resize_shorter > 4096)
         return -1;
@@ -257,10 +289,15 @@ int vithip_images_u8_resize_crop_check(const vithip_image_u8 *images, int n, int
     return 0;
 }
 
-int vithip_images_u8_resize_crop_to_f32(vithip_stream_t stream, const vithip_image_u8 *images, int n, float *dst, int img_size, int chans,
-                                        int resize_shorter, const float *mean, const float *std) {
+int vithip_images_u8_resize_crop_check(const vithip_image_u8 *images, int n, int img_size, int chans, int resize_shorter) {
+    return vithip_images_u8_resize_crop_check_filter(images, n, img_size, chans, resize_shorter, VITHIP_RESIZE_BILINEAR);
+}
+
+int vithip_images_u8_resize_crop_to_f32_filter(vithip_stream_t stream, const vithip_image_u8 *images, int n, float *dst, int img_size,
+                                               int chans, int resize_shorter, int filter, const float *mean, const float *std) {
     if (!dst || !mean || !std || (reinterpret_cast<size_t>(dst) & 15)) return static_cast<int>(hipErrorInvalidValue);
-    if (vithip_images_u8_resize_crop_check(images, n, img_size, chans, resize_shorter) != 0) return static_cast<int>(hipErrorInvalidValue);
+    if (vithip_images_u8_resize_crop_check_filter(images, n, img_size, chans, resize_shorter, filter) != 0)
+        return static_cast<int>(hipErrorInvalidValue);
     pp_consts nk = {};
     for (int c = 0; c < chans; ++c) {
         if (!std::isfinite(mean[c]) || !std::isfinite(std[c]) || std[c] == 0.0f) return static_cast<int>(hipErrorInvalidValue);
@@ -275,21 +312,27 @@ int vithip_images_u8_resize_crop_to_f32(vithip_stream_t stream, const vithip_ima
         int grid_x = 1;
         for (int i = 0; i < count; ++i) {
             make_record(images[first + i], img_size, resize_shorter, &b.r[i]);
-            const int tiles = tiles_of(tile_shape(b.r[i], img_size, chans), img_size);
+            const int tiles = tiles_of(tile_shape(b.r[i], img_size, chans, filter), img_size);
             if (tiles > grid_x) grid_x = tiles;
         }
         if (grid_x > PP_MAX_GRID_X) grid_x = PP_MAX_GRID_X;
         float *d = dst + (size_t)first * img;
         int rc;
         switch (chans) {
-            case 1: rc = launch<1>(s, b, count, grid_x, d, img_size, nk); break;
-            case 2: rc = launch<2>(s, b, count, grid_x, d, img_size, nk); break;
-            case 3: rc = launch<3>(s, b, count, grid_x, d, img_size, nk); break;
-            default: rc = launch<4>(s, b, count, grid_x, d, img_size, nk); break;
+            case 1: rc = launch<1>(s, b, count, grid_x, d, img_size, nk, filter); break;
+            case 2: rc = launch<2>(s, b, count, grid_x, d, img_size, nk, filter); break;
+            case 3: rc = launch<3>(s, b, count, grid_x, d, img_size, nk, filter); break;
+            default: rc = launch<4>(s, b, count, grid_x, d, img_size, nk, filter); break;
         }
         if (rc) return rc;
     }
     return 0;
+}
+
+int vithip_images_u8_resize_crop_to_f32(vithip_stream_t stream, const vithip_image_u8 *images, int n, float *dst, int img_size, int chans,
+                                        int resize_shorter, const float *mean, const float *std) {
+    return vithip_images_u8_resize_crop_to_f32_filter(stream, images, n, dst, img_size, chans, resize_shorter, VITHIP_RESIZE_BILINEAR, mean,
+                                                      std);
 }
 
 }  // extern "C"

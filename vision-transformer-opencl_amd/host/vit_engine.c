@@ -43,8 +43,10 @@ enum { VIT_IN_F32 = 0, VIT_IN_U8 = 1, VIT_IN_IMAGES = 2 };
 typedef struct {
     int kind;           /* VIT_IN_* */
     int resize_shorter; /* VIT_IN_IMAGES */
+    int resize_filter;  /* VIT_IN_IMAGES: the engine's filter when the call began (VIT_RESIZE_* = VITHIP_RESIZE_*) */
     float mean[VIT_MAX_U8_CHANS], std[VIT_MAX_U8_CHANS];
 } vit_input;
+_Static_assert(VIT_RESIZE_BILINEAR == VITHIP_RESIZE_BILINEAR && VIT_RESIZE_BICUBIC == VITHIP_RESIZE_BICUBIC, "one numbering of the filters");
 _Static_assert(sizeof(vit_image_u8) == sizeof(vithip_image_u8) && offsetof(vit_image_u8, pixels) == offsetof(vithip_image_u8, pixels) &&
                    offsetof(vit_image_u8, height) == offsetof(vithip_image_u8, height) &&
                    offsetof(vit_image_u8, width) == offsetof(vithip_image_u8, width),
@@ -112,6 +114,7 @@ struct vit_engine {
     const void *g_images; vit_input g_in; vit_output g_out; int g_n;
     unsigned short **w16;        /* per weight index; NULL for tensors that stay fp32 */
     int weights_loaded;
+    int resize_filter;           /* VIT_RESIZE_*: the filter of the _images calls (vit_engine_set_resize_filter) */
 
     /* workspace for max_batch images */
     float *x, *y, *qkv, *hbuf, *z, *logits;
@@ -434,6 +437,17 @@ int vit_engine_set_lanes(vit_engine *e, int lanes) {
     HIP_TRY(e, vithip_set_device(e->opt.device));
     return ensure_gemm_workspaces(e);
 }
+
+int vit_engine_set_resize_filter(vit_engine *e, int filter) {
+    if (!e) return VIT_ERR_ARG;
+    if (filter != VIT_RESIZE_BILINEAR && filter != VIT_RESIZE_BICUBIC)
+        return fail(e, VIT_ERR_ARG, "resize filter %d: VIT_RESIZE_BILINEAR (%d) or VIT_RESIZE_BICUBIC (%d)", filter, VIT_RESIZE_BILINEAR,
+                    VIT_RESIZE_BICUBIC);
+    e->resize_filter = filter;
+    return VIT_OK;
+}
+
+int vit_engine_get_resize_filter(const vit_engine *e) { return e ? e->resize_filter : -1; }
 
 int vit_engine_set_profile(vit_engine *e, int on) {
     if (on && !e->ev_ready) {
@@ -870,8 +884,9 @@ static int stage_embed(chunk_ctx *c, const void *d_images, const vit_input *in, 
         if (in->kind != VIT_IN_F32) {
             HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_EMBED));
             if (in->kind == VIT_IN_IMAGES)
-                HIP_TRY(e, vithip_images_u8_resize_crop_to_f32(ln->s, (const vithip_image_u8 *)d_images + ln->off, ln->n, f32_stage + ln->off * img,
-                                                               cfg->img_size, cfg->in_chans, in->resize_shorter, in->mean, in->std));
+                HIP_TRY(e, vithip_images_u8_resize_crop_to_f32_filter(ln->s, (const vithip_image_u8 *)d_images + ln->off, ln->n,
+                                                                      f32_stage + ln->off * img, cfg->img_size, cfg->in_chans,
+                                                                      in->resize_shorter, in->resize_filter, in->mean, in->std));
             else
                 HIP_TRY(e, vithip_images_u8_to_f32(ln->s, (const unsigned char *)d_images + ln->off * img, f32_stage + ln->off * img,
                                                    ln->n, cfg->img_size, cfg->in_chans, in->mean, in->std));
@@ -1242,10 +1257,12 @@ static int input_images(vit_engine *e, const char *who, const vit_image_u8 *imag
     if (rc) return rc;
     in->kind = VIT_IN_IMAGES;
     in->resize_shorter = pp->resize_shorter;
+    in->resize_filter = e->resize_filter;
     if (pp->resize_shorter < e->cfg.img_size || pp->resize_shorter > 4096)
         return fail(e, VIT_ERR_ARG, "%s: resize_shorter = %d must be img_size = %d .. 4096 (a smaller image would have to be padded)", who,
                     pp->resize_shorter, e->cfg.img_size);
-    const int bad = vithip_images_u8_resize_crop_check((const vithip_image_u8 *)images, n, e->cfg.img_size, e->cfg.in_chans, pp->resize_shorter);
+    const int bad = vithip_images_u8_resize_crop_check_filter((const vithip_image_u8 *)images, n, e->cfg.img_size, e->cfg.in_chans,
+                                                              pp->resize_shorter, in->resize_filter);
     if (bad > 0)
         return fail(e, VIT_ERR_ARG, "%s: image %d (pixels %p, %d x %d): pixels must not be NULL, height and width 1..16384, the shorter side "
                     "at most 64 x resize_shorter", who, bad - 1, (const void *)images[bad - 1].pixels, images[bad - 1].height, images[bad - 1].width);
