@@ -396,13 +396,68 @@ int vit_engine_intermediate_host_images(vit_engine *e, const vit_image_u8 *image
                                         const vit_intermediate_spec *spec, float *const *out);
 
 /*
+ * Top-k class records instead of probabilities: the k most likely classes of every image (ImageNet top-5, "the five best guesses").
+ * The row of image i is 2k 32-bit words,
+ *
+ *     row[0 .. k-1]   the labels (int32), best first
+ *     row[k .. 2k-1]  their scores as fp32 bit patterns
+ *
+ * labels first, then bit patterns, as in the 8-byte records of vit_dp.h.  The score of a class is its probability (VIT_SCORE_PROB: the
+ * bits the matching forward call of the same engine returns, and slot 0 is that call's top-1 record) or its logit (VIT_SCORE_LOGIT);
+ * for both engine dtypes the fp32 logits are read.  Order: higher score first, among equal scores (==) the lower label first.  A
+ * class whose score is NaN is not a candidate; slots left over when fewer than k candidates exist hold label 0x7fffffff and score
+ * -1.0f (PROB) or -INFINITY (LOGIT) -- with PROB, one non-finite logit makes every probability of that image NaN and its whole row
+ * empty slots, exactly the top-1 record a forward gives it; the other images of the batch are untouched.
+ * (vithip_softmax_topk_f32 in vit_hip_kernels.h states the arithmetic.)
+ *
+ * The whole forward runs, the final LayerNorm and the head GEMM included; then each lane launches vithip_softmax_topk_f32 on its rows
+ * of the logits in place of vithip_softmax_top1_f32: no [n][classes] array is written anywhere.  An image's row has the same bits
+ * whatever prune_last_layer and lanes are set to, wherever the image sits in whatever batch and whichever of the six calls delivers the
+ * same pixels.  prune_last_layer engines use the pruned last layer: only the class row is needed.  No atomics.
+ *
+ * The six calls mirror the six features calls: the same images, chunking, lanes, stream rules, blocking behaviour and _images eager
+ * rule; `out` takes the place of the feature rows (device: one [n][2k] array of 32-bit words; host: caller-allocated rows out[i] of
+ * 2k words).  On the host path only the records cross PCIe, 8k bytes per image instead of 4 * classes.  The host calls share the
+ * pinned output staging of the features calls and its rule: it is (re)allocated for the widest row seen so far (2k words can exceed
+ * the classes-sized start on a small head); if that does not fit, the call returns VIT_ERR_NOMEM, the staging is back at its
+ * classes-sized start and the engine stays usable.
+ * use_graph: the graph is keyed on the kind of output, k and score too, so forwards and top-k calls on the same n and pointers, or two
+ * top-k calls that differ in k or score, never replay each other's graph.  Profiling: the launch (one per lane and chunk) is accounted
+ * to VIT_STAGE_SOFTMAX.  vit_engine_read_logits() after a top-k call works: the head ran, and these are the logits the records of the
+ * last chunk were taken from.
+ * VIT_ERR_ARG (the engine stays usable, nothing was enqueued): NULL pointers, n <= 0, k outside 1..min(VIT_MAX_TOPK, num_classes)
+ * (the message names both), an unknown score, reserved != 0, and what the matching forward refuses.
+ */
+enum { VIT_SCORE_PROB = 0, VIT_SCORE_LOGIT = 1 };
+#define VIT_MAX_TOPK 64
+typedef struct {
+    int k;         /* 1..min(VIT_MAX_TOPK, num_classes) */
+    int score;     /* VIT_SCORE_* */
+    int reserved;  /* must be 0 */
+} vit_topk_spec;
+
+/* 32-bit words per output row: 2k; 0 on a bad spec */
+size_t vit_engine_topk_row_elems(const vit_engine *e, const vit_topk_spec *spec);
+int vit_engine_topk_device(vit_engine *e, const float *d_images, int n, const vit_topk_spec *spec, int *d_out, void *stream);
+int vit_engine_topk_host(vit_engine *e, const float *const *images, int n, const vit_topk_spec *spec, int *const *out);
+int vit_engine_topk_device_u8(vit_engine *e, const unsigned char *d_images, int n, const float *mean, const float *std,
+                              const vit_topk_spec *spec, int *d_out, void *stream);
+int vit_engine_topk_host_u8(vit_engine *e, const unsigned char *const *images, int n, const float *mean, const float *std,
+                            const vit_topk_spec *spec, int *const *out);
+int vit_engine_topk_device_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, const vit_topk_spec *spec,
+                                  int *d_out, void *stream);
+int vit_engine_topk_host_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, const vit_topk_spec *spec,
+                                int *const *out);
+
+/*
  * The fp32 GEMMs' helper-piece hand-over (csrc/vit_gemm_persistent.hip) since the last call, summed over the lanes: tiles whose
  * first K-steps came from a helper workgroup / tiles whose owner found no piece when it looked and computed all of it.  The
  * second number is lost time, never a wrong result (nothing in the hand-over waits or gives up).  Synchronises the device.
  */
 int vit_engine_handover_stats(vit_engine *e, long *taken, long *recomputed);
 
-/* Debug/test taps: copy the logits of the most recent chunk (rows = images of that chunk; an error after a features call). */
+/* Debug/test taps: copy the logits of the most recent chunk (rows = images of that chunk; an error after a features, attention or
+ * intermediate call, which write none; after a top-k call the logits its records were taken from). */
 int vit_engine_read_logits(vit_engine *e, float *dst, int rows);
 /* Where a MEAN features chunk of nb <= max_batch images would put things inside the engine's y allocation (max_batch * tokens *
  * embed_dim floats), for lane `lane` under the current lane setting; launches nothing.  Byte offsets from the allocation's start:

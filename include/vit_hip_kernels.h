@@ -338,6 +338,32 @@ int vithip_softmax_top1_f32(vithip_stream_t stream, const float *logits, int ld_
                             int rows, int classes);
 
 /*
+ * The k best classes of every row as records instead of the probabilities (csrc/vit_topk.hip): the output row of image i is
+ *     out[i * ld_out + 0 .. k-1]   the labels (int32), best first
+ *     out[i * ld_out + k .. 2k-1]  their scores, as fp32 bit patterns
+ * (labels, then bit patterns: the convention of the records in vit_dp.h).  ld_out counts 32-bit words.
+ * The score of class c:
+ *   VITHIP_SCORE_PROB   the probability vithip_softmax_top1_f32 stores for the same logits row, bit for bit:
+ *                       mx = max_c logits[c]; e_c = expf(logits[c] - mx); sum = sum_c e_c in that kernel's order (thread-strided
+ *                       partial sums, a wave butterfly, the four waves added 0..3); score = e_c / sum
+ *   VITHIP_SCORE_LOGIT  logits[c]
+ * Order: slot 0 is the best; slot j holds the best candidate after the one in slot j-1 under the total order "higher score first;
+ * among equal scores (==, so -0.0 ties +0.0) the lower label first" -- the first-maximum-wins rule of Main.c:64-68, continued.
+ * A class whose score is NaN is not a candidate (+-inf are ordinary values); slots left over when fewer than k candidates exist hold
+ * label 0x7fffffff and score -1.0f (PROB) or -INFINITY (LOGIT).  PROB slot 0 is therefore always the (label, prob) pair of
+ * vithip_softmax_top1_f32, including its (0x7fffffff, -1.0f) for a row whose probabilities are all NaN.
+ * Nothing but the 2k words of each row is written and logits is only read; a row's records depend on that row's logits alone (one
+ * workgroup per row, no atomics: reproducible bit for bit whatever rows is and wherever the row sits).
+ * hipErrorInvalidValue, before anything is launched: NULL pointers, rows <= 0, k < 1, k > classes, k > VITHIP_MAX_TOPK,
+ * ld_logits < classes, ld_out < 2k, an unknown score.
+ */
+enum { VITHIP_SCORE_PROB = 0, VITHIP_SCORE_LOGIT = 1 };
+#define VITHIP_MAX_TOPK 64
+int vithip_softmax_topk_f32(vithip_stream_t stream, const float *logits, int ld_logits,
+                            int *out, int ld_out /* 32-bit words per row, >= 2k */,
+                            int rows, int classes, int k, int score);
+
+/*
  * The model input from 8-bit pixels (csrc/vit_input.hip): src [n][S][S][C] uint8, channels interleaved as image decoders
  * write them -> dst [n][C][S][S] fp32,
  *     dst[i][c][h][w] = ((float)src[i][h][w][c] / 255.0f - mean[c]) / std[c]

@@ -80,6 +80,19 @@ class CIntermediateSpec(C.Structure):  # vit_intermediate_spec
 TAP_KINDS = {"cls": 0, "tokens": 1, "patches": 2, "map": 3}  # VIT_TAP_* / VITHIP_TAP_*
 
 
+class CTopkSpec(C.Structure):  # vit_topk_spec
+    _fields_ = [("k", C.c_int), ("score", C.c_int), ("reserved", C.c_int)]
+
+
+SCORES = {"prob": 0, "logit": 1}  # VIT_SCORE_* / VITHIP_SCORE_*
+VIT_MAX_TOPK = 64
+TOPK_EMPTY_LABEL = 0x7FFFFFFF  # the label of a slot no candidate was left for; its score: -1.0 (prob) or -inf (logit)
+
+
+def _score(score) -> int:
+    return SCORES[score] if isinstance(score, str) else int(score)
+
+
 class CPosResample(C.Structure):  # vit_pos_resample
     _fields_ = [("src_img_size", C.c_int), ("mode", C.c_int), ("reserved", C.c_int)]
 
@@ -116,6 +129,19 @@ def attention_spec(kind, reserved: int = 0) -> CAttentionSpec:
     """kind: "heads" | "head_mean" (or a raw VIT_ATTN_* integer, passed through unchecked for the C side to judge)."""
     k = ATTENTION_KINDS[kind] if isinstance(kind, str) else int(kind)
     return CAttentionSpec(k, int(reserved))
+
+
+def topk_spec(k: int, score="prob", reserved: int = 0) -> CTopkSpec:
+    """score: "prob" | "logit" (or a raw VIT_SCORE_* integer); everything is passed through unchecked for the C side to judge."""
+    return CTopkSpec(int(k), _score(score), int(reserved))
+
+
+def split_topk(records):
+    """[n][2k] int32 records -> (labels int32 [n][k], scores float32 [n][k]): a row is k labels, then the k scores' bit patterns."""
+    records = np.ascontiguousarray(records, np.int32)
+    k = records.shape[-1] // 2
+    assert records.shape[-1] == 2 * k, records.shape
+    return records[..., :k].copy(), records[..., k:].copy().view(np.float32)
 
 
 def intermediate_spec(layers, kind="cls", norm=True, depth: Optional[int] = None, reserved: int = 0) -> CIntermediateSpec:
@@ -223,14 +249,14 @@ def lib() -> C.CDLL:
         # the forward surface, output kind x place x input kind: (engine, images, n) + normalisation + spec + destination
         norm = {"": [], "_u8": [f32p, f32p], "_images": [C.POINTER(CPreproc)]}
         spec = {"forward": [], "features": [C.POINTER(CFeatureSpec)], "cls_attention": [C.POINTER(CAttentionSpec)],
-                "intermediate": [C.POINTER(CIntermediateSpec)]}
+                "intermediate": [C.POINTER(CIntermediateSpec)], "topk": [C.POINTER(CTopkSpec)]}
         for out in spec:
             for place in ("host", "device"):
                 for kind in norm:
                     images = C.POINTER(CImageU8) if kind == "_images" else C.c_void_p if place == "device" else \
                         C.POINTER(C.c_void_p if kind == "_u8" else f32p)
                     # host: a row per image; device: the rows, a forward's top-1 labels and probabilities, the stream
-                    dst = [C.POINTER(f32p)] if place == "host" else [C.c_void_p] * (4 if out == "forward" else 2)
+                    dst = [C.POINTER(i32p if out == "topk" else f32p)] if place == "host" else [C.c_void_p] * (4 if out == "forward" else 2)
                     name = f"vit_engine_{out}_{place}{kind}"
                     if hasattr(L, name):  # VIT_HIP_LIBRARY may name an earlier build (A/B timing), which lacks the later calls
                         getattr(L, name).argtypes = [C.c_void_p, images, C.c_int] + norm[kind] + spec[out] + dst
@@ -263,6 +289,10 @@ def lib() -> C.CDLL:
             L.vit_engine_intermediate_row_elems.restype = C.c_size_t
             L.vit_engine_intermediate_row_elems.argtypes = [C.c_void_p, C.POINTER(CIntermediateSpec)]
             L.vithip_tap_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p] + [C.c_int] * 4
+        if hasattr(L, "vit_engine_topk_device"):  # an earlier build (see above) has no top-k calls
+            L.vit_engine_topk_row_elems.restype = C.c_size_t
+            L.vit_engine_topk_row_elems.argtypes = [C.c_void_p, C.POINTER(CTopkSpec)]
+            L.vithip_softmax_topk_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_int] * 4
         if hasattr(L, "vit_engine_load_weights_resampled"):  # an earlier build (see above) cannot resample a position embedding
             L.vit_engine_load_weights_resampled.argtypes = [C.c_void_p, C.POINTER(CNetwork), C.c_int, C.POINTER(CPosResample)]
             L.vit_engine_copy_weights_resampled.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
@@ -1033,6 +1063,38 @@ def softmax_top1(logits, ld_logits: Optional[int] = None, ld_probs: Optional[int
     return dp.window(), dlab.window().reshape(rows) if want_label else None, dpr.window().reshape(rows) if want_prob else None
 
 
+def softmax_topk(logits, k: int, score="prob", ld_logits: Optional[int] = None, ld_out: Optional[int] = None, guard: int = 0,
+                 fill_bits: int = 0, out_offset: int = 0, out: Optional[dict] = None) -> np.ndarray:
+    """vithip_softmax_topk_f32 -> the records [rows][2k] int32 (split_topk() takes them apart).  ld_logits (>= classes): the rows
+    of logits are laid out at that step, the pad columns preset to fill_bits; ld_out (>= 2k): 32-bit words per output row.
+    guard, fill_bits: the records get `guard` words either side of them and every word of the allocation is preset to the bit pattern
+    fill_bits; out_offset: words the records are shifted by (a misaligned destination).  `out` receives the output allocation as the
+    call left it under "raw" and the logits allocation as the call left it under "logits_raw" (uint32 views of both under the
+    same names + "_before" as they were uploaded)."""
+    logits = _as_f32(logits)
+    rows, classes = logits.shape
+    ldl = classes if ld_logits is None else int(ld_logits)
+    ldo = 2 * int(k) if ld_out is None else int(ld_out)
+    src = np.full((rows, max(ldl, 1)), fill_bits, np.uint32).view(np.float32)
+    if ldl >= classes:
+        src[:, :classes] = logits
+    else:  # a leading dimension the launcher must refuse: it never reads the buffer
+        src = logits.copy()
+    raw = np.full(2 * guard + out_offset + rows * max(ldo, 1), fill_bits, np.uint32)
+    d_src, d_raw = DeviceArray.from_numpy(src), DeviceArray.from_numpy(raw)
+    try:
+        hip_check(lib().vithip_softmax_topk_f32(None, d_src.ptr, ldl, d_raw.ptr + 4 * (guard + out_offset), ldo, rows, classes, int(k),
+                                                _score(score)), "vithip_softmax_topk_f32")
+        after, src_after = d_raw.numpy(), d_src.numpy()
+    finally:
+        d_src.free()
+        d_raw.free()
+    if out is not None:
+        out.update(raw=after, raw_before=raw, logits_raw=src_after.view(np.uint32), logits_raw_before=src.view(np.uint32))
+    lo = guard + out_offset
+    return after[lo:lo + rows * ldo].reshape(rows, ldo)[:, :2 * int(k)].copy().view(np.int32)
+
+
 def _norm_consts(mean, std, chans: int):
     """mean / std as the host float arrays of `chans` entries the C-ABI reads (None stays NULL)."""
     out = []
@@ -1168,8 +1230,8 @@ class Engine:
         L.vit_engine_copy_weights.argtypes = [C.c_void_p, C.c_void_p]
         self._check(L.vit_engine_copy_weights(self._h, other._h), "vit_engine_copy_weights")
 
-    # ---- the forward surface: vit_engine_<out>_<place><inp>, out "forward" | "features" | "cls_attention" | "intermediate", inp "" | "_u8" | "_images" ----
-    def _call_args(self, out, inp, kind, l2_normalize, mean, std, resize_shorter, layers=None, norm=True) -> list:
+    # ---- the forward surface: vit_engine_<out>_<place><inp>, out "forward" | "features" | "cls_attention" | "intermediate" | "topk", inp "" | "_u8" | "_images" ----
+    def _call_args(self, out, inp, kind, l2_normalize, mean, std, resize_shorter, layers=None, norm=True, topk=None) -> list:
         """What lies between n and the destination in the C call: the normalisation of the input kind, the spec of the output kind."""
         args = []
         if inp == "_u8":
@@ -1178,12 +1240,14 @@ class Engine:
             args.append(C.byref(preproc_params(resize_shorter, mean, std, self.cfg.in_chans)))
         if out == "intermediate":
             args.append(C.byref(intermediate_spec(layers, kind, norm, self.cfg.depth)))
+        elif out == "topk":
+            args.append(C.byref(topk))
         elif out != "forward":
             args.append(C.byref(feature_spec(kind, l2_normalize) if out == "features" else attention_spec(kind)))
         return args
 
     def _host(self, out, inp, images, kind=None, l2_normalize=False, mean=None, std=None, resize_shorter=None, layers=None,
-              norm=True) -> np.ndarray:
+              norm=True, topk=None) -> np.ndarray:
         """A host-path call: per-image pointers (or records) in, per-image rows of a new array out."""
         if inp == "_images":
             keep, in_ptrs = host_image_records(images, self.cfg.in_chans)
@@ -1194,26 +1258,29 @@ class Engine:
             keep = _as_f32(images)
             in_ptrs = (f32p * len(keep))(*[im.ctypes.data_as(f32p) for im in keep])
         n = len(keep)
-        args = self._call_args(out, inp, kind, l2_normalize, mean, std, resize_shorter, layers, norm)
+        args = self._call_args(out, inp, kind, l2_normalize, mean, std, resize_shorter, layers, norm, topk)
         if out == "forward":
             shape = (n, self.cfg.num_classes)
+        elif out == "topk":
+            shape = (n, 2 * max(topk.k, 1))  # a spec the C side refuses still gets rows: the call must see its own arguments
         elif out == "intermediate":
             shape = self.intermediate_shape(n, layers, kind, norm)
         else:
             shape = self.feature_shape(n, kind, l2_normalize) if out == "features" else self.attention_shape(n, kind)
-        rows = np.empty(shape, np.float32)
-        out_ptrs = (f32p * n)(*[rows[i].ctypes.data_as(f32p) for i in range(n)])
+        rowp = i32p if out == "topk" else f32p
+        rows = np.empty(shape, np.int32 if out == "topk" else np.float32)
+        out_ptrs = (rowp * n)(*[rows[i].ctypes.data_as(rowp) for i in range(n)])
         name = f"vit_engine_{out}_host{inp}"
         self._check(getattr(lib(), name)(self._h, in_ptrs, n, *args, out_ptrs), name)
         return rows
 
     def _device(self, out, inp, images, n, dst, kind=None, l2_normalize=False, mean=None, std=None, resize_shorter=None, d_label=0,
-                d_prob=0, stream=0, layers=None, norm=True) -> None:
+                d_prob=0, stream=0, layers=None, norm=True, topk=None) -> None:
         """A device-path call: raw HBM addresses (images: a list of (ptr, H, W) for "_images"), async on `stream`."""
         if inp == "_images":
             images = image_records(images)
             n = len(images)
-        args = self._call_args(out, inp, kind, l2_normalize, mean, std, resize_shorter, layers, norm)
+        args = self._call_args(out, inp, kind, l2_normalize, mean, std, resize_shorter, layers, norm, topk)
         top1 = [d_label or None, d_prob or None] if out == "forward" else []
         name = f"vit_engine_{out}_device{inp}"
         self._check(getattr(lib(), name)(self._h, images, n, *args, dst, *top1, stream or None), name)
@@ -1361,6 +1428,42 @@ class Engine:
         """Device-resident path: images = a list of (ptr, H, W) in HBM, d_out [n][row] fp32; async on `stream`."""
         self._device("intermediate", "_images", images, None, d_out, kind, mean=mean, std=std, resize_shorter=resize_shorter, stream=stream,
                      layers=layers, norm=norm)
+
+    # ---- top-k class records (vit_engine_topk_*): rows of 2k int32 words, k labels then the k scores' bit patterns (split_topk) ----
+    def topk_shape(self, n: int, k: int) -> tuple:
+        """Shape of the int32 records n images give: (n, 2k)."""
+        spec = topk_spec(k)
+        elems = lib().vit_engine_topk_row_elems(self._h, C.byref(spec))
+        if elems == 0:
+            raise VitError(f"bad top-k spec (k={k!r}): k must be 1..min({VIT_MAX_TOPK}, {self.cfg.num_classes})")
+        return (n, elems)
+
+    def topk_host(self, images: np.ndarray, k: int, score="prob", reserved: int = 0) -> np.ndarray:
+        """Host path: per-image pointers in, per-image records out, int32 [n][2k]; score "prob" | "logit"."""
+        return self._host("topk", "", images, topk=topk_spec(k, score, reserved))
+
+    def topk_host_u8(self, images: np.ndarray, k: int, score="prob", mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
+        """Host path from 8-bit pixels [n][S][S][C] (see forward_u8)."""
+        return self._host("topk", "_u8", images, mean=mean, std=std, topk=topk_spec(k, score))
+
+    def topk_host_images(self, images, resize_shorter: int, k: int, score="prob", mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
+        """Host path: a list of [H][W][C] uint8 arrays of any sizes in, records out (see topk_host)."""
+        return self._host("topk", "_images", images, mean=mean, std=std, resize_shorter=resize_shorter, topk=topk_spec(k, score))
+
+    def topk_device(self, d_images: int, n: int, d_out: int, k: int, score="prob", stream: int = 0, reserved: int = 0) -> None:
+        """Device-resident path: raw HBM addresses, d_out [n][2k] int32, async on `stream`."""
+        self._device("topk", "", d_images, n, d_out, stream=stream, topk=topk_spec(k, score, reserved))
+
+    def topk_device_u8(self, d_images: int, n: int, d_out: int, k: int, score="prob", mean=IMAGENET_MEAN, std=IMAGENET_STD,
+                       stream: int = 0) -> None:
+        """Device-resident path from 8-bit pixels [n][S][S][C] in HBM (raw addresses), async on `stream`."""
+        self._device("topk", "_u8", d_images, n, d_out, mean=mean, std=std, stream=stream, topk=topk_spec(k, score))
+
+    def topk_device_images(self, images, d_out: int, resize_shorter: int, k: int, score="prob", mean=IMAGENET_MEAN, std=IMAGENET_STD,
+                           stream: int = 0) -> None:
+        """Device-resident path: images = a list of (ptr, H, W) in HBM, d_out [n][2k] int32; async on `stream`."""
+        self._device("topk", "_images", images, None, d_out, mean=mean, std=std, resize_shorter=resize_shorter, stream=stream,
+                     topk=topk_spec(k, score))
 
     def pool_scratch_layout(self, nb: int) -> list:
         """vit_engine_debug_pool_scratch for every lane of a MEAN chunk of nb images: per lane a dict of byte ranges inside the y

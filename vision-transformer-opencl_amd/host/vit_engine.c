@@ -54,22 +54,28 @@ _Static_assert(sizeof(vit_image_u8) == sizeof(vithip_image_u8) && offsetof(vit_i
 
 /* What a forward writes, besides where: probabilities [n][classes] and the optional top-1 records, the embedding rows `spec`
  * asks for (stage_features), the class token's attention over the tokens in the last layer (stage_cls_attention), or the residual
- * stream behind the layers `tap` names (stage_tap), [n][out_row_elems()].
+ * stream behind the layers `tap` names (stage_tap), [n][out_row_elems()] -- or, behind the head, the k best classes as records in
+ * place of the probabilities (stage_head; 32-bit words, as many bytes as a float each).
  * Zero-filled before use: the graph cache compares it bytewise.  The pointers are those of the call's (or chunk's) first image. */
-enum { VIT_OUT_PROBS = 0, VIT_OUT_FEATURES = 1, VIT_OUT_ATTENTION = 2, VIT_OUT_INTERMEDIATE = 3 };
+enum { VIT_OUT_PROBS = 0, VIT_OUT_FEATURES = 1, VIT_OUT_ATTENTION = 2, VIT_OUT_INTERMEDIATE = 3, VIT_OUT_TOPK = 4 };
 typedef struct {
     int kind;              /* VIT_OUT_PROBS: dst = probabilities, label / prob = top-1 (may be NULL); _FEATURES: dst = the rows of spec;
-                            * _ATTENTION: dst = the rows of attn_kind; _INTERMEDIATE: dst = the rows of tap */
+                            * _ATTENTION: dst = the rows of attn_kind; _INTERMEDIATE: dst = the rows of tap; _TOPK: dst = the records of
+                            * topk, [n][2k] 32-bit words */
     vit_feature_spec spec;
-    int attn_kind;         /* VIT_ATTN_* (0 otherwise); with it the struct has no padding, which a bytewise comparison would read */
+    int attn_kind;         /* VIT_ATTN_* (0 otherwise) */
+    vit_topk_spec topk;    /* _TOPK: the checked spec (all zero otherwise) */
+    int zero;              /* always 0: with it the struct has no padding, which a bytewise comparison would read */
     vit_intermediate_spec tap; /* _INTERMEDIATE: the checked spec, layers[num_layers..] zero (all zero otherwise) */
     float *dst;
     int *label;
     float *prob;
 } vit_output;
-_Static_assert(sizeof(vit_output) == 4 * sizeof(int) + sizeof(vit_intermediate_spec) + 3 * sizeof(void *) &&
-                   sizeof(vit_intermediate_spec) == (4 + VIT_MAX_TAPS) * sizeof(int) && sizeof(vit_intermediate_spec) % sizeof(void *) == 0,
+_Static_assert(sizeof(vit_output) == 5 * sizeof(int) + sizeof(vit_topk_spec) + sizeof(vit_intermediate_spec) + 3 * sizeof(void *) &&
+                   sizeof(vit_topk_spec) == 3 * sizeof(int) && sizeof(vit_intermediate_spec) == (4 + VIT_MAX_TAPS) * sizeof(int) && sizeof(vit_intermediate_spec) % sizeof(void *) == 0,
                "vit_output must stay free of padding: the graph cache compares it bytewise");
+_Static_assert(VIT_SCORE_PROB == VITHIP_SCORE_PROB && VIT_SCORE_LOGIT == VITHIP_SCORE_LOGIT && VIT_MAX_TOPK == VITHIP_MAX_TOPK,
+               "one numbering of the scores, one bound on k");
 
 /* The resolved operands of the forward.  A GEMM's: W [N][K] in the engine's GEMM dtype, fp32 bias [N], the column sums of W where
  * the LayerNorm fold's epilogue subtracts mean * colsum (else NULL), W's pre-split image on split engines (else NULL). */
@@ -1025,8 +1031,9 @@ static int encoder_layer(chunk_ctx *c, int l) {
 }
 
 /* final LayerNorm on the class-token rows only (ViT_seq.c:429-433 normalises all rows, uses row 0), classifier head
- * (ViT_seq.c:435), Softmax (ViT_seq.c:437) + top-1 (Main.c:62-70) */
-static int stage_head(chunk_ctx *c, float *d_probs, int *d_label, float *d_prob) {
+ * (ViT_seq.c:435), Softmax (ViT_seq.c:437) + top-1 (Main.c:62-70) -- or, for a top-k call, the k best classes of the same logits as
+ * records in the softmax's place: d_probs is then [n][2k] 32-bit words and nothing of [n][classes] is written */
+static int stage_head(chunk_ctx *c, float *d_probs, int *d_label, float *d_prob, const vit_topk_spec *topk) {
     vit_engine *e = c->e;
     const int T = c->T, D = c->D, NC = c->NC;
     for (int j = 0; j < c->L; ++j) {
@@ -1045,15 +1052,21 @@ static int stage_head(chunk_ctx *c, float *d_probs, int *d_label, float *d_prob)
         const vit_lane *ln = &c->lane[j];
         const size_t o = (size_t)ln->off;
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_SOFTMAX));
-        HIP_TRY(e, vithip_softmax_top1_f32(ln->s, e->logits + o * NC, NC, d_probs + o * NC, NC, d_label ? d_label + o : NULL, d_prob ? d_prob + o : NULL, ln->n, NC));
+        if (topk)
+            HIP_TRY(e, vithip_softmax_topk_f32(ln->s, e->logits + o * NC, NC, (int *)d_probs + o * 2 * (size_t)topk->k, 2 * topk->k, ln->n, NC, topk->k,
+                                               topk->score));
+        else
+            HIP_TRY(e, vithip_softmax_top1_f32(ln->s, e->logits + o * NC, NC, d_probs + o * NC, NC, d_label ? d_label + o : NULL, d_prob ? d_prob + o : NULL, ln->n, NC));
         HIP_TRY(e, stage_end(e, ln->s));
     }
     return VIT_OK;
 }
 
-/* The row width's one home: floats per image of an output kind; `kind` is the VIT_FEAT_* or VIT_ATTN_* of a valid spec */
+/* The row width's one home: floats per image of an output kind; `kind` is the VIT_FEAT_* or VIT_ATTN_* of a valid spec, or the k of a
+ * top-k one (its 2k words are 32 bits each, like a float) */
 static size_t row_elems(const vit_engine *e, int out_kind, int kind) {
     if (out_kind == VIT_OUT_PROBS) return (size_t)e->cfg.num_classes;
+    if (out_kind == VIT_OUT_TOPK) return 2 * (size_t)kind;
     if (out_kind == VIT_OUT_ATTENTION) return (kind == VIT_ATTN_HEADS ? (size_t)e->cfg.num_heads : 1) * (size_t)e->tokens;
     return (kind == VIT_FEAT_TOKENS ? (size_t)e->tokens : 1) * (size_t)e->cfg.embed_dim;
 }
@@ -1064,7 +1077,7 @@ static size_t tap_block_elems(const vit_engine *e, int kind) {
 }
 static size_t out_row_elems(const vit_engine *e, const vit_output *out) {
     if (out->kind == VIT_OUT_INTERMEDIATE) return (size_t)out->tap.num_layers * tap_block_elems(e, out->tap.kind);
-    return row_elems(e, out->kind, out->kind == VIT_OUT_ATTENTION ? out->attn_kind : out->spec.kind);
+    return row_elems(e, out->kind, out->kind == VIT_OUT_ATTENTION ? out->attn_kind : out->kind == VIT_OUT_TOPK ? out->topk.k : out->spec.kind);
 }
 
 /* The embedding rows of the chunk instead of the head: the final LayerNorm of the class rows (exactly the launch stage_head makes,
@@ -1210,13 +1223,13 @@ static int forward_chunk(vit_engine *e, vithip_stream_t s, const void *d_images,
         for (int l = 0; l < cfg->depth; ++l) RUN(encoder_layer(c, l));
         if (out->kind == VIT_OUT_FEATURES) RUN(stage_features(c, out));
         else if (out->kind == VIT_OUT_ATTENTION) RUN(stage_cls_attention(c, out));
-        else RUN(stage_head(c, out->dst, out->label, out->prob));
+        else RUN(stage_head(c, out->dst, out->label, out->prob, out->kind == VIT_OUT_TOPK ? &out->topk : NULL));
     }
     for (int j = 1; j < c->L; ++j) { /* join */
         HIP_TRY(e, vithip_event_record(e->ev_join[j - 1], c->lane[j].s));
         HIP_TRY(e, vithip_stream_wait_event(s, e->ev_join[j - 1]));
     }
-    e->last_rows = out->kind == VIT_OUT_PROBS ? nb : 0; /* rows of e->logits the chunk wrote (vit_engine_read_logits) */
+    e->last_rows = out->kind == VIT_OUT_PROBS || out->kind == VIT_OUT_TOPK ? nb : 0; /* rows of e->logits the chunk wrote (vit_engine_read_logits) */
     return VIT_OK;
 }
 #undef RUN
@@ -1319,6 +1332,35 @@ static int output_attention(vit_engine *e, const char *who, const vit_attention_
     out->attn_kind = spec->kind;
     out->dst = dst;
     return VIT_OK;
+}
+
+/* The top-k spec, checked against the model: NULL, or what is wrong as a format for (who, arg[0], arg[1]). */
+static const char *topk_spec_fault(const vit_engine *e, const vit_topk_spec *spec, int arg[2]) {
+    arg[0] = arg[1] = 0;
+    if (!spec) return "%s: the top-k spec is required";
+    arg[0] = spec->k; arg[1] = e->cfg.num_classes < VIT_MAX_TOPK ? e->cfg.num_classes : VIT_MAX_TOPK;
+    if (spec->k < 1 || spec->k > arg[1]) return "%s: k = %d must be 1..%d (the smaller of VIT_MAX_TOPK and num_classes)";
+    arg[0] = spec->score;
+    if (spec->score != VIT_SCORE_PROB && spec->score != VIT_SCORE_LOGIT) return "%s: unknown score %d";
+    arg[0] = spec->reserved;
+    if (spec->reserved != 0) return "%s: vit_topk_spec.reserved must be 0 (got %d)";
+    return NULL;
+}
+
+static int output_topk(vit_engine *e, const char *who, const vit_topk_spec *spec, float *dst, vit_output *out) {
+    int arg[2];
+    const char *fault = topk_spec_fault(e, spec, arg);
+    memset(out, 0, sizeof(*out));
+    if (fault) return fail(e, VIT_ERR_ARG, fault, who, arg[0], arg[1]);
+    out->kind = VIT_OUT_TOPK;
+    out->topk.k = spec->k; out->topk.score = spec->score;
+    out->dst = dst;
+    return VIT_OK;
+}
+
+size_t vit_engine_topk_row_elems(const vit_engine *e, const vit_topk_spec *spec) {
+    int arg[2];
+    return e && !topk_spec_fault(e, spec, arg) ? row_elems(e, VIT_OUT_TOPK, spec->k) : 0;
 }
 
 /* The intermediate spec, checked against the model: NULL, or what is wrong as a format for (who, arg[0], arg[1]). */
@@ -1544,7 +1586,7 @@ static int cut_pieces(vit_engine *e, const char *who, int kind, const void *imag
 }
 
 /* The output staging holds max_batch rows of out_row_cap floats: classes at first, grown to the widest feature, attention or intermediate row a
- * host call has asked for (TOKENS: tokens * embed_dim; HEADS: heads * tokens).  Growing waits for everything in flight, frees both slots and allocates them again; if
+ * host call has asked for (TOKENS: tokens * embed_dim; HEADS: heads * tokens; top-k records: 2k words, wider than a head of fewer classes).  Growing waits for everything in flight, frees both slots and allocates them again; if
  * that fails the call fails with VIT_ERR_NOMEM and the staging is back at its classes-sized start. */
 static int alloc_out_stage(vit_engine *e, size_t bytes) { /* both slots, freed first; a HIP error code, with both slots freed again */
     int rc = 0;
@@ -1692,8 +1734,9 @@ typedef struct {
     const float *mean, *std; /* VIT_IN_U8 */
     const vit_preproc *pp;  /* VIT_IN_IMAGES */
     int out_kind;           /* VIT_OUT_* */
-    const void *spec;       /* vit_feature_spec (VIT_OUT_FEATURES), vit_attention_spec (_ATTENTION) or vit_intermediate_spec (_INTERMEDIATE) */
-    float *dst;             /* VIT_AT_DEVICE: [n][row] */
+    const void *spec;       /* vit_feature_spec (VIT_OUT_FEATURES), vit_attention_spec (_ATTENTION), vit_intermediate_spec (_INTERMEDIATE) or
+                             * vit_topk_spec (_TOPK) */
+    float *dst;             /* VIT_AT_DEVICE: [n][row]; _TOPK: the caller's 32-bit words, carried as the floats they are as wide as */
     float *const *rows;     /* VIT_AT_HOST: a row per image */
     int *label;             /* VIT_AT_DEVICE, VIT_OUT_PROBS: top-1 (may be NULL) */
     float *prob;
@@ -1718,6 +1761,7 @@ static int run_call(vit_engine *e, const vit_call *c) {
     if (c->out_kind == VIT_OUT_FEATURES) rc = output_features(e, c->who, (const vit_feature_spec *)c->spec, c->dst, &out);
     else if (c->out_kind == VIT_OUT_ATTENTION) rc = output_attention(e, c->who, (const vit_attention_spec *)c->spec, c->dst, &out);
     else if (c->out_kind == VIT_OUT_INTERMEDIATE) rc = output_intermediate(e, c->who, (const vit_intermediate_spec *)c->spec, c->dst, &out);
+    else if (c->out_kind == VIT_OUT_TOPK) rc = output_topk(e, c->who, (const vit_topk_spec *)c->spec, c->dst, &out);
     else out = output_probs(c->dst, c->label, c->prob);
     if (rc) return rc;
     return host ? forward_host_in(e, c->who, c->images, &in, c->n, &out, c->rows) : forward_device_in(e, c->images, &in, c->n, &out, c->stream);
@@ -1864,6 +1908,40 @@ int vit_engine_intermediate_host_images(vit_engine *e, const vit_image_u8 *image
                                         const vit_intermediate_spec *spec, float *const *out) {
     return run_call(e, &(vit_call){.who = "intermediate_host_images", .place = VIT_AT_HOST, .in_kind = VIT_IN_IMAGES, .images = images,
                                     .n = n, .pp = pp, .out_kind = VIT_OUT_INTERMEDIATE, .spec = spec, .rows = out});
+}
+
+int vit_engine_topk_device(vit_engine *e, const float *d_images, int n, const vit_topk_spec *spec, int *d_out, void *stream) {
+    return run_call(e, &(vit_call){.who = "topk_device", .place = VIT_AT_DEVICE, .in_kind = VIT_IN_F32, .images = d_images, .n = n,
+                                    .out_kind = VIT_OUT_TOPK, .spec = spec, .dst = (float *)d_out, .stream = stream});
+}
+
+int vit_engine_topk_device_u8(vit_engine *e, const unsigned char *d_images, int n, const float *mean, const float *std,
+                              const vit_topk_spec *spec, int *d_out, void *stream) {
+    return run_call(e, &(vit_call){.who = "topk_device_u8", .place = VIT_AT_DEVICE, .in_kind = VIT_IN_U8, .images = d_images, .n = n,
+                                    .mean = mean, .std = std, .out_kind = VIT_OUT_TOPK, .spec = spec, .dst = (float *)d_out, .stream = stream});
+}
+
+int vit_engine_topk_device_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, const vit_topk_spec *spec,
+                                  int *d_out, void *stream) {
+    return run_call(e, &(vit_call){.who = "topk_device_images", .place = VIT_AT_DEVICE, .in_kind = VIT_IN_IMAGES, .images = images,
+                                    .n = n, .pp = pp, .out_kind = VIT_OUT_TOPK, .spec = spec, .dst = (float *)d_out, .stream = stream});
+}
+
+int vit_engine_topk_host(vit_engine *e, const float *const *images, int n, const vit_topk_spec *spec, int *const *out) {
+    return run_call(e, &(vit_call){.who = "topk_host", .place = VIT_AT_HOST, .in_kind = VIT_IN_F32, .images = images, .n = n,
+                                    .out_kind = VIT_OUT_TOPK, .spec = spec, .rows = (float *const *)out});
+}
+
+int vit_engine_topk_host_u8(vit_engine *e, const unsigned char *const *images, int n, const float *mean, const float *std,
+                            const vit_topk_spec *spec, int *const *out) {
+    return run_call(e, &(vit_call){.who = "topk_host_u8", .place = VIT_AT_HOST, .in_kind = VIT_IN_U8, .images = images, .n = n,
+                                    .mean = mean, .std = std, .out_kind = VIT_OUT_TOPK, .spec = spec, .rows = (float *const *)out});
+}
+
+int vit_engine_topk_host_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, const vit_topk_spec *spec,
+                                int *const *out) {
+    return run_call(e, &(vit_call){.who = "topk_host_images", .place = VIT_AT_HOST, .in_kind = VIT_IN_IMAGES, .images = images, .n = n,
+                                    .pp = pp, .out_kind = VIT_OUT_TOPK, .spec = spec, .rows = (float *const *)out});
 }
 
 int vit_engine_handover_stats(vit_engine *e, long *taken, long *recomputed) {
