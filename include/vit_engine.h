@@ -450,6 +450,59 @@ int vit_engine_topk_host_images(vit_engine *e, const vit_image_u8 *images, int n
                                 int *const *out);
 
 /*
+ * Pooled and multi-layer classifier heads: another operand for the head GEMM, as engine state.  The checkpoint's own head (tensors
+ * base+2, base+3 of the Network) reads LayerNorm_final(x[i][0]); the published classifiers of DINOv2 and of timm's average-pooled
+ * ViTs read something else.  With f the final LayerNorm (tensors base, base+1), x_l the residual stream behind encoder layer l (layer
+ * l = oracle stages[l + 1], as in vit_intermediate_spec), P = T - 1 and K = num_cls_layers, the operand row of image i is
+ *
+ *     [ f(x_{l_0}[i][0]) | ... | f(x_{l_{K-1}}[i][0]) | pooled ]          in_features = (K + (pool != NONE)) * D floats
+ *
+ *     VIT_HEAD_POOL_NONE        no pooled block
+ *     VIT_HEAD_POOL_AVG         pooled = 1/P * sum_{t=1..P} f(x_last[i][t])       norm, then mean (DINOv2 linear heads; timm avg pool)
+ *     VIT_HEAD_POOL_AVG_FCNORM  pooled = f(1/P * sum_{t=1..P} x_last[i][t])       mean, then norm (timm fc_norm, MAE fine-tuned ViTs:
+ *                                                                                 the caller puts fc_norm.weight / .bias into base, base+1)
+ *
+ * over the patch tokens of the LAST layer, and logits = operand . weight^T + bias: weight [num_classes][in_features] row-major
+ * (nn.Linear.weight), bias [num_classes], HOST fp32 arrays read during the call and uploaded as they are (no rounding) to an
+ * allocation of the head's own.  The Network layout, the weight image and the cache file do not know about it.
+ *
+ *     DINOv2 linear head, 1 layer    K = 1, cls_layers = {depth-1}, AVG          weight columns [cls | mean of patch tokens]
+ *     DINOv2 linear head, 4 layers   K = 4, cls_layers = {depth-4..depth-1}, AVG  weight columns [cls of the four layers, earliest first | mean]
+ *     timm global_pool='avg'         K = 0, AVG;   with fc_norm: K = 0, AVG_FCNORM
+ *     another linear probe           K = 1, cls_layers = {depth-1}, NONE: swaps probes on one resident backbone
+ *
+ * Every probability and top-k call, vit_engine_read_logits and the callers built on them use the head in force.  Bits: a class block
+ * is the row of an intermediate call (VIT_TAP_CLS, norm = 1) for that layer, an AVG block the row of a VIT_FEAT_MEAN features call
+ * without L2 -- the same launches, pointed at the operand; AVG_FCNORM is vithip_pool_layernorm_f32 (vit_hip_kernels.h).  The head GEMM is
+ * fp32 on both engine dtypes.  An image's operand, logits and probabilities have the same bits whatever lanes is set to, wherever the
+ * image sits in the batch and whichever of the six input paths delivers the pixels.  All `depth` layers always run.  The features,
+ * attention and intermediate calls do not see the head.
+ * prune_last_layer engines keep pruning with pool = NONE (only class rows are read; same bits); with a pooled block the last layer
+ * runs unpruned for that call -- not an error, the rule of MEAN features.
+ *
+ * vit_engine_set_head: synchronises the device and drops a captured graph, as a weight install does.  spec == NULL (weight and bias
+ * must then be NULL) restores the checkpoint's own head -- and so does EVERY weight install (vit_engine_load_weights*,
+ * vit_engine_load_weight_image, vit_engine_copy_weights*): set the head again behind it.  A head is not copied by copy_weights: set it
+ * per engine.  The new weight, bias and operand rows ([max_batch][in_features]) are allocated before the old ones are freed: on
+ * VIT_ERR_NOMEM the previous head stays in force and the engine stays usable.  VIT_ERR_STATE: no weights loaded yet.  VIT_ERR_ARG,
+ * nothing changed: a NULL weight or bias with a spec, num_cls_layers outside 0..VIT_MAX_TAPS, a layer outside 0..depth-1 or not above
+ * the one before it (the message names the entry), an unknown pool, reserved != 0, an empty operand (K = 0 and NONE).
+ * vit_engine_read_head_operand: debug/test tap beside vit_engine_read_logits -- the operand rows of the most recent chunk (rows of
+ * in_features floats; with the checkpoint's own head, of D floats); an error where read_logits is one.
+ */
+enum { VIT_HEAD_POOL_NONE = 0, VIT_HEAD_POOL_AVG = 1, VIT_HEAD_POOL_AVG_FCNORM = 2 };
+typedef struct {
+    int num_cls_layers;            /* 0..VIT_MAX_TAPS */
+    int cls_layers[VIT_MAX_TAPS];  /* strictly increasing, 0 <= l < depth (layer l = oracle stages[l + 1], as in vit_intermediate_spec) */
+    int pool;                      /* VIT_HEAD_POOL_*: over the patch tokens (rows 1..T-1) of the LAST layer */
+    int reserved;                  /* must be 0 */
+} vit_head_spec;
+/* (num_cls_layers + (pool != NONE)) * D; 0 on a bad spec */
+size_t vit_engine_head_in_features(const vit_engine *e, const vit_head_spec *spec);
+int vit_engine_set_head(vit_engine *e, const vit_head_spec *spec, const float *weight, const float *bias);
+int vit_engine_read_head_operand(vit_engine *e, float *dst, int rows);
+
+/*
  * The fp32 GEMMs' helper-piece hand-over (csrc/vit_gemm_persistent.hip) since the last call, summed over the lanes: tiles whose
  * first K-steps came from a helper workgroup / tiles whose owner found no piece when it looked and computed all of it.  The
  * second number is lost time, never a wrong result (nothing in the hand-over waits or gives up).  Synchronises the device.

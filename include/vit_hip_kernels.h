@@ -455,6 +455,23 @@ int vithip_layernorm_pool_f32(vithip_stream_t stream, const float *x, size_t ldx
 /* x[r][0..dim) /= max(||x[r]||_2, 1e-12) in place (torch.nn.functional.normalize), one workgroup per row: a row's bits do not
  * depend on the number of rows.  dim % 4 == 0, ldx >= dim and a multiple of 4, x 16-byte aligned. */
 int vithip_l2_normalize_rows_f32(vithip_stream_t stream, float *x, size_t ldx, int rows, int dim);
+/*
+ * The other order, pool first and normalise the pooled row (timm's fc_norm heads; csrc/vit_pool.hip):
+ *     m[i][0..dim) = (sum_{t in [first_tok, tokens)} x_it) / (tokens - first_tok);   out[i] = LayerNorm(m[i]) with gamma / beta,
+ * or out[i] = m[i] itself when gamma and beta are both NULL.  Rows of x as above.  The LayerNorm is the arithmetic of
+ * vithip_layernorm_f32 (csrc/vit_layernorm_row.hpp) on the stored fp32 m[i]:
+ *     pool_layernorm(x, gamma, beta) == vithip_layernorm_f32(pool_layernorm(x, NULL, NULL), gamma, beta)   bit for bit.
+ * Same structure and contract as vithip_layernorm_pool_f32: segments of 16 token rows per workgroup summed in a fixed order, one
+ * small finishing launch (one wave per image) that adds the segment sums in index order, divides and normalises; the order depends
+ * on (tokens, first_tok, dim) only, so an image's output row has the same bits at every place of every batch; no atomics; x is read
+ * once; a non-finite row of x reaches its own image's row only.  Only out[i][0..dim) is written.
+ * workspace: vithip_pool_layernorm_f32_workspace_floats(images, tokens, first_tok, dim) floats, 16-byte aligned, free again when the
+ * launches have run.  dim % 4 == 0, dim <= 2048, tokens >= 2, 0 <= first_tok < tokens, ldx / ldo >= dim and multiples of 4, pointers
+ * 16-byte aligned, gamma and beta both NULL or both set; hipErrorInvalidValue otherwise, nothing launched.
+ */
+size_t vithip_pool_layernorm_f32_workspace_floats(int images, int tokens, int first_tok, int dim);
+int vithip_pool_layernorm_f32(vithip_stream_t stream, const float *x, size_t ldx, float *out, size_t ldo, const float *gamma,
+                              const float *beta, int images, int tokens, int first_tok, int dim, float *workspace);
 
 /*
  * The class token's attention over the tokens of its image (csrc/vit_cls_attention.hip): the softmax row of query 0, stored instead

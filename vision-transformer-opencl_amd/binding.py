@@ -80,6 +80,28 @@ class CIntermediateSpec(C.Structure):  # vit_intermediate_spec
 TAP_KINDS = {"cls": 0, "tokens": 1, "patches": 2, "map": 3}  # VIT_TAP_* / VITHIP_TAP_*
 
 
+class CHeadSpec(C.Structure):  # vit_head_spec
+    _fields_ = [("num_cls_layers", C.c_int), ("cls_layers", C.c_int * VIT_MAX_TAPS), ("pool", C.c_int), ("reserved", C.c_int)]
+
+
+HEAD_POOLS = {"none": 0, "avg": 1, "avg_fcnorm": 2}  # VIT_HEAD_POOL_*
+
+
+def head_spec(cls_layers=(), pool="none", depth: Optional[int] = None, reserved: int = 0) -> CHeadSpec:
+    """cls_layers: the layers whose class rows the head reads, in increasing order; with `depth` given, negative entries count from
+    the last layer (-1 = depth - 1).  pool: "none" | "avg" | "avg_fcnorm" (or a raw VIT_HEAD_POOL_* integer); everything is passed
+    through unchecked for the C side to judge: num_cls_layers is len(cls_layers) even where that exceeds VIT_MAX_TAPS."""
+    ls = [int(l) for l in (cls_layers if hasattr(cls_layers, "__iter__") else [cls_layers])]
+    if depth is not None:
+        ls = [l + depth if l < 0 else l for l in ls]
+    spec = CHeadSpec(len(ls))
+    for j, l in enumerate(ls[:VIT_MAX_TAPS]):
+        spec.cls_layers[j] = l
+    spec.pool = HEAD_POOLS[pool] if isinstance(pool, str) else int(pool)
+    spec.reserved = int(reserved)
+    return spec
+
+
 class CTopkSpec(C.Structure):  # vit_topk_spec
     _fields_ = [("k", C.c_int), ("score", C.c_int), ("reserved", C.c_int)]
 
@@ -298,6 +320,15 @@ def lib() -> C.CDLL:
             L.vit_engine_copy_weights_resampled.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
             L.vithip_pos_resample_table.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), f32p, C.c_int]
             L.vithip_pos_resample_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]
+        if hasattr(L, "vit_engine_set_head"):  # an earlier build (see above) has the checkpoint's own head only
+            L.vit_engine_head_in_features.restype = C.c_size_t
+            L.vit_engine_head_in_features.argtypes = [C.c_void_p, C.POINTER(CHeadSpec)]
+            L.vit_engine_set_head.argtypes = [C.c_void_p, C.POINTER(CHeadSpec), f32p, f32p]
+            L.vit_engine_read_head_operand.argtypes = [C.c_void_p, f32p, C.c_int]
+            L.vithip_pool_layernorm_f32_workspace_floats.restype = C.c_size_t
+            L.vithip_pool_layernorm_f32_workspace_floats.argtypes = [C.c_int] * 4
+            L.vithip_pool_layernorm_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.vit_engine_read_logits.argtypes = [C.c_void_p, f32p, C.c_int]
         L.vit_engine_sync.argtypes = [C.c_void_p]
         L.vit_engine_get_stage_times.argtypes = [C.c_void_p, C.POINTER(CStageTimes)]
@@ -822,6 +853,31 @@ def layernorm_pool(x, gamma, beta, images: int, tokens: int, first_tok: int = 1,
     return do.numpy()
 
 
+def pool_layernorm(x, gamma, beta, images: int, tokens: int, first_tok: int = 1, ldx: Optional[int] = None, ldo: Optional[int] = None,
+                   frames=None, out: Optional[dict] = None, override: Optional[dict] = None, out_offset: int = 0) -> np.ndarray:
+    """vithip_pool_layernorm_f32: x [images * tokens][dim] -> [images][dim], the LayerNorm of the mean over tokens first_tok..;
+    gamma = beta = None stores the mean itself.  ldx / ldo, frames, out: as for layernorm(); the output frames are "out" (a row per
+    image) and "ws" (the workspace, exactly the declared floats).  override: C arguments by name (x, ldx, out, ldo, gamma, beta,
+    images, tokens, first_tok, dim, workspace) that replace the ones derived here, for the refusal tests; out_offset: elements by
+    which the output's base is moved off its alignment."""
+    x = _as_f32(x)
+    rows, dim = x.shape
+    assert rows == images * tokens
+    L = lib()
+    F = frames or _Plain
+    dx = F.framed(x, ldx)
+    dg = F.framed(_as_f32(gamma)) if gamma is not None else None
+    db = F.framed(_as_f32(beta)) if beta is not None else None
+    do = F.out_frame(images, dim, ldo, offset=out_offset)
+    ws = F.out_frame(1, max(1, L.vithip_pool_layernorm_f32_workspace_floats(images, tokens, first_tok, dim)))
+    _note(out, out=do, ws=ws)
+    a = dict(x=dx.ptr, ldx=dx.ld, out=do.ptr, ldo=do.ld, gamma=dg.ptr if dg else None, beta=db.ptr if db else None, images=images,
+             tokens=tokens, first_tok=first_tok, dim=dim, workspace=ws.ptr)
+    a.update(override or {})
+    hip_check(L.vithip_pool_layernorm_f32(None, *a.values()), "vithip_pool_layernorm_f32")
+    return do.window()
+
+
 def l2_normalize_rows(x) -> np.ndarray:
     """vithip_l2_normalize_rows_f32: row / max(||row||_2, 1e-12)."""
     x = _as_f32(x)
@@ -1186,6 +1242,7 @@ class Engine:
                  fp32_split: int = 0):
         self.cfg = cfg
         self._h = C.c_void_p()
+        self._head_in = None  # floats per operand row of a head set by set_head(); None: the checkpoint's own head (embed_dim)
         cc = CConfig.of(cfg)
         opt = COptions(device, max_batch, 1 if profile else 0, lanes, {"f32": 0, "bf16": 1}[dtype],
                        1 if prune_last_layer else 0, 1 if use_graph else 0, gemm_tile, ln_fold, gemm_handover_test, host_first_piece,
@@ -1200,12 +1257,15 @@ class Engine:
 
     def _check(self, rc: int, what: str) -> None:
         if rc != 0:
-            raise VitError(f"{what} failed ({rc}): {lib().vit_engine_last_error(self._h).decode()}")
+            err = VitError(f"{what} failed ({rc}): {lib().vit_engine_last_error(self._h).decode()}")
+            err.code = int(rc)  # VIT_ERR_*
+            raise err
 
     def load_weights(self, weights: Sequence[np.ndarray], pos_from: Optional[int] = None, pos_mode="bicubic") -> None:
         """pos_from: the input size the checkpoint was trained at; its position embedding (tensor 3, for that size) is resampled on
         the device to this engine's cfg.img_size, pos_mode "bicubic" | "bicubic_aa" (vit_engine_load_weights_resampled)."""
         arr, keep = networks_from(weights)
+        self._head_in = None  # every install restores the checkpoint's own head
         if pos_from is None:
             self._check(lib().vit_engine_load_weights(self._h, arr, len(weights)), "vit_engine_load_weights")
             return
@@ -1213,6 +1273,7 @@ class Engine:
         self._check(lib().vit_engine_load_weights_resampled(self._h, arr, len(weights), C.byref(rs)), "vit_engine_load_weights_resampled")
 
     def load_weight_image(self, img: "WeightImage") -> None:
+        self._head_in = None
         self._check(lib().vit_engine_load_weight_image(self._h, C.byref(img.c)), "vit_engine_load_weight_image")
 
     def read_weight_image(self) -> "WeightImage":
@@ -1224,6 +1285,7 @@ class Engine:
         """pos_mode "bicubic" | "bicubic_aa": `other` may run at another img_size; its resident position embedding is resampled to
         this engine's (vit_engine_copy_weights_resampled).  None: the plain replication between equal configurations."""
         L = lib()
+        self._head_in = None
         if pos_mode is not None:
             self._check(L.vit_engine_copy_weights_resampled(self._h, other._h, _pos_mode(pos_mode)), "vit_engine_copy_weights_resampled")
             return
@@ -1484,6 +1546,40 @@ class Engine:
     def logits(self, rows: int) -> np.ndarray:
         out = np.empty((rows, self.cfg.num_classes), np.float32)
         self._check(lib().vit_engine_read_logits(self._h, out.ctypes.data_as(f32p), rows), "vit_engine_read_logits")
+        return out
+
+    # ---- classifier heads (vit_engine_set_head): pooled and multi-layer operands for the head GEMM ----
+    def head_in_features(self, cls_layers=(), pool="none") -> int:
+        """Floats per operand row of such a head, (len(cls_layers) + (pool != "none")) * embed_dim; 0 on a bad spec."""
+        return int(lib().vit_engine_head_in_features(self._h, C.byref(head_spec(cls_layers, pool, self.cfg.depth))))
+
+    def set_head(self, weight, bias, cls_layers=(), pool="none", reserved: int = 0) -> None:
+        """A head of its own for every later probability / top-k call: weight [num_classes][in_features] (nn.Linear.weight), bias
+        [num_classes]; the operand row is [final LayerNorm of the class rows behind cls_layers | pooled patch tokens of the last
+        layer], pool "none" | "avg" (norm, then mean) | "avg_fcnorm" (mean, then norm).  Negative layers count from the last.
+        Every weight install restores the checkpoint's own head: call this again behind it.
+          DINOv2 linear head, 1 layer: cls_layers=(-1,), pool="avg";  4 layers: cls_layers=(-4, -3, -2, -1), pool="avg"
+          timm global_pool="avg": pool="avg";  with fc_norm: pool="avg_fcnorm" (fc_norm's tensors in the final LayerNorm's slots)"""
+        spec = head_spec(cls_layers, pool, self.cfg.depth, reserved)
+        w = None if weight is None else _as_f32(weight)
+        b = None if bias is None else _as_f32(bias)
+        F = int(lib().vit_engine_head_in_features(self._h, C.byref(spec)))
+        if F and w is not None and b is not None and (w.size != self.cfg.num_classes * F or b.size != self.cfg.num_classes):
+            raise VitError(f"set_head: weight has {w.size} floats and bias {b.size}, the head needs {self.cfg.num_classes} x {F} and "
+                           f"{self.cfg.num_classes}")
+        self._check(lib().vit_engine_set_head(self._h, C.byref(spec), None if w is None else w.ctypes.data_as(f32p),
+                                              None if b is None else b.ctypes.data_as(f32p)), "vit_engine_set_head")
+        self._head_in = F
+
+    def reset_head(self) -> None:
+        """Back to the checkpoint's own head (vit_engine_set_head with a NULL spec)."""
+        self._check(lib().vit_engine_set_head(self._h, None, None, None), "vit_engine_set_head")
+        self._head_in = None
+
+    def head_operand(self, rows: int) -> np.ndarray:
+        """vit_engine_read_head_operand: the head GEMM's operand rows of the most recent chunk, [rows][in_features]."""
+        out = np.empty((rows, self._head_in or self.cfg.embed_dim), np.float32)
+        self._check(lib().vit_engine_read_head_operand(self._h, out.ctypes.data_as(f32p), rows), "vit_engine_read_head_operand")
         return out
 
     def handover_stats(self) -> dict:

@@ -23,9 +23,20 @@
 //
 // l2_normalize_rows: row /= max(||row||_2, 1e-12) (torch.nn.functional.normalize), one workgroup per row, the sum of squares
 // reduced in a fixed order -- the bits of a row do not depend on how many rows the launch has.
+//
+// pool_layernorm: the other order, for heads that pool first and normalise the pooled row (timm fc_norm):
+//
+//   m[i][:] = 1/(tokens - first_tok) * sum_{t = first_tok}^{tokens-1} x[i][t][:];   out[i] = LayerNorm(m[i])   (or m[i] itself)
+//
+// The same two launches with the same segments, the same order of additions and the same clamped loads, minus the statistics
+// in the streaming pass: pool_sum_partial adds raw rows, pool_layernorm_finish (ONE wave per image, which holds the row as
+// vit_layernorm_row.hpp wants it) adds the partial rows in segment order, divides by the row count and normalises the row with
+// the arithmetic of vithip_layernorm_f32 -- the pooled row passes through LDS, so the statistics are taken from the stored fp32
+// values exactly as a vithip_layernorm_f32 launch would take them from memory.
 #include <hip/hip_runtime.h>
 
 #include "vit_hip_kernels.h"
+#include "vit_layernorm_row.hpp"
 
 namespace {
 
@@ -155,12 +166,125 @@ __global__ __launch_bounds__(POOL_THREADS) void l2_normalize_rows_kernel(float *
     }
 }
 
+// pool_layernorm, launch 1: layernorm_pool_partial_kernel without the statistics.  grid.x = images * segs; partial [images][segs][dim]
+template <int NVEC>
+__global__ __launch_bounds__(POOL_THREADS) void pool_sum_partial_kernel(const float *__restrict__ x, size_t ldx, float *__restrict__ partial,
+                                                                         int tokens, int first_tok, int dim, int segs) {
+    __shared__ f32x4 red[POOL_WAVES - 1][NVEC * 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int image = blockIdx.x / segs, seg = blockIdx.x - image * segs;
+    const float *img = x + (size_t)image * tokens * ldx;
+    const int t0 = first_tok + seg * POOL_SEG + wave;
+
+    f32x4 v[POOL_ROWS_PER_WAVE][NVEC];
+#pragma unroll
+    for (int k = 0; k < POOL_ROWS_PER_WAVE; ++k) {
+        const int t = t0 + k * POOL_WAVES;
+        const float *src = img + (size_t)(t < tokens ? t : tokens - 1) * ldx;  // clamped: always a row of this image
+#pragma unroll
+        for (int i = 0; i < NVEC; ++i) {
+            const int c = (i * 64 + lane) * 4;
+            v[k][i] = c < dim ? *reinterpret_cast<const f32x4 *>(src + c) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        }
+    }
+    f32x4 acc[NVEC];
+#pragma unroll
+    for (int i = 0; i < NVEC; ++i) acc[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int k = 0; k < POOL_ROWS_PER_WAVE; ++k) {
+        if (t0 + k * POOL_WAVES < tokens) {  // wave-uniform
+#pragma unroll
+            for (int i = 0; i < NVEC; ++i) acc[i] += v[k][i];
+        }
+    }
+    if (wave > 0) {
+#pragma unroll
+        for (int i = 0; i < NVEC; ++i) red[wave - 1][i * 64 + lane] = acc[i];
+    }
+    __syncthreads();
+    if (wave == 0) {
+        float *dst = partial + ((size_t)image * segs + seg) * dim;
+#pragma unroll
+        for (int i = 0; i < NVEC; ++i) {
+            const int c = (i * 64 + lane) * 4;
+            if (c < dim) {
+                f32x4 a = acc[i];
+#pragma unroll
+                for (int w = 0; w < POOL_WAVES - 1; ++w) a += red[w][i * 64 + lane];
+                *reinterpret_cast<f32x4 *>(dst + c) = a;
+            }
+        }
+    }
+}
+
+// pool_layernorm, launch 2: one workgroup of ONE wave per image; lane q holds float4 q, q + 64, ... of the row (vit_layernorm_row.hpp).
+// gamma == NULL (then beta is too; workgroup-uniform): the pooled mean itself is the output.
+template <int NVEC>
+__global__ __launch_bounds__(64) void pool_layernorm_finish_kernel(const float *__restrict__ partial, float *__restrict__ out, size_t ldo,
+                                                                   const float *__restrict__ gamma, const float *__restrict__ beta, int dim,
+                                                                   int segs, float count) {
+    __shared__ f32x4 pooled[NVEC * 64];
+    const int lane = threadIdx.x;
+    const float *src = partial + (size_t)blockIdx.x * segs * dim;
+    float *dst = out + (size_t)blockIdx.x * ldo;
+    // segments outermost: the lane's NVEC loads of a segment are independent, so the chain of dependent loads is segs long
+    f32x4 a[NVEC];
+#pragma unroll
+    for (int i = 0; i < NVEC; ++i) {
+        const int c = (i * 64 + lane) * 4;
+        a[i] = c < dim ? *reinterpret_cast<const f32x4 *>(src + c) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+    for (int s = 1; s < segs; ++s) {
+#pragma unroll
+        for (int i = 0; i < NVEC; ++i) {
+            const int c = (i * 64 + lane) * 4;
+            if (c < dim) a[i] += *reinterpret_cast<const f32x4 *>(src + (size_t)s * dim + c);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NVEC; ++i) {
+        const int c = (i * 64 + lane) * 4;
+        if (c < dim) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a[i][j] = a[i][j] / count;
+            if (gamma) pooled[i * 64 + lane] = a[i];
+            else *reinterpret_cast<f32x4 *>(dst + c) = a[i];
+        }
+    }
+    if (!gamma) return;
+    __syncthreads();
+    f32x4 v[NVEC];
+    float mean, inv_std;
+    vit_ln::row_stats<NVEC>(reinterpret_cast<const float *>(pooled), dim, lane, v, mean, inv_std);
+#pragma unroll
+    for (int i = 0; i < NVEC; ++i) {
+        const int c = (i * 64 + lane) * 4;
+        if (c < dim) {
+            const f32x4 g = *reinterpret_cast<const f32x4 *>(gamma + c);
+            const f32x4 b = *reinterpret_cast<const f32x4 *>(beta + c);
+            *reinterpret_cast<f32x4 *>(dst + c) = vit_ln::row_affine(v[i], mean, inv_std, g, b);
+        }
+    }
+}
+
 int pool_segs(int tokens, int first_tok) { return (tokens - first_tok + POOL_SEG - 1) / POOL_SEG; }
 
 template <int NVEC>
 int launch_partial(hipStream_t s, const float *x, size_t ldx, float *partial, int images, int tokens, int first_tok, int dim, int segs) {
     hipLaunchKernelGGL(layernorm_pool_partial_kernel<NVEC>, dim3((unsigned)images * (unsigned)segs), dim3(POOL_THREADS), 0, s, x, ldx,
                        partial, tokens, first_tok, dim, segs);
+    return static_cast<int>(hipGetLastError());
+}
+
+template <int NVEC>
+int launch_pool_layernorm(hipStream_t s, const float *x, size_t ldx, float *out, size_t ldo, const float *gamma, const float *beta,
+                          float *partial, int images, int tokens, int first_tok, int dim, int segs) {
+    hipLaunchKernelGGL(pool_sum_partial_kernel<NVEC>, dim3((unsigned)images * (unsigned)segs), dim3(POOL_THREADS), 0, s, x, ldx, partial,
+                       tokens, first_tok, dim, segs);
+    const int rc = static_cast<int>(hipGetLastError());
+    if (rc) return rc;
+    hipLaunchKernelGGL(pool_layernorm_finish_kernel<NVEC>, dim3(images), dim3(64), 0, s, partial, out, ldo, gamma, beta, dim, segs,
+                       (float)(tokens - first_tok));
     return static_cast<int>(hipGetLastError());
 }
 
@@ -211,6 +335,32 @@ int vithip_layernorm_pool_f32(vithip_stream_t stream, const float *x, size_t ldx
     rc = static_cast<int>(hipGetLastError());
     if (rc || !l2_normalize) return rc;
     return l2_launch(s, out, ldo, images, dim);
+}
+
+size_t vithip_pool_layernorm_f32_workspace_floats(int images, int tokens, int first_tok, int dim) {
+    return vithip_layernorm_pool_f32_workspace_floats(images, tokens, first_tok, dim);  // the same partial rows
+}
+
+int vithip_pool_layernorm_f32(vithip_stream_t stream, const float *x, size_t ldx, float *out, size_t ldo, const float *gamma,
+                              const float *beta, int images, int tokens, int first_tok, int dim, float *workspace) {
+    if (!x || !out || (gamma == nullptr) != (beta == nullptr) || !workspace || images <= 0 || dim <= 0 || first_tok < 0 || tokens < 2 ||
+        tokens <= first_tok)
+        return static_cast<int>(hipErrorInvalidValue);
+    if (dim % 4 || dim > 64 * 4 * POOL_MAX_VEC || ldx % 4 || ldo % 4 || ldx < (size_t)dim || ldo < (size_t)dim)
+        return static_cast<int>(hipErrorInvalidValue);
+    if ((reinterpret_cast<size_t>(x) & 15) || (reinterpret_cast<size_t>(out) & 15) || (reinterpret_cast<size_t>(gamma) & 15) ||
+        (reinterpret_cast<size_t>(beta) & 15) || (reinterpret_cast<size_t>(workspace) & 15))
+        return static_cast<int>(hipErrorInvalidValue);
+    const int segs = pool_segs(tokens, first_tok);
+    if ((size_t)images * segs > (size_t)0x7fffffff) return static_cast<int>(hipErrorInvalidValue);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch ((dim + 255) / 256) {
+        case 1: return launch_pool_layernorm<1>(s, x, ldx, out, ldo, gamma, beta, workspace, images, tokens, first_tok, dim, segs);
+        case 2: return launch_pool_layernorm<2>(s, x, ldx, out, ldo, gamma, beta, workspace, images, tokens, first_tok, dim, segs);
+        case 3: return launch_pool_layernorm<3>(s, x, ldx, out, ldo, gamma, beta, workspace, images, tokens, first_tok, dim, segs);
+        case 4: return launch_pool_layernorm<4>(s, x, ldx, out, ldo, gamma, beta, workspace, images, tokens, first_tok, dim, segs);
+        default: return launch_pool_layernorm<POOL_MAX_VEC>(s, x, ldx, out, ldo, gamma, beta, workspace, images, tokens, first_tok, dim, segs);
+    }
 }
 
 }  // extern "C"

@@ -124,6 +124,12 @@ struct vit_engine {
 
     /* workspace for max_batch images */
     float *x, *y, *qkv, *hbuf, *z, *logits;
+    /* a caller's classifier head (vit_engine_set_head); head_w == NULL: the checkpoint's own (final.head, reading z).  The checked
+     * spec, the operand's width (num_cls_layers + (pool != NONE)) * D, and three allocations of the head's own: the weight
+     * [num_classes][head_in] with a zeroed tail pad behind it (as wblob has), the bias, and the operand rows [max_batch][head_in] */
+    vit_head_spec head;
+    size_t head_in;
+    float *head_w, *head_b, *head_operand;
     /* host-pointer path: double-buffered staging so that gather + H2D of piece i+1 overlap compute of piece i */
     float *in_stage[2], *out_stage[2];   /* device */
     float *pin_in[2], *pin_out[2];       /* pinned host */
@@ -408,6 +414,7 @@ void vit_engine_destroy(vit_engine *e) {
     if (e->graph) vithip_graph_destroy(e->graph);
     vithip_free(e->x); vithip_free(e->y); vithip_free(e->qkv); vithip_free(e->hbuf);
     vithip_free(e->z); vithip_free(e->logits);
+    vithip_free(e->head_w); vithip_free(e->head_b); vithip_free(e->head_operand);
     for (int j = 0; j < VIT_MAX_LANES; ++j) vithip_gemm_f32_workspace_destroy(e->gemm_ws[j]);
     if (e->copy_stream) { vithip_stream_sync(e->copy_stream); vithip_stream_destroy(e->copy_stream); }
     if (e->ev_in_stage) vithip_event_destroy(e->ev_in_stage);
@@ -545,8 +552,20 @@ static int resolve_operands(vit_engine *e) {
     return VIT_OK;
 }
 
-/* The tail of every install, behind the last write to wblob: the fold, the split images and the operand table, then the sync. */
+/* Back to the checkpoint's own head: a caller's head (vit_engine_set_head) and its allocations go.  Nothing may be in flight. */
+static void restore_own_head(vit_engine *e) {
+    if (!e->head_w) return;
+    vithip_free(e->head_w); vithip_free(e->head_b); vithip_free(e->head_operand);
+    e->head_w = e->head_b = e->head_operand = NULL;
+    memset(&e->head, 0, sizeof(e->head));
+    e->head_in = 0;
+    e->last_rows = 0;
+}
+
+/* The tail of every install, behind the last write to wblob: the fold, the split images and the operand table, then the sync.
+ * Every install also puts the checkpoint's own head back in force (alloc_weight_blob has synchronised and dropped the graph). */
 static int finish_install(vit_engine *e) {
+    restore_own_head(e);
     const int rc = resolve_operands(e);
     if (rc) return rc;
     HIP_TRY(e, vithip_stream_sync(e->stream));
@@ -1030,22 +1049,30 @@ static int encoder_layer(chunk_ctx *c, int l) {
     return VIT_OK;
 }
 
+static int head_last_blocks(chunk_ctx *c, const vit_lane *ln); /* behind stage_features, whose pooling scratch it shares */
+
 /* final LayerNorm on the class-token rows only (ViT_seq.c:429-433 normalises all rows, uses row 0), classifier head
  * (ViT_seq.c:435), Softmax (ViT_seq.c:437) + top-1 (Main.c:62-70) -- or, for a top-k call, the k best classes of the same logits as
  * records in the softmax's place: d_probs is then [n][2k] 32-bit words and nothing of [n][classes] is written */
 static int stage_head(chunk_ctx *c, float *d_probs, int *d_label, float *d_prob, const vit_topk_spec *topk) {
     vit_engine *e = c->e;
     const int T = c->T, D = c->D, NC = c->NC;
+    /* the head GEMM's operand: the checkpoint's own head reads z [n][D]; a caller's head its operand rows [n][head_in], whose
+     * class blocks of earlier layers are in place (stage_head_tap) and whose last-layer blocks are written here */
+    const int F = e->head_w ? (int)e->head_in : D;
+    float *const operand = e->head_w ? e->head_operand : e->z;
+    const vit_gemm_ops head = e->head_w ? (vit_gemm_ops){.W = e->head_w, .bias = e->head_b} : e->final.head;
     for (int j = 0; j < c->L; ++j) {
         const vit_lane *ln = &c->lane[j];
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
-        HIP_TRY(e, vithip_layernorm_f32(ln->s, ln->x, (size_t)T * D, e->z + (size_t)ln->off * D, (size_t)D, e->final.ln_g, e->final.ln_b, ln->n, D));
+        if (!e->head_w) HIP_TRY(e, vithip_layernorm_f32(ln->s, ln->x, (size_t)T * D, e->z + (size_t)ln->off * D, (size_t)D, e->final.ln_g, e->final.ln_b, ln->n, D));
+        else RUN(head_last_blocks(c, ln));
         HIP_TRY(e, stage_end(e, ln->s));
     }
     for (int j = 0; j < c->L; ++j) {
         const vit_lane *ln = &c->lane[j];
-        const gemm_desc g = {.stage = VIT_STAGE_HEAD, .A = e->z + (size_t)ln->off * D, .lda = D, .ops = e->final.head,
-                             .C = e->logits + (size_t)ln->off * NC, .ldc = NC, .M = ln->n, .N = NC, .K = D, .role = VITHIP_EPI_BIAS};
+        const gemm_desc g = {.stage = VIT_STAGE_HEAD, .A = operand + (size_t)ln->off * F, .lda = F, .ops = head,
+                             .C = e->logits + (size_t)ln->off * NC, .ldc = NC, .M = ln->n, .N = NC, .K = F, .role = VITHIP_EPI_BIAS};
         RUN(gemm(e, ln->s, &g, NULL));
     }
     for (int j = 0; j < c->L; ++j) {
@@ -1156,6 +1183,52 @@ static int stage_tap(chunk_ctx *c, const vit_output *out, int j) {
     return VIT_OK;
 }
 
+/* A caller's head (vit_engine_set_head).  The operand row of an image is [class blocks, in the order of cls_layers | pooled block],
+ * head_in floats; every launch writes one block of the lane's images with the whole row as its image stride, like stage_tap.
+ *
+ * stage_head_tap: behind encoder layer l < depth - 1 when cls_layers names it: the class block of that layer, the launch (and so
+ * the bits) of an intermediate call with VIT_TAP_CLS, norm = 1. */
+static int stage_head_tap(chunk_ctx *c, int l) {
+    vit_engine *e = c->e;
+    const vit_head_spec *h = &e->head;
+    int k = 0;
+    while (k < h->num_cls_layers && h->cls_layers[k] != l) ++k;
+    if (k == h->num_cls_layers || l == e->cfg.depth - 1) return VIT_OK;
+    for (int j = 0; j < c->L; ++j) {
+        const vit_lane *ln = &c->lane[j];
+        HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
+        HIP_TRY(e, vithip_tap_f32(ln->s, ln->x, (size_t)c->D, e->head_operand + (size_t)ln->off * e->head_in + (size_t)k * c->D, e->head_in,
+                                  e->final.ln_g, e->final.ln_b, ln->n, c->T, c->D, VITHIP_TAP_CLS));
+        HIP_TRY(e, stage_end(e, ln->s));
+    }
+    return VIT_OK;
+}
+
+/* ... and the blocks of the last layer, for one lane inside stage_head's LayerNorm bracket: its class block by the launch the
+ * checkpoint's own head makes (a pruned last layer has updated exactly those rows), the pooled block by the launch of a MEAN
+ * features call without L2 (AVG) or by pool-then-normalise (AVG_FCNORM), their scratch in the lane's own rows of y as there. */
+static int head_last_blocks(chunk_ctx *c, const vit_lane *ln) {
+    vit_engine *e = c->e;
+    const vit_head_spec *h = &e->head;
+    const size_t T = (size_t)c->T, D = (size_t)c->D, F = e->head_in;
+    const int K = h->num_cls_layers;
+    float *row = e->head_operand + (size_t)ln->off * F;
+    if (K && h->cls_layers[K - 1] == e->cfg.depth - 1)
+        HIP_TRY(e, vithip_layernorm_f32(ln->s, ln->x, T * D, row + (size_t)(K - 1) * D, F, e->final.ln_g, e->final.ln_b, ln->n, c->D));
+    if (h->pool == VIT_HEAD_POOL_NONE) return VIT_OK;
+    const size_t esz = e->opt.dtype == VIT_DTYPE_BF16 ? sizeof(unsigned short) : sizeof(float);
+    size_t need;
+    float *scratch = pool_scratch(c, ln, &need); /* both pooling kernels keep the same partial rows */
+    if (need == 0 || need > (size_t)ln->n * T * D * esz || ((size_t)scratch & 15))
+        return fail(e, VIT_ERR_STATE, "head: the pooling scratch (%zu bytes) does not fit the lane's own %zu bytes of y", need,
+                    (size_t)ln->n * T * D * esz);
+    if (h->pool == VIT_HEAD_POOL_AVG)
+        HIP_TRY(e, vithip_layernorm_pool_f32(ln->s, ln->x, D, row + (size_t)K * D, F, e->final.ln_g, e->final.ln_b, ln->n, c->T, 1, c->D, 0, scratch));
+    else
+        HIP_TRY(e, vithip_pool_layernorm_f32(ln->s, ln->x, D, row + (size_t)K * D, F, e->final.ln_g, e->final.ln_b, ln->n, c->T, 1, c->D, scratch));
+    return VIT_OK;
+}
+
 /* The chunk's context for nb images written as `out` says: dimensions, whether the last layer is pruned, and the lanes -- their
  * images, streams and rows of the activation buffers.  Launches nothing. */
 static void chunk_setup(vit_engine *e, vithip_stream_t s, int nb, const vit_output *out, chunk_ctx *c) {
@@ -1165,7 +1238,8 @@ static void chunk_setup(vit_engine *e, vithip_stream_t s, int nb, const vit_outp
     c->L = e->opt.lanes > VIT_MAX_LANES ? VIT_MAX_LANES : e->opt.lanes;
     if (c->L < 1 || nb < 2 * c->L) c->L = 1;
     c->pruned = e->opt.prune_last_layer && c->T <= 224 && !(out->kind == VIT_OUT_FEATURES && out->spec.kind != VIT_FEAT_CLS) &&
-                !(out->kind == VIT_OUT_INTERMEDIATE && out->tap.kind != VIT_TAP_CLS);
+                !(out->kind == VIT_OUT_INTERMEDIATE && out->tap.kind != VIT_TAP_CLS) &&
+                !((out->kind == VIT_OUT_PROBS || out->kind == VIT_OUT_TOPK) && e->head_w && e->head.pool != VIT_HEAD_POOL_NONE);
     c->qkv_only = out->kind == VIT_OUT_ATTENTION;
     const int bf16 = e->opt.dtype == VIT_DTYPE_BF16;
     const size_t B = (size_t)e->opt.max_batch, T = (size_t)c->T, D = (size_t)c->D, H = (size_t)c->H;
@@ -1220,7 +1294,11 @@ static int forward_chunk(vit_engine *e, vithip_stream_t s, const void *d_images,
             if (l == out->tap.layers[j]) RUN(stage_tap(c, out, j++));
         }
     } else {
-        for (int l = 0; l < cfg->depth; ++l) RUN(encoder_layer(c, l));
+        const int head_taps = e->head_w && (out->kind == VIT_OUT_PROBS || out->kind == VIT_OUT_TOPK);
+        for (int l = 0; l < cfg->depth; ++l) {
+            RUN(encoder_layer(c, l));
+            if (head_taps) RUN(stage_head_tap(c, l));
+        }
         if (out->kind == VIT_OUT_FEATURES) RUN(stage_features(c, out));
         else if (out->kind == VIT_OUT_ATTENTION) RUN(stage_cls_attention(c, out));
         else RUN(stage_head(c, out->dst, out->label, out->prob, out->kind == VIT_OUT_TOPK ? &out->topk : NULL));
@@ -1966,6 +2044,94 @@ int vit_engine_read_logits(vit_engine *e, float *dst, int rows) {
     if (rows <= 0 || rows > e->last_rows) return fail(e, VIT_ERR_ARG, "read_logits: %d rows requested, last chunk had %d", rows, e->last_rows);
     HIP_TRY(e, vithip_device_sync()); /* the chunk may have run on a caller-provided stream */
     HIP_TRY(e, vithip_memcpy_d2h(dst, e->logits, (size_t)rows * e->cfg.num_classes * sizeof(float), e->stream));
+    HIP_TRY(e, vithip_stream_sync(e->stream));
+    return VIT_OK;
+}
+
+/* The head spec, checked against the model: NULL, or what is wrong as a format for (arg[0], arg[1]). */
+static const char *head_spec_fault(const vit_engine *e, const vit_head_spec *spec, int arg[2]) {
+    arg[0] = arg[1] = 0;
+    arg[0] = spec->num_cls_layers; arg[1] = VIT_MAX_TAPS;
+    if (spec->num_cls_layers < 0 || spec->num_cls_layers > VIT_MAX_TAPS) return "set_head: num_cls_layers = %d must be 0..%d";
+    arg[0] = spec->pool;
+    if (spec->pool != VIT_HEAD_POOL_NONE && spec->pool != VIT_HEAD_POOL_AVG && spec->pool != VIT_HEAD_POOL_AVG_FCNORM)
+        return "set_head: unknown pool %d";
+    arg[0] = spec->reserved;
+    if (spec->reserved != 0) return "set_head: vit_head_spec.reserved must be 0 (got %d)";
+    for (int j = 0; j < spec->num_cls_layers; ++j) {
+        arg[0] = j; arg[1] = spec->cls_layers[j];
+        if (spec->cls_layers[j] < 0 || spec->cls_layers[j] >= e->cfg.depth) return "set_head: cls_layers[%d] = %d is not a layer of the model";
+        if (j && spec->cls_layers[j] <= spec->cls_layers[j - 1]) return "set_head: cls_layers[%d] = %d is not above the entry before it (strictly increasing)";
+    }
+    if (spec->num_cls_layers == 0 && spec->pool == VIT_HEAD_POOL_NONE) return "set_head: the operand is empty (no class layers and no pooled block)";
+    if (spec->pool != VIT_HEAD_POOL_NONE && e->tokens < 2) return "set_head: a pooled block needs at least one patch token";
+    return NULL;
+}
+
+size_t vit_engine_head_in_features(const vit_engine *e, const vit_head_spec *spec) {
+    int arg[2];
+    if (!e || !spec || head_spec_fault(e, spec, arg)) return 0;
+    return (size_t)(spec->num_cls_layers + (spec->pool != VIT_HEAD_POOL_NONE)) * (size_t)e->cfg.embed_dim;
+}
+
+int vit_engine_set_head(vit_engine *e, const vit_head_spec *spec, const float *weight, const float *bias) {
+    if (!e) return VIT_ERR_ARG;
+    if (!spec && (weight || bias)) return fail(e, VIT_ERR_ARG, "set_head: a NULL spec (the checkpoint's own head) takes no weight and no bias");
+    if (spec) {
+        int arg[2];
+        const char *fault = head_spec_fault(e, spec, arg);
+        if (fault) return fail(e, VIT_ERR_ARG, fault, arg[0], arg[1]);
+        if (!weight || !bias) return fail(e, VIT_ERR_ARG, "set_head: weight and bias are required with a spec");
+    }
+    if (!e->weights_loaded) return fail(e, VIT_ERR_STATE, "set_head before vit_engine_load_weights()");
+    HIP_TRY(e, vithip_set_device(e->opt.device));
+    if (!spec) { /* as an install: nothing in flight, no graph with the old operands in its launches */
+        HIP_TRY(e, vithip_device_sync());
+        drop_graph(e);
+        restore_own_head(e);
+        return VIT_OK;
+    }
+    /* the new head first, whole; only then the old one goes */
+    const size_t F = vit_engine_head_in_features(e, spec), NC = (size_t)e->cfg.num_classes, B = (size_t)e->opt.max_batch;
+    const size_t wbytes = NC * F * sizeof(float);
+    const size_t pad = 128 * F * sizeof(float) > WEIGHT_TAIL_PAD ? 128 * F * sizeof(float) : WEIGHT_TAIL_PAD; /* a GEMM tile of rows */
+    float *w = NULL, *b = NULL, *operand = NULL;
+    int hrc = vithip_malloc((void **)&w, wbytes + pad);
+    if (!hrc) hrc = vithip_malloc((void **)&b, NC * sizeof(float));
+    if (!hrc) hrc = vithip_malloc((void **)&operand, B * F * sizeof(float));
+    if (hrc) {
+        vithip_free(w); vithip_free(b); vithip_free(operand);
+        return fail(e, VIT_ERR_NOMEM, "set_head: no memory for a head of %zu x %zu floats and %zu operand rows (HIP error %d: %s); the previous head stays",
+                    NC, F, B, hrc, vithip_error_string(hrc));
+    }
+    hrc = vithip_memcpy_h2d(w, weight, wbytes, e->stream);
+    if (!hrc) hrc = vithip_memset((char *)w + wbytes, 0, pad, e->stream);
+    if (!hrc) hrc = vithip_memcpy_h2d(b, bias, NC * sizeof(float), e->stream);
+    if (!hrc) hrc = vithip_memset(operand, 0, B * F * sizeof(float), e->stream);
+    if (!hrc) hrc = vithip_device_sync(); /* the uploads, and every forward that still reads the old head, on whatever stream */
+    if (hrc) {
+        vithip_free(w); vithip_free(b); vithip_free(operand);
+        return fail(e, VIT_ERR_HIP, "set_head: HIP error %d (%s) uploading the head; the previous head stays", hrc, vithip_error_string(hrc));
+    }
+    drop_graph(e);
+    restore_own_head(e);
+    memset(&e->head, 0, sizeof(e->head)); /* the entries of cls_layers behind num_cls_layers stay zero */
+    e->head.num_cls_layers = spec->num_cls_layers;
+    for (int j = 0; j < spec->num_cls_layers; ++j) e->head.cls_layers[j] = spec->cls_layers[j];
+    e->head.pool = spec->pool;
+    e->head_in = F;
+    e->head_w = w; e->head_b = b; e->head_operand = operand;
+    e->last_rows = 0;
+    return VIT_OK;
+}
+
+int vit_engine_read_head_operand(vit_engine *e, float *dst, int rows) {
+    if (!e || !dst) return VIT_ERR_ARG;
+    if (rows <= 0 || rows > e->last_rows) return fail(e, VIT_ERR_ARG, "read_head_operand: %d rows requested, last chunk had %d", rows, e->last_rows);
+    const float *operand = e->head_w ? e->head_operand : e->z;
+    const size_t F = e->head_w ? e->head_in : (size_t)e->cfg.embed_dim;
+    HIP_TRY(e, vithip_device_sync()); /* the chunk may have run on a caller-provided stream */
+    HIP_TRY(e, vithip_memcpy_d2h(dst, operand, (size_t)rows * F * sizeof(float), e->stream));
     HIP_TRY(e, vithip_stream_sync(e->stream));
     return VIT_OK;
 }
