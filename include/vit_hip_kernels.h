@@ -318,6 +318,29 @@ int vithip_layernorm_f32(vithip_stream_t stream, const float *x, size_t ldx, flo
                          const float *gamma, const float *beta, int rows, int dim);
 
 /*
+ * SwiGLU: the gate of a gated MLP (csrc/vit_swiglu.hip; Dinov2SwiGLUFFN of transformers, SwiGLUFFNFused of DINOv2).
+ *     h[r][j] = silu(u[r][j]) * u[r][H + j]   for r < rows, j < H,   silu(g) = g / (1 + exp(-g))
+ * u: [rows][ldu], the first 2H columns are read (gate | value: what chunk(2, dim=-1) makes of the w12 output);
+ * h: [rows][ldh], the first H columns are written and nothing else.
+ * Arithmetic, per element with gate g and value v, all fp32, one rounding per step:
+ *     e = expf(-g)  (the library expf, within 1 ulp);  s = 1.0f + e;  q = g / s  (IEEE-rounded);  h = q * v
+ * and, for g < -87 only, where expf(-g) nears and then passes the end of the fp32 range while silu(g) is still a normal number
+ * (silu(-89) = -2.0e-37):
+ *     t = expf(0.5f * g);  h = ((g * t) * v) * t          (1 + exp(g) rounds to 1 there)
+ * which keeps the result inside 4 ulp + 2^-126 of the exact one over the whole range.  _bf16 widens both inputs to fp32 (exact), does
+ * the same and rounds h to bf16 once, to nearest even (the conversion of every other bf16 store).  So: g = +Inf gives v * Inf,
+ * g = -Inf gives NaN (as PyTorch's x * sigmoid(x)), a NaN in g or v gives NaN, g < -208 (t underflows) gives -0 * v.
+ * Aliasing: exactly in place (h == u and ldh == ldu: the gate half of a row becomes h, the value half keeps its bits) or disjoint
+ * address ranges; any other overlap is hipErrorInvalidValue.
+ * Requirements (anything else: hipErrorInvalidValue, nothing launched): rows >= 1; H >= 4 and H % 4 == 0 (_bf16: 8); ldu >= 2H,
+ * ldh >= H, both multiples of 4 (_bf16: 8); u and h 16-byte aligned.  Offsets are 64-bit (rows * ldu may pass 2^31 elements).
+ * Values are element-local: a non-finite u[r][j] or u[r][H + j] reaches h[r][j] alone; every other output has the bits of the same
+ * launch on clean data.
+ */
+int vithip_swiglu_f32(vithip_stream_t stream, const float *u, size_t ldu, float *h, size_t ldh, int rows, int H);
+int vithip_swiglu_bf16(vithip_stream_t stream, const unsigned short *u, size_t ldu, unsigned short *h, size_t ldh, int rows, int H);
+
+/*
  * Fused scaled-dot-product attention, one workgroup per (image, head) (x blocks of 256 queries when chunked).
  * qkv: [n*T][3*D] rows = tokens, columns [Q | K | V], head h = columns 64h..64h+63 of each.
  * out: [n*T][D].  scores = q.k / sqrtf(64); row softmax with max subtraction; out = P.V.

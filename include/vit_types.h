@@ -37,7 +37,7 @@ typedef struct {
  * ViT_opencl.c:12-23); here they are a runtime struct so that the same engine serves
  * ViT-B/16-224 (the default), reduced test models and ViT-L/16-384.
  * Constraints of the HIP path: embed_dim / num_heads == 64, embed_dim % 32 == 0, embed_dim <= 2048,
- * hidden_dim % 32 == 0, patch_size and img_size even (patch 14 included; the 8-bit and decoded-image
+ * hidden_dim % 32 == 0 (bf16 engines: % 64; under VIT_MLP_SWIGLU the 2 * hidden_dim rows of fc1 inherit it), patch_size and img_size even (patch 14 included; the 8-bit and decoded-image
  * input calls also need img_size % 4 == 0).
  */
 typedef struct {
@@ -48,8 +48,24 @@ typedef struct {
     int embed_dim;    /* 768 */
     int depth;        /* 12  */
     int num_heads;    /* 12  */
-    int hidden_dim;   /* 3072 = (int)(embed_dim * mlp_ratio), ViT_seq.c:254 */
+    int hidden_dim;   /* 3072 = (int)(embed_dim * mlp_ratio), ViT_seq.c:254: the width of the hidden layer that fc2 reads, below 2^24;
+                       * bits 24..30 hold the MLP kind (0 = VIT_MLP_GELU, so a plain width is a GELU model): VIT_HIDDEN_DIM_OF() */
 } vit_config;
+
+/*
+ * The MLP kind.  VIT_MLP_GELU: fc1 -> erf-GELU -> fc2.  VIT_MLP_SWIGLU: fc1 is the fused [2 * H][embed_dim] "w12" (gate rows first,
+ * value rows behind) and the hidden layer is silu(gate) * value.  The struct keeps its eight ints -- compiled callers, positional
+ * initialisers and the cache file's eight header words stay as they are -- so the kind travels in the top bits of hidden_dim:
+ *     vit_config g14 = {224, 14, 3, 1000, 1536, 40, 24, VIT_HIDDEN_DIM_OF(4096, VIT_MLP_SWIGLU)};
+ * Read the two parts with VIT_HIDDEN_DIM(cfg) and VIT_MLP_KIND(cfg), never hidden_dim itself.
+ */
+enum { VIT_MLP_GELU = 0, VIT_MLP_SWIGLU = 1 };
+#define VIT_MLP_SHIFT 24
+#define VIT_HIDDEN_DIM_OF(width, mlp) ((int)(width) | ((int)(mlp) << VIT_MLP_SHIFT))
+#define VIT_HIDDEN_DIM(cfg) ((cfg)->hidden_dim & ((1 << VIT_MLP_SHIFT) - 1))
+#define VIT_MLP_KIND(cfg) ((cfg)->hidden_dim >> VIT_MLP_SHIFT)
+/* output rows of the fc1 weight (tensors 8 and 9 of a layer hold VIT_FC1_ROWS * embed_dim and VIT_FC1_ROWS floats) */
+#define VIT_FC1_ROWS(cfg) (VIT_MLP_KIND(cfg) == VIT_MLP_SWIGLU ? 2 * VIT_HIDDEN_DIM(cfg) : VIT_HIDDEN_DIM(cfg))
 
 #define VIT_WEIGHTS_PER_LAYER 12
 /* number of Network entries: cls, conv w/b, pos, 12 per layer, ln w/b, head w/b (Main.c:29-30 => 152) */

@@ -11,7 +11,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .synth import ModelConfig
+from .synth import MLP_KINDS, MLP_SHIFT, ModelConfig
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # VIT_HIP_LIBRARY: the probe build (make probes -> libvit_mi355x_probe.so) for the tools/ scripts; default = the product
@@ -39,7 +39,7 @@ class CConfig(C.Structure):
     @classmethod
     def of(cls, cfg: ModelConfig) -> "CConfig":
         return cls(cfg.img_size, cfg.patch_size, cfg.in_chans, cfg.num_classes, cfg.embed_dim,
-                   cfg.depth, cfg.num_heads, cfg.hidden_dim)
+                   cfg.depth, cfg.num_heads, cfg.hidden_dim | (MLP_KINDS.get(cfg.mlp, cfg.mlp) << MLP_SHIFT))
 
 
 class CNetwork(C.Structure):  # Network.h:18-21
@@ -764,6 +764,32 @@ def layernorm(x, gamma, beta, ldx: Optional[int] = None, ldy: Optional[int] = No
     _note(out, y=dy)
     hip_check(lib().vithip_layernorm_f32(None, dx.ptr, dx.ld, dy.ptr, dy.ld, dg.ptr, db.ptr, rows, dim), "vithip_layernorm_f32")
     return dy.window()
+
+
+def swiglu_raw(u_ptr, ldu: int, h_ptr, ldh: int, rows: int, H: int, bf16: bool = False) -> int:
+    """vithip_swiglu_f32 / vithip_swiglu_bf16 on caller-owned device addresses; returns the HIP status (no exception)."""
+    fn = lib().vithip_swiglu_bf16 if bf16 else lib().vithip_swiglu_f32
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int]
+    return int(fn(None, u_ptr, ldu, h_ptr, ldh, rows, H))
+
+
+def swiglu(u, H: int, in_place: bool = False, ldu: Optional[int] = None, ldh: Optional[int] = None, frames=None,
+           out: Optional[dict] = None) -> np.ndarray:
+    """vithip_swiglu_f32 (u float32) or vithip_swiglu_bf16 (u uint16 = bf16 bits): u [rows][2H] = gate | value -> h [rows][H].
+    in_place: h is written over the gate half of u's own rows (ldh = ldu); the returned rows are then all 2H columns of u after the
+    launch, [h | value].  ldu / ldh, frames, out: as for gemm(); the output frame is "h" (in place: u's frame)."""
+    u = np.ascontiguousarray(u)
+    bf16 = u.dtype == np.uint16
+    if not bf16:
+        u = _as_f32(u)
+    rows, two_h = u.shape
+    assert two_h == 2 * H, (u.shape, H)
+    F = frames or _Plain
+    du = F.framed(u, ldu)
+    dh = du if in_place else F.out_frame(rows, H, ldh, u.dtype)
+    _note(out, h=dh)
+    hip_check(swiglu_raw(du.ptr, du.ld, dh.ptr, dh.ld, rows, H, bf16), "vithip_swiglu_bf16" if bf16 else "vithip_swiglu_f32")
+    return dh.window()
 
 
 def tap_block(images: int, tokens: int, dim: int, layout) -> tuple:

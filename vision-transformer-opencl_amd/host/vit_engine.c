@@ -168,11 +168,11 @@ enum { LW_LN1_G, LW_LN1_B, LW_QKV_W, LW_QKV_B, LW_OUT_W, LW_OUT_B, LW_LN2_G, LW_
 _Static_assert(LW_FC2_B + 1 == VIT_WEIGHTS_PER_LAYER, "LW_* names every tensor of a layer");
 
 /* The derived operands' layout, per layer (resolve_operands fills them, and names the slots):
- *   wfold   [gamma1-folded in_proj 3D x D | gamma2-folded fc1 H x D], elements of the engine's GEMM dtype
- *   wfoldf  [colsum qkv 3D | bias qkv 3D | colsum fc1 H | bias fc1 H]
+ *   wfold   [gamma1-folded in_proj 3D x D | gamma2-folded fc1 H1 x D], elements of the engine's GEMM dtype
+ *   wfoldf  [colsum qkv 3D | bias qkv 3D | colsum fc1 H1 | bias fc1 H1]        (H1 = VIT_FC1_ROWS: H, or 2H under SwiGLU)
  *   wsplit  the images of [qkv | out_proj | fc1 | fc2] at wsplit_off[0..3], wsplit_layer bytes (vit_engine_create) */
-static size_t fold_w_elems(const vit_config *c) { return (3 * (size_t)c->embed_dim + (size_t)c->hidden_dim) * (size_t)c->embed_dim; }
-static size_t fold_f_elems(const vit_config *c) { return 6 * (size_t)c->embed_dim + 2 * (size_t)c->hidden_dim; }
+static size_t fold_w_elems(const vit_config *c) { return (3 * (size_t)c->embed_dim + (size_t)VIT_FC1_ROWS(c)) * (size_t)c->embed_dim; }
+static size_t fold_f_elems(const vit_config *c) { return 6 * (size_t)c->embed_dim + 2 * (size_t)VIT_FC1_ROWS(c); }
 
 /* ------------------------------------------------------------------------------------------ */
 
@@ -187,7 +187,7 @@ int vit_config_tokens(const vit_config *cfg) {
 }
 
 size_t vit_config_weight_size(const vit_config *cfg, int index) {
-    const size_t D = (size_t)cfg->embed_dim, H = (size_t)cfg->hidden_dim;
+    const size_t D = (size_t)cfg->embed_dim, H = (size_t)VIT_HIDDEN_DIM(cfg), H1 = (size_t)VIT_FC1_ROWS(cfg);
     const size_t T = (size_t)vit_config_tokens(cfg);
     const size_t PK = (size_t)cfg->in_chans * cfg->patch_size * cfg->patch_size;
     const int base = 4 + VIT_WEIGHTS_PER_LAYER * cfg->depth;
@@ -201,25 +201,25 @@ size_t vit_config_weight_size(const vit_config *cfg, int index) {
         return s[index - base];
     }
     {
-        /* ln1 w,b | in_proj w,b | out_proj w,b | ln2 w,b | fc1 w,b | fc2 w,b  (ViT_seq.c:366-426) */
-        const size_t s[12] = {D, D, 3 * D * D, 3 * D, D * D, D, D, D, H * D, H, D * H, D};
+        /* ln1 w,b | in_proj w,b | out_proj w,b | ln2 w,b | fc1 w,b | fc2 w,b  (ViT_seq.c:366-426); SwiGLU: fc1 = w12, 2H rows */
+        const size_t s[12] = {D, D, 3 * D * D, 3 * D, D * D, D, D, D, H1 * D, H1, D * H, D};
         return s[(index - 4) % VIT_WEIGHTS_PER_LAYER];
     }
 }
 
 unsigned long long vit_config_macs_per_image(const vit_config *cfg) {
     const unsigned long long T = (unsigned long long)vit_config_tokens(cfg), D = cfg->embed_dim,
-                             H = cfg->hidden_dim, hd = D / cfg->num_heads,
+                             H = VIT_HIDDEN_DIM(cfg), H1 = (unsigned long long)VIT_FC1_ROWS(cfg), hd = D / cfg->num_heads,
                              PK = (unsigned long long)cfg->in_chans * cfg->patch_size * cfg->patch_size;
-    const unsigned long long layer = T * D * 3 * D + 2 * cfg->num_heads * T * T * hd + T * D * D + 2 * T * D * H;
+    const unsigned long long layer = T * D * 3 * D + 2 * cfg->num_heads * T * T * hd + T * D * D + T * D * H1 + T * H * D;
     return (T - 1) * PK * D + cfg->depth * layer + D * cfg->num_classes;
 }
 
 unsigned long long vit_config_macs_per_image_pruned(const vit_config *cfg) {
-    const unsigned long long T = (unsigned long long)vit_config_tokens(cfg), D = cfg->embed_dim, H = cfg->hidden_dim,
-                             hd = D / cfg->num_heads;
+    const unsigned long long T = (unsigned long long)vit_config_tokens(cfg), D = cfg->embed_dim, H = VIT_HIDDEN_DIM(cfg),
+                             H1 = (unsigned long long)VIT_FC1_ROWS(cfg), hd = D / cfg->num_heads;
     /* last layer: Q projection, both attention products, out_proj, fc1, fc2 for one row instead of T */
-    const unsigned long long saved = (T - 1) * (D * D + 2 * cfg->num_heads * T * hd + D * D + 2 * D * H);
+    const unsigned long long saved = (T - 1) * (D * D + 2 * cfg->num_heads * T * hd + D * D + D * H1 + H * D);
     return vit_config_macs_per_image(cfg) - saved;
 }
 
@@ -262,12 +262,15 @@ const vit_config *vit_engine_config(const vit_engine *e) { return &e->cfg; }
 static int check_config(vit_engine *e) {
     const vit_config *c = &e->cfg;
     if (c->img_size <= 0 || c->patch_size <= 0 || c->in_chans <= 0 || c->num_classes <= 0 ||
-        c->embed_dim <= 0 || c->depth <= 0 || c->num_heads <= 0 || c->hidden_dim <= 0)
+        c->embed_dim <= 0 || c->depth <= 0 || c->num_heads <= 0 || c->hidden_dim <= 0 || VIT_HIDDEN_DIM(c) == 0)
         return fail(e, VIT_ERR_ARG, "vit_config: all dimensions must be positive");
+    if (VIT_MLP_KIND(c) != VIT_MLP_GELU && VIT_MLP_KIND(c) != VIT_MLP_SWIGLU)
+        return fail(e, VIT_ERR_ARG, "vit_config.hidden_dim: MLP kind %d (VIT_MLP_KIND, bits 24..30): VIT_MLP_GELU (%d) or VIT_MLP_SWIGLU (%d)",
+                    VIT_MLP_KIND(c), VIT_MLP_GELU, VIT_MLP_SWIGLU);
     if (c->img_size % c->patch_size) return fail(e, VIT_ERR_ARG, "img_size must be a multiple of patch_size");
     if (c->embed_dim % c->num_heads || c->embed_dim / c->num_heads != 64)
         return fail(e, VIT_ERR_ARG, "HIP attention kernel needs head_dim == 64 (got %d/%d)", c->embed_dim, c->num_heads);
-    if (c->embed_dim % 32 || c->hidden_dim % 32)
+    if (c->embed_dim % 32 || VIT_HIDDEN_DIM(c) % 32)
         return fail(e, VIT_ERR_ARG, "embed_dim and hidden_dim must be multiples of 32");
     /* what vithip_patch_embed_f32 takes: the 16-byte gather or, for every other even geometry (patch 14), the general kernel */
     if (c->patch_size % 2 || c->img_size % 2)
@@ -304,7 +307,7 @@ int vit_engine_create(vit_engine **out, const vit_config *cfg, const vit_engine_
         /* The fp32 GEMMs (and the patch gather) address an A operand through a buffer descriptor with 32-bit byte
          * offsets (csrc/vit_gemm.hip): one launch may span < 2 GiB of images, LN output, attention output or MLP hidden
          * rows.  That bounds the images of one LANE; larger chunks are cut down in forward_device/forward_host. */
-        const size_t T_ = (size_t)e->tokens, per[3] = {T_ * (size_t)e->cfg.hidden_dim, T_ * (size_t)e->cfg.embed_dim,
+        const size_t T_ = (size_t)e->tokens, per[3] = {T_ * (size_t)VIT_FC1_ROWS(&e->cfg), T_ * (size_t)e->cfg.embed_dim,
                                                          (size_t)e->cfg.in_chans * e->cfg.img_size * e->cfg.img_size};
         size_t worst = per[0] > per[1] ? per[0] : per[1];
         if (per[2] > worst) worst = per[2];
@@ -332,12 +335,14 @@ int vit_engine_create(vit_engine **out, const vit_config *cfg, const vit_engine_
     HIP_TRY(e, vithip_event_create(&e->ev_fork));
 
     const size_t B = (size_t)e->opt.max_batch, T = (size_t)e->tokens, D = (size_t)e->cfg.embed_dim,
-                 H = (size_t)e->cfg.hidden_dim, NC = (size_t)e->cfg.num_classes;
+                 H = (size_t)VIT_HIDDEN_DIM(&e->cfg), H1 = (size_t)VIT_FC1_ROWS(&e->cfg), NC = (size_t)e->cfg.num_classes;
     const size_t img = (size_t)e->cfg.in_chans * e->cfg.img_size * e->cfg.img_size;
     HIP_TRY(e, vithip_malloc((void **)&e->x, B * T * D * sizeof(float)));
     HIP_TRY(e, vithip_malloc((void **)&e->y, B * T * D * sizeof(float)));
     HIP_TRY(e, vithip_malloc((void **)&e->qkv, B * T * 3 * D * sizeof(float)));
-    HIP_TRY(e, vithip_malloc((void **)&e->hbuf, B * T * H * sizeof(float)));
+    /* the MLP's rows: the hidden layer or, under SwiGLU, fc1's [gate | value] rows, whose gate half becomes the hidden layer in
+     * place (encoder_layer) */
+    HIP_TRY(e, vithip_malloc((void **)&e->hbuf, B * T * H1 * sizeof(float)));
     HIP_TRY(e, vithip_malloc((void **)&e->z, B * D * sizeof(float)));
     HIP_TRY(e, vithip_malloc((void **)&e->logits, B * NC * sizeof(float)));
     if (e->opt.lanes > VIT_MAX_LANES) e->opt.lanes = VIT_MAX_LANES;
@@ -373,7 +378,7 @@ int vit_engine_create(vit_engine **out, const vit_config *cfg, const vit_engine_
         /* W's pieces, made once per upload (resolve_operands): the persistent split walk then splits only A.  6 bytes per weight of
          * the four encoder GEMMs; without the image (K not a multiple of 32) every GEMM splits W on the fly, with the same bits */
         const size_t b[4] = {vithip_split3_weights_bytes((int)(3 * D), (int)D), vithip_split3_weights_bytes((int)D, (int)D),
-                             vithip_split3_weights_bytes((int)H, (int)D), vithip_split3_weights_bytes((int)D, (int)H)};
+                             vithip_split3_weights_bytes((int)H1, (int)D), vithip_split3_weights_bytes((int)D, (int)H)};
         if (b[0] && b[1] && b[2] && b[3]) {
             e->wsplit_layer = 0;
             for (int i = 0; i < 4; ++i) { e->wsplit_off[i] = e->wsplit_layer; e->wsplit_layer += b[i]; }
@@ -399,7 +404,7 @@ int vit_engine_create(vit_engine **out, const vit_config *cfg, const vit_engine_
     if (!e->w || !e->w16 || !e->layer || !e->img_recs || !e->img_off) return fail(e, VIT_ERR_NOMEM, "out of host memory");
     if (e->opt.dtype != VIT_DTYPE_F32 && e->opt.dtype != VIT_DTYPE_BF16)
         return fail(e, VIT_ERR_ARG, "dtype must be VIT_DTYPE_F32 or VIT_DTYPE_BF16");
-    if (e->opt.dtype == VIT_DTYPE_BF16 && (e->cfg.embed_dim % 64 || e->cfg.hidden_dim % 64))
+    if (e->opt.dtype == VIT_DTYPE_BF16 && (e->cfg.embed_dim % 64 || VIT_HIDDEN_DIM(&e->cfg) % 64))
         return fail(e, VIT_ERR_ARG, "bf16 path needs embed_dim and hidden_dim to be multiples of 64");
     if (e->opt.profile) return vit_engine_set_profile(e, 1);
     return VIT_OK;
@@ -510,7 +515,7 @@ static int alloc_weight_blob(vit_engine *e, const size_t *off, size_t f32_floats
  *   split  fp32 engines: W's pieces, 4 launches per layer.
  * The table points into wblob, which alloc_weight_blob may move: it is rebuilt by every install, never patched. */
 static int resolve_operands(vit_engine *e) {
-    const int bf16 = e->opt.dtype == VIT_DTYPE_BF16, D = e->cfg.embed_dim, H = e->cfg.hidden_dim;
+    const int bf16 = e->opt.dtype == VIT_DTYPE_BF16, D = e->cfg.embed_dim, H = VIT_HIDDEN_DIM(&e->cfg), H1 = VIT_FC1_ROWS(&e->cfg);
     const size_t esz = bf16 ? sizeof(unsigned short) : sizeof(float);
     float **tail = e->w + W_LAYER0 + VIT_WEIGHTS_PER_LAYER * e->cfg.depth;
     e->embed = (vit_embed_ops){e->w[W_CLS], e->w[W_CONV_W], e->w[W_CONV_B], e->w[W_POS], e->w16[W_CONV_W]};
@@ -524,15 +529,15 @@ static int resolve_operands(vit_engine *e) {
 #undef GEMM_OPS
         if (e->fold) {
             void *w_qkv = at(e->wfold, (size_t)l * fold_w_elems(&e->cfg), esz), *w_fc1 = at(w_qkv, 3 * (size_t)D * D, esz);
-            float *cs_qkv = e->wfoldf + (size_t)l * fold_f_elems(&e->cfg), *b_qkv = cs_qkv + 3 * D, *cs_fc1 = b_qkv + 3 * D, *b_fc1 = cs_fc1 + H;
+            float *cs_qkv = e->wfoldf + (size_t)l * fold_f_elems(&e->cfg), *b_qkv = cs_qkv + 3 * D, *cs_fc1 = b_qkv + 3 * D, *b_fc1 = cs_fc1 + H1;
             if (bf16) { /* in_proj: the Q rows also carry the factor of the scores' exponent (the attention kernels are told: _qscaled) */
                 HIP_TRY(e, vithip_ln_fold_weights_scaled(e->stream, lw[LW_QKV_W], lw[LW_QKV_B], o.ln1_g, o.ln1_b, w_qkv, cs_qkv, b_qkv, 3 * D, D, D, VITHIP_QSCALE));
-                HIP_TRY(e, vithip_ln_fold_weights(e->stream, lw[LW_FC1_W], lw[LW_FC1_B], o.ln2_g, o.ln2_b, w_fc1, cs_fc1, b_fc1, H, D));
+                HIP_TRY(e, vithip_ln_fold_weights(e->stream, lw[LW_FC1_W], lw[LW_FC1_B], o.ln2_g, o.ln2_b, w_fc1, cs_fc1, b_fc1, H1, D));
             } else { /* fp32 products, sums in double, rounded once; centred weights (vit_hip_kernels.h): the GEMMs deliver
                       * x . (gamma W)^T - mean * colsum themselves and their epilogues only scale, so no column sums are passed on:
                       * their slots receive what the weights' rounding left of the sums and are not read again */
                 HIP_TRY(e, vithip_ln_fold_weights_f32_centered(e->stream, lw[LW_QKV_W], lw[LW_QKV_B], o.ln1_g, o.ln1_b, w_qkv, cs_qkv, b_qkv, 3 * D, D));
-                HIP_TRY(e, vithip_ln_fold_weights_f32_centered(e->stream, lw[LW_FC1_W], lw[LW_FC1_B], o.ln2_g, o.ln2_b, w_fc1, cs_fc1, b_fc1, H, D));
+                HIP_TRY(e, vithip_ln_fold_weights_f32_centered(e->stream, lw[LW_FC1_W], lw[LW_FC1_B], o.ln2_g, o.ln2_b, w_fc1, cs_fc1, b_fc1, H1, D));
                 cs_qkv = cs_fc1 = NULL;
             }
             o.qkv.W = w_qkv; o.qkv.bias = b_qkv; o.qkv.colsum = cs_qkv;
@@ -540,7 +545,7 @@ static int resolve_operands(vit_engine *e) {
         }
         if (e->wsplit) { /* 4 launches: the image of every encoder GEMM weight as its GEMM reads it, folded (centred) or raw */
             vit_gemm_ops *g[4] = {&o.qkv, &o.out, &o.fc1, &o.fc2}; /* the order of wsplit_off[] */
-            const int N[4] = {3 * D, D, H, D}, K[4] = {D, D, D, H};
+            const int N[4] = {3 * D, D, H1, D}, K[4] = {D, D, D, H};
             for (int i = 0; i < 4; ++i) {
                 void *img = e->wsplit + (size_t)l * e->wsplit_layer + e->wsplit_off[i];
                 HIP_TRY(e, vithip_split3_weights_f32(e->stream, g[i]->W, K[i], N[i], K[i], img));
@@ -883,6 +888,7 @@ typedef struct {
     vit_lane lane[VIT_MAX_LANES];
     int L;                       /* lanes in use for this chunk */
     int T, D, H, NC;
+    int H1;                      /* columns of a row of the lanes' h: VIT_FC1_ROWS (H; 2H under SwiGLU, [gate -> hidden | value]) */
     int pruned;                  /* the last layer computes the class rows only: prune_last_layer, unless the chunk's output needs every token */
     int qkv_only;                /* the last layer stops behind its QKV GEMM: the chunk's output is read from its Q and K (attention calls) */
 } chunk_ctx;
@@ -955,6 +961,9 @@ static int row_stats(chunk_ctx *c, const vit_lane *ln, size_t ldx, float *pairs,
 /*
  * Encoder layer l (ViT_seq.c:276-300): LN1 -> QKV in_proj -> attention -> out_proj + residual -> LN2 -> fc1 + GELU -> fc2 +
  * residual, each step issued for every lane before the next one starts.  What varies is where rows are and which kernel runs:
+ *   mlp     VIT_MLP_SWIGLU: fc1 is the bias-only GEMM of the fused w12, N = 2H, into rows of 2H columns [gate | value]; one launch
+ *           (vithip_swiglu_*, still the fc1 stage) turns the gate half into the hidden layer silu(gate) * value in place; fc2 reads it
+ *           there, lda = 2H.  The GEMMs know nothing of it, and a GELU engine's launches are the ones they were.
  *   dtype   bf16 engines keep the LN output, qkv, the attention output and the MLP hidden layer in bf16; the residual stream x,
  *           the LayerNorm statistics, softmax and every accumulation stay fp32.
  *   fold    the LayerNorm fold (vit_hip_kernels.h, "LayerNorm folding"): in_proj and fc1 read the raw rows (x, or its bf16 copy)
@@ -968,7 +977,7 @@ static int row_stats(chunk_ctx *c, const vit_lane *ln, size_t ldx, float *pairs,
  */
 static int encoder_layer(chunk_ctx *c, int l) {
     vit_engine *e = c->e;
-    const int T = c->T, D = c->D, H = c->H, heads = e->cfg.num_heads;
+    const int T = c->T, D = c->D, H = c->H, H1 = c->H1, heads = e->cfg.num_heads, swiglu = VIT_MLP_KIND(&e->cfg) == VIT_MLP_SWIGLU;
     const int bf16 = e->opt.dtype == VIT_DTYPE_BF16, fold = e->fold, feeds_next = l + 1 < e->cfg.depth;
     const int pruned = c->pruned && !feeds_next;
     const size_t esz = bf16 ? sizeof(unsigned short) : sizeof(float); /* GEMM weights and activations */
@@ -1031,17 +1040,23 @@ static int encoder_layer(chunk_ctx *c, int l) {
         if (!fold) RUN(layernorm(c, ln->s, ln->x, (size_t)r * D, ln->y, D, o->ln2_g, o->ln2_b, rows[j]));
         else if (!ln2_ready[j]) RUN(row_stats(c, ln, (size_t)r * D, pairs[j], rows[j]));
     }
-    for (int j = 0; j < c->L; ++j) { /* fc1 + GELU (ViT_seq.c:258-264) */
+    for (int j = 0; j < c->L; ++j) { /* fc1 + GELU (ViT_seq.c:258-264); SwiGLU: w12 + bias, then the gate */
         const vit_lane *ln = &c->lane[j];
-        gemm_desc g = {.stage = VIT_STAGE_FC1, .bf16 = bf16, .A = ln->y, .lda = D, .ops = o->fc1, .C = ln->h, .ldc = H,
-                       .M = rows[j], .N = H, .K = D, .role = VITHIP_EPI_BIAS_GELU};
+        gemm_desc g = {.stage = VIT_STAGE_FC1, .bf16 = bf16, .A = ln->y, .lda = D, .ops = o->fc1, .C = ln->h, .ldc = H1,
+                       .M = rows[j], .N = H1, .K = D, .role = swiglu ? VITHIP_EPI_BIAS : VITHIP_EPI_BIAS_GELU};
         if (fold) { g.A = ln->xa; g.lda = r * D; g.ln_rows = pairs[j]; }
         RUN(gemm(e, ln->s, &g, NULL));
+        if (swiglu) {
+            HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_FC1));
+            if (bf16) HIP_TRY(e, vithip_swiglu_bf16(ln->s, ln->h, (size_t)H1, ln->h, (size_t)H1, rows[j], H));
+            else HIP_TRY(e, vithip_swiglu_f32(ln->s, ln->h, (size_t)H1, ln->h, (size_t)H1, rows[j], H));
+            HIP_TRY(e, stage_end(e, ln->s));
+        }
     }
     for (int j = 0; j < c->L; ++j) { /* fc2 + residual (ViT_seq.c:266,297-299): x += h . W2^T + b2; folded, it also leaves the
                                       * pairs of the next layer's LN1 when there is one */
         vit_lane *ln = &c->lane[j];
-        gemm_desc g = {.stage = VIT_STAGE_FC2, .bf16 = bf16, .A = ln->h, .lda = H, .ops = o->fc2, .C = ln->x, .ldc = r * D,
+        gemm_desc g = {.stage = VIT_STAGE_FC2, .bf16 = bf16, .A = ln->h, .lda = H1, .ops = o->fc2, .C = ln->x, .ldc = r * D,
                        .M = rows[j], .N = D, .K = H, .role = VITHIP_EPI_BIAS_RESIDUAL};
         if (fold && feeds_next) { g.stats_rows = ln->tok_pairs; g.stats_part = ln->partials; g.x16 = bf16 ? ln->xa : NULL; }
         RUN(gemm(e, ln->s, &g, &ln->stats_ready));
@@ -1234,7 +1249,7 @@ static int head_last_blocks(chunk_ctx *c, const vit_lane *ln) {
 static void chunk_setup(vit_engine *e, vithip_stream_t s, int nb, const vit_output *out, chunk_ctx *c) {
     const vit_config *cfg = &e->cfg;
     c->e = e;
-    c->T = e->tokens; c->D = cfg->embed_dim; c->H = cfg->hidden_dim; c->NC = cfg->num_classes;
+    c->T = e->tokens; c->D = cfg->embed_dim; c->H = VIT_HIDDEN_DIM(cfg); c->H1 = VIT_FC1_ROWS(cfg); c->NC = cfg->num_classes;
     c->L = e->opt.lanes > VIT_MAX_LANES ? VIT_MAX_LANES : e->opt.lanes;
     if (c->L < 1 || nb < 2 * c->L) c->L = 1;
     c->pruned = e->opt.prune_last_layer && c->T <= 224 && !(out->kind == VIT_OUT_FEATURES && out->spec.kind != VIT_FEAT_CLS) &&
@@ -1242,7 +1257,7 @@ static void chunk_setup(vit_engine *e, vithip_stream_t s, int nb, const vit_outp
                 !((out->kind == VIT_OUT_PROBS || out->kind == VIT_OUT_TOPK) && e->head_w && e->head.pool != VIT_HEAD_POOL_NONE);
     c->qkv_only = out->kind == VIT_OUT_ATTENTION;
     const int bf16 = e->opt.dtype == VIT_DTYPE_BF16;
-    const size_t B = (size_t)e->opt.max_batch, T = (size_t)c->T, D = (size_t)c->D, H = (size_t)c->H;
+    const size_t B = (size_t)e->opt.max_batch, T = (size_t)c->T, D = (size_t)c->D, H1 = (size_t)c->H1;
     const size_t esz = bf16 ? sizeof(unsigned short) : sizeof(float);
     /* Where the LayerNorm fold keeps its row statistics.  fp32 engines: ln_rows32 = the pairs of max_batch * T token rows, then
      * of max_batch class rows; ln_part32 = the partial sums, [D / 64][rows][2] per lane.  bf16 engines: the idle halves of the y
@@ -1265,7 +1280,7 @@ static void chunk_setup(vit_engine *e, vithip_stream_t s, int nb, const vit_outp
         ln->s = j == 0 ? s : e->aux_stream[j - 1];
         const size_t row0 = (size_t)ln->off * T;
         ln->x = e->x + row0 * D;
-        ln->y = at(e->y, row0 * D, esz); ln->qkv = at(e->qkv, row0 * 3 * D, esz); ln->h = at(e->hbuf, row0 * H, esz);
+        ln->y = at(e->y, row0 * D, esz); ln->qkv = at(e->qkv, row0 * 3 * D, esz); ln->h = at(e->hbuf, row0 * H1, esz);
         if (e->fold) {
             ln->xa = bf16 ? (void *)(x16 + row0 * D) : (void *)ln->x;
             ln->tok_pairs = pairs + row0 * 2;
@@ -1542,8 +1557,10 @@ static int forward_device_in(vit_engine *e, const void *d_images, const vit_inpu
             return rc;
         }
         if (e->opt.profile) e->pending_images += nb;
-        /* read the brackets back lazily (it needs an event sync): only when the pool runs low */
-        if (e->opt.profile && e->ev_used > MAX_EVENTS - 256 && (rc = collect_profile(e))) return rc;
+        /* read the brackets back lazily (it needs an event sync): only when the pool runs low, that is when the next chunk (at
+         * most 12 brackets per layer and lane, 16 around them) might not fit: a depth-40 model takes more than 256 per lane */
+        const int chunk_brackets = e->opt.lanes * (12 * e->cfg.depth + 16);
+        if (e->opt.profile && e->ev_used > MAX_EVENTS - (chunk_brackets > 256 ? chunk_brackets : 256) && (rc = collect_profile(e))) return rc;
     }
     if (graphable) { /* nothing ran yet: the launches above were recorded; instantiate and run them */
         HIP_TRY(e, vithip_graph_end(s, &e->graph));

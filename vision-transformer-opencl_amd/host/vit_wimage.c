@@ -16,20 +16,27 @@
 #include <sys/stat.h>
 
 #define VITW_MAGIC 0x57544956u /* "VITW" little endian */
-#define VITW_VERSION 2u
+/* Version 2 = a VIT_MLP_GELU model (the only kind there was when those files were written: they stay loadable, and are still written
+ * bit for bit); version 3 = the same header for a VIT_MLP_SWIGLU model, whose eighth configuration word carries the kind in its top
+ * bits (VIT_MLP_KIND): a reader from before the kind existed takes version 2 only and so refuses the file instead of reading that
+ * word as a width. */
+#define VITW_VERSION_GELU 2u
+#define VITW_VERSION_SWIGLU 3u
+static int mlp_ok(const vit_config *cfg) { return VIT_MLP_KIND(cfg) == VIT_MLP_GELU || VIT_MLP_KIND(cfg) == VIT_MLP_SWIGLU; }
+static uint32_t vitw_version(const vit_config *cfg) { return VIT_MLP_KIND(cfg) == VIT_MLP_SWIGLU ? VITW_VERSION_SWIGLU : VITW_VERSION_GELU; }
 #define SLOT 128u              /* floats: 512-B fp32 slots = 256-B bf16 slots */
 #define PAYLOAD_ALIGN 4096u
 
 /* ---- layout -------------------------------------------------------------------------------- */
 
 static size_t expect_size(const vit_config *cfg, int idx) {
-    const size_t D = (size_t)cfg->embed_dim, H = (size_t)cfg->hidden_dim;
+    const size_t D = (size_t)cfg->embed_dim, H = (size_t)VIT_HIDDEN_DIM(cfg), H1 = (size_t)VIT_FC1_ROWS(cfg);
     const size_t G = (size_t)(cfg->img_size / cfg->patch_size), T = G * G + 1;
     const size_t PK = (size_t)cfg->in_chans * cfg->patch_size * cfg->patch_size;
     const int base = 4 + VIT_WEIGHTS_PER_LAYER * cfg->depth;
     if (idx < 4) { const size_t s[4] = {D, D * PK, D, T * D}; return s[idx]; }
     if (idx >= base) { const size_t s[4] = {D, D, (size_t)cfg->num_classes * D, (size_t)cfg->num_classes}; return s[idx - base]; }
-    { const size_t s[12] = {D, D, 3 * D * D, 3 * D, D * D, D, D, D, H * D, H, D * H, D}; return s[(idx - 4) % VIT_WEIGHTS_PER_LAYER]; }
+    { const size_t s[12] = {D, D, 3 * D * D, 3 * D, D * D, D, D, D, H1 * D, H1, D * H, D}; return s[(idx - 4) % VIT_WEIGHTS_PER_LAYER]; }
 }
 
 static int is_gemm_operand(const vit_config *cfg, int idx) {
@@ -94,7 +101,7 @@ void vit_weight_image_free(vit_weight_image *img) {
 }
 
 int vit_weight_image_build(vit_weight_image *img, const vit_config *cfg, const Network network[], int count, int with_bf16) {
-    if (!img || !cfg || !network || count != VIT_WEIGHT_COUNT(cfg->depth)) return -1;
+    if (!img || !cfg || !network || !mlp_ok(cfg) || count != VIT_WEIGHT_COUNT(cfg->depth)) return -1;
     for (int i = 0; i < count; ++i)
         if (!network[i].data || network[i].size != expect_size(cfg, i)) return -1;
     if (image_alloc(img, cfg, with_bf16)) return -1;
@@ -182,13 +189,13 @@ typedef struct {
 } vitw_header;
 
 int vit_weight_image_save(const vit_weight_image *img, const char *path, const char *source_dir) {
-    if (!img || !img->f32 || !path) return -1;
+    if (!img || !img->f32 || !path || !mlp_ok(&img->cfg)) return -1;
     vitw_source *src = NULL;
     int ns = 0;
     if (source_dir && (ns = scan_sources(source_dir, img->count, &src)) < 0) return -1;
     vitw_header h;
     memset(&h, 0, sizeof(h));
-    h.magic = VITW_MAGIC; h.version = VITW_VERSION; h.count = (uint32_t)img->count; h.n_sources = (uint32_t)ns;
+    h.magic = VITW_MAGIC; h.version = vitw_version(&img->cfg); h.count = (uint32_t)img->count; h.n_sources = (uint32_t)ns;
     memcpy(h.cfg, &img->cfg, sizeof(h.cfg));
     h.f32_floats = img->f32_floats; h.gemm_floats = img->gemm_floats; h.bf16_elems = img->bf16_elems;
     const size_t meta = sizeof(h) + (size_t)ns * sizeof(vitw_source);
@@ -212,11 +219,12 @@ int vit_weight_image_save(const vit_weight_image *img, const char *path, const c
 int vit_weight_image_load(vit_weight_image *img, const char *path, const vit_config *cfg, const char *source_dir) {
     if (!img || !path || !cfg) return -1;
     memset(img, 0, sizeof(*img));
+    if (!mlp_ok(cfg)) return -1;
     FILE *fp = fopen(path, "rb");
     if (!fp) return -1;
     vitw_header h;
     vitw_source *stored = NULL, *now = NULL;
-    int ok = fread(&h, sizeof(h), 1, fp) == 1 && h.magic == VITW_MAGIC && h.version == VITW_VERSION &&
+    int ok = fread(&h, sizeof(h), 1, fp) == 1 && h.magic == VITW_MAGIC && h.version == vitw_version(cfg) &&
              h.count == (uint32_t)VIT_WEIGHT_COUNT(cfg->depth) && memcmp(h.cfg, cfg, sizeof(h.cfg)) == 0 &&
              h.n_sources <= 65536;
     if (ok && h.n_sources) {

@@ -54,9 +54,14 @@ def round6(w: np.ndarray) -> np.ndarray:
     return (r / np.float32(1000000.0)).astype(np.float32)
 
 
+MLP_KINDS = {"gelu": 0, "swiglu": 1}  # VIT_MLP_GELU, VIT_MLP_SWIGLU
+MLP_SHIFT = 24  # VIT_MLP_SHIFT: vit_config.hidden_dim carries the kind in bits 24..30 (binding.CConfig.of packs it)
+
+
 @dataclass(frozen=True)
 class ModelConfig:
-    """Runtime form of ViT_seq.c:10-21."""
+    """Runtime form of ViT_seq.c:10-21.  mlp: "gelu" (fc1 -> erf-GELU -> fc2) or "swiglu" (fc1 is the fused w12 with 2 * hidden_dim
+    rows, gate rows first; the hidden layer is silu(gate) * value: DINOv2 ViT-g/14, EVA-02)."""
     img_size: int = 224
     patch_size: int = 16
     in_chans: int = 3
@@ -65,6 +70,16 @@ class ModelConfig:
     depth: int = 12
     num_heads: int = 12
     hidden_dim: int = 3072
+    mlp: str = "gelu"
+
+    def __post_init__(self):
+        if self.mlp not in MLP_KINDS and not isinstance(self.mlp, int):  # an int goes into vit_config as it is (the engine checks it)
+            raise ValueError(f"mlp = {self.mlp!r}: one of {sorted(MLP_KINDS)}")
+
+    @property
+    def fc1_rows(self) -> int:
+        """Output rows of the fc1 weight: hidden_dim, or 2 * hidden_dim for the fused gate | value projection of SwiGLU."""
+        return 2 * self.hidden_dim if MLP_KINDS.get(self.mlp, self.mlp) == MLP_KINDS["swiglu"] else self.hidden_dim
 
     @property
     def tokens(self) -> int:
@@ -86,23 +101,25 @@ class ModelConfig:
     @property
     def macs_per_image(self) -> int:
         """Algorithmic MACs: conv + depth*(QKV + QK^T + PV + out + fc1 + fc2) + head."""
-        T, D, H = self.tokens, self.embed_dim, self.hidden_dim
+        T, D, H, H1 = self.tokens, self.embed_dim, self.hidden_dim, self.fc1_rows
         hd = D // self.num_heads
-        per_layer = T * D * 3 * D + 2 * self.num_heads * T * T * hd + T * D * D + 2 * T * D * H
+        per_layer = T * D * 3 * D + 2 * self.num_heads * T * T * hd + T * D * D + T * D * H1 + T * H * D
         return self.patches * self.patch_dim * D + self.depth * per_layer + D * self.num_classes
 
     def weight_shapes(self):
-        D, H, T = self.embed_dim, self.hidden_dim, self.tokens
+        D, H, H1, T = self.embed_dim, self.hidden_dim, self.fc1_rows, self.tokens
         shapes = [(D,), (D, self.patch_dim), (D,), (T, D)]
         for _ in range(self.depth):
             shapes += [(D,), (D,), (3 * D, D), (3 * D,), (D, D), (D,), (D,), (D,),
-                       (H, D), (H,), (D, H), (D,)]
+                       (H1, D), (H1,), (D, H), (D,)]
         shapes += [(D,), (D,), (self.num_classes, D), (self.num_classes,)]
         return shapes
 
 
 VIT_B16 = ModelConfig()
 VIT_L16_384 = ModelConfig(img_size=384, embed_dim=1024, depth=24, num_heads=16, hidden_dim=4096)
+# DINOv2 ViT-g/14: patch 14, the fused SwiGLU MLP (w12 [8192][1536], w3 [1536][4096])
+VIT_G14 = ModelConfig(img_size=224, patch_size=14, embed_dim=1536, depth=40, num_heads=24, hidden_dim=4096, mlp="swiglu")
 # reduced models for fast live-oracle parity (head_dim stays 64 as in ViT-B/L)
 VIT_TINY = ModelConfig(img_size=32, num_classes=10, embed_dim=128, depth=2, num_heads=2, hidden_dim=256)
 VIT_SMALL = ModelConfig(img_size=64, num_classes=100, embed_dim=192, depth=3, num_heads=3, hidden_dim=768)
