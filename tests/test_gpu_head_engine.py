@@ -257,6 +257,37 @@ def test_prune_last_layer_changes_no_bit(oracle, engines, family, dtype):
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
+@pytest.mark.parametrize("prune", [False, True])
+@pytest.mark.parametrize("name,n,lanes", [("tiny14", 3, 1), ("deep14_70", 8, 2)])  # lanes split only when n >= 2 * lanes
+def test_the_checkpoints_head_set_as_a_callers_head_gives_the_own_heads_bits(engines, name, n, lanes, prune, dtype):
+    """The own head is the instance {cls_layers = (depth - 1,), pool none} over the checkpoint's head tensors: set by the caller it
+    issues the own head's launches, so every output of the head has the own head's bits, and the operand is D wide in both states."""
+    cfg, W = MODELS[name], weights(name)
+    eng = engines(name, dtype, max_batch=8 if lanes > 1 else 4, **({"prune_last_layer": True} if prune else {}))
+    eng.set_lanes(lanes)
+    d_img = B.DeviceArray.from_numpy(synth.make_images(cfg, n, 200 + n))
+    k = 3
+
+    def outputs():  # probabilities, top-1 labels, top-1 probabilities, logits, operand rows, top-k records
+        out = list(device_forward(eng, d_img, n)) + [eng.logits(n), eng.head_operand(n)]
+        d_rec = B.DeviceArray((n, 2 * k), np.int32)
+        eng.topk_device(d_img.ptr, n, d_rec.ptr, k)
+        eng.sync()
+        return out + [d_rec.numpy()]
+
+    own = outputs()
+    assert np.isfinite(own[0]).all() and (own[1] == own[0].argmax(1)).all() and own[4].shape == (n, cfg.embed_dim)
+    eng.set_head(W[-2], W[-1], (cfg.depth - 1,), "none")
+    assert eng.head_in_features((cfg.depth - 1,), "none") == cfg.embed_dim
+    for state in ("set_head", "reset_head"):
+        got = outputs()
+        assert got[4].shape == (n, cfg.embed_dim), state
+        for what, a, b in zip(("probs", "labels", "top-1 probs", "logits", "operand", "top-k records"), got, own):
+            assert same_bits(a, b), (state, what)
+        eng.reset_head()
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
 def test_a_captured_graph_does_not_outlive_the_head_it_was_captured_with(oracle, engines, dtype):
     name = "deep14"
     plain, graph = engines(name, dtype, max_batch=4), engines(name, dtype, max_batch=4, use_graph=True)

@@ -8,7 +8,9 @@
  *   depth x { LN1 -> QKV GEMM -> fused attention -> out_proj GEMM (+bias +residual, in place)
  *             LN2 -> fc1 GEMM (+bias +GELU) -> fc2 GEMM (+bias +residual, in place) }
  *   LN on the class-token rows only -> head GEMM -> softmax + top-1
- *   (a features call ends instead in the final LN of the rows it returns, or in the fused LN + mean over the patch tokens;
+ *   (one head, vit_head: the checkpoint's own is the instance {class block of the last layer} over z; every kind of final block --
+ *    class, pooled, tap -- has one writer, whoever asks for it;
+ *    a features call ends instead in the final LN of the rows it returns, or in the fused LN + mean over the patch tokens;
  *    an attention call stops the last layer behind its QKV GEMM and stores the class token's softmax row;
  *    an intermediate call copies rows of x out behind the layers it taps and stops behind the deepest of them)
  *
@@ -83,6 +85,10 @@ typedef struct { const void *W; const float *bias, *colsum; const void *w_split;
 typedef struct { const float *ln1_g, *ln1_b, *ln2_g, *ln2_b; vit_gemm_ops qkv, out, fc1, fc2; } vit_layer_ops;
 typedef struct { const float *cls, *conv_w, *conv_b, *pos; const unsigned short *conv_w16; /* bf16 engines */ } vit_embed_ops;
 typedef struct { const float *ln_g, *ln_b; vit_gemm_ops head; } vit_final_ops;
+/* The classifier head in force: the checked spec (cls_layers behind num_cls_layers zero), the operand's width `in` =
+ * (num_cls_layers + (pool != NONE)) * D, the head GEMM's W [num_classes][in] and bias, the operand rows [max_batch][in].  owned: the
+ * three are allocations of the head's own (W with a zeroed tail pad behind it, as wblob has), which go with it. */
+typedef struct { vit_head_spec spec; size_t in; vit_gemm_ops ops; float *operand; int owned; } vit_head;
 
 struct vit_engine {
     vit_config cfg;
@@ -124,12 +130,8 @@ struct vit_engine {
 
     /* workspace for max_batch images */
     float *x, *y, *qkv, *hbuf, *z, *logits;
-    /* a caller's classifier head (vit_engine_set_head); head_w == NULL: the checkpoint's own (final.head, reading z).  The checked
-     * spec, the operand's width (num_cls_layers + (pool != NONE)) * D, and three allocations of the head's own: the weight
-     * [num_classes][head_in] with a zeroed tail pad behind it (as wblob has), the bias, and the operand rows [max_batch][head_in] */
-    vit_head_spec head;
-    size_t head_in;
-    float *head_w, *head_b, *head_operand;
+    /* the one classifier head: the checkpoint's own (restore_own_head) or a caller's (vit_engine_set_head); no stage tells them apart */
+    vit_head head;
     /* host-pointer path: double-buffered staging so that gather + H2D of piece i+1 overlap compute of piece i */
     float *in_stage[2], *out_stage[2];   /* device */
     float *pin_in[2], *pin_out[2];       /* pinned host */
@@ -410,6 +412,12 @@ int vit_engine_create(vit_engine **out, const vit_config *cfg, const vit_engine_
     return VIT_OK;
 }
 
+/* a caller's head owns its weight, bias and operand rows; the checkpoint's own points into wblob and z */
+static void release_head(vit_head *h) {
+    if (!h->owned) return;
+    vithip_free((void *)h->ops.W); vithip_free((void *)h->ops.bias); vithip_free(h->operand);
+}
+
 void vit_engine_destroy(vit_engine *e) {
     if (!e) return;
     vithip_set_device(e->opt.device);
@@ -419,7 +427,7 @@ void vit_engine_destroy(vit_engine *e) {
     if (e->graph) vithip_graph_destroy(e->graph);
     vithip_free(e->x); vithip_free(e->y); vithip_free(e->qkv); vithip_free(e->hbuf);
     vithip_free(e->z); vithip_free(e->logits);
-    vithip_free(e->head_w); vithip_free(e->head_b); vithip_free(e->head_operand);
+    release_head(&e->head);
     for (int j = 0; j < VIT_MAX_LANES; ++j) vithip_gemm_f32_workspace_destroy(e->gemm_ws[j]);
     if (e->copy_stream) { vithip_stream_sync(e->copy_stream); vithip_stream_destroy(e->copy_stream); }
     if (e->ev_in_stage) vithip_event_destroy(e->ev_in_stage);
@@ -557,21 +565,21 @@ static int resolve_operands(vit_engine *e) {
     return VIT_OK;
 }
 
-/* Back to the checkpoint's own head: a caller's head (vit_engine_set_head) and its allocations go.  Nothing may be in flight. */
+/* Back to the checkpoint's own head: a caller's head (vit_engine_set_head) and its allocations go.  Nothing may be in flight.  The
+ * own head is an instance like any other: the class block of the last layer alone, final.head (as installed: wblob may move) over z. */
 static void restore_own_head(vit_engine *e) {
-    if (!e->head_w) return;
-    vithip_free(e->head_w); vithip_free(e->head_b); vithip_free(e->head_operand);
-    e->head_w = e->head_b = e->head_operand = NULL;
-    memset(&e->head, 0, sizeof(e->head));
-    e->head_in = 0;
-    e->last_rows = 0;
+    if (e->head.owned) e->last_rows = 0;
+    release_head(&e->head);
+    e->head = (vit_head){.spec = {.num_cls_layers = 1, .cls_layers = {e->cfg.depth - 1}, .pool = VIT_HEAD_POOL_NONE},
+                         .in = (size_t)e->cfg.embed_dim, .ops = e->final.head, .operand = e->z, .owned = 0};
 }
 
 /* The tail of every install, behind the last write to wblob: the fold, the split images and the operand table, then the sync.
- * Every install also puts the checkpoint's own head back in force (alloc_weight_blob has synchronised and dropped the graph). */
+ * Every install also puts the checkpoint's own head back in force (alloc_weight_blob has synchronised and dropped the graph),
+ * whatever became of the derived operands' launches: final.head is set before the first of them. */
 static int finish_install(vit_engine *e) {
-    restore_own_head(e);
     const int rc = resolve_operands(e);
+    restore_own_head(e);
     if (rc) return rc;
     HIP_TRY(e, vithip_stream_sync(e->stream));
     e->weights_loaded = 1;
@@ -889,7 +897,8 @@ typedef struct {
     int L;                       /* lanes in use for this chunk */
     int T, D, H, NC;
     int H1;                      /* columns of a row of the lanes' h: VIT_FC1_ROWS (H; 2H under SwiGLU, [gate -> hidden | value]) */
-    int pruned;                  /* the last layer computes the class rows only: prune_last_layer, unless the chunk's output needs every token */
+    size_t esz;                  /* bytes of an element of the lanes' y, qkv and h: 4, or 2 on bf16 engines */
+    int pruned;                  /* the last layer computes the class rows only: prune_last_layer, where the chunk's output reads no others (class_rows_only) */
     int qkv_only;                /* the last layer stops behind its QKV GEMM: the chunk's output is read from its Q and K (attention calls) */
 } chunk_ctx;
 
@@ -969,7 +978,7 @@ static int row_stats(chunk_ctx *c, const vit_lane *ln, size_t ldx, float *pairs,
  *   fold    the LayerNorm fold (vit_hip_kernels.h, "LayerNorm folding"): in_proj and fc1 read the raw rows (x, or its bf16 copy)
  *           with the gamma/beta-folded operands (vit_layer_ops) and a pair per row; a LayerNorm becomes a statistics pass,
  *           or nothing where the residual GEMM in front has left the pairs.  The bf16 Q rows carry the scores' exponent factor.
- *   pruned  prune_last_layer, for chunks whose output reads the class rows only (chunk_ctx.pruned: probabilities, CLS features and CLS taps;
+ *   pruned  prune_last_layer, for chunks whose output reads the class rows only (class_rows_only: probabilities, CLS features and CLS taps;
  *           MEAN and TOKENS run the layer in full): K and V of every token, everything else for the class rows only.  The class rows of a [n*T][w]
  *           buffer are rows 0, T, 2T, ... = a matrix with leading dimension T*w, which every operator takes as it is.
  *   qkv_only  attention calls: the last layer ends behind in_proj, with K of every token and Q of (at least) the class rows in the
@@ -980,7 +989,6 @@ static int encoder_layer(chunk_ctx *c, int l) {
     const int T = c->T, D = c->D, H = c->H, H1 = c->H1, heads = e->cfg.num_heads, swiglu = VIT_MLP_KIND(&e->cfg) == VIT_MLP_SWIGLU;
     const int bf16 = e->opt.dtype == VIT_DTYPE_BF16, fold = e->fold, feeds_next = l + 1 < e->cfg.depth;
     const int pruned = c->pruned && !feeds_next;
-    const size_t esz = bf16 ? sizeof(unsigned short) : sizeof(float); /* GEMM weights and activations */
     const vit_layer_ops *o = &e->layer[l];
     /* the rows the layer computes past K and V: every token row, or the class rows (row step T); and their pairs (fold) */
     const int r = pruned ? T : 1;
@@ -1002,7 +1010,7 @@ static int encoder_layer(chunk_ctx *c, int l) {
                        .ldc = 3 * D, .M = ln->n * T, .N = 3 * D, .K = D, .role = VITHIP_EPI_BIAS, .ln_rows = ln->tok_pairs};
         if (pruned) { /* K and V of every token (in_proj rows D..3D), then Q of the class rows, whose pairs are gathered first */
             gemm_desc kv = g;
-            kv.ops.W = at(g.ops.W, (size_t)D * D, esz); kv.ops.bias = g.ops.bias + D; kv.C = at(ln->qkv, D, esz); kv.N = 2 * D;
+            kv.ops.W = at(g.ops.W, (size_t)D * D, c->esz); kv.ops.bias = g.ops.bias + D; kv.C = at(ln->qkv, D, c->esz); kv.N = 2 * D;
             kv.ops.colsum = g.ops.colsum ? g.ops.colsum + D : NULL;
             /* the image of rows D.. starts at a panel boundary only when D is a multiple of 128 (panel = 128 rows x K x 6 bytes) */
             kv.ops.w_split = g.ops.w_split && D % 128 == 0 ? at(g.ops.w_split, (size_t)D * D * 6, 1) : NULL;
@@ -1064,29 +1072,66 @@ static int encoder_layer(chunk_ctx *c, int l) {
     return VIT_OK;
 }
 
-static int head_last_blocks(chunk_ctx *c, const vit_lane *ln); /* behind stage_features, whose pooling scratch it shares */
+/* The final blocks: what a chunk returns from the residual stream (the head's operand, embedding rows, tapped layers) is made of
+ * three kinds of block with one writer each.  A writer serves one lane inside the bracket its caller has opened and writes the block
+ * of each of the lane's images at dst, dst + ld, ..: ld is an image's whole row, the caller's or the head's operand's.
+ * class_block: the final LayerNorm of the class rows (ViT_seq.c:429-433 normalises all rows, uses row 0): row step T*D, exactly the
+ * rows a pruned last layer has updated.  Not vithip_tap_f32 with VITHIP_TAP_CLS: the same bits, but another launch. */
+static int class_block(chunk_ctx *c, const vit_lane *ln, float *dst, size_t ld) {
+    HIP_TRY(c->e, vithip_layernorm_f32(ln->s, ln->x, (size_t)c->T * c->D, dst, ld, c->e->final.ln_g, c->e->final.ln_b, ln->n, c->D));
+    return VIT_OK;
+}
 
-/* final LayerNorm on the class-token rows only (ViT_seq.c:429-433 normalises all rows, uses row 0), classifier head
- * (ViT_seq.c:435), Softmax (ViT_seq.c:437) + top-1 (Main.c:62-70) -- or, for a top-k call, the k best classes of the same logits as
- * records in the softmax's place: d_probs is then [n][2k] 32-bit words and nothing of [n][classes] is written */
-static int stage_head(chunk_ctx *c, float *d_probs, int *d_label, float *d_prob, const vit_topk_spec *topk) {
+/* The pooling scratch is the head of the lane's OWN rows of y (ln->y: n * T * D elements of 4 or, bf16 engines, 2 bytes), which the
+ * lane's own stream has finished with behind its last layer.  Nothing of another lane may be touched: lanes run on independent
+ * streams and the others may still be in their last layer, reading their y and (fold) the bf16 copy of x in y's upper half.  The
+ * scratch is one [D] fp32 row per 16 tokens, at most n * T * D * 2 bytes for every T >= 2; checked by pooled_block all the same. */
+static float *pool_scratch(const chunk_ctx *c, const vit_lane *ln, size_t *bytes) {
+    *bytes = vithip_layernorm_pool_f32_workspace_floats(ln->n, c->T, 1, c->D) * sizeof(float);
+    return (float *)ln->y;
+}
+
+/* pooled_block: the mean over the patch tokens: normalise, then pool (l2: and L2-normalise the mean) or, fcnorm, pool, then
+ * normalise; both kernels keep the same partial rows in the scratch.  who: the caller, for the message. */
+static int pooled_block(chunk_ctx *c, const vit_lane *ln, float *dst, size_t ld, int fcnorm, int l2, const char *who) {
     vit_engine *e = c->e;
-    const int T = c->T, D = c->D, NC = c->NC;
-    /* the head GEMM's operand: the checkpoint's own head reads z [n][D]; a caller's head its operand rows [n][head_in], whose
-     * class blocks of earlier layers are in place (stage_head_tap) and whose last-layer blocks are written here */
-    const int F = e->head_w ? (int)e->head_in : D;
-    float *const operand = e->head_w ? e->head_operand : e->z;
-    const vit_gemm_ops head = e->head_w ? (vit_gemm_ops){.W = e->head_w, .bias = e->head_b} : e->final.head;
+    const size_t D = (size_t)c->D, own = (size_t)ln->n * c->T * D * c->esz;
+    size_t need;
+    float *scratch = pool_scratch(c, ln, &need);
+    if (need == 0 || need > own || ((size_t)scratch & 15))
+        return fail(e, VIT_ERR_STATE, "%s: the pooling scratch (%zu bytes) does not fit the lane's own %zu bytes of y", who, need, own);
+    if (fcnorm) HIP_TRY(e, vithip_pool_layernorm_f32(ln->s, ln->x, D, dst, ld, e->final.ln_g, e->final.ln_b, ln->n, c->T, 1, c->D, scratch));
+    else HIP_TRY(e, vithip_layernorm_pool_f32(ln->s, ln->x, D, dst, ld, e->final.ln_g, e->final.ln_b, ln->n, c->T, 1, c->D, l2, scratch));
+    return VIT_OK;
+}
+
+/* tap_block: the rows `kind` (VITHIP_TAP_*) names of x as the layer in front has just left it; norm: through the final LayerNorm */
+static int tap_block(chunk_ctx *c, const vit_lane *ln, float *dst, size_t ld, int norm, int kind) {
+    const vit_final_ops *f = &c->e->final;
+    HIP_TRY(c->e, vithip_tap_f32(ln->s, ln->x, (size_t)c->D, dst, ld, norm ? f->ln_g : NULL, norm ? f->ln_b : NULL, ln->n, c->T, c->D, kind));
+    return VIT_OK;
+}
+
+/* The head (vit_head): the blocks of the last layer into the operand rows -- the class blocks of earlier layers are in place
+ * (stage_head_tap) --, classifier head (ViT_seq.c:435), Softmax (ViT_seq.c:437) + top-1 (Main.c:62-70) -- or, for a top-k call, the k
+ * best classes of the same logits as records in the softmax's place: out->dst is then [n][2k] 32-bit words and nothing of
+ * [n][classes] is written.  The checkpoint's own head is the case K = 1, in = D: one class block per lane into z, ld = D. */
+static int stage_head(chunk_ctx *c, const vit_output *out) {
+    vit_engine *e = c->e;
+    const vit_head *h = &e->head;
+    const int NC = c->NC, K = h->spec.num_cls_layers, F = (int)h->in;
     for (int j = 0; j < c->L; ++j) {
         const vit_lane *ln = &c->lane[j];
+        float *row = h->operand + (size_t)ln->off * h->in;
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
-        if (!e->head_w) HIP_TRY(e, vithip_layernorm_f32(ln->s, ln->x, (size_t)T * D, e->z + (size_t)ln->off * D, (size_t)D, e->final.ln_g, e->final.ln_b, ln->n, D));
-        else RUN(head_last_blocks(c, ln));
+        if (K && h->spec.cls_layers[K - 1] == e->cfg.depth - 1) RUN(class_block(c, ln, row + (size_t)(K - 1) * c->D, h->in));
+        if (h->spec.pool != VIT_HEAD_POOL_NONE)
+            RUN(pooled_block(c, ln, row + (size_t)K * c->D, h->in, h->spec.pool == VIT_HEAD_POOL_AVG_FCNORM, 0, "head"));
         HIP_TRY(e, stage_end(e, ln->s));
     }
     for (int j = 0; j < c->L; ++j) {
         const vit_lane *ln = &c->lane[j];
-        const gemm_desc g = {.stage = VIT_STAGE_HEAD, .A = operand + (size_t)ln->off * F, .lda = F, .ops = head,
+        const gemm_desc g = {.stage = VIT_STAGE_HEAD, .A = h->operand + (size_t)ln->off * F, .lda = F, .ops = h->ops,
                              .C = e->logits + (size_t)ln->off * NC, .ldc = NC, .M = ln->n, .N = NC, .K = F, .role = VITHIP_EPI_BIAS};
         RUN(gemm(e, ln->s, &g, NULL));
     }
@@ -1094,11 +1139,11 @@ static int stage_head(chunk_ctx *c, float *d_probs, int *d_label, float *d_prob,
         const vit_lane *ln = &c->lane[j];
         const size_t o = (size_t)ln->off;
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_SOFTMAX));
-        if (topk)
-            HIP_TRY(e, vithip_softmax_topk_f32(ln->s, e->logits + o * NC, NC, (int *)d_probs + o * 2 * (size_t)topk->k, 2 * topk->k, ln->n, NC, topk->k,
-                                               topk->score));
+        if (out->kind == VIT_OUT_TOPK)
+            HIP_TRY(e, vithip_softmax_topk_f32(ln->s, e->logits + o * NC, NC, (int *)out->dst + o * 2 * (size_t)out->topk.k, 2 * out->topk.k, ln->n, NC,
+                                               out->topk.k, out->topk.score));
         else
-            HIP_TRY(e, vithip_softmax_top1_f32(ln->s, e->logits + o * NC, NC, d_probs + o * NC, NC, d_label ? d_label + o : NULL, d_prob ? d_prob + o : NULL, ln->n, NC));
+            HIP_TRY(e, vithip_softmax_top1_f32(ln->s, e->logits + o * NC, NC, out->dst + o * NC, NC, out->label ? out->label + o : NULL, out->prob ? out->prob + o : NULL, ln->n, NC));
         HIP_TRY(e, stage_end(e, ln->s));
     }
     return VIT_OK;
@@ -1122,39 +1167,21 @@ static size_t out_row_elems(const vit_engine *e, const vit_output *out) {
     return row_elems(e, out->kind, out->kind == VIT_OUT_ATTENTION ? out->attn_kind : out->kind == VIT_OUT_TOPK ? out->topk.k : out->spec.kind);
 }
 
-/* The embedding rows of the chunk instead of the head: the final LayerNorm of the class rows (exactly the launch stage_head makes,
- * pointed at the caller's rows), of every row, or fused with the mean over the patch tokens (vithip_layernorm_pool_f32).
- * The pooling scratch is the head of the lane's OWN rows of y (ln->y: n * T * D elements of 4 or, bf16 engines, 2 bytes), which the
- * lane's own stream has finished with behind its last layer.  Nothing of another lane may be touched: lanes run on independent
- * streams and the others may still be in their last layer, reading their y and (fold) the bf16 copy of x in y's upper half.  The
- * scratch is one [D] fp32 row per 16 tokens, at most n * T * D * 2 bytes for every T >= 2; checked below all the same. */
-static float *pool_scratch(const chunk_ctx *c, const vit_lane *ln, size_t *bytes) {
-    *bytes = vithip_layernorm_pool_f32_workspace_floats(ln->n, c->T, 1, c->D) * sizeof(float);
-    return (float *)ln->y;
-}
-
+/* The embedding rows of the chunk instead of the head: the class block (the checkpoint's own head's operand, in the caller's rows),
+ * the final LayerNorm of every row, or the pooled block. */
 static int stage_features(chunk_ctx *c, const vit_output *out) {
     vit_engine *e = c->e;
-    const size_t T = (size_t)c->T, D = (size_t)c->D;
+    const size_t D = (size_t)c->D;
     for (int j = 0; j < c->L; ++j) {
         const vit_lane *ln = &c->lane[j];
         float *dst = out->dst + (size_t)ln->off * out_row_elems(e, out);
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
-        if (out->spec.kind == VIT_FEAT_CLS)
-            HIP_TRY(e, vithip_layernorm_f32(ln->s, ln->x, T * D, dst, D, e->final.ln_g, e->final.ln_b, ln->n, c->D));
-        else if (out->spec.kind == VIT_FEAT_TOKENS)
+        if (out->spec.kind == VIT_FEAT_CLS) {
+            RUN(class_block(c, ln, dst, D));
+            if (out->spec.l2_normalize) HIP_TRY(e, vithip_l2_normalize_rows_f32(ln->s, dst, D, ln->n, c->D));
+        } else if (out->spec.kind == VIT_FEAT_TOKENS)
             HIP_TRY(e, vithip_layernorm_f32(ln->s, ln->x, D, dst, D, e->final.ln_g, e->final.ln_b, ln->n * c->T, c->D));
-        else {
-            const size_t esz = e->opt.dtype == VIT_DTYPE_BF16 ? sizeof(unsigned short) : sizeof(float);
-            size_t need;
-            float *scratch = pool_scratch(c, ln, &need);
-            if (need == 0 || need > (size_t)ln->n * T * D * esz || ((size_t)scratch & 15))
-                return fail(e, VIT_ERR_STATE, "features: the pooling scratch (%zu bytes) does not fit the lane's own %zu bytes of y", need,
-                            (size_t)ln->n * T * D * esz);
-            HIP_TRY(e, vithip_layernorm_pool_f32(ln->s, ln->x, D, dst, D, e->final.ln_g, e->final.ln_b, ln->n, c->T, 1, c->D, out->spec.l2_normalize,
-                                                 scratch));
-        }
-        if (out->spec.kind == VIT_FEAT_CLS && out->spec.l2_normalize) HIP_TRY(e, vithip_l2_normalize_rows_f32(ln->s, dst, D, ln->n, c->D));
+        else RUN(pooled_block(c, ln, dst, D, 0, out->spec.l2_normalize, "features"));
         HIP_TRY(e, stage_end(e, ln->s));
     }
     return VIT_OK;
@@ -1181,67 +1208,45 @@ static int stage_cls_attention(chunk_ctx *c, const vit_output *out) {
     return VIT_OK;
 }
 
-/* Block j of an intermediate call's rows: the residual stream as encoder_layer(layers[j]) has just left it, one vithip_tap_f32 launch
- * per lane, from the lane's rows of x into block j of its images' rows -- an image's row is the call's blocks side by side, so the
- * image stride of every launch is the whole row.  norm: through the final LayerNorm's gamma and beta.  A pruned last layer (CLS only)
- * has updated the class rows of x alone, which is all that CLS reads. */
+/* Block j of an intermediate call's rows: the residual stream as encoder_layer(layers[j]) has just left it, one tap block per lane.
+ * A pruned last layer (CLS only) has updated the class rows of x alone, which is all that CLS reads. */
 static int stage_tap(chunk_ctx *c, const vit_output *out, int j) {
     vit_engine *e = c->e;
     const size_t row = out_row_elems(e, out), block = tap_block_elems(e, out->tap.kind);
     for (int k = 0; k < c->L; ++k) {
         const vit_lane *ln = &c->lane[k];
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
-        HIP_TRY(e, vithip_tap_f32(ln->s, ln->x, (size_t)c->D, out->dst + (size_t)ln->off * row + (size_t)j * block, row,
-                                  out->tap.norm ? e->final.ln_g : NULL, out->tap.norm ? e->final.ln_b : NULL, ln->n, c->T, c->D, out->tap.kind));
+        RUN(tap_block(c, ln, out->dst + (size_t)ln->off * row + (size_t)j * block, row, out->tap.norm, out->tap.kind));
         HIP_TRY(e, stage_end(e, ln->s));
     }
     return VIT_OK;
 }
 
-/* A caller's head (vit_engine_set_head).  The operand row of an image is [class blocks, in the order of cls_layers | pooled block],
- * head_in floats; every launch writes one block of the lane's images with the whole row as its image stride, like stage_tap.
- *
- * stage_head_tap: behind encoder layer l < depth - 1 when cls_layers names it: the class block of that layer, the launch (and so
- * the bits) of an intermediate call with VIT_TAP_CLS, norm = 1. */
+/* The head's operand row of an image is [class blocks, in the order of cls_layers | pooled block], head.in floats.  Behind encoder
+ * layer l < depth - 1 when cls_layers names it: the class block of that layer, the launch (and so the bits) of an intermediate call
+ * with VIT_TAP_CLS, norm = 1.  The blocks of the last layer are stage_head's; the checkpoint's own head names no other layer. */
 static int stage_head_tap(chunk_ctx *c, int l) {
     vit_engine *e = c->e;
-    const vit_head_spec *h = &e->head;
+    const vit_head *h = &e->head;
     int k = 0;
-    while (k < h->num_cls_layers && h->cls_layers[k] != l) ++k;
-    if (k == h->num_cls_layers || l == e->cfg.depth - 1) return VIT_OK;
+    while (k < h->spec.num_cls_layers && h->spec.cls_layers[k] != l) ++k;
+    if (k == h->spec.num_cls_layers || l == e->cfg.depth - 1) return VIT_OK;
     for (int j = 0; j < c->L; ++j) {
         const vit_lane *ln = &c->lane[j];
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
-        HIP_TRY(e, vithip_tap_f32(ln->s, ln->x, (size_t)c->D, e->head_operand + (size_t)ln->off * e->head_in + (size_t)k * c->D, e->head_in,
-                                  e->final.ln_g, e->final.ln_b, ln->n, c->T, c->D, VITHIP_TAP_CLS));
+        RUN(tap_block(c, ln, h->operand + (size_t)ln->off * h->in + (size_t)k * c->D, h->in, 1, VITHIP_TAP_CLS));
         HIP_TRY(e, stage_end(e, ln->s));
     }
     return VIT_OK;
 }
 
-/* ... and the blocks of the last layer, for one lane inside stage_head's LayerNorm bracket: its class block by the launch the
- * checkpoint's own head makes (a pruned last layer has updated exactly those rows), the pooled block by the launch of a MEAN
- * features call without L2 (AVG) or by pool-then-normalise (AVG_FCNORM), their scratch in the lane's own rows of y as there. */
-static int head_last_blocks(chunk_ctx *c, const vit_lane *ln) {
-    vit_engine *e = c->e;
-    const vit_head_spec *h = &e->head;
-    const size_t T = (size_t)c->T, D = (size_t)c->D, F = e->head_in;
-    const int K = h->num_cls_layers;
-    float *row = e->head_operand + (size_t)ln->off * F;
-    if (K && h->cls_layers[K - 1] == e->cfg.depth - 1)
-        HIP_TRY(e, vithip_layernorm_f32(ln->s, ln->x, T * D, row + (size_t)(K - 1) * D, F, e->final.ln_g, e->final.ln_b, ln->n, c->D));
-    if (h->pool == VIT_HEAD_POOL_NONE) return VIT_OK;
-    const size_t esz = e->opt.dtype == VIT_DTYPE_BF16 ? sizeof(unsigned short) : sizeof(float);
-    size_t need;
-    float *scratch = pool_scratch(c, ln, &need); /* both pooling kernels keep the same partial rows */
-    if (need == 0 || need > (size_t)ln->n * T * D * esz || ((size_t)scratch & 15))
-        return fail(e, VIT_ERR_STATE, "head: the pooling scratch (%zu bytes) does not fit the lane's own %zu bytes of y", need,
-                    (size_t)ln->n * T * D * esz);
-    if (h->pool == VIT_HEAD_POOL_AVG)
-        HIP_TRY(e, vithip_layernorm_pool_f32(ln->s, ln->x, D, row + (size_t)K * D, F, e->final.ln_g, e->final.ln_b, ln->n, c->T, 1, c->D, 0, scratch));
-    else
-        HIP_TRY(e, vithip_pool_layernorm_f32(ln->s, ln->x, D, row + (size_t)K * D, F, e->final.ln_g, e->final.ln_b, ln->n, c->T, 1, c->D, scratch));
-    return VIT_OK;
+/* What each output kind reads of x behind the last layer: 1 where that is the class rows alone, which are all a pruned last layer
+ * updates.  A kind that is not named here runs the layer in full: a new output cannot silently return rows of the layer before. */
+static int class_rows_only(const vit_engine *e, const vit_output *out) {
+    if (out->kind == VIT_OUT_PROBS || out->kind == VIT_OUT_TOPK) return e->head.spec.pool == VIT_HEAD_POOL_NONE; /* a pooled block reads every patch row */
+    if (out->kind == VIT_OUT_FEATURES) return out->spec.kind == VIT_FEAT_CLS; /* MEAN and TOKENS read every row */
+    if (out->kind == VIT_OUT_INTERMEDIATE) return out->tap.kind == VIT_TAP_CLS;
+    return out->kind == VIT_OUT_ATTENTION; /* Q of the class rows, K of every token (qkv_only) */
 }
 
 /* The chunk's context for nb images written as `out` says: dimensions, whether the last layer is pruned, and the lanes -- their
@@ -1252,13 +1257,11 @@ static void chunk_setup(vit_engine *e, vithip_stream_t s, int nb, const vit_outp
     c->T = e->tokens; c->D = cfg->embed_dim; c->H = VIT_HIDDEN_DIM(cfg); c->H1 = VIT_FC1_ROWS(cfg); c->NC = cfg->num_classes;
     c->L = e->opt.lanes > VIT_MAX_LANES ? VIT_MAX_LANES : e->opt.lanes;
     if (c->L < 1 || nb < 2 * c->L) c->L = 1;
-    c->pruned = e->opt.prune_last_layer && c->T <= 224 && !(out->kind == VIT_OUT_FEATURES && out->spec.kind != VIT_FEAT_CLS) &&
-                !(out->kind == VIT_OUT_INTERMEDIATE && out->tap.kind != VIT_TAP_CLS) &&
-                !((out->kind == VIT_OUT_PROBS || out->kind == VIT_OUT_TOPK) && e->head_w && e->head.pool != VIT_HEAD_POOL_NONE);
+    c->pruned = e->opt.prune_last_layer && c->T <= 224 && class_rows_only(e, out);
     c->qkv_only = out->kind == VIT_OUT_ATTENTION;
     const int bf16 = e->opt.dtype == VIT_DTYPE_BF16;
     const size_t B = (size_t)e->opt.max_batch, T = (size_t)c->T, D = (size_t)c->D, H1 = (size_t)c->H1;
-    const size_t esz = bf16 ? sizeof(unsigned short) : sizeof(float);
+    const size_t esz = c->esz = bf16 ? sizeof(unsigned short) : sizeof(float);
     /* Where the LayerNorm fold keeps its row statistics.  fp32 engines: ln_rows32 = the pairs of max_batch * T token rows, then
      * of max_batch class rows; ln_part32 = the partial sums, [D / 64][rows][2] per lane.  bf16 engines: the idle halves of the y
      * and qkv allocations, which bf16 activations only half fill -- the bf16 copy of x in y's; the partial sums
@@ -1309,14 +1312,14 @@ static int forward_chunk(vit_engine *e, vithip_stream_t s, const void *d_images,
             if (l == out->tap.layers[j]) RUN(stage_tap(c, out, j++));
         }
     } else {
-        const int head_taps = e->head_w && (out->kind == VIT_OUT_PROBS || out->kind == VIT_OUT_TOPK);
+        const int head_taps = out->kind == VIT_OUT_PROBS || out->kind == VIT_OUT_TOPK;
         for (int l = 0; l < cfg->depth; ++l) {
             RUN(encoder_layer(c, l));
             if (head_taps) RUN(stage_head_tap(c, l));
         }
         if (out->kind == VIT_OUT_FEATURES) RUN(stage_features(c, out));
         else if (out->kind == VIT_OUT_ATTENTION) RUN(stage_cls_attention(c, out));
-        else RUN(stage_head(c, out->dst, out->label, out->prob, out->kind == VIT_OUT_TOPK ? &out->topk : NULL));
+        else RUN(stage_head(c, out));
     }
     for (int j = 1; j < c->L; ++j) { /* join */
         HIP_TRY(e, vithip_event_record(e->ev_join[j - 1], c->lane[j].s));
@@ -2131,13 +2134,11 @@ int vit_engine_set_head(vit_engine *e, const vit_head_spec *spec, const float *w
         return fail(e, VIT_ERR_HIP, "set_head: HIP error %d (%s) uploading the head; the previous head stays", hrc, vithip_error_string(hrc));
     }
     drop_graph(e);
-    restore_own_head(e);
-    memset(&e->head, 0, sizeof(e->head)); /* the entries of cls_layers behind num_cls_layers stay zero */
-    e->head.num_cls_layers = spec->num_cls_layers;
-    for (int j = 0; j < spec->num_cls_layers; ++j) e->head.cls_layers[j] = spec->cls_layers[j];
-    e->head.pool = spec->pool;
-    e->head_in = F;
-    e->head_w = w; e->head_b = b; e->head_operand = operand;
+    release_head(&e->head);
+    e->head = (vit_head){.in = F, .ops = {.W = w, .bias = b}, .operand = operand, .owned = 1};
+    e->head.spec.num_cls_layers = spec->num_cls_layers; /* the entries of cls_layers behind num_cls_layers stay zero */
+    for (int j = 0; j < spec->num_cls_layers; ++j) e->head.spec.cls_layers[j] = spec->cls_layers[j];
+    e->head.spec.pool = spec->pool;
     e->last_rows = 0;
     return VIT_OK;
 }
@@ -2145,10 +2146,8 @@ int vit_engine_set_head(vit_engine *e, const vit_head_spec *spec, const float *w
 int vit_engine_read_head_operand(vit_engine *e, float *dst, int rows) {
     if (!e || !dst) return VIT_ERR_ARG;
     if (rows <= 0 || rows > e->last_rows) return fail(e, VIT_ERR_ARG, "read_head_operand: %d rows requested, last chunk had %d", rows, e->last_rows);
-    const float *operand = e->head_w ? e->head_operand : e->z;
-    const size_t F = e->head_w ? e->head_in : (size_t)e->cfg.embed_dim;
     HIP_TRY(e, vithip_device_sync()); /* the chunk may have run on a caller-provided stream */
-    HIP_TRY(e, vithip_memcpy_d2h(dst, operand, (size_t)rows * F * sizeof(float), e->stream));
+    HIP_TRY(e, vithip_memcpy_d2h(dst, e->head.operand, (size_t)rows * e->head.in * sizeof(float), e->stream));
     HIP_TRY(e, vithip_stream_sync(e->stream));
     return VIT_OK;
 }
@@ -2162,12 +2161,11 @@ int vit_engine_debug_pool_scratch(vit_engine *e, int nb, int lane, size_t range[
     chunk_setup(e, e->stream, nb, &out, &c);
     if (lane >= c.L) return -1;
     const vit_lane *ln = &c.lane[lane];
-    const size_t esz = e->opt.dtype == VIT_DTYPE_BF16 ? sizeof(unsigned short) : sizeof(float);
     const size_t rows = (size_t)ln->n * c.T * c.D;
     size_t need;
     const char *base = (const char *)e->y, *scratch = (const char *)pool_scratch(&c, ln, &need);
     range[0] = (size_t)(scratch - base); range[1] = range[0] + need;
-    range[2] = (size_t)((const char *)ln->y - base); range[3] = range[2] + rows * esz;
+    range[2] = (size_t)((const char *)ln->y - base); range[3] = range[2] + rows * c.esz;
     range[4] = range[5] = 0;
     if (ln->xa && ln->xa != (void *)ln->x) { /* the fold's bf16 copy of x, in y's upper half */
         range[4] = (size_t)((const char *)ln->xa - base); range[5] = range[4] + rows * sizeof(unsigned short);
