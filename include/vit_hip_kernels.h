@@ -482,7 +482,7 @@ int vithip_l2_normalize_rows_f32(vithip_stream_t stream, float *x, size_t ldx, i
  * The other order, pool first and normalise the pooled row (timm's fc_norm heads; csrc/vit_pool.hip):
  *     m[i][0..dim) = (sum_{t in [first_tok, tokens)} x_it) / (tokens - first_tok);   out[i] = LayerNorm(m[i]) with gamma / beta,
  * or out[i] = m[i] itself when gamma and beta are both NULL.  Rows of x as above.  The LayerNorm is the arithmetic of
- * vithip_layernorm_f32 (csrc/vit_layernorm_row.hpp) on the stored fp32 m[i]:
+ * vithip_layernorm_f32 (csrc/vit_row.hpp) on the stored fp32 m[i]:
  *     pool_layernorm(x, gamma, beta) == vithip_layernorm_f32(pool_layernorm(x, NULL, NULL), gamma, beta)   bit for bit.
  * Same structure and contract as vithip_layernorm_pool_f32: segments of 16 token rows per workgroup summed in a fixed order, one
  * small finishing launch (one wave per image) that adds the segment sums in index order, divides and normalises; the order depends
@@ -527,7 +527,7 @@ int vithip_cls_attention_bf16(vithip_stream_t stream, const unsigned short *qkv,
  *   VITHIP_TAP_PATCHES  [P][dim]       = f(r(1..P))
  *   VITHIP_TAP_MAP      [dim][P]       element [d][t - 1] = f(r(t))[d]: [dim][g][g] for a square grid of g x g patches, raster order
  * Normalised values are the bits vithip_layernorm_f32 gives for the same row (one device function holds the arithmetic of both,
- * csrc/vit_layernorm_row.hpp), unnormalised ones the bits of x; MAP is the exact transpose of PATCHES.  Only the block of each
+ * csrc/vit_row.hpp), unnormalised ones the bits of x; MAP is the exact transpose of PATCHES.  Only the block of each
  * image is written: the floats from its end up to out_image_stride are not touched, so several launches can fill one output row
  * side by side.  MAP goes through an LDS tile and stores runs of up to 32 tokens per channel (16 above dim 1024), as 16 bytes per lane when P % 4 == 0
  * and as 4 bytes per lane otherwise; any P >= 1 is correct.  No atomics; results do not depend on the grid.  Non-finite values in

@@ -7,17 +7,13 @@ the batch it sits in.
 import numpy as np
 import pytest
 
+from engine_helpers import same_bits
 from test_features_abi import POOL_REL, l2_normalize_f64, pool_reference
 from vit_amd import binding as B
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(256, 197, 768), (1, 197, 768), (3, 5, 128), (7, 17, 192), (5, 577, 1024), (300, 2, 64), (2, 50, 2048)]
-
-
-def same_bits(a, b) -> bool:
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
 def operands(images, tokens, dim, seed, ldx=None):
@@ -81,6 +77,26 @@ def test_an_image_of_nans_poisons_exactly_its_own_row(images, tokens, dim):
         assert np.isfinite(got[others]).all()
         if not l2:
             assert same_bits(got[others], clean[others])
+
+
+@pytest.mark.parametrize("images", [1, 5])
+@pytest.mark.parametrize("dim", [64, 192, 768, 1024, 1280, 2048])  # NVEC 1, 1, 3, 4, 8, 8
+def test_one_pooled_row_is_the_layernorm_row_bit_for_bit(dim, images):
+    """The head of csrc/vit_pool.hip: the row statistics are layernorm_f32_kernel's to the bit.  tokens = 2, first_tok = 1 pools
+    exactly one row, and gamma = 1, beta = 0 and the division by 1.0f are exact: the output row is (x - mean) * inv_std of token 1.
+    vithip_layernorm_f32 takes the same row straight out of x (leading dimension 2 * dim, from element dim on).  Compared as
+    floats: the pooled sum starts from +0 and cannot keep the sign of a zero."""
+    rng = np.random.default_rng(31 * dim + images)
+    x = rng.uniform(-1.5, 1.5, size=(images * 2, dim)).astype(np.float32)
+    one, zero = np.ones(dim, np.float32), np.zeros(dim, np.float32)
+    pooled = B.layernorm_pool(x, one, zero, images, 2, 1, False)
+    dx, dg, db = B.DeviceArray.from_numpy(x), B.DeviceArray.from_numpy(one), B.DeviceArray.from_numpy(zero)
+    dy = B.DeviceArray((images, dim))
+    B.hip_check(B.lib().vithip_layernorm_f32(None, dx.ptr + 4 * dim, 2 * dim, dy.ptr, dim, dg.ptr, db.ptr, images, dim), "layernorm")
+    rows = dy.numpy()
+    print(f"dim {dim}, images {images}: {int((pooled != rows).sum())} of {rows.size} elements differ")
+    assert np.isfinite(rows).all() and rows.any()
+    assert (pooled == rows).all()
 
 
 def test_constant_rows_go_through_the_epsilon():

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import strided
+from engine_helpers import same_bits
 from vit_amd import binding as B
 
 pytestmark = pytest.mark.gpu
@@ -20,11 +21,6 @@ REL = 2e-5  # tests/test_gpu_ops.py
 TOKENS = [2, 17, 18, 50, 197, 257]   # one patch behind a class row; exactly one segment; a full segment and one row; ragged ones
 DIMS = [64, 192, 512, 768, 1024, 2048]  # every variant of the kernels: 1, 1, 2, 3, 4, 8 float4 per lane
 HIP_INVALID_VALUE = 1
-
-
-def same_bits(a, b) -> bool:
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
 def operands(images, tokens, dim, seed):

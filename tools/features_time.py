@@ -33,7 +33,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 CONFIGS = {"f32": 256, "bf16": 2048}
-KERNELS = ("layernorm_pool_partial_kernel", "layernorm_pool_finish_kernel", "l2_normalize_rows_kernel", "layernorm_f32_kernel")
+KERNELS = ("pool_partial_kernel","layernorm_pool_finish_kernel", "l2_normalize_rows_kernel", "layernorm_f32_kernel")
 POOL_SHAPES = [(1, 197, 768), (8, 197, 768), (256, 197, 768), (2048, 197, 768)]
 
 

@@ -26,10 +26,13 @@
 #include <hip/hip_runtime.h>
 
 #include "vit_hip_kernels.h"
+#include "vit_row.hpp"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using vit_row::f32x4;
+using vit_row::wave_max;
+using vit_row::wave_sum;
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int CA_THREADS = 256;
@@ -60,17 +63,6 @@ template <> struct Elems<true> {
         }
     }
 };
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 // max / sum over the workgroup, the waves' values combined in wave order; every thread gets the result
 template <bool MAX>

@@ -9,18 +9,15 @@
 #include <hip/hip_runtime.h>
 
 #include "vit_hip_kernels.h"
+#include "vit_row.hpp"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using vit_row::aligned16;
+using vit_row::f32x4;
+using vit_row::wave_sum;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 __device__ __forceinline__ f32x2 finish(float s, float ss, int dim) {
     const float mean = s / (float)dim;
@@ -185,7 +182,6 @@ __global__ __launch_bounds__(256) void rowstats_f32_kernel(const float *__restri
     }
 }
 
-constexpr int RS_MAX_VEC = 8;  // float4 per lane: dim <= 2048
 template <int NVEC>
 __global__ __launch_bounds__(256) void rowstats_bf16_kernel(const float *__restrict__ x, size_t ldx, unsigned short *__restrict__ x16,
                                                             size_t ldx16, float *__restrict__ rows_out, int rows, int dim) {
@@ -215,23 +211,12 @@ __global__ __launch_bounds__(256) void rowstats_bf16_kernel(const float *__restr
     }
 }
 
+// Strips x (sum, sum of squares) of a residual GEMM's epilogue -> one pair per row, strips in ascending column order, the same for
+// every row and every launch.  FINISH = finish: (rstd, mean * rstd).  FINISH = finish_f32, the fp32 fold (csrc/vit_gemm_common.hpp,
+// epilogue_store_residual_stats): (rstd, mean) as vithip_rowstats_f32 finishes them, the same bits as that kernel on the stored rows.
+template <f32x2 (*FINISH)(float, float, int)>
 __global__ __launch_bounds__(256) void rowstats_finalize_kernel(const float *__restrict__ partials, int strips, int rows, int dim,
                                                                 float *__restrict__ rows_out) {
-    const int row = blockIdx.x * 256 + threadIdx.x;
-    if (row >= rows) return;
-    float s = 0.f, ss = 0.f;
-    for (int k = 0; k < strips; ++k) {  // strips in ascending column order, the same for every row and every launch
-        const f32x2 v = *reinterpret_cast<const f32x2 *>(partials + ((size_t)k * rows + row) * 2);
-        s += v.x;
-        ss += v.y;
-    }
-    *reinterpret_cast<f32x2 *>(rows_out + (size_t)row * 2) = finish(s, ss, dim);
-}
-
-// fp32 fold: strips of a residual GEMM's epilogue (csrc/vit_gemm_common.hpp, epilogue_store_residual_stats) -> (rstd, mean),
-// strips added in ascending order from 0 and finished as vithip_rowstats_f32 does: the same bits as that kernel on the stored rows
-__global__ __launch_bounds__(256) void rowstats_finalize_f32_kernel(const float *__restrict__ partials, int strips, int rows, int dim,
-                                                                    float *__restrict__ rows_out) {
     const int row = blockIdx.x * 256 + threadIdx.x;
     if (row >= rows) return;
     float s = 0.f, ss = 0.f;
@@ -240,7 +225,7 @@ __global__ __launch_bounds__(256) void rowstats_finalize_f32_kernel(const float 
         s += v.x;
         ss += v.y;
     }
-    *reinterpret_cast<f32x2 *>(rows_out + (size_t)row * 2) = finish_f32(s, ss, dim);
+    *reinterpret_cast<f32x2 *>(rows_out + (size_t)row * 2) = FINISH(s, ss, dim);
 }
 
 __global__ __launch_bounds__(256) void gather_rows_kernel(const float *__restrict__ src, size_t src_stride, float *__restrict__ dst,
@@ -250,8 +235,6 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float *__restric
     const size_t r = i / width, c = i - r * width;
     dst[r * dst_stride + c] = src[r * src_stride + c];
 }
-
-bool aligned16(const void *p) { return (reinterpret_cast<size_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -296,50 +279,39 @@ int vithip_ln_fold_weights_f32_centered(vithip_stream_t stream, const float *W, 
 }
 
 int vithip_rowstats_f32(vithip_stream_t stream, const float *x, size_t ldx, float *rows_out, int rows, int dim) {
+    // not vit_row::rows_ok: the kernel loads single floats (x 4-byte aligned, any ldx >= dim) in whole 64-column strips (dim % 64)
     if (!x || !rows_out || rows <= 0 || dim <= 0 || dim % 64 || dim > 2048 || ldx < (size_t)dim ||
         (reinterpret_cast<size_t>(x) & 3) || (reinterpret_cast<size_t>(rows_out) & 7))
         return static_cast<int>(hipErrorInvalidValue);
-    int blocks = (rows + 3) / 4;
-    if (blocks > 256 * 16) blocks = 256 * 16;
+    const dim3 grid(vit_row::grid_for_rows(rows)), block(256);
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define RSF_LAUNCH(NP) hipLaunchKernelGGL(rowstats_f32_kernel<NP>, dim3(blocks), dim3(256), 0, s, x, ldx, rows_out, rows, dim)
-    switch ((dim / 64 + 1) / 2) {
-        case 2: RSF_LAUNCH(2); break;   // 192, 256
-        case 6: RSF_LAUNCH(6); break;   // 768
-        case 8: RSF_LAUNCH(8); break;   // 1024
-        default: RSF_LAUNCH(0); break;
+    switch ((dim / 64 + 1) / 2) {  // strip pairs; a rule of this kernel, not the NVEC of the row schedule
+        case 2: hipLaunchKernelGGL(rowstats_f32_kernel<2>, grid, block, 0, s, x, ldx, rows_out, rows, dim); break;  // 192, 256
+        case 6: hipLaunchKernelGGL(rowstats_f32_kernel<6>, grid, block, 0, s, x, ldx, rows_out, rows, dim); break;  // 768
+        case 8: hipLaunchKernelGGL(rowstats_f32_kernel<8>, grid, block, 0, s, x, ldx, rows_out, rows, dim); break;  // 1024
+        default: hipLaunchKernelGGL(rowstats_f32_kernel<0>, grid, block, 0, s, x, ldx, rows_out, rows, dim); break;
     }
-#undef RSF_LAUNCH
     return static_cast<int>(hipGetLastError());
 }
 
 int vithip_rowstats_bf16(vithip_stream_t stream, const float *x, size_t ldx, unsigned short *x16, size_t ldx16, float *rows_out,
                          int rows, int dim) {
-    if (!x || !x16 || !rows_out || rows <= 0 || dim <= 0 || dim % 4 || dim > 64 * 4 * RS_MAX_VEC || ldx % 4 || ldx16 % 4 ||
-        ldx < (size_t)dim || ldx16 < (size_t)dim || !aligned16(x) || (reinterpret_cast<size_t>(x16) & 7) ||
-        (reinterpret_cast<size_t>(rows_out) & 7))
+    // x16 takes 8-byte stores of four bf16: 8-byte aligned, not the 16 of vit_row::rows_ok
+    if (!x || !x16 || !rows_out || rows <= 0 || !vit_row::rows_ok(x, ldx, dim) || ldx16 % 4 || ldx16 < (size_t)dim ||
+        (reinterpret_cast<size_t>(x16) & 7) || (reinterpret_cast<size_t>(rows_out) & 7))
         return static_cast<int>(hipErrorInvalidValue);
-    const int nvec = (dim + 255) / 256;
-    int blocks = (rows + 3) / 4;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-#define RS_LAUNCH(NV) hipLaunchKernelGGL(rowstats_bf16_kernel<NV>, dim3(blocks), dim3(256), 0, s, x, ldx, x16, ldx16, rows_out, rows, dim)
-    switch (nvec) {
-        case 1: RS_LAUNCH(1); break;
-        case 2: RS_LAUNCH(2); break;
-        case 3: RS_LAUNCH(3); break;
-        case 4: RS_LAUNCH(4); break;
-        default: RS_LAUNCH(8); break;
-    }
-#undef RS_LAUNCH
-    return static_cast<int>(hipGetLastError());
+    return vit_row::dispatch_nvec(dim, [&](auto nvec) {
+        hipLaunchKernelGGL(rowstats_bf16_kernel<decltype(nvec)::value>, dim3(vit_row::grid_for_rows(rows)), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), x, ldx, x16, ldx16, rows_out, rows, dim);
+        return static_cast<int>(hipGetLastError());
+    });
 }
 
 int vithip_rowstats_finalize(vithip_stream_t stream, const float *partials, int strips, int rows, int dim, float *rows_out) {
     if (!partials || !rows_out || strips <= 0 || rows <= 0 || dim <= 0 || (reinterpret_cast<size_t>(partials) & 7) ||
         (reinterpret_cast<size_t>(rows_out) & 7))
         return static_cast<int>(hipErrorInvalidValue);
-    hipLaunchKernelGGL(rowstats_finalize_kernel, dim3((rows + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), partials,
+    hipLaunchKernelGGL(rowstats_finalize_kernel<finish>, dim3((rows + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), partials,
                        strips, rows, dim, rows_out);
     return static_cast<int>(hipGetLastError());
 }
@@ -348,7 +320,7 @@ int vithip_rowstats_finalize_f32(vithip_stream_t stream, const float *partials, 
     if (!partials || !rows_out || rows <= 0 || dim <= 0 || dim % 64 || (reinterpret_cast<size_t>(partials) & 7) ||
         (reinterpret_cast<size_t>(rows_out) & 7))
         return static_cast<int>(hipErrorInvalidValue);
-    hipLaunchKernelGGL(rowstats_finalize_f32_kernel, dim3((rows + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), partials,
+    hipLaunchKernelGGL(rowstats_finalize_kernel<finish_f32>, dim3((rows + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), partials,
                        dim / 64, rows, dim, rows_out);
     return static_cast<int>(hipGetLastError());
 }

@@ -3,7 +3,8 @@
 //   out[i][:] = gamma * ( 1/(tokens - first_tok) * sum_{t = first_tok}^{tokens-1} (x[i][t][:] - mean_t) * inv_std_t ) + beta
 //
 // with the per-row statistics of layernorm_f32_kernel (csrc/vit_rowops.hip) to the bit: the same lanes add the same elements in
-// the same order, mean = s / dim, var = ss / dim - mean * mean, inv_std = 1 / sqrtf((double)var + 1e-6).  gamma and beta are
+// the same order, mean = s / dim, var = ss / dim - mean * mean, inv_std = 1 / sqrtf((double)var + 1e-6)
+// (tests/test_gpu_pool_kernel.py::test_one_pooled_row_is_the_layernorm_row_bit_for_bit).  gamma and beta are
 // applied ONCE, to the pooled (x - mean) * inv_std: the mean over tokens is linear, so this is the mean of the LayerNorm rows
 // with two fewer operations per element in the streaming pass and nothing but x read there.  One choice for every shape.
 //
@@ -28,37 +29,29 @@
 //
 //   m[i][:] = 1/(tokens - first_tok) * sum_{t = first_tok}^{tokens-1} x[i][t][:];   out[i] = LayerNorm(m[i])   (or m[i] itself)
 //
-// The same two launches with the same segments, the same order of additions and the same clamped loads, minus the statistics
-// in the streaming pass: pool_sum_partial adds raw rows, pool_layernorm_finish (ONE wave per image, which holds the row as
-// vit_layernorm_row.hpp wants it) adds the partial rows in segment order, divides by the row count and normalises the row with
-// the arithmetic of vithip_layernorm_f32 -- the pooled row passes through LDS, so the statistics are taken from the stored fp32
-// values exactly as a vithip_layernorm_f32 launch would take them from memory.
+// The same two launches and the same streaming kernel, pool_partial, with NORM = false: it adds raw rows.  pool_layernorm_finish
+// (ONE wave per image, which holds the row as vit_row.hpp wants it) adds the partial rows in segment order, divides by the row
+// count and normalises the row with the arithmetic of vithip_layernorm_f32 -- the pooled row passes through LDS, so the statistics
+// are taken from the stored fp32 values exactly as a vithip_layernorm_f32 launch would take them from memory.
 #include <hip/hip_runtime.h>
 
 #include "vit_hip_kernels.h"
-#include "vit_layernorm_row.hpp"
+#include "vit_row.hpp"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using vit_row::f32x4;
+using vit_row::wave_sum;
 
 constexpr int POOL_THREADS = 256;
 constexpr int POOL_WAVES = POOL_THREADS / 64;
 constexpr int POOL_ROWS_PER_WAVE = 4;
 constexpr int POOL_SEG = POOL_WAVES * POOL_ROWS_PER_WAVE;  // token rows per workgroup
-constexpr int POOL_MAX_VEC = 8;                           // float4 per lane: dim <= 64*4*8 = 2048
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// grid.x = images * segs; partial [images][segs][dim]
-template <int NVEC>
-__global__ __launch_bounds__(POOL_THREADS) void layernorm_pool_partial_kernel(const float *__restrict__ x, size_t ldx,
-                                                                               float *__restrict__ partial, int tokens,
-                                                                               int first_tok, int dim, int segs) {
+// grid.x = images * segs; partial [images][segs][dim].  NORM: a row contributes (v - mean) * inv_std of its own statistics, else v.
+template <int NVEC, bool NORM>
+__global__ __launch_bounds__(POOL_THREADS) void pool_partial_kernel(const float *__restrict__ x, size_t ldx, float *__restrict__ partial,
+                                                                     int tokens, int first_tok, int dim, int segs) {
     __shared__ f32x4 red[POOL_WAVES - 1][NVEC * 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int image = blockIdx.x / segs, seg = blockIdx.x - image * segs;
@@ -81,25 +74,33 @@ __global__ __launch_bounds__(POOL_THREADS) void layernorm_pool_partial_kernel(co
     for (int i = 0; i < NVEC; ++i) acc[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
     for (int k = 0; k < POOL_ROWS_PER_WAVE; ++k) {
-        float s = 0.0f, ss = 0.0f;
+        const bool live = t0 + k * POOL_WAVES < tokens;  // wave-uniform
+        if constexpr (NORM) {
+            // the expressions of vit_row::row_stats, on rows already in registers (clamped rows take part in the shuffles).  A copy on
+            // purpose: a load-free function split out of row_stats changes which products layernorm_f32_kernel contracts
+            float s = 0.0f, ss = 0.0f;
 #pragma unroll
-        for (int i = 0; i < NVEC; ++i) {
-            const int c = (i * 64 + lane) * 4;
-            if (c < dim) {
-                s += (v[k][i][0] + v[k][i][1]) + (v[k][i][2] + v[k][i][3]);
-                ss += (v[k][i][0] * v[k][i][0] + v[k][i][1] * v[k][i][1]) + (v[k][i][2] * v[k][i][2] + v[k][i][3] * v[k][i][3]);
+            for (int i = 0; i < NVEC; ++i) {
+                const int c = (i * 64 + lane) * 4;
+                if (c < dim) {
+                    s += (v[k][i][0] + v[k][i][1]) + (v[k][i][2] + v[k][i][3]);
+                    ss += (v[k][i][0] * v[k][i][0] + v[k][i][1] * v[k][i][1]) + (v[k][i][2] * v[k][i][2] + v[k][i][3] * v[k][i][3]);
+                }
             }
-        }
-        s = wave_sum(s);
-        ss = wave_sum(ss);
-        const float mean = s / (float)dim;
-        const float var = ss / (float)dim - mean * mean;
-        const float inv_std = 1.0f / sqrtf((float)((double)var + 1e-6));
-        if (t0 + k * POOL_WAVES < tokens) {  // wave-uniform
+            s = wave_sum(s);
+            ss = wave_sum(ss);
+            const float mean = s / (float)dim;
+            const float var = ss / (float)dim - mean * mean;
+            const float inv_std = 1.0f / sqrtf((float)((double)var + 1e-6));
+            if (live) {
 #pragma unroll
-            for (int i = 0; i < NVEC; ++i)
+                for (int i = 0; i < NVEC; ++i)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] += (v[k][i][j] - mean) * inv_std;
+                    for (int j = 0; j < 4; ++j) acc[i][j] += (v[k][i][j] - mean) * inv_std;
+            }
+        } else if (live) {
+#pragma unroll
+            for (int i = 0; i < NVEC; ++i) acc[i] += v[k][i];
         }
     }
     if (wave > 0) {
@@ -166,58 +167,7 @@ __global__ __launch_bounds__(POOL_THREADS) void l2_normalize_rows_kernel(float *
     }
 }
 
-// pool_layernorm, launch 1: layernorm_pool_partial_kernel without the statistics.  grid.x = images * segs; partial [images][segs][dim]
-template <int NVEC>
-__global__ __launch_bounds__(POOL_THREADS) void pool_sum_partial_kernel(const float *__restrict__ x, size_t ldx, float *__restrict__ partial,
-                                                                         int tokens, int first_tok, int dim, int segs) {
-    __shared__ f32x4 red[POOL_WAVES - 1][NVEC * 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int image = blockIdx.x / segs, seg = blockIdx.x - image * segs;
-    const float *img = x + (size_t)image * tokens * ldx;
-    const int t0 = first_tok + seg * POOL_SEG + wave;
-
-    f32x4 v[POOL_ROWS_PER_WAVE][NVEC];
-#pragma unroll
-    for (int k = 0; k < POOL_ROWS_PER_WAVE; ++k) {
-        const int t = t0 + k * POOL_WAVES;
-        const float *src = img + (size_t)(t < tokens ? t : tokens - 1) * ldx;  // clamped: always a row of this image
-#pragma unroll
-        for (int i = 0; i < NVEC; ++i) {
-            const int c = (i * 64 + lane) * 4;
-            v[k][i] = c < dim ? *reinterpret_cast<const f32x4 *>(src + c) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        }
-    }
-    f32x4 acc[NVEC];
-#pragma unroll
-    for (int i = 0; i < NVEC; ++i) acc[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int k = 0; k < POOL_ROWS_PER_WAVE; ++k) {
-        if (t0 + k * POOL_WAVES < tokens) {  // wave-uniform
-#pragma unroll
-            for (int i = 0; i < NVEC; ++i) acc[i] += v[k][i];
-        }
-    }
-    if (wave > 0) {
-#pragma unroll
-        for (int i = 0; i < NVEC; ++i) red[wave - 1][i * 64 + lane] = acc[i];
-    }
-    __syncthreads();
-    if (wave == 0) {
-        float *dst = partial + ((size_t)image * segs + seg) * dim;
-#pragma unroll
-        for (int i = 0; i < NVEC; ++i) {
-            const int c = (i * 64 + lane) * 4;
-            if (c < dim) {
-                f32x4 a = acc[i];
-#pragma unroll
-                for (int w = 0; w < POOL_WAVES - 1; ++w) a += red[w][i * 64 + lane];
-                *reinterpret_cast<f32x4 *>(dst + c) = a;
-            }
-        }
-    }
-}
-
-// pool_layernorm, launch 2: one workgroup of ONE wave per image; lane q holds float4 q, q + 64, ... of the row (vit_layernorm_row.hpp).
+// pool_layernorm, launch 2: one workgroup of ONE wave per image; lane q holds float4 q, q + 64, ... of the row (vit_row.hpp).
 // gamma == NULL (then beta is too; workgroup-uniform): the pooled mean itself is the output.
 template <int NVEC>
 __global__ __launch_bounds__(64) void pool_layernorm_finish_kernel(const float *__restrict__ partial, float *__restrict__ out, size_t ldo,
@@ -255,36 +205,34 @@ __global__ __launch_bounds__(64) void pool_layernorm_finish_kernel(const float *
     __syncthreads();
     f32x4 v[NVEC];
     float mean, inv_std;
-    vit_ln::row_stats<NVEC>(reinterpret_cast<const float *>(pooled), dim, lane, v, mean, inv_std);
+    vit_row::row_stats<NVEC>(reinterpret_cast<const float *>(pooled), dim, lane, v, mean, inv_std);
 #pragma unroll
     for (int i = 0; i < NVEC; ++i) {
         const int c = (i * 64 + lane) * 4;
         if (c < dim) {
             const f32x4 g = *reinterpret_cast<const f32x4 *>(gamma + c);
             const f32x4 b = *reinterpret_cast<const f32x4 *>(beta + c);
-            *reinterpret_cast<f32x4 *>(dst + c) = vit_ln::row_affine(v[i], mean, inv_std, g, b);
+            *reinterpret_cast<f32x4 *>(dst + c) = vit_row::row_affine(v[i], mean, inv_std, g, b);
         }
     }
 }
 
 int pool_segs(int tokens, int first_tok) { return (tokens - first_tok + POOL_SEG - 1) / POOL_SEG; }
 
-template <int NVEC>
-int launch_partial(hipStream_t s, const float *x, size_t ldx, float *partial, int images, int tokens, int first_tok, int dim, int segs) {
-    hipLaunchKernelGGL(layernorm_pool_partial_kernel<NVEC>, dim3((unsigned)images * (unsigned)segs), dim3(POOL_THREADS), 0, s, x, ldx,
-                       partial, tokens, first_tok, dim, segs);
-    return static_cast<int>(hipGetLastError());
+// What both pooling launchers ask of their arguments; affine_optional: gamma == beta == NULL is allowed.
+bool pool_args_ok(const float *x, size_t ldx, const float *out, size_t ldo, const float *gamma, const float *beta, bool affine_optional,
+                  int images, int tokens, int first_tok, int dim, const float *workspace) {
+    if (!x || !out || !workspace || images <= 0 || first_tok < 0 || tokens < 2 || tokens <= first_tok) return false;
+    if (affine_optional ? (gamma == nullptr) != (beta == nullptr) : !gamma || !beta) return false;
+    if (!vit_row::rows_ok(x, ldx, dim) || !vit_row::rows_ok(out, ldo, dim)) return false;
+    if (!vit_row::aligned16(gamma) || !vit_row::aligned16(beta) || !vit_row::aligned16(workspace)) return false;
+    return (size_t)images * pool_segs(tokens, first_tok) <= (size_t)0x7fffffff;  // grid.x of the partial launch
 }
 
-template <int NVEC>
-int launch_pool_layernorm(hipStream_t s, const float *x, size_t ldx, float *out, size_t ldo, const float *gamma, const float *beta,
-                          float *partial, int images, int tokens, int first_tok, int dim, int segs) {
-    hipLaunchKernelGGL(pool_sum_partial_kernel<NVEC>, dim3((unsigned)images * (unsigned)segs), dim3(POOL_THREADS), 0, s, x, ldx, partial,
-                       tokens, first_tok, dim, segs);
-    const int rc = static_cast<int>(hipGetLastError());
-    if (rc) return rc;
-    hipLaunchKernelGGL(pool_layernorm_finish_kernel<NVEC>, dim3(images), dim3(64), 0, s, partial, out, ldo, gamma, beta, dim, segs,
-                       (float)(tokens - first_tok));
+template <int NVEC, bool NORM>
+int launch_partial(hipStream_t s, const float *x, size_t ldx, float *partial, int images, int tokens, int first_tok, int dim, int segs) {
+    hipLaunchKernelGGL((pool_partial_kernel<NVEC, NORM>), dim3((unsigned)images * (unsigned)segs), dim3(POOL_THREADS), 0, s, x, ldx,
+                       partial, tokens, first_tok, dim, segs);
     return static_cast<int>(hipGetLastError());
 }
 
@@ -303,32 +251,22 @@ size_t vithip_layernorm_pool_f32_workspace_floats(int images, int tokens, int fi
 }
 
 int vithip_l2_normalize_rows_f32(vithip_stream_t stream, float *x, size_t ldx, int rows, int dim) {
-    if (!x || rows <= 0 || dim <= 0 || dim % 4 || ldx % 4 || ldx < (size_t)dim || (reinterpret_cast<size_t>(x) & 15))
+    // not vit_row::rows_ok: the workgroup strides over the row, so dim has no upper bound
+    if (!x || rows <= 0 || dim <= 0 || dim % 4 || ldx % 4 || ldx < (size_t)dim || !vit_row::aligned16(x))
         return static_cast<int>(hipErrorInvalidValue);
     return l2_launch(static_cast<hipStream_t>(stream), x, ldx, rows, dim);
 }
 
 int vithip_layernorm_pool_f32(vithip_stream_t stream, const float *x, size_t ldx, float *out, size_t ldo, const float *gamma,
                               const float *beta, int images, int tokens, int first_tok, int dim, int l2_normalize, float *workspace) {
-    if (!x || !out || !gamma || !beta || !workspace || images <= 0 || dim <= 0 || first_tok < 0 || tokens < 2 || tokens <= first_tok)
-        return static_cast<int>(hipErrorInvalidValue);
-    if (dim % 4 || dim > 64 * 4 * POOL_MAX_VEC || ldx % 4 || ldo % 4 || ldx < (size_t)dim || ldo < (size_t)dim ||
+    if (!pool_args_ok(x, ldx, out, ldo, gamma, beta, false, images, tokens, first_tok, dim, workspace) ||
         (l2_normalize != 0 && l2_normalize != 1))
         return static_cast<int>(hipErrorInvalidValue);
-    if ((reinterpret_cast<size_t>(x) & 15) || (reinterpret_cast<size_t>(out) & 15) || (reinterpret_cast<size_t>(gamma) & 15) ||
-        (reinterpret_cast<size_t>(beta) & 15) || (reinterpret_cast<size_t>(workspace) & 15))
-        return static_cast<int>(hipErrorInvalidValue);
     const int segs = pool_segs(tokens, first_tok);
-    if ((size_t)images * segs > (size_t)0x7fffffff) return static_cast<int>(hipErrorInvalidValue);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc;
-    switch ((dim + 255) / 256) {
-        case 1: rc = launch_partial<1>(s, x, ldx, workspace, images, tokens, first_tok, dim, segs); break;
-        case 2: rc = launch_partial<2>(s, x, ldx, workspace, images, tokens, first_tok, dim, segs); break;
-        case 3: rc = launch_partial<3>(s, x, ldx, workspace, images, tokens, first_tok, dim, segs); break;
-        case 4: rc = launch_partial<4>(s, x, ldx, workspace, images, tokens, first_tok, dim, segs); break;
-        default: rc = launch_partial<POOL_MAX_VEC>(s, x, ldx, workspace, images, tokens, first_tok, dim, segs); break;
-    }
+    int rc = vit_row::dispatch_nvec(dim, [&](auto nvec) {
+        return launch_partial<decltype(nvec)::value, true>(s, x, ldx, workspace, images, tokens, first_tok, dim, segs);
+    });
     if (rc) return rc;
     hipLaunchKernelGGL(layernorm_pool_finish_kernel, dim3(images), dim3(POOL_THREADS), 0, s, workspace, out, ldo, gamma, beta, dim, segs,
                        (float)(tokens - first_tok));
@@ -343,24 +281,18 @@ size_t vithip_pool_layernorm_f32_workspace_floats(int images, int tokens, int fi
 
 int vithip_pool_layernorm_f32(vithip_stream_t stream, const float *x, size_t ldx, float *out, size_t ldo, const float *gamma,
                               const float *beta, int images, int tokens, int first_tok, int dim, float *workspace) {
-    if (!x || !out || (gamma == nullptr) != (beta == nullptr) || !workspace || images <= 0 || dim <= 0 || first_tok < 0 || tokens < 2 ||
-        tokens <= first_tok)
-        return static_cast<int>(hipErrorInvalidValue);
-    if (dim % 4 || dim > 64 * 4 * POOL_MAX_VEC || ldx % 4 || ldo % 4 || ldx < (size_t)dim || ldo < (size_t)dim)
-        return static_cast<int>(hipErrorInvalidValue);
-    if ((reinterpret_cast<size_t>(x) & 15) || (reinterpret_cast<size_t>(out) & 15) || (reinterpret_cast<size_t>(gamma) & 15) ||
-        (reinterpret_cast<size_t>(beta) & 15) || (reinterpret_cast<size_t>(workspace) & 15))
+    if (!pool_args_ok(x, ldx, out, ldo, gamma, beta, true, images, tokens, first_tok, dim, workspace))
         return static_cast<int>(hipErrorInvalidValue);
     const int segs = pool_segs(tokens, first_tok);
-    if ((size_t)images * segs > (size_t)0x7fffffff) return static_cast<int>(hipErrorInvalidValue);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch ((dim + 255) / 256) {
-        case 1: return launch_pool_layernorm<1>(s, x, ldx, out, ldo, gamma, beta, workspace, images, tokens, first_tok, dim, segs);
-        case 2: return launch_pool_layernorm<2>(s, x, ldx, out, ldo, gamma, beta, workspace, images, tokens, first_tok, dim, segs);
-        case 3: return launch_pool_layernorm<3>(s, x, ldx, out, ldo, gamma, beta, workspace, images, tokens, first_tok, dim, segs);
-        case 4: return launch_pool_layernorm<4>(s, x, ldx, out, ldo, gamma, beta, workspace, images, tokens, first_tok, dim, segs);
-        default: return launch_pool_layernorm<POOL_MAX_VEC>(s, x, ldx, out, ldo, gamma, beta, workspace, images, tokens, first_tok, dim, segs);
-    }
+    return vit_row::dispatch_nvec(dim, [&](auto nvec) {
+        constexpr int NVEC = decltype(nvec)::value;
+        const int rc = launch_partial<NVEC, false>(s, x, ldx, workspace, images, tokens, first_tok, dim, segs);
+        if (rc) return rc;
+        hipLaunchKernelGGL(pool_layernorm_finish_kernel<NVEC>, dim3(images), dim3(64), 0, s, workspace, out, ldo, gamma, beta, dim, segs,
+                           (float)(tokens - first_tok));
+        return static_cast<int>(hipGetLastError());
+    });
 }
 
 }  // extern "C"

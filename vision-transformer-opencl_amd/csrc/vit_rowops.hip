@@ -5,27 +5,20 @@
 //   y = (x - mean) * inv_std * gamma + beta.
 // One 64-lane wave per row: the row is read once as float4 (dim <= 2048 stays in registers),
 // the two sums are reduced with wave shuffles, no LDS and no barrier.  HBM-bound by design.
-// The row's arithmetic is csrc/vit_layernorm_row.hpp, which csrc/vit_tap.hip shares bit for bit.
+// The row's arithmetic is csrc/vit_row.hpp, which csrc/vit_tap.hip shares bit for bit.
 //
 // softmax_top1 follows ViT_seq.c:304-324 and the argmax of Main.c:62-70 (first maximum wins).
 #include <hip/hip_runtime.h>
 
 #include "vit_hip_kernels.h"
-#include "vit_layernorm_row.hpp"
+#include "vit_row.hpp"
 
 namespace {
 
-using vit_ln::f32x4;
-using vit_ln::wave_sum;
+using vit_row::f32x4;
 
-constexpr int LN_THREADS = 256;
-constexpr int LN_MAX_VEC = vit_ln::MAX_VEC;  // float4 per lane: dim <= 64*4*8 = 2048
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
+constexpr int LN_THREADS = vit_row::THREADS;
+constexpr int SM_THREADS = vit_row::THREADS;
 
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 
@@ -44,7 +37,7 @@ __global__ __launch_bounds__(LN_THREADS) void layernorm_f32_kernel(const float *
         const float *src = x + (size_t)row * ldx;
         f32x4 v[NVEC];
         float mean, inv_std;
-        vit_ln::row_stats<NVEC>(src, dim, lane, v, mean, inv_std);
+        vit_row::row_stats<NVEC>(src, dim, lane, v, mean, inv_std);
         OUT *dst = y + (size_t)row * ldy;
 #pragma unroll
         for (int i = 0; i < NVEC; ++i) {
@@ -52,7 +45,7 @@ __global__ __launch_bounds__(LN_THREADS) void layernorm_f32_kernel(const float *
             if (c < dim) {
                 const f32x4 g = *reinterpret_cast<const f32x4 *>(gamma + c);
                 const f32x4 b = *reinterpret_cast<const f32x4 *>(beta + c);
-                const f32x4 o = vit_ln::row_affine(v[i], mean, inv_std, g, b);
+                const f32x4 o = vit_row::row_affine(v[i], mean, inv_std, g, b);
                 if constexpr (sizeof(OUT) == 4) {
                     *reinterpret_cast<f32x4 *>(dst + c) = o;
                 } else {
@@ -66,42 +59,19 @@ __global__ __launch_bounds__(LN_THREADS) void layernorm_f32_kernel(const float *
     }
 }
 
-constexpr int SM_THREADS = 256;
-
 // One workgroup per row.
 __global__ __launch_bounds__(SM_THREADS) void softmax_top1_f32_kernel(const float *__restrict__ logits, int ld_logits,
                                                                       float *__restrict__ probs, int ld_probs,
                                                                       int *__restrict__ top1_label,
                                                                       float *__restrict__ top1_prob, int classes) {
-    __shared__ float red_f[SM_THREADS / 64];
+    __shared__ float red_f[2][SM_THREADS / 64];
     __shared__ int red_i[SM_THREADS / 64];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float *src = logits + (size_t)row * ld_logits;
     float *dst = probs + (size_t)row * ld_probs;
 
-    float mx = -INFINITY;
-    for (int c = tid; c < classes; c += SM_THREADS) mx = fmaxf(mx, src[c]);
-    mx = wave_max(mx);
-    if (lane == 0) red_f[wave] = mx;
-    __syncthreads();
-    mx = red_f[0];
-#pragma unroll
-    for (int w = 1; w < SM_THREADS / 64; ++w) mx = fmaxf(mx, red_f[w]);
-    __syncthreads();
-
-    float sum = 0.0f;
-    for (int c = tid; c < classes; c += SM_THREADS) {
-        const float e = expf(src[c] - mx);
-        dst[c] = e;
-        sum += e;
-    }
-    sum = wave_sum(sum);
-    if (lane == 0) red_f[wave] = sum;
-    __syncthreads();
-    sum = 0.0f;
-#pragma unroll
-    for (int w = 0; w < SM_THREADS / 64; ++w) sum += red_f[w];
-    __syncthreads();
+    float mx, sum;
+    vit_row::softmax_row_stats(src, classes, red_f, mx, sum, [&](int c, float e) { dst[c] = e; });
 
     // normalise (each thread re-reads only its own writes) and track the first maximum probability
     float best = -1.0f;
@@ -117,46 +87,30 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_top1_f32_kernel(const floa
         const int oa = __shfl_xor(arg, off);
         if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
     }
-    if (lane == 0) { red_f[wave] = best; red_i[wave] = arg; }
+    // red_f[0] held the maxima: every wave read them in front of the barrier behind which it got here
+    if (lane == 0) { red_f[0][wave] = best; red_i[wave] = arg; }
     __syncthreads();
     if (tid == 0) {
-        best = red_f[0]; arg = red_i[0];
+        best = red_f[0][0]; arg = red_i[0];
         for (int w = 1; w < SM_THREADS / 64; ++w)
-            if (red_f[w] > best || (red_f[w] == best && red_i[w] < arg)) { best = red_f[w]; arg = red_i[w]; }
+            if (red_f[0][w] > best || (red_f[0][w] == best && red_i[w] < arg)) { best = red_f[0][w]; arg = red_i[w]; }
         if (top1_label) top1_label[row] = arg;
         if (top1_prob) top1_prob[row] = best;
     }
 }
 
-template <int NVEC, typename OUT>
-int launch_ln(hipStream_t s, const float *x, size_t ldx, OUT *y, size_t ldy, const float *gamma,
-              const float *beta, int rows, int dim) {
-    const int rows_per_block = LN_THREADS / 64;
-    int blocks = (rows + rows_per_block - 1) / rows_per_block;
-    if (blocks > 256 * 16) blocks = 256 * 16;  // grid-stride beyond 16 workgroups per CU
-    hipLaunchKernelGGL((layernorm_f32_kernel<NVEC, OUT>), dim3(blocks), dim3(LN_THREADS), 0, s, x, ldx, y, ldy, gamma,
-                       beta, rows, dim);
-    return static_cast<int>(hipGetLastError());
-}
-
 template <typename OUT>
 int layernorm_dispatch(vithip_stream_t stream, const float *x, size_t ldx, OUT *y, size_t ldy, const float *gamma,
                        const float *beta, int rows, int dim) {
-    if (!x || !y || !gamma || !beta || rows <= 0 || dim <= 0) return static_cast<int>(hipErrorInvalidValue);
-    if (dim % 4 || dim > 64 * 4 * LN_MAX_VEC || ldx % 4 || ldy % 4 || ldx < (size_t)dim || ldy < (size_t)dim)
+    // y is held to the rule of x whatever OUT is: a bf16 destination too is 16-byte aligned with ldy % 4 == 0
+    if (!x || !y || !gamma || !beta || rows <= 0 || !vit_row::rows_ok(x, ldx, dim) || !vit_row::rows_ok(y, ldy, dim) ||
+        !vit_row::aligned16(gamma) || !vit_row::aligned16(beta))
         return static_cast<int>(hipErrorInvalidValue);
-    if ((reinterpret_cast<size_t>(x) & 15) || (reinterpret_cast<size_t>(y) & 15) ||
-        (reinterpret_cast<size_t>(gamma) & 15) || (reinterpret_cast<size_t>(beta) & 15))
-        return static_cast<int>(hipErrorInvalidValue);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nvec = (dim + 255) / 256;
-    switch (nvec) {
-        case 1: return launch_ln<1, OUT>(s, x, ldx, y, ldy, gamma, beta, rows, dim);
-        case 2: return launch_ln<2, OUT>(s, x, ldx, y, ldy, gamma, beta, rows, dim);
-        case 3: return launch_ln<3, OUT>(s, x, ldx, y, ldy, gamma, beta, rows, dim);
-        case 4: return launch_ln<4, OUT>(s, x, ldx, y, ldy, gamma, beta, rows, dim);
-        default: return launch_ln<LN_MAX_VEC, OUT>(s, x, ldx, y, ldy, gamma, beta, rows, dim);
-    }
+    return vit_row::dispatch_nvec(dim, [&](auto nvec) {
+        hipLaunchKernelGGL((layernorm_f32_kernel<decltype(nvec)::value, OUT>), dim3(vit_row::grid_for_rows(rows)), dim3(LN_THREADS), 0,
+                           static_cast<hipStream_t>(stream), x, ldx, y, ldy, gamma, beta, rows, dim);
+        return static_cast<int>(hipGetLastError());
+    });
 }
 
 }  // namespace

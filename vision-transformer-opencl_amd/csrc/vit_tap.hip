@@ -1,6 +1,6 @@
 // csrc/vit_tap.hip -- rows of the residual stream as an output: the class row, every token, the patch tokens, or the patch tokens as
 // a channel-major map [dim][patches], each optionally through a LayerNorm of exactly the bits of vithip_layernorm_f32
-// (csrc/vit_layernorm_row.hpp holds the row arithmetic of both).
+// (csrc/vit_row.hpp holds the row arithmetic of both).
 //
 // CLS / TOKENS / PATCHES keep rows as rows: the LayerNorm kernel's schedule (one 64-lane wave per row, the row in registers, 16-byte
 // loads and stores) with a source row and a destination that are computed per (image, token) instead of from one leading dimension.
@@ -24,13 +24,13 @@
 
 #include "vit_device.hpp"
 #include "vit_hip_kernels.h"
-#include "vit_layernorm_row.hpp"
+#include "vit_row.hpp"
 
 namespace {
 
-using vit_ln::f32x4;
+using vit_row::f32x4;
 
-constexpr int TAP_THREADS = 256;
+constexpr int TAP_THREADS = vit_row::THREADS;
 // 16 waves per workgroup; 8 where a lane holds 8 vectors of its row (dim > 1024): 16 waves leave a lane 128 registers, too few for those
 constexpr int map_threads(int nvec) { return nvec > 4 ? 512 : 1024; }
 constexpr int MAP_PAD = 4;
@@ -43,14 +43,14 @@ __device__ __forceinline__ void tap_row(const float *__restrict__ src, float *__
     f32x4 v[NVEC];
     if constexpr (NORM) {
         float mean, inv_std;
-        vit_ln::row_stats<NVEC>(src, dim, lane, v, mean, inv_std);
+        vit_row::row_stats<NVEC>(src, dim, lane, v, mean, inv_std);
 #pragma unroll
         for (int i = 0; i < NVEC; ++i) {
             const int c = (i * 64 + lane) * 4;
             if (c < dim) {
                 const f32x4 g = *reinterpret_cast<const f32x4 *>(gamma + c);
                 const f32x4 b = *reinterpret_cast<const f32x4 *>(beta + c);
-                *reinterpret_cast<f32x4 *>(dst + c) = vit_ln::row_affine(v[i], mean, inv_std, g, b);
+                *reinterpret_cast<f32x4 *>(dst + c) = vit_row::row_affine(v[i], mean, inv_std, g, b);
             }
         }
     } else {
@@ -158,24 +158,9 @@ int launch_tap(hipStream_t s, const float *x, size_t ldx, float *out, size_t out
     const int first_tok = layout == VITHIP_TAP_PATCHES ? 1 : 0;
     const int per_image = layout == VITHIP_TAP_CLS ? 1 : tokens - first_tok;
     const int rows = images * per_image;
-    const int rows_per_block = TAP_THREADS / 64;
-    int blocks = (rows + rows_per_block - 1) / rows_per_block;
-    if (blocks > 256 * 16) blocks = 256 * 16;  // grid-stride beyond 16 workgroups per CU, as the LayerNorm
-    hipLaunchKernelGGL((tap_rows_kernel<NVEC, NORM>), dim3(blocks), dim3(TAP_THREADS), 0, s, x, ldx, out, out_image_stride, gamma, beta,
-                       rows, per_image, first_tok, tokens, dim);
+    hipLaunchKernelGGL((tap_rows_kernel<NVEC, NORM>), dim3(vit_row::grid_for_rows(rows)), dim3(TAP_THREADS), 0, s, x, ldx, out,
+                       out_image_stride, gamma, beta, rows, per_image, first_tok, tokens, dim);
     return static_cast<int>(hipGetLastError());
-}
-
-template <bool NORM>
-int tap_dispatch(hipStream_t s, const float *x, size_t ldx, float *out, size_t out_image_stride, const float *gamma, const float *beta,
-                 int images, int tokens, int dim, int layout) {
-    switch ((dim + 255) / 256) {
-        case 1: return launch_tap<1, NORM>(s, x, ldx, out, out_image_stride, gamma, beta, images, tokens, dim, layout);
-        case 2: return launch_tap<2, NORM>(s, x, ldx, out, out_image_stride, gamma, beta, images, tokens, dim, layout);
-        case 3: return launch_tap<3, NORM>(s, x, ldx, out, out_image_stride, gamma, beta, images, tokens, dim, layout);
-        case 4: return launch_tap<4, NORM>(s, x, ldx, out, out_image_stride, gamma, beta, images, tokens, dim, layout);
-        default: return launch_tap<vit_ln::MAX_VEC, NORM>(s, x, ldx, out, out_image_stride, gamma, beta, images, tokens, dim, layout);
-    }
 }
 
 }  // namespace
@@ -186,15 +171,17 @@ extern "C" int vithip_tap_f32(vithip_stream_t stream, const float *x, size_t ldx
     if (!x || !out || !gamma != !beta || images <= 0 || tokens <= 0 || dim <= 0) return bad;
     if (layout != VITHIP_TAP_CLS && layout != VITHIP_TAP_TOKENS && layout != VITHIP_TAP_PATCHES && layout != VITHIP_TAP_MAP) return bad;
     if ((layout == VITHIP_TAP_PATCHES || layout == VITHIP_TAP_MAP) && tokens < 2) return bad;
-    if (dim % 4 || dim > 64 * 4 * vit_ln::MAX_VEC || ldx % 4 || ldx < (size_t)dim || out_image_stride % 4) return bad;
+    if (!vit_row::rows_ok(x, ldx, dim)) return bad;
     if ((long long)images * tokens > 0x7fffffffLL) return bad;                                     // row numbers are ints
     if (layout == VITHIP_TAP_MAP && (tokens - 1 + 15) / 16 > 65535) return bad;      // MAP: token tiles in grid.y
     const size_t per_image = layout == VITHIP_TAP_CLS ? 1 : layout == VITHIP_TAP_TOKENS ? (size_t)tokens : (size_t)tokens - 1;
-    if (out_image_stride < per_image * (size_t)dim) return bad;
-    if ((reinterpret_cast<size_t>(x) & 15) || (reinterpret_cast<size_t>(out) & 15) || (reinterpret_cast<size_t>(gamma) & 15) ||
-        (reinterpret_cast<size_t>(beta) & 15))
-        return bad;
+    // out is not a matrix of rows with one leading dimension: an image's rows are dense, its stride covers them
+    if (!vit_row::aligned16(out) || out_image_stride % 4 || out_image_stride < per_image * (size_t)dim) return bad;
+    if (!vit_row::aligned16(gamma) || !vit_row::aligned16(beta)) return bad;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return gamma ? tap_dispatch<true>(s, x, ldx, out, out_image_stride, gamma, beta, images, tokens, dim, layout)
-                 : tap_dispatch<false>(s, x, ldx, out, out_image_stride, gamma, beta, images, tokens, dim, layout);
+    return vit_row::dispatch_nvec(dim, [&](auto nvec) {
+        constexpr int NVEC = decltype(nvec)::value;
+        return gamma ? launch_tap<NVEC, true>(s, x, ldx, out, out_image_stride, gamma, beta, images, tokens, dim, layout)
+                     : launch_tap<NVEC, false>(s, x, ldx, out, out_image_stride, gamma, beta, images, tokens, dim, layout);
+    });
 }

@@ -1,12 +1,8 @@
 // csrc/vit_topk.hip -- the k best classes of every logits row, as records: k labels, then the k scores' fp32 bit patterns.
 //
 // The score of class c is logits[c] (VITHIP_SCORE_LOGIT) or the probability softmax_top1_f32_kernel (csrc/vit_rowops.hip) stores
-// for the same row, bit for bit (VITHIP_SCORE_PROB).  That kernel's order of operations is restated here:
-//   mx  = max over the row: thread t takes classes t, t + 256, ... with fmaxf from -INFINITY, the wave's 64 values meet in an xor
-//         butterfly (32, 16, .. 1), the four waves' values are folded 0, 1, 2, 3
-//   e_c = expf(logits[c] - mx)
-//   sum = thread t adds its e_c in ascending c from 0.0f, wave_sum (the same butterfly), the four waves are added 0, 1, 2, 3 from 0.0f
-//   p_c = e_c / sum
+// for the same row, bit for bit (VITHIP_SCORE_PROB): both kernels take the row's maximum and its sum of e_c = expf(logits[c] - mx)
+// from vit_row::softmax_row_stats (csrc/vit_row.hpp), and p_c = e_c / sum.
 // Nothing but the records is written: the probabilities live in LDS while a row is selected from (TOPK_CACHE floats; thread t keeps
 // its own classes t, t + 256, ... there and is their only reader, so the cache needs no barrier and lanes touch consecutive banks) or,
 // for a longer row, are recomputed from the logits in every selection round.  Both give the same bits: e_c / sum is one expression.
@@ -21,25 +17,14 @@
 #include <hip/hip_runtime.h>
 
 #include "vit_hip_kernels.h"
+#include "vit_row.hpp"
 
 namespace {
 
-constexpr int TOPK_THREADS = 256;
+constexpr int TOPK_THREADS = vit_row::THREADS;
 constexpr int TOPK_WAVES = TOPK_THREADS / 64;
 constexpr int TOPK_CACHE = 4096;  // floats of LDS for a row's scores; a longer row is recomputed per round
 constexpr int TOPK_EMPTY = 0x7fffffff;
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 // (s, c) comes before (bs, bc) in the total order
 __device__ __forceinline__ bool before(float s, int c, float bs, int bc) { return s > bs || (s == bs && c < bc); }
@@ -56,29 +41,11 @@ __global__ __launch_bounds__(TOPK_THREADS) void softmax_topk_f32_kernel(const fl
 
     float mx = 0.0f, sum = 1.0f;
     if (PROB) {
-        mx = -INFINITY;
-        for (int c = tid; c < classes; c += TOPK_THREADS) mx = fmaxf(mx, src[c]);
-        mx = wave_max(mx);
-        if (lane == 0) red_f[0][wave] = mx;
-        __syncthreads();
-        mx = red_f[0][0];
-#pragma unroll
-        for (int w = 1; w < TOPK_WAVES; ++w) mx = fmaxf(mx, red_f[0][w]);
-
-        sum = 0.0f;
-        for (int c = tid; c < classes; c += TOPK_THREADS) {
-            const float e = expf(src[c] - mx);
+        vit_row::softmax_row_stats(src, classes, red_f, mx, sum, [&](int c, float e) {
             if (CACHED) cache[c] = e;
-            sum += e;
-        }
-        sum = wave_sum(sum);
-        if (lane == 0) red_f[1][wave] = sum;
-        __syncthreads();
-        sum = 0.0f;
-#pragma unroll
-        for (int w = 0; w < TOPK_WAVES; ++w) sum += red_f[1][w];
-        // no barrier here: round 0 writes red_f[0], which everyone read in front of the barrier above, and round 1 writes
-        // red_f[1] behind round 0's barrier
+        });
+        // no barrier here: round 0 writes red_f[0], which everyone read in front of the function's second barrier, and round 1
+        // writes red_f[1] behind round 0's barrier
         if (CACHED)
             for (int c = tid; c < classes; c += TOPK_THREADS) cache[c] = cache[c] / sum;
     } else if (CACHED) {
