@@ -200,10 +200,15 @@ int vit_engine_forward_host_u8(vit_engine *e, const unsigned char *const *images
  *   VIT_FEAT_CLS     out[i] = y[i][0]                                  [n][D]     the operand the classifier head reads
  *   VIT_FEAT_MEAN    out[i] = 1/(T-1) * sum_{t=1}^{T-1} y[i][t]        [n][D]     mean of the patch tokens (timm global_pool='avg')
  *   VIT_FEAT_TOKENS  out[i][t] = y[i][t], class row first              [n][T][D]  all tokens (timm forward_features)
+ *   VIT_FEAT_HEAD    out[i] = head(operand[i])                         [n][num_classes]  the head in force -- the checkpoint's or one
+ *                    from vit_engine_set_head -- applied to its operand, no softmax: CLIP's projected image embedding when the head
+ *                    slot holds visual_projection with a zero bias.  Without l2_normalize the rows are the bits
+ *                    vit_engine_read_logits() returns for the chunk; read_logits after the call works and returns the un-normalised
+ *                    rows.  A prune_last_layer engine prunes exactly when a probabilities call would; accounted to VIT_STAGE_HEAD.
  *
- * Rows are fp32 for both engine dtypes.  The head GEMM and the softmax are not launched.  CLS is the bits the head of a forward
+ * Rows are fp32 for both engine dtypes.  Except for HEAD, the head GEMM is not launched; the softmax never is.  CLS is the bits the head of a forward
  * call reads.  MEAN is one pass over x (vithip_layernorm_pool_f32): the normalised tokens are never stored, and an image's row
- * has the same bits wherever the image sits in whatever batch.  l2_normalize = 1 (CLS and MEAN only) divides each output row by
+ * has the same bits wherever the image sits in whatever batch.  l2_normalize = 1 (CLS, MEAN and HEAD) divides each output row by
  * max(||row||_2, 1e-12) (torch.nn.functional.normalize).
  *
  * The four calls mirror the four forwards: the same images, chunking, lanes, stream rules and blocking behaviour; `out` takes the
@@ -214,17 +219,17 @@ int vit_engine_forward_host_u8(vit_engine *e, const unsigned char *const *images
  * prune_last_layer engines: a CLS call uses the pruned last layer (same bits as unpruned); a MEAN or TOKENS call needs every token
  * of the last layer and runs it unpruned -- for that call only, not an error.  use_graph: the graph is keyed on the kind of output
  * too, so forwards and feature calls on the same n and pointers never replay each other's graph.  Profiling: the launches are
- * accounted to VIT_STAGE_LN.  vit_engine_read_logits() after a features call is an error: nothing wrote logits.
+ * accounted to VIT_STAGE_LN.  vit_engine_read_logits() after a CLS, MEAN or TOKENS call is an error: nothing wrote logits.
  * VIT_ERR_ARG (the engine stays usable): NULL pointers, n <= 0, unknown kind, l2_normalize other than 0 / 1, l2_normalize with
  * TOKENS, and what the matching forward refuses.
  */
-enum { VIT_FEAT_CLS = 0, VIT_FEAT_MEAN = 1, VIT_FEAT_TOKENS = 2 };
+enum { VIT_FEAT_CLS = 0, VIT_FEAT_MEAN = 1, VIT_FEAT_TOKENS = 2, VIT_FEAT_HEAD = 4 /* 3 stays unassigned: callers know it as an unknown kind (VIT_ERR_ARG) */ };
 typedef struct {
     int kind;          /* VIT_FEAT_* */
-    int l2_normalize;  /* 0 / 1; CLS and MEAN only */
+    int l2_normalize;  /* 0 / 1; not with TOKENS */
 } vit_feature_spec;
 
-/* floats per output row: D, D or tokens * D; 0 on a bad spec */
+/* floats per output row: D, D, tokens * D or (HEAD) num_classes; 0 on a bad spec */
 size_t vit_engine_feature_row_elems(const vit_engine *e, const vit_feature_spec *spec);
 int vit_engine_features_device(vit_engine *e, const float *d_images, int n, const vit_feature_spec *spec, float *d_out, void *stream);
 int vit_engine_features_host(vit_engine *e, const float *const *images, int n, const vit_feature_spec *spec, float *const *out);
@@ -501,6 +506,32 @@ typedef struct {
 size_t vit_engine_head_in_features(const vit_engine *e, const vit_head_spec *spec);
 int vit_engine_set_head(vit_engine *e, const vit_head_spec *spec, const float *weight, const float *bias);
 int vit_engine_read_head_operand(vit_engine *e, float *dst, int rows);
+
+/*
+ * CLIP image towers (OpenAI / OpenCLIP ViT-B/32, B/16, L/14): VIT_MLP_QUICKGELU (or VIT_MLP_GELU for OpenCLIP checkpoints trained with
+ * plain GELU) in vit_config, and the three pieces below; the projected embedding is a features call of VIT_FEAT_HEAD with the head
+ * slot holding visual_projection (num_classes = projection_dim, zero bias).  INTEGRATION.md has the checkpoint mapping.
+ *
+ * vit_engine_set_layernorm_eps: the epsilon of EVERY LayerNorm the engine runs -- the encoder's, the fold's statistics passes and the
+ * finalise launch behind the stats-producing GEMMs, the final LayerNorm, the pooled blocks, the normalised taps and the pre-norm.  A
+ * DOUBLE, added to the variance in double before the cast; the default is exactly the double 1e-6 (VITHIP_LN_EPS; CLIP: 1e-5, HF
+ * ViTModel: 1e-12).  Architecture, not checkpoint data: it PERSISTS across weight installs, and the copy calls do not carry it.
+ * Synchronises the device and drops a captured graph, as vit_engine_set_head does.  VIT_ERR_ARG, nothing changed: eps not finite or
+ * not > 0.  (The gamma/beta weight fold does not depend on it.)
+ *
+ * vit_engine_set_pre_norm: a LayerNorm in front of layer 0 (CLIP's ln_pre, transformers' pre_layrnorm), applied to [cls | patches] +
+ * pos; its output IS the residual stream.  gamma and beta are HOST arrays of embed_dim floats, uploaded as they are to an allocation
+ * of the engine's own.  NULL, NULL removes it; one NULL alone is VIT_ERR_ARG.  Behind the embedding each lane runs one LayerNorm in
+ * place on its n * T rows of the fp32 residual stream (both engine dtypes), with the engine's epsilon, accounted to VIT_STAGE_LN.
+ * Intermediate calls (norm = 0) return the stream behind each layer as ever (hidden_states[l + 1] of transformers); nothing returns
+ * the pre-norm's own output.  The rules of vit_engine_set_head: it synchronises the device and drops a captured graph; EVERY weight
+ * install (vit_engine_load_weights*, vit_engine_load_weight_image, vit_engine_copy_weights*) removes it: set it again behind it; it
+ * is not copied by copy_weights: set it per engine.  The new allocation is made before the old one is freed: on VIT_ERR_NOMEM the
+ * previous pre-norm stays in force and the engine stays usable.  VIT_ERR_STATE: no weights loaded yet.
+ */
+int vit_engine_set_layernorm_eps(vit_engine *e, double eps);
+double vit_engine_get_layernorm_eps(const vit_engine *e);
+int vit_engine_set_pre_norm(vit_engine *e, const float *gamma, const float *beta);
 
 /*
  * The fp32 GEMMs' helper-piece hand-over (csrc/vit_gemm_persistent.hip) since the last call, summed over the lanes: tiles whose

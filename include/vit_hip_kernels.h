@@ -75,7 +75,13 @@ int vithip_graph_destroy(vithip_graph_t graph);
 
 /* ---- kernels ------------------------------------------------------------------------- */
 
-enum { VITHIP_EPI_BIAS = 0, VITHIP_EPI_BIAS_GELU = 1, VITHIP_EPI_BIAS_RESIDUAL = 2 };
+/* The LayerNorm epsilon of every entry point that does not take one: the DOUBLE 1e-6 of the reference (ViT_seq.c:103-121), added to
+ * the variance in double before the cast back to float.  Every such entry point has a sibling `<name>_eps(..., double eps)` with one
+ * more, last, argument (finite, > 0, else hipErrorInvalidValue) and IS a call of that sibling with VITHIP_LN_EPS: the two cannot
+ * drift, and with this value the sibling gives the old entry point's bits.  (CLIP: 1e-5.  HF ViTModel: 1e-12.) */
+#define VITHIP_LN_EPS 1e-6
+enum { VITHIP_EPI_BIAS = 0, VITHIP_EPI_BIAS_GELU = 1, VITHIP_EPI_BIAS_RESIDUAL = 2,
+       VITHIP_EPI_BIAS_QGELU = 6 /* 3, 4, 5 and 7 are the library's own fold forms */ };
 
 /*
  * C[M][ldc] (first N columns) = epilogue(A[M][K] . W[N][K]^T + bias[N]):
@@ -83,6 +89,10 @@ enum { VITHIP_EPI_BIAS = 0, VITHIP_EPI_BIAS_GELU = 1, VITHIP_EPI_BIAS_RESIDUAL =
  * operands).  fp32 in, fp32 MFMA accumulate (v_mfma_f32_32x32x2_f32), fp32 out.
  *   EPI_BIAS_GELU:     y = 0.5*y*(1+erff(y/sqrtf(2)))                 (ViT_seq.c:231-233)
  *   EPI_BIAS_RESIDUAL: y += residual[m][n]; residual may alias C      (ViT_seq.c:286-288,297-299)
+ *   EPI_BIAS_QGELU:    y = y / (1 + exp(-1.702 y)), CLIP's QuickGELU: PyTorch's x * torch.sigmoid(1.702 * x).  One sequence in every
+ *                      kernel, fp32 and bf16, value by value: t = y * fp32(-1.702 * log2 e) (v_mul_f32), e = 2^t (v_exp_f32),
+ *                      d = 1 + e (v_add_f32), r = 1 / d (v_rcp_f32), y * r (v_mul_f32).  +Inf gives +Inf, -Inf and NaN give NaN, a
+ *                      large negative finite y gives a tiny negative value or -0 (r flushes to 0 once d passes 2^126), never NaN.
  * Requirements, the same for every tile code, both arithmetics and the w_split image (anything else: hipErrorInvalidValue):
  *   K % 32 == 0; lda, ldw >= K and % 4 == 0, A and W 16-byte aligned (the operands are read 128 bits at a time);
  *   ldc, ldr >= N, any value: C, residual and bias are accessed one float at a time and need only their natural 4-byte
@@ -114,7 +124,7 @@ typedef struct {
     /* testing: 1 = the helper workgroups run their pieces LAST, so that owners look for them too early and take the
      * compute-it-yourself path (results must not change); 0 = normal. */
     int handover_test;
-    /* LayerNorm folded into the GEMM behind it (both NULL = off; EPI_BIAS and EPI_BIAS_GELU only): A holds the UN-normalised
+    /* LayerNorm folded into the GEMM behind it (both NULL = off; EPI_BIAS, EPI_BIAS_GELU and EPI_BIAS_QGELU only): A holds the UN-normalised
      * rows x, W and bias are the gamma- and beta-folded operands of vithip_ln_fold_weights_f32(), ln_rows [M][2] = (rstd, mean)
      * per row of A (vithip_rowstats_f32), ln_colsum [N] -- or NULL when W is the CENTRED weight of
      * vithip_ln_fold_weights_f32_centered(), whose product needs no centring (the term below is then skipped); the epilogue computes
@@ -142,6 +152,8 @@ typedef struct {
      * from the image and splits only A; every other kernel ignores the field.  The pieces are the ones the on-the-fly split makes,
      * so the result has the same bits with and without it. */
     const void *w_split;
+    /* the LayerNorm epsilon of stats_out (ignored without it): 0 = VITHIP_LN_EPS, else a finite positive double */
+    double stats_eps;
 } vithip_gemm_args;
 /* Non-finite values (NaN, +-Inf, or finite ones whose products overflow) in one row of A reach only that row of C and of stats_out,
  * whatever the tile, arith, w_split or workspace: every other output has the bits of the same launch on clean data
@@ -172,8 +184,10 @@ int vithip_ln_fold_weights_f32_centered(vithip_stream_t stream, const float *W, 
  * added first, then a 32-lane butterfly 16, 8, 4, 2, 1; strips in ascending order), the order a GEMM epilogue that holds the
  * row in its accumulators can reproduce -- so that whoever produces the statistics produces the same bits. */
 int vithip_rowstats_f32(vithip_stream_t stream, const float *x, size_t ldx, float *rows_out, int rows, int dim);
+int vithip_rowstats_f32_eps(vithip_stream_t stream, const float *x, size_t ldx, float *rows_out, int rows, int dim, double eps);
 /* partials [dim / 64][rows][2] (sum, sum of squares per 64-column strip, in the order above) -> rows_out [rows][2] */
 int vithip_rowstats_finalize_f32(vithip_stream_t stream, const float *partials, int rows, int dim, float *rows_out);
+int vithip_rowstats_finalize_f32_eps(vithip_stream_t stream, const float *partials, int rows, int dim, float *rows_out, double eps);
 size_t vithip_gemm_f32_workspace_bytes(void);             /* device bytes a workspace takes on the current device */
 int vithip_gemm_f32_workspace_create(void **workspace);   /* on the current device */
 int vithip_gemm_f32_workspace_destroy(void *workspace);
@@ -184,13 +198,14 @@ void *vithip_gemm_f32_workspace_device_ptr(void *workspace);  /* [flag per owner
 /* ---- bf16 variant (BASELINE.json configs[2]) ---------------------------------
  * bf16 values are raw uint16 (upper half of the fp32 bit pattern, round-to-nearest-even). */
 enum { VITHIP_BF16_EPI_BF16 = 0, VITHIP_BF16_EPI_BF16_GELU = 1, VITHIP_BF16_EPI_F32_RESIDUAL = 2,
-       VITHIP_BF16_EPI_F32_EMBED = 3 /* internal to vithip_patch_embed_bf16 */ };
+       VITHIP_BF16_EPI_F32_EMBED = 3 /* internal to vithip_patch_embed_bf16 */,
+       VITHIP_BF16_EPI_BF16_QGELU = 4 /* C bf16 = bf16(q(acc + bias)): the fp32 sequence of VITHIP_EPI_BIAS_QGELU on the fp32 accumulator, rounded once */ };
 typedef struct {
     const unsigned short *A; int lda;   /* bf16 [M][lda], K contiguous */
     const unsigned short *W; int ldw;   /* bf16 [N][ldw] */
     const float *bias;                  /* fp32 [N] */
     const float *residual; int ldr;     /* fp32, EPI_F32_RESIDUAL only; may alias C */
-    void *C; int ldc;                   /* bf16 (EPI_BF16, EPI_BF16_GELU) or fp32 (EPI_F32_RESIDUAL) */
+    void *C; int ldc;                   /* bf16 (EPI_BF16, EPI_BF16_GELU, EPI_BF16_QGELU) or fp32 (EPI_F32_RESIDUAL) */
     int M, N, K;                        /* K % 64 == 0, N % 4 == 0, lda/ldw % 8 == 0 */
     int epilogue;
     /* testing, per call: 0 auto (ping-pong kernel whenever K >= 128), 1 two-stage kernel (vit_gemm_bf16.hip: the fallback for
@@ -200,7 +215,7 @@ typedef struct {
      * producer, EPI_F32_RESIDUAL with x16 and row_partials set: besides C the epilogue stores bf16(C) to x16 [M][ldx16]
      *   (ldx16 % 8 == 0, 16-byte aligned) and the partial (sum, sum of squares) of every row over every 64-column strip to
      *   row_partials [vithip_ln_strips(N)][M][2]; vithip_rowstats_finalize() turns them into ln_rows;
-     * consumer, EPI_BF16 / EPI_BF16_GELU with ln_rows and ln_colsum set: A is the UN-normalised bf16 row, W and bias are the
+     * consumer, EPI_BF16 / EPI_BF16_GELU / EPI_BF16_QGELU with ln_rows and ln_colsum set: A is the UN-normalised bf16 row, W and bias are the
      *   gamma- and beta-folded operands of vithip_ln_fold_weights(), ln_rows [M][2] = (rstd, mean * rstd) per row of A and
      *   ln_colsum [N]; the epilogue computes rstd * acc - (mean * rstd) * colsum + bias = LayerNorm(x) . W^T + b. */
     const float *ln_rows, *ln_colsum;
@@ -231,9 +246,12 @@ int vithip_ln_fold_weights_scaled(vithip_stream_t stream, const float *W, const 
  * residual GEMM in front of it). */
 int vithip_rowstats_bf16(vithip_stream_t stream, const float *x, size_t ldx, unsigned short *x16, size_t ldx16,
                          float *rows_out, int rows, int dim);
+int vithip_rowstats_bf16_eps(vithip_stream_t stream, const float *x, size_t ldx, unsigned short *x16, size_t ldx16,
+                             float *rows_out, int rows, int dim, double eps);
 /* strips = vithip_ln_strips(N) = 4 * ceil(N / 256): partials [strips][rows][2] (sum, sum of squares) -> rows_out [rows][2]. */
 int vithip_ln_strips(int N);
 int vithip_rowstats_finalize(vithip_stream_t stream, const float *partials, int strips, int rows, int dim, float *rows_out);
+int vithip_rowstats_finalize_eps(vithip_stream_t stream, const float *partials, int strips, int rows, int dim, float *rows_out, double eps);
 /* dst[r * dst_stride .. + width) = src[r * src_stride .. + width): a strided row subset made compact (e.g. the pairs of the class
  * rows).  rows, width >= 1; both strides >= width; 4-byte alignment suffices. */
 int vithip_gather_rows_f32(vithip_stream_t stream, const float *src, size_t src_stride, float *dst, size_t dst_stride, int rows,
@@ -245,6 +263,8 @@ int vithip_gather_rows_f32(vithip_stream_t stream, const float *src, size_t src_
  * outputs; all other outputs have the bits of the same launch on clean data. */
 int vithip_layernorm_f32_bf16out(vithip_stream_t stream, const float *x, size_t ldx, unsigned short *y, size_t ldy,
                                  const float *gamma, const float *beta, int rows, int dim);
+int vithip_layernorm_f32_bf16out_eps(vithip_stream_t stream, const float *x, size_t ldx, unsigned short *y, size_t ldy,
+                                     const float *gamma, const float *beta, int rows, int dim, double eps);
 int vithip_attention_bf16io(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out,
                             int n_images, int tokens, int heads);
 int vithip_attention_bf16io_f32math(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out,
@@ -316,6 +336,11 @@ int vithip_patch_embed_f32_general(vithip_stream_t stream, const float *images, 
  */
 int vithip_layernorm_f32(vithip_stream_t stream, const float *x, size_t ldx, float *y, size_t ldy,
                          const float *gamma, const float *beta, int rows, int dim);
+/* x and y: either the SAME rows (y == x and ldy == ldx: in place, the bits of the out-of-place call -- a wave holds its whole row in
+ * registers before it stores any of it) or disjoint; rows that overlap in any other way are refused (both layernorm entries and
+ * their siblings; the bf16 store is never in place). */
+int vithip_layernorm_f32_eps(vithip_stream_t stream, const float *x, size_t ldx, float *y, size_t ldy,
+                             const float *gamma, const float *beta, int rows, int dim, double eps);
 
 /*
  * SwiGLU: the gate of a gated MLP (csrc/vit_swiglu.hip; Dinov2SwiGLUFFN of transformers, SwiGLUFFNFused of DINOv2).
@@ -475,6 +500,9 @@ int vithip_images_u8_resize_crop_check_filter(const vithip_image_u8 *images, int
 size_t vithip_layernorm_pool_f32_workspace_floats(int images, int tokens, int first_tok, int dim);
 int vithip_layernorm_pool_f32(vithip_stream_t stream, const float *x, size_t ldx, float *out, size_t ldo, const float *gamma,
                               const float *beta, int images, int tokens, int first_tok, int dim, int l2_normalize, float *workspace);
+int vithip_layernorm_pool_f32_eps(vithip_stream_t stream, const float *x, size_t ldx, float *out, size_t ldo, const float *gamma,
+                                  const float *beta, int images, int tokens, int first_tok, int dim, int l2_normalize, float *workspace,
+                                  double eps);
 /* x[r][0..dim) /= max(||x[r]||_2, 1e-12) in place (torch.nn.functional.normalize), one workgroup per row: a row's bits do not
  * depend on the number of rows.  dim % 4 == 0, ldx >= dim and a multiple of 4, x 16-byte aligned. */
 int vithip_l2_normalize_rows_f32(vithip_stream_t stream, float *x, size_t ldx, int rows, int dim);
@@ -495,6 +523,8 @@ int vithip_l2_normalize_rows_f32(vithip_stream_t stream, float *x, size_t ldx, i
 size_t vithip_pool_layernorm_f32_workspace_floats(int images, int tokens, int first_tok, int dim);
 int vithip_pool_layernorm_f32(vithip_stream_t stream, const float *x, size_t ldx, float *out, size_t ldo, const float *gamma,
                               const float *beta, int images, int tokens, int first_tok, int dim, float *workspace);
+int vithip_pool_layernorm_f32_eps(vithip_stream_t stream, const float *x, size_t ldx, float *out, size_t ldo, const float *gamma,
+                                  const float *beta, int images, int tokens, int first_tok, int dim, float *workspace, double eps);
 
 /*
  * The class token's attention over the tokens of its image (csrc/vit_cls_attention.hip): the softmax row of query 0, stored instead
@@ -541,6 +571,8 @@ int vithip_tap_f32(vithip_stream_t s, const float *x, size_t ldx,          /* [i
                    float *out, size_t out_image_stride,                     /* floats from one image's block to the next */
                    const float *gamma, const float *beta,                   /* both NULL: copy the rows unnormalised */
                    int images, int tokens, int dim, int layout);
+int vithip_tap_f32_eps(vithip_stream_t s, const float *x, size_t ldx, float *out, size_t out_image_stride, const float *gamma,
+                       const float *beta, int images, int tokens, int dim, int layout, double eps);
 
 /*
  * A position embedding resampled to another patch grid (csrc/vit_pos_resample.hip), so that a checkpoint runs at another input size.

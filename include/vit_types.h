@@ -54,12 +54,13 @@ typedef struct {
 
 /*
  * The MLP kind.  VIT_MLP_GELU: fc1 -> erf-GELU -> fc2.  VIT_MLP_SWIGLU: fc1 is the fused [2 * H][embed_dim] "w12" (gate rows first,
- * value rows behind) and the hidden layer is silu(gate) * value.  The struct keeps its eight ints -- compiled callers, positional
+ * value rows behind) and the hidden layer is silu(gate) * value.  VIT_MLP_QUICKGELU (CLIP): fc1 -> y * sigmoid(1.702 y) -> fc2, the
+ * layout of a GELU model.  The struct keeps its eight ints -- compiled callers, positional
  * initialisers and the cache file's eight header words stay as they are -- so the kind travels in the top bits of hidden_dim:
  *     vit_config g14 = {224, 14, 3, 1000, 1536, 40, 24, VIT_HIDDEN_DIM_OF(4096, VIT_MLP_SWIGLU)};
  * Read the two parts with VIT_HIDDEN_DIM(cfg) and VIT_MLP_KIND(cfg), never hidden_dim itself.
  */
-enum { VIT_MLP_GELU = 0, VIT_MLP_SWIGLU = 1 };
+enum { VIT_MLP_GELU = 0, VIT_MLP_SWIGLU = 1, VIT_MLP_QUICKGELU = 3 /* 2 stays unassigned: callers know it as a refused kind */ };
 #define VIT_MLP_SHIFT 24
 #define VIT_HIDDEN_DIM_OF(width, mlp) ((int)(width) | ((int)(mlp) << VIT_MLP_SHIFT))
 #define VIT_HIDDEN_DIM(cfg) ((cfg)->hidden_dim & ((1 << VIT_MLP_SHIFT) - 1))

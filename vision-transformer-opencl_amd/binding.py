@@ -11,7 +11,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .synth import MLP_KINDS, MLP_SHIFT, ModelConfig
+from .synth import MLP_CODES, MLP_SHIFT, ModelConfig
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # VIT_HIP_LIBRARY: the probe build (make probes -> libvit_mi355x_probe.so) for the tools/ scripts; default = the product
@@ -25,6 +25,7 @@ STAGES = ("embed", "ln", "qkv", "attn", "outproj", "fc1", "fc2", "head", "softma
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL = 0, 1, 2
+EPI_BIAS_QGELU = 6  # VITHIP_EPI_BIAS_QGELU (3, 4, 5 and 7 are the library's own fold forms)
 ARITH_F32, ARITH_SPLIT3 = 0, 1   # vithip_gemm_args.arith
 
 
@@ -39,7 +40,7 @@ class CConfig(C.Structure):
     @classmethod
     def of(cls, cfg: ModelConfig) -> "CConfig":
         return cls(cfg.img_size, cfg.patch_size, cfg.in_chans, cfg.num_classes, cfg.embed_dim,
-                   cfg.depth, cfg.num_heads, cfg.hidden_dim | (MLP_KINDS.get(cfg.mlp, cfg.mlp) << MLP_SHIFT))
+                   cfg.depth, cfg.num_heads, cfg.hidden_dim | (MLP_CODES.get(cfg.mlp, cfg.mlp) << MLP_SHIFT))
 
 
 class CNetwork(C.Structure):  # Network.h:18-21
@@ -60,7 +61,7 @@ class CFeatureSpec(C.Structure):  # vit_feature_spec
     _fields_ = [("kind", C.c_int), ("l2_normalize", C.c_int)]
 
 
-FEATURE_KINDS = {"cls": 0, "mean": 1, "tokens": 2}  # VIT_FEAT_*
+FEATURE_KINDS = {"cls": 0, "mean": 1, "tokens": 2, "head": 4}  # VIT_FEAT_* (3 is unassigned)
 
 
 class CAttentionSpec(C.Structure):  # vit_attention_spec
@@ -198,7 +199,7 @@ class CGemmArgs(C.Structure):
                 ("C", C.c_void_p), ("ldc", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
                 ("epilogue", C.c_int), ("tile", C.c_int), ("group_m", C.c_int), ("workspace", C.c_void_p),
                 ("handover_test", C.c_int), ("ln_rows", C.c_void_p), ("ln_colsum", C.c_void_p),
-                ("stats_out", C.c_void_p), ("stats_partials", C.c_void_p), ("arith", C.c_int), ("w_split", C.c_void_p)]
+                ("stats_out", C.c_void_p), ("stats_partials", C.c_void_p), ("arith", C.c_int), ("w_split", C.c_void_p), ("stats_eps", C.c_double)]
 
 
 _lib: Optional[C.CDLL] = None
@@ -483,6 +484,19 @@ class _Plain:
         return _PlainBuffer(rows, width, ld, dtype, offset, preload)
 
 
+def _ln_fn(name: str, eps):
+    """(function, extra arguments) of a LayerNorm entry point: `name` itself, or with an epsilon its sibling `name_eps`, which takes
+    one more, last, double.  Call it behind the place that sets `name`'s argtypes."""
+    L = lib()
+    base = getattr(L, name)
+    if eps is None:
+        return base, ()
+    fn = getattr(L, name + "_eps")
+    assert base.argtypes, name
+    fn.argtypes = list(base.argtypes) + [C.c_double]
+    return fn, (float(eps),)
+
+
 def _note(sink, **frames):
     """Hand the output frames of a call to the caller's dict (before the launch: a refused call leaves them to be inspected)."""
     if sink is not None:
@@ -493,7 +507,7 @@ def gemm(A, W, bias, residual=None, epilogue=EPI_BIAS, tile: int = 0, group_m: i
          handover_test: int = 0, stats: Optional[dict] = None, ln=None, row_stats: Optional[dict] = None,
          arith: int = ARITH_F32, w_split: bool = False, lda: Optional[int] = None, ldw: Optional[int] = None,
          ldr: Optional[int] = None, ldc: Optional[int] = None, in_place: bool = False, offset: int = 0, frames=None,
-         out: Optional[dict] = None) -> np.ndarray:
+         out: Optional[dict] = None, stats_eps: float = 0.0) -> np.ndarray:
     """C = epilogue(A . W^T + bias) through vithip_gemm_f32 (tile / group_m: per-call tuning fields, 0 = auto;
     workspace: lend the scratch that enables the helper pieces of the persistent walk; handover_test: see
     vithip_gemm_args; stats: receives the hand-over counters {"taken", "recomputed"} of the launch;
@@ -506,7 +520,8 @@ def gemm(A, W, bias, residual=None, epilogue=EPI_BIAS, tile: int = 0, group_m: i
     lda / ldw / ldr / ldc: leading dimensions (default: dense); in_place: C is the residual's buffer (ldr = ldc);
     offset: C, bias and the residual start this many floats past a 16-byte boundary;
     frames: who allocates the operands (default: exact buffers; tests/strided.py: guarded, sentinel-filled frames);
-    out: a dict that receives the output frames "C", "stats" and "partials"."""
+    out: a dict that receives the output frames "C", "stats" and "partials";
+    stats_eps: the LayerNorm epsilon of row_stats (vithip_gemm_args.stats_eps; 0 = the default, the double 1e-6)."""
     A, W, bias = _as_f32(A), _as_f32(W), _as_f32(bias)
     M, K = A.shape
     N = W.shape[0]
@@ -529,6 +544,7 @@ def gemm(A, W, bias, residual=None, epilogue=EPI_BIAS, tile: int = 0, group_m: i
     dImg = split3_weights_device(dW, N, K, dW.ld) if w_split else None
     if dImg is not None:
         args.w_split = dImg.ptr
+    args.stats_eps = stats_eps
     if row_stats is not None:
         row_stats["in_epilogue"] = int(lib().vithip_gemm_f32_stats_in_epilogue(C.byref(args)))
     try:
@@ -615,6 +631,7 @@ class CGemmBf16Args(C.Structure):
 
 
 BF16_EPI_BF16, BF16_EPI_BF16_GELU, BF16_EPI_F32_RESIDUAL = 0, 1, 2
+BF16_EPI_BF16_QGELU = 4  # VITHIP_BF16_EPI_BF16_QGELU (3 is the patch embedding's own)
 
 
 def to_bf16_bits(x: np.ndarray) -> np.ndarray:
@@ -690,7 +707,7 @@ def ln_fold_weights(W, bias, gamma, beta):
     return dWf.numpy(), dcs.numpy(), dbf.numpy()
 
 
-def rowstats_bf16(x, ldx: Optional[int] = None, ldx16: Optional[int] = None, frames=None, out: Optional[dict] = None):
+def rowstats_bf16(x, ldx: Optional[int] = None, ldx16: Optional[int] = None, frames=None, out: Optional[dict] = None, eps=None):
     """vithip_rowstats_bf16 -> (bf16(x) bits, rows [M][2] = (rstd, mean * rstd)).  ldx / ldx16, frames, out: as for gemm(); the
     output frames are "x16" and "rows"."""
     x = _as_f32(x)
@@ -700,23 +717,31 @@ def rowstats_bf16(x, ldx: Optional[int] = None, ldx16: Optional[int] = None, fra
     F = frames or _Plain
     dx, d16, dr = F.framed(x, ldx), F.out_frame(rows, dim, ldx16, np.uint16), F.out_frame(rows, 2)
     _note(out, x16=d16, rows=dr)
-    hip_check(L.vithip_rowstats_bf16(None, dx.ptr, dx.ld, d16.ptr, d16.ld, dr.ptr, rows, dim), "vithip_rowstats_bf16")
+    fn, e = _ln_fn("vithip_rowstats_bf16", eps)
+    hip_check(fn(None, dx.ptr, dx.ld, d16.ptr, d16.ld, dr.ptr, rows, dim, *e), "vithip_rowstats_bf16")
     return d16.window(), dr.window()
 
 
-def rowstats_finalize(partials, dim: int):
-    """vithip_rowstats_finalize: partials [strips][M][2] -> rows [M][2]."""
+def rowstats_finalize(partials, dim: int, eps=None, f32: bool = False):
+    """vithip_rowstats_finalize: partials [strips][M][2] -> rows [M][2] = (rstd, mean * rstd); f32: vithip_rowstats_finalize_f32, the
+    fp32 fold's (rstd, mean) of [dim / 64][M][2].  eps: the _eps sibling."""
     partials = _as_f32(partials)
     strips, rows, _ = partials.shape
     L = lib()
     L.vithip_rowstats_finalize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     dp, dr = DeviceArray.from_numpy(partials), DeviceArray((rows, 2), np.float32)
-    hip_check(L.vithip_rowstats_finalize(None, dp.ptr, strips, rows, dim, dr.ptr), "vithip_rowstats_finalize")
+    if f32:
+        L.vithip_rowstats_finalize_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        fn, e = _ln_fn("vithip_rowstats_finalize_f32", eps)
+        hip_check(fn(None, dp.ptr, rows, dim, dr.ptr, *e), "vithip_rowstats_finalize_f32")
+        return dr.numpy()
+    fn, e = _ln_fn("vithip_rowstats_finalize", eps)
+    hip_check(fn(None, dp.ptr, strips, rows, dim, dr.ptr, *e), "vithip_rowstats_finalize")
     return dr.numpy()
 
 
 def layernorm_bf16out(x, gamma, beta, ldx: Optional[int] = None, ldy: Optional[int] = None, frames=None,
-                      out: Optional[dict] = None) -> np.ndarray:
+                      out: Optional[dict] = None, eps=None) -> np.ndarray:
     """vithip_layernorm_f32_bf16out -> bf16 bits.  ldx / ldy, frames, out: as for gemm(); the output frame is "y"."""
     x = _as_f32(x)
     rows, dim = x.shape
@@ -727,8 +752,8 @@ def layernorm_bf16out(x, gamma, beta, ldx: Optional[int] = None, ldy: Optional[i
     dx, dg, db = F.framed(x, ldx), F.framed(_as_f32(gamma)), F.framed(_as_f32(beta))
     dy = F.out_frame(rows, dim, ldy, np.uint16)
     _note(out, y=dy)
-    hip_check(L.vithip_layernorm_f32_bf16out(None, dx.ptr, dx.ld, dy.ptr, dy.ld, dg.ptr, db.ptr, rows, dim),
-              "vithip_layernorm_f32_bf16out")
+    fn, e = _ln_fn("vithip_layernorm_f32_bf16out", eps)
+    hip_check(fn(None, dx.ptr, dx.ld, dy.ptr, dy.ld, dg.ptr, db.ptr, rows, dim, *e), "vithip_layernorm_f32_bf16out")
     return dy.window()
 
 
@@ -754,15 +779,21 @@ def attention_bf16io(qkv_bits, n_images: int, tokens: int, heads: int, f32math: 
 
 
 def layernorm(x, gamma, beta, ldx: Optional[int] = None, ldy: Optional[int] = None, frames=None,
-              out: Optional[dict] = None) -> np.ndarray:
-    """vithip_layernorm_f32.  ldx / ldy, frames, out: as for gemm(); the output frame is "y"."""
+              out: Optional[dict] = None, eps=None, in_place: bool = False) -> np.ndarray:
+    """vithip_layernorm_f32 (eps: vithip_layernorm_f32_eps).  ldx / ldy, frames, out: as for gemm(); the output frame is "y".
+    in_place: y is x's own frame (y == x, ldy == ldx)."""
     x = _as_f32(x)
     rows, dim = x.shape
     F = frames or _Plain
-    dx, dg, db = F.framed(x, ldx), F.framed(_as_f32(gamma)), F.framed(_as_f32(beta))
-    dy = F.out_frame(rows, dim, ldy)
+    dg, db = F.framed(_as_f32(gamma)), F.framed(_as_f32(beta))
+    if in_place:
+        dx = dy = F.out_frame(rows, dim, ldx, preload=x)
+    else:
+        dx = F.framed(x, ldx)
+        dy = F.out_frame(rows, dim, ldy)
     _note(out, y=dy)
-    hip_check(lib().vithip_layernorm_f32(None, dx.ptr, dx.ld, dy.ptr, dy.ld, dg.ptr, db.ptr, rows, dim), "vithip_layernorm_f32")
+    fn, e = _ln_fn("vithip_layernorm_f32", eps)
+    hip_check(fn(None, dx.ptr, dx.ld, dy.ptr, dy.ld, dg.ptr, db.ptr, rows, dim, *e), "vithip_layernorm_f32")
     return dy.window()
 
 
@@ -799,7 +830,7 @@ def tap_block(images: int, tokens: int, dim: int, layout) -> tuple:
 
 
 def tap(x, gamma, beta, images: int, tokens: int, layout, ldx: Optional[int] = None, out_image_stride: Optional[int] = None,
-        frames=None, out: Optional[dict] = None, d_out: Optional[int] = None) -> Optional[np.ndarray]:
+        frames=None, out: Optional[dict] = None, d_out: Optional[int] = None, eps=None) -> Optional[np.ndarray]:
     """vithip_tap_f32: x [images * tokens][dim] -> per image the block of `layout`; gamma = beta = None copies the rows unnormalised.
     ldx, frames, out: as for layernorm(); the output frame "out" has one row per image, a block wide, out_image_stride apart.
     d_out: a raw device address to write to instead (out_image_stride is then required); nothing is returned."""
@@ -810,15 +841,16 @@ def tap(x, gamma, beta, images: int, tokens: int, layout, ldx: Optional[int] = N
     dx = F.framed(x, ldx)
     dg = F.framed(_as_f32(gamma)) if gamma is not None else None
     db = F.framed(_as_f32(beta)) if beta is not None else None
-    args = (dg.ptr if dg else None, db.ptr if db else None, images, tokens, dim, k)
+    fn, e = _ln_fn("vithip_tap_f32", eps)
+    args = (dg.ptr if dg else None, db.ptr if db else None, images, tokens, dim, k) + e
     if d_out is not None:
-        hip_check(lib().vithip_tap_f32(None, dx.ptr, dx.ld, d_out, out_image_stride, *args), "vithip_tap_f32")
+        hip_check(fn(None, dx.ptr, dx.ld, d_out, out_image_stride, *args), "vithip_tap_f32")
         hip_check(lib().vithip_device_sync(), "sync")
         return None
     shape = tap_block(images, tokens, dim, k)
     do = F.out_frame(images, int(np.prod(shape)), out_image_stride)
     _note(out, out=do)
-    hip_check(lib().vithip_tap_f32(None, dx.ptr, dx.ld, do.ptr, do.ld, *args), "vithip_tap_f32")
+    hip_check(fn(None, dx.ptr, dx.ld, do.ptr, do.ld, *args), "vithip_tap_f32")
     return do.window().reshape((images,) + shape)
 
 
@@ -863,7 +895,7 @@ def pos_resample(pos, g_dst: int, mode, g_src: Optional[int] = None, guard: int 
     return raw[guard + dst_offset:guard + dst_offset + n].reshape(-1, dim).copy()
 
 
-def layernorm_pool(x, gamma, beta, images: int, tokens: int, first_tok: int = 1, l2_normalize: bool = False) -> np.ndarray:
+def layernorm_pool(x, gamma, beta, images: int, tokens: int, first_tok: int = 1, l2_normalize: bool = False, eps=None) -> np.ndarray:
     """vithip_layernorm_pool_f32: x [images * tokens][ld >= dim] (dim = len(gamma)) -> [images][dim], the mean over tokens
     first_tok.. of the LayerNorm rows, optionally L2-normalised.  Columns dim.. of x are padding (ldx > dim)."""
     x = _as_f32(x)
@@ -874,13 +906,14 @@ def layernorm_pool(x, gamma, beta, images: int, tokens: int, first_tok: int = 1,
     dx, dg, db = DeviceArray.from_numpy(x), DeviceArray.from_numpy(_as_f32(gamma)), DeviceArray.from_numpy(_as_f32(beta))
     do = DeviceArray((images, dim))
     ws = DeviceArray((max(1, L.vithip_layernorm_pool_f32_workspace_floats(images, tokens, first_tok, dim)),))
-    hip_check(L.vithip_layernorm_pool_f32(None, dx.ptr, ldx, do.ptr, dim, dg.ptr, db.ptr, images, tokens, first_tok, dim,
-                                          int(l2_normalize), ws.ptr), "vithip_layernorm_pool_f32")
+    fn, e = _ln_fn("vithip_layernorm_pool_f32", eps)
+    hip_check(fn(None, dx.ptr, ldx, do.ptr, dim, dg.ptr, db.ptr, images, tokens, first_tok, dim, int(l2_normalize), ws.ptr, *e),
+              "vithip_layernorm_pool_f32")
     return do.numpy()
 
 
 def pool_layernorm(x, gamma, beta, images: int, tokens: int, first_tok: int = 1, ldx: Optional[int] = None, ldo: Optional[int] = None,
-                   frames=None, out: Optional[dict] = None, override: Optional[dict] = None, out_offset: int = 0) -> np.ndarray:
+                   frames=None, out: Optional[dict] = None, override: Optional[dict] = None, out_offset: int = 0, eps=None) -> np.ndarray:
     """vithip_pool_layernorm_f32: x [images * tokens][dim] -> [images][dim], the LayerNorm of the mean over tokens first_tok..;
     gamma = beta = None stores the mean itself.  ldx / ldo, frames, out: as for layernorm(); the output frames are "out" (a row per
     image) and "ws" (the workspace, exactly the declared floats).  override: C arguments by name (x, ldx, out, ldo, gamma, beta,
@@ -900,7 +933,8 @@ def pool_layernorm(x, gamma, beta, images: int, tokens: int, first_tok: int = 1,
     a = dict(x=dx.ptr, ldx=dx.ld, out=do.ptr, ldo=do.ld, gamma=dg.ptr if dg else None, beta=db.ptr if db else None, images=images,
              tokens=tokens, first_tok=first_tok, dim=dim, workspace=ws.ptr)
     a.update(override or {})
-    hip_check(L.vithip_pool_layernorm_f32(None, *a.values()), "vithip_pool_layernorm_f32")
+    fn, e = _ln_fn("vithip_pool_layernorm_f32", eps)
+    hip_check(fn(None, *a.values(), *e), "vithip_pool_layernorm_f32")
     return do.window()
 
 
@@ -938,7 +972,7 @@ def ln_fold_weights_f32_centered(W, bias, gamma, beta):
     return dWf.numpy(), dcs.numpy(), dbf.numpy()
 
 
-def rowstats_f32(x, ldx: Optional[int] = None, frames=None, out: Optional[dict] = None) -> np.ndarray:
+def rowstats_f32(x, ldx: Optional[int] = None, frames=None, out: Optional[dict] = None, eps=None) -> np.ndarray:
     """vithip_rowstats_f32 -> [rows][2] = (rstd, mean).  ldx, frames, out: as for gemm(); the output frame is "rows"."""
     x = _as_f32(x)
     rows, dim = x.shape
@@ -947,7 +981,8 @@ def rowstats_f32(x, ldx: Optional[int] = None, frames=None, out: Optional[dict] 
     F = frames or _Plain
     dx, dr = F.framed(x, ldx), F.out_frame(rows, 2)
     _note(out, rows=dr)
-    hip_check(L.vithip_rowstats_f32(None, dx.ptr, dx.ld, dr.ptr, rows, dim), "vithip_rowstats_f32")
+    fn, e = _ln_fn("vithip_rowstats_f32", eps)
+    hip_check(fn(None, dx.ptr, dx.ld, dr.ptr, rows, dim, *e), "vithip_rowstats_f32")
     return dr.window()
 
 
@@ -1392,14 +1427,16 @@ class Engine:
         """Device-resident path from 8-bit pixels [n][S][S][C] in HBM (raw addresses), async on `stream`."""
         self._device("forward", "_u8", d_images, n, d_probs, mean=mean, std=std, d_label=d_label, d_prob=d_prob, stream=stream)
 
-    # ---- embedding outputs (vit_engine_features_*): kind "cls" | "mean" | "tokens", fp32 rows for both dtypes ----
+    # ---- embedding outputs (vit_engine_features_*): kind "cls" | "mean" | "tokens" | "head", fp32 rows for both dtypes ----
     def feature_shape(self, n: int, kind="cls", l2_normalize=False) -> tuple:
-        """Shape of the rows n images give: (n, D), or (n, tokens, D) for "tokens"."""
+        """Shape of the rows n images give: (n, D), (n, tokens, D) for "tokens", (n, num_classes) for "head"."""
         spec = feature_spec(kind, l2_normalize)
         elems = lib().vit_engine_feature_row_elems(self._h, C.byref(spec))
         if elems == 0:
             raise VitError(f"bad feature spec (kind={kind!r}, l2_normalize={l2_normalize!r})")
         D = self.cfg.embed_dim
+        if FEATURE_KINDS.get(kind, kind) == FEATURE_KINDS["head"]:
+            return (n, elems)
         return (n, D) if elems == D else (n, elems // D, D)
 
     def features(self, images: np.ndarray, kind="cls", l2_normalize=False) -> np.ndarray:
@@ -1620,6 +1657,32 @@ class Engine:
         L = lib()
         L.vit_engine_set_lanes.argtypes = [C.c_void_p, C.c_int]
         self._check(L.vit_engine_set_lanes(self._h, lanes), "vit_engine_set_lanes")
+
+    def set_layernorm_eps(self, eps: float) -> None:
+        """vit_engine_set_layernorm_eps: the epsilon (a double; default 1e-6) of every LayerNorm the engine runs.  It persists across
+        weight installs.  CLIP: 1e-5."""
+        L = lib()
+        L.vit_engine_set_layernorm_eps.argtypes = [C.c_void_p, C.c_double]
+        self._check(L.vit_engine_set_layernorm_eps(self._h, float(eps)), "vit_engine_set_layernorm_eps")
+
+    def get_layernorm_eps(self) -> float:
+        L = lib()
+        L.vit_engine_get_layernorm_eps.argtypes = [C.c_void_p]
+        L.vit_engine_get_layernorm_eps.restype = C.c_double
+        return float(L.vit_engine_get_layernorm_eps(self._h))
+
+    def set_pre_norm(self, gamma, beta) -> None:
+        """vit_engine_set_pre_norm: a LayerNorm in front of layer 0 (CLIP's ln_pre), gamma / beta [embed_dim]; None, None removes it.
+        Every weight install removes it: call this again behind it."""
+        L = lib()
+        L.vit_engine_set_pre_norm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        g = None if gamma is None else _as_f32(gamma).reshape(-1)
+        b = None if beta is None else _as_f32(beta).reshape(-1)
+        for a in (g, b):
+            if a is not None and a.size != self.cfg.embed_dim:
+                raise VitError(f"set_pre_norm: {a.size} floats, the model has embed_dim = {self.cfg.embed_dim}")
+        self._check(L.vit_engine_set_pre_norm(self._h, None if g is None else g.ctypes.data, None if b is None else b.ctypes.data),
+                    "vit_engine_set_pre_norm")
 
     def set_resize_filter(self, filter) -> None:
         """vit_engine_set_resize_filter: "bilinear" (the default) | "bicubic", the Resize filter of every *_images call from the next one

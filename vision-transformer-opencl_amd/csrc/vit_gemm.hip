@@ -177,7 +177,7 @@ __global__ __launch_bounds__(256, (ARITH == ARITH_SPLIT3 ? 2 : BK == 16 ? 3 : 1)
         bias_r[j] = n < p.N ? p.bias[n] : 0.0f;
     }
     FoldOperands<TN, TM> fold{};  // LayerNorm fold (consumer): the folded weight's column sums and the lane's rows' pairs beside the bias
-    if constexpr (EPI == EPI_BIAS_LN || EPI == EPI_BIAS_GELU_LN) {
+    if constexpr (epi_is_fold(EPI)) {
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int n = n0 + wn * WN + j * 32 + r;
@@ -407,6 +407,12 @@ int launch_tile(hipStream_t stream, GemmParams &p, int epilogue) {
                 break;
             case EPI_BIAS_GELU_LN:
                 hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WM, WN, EPI_BIAS_GELU_LN, A_DENSE, 0, BK, PIPE, ARITH>), grid, block, 0, stream, p);
+                break;
+            case VITHIP_EPI_BIAS_QGELU:
+                hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_QGELU, A_DENSE, 0, BK, PIPE, ARITH>), grid, block, 0, stream, p);
+                break;
+            case EPI_BIAS_QGELU_LN:
+                hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WM, WN, EPI_BIAS_QGELU_LN, A_DENSE, 0, BK, PIPE, ARITH>), grid, block, 0, stream, p);
                 break;
             default:
                 return static_cast<int>(hipErrorInvalidValue);
@@ -673,15 +679,20 @@ int vithip_gemm_f32(vithip_stream_t stream, const vithip_gemm_args *a) {
     if (a->w_split && !aligned16(a->w_split)) return static_cast<int>(hipErrorInvalidValue);
     p.w_split = a->arith == ARITH_SPLIT3 ? a->w_split : nullptr;  // (the fp32 arithmetic has no use for it)
     int epilogue = a->epilogue;
+    // the public roles only: the codes in between are the fold forms made below, which read operands a caller's args do not carry
+    if (epilogue != VITHIP_EPI_BIAS && epilogue != VITHIP_EPI_BIAS_GELU && epilogue != VITHIP_EPI_BIAS_RESIDUAL && epilogue != VITHIP_EPI_BIAS_QGELU)
+        return static_cast<int>(hipErrorInvalidValue);
     if (a->ln_rows || a->ln_colsum) {  // LayerNorm fold, consumer side (ln_colsum NULL: the weight is the CENTRED one, see the header)
-        if (!a->ln_rows || (epilogue != VITHIP_EPI_BIAS && epilogue != VITHIP_EPI_BIAS_GELU) ||
+        if (!a->ln_rows || (epilogue != VITHIP_EPI_BIAS && epilogue != VITHIP_EPI_BIAS_GELU && epilogue != VITHIP_EPI_BIAS_QGELU) ||
             (reinterpret_cast<size_t>(a->ln_rows) & 7))
             return static_cast<int>(hipErrorInvalidValue);
         p.ln_rows = a->ln_rows;
         p.ln_colsum = a->ln_colsum;
-        epilogue = epilogue == VITHIP_EPI_BIAS ? vitgemm::EPI_BIAS_LN : vitgemm::EPI_BIAS_GELU_LN;
+        epilogue = epilogue == VITHIP_EPI_BIAS ? vitgemm::EPI_BIAS_LN
+                   : epilogue == VITHIP_EPI_BIAS_GELU ? vitgemm::EPI_BIAS_GELU_LN : vitgemm::EPI_BIAS_QGELU_LN;
     }
     if (a->stats_out) {  // ... producer side
+        if (!(a->stats_eps >= 0.0) || !(a->stats_eps < 1.0e300)) return static_cast<int>(hipErrorInvalidValue);
         if (epilogue != VITHIP_EPI_BIAS_RESIDUAL || a->N % 64 || a->N > 2048 || (reinterpret_cast<size_t>(a->stats_out) & 7) ||
             (reinterpret_cast<size_t>(a->stats_partials) & 7))
             return static_cast<int>(hipErrorInvalidValue);
@@ -690,8 +701,9 @@ int vithip_gemm_f32(vithip_stream_t stream, const vithip_gemm_args *a) {
     const int rc = a->arith == ARITH_SPLIT3 ? dispatch<A_DENSE, ARITH_SPLIT3>(static_cast<hipStream_t>(stream), p, epilogue, a->tile, a->group_m)
                                             : dispatch<A_DENSE>(static_cast<hipStream_t>(stream), p, epilogue, a->tile, a->group_m);
     if (rc != 0 || !a->stats_out) return rc;
-    if (p.stats_in_epilogue) return vithip_rowstats_finalize_f32(stream, a->stats_partials, a->M, a->N, a->stats_out);
-    return vithip_rowstats_f32(stream, a->C, (size_t)a->ldc, a->stats_out, a->M, a->N);
+    const double eps = a->stats_eps == 0.0 ? VITHIP_LN_EPS : a->stats_eps;  // (the siblings refuse what is not finite and positive)
+    if (p.stats_in_epilogue) return vithip_rowstats_finalize_f32_eps(stream, a->stats_partials, a->M, a->N, a->stats_out, eps);
+    return vithip_rowstats_f32_eps(stream, a->C, (size_t)a->ldc, a->stats_out, a->M, a->N, eps);
 }
 
 int vithip_patch_embed_f32(vithip_stream_t stream, const float *images, const float *conv_w,

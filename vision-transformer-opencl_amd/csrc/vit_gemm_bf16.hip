@@ -32,6 +32,7 @@
 namespace {
 
 using vitgemm::erf_fp32;
+using vitgemm::quick_gelu;
 using vitgemm::tile_coords;
 using vitgemm::xcd_remap;
 
@@ -172,6 +173,7 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_bf16_nt_kernel(const Bf16Para
         // the same coalesced way.  Row pitches 520 B / 1040 B keep the block writes conflict-free.
         auto finish = [&](float t) {
             if constexpr (EPI == VITHIP_BF16_EPI_BF16_GELU) t = 0.5f * t * (1.0f + erf_fp32(t * 0.70710678118654752440f));
+            if constexpr (EPI == VITHIP_BF16_EPI_BF16_QGELU) t = quick_gelu(t);
             return t;
         };
         if constexpr (EPI == VITHIP_BF16_EPI_F32_RESIDUAL) {
@@ -419,7 +421,7 @@ int vithip_gemm_bf16(vithip_stream_t stream, const vithip_gemm_bf16_args *a) {
     // LayerNorm fold: consumer (ln_rows + ln_colsum on the bf16 epilogues) or producer (x16 + row_partials on the residual one)
     const bool ln_consumer = a->ln_rows || a->ln_colsum, ln_producer = a->x16 || a->row_partials;
     if (ln_consumer) {
-        if (!a->ln_rows || !a->ln_colsum || ln_producer || (a->epilogue != VITHIP_BF16_EPI_BF16 && a->epilogue != VITHIP_BF16_EPI_BF16_GELU) ||
+        if (!a->ln_rows || !a->ln_colsum || ln_producer || (a->epilogue != VITHIP_BF16_EPI_BF16 && a->epilogue != VITHIP_BF16_EPI_BF16_GELU && a->epilogue != VITHIP_BF16_EPI_BF16_QGELU) ||
             (reinterpret_cast<size_t>(a->ln_rows) & 7) || !aligned16(a->ln_colsum))
             return static_cast<int>(hipErrorInvalidValue);
         p.ln_rows = a->ln_rows;
@@ -450,7 +452,7 @@ int vithip_gemm_bf16(vithip_stream_t stream, const vithip_gemm_bf16_args *a) {
     if ((g_variant == 5 && a->epilogue != VITHIP_BF16_EPI_F32_RESIDUAL && !ln_consumer) || (a->epilogue >= 501 && a->epilogue <= 505))
         return vitgemm::launch_gemm_bf16_w4(s, p, a->epilogue, g_cus);  // four-wave experiment
 #endif
-    const bool pp_ok = p.K >= 2 * TBK && a->epilogue >= 0 && a->epilogue <= VITHIP_BF16_EPI_F32_RESIDUAL &&
+    const bool pp_ok = p.K >= 2 * TBK && ((a->epilogue >= 0 && a->epilogue <= VITHIP_BF16_EPI_F32_RESIDUAL) || a->epilogue == VITHIP_BF16_EPI_BF16_QGELU) &&
                        (size_t)p.lda * 2 * 256 < (1u << 31) && (size_t)p.ldw * 2 * 256 < (1u << 31);
     if ((variant >= 2 || ln_consumer || ln_producer) && (!pp_ok || variant == 1)) return static_cast<int>(hipErrorInvalidValue);
 #ifdef VIT_PROBES
@@ -473,6 +475,7 @@ int vithip_gemm_bf16(vithip_stream_t stream, const vithip_gemm_bf16_args *a) {
 #endif
         case VITHIP_BF16_EPI_BF16: hipLaunchKernelGGL(gemm_bf16_nt_kernel<VITHIP_BF16_EPI_BF16>, grid, block, 0, s, p); break;
         case VITHIP_BF16_EPI_BF16_GELU: hipLaunchKernelGGL(gemm_bf16_nt_kernel<VITHIP_BF16_EPI_BF16_GELU>, grid, block, 0, s, p); break;
+        case VITHIP_BF16_EPI_BF16_QGELU: hipLaunchKernelGGL(gemm_bf16_nt_kernel<VITHIP_BF16_EPI_BF16_QGELU>, grid, block, 0, s, p); break;
         case VITHIP_BF16_EPI_F32_RESIDUAL: hipLaunchKernelGGL(gemm_bf16_nt_kernel<VITHIP_BF16_EPI_F32_RESIDUAL>, grid, block, 0, s, p); break;
         default: return static_cast<int>(hipErrorInvalidValue);
     }

@@ -600,6 +600,7 @@ __global__ __launch_bounds__(PTHREADS) void gemm_bf16_pp_kernel(const Bf16Params
                         v[2 * jj] = f32x2{t4[0], t4[1]};
                         v[2 * jj + 1] = f32x2{t4[2], t4[3]};
                     }
+                    if constexpr (EPI == VITHIP_BF16_EPI_BF16_QGELU) quick_gelu_lockstep<4>(v);
                     if constexpr (EPI == VITHIP_BF16_EPI_BF16_GELU) {
 #if PP_GELU_LOCKSTEP == 4
                         gelu_bf16_lockstep<4>(v);
@@ -892,6 +893,7 @@ int launch_gemm_bf16_pp(hipStream_t s, const Bf16Params &p, int epilogue, int cu
         switch (epilogue) {
             case VITHIP_BF16_EPI_BF16: hipLaunchKernelGGL((gemm_bf16_pp_kernel<VITHIP_BF16_EPI_BF16, 0, 0, true>), grid, block, 0, s, p); break;
             case VITHIP_BF16_EPI_BF16_GELU: hipLaunchKernelGGL((gemm_bf16_pp_kernel<VITHIP_BF16_EPI_BF16_GELU, 0, 0, true>), grid, block, 0, s, p); break;
+            case VITHIP_BF16_EPI_BF16_QGELU: hipLaunchKernelGGL((gemm_bf16_pp_kernel<VITHIP_BF16_EPI_BF16_QGELU, 0, 0, true>), grid, block, 0, s, p); break;
             case VITHIP_BF16_EPI_F32_RESIDUAL: hipLaunchKernelGGL((gemm_bf16_pp_kernel<VITHIP_BF16_EPI_F32_RESIDUAL, 0, 0, true>), grid, block, 0, s, p); break;
             default: return static_cast<int>(hipErrorInvalidValue);
         }
@@ -900,6 +902,7 @@ int launch_gemm_bf16_pp(hipStream_t s, const Bf16Params &p, int epilogue, int cu
     switch (epilogue) {
         case VITHIP_BF16_EPI_BF16: hipLaunchKernelGGL(gemm_bf16_pp_kernel<VITHIP_BF16_EPI_BF16>, grid, block, 0, s, p); break;
         case VITHIP_BF16_EPI_BF16_GELU: hipLaunchKernelGGL(gemm_bf16_pp_kernel<VITHIP_BF16_EPI_BF16_GELU>, grid, block, 0, s, p); break;
+        case VITHIP_BF16_EPI_BF16_QGELU: hipLaunchKernelGGL(gemm_bf16_pp_kernel<VITHIP_BF16_EPI_BF16_QGELU>, grid, block, 0, s, p); break;
         case VITHIP_BF16_EPI_F32_RESIDUAL: hipLaunchKernelGGL(gemm_bf16_pp_kernel<VITHIP_BF16_EPI_F32_RESIDUAL>, grid, block, 0, s, p); break;
         case VITHIP_BF16_EPI_F32_EMBED: hipLaunchKernelGGL(gemm_bf16_pp_kernel<VITHIP_BF16_EPI_F32_EMBED>, grid, block, 0, s, p); break;
 #ifdef VIT_PROBES  // timing-only (DBG) and stamped / event-log (STAMP) instantiations: probe build only

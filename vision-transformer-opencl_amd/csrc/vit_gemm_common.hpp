@@ -19,7 +19,11 @@ constexpr int KALIGN = 32;  // K must be a multiple of this (covers every K step
 enum { A_DENSE = 0, A_PATCHES = 1 };
 // epilogue codes beyond the public three (vit_hip_kernels.h): the consumer side of the LayerNorm fold (ln_rows / ln_colsum set)
 // and the producer side: the residual epilogue that also leaves the row sums of what it stored (row_partials set; persistent walk)
-enum { EPI_BIAS_LN = 3, EPI_BIAS_GELU_LN = 4, EPI_RESIDUAL_STATS = 5 };
+enum { EPI_BIAS_LN = 3, EPI_BIAS_GELU_LN = 4, EPI_RESIDUAL_STATS = 5, EPI_BIAS_QGELU_LN = 7 /* 6 is VITHIP_EPI_BIAS_QGELU */ };
+// compile-time properties of an epilogue code: fold consumer; which activation follows the bias
+constexpr bool epi_is_fold(int epi) { return epi == EPI_BIAS_LN || epi == EPI_BIAS_GELU_LN || epi == EPI_BIAS_QGELU_LN; }
+constexpr bool epi_is_gelu(int epi) { return epi == VITHIP_EPI_BIAS_GELU || epi == EPI_BIAS_GELU_LN; }
+constexpr bool epi_is_qgelu(int epi) { return epi == VITHIP_EPI_BIAS_QGELU || epi == EPI_BIAS_QGELU_LN; }
 
 struct GemmParams {
     const float *A;
@@ -177,6 +181,51 @@ __device__ __forceinline__ void gelu_bf16_lockstep(f32x2 (&y)[NP]) {
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int v = 0; v < NP; ++v) y[v] = __builtin_elementwise_fma(-t[v], q[v], relu_keep_nan(y[v]));
+}
+
+// QuickGELU (CLIP): q(y) = y / (1 + exp(-1.702 y)), PyTorch's x * torch.sigmoid(1.702 * x).  The one sequence of every GEMM kernel,
+// fp32 and bf16 alike (include/vit_hip_kernels.h states it):
+//     t = y * QGELU_K         v_mul_f32     QGELU_K = fp32(-1.702 * log2 e)
+//     e = exp2(t)             v_exp_f32
+//     d = 1 + e               v_add_f32
+//     r = 1 / d               v_rcp_f32
+//     q = y * r               v_mul_f32
+// Five dependent steps against ~20 of gelu_erf.  +Inf: e = 0, r = 1, q = +Inf.  -Inf: e = Inf, r = 0, q = -Inf * 0 = NaN (as PyTorch).
+// NaN: NaN.  A large negative finite y: e overflows to Inf (or d is past 2^126 and v_rcp_f32 flushes its subnormal result), r = 0,
+// q = -0 -- never NaN: only an infinite y meets the zero.
+constexpr float QGELU_K = -2.4554669595930157f;
+__device__ __forceinline__ float quick_gelu(float y) {
+    const float e = __builtin_amdgcn_exp2f(y * QGELU_K);
+    return y * __builtin_amdgcn_rcpf(1.0f + e);
+}
+// The same values for NP pairs advanced TOGETHER, as gelu_bf16_lockstep / gelu_erf_x8 do it: the multiplies and the add in their packed
+// forms (v_pk_mul_f32 / v_pk_add_f32 round like the scalar ones), v_exp_f32 and v_rcp_f32 -- quarter-rate, one value each -- of all
+// the chains back to back behind the scheduling fences instead of one chain's exp waiting for its own rcp.
+template <int NP>
+__device__ __forceinline__ void quick_gelu_lockstep(f32x2 (&y)[NP]) {
+    f32x2 t[NP];
+#pragma unroll
+    for (int v = 0; v < NP; ++v) t[v] = y[v] * f32x2{QGELU_K, QGELU_K};
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int v = 0; v < NP; ++v) t[v] = f32x2{__builtin_amdgcn_exp2f(t[v].x), __builtin_amdgcn_exp2f(t[v].y)};
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int v = 0; v < NP; ++v) t[v] = f32x2{1.0f, 1.0f} + t[v];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int v = 0; v < NP; ++v) t[v] = f32x2{__builtin_amdgcn_rcpf(t[v].x), __builtin_amdgcn_rcpf(t[v].y)};
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int v = 0; v < NP; ++v) y[v] = y[v] * t[v];
+}
+__device__ __forceinline__ void quick_gelu_x8(float (&y)[8]) {
+    f32x2 yy[4];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) yy[v] = f32x2{y[2 * v], y[2 * v + 1]};
+    quick_gelu_lockstep<4>(yy);
+#pragma unroll
+    for (int v = 0; v < 4; ++v) y[2 * v] = yy[v].x, y[2 * v + 1] = yy[v].y;
 }
 
 // Workgroup id -> tile id such that ids sharing an XCD (id % 8) get consecutive tiles.
@@ -387,8 +436,8 @@ __device__ __forceinline__ void epilogue_store(const GemmParams &p, const f32x16
                                                const float (&bias_r)[WN / 32], int m0, int n0, int wm, int wn,
                                                int r, int h, const FoldOperands<WN / 32, WM / 32> &fold = FoldOperands<WN / 32, WM / 32>{}) {
     constexpr int TM = WM / 32, TN = WN / 32;
-    constexpr bool FOLD = EPI == EPI_BIAS_LN || EPI == EPI_BIAS_GELU_LN;
-    constexpr bool GELU = EPI == VITHIP_EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_LN;
+    constexpr bool FOLD = epi_is_fold(EPI);
+    constexpr bool GELU = epi_is_gelu(EPI), QGELU = epi_is_qgelu(EPI);
     constexpr int ST_NT = 2;  // cache policy of the bias / GELU stores: non-temporal (qkv and the hidden layer are read by the NEXT launch)
     const bool interior = (m0 + BM <= p.M) && (n0 + BN <= p.N);  // workgroup-uniform
     if (interior) {
@@ -429,6 +478,7 @@ __device__ __forceinline__ void epilogue_store(const GemmParams &p, const f32x16
 #pragma unroll
                         for (int q = 0; q < 8; ++q) y[q] = fold_scale(src[j][half * 8 + q], row_rstd[half * 8 + q], bias_r[j]);
                         if constexpr (GELU) gelu_erf_x8(y);
+                        if constexpr (QGELU) quick_gelu_x8(y);
 #pragma unroll
                         for (int q = 0; q < 8; ++q) {
                             const int v = half * 8 + q;
@@ -516,6 +566,7 @@ __device__ __forceinline__ void epilogue_store(const GemmParams &p, const f32x16
 #pragma unroll
                             for (int q = 0; q < 8; ++q) y[q] = acc[i][j][half * 8 + q] + bias_r[j];
                             if constexpr (GELU) gelu_erf_x8(y);
+                        if constexpr (QGELU) quick_gelu_x8(y);
 #pragma unroll
                             for (int q = 0; q < 8; ++q) {
                                 const int v = half * 8 + q;
@@ -550,6 +601,7 @@ __device__ __forceinline__ void epilogue_store(const GemmParams &p, const f32x16
                             p.C[((size_t)m + im + 1) * p.ldc + n] = y;
                         } else {
                             if constexpr (GELU) y = gelu_erf(y);
+                            if constexpr (QGELU) y = quick_gelu(y);
                             if constexpr (EPI == VITHIP_EPI_BIAS_RESIDUAL) y += p.R[(size_t)m * p.ldr + n];
                             p.C[(size_t)m * p.ldc + n] = y;
                         }

@@ -86,7 +86,7 @@ __global__ __launch_bounds__(256) void gemm_f32_nt_latency_kernel(const GemmPara
     // time IS its dependent chain, a load in the epilogue would be on it
     [[maybe_unused]] float colsum = 0.0f;
     [[maybe_unused]] f32x2 rowpair[4] = {};
-    if constexpr (EPI == EPI_BIAS_LN || EPI == EPI_BIAS_GELU_LN) {
+    if constexpr (epi_is_fold(EPI)) {
         colsum = (p.ln_colsum && n < p.N) ? p.ln_colsum[n] : 0.0f;  // NULL: centred weights
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
@@ -143,10 +143,11 @@ __global__ __launch_bounds__(256) void gemm_f32_nt_latency_kernel(const GemmPara
         const int m = m0 + 16 * wm + 4 * g + v;
         if (m < p.M && n < p.N) {
             float y;
-            if constexpr (EPI == EPI_BIAS_LN || EPI == EPI_BIAS_GELU_LN)  // LayerNorm fold, consumer (vit_gemm_common.hpp)
+            if constexpr (epi_is_fold(EPI))  // LayerNorm fold, consumer (vit_gemm_common.hpp)
                 y = fold_scale(fold_center(acc[v], rowpair[v].y, colsum), rowpair[v].x, bias);
             else y = acc[v] + bias;
-            if constexpr (EPI == VITHIP_EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_LN) y = gelu_erf(y);
+            if constexpr (epi_is_gelu(EPI)) y = gelu_erf(y);
+            if constexpr (epi_is_qgelu(EPI)) y = quick_gelu(y);
             if constexpr (EPI == VITHIP_EPI_BIAS_RESIDUAL) y += p.R[(size_t)m * p.ldr + n];
             p.C[(size_t)m * p.ldc + n] = y;
         }
@@ -166,6 +167,8 @@ int launch_gemm_f32_latency(hipStream_t stream, GemmParams &p, int epilogue) {
         case VITHIP_EPI_BIAS_RESIDUAL: hipLaunchKernelGGL(gemm_f32_nt_latency_kernel<VITHIP_EPI_BIAS_RESIDUAL>, grid, block, 0, stream, p); break;
         case EPI_BIAS_LN: hipLaunchKernelGGL(gemm_f32_nt_latency_kernel<EPI_BIAS_LN>, grid, block, 0, stream, p); break;
         case EPI_BIAS_GELU_LN: hipLaunchKernelGGL(gemm_f32_nt_latency_kernel<EPI_BIAS_GELU_LN>, grid, block, 0, stream, p); break;
+        case VITHIP_EPI_BIAS_QGELU: hipLaunchKernelGGL(gemm_f32_nt_latency_kernel<VITHIP_EPI_BIAS_QGELU>, grid, block, 0, stream, p); break;
+        case EPI_BIAS_QGELU_LN: hipLaunchKernelGGL(gemm_f32_nt_latency_kernel<EPI_BIAS_QGELU_LN>, grid, block, 0, stream, p); break;
         default: return static_cast<int>(hipErrorInvalidValue);
     }
     return static_cast<int>(hipGetLastError());

@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
     // alternating: wave 0 issues the next tile's copy as soon as ITS epilogue is done, while the other waves may still be reading
     // the finished tile's pairs; a buffer's next writer is two tiles (many barriers) later.  (An unknown younger operation in the
     // queue only makes the compiler's own counted waits wait for one load more than they need.)
-    constexpr bool FOLD = EPI == EPI_BIAS_LN || EPI == EPI_BIAS_GELU_LN;
+    constexpr bool FOLD = epi_is_fold(EPI);
     __shared__ __attribute__((aligned(16))) f32x2 fold_rows_lds[FOLD ? 2 * BM : 2];
     static_assert(!FOLD || BM == 128, "one 16-byte lane copy of 64 lanes = 128 rows");
     float *const As0 = lds;
@@ -588,6 +588,12 @@ int launch_persistent_tile(hipStream_t stream, GemmParams &p, int epilogue, int 
             case EPI_BIAS_GELU_LN:
                 hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_GELU_LN, false, true, 0, ARITH, WIMG>), grid, block, 0, stream, p);
                 break;
+            case VITHIP_EPI_BIAS_QGELU:
+                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_QGELU, false, true, 0, ARITH, WIMG>), grid, block, 0, stream, p);
+                break;
+            case EPI_BIAS_QGELU_LN:
+                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_QGELU_LN, false, true, 0, ARITH, WIMG>), grid, block, 0, stream, p);
+                break;
             case EPI_RESIDUAL_STATS:
                 hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_RESIDUAL_STATS, false, true, 0, ARITH, WIMG>), grid, block, 0, stream, p);
                 break;
@@ -611,6 +617,12 @@ int launch_persistent_tile(hipStream_t stream, GemmParams &p, int epilogue, int 
             break;
         case EPI_BIAS_GELU_LN:
             hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_GELU_LN, false, false, 0, ARITH, WIMG>), grid, block, 0, stream, p);
+            break;
+        case VITHIP_EPI_BIAS_QGELU:
+            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_QGELU, false, false, 0, ARITH, WIMG>), grid, block, 0, stream, p);
+            break;
+        case EPI_BIAS_QGELU_LN:
+            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_QGELU_LN, false, false, 0, ARITH, WIMG>), grid, block, 0, stream, p);
             break;
         case EPI_RESIDUAL_STATS:
             hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_RESIDUAL_STATS, false, false, 0, ARITH, WIMG>), grid, block, 0, stream, p);

@@ -5,7 +5,8 @@
 //   rowstats_bf16_kernel     first LayerNorm of the stack: x16 = bf16(x), rows = (rstd, mean*rstd)   (one wave per row, HBM-bound)
 //   rowstats_finalize_kernel per residual GEMM: strips x (sum, sum of squares) -> (rstd, mean*rstd), fixed summation order
 //
-// Statistics follow ViT_seq.c:103-121 as csrc/vit_rowops.hip does: var = E[x^2] - mean^2, 1/sqrtf((double)var + 1e-6).
+// Statistics follow ViT_seq.c:103-121 as csrc/vit_rowops.hip does: var = E[x^2] - mean^2, 1/sqrtf((double)var + eps), eps the double
+// the caller passes (the entry points without _eps pass VITHIP_LN_EPS, the double 1e-6).
 #include <hip/hip_runtime.h>
 
 #include "vit_hip_kernels.h"
@@ -19,10 +20,10 @@ using vit_row::wave_sum;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 
-__device__ __forceinline__ f32x2 finish(float s, float ss, int dim) {
+__device__ __forceinline__ f32x2 finish(float s, float ss, int dim, double eps) {
     const float mean = s / (float)dim;
     const float var = ss / (float)dim - mean * mean;
-    const float inv_std = 1.0f / sqrtf((float)((double)var + 1e-6));
+    const float inv_std = 1.0f / sqrtf((float)((double)var + eps));
     return f32x2{inv_std, mean * inv_std};
 }
 
@@ -61,12 +62,12 @@ __global__ __launch_bounds__(256) void ln_fold_weights_kernel(const float *__res
 
 // (rstd, mean) for the fp32 fold: every operation rounded on its own -- contraction is switched off for the body (HIP's
 // __fmul_rn & co. are plain operators that the compiler may still fuse; its __fsqrt_rn is the approximate square root)
-__device__ __forceinline__ f32x2 finish_f32(float s, float ss, int dim) {
+__device__ __forceinline__ f32x2 finish_f32(float s, float ss, int dim, double eps) {
 #pragma clang fp contract(off)
     const float mean = s / (float)dim;
     const float sq = mean * mean;
     const float var = ss / (float)dim - sq;
-    const float inv_std = 1.0f / __builtin_sqrtf((float)((double)var + 1e-6));
+    const float inv_std = 1.0f / __builtin_sqrtf((float)((double)var + eps));
     return f32x2{inv_std, mean};
 }
 
@@ -133,7 +134,7 @@ __global__ __launch_bounds__(256) void ln_fold_weights_f32_kernel(const float *_
 // halves of the wave on two strips at a time.  NP = strip pairs per row (0: run-time count).
 template <int NP>
 __global__ __launch_bounds__(256) void rowstats_f32_kernel(const float *__restrict__ x, size_t ldx, float *__restrict__ rows_out,
-                                                           int rows, int dim) {
+                                                           int rows, int dim, double eps) {
     const int lane = threadIdx.x & 63, l = lane & 31, half = lane >> 5;
     const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
     const int nwaves = (gridDim.x * 256) >> 6;
@@ -178,13 +179,13 @@ __global__ __launch_bounds__(256) void rowstats_f32_kernel(const float *__restri
                 pair(k, ok ? src[strip * 64 + l] : 0.f, ok ? src[strip * 64 + 32 + l] : 0.f);
             }
         }
-        if (lane == 0) *reinterpret_cast<f32x2 *>(rows_out + (size_t)row * 2) = finish_f32(s, ss, dim);
+        if (lane == 0) *reinterpret_cast<f32x2 *>(rows_out + (size_t)row * 2) = finish_f32(s, ss, dim, eps);
     }
 }
 
 template <int NVEC>
 __global__ __launch_bounds__(256) void rowstats_bf16_kernel(const float *__restrict__ x, size_t ldx, unsigned short *__restrict__ x16,
-                                                            size_t ldx16, float *__restrict__ rows_out, int rows, int dim) {
+                                                            size_t ldx16, float *__restrict__ rows_out, int rows, int dim, double eps) {
     const int lane = threadIdx.x & 63;
     const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
     const int nwaves = (gridDim.x * 256) >> 6;
@@ -207,16 +208,16 @@ __global__ __launch_bounds__(256) void rowstats_bf16_kernel(const float *__restr
         }
         s = wave_sum(s);
         ss = wave_sum(ss);
-        if (lane == 0) *reinterpret_cast<f32x2 *>(rows_out + (size_t)row * 2) = finish(s, ss, dim);
+        if (lane == 0) *reinterpret_cast<f32x2 *>(rows_out + (size_t)row * 2) = finish(s, ss, dim, eps);
     }
 }
 
 // Strips x (sum, sum of squares) of a residual GEMM's epilogue -> one pair per row, strips in ascending column order, the same for
 // every row and every launch.  FINISH = finish: (rstd, mean * rstd).  FINISH = finish_f32, the fp32 fold (csrc/vit_gemm_common.hpp,
 // epilogue_store_residual_stats): (rstd, mean) as vithip_rowstats_f32 finishes them, the same bits as that kernel on the stored rows.
-template <f32x2 (*FINISH)(float, float, int)>
+template <f32x2 (*FINISH)(float, float, int, double)>
 __global__ __launch_bounds__(256) void rowstats_finalize_kernel(const float *__restrict__ partials, int strips, int rows, int dim,
-                                                                float *__restrict__ rows_out) {
+                                                                float *__restrict__ rows_out, double eps) {
     const int row = blockIdx.x * 256 + threadIdx.x;
     if (row >= rows) return;
     float s = 0.f, ss = 0.f;
@@ -225,7 +226,7 @@ __global__ __launch_bounds__(256) void rowstats_finalize_kernel(const float *__r
         s += v.x;
         ss += v.y;
     }
-    *reinterpret_cast<f32x2 *>(rows_out + (size_t)row * 2) = FINISH(s, ss, dim);
+    *reinterpret_cast<f32x2 *>(rows_out + (size_t)row * 2) = FINISH(s, ss, dim, eps);
 }
 
 __global__ __launch_bounds__(256) void gather_rows_kernel(const float *__restrict__ src, size_t src_stride, float *__restrict__ dst,
@@ -278,51 +279,66 @@ int vithip_ln_fold_weights_f32_centered(vithip_stream_t stream, const float *W, 
     return static_cast<int>(hipGetLastError());
 }
 
-int vithip_rowstats_f32(vithip_stream_t stream, const float *x, size_t ldx, float *rows_out, int rows, int dim) {
+static bool eps_ok(double eps) { return eps > 0.0 && eps < 1.0e300; }  // finite and positive (NaN fails both)
+
+int vithip_rowstats_f32_eps(vithip_stream_t stream, const float *x, size_t ldx, float *rows_out, int rows, int dim, double eps) {
     // not vit_row::rows_ok: the kernel loads single floats (x 4-byte aligned, any ldx >= dim) in whole 64-column strips (dim % 64)
     if (!x || !rows_out || rows <= 0 || dim <= 0 || dim % 64 || dim > 2048 || ldx < (size_t)dim ||
-        (reinterpret_cast<size_t>(x) & 3) || (reinterpret_cast<size_t>(rows_out) & 7))
+        (reinterpret_cast<size_t>(x) & 3) || (reinterpret_cast<size_t>(rows_out) & 7) || !eps_ok(eps))
         return static_cast<int>(hipErrorInvalidValue);
     const dim3 grid(vit_row::grid_for_rows(rows)), block(256);
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch ((dim / 64 + 1) / 2) {  // strip pairs; a rule of this kernel, not the NVEC of the row schedule
-        case 2: hipLaunchKernelGGL(rowstats_f32_kernel<2>, grid, block, 0, s, x, ldx, rows_out, rows, dim); break;  // 192, 256
-        case 6: hipLaunchKernelGGL(rowstats_f32_kernel<6>, grid, block, 0, s, x, ldx, rows_out, rows, dim); break;  // 768
-        case 8: hipLaunchKernelGGL(rowstats_f32_kernel<8>, grid, block, 0, s, x, ldx, rows_out, rows, dim); break;  // 1024
-        default: hipLaunchKernelGGL(rowstats_f32_kernel<0>, grid, block, 0, s, x, ldx, rows_out, rows, dim); break;
+        case 2: hipLaunchKernelGGL(rowstats_f32_kernel<2>, grid, block, 0, s, x, ldx, rows_out, rows, dim, eps); break;  // 192, 256
+        case 6: hipLaunchKernelGGL(rowstats_f32_kernel<6>, grid, block, 0, s, x, ldx, rows_out, rows, dim, eps); break;  // 768
+        case 8: hipLaunchKernelGGL(rowstats_f32_kernel<8>, grid, block, 0, s, x, ldx, rows_out, rows, dim, eps); break;  // 1024
+        default: hipLaunchKernelGGL(rowstats_f32_kernel<0>, grid, block, 0, s, x, ldx, rows_out, rows, dim, eps); break;
     }
     return static_cast<int>(hipGetLastError());
 }
+int vithip_rowstats_f32(vithip_stream_t stream, const float *x, size_t ldx, float *rows_out, int rows, int dim) {
+    return vithip_rowstats_f32_eps(stream, x, ldx, rows_out, rows, dim, VITHIP_LN_EPS);
+}
 
-int vithip_rowstats_bf16(vithip_stream_t stream, const float *x, size_t ldx, unsigned short *x16, size_t ldx16, float *rows_out,
-                         int rows, int dim) {
+int vithip_rowstats_bf16_eps(vithip_stream_t stream, const float *x, size_t ldx, unsigned short *x16, size_t ldx16, float *rows_out,
+                             int rows, int dim, double eps) {
     // x16 takes 8-byte stores of four bf16: 8-byte aligned, not the 16 of vit_row::rows_ok
     if (!x || !x16 || !rows_out || rows <= 0 || !vit_row::rows_ok(x, ldx, dim) || ldx16 % 4 || ldx16 < (size_t)dim ||
-        (reinterpret_cast<size_t>(x16) & 7) || (reinterpret_cast<size_t>(rows_out) & 7))
+        (reinterpret_cast<size_t>(x16) & 7) || (reinterpret_cast<size_t>(rows_out) & 7) || !eps_ok(eps))
         return static_cast<int>(hipErrorInvalidValue);
     return vit_row::dispatch_nvec(dim, [&](auto nvec) {
         hipLaunchKernelGGL(rowstats_bf16_kernel<decltype(nvec)::value>, dim3(vit_row::grid_for_rows(rows)), dim3(256), 0,
-                           static_cast<hipStream_t>(stream), x, ldx, x16, ldx16, rows_out, rows, dim);
+                           static_cast<hipStream_t>(stream), x, ldx, x16, ldx16, rows_out, rows, dim, eps);
         return static_cast<int>(hipGetLastError());
     });
 }
-
-int vithip_rowstats_finalize(vithip_stream_t stream, const float *partials, int strips, int rows, int dim, float *rows_out) {
-    if (!partials || !rows_out || strips <= 0 || rows <= 0 || dim <= 0 || (reinterpret_cast<size_t>(partials) & 7) ||
-        (reinterpret_cast<size_t>(rows_out) & 7))
-        return static_cast<int>(hipErrorInvalidValue);
-    hipLaunchKernelGGL(rowstats_finalize_kernel<finish>, dim3((rows + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), partials,
-                       strips, rows, dim, rows_out);
-    return static_cast<int>(hipGetLastError());
+int vithip_rowstats_bf16(vithip_stream_t stream, const float *x, size_t ldx, unsigned short *x16, size_t ldx16, float *rows_out,
+                         int rows, int dim) {
+    return vithip_rowstats_bf16_eps(stream, x, ldx, x16, ldx16, rows_out, rows, dim, VITHIP_LN_EPS);
 }
 
-int vithip_rowstats_finalize_f32(vithip_stream_t stream, const float *partials, int rows, int dim, float *rows_out) {
+int vithip_rowstats_finalize_eps(vithip_stream_t stream, const float *partials, int strips, int rows, int dim, float *rows_out, double eps) {
+    if (!partials || !rows_out || strips <= 0 || rows <= 0 || dim <= 0 || (reinterpret_cast<size_t>(partials) & 7) ||
+        (reinterpret_cast<size_t>(rows_out) & 7) || !eps_ok(eps))
+        return static_cast<int>(hipErrorInvalidValue);
+    hipLaunchKernelGGL(rowstats_finalize_kernel<finish>, dim3((rows + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), partials,
+                       strips, rows, dim, rows_out, eps);
+    return static_cast<int>(hipGetLastError());
+}
+int vithip_rowstats_finalize(vithip_stream_t stream, const float *partials, int strips, int rows, int dim, float *rows_out) {
+    return vithip_rowstats_finalize_eps(stream, partials, strips, rows, dim, rows_out, VITHIP_LN_EPS);
+}
+
+int vithip_rowstats_finalize_f32_eps(vithip_stream_t stream, const float *partials, int rows, int dim, float *rows_out, double eps) {
     if (!partials || !rows_out || rows <= 0 || dim <= 0 || dim % 64 || (reinterpret_cast<size_t>(partials) & 7) ||
-        (reinterpret_cast<size_t>(rows_out) & 7))
+        (reinterpret_cast<size_t>(rows_out) & 7) || !eps_ok(eps))
         return static_cast<int>(hipErrorInvalidValue);
     hipLaunchKernelGGL(rowstats_finalize_kernel<finish_f32>, dim3((rows + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), partials,
-                       dim / 64, rows, dim, rows_out);
+                       dim / 64, rows, dim, rows_out, eps);
     return static_cast<int>(hipGetLastError());
+}
+int vithip_rowstats_finalize_f32(vithip_stream_t stream, const float *partials, int rows, int dim, float *rows_out) {
+    return vithip_rowstats_finalize_f32_eps(stream, partials, rows, dim, rows_out, VITHIP_LN_EPS);
 }
 
 int vithip_gather_rows_f32(vithip_stream_t stream, const float *src, size_t src_stride, float *dst, size_t dst_stride, int rows,

@@ -3,7 +3,7 @@
 //   out[i][:] = gamma * ( 1/(tokens - first_tok) * sum_{t = first_tok}^{tokens-1} (x[i][t][:] - mean_t) * inv_std_t ) + beta
 //
 // with the per-row statistics of layernorm_f32_kernel (csrc/vit_rowops.hip) to the bit: the same lanes add the same elements in
-// the same order, mean = s / dim, var = ss / dim - mean * mean, inv_std = 1 / sqrtf((double)var + 1e-6)
+// the same order, mean = s / dim, var = ss / dim - mean * mean, inv_std = 1 / sqrtf((double)var + eps)
 // (tests/test_gpu_pool_kernel.py::test_one_pooled_row_is_the_layernorm_row_bit_for_bit).  gamma and beta are
 // applied ONCE, to the pooled (x - mean) * inv_std: the mean over tokens is linear, so this is the mean of the LayerNorm rows
 // with two fewer operations per element in the streaming pass and nothing but x read there.  One choice for every shape.
@@ -51,7 +51,7 @@ constexpr int POOL_SEG = POOL_WAVES * POOL_ROWS_PER_WAVE;  // token rows per wor
 // grid.x = images * segs; partial [images][segs][dim].  NORM: a row contributes (v - mean) * inv_std of its own statistics, else v.
 template <int NVEC, bool NORM>
 __global__ __launch_bounds__(POOL_THREADS) void pool_partial_kernel(const float *__restrict__ x, size_t ldx, float *__restrict__ partial,
-                                                                     int tokens, int first_tok, int dim, int segs) {
+                                                                     int tokens, int first_tok, int dim, int segs, double eps) {
     __shared__ f32x4 red[POOL_WAVES - 1][NVEC * 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int image = blockIdx.x / segs, seg = blockIdx.x - image * segs;
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(POOL_THREADS) void pool_partial_kernel(const float 
             ss = wave_sum(ss);
             const float mean = s / (float)dim;
             const float var = ss / (float)dim - mean * mean;
-            const float inv_std = 1.0f / sqrtf((float)((double)var + 1e-6));
+            const float inv_std = 1.0f / sqrtf((float)((double)var + eps));
             if (live) {
 #pragma unroll
                 for (int i = 0; i < NVEC; ++i)
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(POOL_THREADS) void l2_normalize_rows_kernel(float *
 template <int NVEC>
 __global__ __launch_bounds__(64) void pool_layernorm_finish_kernel(const float *__restrict__ partial, float *__restrict__ out, size_t ldo,
                                                                    const float *__restrict__ gamma, const float *__restrict__ beta, int dim,
-                                                                   int segs, float count) {
+                                                                   int segs, float count, double eps) {
     __shared__ f32x4 pooled[NVEC * 64];
     const int lane = threadIdx.x;
     const float *src = partial + (size_t)blockIdx.x * segs * dim;
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(64) void pool_layernorm_finish_kernel(const float *
     __syncthreads();
     f32x4 v[NVEC];
     float mean, inv_std;
-    vit_row::row_stats<NVEC>(reinterpret_cast<const float *>(pooled), dim, lane, v, mean, inv_std);
+    vit_row::row_stats<NVEC>(reinterpret_cast<const float *>(pooled), dim, lane, v, mean, inv_std, eps);
 #pragma unroll
     for (int i = 0; i < NVEC; ++i) {
         const int c = (i * 64 + lane) * 4;
@@ -230,9 +230,10 @@ bool pool_args_ok(const float *x, size_t ldx, const float *out, size_t ldo, cons
 }
 
 template <int NVEC, bool NORM>
-int launch_partial(hipStream_t s, const float *x, size_t ldx, float *partial, int images, int tokens, int first_tok, int dim, int segs) {
+int launch_partial(hipStream_t s, const float *x, size_t ldx, float *partial, int images, int tokens, int first_tok, int dim, int segs,
+                   double eps) {
     hipLaunchKernelGGL((pool_partial_kernel<NVEC, NORM>), dim3((unsigned)images * (unsigned)segs), dim3(POOL_THREADS), 0, s, x, ldx,
-                       partial, tokens, first_tok, dim, segs);
+                       partial, tokens, first_tok, dim, segs, eps);
     return static_cast<int>(hipGetLastError());
 }
 
@@ -257,15 +258,16 @@ int vithip_l2_normalize_rows_f32(vithip_stream_t stream, float *x, size_t ldx, i
     return l2_launch(static_cast<hipStream_t>(stream), x, ldx, rows, dim);
 }
 
-int vithip_layernorm_pool_f32(vithip_stream_t stream, const float *x, size_t ldx, float *out, size_t ldo, const float *gamma,
-                              const float *beta, int images, int tokens, int first_tok, int dim, int l2_normalize, float *workspace) {
+int vithip_layernorm_pool_f32_eps(vithip_stream_t stream, const float *x, size_t ldx, float *out, size_t ldo, const float *gamma,
+                                  const float *beta, int images, int tokens, int first_tok, int dim, int l2_normalize, float *workspace,
+                                  double eps) {
     if (!pool_args_ok(x, ldx, out, ldo, gamma, beta, false, images, tokens, first_tok, dim, workspace) ||
-        (l2_normalize != 0 && l2_normalize != 1))
+        (l2_normalize != 0 && l2_normalize != 1) || !(eps > 0.0) || !(eps < 1.0e300))
         return static_cast<int>(hipErrorInvalidValue);
     const int segs = pool_segs(tokens, first_tok);
     hipStream_t s = static_cast<hipStream_t>(stream);
     int rc = vit_row::dispatch_nvec(dim, [&](auto nvec) {
-        return launch_partial<decltype(nvec)::value, true>(s, x, ldx, workspace, images, tokens, first_tok, dim, segs);
+        return launch_partial<decltype(nvec)::value, true>(s, x, ldx, workspace, images, tokens, first_tok, dim, segs, eps);
     });
     if (rc) return rc;
     hipLaunchKernelGGL(layernorm_pool_finish_kernel, dim3(images), dim3(POOL_THREADS), 0, s, workspace, out, ldo, gamma, beta, dim, segs,
@@ -274,25 +276,34 @@ int vithip_layernorm_pool_f32(vithip_stream_t stream, const float *x, size_t ldx
     if (rc || !l2_normalize) return rc;
     return l2_launch(s, out, ldo, images, dim);
 }
+int vithip_layernorm_pool_f32(vithip_stream_t stream, const float *x, size_t ldx, float *out, size_t ldo, const float *gamma,
+                              const float *beta, int images, int tokens, int first_tok, int dim, int l2_normalize, float *workspace) {
+    return vithip_layernorm_pool_f32_eps(stream, x, ldx, out, ldo, gamma, beta, images, tokens, first_tok, dim, l2_normalize, workspace,
+                                         VITHIP_LN_EPS);
+}
 
 size_t vithip_pool_layernorm_f32_workspace_floats(int images, int tokens, int first_tok, int dim) {
     return vithip_layernorm_pool_f32_workspace_floats(images, tokens, first_tok, dim);  // the same partial rows
 }
 
-int vithip_pool_layernorm_f32(vithip_stream_t stream, const float *x, size_t ldx, float *out, size_t ldo, const float *gamma,
-                              const float *beta, int images, int tokens, int first_tok, int dim, float *workspace) {
-    if (!pool_args_ok(x, ldx, out, ldo, gamma, beta, true, images, tokens, first_tok, dim, workspace))
+int vithip_pool_layernorm_f32_eps(vithip_stream_t stream, const float *x, size_t ldx, float *out, size_t ldo, const float *gamma,
+                                  const float *beta, int images, int tokens, int first_tok, int dim, float *workspace, double eps) {
+    if (!pool_args_ok(x, ldx, out, ldo, gamma, beta, true, images, tokens, first_tok, dim, workspace) || !(eps > 0.0) || !(eps < 1.0e300))
         return static_cast<int>(hipErrorInvalidValue);
     const int segs = pool_segs(tokens, first_tok);
     hipStream_t s = static_cast<hipStream_t>(stream);
     return vit_row::dispatch_nvec(dim, [&](auto nvec) {
         constexpr int NVEC = decltype(nvec)::value;
-        const int rc = launch_partial<NVEC, false>(s, x, ldx, workspace, images, tokens, first_tok, dim, segs);
+        const int rc = launch_partial<NVEC, false>(s, x, ldx, workspace, images, tokens, first_tok, dim, segs, eps);
         if (rc) return rc;
         hipLaunchKernelGGL(pool_layernorm_finish_kernel<NVEC>, dim3(images), dim3(64), 0, s, workspace, out, ldo, gamma, beta, dim, segs,
-                           (float)(tokens - first_tok));
+                           (float)(tokens - first_tok), eps);
         return static_cast<int>(hipGetLastError());
     });
+}
+int vithip_pool_layernorm_f32(vithip_stream_t stream, const float *x, size_t ldx, float *out, size_t ldo, const float *gamma,
+                              const float *beta, int images, int tokens, int first_tok, int dim, float *workspace) {
+    return vithip_pool_layernorm_f32_eps(stream, x, ldx, out, ldo, gamma, beta, images, tokens, first_tok, dim, workspace, VITHIP_LN_EPS);
 }
 
 }  // extern "C"

@@ -6,7 +6,8 @@
 //
 // LayerNorm of a row (row_stats, row_affine; every kernel that must give the bits of vithip_layernorm_f32 calls these two): the
 // two sums are added per lane in vector order, then across the wave by xor shuffles from 32 down to 1;
-//   mean = sum / dim, var = sum_sq / dim - mean * mean, inv_std = 1 / sqrtf((float)((double)var + 1e-6))      (ViT_seq.c:103-121)
+//   mean = sum / dim, var = sum_sq / dim - mean * mean, inv_std = 1 / sqrtf((float)((double)var + eps))       (ViT_seq.c:103-121)
+// with eps a DOUBLE the caller passes (VITHIP_LN_EPS = the double 1e-6 of the reference; added in double before the cast)
 // and an element becomes (x - mean) * inv_std * gamma + beta.  Whoever changes an expression here changes every caller alike.
 //
 // Softmax of a row by a whole workgroup (softmax_row_stats): the one order of operations behind vithip_softmax_top1_f32 and the
@@ -40,7 +41,7 @@ __device__ __forceinline__ float wave_max(float v) {
 // Reads the row at src into v and leaves its statistics; every lane of the wave must call it.
 template <int NVEC>
 __device__ __forceinline__ void row_stats(const float *__restrict__ src, int dim, int lane, f32x4 (&v)[NVEC], float &mean,
-                                          float &inv_std) {
+                                          float &inv_std, double eps) {
     float s = 0.0f, ss = 0.0f;
 #pragma unroll
     for (int i = 0; i < NVEC; ++i) {
@@ -55,7 +56,7 @@ __device__ __forceinline__ void row_stats(const float *__restrict__ src, int dim
     ss = wave_sum(ss);
     mean = s / (float)dim;
     const float var = ss / (float)dim - mean * mean;
-    inv_std = 1.0f / sqrtf((float)((double)var + 1e-6));
+    inv_std = 1.0f / sqrtf((float)((double)var + eps));
 }
 
 // Four normalised elements from four of the row's, with the gamma and beta of their columns.

@@ -25,11 +25,13 @@ typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 // OUT = float, or unsigned short (bf16 bits) for the bf16 variant of the forward: statistics and the
 // affine map are fp32 either way, only the store rounds.
 template <int NVEC, typename OUT>
-__global__ __launch_bounds__(LN_THREADS) void layernorm_f32_kernel(const float *__restrict__ x, size_t ldx,
-                                                                   OUT *__restrict__ y, size_t ldy,
+// x and y carry no __restrict__: y may BE x (same base, ldy == ldx, OUT = float).  A wave reads its whole row into registers in
+// row_stats before row_affine stores any of it, and rows do not overlap each other, so the in-place form is structurally safe.
+__global__ __launch_bounds__(LN_THREADS) void layernorm_f32_kernel(const float *x, size_t ldx,
+                                                                   OUT *y, size_t ldy,
                                                                    const float *__restrict__ gamma,
                                                                    const float *__restrict__ beta,
-                                                                   int rows, int dim) {
+                                                                   int rows, int dim, double eps) {
     const int lane = threadIdx.x & 63;
     const int wave = (blockIdx.x * LN_THREADS + threadIdx.x) >> 6;
     const int nwaves = (gridDim.x * LN_THREADS) >> 6;
@@ -37,7 +39,7 @@ __global__ __launch_bounds__(LN_THREADS) void layernorm_f32_kernel(const float *
         const float *src = x + (size_t)row * ldx;
         f32x4 v[NVEC];
         float mean, inv_std;
-        vit_row::row_stats<NVEC>(src, dim, lane, v, mean, inv_std);
+        vit_row::row_stats<NVEC>(src, dim, lane, v, mean, inv_std, eps);
         OUT *dst = y + (size_t)row * ldy;
 #pragma unroll
         for (int i = 0; i < NVEC; ++i) {
@@ -101,14 +103,21 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_top1_f32_kernel(const floa
 
 template <typename OUT>
 int layernorm_dispatch(vithip_stream_t stream, const float *x, size_t ldx, OUT *y, size_t ldy, const float *gamma,
-                       const float *beta, int rows, int dim) {
+                       const float *beta, int rows, int dim, double eps) {
     // y is held to the rule of x whatever OUT is: a bf16 destination too is 16-byte aligned with ldy % 4 == 0
     if (!x || !y || !gamma || !beta || rows <= 0 || !vit_row::rows_ok(x, ldx, dim) || !vit_row::rows_ok(y, ldy, dim) ||
-        !vit_row::aligned16(gamma) || !vit_row::aligned16(beta))
+        !vit_row::aligned16(gamma) || !vit_row::aligned16(beta) || !(eps > 0.0) || !(eps < 1.0e300))
         return static_cast<int>(hipErrorInvalidValue);
+    // in place (y == x, ldy == ldx, fp32 out) or disjoint: anything in between would read rows another wave has written
+    {
+        const char *xb = reinterpret_cast<const char *>(x), *yb = reinterpret_cast<const char *>(y);
+        const size_t xs = ((size_t)(rows - 1) * ldx + dim) * sizeof(float), ys = ((size_t)(rows - 1) * ldy + dim) * sizeof(OUT);
+        const bool in_place = xb == yb && ldx == ldy && sizeof(OUT) == sizeof(float);
+        if (!in_place && xb < yb + ys && yb < xb + xs) return static_cast<int>(hipErrorInvalidValue);
+    }
     return vit_row::dispatch_nvec(dim, [&](auto nvec) {
         hipLaunchKernelGGL((layernorm_f32_kernel<decltype(nvec)::value, OUT>), dim3(vit_row::grid_for_rows(rows)), dim3(LN_THREADS), 0,
-                           static_cast<hipStream_t>(stream), x, ldx, y, ldy, gamma, beta, rows, dim);
+                           static_cast<hipStream_t>(stream), x, ldx, y, ldy, gamma, beta, rows, dim, eps);
         return static_cast<int>(hipGetLastError());
     });
 }
@@ -117,14 +126,22 @@ int layernorm_dispatch(vithip_stream_t stream, const float *x, size_t ldx, OUT *
 
 extern "C" {
 
+int vithip_layernorm_f32_eps(vithip_stream_t stream, const float *x, size_t ldx, float *y, size_t ldy,
+                             const float *gamma, const float *beta, int rows, int dim, double eps) {
+    return layernorm_dispatch<float>(stream, x, ldx, y, ldy, gamma, beta, rows, dim, eps);
+}
 int vithip_layernorm_f32(vithip_stream_t stream, const float *x, size_t ldx, float *y, size_t ldy,
                          const float *gamma, const float *beta, int rows, int dim) {
-    return layernorm_dispatch<float>(stream, x, ldx, y, ldy, gamma, beta, rows, dim);
+    return vithip_layernorm_f32_eps(stream, x, ldx, y, ldy, gamma, beta, rows, dim, VITHIP_LN_EPS);
 }
 
+int vithip_layernorm_f32_bf16out_eps(vithip_stream_t stream, const float *x, size_t ldx, unsigned short *y, size_t ldy,
+                                     const float *gamma, const float *beta, int rows, int dim, double eps) {
+    return layernorm_dispatch<unsigned short>(stream, x, ldx, y, ldy, gamma, beta, rows, dim, eps);
+}
 int vithip_layernorm_f32_bf16out(vithip_stream_t stream, const float *x, size_t ldx, unsigned short *y, size_t ldy,
                                  const float *gamma, const float *beta, int rows, int dim) {
-    return layernorm_dispatch<unsigned short>(stream, x, ldx, y, ldy, gamma, beta, rows, dim);
+    return vithip_layernorm_f32_bf16out_eps(stream, x, ldx, y, ldy, gamma, beta, rows, dim, VITHIP_LN_EPS);
 }
 
 int vithip_softmax_top1_f32(vithip_stream_t stream, const float *logits, int ld_logits, float *probs,

@@ -39,11 +39,11 @@ __host__ __device__ constexpr int map_tile_tokens(int dim) { return dim <= 1024 
 // One row: source -> destination, normalised with the row's own statistics (NORM) or copied.  Every lane of the wave calls it.
 template <int NVEC, bool NORM>
 __device__ __forceinline__ void tap_row(const float *__restrict__ src, float *__restrict__ dst, const float *__restrict__ gamma,
-                                        const float *__restrict__ beta, int dim, int lane) {
+                                        const float *__restrict__ beta, int dim, int lane, double eps) {
     f32x4 v[NVEC];
     if constexpr (NORM) {
         float mean, inv_std;
-        vit_row::row_stats<NVEC>(src, dim, lane, v, mean, inv_std);
+        vit_row::row_stats<NVEC>(src, dim, lane, v, mean, inv_std, eps);
 #pragma unroll
         for (int i = 0; i < NVEC; ++i) {
             const int c = (i * 64 + lane) * 4;
@@ -67,7 +67,7 @@ template <int NVEC, bool NORM>
 __global__ __launch_bounds__(TAP_THREADS) void tap_rows_kernel(const float *__restrict__ x, size_t ldx, float *__restrict__ out,
                                                                size_t out_image_stride, const float *__restrict__ gamma,
                                                                const float *__restrict__ beta, int rows, int rows_per_image,
-                                                               int first_tok, int tokens, int dim) {
+                                                               int first_tok, int tokens, int dim, double eps) {
     const int lane = threadIdx.x & 63;
     const int wave = (blockIdx.x * TAP_THREADS + threadIdx.x) >> 6;
     const int nwaves = (gridDim.x * TAP_THREADS) >> 6;
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(TAP_THREADS) void tap_rows_kernel(const float *__re
         if (r >= rows_per_image) { r -= rows_per_image; ++image; }
         const float *src = x + ((size_t)image * tokens + first_tok + r) * ldx;
         float *dst = out + (size_t)image * out_image_stride + (size_t)r * dim;
-        tap_row<NVEC, NORM>(src, dst, gamma, beta, dim, lane);
+        tap_row<NVEC, NORM>(src, dst, gamma, beta, dim, lane, eps);
     }
 }
 
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(TAP_THREADS) void tap_rows_kernel(const float *__re
 template <int NVEC, bool NORM, bool VEC>
 __global__ __launch_bounds__(map_threads(NVEC)) void tap_map_kernel(const float *__restrict__ x, size_t ldx, float *__restrict__ out,
                                                               size_t out_image_stride, const float *__restrict__ gamma,
-                                                              const float *__restrict__ beta, int tokens, int dim) {
+                                                              const float *__restrict__ beta, int tokens, int dim, double eps) {
     extern __shared__ __attribute__((aligned(16))) float tile[];
     constexpr int NWAVES = map_threads(NVEC) / 64;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(map_threads(NVEC)) void tap_map_kernel(const float 
     const float *rows = x + ((size_t)blockIdx.x * tokens + 1 + t0) * ldx;
     float *dst = out + (size_t)blockIdx.x * out_image_stride + t0;
 
-    for (int k = wave; k < valid; k += NWAVES) tap_row<NVEC, NORM>(rows + (size_t)k * ldx, tile + k * ld, gamma, beta, dim, lane);
+    for (int k = wave; k < valid; k += NWAVES) tap_row<NVEC, NORM>(rows + (size_t)k * ldx, tile + k * ld, gamma, beta, dim, lane, eps);
     __syncthreads();
 
     if constexpr (VEC) {
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(map_threads(NVEC)) void tap_map_kernel(const float 
 
 template <int NVEC, bool NORM>
 int launch_tap(hipStream_t s, const float *x, size_t ldx, float *out, size_t out_image_stride, const float *gamma, const float *beta,
-               int images, int tokens, int dim, int layout) {
+               int images, int tokens, int dim, int layout, double eps) {
     if (layout == VITHIP_TAP_MAP) {
         const int patches = tokens - 1, tt = map_tile_tokens(dim);
         const dim3 grid(images, (patches + tt - 1) / tt);
@@ -141,7 +141,7 @@ int launch_tap(hipStream_t s, const float *x, size_t ldx, float *out, size_t out
                 attr_set.set(dev);
             }
             hipLaunchKernelGGL((tap_map_kernel<NVEC, NORM, true>), grid, dim3(map_threads(NVEC)), lds, s, x, ldx, out, out_image_stride, gamma,
-                               beta, tokens, dim);
+                               beta, tokens, dim, eps);
         } else {
             static vitdev::PerDeviceOnce attr_set;
             if (!attr_set.is_done(dev)) {
@@ -151,7 +151,7 @@ int launch_tap(hipStream_t s, const float *x, size_t ldx, float *out, size_t out
                 attr_set.set(dev);
             }
             hipLaunchKernelGGL((tap_map_kernel<NVEC, NORM, false>), grid, dim3(map_threads(NVEC)), lds, s, x, ldx, out, out_image_stride, gamma,
-                               beta, tokens, dim);
+                               beta, tokens, dim, eps);
         }
         return static_cast<int>(hipGetLastError());
     }
@@ -159,16 +159,16 @@ int launch_tap(hipStream_t s, const float *x, size_t ldx, float *out, size_t out
     const int per_image = layout == VITHIP_TAP_CLS ? 1 : tokens - first_tok;
     const int rows = images * per_image;
     hipLaunchKernelGGL((tap_rows_kernel<NVEC, NORM>), dim3(vit_row::grid_for_rows(rows)), dim3(TAP_THREADS), 0, s, x, ldx, out,
-                       out_image_stride, gamma, beta, rows, per_image, first_tok, tokens, dim);
+                       out_image_stride, gamma, beta, rows, per_image, first_tok, tokens, dim, eps);
     return static_cast<int>(hipGetLastError());
 }
 
 }  // namespace
 
-extern "C" int vithip_tap_f32(vithip_stream_t stream, const float *x, size_t ldx, float *out, size_t out_image_stride, const float *gamma,
-                              const float *beta, int images, int tokens, int dim, int layout) {
+extern "C" int vithip_tap_f32_eps(vithip_stream_t stream, const float *x, size_t ldx, float *out, size_t out_image_stride, const float *gamma,
+                                  const float *beta, int images, int tokens, int dim, int layout, double eps) {
     const int bad = static_cast<int>(hipErrorInvalidValue);
-    if (!x || !out || !gamma != !beta || images <= 0 || tokens <= 0 || dim <= 0) return bad;
+    if (!x || !out || !gamma != !beta || images <= 0 || tokens <= 0 || dim <= 0 || !(eps > 0.0) || !(eps < 1.0e300)) return bad;
     if (layout != VITHIP_TAP_CLS && layout != VITHIP_TAP_TOKENS && layout != VITHIP_TAP_PATCHES && layout != VITHIP_TAP_MAP) return bad;
     if ((layout == VITHIP_TAP_PATCHES || layout == VITHIP_TAP_MAP) && tokens < 2) return bad;
     if (!vit_row::rows_ok(x, ldx, dim)) return bad;
@@ -181,7 +181,11 @@ extern "C" int vithip_tap_f32(vithip_stream_t stream, const float *x, size_t ldx
     hipStream_t s = static_cast<hipStream_t>(stream);
     return vit_row::dispatch_nvec(dim, [&](auto nvec) {
         constexpr int NVEC = decltype(nvec)::value;
-        return gamma ? launch_tap<NVEC, true>(s, x, ldx, out, out_image_stride, gamma, beta, images, tokens, dim, layout)
-                     : launch_tap<NVEC, false>(s, x, ldx, out, out_image_stride, gamma, beta, images, tokens, dim, layout);
+        return gamma ? launch_tap<NVEC, true>(s, x, ldx, out, out_image_stride, gamma, beta, images, tokens, dim, layout, eps)
+                     : launch_tap<NVEC, false>(s, x, ldx, out, out_image_stride, gamma, beta, images, tokens, dim, layout, eps);
     });
+}
+extern "C" int vithip_tap_f32(vithip_stream_t stream, const float *x, size_t ldx, float *out, size_t out_image_stride, const float *gamma,
+                              const float *beta, int images, int tokens, int dim, int layout) {
+    return vithip_tap_f32_eps(stream, x, ldx, out, out_image_stride, gamma, beta, images, tokens, dim, layout, VITHIP_LN_EPS);
 }

@@ -127,6 +127,8 @@ struct vit_engine {
     unsigned short **w16;        /* per weight index; NULL for tensors that stay fp32 */
     int weights_loaded;
     int resize_filter;           /* VIT_RESIZE_*: the filter of the _images calls (vit_engine_set_resize_filter) */
+    double ln_eps;               /* the epsilon of every LayerNorm the engine runs (vit_engine_set_layernorm_eps): architecture, kept across installs */
+    float *pre_g, *pre_b;        /* the LayerNorm in front of layer 0 (vit_engine_set_pre_norm), the engine's own allocation; NULL: none */
 
     /* workspace for max_batch images */
     float *x, *y, *qkv, *hbuf, *z, *logits;
@@ -266,9 +268,9 @@ static int check_config(vit_engine *e) {
     if (c->img_size <= 0 || c->patch_size <= 0 || c->in_chans <= 0 || c->num_classes <= 0 ||
         c->embed_dim <= 0 || c->depth <= 0 || c->num_heads <= 0 || c->hidden_dim <= 0 || VIT_HIDDEN_DIM(c) == 0)
         return fail(e, VIT_ERR_ARG, "vit_config: all dimensions must be positive");
-    if (VIT_MLP_KIND(c) != VIT_MLP_GELU && VIT_MLP_KIND(c) != VIT_MLP_SWIGLU)
-        return fail(e, VIT_ERR_ARG, "vit_config.hidden_dim: MLP kind %d (VIT_MLP_KIND, bits 24..30): VIT_MLP_GELU (%d) or VIT_MLP_SWIGLU (%d)",
-                    VIT_MLP_KIND(c), VIT_MLP_GELU, VIT_MLP_SWIGLU);
+    if (VIT_MLP_KIND(c) != VIT_MLP_GELU && VIT_MLP_KIND(c) != VIT_MLP_SWIGLU && VIT_MLP_KIND(c) != VIT_MLP_QUICKGELU)
+        return fail(e, VIT_ERR_ARG, "vit_config.hidden_dim: MLP kind %d (VIT_MLP_KIND, bits 24..30): VIT_MLP_GELU (%d), VIT_MLP_SWIGLU (%d) or VIT_MLP_QUICKGELU (%d)",
+                    VIT_MLP_KIND(c), VIT_MLP_GELU, VIT_MLP_SWIGLU, VIT_MLP_QUICKGELU);
     if (c->img_size % c->patch_size) return fail(e, VIT_ERR_ARG, "img_size must be a multiple of patch_size");
     if (c->embed_dim % c->num_heads || c->embed_dim / c->num_heads != 64)
         return fail(e, VIT_ERR_ARG, "HIP attention kernel needs head_dim == 64 (got %d/%d)", c->embed_dim, c->num_heads);
@@ -299,6 +301,7 @@ int vit_engine_create(vit_engine **out, const vit_config *cfg, const vit_engine_
     *out = e; /* returned even on failure so the caller can read the message, then destroy */
     e->cfg = cfg ? *cfg : vit_config_b16();
     if (opt) e->opt = *opt; else vit_engine_default_options(&e->opt);
+    e->ln_eps = VITHIP_LN_EPS;
     if (e->opt.max_batch <= 0) e->opt.max_batch = 256;
     if (e->opt.lanes < 1) e->opt.lanes = 1;
     int rc = check_config(e);
@@ -428,6 +431,7 @@ void vit_engine_destroy(vit_engine *e) {
     vithip_free(e->x); vithip_free(e->y); vithip_free(e->qkv); vithip_free(e->hbuf);
     vithip_free(e->z); vithip_free(e->logits);
     release_head(&e->head);
+    vithip_free(e->pre_g); /* one allocation: gamma, beta behind it */
     for (int j = 0; j < VIT_MAX_LANES; ++j) vithip_gemm_f32_workspace_destroy(e->gemm_ws[j]);
     if (e->copy_stream) { vithip_stream_sync(e->copy_stream); vithip_stream_destroy(e->copy_stream); }
     if (e->ev_in_stage) vithip_event_destroy(e->ev_in_stage);
@@ -474,6 +478,57 @@ int vit_engine_set_resize_filter(vit_engine *e, int filter) {
 }
 
 int vit_engine_get_resize_filter(const vit_engine *e) { return e ? e->resize_filter : -1; }
+
+static void drop_graph(vit_engine *e);
+
+int vit_engine_set_layernorm_eps(vit_engine *e, double eps) {
+    if (!e) return VIT_ERR_ARG;
+    if (!(eps > 0.0) || !isfinite(eps)) return fail(e, VIT_ERR_ARG, "set_layernorm_eps: eps = %g must be finite and > 0", eps);
+    HIP_TRY(e, vithip_set_device(e->opt.device));
+    HIP_TRY(e, vithip_device_sync()); /* a captured forward holds the old value in its launches */
+    drop_graph(e);
+    e->ln_eps = eps;
+    return VIT_OK;
+}
+
+double vit_engine_get_layernorm_eps(const vit_engine *e) { return e ? e->ln_eps : 0.0; }
+
+/* Nothing may be in flight (the callers have synchronised). */
+static void release_pre_norm(vit_engine *e) {
+    vithip_free(e->pre_g);
+    e->pre_g = e->pre_b = NULL;
+}
+
+int vit_engine_set_pre_norm(vit_engine *e, const float *gamma, const float *beta) {
+    if (!e) return VIT_ERR_ARG;
+    if (!gamma != !beta) return fail(e, VIT_ERR_ARG, "set_pre_norm: gamma and beta come together (both NULL removes the pre-norm)");
+    if (!e->weights_loaded) return fail(e, VIT_ERR_STATE, "set_pre_norm before vit_engine_load_weights()");
+    HIP_TRY(e, vithip_set_device(e->opt.device));
+    if (!gamma) { /* as an install: nothing in flight, no graph with the old launch list */
+        HIP_TRY(e, vithip_device_sync());
+        drop_graph(e);
+        release_pre_norm(e);
+        return VIT_OK;
+    }
+    /* the new pair first, whole; only then the old one goes */
+    const size_t D = (size_t)e->cfg.embed_dim;
+    float *g = NULL;
+    int hrc = vithip_malloc((void **)&g, 2 * D * sizeof(float));
+    if (hrc)
+        return fail(e, VIT_ERR_NOMEM, "set_pre_norm: no memory for 2 x %zu floats (HIP error %d: %s); the previous pre-norm stays", D, hrc,
+                    vithip_error_string(hrc));
+    hrc = vithip_memcpy_h2d(g, gamma, D * sizeof(float), e->stream);
+    if (!hrc) hrc = vithip_memcpy_h2d(g + D, beta, D * sizeof(float), e->stream);
+    if (!hrc) hrc = vithip_device_sync(); /* the uploads, and every forward that still reads the old pair, on whatever stream */
+    if (hrc) {
+        vithip_free(g);
+        return fail(e, VIT_ERR_HIP, "set_pre_norm: HIP error %d (%s) uploading; the previous pre-norm stays", hrc, vithip_error_string(hrc));
+    }
+    drop_graph(e);
+    release_pre_norm(e);
+    e->pre_g = g; e->pre_b = g + D; /* D % 32 == 0: beta is 16-byte aligned too */
+    return VIT_OK;
+}
 
 int vit_engine_set_profile(vit_engine *e, int on) {
     if (on && !e->ev_ready) {
@@ -580,6 +635,7 @@ static void restore_own_head(vit_engine *e) {
 static int finish_install(vit_engine *e) {
     const int rc = resolve_operands(e);
     restore_own_head(e);
+    release_pre_norm(e); /* checkpoint data like a caller's head: every install removes it (the epsilon, architecture, stays) */
     if (rc) return rc;
     HIP_TRY(e, vithip_stream_sync(e->stream));
     e->weights_loaded = 1;
@@ -800,7 +856,7 @@ typedef struct {
     vit_gemm_ops ops;                  /* W [N][K], bias; colsum and w_split: the fold's consumers and split engines */
     void *C; int ldc;
     int M, N, K;
-    int role;                          /* VITHIP_EPI_BIAS, VITHIP_EPI_BIAS_GELU or VITHIP_EPI_BIAS_RESIDUAL */
+    int role;                          /* VITHIP_EPI_BIAS, VITHIP_EPI_BIAS_GELU, VITHIP_EPI_BIAS_QGELU or VITHIP_EPI_BIAS_RESIDUAL */
     const float *ln_rows;              /* consumer */
     float *stats_rows, *stats_part;    /* producer */
     unsigned short *x16;               /* bf16 producer: the bf16 copy of C, leading dimension ldc */
@@ -813,7 +869,7 @@ static int gemm(vit_engine *e, vithip_stream_t s, const gemm_desc *g, int *stats
     HIP_TRY(e, stage_begin(e, s, g->stage));
     if (g->bf16) {
         static const int epi16[] = {[VITHIP_EPI_BIAS] = VITHIP_BF16_EPI_BF16, [VITHIP_EPI_BIAS_GELU] = VITHIP_BF16_EPI_BF16_GELU,
-                                    [VITHIP_EPI_BIAS_RESIDUAL] = VITHIP_BF16_EPI_F32_RESIDUAL};
+                                    [VITHIP_EPI_BIAS_RESIDUAL] = VITHIP_BF16_EPI_F32_RESIDUAL, [VITHIP_EPI_BIAS_QGELU] = VITHIP_BF16_EPI_BF16_QGELU};
         vithip_gemm_bf16_args a;
         memset(&a, 0, sizeof(a));
         a.A = g->A; a.lda = g->lda; a.W = g->ops.W; a.ldw = g->K; a.bias = g->ops.bias; a.residual = res; a.ldr = ldr;
@@ -835,14 +891,14 @@ static int gemm(vit_engine *e, vithip_stream_t s, const gemm_desc *g, int *stats
         a.A = g->A; a.lda = g->lda; a.W = g->ops.W; a.ldw = g->K; a.bias = g->ops.bias; a.residual = res; a.ldr = ldr;
         a.C = g->C; a.ldc = g->ldc; a.M = g->M; a.N = g->N; a.K = g->K; a.epilogue = g->role;
         a.ln_rows = g->ln_rows; a.ln_colsum = g->ops.colsum;
-        a.stats_out = g->stats_rows; a.stats_partials = g->stats_part;
+        a.stats_out = g->stats_rows; a.stats_partials = g->stats_part; a.stats_eps = e->ln_eps;
         if (!(ready = vithip_gemm_f32_stats_in_epilogue(&a))) a.stats_out = a.stats_partials = NULL;
         HIP_TRY(e, vithip_gemm_f32(s, &a));
     }
     HIP_TRY(e, stage_end(e, s));
     if (g->bf16 && ready) {
         HIP_TRY(e, stage_begin(e, s, VIT_STAGE_LN));
-        HIP_TRY(e, vithip_rowstats_finalize(s, g->stats_part, vithip_ln_strips(g->N), g->M, g->N, g->stats_rows));
+        HIP_TRY(e, vithip_rowstats_finalize_eps(s, g->stats_part, vithip_ln_strips(g->N), g->M, g->N, g->stats_rows, e->ln_eps));
         HIP_TRY(e, stage_end(e, s));
     }
     if (stats_ready) *stats_ready = ready;
@@ -950,8 +1006,8 @@ static int layernorm(chunk_ctx *c, vithip_stream_t s, const float *x, size_t ldx
                      const float *beta, int rows) {
     vit_engine *e = c->e;
     HIP_TRY(e, stage_begin(e, s, VIT_STAGE_LN));
-    if (e->opt.dtype == VIT_DTYPE_BF16) HIP_TRY(e, vithip_layernorm_f32_bf16out(s, x, ldx, y, ldy, gamma, beta, rows, c->D));
-    else HIP_TRY(e, vithip_layernorm_f32(s, x, ldx, y, ldy, gamma, beta, rows, c->D));
+    if (e->opt.dtype == VIT_DTYPE_BF16) HIP_TRY(e, vithip_layernorm_f32_bf16out_eps(s, x, ldx, y, ldy, gamma, beta, rows, c->D, e->ln_eps));
+    else HIP_TRY(e, vithip_layernorm_f32_eps(s, x, ldx, y, ldy, gamma, beta, rows, c->D, e->ln_eps));
     HIP_TRY(e, stage_end(e, s));
     return VIT_OK;
 }
@@ -961,8 +1017,8 @@ static int layernorm(chunk_ctx *c, vithip_stream_t s, const float *x, size_t ldx
 static int row_stats(chunk_ctx *c, const vit_lane *ln, size_t ldx, float *pairs, int rows) {
     vit_engine *e = c->e;
     HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
-    if (e->opt.dtype == VIT_DTYPE_BF16) HIP_TRY(e, vithip_rowstats_bf16(ln->s, ln->x, ldx, ln->xa, ldx, pairs, rows, c->D));
-    else HIP_TRY(e, vithip_rowstats_f32(ln->s, ln->x, ldx, pairs, rows, c->D));
+    if (e->opt.dtype == VIT_DTYPE_BF16) HIP_TRY(e, vithip_rowstats_bf16_eps(ln->s, ln->x, ldx, ln->xa, ldx, pairs, rows, c->D, e->ln_eps));
+    else HIP_TRY(e, vithip_rowstats_f32_eps(ln->s, ln->x, ldx, pairs, rows, c->D, e->ln_eps));
     HIP_TRY(e, stage_end(e, ln->s));
     return VIT_OK;
 }
@@ -973,6 +1029,7 @@ static int row_stats(chunk_ctx *c, const vit_lane *ln, size_t ldx, float *pairs,
  *   mlp     VIT_MLP_SWIGLU: fc1 is the bias-only GEMM of the fused w12, N = 2H, into rows of 2H columns [gate | value]; one launch
  *           (vithip_swiglu_*, still the fc1 stage) turns the gate half into the hidden layer silu(gate) * value in place; fc2 reads it
  *           there, lda = 2H.  The GEMMs know nothing of it, and a GELU engine's launches are the ones they were.
+ *           VIT_MLP_QUICKGELU: the launches of a GELU engine with fc1's epilogue role VITHIP_EPI_BIAS_QGELU in VITHIP_EPI_BIAS_GELU's place.
  *   dtype   bf16 engines keep the LN output, qkv, the attention output and the MLP hidden layer in bf16; the residual stream x,
  *           the LayerNorm statistics, softmax and every accumulation stay fp32.
  *   fold    the LayerNorm fold (vit_hip_kernels.h, "LayerNorm folding"): in_proj and fc1 read the raw rows (x, or its bf16 copy)
@@ -987,6 +1044,8 @@ static int row_stats(chunk_ctx *c, const vit_lane *ln, size_t ldx, float *pairs,
 static int encoder_layer(chunk_ctx *c, int l) {
     vit_engine *e = c->e;
     const int T = c->T, D = c->D, H = c->H, H1 = c->H1, heads = e->cfg.num_heads, swiglu = VIT_MLP_KIND(&e->cfg) == VIT_MLP_SWIGLU;
+    /* fc1's epilogue by MLP kind: the activation of a GELU or QuickGELU model is part of the GEMM; SwiGLU's gate is a launch behind it */
+    const int fc1_role = swiglu ? VITHIP_EPI_BIAS : VIT_MLP_KIND(&e->cfg) == VIT_MLP_QUICKGELU ? VITHIP_EPI_BIAS_QGELU : VITHIP_EPI_BIAS_GELU;
     const int bf16 = e->opt.dtype == VIT_DTYPE_BF16, fold = e->fold, feeds_next = l + 1 < e->cfg.depth;
     const int pruned = c->pruned && !feeds_next;
     const vit_layer_ops *o = &e->layer[l];
@@ -1051,7 +1110,7 @@ static int encoder_layer(chunk_ctx *c, int l) {
     for (int j = 0; j < c->L; ++j) { /* fc1 + GELU (ViT_seq.c:258-264); SwiGLU: w12 + bias, then the gate */
         const vit_lane *ln = &c->lane[j];
         gemm_desc g = {.stage = VIT_STAGE_FC1, .bf16 = bf16, .A = ln->y, .lda = D, .ops = o->fc1, .C = ln->h, .ldc = H1,
-                       .M = rows[j], .N = H1, .K = D, .role = swiglu ? VITHIP_EPI_BIAS : VITHIP_EPI_BIAS_GELU};
+                       .M = rows[j], .N = H1, .K = D, .role = fc1_role};
         if (fold) { g.A = ln->xa; g.lda = r * D; g.ln_rows = pairs[j]; }
         RUN(gemm(e, ln->s, &g, NULL));
         if (swiglu) {
@@ -1078,7 +1137,7 @@ static int encoder_layer(chunk_ctx *c, int l) {
  * class_block: the final LayerNorm of the class rows (ViT_seq.c:429-433 normalises all rows, uses row 0): row step T*D, exactly the
  * rows a pruned last layer has updated.  Not vithip_tap_f32 with VITHIP_TAP_CLS: the same bits, but another launch. */
 static int class_block(chunk_ctx *c, const vit_lane *ln, float *dst, size_t ld) {
-    HIP_TRY(c->e, vithip_layernorm_f32(ln->s, ln->x, (size_t)c->T * c->D, dst, ld, c->e->final.ln_g, c->e->final.ln_b, ln->n, c->D));
+    HIP_TRY(c->e, vithip_layernorm_f32_eps(ln->s, ln->x, (size_t)c->T * c->D, dst, ld, c->e->final.ln_g, c->e->final.ln_b, ln->n, c->D, c->e->ln_eps));
     return VIT_OK;
 }
 
@@ -1100,22 +1159,28 @@ static int pooled_block(chunk_ctx *c, const vit_lane *ln, float *dst, size_t ld,
     float *scratch = pool_scratch(c, ln, &need);
     if (need == 0 || need > own || ((size_t)scratch & 15))
         return fail(e, VIT_ERR_STATE, "%s: the pooling scratch (%zu bytes) does not fit the lane's own %zu bytes of y", who, need, own);
-    if (fcnorm) HIP_TRY(e, vithip_pool_layernorm_f32(ln->s, ln->x, D, dst, ld, e->final.ln_g, e->final.ln_b, ln->n, c->T, 1, c->D, scratch));
-    else HIP_TRY(e, vithip_layernorm_pool_f32(ln->s, ln->x, D, dst, ld, e->final.ln_g, e->final.ln_b, ln->n, c->T, 1, c->D, l2, scratch));
+    if (fcnorm) HIP_TRY(e, vithip_pool_layernorm_f32_eps(ln->s, ln->x, D, dst, ld, e->final.ln_g, e->final.ln_b, ln->n, c->T, 1, c->D, scratch, e->ln_eps));
+    else HIP_TRY(e, vithip_layernorm_pool_f32_eps(ln->s, ln->x, D, dst, ld, e->final.ln_g, e->final.ln_b, ln->n, c->T, 1, c->D, l2, scratch, e->ln_eps));
     return VIT_OK;
 }
 
 /* tap_block: the rows `kind` (VITHIP_TAP_*) names of x as the layer in front has just left it; norm: through the final LayerNorm */
 static int tap_block(chunk_ctx *c, const vit_lane *ln, float *dst, size_t ld, int norm, int kind) {
     const vit_final_ops *f = &c->e->final;
-    HIP_TRY(c->e, vithip_tap_f32(ln->s, ln->x, (size_t)c->D, dst, ld, norm ? f->ln_g : NULL, norm ? f->ln_b : NULL, ln->n, c->T, c->D, kind));
+    HIP_TRY(c->e, vithip_tap_f32_eps(ln->s, ln->x, (size_t)c->D, dst, ld, norm ? f->ln_g : NULL, norm ? f->ln_b : NULL, ln->n, c->T, c->D, kind,
+                                     c->e->ln_eps));
     return VIT_OK;
 }
 
 /* The head (vit_head): the blocks of the last layer into the operand rows -- the class blocks of earlier layers are in place
  * (stage_head_tap) --, classifier head (ViT_seq.c:435), Softmax (ViT_seq.c:437) + top-1 (Main.c:62-70) -- or, for a top-k call, the k
  * best classes of the same logits as records in the softmax's place: out->dst is then [n][2k] 32-bit words and nothing of
- * [n][classes] is written.  The checkpoint's own head is the case K = 1, in = D: one class block per lane into z, ld = D. */
+ * [n][classes] is written; or, for a features call of VIT_FEAT_HEAD, the logits rows themselves, copied to the caller's rows (and
+ * L2-normalised there when the spec says so).  The checkpoint's own head is the case K = 1, in = D: one class block per lane into z, ld = D. */
+static int runs_head(const vit_output *out) {
+    return out->kind == VIT_OUT_PROBS || out->kind == VIT_OUT_TOPK || (out->kind == VIT_OUT_FEATURES && out->spec.kind == VIT_FEAT_HEAD);
+}
+static size_t out_row_elems(const vit_engine *e, const vit_output *out);
 static int stage_head(chunk_ctx *c, const vit_output *out) {
     vit_engine *e = c->e;
     const vit_head *h = &e->head;
@@ -1138,6 +1203,15 @@ static int stage_head(chunk_ctx *c, const vit_output *out) {
     for (int j = 0; j < c->L; ++j) {
         const vit_lane *ln = &c->lane[j];
         const size_t o = (size_t)ln->off;
+        if (out->kind == VIT_OUT_FEATURES) { /* VIT_FEAT_HEAD: the rows of e->logits as they are (vit_engine_read_logits keeps the
+                                              * un-normalised ones), then F.normalize on the caller's copy */
+            float *dst = out->dst + o * out_row_elems(e, out);
+            HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_HEAD));
+            HIP_TRY(e, vithip_gather_rows_f32(ln->s, e->logits + o * NC, (size_t)NC, dst, (size_t)NC, ln->n, NC));
+            if (out->spec.l2_normalize) HIP_TRY(e, vithip_l2_normalize_rows_f32(ln->s, dst, (size_t)NC, ln->n, NC));
+            HIP_TRY(e, stage_end(e, ln->s));
+            continue;
+        }
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_SOFTMAX));
         if (out->kind == VIT_OUT_TOPK)
             HIP_TRY(e, vithip_softmax_topk_f32(ln->s, e->logits + o * NC, NC, (int *)out->dst + o * 2 * (size_t)out->topk.k, 2 * out->topk.k, ln->n, NC,
@@ -1155,6 +1229,7 @@ static size_t row_elems(const vit_engine *e, int out_kind, int kind) {
     if (out_kind == VIT_OUT_PROBS) return (size_t)e->cfg.num_classes;
     if (out_kind == VIT_OUT_TOPK) return 2 * (size_t)kind;
     if (out_kind == VIT_OUT_ATTENTION) return (kind == VIT_ATTN_HEADS ? (size_t)e->cfg.num_heads : 1) * (size_t)e->tokens;
+    if (kind == VIT_FEAT_HEAD) return (size_t)e->cfg.num_classes;
     return (kind == VIT_FEAT_TOKENS ? (size_t)e->tokens : 1) * (size_t)e->cfg.embed_dim;
 }
 /* ... and of one tapped layer's block of an intermediate row; `kind` is the VIT_TAP_* of a valid spec */
@@ -1180,7 +1255,7 @@ static int stage_features(chunk_ctx *c, const vit_output *out) {
             RUN(class_block(c, ln, dst, D));
             if (out->spec.l2_normalize) HIP_TRY(e, vithip_l2_normalize_rows_f32(ln->s, dst, D, ln->n, c->D));
         } else if (out->spec.kind == VIT_FEAT_TOKENS)
-            HIP_TRY(e, vithip_layernorm_f32(ln->s, ln->x, D, dst, D, e->final.ln_g, e->final.ln_b, ln->n * c->T, c->D));
+            HIP_TRY(e, vithip_layernorm_f32_eps(ln->s, ln->x, D, dst, D, e->final.ln_g, e->final.ln_b, ln->n * c->T, c->D, e->ln_eps));
         else RUN(pooled_block(c, ln, dst, D, 0, out->spec.l2_normalize, "features"));
         HIP_TRY(e, stage_end(e, ln->s));
     }
@@ -1243,7 +1318,7 @@ static int stage_head_tap(chunk_ctx *c, int l) {
 /* What each output kind reads of x behind the last layer: 1 where that is the class rows alone, which are all a pruned last layer
  * updates.  A kind that is not named here runs the layer in full: a new output cannot silently return rows of the layer before. */
 static int class_rows_only(const vit_engine *e, const vit_output *out) {
-    if (out->kind == VIT_OUT_PROBS || out->kind == VIT_OUT_TOPK) return e->head.spec.pool == VIT_HEAD_POOL_NONE; /* a pooled block reads every patch row */
+    if (runs_head(out)) return e->head.spec.pool == VIT_HEAD_POOL_NONE; /* a pooled block reads every patch row */
     if (out->kind == VIT_OUT_FEATURES) return out->spec.kind == VIT_FEAT_CLS; /* MEAN and TOKENS read every row */
     if (out->kind == VIT_OUT_INTERMEDIATE) return out->tap.kind == VIT_TAP_CLS;
     return out->kind == VIT_OUT_ATTENTION; /* Q of the class rows, K of every token (qkv_only) */
@@ -1293,6 +1368,21 @@ static void chunk_setup(vit_engine *e, vithip_stream_t s, int nb, const vit_outp
     }
 }
 
+/* The LayerNorm in front of layer 0 (CLIP's ln_pre; vit_engine_set_pre_norm): each lane normalises its n * T rows of the fp32
+ * residual stream x IN PLACE (y == x, ldy == ldx: the stated contract of vithip_layernorm_f32_eps), with the engine's epsilon.  x is
+ * fp32 on both engine dtypes.  Layer 0 then proceeds as ever: with the fold its statistics pass runs on these rows (stats_ready is
+ * false at the start of a chunk) and, on bf16 engines, writes their bf16 copy. */
+static int stage_pre_norm(chunk_ctx *c) {
+    vit_engine *e = c->e;
+    for (int j = 0; j < c->L; ++j) {
+        const vit_lane *ln = &c->lane[j];
+        HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
+        HIP_TRY(e, vithip_layernorm_f32_eps(ln->s, ln->x, (size_t)c->D, ln->x, (size_t)c->D, e->pre_g, e->pre_b, ln->n * c->T, c->D, e->ln_eps));
+        HIP_TRY(e, stage_end(e, ln->s));
+    }
+    return VIT_OK;
+}
+
 /* d_images: the chunk's first image, of the kind `in` says; f32_stage: where 8-bit images are normalised to (max_batch images);
  * out: what to write, at the chunk's first row */
 static int forward_chunk(vit_engine *e, vithip_stream_t s, const void *d_images, const vit_input *in, float *f32_stage, int nb,
@@ -1306,18 +1396,19 @@ static int forward_chunk(vit_engine *e, vithip_stream_t s, const void *d_images,
         for (int j = 1; j < c->L; ++j) HIP_TRY(e, vithip_stream_wait_event(c->lane[j].s, e->ev_fork));
     }
     RUN(stage_embed(c, d_images, in, f32_stage));
+    if (e->pre_g) RUN(stage_pre_norm(c));
     if (out->kind == VIT_OUT_INTERMEDIATE) { /* the layers up to the deepest tap, a block of the rows behind each tapped one; nothing else */
         for (int l = 0, j = 0; j < out->tap.num_layers; ++l) {
             RUN(encoder_layer(c, l));
             if (l == out->tap.layers[j]) RUN(stage_tap(c, out, j++));
         }
     } else {
-        const int head_taps = out->kind == VIT_OUT_PROBS || out->kind == VIT_OUT_TOPK;
+        const int head_taps = runs_head(out);
         for (int l = 0; l < cfg->depth; ++l) {
             RUN(encoder_layer(c, l));
             if (head_taps) RUN(stage_head_tap(c, l));
         }
-        if (out->kind == VIT_OUT_FEATURES) RUN(stage_features(c, out));
+        if (out->kind == VIT_OUT_FEATURES && !head_taps) RUN(stage_features(c, out));
         else if (out->kind == VIT_OUT_ATTENTION) RUN(stage_cls_attention(c, out));
         else RUN(stage_head(c, out));
     }
@@ -1325,7 +1416,7 @@ static int forward_chunk(vit_engine *e, vithip_stream_t s, const void *d_images,
         HIP_TRY(e, vithip_event_record(e->ev_join[j - 1], c->lane[j].s));
         HIP_TRY(e, vithip_stream_wait_event(s, e->ev_join[j - 1]));
     }
-    e->last_rows = out->kind == VIT_OUT_PROBS || out->kind == VIT_OUT_TOPK ? nb : 0; /* rows of e->logits the chunk wrote (vit_engine_read_logits) */
+    e->last_rows = runs_head(out) ? nb : 0; /* rows of e->logits the chunk wrote (vit_engine_read_logits) */
     return VIT_OK;
 }
 #undef RUN
@@ -1392,10 +1483,10 @@ static vit_output output_probs(float *probs, int *label, float *prob) {
 static const char *feature_spec_fault(const vit_feature_spec *spec, int *arg) {
     if (!spec) return "%s: the feature spec is required";
     *arg = spec->kind;
-    if (spec->kind != VIT_FEAT_CLS && spec->kind != VIT_FEAT_MEAN && spec->kind != VIT_FEAT_TOKENS) return "%s: unknown feature kind %d";
+    if (spec->kind != VIT_FEAT_CLS && spec->kind != VIT_FEAT_MEAN && spec->kind != VIT_FEAT_TOKENS && spec->kind != VIT_FEAT_HEAD) return "%s: unknown feature kind %d";
     *arg = spec->l2_normalize;
     if (spec->l2_normalize != 0 && spec->l2_normalize != 1) return "%s: l2_normalize must be 0 or 1 (got %d)";
-    if (spec->l2_normalize && spec->kind == VIT_FEAT_TOKENS) return "%s: l2_normalize applies to the CLS and MEAN rows, not to TOKENS";
+    if (spec->l2_normalize && spec->kind == VIT_FEAT_TOKENS) return "%s: l2_normalize applies to the CLS, MEAN and HEAD rows, not to TOKENS";
     return NULL;
 }
 static const char *attention_spec_fault(const vit_attention_spec *spec, int *arg) {

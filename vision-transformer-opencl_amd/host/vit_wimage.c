@@ -21,9 +21,11 @@
  * bits (VIT_MLP_KIND): a reader from before the kind existed takes version 2 only and so refuses the file instead of reading that
  * word as a width. */
 #define VITW_VERSION_GELU 2u
-#define VITW_VERSION_SWIGLU 3u
-static int mlp_ok(const vit_config *cfg) { return VIT_MLP_KIND(cfg) == VIT_MLP_GELU || VIT_MLP_KIND(cfg) == VIT_MLP_SWIGLU; }
-static uint32_t vitw_version(const vit_config *cfg) { return VIT_MLP_KIND(cfg) == VIT_MLP_SWIGLU ? VITW_VERSION_SWIGLU : VITW_VERSION_GELU; }
+#define VITW_VERSION_SWIGLU 3u /* every non-zero kind: VIT_MLP_QUICKGELU too, told from SwiGLU by the kind bits of that eighth word, which a load compares */
+static int mlp_ok(const vit_config *cfg) {
+    return VIT_MLP_KIND(cfg) == VIT_MLP_GELU || VIT_MLP_KIND(cfg) == VIT_MLP_SWIGLU || VIT_MLP_KIND(cfg) == VIT_MLP_QUICKGELU;
+}
+static uint32_t vitw_version(const vit_config *cfg) { return VIT_MLP_KIND(cfg) != VIT_MLP_GELU ? VITW_VERSION_SWIGLU : VITW_VERSION_GELU; }
 #define SLOT 128u              /* floats: 512-B fp32 slots = 256-B bf16 slots */
 #define PAYLOAD_ALIGN 4096u
 

@@ -54,14 +54,17 @@ def round6(w: np.ndarray) -> np.ndarray:
     return (r / np.float32(1000000.0)).astype(np.float32)
 
 
-MLP_KINDS = {"gelu": 0, "swiglu": 1}  # VIT_MLP_GELU, VIT_MLP_SWIGLU
+MLP_KINDS = {"gelu": 0, "swiglu": 1}  # VIT_MLP_GELU, VIT_MLP_SWIGLU: the kinds with an fc1 layout of their own
+MLP_ACTIVATIONS = {"quickgelu": 3}    # VIT_MLP_QUICKGELU: a GELU model's layout with another activation in fc1's epilogue (2 is unassigned)
+MLP_CODES = {**MLP_KINDS, **MLP_ACTIVATIONS}  # name -> the kind bits of vit_config.hidden_dim
 MLP_SHIFT = 24  # VIT_MLP_SHIFT: vit_config.hidden_dim carries the kind in bits 24..30 (binding.CConfig.of packs it)
 
 
 @dataclass(frozen=True)
 class ModelConfig:
     """Runtime form of ViT_seq.c:10-21.  mlp: "gelu" (fc1 -> erf-GELU -> fc2) or "swiglu" (fc1 is the fused w12 with 2 * hidden_dim
-    rows, gate rows first; the hidden layer is silu(gate) * value: DINOv2 ViT-g/14, EVA-02)."""
+    rows, gate rows first; the hidden layer is silu(gate) * value: DINOv2 ViT-g/14, EVA-02) or "quickgelu" (fc1 -> y * sigmoid(1.702 y)
+    -> fc2: OpenAI CLIP's image tower)."""
     img_size: int = 224
     patch_size: int = 16
     in_chans: int = 3
@@ -73,13 +76,13 @@ class ModelConfig:
     mlp: str = "gelu"
 
     def __post_init__(self):
-        if self.mlp not in MLP_KINDS and not isinstance(self.mlp, int):  # an int goes into vit_config as it is (the engine checks it)
-            raise ValueError(f"mlp = {self.mlp!r}: one of {sorted(MLP_KINDS)}")
+        if self.mlp not in MLP_CODES and not isinstance(self.mlp, int):  # an int goes into vit_config as it is (the engine checks it)
+            raise ValueError(f"mlp = {self.mlp!r}: one of {sorted(MLP_CODES)}")
 
     @property
     def fc1_rows(self) -> int:
         """Output rows of the fc1 weight: hidden_dim, or 2 * hidden_dim for the fused gate | value projection of SwiGLU."""
-        return 2 * self.hidden_dim if MLP_KINDS.get(self.mlp, self.mlp) == MLP_KINDS["swiglu"] else self.hidden_dim
+        return 2 * self.hidden_dim if MLP_CODES.get(self.mlp, self.mlp) == MLP_KINDS["swiglu"] else self.hidden_dim
 
     @property
     def tokens(self) -> int:
@@ -120,6 +123,9 @@ VIT_B16 = ModelConfig()
 VIT_L16_384 = ModelConfig(img_size=384, embed_dim=1024, depth=24, num_heads=16, hidden_dim=4096)
 # DINOv2 ViT-g/14: patch 14, the fused SwiGLU MLP (w12 [8192][1536], w3 [1536][4096])
 VIT_G14 = ModelConfig(img_size=224, patch_size=14, embed_dim=1536, depth=40, num_heads=24, hidden_dim=4096, mlp="swiglu")
+# CLIP image towers (OpenAI ViT-B/16 and ViT-L/14): QuickGELU; num_classes is the projection width (the head slot holds visual_projection)
+CLIP_B16 = ModelConfig(num_classes=512, mlp="quickgelu")
+CLIP_L14 = ModelConfig(patch_size=14, num_classes=768, embed_dim=1024, depth=24, num_heads=16, hidden_dim=4096, mlp="quickgelu")
 # reduced models for fast live-oracle parity (head_dim stays 64 as in ViT-B/L)
 VIT_TINY = ModelConfig(img_size=32, num_classes=10, embed_dim=128, depth=2, num_heads=2, hidden_dim=256)
 VIT_SMALL = ModelConfig(img_size=64, num_classes=100, embed_dim=192, depth=3, num_heads=3, hidden_dim=768)
