@@ -297,9 +297,9 @@ int vit_engine_get_resize_filter(const vit_engine *e);  /* -1 for a NULL engine 
 /*
  * The class token's attention over the tokens, in the LAST encoder layer, instead of probabilities: the DINO-style saliency map of a
  * ViT.  With q[i][h] the class row's query of image i and head h in that layer and k[i][h][t] the key of token t (T = tokens, the
- * class token's own key first, head_dim = 64):
+ * class token's own key first, head_dim = embed_dim / num_heads: 64, or 72 .. 128 through vithip_cls_attention_*_hd):
  *
- *     s_t = (q . k_t) / sqrtf(64);   p[i][h][t] = expf(s_t - max_t s) / sum_t expf(s_t - max)          (ViT_seq.c:156-190, query row 0)
+ *     s_t = (q . k_t) / sqrtf(head_dim);   p[i][h][t] = expf(s_t - max_t s) / sum_t expf(s_t - max)          (ViT_seq.c:156-190, query row 0)
  *
  *   VIT_ATTN_HEADS      out[i][h][t] = p[i][h][t]                                       [n][heads][T]  every row sums to 1
  *   VIT_ATTN_HEAD_MEAN  out[i][t] = (p[i][0][t] + p[i][1][t] + ...) / (float)heads      [n][T]         heads added in order, in fp32:

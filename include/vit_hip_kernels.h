@@ -282,6 +282,30 @@ int vithip_attention_bf16io_rows(vithip_stream_t stream, const unsigned short *q
  * one image's rows reach only that image's outputs; all other outputs have the bits of the same launch on clean data. */
 int vithip_attention_bf16io_qscaled(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out, int n_images,
                                     int tokens, int heads, int q_rows);
+/*
+ * The attention entries for any accepted head_dim (csrc/vit_attention_hd.hip): 64, and every multiple of 8 from 72 to 128.  The
+ * layout is the one of vithip_attention_f32 / _bf16io with 64 replaced by head_dim: qkv [n*T][3*heads*head_dim], columns [Q | K | V],
+ * head h = columns head_dim*h.. of each; out [n*T][heads*head_dim]; scores = q.k / sqrtf(head_dim), row softmax with max
+ * subtraction, out = P.V.  Only the first q_rows (1..tokens) query rows of every image are computed and stored.
+ *   head_dim == 64: a call of vithip_attention_f32 / _f32_rows, _bf16io / _bf16io_rows / _bf16io_qscaled -- their bits and their
+ *     limits (q_rows < tokens needs tokens <= 224).
+ *   otherwise: one streaming kernel, any tokens >= 1 and any q_rows; fp32 on v_mfma_f32_32x32x2_f32 with an fp32 softmax; bf16 with
+ *     both products on v_mfma_f32_32x32x16_bf16, fp32 scores and softmax, the output rounded to bf16 once; P enters its product in two
+ *     bf16 pieces, bf16(p) + bf16(p - bf16(p)), so its rounding (2^-17) stays far below the output's.  The tail of
+ *     a contraction that is no multiple of 16 is zero-filled on chip: nothing is read behind column head_dim of a head's slice.
+ *   q_scaled = 1 (bf16): the Q columns hold vithip_qscale(head_dim) * q; p = exp2(q.k - max), no further scaling.
+ * No atomics; an image's output bits depend on neither the batch size nor its place in the batch; non-finite values in one image's
+ * rows reach only that image's outputs; nothing is written outside rows 0..q_rows-1 of an image or behind column heads*head_dim.
+ * hipErrorInvalidValue, nothing launched: any other head_dim, NULL or not 16-byte aligned pointers, non-positive sizes,
+ * q_rows outside 1..tokens, q_scaled other than 0 / 1.
+ */
+int vithip_attention_f32_hd(vithip_stream_t stream, const float *qkv, float *out, int n_images, int tokens, int heads, int head_dim,
+                            int q_rows);
+int vithip_attention_bf16io_hd(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out, int n_images, int tokens,
+                               int heads, int head_dim, int q_rows, int q_scaled);
+/* (float)((1 / sqrt((double)head_dim)) * log2(e)): the factor of the scores' exponent, softmax(q.k / sqrt(hd)) = 2^(qscale q.k -
+ * max) / sum; vithip_qscale(64) has the bits of VITHIP_QSCALE.  0.0f for a head_dim the kernels refuse. */
+float vithip_qscale(int head_dim);
 /* Patch embedding on the bf16 matrix pipe (same result layout as vithip_patch_embed_f32: x[n][tokens][D] fp32 with
  * class token and pos_emb applied; ViT_seq.c:25-101): the images are cut into bf16 patch rows
  * (patches16: workspace of n * (img/patch)^2 * chans*patch^2 bf16), multiplied with the bf16 conv weight
@@ -369,7 +393,7 @@ int vithip_swiglu_bf16(vithip_stream_t stream, const unsigned short *u, size_t l
  * Fused scaled-dot-product attention, one workgroup per (image, head) (x blocks of 256 queries when chunked).
  * qkv: [n*T][3*D] rows = tokens, columns [Q | K | V], head h = columns 64h..64h+63 of each.
  * out: [n*T][D].  scores = q.k / sqrtf(64); row softmax with max subtraction; out = P.V.
- * head_dim must be 64.  Up to 224 tokens K and V of one head stay resident in LDS; longer sequences
+ * head_dim is 64 here (other head dims: vithip_attention_f32_hd below the bf16 entries).  Up to 224 tokens K and V of one head stay resident in LDS; longer sequences
  * (ViT-L/16-384: 577) stream K/V through LDS in 224-key chunks with an online softmax.
  * Non-finite values in one image's rows reach only that image's outputs; all other outputs have the bits of the same launch on
  * clean data.
@@ -546,6 +570,13 @@ int vithip_cls_attention_f32(vithip_stream_t stream, const float *qkv, size_t q_
                              int tokens, int heads, int head_mean);
 int vithip_cls_attention_bf16(vithip_stream_t stream, const unsigned short *qkv, size_t q_row_stride, float *out, size_t ld_out,
                               int n_images, int tokens, int heads, int head_mean, int q_scaled);
+/* The same contract with 64 replaced by head_dim (64, or a multiple of 8 from 72 to 128; anything else: hipErrorInvalidValue):
+ * s_t = (q . k_t) / sqrtf(head_dim), q_scaled Q columns hold vithip_qscale(head_dim) * q.  head_dim == 64 is a call of the entries
+ * above (their bits); the other head dims run the kernel of csrc/vit_attention_hd.hip. */
+int vithip_cls_attention_f32_hd(vithip_stream_t stream, const float *qkv, size_t q_row_stride, float *out, size_t ld_out, int n_images,
+                                int tokens, int heads, int head_dim, int head_mean);
+int vithip_cls_attention_bf16_hd(vithip_stream_t stream, const unsigned short *qkv, size_t q_row_stride, float *out, size_t ld_out,
+                                 int n_images, int tokens, int heads, int head_dim, int head_mean, int q_scaled);
 
 /*
  * Rows of the residual stream as an output (csrc/vit_tap.hip): per image the class row, every token, the patch tokens, or the patch

@@ -36,7 +36,8 @@ typedef struct {
  * Model dimensions.  The reference fixes them with macros (ViT_seq.c:10-21,
  * ViT_opencl.c:12-23); here they are a runtime struct so that the same engine serves
  * ViT-B/16-224 (the default), reduced test models and ViT-L/16-384.
- * Constraints of the HIP path: embed_dim / num_heads == 64, embed_dim % 32 == 0, embed_dim <= 2048,
+ * Constraints of the HIP path: head_dim = embed_dim / num_heads is 64 or a multiple of 8 from 72 to 128 (80: ViT-H/14, 88: ViT-g-14,
+ * 104: ViT-bigG-14; vithip_qscale(head_dim) != 0), embed_dim % 32 == 0 (bf16 engines and the LayerNorm fold: % 64), embed_dim <= 2048,
  * hidden_dim % 32 == 0 (bf16 engines: % 64; under VIT_MLP_SWIGLU the 2 * hidden_dim rows of fc1 inherit it), patch_size and img_size even (patch 14 included; the 8-bit and decoded-image
  * input calls also need img_size % 4 == 0).
  */

@@ -372,6 +372,13 @@ def lib() -> C.CDLL:
         L.vithip_layernorm_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                            C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.vithip_attention_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+        if hasattr(L, "vithip_attention_f32_hd"):  # an earlier build (see above) has head_dim 64 only
+            L.vithip_qscale.restype = C.c_float
+            L.vithip_qscale.argtypes = [C.c_int]
+            L.vithip_attention_f32_hd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5
+            L.vithip_attention_bf16io_hd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6
+            L.vithip_cls_attention_f32_hd.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_int] * 5
+            L.vithip_cls_attention_bf16_hd.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_int] * 6
         L.vithip_softmax_top1_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                               C.c_void_p, C.c_int, C.c_int]
         L.vithip_event_create.argtypes = [C.POINTER(C.c_void_p)]
@@ -1080,6 +1087,69 @@ def cls_attention_bf16(qkv_bits, n_images: int, tokens: int, heads: int, head_me
     assert qkv_bits.shape == (n_images * tokens, 3 * heads * 64)
     return _cls_attention("vithip_cls_attention_bf16", DeviceArray.from_numpy(qkv_bits), n_images, tokens, heads, head_mean, ld_out, fill,
                           (int(q_scaled),))
+
+
+def qscale(head_dim: int) -> float:
+    """vithip_qscale: (1/sqrt(head_dim)) * log2(e) as the fp32 value the kernels and the engine's fold use; 0.0 for a head_dim they
+    refuse.  qscale(64) == QSCALE."""
+    return float(lib().vithip_qscale(int(head_dim)))
+
+
+def _attention_hd(name, qkv, dtype, n_images, tokens, heads, head_dim, q_rows, fill, frames, out, extra=()):
+    rows, D = n_images * tokens, heads * head_dim
+    assert qkv.shape == (rows, 3 * D)
+    if frames is None:
+        dq, do = _Plain.framed(qkv), _Plain.out_frame(rows, D, dtype=dtype, preload=np.full((rows, D), fill, dtype))
+    else:
+        dq, do = frames.framed(qkv), frames.out_frame(rows, D, dtype=dtype)
+    _note(out, out=do)
+    hip_check(getattr(lib(), name)(None, dq.ptr, do.ptr, n_images, tokens, heads, head_dim, tokens if q_rows is None else q_rows, *extra), name)
+    return do.window()
+
+
+def attention_hd(qkv, n_images: int, tokens: int, heads: int, head_dim: int, q_rows: Optional[int] = None, fill: float = 0.0,
+                 frames=None, out: Optional[dict] = None) -> np.ndarray:
+    """vithip_attention_f32_hd: qkv [n_images * tokens][3 * heads * head_dim] fp32 -> [n_images * tokens][heads * head_dim]; only
+    the first q_rows (default: all) query rows of every image are written, the others keep `fill` (with `frames`: the frame's
+    sentinel, and `out` receives the frame "out")."""
+    return _attention_hd("vithip_attention_f32_hd", _as_f32(qkv), np.float32, n_images, tokens, heads, head_dim, q_rows, fill, frames, out)
+
+
+def attention_bf16io_hd(qkv_bits, n_images: int, tokens: int, heads: int, head_dim: int, q_rows: Optional[int] = None,
+                        q_scaled: bool = False, fill: int = 0, frames=None, out: Optional[dict] = None) -> np.ndarray:
+    """vithip_attention_bf16io_hd: the same on bf16 bits (uint16); q_scaled: the Q columns hold qscale(head_dim) * q."""
+    return _attention_hd("vithip_attention_bf16io_hd", np.ascontiguousarray(qkv_bits, np.uint16), np.uint16, n_images, tokens, heads,
+                         head_dim, q_rows, fill, frames, out, (int(q_scaled),))
+
+
+def _cls_attention_hd(fn_name, dq, n_images, tokens, heads, head_dim, head_mean, ld_out, fill, extra=()):
+    row = tokens if head_mean else heads * tokens
+    ld = row if ld_out is None else int(ld_out)
+    do = DeviceArray((n_images, ld)) if fill is None else DeviceArray.from_numpy(np.full((n_images, ld), fill, np.float32))
+    hip_check(getattr(lib(), fn_name)(None, dq.ptr, 3 * heads * head_dim, do.ptr, ld, n_images, tokens, heads, head_dim, int(head_mean),
+                                      *extra), fn_name)
+    res = do.numpy()
+    if ld_out is not None:
+        return res
+    return res if head_mean else res.reshape(n_images, heads, tokens)
+
+
+def cls_attention_hd(qkv, n_images: int, tokens: int, heads: int, head_dim: int, head_mean: bool = False, ld_out: Optional[int] = None,
+                     fill: Optional[float] = None) -> np.ndarray:
+    """vithip_cls_attention_f32_hd: cls_attention() for qkv [n_images * tokens][3 * heads * head_dim]."""
+    qkv = _as_f32(qkv)
+    assert qkv.shape == (n_images * tokens, 3 * heads * head_dim)
+    return _cls_attention_hd("vithip_cls_attention_f32_hd", DeviceArray.from_numpy(qkv), n_images, tokens, heads, head_dim, head_mean,
+                             ld_out, fill)
+
+
+def cls_attention_bf16_hd(qkv_bits, n_images: int, tokens: int, heads: int, head_dim: int, head_mean: bool = False,
+                          q_scaled: bool = False, ld_out: Optional[int] = None, fill: Optional[float] = None) -> np.ndarray:
+    """vithip_cls_attention_bf16_hd: the same from bf16 bits (uint16); q_scaled: the Q columns hold qscale(head_dim) * q."""
+    qkv_bits = np.ascontiguousarray(qkv_bits, np.uint16)
+    assert qkv_bits.shape == (n_images * tokens, 3 * heads * head_dim)
+    return _cls_attention_hd("vithip_cls_attention_bf16_hd", DeviceArray.from_numpy(qkv_bits), n_images, tokens, heads, head_dim,
+                             head_mean, ld_out, fill, (int(q_scaled),))
 
 
 def patch_embed(cfg: ModelConfig, images, conv_w, conv_b, cls, pos) -> np.ndarray:

@@ -272,8 +272,9 @@ static int check_config(vit_engine *e) {
         return fail(e, VIT_ERR_ARG, "vit_config.hidden_dim: MLP kind %d (VIT_MLP_KIND, bits 24..30): VIT_MLP_GELU (%d), VIT_MLP_SWIGLU (%d) or VIT_MLP_QUICKGELU (%d)",
                     VIT_MLP_KIND(c), VIT_MLP_GELU, VIT_MLP_SWIGLU, VIT_MLP_QUICKGELU);
     if (c->img_size % c->patch_size) return fail(e, VIT_ERR_ARG, "img_size must be a multiple of patch_size");
-    if (c->embed_dim % c->num_heads || c->embed_dim / c->num_heads != 64)
-        return fail(e, VIT_ERR_ARG, "HIP attention kernel needs head_dim == 64 (got %d/%d)", c->embed_dim, c->num_heads);
+    if (c->embed_dim % c->num_heads || vithip_qscale(c->embed_dim / c->num_heads) == 0.0f) /* what the attention kernels take */
+        return fail(e, VIT_ERR_ARG, "HIP attention kernels need head_dim 64 or a multiple of 8 from 72 to 128 (got %d/%d)", c->embed_dim,
+                    c->num_heads);
     if (c->embed_dim % 32 || VIT_HIDDEN_DIM(c) % 32)
         return fail(e, VIT_ERR_ARG, "embed_dim and hidden_dim must be multiples of 32");
     /* what vithip_patch_embed_f32 takes: the 16-byte gather or, for every other even geometry (patch 14), the general kernel */
@@ -594,7 +595,7 @@ static int resolve_operands(vit_engine *e) {
             void *w_qkv = at(e->wfold, (size_t)l * fold_w_elems(&e->cfg), esz), *w_fc1 = at(w_qkv, 3 * (size_t)D * D, esz);
             float *cs_qkv = e->wfoldf + (size_t)l * fold_f_elems(&e->cfg), *b_qkv = cs_qkv + 3 * D, *cs_fc1 = b_qkv + 3 * D, *b_fc1 = cs_fc1 + H1;
             if (bf16) { /* in_proj: the Q rows also carry the factor of the scores' exponent (the attention kernels are told: _qscaled) */
-                HIP_TRY(e, vithip_ln_fold_weights_scaled(e->stream, lw[LW_QKV_W], lw[LW_QKV_B], o.ln1_g, o.ln1_b, w_qkv, cs_qkv, b_qkv, 3 * D, D, D, VITHIP_QSCALE));
+                HIP_TRY(e, vithip_ln_fold_weights_scaled(e->stream, lw[LW_QKV_W], lw[LW_QKV_B], o.ln1_g, o.ln1_b, w_qkv, cs_qkv, b_qkv, 3 * D, D, D, vithip_qscale(D / e->cfg.num_heads)));
                 HIP_TRY(e, vithip_ln_fold_weights(e->stream, lw[LW_FC1_W], lw[LW_FC1_B], o.ln2_g, o.ln2_b, w_fc1, cs_fc1, b_fc1, H1, D));
             } else { /* fp32 products, sums in double, rounded once; centred weights (vit_hip_kernels.h): the GEMMs deliver
                       * x . (gamma W)^T - mean * colsum themselves and their epilogues only scale, so no column sums are passed on:
@@ -1087,11 +1088,9 @@ static int encoder_layer(chunk_ctx *c, int l) {
     for (int j = 0; j < c->L; ++j) { /* scores, softmax, P.V (ViT_seq.c:156-215) -> y; pruned: for the class rows */
         const vit_lane *ln = &c->lane[j];
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_ATTN));
-        if (!bf16 && pruned) HIP_TRY(e, vithip_attention_f32_rows(ln->s, ln->qkv, ln->y, ln->n, T, heads, 1));
-        else if (!bf16) HIP_TRY(e, vithip_attention_f32(ln->s, ln->qkv, ln->y, ln->n, T, heads));
-        else if (fold) HIP_TRY(e, vithip_attention_bf16io_qscaled(ln->s, ln->qkv, ln->y, ln->n, T, heads, pruned ? 1 : T));
-        else if (pruned) HIP_TRY(e, vithip_attention_bf16io_rows(ln->s, ln->qkv, ln->y, ln->n, T, heads, 1));
-        else HIP_TRY(e, vithip_attention_bf16io(ln->s, ln->qkv, ln->y, ln->n, T, heads));
+        /* head_dim 64: the entries these generalise (_f32 / _f32_rows, _bf16io / _rows / _qscaled), their launches and their bits */
+        if (!bf16) HIP_TRY(e, vithip_attention_f32_hd(ln->s, ln->qkv, ln->y, ln->n, T, heads, D / heads, pruned ? 1 : T));
+        else HIP_TRY(e, vithip_attention_bf16io_hd(ln->s, ln->qkv, ln->y, ln->n, T, heads, D / heads, pruned ? 1 : T, fold));
         HIP_TRY(e, stage_end(e, ln->s));
     }
     for (int j = 0; j < c->L; ++j) { /* out_proj + residual (ViT_seq.c:219-227,286-288): x += y . Wo^T + bo; folded, it also
@@ -1264,20 +1263,20 @@ static int stage_features(chunk_ctx *c, const vit_output *out) {
 
 /* The class token's attention of the last layer instead of everything behind its in_proj: one launch per lane over the lane's qkv
  * rows as encoder_layer (qkv_only) left them -- Q of the class rows at row step T, K of every token; bf16 fold engines keep
- * VITHIP_QSCALE * q there.  Nothing has written those rows since: the fold's statistics live in other allocations (fp32) or in the
+ * vithip_qscale(head_dim) * q there.  Nothing has written those rows since: the fold's statistics live in other allocations (fp32) or in the
  * upper half of qkv's (bf16; chunk_setup), and the next writer is the next chunk's first in_proj on the same streams. */
 static int stage_cls_attention(chunk_ctx *c, const vit_output *out) {
     vit_engine *e = c->e;
-    const int heads = e->cfg.num_heads, mean = out->attn_kind == VIT_ATTN_HEAD_MEAN;
+    const int heads = e->cfg.num_heads, hd = c->D / heads, mean = out->attn_kind == VIT_ATTN_HEAD_MEAN;
     const size_t row = out_row_elems(e, out), ld = 3 * (size_t)c->D;
     for (int j = 0; j < c->L; ++j) {
         const vit_lane *ln = &c->lane[j];
         float *dst = out->dst + (size_t)ln->off * row;
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_ATTN));
         if (e->opt.dtype == VIT_DTYPE_BF16)
-            HIP_TRY(e, vithip_cls_attention_bf16(ln->s, (const unsigned short *)ln->qkv, ld, dst, row, ln->n, c->T, heads, mean, e->fold));
+            HIP_TRY(e, vithip_cls_attention_bf16_hd(ln->s, (const unsigned short *)ln->qkv, ld, dst, row, ln->n, c->T, heads, hd, mean, e->fold));
         else
-            HIP_TRY(e, vithip_cls_attention_f32(ln->s, (const float *)ln->qkv, ld, dst, row, ln->n, c->T, heads, mean));
+            HIP_TRY(e, vithip_cls_attention_f32_hd(ln->s, (const float *)ln->qkv, ld, dst, row, ln->n, c->T, heads, hd, mean));
         HIP_TRY(e, stage_end(e, ln->s));
     }
     return VIT_OK;

@@ -126,6 +126,11 @@ VIT_G14 = ModelConfig(img_size=224, patch_size=14, embed_dim=1536, depth=40, num
 # CLIP image towers (OpenAI ViT-B/16 and ViT-L/14): QuickGELU; num_classes is the projection width (the head slot holds visual_projection)
 CLIP_B16 = ModelConfig(num_classes=512, mlp="quickgelu")
 CLIP_L14 = ModelConfig(patch_size=14, num_classes=768, embed_dim=1024, depth=24, num_heads=16, hidden_dim=4096, mlp="quickgelu")
+# head_dim 80: ViT-H/14 (MAE ViT-H, timm vit_huge_patch14_224) and the OpenCLIP ViT-H-14 image tower (erf-GELU, projection 1024);
+# head_dim 104: OpenCLIP ViT-bigG-14 (projection 1280).  Attention: csrc/vit_attention_hd.hip
+VIT_H14 = ModelConfig(patch_size=14, embed_dim=1280, depth=32, num_heads=16, hidden_dim=5120)
+CLIP_H14 = ModelConfig(patch_size=14, num_classes=1024, embed_dim=1280, depth=32, num_heads=16, hidden_dim=5120)
+CLIP_BIGG14 = ModelConfig(patch_size=14, num_classes=1280, embed_dim=1664, depth=48, num_heads=16, hidden_dim=8192)
 # reduced models for fast live-oracle parity (head_dim stays 64 as in ViT-B/L)
 VIT_TINY = ModelConfig(img_size=32, num_classes=10, embed_dim=128, depth=2, num_heads=2, hidden_dim=256)
 VIT_SMALL = ModelConfig(img_size=64, num_classes=100, embed_dim=192, depth=3, num_heads=3, hidden_dim=768)
