@@ -36,7 +36,7 @@
 
 namespace vitgemm {
 int launch_persistent(hipStream_t stream, GemmParams &p, int epilogue, int group_m, int arith = ARITH_F32);  // vit_gemm_persistent.hip
-int launch_persistent_stamped(hipStream_t stream, GemmParams &p, int epilogue, int group_m);
+int launch_persistent_stamped(hipStream_t stream, GemmParams &p, int epilogue, int group_m, int arith = ARITH_F32);
 int launch_persistent_switchoff(hipStream_t stream, GemmParams &p, int epilogue, int group_m, int dbg);  // probe build
 int persistent_piece_steps(int M, int N, int K, int slots, int wgs, int kstep);
 }
@@ -450,6 +450,12 @@ int dispatch(hipStream_t stream, GemmParams &p, int epilogue, int tile, int grou
 #ifdef VIT_PROBES
     if (g_gemm_tile) tile = g_gemm_tile;
     if (g_gemm_group) p.group_m = g_gemm_group;
+    if constexpr (AMODE == A_DENSE && SPLIT) {  // the stamped image walk (tools/gemm_f32_split_stamps.py)
+        if (tile == 129) {
+            p.dbg = g_gemm_dbg;
+            return g_gemm_dbg ? vitgemm::launch_persistent_stamped(stream, p, epilogue, p.group_m, ARITH) : static_cast<int>(hipErrorInvalidValue);
+        }
+    }
     if constexpr (AMODE == A_DENSE && !SPLIT) {
         switch (tile) {  // timing-only probes, never selected by the engine
             case 101: return launch_probe<1>(stream, p);

@@ -300,6 +300,17 @@ __device__ __forceinline__ u32x4 split3_piece8(f32x4 &x0, f32x4 &x1, int piece) 
     return u32x4{p0[0], p0[1], p1[0], p1[1]};
 }
 
+// piece `piece` of two values, value by value the arithmetic of split3_piece: a quarter of a plane chunk, for the image walk's
+// finer restage slots
+__device__ __forceinline__ unsigned split3_piece2(f32x2 &x, int piece) {
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    bf16x2 b;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) b[e] = (__bf16)x[e];
+    if (piece < 2) x = x - f32x2{bf16_to_f32(b[0]), bf16_to_f32(b[1])};  // exact
+    return __builtin_bit_cast(unsigned, b);
+}
+
 // ---- pre-split weights (vithip_gemm_args.w_split) and the swizzled LDS rows of the walk that reads them --------------------------
 // Image of W [N][K]: one block per (128-row panel, 16-deep K step), panel-major, K steps ascending inside a panel.  A block is
 // 3 planes x 128 rows x 16 bf16; its 16-byte chunk c = plane * 256 + 2 * row + half holds k 8 half .. 8 half + 7 of one plane of
@@ -357,9 +368,13 @@ __device__ __forceinline__ void split3_step(f32x16 (&acc)[TM][TN], const float *
 // the lane's float offset of its chunk (2 piece + h) inside that row (the same for every block: blocks are 32 rows apart and the
 // swizzle repeats every 16).  restage(q), q < NS, goes right behind matrix instruction floor(q * NM / NS): spread over the whole
 // step, with the last slot a few instructions ahead of the barrier.
-template <int TM, int TN, int NS, typename Restage>
+struct Split3NoHook {
+    __device__ __forceinline__ void operator()() const {}
+};
+// landed(): a hook between the fragment reads and the first matrix instruction (the stamped probe instantiation; nothing otherwise)
+template <int TM, int TN, int NS, typename Restage, typename Landed = Split3NoHook>
 __device__ __forceinline__ void split3_step_sw(f32x16 (&acc)[TM][TN], const float *As, const float *Bs, const int (&poff)[3],
-                                               Restage &&restage) {
+                                               Restage &&restage, Landed &&landed = Landed{}) {
     bf16x8 a[TM][3], b[TN][3];
 #pragma unroll
     for (int o = 0; o < 3; ++o) {
@@ -369,6 +384,7 @@ __device__ __forceinline__ void split3_step_sw(f32x16 (&acc)[TM][TN], const floa
 #pragma unroll
         for (int j = 0; j < TN; ++j) b[j][pb] = *reinterpret_cast<const bf16x8 *>(Bs + j * 32 * SPLIT_LD_SW + poff[pb]);
     }
+    landed();
     __builtin_amdgcn_sched_barrier(0);
     constexpr int NM = 6 * TM * TN;
     static_assert(NS <= NM, "one restage slot per matrix instruction at most");
@@ -383,6 +399,127 @@ __device__ __forceinline__ void split3_step_sw(f32x16 (&acc)[TM][TN], const floa
             for (int q = slot_before; q < slot_after; ++q) restage(q);
             __builtin_amdgcn_sched_barrier(0);
         }
+    }
+}
+
+// ---- the pipelined step of the image walk: the fragments of step g + 1 are read under the matrix instructions of step g ----------
+// Two LDS buffers and one barrier per step as before, but the barrier sits INSIDE the step, behind matrix instruction
+// SPLIT_PF_BARRIER: all restage writes into the other buffer go in front of it, and behind it that buffer holds step g + 1
+// complete, so its twelve fragment reads are issued two per gap under the rest of this step's matrix instructions.  The term order
+// kills the piece registers one after the other (W-lo behind instruction 3, A-lo 7, W-mid 15, A-mid 19, both hi 23 at 2 x 2
+// accumulators), so eight of the twelve reads land in registers that are already dead; the two hi pieces, live to the step's
+// end, are read into a spare set and moved over at the step's end.  A segment's first step reads its fragments at its top
+// (split3_read_cold) and its last step (PF = false) prefetches nothing: no fragment is live across an epilogue, where the
+// register count peaks.
+struct Split3PfRead { int w, piece, behind; };  // operand (0 = A, 1 = W), piece, the matrix instruction its reads go behind
+constexpr int SPLIT_PF_BARRIER = 15;
+// both hi first (the moves out of the spare set at the next step's top wait for them), then in the order the next step's terms
+// need the rest: (hi, lo) (lo, hi) (mid, mid)
+constexpr Split3PfRead SPLIT_PF_READS[6] = {{0, 0, 15}, {1, 0, 16}, {1, 2, 17}, {0, 2, 18}, {0, 1, 19}, {1, 1, 20}};
+// restage slots of the pipelined step: slot q goes behind matrix instruction at(q)
+struct Split3SlotsCoarse {  // the six slots of restage_slot (A plane, W plane, alternating)
+    static constexpr int N = 6;
+    static constexpr int at(int q) { return (q * (SPLIT_PF_BARRIER + 1)) / N; }
+};
+// Finer slots (restage_fine of the walk): A's split in quarters of a plane (two values: 4 vector instructions for hi and mid, 1
+// for lo), so that no gap between two matrix instructions carries more than 4 of them plus one LDS write or one global load.
+//   q 0-3 hi quarters, 4 hi write | 5-8 mid quarters, 9 mid write | 10, 11 lo halves, 12 lo write | 13, 14 the loads of A
+//   15-17 W plane writes | 18-20 W image loads (each behind its plane's write)
+struct Split3SlotsFine {
+    static constexpr int N = 21;
+    static constexpr int at(int q) {
+        constexpr int gap[N] = {0, 1, 2, 3, 4, 4, 5, 6, 7, 8, 8, 9, 10, 12, 13, 1, 5, 9, 2, 6, 11};
+        return gap[q];
+    }
+};
+// last matrix instruction (of 6 x per_term) that reads piece `piece` of operand w
+constexpr int split3_last_use(int w, int piece, int per_term) {
+    int last = -1;
+    for (int t = 0; t < 6; ++t)
+        if ((w ? SPLIT_TERM_W[t] : SPLIT_TERM_A[t]) == piece) last = (t + 1) * per_term - 1;
+    return last;
+}
+template <class Slots>
+constexpr bool split3_pf_schedule_ok(int per_term) {
+    for (int q = 0; q < Slots::N; ++q)  // every restage write in front of the barrier
+        if (Slots::at(q) < 0 || Slots::at(q) > SPLIT_PF_BARRIER) return false;
+    bool seen[2][3] = {};
+    for (int e = 0; e < 6; ++e) {
+        const Split3PfRead rd = SPLIT_PF_READS[e];
+        if (rd.behind < SPLIT_PF_BARRIER || rd.behind >= 6 * per_term) return false;  // every read of the other buffer behind it
+        // mid and lo are overwritten in place: behind their last use (hi goes to the other set)
+        if (rd.piece != 0 && rd.behind < split3_last_use(rd.w, rd.piece, per_term)) return false;
+        if (e > 0 && rd.behind < SPLIT_PF_READS[e - 1].behind) return false;
+        seen[rd.w][rd.piece] = true;
+    }
+    for (int w = 0; w < 2; ++w)
+        for (int pc = 0; pc < 3; ++pc)
+            if (!seen[w][pc]) return false;
+    return true;
+}
+template <int TM, int TN>
+struct Split3Frags {
+    bf16x8 a[TM][3], b[TN][3];  // the step's pieces; mid and lo of the next step are read in place
+    bf16x8 a_hn[TM], b_hn[TN];  // hi of the next step (hi of this one is live to the step's last matrix instruction)
+};
+// the reads of entry e of SPLIT_PF_READS from the tiles As / Bs; NEXT: hi goes to the spare set
+template <int TM, int TN, bool NEXT>
+__device__ __forceinline__ void split3_read_piece(Split3Frags<TM, TN> &f, const float *As, const float *Bs, const int (&poff)[3], int e) {
+    const Split3PfRead rd = SPLIT_PF_READS[e];
+    if (rd.w == 0) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const bf16x8 v = *reinterpret_cast<const bf16x8 *>(As + i * 32 * SPLIT_LD_SW + poff[rd.piece]);
+            if (NEXT && rd.piece == 0) f.a_hn[i] = v;
+            else f.a[i][rd.piece] = v;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const bf16x8 v = *reinterpret_cast<const bf16x8 *>(Bs + j * 32 * SPLIT_LD_SW + poff[rd.piece]);
+            if (NEXT && rd.piece == 0) f.b_hn[j] = v;
+            else f.b[j][rd.piece] = v;
+        }
+    }
+}
+// A segment's first step: its fragments from its own buffer (As / Bs), read at the top, in the order the prefetch reads them
+template <int TM, int TN>
+__device__ __forceinline__ void split3_read_cold(Split3Frags<TM, TN> &f, const float *As, const float *Bs, const int (&poff)[3]) {
+#pragma unroll
+    for (int e = 0; e < 6; ++e) split3_read_piece<TM, TN, false>(f, As, Bs, poff, e);
+}
+// One step from the fragments in f; restage(q), q < Slots::N, behind matrix instruction Slots::at(q); sync() is the step's
+// barrier; PF: the fragments of the next step from the other buffer (An / Bn) into f; landed(): as in split3_step_sw.
+template <int TM, int TN, bool PF, class Slots, typename Restage, typename Sync, typename Landed = Split3NoHook>
+__device__ __forceinline__ void split3_step_pf(f32x16 (&acc)[TM][TN], Split3Frags<TM, TN> &f, const float *An, const float *Bn,
+                                               const int (&poff)[3], Restage &&restage, Sync &&sync, Landed &&landed = Landed{}) {
+    constexpr int NM = 6 * TM * TN;
+    static_assert(NM == 24, "the schedule table is laid out for 2 x 2 accumulators");
+    static_assert(split3_pf_schedule_ok<Slots>(TM * TN),
+                  "restage writes in front of the barrier, reads of the other buffer behind it and behind the last use of what they overwrite");
+    landed();
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int idx = 0; idx < NM; ++idx) {
+        const int t = idx / (TM * TN), i = (idx / TN) % TM, j = idx % TN;
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[i][SPLIT_TERM_A[t]], f.b[j][SPLIT_TERM_W[t]], acc[i][j], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < Slots::N; ++q)
+            if (Slots::at(q) == idx) restage(q);
+        if (idx == SPLIT_PF_BARRIER) sync();
+        if constexpr (PF) {
+#pragma unroll
+            for (int e = 0; e < 6; ++e)
+                if (SPLIT_PF_READS[e].behind == idx) split3_read_piece<TM, TN, true>(f, An, Bn, poff, e);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (PF) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i) f.a[i][0] = f.a_hn[i];
+#pragma unroll
+        for (int j = 0; j < TN; ++j) f.b[j][0] = f.b_hn[j];
     }
 }
 

@@ -35,7 +35,28 @@
 // workspace (vithip_gemm_f32_workspace_stats): a recomputed piece costs x K-steps of one workgroup, never a wrong bit.
 #include "vit_gemm_common.hpp"
 
+// The image walk's step: SPLIT_STEP_PREFETCH = 1 reads the fragments of step g + 1 under the matrix instructions
+// of step g (split3_step_pf), 0 is the step that reads them behind its barrier (split3_step_sw).  -DSPLIT_STEP_PLAIN builds the
+// latter: the "before" arm of tools/build_variant.sh from the same tree.  The same bits either way.
+#ifdef SPLIT_STEP_PLAIN
+#undef SPLIT_STEP_PREFETCH
+#define SPLIT_STEP_PREFETCH 0
+#endif
+#ifndef SPLIT_STEP_PREFETCH
+#define SPLIT_STEP_PREFETCH 1
+#endif
+// SPLIT_STEP_FINE = 1: A's split dealt out over the gaps in quarters of a plane (Split3SlotsFine) instead of a plane per slot
+#ifdef SPLIT_STEP_PLAIN
+#undef SPLIT_STEP_FINE
+#define SPLIT_STEP_FINE 0
+#endif
+#ifndef SPLIT_STEP_FINE
+#define SPLIT_STEP_FINE 1
+#endif
+
 namespace vitgemm {
+
+using SplitSlots = std::conditional_t<SPLIT_STEP_FINE != 0, Split3SlotsFine, Split3SlotsCoarse>;
 
 constexpr int PBK = 32;           // K step
 constexpr int PLD = PBK + 4;      // padded LDS row (floats)
@@ -54,12 +75,18 @@ constexpr int SK_HEADER_BYTES = 4096, SK_MAX_OWNERS = 1000, SK_STAT_TAKEN = 1016
 // into three 16-byte plane chunks) and three 16-byte image chunks of W, all written with ds_write_b128 into swizzled rows of
 // SPLIT_LD_SW floats (64 KB), conflict-free (see split_swizzle).  Six restage slots (A plane, W plane, alternating) spread over
 // all 24 matrix instructions of the step.  The same pieces in the same places of the product: the same bits as WIMG = false.
+// That is the plain step (split3_step_sw).  The default build deals A's split out in quarters of a plane over the first 14 gaps
+// (restage_fine) and, except under the residual epilogues, reads the fragments of the next step under this step's matrix
+// instructions (PIPE, split3_step_pf); the switches are at the head of this file.
 template <int BM, int BN, int WM, int WN, int EPI, bool STAMP = false, bool SK = false, int DBG = 0, int ARITH = ARITH_F32,
           bool WIMG = false>
 __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const GemmParams p) {
     constexpr bool SPLIT = ARITH == ARITH_SPLIT3;
     static_assert(!SPLIT || DBG == 0, "switch-off builds are fp32 only");
-    static_assert(!WIMG || (SPLIT && BM == WIMG_ROWS && BN == WIMG_ROWS && !STAMP), "the weight image feeds the 128x128 split walk");
+    static_assert(!WIMG || (SPLIT && BM == WIMG_ROWS && BN == WIMG_ROWS), "the weight image feeds the 128x128 split walk");
+    // The pipelined step pays under the fold consumers' walks (QKV, fc1) and not under the residual ones (out_proj, fc2), which are
+    // faster with the finer slots alone: measured per launch at batch 256, profiles/r21.
+    constexpr bool PIPE = WIMG && SPLIT_STEP_PREFETCH != 0 && EPI != VITHIP_EPI_BIAS_RESIDUAL && EPI != EPI_RESIDUAL_STATS;
     constexpr int PBK = SPLIT ? SPLIT_BK : vitgemm::PBK;  // K step
     constexpr int PLD = WIMG ? SPLIT_LD_SW : SPLIT ? SPLIT_LD : vitgemm::PLD;  // LDS row (floats)
     constexpr int ROWS_PER_PASS = 256 / (PBK / 4);
@@ -100,6 +127,21 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
     const int wm = wave / WGN, wn = wave % WGN;
 
     unsigned long long st0 = 0, st_rt0 = 0, st_loop0 = 0, st_epi = 0;
+    // WIMG stamps: the sum over the K steps of the cycles from the step's top (the plain step: leaving its barrier) to the point in
+    // front of its first matrix instruction where its twelve fragments have landed
+    [[maybe_unused]] unsigned long long st_frag = 0, st_top = 0, st_landed = 0;
+    auto stamp_top = [&]() __attribute__((always_inline)) {
+        if constexpr (STAMP && WIMG) st_top = __builtin_amdgcn_s_memtime();
+    };
+    auto stamp_landed = [&]() __attribute__((always_inline)) {
+        if constexpr (STAMP && WIMG) {
+            __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0), nothing else
+            st_landed = __builtin_amdgcn_s_memtime();
+        }
+    };
+    auto stamp_step = [&]() __attribute__((always_inline)) {
+        if constexpr (STAMP && WIMG) st_frag += st_landed - st_top;
+    };
     if constexpr (STAMP) {
         st0 = __builtin_amdgcn_s_memtime();
         st_rt0 = __builtin_amdgcn_s_memrealtime();
@@ -311,6 +353,41 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
         }
     };
 
+    // the same in Split3SlotsFine's finer slots
+    u32x4 a_plane;  // the plane chunk of A being put together
+    auto restage_fine = [&](int q, int buf, int k0) {
+        if (q <= 12) {
+            const int pl = q / 5, sub = q % 5;  // hi and mid: four quarters and the write; lo: two halves and the write
+            // (the empty asm statements pin a quarter's results to its slot: without them the vectoriser and the sinking passes,
+            // which scheduling fences do not hold, gather the quarters again in front of the plane's write)
+            auto quarter = [&](int s4) __attribute__((always_inline)) {  // values 2 s4, 2 s4 + 1 of the thread's eight
+                f32x4 &x = a_stage[s4 >> 1];
+                const int o = 2 * (s4 & 1);
+                f32x2 xx = {x[o], x[o + 1]};
+                unsigned pc = split3_piece2(xx, pl);
+                asm volatile("" : "+v"(pc), "+v"(xx));
+                x[o] = xx[0];
+                x[o + 1] = xx[1];
+                a_plane[s4] = pc;
+            };
+            if (pl < 2 && sub < 4) quarter(sub);
+            else if (pl == 2 && sub < 2) {
+                quarter(2 * sub);
+                quarter(2 * sub + 1);
+            } else *reinterpret_cast<u32x4 *>(As0 + buf * BM * PLD + wr_off[pl]) = a_plane;
+        } else if (q <= 14) {
+            a_stage[q - 13] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, a_src[q - 13], k0 * 4, 0));
+        } else if (q <= 17) {
+            write_w_plane(Bs0 + buf * BN * PLD, q - 15);
+        } else {
+            w_stage[q - 18] = __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, b_src[q - 18], (k0 / PBK) * WIMG_BLOCK_BYTES, 0);
+        }
+    };
+    auto restage_any = [&](int q, int buf, int k0) __attribute__((always_inline)) {
+        if constexpr (SPLIT_STEP_FINE != 0) restage_fine(q, buf, k0);
+        else restage_slot(q, buf, k0);
+    };
+
     const int a_frag_off = WIMG ? (wm * WM + r) * PLD : (wm * WM + r) * PLD + h * 4;
     const int b_frag_off = WIMG ? (wn * WN + r) * PLD : (wn * WN + r) * PLD + h * 4;
     int frag_poff[3];  // WIMG: the lane's chunk (2 piece + h) inside its rows (the swizzle repeats every 16 rows)
@@ -451,12 +528,21 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
     if (DBG == 4) read_frags(0, 1, 1);
     (void)af; (void)bf;
 
-    if constexpr (STAMP) st_loop0 = __builtin_amdgcn_s_memtime();
-    int cur = 0;
-    for (int g = 0; g < steps; ++g) {
-        const int k_ahead = k_l * PBK;  // offset of the step the restage loads fetch (step g + 2)
+    auto end_segment = [&]() {  // segment finished: store the tile (or park the piece), start the next one
+        unsigned long long e0 = 0;
+        if constexpr (STAMP) e0 = __builtin_amdgcn_s_memtime();
+        if (SK && out_c >= 0) park(out_c);
+        else if (DBG != 1 || p.M < 0) {  // (M < 0: never; keeps the MFMAs alive)
+            if constexpr (EPI == EPI_RESIDUAL_STATS) epilogue_store_residual_stats<BM, BN, WM, WN>(p, acc, bias_r, m0, n0, wm, wn, r, h);
+            else epilogue_store<BM, BN, WM, WN, EPI, A_DENSE>(p, acc, bias_r, m0, n0, wm, wn, r, h, fold);
+        }
+        if constexpr (STAMP) st_epi += __builtin_amdgcn_s_memtime() - e0;
+        if (++seg_c < nseg) begin_segment(seg_c);
+    };
+    // top of a tile's last step (fold consumers): the copy of its rows' pairs has landed (see fold_rows_lds)
+    auto fold_rows_landed = [&]() {
         if constexpr (FOLD) {
-            if (k_c + 1 == kend_c && out_c < 0) {  // the tile's last step: the copy of its rows' pairs has landed (see fold_rows_lds)
+            if (out_c < 0) {
                 // vmcnt retires in order: once at most FOLD_WAIT = 2 * NS operations are outstanding, everything older than the
                 // restage loads of the last two K-steps is done.  The copy was issued before this tile's first restage load, and a
                 // tile of FOLD_MIN_STEPS steps has issued (FOLD_MIN_STEPS - 1) * NS >= FOLD_WAIT + NS of them by now.
@@ -468,10 +554,58 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
         }
-        if constexpr (WIMG) {
+    };
+
+    if constexpr (STAMP) st_loop0 = __builtin_amdgcn_s_memtime();
+    int cur = 0;
+    if constexpr (PIPE) {
+        // The pipelined step (split3_step_pf): segment by segment, so that the fragments are dead at every epilogue by
+        // construction -- a segment's first step reads them at its top, its last step prefetches none.  The load cursor,
+        // the restage slots (all in front of the step's barrier now), the hand-over and the fold's counted wait are the flat
+        // loop's: a step still issues its NL global loads, and the copy is still waited for at the top of the tile's last step.
+        Split3Frags<TM, TN> frags;
+        auto tile_a = [&](int buf) { return As0 + buf * BM * PLD + a_frag_off; };
+        auto tile_b = [&](int buf) { return Bs0 + buf * BN * PLD + b_frag_off; };
+        auto step = [&](auto prefetch) __attribute__((always_inline)) {
+            constexpr bool PF = decltype(prefetch)::value;
+            const int k_ahead = k_l * PBK;  // offset of the step the restage loads fetch (two steps ahead)
+            split3_step_pf<TM, TN, PF, SplitSlots>(acc, frags, tile_a(cur ^ 1), tile_b(cur ^ 1), frag_poff,
+                [&](int q) __attribute__((always_inline)) { restage_any(q, cur ^ 1, k_ahead); }, [] { __syncthreads(); }, stamp_landed);
+            stamp_step();
+            stamp_top();
+            advance_load_cursor();
+            cur ^= 1;
+            ++k_c;
+        };
+        for (;;) {
+            stamp_top();
+            split3_read_cold<TM, TN>(frags, tile_a(cur), tile_b(cur), frag_poff);
+            while (k_c + 1 < kend_c) step(std::true_type{});
+            fold_rows_landed();
+            step(std::false_type{});
+            end_segment();
+            if (seg_c >= nseg) break;
+        }
+    } else
+    for (int g = 0; g < steps; ++g) {
+        const int k_ahead = k_l * PBK;  // offset of the step the restage loads fetch (step g + 2)
+        if (k_c + 1 == kend_c) fold_rows_landed();
+        if constexpr (WIMG && SPLIT_STEP_FINE != 0) {
+            // the plain step's order (fragments behind the barrier, the barrier at the step's end) with the finer slots
+            Split3Frags<TM, TN> frags;
+            stamp_top();
+            split3_read_cold<TM, TN>(frags, As0 + cur * BM * PLD + a_frag_off, Bs0 + cur * BN * PLD + b_frag_off, frag_poff);
+            split3_step_pf<TM, TN, false, SplitSlots>(acc, frags, nullptr, nullptr, frag_poff,
+                [&](int q) __attribute__((always_inline)) { restage_fine(q, cur ^ 1, k_ahead); }, [] {}, stamp_landed);
+            stamp_step();
+            advance_load_cursor();
+            __syncthreads();
+        } else if constexpr (WIMG) {
             // as below, on the swizzled tiles: the six restage slots of step g + 1 / g + 2 spread over all the step's matrix instructions
+            stamp_top();
             split3_step_sw<TM, TN, NSL>(acc, As0 + cur * BM * PLD + a_frag_off, Bs0 + cur * BN * PLD + b_frag_off, frag_poff,
-                                        [&](int q) __attribute__((always_inline)) { restage_slot(q, cur ^ 1, k_ahead); });
+                                        [&](int q) __attribute__((always_inline)) { restage_slot(q, cur ^ 1, k_ahead); }, stamp_landed);
+            stamp_step();
             advance_load_cursor();
             __syncthreads();
         } else if constexpr (SPLIT) {
@@ -510,23 +644,13 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
         }
         cur ^= 1;
 
-        if (++k_c == kend_c) {  // segment finished: store the tile (or park the piece), start the next one
-            unsigned long long e0 = 0;
-            if constexpr (STAMP) e0 = __builtin_amdgcn_s_memtime();
-            if (SK && out_c >= 0) park(out_c);
-            else if (DBG != 1 || p.M < 0) {  // (M < 0: never; keeps the MFMAs alive)
-                if constexpr (EPI == EPI_RESIDUAL_STATS) epilogue_store_residual_stats<BM, BN, WM, WN>(p, acc, bias_r, m0, n0, wm, wn, r, h);
-                else epilogue_store<BM, BN, WM, WN, EPI, A_DENSE>(p, acc, bias_r, m0, n0, wm, wn, r, h, fold);
-            }
-            if constexpr (STAMP) st_epi += __builtin_amdgcn_s_memtime() - e0;
-            if (++seg_c < nseg) begin_segment(seg_c);
-        }
+        if (++k_c == kend_c) end_segment();
     }
     if constexpr (STAMP) {
         const unsigned long long c3 = __builtin_amdgcn_s_memtime(), r3 = __builtin_amdgcn_s_memrealtime();
         if (tid == 0) {
             unsigned long long *d = p.dbg + (size_t)blockIdx.x * 8;
-            d[0] = st0; d[1] = st_loop0; d[2] = st_epi; d[3] = c3; d[4] = st_rt0; d[5] = r3;
+            d[0] = st0; d[1] = st_loop0; d[2] = st_epi; d[3] = c3; d[4] = WIMG ? st_frag : st_rt0; d[5] = r3;
             d[6] = (unsigned long long)nseg; d[7] = (unsigned long long)steps;
         }
     }
@@ -635,7 +759,9 @@ int launch_persistent_tile(hipStream_t stream, GemmParams &p, int epilogue, int 
 
 #ifdef VIT_PROBES
 // Stamped probe build (tools/gemm_probe.py --stamp-tile 129): p.dbg receives 8 x u64 per workgroup.
-int launch_persistent_stamped(hipStream_t stream, GemmParams &p, int epilogue, int group_m) {
+// arith = ARITH_SPLIT3 with a weight image (tools/gemm_f32_split_stamps.py): the image walk, word 4 of a record = the summed
+// fragment waits of its K steps
+int launch_persistent_stamped(hipStream_t stream, GemmParams &p, int epilogue, int group_m, int arith) {
     const int wgs = persistent_wgs();
     if (wgs <= 0) return static_cast<int>(hipErrorInvalidDevice);
     p.tiles_m = (p.M + 127) / 128;
@@ -643,6 +769,19 @@ int launch_persistent_stamped(hipStream_t stream, GemmParams &p, int epilogue, i
     p.group_m = group_m;
     const int total = p.tiles_m * p.tiles_n;
     const dim3 grid(total < wgs ? total : wgs), block(256);
+    if (arith == ARITH_SPLIT3) {
+        if (!p.w_split) return static_cast<int>(hipErrorInvalidValue);
+        p.sk_x = 0;
+        if (epilogue == EPI_BIAS_GELU_LN)
+            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<128, 128, 64, 64, EPI_BIAS_GELU_LN, true, false, 0, ARITH_SPLIT3, true>), grid, block, 0, stream, p);
+        else if (epilogue == EPI_BIAS_LN)
+            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<128, 128, 64, 64, EPI_BIAS_LN, true, false, 0, ARITH_SPLIT3, true>), grid, block, 0, stream, p);
+        else if (epilogue == VITHIP_EPI_BIAS_RESIDUAL)
+            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<128, 128, 64, 64, VITHIP_EPI_BIAS_RESIDUAL, true, false, 0, ARITH_SPLIT3, true>), grid, block, 0, stream, p);
+        else
+            return static_cast<int>(hipErrorInvalidValue);
+        return static_cast<int>(hipGetLastError());
+    }
     if (epilogue == VITHIP_EPI_BIAS_GELU)
         hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<128, 128, 64, 64, VITHIP_EPI_BIAS_GELU, true>), grid, block, 0, stream, p);
     else if (epilogue == EPI_BIAS_GELU_LN)  // the LayerNorm fold's consumer epilogues (tools/gemm_f32_fold_stamps.py)
