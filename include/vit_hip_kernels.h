@@ -259,6 +259,7 @@ int vithip_gather_rows_f32(vithip_stream_t stream, const float *src, size_t src_
 /* LayerNorm with fp32 statistics and a bf16 store; attention reading bf16 Q/K/V [n*tokens][3*heads*64] and
  * writing bf16 [n*tokens][heads*64]: both products on bf16 MFMA with fp32 softmax (P rounded to bf16 once);
  * vithip_attention_bf16io_f32math: same I/O, K/V widened to fp32 in LDS and the fp32 kernel's arithmetic (cross-check).
+ * Which kernel an attention entry runs for which arguments, and what each refuses: the table at the head of csrc/vit_attention.hip.
  * Non-finite values in one row (LayerNorm) / in one image's rows (both attention entries) reach only that row's / that image's
  * outputs; all other outputs have the bits of the same launch on clean data. */
 int vithip_layernorm_f32_bf16out(vithip_stream_t stream, const float *x, size_t ldx, unsigned short *y, size_t ldy,
@@ -276,23 +277,21 @@ int vithip_attention_f32_rows(vithip_stream_t stream, const float *qkv, float *o
                               int q_rows);
 int vithip_attention_bf16io_rows(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out, int n_images,
                                  int tokens, int heads, int q_rows);
-/* As vithip_attention_bf16io (q_rows = tokens) / _rows, for Q columns that already hold VITHIP_QSCALE * q.  For the streamed
- * kernel (225..704 tokens) this removes the scale-and-subtract of every score: the score accumulators start at -max; the
- * resident kernel (up to 224) and the chunked one (beyond 704) take the factor 1 in place of VITHIP_QSCALE.  Non-finite values in
- * one image's rows reach only that image's outputs; all other outputs have the bits of the same launch on clean data. */
+/* As vithip_attention_bf16io (q_rows = tokens) / _rows (q_rows < tokens: tokens <= 224), for Q columns that already hold
+ * VITHIP_QSCALE * q: the kernels then scale no score.  Non-finite values in one image's rows reach only that image's outputs; all
+ * other outputs have the bits of the same launch on clean data. */
 int vithip_attention_bf16io_qscaled(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out, int n_images,
                                     int tokens, int heads, int q_rows);
 /*
- * The attention entries for any accepted head_dim (csrc/vit_attention_hd.hip): 64, and every multiple of 8 from 72 to 128.  The
+ * The attention entries for any accepted head_dim: 64, and every multiple of 8 from 72 to 128 (csrc/vit_attention_hd.hip).  The
  * layout is the one of vithip_attention_f32 / _bf16io with 64 replaced by head_dim: qkv [n*T][3*heads*head_dim], columns [Q | K | V],
  * head h = columns head_dim*h.. of each; out [n*T][heads*head_dim]; scores = q.k / sqrtf(head_dim), row softmax with max
  * subtraction, out = P.V.  Only the first q_rows (1..tokens) query rows of every image are computed and stored.
- *   head_dim == 64: a call of vithip_attention_f32 / _f32_rows, _bf16io / _bf16io_rows / _bf16io_qscaled -- their bits and their
- *     limits (q_rows < tokens needs tokens <= 224).
- *   otherwise: one streaming kernel, any tokens >= 1 and any q_rows; fp32 on v_mfma_f32_32x32x2_f32 with an fp32 softmax; bf16 with
- *     both products on v_mfma_f32_32x32x16_bf16, fp32 scores and softmax, the output rounded to bf16 once; P enters its product in two
- *     bf16 pieces, bf16(p) + bf16(p - bf16(p)), so its rounding (2^-17) stays far below the output's.  The tail of
- *     a contraction that is no multiple of 16 is zero-filled on chip: nothing is read behind column head_dim of a head's slice.
+ *   head_dim == 64: the bits and the limits of vithip_attention_f32 / _f32_rows, _bf16io / _bf16io_rows / _bf16io_qscaled
+ *     (q_rows < tokens needs tokens <= 224).
+ *   otherwise: any tokens >= 1 and any q_rows, heads <= 65535; fp32 arithmetic for fp32, for bf16 both products on the bf16 matrix
+ *     pipe with fp32 scores and softmax and the output rounded to bf16 once.  Nothing is read behind column head_dim of a head's slice.
+ *   The kernels behind both: the table at the head of csrc/vit_attention.hip.
  *   q_scaled = 1 (bf16): the Q columns hold vithip_qscale(head_dim) * q; p = exp2(q.k - max), no further scaling.
  * No atomics; an image's output bits depend on neither the batch size nor its place in the batch; non-finite values in one image's
  * rows reach only that image's outputs; nothing is written outside rows 0..q_rows-1 of an image or behind column heads*head_dim.
@@ -393,8 +392,8 @@ int vithip_swiglu_bf16(vithip_stream_t stream, const unsigned short *u, size_t l
  * Fused scaled-dot-product attention, one workgroup per (image, head) (x blocks of 256 queries when chunked).
  * qkv: [n*T][3*D] rows = tokens, columns [Q | K | V], head h = columns 64h..64h+63 of each.
  * out: [n*T][D].  scores = q.k / sqrtf(64); row softmax with max subtraction; out = P.V.
- * head_dim is 64 here (other head dims: vithip_attention_f32_hd below the bf16 entries).  Up to 224 tokens K and V of one head stay resident in LDS; longer sequences
- * (ViT-L/16-384: 577) stream K/V through LDS in 224-key chunks with an online softmax.
+ * head_dim is 64 here (other head dims: vithip_attention_f32_hd below the bf16 entries); any tokens >= 1.  The kernels by sequence
+ * length: the table at the head of csrc/vit_attention.hip.
  * Non-finite values in one image's rows reach only that image's outputs; all other outputs have the bits of the same launch on
  * clean data.
  */
@@ -571,8 +570,8 @@ int vithip_cls_attention_f32(vithip_stream_t stream, const float *qkv, size_t q_
 int vithip_cls_attention_bf16(vithip_stream_t stream, const unsigned short *qkv, size_t q_row_stride, float *out, size_t ld_out,
                               int n_images, int tokens, int heads, int head_mean, int q_scaled);
 /* The same contract with 64 replaced by head_dim (64, or a multiple of 8 from 72 to 128; anything else: hipErrorInvalidValue):
- * s_t = (q . k_t) / sqrtf(head_dim), q_scaled Q columns hold vithip_qscale(head_dim) * q.  head_dim == 64 is a call of the entries
- * above (their bits); the other head dims run the kernel of csrc/vit_attention_hd.hip. */
+ * s_t = (q . k_t) / sqrtf(head_dim), q_scaled Q columns hold vithip_qscale(head_dim) * q.  head_dim == 64 gives the bits of the
+ * entries above; all four are one kernel and one launcher (csrc/vit_cls_attention.hip). */
 int vithip_cls_attention_f32_hd(vithip_stream_t stream, const float *qkv, size_t q_row_stride, float *out, size_t ld_out, int n_images,
                                 int tokens, int heads, int head_dim, int head_mean);
 int vithip_cls_attention_bf16_hd(vithip_stream_t stream, const unsigned short *qkv, size_t q_row_stride, float *out, size_t ld_out,

@@ -412,3 +412,16 @@ def test_cls_kernel_isolation_and_footprint(dtype):
     assert entry(None, dq.ptr, 3 * D - 8, do.ptr, heads * T, n, T, heads, hd, 0, *extra) == INVALID
     assert entry(None, None, 3 * D, do.ptr, heads * T, n, T, heads, hd, 0, *extra) == INVALID
     assert (do.numpy() == 7.0).all()
+
+
+@pytest.mark.parametrize("head_mean", [False, True], ids=["heads", "head-mean"])
+@pytest.mark.parametrize("T", [17, 197])
+def test_cls_head_dim_64_is_the_existing_entry(T, head_mean):
+    """The class-row _hd entries with head_dim 64 give the bits of vithip_cls_attention_f32 / _bf16."""
+    heads, n = 3, 2
+    vals = u(140 + T, (n * T, 3 * heads * 64), 1.5)
+    bits = B.to_bf16_bits(vals)
+    assert same_bits(B.cls_attention_hd(vals, n, T, heads, 64, head_mean=head_mean), B.cls_attention(vals, n, T, heads, head_mean=head_mean))
+    for q_scaled in (False, True):
+        got = B.cls_attention_bf16_hd(bits, n, T, heads, 64, head_mean=head_mean, q_scaled=q_scaled)
+        assert same_bits(got, B.cls_attention_bf16(bits, n, T, heads, head_mean=head_mean, q_scaled=q_scaled)), q_scaled

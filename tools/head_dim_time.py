@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """Attention at head dims other than 64 against the head_dim 64 kernels at equal MACs (GPU box only).
 
-    python3 tools/head_dim_time.py [--steps K] [--warmup W] [--batch N] [--parts kernel,engine] [--out FILE.jsonl]
+    python3 tools/head_dim_time.py [--steps K] [--warmup W] [--batch N] [--parts kernel,cls,engine] [--out FILE.jsonl]
 
 kernel  one attention launch at batch N (default 256), 257 tokens: 16 heads x 80 (ViT-H/14) beside 20 heads x 64, and 16 x 104
         (ViT-bigG-14) beside 26 x 64 -- the same D, so the same multiply-adds in both products -- fp32 and bf16 (q_scaled, the engine's
         default).  Random U(-1.5, 1.5) operands; the legs of a pair alternate sample by sample in one process, a sample is `reps`
         back-to-back launches between device events.  One JSON line per leg (median, min, max ms per launch) and the ratio of medians.
+cls     the class token's attention row (vithip_cls_attention_*_hd, per head) on the same pairs of shapes, fp32 and bf16, timed the
+        same way with 20 launches per sample.
 engine  synth.VIT_H14 forward_device at batch 64 with the profile on, fp32 and bf16: ms per call and the stage table, with the share
         of the attention stage.
 """
@@ -33,9 +35,9 @@ def emit(out, rec):
         out.flush()
 
 
-def kernel_part(B, a, out):
+def kernel_part(B, a, out, cls=False):
     L = B.lib()
-    n, T, reps = a.batch, 257, 5
+    n, T, reps = a.batch, 257, 20 if cls else 5
     ev = [C.c_void_p(), C.c_void_p()]
     for e in ev:
         B.hip_check(L.vithip_event_create(C.byref(e)), "event_create")
@@ -47,7 +49,14 @@ def kernel_part(B, a, out):
             vals = rng.uniform(-1.5, 1.5, (n * T, 3 * D)).astype(np.float32)
             d_q = B.DeviceArray.from_numpy(vals if dtype == "f32" else B.to_bf16_bits(vals))
             d_o = B.DeviceArray((n * T, D), np.float32 if dtype == "f32" else np.uint16)
-            if dtype == "f32":
+            if cls:
+                d_o.free()
+                d_o = B.DeviceArray((n, max(heads, heads64) * T))
+                fn = L.vithip_cls_attention_f32_hd if dtype == "f32" else L.vithip_cls_attention_bf16_hd
+                tail = () if dtype == "f32" else (0,)
+                legs = {f"{heads}x{hd}": lambda: fn(None, d_q.ptr, 3 * D, d_o.ptr, heads * T, n, T, heads, hd, 0, *tail),
+                        f"{heads64}x64": lambda: fn(None, d_q.ptr, 3 * D, d_o.ptr, heads64 * T, n, T, heads64, 64, 0, *tail)}
+            elif dtype == "f32":
                 legs = {f"{heads}x{hd}": lambda: L.vithip_attention_f32_hd(None, d_q.ptr, d_o.ptr, n, T, heads, hd, T),
                         f"{heads64}x64": lambda: L.vithip_attention_f32_hd(None, d_q.ptr, d_o.ptr, n, T, heads64, 64, T)}
             else:
@@ -66,12 +75,15 @@ def kernel_part(B, a, out):
                     if step >= a.warmup:
                         ms[leg].append(t.value / reps)
             macs = 2 * n * heads * T * T * hd  # both products
+            part = "cls" if cls else "kernel"
             for leg in order:
                 med = statistics.median(ms[leg])
-                emit(out, {"part": "kernel", "dtype": dtype, "shape": leg, "images": n, "tokens": T, "reps_per_sample": reps,
-                           "median_ms": round(med, 4), "min_ms": round(min(ms[leg]), 4), "max_ms": round(max(ms[leg]), 4),
-                           "steps": len(ms[leg]), "TFLOPs": round(2 * macs / (med * 1e-3) / 1e12, 1)})
-            emit(out, {"part": "kernel", "dtype": dtype, "pair": order,
+                rate = {"K_GBps": round(n * T * D * (4 if dtype == "f32" else 2) / (med * 1e-3) / 1e9, 1)} if cls else \
+                       {"TFLOPs": round(2 * macs / (med * 1e-3) / 1e12, 1)}
+                emit(out, dict({"part": part, "dtype": dtype, "shape": leg, "images": n, "tokens": T, "reps_per_sample": reps,
+                                "median_ms": round(med, 4), "min_ms": round(min(ms[leg]), 4), "max_ms": round(max(ms[leg]), 4),
+                                "steps": len(ms[leg])}, **rate))
+            emit(out, {"part": part, "dtype": dtype, "pair": order,
                        "ratio_of_medians": round(statistics.median(ms[order[0]]) / statistics.median(ms[order[1]]), 3)})
             d_q.free()
             d_o.free()
@@ -121,6 +133,8 @@ def main():
     parts = a.parts.split(",")
     if "kernel" in parts:
         kernel_part(B, a, out)
+    if "cls" in parts:
+        kernel_part(B, a, out, cls=True)
     if "engine" in parts:
         engine_part(pkg, B, a, out)
 

@@ -306,8 +306,6 @@ def lib() -> C.CDLL:
         if hasattr(L, "vit_engine_cls_attention_device"):  # an earlier build (see above) has no attention calls
             L.vit_engine_attention_row_elems.restype = C.c_size_t
             L.vit_engine_attention_row_elems.argtypes = [C.c_void_p, C.POINTER(CAttentionSpec)]
-            L.vithip_cls_attention_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_int] * 4
-            L.vithip_cls_attention_bf16.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_int] * 5
         if hasattr(L, "vit_engine_intermediate_device"):  # an earlier build (see above) has no intermediate calls
             L.vit_engine_intermediate_row_elems.restype = C.c_size_t
             L.vit_engine_intermediate_row_elems.argtypes = [C.c_void_p, C.POINTER(CIntermediateSpec)]
@@ -371,14 +369,22 @@ def lib() -> C.CDLL:
             L.vit_weights_fold_layer_scale.argtypes = [C.POINTER(CConfig), C.POINTER(CNetwork), C.c_int, C.POINTER(CNetwork), C.c_int]
         L.vithip_layernorm_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                            C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-        L.vithip_attention_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+        # the attention entries: (stream, qkv, out) or (stream, qkv, row stride, out, ld_out), then ints (include/vit_hip_kernels.h)
+        pv, cls = [C.c_void_p] * 3, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+        for fn in ("vithip_attention_f32", "vithip_attention_bf16io", "vithip_attention_bf16io_f32math"):
+            getattr(L, fn).argtypes = pv + [C.c_int] * 3
+        for fn in ("vithip_attention_f32_rows", "vithip_attention_bf16io_rows", "vithip_attention_bf16io_qscaled"):
+            getattr(L, fn).argtypes = pv + [C.c_int] * 4
+        if hasattr(L, "vit_engine_cls_attention_device"):  # an earlier build (see above) has no attention calls
+            L.vithip_cls_attention_f32.argtypes = cls + [C.c_int] * 4
+            L.vithip_cls_attention_bf16.argtypes = cls + [C.c_int] * 5
         if hasattr(L, "vithip_attention_f32_hd"):  # an earlier build (see above) has head_dim 64 only
             L.vithip_qscale.restype = C.c_float
             L.vithip_qscale.argtypes = [C.c_int]
-            L.vithip_attention_f32_hd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5
-            L.vithip_attention_bf16io_hd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6
-            L.vithip_cls_attention_f32_hd.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_int] * 5
-            L.vithip_cls_attention_bf16_hd.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_int] * 6
+            L.vithip_attention_f32_hd.argtypes = pv + [C.c_int] * 5
+            L.vithip_attention_bf16io_hd.argtypes = pv + [C.c_int] * 6
+            L.vithip_cls_attention_f32_hd.argtypes = cls + [C.c_int] * 5
+            L.vithip_cls_attention_bf16_hd.argtypes = cls + [C.c_int] * 6
         L.vithip_softmax_top1_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                               C.c_void_p, C.c_int, C.c_int]
         L.vithip_event_create.argtypes = [C.POINTER(C.c_void_p)]
@@ -767,22 +773,33 @@ def layernorm_bf16out(x, gamma, beta, ldx: Optional[int] = None, ldy: Optional[i
 QSCALE = 0.18033688011112042  # VITHIP_QSCALE: (1/sqrt(64)) * log2(e)
 
 
+def _attention(name, qkv, n_images, tokens, heads, head_dim, args, fill=0, frames=None, out=None):
+    """The P.V entry `name`(stream, qkv, out, n_images, tokens, heads, *args): qkv [n_images * tokens][3 * heads * head_dim], fp32 or
+    bf16 bits, -> [n_images * tokens][heads * head_dim] of the same type.  Rows the call does not write keep `fill` (with `frames`:
+    the frame's sentinel), and `out` receives the frame "out"."""
+    rows, D = n_images * tokens, heads * head_dim
+    qkv = qkv.reshape(rows, 3 * D)
+    if frames is None:
+        dq, do = _Plain.framed(qkv), _Plain.out_frame(rows, D, dtype=qkv.dtype, preload=np.full((rows, D), fill, qkv.dtype))
+    else:
+        dq, do = frames.framed(qkv), frames.out_frame(rows, D, dtype=qkv.dtype)
+    _note(out, out=do)
+    hip_check(getattr(lib(), name)(None, dq.ptr, do.ptr, n_images, tokens, heads, *args), name)
+    return do.window()
+
+
+def _bits(a) -> np.ndarray:
+    return np.ascontiguousarray(a, np.uint16)
+
+
 def attention_bf16io(qkv_bits, n_images: int, tokens: int, heads: int, f32math: bool = False, q_scaled: bool = False,
                      q_rows: Optional[int] = None) -> np.ndarray:
     """vithip_attention_bf16io (bf16 MFMA), vithip_attention_bf16io_f32math (fp32 arithmetic) or, q_scaled,
     vithip_attention_bf16io_qscaled (the Q columns hold QSCALE * q) -> bf16 bits."""
-    D = heads * 64
-    dq = DeviceArray.from_numpy(np.ascontiguousarray(qkv_bits, np.uint16))
-    do = DeviceArray((n_images * tokens, D), np.uint16)
     if q_scaled:
-        fn = lib().vithip_attention_bf16io_qscaled
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
-        hip_check(fn(None, dq.ptr, do.ptr, n_images, tokens, heads, q_rows or tokens), "vithip_attention_bf16io_qscaled")
-        return do.numpy()
-    fn = getattr(lib(), "vithip_attention_bf16io_f32math" if f32math else "vithip_attention_bf16io")
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
-    hip_check(fn(None, dq.ptr, do.ptr, n_images, tokens, heads), "vithip_attention_bf16io")
-    return do.numpy()
+        return _attention("vithip_attention_bf16io_qscaled", _bits(qkv_bits), n_images, tokens, heads, 64, (q_rows or tokens,))
+    return _attention("vithip_attention_bf16io_f32math" if f32math else "vithip_attention_bf16io", _bits(qkv_bits), n_images, tokens,
+                      heads, 64, ())
 
 
 def layernorm(x, gamma, beta, ldx: Optional[int] = None, ldy: Optional[int] = None, frames=None,
@@ -1016,77 +1033,22 @@ def gather_rows(src, src_stride: Optional[int] = None, dst_stride: Optional[int]
 
 
 def attention(qkv, n_images: int, tokens: int, heads: int) -> np.ndarray:
-    qkv = _as_f32(qkv)
-    D = heads * 64
-    assert qkv.shape == (n_images * tokens, 3 * D)
-    dq = DeviceArray.from_numpy(qkv)
-    do = DeviceArray((n_images * tokens, D))
-    hip_check(lib().vithip_attention_f32(None, dq.ptr, do.ptr, n_images, tokens, heads), "vithip_attention_f32")
-    return do.numpy()
+    return _attention("vithip_attention_f32", _as_f32(qkv), n_images, tokens, heads, 64, ())
 
 
 def attention_rows(qkv, n_images: int, tokens: int, heads: int, q_rows: int, fill: float = 0.0, frames=None,
                    out: Optional[dict] = None) -> np.ndarray:
     """vithip_attention_f32_rows: the output buffer is pre-filled with `fill` to show which rows are written (with `frames`: the
     frame's sentinel instead, and `out` receives the frame "out")."""
-    qkv = _as_f32(qkv)
-    D = heads * 64
-    L = lib()
-    L.vithip_attention_f32_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
-    if frames is None:
-        dq, do = _Plain.framed(qkv), _Plain.out_frame(n_images * tokens, D, preload=np.full((n_images * tokens, D), fill, np.float32))
-    else:
-        dq, do = frames.framed(qkv), frames.out_frame(n_images * tokens, D)
-    _note(out, out=do)
-    hip_check(L.vithip_attention_f32_rows(None, dq.ptr, do.ptr, n_images, tokens, heads, q_rows), "vithip_attention_f32_rows")
-    return do.window()
+    return _attention("vithip_attention_f32_rows", _as_f32(qkv), n_images, tokens, heads, 64, (q_rows,), fill, frames, out)
 
 
 def attention_bf16io_rows(qkv_bits, n_images: int, tokens: int, heads: int, q_rows: int, q_scaled: bool = False, frames=None,
                           out: Optional[dict] = None) -> np.ndarray:
     """vithip_attention_bf16io_rows or, q_scaled, vithip_attention_bf16io_qscaled -> bf16 bits [n * tokens][heads * 64]; rows
     q_rows.. of every image keep what the buffer held (zeros, or the sentinel of `frames`); `out` receives the frame "out"."""
-    F = frames or _Plain
     name = "vithip_attention_bf16io_qscaled" if q_scaled else "vithip_attention_bf16io_rows"
-    fn = getattr(lib(), name)
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
-    dq, do = F.framed(np.ascontiguousarray(qkv_bits, np.uint16)), F.out_frame(n_images * tokens, heads * 64, dtype=np.uint16)
-    _note(out, out=do)
-    hip_check(fn(None, dq.ptr, do.ptr, n_images, tokens, heads, q_rows), name)
-    return do.window()
-
-
-def _cls_attention(fn_name, dq, n_images, tokens, heads, head_mean, ld_out, fill, extra=()):
-    row = tokens if head_mean else heads * tokens
-    ld = row if ld_out is None else int(ld_out)
-    if fill is None:
-        do = DeviceArray((n_images, ld))
-    else:
-        do = DeviceArray.from_numpy(np.full((n_images, ld), fill, np.float32))
-    hip_check(getattr(lib(), fn_name)(None, dq.ptr, 3 * heads * 64, do.ptr, ld, n_images, tokens, heads, int(head_mean), *extra), fn_name)
-    out = do.numpy()
-    if ld_out is not None:
-        return out
-    return out if head_mean else out.reshape(n_images, heads, tokens)
-
-
-def cls_attention(qkv, n_images: int, tokens: int, heads: int, head_mean: bool = False, ld_out: Optional[int] = None,
-                  fill: Optional[float] = None) -> np.ndarray:
-    """vithip_cls_attention_f32: qkv [n_images * tokens][3 * heads * 64] fp32 -> the class rows' softmax [n][heads][tokens], or
-    [n][tokens] with head_mean.  ld_out (>= the row): the raw [n][ld_out] buffer comes back, pre-filled with `fill`, to show what
-    the kernel wrote."""
-    qkv = _as_f32(qkv)
-    assert qkv.shape == (n_images * tokens, 3 * heads * 64)
-    return _cls_attention("vithip_cls_attention_f32", DeviceArray.from_numpy(qkv), n_images, tokens, heads, head_mean, ld_out, fill)
-
-
-def cls_attention_bf16(qkv_bits, n_images: int, tokens: int, heads: int, head_mean: bool = False, q_scaled: bool = False,
-                       ld_out: Optional[int] = None, fill: Optional[float] = None) -> np.ndarray:
-    """vithip_cls_attention_bf16: the same from bf16 bits (uint16); q_scaled: the Q columns hold QSCALE * q.  fp32 out."""
-    qkv_bits = np.ascontiguousarray(qkv_bits, np.uint16)
-    assert qkv_bits.shape == (n_images * tokens, 3 * heads * 64)
-    return _cls_attention("vithip_cls_attention_bf16", DeviceArray.from_numpy(qkv_bits), n_images, tokens, heads, head_mean, ld_out, fill,
-                          (int(q_scaled),))
+    return _attention(name, _bits(qkv_bits), n_images, tokens, heads, 64, (q_rows,), 0, frames, out)
 
 
 def qscale(head_dim: int) -> float:
@@ -1095,61 +1057,63 @@ def qscale(head_dim: int) -> float:
     return float(lib().vithip_qscale(int(head_dim)))
 
 
-def _attention_hd(name, qkv, dtype, n_images, tokens, heads, head_dim, q_rows, fill, frames, out, extra=()):
-    rows, D = n_images * tokens, heads * head_dim
-    assert qkv.shape == (rows, 3 * D)
-    if frames is None:
-        dq, do = _Plain.framed(qkv), _Plain.out_frame(rows, D, dtype=dtype, preload=np.full((rows, D), fill, dtype))
-    else:
-        dq, do = frames.framed(qkv), frames.out_frame(rows, D, dtype=dtype)
-    _note(out, out=do)
-    hip_check(getattr(lib(), name)(None, dq.ptr, do.ptr, n_images, tokens, heads, head_dim, tokens if q_rows is None else q_rows, *extra), name)
-    return do.window()
-
-
 def attention_hd(qkv, n_images: int, tokens: int, heads: int, head_dim: int, q_rows: Optional[int] = None, fill: float = 0.0,
                  frames=None, out: Optional[dict] = None) -> np.ndarray:
     """vithip_attention_f32_hd: qkv [n_images * tokens][3 * heads * head_dim] fp32 -> [n_images * tokens][heads * head_dim]; only
     the first q_rows (default: all) query rows of every image are written, the others keep `fill` (with `frames`: the frame's
     sentinel, and `out` receives the frame "out")."""
-    return _attention_hd("vithip_attention_f32_hd", _as_f32(qkv), np.float32, n_images, tokens, heads, head_dim, q_rows, fill, frames, out)
+    return _attention("vithip_attention_f32_hd", _as_f32(qkv), n_images, tokens, heads, head_dim,
+                      (head_dim, tokens if q_rows is None else q_rows), fill, frames, out)
 
 
 def attention_bf16io_hd(qkv_bits, n_images: int, tokens: int, heads: int, head_dim: int, q_rows: Optional[int] = None,
                         q_scaled: bool = False, fill: int = 0, frames=None, out: Optional[dict] = None) -> np.ndarray:
     """vithip_attention_bf16io_hd: the same on bf16 bits (uint16); q_scaled: the Q columns hold qscale(head_dim) * q."""
-    return _attention_hd("vithip_attention_bf16io_hd", np.ascontiguousarray(qkv_bits, np.uint16), np.uint16, n_images, tokens, heads,
-                         head_dim, q_rows, fill, frames, out, (int(q_scaled),))
+    return _attention("vithip_attention_bf16io_hd", _bits(qkv_bits), n_images, tokens, heads, head_dim,
+                      (head_dim, tokens if q_rows is None else q_rows, int(q_scaled)), fill, frames, out)
 
 
-def _cls_attention_hd(fn_name, dq, n_images, tokens, heads, head_dim, head_mean, ld_out, fill, extra=()):
+def _cls_attention(name, qkv, n_images, tokens, heads, head_dim, head_mean, q_scaled, ld_out, fill):
+    """The class-row entry `name`(stream, qkv, row stride, out, ld_out, n_images, tokens, heads[, head_dim], head_mean[, q_scaled]):
+    head_dim goes to the _hd entries, q_scaled (None for fp32) to the bf16 ones."""
+    assert qkv.shape == (n_images * tokens, 3 * heads * head_dim)
+    args = ((head_dim,) if name.endswith("_hd") else ()) + (int(head_mean),) + (() if q_scaled is None else (int(q_scaled),))
     row = tokens if head_mean else heads * tokens
     ld = row if ld_out is None else int(ld_out)
     do = DeviceArray((n_images, ld)) if fill is None else DeviceArray.from_numpy(np.full((n_images, ld), fill, np.float32))
-    hip_check(getattr(lib(), fn_name)(None, dq.ptr, 3 * heads * head_dim, do.ptr, ld, n_images, tokens, heads, head_dim, int(head_mean),
-                                      *extra), fn_name)
+    dq = DeviceArray.from_numpy(qkv)
+    hip_check(getattr(lib(), name)(None, dq.ptr, 3 * heads * head_dim, do.ptr, ld, n_images, tokens, heads, *args), name)
     res = do.numpy()
     if ld_out is not None:
         return res
     return res if head_mean else res.reshape(n_images, heads, tokens)
 
 
+def cls_attention(qkv, n_images: int, tokens: int, heads: int, head_mean: bool = False, ld_out: Optional[int] = None,
+                  fill: Optional[float] = None) -> np.ndarray:
+    """vithip_cls_attention_f32: qkv [n_images * tokens][3 * heads * 64] fp32 -> the class rows' softmax [n][heads][tokens], or
+    [n][tokens] with head_mean.  ld_out (>= the row): the raw [n][ld_out] buffer comes back, pre-filled with `fill`, to show what
+    the kernel wrote."""
+    return _cls_attention("vithip_cls_attention_f32", _as_f32(qkv), n_images, tokens, heads, 64, head_mean, None, ld_out, fill)
+
+
+def cls_attention_bf16(qkv_bits, n_images: int, tokens: int, heads: int, head_mean: bool = False, q_scaled: bool = False,
+                       ld_out: Optional[int] = None, fill: Optional[float] = None) -> np.ndarray:
+    """vithip_cls_attention_bf16: the same from bf16 bits (uint16); q_scaled: the Q columns hold QSCALE * q.  fp32 out."""
+    return _cls_attention("vithip_cls_attention_bf16", _bits(qkv_bits), n_images, tokens, heads, 64, head_mean, q_scaled, ld_out, fill)
+
+
 def cls_attention_hd(qkv, n_images: int, tokens: int, heads: int, head_dim: int, head_mean: bool = False, ld_out: Optional[int] = None,
                      fill: Optional[float] = None) -> np.ndarray:
     """vithip_cls_attention_f32_hd: cls_attention() for qkv [n_images * tokens][3 * heads * head_dim]."""
-    qkv = _as_f32(qkv)
-    assert qkv.shape == (n_images * tokens, 3 * heads * head_dim)
-    return _cls_attention_hd("vithip_cls_attention_f32_hd", DeviceArray.from_numpy(qkv), n_images, tokens, heads, head_dim, head_mean,
-                             ld_out, fill)
+    return _cls_attention("vithip_cls_attention_f32_hd", _as_f32(qkv), n_images, tokens, heads, head_dim, head_mean, None, ld_out, fill)
 
 
 def cls_attention_bf16_hd(qkv_bits, n_images: int, tokens: int, heads: int, head_dim: int, head_mean: bool = False,
                           q_scaled: bool = False, ld_out: Optional[int] = None, fill: Optional[float] = None) -> np.ndarray:
     """vithip_cls_attention_bf16_hd: the same from bf16 bits (uint16); q_scaled: the Q columns hold qscale(head_dim) * q."""
-    qkv_bits = np.ascontiguousarray(qkv_bits, np.uint16)
-    assert qkv_bits.shape == (n_images * tokens, 3 * heads * head_dim)
-    return _cls_attention_hd("vithip_cls_attention_bf16_hd", DeviceArray.from_numpy(qkv_bits), n_images, tokens, heads, head_dim,
-                             head_mean, ld_out, fill, (int(q_scaled),))
+    return _cls_attention("vithip_cls_attention_bf16_hd", _bits(qkv_bits), n_images, tokens, heads, head_dim, head_mean, q_scaled,
+                          ld_out, fill)
 
 
 def patch_embed(cfg: ModelConfig, images, conv_w, conv_b, cls, pos) -> np.ndarray:

@@ -15,34 +15,53 @@
 //       accumulator is already the B operand of this product (k = lane>>5 selects
 //       key_a / key_a+4), so P goes from softmax to the second MFMA with no data movement.
 // The softmax normaliser is applied to O (32 values per lane) instead of P (112 per lane).
+//
+// ---- Which kernel runs: the routing of the eight vithip_attention_* entries (route() at the end of this file) ----------------------
+//
+// Every entry first asks: head_dim is 64 or a multiple of 8 from 72 to 128; q_scaled is 0 or 1; qkv and out are non-null and
+// 16-byte aligned; n_images, tokens, heads > 0; 0 < q_rows <= tokens.  Anything else is hipErrorInvalidValue.  Then, first match:
+//
+//       element  head_dim   tokens      kernel                                                           file
+//   1   fp32     64         <= 224      attention_f32_resident_kernel (16x16x4 fp32, LDS-DMA)            vit_attention_resident.hip
+//   2   fp32     64         >  224      attention_f32_chunked_kernel<float>                              here
+//   3   bf16     64         <= 224      attention_bf16_kernel<ceil(tokens / 32)> (bf16 MFMA, resident)   here
+//   4   bf16     64         225 - 704   attention_bf16_stream_kernel<q_scaled>                           vit_attention_stream.hip
+//   5   bf16     64         >  704      attention_bf16_chunked_kernel                                    here
+//   6   bf16     64         any         _f32math only: attention_f32_kernel<.., bf16> up to 224 tokens,  here
+//                                       attention_f32_chunked_kernel<bf16> beyond (fp32 arithmetic on bf16 I/O: the cross-check)
+//   7   either   72 - 128   any         attention_hd_kernel<head_dim, bf16, q_scaled>                    vit_attention_hd.hip
+//
+// Only the resident kernels (1, 3, 6 up to 224 tokens) and 7 stop at q_rows; 2, 4 and 5 compute every query row.  So at head_dim 64,
+// q_rows < tokens is refused beyond 224 tokens, whichever entry it came through (_hd with 64 included), and the two _rows entries
+// refuse more than 224 tokens even with q_rows = tokens.  q_scaled (bf16; the Q columns hold vithip_qscale(head_dim) * q) changes no
+// route: 3 and 5 take the factor 1 in place of kScale64, 4 and 7 run their q_scaled instance.  6 takes plain q only.  Route 7 has two
+// limits of its own: heads <= 65535 and n_images * ceil(q_rows / 128) < 2^31 (its grid).
+//
+//   entry                            element  head_dim  q_rows    q_scaled  routes
+//   vithip_attention_f32             fp32     64        tokens    -         1 2
+//   vithip_attention_f32_rows        fp32     64        argument  -         1
+//   vithip_attention_f32_hd          fp32     argument  argument  -         1 2 7
+//   vithip_attention_bf16io          bf16     64        tokens    0         3 4 5
+//   vithip_attention_bf16io_rows     bf16     64        argument  0         3
+//   vithip_attention_bf16io_qscaled  bf16     64        argument  1         3 4 5
+//   vithip_attention_bf16io_f32math  bf16     64        tokens    0         6
+//   vithip_attention_bf16io_hd       bf16     argument  argument  argument  3 4 5 7
+//
+// The class token's attention row (vithip_cls_attention_*) is one kernel for every head_dim and length: vit_cls_attention.hip.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 
+#include "vit_attention.hpp"
 #include "vit_device.hpp"
 #include "vit_hip_kernels.h"
 #ifdef VIT_PROBES
 #include "vit_probes.h"
 #endif
 
-namespace vitattn {
-#ifdef VIT_PROBES
-extern unsigned long long *g_res_dbg;
-extern unsigned long long *g_stream_dbg;
-extern int g_res_mode;
-#endif
-int attention_f32_resident(hipStream_t s, const float *qkv, float *out, int n_images, int tokens, int heads, int q_rows);  // vit_attention_resident.hip
-int attention_bf16_stream(hipStream_t s, const unsigned short *qkv, unsigned short *out, int n_images, int tokens, int heads, bool q_scaled);  // vit_attention_stream.hip
-}
-
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-typedef unsigned short bf16_t;  // raw bf16 bits (bf16 variant of the forward: qkv and the output are bf16,
-                                // scores, softmax and accumulation stay fp32)
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
+using namespace vitattn;
 
 template <typename IO> __device__ __forceinline__ f32x4 load4(const IO *p);
 template <> __device__ __forceinline__ f32x4 load4<float>(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
@@ -189,7 +208,7 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_f32_kernel(const IO *__
             }
         }
         mx = fmaxf(mx, __shfl_xor(mx, 32));
-        constexpr float kScale = 0.125f * 1.4426950408889634f;  // (1/sqrtf(64)) * log2(e)
+        constexpr float kScale = kScale64;
         const float mxs = -mx * kScale;
         float sum = 0.0f;
 #pragma unroll
@@ -306,7 +325,7 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_f32_chunked_kernel(cons
 #pragma unroll
         for (int v = 0; v < 16; ++v) o[dt][v] = 0.0f;
     float m_run = -INFINITY, l_run = 0.0f;  // l_run: this lane half's share of the row sum
-    constexpr float kScale = 0.125f * 1.4426950408889634f;
+    constexpr float kScale = kScale64;
     const int h4 = 4 * h;
 
     const int nchunks = (tokens + CKEYS - 1) / CKEYS;
@@ -441,27 +460,6 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_f32_chunked_kernel(cons
 //     32x32 accumulator, packed to bf16, are exactly the k-step-s fragment whose element j of lane half h
 //     is key 16s + 8(j>>2) + 4h + (j&3) -- the V^T fragment is gathered in that same order.
 // Softmax, max and sums are fp32; P is rounded to bf16 once (the documented cost of the bf16 variant).
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4s;
-typedef short short4v __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) short4v lds_short4v;
-typedef __attribute__((address_space(3))) void lds_void_t;
-
-// A fragment of O^T = V^T . P^T for d-tile dt and the 16 keys starting at key16 (a multiple of 16), in the key order
-// of the P fragment: element j of lane half h is key key16 + 8(j>>2) + 4h + (j&3).  Vs: [keys][64] bf16, swizzled as
-// above.  Per 16-lane group the transposing read takes a block of 4 keys x 16 d: lane 4q+p of the group supplies the
-// address of key row q, d columns 4p..4p+3, lane i receives column i.  EXEC must be all ones (wave-uniform callers).
-__device__ __forceinline__ bf16x8 v_fragment_tr(const bf16_t *Vs, int key16, int dt, int lane) {
-    const int h = lane >> 5, g2 = (lane >> 4) & 1, q = (lane & 15) >> 2, pq = lane & 3;
-    const int row = key16 + 4 * h + q;                     // (row >> 1) & 1 == (q >> 1) & 1: key16 + 4h is a multiple of 4
-    const int chunk = (dt * 4 + 2 * g2 + (pq >> 1)) ^ (4 * ((q >> 1) & 1));
-    const bf16_t *ptr = Vs + row * HD + chunk * 8 + 4 * (pq & 1);
-    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4v *)ptr);
-    const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4v *)(ptr + 8 * HD));
-    typedef short short8v __attribute__((ext_vector_type(8)));
-    const short8v both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, both);
-}
 
 // Persistent: a workgroup walks (image, head) items.  K and V of the NEXT item arrive by LDS-DMA in a second LDS image and its Q
 // fragments in registers while the current item multiplies, so the HBM round trip that used to open every workgroup hides under
@@ -510,8 +508,8 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_bf16_kernel(const bf16_
                 const int row = 8 * piece + (lane >> 3), cp = lane & 7;
                 const int kvoff = row * ld * 2 + ((cp ^ ((row >> 1) & 7)) * 16);
                 const int vvoff = row * ld * 2 + ((cp ^ (4 * ((row >> 1) & 1))) * 16);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (lds_void_t *)(kd + piece * 8 * HD), 16, kvoff, 0, 0, 0);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_void_t *)(vd + piece * 8 * HD), 16, vvoff, 0, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (lds_void *)(kd + piece * 8 * HD), 16, kvoff, 0, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_void *)(vd + piece * 8 * HD), 16, vvoff, 0, 0, 0);
             }
         }
     };
@@ -614,14 +612,14 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_bf16_kernel(const bf16_
                         if constexpr (ATT_PROBE & 4) {  // the conversions and the transposing reads stay, the products go
 #pragma unroll
                             for (int dt = 0; dt < 2; ++dt) {
-                                const bf16x8 vf = v_fragment_tr(Vs, kt * 32 + 16 * s2, dt, lane);
+                                const bf16x8 vf = v_fragment_tr<HD>(Vs, kt * 32 + 16 * s2, dt, lane);
                                 asm volatile("" ::"v"(vf), "v"(pf));
                             }
                             continue;
                         }
 #pragma unroll
                         for (int dt = 0; dt < 2; ++dt)
-                            o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v_fragment_tr(Vs, kt * 32 + 16 * s2, dt, lane), pf, o[dt], 0, 0, 0);
+                            o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v_fragment_tr<HD>(Vs, kt * 32 + 16 * s2, dt, lane), pf, o[dt], 0, 0, 0);
                         lsum = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, pf, lsum, 0, 0, 0);
                     }
                 }
@@ -638,7 +636,7 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_bf16_kernel(const bf16_
                 for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
                     for (int g = 0; g < 4; g += 2) {
-                        bf16x4s w0, w1;
+                        bf16x4 w0, w1;
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
                             w0[q] = (__bf16)(o[dt][4 * g + q] * inv);
@@ -790,7 +788,7 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_bf16_chunked_kernel(con
                     for (int j = 0; j < 8; ++j) pf[j] = (__bf16)st[kt][8 * s2 + j];
 #pragma unroll
                     for (int dt = 0; dt < 2; ++dt)
-                        o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v_fragment_tr(Vs, kt * 32 + 16 * s2, dt, lane), pf, o[dt], 0, 0, 0);
+                        o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v_fragment_tr<HD>(Vs, kt * 32 + 16 * s2, dt, lane), pf, o[dt], 0, 0, 0);
                 }
             }
         }
@@ -813,6 +811,8 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_bf16_chunked_kernel(con
     }
 }
 
+// ---- launches of this file's kernels --------------------------------------------------------------------------------------------
+
 template <int NKT>
 int launch_bf16(hipStream_t s, const bf16_t *qkv, bf16_t *out, int n_images, int tokens, int heads, int q_rows, bool q_scaled) {
     const int items = heads * n_images;
@@ -821,42 +821,62 @@ int launch_bf16(hipStream_t s, const bf16_t *qkv, bf16_t *out, int n_images, int
     const int per_cu = NKT <= 3 ? 2 : 1;  // VGPR-limited residency (8 waves per workgroup)
     const int grid = items < cus * per_cu ? items : cus * per_cu;
     hipLaunchKernelGGL(attention_bf16_kernel<NKT>, dim3(grid), dim3(ATT_THREADS), 0, s, qkv, out, tokens, heads, items, q_rows,
-                       q_scaled ? 1.0f : 0.125f * 1.4426950408889634f);
+                       q_scaled ? 1.0f : kScale64);
     return static_cast<int>(hipGetLastError());
 }
 
 template <int NKT, typename IO>
-int launch(hipStream_t s, const IO *qkv, IO *out, int n_images, int tokens, int heads, int q_rows) {
+int launch_f32(hipStream_t s, const IO *qkv, IO *out, int n_images, int tokens, int heads, int q_rows) {
     hipLaunchKernelGGL((attention_f32_kernel<NKT, IO>), dim3(heads, n_images), dim3(ATT_THREADS), 0, s, qkv, out,
                        tokens, heads, q_rows, g_attn_dbg);
     return static_cast<int>(hipGetLastError());
 }
 
+inline dim3 chunked_grid(int n_images, int tokens, int heads) {  // a block of 8 query tiles per workgroup
+    return dim3(heads, n_images, ((tokens + 31) / 32 + ATT_WAVES - 1) / ATT_WAVES);
+}
+
+// ---- the router: rows 1-2 and 6 of the table at the head of this file (IO = float: 1-2, IO = bf16 bits: 6) ---------------------------
 template <typename IO>
-int attention_dispatch(hipStream_t s, const IO *qkv, IO *out, int n_images, int tokens, int heads, int q_rows) {
-    if (!qkv || !out || n_images <= 0 || tokens <= 0 || heads <= 0 || q_rows <= 0 || q_rows > tokens)
-        return static_cast<int>(hipErrorInvalidValue);
-    if ((reinterpret_cast<size_t>(qkv) & 15) || (reinterpret_cast<size_t>(out) & 15))
-        return static_cast<int>(hipErrorInvalidValue);
-    const int nkt = (tokens + 31) / 32;
+int route_f32_math(hipStream_t s, const IO *qkv, IO *out, int n_images, int tokens, int heads, int q_rows) {
     if constexpr (std::is_same<IO, float>::value) {
-        // fp32 I/O up to 224 tokens: the 16x16x4 kernel with LDS-DMA staging (vit_attention_resident.hip)
-        if (tokens <= 224) return vitattn::attention_f32_resident(s, qkv, out, n_images, tokens, heads, q_rows);
+        if (tokens <= 224) return attention_f32_resident(s, qkv, out, n_images, tokens, heads, q_rows);
     }
-    switch (nkt) {
-        case 1: return launch<1, IO>(s, qkv, out, n_images, tokens, heads, q_rows);
-        case 2: return launch<2, IO>(s, qkv, out, n_images, tokens, heads, q_rows);
-        case 3: return launch<3, IO>(s, qkv, out, n_images, tokens, heads, q_rows);
-        case 4: return launch<4, IO>(s, qkv, out, n_images, tokens, heads, q_rows);
-        case 5: return launch<5, IO>(s, qkv, out, n_images, tokens, heads, q_rows);
-        case 6: return launch<6, IO>(s, qkv, out, n_images, tokens, heads, q_rows);
-        case 7: return launch<7, IO>(s, qkv, out, n_images, tokens, heads, q_rows);
-        default: {  // > 224 tokens: K/V stream through LDS in chunks, online softmax (computes every query row)
-            const int qblocks = (nkt + ATT_WAVES - 1) / ATT_WAVES;
-            hipLaunchKernelGGL(attention_f32_chunked_kernel<IO>, dim3(heads, n_images, qblocks), dim3(ATT_THREADS), 0, s,
-                               qkv, out, tokens, heads);
-            return static_cast<int>(hipGetLastError());
-        }
+    if (tokens > 224) {  // computes every query row
+        hipLaunchKernelGGL(attention_f32_chunked_kernel<IO>, chunked_grid(n_images, tokens, heads), dim3(ATT_THREADS), 0, s, qkv, out,
+                           tokens, heads);
+        return static_cast<int>(hipGetLastError());
+    }
+    // bf16 I/O only; the float instances of attention_f32_kernel stay built, no entry reaches them
+    return dispatch_int<1, 7>((tokens + 31) / 32, [&](auto nkt) {
+        return launch_f32<decltype(nkt)::value, IO>(s, qkv, out, n_images, tokens, heads, q_rows);
+    });
+}
+
+// Every vithip_attention_* entry is one call of this.  resident_only: the entry refuses more than 224 tokens whatever q_rows is.
+template <typename IO>
+int route(vithip_stream_t stream, const IO *qkv, IO *out, int n_images, int tokens, int heads, int head_dim, int q_rows, int q_scaled,
+          bool f32_math = false, bool resident_only = false) {
+    constexpr int refused = static_cast<int>(hipErrorInvalidValue);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!hd_accepted(head_dim) || (q_scaled != 0 && q_scaled != 1) || !qkv_args_ok(qkv, out, n_images, tokens, heads, q_rows))
+        return refused;
+    if constexpr (std::is_same<IO, float>::value) {
+        if (head_dim != 64) return attention_hd_f32(s, qkv, out, n_images, tokens, heads, head_dim, q_rows);
+        if (tokens > 224 && (resident_only || q_rows < tokens)) return refused;
+        return route_f32_math<float>(s, qkv, out, n_images, tokens, heads, q_rows);
+    } else {
+        if (head_dim != 64) return attention_hd_bf16(s, qkv, out, n_images, tokens, heads, head_dim, q_rows, q_scaled != 0);
+        if (tokens > 224 && (resident_only || q_rows < tokens)) return refused;
+        if (f32_math) return q_scaled ? refused : route_f32_math<bf16_t>(s, qkv, out, n_images, tokens, heads, q_rows);
+        if (tokens <= 224)
+            return dispatch_int<1, 7>((tokens + 31) / 32, [&](auto nkt) {
+                return launch_bf16<decltype(nkt)::value>(s, qkv, out, n_images, tokens, heads, q_rows, q_scaled != 0);
+            });
+        if (tokens <= 704) return attention_bf16_stream(s, qkv, out, n_images, tokens, heads, q_scaled != 0);
+        hipLaunchKernelGGL(attention_bf16_chunked_kernel, chunked_grid(n_images, tokens, heads), dim3(ATT_THREADS), 0, s, qkv, out, tokens,
+                           heads, q_scaled ? 1.0f : kScale64);
+        return static_cast<int>(hipGetLastError());
     }
 }
 
@@ -876,78 +896,46 @@ extern "C" int vithip_attention_set_debug_buffer(void *buf) {
 }
 #endif
 
-extern "C" int vithip_attention_f32(vithip_stream_t stream, const float *qkv, float *out,
-                                    int n_images, int tokens, int heads) {
-    return attention_dispatch<float>(static_cast<hipStream_t>(stream), qkv, out, n_images, tokens, heads, tokens);
+extern "C" {
+
+// ---- the entries (include/vit_hip_kernels.h): arguments of route() are head_dim, q_rows, q_scaled, f32_math, resident_only ----------
+
+int vithip_attention_f32(vithip_stream_t stream, const float *qkv, float *out, int n_images, int tokens, int heads) {
+    return route<float>(stream, qkv, out, n_images, tokens, heads, 64, tokens, 0);
 }
 
-// bf16 variant: qkv and out hold bf16 bits; K/V are widened to fp32 while staged into LDS and all
-// arithmetic (fp32 MFMA, softmax) is the same as above; the output is rounded to bf16 once.
-static int attention_bf16io_q(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out, int n_images, int tokens,
-                              int heads, int q_rows, bool bf16_mfma = true, bool q_scaled = false);
-
-// As vithip_attention_bf16io / _rows, for Q columns that already hold 0.125 * log2(e) * q (the factor of the scores' exponent,
-// folded into the in_proj weights by the engine: q is then rounded to bf16 once, as before, and the kernels save the scaling).
-// q_rows < tokens needs tokens <= 224.
-extern "C" int vithip_attention_bf16io_qscaled(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out,
-                                               int n_images, int tokens, int heads, int q_rows) {
-    if (q_rows != tokens && tokens > 224) return static_cast<int>(hipErrorInvalidValue);
-    return attention_bf16io_q(stream, qkv, out, n_images, tokens, heads, q_rows, true, true);
+int vithip_attention_f32_rows(vithip_stream_t stream, const float *qkv, float *out, int n_images, int tokens, int heads, int q_rows) {
+    return route<float>(stream, qkv, out, n_images, tokens, heads, 64, q_rows, 0, false, true);
 }
 
-extern "C" int vithip_attention_bf16io(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out,
-                                       int n_images, int tokens, int heads) {
-    return attention_bf16io_q(stream, qkv, out, n_images, tokens, heads, tokens);
+int vithip_attention_f32_hd(vithip_stream_t stream, const float *qkv, float *out, int n_images, int tokens, int heads, int head_dim,
+                            int q_rows) {
+    return route<float>(stream, qkv, out, n_images, tokens, heads, head_dim, q_rows, 0);
 }
 
-// Same I/O, fp32 arithmetic: K/V widened to fp32 in LDS, both products on the fp32 matrix pipe (the cross-check of the
-// bf16-MFMA kernel: only the final rounding of the output to bf16 differs from vithip_attention_f32).
-extern "C" int vithip_attention_bf16io_f32math(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out,
-                                               int n_images, int tokens, int heads) {
-    return attention_bf16io_q(stream, qkv, out, n_images, tokens, heads, tokens, false);
+int vithip_attention_bf16io(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out, int n_images, int tokens,
+                            int heads) {
+    return route<bf16_t>(stream, qkv, out, n_images, tokens, heads, 64, tokens, 0);
 }
 
-// Only the first q_rows query rows of every image (the class token for q_rows = 1; tokens <= 224): used by the engine's
-// exact last-layer pruning -- everything after the last attention depends on row 0 alone.
-extern "C" int vithip_attention_f32_rows(vithip_stream_t stream, const float *qkv, float *out, int n_images, int tokens,
-                                         int heads, int q_rows) {
-    if (tokens > 224) return static_cast<int>(hipErrorInvalidValue);
-    return attention_dispatch<float>(static_cast<hipStream_t>(stream), qkv, out, n_images, tokens, heads, q_rows);
+int vithip_attention_bf16io_rows(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out, int n_images, int tokens,
+                                 int heads, int q_rows) {
+    return route<bf16_t>(stream, qkv, out, n_images, tokens, heads, 64, q_rows, 0, false, true);
 }
 
-extern "C" int vithip_attention_bf16io_rows(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out,
-                                            int n_images, int tokens, int heads, int q_rows) {
-    if (tokens > 224) return static_cast<int>(hipErrorInvalidValue);
-    return attention_bf16io_q(stream, qkv, out, n_images, tokens, heads, q_rows);
+int vithip_attention_bf16io_qscaled(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out, int n_images, int tokens,
+                                    int heads, int q_rows) {
+    return route<bf16_t>(stream, qkv, out, n_images, tokens, heads, 64, q_rows, 1);
 }
 
-static int attention_bf16io_q(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out, int n_images, int tokens,
-                              int heads, int q_rows, bool bf16_mfma, bool q_scaled) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (q_rows <= 0 || q_rows > tokens) return static_cast<int>(hipErrorInvalidValue);
-    if (!qkv || !out || n_images <= 0 || tokens <= 0 || heads <= 0 || (reinterpret_cast<size_t>(qkv) & 15) ||
-        (reinterpret_cast<size_t>(out) & 15))
-        return static_cast<int>(hipErrorInvalidValue);
-    if (bf16_mfma) {  // bf16 matrix path while K/V of a head fit LDS; longer sequences use the chunked kernel
-        switch ((tokens + 31) / 32) {
-            case 1: return launch_bf16<1>(s, qkv, out, n_images, tokens, heads, q_rows, q_scaled);
-            case 2: return launch_bf16<2>(s, qkv, out, n_images, tokens, heads, q_rows, q_scaled);
-            case 3: return launch_bf16<3>(s, qkv, out, n_images, tokens, heads, q_rows, q_scaled);
-            case 4: return launch_bf16<4>(s, qkv, out, n_images, tokens, heads, q_rows, q_scaled);
-            case 5: return launch_bf16<5>(s, qkv, out, n_images, tokens, heads, q_rows, q_scaled);
-            case 6: return launch_bf16<6>(s, qkv, out, n_images, tokens, heads, q_rows, q_scaled);
-            case 7: return launch_bf16<7>(s, qkv, out, n_images, tokens, heads, q_rows, q_scaled);
-            default: {
-                // 225..704 tokens (ViT-L/16-384: 577): all query blocks of a head in one persistent workgroup, K/V streamed
-                // once through an LDS-DMA ring (vit_attention_stream.hip); longer sequences: the chunked kernel below
-                if (tokens <= 704) return vitattn::attention_bf16_stream(s, qkv, out, n_images, tokens, heads, q_scaled);
-                const int qblocks = ((tokens + 31) / 32 + ATT_WAVES - 1) / ATT_WAVES;
-                hipLaunchKernelGGL(attention_bf16_chunked_kernel, dim3(heads, n_images, qblocks), dim3(ATT_THREADS), 0, s, qkv,
-                                   out, tokens, heads, q_scaled ? 1.0f : 0.125f * 1.4426950408889634f);
-                return static_cast<int>(hipGetLastError());
-            }
-        }
-    }
-    if (q_scaled) return static_cast<int>(hipErrorInvalidValue);  // the fp32-arithmetic cross-check takes plain q
-    return attention_dispatch<bf16_t>(s, qkv, out, n_images, tokens, heads, q_rows);
+int vithip_attention_bf16io_f32math(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out, int n_images, int tokens,
+                                    int heads) {
+    return route<bf16_t>(stream, qkv, out, n_images, tokens, heads, 64, tokens, 0, true);
 }
+
+int vithip_attention_bf16io_hd(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out, int n_images, int tokens,
+                               int heads, int head_dim, int q_rows, int q_scaled) {
+    return route<bf16_t>(stream, qkv, out, n_images, tokens, heads, head_dim, q_rows, q_scaled);
+}
+
+}  // extern "C"

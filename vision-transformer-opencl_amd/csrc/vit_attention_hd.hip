@@ -1,6 +1,6 @@
 // csrc/vit_attention_hd.hip -- attention for head dims other than 64: every multiple of 8 from 72 to 128 (ViT-H/14: 80, OpenCLIP
-// ViT-g-14 / EVA-g: 88, SigLIP2 giant: 96, OpenCLIP ViT-bigG-14: 104).  head_dim 64 is not computed here: each entry hands it to the
-// entry it generalises (vit_attention.hip, vit_cls_attention.hip), whose kernels are untouched.
+// ViT-g-14 / EVA-g: 88, SigLIP2 giant: 96, OpenCLIP ViT-bigG-14: 104).  head_dim 64 is not computed here; the entries and what sends
+// them here are in vit_attention.hip (route 7 of the table at its head).  The class token's row at these head dims: vit_cls_attention.hip.
 //
 // Reference semantics: ViT_seq.c:156-215 with 64 replaced by head_dim (scores / sqrtf(head_dim), row softmax with max subtraction,
 // P.V).  qkv [n*T][3*heads*hd], columns [Q | K | V], head h = columns hd*h.. of each; out [n*T][heads*hd].
@@ -31,17 +31,12 @@
 
 #include <type_traits>
 
+#include "vit_attention.hpp"
 #include "vit_hip_kernels.h"
-#include "vit_row.hpp"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short bf16_t;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+using namespace vitattn;
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 // A workgroup is 4 waves of 32 query rows.  What counts is how many workgroups a CU holds to cover each other's staging and
@@ -265,242 +260,33 @@ __global__ __launch_bounds__(HD_THREADS, (Geo<HD, BF16>::MIN_WAVES)) void attent
     }
 }
 
-bool hd_accepted(int head_dim) { return head_dim == 64 || (head_dim >= 72 && head_dim <= 128 && head_dim % 8 == 0); }
-
-template <int HD, bool BF16, bool QS>
-int launch_hd(hipStream_t s, const typename Geo<HD, BF16>::elem *qkv, typename Geo<HD, BF16>::elem *out, int n_images, int tokens,
-              int heads, int q_rows, float scale) {
-    const int qblocks = (q_rows + HD_QROWS - 1) / HD_QROWS;
-    hipLaunchKernelGGL((attention_hd_kernel<HD, BF16, QS>), dim3((unsigned)(n_images * qblocks), (unsigned)heads), dim3(HD_THREADS), 0, s,
-                       qkv, out, tokens, heads, q_rows, qblocks, scale);
-    return static_cast<int>(hipGetLastError());
-}
-
 template <bool BF16, bool QS>
-int dispatch_hd(hipStream_t s, const typename Geo<128, BF16>::elem *qkv, typename Geo<128, BF16>::elem *out, int n_images, int tokens,
-                int heads, int head_dim, int q_rows) {
-    if (!qkv || !out || n_images <= 0 || tokens <= 0 || heads <= 0 || heads > 65535 || q_rows <= 0 || q_rows > tokens)
-        return static_cast<int>(hipErrorInvalidValue);
-    if ((reinterpret_cast<size_t>(qkv) & 15) || (reinterpret_cast<size_t>(out) & 15)) return static_cast<int>(hipErrorInvalidValue);
-    const long long blocks = (long long)n_images * ((q_rows + HD_QROWS - 1) / HD_QROWS);
-    if (blocks > 0x7fffffffLL) return static_cast<int>(hipErrorInvalidValue);
+int launch_hd(hipStream_t s, const typename Geo<128, BF16>::elem *qkv, typename Geo<128, BF16>::elem *out, int n_images, int tokens,
+              int heads, int head_dim, int q_rows) {
+    const int qblocks = (q_rows + HD_QROWS - 1) / HD_QROWS;
+    if (heads > 65535 || (long long)n_images * qblocks > 0x7fffffffLL) return static_cast<int>(hipErrorInvalidValue);  // the grid
     const float scale = QS ? 1.0f : vithip_qscale(head_dim);
-    switch (head_dim) {
-#define HD_CASE(N) case N: return launch_hd<N, BF16, QS>(s, qkv, out, n_images, tokens, heads, q_rows, scale);
-        HD_CASE(72) HD_CASE(80) HD_CASE(88) HD_CASE(96) HD_CASE(104) HD_CASE(112) HD_CASE(120) HD_CASE(128)
-#undef HD_CASE
-        default: return static_cast<int>(hipErrorInvalidValue);
-    }
-}
-
-// ---- the class token's attention row (the contract of vit_cls_attention.hip with 64 replaced by head_dim) -----------------------
-//
-// The same three passes: scores of all keys (a group of lanes per key), sum of the weights, the stored row.  A group is 16 lanes for
-// both element types and a lane takes the 16-byte pieces sub, sub + 16 of a head's slice of a row (fp32: 18..32 pieces, two rounds;
-// bf16: 9..16 pieces, one round); a piece past head_dim is not loaded and adds nothing.  Products in element order, pieces in
-// order, then the butterfly: score() is one function of (image, head, key) and gives the same bits wherever it is called.
-using vit_row::wave_max;
-using vit_row::wave_sum;
-
-constexpr int CA_THREADS = 256, CA_WAVES = CA_THREADS / 64, CA_CACHE = 4096, CA_GROUP = 16, CA_KEYS = CA_THREADS / CA_GROUP;
-constexpr int CA_AHEAD = 2;  // keys a group loads ahead in pass 1
-
-template <bool BF16> struct Piece;
-template <> struct Piece<false> {
-    static constexpr int VEC = 4, ROUNDS = 2;
-    typedef float elem;
-    static __device__ __forceinline__ void load(const float *p, float (&v)[4]) {
-        const f32x4 a = *reinterpret_cast<const f32x4 *>(p);
-        v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3];
-    }
-};
-template <> struct Piece<true> {
-    static constexpr int VEC = 8, ROUNDS = 1;
-    typedef unsigned short elem;
-    static __device__ __forceinline__ void load(const unsigned short *p, float (&v)[8]) {
-        const u32x4 a = *reinterpret_cast<const u32x4 *>(p);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            v[2 * j] = __uint_as_float(a[j] << 16);
-            v[2 * j + 1] = __uint_as_float(a[j] & 0xffff0000u);
-        }
-    }
-};
-
-template <bool MAX>
-__device__ __forceinline__ float block_reduce(float v, float *red) {
-    v = MAX ? wave_max(v) : wave_sum(v);
-    __syncthreads();  // red may still be read from the reduction before
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = red[0];
-#pragma unroll
-    for (int w = 1; w < CA_WAVES; ++w) r = MAX ? fmaxf(r, red[w]) : r + red[w];
-    return r;
-}
-
-template <bool BF16>
-__global__ __launch_bounds__(CA_THREADS) void cls_attention_hd_kernel(const typename Piece<BF16>::elem *__restrict__ qkv, size_t row_stride,
-                                                                       float *__restrict__ out, size_t ld_out, int tokens, int heads,
-                                                                       int head_dim, int head_mean, int q_scaled, float scale) {
-    typedef Piece<BF16> E;
-    constexpr int VEC = E::VEC, ROUNDS = E::ROUNDS;
-    __shared__ float cache[CA_CACHE];
-    __shared__ float red[CA_WAVES];
-
-    const int tid = threadIdx.x, sub = tid % CA_GROUP, grp = tid / CA_GROUP;
-    const int image = head_mean ? blockIdx.x : blockIdx.x / heads;
-    const int h_lo = head_mean ? 0 : blockIdx.x - image * heads, h_hi = head_mean ? heads : h_lo + 1;
-    const size_t D = (size_t)heads * head_dim;
-    const typename E::elem *rows = qkv + (size_t)image * tokens * row_stride;  // the image's token rows: [Q | K | V]
-    const int cached = tokens < CA_CACHE ? tokens : CA_CACHE;
-    bool mine[ROUNDS];  // this lane has a piece in round i
-#pragma unroll
-    for (int i = 0; i < ROUNDS; ++i) mine[i] = (sub + CA_GROUP * i) * VEC < head_dim;
-
-    for (int h = h_lo; h < h_hi; ++h) {
-        float q[ROUNDS][VEC];
-#pragma unroll
-        for (int i = 0; i < ROUNDS; ++i) {
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) q[i][j] = 0.0f;
-            if (mine[i]) E::load(rows + (size_t)h * head_dim + (sub + CA_GROUP * i) * VEC, q[i]);
-        }
-        const typename E::elem *kh = rows + D + (size_t)h * head_dim + sub * VEC;  // this lane's first 16 bytes of key 0
-
-        auto load_key = [&](int t, float (&k)[ROUNDS][VEC]) {
-#pragma unroll
-            for (int i = 0; i < ROUNDS; ++i) {
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) k[i][j] = 0.0f;
-                if (mine[i]) E::load(kh + (size_t)t * row_stride + CA_GROUP * i * VEC, k[i]);
-            }
-        };
-        // the score of a key whose pieces are in k, in every lane of the group
-        auto dot = [&](const float (&k)[ROUNDS][VEC]) -> float {
-            float a = q[0][0] * k[0][0];
-#pragma unroll
-            for (int i = 0; i < ROUNDS; ++i)
-#pragma unroll
-                for (int j = (i == 0 ? 1 : 0); j < VEC; ++j) a = fmaf(q[i][j], k[i][j], a);
-#pragma unroll
-            for (int off = CA_GROUP / 2; off > 0; off >>= 1) a += __shfl_xor(a, off);
-            return a * scale;
-        };
-        auto score = [&](int t) -> float {
-            float k[ROUNDS][VEC];
-            load_key(t, k);
-            return dot(k);
-        };
-        auto weight = [&](float s, float m) -> float { return q_scaled ? exp2f(s - m) : expf(s - m); };
-
-        __syncthreads();  // the cache of the head before has been read
-        float m = -INFINITY;
-        for (int t0 = grp; t0 < tokens; t0 += CA_AHEAD * CA_KEYS) {
-            float k[CA_AHEAD][ROUNDS][VEC];
-#pragma unroll
-            for (int u = 0; u < CA_AHEAD; ++u) {
-                const int t = t0 + u * CA_KEYS;
-                load_key(t < tokens ? t : tokens - 1, k[u]);  // clamped: always a row of this image
-            }
-#pragma unroll
-            for (int u = 0; u < CA_AHEAD; ++u) {
-                const int t = t0 + u * CA_KEYS;
-                const float s = dot(k[u]);
-                if (t < tokens) {
-                    if (sub == 0 && t < CA_CACHE) cache[t] = s;
-                    m = fmaxf(m, s);
-                }
-            }
-        }
-        m = block_reduce<true>(m, red);  // its barriers also publish the cache
-
-        float l = 0.0f;
-        for (int t = tid; t < cached; t += CA_THREADS) l += weight(cache[t], m);
-        for (int t = CA_CACHE + grp; t < tokens; t += CA_KEYS) {  // past the cache: the group recomputes, its first lane counts
-            const float w = weight(score(t), m);
-            if (sub == 0) l += w;
-        }
-        l = block_reduce<false>(l, red);
-
-        float *dst = out + (size_t)image * ld_out + (head_mean ? 0 : (size_t)h * tokens);
-        const int first = h == 0, last = h == heads - 1;
-        auto emit = [&](int t, float p) {  // the owner of dst[t] is the same thread for every head
-            if (head_mean) {
-                if (!first) p = dst[t] + p;
-                if (last) p = p / (float)heads;
-            }
-            dst[t] = p;
-        };
-        for (int t = tid; t < cached; t += CA_THREADS) emit(t, weight(cache[t], m) / l);
-        for (int t = CA_CACHE + grp; t < tokens; t += CA_KEYS) {
-            const float p = weight(score(t), m) / l;
-            if (sub == 0) emit(t, p);
-        }
-    }
-}
-
-template <bool BF16>
-int launch_cls_hd(vithip_stream_t stream, const typename Piece<BF16>::elem *qkv, size_t q_row_stride, float *out, size_t ld_out,
-                  int n_images, int tokens, int heads, int head_dim, int head_mean, int q_scaled) {
-    if (!qkv || !out || n_images <= 0 || tokens <= 0 || heads <= 0 || (head_mean != 0 && head_mean != 1) || (q_scaled != 0 && q_scaled != 1))
-        return static_cast<int>(hipErrorInvalidValue);
-    const size_t width = 3 * (size_t)heads * head_dim, row = head_mean ? (size_t)tokens : (size_t)heads * tokens;
-    if (q_row_stride < width || q_row_stride % Piece<BF16>::VEC || ld_out < row) return static_cast<int>(hipErrorInvalidValue);
-    if ((reinterpret_cast<size_t>(qkv) & 15) || (reinterpret_cast<size_t>(out) & 3)) return static_cast<int>(hipErrorInvalidValue);
-    const size_t blocks = (size_t)n_images * (head_mean ? 1 : (size_t)heads);
-    if (blocks > (size_t)0x7fffffff) return static_cast<int>(hipErrorInvalidValue);
-    const float scale = q_scaled ? 1.0f : 1.0f / sqrtf((float)head_dim);
-    hipLaunchKernelGGL(cls_attention_hd_kernel<BF16>, dim3((unsigned)blocks), dim3(CA_THREADS), 0, static_cast<hipStream_t>(stream), qkv,
-                       q_row_stride, out, ld_out, tokens, heads, head_dim, head_mean, q_scaled, scale);
-    return static_cast<int>(hipGetLastError());
+    return dispatch_int<72, 8, 8>(head_dim, [&](auto hd) {
+        hipLaunchKernelGGL((attention_hd_kernel<decltype(hd)::value, BF16, QS>), dim3((unsigned)(n_images * qblocks), (unsigned)heads),
+                           dim3(HD_THREADS), 0, s, qkv, out, tokens, heads, q_rows, qblocks, scale);
+        return static_cast<int>(hipGetLastError());
+    });
 }
 
 }  // namespace
 
-extern "C" {
+// The callers (route() in vit_attention.hip) have checked the arguments every P.V entry shares (vitattn::qkv_args_ok).
+int vitattn::attention_hd_f32(hipStream_t s, const float *qkv, float *out, int n_images, int tokens, int heads, int head_dim, int q_rows) {
+    return launch_hd<false, false>(s, qkv, out, n_images, tokens, heads, head_dim, q_rows);
+}
 
-float vithip_qscale(int head_dim) {
-    if (!hd_accepted(head_dim)) return 0.0f;
+int vitattn::attention_hd_bf16(hipStream_t s, const unsigned short *qkv, unsigned short *out, int n_images, int tokens, int heads,
+                               int head_dim, int q_rows, bool q_scaled) {
+    return q_scaled ? launch_hd<true, true>(s, qkv, out, n_images, tokens, heads, head_dim, q_rows)
+                    : launch_hd<true, false>(s, qkv, out, n_images, tokens, heads, head_dim, q_rows);
+}
+
+extern "C" float vithip_qscale(int head_dim) {
+    if (!vitattn::hd_accepted(head_dim)) return 0.0f;
     return (float)((1.0 / sqrt((double)head_dim)) * 1.4426950408889634074);  // log2(e)
 }
-
-int vithip_attention_f32_hd(vithip_stream_t stream, const float *qkv, float *out, int n_images, int tokens, int heads, int head_dim,
-                            int q_rows) {
-    if (!hd_accepted(head_dim)) return static_cast<int>(hipErrorInvalidValue);
-    if (head_dim == 64) {
-        if (q_rows == tokens) return vithip_attention_f32(stream, qkv, out, n_images, tokens, heads);
-        return vithip_attention_f32_rows(stream, qkv, out, n_images, tokens, heads, q_rows);
-    }
-    return dispatch_hd<false, false>(static_cast<hipStream_t>(stream), qkv, out, n_images, tokens, heads, head_dim, q_rows);
-}
-
-int vithip_attention_bf16io_hd(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out, int n_images, int tokens,
-                               int heads, int head_dim, int q_rows, int q_scaled) {
-    if (!hd_accepted(head_dim) || (q_scaled != 0 && q_scaled != 1)) return static_cast<int>(hipErrorInvalidValue);
-    if (head_dim == 64) {
-        if (q_scaled) return vithip_attention_bf16io_qscaled(stream, qkv, out, n_images, tokens, heads, q_rows);
-        if (q_rows == tokens) return vithip_attention_bf16io(stream, qkv, out, n_images, tokens, heads);
-        return vithip_attention_bf16io_rows(stream, qkv, out, n_images, tokens, heads, q_rows);
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    return q_scaled ? dispatch_hd<true, true>(s, qkv, out, n_images, tokens, heads, head_dim, q_rows)
-                    : dispatch_hd<true, false>(s, qkv, out, n_images, tokens, heads, head_dim, q_rows);
-}
-
-int vithip_cls_attention_f32_hd(vithip_stream_t stream, const float *qkv, size_t q_row_stride, float *out, size_t ld_out, int n_images,
-                                int tokens, int heads, int head_dim, int head_mean) {
-    if (!hd_accepted(head_dim)) return static_cast<int>(hipErrorInvalidValue);
-    if (head_dim == 64) return vithip_cls_attention_f32(stream, qkv, q_row_stride, out, ld_out, n_images, tokens, heads, head_mean);
-    return launch_cls_hd<false>(stream, qkv, q_row_stride, out, ld_out, n_images, tokens, heads, head_dim, head_mean, 0);
-}
-
-int vithip_cls_attention_bf16_hd(vithip_stream_t stream, const unsigned short *qkv, size_t q_row_stride, float *out, size_t ld_out,
-                                 int n_images, int tokens, int heads, int head_dim, int head_mean, int q_scaled) {
-    if (!hd_accepted(head_dim)) return static_cast<int>(hipErrorInvalidValue);
-    if (head_dim == 64)
-        return vithip_cls_attention_bf16(stream, qkv, q_row_stride, out, ld_out, n_images, tokens, heads, head_mean, q_scaled);
-    return launch_cls_hd<true>(stream, qkv, q_row_stride, out, ld_out, n_images, tokens, heads, head_dim, head_mean, q_scaled);
-}
-
-}  // extern "C"

@@ -34,21 +34,17 @@
 
 #include <type_traits>
 
+#include "vit_attention.hpp"
 #include "vit_device.hpp"
 #include "vit_hip_kernels.h"
 
 namespace vitattn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int HD = 64;            // head_dim
 constexpr int ROWB = HD * 4;      // bytes of one K or V row in LDS
 constexpr int RES_WAVES = 8;
 constexpr int RES_THREADS = RES_WAVES * 64;
 constexpr int PART_LD = 68;       // floats per query row of a tail partial: 64 x O, max, sum, pad
-constexpr float kScale = 0.125f * 1.4426950408889634f;  // (1 / sqrtf(64)) * log2(e): p = exp2(s*kScale - max*kScale)
 
 // NKT 16-key tiles: tokens <= 16 * NKT.  PARTS: the small-batch instantiation that spreads a head over parts_arg workgroups
 // (a run-time `parts` costs the metric configuration 1 % in registers and spills: it gets its own code)
@@ -229,13 +225,13 @@ __global__ __launch_bounds__(RES_THREADS) void attention_f32_resident_kernel(con
         }
         mx = fmaxf(mx, __shfl_xor(mx, 16));
         mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float mxs = -mx * kScale;
+        const float mxs = -mx * kScale64;
         float sum = 0.0f;
 #pragma unroll
         for (int kt = KT0; kt < KT1; ++kt)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const float e = __builtin_amdgcn_exp2f(fmaf(st[kt][i], kScale, mxs));  // exp2(-inf) = 0: masked keys
+                const float e = __builtin_amdgcn_exp2f(fmaf(st[kt][i], kScale64, mxs));  // exp2(-inf) = 0: masked keys
                 st[kt][i] = e;
                 sum += e;
             }
@@ -315,7 +311,7 @@ __global__ __launch_bounds__(RES_THREADS) void attention_f32_resident_kernel(con
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            a[k] = __builtin_amdgcn_exp2f((pk[k][64] - M) * kScale);
+            a[k] = __builtin_amdgcn_exp2f((pk[k][64] - M) * kScale64);
             den += pk[k][65] * a[k];
         }
         const float inv = 1.0f / den;
@@ -576,23 +572,9 @@ int launch_resident(hipStream_t s, const float *qkv, float *out, int n_images, i
 int attention_f32_resident(hipStream_t s, const float *qkv, float *out, int n_images, int tokens, int heads, int q_rows) {
     const int cus = vitdev::current_cus();
     if (cus <= 0) return static_cast<int>(hipErrorInvalidDevice);
-    switch ((tokens + 15) / 16) {
-        case 1: return launch_resident<1>(s, qkv, out, n_images, tokens, heads, q_rows, cus);
-        case 2: return launch_resident<2>(s, qkv, out, n_images, tokens, heads, q_rows, cus);
-        case 3: return launch_resident<3>(s, qkv, out, n_images, tokens, heads, q_rows, cus);
-        case 4: return launch_resident<4>(s, qkv, out, n_images, tokens, heads, q_rows, cus);
-        case 5: return launch_resident<5>(s, qkv, out, n_images, tokens, heads, q_rows, cus);
-        case 6: return launch_resident<6>(s, qkv, out, n_images, tokens, heads, q_rows, cus);
-        case 7: return launch_resident<7>(s, qkv, out, n_images, tokens, heads, q_rows, cus);
-        case 8: return launch_resident<8>(s, qkv, out, n_images, tokens, heads, q_rows, cus);
-        case 9: return launch_resident<9>(s, qkv, out, n_images, tokens, heads, q_rows, cus);
-        case 10: return launch_resident<10>(s, qkv, out, n_images, tokens, heads, q_rows, cus);
-        case 11: return launch_resident<11>(s, qkv, out, n_images, tokens, heads, q_rows, cus);
-        case 12: return launch_resident<12>(s, qkv, out, n_images, tokens, heads, q_rows, cus);
-        case 13: return launch_resident<13>(s, qkv, out, n_images, tokens, heads, q_rows, cus);
-        case 14: return launch_resident<14>(s, qkv, out, n_images, tokens, heads, q_rows, cus);
-        default: return static_cast<int>(hipErrorInvalidValue);
-    }
+    return dispatch_int<1, 14>((tokens + 15) / 16, [&](auto nkt) {
+        return launch_resident<decltype(nkt)::value>(s, qkv, out, n_images, tokens, heads, q_rows, cus);
+    });
 }
 
 }  // namespace vitattn

@@ -32,21 +32,11 @@
 
 #include <type_traits>
 
+#include "vit_attention.hpp"
 #include "vit_device.hpp"
 #include "vit_hip_kernels.h"
 
 namespace vitattn {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short bf16_t;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef short short4v __attribute__((ext_vector_type(4)));
-typedef short short8v __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) short4v lds_short4v;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SHD = 64;                  // head_dim
 constexpr int ST_WAVES = 8, ST_THREADS = ST_WAVES * 64;
@@ -55,7 +45,6 @@ constexpr int SKEYS = SKT * 32;          // 128 keys
 constexpr int SBUF = 2 * SKEYS * SHD;    // bf16 elements of one ring slot: K[128][64] then V[128][64]
 constexpr int MAXB = 3;                  // query blocks per wave: tokens <= 8 * 3 * 32 = 768
 constexpr int SUB = 2;                   // key tiles whose scores are in registers at a time
-constexpr float kScaleS = 0.125f * 1.4426950408889634f;
 // Row sums from the matrix pipe (softmax_pv): built, exact to the bf16 rounding of P, and measured SLOWER here (2.37 against 2.22 ms per
 // launch at ViT-L/16-384, batch 1024: the four extra MFMAs per unit cost more than the 32 v_add_f32 they replace -- the resident
 // kernel of vit_attention.hip, whose units are longer, gains 1 % from the same change and keeps it).  Off.
@@ -109,19 +98,6 @@ __device__ __forceinline__ float max_halves(float x) {
     float a = x, b = x;
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
     return fmaxf(a, b);
-}
-
-// A fragment of O^T = V^T . P^T for d-tile dt and the 16 keys from key16 (see attention_bf16_kernel): lane 4q+p of a
-// 16-lane group addresses key row q, d columns 4p..4p+3 of a 4 x 16 block and receives column i.  EXEC all ones.
-__device__ __forceinline__ bf16x8 v_frag_tr(const bf16_t *Vs, int key16, int dt, int lane) {
-    const int h = lane >> 5, g2 = (lane >> 4) & 1, q = (lane & 15) >> 2, pq = lane & 3;
-    const int row = key16 + 4 * h + q;
-    const int chunk = (dt * 4 + 2 * g2 + (pq >> 1)) ^ (4 * ((q >> 1) & 1));
-    const bf16_t *ptr = Vs + row * SHD + chunk * 8 + 4 * (pq & 1);
-    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4v *)ptr);
-    const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4v *)(ptr + 8 * SHD));
-    const short8v both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, both);
 }
 
 // QS: the Q columns of qkv hold c * q, c = 0.125 * log2(e) (the engine folds c into the in_proj weights, so q is rounded to bf16
@@ -460,9 +436,9 @@ __global__ __launch_bounds__(ST_THREADS) void attention_bf16_stream_kernel(const
                     }
                 if constexpr (!MSUM) sum2 = f32x2{s4[0] + s4[1], s4[2] + s4[3]};
             } else {
-                m_new = (cmax - m_old) * kScaleS > kDefer ? cmax : m_old;  // first sub-chunk: m_old = -inf -> cmax (finite)
+                m_new = (cmax - m_old) * kScale64 > kDefer ? cmax : m_old;  // first sub-chunk: m_old = -inf -> cmax (finite)
                 m_run[b] = m_new;
-                const f32x2 sc2 = {kScaleS, kScaleS}, mxs2 = {-m_new * kScaleS, -m_new * kScaleS};
+                const f32x2 sc2 = {kScale64, kScale64}, mxs2 = {-m_new * kScale64, -m_new * kScale64};
 #pragma unroll
                 for (int u = 0; u < SUB; ++u)
 #pragma unroll
@@ -475,7 +451,7 @@ __global__ __launch_bounds__(ST_THREADS) void attention_bf16_stream_kernel(const
                     }
             }
             if (__any(m_new != m_old)) {  // wave-uniform: most sub-chunks leave every row's maximum where it was
-                const float alpha = __builtin_amdgcn_exp2f((m_old - m_new) * (QS ? 1.0f : kScaleS));  // first one: exp2(-inf) = 0
+                const float alpha = __builtin_amdgcn_exp2f((m_old - m_new) * (QS ? 1.0f : kScale64));  // first one: exp2(-inf) = 0
                 l_run[b] *= alpha;
                 const f32x2 a2 = {alpha, alpha};
 #pragma unroll
@@ -507,7 +483,7 @@ __global__ __launch_bounds__(ST_THREADS) void attention_bf16_stream_kernel(const
             asm volatile("" : "+v"(lane_v));  // the V^T fragment addresses are made per unit, not kept across the step
             auto read_v = [&](int g, int set) __attribute__((always_inline)) {  // g = 2 u + s2
 #pragma unroll
-                for (int dt = 0; dt < 2; ++dt) vf[set][dt] = v_frag_tr(Vs, (k0 + (g >> 1)) * 32 + 16 * (g & 1), dt, lane_v);
+                for (int dt = 0; dt < 2; ++dt) vf[set][dt] = v_fragment_tr<SHD>(Vs, (k0 + (g >> 1)) * 32 + 16 * (g & 1), dt, lane_v);
             };
             read_v(0, 0);
 #pragma unroll

@@ -1,7 +1,11 @@
 // csrc/vit_cls_attention.hip -- the class token's attention over the tokens of its image: one query row of the softmax, stored.
 //
-//   s_t = (q . k_t) / sqrtf(64)           q = Q[i*T + 0][64h..], k_t = K[i*T + t][64h..]          (ViT_seq.c:156-190, one query row)
+//   s_t = (q . k_t) / sqrtf(hd)           q = Q[i*T + 0][hd*h..], k_t = K[i*T + t][hd*h..]          (ViT_seq.c:156-190, one query row)
 //   p_t = expf(s_t - max_t s) / sum_t expf(s_t - max)      t = 0..T-1, the class key included
+//
+// One kernel, cls_attention_kernel<BF16, HD64>, and one launcher behind the four entries vithip_cls_attention_f32 / _bf16 (head_dim 64)
+// and _f32_hd / _bf16_hd (head_dim 64, or a multiple of 8 from 72 to 128).  HD64 chooses between two schedules of the same three
+// passes (struct Sched); what follows describes head_dim 64, the differences of the other one stand at Sched.
 //
 // Every other attention kernel here keeps P in registers or LDS and stores P.V; this one stores P and never reads V.  It is bound by
 // reading K once, n * T * heads * 64 elements, so the layout follows the bytes: a head's slice of a K row is 256 B (fp32) or 128 B
@@ -22,28 +26,29 @@
 // (float)heads behind the last: ((p0 + p1) + p2 ...) / heads of exactly the bits head_mean = 0 stores.  No atomics, nothing depends
 // on arrival order, and an image's row does not depend on where the image sits in the batch.
 //
-// q_scaled (bf16 fold engines): the Q columns hold VITHIP_QSCALE * q, the exponent of 2 of the softmax: p = exp2f(q.k - max) / sum.
+// q_scaled (bf16 fold engines): the Q columns hold vithip_qscale(hd) * q, the exponent of 2 of the softmax: p = exp2f(q.k - max) / sum.
 #include <hip/hip_runtime.h>
 
+#include <math.h>
+
+#include "vit_attention.hpp"
 #include "vit_hip_kernels.h"
 #include "vit_row.hpp"
 
 namespace {
 
-using vit_row::f32x4;
 using vit_row::wave_max;
 using vit_row::wave_sum;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+using vitattn::f32x4;
+using vitattn::u32x4;
 
 constexpr int CA_THREADS = 256;
 constexpr int CA_WAVES = CA_THREADS / 64;
 constexpr int CA_CACHE = 4096;  // scores kept in LDS (16 KB); keys past it are recomputed
-constexpr int HEAD_DIM = 64;
-constexpr int CA_AHEAD = 4;     // keys a group loads ahead in pass 1
 
 // 16 bytes of a row as fp32: 4 floats, or 8 bf16 widened (element 2j in the low half of word j)
-template <bool BF16> struct Elems;
-template <> struct Elems<false> {
+template <bool BF16> struct Piece;
+template <> struct Piece<false> {
     static constexpr int VEC = 4;
     typedef float elem;
     static __device__ __forceinline__ void load(const float *p, float (&v)[4]) {
@@ -51,7 +56,7 @@ template <> struct Elems<false> {
         v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3];
     }
 };
-template <> struct Elems<true> {
+template <> struct Piece<true> {
     static constexpr int VEC = 8;
     typedef unsigned short elem;
     static __device__ __forceinline__ void load(const unsigned short *p, float (&v)[8]) {
@@ -62,6 +67,17 @@ template <> struct Elems<true> {
             v[2 * j + 1] = __uint_as_float(a[j] & 0xffff0000u);
         }
     }
+};
+
+// The two schedules.  HD64: a head's slice of a row is exactly one 16-byte piece per lane of the group.  Otherwise (72..128): a group
+// of 16 lanes for both element types, a lane takes the pieces sub, sub + 16 of the slice (fp32: 18..32 pieces, two rounds; bf16:
+// 9..16 pieces, one round); a piece past head_dim is not loaded and adds nothing.
+template <bool BF16, bool HD64> struct Sched {
+    static constexpr int VEC = Piece<BF16>::VEC;
+    static constexpr int GROUP = HD64 ? 64 / VEC : 16;        // lanes per key
+    static constexpr int ROUNDS = HD64 || BF16 ? 1 : 2;       // pieces per lane
+    static constexpr int AHEAD = HD64 ? 4 : 2;                // keys a group loads ahead in pass 1
+    static constexpr int KEYS = CA_THREADS / GROUP;           // keys per workgroup step
 };
 
 // max / sum over the workgroup, the waves' values combined in wave order; every thread gets the result
@@ -77,55 +93,76 @@ __device__ __forceinline__ float block_reduce(float v, float *red) {
     return r;
 }
 
-template <bool BF16>
-__global__ __launch_bounds__(CA_THREADS) void cls_attention_kernel(const typename Elems<BF16>::elem *__restrict__ qkv, size_t row_stride,
+// scale: 1 / sqrtf(head_dim), or 1 with q_scaled.  HD64: head_dim_arg is 64 and is not read.
+template <bool BF16, bool HD64>
+__global__ __launch_bounds__(CA_THREADS) void cls_attention_kernel(const typename Piece<BF16>::elem *__restrict__ qkv, size_t row_stride,
                                                                     float *__restrict__ out, size_t ld_out, int tokens, int heads,
-                                                                    int head_mean, int q_scaled) {
-    typedef Elems<BF16> E;
-    constexpr int VEC = E::VEC, GROUP = HEAD_DIM / VEC, KEYS = CA_THREADS / GROUP;  // lanes per key, keys per workgroup step
+                                                                    int head_dim_arg, int head_mean, int q_scaled, float scale) {
+    typedef Piece<BF16> E;
+    typedef Sched<BF16, HD64> S;
+    constexpr int VEC = S::VEC, GROUP = S::GROUP, ROUNDS = S::ROUNDS, AHEAD = S::AHEAD, KEYS = S::KEYS;
     __shared__ float cache[CA_CACHE];
     __shared__ float red[CA_WAVES];
 
+    const int head_dim = HD64 ? 64 : head_dim_arg;
     const int tid = threadIdx.x, sub = tid % GROUP, grp = tid / GROUP;
     const int image = head_mean ? blockIdx.x : blockIdx.x / heads;
     const int h_lo = head_mean ? 0 : blockIdx.x - image * heads, h_hi = head_mean ? heads : h_lo + 1;
-    const size_t D = (size_t)heads * HEAD_DIM;
+    const size_t D = (size_t)heads * head_dim;
     const typename E::elem *rows = qkv + (size_t)image * tokens * row_stride;  // the image's token rows: [Q | K | V]
     const int cached = tokens < CA_CACHE ? tokens : CA_CACHE;
-    const float scale = q_scaled ? 1.0f : 0.125f;  // 1 / sqrtf(64), exact
+    bool mine[ROUNDS];  // this lane has a piece in round i
+#pragma unroll
+    for (int i = 0; i < ROUNDS; ++i) mine[i] = HD64 || (sub + GROUP * i) * VEC < head_dim;
 
     for (int h = h_lo; h < h_hi; ++h) {
-        float q[VEC];
-        E::load(rows + (size_t)h * HEAD_DIM + sub * VEC, q);
-        const typename E::elem *kh = rows + D + (size_t)h * HEAD_DIM + sub * VEC;  // this lane's 16 bytes of key 0
-
-        // the score of a key whose 16 bytes are in k, in every lane of the group: products in element order, then the butterfly
-        auto dot = [&](const float (&k)[VEC]) -> float {
-            float a = q[0] * k[0];
+        float q[ROUNDS][VEC];
 #pragma unroll
-            for (int j = 1; j < VEC; ++j) a = fmaf(q[j], k[j], a);
+        for (int i = 0; i < ROUNDS; ++i) {
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) q[i][j] = 0.0f;
+            if (mine[i]) E::load(rows + (size_t)h * head_dim + (sub + GROUP * i) * VEC, q[i]);
+        }
+        const typename E::elem *kh = rows + D + (size_t)h * head_dim + sub * VEC;  // this lane's first 16 bytes of key 0
+
+        auto load_key = [&](int t, float (&k)[ROUNDS][VEC]) {
+#pragma unroll
+            for (int i = 0; i < ROUNDS; ++i) {
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) k[i][j] = 0.0f;
+                if (mine[i]) E::load(kh + (size_t)t * row_stride + GROUP * i * VEC, k[i]);
+            }
+        };
+        // the score of a key whose pieces are in k, in every lane of the group: products in element order, pieces in order, then the
+        // butterfly
+        auto dot = [&](const float (&k)[ROUNDS][VEC]) -> float {
+            float a = q[0][0] * k[0][0];
+#pragma unroll
+            for (int i = 0; i < ROUNDS; ++i)
+#pragma unroll
+                for (int j = (i == 0 ? 1 : 0); j < VEC; ++j) a = fmaf(q[i][j], k[i][j], a);
 #pragma unroll
             for (int off = GROUP / 2; off > 0; off >>= 1) a += __shfl_xor(a, off);
             return a * scale;
         };
         auto score = [&](int t) -> float {
-            float k[VEC];
-            E::load(kh + (size_t)t * row_stride, k);
+            float k[ROUNDS][VEC];
+            load_key(t, k);
             return dot(k);
         };
         auto weight = [&](float s, float m) -> float { return q_scaled ? exp2f(s - m) : expf(s - m); };
 
         __syncthreads();  // the cache of the head before has been read
         float m = -INFINITY;
-        for (int t0 = grp; t0 < tokens; t0 += CA_AHEAD * KEYS) {  // CA_AHEAD keys of the group in flight before the first is used
-            float k[CA_AHEAD][VEC];
+        for (int t0 = grp; t0 < tokens; t0 += AHEAD * KEYS) {  // AHEAD keys of the group in flight before the first is used
+            float k[AHEAD][ROUNDS][VEC];
 #pragma unroll
-            for (int u = 0; u < CA_AHEAD; ++u) {
+            for (int u = 0; u < AHEAD; ++u) {
                 const int t = t0 + u * KEYS;
-                E::load(kh + (size_t)(t < tokens ? t : tokens - 1) * row_stride, k[u]);  // clamped: always a row of this image
+                load_key(t < tokens ? t : tokens - 1, k[u]);  // clamped: always a row of this image
             }
 #pragma unroll
-            for (int u = 0; u < CA_AHEAD; ++u) {
+            for (int u = 0; u < AHEAD; ++u) {
                 const int t = t0 + u * KEYS;
                 const float s = dot(k[u]);
                 if (t < tokens) {
@@ -161,18 +198,22 @@ __global__ __launch_bounds__(CA_THREADS) void cls_attention_kernel(const typenam
     }
 }
 
+// The one launcher behind the four entries.
 template <bool BF16>
-int launch(vithip_stream_t stream, const typename Elems<BF16>::elem *qkv, size_t q_row_stride, float *out, size_t ld_out, int n_images,
-           int tokens, int heads, int head_mean, int q_scaled) {
-    if (!qkv || !out || n_images <= 0 || tokens <= 0 || heads <= 0 || (head_mean != 0 && head_mean != 1) || (q_scaled != 0 && q_scaled != 1))
+int launch(vithip_stream_t stream, const typename Piece<BF16>::elem *qkv, size_t q_row_stride, float *out, size_t ld_out, int n_images,
+           int tokens, int heads, int head_dim, int head_mean, int q_scaled) {
+    if (!vitattn::hd_accepted(head_dim) || !qkv || !out || n_images <= 0 || tokens <= 0 || heads <= 0 ||
+        (head_mean != 0 && head_mean != 1) || (q_scaled != 0 && q_scaled != 1))
         return static_cast<int>(hipErrorInvalidValue);
-    const size_t width = 3 * (size_t)heads * HEAD_DIM, row = head_mean ? (size_t)tokens : (size_t)heads * tokens;
-    if (q_row_stride < width || q_row_stride % Elems<BF16>::VEC || ld_out < row) return static_cast<int>(hipErrorInvalidValue);
-    if ((reinterpret_cast<size_t>(qkv) & 15) || (reinterpret_cast<size_t>(out) & 3)) return static_cast<int>(hipErrorInvalidValue);
+    const size_t width = 3 * (size_t)heads * head_dim, row = head_mean ? (size_t)tokens : (size_t)heads * tokens;
+    if (q_row_stride < width || q_row_stride % Piece<BF16>::VEC || ld_out < row) return static_cast<int>(hipErrorInvalidValue);
+    if (!vit_row::aligned16(qkv) || (reinterpret_cast<size_t>(out) & 3)) return static_cast<int>(hipErrorInvalidValue);
     const size_t blocks = (size_t)n_images * (head_mean ? 1 : (size_t)heads);
     if (blocks > (size_t)0x7fffffff) return static_cast<int>(hipErrorInvalidValue);
-    hipLaunchKernelGGL(cls_attention_kernel<BF16>, dim3((unsigned)blocks), dim3(CA_THREADS), 0, static_cast<hipStream_t>(stream), qkv,
-                       q_row_stride, out, ld_out, tokens, heads, head_mean, q_scaled);
+    const float scale = q_scaled ? 1.0f : 1.0f / sqrtf((float)head_dim);  // head_dim 64: 0.125f, exact
+    const auto kernel = head_dim == 64 ? cls_attention_kernel<BF16, true> : cls_attention_kernel<BF16, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(CA_THREADS), 0, static_cast<hipStream_t>(stream), qkv, q_row_stride, out,
+                       ld_out, tokens, heads, head_dim, head_mean, q_scaled, scale);
     return static_cast<int>(hipGetLastError());
 }
 
@@ -182,12 +223,22 @@ extern "C" {
 
 int vithip_cls_attention_f32(vithip_stream_t stream, const float *qkv, size_t q_row_stride, float *out, size_t ld_out, int n_images,
                              int tokens, int heads, int head_mean) {
-    return launch<false>(stream, qkv, q_row_stride, out, ld_out, n_images, tokens, heads, head_mean, 0);
+    return launch<false>(stream, qkv, q_row_stride, out, ld_out, n_images, tokens, heads, 64, head_mean, 0);
 }
 
 int vithip_cls_attention_bf16(vithip_stream_t stream, const unsigned short *qkv, size_t q_row_stride, float *out, size_t ld_out,
                               int n_images, int tokens, int heads, int head_mean, int q_scaled) {
-    return launch<true>(stream, qkv, q_row_stride, out, ld_out, n_images, tokens, heads, head_mean, q_scaled);
+    return launch<true>(stream, qkv, q_row_stride, out, ld_out, n_images, tokens, heads, 64, head_mean, q_scaled);
+}
+
+int vithip_cls_attention_f32_hd(vithip_stream_t stream, const float *qkv, size_t q_row_stride, float *out, size_t ld_out, int n_images,
+                                int tokens, int heads, int head_dim, int head_mean) {
+    return launch<false>(stream, qkv, q_row_stride, out, ld_out, n_images, tokens, heads, head_dim, head_mean, 0);
+}
+
+int vithip_cls_attention_bf16_hd(vithip_stream_t stream, const unsigned short *qkv, size_t q_row_stride, float *out, size_t ld_out,
+                                 int n_images, int tokens, int heads, int head_dim, int head_mean, int q_scaled) {
+    return launch<true>(stream, qkv, q_row_stride, out, ld_out, n_images, tokens, heads, head_dim, head_mean, q_scaled);
 }
 
 }  // extern "C"
