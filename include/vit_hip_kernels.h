@@ -302,6 +302,13 @@ int vithip_attention_f32_hd(vithip_stream_t stream, const float *qkv, float *out
                             int q_rows);
 int vithip_attention_bf16io_hd(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out, int n_images, int tokens,
                                int heads, int head_dim, int q_rows, int q_scaled);
+/* vithip_attention_f32_hd's layout, arguments and guarantees at head_dim 64 (any other head_dim: hipErrorInvalidValue), any tokens >= 1
+ * and any q_rows, heads <= 65535, with both products on the bf16 matrix pipe: every fp32 operand (Q, K, V and the softmax weights) is
+ * split into three bf16 pieces and each fp32 product becomes the six piece products of rank <= 2, added small terms first (the
+ * arithmetic of vithip_gemm_args.arith = 1).  Scores, softmax and accumulation are fp32; the result differs from fp32 arithmetic in
+ * the last bits.  A row's bits depend on neither the batch size, nor the image's place in the batch, nor q_rows. */
+int vithip_attention_f32_split(vithip_stream_t stream, const float *qkv, float *out, int n_images, int tokens, int heads, int head_dim,
+                               int q_rows);
 /* (float)((1 / sqrt((double)head_dim)) * log2(e)): the factor of the scores' exponent, softmax(q.k / sqrt(hd)) = 2^(qscale q.k -
  * max) / sum; vithip_qscale(64) has the bits of VITHIP_QSCALE.  0.0f for a head_dim the kernels refuse. */
 float vithip_qscale(int head_dim);

@@ -385,6 +385,8 @@ def lib() -> C.CDLL:
             L.vithip_attention_bf16io_hd.argtypes = pv + [C.c_int] * 6
             L.vithip_cls_attention_f32_hd.argtypes = cls + [C.c_int] * 5
             L.vithip_cls_attention_bf16_hd.argtypes = cls + [C.c_int] * 6
+        if hasattr(L, "vithip_attention_f32_split"):  # an earlier build (see above) has fp32 arithmetic only
+            L.vithip_attention_f32_split.argtypes = pv + [C.c_int] * 5
         L.vithip_softmax_top1_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                               C.c_void_p, C.c_int, C.c_int]
         L.vithip_event_create.argtypes = [C.POINTER(C.c_void_p)]
@@ -1064,6 +1066,13 @@ def attention_hd(qkv, n_images: int, tokens: int, heads: int, head_dim: int, q_r
     sentinel, and `out` receives the frame "out")."""
     return _attention("vithip_attention_f32_hd", _as_f32(qkv), n_images, tokens, heads, head_dim,
                       (head_dim, tokens if q_rows is None else q_rows), fill, frames, out)
+
+
+def attention_split(qkv, n_images: int, tokens: int, heads: int, q_rows: Optional[int] = None, fill: float = 0.0, frames=None,
+                    out: Optional[dict] = None) -> np.ndarray:
+    """vithip_attention_f32_split: attention_hd() at head_dim 64 with both products on the bf16 matrix pipe (three-piece split)."""
+    return _attention("vithip_attention_f32_split", _as_f32(qkv), n_images, tokens, heads, 64,
+                      (64, tokens if q_rows is None else q_rows), fill, frames, out)
 
 
 def attention_bf16io_hd(qkv_bits, n_images: int, tokens: int, heads: int, head_dim: int, q_rows: Optional[int] = None,

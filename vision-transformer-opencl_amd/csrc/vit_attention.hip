@@ -16,7 +16,7 @@
 //       key_a / key_a+4), so P goes from softmax to the second MFMA with no data movement.
 // The softmax normaliser is applied to O (32 values per lane) instead of P (112 per lane).
 //
-// ---- Which kernel runs: the routing of the eight vithip_attention_* entries (route() at the end of this file) ----------------------
+// ---- Which kernel runs: the routing of the nine vithip_attention_* entries (route() at the end of this file) ----------------------
 //
 // Every entry first asks: head_dim is 64 or a multiple of 8 from 72 to 128; q_scaled is 0 or 1; qkv and out are non-null and
 // 16-byte aligned; n_images, tokens, heads > 0; 0 < q_rows <= tokens.  Anything else is hipErrorInvalidValue.  Then, first match:
@@ -30,17 +30,20 @@
 //   6   bf16     64         any         _f32math only: attention_f32_kernel<.., bf16> up to 224 tokens,  here
 //                                       attention_f32_chunked_kernel<bf16> beyond (fp32 arithmetic on bf16 I/O: the cross-check)
 //   7   either   72 - 128   any         attention_hd_kernel<head_dim, bf16, q_scaled>                    vit_attention_hd.hip
+//   8   fp32     64         any         _f32_split only: attention_split_kernel (six bf16 products of    vit_attention_hd.hip
+//                                       the operands' three-piece split in place of each fp32 product)
 //
-// Only the resident kernels (1, 3, 6 up to 224 tokens) and 7 stop at q_rows; 2, 4 and 5 compute every query row.  So at head_dim 64,
+// Only the resident kernels (1, 3, 6 up to 224 tokens), 7 and 8 stop at q_rows; 2, 4 and 5 compute every query row.  So at head_dim 64,
 // q_rows < tokens is refused beyond 224 tokens, whichever entry it came through (_hd with 64 included), and the two _rows entries
 // refuse more than 224 tokens even with q_rows = tokens.  q_scaled (bf16; the Q columns hold vithip_qscale(head_dim) * q) changes no
-// route: 3 and 5 take the factor 1 in place of kScale64, 4 and 7 run their q_scaled instance.  6 takes plain q only.  Route 7 has two
-// limits of its own: heads <= 65535 and n_images * ceil(q_rows / 128) < 2^31 (its grid).
+// route: 3 and 5 take the factor 1 in place of kScale64, 4 and 7 run their q_scaled instance.  6 takes plain q only.  Routes 7 and 8
+// have two limits of their own: heads <= 65535 and n_images * ceil(q_rows / 128) < 2^31 (their grids).
 //
 //   entry                            element  head_dim  q_rows    q_scaled  routes
 //   vithip_attention_f32             fp32     64        tokens    -         1 2
 //   vithip_attention_f32_rows        fp32     64        argument  -         1
 //   vithip_attention_f32_hd          fp32     argument  argument  -         1 2 7
+//   vithip_attention_f32_split       fp32     64 only   argument  -         8
 //   vithip_attention_bf16io          bf16     64        tokens    0         3 4 5
 //   vithip_attention_bf16io_rows     bf16     64        argument  0         3
 //   vithip_attention_bf16io_qscaled  bf16     64        argument  1         3 4 5
@@ -856,12 +859,13 @@ int route_f32_math(hipStream_t s, const IO *qkv, IO *out, int n_images, int toke
 // Every vithip_attention_* entry is one call of this.  resident_only: the entry refuses more than 224 tokens whatever q_rows is.
 template <typename IO>
 int route(vithip_stream_t stream, const IO *qkv, IO *out, int n_images, int tokens, int heads, int head_dim, int q_rows, int q_scaled,
-          bool f32_math = false, bool resident_only = false) {
+          bool f32_math = false, bool resident_only = false, bool split = false) {
     constexpr int refused = static_cast<int>(hipErrorInvalidValue);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (!hd_accepted(head_dim) || (q_scaled != 0 && q_scaled != 1) || !qkv_args_ok(qkv, out, n_images, tokens, heads, q_rows))
         return refused;
     if constexpr (std::is_same<IO, float>::value) {
+        if (split) return head_dim == 64 ? attention_split_f32(s, qkv, out, n_images, tokens, heads, q_rows) : refused;
         if (head_dim != 64) return attention_hd_f32(s, qkv, out, n_images, tokens, heads, head_dim, q_rows);
         if (tokens > 224 && (resident_only || q_rows < tokens)) return refused;
         return route_f32_math<float>(s, qkv, out, n_images, tokens, heads, q_rows);
@@ -898,7 +902,7 @@ extern "C" int vithip_attention_set_debug_buffer(void *buf) {
 
 extern "C" {
 
-// ---- the entries (include/vit_hip_kernels.h): arguments of route() are head_dim, q_rows, q_scaled, f32_math, resident_only ----------
+// ---- the entries (include/vit_hip_kernels.h): arguments of route() are head_dim, q_rows, q_scaled, f32_math, resident_only, split ---
 
 int vithip_attention_f32(vithip_stream_t stream, const float *qkv, float *out, int n_images, int tokens, int heads) {
     return route<float>(stream, qkv, out, n_images, tokens, heads, 64, tokens, 0);
@@ -911,6 +915,11 @@ int vithip_attention_f32_rows(vithip_stream_t stream, const float *qkv, float *o
 int vithip_attention_f32_hd(vithip_stream_t stream, const float *qkv, float *out, int n_images, int tokens, int heads, int head_dim,
                             int q_rows) {
     return route<float>(stream, qkv, out, n_images, tokens, heads, head_dim, q_rows, 0);
+}
+
+int vithip_attention_f32_split(vithip_stream_t stream, const float *qkv, float *out, int n_images, int tokens, int heads, int head_dim,
+                               int q_rows) {
+    return route<float>(stream, qkv, out, n_images, tokens, heads, head_dim, q_rows, 0, false, false, true);
 }
 
 int vithip_attention_bf16io(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out, int n_images, int tokens,

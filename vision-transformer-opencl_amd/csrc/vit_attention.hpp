@@ -81,6 +81,9 @@ __attribute__((visibility("hidden"))) int attention_hd_f32(hipStream_t s, const 
                                                            int heads, int head_dim, int q_rows);
 __attribute__((visibility("hidden"))) int attention_hd_bf16(hipStream_t s, const unsigned short *qkv, unsigned short *out, int n_images,
                                                             int tokens, int heads, int head_dim, int q_rows, bool q_scaled);
+// vit_attention_hd.hip: fp32, head_dim 64, any tokens, on the bf16 matrix pipe (three-piece split); the same two limits
+__attribute__((visibility("hidden"))) int attention_split_f32(hipStream_t s, const float *qkv, float *out, int n_images, int tokens,
+                                                              int heads, int q_rows);
 
 #ifdef VIT_PROBES  // the probe build's globals, set by vithip_attention_set_debug_buffer / _set_probe_mode (vit_attention.hip)
 extern unsigned long long *g_res_dbg;     // vit_attention_resident.hip

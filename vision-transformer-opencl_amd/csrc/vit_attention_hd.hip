@@ -1,6 +1,7 @@
 // csrc/vit_attention_hd.hip -- attention for head dims other than 64: every multiple of 8 from 72 to 128 (ViT-H/14: 80, OpenCLIP
-// ViT-g-14 / EVA-g: 88, SigLIP2 giant: 96, OpenCLIP ViT-bigG-14: 104).  head_dim 64 is not computed here; the entries and what sends
-// them here are in vit_attention.hip (route 7 of the table at its head).  The class token's row at these head dims: vit_cls_attention.hip.
+// ViT-g-14 / EVA-g: 88, SigLIP2 giant: 96, OpenCLIP ViT-bigG-14: 104).  Of head_dim 64 only the split mode is computed here (fp32 on
+// the bf16 matrix pipe: attention_split_kernel, below the streaming kernel whose skeleton it shares).  The entries and what sends them
+// here are in vit_attention.hip (routes 7 and 8 of the table at its head).  The class token's row at these head dims: vit_cls_attention.hip.
 //
 // Reference semantics: ViT_seq.c:156-215 with 64 replaced by head_dim (scores / sqrtf(head_dim), row softmax with max subtraction,
 // P.V).  qkv [n*T][3*heads*hd], columns [Q | K | V], head h = columns hd*h.. of each; out [n*T][heads*hd].
@@ -33,6 +34,7 @@
 
 #include "vit_attention.hpp"
 #include "vit_hip_kernels.h"
+#include "vit_split3.hpp"
 
 namespace {
 
@@ -260,6 +262,233 @@ __global__ __launch_bounds__(HD_THREADS, (Geo<HD, BF16>::MIN_WAVES)) void attent
     }
 }
 
+// ---- fp32 in and out at head_dim 64 on the bf16 matrix pipe: the three-piece split (route 8 of vit_attention.hip) -------
+// The skeleton of the bf16 mode above -- the same chunks of 64 keys, the same K rows and V^T rows (Geo<64, true>), the same online
+// softmax -- with every fp32 operand in three bf16 pieces (vit_split3.hpp: hi, mid, lo, each rounded to nearest even) and both
+// products as the six piece products of rank <= 2, small terms first in the GEMM's order, on one accumulator:
+//   K, V  split while a chunk is staged: three LDS planes of each (3 x 9 KB + 3 x 8.5 KB);
+//   Q     split once, into registers (3 x 4 bf16x8 per lane);
+//   P     split per 16 keys after the v_exp_f32: 0 <= p <= 2^kDefer, so hi + mid + lo == p exactly.
+// The contraction over d runs in four steps of 16 and a step adds its six terms before the next one starts, as a K step of the split
+// GEMM does; O^T takes the six terms of 16 keys at a time.  A group of 16 keys past the last token is skipped (its P is 0).
+// Keys past the last token are zeros in all planes and their scores are -inf; a workgroup reads one image's rows only; no atomics:
+// a row's bits depend on neither the batch, nor the image's place in it, nor q_rows.
+// Measured at batch 256, 197 tokens (profiles/r23): 4 waves with three workgroups per CU 0.28 ms per launch; 8 waves (one staging pass
+// per head, -DATT_SPLIT_WAVES=8) 0.31 ms, alone on their CU at 165 VGPRs, and they spill when capped at 128 for two workgroups.
+#ifndef ATT_SPLIT_WAVES
+#define ATT_SPLIT_WAVES 4  // waves (32 query rows each) per workgroup
+#endif
+#ifndef ATT_SPLIT_MINW
+#define ATT_SPLIT_MINW 3   // waves per SIMD the register allocation leaves room for: 3 workgroups of 4 waves per CU (3 x 52.5 KB of LDS)
+#endif
+constexpr int SP_WAVES = ATT_SPLIT_WAVES, SP_THREADS = SP_WAVES * 64, SP_QROWS = SP_WAVES * 32;
+
+__global__ __launch_bounds__(SP_THREADS, ATT_SPLIT_MINW) void attention_split_kernel(const float *__restrict__ qkv, float *__restrict__ out,
+                                                                                    int tokens, int heads, int q_rows, int qblocks) {
+    using vitsplit::SPLIT_TERM_A;
+    using vitsplit::SPLIT_TERM_W;
+    using vitsplit::split3_piece8;
+    typedef Geo<64, true> G;
+    constexpr int HD = 64, KC = G::KC, KT = G::KT, DT = G::DT, KROW = G::KROW, VROW = G::VROW, NQ = HD / 16;
+    __shared__ __attribute__((aligned(16))) bf16_t Ks[3 * G::K_ELEMS];  // plane pl (0 = hi, 1 = mid, 2 = lo) at pl * K_ELEMS
+    __shared__ __attribute__((aligned(16))) bf16_t Vt[3 * G::V_ELEMS];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const int image = blockIdx.x / qblocks, qblock = blockIdx.x - image * qblocks, head = blockIdx.y;
+    const size_t D = (size_t)heads * HD, ld = 3 * D;
+    const float *rows = qkv + (size_t)image * tokens * ld + (size_t)head * HD;  // the image's token rows, this head's Q columns
+    const float *krows = rows + D, *vrows = rows + 2 * D;
+    const int qrow0 = qblock * SP_QROWS + wave * 32;
+    const bool active = qrow0 < q_rows;  // wave-uniform: this wave owns query rows
+    const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
+
+    // ---- the pieces of this wave's 32 query rows, for all of the sequence: d = 16 ks + 8 h + (0..7) of row r on the lane
+    bf16x8 qf[3][NQ];
+    {
+        int qrow = qrow0 + r;
+        qrow = qrow < q_rows ? qrow : q_rows - 1;  // a row of this image; dropped at the store
+        const float *qp = rows + (size_t)qrow * ld + 8 * h;
+#pragma unroll
+        for (int ks = 0; ks < NQ; ++ks) {
+            f32x4 x0 = zero4, x1 = zero4;
+            if (active) {
+                x0 = *reinterpret_cast<const f32x4 *>(qp + 16 * ks);
+                x1 = *reinterpret_cast<const f32x4 *>(qp + 16 * ks + 4);
+            }
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) qf[pl][ks] = __builtin_bit_cast(bf16x8, split3_piece8(x0, x1, pl));
+        }
+    }
+
+    f32x16 o[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int v = 0; v < 16; ++v) o[dt][v] = 0.0f;
+    float m_run = -INFINITY, l_run = 0.0f;  // per query (lane & 31); l_run: this half-wave's keys
+
+    // ---- a chunk of K and V on its way to the LDS: fetch() takes this thread's share into registers (zeros behind the last token),
+    // store() splits it and writes the three planes.  K: eight d of a key per item, one 16-byte piece of each plane.  V transposed:
+    // the same 8 d of two adjacent keys per item, 8 dword writes per plane, adjacent lanes on adjacent banks.
+    constexpr int K_ITEMS = KC * (HD / 8), V_ITEMS = (KC / 2) * (HD / 8);
+    constexpr int KI = (K_ITEMS + SP_THREADS - 1) / SP_THREADS;
+    constexpr int V_TID0 = SP_THREADS > V_ITEMS ? SP_THREADS - V_ITEMS : 0;  // V goes to the last waves: with 8, the one without rows at 197 tokens
+    static_assert(V_ITEMS <= SP_THREADS, "one V item per thread at most");
+    const int vi = tid - V_TID0;
+    f32x4 kx[KI][2], vx[4];
+    auto fetch = [&](int key0) {
+#pragma unroll
+        for (int it = 0; it < KI; ++it) {
+            const int i = tid + it * SP_THREADS, row = i / (HD / 8), c = i - row * (HD / 8), key = key0 + row;
+            kx[it][0] = kx[it][1] = zero4;
+            if (i < K_ITEMS && key < tokens) {
+                const float *p = krows + (size_t)key * ld + 8 * c;
+                kx[it][0] = *reinterpret_cast<const f32x4 *>(p);
+                kx[it][1] = *reinterpret_cast<const f32x4 *>(p + 4);
+            }
+        }
+        if (vi >= 0) {
+            const int c = vi / (KC / 2), key = key0 + 2 * (vi - c * (KC / 2));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) vx[j] = zero4;
+            if (key < tokens) {
+                const float *p = vrows + (size_t)key * ld + 8 * c;
+                vx[0] = *reinterpret_cast<const f32x4 *>(p);
+                vx[1] = *reinterpret_cast<const f32x4 *>(p + 4);
+            }
+            if (key + 1 < tokens) {
+                const float *p = vrows + (size_t)(key + 1) * ld + 8 * c;
+                vx[2] = *reinterpret_cast<const f32x4 *>(p);
+                vx[3] = *reinterpret_cast<const f32x4 *>(p + 4);
+            }
+        }
+    };
+    auto store = [&](bf16_t *Kd, bf16_t *Vd) {
+#pragma unroll
+        for (int it = 0; it < KI; ++it) {
+            const int i = tid + it * SP_THREADS, row = i / (HD / 8), c = i - row * (HD / 8);
+            if (i < K_ITEMS) {
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl)
+                    *reinterpret_cast<u32x4 *>(Kd + pl * G::K_ELEMS + row * KROW + 8 * c) = split3_piece8(kx[it][0], kx[it][1], pl);
+            }
+        }
+        if (vi >= 0) {
+            const int c = vi / (KC / 2), row = 2 * (vi - c * (KC / 2));
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) {
+                const u32x4 a = split3_piece8(vx[0], vx[1], pl), b = split3_piece8(vx[2], vx[3], pl);
+                bf16_t *vd = Vd + pl * G::V_ELEMS + (c * 8) * VROW + row;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {  // elements 2j, 2j + 1 of the piece: key `row` in the low half, key row + 1 in the high half
+                    *reinterpret_cast<unsigned *>(vd + (2 * j) * VROW) = (a[j] & 0xffffu) | (b[j] << 16);
+                    *reinterpret_cast<unsigned *>(vd + (2 * j + 1) * VROW) = (a[j] >> 16) | (b[j] & 0xffff0000u);
+                }
+            }
+        }
+    };
+
+    for (int key0 = 0; key0 < tokens; key0 += KC) {
+        fetch(key0);
+        store(Ks, Vt);
+        __syncthreads();
+
+        if (active) {
+#pragma unroll
+            for (int t = 0; t < KT; ++t) {
+                const int tile0 = key0 + 32 * t;
+                if (tile0 >= tokens) break;  // wave-uniform: a tile of zeros
+                // ---- S^T = K . Q^T: key = (v & 3) + 8 (v >> 2) + 4 h of the tile in register v, query r on the lane
+                f32x16 s;
+#pragma unroll
+                for (int v = 0; v < 16; ++v) s[v] = 0.0f;
+                const bf16_t *kp = Ks + (32 * t + r) * KROW + 8 * h;
+#pragma unroll
+                for (int ks = 0; ks < NQ; ++ks) {
+                    bf16x8 kf[3];
+#pragma unroll
+                    for (int pl = 0; pl < 3; ++pl) kf[pl] = *reinterpret_cast<const bf16x8 *>(kp + pl * G::K_ELEMS + 16 * ks);
+#pragma unroll
+                    for (int term = 0; term < 6; ++term)
+                        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[SPLIT_TERM_A[term]], qf[SPLIT_TERM_W[term]][ks], s, 0, 0, 0);
+                }
+                if (tile0 + 32 > tokens) {  // wave-uniform: the sequence's last tile
+#pragma unroll
+                    for (int v = 0; v < 16; ++v) {
+                        const int key = tile0 + (v & 3) + 8 * (v >> 2) + 4 * h;
+                        s[v] = key < tokens ? s[v] : -INFINITY;
+                    }
+                }
+                // ---- online softmax, as in attention_hd_kernel: p = 2^(scale s - scale m), m the deferred running maximum
+                float cmax = s[0];
+#pragma unroll
+                for (int v = 1; v < 16; ++v) cmax = fmaxf(cmax, s[v]);
+                cmax = fmaxf(cmax, __shfl_xor(cmax, 32));
+                constexpr float kDefer = 8.0f, scale = kScale64;
+                const float m_old = m_run;
+                const float m_new = (cmax - m_old) * scale > kDefer ? cmax : m_old;  // first tile: m_old = -inf -> cmax
+                const float mneg = -m_new * scale;
+                m_run = m_new;
+                float sum = 0.0f;
+#pragma unroll
+                for (int v = 0; v < 16; ++v) {
+                    s[v] = __builtin_amdgcn_exp2f(fmaf(s[v], scale, mneg));  // exp2(-inf) = 0: masked keys
+                    sum += s[v];
+                }
+                if (__any(m_new != m_old)) {  // wave-uniform
+                    const float alpha = __builtin_amdgcn_exp2f((m_old - m_new) * scale);  // first tile: exp2(-inf) = 0; unmoved rows: 1
+                    l_run *= alpha;
+#pragma unroll
+                    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+                        for (int v = 0; v < 16; ++v) o[dt][v] *= alpha;
+                }
+                l_run += sum;
+                // ---- O^T += V^T . P^T: d = 32 dt + r on the A operand's lane, the keys of register v as above
+#pragma unroll
+                for (int s2 = 0; s2 < 2; ++s2) {
+                    if (tile0 + 16 * s2 >= tokens) break;  // wave-uniform: sixteen masked keys
+                    f32x4 x0 = {s[8 * s2], s[8 * s2 + 1], s[8 * s2 + 2], s[8 * s2 + 3]};
+                    f32x4 x1 = {s[8 * s2 + 4], s[8 * s2 + 5], s[8 * s2 + 6], s[8 * s2 + 7]};
+                    bf16x8 pf[3], vf[DT][3];
+#pragma unroll
+                    for (int pl = 0; pl < 3; ++pl) pf[pl] = __builtin_bit_cast(bf16x8, split3_piece8(x0, x1, pl));
+#pragma unroll
+                    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+                        for (int pl = 0; pl < 3; ++pl) {
+                            const bf16_t *vp = Vt + pl * G::V_ELEMS + (32 * dt + r) * VROW + 32 * t + 16 * s2 + 4 * h;
+                            const u32x2 lo = *reinterpret_cast<const u32x2 *>(vp), hi = *reinterpret_cast<const u32x2 *>(vp + 8);
+                            const u32x4 both = {lo[0], lo[1], hi[0], hi[1]};
+                            vf[dt][pl] = __builtin_bit_cast(bf16x8, both);
+                        }
+#pragma unroll
+                    for (int term = 0; term < 6; ++term)
+#pragma unroll
+                        for (int dt = 0; dt < DT; ++dt)
+                            o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[dt][SPLIT_TERM_A[term]], pf[SPLIT_TERM_W[term]], o[dt], 0, 0, 0);
+                }
+            }
+        }
+        __syncthreads();  // everybody is done with the chunk
+    }
+
+    // ---- normalise and store: a lane holds d = 32 dt + 8 q + 4 h + (0..3) of its query row in registers 4 q .. 4 q + 3
+    const int qrow = qrow0 + r;
+    if (active && qrow < q_rows) {
+        const float inv = 1.0f / (l_run + __shfl_xor(l_run, 32));
+        float *dst = out + ((size_t)image * tokens + qrow) * D + (size_t)head * HD + 4 * h;
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const f32x4 w = {o[dt][4 * q] * inv, o[dt][4 * q + 1] * inv, o[dt][4 * q + 2] * inv, o[dt][4 * q + 3] * inv};
+                *reinterpret_cast<f32x4 *>(dst + 32 * dt + 8 * q) = w;
+            }
+    }
+}
+
 template <bool BF16, bool QS>
 int launch_hd(hipStream_t s, const typename Geo<128, BF16>::elem *qkv, typename Geo<128, BF16>::elem *out, int n_images, int tokens,
               int heads, int head_dim, int q_rows) {
@@ -284,6 +513,14 @@ int vitattn::attention_hd_bf16(hipStream_t s, const unsigned short *qkv, unsigne
                                int head_dim, int q_rows, bool q_scaled) {
     return q_scaled ? launch_hd<true, true>(s, qkv, out, n_images, tokens, heads, head_dim, q_rows)
                     : launch_hd<true, false>(s, qkv, out, n_images, tokens, heads, head_dim, q_rows);
+}
+
+int vitattn::attention_split_f32(hipStream_t s, const float *qkv, float *out, int n_images, int tokens, int heads, int q_rows) {
+    const int qblocks = (q_rows + SP_QROWS - 1) / SP_QROWS;
+    if (heads > 65535 || (long long)n_images * qblocks > 0x7fffffffLL) return static_cast<int>(hipErrorInvalidValue);  // the grid
+    hipLaunchKernelGGL(attention_split_kernel, dim3((unsigned)(n_images * qblocks), (unsigned)heads), dim3(SP_THREADS), 0, s, qkv, out,
+                       tokens, heads, q_rows, qblocks);
+    return static_cast<int>(hipGetLastError());
 }
 
 extern "C" float vithip_qscale(int head_dim) {

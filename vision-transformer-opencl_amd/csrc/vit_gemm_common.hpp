@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "vit_hip_kernels.h"
+#include "vit_split3.hpp"
 
 namespace vitgemm {
 
@@ -268,47 +269,18 @@ constexpr int SPLIT_BK = 16;  // K step of the split kernels
 // LDS row of the split kernels: [hi 16 x bf16 | mid 16 | lo 16 | 16 bytes of padding] = 28 dwords.  A ds_read_b128 of 16
 // consecutive rows (one piece, one half of the K step) then touches 16 distinct 4-bank slots: conflict-free like the fp32 rows.
 constexpr int SPLIT_LD = 28;  // floats
-// piece pairs (A piece, W piece) in accumulation order; 0 = hi, 1 = mid, 2 = lo
-constexpr int SPLIT_TERM_A[6] = {0, 2, 1, 0, 1, 0};
-constexpr int SPLIT_TERM_W[6] = {2, 0, 1, 1, 0, 0};
-
-__device__ __forceinline__ float bf16_to_f32(__bf16 v) {
-    return __builtin_bit_cast(float, (unsigned)__builtin_bit_cast(unsigned short, v) << 16);
-}
-// piece `piece` (0 = hi, 1 = mid, 2 = lo) of four values, taken in this order: x holds what the earlier pieces left of the values
-// and, for pieces 0 and 1, is left holding the remainder for the next one.  The one definition of the pieces: the on-the-fly split
-// of both operands, the image walk's split of A and the weight-image producer (vit_split_weights.hip) all make them here.
-__device__ __forceinline__ u32x2 split3_piece(f32x4 &x, int piece) {
-    bf16x4 b;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) b[e] = (__bf16)x[e];  // v_cvt_pk_bf16_f32: round to nearest even
-    if (piece < 2) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) x[e] = x[e] - bf16_to_f32(b[e]);  // exact
-    }
-    return __builtin_bit_cast(u32x2, b);
-}
+// The pieces themselves, their arithmetic and the order of the six products: vit_split3.hpp (shared with the attention kernel).
+using vitsplit::SPLIT_TERM_A;
+using vitsplit::SPLIT_TERM_W;
+using vitsplit::bf16_to_f32;
+using vitsplit::split3_piece;
+using vitsplit::split3_piece2;
+using vitsplit::split3_piece8;
 // four consecutive-k values of one row -> the three pieces of each, written to their planes of the split LDS row `row`
 // (kc = k offset inside the K step, a multiple of 4: one ds_write_b64 per piece)
 __device__ __forceinline__ void split3_store(float *row, int kc, f32x4 x) {
 #pragma unroll
     for (int piece = 0; piece < 3; ++piece) *reinterpret_cast<u32x2 *>(row + piece * 8 + kc / 2) = split3_piece(x, piece);
-}
-// the same for eight consecutive k (x0 = k 0..3, x1 = k 4..7): piece `piece` of all eight as one 16-byte plane chunk
-__device__ __forceinline__ u32x4 split3_piece8(f32x4 &x0, f32x4 &x1, int piece) {
-    const u32x2 p0 = split3_piece(x0, piece), p1 = split3_piece(x1, piece);
-    return u32x4{p0[0], p0[1], p1[0], p1[1]};
-}
-
-// piece `piece` of two values, value by value the arithmetic of split3_piece: a quarter of a plane chunk, for the image walk's
-// finer restage slots
-__device__ __forceinline__ unsigned split3_piece2(f32x2 &x, int piece) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    bf16x2 b;
-#pragma unroll
-    for (int e = 0; e < 2; ++e) b[e] = (__bf16)x[e];
-    if (piece < 2) x = x - f32x2{bf16_to_f32(b[0]), bf16_to_f32(b[1])};  // exact
-    return __builtin_bit_cast(unsigned, b);
 }
 
 // ---- pre-split weights (vithip_gemm_args.w_split) and the swizzled LDS rows of the walk that reads them --------------------------

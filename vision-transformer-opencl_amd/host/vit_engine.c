@@ -1089,7 +1089,10 @@ static int encoder_layer(chunk_ctx *c, int l) {
         const vit_lane *ln = &c->lane[j];
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_ATTN));
         /* head_dim 64: the entries these generalise (_f32 / _f32_rows, _bf16io / _rows / _qscaled), their launches and their bits */
-        if (!bf16) HIP_TRY(e, vithip_attention_f32_hd(ln->s, ln->qkv, ln->y, ln->n, T, heads, D / heads, pruned ? 1 : T));
+        /* fp32 with the split on (fp32_split >= 0), head_dim 64: both products on the bf16 matrix pipe, like the GEMMs around them */
+        if (!bf16 && e->split && D / heads == 64)
+            HIP_TRY(e, vithip_attention_f32_split(ln->s, ln->qkv, ln->y, ln->n, T, heads, 64, pruned ? 1 : T));
+        else if (!bf16) HIP_TRY(e, vithip_attention_f32_hd(ln->s, ln->qkv, ln->y, ln->n, T, heads, D / heads, pruned ? 1 : T));
         else HIP_TRY(e, vithip_attention_bf16io_hd(ln->s, ln->qkv, ln->y, ln->n, T, heads, D / heads, pruned ? 1 : T, fold));
         HIP_TRY(e, stage_end(e, ln->s));
     }
