@@ -508,6 +508,83 @@ int vit_engine_set_head(vit_engine *e, const vit_head_spec *spec, const float *w
 int vit_engine_read_head_operand(vit_engine *e, float *dst, int rows);
 
 /*
+ * Dense linear heads: a class per pixel from the patch tokens, on the device -- the published segmentation heads of DINOv2 (mmseg
+ * BNHead, `linear` on one layer and `ms` on four): BatchNorm + 1x1 conv over the channel concatenation of the tapped layers' patch
+ * tokens, the logits resized bilinearly to the image, then the argmax.  The head is engine state, beside and independent of the
+ * classifier head: setting or removing one never disturbs the other.
+ *
+ * With K = num_layers, D = embed_dim, P = T - 1 = g * g patches (g = img_size / patch_size) and A_j the [P][D] rows of an
+ * intermediate call of VIT_TAP_PATCHES with the head's norm for layer layers[j], an image's logits [P][num_classes] are
+ *     logits = bias + sum_j A_j . weight[:, j*D .. (j+1)*D]^T
+ * weight [num_classes][K * D] row-major: the 1x1 conv's weight, the earliest layer's columns first (a BatchNorm in front of it is
+ * folded on the host: vit_dense_head_fold_batchnorm, vit_io.h); bias [num_classes]; HOST fp32 arrays read during the call and uploaded
+ * as they are.  Bits: a chain of vithip_gemm_f32 launches with arith = 0 (fp32 MFMA, as the classifier head uses, on both engine
+ * dtypes: the residual stream is fp32 on both), in layer order -- the first with VITHIP_EPI_BIAS, W = weight, ldw = K * D, the later
+ * ones with VITHIP_EPI_BIAS_RESIDUAL, a zero bias, W = weight + j * D and residual = C.  Each tap and its GEMM run directly behind
+ * their layer (the next layer overwrites the stream): the head holds one [max_batch][P][D] scratch and the logits
+ * [max_batch][P][num_classes], allocated by vit_engine_set_dense_head.
+ *
+ * vit_engine_set_dense_head: the rules of vit_engine_set_head.  It synchronises the device and drops a captured graph; the new
+ * allocations are made before the old ones are freed, on VIT_ERR_NOMEM the previous dense head stays in force; spec == NULL (weight
+ * and bias must then be NULL) removes the head; EVERY weight install removes it, and the copy calls do not carry it: set it again
+ * behind them, per engine.  VIT_ERR_STATE: no weights loaded yet.  VIT_ERR_ARG, nothing changed: a NULL weight or bias with a spec,
+ * num_layers outside 1..VIT_MAX_TAPS, a layer outside 0..depth-1 or not above the one before it (the message names the entry), norm
+ * other than 0 / 1, num_classes outside 1..255, reserved != 0, an img_size / patch_size that does not give a square grid of T - 1
+ * patches.
+ *
+ * The six calls mirror the six intermediate calls argument for argument (`out` is untyped: labels are bytes): the same images,
+ * chunking, lanes, stream rules, blocking behaviour, pinned output staging (sized in bytes; VIT_ERR_NOMEM puts it back at its
+ * classes-sized start), graph keying on the whole spec and eager _images calls.  Output rows, vit_engine_dense_row_bytes() bytes each
+ * (device: one [n][row] array, any alignment for LABELS, 4-byte aligned for GRID; host: caller-allocated rows out[i]):
+ *
+ *   VIT_DENSE_GRID    fp32 [num_classes][g][g]: entry [c][p] the logit of patch p in raster order, the transpose of the chain above
+ *   VIT_DENSE_LABELS  uint8 [out_h][out_w]: the argmax over the classes of F.interpolate(grid, (out_h, out_w), mode="bilinear",
+ *                     align_corners=False) -- vithip_dense_upsample_argmax_f32 (vit_hip_kernels.h) states the arithmetic and the order:
+ *                     higher wins, among equal values the lower label, a NaN value is no candidate, a pixel without one gets 255.  The
+ *                     full-resolution logits are never stored.  out_h = out_w = 0 means img_size x img_size.
+ *
+ * Layers behind the deepest tap are not launched, nor the final LayerNorm of the forward, the classifier head or the softmax;
+ * prune_last_layer engines run a tapped last layer unpruned for that call.  An image's row has the same bits whatever lanes and
+ * prune_last_layer are set to, wherever the image sits in whatever batch and whichever of the six calls delivers the same pixels.
+ * Non-finite values in one image reach only that image's row.  Profiling: the taps are accounted to VIT_STAGE_LN, the GEMMs to
+ * VIT_STAGE_HEAD, the upsampling (or the transpose) to VIT_STAGE_SOFTMAX.  vit_engine_read_logits() after a dense call is an error:
+ * nothing wrote the classifier's logits.
+ * VIT_ERR_STATE: no dense head set.  VIT_ERR_ARG (the engine stays usable, nothing was enqueued): NULL pointers, n <= 0, an unknown
+ * kind, reserved != 0, an out_h or out_w that is not 0 (GRID) or, with 0 standing for img_size, each on its own, outside 1..4096
+ * (LABELS), and what the matching forward refuses.
+ * Not covered: depth heads (class-token concatenation and bins), sliding-window inference, mapping the labels back through
+ * Resize / CenterCrop -- the labels are those of the img_size x img_size crop the engine saw.
+ */
+typedef struct {
+    int num_layers;            /* 1..VIT_MAX_TAPS */
+    int layers[VIT_MAX_TAPS];  /* strictly increasing, 0 <= l < depth, as in vit_intermediate_spec */
+    int norm;                  /* 1: final LayerNorm on every tapped layer (DINOv2), 0: raw stream */
+    int num_classes;           /* 1..255 */
+    int reserved;              /* must be 0 */
+} vit_dense_head_spec;
+int vit_engine_set_dense_head(vit_engine *e, const vit_dense_head_spec *spec, const float *weight, const float *bias);
+
+enum { VIT_DENSE_LABELS = 0, VIT_DENSE_GRID = 1 };
+typedef struct {
+    int kind;          /* VIT_DENSE_* */
+    int out_h, out_w;  /* LABELS: 0 = img_size, else 1..4096; GRID: must be 0 */
+    int reserved;      /* must be 0 */
+} vit_dense_spec;
+
+/* bytes per output row: out_h * out_w (LABELS) or num_classes * g * g * 4 (GRID); 0 on a bad spec or without a dense head */
+size_t vit_engine_dense_row_bytes(const vit_engine *e, const vit_dense_spec *spec);
+int vit_engine_dense_device(vit_engine *e, const float *d_images, int n, const vit_dense_spec *spec, void *d_out, void *stream);
+int vit_engine_dense_host(vit_engine *e, const float *const *images, int n, const vit_dense_spec *spec, void *const *out);
+int vit_engine_dense_device_u8(vit_engine *e, const unsigned char *d_images, int n, const float *mean, const float *std,
+                               const vit_dense_spec *spec, void *d_out, void *stream);
+int vit_engine_dense_host_u8(vit_engine *e, const unsigned char *const *images, int n, const float *mean, const float *std,
+                             const vit_dense_spec *spec, void *const *out);
+int vit_engine_dense_device_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, const vit_dense_spec *spec,
+                                   void *d_out, void *stream);
+int vit_engine_dense_host_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, const vit_dense_spec *spec,
+                                 void *const *out);
+
+/*
  * CLIP image towers (OpenAI / OpenCLIP ViT-B/32, B/16, L/14): VIT_MLP_QUICKGELU (or VIT_MLP_GELU for OpenCLIP checkpoints trained with
  * plain GELU) in vit_config, and the three pieces below; the projected embedding is a features call of VIT_FEAT_HEAD with the head
  * slot holding visual_projection (num_classes = projection_dim, zero bias).  INTEGRATION.md has the checkpoint mapping.

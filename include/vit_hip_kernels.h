@@ -647,6 +647,34 @@ enum { VITHIP_POS_BICUBIC = 0, VITHIP_POS_BICUBIC_AA = 1 };
 int vithip_pos_resample_table(int mode, int in, int out, int *first, int *count, float *weights, int max_taps);
 int vithip_pos_resample_f32(vithip_stream_t stream, const float *src, int g_src, float *dst, int g_dst, int dim, int mode);
 
+/*
+ * The tail of a dense linear head (csrc/vit_dense.hip): per-pixel labels from the logits of a g x g patch grid.  logits: per image
+ * (image_stride floats apart) P = g * g rows of `classes` floats, ld_logits floats from one row to the next, row p the patch p in
+ * raster order -- what a GEMM over the patch tokens writes.  out: per image (out_image_stride BYTES apart) out_h x out_w bytes,
+ *     out[y][x] = argmax_c  F.interpolate(map_c, size=(out_h, out_w), mode="bilinear", align_corners=False)[y][x]
+ * with the arithmetic, per axis (g source cells, `out` destination pixels), in fp32, nothing contracted, every product and sum rounded:
+ *     scale = (float)g / (float)out;  src = scale * ((float)dst + 0.5f) - 0.5f, a negative value becomes 0;
+ *     i0 = (int)src;  i1 = i0 + (i0 < g - 1);  l1 = src - (float)i0;  l0 = 1.0f - l1
+ *     v = l0y * (l0x * v00 + l1x * v01) + l1y * (l0x * v10 + l1x * v11)            v_rc = logits[(i_r(y) * g + i_c(x))][c]
+ * A higher v wins; among equal values (==) the lower label; a class whose v is NaN is not a candidate (+-Inf are ordinary values, and
+ * 0 * Inf is the NaN IEEE says); a pixel without a candidate gets 255 -- hence classes <= 255.  tests/dense_head_model.py restates it.
+ * No full-resolution logit is stored anywhere: a workgroup stages its tile's window of cells in LDS, walks the classes with a
+ * running best per pixel and stores bytes.  Any g >= 1 (g * g an int), any out_h, out_w in 1..4096 and any classes in 1..255 runs: a
+ * window that outgrows the LDS budget (out <= g) is walked in slices of classes, then the tile shrinks.  Only the out_h * out_w bytes
+ * of each image are written, through byte stores: out needs no alignment.  No atomics; results do not depend on the grid; an image's
+ * labels depend on that image's logits alone.
+ * hipErrorInvalidValue, nothing launched: NULL pointers, images < 1, g < 1, classes outside 1..255, out_h or out_w outside 1..4096,
+ * ld_logits < classes, image_stride < (P - 1) * ld_logits + classes, out_image_stride < out_h * out_w.
+ *
+ * vithip_dense_grid_f32: the same logits channel-major, out per image (out_image_stride FLOATS apart) [classes][P] = [classes][g][g],
+ * out[c][p] = logits[p][c] bit for bit.  (Not vithip_tap_f32's MAP: that one skips a class row and needs dim % 4 == 0 and 16-byte
+ * aligned rows, which a head of 21 or 150 classes does not give.)  The same refusals, with out_image_stride < classes * P.
+ */
+int vithip_dense_upsample_argmax_f32(vithip_stream_t stream, const float *logits, int ld_logits, size_t image_stride, unsigned char *out,
+                                     size_t out_image_stride, int images, int g, int classes, int out_h, int out_w);
+int vithip_dense_grid_f32(vithip_stream_t stream, const float *logits, int ld_logits, size_t image_stride, float *out,
+                          size_t out_image_stride, int images, int g, int classes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,20 @@ ImageData *vit_synth_images(const vit_config *cfg, int n, unsigned long long see
  */
 int vit_weights_fold_layer_scale(const vit_config *cfg, Network weights[], int count, const Network scales[], int scale_count);
 
+/*
+ * An eval-mode BatchNorm over the INPUT channels of a dense linear head (mmseg BNHead: decode_head.bn in front of
+ * decode_head.conv_seg) folded into the head's weight [classes][in_features] and bias [classes], on the host, in place, once -- what
+ * vit_engine_set_dense_head then takes.  gamma, beta, mean, var: in_features floats each (bn.weight, bn.bias, bn.running_mean,
+ * bn.running_var); eps: bn.eps.  In double, nothing contracted, k ascending:
+ *     s[k]     = gamma[k] / sqrt(var[k] + eps)
+ *     b'[c]    = (float)(b[c] + sum_k W[c][k] * (beta[k] - mean[k] * s[k]))        from the un-scaled W
+ *     W'[c][k] = (float)(W[c][k] * s[k])
+ * Returns 0, or nonzero with weight and bias untouched: a NULL pointer, classes or in_features < 1, eps not finite or negative, a
+ * non-finite value in any array, or a var[k] + eps that is not positive.
+ */
+int vit_dense_head_fold_batchnorm(float *weight, float *bias, int classes, int in_features, const float *gamma, const float *beta,
+                                  const float *mean, const float *var, double eps);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,39 @@ def head_spec(cls_layers=(), pool="none", depth: Optional[int] = None, reserved:
     return spec
 
 
+class CDenseHeadSpec(C.Structure):  # vit_dense_head_spec
+    _fields_ = [("num_layers", C.c_int), ("layers", C.c_int * VIT_MAX_TAPS), ("norm", C.c_int), ("num_classes", C.c_int), ("reserved", C.c_int)]
+
+
+class CDenseSpec(C.Structure):  # vit_dense_spec
+    _fields_ = [("kind", C.c_int), ("out_h", C.c_int), ("out_w", C.c_int), ("reserved", C.c_int)]
+
+
+DENSE_KINDS = {"labels": 0, "grid": 1}  # VIT_DENSE_*
+DENSE_NO_LABEL = 255  # the label of a pixel no class was a candidate for (every value NaN)
+
+
+def dense_head_spec(layers, norm=True, num_classes: int = 0, depth: Optional[int] = None, reserved: int = 0) -> CDenseHeadSpec:
+    """layers: the encoder layers whose patch tokens the head reads, in increasing order (mmseg out_indices); with `depth` given,
+    negative entries count from the last layer.  Everything is passed through unchecked for the C side to judge."""
+    ls = [int(l) for l in (layers if hasattr(layers, "__iter__") else [layers])]
+    if depth is not None:
+        ls = [l + depth if l < 0 else l for l in ls]
+    spec = CDenseHeadSpec(len(ls))
+    for j, l in enumerate(ls[:VIT_MAX_TAPS]):
+        spec.layers[j] = l
+    spec.norm, spec.num_classes, spec.reserved = int(norm), int(num_classes), int(reserved)
+    return spec
+
+
+def dense_spec(kind="labels", out_size=None, reserved: int = 0) -> CDenseSpec:
+    """kind: "labels" | "grid" (or a raw VIT_DENSE_* integer); out_size: None (img_size x img_size), an int (square) or (out_h,
+    out_w); passed through unchecked for the C side to judge."""
+    k = DENSE_KINDS[kind] if isinstance(kind, str) else int(kind)
+    h, w = (0, 0) if out_size is None else (out_size, out_size) if isinstance(out_size, (int, np.integer)) else out_size
+    return CDenseSpec(k, int(h), int(w), int(reserved))
+
+
 class CTopkSpec(C.Structure):  # vit_topk_spec
     _fields_ = [("k", C.c_int), ("score", C.c_int), ("reserved", C.c_int)]
 
@@ -272,14 +305,14 @@ def lib() -> C.CDLL:
         # the forward surface, output kind x place x input kind: (engine, images, n) + normalisation + spec + destination
         norm = {"": [], "_u8": [f32p, f32p], "_images": [C.POINTER(CPreproc)]}
         spec = {"forward": [], "features": [C.POINTER(CFeatureSpec)], "cls_attention": [C.POINTER(CAttentionSpec)],
-                "intermediate": [C.POINTER(CIntermediateSpec)], "topk": [C.POINTER(CTopkSpec)]}
+                "intermediate": [C.POINTER(CIntermediateSpec)], "topk": [C.POINTER(CTopkSpec)], "dense": [C.POINTER(CDenseSpec)]}
         for out in spec:
             for place in ("host", "device"):
                 for kind in norm:
                     images = C.POINTER(CImageU8) if kind == "_images" else C.c_void_p if place == "device" else \
                         C.POINTER(C.c_void_p if kind == "_u8" else f32p)
                     # host: a row per image; device: the rows, a forward's top-1 labels and probabilities, the stream
-                    dst = [C.POINTER(i32p if out == "topk" else f32p)] if place == "host" else [C.c_void_p] * (4 if out == "forward" else 2)
+                    dst = [C.POINTER(i32p if out == "topk" else C.c_void_p if out == "dense" else f32p)] if place == "host" else [C.c_void_p] * (4 if out == "forward" else 2)
                     name = f"vit_engine_{out}_{place}{kind}"
                     if hasattr(L, name):  # VIT_HIP_LIBRARY may name an earlier build (A/B timing), which lacks the later calls
                         getattr(L, name).argtypes = [C.c_void_p, images, C.c_int] + norm[kind] + spec[out] + dst
@@ -328,6 +361,13 @@ def lib() -> C.CDLL:
             L.vithip_pool_layernorm_f32_workspace_floats.argtypes = [C.c_int] * 4
             L.vithip_pool_layernorm_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        if hasattr(L, "vit_engine_set_dense_head"):  # an earlier build (see above) has no dense heads
+            L.vit_engine_set_dense_head.argtypes = [C.c_void_p, C.POINTER(CDenseHeadSpec), f32p, f32p]
+            L.vit_engine_dense_row_bytes.restype = C.c_size_t
+            L.vit_engine_dense_row_bytes.argtypes = [C.c_void_p, C.POINTER(CDenseSpec)]
+            L.vit_dense_head_fold_batchnorm.argtypes = [f32p, f32p, C.c_int, C.c_int, f32p, f32p, f32p, f32p, C.c_double]
+            L.vithip_dense_upsample_argmax_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_int] * 5
+            L.vithip_dense_grid_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_int] * 3
         L.vit_engine_read_logits.argtypes = [C.c_void_p, f32p, C.c_int]
         L.vit_engine_sync.argtypes = [C.c_void_p]
         L.vit_engine_get_stage_times.argtypes = [C.c_void_p, C.POINTER(CStageTimes)]
@@ -1169,6 +1209,30 @@ def fold_layer_scale_raw(cfg: ModelConfig, weights, scales, count: Optional[int]
                                                   s_arr, len(scales or []) if scale_count is None else scale_count))
 
 
+def fold_batchnorm_raw(weight, bias, classes: int, in_features: int, gamma, beta, mean, var, eps: float) -> int:
+    """vit_dense_head_fold_batchnorm on the arrays themselves, IN PLACE (float32, C-contiguous; None = a NULL pointer), every argument
+    passed through unchecked: returns the C return code (0, or nonzero with nothing written)."""
+    ptr = lambda a: None if a is None else a.ctypes.data_as(f32p)
+    return int(lib().vit_dense_head_fold_batchnorm(ptr(weight), ptr(bias), int(classes), int(in_features), ptr(gamma), ptr(beta), ptr(mean),
+                                                   ptr(var), float(eps)))
+
+
+def fold_batchnorm(weight, bias, gamma, beta, mean, var, eps: float = 1e-5):
+    """An eval-mode BatchNorm over the input channels (mmseg BNHead: decode_head.bn.weight / .bias / .running_mean / .running_var)
+    folded into a dense head's weight [classes][in_features] (conv_seg.weight, its trailing 1 x 1 dropped) and bias [classes]: returns
+    new (weight, bias) float32 arrays for Engine.set_dense_head.  No GPU involved."""
+    w = np.array(weight, np.float32, order="C")
+    b = np.array(bias, np.float32, order="C").reshape(-1)
+    w = w.reshape(b.size, -1)
+    bn = [np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1)) for a in (gamma, beta, mean, var)]
+    if any(a.size != w.shape[1] for a in bn):
+        raise VitError(f"fold_batchnorm: the BatchNorm has {[a.size for a in bn]} channels, the weight {w.shape[1]} input features")
+    rc = fold_batchnorm_raw(w, b, w.shape[0], w.shape[1], *bn, eps)
+    if rc:
+        raise VitError(f"vit_dense_head_fold_batchnorm refused the call ({rc}): non-finite values, eps < 0 or var + eps <= 0")
+    return w, b
+
+
 def fold_layer_scale(cfg: ModelConfig, weights: Sequence[np.ndarray], scales: Sequence[np.ndarray]) -> list:
     """LayerScale folded into out_proj and fc2 (vit_weights_fold_layer_scale): scales = [ls1 of layer 0, ls2 of layer 0, ls1 of layer
     1, ...], each [embed_dim].  Returns the folded tensors as new arrays (the caller's stay as they are): ordinary weights for
@@ -1253,6 +1317,49 @@ def softmax_topk(logits, k: int, score="prob", ld_logits: Optional[int] = None, 
         out.update(raw=after, raw_before=raw, logits_raw=src_after.view(np.uint32), logits_raw_before=src.view(np.uint32))
     lo = guard + out_offset
     return after[lo:lo + rows * ldo].reshape(rows, ldo)[:, :2 * int(k)].copy().view(np.int32)
+
+
+def dense_upsample_argmax_raw(logits_ptr, ld_logits: int, image_stride: int, out_ptr, out_image_stride: int, images: int, g: int,
+                              classes: int, out_h: int, out_w: int) -> int:
+    """vithip_dense_upsample_argmax_f32 on raw addresses, every argument passed through unchecked: returns the HIP error code."""
+    return int(lib().vithip_dense_upsample_argmax_f32(None, logits_ptr, int(ld_logits), int(image_stride), out_ptr, int(out_image_stride),
+                                                      int(images), int(g), int(classes), int(out_h), int(out_w)))
+
+
+def dense_upsample_argmax(logits, out_h: int, out_w: int, ld_logits: Optional[int] = None, image_rows: Optional[int] = None,
+                          out_ld_words: Optional[int] = None, pad_value: float = 0.0, frames=None, out: Optional[dict] = None) -> np.ndarray:
+    """vithip_dense_upsample_argmax_f32: logits [n][g * g][classes] -> labels uint8 [n][out_h][out_w].
+    ld_logits (>= classes): floats from one cell's row to the next; image_rows (>= g * g): rows from one image to the next, the rows
+    behind an image's g * g holding pad_value; out_ld_words: 32-bit words from one image's labels to the next (the byte stride is 4 x
+    that; default: out_h * out_w rounded up to a word).  frames: who allocates (default: exact buffers; tests/strided.py: guarded,
+    sentinel-filled frames -- the labels then sit in an int32 frame of one row per image); `out` receives the frames "logits" and
+    "labels" (before the launch: a refused call leaves them to be inspected)."""
+    logits = _as_f32(logits)
+    n, P, classes = logits.shape
+    g = int(round(P ** 0.5))
+    assert g * g == P, P
+    rows = P if image_rows is None else int(image_rows)
+    src = np.full((n, rows, classes), pad_value, np.float32)
+    src[:, :P] = logits
+    F = frames or _Plain
+    dL = F.framed(src.reshape(n * rows, classes), ld_logits)
+    words = (out_h * out_w + 3) // 4
+    dO = F.out_frame(n, words, out_ld_words, dtype=np.int32)
+    _note(out, logits=dL, labels=dO)
+    hip_check(dense_upsample_argmax_raw(dL.ptr, dL.ld, rows * dL.ld, dO.ptr, 4 * dO.ld, n, g, classes, out_h, out_w),
+              "vithip_dense_upsample_argmax_f32")
+    return np.ascontiguousarray(dO.window()).view(np.uint8)[:, :out_h * out_w].reshape(n, out_h, out_w).copy()
+
+
+def dense_grid(logits) -> np.ndarray:
+    """vithip_dense_grid_f32: logits [n][g * g][classes] -> fp32 [n][classes][g][g], the transpose."""
+    logits = _as_f32(logits)
+    n, P, classes = logits.shape
+    g = int(round(P ** 0.5))
+    assert g * g == P, P
+    d_src, d_out = DeviceArray.from_numpy(logits), DeviceArray((n, classes, g, g))
+    hip_check(lib().vithip_dense_grid_f32(None, d_src.ptr, classes, P * classes, d_out.ptr, P * classes, n, g, classes), "vithip_dense_grid_f32")
+    return d_out.numpy()
 
 
 def _norm_consts(mean, std, chans: int):
@@ -1396,8 +1503,8 @@ class Engine:
         L.vit_engine_copy_weights.argtypes = [C.c_void_p, C.c_void_p]
         self._check(L.vit_engine_copy_weights(self._h, other._h), "vit_engine_copy_weights")
 
-    # ---- the forward surface: vit_engine_<out>_<place><inp>, out "forward" | "features" | "cls_attention" | "intermediate" | "topk", inp "" | "_u8" | "_images" ----
-    def _call_args(self, out, inp, kind, l2_normalize, mean, std, resize_shorter, layers=None, norm=True, topk=None) -> list:
+    # ---- the forward surface: vit_engine_<out>_<place><inp>, out "forward" | "features" | "cls_attention" | "intermediate" | "topk" | "dense", inp "" | "_u8" | "_images" ----
+    def _call_args(self, out, inp, kind, l2_normalize, mean, std, resize_shorter, layers=None, norm=True, topk=None, dense=None) -> list:
         """What lies between n and the destination in the C call: the normalisation of the input kind, the spec of the output kind."""
         args = []
         if inp == "_u8":
@@ -1408,12 +1515,14 @@ class Engine:
             args.append(C.byref(intermediate_spec(layers, kind, norm, self.cfg.depth)))
         elif out == "topk":
             args.append(C.byref(topk))
+        elif out == "dense":
+            args.append(C.byref(dense))
         elif out != "forward":
             args.append(C.byref(feature_spec(kind, l2_normalize) if out == "features" else attention_spec(kind)))
         return args
 
     def _host(self, out, inp, images, kind=None, l2_normalize=False, mean=None, std=None, resize_shorter=None, layers=None,
-              norm=True, topk=None) -> np.ndarray:
+              norm=True, topk=None, dense=None) -> np.ndarray:
         """A host-path call: per-image pointers (or records) in, per-image rows of a new array out."""
         if inp == "_images":
             keep, in_ptrs = host_image_records(images, self.cfg.in_chans)
@@ -1424,29 +1533,32 @@ class Engine:
             keep = _as_f32(images)
             in_ptrs = (f32p * len(keep))(*[im.ctypes.data_as(f32p) for im in keep])
         n = len(keep)
-        args = self._call_args(out, inp, kind, l2_normalize, mean, std, resize_shorter, layers, norm, topk)
+        args = self._call_args(out, inp, kind, l2_normalize, mean, std, resize_shorter, layers, norm, topk, dense)
         if out == "forward":
             shape = (n, self.cfg.num_classes)
+        elif out == "dense":
+            shape = self.dense_shape(n, dense)
         elif out == "topk":
             shape = (n, 2 * max(topk.k, 1))  # a spec the C side refuses still gets rows: the call must see its own arguments
         elif out == "intermediate":
             shape = self.intermediate_shape(n, layers, kind, norm)
         else:
             shape = self.feature_shape(n, kind, l2_normalize) if out == "features" else self.attention_shape(n, kind)
-        rowp = i32p if out == "topk" else f32p
-        rows = np.empty(shape, np.int32 if out == "topk" else np.float32)
-        out_ptrs = (rowp * n)(*[rows[i].ctypes.data_as(rowp) for i in range(n)])
+        rowp = i32p if out == "topk" else C.c_void_p if out == "dense" else f32p
+        labels = out == "dense" and dense.kind == DENSE_KINDS["labels"]
+        rows = np.empty(shape, np.int32 if out == "topk" else np.uint8 if labels else np.float32)
+        out_ptrs = (rowp * n)(*[rows[i].ctypes.data if out == "dense" else rows[i].ctypes.data_as(rowp) for i in range(n)])
         name = f"vit_engine_{out}_host{inp}"
         self._check(getattr(lib(), name)(self._h, in_ptrs, n, *args, out_ptrs), name)
         return rows
 
     def _device(self, out, inp, images, n, dst, kind=None, l2_normalize=False, mean=None, std=None, resize_shorter=None, d_label=0,
-                d_prob=0, stream=0, layers=None, norm=True, topk=None) -> None:
+                d_prob=0, stream=0, layers=None, norm=True, topk=None, dense=None) -> None:
         """A device-path call: raw HBM addresses (images: a list of (ptr, H, W) for "_images"), async on `stream`."""
         if inp == "_images":
             images = image_records(images)
             n = len(images)
-        args = self._call_args(out, inp, kind, l2_normalize, mean, std, resize_shorter, layers, norm, topk)
+        args = self._call_args(out, inp, kind, l2_normalize, mean, std, resize_shorter, layers, norm, topk, dense)
         top1 = [d_label or None, d_prob or None] if out == "forward" else []
         name = f"vit_engine_{out}_device{inp}"
         self._check(getattr(lib(), name)(self._h, images, n, *args, dst, *top1, stream or None), name)
@@ -1681,6 +1793,69 @@ class Engine:
         """Back to the checkpoint's own head (vit_engine_set_head with a NULL spec)."""
         self._check(lib().vit_engine_set_head(self._h, None, None, None), "vit_engine_set_head")
         self._head_in = None
+
+    # ---- dense linear heads (vit_engine_set_dense_head, vit_engine_dense_*): a class per pixel from the patch tokens ----
+    def set_dense_head(self, weight, bias, layers, norm=True, reserved: int = 0) -> None:
+        """A dense linear head for the dense calls: weight [num_classes][len(layers) * embed_dim] (the 1x1 conv's weight, the
+        earliest layer's columns first; a BatchNorm in front of it folded by fold_batchnorm), bias [num_classes]; num_classes is
+        taken from bias.  layers: the tapped encoder layers (mmseg out_indices; negative entries count from the last), norm: the
+        final LayerNorm on every tap (DINOv2).  Independent of the classifier head.  Every weight install removes it: call this
+        again behind it.  DINOv2 `linear`: layers=(-1,);  `ms`: layers=(-4, -3, -2, -1) of ViT-S/B (out_indices [8, 9, 10, 11])."""
+        w = None if weight is None else _as_f32(weight)
+        b = None if bias is None else _as_f32(bias)
+        spec = dense_head_spec(layers, norm, 0 if b is None else b.size, self.cfg.depth, reserved)
+        F = spec.num_layers * self.cfg.embed_dim
+        if w is not None and b is not None and w.size != b.size * F:
+            raise VitError(f"set_dense_head: weight has {w.size} floats, {b.size} classes over {spec.num_layers} layers need {b.size} x {F}")
+        self._check(lib().vit_engine_set_dense_head(self._h, C.byref(spec), None if w is None else w.ctypes.data_as(f32p),
+                                                    None if b is None else b.ctypes.data_as(f32p)), "vit_engine_set_dense_head")
+
+    def reset_dense_head(self) -> None:
+        """Remove the dense head (vit_engine_set_dense_head with a NULL spec)."""
+        self._check(lib().vit_engine_set_dense_head(self._h, None, None, None), "vit_engine_set_dense_head")
+
+    def dense_row_bytes(self, kind="labels", out_size=None) -> int:
+        """Bytes per output row of a dense call; 0 on a bad spec or without a dense head."""
+        return int(lib().vit_engine_dense_row_bytes(self._h, C.byref(dense_spec(kind, out_size))))
+
+    def dense_shape(self, n: int, spec) -> tuple:
+        """Shape of the rows n images give: (n, out_h, out_w) uint8 labels or (n, num_classes, g, g) fp32 logits.  A spec the C side
+        refuses still gets rows (the call must see its own arguments and say what is wrong)."""
+        g = self.cfg.img_size // self.cfg.patch_size
+        nbytes = int(lib().vit_engine_dense_row_bytes(self._h, C.byref(spec)))
+        if spec.kind == DENSE_KINDS["labels"]:
+            h, w = spec.out_h or self.cfg.img_size, spec.out_w or self.cfg.img_size
+            return (n, h, w) if nbytes == h * w else (n, 1, 1)
+        return (n, nbytes // (4 * g * g), g, g) if nbytes else (n, 1, 1, 1)
+
+    def dense(self, images: np.ndarray, kind="labels", out_size=None) -> np.ndarray:
+        """Host path: per-image pointers in, per-image rows out -- kind "labels": uint8 [n][out_h][out_w], the argmax over the
+        classes of the head's logits resized bilinearly (align_corners=False) to out_size (None: img_size; an int or (h, w));
+        kind "grid": fp32 [n][num_classes][g][g], the logits themselves."""
+        return self._host("dense", "", images, dense=dense_spec(kind, out_size))
+
+    def dense_u8(self, images: np.ndarray, kind="labels", out_size=None, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
+        """Host path from 8-bit pixels [n][S][S][C] (see forward_u8)."""
+        return self._host("dense", "_u8", images, mean=mean, std=std, dense=dense_spec(kind, out_size))
+
+    def dense_images(self, images, resize_shorter: int, kind="labels", out_size=None, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
+        """Host path: a list of [H][W][C] uint8 arrays of any sizes in (see forward_images); the labels are those of the crop."""
+        return self._host("dense", "_images", images, mean=mean, std=std, resize_shorter=resize_shorter, dense=dense_spec(kind, out_size))
+
+    def dense_device(self, d_images: int, n: int, d_out: int, kind="labels", out_size=None, stream: int = 0) -> None:
+        """Device-resident path: raw HBM addresses, d_out [n][dense_row_bytes()] bytes, async on `stream`."""
+        self._device("dense", "", d_images, n, d_out, stream=stream, dense=dense_spec(kind, out_size))
+
+    def dense_device_u8(self, d_images: int, n: int, d_out: int, kind="labels", out_size=None, mean=IMAGENET_MEAN, std=IMAGENET_STD,
+                        stream: int = 0) -> None:
+        """Device-resident path from 8-bit pixels [n][S][S][C] in HBM."""
+        self._device("dense", "_u8", d_images, n, d_out, mean=mean, std=std, stream=stream, dense=dense_spec(kind, out_size))
+
+    def dense_device_images(self, images, d_out: int, resize_shorter: int, kind="labels", out_size=None, mean=IMAGENET_MEAN,
+                            std=IMAGENET_STD, stream: int = 0) -> None:
+        """Device-resident path from decoded images: a list of (ptr, H, W) records (see forward_device_images)."""
+        self._device("dense", "_images", images, None, d_out, mean=mean, std=std, resize_shorter=resize_shorter, stream=stream,
+                     dense=dense_spec(kind, out_size))
 
     def head_operand(self, rows: int) -> np.ndarray:
         """vit_engine_read_head_operand: the head GEMM's operand rows of the most recent chunk, [rows][in_features]."""

@@ -12,7 +12,9 @@
  *    class, pooled, tap -- has one writer, whoever asks for it;
  *    a features call ends instead in the final LN of the rows it returns, or in the fused LN + mean over the patch tokens;
  *    an attention call stops the last layer behind its QKV GEMM and stores the class token's softmax row;
- *    an intermediate call copies rows of x out behind the layers it taps and stops behind the deepest of them)
+ *    an intermediate call copies rows of x out behind the layers it taps and stops behind the deepest of them;
+ *    a dense call walks the layers of the dense head the same way, with a tap and a GEMM into per-patch logits behind each, and ends in
+ *    the upsample + argmax launch that turns them into a label per pixel)
  *
  * Weights are validated and uploaded once (the reference re-uploads them per op per image, e.g. ViT_opencl.c:136,630-631); every
  * install route ends in finish_install, which derives the folded and pre-split operands and resolves, per layer, what each GEMM and
@@ -57,9 +59,10 @@ _Static_assert(sizeof(vit_image_u8) == sizeof(vithip_image_u8) && offsetof(vit_i
 /* What a forward writes, besides where: probabilities [n][classes] and the optional top-1 records, the embedding rows `spec`
  * asks for (stage_features), the class token's attention over the tokens in the last layer (stage_cls_attention), or the residual
  * stream behind the layers `tap` names (stage_tap), [n][out_row_elems()] -- or, behind the head, the k best classes as records in
- * place of the probabilities (stage_head; 32-bit words, as many bytes as a float each).
+ * place of the probabilities (stage_head; 32-bit words, as many bytes as a float each) -- or the rows of a dense call
+ * (stage_dense_out: [n][out_row_bytes()] BYTES, labels or the fp32 grid; the one kind whose row is not counted in floats).
  * Zero-filled before use: the graph cache compares it bytewise.  The pointers are those of the call's (or chunk's) first image. */
-enum { VIT_OUT_PROBS = 0, VIT_OUT_FEATURES = 1, VIT_OUT_ATTENTION = 2, VIT_OUT_INTERMEDIATE = 3, VIT_OUT_TOPK = 4 };
+enum { VIT_OUT_PROBS = 0, VIT_OUT_FEATURES = 1, VIT_OUT_ATTENTION = 2, VIT_OUT_INTERMEDIATE = 3, VIT_OUT_TOPK = 4, VIT_OUT_DENSE = 5 };
 typedef struct {
     int kind;              /* VIT_OUT_PROBS: dst = probabilities, label / prob = top-1 (may be NULL); _FEATURES: dst = the rows of spec;
                             * _ATTENTION: dst = the rows of attn_kind; _INTERMEDIATE: dst = the rows of tap; _TOPK: dst = the records of
@@ -69,12 +72,13 @@ typedef struct {
     vit_topk_spec topk;    /* _TOPK: the checked spec (all zero otherwise) */
     int zero;              /* always 0: with it the struct has no padding, which a bytewise comparison would read */
     vit_intermediate_spec tap; /* _INTERMEDIATE: the checked spec, layers[num_layers..] zero (all zero otherwise) */
+    vit_dense_spec dense;  /* _DENSE: the checked spec with out_h / out_w resolved (all zero otherwise); the head is engine state */
     float *dst;
     int *label;
     float *prob;
 } vit_output;
-_Static_assert(sizeof(vit_output) == 5 * sizeof(int) + sizeof(vit_topk_spec) + sizeof(vit_intermediate_spec) + 3 * sizeof(void *) &&
-                   sizeof(vit_topk_spec) == 3 * sizeof(int) && sizeof(vit_intermediate_spec) == (4 + VIT_MAX_TAPS) * sizeof(int) && sizeof(vit_intermediate_spec) % sizeof(void *) == 0,
+_Static_assert(sizeof(vit_output) == 5 * sizeof(int) + sizeof(vit_topk_spec) + sizeof(vit_intermediate_spec) + sizeof(vit_dense_spec) + 3 * sizeof(void *) &&
+                   sizeof(vit_dense_spec) == 4 * sizeof(int) && sizeof(vit_topk_spec) == 3 * sizeof(int) && sizeof(vit_intermediate_spec) == (4 + VIT_MAX_TAPS) * sizeof(int) && sizeof(vit_intermediate_spec) % sizeof(void *) == 0,
                "vit_output must stay free of padding: the graph cache compares it bytewise");
 _Static_assert(VIT_SCORE_PROB == VITHIP_SCORE_PROB && VIT_SCORE_LOGIT == VITHIP_SCORE_LOGIT && VIT_MAX_TOPK == VITHIP_MAX_TOPK,
                "one numbering of the scores, one bound on k");
@@ -89,6 +93,10 @@ typedef struct { const float *ln_g, *ln_b; vit_gemm_ops head; } vit_final_ops;
  * (num_cls_layers + (pool != NONE)) * D, the head GEMM's W [num_classes][in] and bias, the operand rows [max_batch][in].  owned: the
  * three are allocations of the head's own (W with a zeroed tail pad behind it, as wblob has), which go with it. */
 typedef struct { vit_head_spec spec; size_t in; vit_gemm_ops ops; float *operand; int owned; } vit_head;
+/* The dense head in force (vit_engine_set_dense_head; num_layers == 0: none): the checked spec (layers behind num_layers zero), the
+ * 1x1 conv's W [num_classes][num_layers * D] (a zeroed tail pad behind it) and bias, a zero bias for the chain's later GEMMs, the
+ * patch rows of the layer just tapped [max_batch][P][D] and the logits [max_batch][P][num_classes]: five allocations of its own. */
+typedef struct { vit_dense_head_spec spec; float *W, *bias, *zero_bias, *rows, *logits; } vit_dense_head;
 
 struct vit_engine {
     vit_config cfg;
@@ -134,10 +142,11 @@ struct vit_engine {
     float *x, *y, *qkv, *hbuf, *z, *logits;
     /* the one classifier head: the checkpoint's own (restore_own_head) or a caller's (vit_engine_set_head); no stage tells them apart */
     vit_head head;
+    vit_dense_head dense;
     /* host-pointer path: double-buffered staging so that gather + H2D of piece i+1 overlap compute of piece i */
     float *in_stage[2], *out_stage[2];   /* device */
     float *pin_in[2], *pin_out[2];       /* pinned host */
-    size_t out_row_cap;                  /* floats per image out_stage / pin_out hold: classes, or the widest feature row seen */
+    size_t out_row_cap;                  /* BYTES per image out_stage / pin_out hold: classes floats, or the widest row seen */
     vithip_stream_t copy_stream;
     vithip_event_t ev_h2d[2], ev_done[2];
     /* 8-bit input: the host path's byte staging (allocated by the first u8 host call); the device path normalises into
@@ -392,7 +401,7 @@ int vit_engine_create(vit_engine **out, const vit_config *cfg, const vit_engine_
         }
     }
     HIP_TRY(e, vithip_stream_create(&e->copy_stream));
-    e->out_row_cap = NC;
+    e->out_row_cap = NC * sizeof(float);
     for (int b = 0; b < 2; ++b) {
         HIP_TRY(e, vithip_malloc((void **)&e->in_stage[b], B * img * sizeof(float)));
         HIP_TRY(e, vithip_malloc((void **)&e->out_stage[b], B * NC * sizeof(float)));
@@ -422,6 +431,12 @@ static void release_head(vit_head *h) {
     vithip_free((void *)h->ops.W); vithip_free((void *)h->ops.bias); vithip_free(h->operand);
 }
 
+/* the dense head's allocations go with it; nothing may be in flight */
+static void release_dense_head(vit_dense_head *h) {
+    vithip_free(h->W); vithip_free(h->bias); vithip_free(h->zero_bias); vithip_free(h->rows); vithip_free(h->logits);
+    memset(h, 0, sizeof(*h));
+}
+
 void vit_engine_destroy(vit_engine *e) {
     if (!e) return;
     vithip_set_device(e->opt.device);
@@ -432,6 +447,7 @@ void vit_engine_destroy(vit_engine *e) {
     vithip_free(e->x); vithip_free(e->y); vithip_free(e->qkv); vithip_free(e->hbuf);
     vithip_free(e->z); vithip_free(e->logits);
     release_head(&e->head);
+    release_dense_head(&e->dense);
     vithip_free(e->pre_g); /* one allocation: gamma, beta behind it */
     for (int j = 0; j < VIT_MAX_LANES; ++j) vithip_gemm_f32_workspace_destroy(e->gemm_ws[j]);
     if (e->copy_stream) { vithip_stream_sync(e->copy_stream); vithip_stream_destroy(e->copy_stream); }
@@ -636,6 +652,7 @@ static void restore_own_head(vit_engine *e) {
 static int finish_install(vit_engine *e) {
     const int rc = resolve_operands(e);
     restore_own_head(e);
+    release_dense_head(&e->dense); /* a caller's head like the classifier's: every install removes it */
     release_pre_norm(e); /* checkpoint data like a caller's head: every install removes it (the epsilon, architecture, stays) */
     if (rc) return rc;
     HIP_TRY(e, vithip_stream_sync(e->stream));
@@ -855,6 +872,7 @@ typedef struct {
     int stage, bf16;
     const void *A; int lda;
     vit_gemm_ops ops;                  /* W [N][K], bias; colsum and w_split: the fold's consumers and split engines */
+    int ldw;                           /* fp32 GEMMs: floats from one row of W to the next; 0 = K (a column block of a wider W: the dense head) */
     void *C; int ldc;
     int M, N, K;
     int role;                          /* VITHIP_EPI_BIAS, VITHIP_EPI_BIAS_GELU, VITHIP_EPI_BIAS_QGELU or VITHIP_EPI_BIAS_RESIDUAL */
@@ -889,7 +907,7 @@ static int gemm(vit_engine *e, vithip_stream_t s, const gemm_desc *g, int *stats
         a.handover_test = e->opt.gemm_handover_test; a.tile = e->opt.gemm_tile;
         a.arith = e->split && g->stage != VIT_STAGE_HEAD; /* every encoder GEMM (the embedding does not come through here) */
         a.w_split = a.arith ? g->ops.w_split : NULL;
-        a.A = g->A; a.lda = g->lda; a.W = g->ops.W; a.ldw = g->K; a.bias = g->ops.bias; a.residual = res; a.ldr = ldr;
+        a.A = g->A; a.lda = g->lda; a.W = g->ops.W; a.ldw = g->ldw ? g->ldw : g->K; a.bias = g->ops.bias; a.residual = res; a.ldr = ldr;
         a.C = g->C; a.ldc = g->ldc; a.M = g->M; a.N = g->N; a.K = g->K; a.epilogue = g->role;
         a.ln_rows = g->ln_rows; a.ln_colsum = g->ops.colsum;
         a.stats_out = g->stats_rows; a.stats_partials = g->stats_part; a.stats_eps = e->ln_eps;
@@ -1239,9 +1257,19 @@ static size_t tap_block_elems(const vit_engine *e, int kind) {
     const size_t T = (size_t)e->tokens;
     return (kind == VIT_TAP_CLS ? 1 : kind == VIT_TAP_TOKENS ? T : T - 1) * (size_t)e->cfg.embed_dim;
 }
+/* a dense row in BYTES: labels are a byte per pixel, the grid classes * P floats (`spec` checked, out_h / out_w resolved) */
+static size_t dense_row_bytes(const vit_engine *e, const vit_dense_spec *spec) {
+    if (spec->kind == VIT_DENSE_LABELS) return (size_t)spec->out_h * (size_t)spec->out_w;
+    return (size_t)e->dense.spec.num_classes * (size_t)(e->tokens - 1) * sizeof(float);
+}
+/* floats per row of every kind but VIT_OUT_DENSE, whose rows the routing below measures in bytes (out_row_bytes) */
 static size_t out_row_elems(const vit_engine *e, const vit_output *out) {
     if (out->kind == VIT_OUT_INTERMEDIATE) return (size_t)out->tap.num_layers * tap_block_elems(e, out->tap.kind);
     return row_elems(e, out->kind, out->kind == VIT_OUT_ATTENTION ? out->attn_kind : out->kind == VIT_OUT_TOPK ? out->topk.k : out->spec.kind);
+}
+
+static size_t out_row_bytes(const vit_engine *e, const vit_output *out) {
+    return out->kind == VIT_OUT_DENSE ? dense_row_bytes(e, &out->dense) : out_row_elems(e, out) * sizeof(float);
 }
 
 /* The embedding rows of the chunk instead of the head: the class block (the checkpoint's own head's operand, in the caller's rows),
@@ -1299,6 +1327,52 @@ static int stage_tap(chunk_ctx *c, const vit_output *out, int j) {
     return VIT_OK;
 }
 
+/* A dense call behind encoder layer layers[j]: per lane the patch rows of x as the layer has just left them (the tap of an
+ * intermediate call of VIT_TAP_PATCHES) into the head's scratch, then the GEMM of the chain over them -- the first writes
+ * bias + A_0 . W_0^T, the later ones add A_j . W_j^T in place, W_j the column block j of the head's W.  fp32 MFMA on both dtypes. */
+static int stage_dense_tap(chunk_ctx *c, int j) {
+    vit_engine *e = c->e;
+    const vit_dense_head *h = &e->dense;
+    const size_t P = (size_t)c->T - 1, D = (size_t)c->D;
+    const int NC = h->spec.num_classes, K = h->spec.num_layers;
+    for (int k = 0; k < c->L; ++k) {
+        const vit_lane *ln = &c->lane[k];
+        HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
+        RUN(tap_block(c, ln, h->rows + (size_t)ln->off * P * D, P * D, h->spec.norm, VITHIP_TAP_PATCHES));
+        HIP_TRY(e, stage_end(e, ln->s));
+    }
+    for (int k = 0; k < c->L; ++k) {
+        const vit_lane *ln = &c->lane[k];
+        const gemm_desc g = {.stage = VIT_STAGE_HEAD, .A = h->rows + (size_t)ln->off * P * D, .lda = c->D,
+                             .ops = {.W = h->W + (size_t)j * D, .bias = j ? h->zero_bias : h->bias}, .ldw = K * c->D,
+                             .C = h->logits + (size_t)ln->off * P * NC, .ldc = NC, .M = ln->n * (int)P, .N = NC, .K = c->D,
+                             .role = j ? VITHIP_EPI_BIAS_RESIDUAL : VITHIP_EPI_BIAS};
+        RUN(gemm(e, ln->s, &g, NULL));
+    }
+    return VIT_OK;
+}
+
+/* ... and behind the deepest of them: the lane's logits [n][P][classes] become its images' rows -- the labels of the upsampled maps
+ * (nothing of full resolution but the labels is written) or the channel-major grid. */
+static int stage_dense_out(chunk_ctx *c, const vit_output *out) {
+    vit_engine *e = c->e;
+    const vit_dense_head *h = &e->dense;
+    const int g = e->cfg.img_size / e->cfg.patch_size, NC = h->spec.num_classes;
+    const size_t P = (size_t)c->T - 1, row = out_row_bytes(e, out);
+    for (int k = 0; k < c->L; ++k) {
+        const vit_lane *ln = &c->lane[k];
+        const float *logits = h->logits + (size_t)ln->off * P * NC;
+        unsigned char *dst = (unsigned char *)out->dst + (size_t)ln->off * row;
+        HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_SOFTMAX));
+        if (out->dense.kind == VIT_DENSE_LABELS)
+            HIP_TRY(e, vithip_dense_upsample_argmax_f32(ln->s, logits, NC, P * NC, dst, row, ln->n, g, NC, out->dense.out_h, out->dense.out_w));
+        else
+            HIP_TRY(e, vithip_dense_grid_f32(ln->s, logits, NC, P * NC, (float *)dst, row / sizeof(float), ln->n, g, NC));
+        HIP_TRY(e, stage_end(e, ln->s));
+    }
+    return VIT_OK;
+}
+
 /* The head's operand row of an image is [class blocks, in the order of cls_layers | pooled block], head.in floats.  Behind encoder
  * layer l < depth - 1 when cls_layers names it: the class block of that layer, the launch (and so the bits) of an intermediate call
  * with VIT_TAP_CLS, norm = 1.  The blocks of the last layer are stage_head's; the checkpoint's own head names no other layer. */
@@ -1323,6 +1397,7 @@ static int class_rows_only(const vit_engine *e, const vit_output *out) {
     if (runs_head(out)) return e->head.spec.pool == VIT_HEAD_POOL_NONE; /* a pooled block reads every patch row */
     if (out->kind == VIT_OUT_FEATURES) return out->spec.kind == VIT_FEAT_CLS; /* MEAN and TOKENS read every row */
     if (out->kind == VIT_OUT_INTERMEDIATE) return out->tap.kind == VIT_TAP_CLS;
+    if (out->kind == VIT_OUT_DENSE) return 0; /* the patch rows of every tapped layer */
     return out->kind == VIT_OUT_ATTENTION; /* Q of the class rows, K of every token (qkv_only) */
 }
 
@@ -1404,6 +1479,13 @@ static int forward_chunk(vit_engine *e, vithip_stream_t s, const void *d_images,
             RUN(encoder_layer(c, l));
             if (l == out->tap.layers[j]) RUN(stage_tap(c, out, j++));
         }
+    } else if (out->kind == VIT_OUT_DENSE) { /* the same walk with the dense head's layers: a tap and a GEMM behind each, then the rows */
+        const vit_dense_head_spec *h = &e->dense.spec;
+        for (int l = 0, j = 0; j < h->num_layers; ++l) {
+            RUN(encoder_layer(c, l));
+            if (l == h->layers[j]) RUN(stage_dense_tap(c, j++));
+        }
+        RUN(stage_dense_out(c, out));
     } else {
         const int head_taps = runs_head(out);
         for (int l = 0; l < cfg->depth; ++l) {
@@ -1594,6 +1676,46 @@ size_t vit_engine_intermediate_row_elems(const vit_engine *e, const vit_intermed
     return e && !intermediate_spec_fault(e, spec, arg) ? (size_t)spec->num_layers * tap_block_elems(e, spec->kind) : 0;
 }
 
+/* The dense spec, checked and resolved against the model (out_h / out_w: 0 becomes img_size): NULL, or what is wrong as a format for
+ * (who, arg[0], arg[1]).  The head itself was checked when it was set. */
+static const char *dense_spec_fault(const vit_engine *e, const vit_dense_spec *spec, vit_dense_spec *res, int arg[2]) {
+    arg[0] = arg[1] = 0;
+    if (!spec) return "%s: the dense spec is required";
+    memset(res, 0, sizeof(*res));
+    arg[0] = spec->kind;
+    if (spec->kind != VIT_DENSE_LABELS && spec->kind != VIT_DENSE_GRID) return "%s: unknown dense kind %d";
+    arg[0] = spec->reserved;
+    if (spec->reserved != 0) return "%s: vit_dense_spec.reserved must be 0 (got %d)";
+    res->kind = spec->kind;
+    arg[0] = spec->out_h; arg[1] = spec->out_w;
+    if (spec->kind == VIT_DENSE_GRID) return spec->out_h || spec->out_w ? "%s: GRID takes no output size (out_h = %d, out_w = %d must be 0)" : NULL;
+    res->out_h = spec->out_h ? spec->out_h : e->cfg.img_size;
+    res->out_w = spec->out_w ? spec->out_w : e->cfg.img_size;
+    if (res->out_h < 1 || res->out_h > 4096 || res->out_w < 1 || res->out_w > 4096)
+        return "%s: out_h = %d and out_w = %d must be 1..4096 each (0 = img_size, which must then be in that range)";
+    return NULL;
+}
+
+static int output_dense(vit_engine *e, const char *who, const vit_dense_spec *spec, float *dst, vit_output *out) {
+    int arg[2];
+    memset(out, 0, sizeof(*out));
+    if (spec && !e->dense.spec.num_layers) return fail(e, VIT_ERR_STATE, "%s before vit_engine_set_dense_head()", who);
+    const char *fault = dense_spec_fault(e, spec, &out->dense, arg);
+    if (fault) {
+        memset(out, 0, sizeof(*out));
+        return fail(e, VIT_ERR_ARG, fault, who, arg[0], arg[1]);
+    }
+    out->kind = VIT_OUT_DENSE;
+    out->dst = dst;
+    return VIT_OK;
+}
+
+size_t vit_engine_dense_row_bytes(const vit_engine *e, const vit_dense_spec *spec) {
+    int arg[2];
+    vit_dense_spec res;
+    return e && e->dense.spec.num_layers && !dense_spec_fault(e, spec, &res, arg) ? dense_row_bytes(e, &res) : 0;
+}
+
 size_t vit_engine_attention_row_elems(const vit_engine *e, const vit_attention_spec *spec) {
     int arg;
     return e && !attention_spec_fault(spec, &arg) ? row_elems(e, VIT_OUT_ATTENTION, spec->kind) : 0;
@@ -1623,7 +1745,7 @@ static int forward_device_in(vit_engine *e, const void *d_images, const vit_inpu
     /* bytes from one image of d_images to the next: fp32 or 8-bit pixels, or a record */
     const size_t img = in->kind == VIT_IN_IMAGES ? sizeof(vithip_image_u8)
                                                  : (size_t)e->cfg.in_chans * e->cfg.img_size * e->cfg.img_size * (in->kind == VIT_IN_U8 ? 1 : sizeof(float));
-    const size_t row = out_row_elems(e, out);
+    const size_t row = out_row_bytes(e, out);
     HIP_TRY(e, vithip_set_device(e->opt.device)); /* the current device is per host thread: several engines may share a process */
     if (in->kind != VIT_IN_F32 && !e->ev_in_stage) HIP_TRY(e, vithip_event_create(&e->ev_in_stage));
     const int chunk = chunk_limit(e);
@@ -1641,7 +1763,7 @@ static int forward_device_in(vit_engine *e, const void *d_images, const vit_inpu
     for (int done = 0; done < n; done += chunk) {
         const int nb = n - done < chunk ? n - done : chunk;
         vit_output o = *out;
-        o.dst += (size_t)done * row;
+        o.dst = (float *)((char *)o.dst + (size_t)done * row);
         if (o.label) o.label += done;
         if (o.prob) o.prob += done;
         int rc = forward_chunk(e, s, (const char *)d_images + (size_t)done * img, in, e->in_stage[0], nb, &o);
@@ -1739,9 +1861,9 @@ static const vithip_image_u8 *piece_records(vit_engine *e, int slot, const vit_i
     return e->img_recs;
 }
 /* wait for the piece in slot b and hand its rows back: images first .. first + count - 1 */
-static int scatter_piece(vit_engine *e, int b, float *const *rows, int first, int count, size_t row) {
+static int scatter_piece(vit_engine *e, int b, float *const *rows, int first, int count, size_t row) { /* row: bytes */
     HIP_TRY(e, vithip_event_sync(e->ev_done[b]));
-    for (int i = 0; i < count; ++i) memcpy(rows[first + i], e->pin_out[b] + (size_t)i * row, row * sizeof(float));
+    for (int i = 0; i < count; ++i) memcpy(rows[first + i], (const char *)e->pin_out[b] + (size_t)i * row, row);
     return VIT_OK;
 }
 
@@ -1776,7 +1898,7 @@ static int cut_pieces(vit_engine *e, const char *who, int kind, const void *imag
     return VIT_OK;
 }
 
-/* The output staging holds max_batch rows of out_row_cap floats: classes at first, grown to the widest feature, attention or intermediate row a
+/* The output staging holds max_batch rows of out_row_cap bytes: classes floats at first, grown to the widest feature, attention or intermediate row a
  * host call has asked for (TOKENS: tokens * embed_dim; HEADS: heads * tokens; top-k records: 2k words, wider than a head of fewer classes).  Growing waits for everything in flight, frees both slots and allocates them again; if
  * that fails the call fails with VIT_ERR_NOMEM and the staging is back at its classes-sized start. */
 static int alloc_out_stage(vit_engine *e, size_t bytes) { /* both slots, freed first; a HIP error code, with both slots freed again */
@@ -1797,15 +1919,15 @@ static int alloc_out_stage(vit_engine *e, size_t bytes) { /* both slots, freed f
     }
     return rc;
 }
-static int ensure_out_stage(vit_engine *e, size_t row) {
+static int ensure_out_stage(vit_engine *e, size_t row) { /* row: bytes */
     if (row <= e->out_row_cap) return VIT_OK;
-    const size_t bytes = (size_t)e->opt.max_batch * row * sizeof(float);
+    const size_t bytes = (size_t)e->opt.max_batch * row;
     HIP_TRY(e, vithip_device_sync());
     int rc = alloc_out_stage(e, bytes);
     if (rc) {
         /* the wide rows do not fit: put the classes-sized staging back, so that the forwards go on as before this call */
-        const size_t NC = (size_t)e->cfg.num_classes;
-        e->out_row_cap = alloc_out_stage(e, (size_t)e->opt.max_batch * NC * sizeof(float)) ? 0 : NC;
+        const size_t own = (size_t)e->cfg.num_classes * sizeof(float);
+        e->out_row_cap = alloc_out_stage(e, (size_t)e->opt.max_batch * own) ? 0 : own;
         return fail(e, VIT_ERR_NOMEM, "no memory for 2 x %zu bytes of pinned and of device output staging (HIP error %d: %s)", bytes,
                     rc, vithip_error_string(rc));
     }
@@ -1823,7 +1945,7 @@ static int forward_host_in(vit_engine *e, const char *who, const void *images, c
     if (!e->weights_loaded) return fail(e, VIT_ERR_STATE, "forward before vit_engine_load_weights()");
     const size_t img = (size_t)e->cfg.in_chans * e->cfg.img_size * e->cfg.img_size;
     const int kind = in->kind, decoded = kind == VIT_IN_IMAGES;
-    const size_t row = out_row_elems(e, out); /* floats per image of the scatter stage */
+    const size_t row = out_row_bytes(e, out); /* bytes per image of the scatter stage */
     for (int i = 0; i < n; ++i)
         if (!host_image(kind, images, i) || !rows[i]) return fail(e, VIT_ERR_ARG, "%s: image or output row %d is NULL", who, i);
     const int chunk = chunk_limit(e);
@@ -1895,7 +2017,7 @@ static int forward_host_in(vit_engine *e, const char *who, const void *images, c
         const void *src = decoded ? (const void *)piece_records(e, b, (const vit_image_u8 *)images, lo[k], nb) : up[b];
         int rc = forward_chunk(e, e->stream, src, in, e->in_stage[b], nb, &o);
         if (rc) return rc;
-        HIP_TRY(e, vithip_memcpy_d2h(e->pin_out[b], e->out_stage[b], (size_t)nb * row * sizeof(float), e->stream));
+        HIP_TRY(e, vithip_memcpy_d2h(e->pin_out[b], e->out_stage[b], (size_t)nb * row, e->stream));
         HIP_TRY(e, vithip_event_record(e->ev_done[b], e->stream));
         if (e->opt.profile) e->pending_images += nb;
         /* piece k-1 (slot b^1) is finished by now or soon: hand its rows back */
@@ -1925,9 +2047,10 @@ typedef struct {
     const float *mean, *std; /* VIT_IN_U8 */
     const vit_preproc *pp;  /* VIT_IN_IMAGES */
     int out_kind;           /* VIT_OUT_* */
-    const void *spec;       /* vit_feature_spec (VIT_OUT_FEATURES), vit_attention_spec (_ATTENTION), vit_intermediate_spec (_INTERMEDIATE) or
-                             * vit_topk_spec (_TOPK) */
-    float *dst;             /* VIT_AT_DEVICE: [n][row]; _TOPK: the caller's 32-bit words, carried as the floats they are as wide as */
+    const void *spec;       /* vit_feature_spec (VIT_OUT_FEATURES), vit_attention_spec (_ATTENTION), vit_intermediate_spec (_INTERMEDIATE),
+                             * vit_topk_spec (_TOPK) or vit_dense_spec (_DENSE) */
+    float *dst;             /* VIT_AT_DEVICE: [n][row]; _TOPK: the caller's 32-bit words, carried as the floats they are as wide as; _DENSE:
+                             * the caller's rows of bytes, carried untyped */
     float *const *rows;     /* VIT_AT_HOST: a row per image */
     int *label;             /* VIT_AT_DEVICE, VIT_OUT_PROBS: top-1 (may be NULL) */
     float *prob;
@@ -1953,6 +2076,7 @@ static int run_call(vit_engine *e, const vit_call *c) {
     else if (c->out_kind == VIT_OUT_ATTENTION) rc = output_attention(e, c->who, (const vit_attention_spec *)c->spec, c->dst, &out);
     else if (c->out_kind == VIT_OUT_INTERMEDIATE) rc = output_intermediate(e, c->who, (const vit_intermediate_spec *)c->spec, c->dst, &out);
     else if (c->out_kind == VIT_OUT_TOPK) rc = output_topk(e, c->who, (const vit_topk_spec *)c->spec, c->dst, &out);
+    else if (c->out_kind == VIT_OUT_DENSE) rc = output_dense(e, c->who, (const vit_dense_spec *)c->spec, c->dst, &out);
     else out = output_probs(c->dst, c->label, c->prob);
     if (rc) return rc;
     return host ? forward_host_in(e, c->who, c->images, &in, c->n, &out, c->rows) : forward_device_in(e, c->images, &in, c->n, &out, c->stream);
@@ -2135,6 +2259,41 @@ int vit_engine_topk_host_images(vit_engine *e, const vit_image_u8 *images, int n
                                     .pp = pp, .out_kind = VIT_OUT_TOPK, .spec = spec, .rows = (float *const *)out});
 }
 
+/* the dense calls: rows of bytes, carried through the one call path as the untyped pointers they are */
+int vit_engine_dense_device(vit_engine *e, const float *d_images, int n, const vit_dense_spec *spec, void *d_out, void *stream) {
+    return run_call(e, &(vit_call){.who = "dense_device", .place = VIT_AT_DEVICE, .in_kind = VIT_IN_F32, .images = d_images, .n = n,
+                                    .out_kind = VIT_OUT_DENSE, .spec = spec, .dst = (float *)d_out, .stream = stream});
+}
+
+int vit_engine_dense_device_u8(vit_engine *e, const unsigned char *d_images, int n, const float *mean, const float *std,
+                               const vit_dense_spec *spec, void *d_out, void *stream) {
+    return run_call(e, &(vit_call){.who = "dense_device_u8", .place = VIT_AT_DEVICE, .in_kind = VIT_IN_U8, .images = d_images, .n = n,
+                                    .mean = mean, .std = std, .out_kind = VIT_OUT_DENSE, .spec = spec, .dst = (float *)d_out, .stream = stream});
+}
+
+int vit_engine_dense_device_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, const vit_dense_spec *spec,
+                                   void *d_out, void *stream) {
+    return run_call(e, &(vit_call){.who = "dense_device_images", .place = VIT_AT_DEVICE, .in_kind = VIT_IN_IMAGES, .images = images,
+                                    .n = n, .pp = pp, .out_kind = VIT_OUT_DENSE, .spec = spec, .dst = (float *)d_out, .stream = stream});
+}
+
+int vit_engine_dense_host(vit_engine *e, const float *const *images, int n, const vit_dense_spec *spec, void *const *out) {
+    return run_call(e, &(vit_call){.who = "dense_host", .place = VIT_AT_HOST, .in_kind = VIT_IN_F32, .images = images, .n = n,
+                                    .out_kind = VIT_OUT_DENSE, .spec = spec, .rows = (float *const *)out});
+}
+
+int vit_engine_dense_host_u8(vit_engine *e, const unsigned char *const *images, int n, const float *mean, const float *std,
+                             const vit_dense_spec *spec, void *const *out) {
+    return run_call(e, &(vit_call){.who = "dense_host_u8", .place = VIT_AT_HOST, .in_kind = VIT_IN_U8, .images = images, .n = n,
+                                    .mean = mean, .std = std, .out_kind = VIT_OUT_DENSE, .spec = spec, .rows = (float *const *)out});
+}
+
+int vit_engine_dense_host_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, const vit_dense_spec *spec,
+                                 void *const *out) {
+    return run_call(e, &(vit_call){.who = "dense_host_images", .place = VIT_AT_HOST, .in_kind = VIT_IN_IMAGES, .images = images, .n = n,
+                                    .pp = pp, .out_kind = VIT_OUT_DENSE, .spec = spec, .rows = (float *const *)out});
+}
+
 int vit_engine_handover_stats(vit_engine *e, long *taken, long *recomputed) {
     if (!e) return VIT_ERR_ARG;
     HIP_TRY(e, vithip_set_device(e->opt.device));
@@ -2242,6 +2401,79 @@ int vit_engine_read_head_operand(vit_engine *e, float *dst, int rows) {
     HIP_TRY(e, vithip_device_sync()); /* the chunk may have run on a caller-provided stream */
     HIP_TRY(e, vithip_memcpy_d2h(dst, e->head.operand, (size_t)rows * e->head.in * sizeof(float), e->stream));
     HIP_TRY(e, vithip_stream_sync(e->stream));
+    return VIT_OK;
+}
+
+/* The dense head spec, checked against the model: NULL, or what is wrong as a format for (arg[0], arg[1]). */
+static const char *dense_head_spec_fault(const vit_engine *e, const vit_dense_head_spec *spec, int arg[2]) {
+    arg[0] = spec->num_layers; arg[1] = VIT_MAX_TAPS;
+    if (spec->num_layers < 1 || spec->num_layers > VIT_MAX_TAPS) return "set_dense_head: num_layers = %d must be 1..%d";
+    arg[0] = spec->norm; arg[1] = 0;
+    if (spec->norm != 0 && spec->norm != 1) return "set_dense_head: norm must be 0 or 1 (got %d)";
+    arg[0] = spec->num_classes;
+    if (spec->num_classes < 1 || spec->num_classes > 255) return "set_dense_head: num_classes = %d must be 1..255 (a label is a byte, 255 the empty one)";
+    arg[0] = spec->reserved;
+    if (spec->reserved != 0) return "set_dense_head: vit_dense_head_spec.reserved must be 0 (got %d)";
+    for (int j = 0; j < spec->num_layers; ++j) {
+        arg[0] = j; arg[1] = spec->layers[j];
+        if (spec->layers[j] < 0 || spec->layers[j] >= e->cfg.depth) return "set_dense_head: layers[%d] = %d is not a layer of the model";
+        if (j && spec->layers[j] <= spec->layers[j - 1]) return "set_dense_head: layers[%d] = %d is not above the entry before it (strictly increasing)";
+    }
+    const int g = e->cfg.img_size / e->cfg.patch_size;
+    arg[0] = g; arg[1] = e->tokens - 1;
+    if (g < 1 || g * g != e->tokens - 1) return "set_dense_head: needs a square grid of patches: (img_size / patch_size = %d)^2 is not the model's %d";
+    return NULL;
+}
+
+int vit_engine_set_dense_head(vit_engine *e, const vit_dense_head_spec *spec, const float *weight, const float *bias) {
+    if (!e) return VIT_ERR_ARG;
+    if (!spec && (weight || bias)) return fail(e, VIT_ERR_ARG, "set_dense_head: a NULL spec (no dense head) takes no weight and no bias");
+    if (spec) {
+        int arg[2];
+        const char *fault = dense_head_spec_fault(e, spec, arg);
+        if (fault) return fail(e, VIT_ERR_ARG, fault, arg[0], arg[1]);
+        if (!weight || !bias) return fail(e, VIT_ERR_ARG, "set_dense_head: weight and bias are required with a spec");
+    }
+    if (!e->weights_loaded) return fail(e, VIT_ERR_STATE, "set_dense_head before vit_engine_load_weights()");
+    HIP_TRY(e, vithip_set_device(e->opt.device));
+    if (!spec) { /* as an install: nothing in flight, no graph with the head's buffers in its launches */
+        HIP_TRY(e, vithip_device_sync());
+        drop_graph(e);
+        release_dense_head(&e->dense);
+        return VIT_OK;
+    }
+    /* the new head first, whole; only then the old one goes */
+    const size_t D = (size_t)e->cfg.embed_dim, F = (size_t)spec->num_layers * D, NC = (size_t)spec->num_classes,
+                 B = (size_t)e->opt.max_batch, P = (size_t)e->tokens - 1;
+    const size_t wbytes = NC * F * sizeof(float);
+    const size_t pad = 128 * F * sizeof(float) > WEIGHT_TAIL_PAD ? 128 * F * sizeof(float) : WEIGHT_TAIL_PAD; /* a GEMM tile of rows */
+    vit_dense_head h;
+    memset(&h, 0, sizeof(h));
+    int hrc = vithip_malloc((void **)&h.W, wbytes + pad);
+    if (!hrc) hrc = vithip_malloc((void **)&h.bias, NC * sizeof(float));
+    if (!hrc) hrc = vithip_malloc((void **)&h.zero_bias, NC * sizeof(float));
+    if (!hrc) hrc = vithip_malloc((void **)&h.rows, B * P * D * sizeof(float));
+    if (!hrc) hrc = vithip_malloc((void **)&h.logits, B * P * NC * sizeof(float));
+    if (hrc) {
+        release_dense_head(&h);
+        return fail(e, VIT_ERR_NOMEM, "set_dense_head: no memory for a head of %zu x %zu floats, %zu x %zu patch rows and their logits (HIP error %d: %s); "
+                    "the previous dense head stays", NC, F, B, P, hrc, vithip_error_string(hrc));
+    }
+    hrc = vithip_memcpy_h2d(h.W, weight, wbytes, e->stream);
+    if (!hrc) hrc = vithip_memset((char *)h.W + wbytes, 0, pad, e->stream);
+    if (!hrc) hrc = vithip_memcpy_h2d(h.bias, bias, NC * sizeof(float), e->stream);
+    if (!hrc) hrc = vithip_memset(h.zero_bias, 0, NC * sizeof(float), e->stream);
+    if (!hrc) hrc = vithip_device_sync(); /* the uploads, and every call that still uses the old head, on whatever stream */
+    if (hrc) {
+        release_dense_head(&h);
+        return fail(e, VIT_ERR_HIP, "set_dense_head: HIP error %d (%s) uploading the head; the previous dense head stays", hrc, vithip_error_string(hrc));
+    }
+    drop_graph(e);
+    release_dense_head(&e->dense);
+    h.spec.num_layers = spec->num_layers; /* the entries of layers behind num_layers stay zero */
+    for (int j = 0; j < spec->num_layers; ++j) h.spec.layers[j] = spec->layers[j];
+    h.spec.norm = spec->norm; h.spec.num_classes = spec->num_classes;
+    e->dense = h;
     return VIT_OK;
 }
 

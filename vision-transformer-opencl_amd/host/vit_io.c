@@ -364,6 +364,35 @@ int vit_weights_fold_layer_scale(const vit_config *cfg, Network weights[], int c
     return 0;
 }
 
+/* An eval-mode BatchNorm over the input channels folded into a dense head's weight and bias (vit_io.h).  Every check runs before the
+ * first write; the per-channel factors live in one scratch array of doubles. */
+int vit_dense_head_fold_batchnorm(float *weight, float *bias, int classes, int in_features, const float *gamma, const float *beta,
+                                  const float *mean, const float *var, double eps) {
+    if (!weight || !bias || !gamma || !beta || !mean || !var || classes < 1 || in_features < 1) return -1;
+    if (!isfinite(eps) || eps < 0.0) return -1;
+    const size_t N = (size_t)classes, K = (size_t)in_features;
+    if (!all_finite(weight, N * K) || !all_finite(bias, N) || !all_finite(gamma, K) || !all_finite(beta, K) || !all_finite(mean, K) ||
+        !all_finite(var, K))
+        return -1;
+    for (size_t k = 0; k < K; ++k)
+        if (!((double)var[k] + eps > 0.0)) return -1;
+    double *s = (double *)malloc(2 * K * sizeof(double)), *t = s ? s + K : NULL; /* t[k] = beta[k] - mean[k] * s[k] */
+    if (!s) return -1;
+    for (size_t k = 0; k < K; ++k) {
+        s[k] = (double)gamma[k] / sqrt((double)var[k] + eps);
+        t[k] = (double)beta[k] - (double)mean[k] * s[k];
+    }
+    for (size_t c = 0; c < N; ++c) {
+        float *row = weight + c * K;
+        double sum = 0.0;
+        for (size_t k = 0; k < K; ++k) sum += (double)row[k] * t[k];
+        bias[c] = (float)((double)bias[c] + sum);
+        for (size_t k = 0; k < K; ++k) row[k] = (float)((double)row[k] * s[k]);
+    }
+    free(s);
+    return 0;
+}
+
 ImageData *vit_synth_images(const vit_config *cfg, int n, unsigned long long seed) {
     if (n <= 0) return NULL;
     const size_t per = (size_t)cfg->in_chans * cfg->img_size * cfg->img_size;
