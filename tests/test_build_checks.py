@@ -100,6 +100,32 @@ def test_the_lint_fails_on_deliberately_broken_sites(listings):
     assert len(found) == 1 and "LDS-DMA" in found[0], found
 
 
+def test_kernel_digest_ignores_block_label_ordinals_and_sees_one_register(listings):
+    """tools/kernel_asm_digests.py compares two trees kernel by kernel.  On the seven latency-tile kernels as compiled: a kernel's text
+    runs from its label through its descriptor; the same text with its block labels renumbered (what a changed instantiation order
+    does: .LBB1_4 -> .LBB6_4) has the same digest; one register of one instruction changed has another."""
+    d, r = listings
+    assert r.returncode == 0, r.stdout + r.stderr
+    spec = importlib.util.spec_from_file_location("kernel_asm_digests", os.path.join(ROOT, "tools", "kernel_asm_digests.py"))
+    dig = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(dig)
+    found = dig.kernel_texts(open(os.path.join(d, "vit_gemm_latency.s")).read())
+    assert len(found) == 7 and all("gemm_f32_nt_latency_kernel" in name for name, _ in found), [name for name, _ in found]
+    assert len({dig.digest(body) for _, body in found}) == 7  # seven epilogues, seven different kernels
+    for name, body in found:
+        assert body.startswith(name + ":") and body.endswith(".end_amdhsa_kernel") and f".amdhsa_kernel {name}" in body
+        assert "s_endpgm" in body and ".amdhsa_next_free_vgpr" in body
+    name, body = next((n, b) for n, b in found if re.search(r"\.LBB[1-9]\d*_\d+", b))
+    ordinal = re.search(r"\.LBB(\d+)_", body).group(1)
+    renumbered = body.replace(f"BB{ordinal}_", f"BB{int(ordinal) + 5}_")
+    assert renumbered != body and dig.digest(renumbered) == dig.digest(body)
+    lines = body.split("\n")
+    k = next(i for i, l in enumerate(lines) if re.match(r"^\s+v_\w+ v\d+, ", l))
+    reg = int(re.match(r"^\s+v_\w+ v(\d+), ", lines[k]).group(1))
+    lines[k] = re.sub(r"v%d, " % reg, "v%d, " % (reg + 1), lines[k], count=1)
+    assert dig.digest("\n".join(lines)) != dig.digest(body)
+
+
 def test_streamed_attention_vector_memory_operations_are_the_ones_its_counted_waits_assume(listings):
     """csrc/vit_attention_stream.hip proves that a head's Q refills have landed with COUNTED `s_waitcnt vmcnt(N)`: N is computed from
     ST_QDMA = 4 LDS-DMA pieces and ST_STORES = 4 output stores per retired query block, in a fixed order per wave.  That arithmetic

@@ -32,7 +32,13 @@ import argparse, concurrent.futures, glob, os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vision-transformer-opencl_amd", "csrc")
-PER_FILE_FLAGS = {"vit_attention_stream": ["-fno-slp-vectorize"]}  # = FLAGS_* of the Makefile
+PER_FILE_FLAGS = {  # = FLAGS_* of the Makefile
+    "vit_attention_stream": ["-fno-slp-vectorize"],
+    "vit_preproc": ["-ffp-contract=off"],
+    "vit_pos_resample": ["-ffp-contract=off"],
+    "vit_swiglu": ["-ffp-contract=off"],
+    "vit_dense": ["-ffp-contract=off"],
+}
 
 VM_STORE = re.compile(r"^(global|buffer|flat|scratch)_store_")
 VM_LOAD = re.compile(r"^(global|buffer|flat|scratch)_load_")
@@ -225,10 +231,10 @@ def check_text(text: str) -> tuple[list[str], dict]:
     return found, stats
 
 
-def compile_to_asm(src: str, outdir: str, extra: list[str] | None = None) -> str:
+def compile_to_asm(src: str, outdir: str, extra: list[str] | None = None, root: str = ROOT) -> str:
     base = os.path.splitext(os.path.basename(src))[0]
     out = os.path.join(outdir, base + ".s")
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
+    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(root, "include"),
            "-Wno-unused-value", "-Wno-inline-asm", *PER_FILE_FLAGS.get(base, []), *(extra or []), "-S", "--cuda-device-only", src, "-o", out]
     subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
     return out

@@ -260,16 +260,15 @@ int launch_gemm_bf16_w4(hipStream_t s, const Bf16Params &p, int epilogue, int cu
         return static_cast<int>(hipErrorInvalidValue);
     const int total = p.tiles_m * p.tiles_n;
     const dim3 grid(total < cus ? total : cus), block(WTHREADS);
-    switch (epilogue) {
-        case VITHIP_BF16_EPI_BF16: hipLaunchKernelGGL(gemm_bf16_w4_kernel<VITHIP_BF16_EPI_BF16>, grid, block, 0, s, p); break;
-        case VITHIP_BF16_EPI_BF16_GELU: hipLaunchKernelGGL(gemm_bf16_w4_kernel<VITHIP_BF16_EPI_BF16_GELU>, grid, block, 0, s, p); break;
-        case 501: hipLaunchKernelGGL((gemm_bf16_w4_kernel<VITHIP_BF16_EPI_BF16, 1>), grid, block, 0, s, p); break;
-        case 502: hipLaunchKernelGGL((gemm_bf16_w4_kernel<VITHIP_BF16_EPI_BF16, 2>), grid, block, 0, s, p); break;
-        case 504: hipLaunchKernelGGL((gemm_bf16_w4_kernel<VITHIP_BF16_EPI_BF16, 4>), grid, block, 0, s, p); break;
-        case 505: hipLaunchKernelGGL((gemm_bf16_w4_kernel<VITHIP_BF16_EPI_BF16, 5>), grid, block, 0, s, p); break;
-        default: return static_cast<int>(hipErrorInvalidValue);
-    }
-    return static_cast<int>(hipGetLastError());
+    if (epilogue > 500)  // 501, 502, 504, 505: the timing-only builds DBG = 1, 2, 4, 5 of the bf16 epilogue
+        return with_epilogue<1, 2, 4, 5>(epilogue - 500, [&](auto dbg) {
+            hipLaunchKernelGGL((gemm_bf16_w4_kernel<VITHIP_BF16_EPI_BF16, decltype(dbg)::value>), grid, block, 0, s, p);
+            return static_cast<int>(hipGetLastError());
+        });
+    return with_epilogue<VITHIP_BF16_EPI_BF16, VITHIP_BF16_EPI_BF16_GELU>(epilogue, [&](auto epi) {
+        hipLaunchKernelGGL(gemm_bf16_w4_kernel<decltype(epi)::value>, grid, block, 0, s, p);
+        return static_cast<int>(hipGetLastError());
+    });
 }
 
 }  // namespace vitgemm

@@ -29,7 +29,9 @@
 //    fuses "+ pos_emb" and the token-row remap into the store.
 #include <new>
 
+#include "vit_device.hpp"
 #include "vit_gemm_common.hpp"
+#include "vit_row.hpp"
 #ifdef VIT_PROBES
 #include "vit_probes.h"
 #endif
@@ -386,48 +388,23 @@ __global__ void cls_rows_kernel(const float *cls, const float *pos, float *x, in
 
 template <int BM, int BN, int WM, int WN, int AMODE, int BK = 32, bool PIPE = false, int ARITH = ARITH_F32>
 int launch_tile(hipStream_t stream, GemmParams &p, int epilogue) {
-    p.tiles_m = (p.M + BM - 1) / BM;
-    p.tiles_n = (p.N + BN - 1) / BN;
-    const dim3 grid(p.tiles_m * p.tiles_n), block(256);
+    const dim3 grid(set_tile_grid(p, BM, BN)), block(256);
     if constexpr (AMODE == A_PATCHES) {
         hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS, A_PATCHES, 0, BK, PIPE>), grid, block, 0, stream, p);
+        return static_cast<int>(hipGetLastError());
     } else {
-        switch (epilogue) {
-            case VITHIP_EPI_BIAS:
-                hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS, A_DENSE, 0, BK, PIPE, ARITH>), grid, block, 0, stream, p);
-                break;
-            case VITHIP_EPI_BIAS_GELU:
-                hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_GELU, A_DENSE, 0, BK, PIPE, ARITH>), grid, block, 0, stream, p);
-                break;
-            case VITHIP_EPI_BIAS_RESIDUAL:
-                hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_RESIDUAL, A_DENSE, 0, BK, PIPE, ARITH>), grid, block, 0, stream, p);
-                break;
-            case EPI_BIAS_LN:
-                hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WM, WN, EPI_BIAS_LN, A_DENSE, 0, BK, PIPE, ARITH>), grid, block, 0, stream, p);
-                break;
-            case EPI_BIAS_GELU_LN:
-                hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WM, WN, EPI_BIAS_GELU_LN, A_DENSE, 0, BK, PIPE, ARITH>), grid, block, 0, stream, p);
-                break;
-            case VITHIP_EPI_BIAS_QGELU:
-                hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_QGELU, A_DENSE, 0, BK, PIPE, ARITH>), grid, block, 0, stream, p);
-                break;
-            case EPI_BIAS_QGELU_LN:
-                hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WM, WN, EPI_BIAS_QGELU_LN, A_DENSE, 0, BK, PIPE, ARITH>), grid, block, 0, stream, p);
-                break;
-            default:
-                return static_cast<int>(hipErrorInvalidValue);
-        }
+        return with_epilogue(TileEpilogues{}, epilogue, [&](auto epi) {
+            hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WM, WN, decltype(epi)::value, A_DENSE, 0, BK, PIPE, ARITH>), grid, block, 0, stream, p);
+            return static_cast<int>(hipGetLastError());
+        });
     }
-    return static_cast<int>(hipGetLastError());
 }
 
 #ifdef VIT_PROBES
 template <int DBG, int EPI = VITHIP_EPI_BIAS, bool PIPE = false>
 int launch_probe(hipStream_t stream, GemmParams &p) {
-    p.tiles_m = (p.M + 127) / 128;
-    p.tiles_n = (p.N + 127) / 128;
-    hipLaunchKernelGGL((gemm_f32_nt_kernel<128, 128, 64, 64, EPI, A_DENSE, DBG, 32, PIPE>),
-                       dim3(p.tiles_m * p.tiles_n), dim3(256), 0, stream, p);
+    const dim3 grid(set_tile_grid(p, 128, 128));
+    hipLaunchKernelGGL((gemm_f32_nt_kernel<128, 128, 64, 64, EPI, A_DENSE, DBG, 32, PIPE>), grid, dim3(256), 0, stream, p);
     return static_cast<int>(hipGetLastError());
 }
 #endif
@@ -545,9 +522,15 @@ int dispatch(hipStream_t stream, GemmParams &p, int epilogue, int tile, int grou
     }
 }
 
-bool aligned16(const void *ptr) { return (reinterpret_cast<size_t>(ptr) & 15) == 0; }
+using vit_row::aligned16;
 
 }  // namespace
+
+int vitgemm::launch_cls_rows(hipStream_t stream, const float *cls, const float *pos, float *x, int n_images, int tokens, int dim) {
+    const int total = n_images * dim;
+    hipLaunchKernelGGL(cls_rows_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, cls, pos, x, n_images, tokens, dim);
+    return static_cast<int>(hipGetLastError());
+}
 
 extern "C" {
 
@@ -586,21 +569,19 @@ struct GemmWorkspace {
 static size_t workspace_dev_bytes(int slots) { return 4096 + (size_t)slots * 128 * 128 * 4; }
 
 size_t vithip_gemm_f32_workspace_bytes(void) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    return workspace_dev_bytes(2 * cus);
+    const int cus = vitdev::current_cus();
+    return cus > 0 ? workspace_dev_bytes(2 * cus) : 0;
 }
 
 int vithip_gemm_f32_workspace_create(void **ws) {
     if (!ws) return static_cast<int>(hipErrorInvalidValue);
     *ws = nullptr;
-    int dev = 0, cus = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return static_cast<int>(e);
+    int dev = 0;
+    const int cus = vitdev::current_cus(&dev);
+    if (cus <= 0) return static_cast<int>(hipErrorInvalidDevice);
     GemmWorkspace *w = new (std::nothrow) GemmWorkspace{nullptr, 2 * cus, dev, 0};
     if (!w) return static_cast<int>(hipErrorOutOfMemory);
-    e = hipExtMallocWithFlags(&w->dev, workspace_dev_bytes(w->slots), hipDeviceMallocUncached);
+    hipError_t e = hipExtMallocWithFlags(&w->dev, workspace_dev_bytes(w->slots), hipDeviceMallocUncached);
     if (e == hipSuccess) e = hipMemset(w->dev, 0, 4096);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
@@ -733,11 +714,7 @@ int vithip_patch_embed_f32(vithip_stream_t stream, const float *images, const fl
     p.M = n_images * G * G; p.N = embed_dim; p.K = K;
     p.patches = G * G; p.grid = G; p.patch = patch_size; p.img = img_size; p.chans = in_chans;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int total = n_images * embed_dim;
-    hipLaunchKernelGGL(cls_rows_kernel, dim3((total + 255) / 256), dim3(256), 0, s, cls, pos, x,
-                       n_images, G * G + 1, embed_dim);
-    int e = static_cast<int>(hipGetLastError());
-    if (e) return e;
+    if (const int e = launch_cls_rows(s, cls, pos, x, n_images, G * G + 1, embed_dim)) return e;
     return dispatch<A_PATCHES>(s, p, VITHIP_EPI_BIAS, 0, 0);
 }
 

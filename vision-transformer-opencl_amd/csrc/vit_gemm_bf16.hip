@@ -25,6 +25,7 @@
 //  * Tile walk: XCD-aware remap + groups of 8 tile rows (as the fp32 kernel).
 #include "vit_device.hpp"
 #include "vit_gemm_common.hpp"
+#include "vit_row.hpp"
 #ifdef VIT_PROBES
 #include "vit_probes.h"
 #endif
@@ -296,14 +297,7 @@ __global__ void patchify_bf16_kernel(const float *__restrict__ images, bf16_t *_
     }
 }
 
-__global__ void cls_rows_bf16path_kernel(const float *cls, const float *pos, float *x, int n_images, int tokens, int dim) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_images * dim) return;
-    const int im = i / dim, d = i - im * dim;
-    x[(size_t)im * tokens * dim + d] = cls[d] + pos[d];  // class_token + pos_emb row 0 (ViT_seq.c:72-101)
-}
-
-bool aligned16(const void *ptr) { return (reinterpret_cast<size_t>(ptr) & 15) == 0; }
+using vit_row::aligned16;
 // The kernel variant is a per-call field of vithip_gemm_bf16_args; the product library has no mutable process-wide state.  The probe build (-DVIT_PROBES) adds process-wide overrides and instrumented kernels.
 #ifdef VIT_PROBES
 int g_variant = 0;  // 0 none, 1 two-stage kernel, 2 ping-pong, 3 stamped ping-pong, 4 event-log ping-pong, 5 four-wave experiment (vit_gemm_bf16_w4.hip)
@@ -369,14 +363,12 @@ int vithip_patch_embed_bf16(vithip_stream_t stream, const float *images, const u
     if (blocks > 256 * 32) blocks = 256 * 32;
     hipLaunchKernelGGL(patchify_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, s, images, patches16, n_images, img_size,
                        patch_size, in_chans);
-    const int total = n_images * embed_dim;
-    hipLaunchKernelGGL(cls_rows_bf16path_kernel, dim3((total + 255) / 256), dim3(256), 0, s, cls, pos, x, n_images, P + 1, embed_dim);
+    if (const int e = vitgemm::launch_cls_rows(s, cls, pos, x, n_images, P + 1, embed_dim)) return e;
     Bf16Params p{};
     p.A = patches16; p.W = conv_w16; p.bias = conv_b; p.R = pos; p.C = x;
     p.lda = K; p.ldw = K; p.ldr = embed_dim; p.ldc = embed_dim;
     p.M = n_images * P; p.N = embed_dim; p.K = K;
-    p.tiles_m = (p.M + TBM - 1) / TBM;
-    p.tiles_n = (p.N + TBN - 1) / TBN;
+    (void)vitgemm::set_tile_grid(p, TBM, TBN);  // (the launcher sizes its own grid)
     p.group_m = 8;
     p.patches = P;
     const int g_cus = vitdev::current_cus();  // of the current device, asked per call (engines of several devices share the process)
@@ -412,8 +404,7 @@ int vithip_gemm_bf16(vithip_stream_t stream, const vithip_gemm_bf16_args *a) {
     p.A = a->A; p.W = a->W; p.bias = a->bias; p.R = a->residual; p.C = a->C;
     p.lda = a->lda; p.ldw = a->ldw; p.ldr = a->ldr; p.ldc = a->ldc;
     p.M = a->M; p.N = a->N; p.K = a->K;
-    p.tiles_m = (p.M + TBM - 1) / TBM;
-    p.tiles_n = (p.N + TBN - 1) / TBN;
+    const int total = vitgemm::set_tile_grid(p, TBM, TBN);
     // tile rows per L2 group of the walk (tools/gemm_bf16_group.py, batch 2048, round 4): N = 768 (three tile columns: out_proj,
     // fc2) fetches 6.56 GB per fc2 launch with groups of 8 rows and 4.95 GB with 2, at 1 % less time; wide N (QKV, fc1) is best at 8
     p.group_m = p.tiles_n <= 4 ? 2 : 8;
@@ -442,7 +433,6 @@ int vithip_gemm_bf16(vithip_stream_t stream, const vithip_gemm_bf16_args *a) {
 #endif
     const int g_cus = vitdev::current_cus();  // of the current device, asked per call (engines of several devices share the process)
     if (g_cus <= 0) return static_cast<int>(hipErrorInvalidDevice);
-    const int total = p.tiles_m * p.tiles_n;
     const dim3 grid(total < g_cus ? total : g_cus), block(THREADS);  // one persistent workgroup per CU
     hipStream_t s = static_cast<hipStream_t>(stream);
     // ping-pong kernel: needs two K steps per tile (its bias slot is recycled every second tile) and
@@ -468,18 +458,17 @@ int vithip_gemm_bf16(vithip_stream_t stream, const vithip_gemm_bf16_args *a) {
     }
 #endif
     if (variant != 1 && pp_ok) return vitgemm::launch_gemm_bf16_pp(s, p, a->epilogue, g_cus);
-    switch (a->epilogue) {
 #ifdef VIT_PROBES
-        case 101: hipLaunchKernelGGL((gemm_bf16_nt_kernel<VITHIP_BF16_EPI_BF16, 1>), grid, block, 0, s, p); break;
-        case 102: hipLaunchKernelGGL((gemm_bf16_nt_kernel<VITHIP_BF16_EPI_BF16, 2>), grid, block, 0, s, p); break;
+    if (a->epilogue == 101 || a->epilogue == 102)  // timing probes of the two-stage kernel: DBG 1, 2
+        return vitgemm::with_epilogue<1, 2>(a->epilogue - 100, [&](auto dbg) {
+            hipLaunchKernelGGL((gemm_bf16_nt_kernel<VITHIP_BF16_EPI_BF16, decltype(dbg)::value>), grid, block, 0, s, p);
+            return static_cast<int>(hipGetLastError());
+        });
 #endif
-        case VITHIP_BF16_EPI_BF16: hipLaunchKernelGGL(gemm_bf16_nt_kernel<VITHIP_BF16_EPI_BF16>, grid, block, 0, s, p); break;
-        case VITHIP_BF16_EPI_BF16_GELU: hipLaunchKernelGGL(gemm_bf16_nt_kernel<VITHIP_BF16_EPI_BF16_GELU>, grid, block, 0, s, p); break;
-        case VITHIP_BF16_EPI_BF16_QGELU: hipLaunchKernelGGL(gemm_bf16_nt_kernel<VITHIP_BF16_EPI_BF16_QGELU>, grid, block, 0, s, p); break;
-        case VITHIP_BF16_EPI_F32_RESIDUAL: hipLaunchKernelGGL(gemm_bf16_nt_kernel<VITHIP_BF16_EPI_F32_RESIDUAL>, grid, block, 0, s, p); break;
-        default: return static_cast<int>(hipErrorInvalidValue);
-    }
-    return static_cast<int>(hipGetLastError());
+    return vitgemm::with_epilogue(vitgemm::Bf16Epilogues{}, a->epilogue, [&](auto epi) {
+        hipLaunchKernelGGL(gemm_bf16_nt_kernel<decltype(epi)::value>, grid, block, 0, s, p);
+        return static_cast<int>(hipGetLastError());
+    });
 }
 
 }  // extern "C"

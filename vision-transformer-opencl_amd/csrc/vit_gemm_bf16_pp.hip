@@ -886,39 +886,26 @@ __global__ __launch_bounds__(PTHREADS) void gemm_bf16_pp_kernel(const Bf16Params
 
 }  // namespace
 
+template <int EPI, int STAMP = 0, int DBG = 0, bool LNF = false>
+static int launch_pp(hipStream_t s, const Bf16Params &p, dim3 grid) {
+    hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI, STAMP, DBG, LNF>), grid, dim3(PTHREADS), 0, s, p);
+    return static_cast<int>(hipGetLastError());
+}
+
 int launch_gemm_bf16_pp(hipStream_t s, const Bf16Params &p, int epilogue, int cus) {
     const int total = p.tiles_m * p.tiles_n;
-    const dim3 grid(total < cus ? total : cus), block(PTHREADS);  // one persistent workgroup per CU
-    if (p.ln_rows || p.x16) {  // LayerNorm folded in (consumer: ln_rows + ln_colsum; producer: x16 + partials)
-        switch (epilogue) {
-            case VITHIP_BF16_EPI_BF16: hipLaunchKernelGGL((gemm_bf16_pp_kernel<VITHIP_BF16_EPI_BF16, 0, 0, true>), grid, block, 0, s, p); break;
-            case VITHIP_BF16_EPI_BF16_GELU: hipLaunchKernelGGL((gemm_bf16_pp_kernel<VITHIP_BF16_EPI_BF16_GELU, 0, 0, true>), grid, block, 0, s, p); break;
-            case VITHIP_BF16_EPI_BF16_QGELU: hipLaunchKernelGGL((gemm_bf16_pp_kernel<VITHIP_BF16_EPI_BF16_QGELU, 0, 0, true>), grid, block, 0, s, p); break;
-            case VITHIP_BF16_EPI_F32_RESIDUAL: hipLaunchKernelGGL((gemm_bf16_pp_kernel<VITHIP_BF16_EPI_F32_RESIDUAL, 0, 0, true>), grid, block, 0, s, p); break;
-            default: return static_cast<int>(hipErrorInvalidValue);
-        }
-        return static_cast<int>(hipGetLastError());
-    }
-    switch (epilogue) {
-        case VITHIP_BF16_EPI_BF16: hipLaunchKernelGGL(gemm_bf16_pp_kernel<VITHIP_BF16_EPI_BF16>, grid, block, 0, s, p); break;
-        case VITHIP_BF16_EPI_BF16_GELU: hipLaunchKernelGGL(gemm_bf16_pp_kernel<VITHIP_BF16_EPI_BF16_GELU>, grid, block, 0, s, p); break;
-        case VITHIP_BF16_EPI_BF16_QGELU: hipLaunchKernelGGL(gemm_bf16_pp_kernel<VITHIP_BF16_EPI_BF16_QGELU>, grid, block, 0, s, p); break;
-        case VITHIP_BF16_EPI_F32_RESIDUAL: hipLaunchKernelGGL(gemm_bf16_pp_kernel<VITHIP_BF16_EPI_F32_RESIDUAL>, grid, block, 0, s, p); break;
-        case VITHIP_BF16_EPI_F32_EMBED: hipLaunchKernelGGL(gemm_bf16_pp_kernel<VITHIP_BF16_EPI_F32_EMBED>, grid, block, 0, s, p); break;
-#ifdef VIT_PROBES  // timing-only (DBG) and stamped / event-log (STAMP) instantiations: probe build only
-        case 201: hipLaunchKernelGGL((gemm_bf16_pp_kernel<VITHIP_BF16_EPI_BF16, 0, 1>), grid, block, 0, s, p); break;
-        case 202: hipLaunchKernelGGL((gemm_bf16_pp_kernel<VITHIP_BF16_EPI_BF16, 0, 2>), grid, block, 0, s, p); break;
-        case 203: hipLaunchKernelGGL((gemm_bf16_pp_kernel<VITHIP_BF16_EPI_BF16, 0, 3>), grid, block, 0, s, p); break;
-        case 204: hipLaunchKernelGGL((gemm_bf16_pp_kernel<VITHIP_BF16_EPI_BF16, 0, 4>), grid, block, 0, s, p); break;
-        case 300 + VITHIP_BF16_EPI_BF16: hipLaunchKernelGGL((gemm_bf16_pp_kernel<VITHIP_BF16_EPI_BF16, 2>), grid, block, 0, s, p); break;
-        case 300 + VITHIP_BF16_EPI_F32_RESIDUAL: hipLaunchKernelGGL((gemm_bf16_pp_kernel<VITHIP_BF16_EPI_F32_RESIDUAL, 2>), grid, block, 0, s, p); break;
-        case 100 + VITHIP_BF16_EPI_BF16: hipLaunchKernelGGL((gemm_bf16_pp_kernel<VITHIP_BF16_EPI_BF16, 1>), grid, block, 0, s, p); break;
-        case 100 + VITHIP_BF16_EPI_BF16_GELU: hipLaunchKernelGGL((gemm_bf16_pp_kernel<VITHIP_BF16_EPI_BF16_GELU, 1>), grid, block, 0, s, p); break;
-        case 100 + VITHIP_BF16_EPI_F32_RESIDUAL: hipLaunchKernelGGL((gemm_bf16_pp_kernel<VITHIP_BF16_EPI_F32_RESIDUAL, 1>), grid, block, 0, s, p); break;
+    const dim3 grid(total < cus ? total : cus);  // one persistent workgroup per CU
+    if (p.ln_rows || p.x16)  // LayerNorm folded in (consumer: ln_rows + ln_colsum; producer: x16 + partials)
+        return with_epilogue(Bf16Epilogues{}, epilogue, [&](auto epi) { return launch_pp<decltype(epi)::value, 0, 0, true>(s, p, grid); });
+#ifdef VIT_PROBES  // probe build only: codes that select the kernel's DBG (timing-only) or STAMP (stamped / event-log) argument
+    if (epilogue >= 201 && epilogue <= 204)
+        return with_epilogue<1, 2, 3, 4>(epilogue - 200, [&](auto dbg) { return launch_pp<VITHIP_BF16_EPI_BF16, 0, decltype(dbg)::value>(s, p, grid); });
+    if (epilogue >= 300)
+        return with_epilogue<VITHIP_BF16_EPI_BF16, VITHIP_BF16_EPI_F32_RESIDUAL>(epilogue - 300, [&](auto epi) { return launch_pp<decltype(epi)::value, 2>(s, p, grid); });
+    if (epilogue >= 100)
+        return with_epilogue<VITHIP_BF16_EPI_BF16, VITHIP_BF16_EPI_BF16_GELU, VITHIP_BF16_EPI_F32_RESIDUAL>(epilogue - 100, [&](auto epi) { return launch_pp<decltype(epi)::value, 1>(s, p, grid); });
 #endif
-        default: return static_cast<int>(hipErrorInvalidValue);
-    }
-    return static_cast<int>(hipGetLastError());
+    return with_epilogue(Bf16PingPongEpilogues{}, epilogue, [&](auto epi) { return launch_pp<decltype(epi)::value>(s, p, grid); });
 }
 
 }  // namespace vitgemm

@@ -26,6 +26,44 @@ constexpr bool epi_is_fold(int epi) { return epi == EPI_BIAS_LN || epi == EPI_BI
 constexpr bool epi_is_gelu(int epi) { return epi == VITHIP_EPI_BIAS_GELU || epi == EPI_BIAS_GELU_LN; }
 constexpr bool epi_is_qgelu(int epi) { return epi == VITHIP_EPI_BIAS_QGELU || epi == EPI_BIAS_QGELU_LN; }
 
+// ---- host side: a run-time epilogue code -> a kernel's template argument ----------------------------------------------------
+// f(std::integral_constant<int, E>) for the E among EPIS... that equals `epilogue`, and its result; hipErrorInvalidValue for a code
+// that is none of them.  Only the listed codes are instantiated: a launcher's list IS the set of kernels it builds.
+template <int... EPIS, typename F>
+int with_epilogue(int epilogue, F &&f) {
+    int rc = static_cast<int>(hipErrorInvalidValue);
+    (void)((epilogue == EPIS && (rc = f(std::integral_constant<int, EPIS>{}), true)) || ...);
+    return rc;
+}
+template <int... EPIS> struct EpilogueList {};
+template <int... EPIS, typename F>
+int with_epilogue(EpilogueList<EPIS...>, int epilogue, F &&f) { return with_epilogue<EPIS...>(epilogue, f); }
+// What each kernel family takes (a new epilogue is added to the lists of the kernels that implement it, nowhere else):
+// one tile per workgroup (vit_gemm.hip) and the latency tile (vit_gemm_latency.hip)
+using TileEpilogues = EpilogueList<VITHIP_EPI_BIAS, VITHIP_EPI_BIAS_GELU, VITHIP_EPI_BIAS_RESIDUAL, EPI_BIAS_LN, EPI_BIAS_GELU_LN,
+                                   VITHIP_EPI_BIAS_QGELU, EPI_BIAS_QGELU_LN>;
+// the persistent walk (vit_gemm_persistent.hip): those, and the residual epilogue that leaves the row sums
+using WalkEpilogues = EpilogueList<VITHIP_EPI_BIAS, VITHIP_EPI_BIAS_GELU, VITHIP_EPI_BIAS_RESIDUAL, EPI_BIAS_LN, EPI_BIAS_GELU_LN,
+                                   VITHIP_EPI_BIAS_QGELU, EPI_BIAS_QGELU_LN, EPI_RESIDUAL_STATS>;
+// bf16: the two-stage kernel (vit_gemm_bf16.hip) and the ping-pong kernel with a LayerNorm folded in (vit_gemm_bf16_pp.hip)
+using Bf16Epilogues = EpilogueList<VITHIP_BF16_EPI_BF16, VITHIP_BF16_EPI_BF16_GELU, VITHIP_BF16_EPI_BF16_QGELU, VITHIP_BF16_EPI_F32_RESIDUAL>;
+// bf16: the ping-pong kernel without a fold, which is also the GEMM of vithip_patch_embed_bf16
+using Bf16PingPongEpilogues = EpilogueList<VITHIP_BF16_EPI_BF16, VITHIP_BF16_EPI_BF16_GELU, VITHIP_BF16_EPI_BF16_QGELU,
+                                           VITHIP_BF16_EPI_F32_RESIDUAL, VITHIP_BF16_EPI_F32_EMBED>;
+
+// p.tiles_m x p.tiles_n tiles of bm x bn over p.M x p.N, and the workgroups of the launch: one per tile, or, for a persistent walk,
+// at most `wgs` of them
+template <typename Params>
+int set_tile_grid(Params &p, int bm, int bn, int wgs = 0) {
+    p.tiles_m = (p.M + bm - 1) / bm;
+    p.tiles_n = (p.N + bn - 1) / bn;
+    const int total = p.tiles_m * p.tiles_n;
+    return wgs > 0 && wgs < total ? wgs : total;
+}
+
+// vit_gemm.hip: x[img][0][:] = cls + pos[0] for every image of x [n_images][tokens][dim] (the class row of every patch embedding)
+int launch_cls_rows(hipStream_t stream, const float *cls, const float *pos, float *x, int n_images, int tokens, int dim);
+
 struct GemmParams {
     const float *A;
     const float *W;

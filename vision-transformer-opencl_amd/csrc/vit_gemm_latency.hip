@@ -158,20 +158,11 @@ __global__ __launch_bounds__(256) void gemm_f32_nt_latency_kernel(const GemmPara
 
 // K % 128 == 0 (the caller falls back to the 64x64 tile otherwise); operands below 2 GiB as for every fp32 kernel.
 int launch_gemm_f32_latency(hipStream_t stream, GemmParams &p, int epilogue) {
-    p.tiles_m = (p.M + LBM - 1) / LBM;
-    p.tiles_n = (p.N + LBN - 1) / LBN;
-    const dim3 grid(p.tiles_m * p.tiles_n), block(256);
-    switch (epilogue) {
-        case VITHIP_EPI_BIAS: hipLaunchKernelGGL(gemm_f32_nt_latency_kernel<VITHIP_EPI_BIAS>, grid, block, 0, stream, p); break;
-        case VITHIP_EPI_BIAS_GELU: hipLaunchKernelGGL(gemm_f32_nt_latency_kernel<VITHIP_EPI_BIAS_GELU>, grid, block, 0, stream, p); break;
-        case VITHIP_EPI_BIAS_RESIDUAL: hipLaunchKernelGGL(gemm_f32_nt_latency_kernel<VITHIP_EPI_BIAS_RESIDUAL>, grid, block, 0, stream, p); break;
-        case EPI_BIAS_LN: hipLaunchKernelGGL(gemm_f32_nt_latency_kernel<EPI_BIAS_LN>, grid, block, 0, stream, p); break;
-        case EPI_BIAS_GELU_LN: hipLaunchKernelGGL(gemm_f32_nt_latency_kernel<EPI_BIAS_GELU_LN>, grid, block, 0, stream, p); break;
-        case VITHIP_EPI_BIAS_QGELU: hipLaunchKernelGGL(gemm_f32_nt_latency_kernel<VITHIP_EPI_BIAS_QGELU>, grid, block, 0, stream, p); break;
-        case EPI_BIAS_QGELU_LN: hipLaunchKernelGGL(gemm_f32_nt_latency_kernel<EPI_BIAS_QGELU_LN>, grid, block, 0, stream, p); break;
-        default: return static_cast<int>(hipErrorInvalidValue);
-    }
-    return static_cast<int>(hipGetLastError());
+    const dim3 grid(set_tile_grid(p, LBM, LBN)), block(256);
+    return with_epilogue(TileEpilogues{}, epilogue, [&](auto epi) {
+        hipLaunchKernelGGL(gemm_f32_nt_latency_kernel<decltype(epi)::value>, grid, block, 0, stream, p);
+        return static_cast<int>(hipGetLastError());
+    });
 }
 
 }  // namespace vitgemm

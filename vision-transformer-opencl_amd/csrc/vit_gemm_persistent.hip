@@ -33,6 +33,7 @@
 // same order: no code path stores a tile whose accumulators it did not wait for, nothing spins, nothing can time out, and
 // the hand-over needs no co-residency of the grid (lanes > 1, shared devices).  The two outcomes are counted in the
 // workspace (vithip_gemm_f32_workspace_stats): a recomputed piece costs x K-steps of one workgroup, never a wrong bit.
+#include "vit_device.hpp"
 #include "vit_gemm_common.hpp"
 
 // The image walk's step: SPLIT_STEP_PREFETCH = 1 reads the fragments of step g + 1 under the matrix instructions
@@ -657,11 +658,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
 }
 
 // 2 workgroups per CU of the CURRENT device (engines of several devices share the process: nothing is cached process-wide)
-static int persistent_wgs() {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    return 2 * cus;
-}
+static int persistent_wgs() { return 2 * vitdev::current_cus(); }
 
 // K-steps of a last-round tile that a helper workgroup runs (0: the hand-over does not pay) for the 128 x 128 persistent walk
 // on a grid of `wgs` workgroups (0: ask the current device) with `slots` parking slots
@@ -687,143 +684,58 @@ template <int BM, int BN, int WM, int WN, int ARITH = ARITH_F32, bool WIMG = fal
 int launch_persistent_tile(hipStream_t stream, GemmParams &p, int epilogue, int group_m) {
     const int wgs = persistent_wgs();
     if (wgs <= 0) return static_cast<int>(hipErrorInvalidDevice);
-    p.tiles_m = (p.M + BM - 1) / BM;
-    p.tiles_n = (p.N + BN - 1) / BN;
+    const dim3 grid(set_tile_grid(p, BM, BN, wgs)), block(256);
     p.group_m = group_m;
-    const int total = p.tiles_m * p.tiles_n;
-    const dim3 grid(total < wgs ? total : wgs), block(256);
     // helper pieces (see the head of this file): on when the caller lent a workspace, a partial last round exists and the
     // piece is long enough to be worth a 64 KB hand-over (>= 4 K-steps)
     p.sk_x = (p.sk_ws && BM == 128 && BN == 128) ? persistent_piece_steps(p.M, p.N, p.K, p.sk_slots, wgs, ARITH == ARITH_SPLIT3 ? SPLIT_BK : PBK) : 0;
-    if (p.sk_x > 0) {
-        switch (epilogue) {
-            case VITHIP_EPI_BIAS:
-                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS, false, true, 0, ARITH, WIMG>), grid, block, 0, stream, p);
-                break;
-            case VITHIP_EPI_BIAS_GELU:
-                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_GELU, false, true, 0, ARITH, WIMG>), grid, block, 0, stream, p);
-                break;
-            case VITHIP_EPI_BIAS_RESIDUAL:
-                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_RESIDUAL, false, true, 0, ARITH, WIMG>), grid, block, 0, stream, p);
-                break;
-            case EPI_BIAS_LN:
-                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_LN, false, true, 0, ARITH, WIMG>), grid, block, 0, stream, p);
-                break;
-            case EPI_BIAS_GELU_LN:
-                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_GELU_LN, false, true, 0, ARITH, WIMG>), grid, block, 0, stream, p);
-                break;
-            case VITHIP_EPI_BIAS_QGELU:
-                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_QGELU, false, true, 0, ARITH, WIMG>), grid, block, 0, stream, p);
-                break;
-            case EPI_BIAS_QGELU_LN:
-                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_QGELU_LN, false, true, 0, ARITH, WIMG>), grid, block, 0, stream, p);
-                break;
-            case EPI_RESIDUAL_STATS:
-                hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_RESIDUAL_STATS, false, true, 0, ARITH, WIMG>), grid, block, 0, stream, p);
-                break;
-            default:
-                return static_cast<int>(hipErrorInvalidValue);
-        }
-        return static_cast<int>(hipGetLastError());
-    }
-    switch (epilogue) {
-        case VITHIP_EPI_BIAS:
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS, false, false, 0, ARITH, WIMG>), grid, block, 0, stream, p);
-            break;
-        case VITHIP_EPI_BIAS_GELU:
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_GELU, false, false, 0, ARITH, WIMG>), grid, block, 0, stream, p);
-            break;
-        case VITHIP_EPI_BIAS_RESIDUAL:
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_RESIDUAL, false, false, 0, ARITH, WIMG>), grid, block, 0, stream, p);
-            break;
-        case EPI_BIAS_LN:
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_LN, false, false, 0, ARITH, WIMG>), grid, block, 0, stream, p);
-            break;
-        case EPI_BIAS_GELU_LN:
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_GELU_LN, false, false, 0, ARITH, WIMG>), grid, block, 0, stream, p);
-            break;
-        case VITHIP_EPI_BIAS_QGELU:
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, VITHIP_EPI_BIAS_QGELU, false, false, 0, ARITH, WIMG>), grid, block, 0, stream, p);
-            break;
-        case EPI_BIAS_QGELU_LN:
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_BIAS_QGELU_LN, false, false, 0, ARITH, WIMG>), grid, block, 0, stream, p);
-            break;
-        case EPI_RESIDUAL_STATS:
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, EPI_RESIDUAL_STATS, false, false, 0, ARITH, WIMG>), grid, block, 0, stream, p);
-            break;
-        default:
-            return static_cast<int>(hipErrorInvalidValue);
-    }
-    return static_cast<int>(hipGetLastError());
+    return with_epilogue(WalkEpilogues{}, epilogue, [&](auto epi) {
+        auto launch = [&](auto sk) {
+            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, decltype(epi)::value, false, decltype(sk)::value, 0, ARITH, WIMG>), grid, block, 0, stream, p);
+            return static_cast<int>(hipGetLastError());
+        };
+        return p.sk_x > 0 ? launch(std::true_type{}) : launch(std::false_type{});
+    });
 }
 
 #ifdef VIT_PROBES
+// The 128 x 128 walk of the probe instantiations below: no helper pieces
+template <int EPI, bool STAMP, int DBG = 0, int ARITH = ARITH_F32, bool WIMG = false>
+static int launch_walk_probe(hipStream_t stream, GemmParams &p, int group_m) {
+    const int wgs = persistent_wgs();
+    if (wgs <= 0) return static_cast<int>(hipErrorInvalidDevice);
+    const dim3 grid(set_tile_grid(p, 128, 128, wgs));
+    p.group_m = group_m;
+    p.sk_x = 0;
+    hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<128, 128, 64, 64, EPI, STAMP, false, DBG, ARITH, WIMG>), grid, dim3(256), 0, stream, p);
+    return static_cast<int>(hipGetLastError());
+}
+
 // Stamped probe build (tools/gemm_probe.py --stamp-tile 129): p.dbg receives 8 x u64 per workgroup.
 // arith = ARITH_SPLIT3 with a weight image (tools/gemm_f32_split_stamps.py): the image walk, word 4 of a record = the summed
 // fragment waits of its K steps
 int launch_persistent_stamped(hipStream_t stream, GemmParams &p, int epilogue, int group_m, int arith) {
-    const int wgs = persistent_wgs();
-    if (wgs <= 0) return static_cast<int>(hipErrorInvalidDevice);
-    p.tiles_m = (p.M + 127) / 128;
-    p.tiles_n = (p.N + 127) / 128;
-    p.group_m = group_m;
-    const int total = p.tiles_m * p.tiles_n;
-    const dim3 grid(total < wgs ? total : wgs), block(256);
     if (arith == ARITH_SPLIT3) {
         if (!p.w_split) return static_cast<int>(hipErrorInvalidValue);
-        p.sk_x = 0;
-        if (epilogue == EPI_BIAS_GELU_LN)
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<128, 128, 64, 64, EPI_BIAS_GELU_LN, true, false, 0, ARITH_SPLIT3, true>), grid, block, 0, stream, p);
-        else if (epilogue == EPI_BIAS_LN)
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<128, 128, 64, 64, EPI_BIAS_LN, true, false, 0, ARITH_SPLIT3, true>), grid, block, 0, stream, p);
-        else if (epilogue == VITHIP_EPI_BIAS_RESIDUAL)
-            hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<128, 128, 64, 64, VITHIP_EPI_BIAS_RESIDUAL, true, false, 0, ARITH_SPLIT3, true>), grid, block, 0, stream, p);
-        else
-            return static_cast<int>(hipErrorInvalidValue);
-        return static_cast<int>(hipGetLastError());
+        return with_epilogue<EPI_BIAS_GELU_LN, EPI_BIAS_LN, VITHIP_EPI_BIAS_RESIDUAL>(epilogue, [&](auto epi) {
+            return launch_walk_probe<decltype(epi)::value, true, 0, ARITH_SPLIT3, true>(stream, p, group_m);
+        });
     }
-    if (epilogue == VITHIP_EPI_BIAS_GELU)
-        hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<128, 128, 64, 64, VITHIP_EPI_BIAS_GELU, true>), grid, block, 0, stream, p);
-    else if (epilogue == EPI_BIAS_GELU_LN)  // the LayerNorm fold's consumer epilogues (tools/gemm_f32_fold_stamps.py)
-        hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<128, 128, 64, 64, EPI_BIAS_GELU_LN, true>), grid, block, 0, stream, p);
-    else if (epilogue == EPI_BIAS_LN)
-        hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<128, 128, 64, 64, EPI_BIAS_LN, true>), grid, block, 0, stream, p);
-    else
-        hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<128, 128, 64, 64, VITHIP_EPI_BIAS, true>), grid, block, 0, stream, p);
-    return static_cast<int>(hipGetLastError());
+    // GELU, the LayerNorm fold's consumer epilogues (tools/gemm_f32_fold_stamps.py); every other code is stamped as the plain bias
+    const bool listed = epilogue == VITHIP_EPI_BIAS_GELU || epilogue == EPI_BIAS_GELU_LN || epilogue == EPI_BIAS_LN;
+    return with_epilogue<VITHIP_EPI_BIAS, VITHIP_EPI_BIAS_GELU, EPI_BIAS_GELU_LN, EPI_BIAS_LN>(listed ? epilogue : VITHIP_EPI_BIAS, [&](auto epi) {
+        return launch_walk_probe<decltype(epi)::value, true>(stream, p, group_m);
+    });
 }
-
 
 // Switch-off builds (tools/gemm_f32_switchoff.py; tile codes 131-136 of the probe library): the persistent walk without helper
 // pieces and with one part of the kernel removed.  Timing only.
-template <int DBG>
-static int launch_switchoff_dbg(hipStream_t stream, const GemmParams &p, int epilogue, dim3 grid) {
-    switch (epilogue) {
-        case VITHIP_EPI_BIAS: hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<128, 128, 64, 64, VITHIP_EPI_BIAS, false, false, DBG>), grid, dim3(256), 0, stream, p); break;
-        case VITHIP_EPI_BIAS_GELU: hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<128, 128, 64, 64, VITHIP_EPI_BIAS_GELU, false, false, DBG>), grid, dim3(256), 0, stream, p); break;
-        case VITHIP_EPI_BIAS_RESIDUAL: hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<128, 128, 64, 64, VITHIP_EPI_BIAS_RESIDUAL, false, false, DBG>), grid, dim3(256), 0, stream, p); break;
-        default: return static_cast<int>(hipErrorInvalidValue);
-    }
-    return static_cast<int>(hipGetLastError());
-}
 int launch_persistent_switchoff(hipStream_t stream, GemmParams &p, int epilogue, int group_m, int dbg) {
-    const int wgs = persistent_wgs();
-    if (wgs <= 0) return static_cast<int>(hipErrorInvalidDevice);
-    p.tiles_m = (p.M + 127) / 128;
-    p.tiles_n = (p.N + 127) / 128;
-    p.group_m = group_m;
-    p.sk_x = 0;
-    const int total = p.tiles_m * p.tiles_n;
-    const dim3 grid(total < wgs ? total : wgs);
-    switch (dbg) {
-        case 1: return launch_switchoff_dbg<1>(stream, p, epilogue, grid);
-        case 2: return launch_switchoff_dbg<2>(stream, p, epilogue, grid);
-        case 3: return launch_switchoff_dbg<3>(stream, p, epilogue, grid);
-        case 4: return launch_switchoff_dbg<4>(stream, p, epilogue, grid);
-        case 5: return launch_switchoff_dbg<5>(stream, p, epilogue, grid);
-        case 6: return launch_switchoff_dbg<6>(stream, p, epilogue, grid);
-        default: return static_cast<int>(hipErrorInvalidValue);
-    }
+    return with_epilogue<1, 2, 3, 4, 5, 6>(dbg, [&](auto dbg_c) {
+        return with_epilogue<VITHIP_EPI_BIAS, VITHIP_EPI_BIAS_GELU, VITHIP_EPI_BIAS_RESIDUAL>(epilogue, [&](auto epi) {
+            return launch_walk_probe<decltype(epi)::value, false, decltype(dbg_c)::value>(stream, p, group_m);
+        });
+    });
 }
 #endif
 

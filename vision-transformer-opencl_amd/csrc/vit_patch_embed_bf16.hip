@@ -14,7 +14,7 @@
 //     incrementally), converts them to bf16 and writes 8-byte halves of the 16-byte chunks of a [128][32] bf16 LDS tile;
 //     W: 2 x 16 bytes of the bf16 conv weight.  64-byte rows, chunk position = chunk ^ ((row >> 2) & 3): conflict-free
 //     ds_read_b128 fragment reads;
-//   * epilogue: + bias + pos_emb, row m -> token row m + image + 1 (the class row is written by cls_rows_embed_kernel);
+//   * epilogue: + bias + pos_emb, row m -> token row m + image + 1 (the class row is written by launch_cls_rows);
 //   * tile id -> (tm, tn) with tn fastest and the XCD remap: the N tiles that re-read an M tile's pixels share an L2.
 // Measured at batch 2048 (tools/embed_time.py): 2.4 ms against 1.0 ms for the two passes.  With the stages switched off one
 // at a time: MFMA + LDS + barriers 0.49 ms, + W loads 0.53, + pixel loads 1.43, + epilogue 1.05, and three K steps of
@@ -212,13 +212,6 @@ __global__ __launch_bounds__(ETHREADS, 3) void patch_embed_bf16_kernel(const Emb
     }
 }
 
-__global__ void cls_rows_embed_kernel(const float *cls, const float *pos, float *x, int n_images, int tokens, int dim) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_images * dim) return;
-    const int im = i / dim, d = i - im * dim;
-    x[(size_t)im * tokens * dim + d] = cls[d] + pos[d];  // class_token + pos_emb row 0 (ViT_seq.c:72-101)
-}
-
 }  // namespace
 
 // images [n][C][S][S] fp32, conv_w16 [D][C*p*p] bf16 -> x [n][1 + G*G][D] fp32.  Returns a hipError_t value.
@@ -230,12 +223,10 @@ int launch_patch_embed_bf16(hipStream_t s, const float *images, const unsigned s
     q.images = images; q.W = conv_w16; q.bias = conv_b; q.pos = pos; q.x = x;
     q.M = n_images * P; q.N = embed_dim; q.K = K;
     q.P = P; q.G = G; q.p = patch_size; q.S = img_size; q.C = in_chans;
-    q.tiles_m = (q.M + EBM - 1) / EBM;
-    q.tiles_n = (q.N + EBN - 1) / EBN;
+    const dim3 grid(set_tile_grid(q, EBM, EBN));
     q.magic_P = (unsigned)((0x100000000ull + (unsigned)P - 1) / (unsigned)P);
-    const int total = n_images * embed_dim;
-    hipLaunchKernelGGL(cls_rows_embed_kernel, dim3((total + 255) / 256), dim3(256), 0, s, cls, pos, x, n_images, P + 1, embed_dim);
-    hipLaunchKernelGGL(patch_embed_bf16_kernel, dim3(q.tiles_m * q.tiles_n), dim3(ETHREADS), 0, s, q);
+    if (const int e = launch_cls_rows(s, cls, pos, x, n_images, P + 1, embed_dim)) return e;
+    hipLaunchKernelGGL(patch_embed_bf16_kernel, grid, dim3(ETHREADS), 0, s, q);
     return static_cast<int>(hipGetLastError());
 }
 

@@ -39,13 +39,6 @@ struct EmbedParams {
     int tiles_m, tiles_n;
 };
 
-__global__ void cls_rows_general_kernel(const float *cls, const float *pos, float *x, int n_images, int tokens, int dim) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n_images * dim) return;
-    const int im = idx / dim, d = idx - im * dim;
-    x[(size_t)im * tokens * dim + d] = cls[d] + pos[d];
-}
-
 __global__ __launch_bounds__(256, 2) void patch_embed_general_kernel(const EmbedParams p) {
     __shared__ __attribute__((aligned(16))) float lds[2 * (GBM + GBN) * GLD];
     float *const As0 = lds;
@@ -210,14 +203,10 @@ int vithip_patch_embed_f32_general(vithip_stream_t stream, const float *images, 
     p.images = images; p.conv_w = conv_w; p.conv_b = conv_b; p.pos = pos; p.x = x;
     p.M = n_images * G * G; p.N = embed_dim; p.K = in_chans * patch_size * patch_size;
     p.patches = G * G; p.grid = G; p.patch = patch_size; p.img = img_size; p.chans = in_chans;
-    p.tiles_m = (p.M + GBM - 1) / GBM;
-    p.tiles_n = (p.N + GBN - 1) / GBN;
+    const dim3 grid(set_tile_grid(p, GBM, GBN));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int total = n_images * embed_dim;
-    hipLaunchKernelGGL(cls_rows_general_kernel, dim3((total + 255) / 256), dim3(256), 0, s, cls, pos, x, n_images, G * G + 1, embed_dim);
-    const int e = static_cast<int>(hipGetLastError());
-    if (e) return e;
-    hipLaunchKernelGGL(patch_embed_general_kernel, dim3(p.tiles_m * p.tiles_n), dim3(256), 0, s, p);
+    if (const int e = launch_cls_rows(s, cls, pos, x, n_images, G * G + 1, embed_dim)) return e;
+    hipLaunchKernelGGL(patch_embed_general_kernel, grid, dim3(256), 0, s, p);
     return static_cast<int>(hipGetLastError());
 }
 
