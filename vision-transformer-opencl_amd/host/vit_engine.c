@@ -58,27 +58,28 @@ _Static_assert(sizeof(vit_image_u8) == sizeof(vithip_image_u8) && offsetof(vit_i
 
 /* What a forward writes, besides where: probabilities [n][classes] and the optional top-1 records, the embedding rows `spec`
  * asks for (stage_features), the class token's attention over the tokens in the last layer (stage_cls_attention), or the residual
- * stream behind the layers `tap` names (stage_tap), [n][out_row_elems()] -- or, behind the head, the k best classes as records in
+ * stream behind the layers `tap` names (stage_tap), [n][row] floats -- or, behind the head, the k best classes as records in
  * place of the probabilities (stage_head; 32-bit words, as many bytes as a float each) -- or the rows of a dense call
- * (stage_dense_out: [n][out_row_bytes()] BYTES, labels or the fp32 grid; the one kind whose row is not counted in floats).
- * Zero-filled before use: the graph cache compares it bytewise.  The pointers are those of the call's (or chunk's) first image. */
-enum { VIT_OUT_PROBS = 0, VIT_OUT_FEATURES = 1, VIT_OUT_ATTENTION = 2, VIT_OUT_INTERMEDIATE = 3, VIT_OUT_TOPK = 4, VIT_OUT_DENSE = 5 };
+ * (stage_dense_out: labels, a byte each, or the fp32 grid).  What the engine knows of each kind, the bytes of its row among it, is
+ * the kind's row of OUT_KINDS.  Zero-filled before use (output_fault): the graph cache compares it bytewise.  The pointers are those
+ * of the call's (or chunk's) first image. */
+enum { VIT_OUT_PROBS = 0, VIT_OUT_FEATURES = 1, VIT_OUT_ATTENTION = 2, VIT_OUT_INTERMEDIATE = 3, VIT_OUT_TOPK = 4, VIT_OUT_DENSE = 5, VIT_OUT_KINDS };
 typedef struct {
-    int kind;              /* VIT_OUT_PROBS: dst = probabilities, label / prob = top-1 (may be NULL); _FEATURES: dst = the rows of spec;
-                            * _ATTENTION: dst = the rows of attn_kind; _INTERMEDIATE: dst = the rows of tap; _TOPK: dst = the records of
-                            * topk, [n][2k] 32-bit words */
-    vit_feature_spec spec;
-    int attn_kind;         /* VIT_ATTN_* (0 otherwise) */
-    vit_topk_spec topk;    /* _TOPK: the checked spec (all zero otherwise) */
+    int kind;              /* VIT_OUT_*: which member of the union is in use (_PROBS: none), and what dst holds */
     int zero;              /* always 0: with it the struct has no padding, which a bytewise comparison would read */
-    vit_intermediate_spec tap; /* _INTERMEDIATE: the checked spec, layers[num_layers..] zero (all zero otherwise) */
-    vit_dense_spec dense;  /* _DENSE: the checked spec with out_h / out_w resolved (all zero otherwise); the head is engine state */
+    union {                /* the kind's checked spec; the bytes behind it stay zero */
+        vit_feature_spec spec;     /* _FEATURES */
+        int attn_kind;             /* _ATTENTION: VIT_ATTN_* */
+        vit_intermediate_spec tap; /* _INTERMEDIATE: layers[num_layers..] zero */
+        vit_topk_spec topk;        /* _TOPK: dst = the records, [n][2k] 32-bit words */
+        vit_dense_spec dense;      /* _DENSE: out_h / out_w resolved; the head is engine state */
+    };
     float *dst;
-    int *label;
+    int *label;            /* _PROBS: top-1 (may be NULL) */
     float *prob;
 } vit_output;
-_Static_assert(sizeof(vit_output) == 5 * sizeof(int) + sizeof(vit_topk_spec) + sizeof(vit_intermediate_spec) + sizeof(vit_dense_spec) + 3 * sizeof(void *) &&
-                   sizeof(vit_dense_spec) == 4 * sizeof(int) && sizeof(vit_topk_spec) == 3 * sizeof(int) && sizeof(vit_intermediate_spec) == (4 + VIT_MAX_TAPS) * sizeof(int) && sizeof(vit_intermediate_spec) % sizeof(void *) == 0,
+_Static_assert(sizeof(vit_output) == 2 * sizeof(int) + sizeof(vit_intermediate_spec) + 3 * sizeof(void *) &&
+                   sizeof(vit_intermediate_spec) == (4 + VIT_MAX_TAPS) * sizeof(int) && sizeof(vit_intermediate_spec) % sizeof(void *) == 0,
                "vit_output must stay free of padding: the graph cache compares it bytewise");
 _Static_assert(VIT_SCORE_PROB == VITHIP_SCORE_PROB && VIT_SCORE_LOGIT == VITHIP_SCORE_LOGIT && VIT_MAX_TOPK == VITHIP_MAX_TOPK,
                "one numbering of the scores, one bound on k");
@@ -975,6 +976,7 @@ typedef struct {
     size_t esz;                  /* bytes of an element of the lanes' y, qkv and h: 4, or 2 on bf16 engines */
     int pruned;                  /* the last layer computes the class rows only: prune_last_layer, where the chunk's output reads no others (class_rows_only) */
     int qkv_only;                /* the last layer stops behind its QKV GEMM: the chunk's output is read from its Q and K (attention calls) */
+    size_t row;                  /* bytes per image of the chunk's output rows (the kind's row_bytes) */
 } chunk_ctx;
 
 #define RUN(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
@@ -1200,7 +1202,6 @@ static int tap_block(chunk_ctx *c, const vit_lane *ln, float *dst, size_t ld, in
 static int runs_head(const vit_output *out) {
     return out->kind == VIT_OUT_PROBS || out->kind == VIT_OUT_TOPK || (out->kind == VIT_OUT_FEATURES && out->spec.kind == VIT_FEAT_HEAD);
 }
-static size_t out_row_elems(const vit_engine *e, const vit_output *out);
 static int stage_head(chunk_ctx *c, const vit_output *out) {
     vit_engine *e = c->e;
     const vit_head *h = &e->head;
@@ -1225,7 +1226,7 @@ static int stage_head(chunk_ctx *c, const vit_output *out) {
         const size_t o = (size_t)ln->off;
         if (out->kind == VIT_OUT_FEATURES) { /* VIT_FEAT_HEAD: the rows of e->logits as they are (vit_engine_read_logits keeps the
                                               * un-normalised ones), then F.normalize on the caller's copy */
-            float *dst = out->dst + o * out_row_elems(e, out);
+            float *dst = out->dst + o * (c->row / sizeof(float));
             HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_HEAD));
             HIP_TRY(e, vithip_gather_rows_f32(ln->s, e->logits + o * NC, (size_t)NC, dst, (size_t)NC, ln->n, NC));
             if (out->spec.l2_normalize) HIP_TRY(e, vithip_l2_normalize_rows_f32(ln->s, dst, (size_t)NC, ln->n, NC));
@@ -1243,35 +1244,6 @@ static int stage_head(chunk_ctx *c, const vit_output *out) {
     return VIT_OK;
 }
 
-/* The row width's one home: floats per image of an output kind; `kind` is the VIT_FEAT_* or VIT_ATTN_* of a valid spec, or the k of a
- * top-k one (its 2k words are 32 bits each, like a float) */
-static size_t row_elems(const vit_engine *e, int out_kind, int kind) {
-    if (out_kind == VIT_OUT_PROBS) return (size_t)e->cfg.num_classes;
-    if (out_kind == VIT_OUT_TOPK) return 2 * (size_t)kind;
-    if (out_kind == VIT_OUT_ATTENTION) return (kind == VIT_ATTN_HEADS ? (size_t)e->cfg.num_heads : 1) * (size_t)e->tokens;
-    if (kind == VIT_FEAT_HEAD) return (size_t)e->cfg.num_classes;
-    return (kind == VIT_FEAT_TOKENS ? (size_t)e->tokens : 1) * (size_t)e->cfg.embed_dim;
-}
-/* ... and of one tapped layer's block of an intermediate row; `kind` is the VIT_TAP_* of a valid spec */
-static size_t tap_block_elems(const vit_engine *e, int kind) {
-    const size_t T = (size_t)e->tokens;
-    return (kind == VIT_TAP_CLS ? 1 : kind == VIT_TAP_TOKENS ? T : T - 1) * (size_t)e->cfg.embed_dim;
-}
-/* a dense row in BYTES: labels are a byte per pixel, the grid classes * P floats (`spec` checked, out_h / out_w resolved) */
-static size_t dense_row_bytes(const vit_engine *e, const vit_dense_spec *spec) {
-    if (spec->kind == VIT_DENSE_LABELS) return (size_t)spec->out_h * (size_t)spec->out_w;
-    return (size_t)e->dense.spec.num_classes * (size_t)(e->tokens - 1) * sizeof(float);
-}
-/* floats per row of every kind but VIT_OUT_DENSE, whose rows the routing below measures in bytes (out_row_bytes) */
-static size_t out_row_elems(const vit_engine *e, const vit_output *out) {
-    if (out->kind == VIT_OUT_INTERMEDIATE) return (size_t)out->tap.num_layers * tap_block_elems(e, out->tap.kind);
-    return row_elems(e, out->kind, out->kind == VIT_OUT_ATTENTION ? out->attn_kind : out->kind == VIT_OUT_TOPK ? out->topk.k : out->spec.kind);
-}
-
-static size_t out_row_bytes(const vit_engine *e, const vit_output *out) {
-    return out->kind == VIT_OUT_DENSE ? dense_row_bytes(e, &out->dense) : out_row_elems(e, out) * sizeof(float);
-}
-
 /* The embedding rows of the chunk instead of the head: the class block (the checkpoint's own head's operand, in the caller's rows),
  * the final LayerNorm of every row, or the pooled block. */
 static int stage_features(chunk_ctx *c, const vit_output *out) {
@@ -1279,7 +1251,7 @@ static int stage_features(chunk_ctx *c, const vit_output *out) {
     const size_t D = (size_t)c->D;
     for (int j = 0; j < c->L; ++j) {
         const vit_lane *ln = &c->lane[j];
-        float *dst = out->dst + (size_t)ln->off * out_row_elems(e, out);
+        float *dst = out->dst + (size_t)ln->off * (c->row / sizeof(float));
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
         if (out->spec.kind == VIT_FEAT_CLS) {
             RUN(class_block(c, ln, dst, D));
@@ -1299,7 +1271,7 @@ static int stage_features(chunk_ctx *c, const vit_output *out) {
 static int stage_cls_attention(chunk_ctx *c, const vit_output *out) {
     vit_engine *e = c->e;
     const int heads = e->cfg.num_heads, hd = c->D / heads, mean = out->attn_kind == VIT_ATTN_HEAD_MEAN;
-    const size_t row = out_row_elems(e, out), ld = 3 * (size_t)c->D;
+    const size_t row = c->row / sizeof(float), ld = 3 * (size_t)c->D;
     for (int j = 0; j < c->L; ++j) {
         const vit_lane *ln = &c->lane[j];
         float *dst = out->dst + (size_t)ln->off * row;
@@ -1313,11 +1285,21 @@ static int stage_cls_attention(chunk_ctx *c, const vit_output *out) {
     return VIT_OK;
 }
 
-/* Block j of an intermediate call's rows: the residual stream as encoder_layer(layers[j]) has just left it, one tap block per lane.
- * A pruned last layer (CLS only) has updated the class rows of x alone, which is all that CLS reads. */
-static int stage_tap(chunk_ctx *c, const vit_output *out, int j) {
+/* floats of one tapped layer's block of an intermediate row; `kind` is the VIT_TAP_* of a valid spec */
+static size_t tap_block_elems(const vit_engine *e, int kind) {
+    const size_t T = (size_t)e->tokens;
+    return (kind == VIT_TAP_CLS ? 1 : kind == VIT_TAP_TOKENS ? T : T - 1) * (size_t)e->cfg.embed_dim;
+}
+
+/* An intermediate call behind encoder layer l = layers[j] (any other layer: nothing) -- block j of its rows: the residual stream as
+ * the layer has just left it, one tap block per lane.  A pruned last layer (CLS only) has updated the class rows of x alone, which
+ * is all that CLS reads. */
+static int stage_tap(chunk_ctx *c, const vit_output *out, int l) {
     vit_engine *e = c->e;
-    const size_t row = out_row_elems(e, out), block = tap_block_elems(e, out->tap.kind);
+    const size_t row = c->row / sizeof(float), block = tap_block_elems(e, out->tap.kind);
+    int j = 0;
+    while (j < out->tap.num_layers && out->tap.layers[j] != l) ++j;
+    if (j == out->tap.num_layers) return VIT_OK;
     for (int k = 0; k < c->L; ++k) {
         const vit_lane *ln = &c->lane[k];
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
@@ -1327,14 +1309,19 @@ static int stage_tap(chunk_ctx *c, const vit_output *out, int j) {
     return VIT_OK;
 }
 
-/* A dense call behind encoder layer layers[j]: per lane the patch rows of x as the layer has just left them (the tap of an
- * intermediate call of VIT_TAP_PATCHES) into the head's scratch, then the GEMM of the chain over them -- the first writes
- * bias + A_0 . W_0^T, the later ones add A_j . W_j^T in place, W_j the column block j of the head's W.  fp32 MFMA on both dtypes. */
-static int stage_dense_tap(chunk_ctx *c, int j) {
+/* A dense call behind encoder layer l = the head's layers[j] (any other layer: nothing): per lane the patch rows of x as the layer
+ * has just left them (the tap of an intermediate call of VIT_TAP_PATCHES) into the head's scratch, then the GEMM of the chain over
+ * them -- the first writes bias + A_0 . W_0^T, the later ones add A_j . W_j^T in place, W_j the column block j of the head's W.
+ * fp32 MFMA on both dtypes.  The spec of the call (out) has no say in it: the layers are the head's. */
+static int stage_dense_tap(chunk_ctx *c, const vit_output *out, int l) {
     vit_engine *e = c->e;
     const vit_dense_head *h = &e->dense;
     const size_t P = (size_t)c->T - 1, D = (size_t)c->D;
     const int NC = h->spec.num_classes, K = h->spec.num_layers;
+    int j = 0;
+    (void)out;
+    while (j < K && h->spec.layers[j] != l) ++j;
+    if (j == K) return VIT_OK;
     for (int k = 0; k < c->L; ++k) {
         const vit_lane *ln = &c->lane[k];
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
@@ -1358,7 +1345,7 @@ static int stage_dense_out(chunk_ctx *c, const vit_output *out) {
     vit_engine *e = c->e;
     const vit_dense_head *h = &e->dense;
     const int g = e->cfg.img_size / e->cfg.patch_size, NC = h->spec.num_classes;
-    const size_t P = (size_t)c->T - 1, row = out_row_bytes(e, out);
+    const size_t P = (size_t)c->T - 1, row = c->row;
     for (int k = 0; k < c->L; ++k) {
         const vit_lane *ln = &c->lane[k];
         const float *logits = h->logits + (size_t)ln->off * P * NC;
@@ -1375,13 +1362,14 @@ static int stage_dense_out(chunk_ctx *c, const vit_output *out) {
 
 /* The head's operand row of an image is [class blocks, in the order of cls_layers | pooled block], head.in floats.  Behind encoder
  * layer l < depth - 1 when cls_layers names it: the class block of that layer, the launch (and so the bits) of an intermediate call
- * with VIT_TAP_CLS, norm = 1.  The blocks of the last layer are stage_head's; the checkpoint's own head names no other layer. */
-static int stage_head_tap(chunk_ctx *c, int l) {
+ * with VIT_TAP_CLS, norm = 1.  The blocks of the last layer are stage_head's; the checkpoint's own head names no other layer.
+ * Nothing for a features call of plain embedding rows, which runs no head. */
+static int stage_head_tap(chunk_ctx *c, const vit_output *out, int l) {
     vit_engine *e = c->e;
     const vit_head *h = &e->head;
     int k = 0;
     while (k < h->spec.num_cls_layers && h->spec.cls_layers[k] != l) ++k;
-    if (k == h->spec.num_cls_layers || l == e->cfg.depth - 1) return VIT_OK;
+    if (!runs_head(out) || k == h->spec.num_cls_layers || l == e->cfg.depth - 1) return VIT_OK;
     for (int j = 0; j < c->L; ++j) {
         const vit_lane *ln = &c->lane[j];
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
@@ -1391,14 +1379,212 @@ static int stage_head_tap(chunk_ctx *c, int l) {
     return VIT_OK;
 }
 
-/* What each output kind reads of x behind the last layer: 1 where that is the class rows alone, which are all a pruned last layer
- * updates.  A kind that is not named here runs the layer in full: a new output cannot silently return rows of the layer before. */
-static int class_rows_only(const vit_engine *e, const vit_output *out) {
+/* What the engine knows of an output kind, all of it: OUT_KINDS below has one row per VIT_OUT_*, and a new kind is a row and its
+ * own functions.  A hook that is absent (NULL) gives the plain answer named with it. */
+typedef struct {
+    /* The caller's spec, checked against the model and copied into *out (zeroed, its kind set: output_fault): NULL, or what is wrong
+     * with it as a format for (who, arg[0], arg[1]) -- the calls and the public row widths ask the same question.  Absent: no spec. */
+    const char *(*check)(const vit_engine *e, const void *spec, vit_output *out, int arg[2]);
+    size_t (*row_bytes)(const vit_engine *e, const vit_output *out); /* bytes per image of the caller's rows */
+    /* Whether the kind reads, of x behind the last layer, the class rows alone, which are all a pruned last layer updates.  Absent:
+     * no -- the layer runs in full, so a new output cannot silently return rows of the layer before. */
+    int (*class_rows_only)(const vit_engine *e, const vit_output *out);
+    int (*last_layer)(const vit_engine *e, const vit_output *out); /* the deepest encoder layer that runs; absent: depth - 1 */
+    int (*after_layer)(chunk_ctx *c, const vit_output *out, int l); /* what runs behind encoder layer l; absent: nothing */
+    int (*finish)(chunk_ctx *c, const vit_output *out);             /* the stage behind the walk; absent: nothing */
+    int qkv_only; /* the last layer stops behind its QKV GEMM (chunk_ctx.qkv_only) */
+} vit_out_kind;
+
+/* The forwards, the top-k calls and the features calls share their hooks: a features call of VIT_FEAT_HEAD runs the head as they do
+ * (runs_head), one of plain embedding rows stage_features in its place. */
+static int head_or_class_rows_only(const vit_engine *e, const vit_output *out) {
     if (runs_head(out)) return e->head.spec.pool == VIT_HEAD_POOL_NONE; /* a pooled block reads every patch row */
-    if (out->kind == VIT_OUT_FEATURES) return out->spec.kind == VIT_FEAT_CLS; /* MEAN and TOKENS read every row */
-    if (out->kind == VIT_OUT_INTERMEDIATE) return out->tap.kind == VIT_TAP_CLS;
-    if (out->kind == VIT_OUT_DENSE) return 0; /* the patch rows of every tapped layer */
-    return out->kind == VIT_OUT_ATTENTION; /* Q of the class rows, K of every token (qkv_only) */
+    return out->spec.kind == VIT_FEAT_CLS; /* MEAN and TOKENS read every row */
+}
+static int stage_head_or_features(chunk_ctx *c, const vit_output *out) {
+    return runs_head(out) ? stage_head(c, out) : stage_features(c, out);
+}
+
+static size_t probs_row_bytes(const vit_engine *e, const vit_output *out) {
+    (void)out;
+    return (size_t)e->cfg.num_classes * sizeof(float);
+}
+
+static const char *features_check(const vit_engine *e, const void *caller, vit_output *out, int arg[2]) {
+    const vit_feature_spec *spec = (const vit_feature_spec *)caller;
+    if (!spec) return "%s: the feature spec is required";
+    arg[0] = spec->kind;
+    if (spec->kind != VIT_FEAT_CLS && spec->kind != VIT_FEAT_MEAN && spec->kind != VIT_FEAT_TOKENS && spec->kind != VIT_FEAT_HEAD) return "%s: unknown feature kind %d";
+    arg[0] = spec->l2_normalize;
+    if (spec->l2_normalize != 0 && spec->l2_normalize != 1) return "%s: l2_normalize must be 0 or 1 (got %d)";
+    if (spec->l2_normalize && spec->kind == VIT_FEAT_TOKENS) return "%s: l2_normalize applies to the CLS, MEAN and HEAD rows, not to TOKENS";
+    if (spec->kind == VIT_FEAT_MEAN && e->tokens < 2) return "%s: MEAN needs at least one patch token";
+    out->spec.kind = spec->kind; out->spec.l2_normalize = spec->l2_normalize;
+    return NULL;
+}
+static size_t features_row_bytes(const vit_engine *e, const vit_output *out) {
+    if (out->spec.kind == VIT_FEAT_HEAD) return probs_row_bytes(e, out);
+    return (out->spec.kind == VIT_FEAT_TOKENS ? (size_t)e->tokens : 1) * (size_t)e->cfg.embed_dim * sizeof(float);
+}
+
+static const char *attention_check(const vit_engine *e, const void *caller, vit_output *out, int arg[2]) {
+    const vit_attention_spec *spec = (const vit_attention_spec *)caller;
+    (void)e;
+    if (!spec) return "%s: the attention spec is required";
+    arg[0] = spec->kind;
+    if (spec->kind != VIT_ATTN_HEADS && spec->kind != VIT_ATTN_HEAD_MEAN) return "%s: unknown attention kind %d";
+    arg[0] = spec->reserved;
+    if (spec->reserved != 0) return "%s: vit_attention_spec.reserved must be 0 (got %d)";
+    out->attn_kind = spec->kind;
+    return NULL;
+}
+static size_t attention_row_bytes(const vit_engine *e, const vit_output *out) {
+    return (out->attn_kind == VIT_ATTN_HEADS ? (size_t)e->cfg.num_heads : 1) * (size_t)e->tokens * sizeof(float);
+}
+static int attention_rows_only(const vit_engine *e, const vit_output *out) { /* Q of the class rows, K of every token (qkv_only) */
+    (void)e; (void)out;
+    return 1;
+}
+
+static const char *intermediate_check(const vit_engine *e, const void *caller, vit_output *out, int arg[2]) {
+    const vit_intermediate_spec *spec = (const vit_intermediate_spec *)caller;
+    if (!spec) return "%s: the intermediate spec is required";
+    arg[0] = spec->kind;
+    if (spec->kind != VIT_TAP_CLS && spec->kind != VIT_TAP_TOKENS && spec->kind != VIT_TAP_PATCHES && spec->kind != VIT_TAP_MAP)
+        return "%s: unknown intermediate kind %d";
+    arg[0] = spec->norm;
+    if (spec->norm != 0 && spec->norm != 1) return "%s: norm must be 0 or 1 (got %d)";
+    arg[0] = spec->num_layers; arg[1] = VIT_MAX_TAPS;
+    if (spec->num_layers < 1 || spec->num_layers > VIT_MAX_TAPS) return "%s: num_layers = %d must be 1..%d";
+    arg[0] = spec->reserved;
+    if (spec->reserved != 0) return "%s: vit_intermediate_spec.reserved must be 0 (got %d)";
+    for (int j = 0; j < spec->num_layers; ++j) {
+        arg[0] = j; arg[1] = spec->layers[j];
+        if (spec->layers[j] < 0 || spec->layers[j] >= e->cfg.depth) return "%s: layers[%d] = %d is not a layer of the model";
+        if (j && spec->layers[j] <= spec->layers[j - 1]) return "%s: layers[%d] = %d is not above the entry before it (strictly increasing)";
+    }
+    const int g = e->cfg.img_size / e->cfg.patch_size;
+    arg[0] = g; arg[1] = e->tokens - 1;
+    if (spec->kind == VIT_TAP_MAP && (g < 1 || g * g != e->tokens - 1)) return "%s: MAP needs a square grid of patches: (img_size / patch_size = %d)^2 is not the model's %d";
+    if (spec->kind == VIT_TAP_PATCHES && e->tokens < 2) return "%s: PATCHES needs at least one patch token";
+    out->tap.kind = spec->kind; out->tap.norm = spec->norm; out->tap.num_layers = spec->num_layers;
+    for (int j = 0; j < spec->num_layers; ++j) out->tap.layers[j] = spec->layers[j]; /* the unused entries stay zero: the graph key compares the whole spec */
+    return NULL;
+}
+static size_t intermediate_row_bytes(const vit_engine *e, const vit_output *out) {
+    return (size_t)out->tap.num_layers * tap_block_elems(e, out->tap.kind) * sizeof(float);
+}
+static int intermediate_rows_only(const vit_engine *e, const vit_output *out) {
+    (void)e;
+    return out->tap.kind == VIT_TAP_CLS;
+}
+static int intermediate_last_layer(const vit_engine *e, const vit_output *out) { /* the deepest tap; nothing else */
+    (void)e;
+    return out->tap.layers[out->tap.num_layers - 1];
+}
+
+static const char *topk_check(const vit_engine *e, const void *caller, vit_output *out, int arg[2]) {
+    const vit_topk_spec *spec = (const vit_topk_spec *)caller;
+    if (!spec) return "%s: the top-k spec is required";
+    arg[0] = spec->k; arg[1] = e->cfg.num_classes < VIT_MAX_TOPK ? e->cfg.num_classes : VIT_MAX_TOPK;
+    if (spec->k < 1 || spec->k > arg[1]) return "%s: k = %d must be 1..%d (the smaller of VIT_MAX_TOPK and num_classes)";
+    arg[0] = spec->score;
+    if (spec->score != VIT_SCORE_PROB && spec->score != VIT_SCORE_LOGIT) return "%s: unknown score %d";
+    arg[0] = spec->reserved;
+    if (spec->reserved != 0) return "%s: vit_topk_spec.reserved must be 0 (got %d)";
+    out->topk.k = spec->k; out->topk.score = spec->score;
+    return NULL;
+}
+static size_t topk_row_bytes(const vit_engine *e, const vit_output *out) { /* 2k 32-bit words */
+    (void)e;
+    return 2 * (size_t)out->topk.k * sizeof(int);
+}
+
+/* The one fault that is the engine's state, not the caller's argument: make_output knows it by its address. */
+static const char NO_DENSE_HEAD[] = "%s before vit_engine_set_dense_head()";
+/* The dense spec is resolved against the model too (out_h / out_w: 0 becomes img_size).  The head itself was checked when it was set. */
+static const char *dense_check(const vit_engine *e, const void *caller, vit_output *out, int arg[2]) {
+    const vit_dense_spec *spec = (const vit_dense_spec *)caller;
+    vit_dense_spec *res = &out->dense;
+    if (!spec) return "%s: the dense spec is required";
+    if (!e->dense.spec.num_layers) return NO_DENSE_HEAD;
+    arg[0] = spec->kind;
+    if (spec->kind != VIT_DENSE_LABELS && spec->kind != VIT_DENSE_GRID) return "%s: unknown dense kind %d";
+    arg[0] = spec->reserved;
+    if (spec->reserved != 0) return "%s: vit_dense_spec.reserved must be 0 (got %d)";
+    res->kind = spec->kind;
+    arg[0] = spec->out_h; arg[1] = spec->out_w;
+    if (spec->kind == VIT_DENSE_GRID) return spec->out_h || spec->out_w ? "%s: GRID takes no output size (out_h = %d, out_w = %d must be 0)" : NULL;
+    res->out_h = spec->out_h ? spec->out_h : e->cfg.img_size;
+    res->out_w = spec->out_w ? spec->out_w : e->cfg.img_size;
+    if (res->out_h < 1 || res->out_h > 4096 || res->out_w < 1 || res->out_w > 4096)
+        return "%s: out_h = %d and out_w = %d must be 1..4096 each (0 = img_size, which must then be in that range)";
+    return NULL;
+}
+/* labels are a byte per pixel, the grid classes * P floats: the one kind whose row is not a whole number of floats */
+static size_t dense_row_bytes(const vit_engine *e, const vit_output *out) {
+    if (out->dense.kind == VIT_DENSE_LABELS) return (size_t)out->dense.out_h * (size_t)out->dense.out_w;
+    return (size_t)e->dense.spec.num_classes * (size_t)(e->tokens - 1) * sizeof(float);
+}
+static int dense_last_layer(const vit_engine *e, const vit_output *out) { /* the deepest layer of the head */
+    (void)out;
+    return e->dense.spec.layers[e->dense.spec.num_layers - 1];
+}
+
+static const vit_out_kind OUT_KINDS[VIT_OUT_KINDS] = {
+    [VIT_OUT_PROBS] = {.row_bytes = probs_row_bytes, .class_rows_only = head_or_class_rows_only, .after_layer = stage_head_tap,
+                       .finish = stage_head_or_features},
+    [VIT_OUT_FEATURES] = {.check = features_check, .row_bytes = features_row_bytes, .class_rows_only = head_or_class_rows_only,
+                          .after_layer = stage_head_tap, .finish = stage_head_or_features},
+    [VIT_OUT_ATTENTION] = {.check = attention_check, .row_bytes = attention_row_bytes, .class_rows_only = attention_rows_only,
+                           .finish = stage_cls_attention, .qkv_only = 1},
+    [VIT_OUT_INTERMEDIATE] = {.check = intermediate_check, .row_bytes = intermediate_row_bytes, .class_rows_only = intermediate_rows_only,
+                              .last_layer = intermediate_last_layer, .after_layer = stage_tap},
+    [VIT_OUT_TOPK] = {.check = topk_check, .row_bytes = topk_row_bytes, .class_rows_only = head_or_class_rows_only,
+                      .after_layer = stage_head_tap, .finish = stage_head_or_features},
+    /* no class_rows_only: the patch rows of every tapped layer */
+    [VIT_OUT_DENSE] = {.check = dense_check, .row_bytes = dense_row_bytes, .last_layer = dense_last_layer, .after_layer = stage_dense_tap,
+                       .finish = stage_dense_out},
+};
+
+/* The output of a call: *out zeroed in full (the graph key compares it bytewise), then what the kind's check makes of the caller's
+ * spec.  NULL, or the fault as a format for (who, arg[0], arg[1]). */
+static const char *output_fault(const vit_engine *e, int kind, const void *spec, vit_output *out, int arg[2]) {
+    memset(out, 0, sizeof(*out));
+    out->kind = kind;
+    arg[0] = arg[1] = 0;
+    return OUT_KINDS[kind].check ? OUT_KINDS[kind].check(e, spec, out, arg) : NULL;
+}
+static int make_output(vit_engine *e, const char *who, int kind, const void *spec, float *dst, int *label, float *prob, vit_output *out) {
+    int arg[2];
+    const char *fault = output_fault(e, kind, spec, out, arg);
+    if (fault) return fail(e, fault == NO_DENSE_HEAD ? VIT_ERR_STATE : VIT_ERR_ARG, fault, who, arg[0], arg[1]);
+    out->dst = dst; out->label = label; out->prob = prob;
+    return VIT_OK;
+}
+static size_t out_row_bytes(const vit_engine *e, const vit_output *out) { return OUT_KINDS[out->kind].row_bytes(e, out); }
+
+/* The public row widths: the kind's check, then its measure -- 0 for no engine and for a spec the calls would refuse (a dense spec
+ * with no dense head set among them). */
+static size_t spec_row_bytes(const vit_engine *e, int kind, const void *spec) {
+    vit_output out;
+    int arg[2];
+    return e && !output_fault(e, kind, spec, &out, arg) ? out_row_bytes(e, &out) : 0;
+}
+size_t vit_engine_feature_row_elems(const vit_engine *e, const vit_feature_spec *spec) {
+    return spec_row_bytes(e, VIT_OUT_FEATURES, spec) / sizeof(float);
+}
+size_t vit_engine_attention_row_elems(const vit_engine *e, const vit_attention_spec *spec) {
+    return spec_row_bytes(e, VIT_OUT_ATTENTION, spec) / sizeof(float);
+}
+size_t vit_engine_intermediate_row_elems(const vit_engine *e, const vit_intermediate_spec *spec) {
+    return spec_row_bytes(e, VIT_OUT_INTERMEDIATE, spec) / sizeof(float);
+}
+size_t vit_engine_topk_row_elems(const vit_engine *e, const vit_topk_spec *spec) {
+    return spec_row_bytes(e, VIT_OUT_TOPK, spec) / sizeof(float);
+}
+size_t vit_engine_dense_row_bytes(const vit_engine *e, const vit_dense_spec *spec) {
+    return spec_row_bytes(e, VIT_OUT_DENSE, spec);
 }
 
 /* The chunk's context for nb images written as `out` says: dimensions, whether the last layer is pruned, and the lanes -- their
@@ -1409,8 +1595,10 @@ static void chunk_setup(vit_engine *e, vithip_stream_t s, int nb, const vit_outp
     c->T = e->tokens; c->D = cfg->embed_dim; c->H = VIT_HIDDEN_DIM(cfg); c->H1 = VIT_FC1_ROWS(cfg); c->NC = cfg->num_classes;
     c->L = e->opt.lanes > VIT_MAX_LANES ? VIT_MAX_LANES : e->opt.lanes;
     if (c->L < 1 || nb < 2 * c->L) c->L = 1;
-    c->pruned = e->opt.prune_last_layer && c->T <= 224 && class_rows_only(e, out);
-    c->qkv_only = out->kind == VIT_OUT_ATTENTION;
+    const vit_out_kind *k = &OUT_KINDS[out->kind];
+    c->pruned = e->opt.prune_last_layer && c->T <= 224 && k->class_rows_only && k->class_rows_only(e, out);
+    c->qkv_only = k->qkv_only;
+    c->row = k->row_bytes(e, out);
     const int bf16 = e->opt.dtype == VIT_DTYPE_BF16;
     const size_t B = (size_t)e->opt.max_batch, T = (size_t)c->T, D = (size_t)c->D, H1 = (size_t)c->H1;
     const size_t esz = c->esz = bf16 ? sizeof(unsigned short) : sizeof(float);
@@ -1464,7 +1652,7 @@ static int stage_pre_norm(chunk_ctx *c) {
  * out: what to write, at the chunk's first row */
 static int forward_chunk(vit_engine *e, vithip_stream_t s, const void *d_images, const vit_input *in, float *f32_stage, int nb,
                          const vit_output *out) {
-    const vit_config *cfg = &e->cfg;
+    const vit_out_kind *k = &OUT_KINDS[out->kind];
     chunk_ctx ctx, *c = &ctx;
     chunk_setup(e, s, nb, out, c);
 
@@ -1474,28 +1662,12 @@ static int forward_chunk(vit_engine *e, vithip_stream_t s, const void *d_images,
     }
     RUN(stage_embed(c, d_images, in, f32_stage));
     if (e->pre_g) RUN(stage_pre_norm(c));
-    if (out->kind == VIT_OUT_INTERMEDIATE) { /* the layers up to the deepest tap, a block of the rows behind each tapped one; nothing else */
-        for (int l = 0, j = 0; j < out->tap.num_layers; ++l) {
-            RUN(encoder_layer(c, l));
-            if (l == out->tap.layers[j]) RUN(stage_tap(c, out, j++));
-        }
-    } else if (out->kind == VIT_OUT_DENSE) { /* the same walk with the dense head's layers: a tap and a GEMM behind each, then the rows */
-        const vit_dense_head_spec *h = &e->dense.spec;
-        for (int l = 0, j = 0; j < h->num_layers; ++l) {
-            RUN(encoder_layer(c, l));
-            if (l == h->layers[j]) RUN(stage_dense_tap(c, j++));
-        }
-        RUN(stage_dense_out(c, out));
-    } else {
-        const int head_taps = runs_head(out);
-        for (int l = 0; l < cfg->depth; ++l) {
-            RUN(encoder_layer(c, l));
-            if (head_taps) RUN(stage_head_tap(c, l));
-        }
-        if (out->kind == VIT_OUT_FEATURES && !head_taps) RUN(stage_features(c, out));
-        else if (out->kind == VIT_OUT_ATTENTION) RUN(stage_cls_attention(c, out));
-        else RUN(stage_head(c, out));
+    /* the one walk: the layers up to the deepest the kind needs, what it runs behind each, then its last stage (OUT_KINDS) */
+    for (int l = 0, last = k->last_layer ? k->last_layer(e, out) : e->cfg.depth - 1; l <= last; ++l) {
+        RUN(encoder_layer(c, l));
+        if (k->after_layer) RUN(k->after_layer(c, out, l));
     }
+    if (k->finish) RUN(k->finish(c, out));
     for (int j = 1; j < c->L; ++j) { /* join */
         HIP_TRY(e, vithip_event_record(e->ev_join[j - 1], c->lane[j].s));
         HIP_TRY(e, vithip_stream_wait_event(s, e->ev_join[j - 1]));
@@ -1553,177 +1725,6 @@ static int input_images(vit_engine *e, const char *who, const vit_image_u8 *imag
     if (bad) return fail(e, VIT_ERR_ARG, "%s: unsupported geometry (img_size %d, in_chans %d, resize_shorter %d)", who, e->cfg.img_size,
                          e->cfg.in_chans, pp->resize_shorter);
     return VIT_OK;
-}
-
-/* The kinds of output descriptor: probabilities + top-1 (the forwards), the checked feature spec of a features call, the checked
- * attention spec of an attention call, or the checked intermediate spec of an intermediate call. */
-static vit_output output_probs(float *probs, int *label, float *prob) {
-    vit_output out;
-    memset(&out, 0, sizeof(out));
-    out.dst = probs; out.label = label; out.prob = prob;
-    return out;
-}
-/* Spec validation's one home per spec: NULL for a valid spec, else what is wrong with it, as a format for (who, *arg). */
-static const char *feature_spec_fault(const vit_feature_spec *spec, int *arg) {
-    if (!spec) return "%s: the feature spec is required";
-    *arg = spec->kind;
-    if (spec->kind != VIT_FEAT_CLS && spec->kind != VIT_FEAT_MEAN && spec->kind != VIT_FEAT_TOKENS && spec->kind != VIT_FEAT_HEAD) return "%s: unknown feature kind %d";
-    *arg = spec->l2_normalize;
-    if (spec->l2_normalize != 0 && spec->l2_normalize != 1) return "%s: l2_normalize must be 0 or 1 (got %d)";
-    if (spec->l2_normalize && spec->kind == VIT_FEAT_TOKENS) return "%s: l2_normalize applies to the CLS, MEAN and HEAD rows, not to TOKENS";
-    return NULL;
-}
-static const char *attention_spec_fault(const vit_attention_spec *spec, int *arg) {
-    if (!spec) return "%s: the attention spec is required";
-    *arg = spec->kind;
-    if (spec->kind != VIT_ATTN_HEADS && spec->kind != VIT_ATTN_HEAD_MEAN) return "%s: unknown attention kind %d";
-    *arg = spec->reserved;
-    if (spec->reserved != 0) return "%s: vit_attention_spec.reserved must be 0 (got %d)";
-    return NULL;
-}
-
-static int output_features(vit_engine *e, const char *who, const vit_feature_spec *spec, float *dst, vit_output *out) {
-    int arg = 0;
-    const char *fault = feature_spec_fault(spec, &arg);
-    memset(out, 0, sizeof(*out));
-    if (fault) return fail(e, VIT_ERR_ARG, fault, who, arg);
-    if (spec->kind == VIT_FEAT_MEAN && e->tokens < 2) return fail(e, VIT_ERR_ARG, "%s: MEAN needs at least one patch token", who);
-    out->kind = VIT_OUT_FEATURES;
-    out->spec.kind = spec->kind; out->spec.l2_normalize = spec->l2_normalize;
-    out->dst = dst;
-    return VIT_OK;
-}
-
-static int output_attention(vit_engine *e, const char *who, const vit_attention_spec *spec, float *dst, vit_output *out) {
-    int arg = 0;
-    const char *fault = attention_spec_fault(spec, &arg);
-    memset(out, 0, sizeof(*out));
-    if (fault) return fail(e, VIT_ERR_ARG, fault, who, arg);
-    out->kind = VIT_OUT_ATTENTION;
-    out->attn_kind = spec->kind;
-    out->dst = dst;
-    return VIT_OK;
-}
-
-/* The top-k spec, checked against the model: NULL, or what is wrong as a format for (who, arg[0], arg[1]). */
-static const char *topk_spec_fault(const vit_engine *e, const vit_topk_spec *spec, int arg[2]) {
-    arg[0] = arg[1] = 0;
-    if (!spec) return "%s: the top-k spec is required";
-    arg[0] = spec->k; arg[1] = e->cfg.num_classes < VIT_MAX_TOPK ? e->cfg.num_classes : VIT_MAX_TOPK;
-    if (spec->k < 1 || spec->k > arg[1]) return "%s: k = %d must be 1..%d (the smaller of VIT_MAX_TOPK and num_classes)";
-    arg[0] = spec->score;
-    if (spec->score != VIT_SCORE_PROB && spec->score != VIT_SCORE_LOGIT) return "%s: unknown score %d";
-    arg[0] = spec->reserved;
-    if (spec->reserved != 0) return "%s: vit_topk_spec.reserved must be 0 (got %d)";
-    return NULL;
-}
-
-static int output_topk(vit_engine *e, const char *who, const vit_topk_spec *spec, float *dst, vit_output *out) {
-    int arg[2];
-    const char *fault = topk_spec_fault(e, spec, arg);
-    memset(out, 0, sizeof(*out));
-    if (fault) return fail(e, VIT_ERR_ARG, fault, who, arg[0], arg[1]);
-    out->kind = VIT_OUT_TOPK;
-    out->topk.k = spec->k; out->topk.score = spec->score;
-    out->dst = dst;
-    return VIT_OK;
-}
-
-size_t vit_engine_topk_row_elems(const vit_engine *e, const vit_topk_spec *spec) {
-    int arg[2];
-    return e && !topk_spec_fault(e, spec, arg) ? row_elems(e, VIT_OUT_TOPK, spec->k) : 0;
-}
-
-/* The intermediate spec, checked against the model: NULL, or what is wrong as a format for (who, arg[0], arg[1]). */
-static const char *intermediate_spec_fault(const vit_engine *e, const vit_intermediate_spec *spec, int arg[2]) {
-    arg[0] = arg[1] = 0;
-    if (!spec) return "%s: the intermediate spec is required";
-    arg[0] = spec->kind;
-    if (spec->kind != VIT_TAP_CLS && spec->kind != VIT_TAP_TOKENS && spec->kind != VIT_TAP_PATCHES && spec->kind != VIT_TAP_MAP)
-        return "%s: unknown intermediate kind %d";
-    arg[0] = spec->norm;
-    if (spec->norm != 0 && spec->norm != 1) return "%s: norm must be 0 or 1 (got %d)";
-    arg[0] = spec->num_layers; arg[1] = VIT_MAX_TAPS;
-    if (spec->num_layers < 1 || spec->num_layers > VIT_MAX_TAPS) return "%s: num_layers = %d must be 1..%d";
-    arg[0] = spec->reserved;
-    if (spec->reserved != 0) return "%s: vit_intermediate_spec.reserved must be 0 (got %d)";
-    for (int j = 0; j < spec->num_layers; ++j) {
-        arg[0] = j; arg[1] = spec->layers[j];
-        if (spec->layers[j] < 0 || spec->layers[j] >= e->cfg.depth) return "%s: layers[%d] = %d is not a layer of the model";
-        if (j && spec->layers[j] <= spec->layers[j - 1]) return "%s: layers[%d] = %d is not above the entry before it (strictly increasing)";
-    }
-    const int g = e->cfg.img_size / e->cfg.patch_size;
-    arg[0] = g; arg[1] = e->tokens - 1;
-    if (spec->kind == VIT_TAP_MAP && (g < 1 || g * g != e->tokens - 1)) return "%s: MAP needs a square grid of patches: (img_size / patch_size = %d)^2 is not the model's %d";
-    if (spec->kind == VIT_TAP_PATCHES && e->tokens < 2) return "%s: PATCHES needs at least one patch token";
-    return NULL;
-}
-
-static int output_intermediate(vit_engine *e, const char *who, const vit_intermediate_spec *spec, float *dst, vit_output *out) {
-    int arg[2];
-    const char *fault = intermediate_spec_fault(e, spec, arg);
-    memset(out, 0, sizeof(*out)); /* the unused layers[] entries stay zero: the graph key compares the whole spec */
-    if (fault) return fail(e, VIT_ERR_ARG, fault, who, arg[0], arg[1]);
-    out->kind = VIT_OUT_INTERMEDIATE;
-    out->tap.kind = spec->kind; out->tap.norm = spec->norm; out->tap.num_layers = spec->num_layers;
-    for (int j = 0; j < spec->num_layers; ++j) out->tap.layers[j] = spec->layers[j];
-    out->dst = dst;
-    return VIT_OK;
-}
-
-size_t vit_engine_intermediate_row_elems(const vit_engine *e, const vit_intermediate_spec *spec) {
-    int arg[2];
-    return e && !intermediate_spec_fault(e, spec, arg) ? (size_t)spec->num_layers * tap_block_elems(e, spec->kind) : 0;
-}
-
-/* The dense spec, checked and resolved against the model (out_h / out_w: 0 becomes img_size): NULL, or what is wrong as a format for
- * (who, arg[0], arg[1]).  The head itself was checked when it was set. */
-static const char *dense_spec_fault(const vit_engine *e, const vit_dense_spec *spec, vit_dense_spec *res, int arg[2]) {
-    arg[0] = arg[1] = 0;
-    if (!spec) return "%s: the dense spec is required";
-    memset(res, 0, sizeof(*res));
-    arg[0] = spec->kind;
-    if (spec->kind != VIT_DENSE_LABELS && spec->kind != VIT_DENSE_GRID) return "%s: unknown dense kind %d";
-    arg[0] = spec->reserved;
-    if (spec->reserved != 0) return "%s: vit_dense_spec.reserved must be 0 (got %d)";
-    res->kind = spec->kind;
-    arg[0] = spec->out_h; arg[1] = spec->out_w;
-    if (spec->kind == VIT_DENSE_GRID) return spec->out_h || spec->out_w ? "%s: GRID takes no output size (out_h = %d, out_w = %d must be 0)" : NULL;
-    res->out_h = spec->out_h ? spec->out_h : e->cfg.img_size;
-    res->out_w = spec->out_w ? spec->out_w : e->cfg.img_size;
-    if (res->out_h < 1 || res->out_h > 4096 || res->out_w < 1 || res->out_w > 4096)
-        return "%s: out_h = %d and out_w = %d must be 1..4096 each (0 = img_size, which must then be in that range)";
-    return NULL;
-}
-
-static int output_dense(vit_engine *e, const char *who, const vit_dense_spec *spec, float *dst, vit_output *out) {
-    int arg[2];
-    memset(out, 0, sizeof(*out));
-    if (spec && !e->dense.spec.num_layers) return fail(e, VIT_ERR_STATE, "%s before vit_engine_set_dense_head()", who);
-    const char *fault = dense_spec_fault(e, spec, &out->dense, arg);
-    if (fault) {
-        memset(out, 0, sizeof(*out));
-        return fail(e, VIT_ERR_ARG, fault, who, arg[0], arg[1]);
-    }
-    out->kind = VIT_OUT_DENSE;
-    out->dst = dst;
-    return VIT_OK;
-}
-
-size_t vit_engine_dense_row_bytes(const vit_engine *e, const vit_dense_spec *spec) {
-    int arg[2];
-    vit_dense_spec res;
-    return e && e->dense.spec.num_layers && !dense_spec_fault(e, spec, &res, arg) ? dense_row_bytes(e, &res) : 0;
-}
-
-size_t vit_engine_attention_row_elems(const vit_engine *e, const vit_attention_spec *spec) {
-    int arg;
-    return e && !attention_spec_fault(spec, &arg) ? row_elems(e, VIT_OUT_ATTENTION, spec->kind) : 0;
-}
-
-size_t vit_engine_feature_row_elems(const vit_engine *e, const vit_feature_spec *spec) {
-    int arg;
-    return e && !feature_spec_fault(spec, &arg) ? row_elems(e, VIT_OUT_FEATURES, spec->kind) : 0;
 }
 
 /* An 8-bit device-path call normalises into in_stage[0] and uses it until s gets past its kernels: the next host-pointer call's
@@ -2072,13 +2073,7 @@ static int run_call(vit_engine *e, const vit_call *c) {
     if (c->in_kind == VIT_IN_U8) rc = input_u8(e, c->who, c->mean, c->std, &in);
     else if (c->in_kind == VIT_IN_IMAGES) rc = input_images(e, c->who, (const vit_image_u8 *)c->images, c->n, c->pp, &in);
     if (rc) return rc;
-    if (c->out_kind == VIT_OUT_FEATURES) rc = output_features(e, c->who, (const vit_feature_spec *)c->spec, c->dst, &out);
-    else if (c->out_kind == VIT_OUT_ATTENTION) rc = output_attention(e, c->who, (const vit_attention_spec *)c->spec, c->dst, &out);
-    else if (c->out_kind == VIT_OUT_INTERMEDIATE) rc = output_intermediate(e, c->who, (const vit_intermediate_spec *)c->spec, c->dst, &out);
-    else if (c->out_kind == VIT_OUT_TOPK) rc = output_topk(e, c->who, (const vit_topk_spec *)c->spec, c->dst, &out);
-    else if (c->out_kind == VIT_OUT_DENSE) rc = output_dense(e, c->who, (const vit_dense_spec *)c->spec, c->dst, &out);
-    else out = output_probs(c->dst, c->label, c->prob);
-    if (rc) return rc;
+    if ((rc = make_output(e, c->who, c->out_kind, c->spec, c->dst, c->label, c->prob, &out))) return rc;
     return host ? forward_host_in(e, c->who, c->images, &in, c->n, &out, c->rows) : forward_device_in(e, c->images, &in, c->n, &out, c->stream);
 }
 
@@ -2482,7 +2477,7 @@ int vit_engine_debug_pool_scratch(vit_engine *e, int nb, int lane, size_t range[
     vit_feature_spec spec = {VIT_FEAT_MEAN, 0};
     vit_output out;
     chunk_ctx c;
-    if (output_features(e, "debug_pool_scratch", &spec, NULL, &out)) return -1;
+    if (make_output(e, "debug_pool_scratch", VIT_OUT_FEATURES, &spec, NULL, NULL, NULL, &out)) return -1;
     chunk_setup(e, e->stream, nb, &out, &c);
     if (lane >= c.L) return -1;
     const vit_lane *ln = &c.lane[lane];
