@@ -83,9 +83,25 @@ typedef struct {
 
 /* ViT-B/16-224: the reference's macros (ViT_seq.c:10-21). */
 vit_config vit_config_b16(void);
-/* tokens = (img/patch)^2 + 1 */
+/* patches = g * g, g = img_size / VIT_PATCH_SIZE; tokens T = 1 + VIT_REGISTER_TOKENS + patches, the rows of an image in the order the
+ * model keeps them: class token, register tokens (none unless vit_config.patch_size carries a count), patch tokens.
+ *
+ * What every output does with R = VIT_REGISTER_TOKENS register tokens (R = 0: everything as it was):
+ *   probabilities, top-k, VIT_FEAT_CLS, VIT_FEAT_HEAD, VIT_TAP_CLS      row 0
+ *   VIT_FEAT_MEAN, pooled heads (VIT_HEAD_POOL_AVG, _AVG_FCNORM)        the mean over the g * g patch tokens, rows 1 + R .. T - 1
+ *                                                                       (transformers' Dinov2WithRegistersForImageClassification)
+ *   VIT_FEAT_TOKENS, VIT_TAP_TOKENS                                     all T rows (hidden_states; x_norm_regtokens = rows 1 .. R)
+ *   VIT_TAP_PATCHES, VIT_TAP_MAP, dense heads                           the g * g patch rows, [P][D] / [D][g][g]
+ *                                                                       (Dinov2WithRegistersBackbone's feature maps)
+ *   class-token attention                                               rows of T weights in stored order, summing to 1 over all
+ *                                                                       T: the patches are entries 1 + R ..; registers are neither
+ *                                                                       dropped nor renormalised away
+ * Below, P = g * g is the count of patch tokens and F = 1 + R the row of the first of them (F = 1 without registers).
+ * vit_engine_copy_weights* need equal R; the resampled loads work on tensor 3 unchanged. */
+int vit_config_patches(const vit_config *cfg);
 int vit_config_tokens(const vit_config *cfg);
-/* Expected element count of weight tensor `index` (reference index map); 0 if out of range. */
+/* Expected element count of weight tensor `index` (reference index map); 0 if out of range.  Tensor 0 is the
+ * prefix [(1 + R)][D] (class token, then register tokens), tensor 3 the position embedding [(g * g + 1)][D] at every R. */
 size_t vit_config_weight_size(const vit_config *cfg, int index);
 /* Algorithmic MACs of one image (17,563,828,224 for ViT-B/16-224). */
 unsigned long long vit_config_macs_per_image(const vit_config *cfg);
@@ -198,7 +214,7 @@ int vit_engine_forward_host_u8(vit_engine *e, const unsigned char *const *images
  * tokens rows of D = embed_dim per image) and y[i][t] = LayerNorm_final(x[i][t]) (the encoder_ln weights, vithip_layernorm_f32):
  *
  *   VIT_FEAT_CLS     out[i] = y[i][0]                                  [n][D]     the operand the classifier head reads
- *   VIT_FEAT_MEAN    out[i] = 1/(T-1) * sum_{t=1}^{T-1} y[i][t]        [n][D]     mean of the patch tokens (timm global_pool='avg')
+ *   VIT_FEAT_MEAN    out[i] = 1/P * sum_{t=F}^{T-1} y[i][t]            [n][D]     mean of the P patch tokens, rows F = 1 + R .. (timm global_pool='avg')
  *   VIT_FEAT_TOKENS  out[i][t] = y[i][t], class row first              [n][T][D]  all tokens (timm forward_features)
  *   VIT_FEAT_HEAD    out[i] = head(operand[i])                         [n][num_classes]  the head in force -- the checkpoint's or one
  *                    from vit_engine_set_head -- applied to its operand, no softmax: CLIP's projected image embedding when the head
@@ -305,7 +321,7 @@ int vit_engine_get_resize_filter(const vit_engine *e);  /* -1 for a NULL engine 
  *   VIT_ATTN_HEAD_MEAN  out[i][t] = (p[i][0][t] + p[i][1][t] + ...) / (float)heads      [n][T]         heads added in order, in fp32:
  *                                                                                       the HEADS bits of the same engine, reduced
  *
- * Rows are fp32 for both engine dtypes; the patch tokens are columns 1..T-1 in raster order.  The last layer runs its LayerNorm (or
+ * Rows are fp32 for both engine dtypes; the patch tokens are columns 1 + R..T-1 in raster order (register tokens, if any, columns 1..R).  The last layer runs its LayerNorm (or
  * the fold's statistics) and its QKV GEMM; then each lane runs vithip_cls_attention_* (vit_hip_kernels.h states the arithmetic) on
  * the Q and K it left.  Nothing else of that layer is launched, nor the final LayerNorm, the head or the softmax.  The map is the
  * softmax the forward itself uses for the class row: fp32 engines compute it in fp32, bf16 engines from the bf16 q and k of their
@@ -347,16 +363,17 @@ int vit_engine_cls_attention_host_images(vit_engine *e, const vit_image_u8 *imag
  * Intermediate-layer outputs instead of probabilities: the residual stream behind chosen encoder layers (DINOv2
  * get_intermediate_layers, timm forward_intermediates).  With x_l the fp32 residual stream behind encoder layer l (T = tokens rows of
  * D = embed_dim per image; layer 0 is the first layer, so x_l is what the oracle calls stages[l + 1]), f = the FINAL LayerNorm
- * (encoder_ln, as DINOv2 norm=True applies it to every tapped layer) when norm = 1 and the identity when norm = 0, P = T - 1 and
+ * (encoder_ln, as DINOv2 norm=True applies it to every tapped layer) when norm = 1 and the identity when norm = 0, P = g * g patch tokens at rows F = 1 + R .. and
  * K = num_layers, the row of image i is K blocks, block j for layer layers[j]:
  *
  *   VIT_TAP_CLS      block = f(x_l[i][0])                        [n][K][D]        = [n][K*D], the operand of a linear probe
- *   VIT_TAP_TOKENS   block[t] = f(x_l[i][t]), class row first    [n][K][T][D]
- *   VIT_TAP_PATCHES  block[t-1] = f(x_l[i][t]), t = 1..P         [n][K][P][D]
- *   VIT_TAP_MAP      block[d][t-1] = f(x_l[i][t])[d]             [n][K][D][g][g]  = [n][K*D][g][g], g = img_size / patch_size, patches in
+ *   VIT_TAP_TOKENS   block[t] = f(x_l[i][t]), class row first,   [n][K][T][D]
+ *                    then the register rows, then the patches
+ *   VIT_TAP_PATCHES  block[p] = f(x_l[i][F + p]), p = 0..P-1     [n][K][P][D]
+ *   VIT_TAP_MAP      block[d][p] = f(x_l[i][F + p])[d]           [n][K][D][g][g]  = [n][K*D][g][g], g = img_size / patch_size, patches in
  *                                                                                 raster order: the channel concatenation of a dense head
  *
- * Rows are fp32 for both engine dtypes.  Behind each tapped layer every lane launches vithip_tap_f32 (vit_hip_kernels.h) once, on
+ * Rows are fp32 for both engine dtypes.  Behind each tapped layer every lane launches vithip_tap_f32_prefix_eps (vit_hip_kernels.h; prefix = F) once, on
  * its own stream, from its rows of x into its images' blocks; normalised values are the bits vithip_layernorm_f32 gives, so a tap of
  * the last layer with norm = 1 is the bits of the matching features call (TOKENS, CLS), MAP is the transpose of PATCHES bit for bit,
  * and block j does not depend on which other layers are tapped.  Layers behind the deepest tap are not launched, nor the final
@@ -375,7 +392,7 @@ int vit_engine_cls_attention_host_images(vit_engine *e, const vit_image_u8 *imag
  * logits.
  * VIT_ERR_ARG (the engine stays usable, nothing was enqueued): NULL pointers, n <= 0, an unknown kind, norm other than 0 / 1, num_layers
  * outside 1..VIT_MAX_TAPS, a layer outside 0..depth-1 or not above the one before it (the message names the entry), reserved != 0, MAP
- * when img_size / patch_size does not give a square grid of T - 1 patches, and what the matching forward refuses.
+ * when img_size / patch_size does not give a square grid of P patches, and what the matching forward refuses.
  */
 enum { VIT_TAP_CLS = 0, VIT_TAP_TOKENS = 1, VIT_TAP_PATCHES = 2, VIT_TAP_MAP = 3 };
 #define VIT_MAX_TAPS 32
@@ -458,7 +475,7 @@ int vit_engine_topk_host_images(vit_engine *e, const vit_image_u8 *images, int n
  * Pooled and multi-layer classifier heads: another operand for the head GEMM, as engine state.  The checkpoint's own head (tensors
  * base+2, base+3 of the Network) reads LayerNorm_final(x[i][0]); the published classifiers of DINOv2 and of timm's average-pooled
  * ViTs read something else.  With f the final LayerNorm (tensors base, base+1), x_l the residual stream behind encoder layer l (layer
- * l = oracle stages[l + 1], as in vit_intermediate_spec), P = T - 1 and K = num_cls_layers, the operand row of image i is
+ * l = oracle stages[l + 1], as in vit_intermediate_spec), P = g * g patch tokens at rows F = 1 + R .. and K = num_cls_layers, the operand row of image i is
  *
  *     [ f(x_{l_0}[i][0]) | ... | f(x_{l_{K-1}}[i][0]) | pooled ]          in_features = (K + (pool != NONE)) * D floats
  *
@@ -499,7 +516,7 @@ enum { VIT_HEAD_POOL_NONE = 0, VIT_HEAD_POOL_AVG = 1, VIT_HEAD_POOL_AVG_FCNORM =
 typedef struct {
     int num_cls_layers;            /* 0..VIT_MAX_TAPS */
     int cls_layers[VIT_MAX_TAPS];  /* strictly increasing, 0 <= l < depth (layer l = oracle stages[l + 1], as in vit_intermediate_spec) */
-    int pool;                      /* VIT_HEAD_POOL_*: over the patch tokens (rows 1..T-1) of the LAST layer */
+    int pool;                      /* VIT_HEAD_POOL_*: over the patch tokens (rows 1 + R..T-1) of the LAST layer */
     int reserved;                  /* must be 0 */
 } vit_head_spec;
 /* (num_cls_layers + (pool != NONE)) * D; 0 on a bad spec */
@@ -513,7 +530,7 @@ int vit_engine_read_head_operand(vit_engine *e, float *dst, int rows);
  * tokens, the logits resized bilinearly to the image, then the argmax.  The head is engine state, beside and independent of the
  * classifier head: setting or removing one never disturbs the other.
  *
- * With K = num_layers, D = embed_dim, P = T - 1 = g * g patches (g = img_size / patch_size) and A_j the [P][D] rows of an
+ * With K = num_layers, D = embed_dim, P = g * g patches (g = img_size / patch_size; rows 1 + R..T-1) and A_j the [P][D] rows of an
  * intermediate call of VIT_TAP_PATCHES with the head's norm for layer layers[j], an image's logits [P][num_classes] are
  *     logits = bias + sum_j A_j . weight[:, j*D .. (j+1)*D]^T
  * weight [num_classes][K * D] row-major: the 1x1 conv's weight, the earliest layer's columns first (a BatchNorm in front of it is
@@ -529,7 +546,7 @@ int vit_engine_read_head_operand(vit_engine *e, float *dst, int rows);
  * and bias must then be NULL) removes the head; EVERY weight install removes it, and the copy calls do not carry it: set it again
  * behind them, per engine.  VIT_ERR_STATE: no weights loaded yet.  VIT_ERR_ARG, nothing changed: a NULL weight or bias with a spec,
  * num_layers outside 1..VIT_MAX_TAPS, a layer outside 0..depth-1 or not above the one before it (the message names the entry), norm
- * other than 0 / 1, num_classes outside 1..255, reserved != 0, an img_size / patch_size that does not give a square grid of T - 1
+ * other than 0 / 1, num_classes outside 1..255, reserved != 0, an img_size / patch_size that does not give a square grid of P
  * patches.
  *
  * The six calls mirror the six intermediate calls argument for argument (`out` is untyped: labels are bytes): the same images,

@@ -356,6 +356,28 @@ int vithip_patch_embed_f32(vithip_stream_t stream, const float *images, const fl
 int vithip_patch_embed_f32_general(vithip_stream_t stream, const float *images, const float *conv_w,
                                    const float *conv_b, const float *cls, const float *pos, float *x,
                                    int n_images, int img_size, int patch_size, int in_chans, int embed_dim);
+/*
+ * The three embeddings the engine runs, for a model with num_registers register tokens between the class token and the patch tokens
+ * (DINOv2 `_reg4`; transformers' Dinov2WithRegistersEmbeddings).  prefix: [(1 + num_registers)][D], the class token, then the
+ * register tokens; pos: [(S/P)^2 + 1][D] as ever -- registers take no position embedding; x: [n][T][D], T = 1 + num_registers + (S/P)^2:
+ *   x[img][0][:]                     = prefix[0] + pos[0]
+ *   x[img][1 + r][:]                 = prefix[1 + r]                         r = 0..num_registers-1, the bits of prefix
+ *   x[img][1 + num_registers + p][:] = conv_b + patch_p . conv_w + pos[1 + p]
+ * Everything else is the entry of the same name without _reg, which is this one at num_registers == 0, bit for bit; a patch row has
+ * the same bits at every num_registers (k ascending; neither the batch nor the image's place in it changes a row), and nothing is
+ * written outside x[n][T][D].  hipErrorInvalidValue, nothing launched: num_registers outside 0..VITHIP_MAX_REGISTER_TOKENS,
+ * n * T >= 2^31, and whatever the plain entry refuses.
+ */
+#define VITHIP_MAX_REGISTER_TOKENS 16
+int vithip_patch_embed_f32_reg(vithip_stream_t stream, const float *images, const float *conv_w, const float *conv_b,
+                               const float *prefix, const float *pos, float *x, int n_images, int img_size, int patch_size,
+                               int in_chans, int embed_dim, int num_registers);
+int vithip_patch_embed_f32_general_reg(vithip_stream_t stream, const float *images, const float *conv_w, const float *conv_b,
+                                       const float *prefix, const float *pos, float *x, int n_images, int img_size, int patch_size,
+                                       int in_chans, int embed_dim, int num_registers);
+int vithip_patch_embed_bf16_reg(vithip_stream_t stream, const float *images, const unsigned short *conv_w16, const float *conv_b,
+                                const float *prefix, const float *pos, float *x, unsigned short *patches16, int n_images,
+                                int img_size, int patch_size, int in_chans, int embed_dim, int num_registers);
 
 /*
  * y[r][0..dim) = (x[r] - mean) * inv_std * gamma + beta for rows r = 0..rows-1 where row r
@@ -610,6 +632,13 @@ int vithip_tap_f32(vithip_stream_t s, const float *x, size_t ldx,          /* [i
                    int images, int tokens, int dim, int layout);
 int vithip_tap_f32_eps(vithip_stream_t s, const float *x, size_t ldx, float *out, size_t out_image_stride, const float *gamma,
                        const float *beta, int images, int tokens, int dim, int layout, double eps);
+/* The same with `prefix` rows in front of an image's patch rows instead of one (a register model keeps its register tokens between
+ * the class token and the patches: prefix = 1 + registers), 1 <= prefix <= tokens, and prefix < tokens for PATCHES and MAP.
+ * P = tokens - prefix; CLS is row 0 and TOKENS every row in stored order, as above; PATCHES and MAP read rows prefix..tokens-1, and
+ * MAP's 16-byte stores key on this P % 4.  No row in front of `prefix` is read by PATCHES or MAP: a non-finite register row reaches
+ * neither.  The two entries above are this one at prefix == 1, bit for bit.  Also refused: prefix outside those bounds. */
+int vithip_tap_f32_prefix_eps(vithip_stream_t s, const float *x, size_t ldx, float *out, size_t out_image_stride, const float *gamma,
+                              const float *beta, int images, int tokens, int prefix, int dim, int layout, double eps);
 
 /*
  * A position embedding resampled to another patch grid (csrc/vit_pos_resample.hip), so that a checkpoint runs at another input size.

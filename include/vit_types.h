@@ -43,7 +43,7 @@ typedef struct {
  */
 typedef struct {
     int img_size;     /* 224 */
-    int patch_size;   /* 16  */
+    int patch_size;   /* 16; bits 24..30 hold the count of register tokens (0: a plain patch size is a model without): VIT_PATCH_SIZE_OF() */
     int in_chans;     /* 3   */
     int num_classes;  /* 1000 */
     int embed_dim;    /* 768 */
@@ -69,8 +69,24 @@ enum { VIT_MLP_GELU = 0, VIT_MLP_SWIGLU = 1, VIT_MLP_QUICKGELU = 3 /* 2 stays un
 /* output rows of the fc1 weight (tensors 8 and 9 of a layer hold VIT_FC1_ROWS * embed_dim and VIT_FC1_ROWS floats) */
 #define VIT_FC1_ROWS(cfg) (VIT_MLP_KIND(cfg) == VIT_MLP_SWIGLU ? 2 * VIT_HIDDEN_DIM(cfg) : VIT_HIDDEN_DIM(cfg))
 
+/*
+ * Register tokens (DINOv2 `_reg4`, "Vision Transformers Need Registers"): R learned rows between the class token and the patch
+ * tokens, T = 1 + R + (img_size / patch_size)^2 token rows in that order.  They take no position embedding, and no output counts
+ * them among "the patch tokens".  As with the MLP kind, the struct keeps its eight ints and the count travels in the top bits of
+ * patch_size:
+ *     vit_config reg = {224, VIT_PATCH_SIZE_OF(14, 4), 3, 1000, 768, 12, 12, 3072};
+ * Read the two parts with VIT_PATCH_SIZE(cfg) and VIT_REGISTER_TOKENS(cfg), never patch_size itself.  Weight tensor 0 of such a
+ * model is the prefix [(1 + R)][embed_dim]: the class token, then the checkpoint's register_tokens in their order; tensor 3, the
+ * position embedding, stays [(g * g + 1)][embed_dim].
+ */
+#define VIT_REG_SHIFT 24
+#define VIT_PATCH_SIZE_OF(patch, regs) ((int)(patch) | ((int)(regs) << VIT_REG_SHIFT))
+#define VIT_PATCH_SIZE(cfg) ((cfg)->patch_size & ((1 << VIT_REG_SHIFT) - 1))
+#define VIT_REGISTER_TOKENS(cfg) ((cfg)->patch_size >> VIT_REG_SHIFT)
+#define VIT_MAX_REGISTER_TOKENS 16
+
 #define VIT_WEIGHTS_PER_LAYER 12
-/* number of Network entries: cls, conv w/b, pos, 12 per layer, ln w/b, head w/b (Main.c:29-30 => 152) */
+/* number of Network entries: cls (the prefix: class token + register tokens), conv w/b, pos, 12 per layer, ln w/b, head w/b (Main.c:29-30 => 152) */
 #define VIT_WEIGHT_COUNT(depth) (4 + VIT_WEIGHTS_PER_LAYER * (depth) + 4)
 
 #ifdef __cplusplus

@@ -11,7 +11,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .synth import MLP_CODES, MLP_SHIFT, ModelConfig
+from .synth import MLP_CODES, MLP_SHIFT, REG_SHIFT, ModelConfig
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # VIT_HIP_LIBRARY: the probe build (make probes -> libvit_mi355x_probe.so) for the tools/ scripts; default = the product
@@ -39,7 +39,7 @@ class CConfig(C.Structure):
 
     @classmethod
     def of(cls, cfg: ModelConfig) -> "CConfig":
-        return cls(cfg.img_size, cfg.patch_size, cfg.in_chans, cfg.num_classes, cfg.embed_dim,
+        return cls(cfg.img_size, cfg.patch_size | (cfg.num_register_tokens << REG_SHIFT), cfg.in_chans, cfg.num_classes, cfg.embed_dim,
                    cfg.depth, cfg.num_heads, cfg.hidden_dim | (MLP_CODES.get(cfg.mlp, cfg.mlp) << MLP_SHIFT))
 
 
@@ -896,10 +896,13 @@ def tap_block(images: int, tokens: int, dim: int, layout) -> tuple:
 
 
 def tap(x, gamma, beta, images: int, tokens: int, layout, ldx: Optional[int] = None, out_image_stride: Optional[int] = None,
-        frames=None, out: Optional[dict] = None, d_out: Optional[int] = None, eps=None) -> Optional[np.ndarray]:
+        frames=None, out: Optional[dict] = None, d_out: Optional[int] = None, eps=None, prefix: Optional[int] = None) -> Optional[np.ndarray]:
     """vithip_tap_f32: x [images * tokens][dim] -> per image the block of `layout`; gamma = beta = None copies the rows unnormalised.
     ldx, frames, out: as for layernorm(); the output frame "out" has one row per image, a block wide, out_image_stride apart.
-    d_out: a raw device address to write to instead (out_image_stride is then required); nothing is returned."""
+    d_out: a raw device address to write to instead (out_image_stride is then required); nothing is returned.
+    prefix: the rows in front of an image's patch rows (1 + register tokens) -- vithip_tap_f32_prefix_eps; None: the entries without."""
+    if prefix is not None:
+        return _tap_prefix(x, gamma, beta, images, tokens, layout, int(prefix), out_image_stride, d_out, eps)
     x = _as_f32(x)
     rows, dim = x.shape
     k = TAP_KINDS[layout] if isinstance(layout, str) else int(layout)
@@ -918,6 +921,27 @@ def tap(x, gamma, beta, images: int, tokens: int, layout, ldx: Optional[int] = N
     _note(out, out=do)
     hip_check(fn(None, dx.ptr, dx.ld, do.ptr, do.ld, *args), "vithip_tap_f32")
     return do.window().reshape((images,) + shape)
+
+
+def _tap_prefix(x, gamma, beta, images, tokens, layout, prefix, out_image_stride, d_out, eps):
+    x = _as_f32(x)
+    rows, dim = x.shape
+    k = TAP_KINDS[layout] if isinstance(layout, str) else int(layout)
+    L = lib()
+    L.vithip_tap_f32_prefix_eps.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_double]
+    dx = DeviceArray.from_numpy(x)
+    dg = DeviceArray.from_numpy(_as_f32(gamma)) if gamma is not None else None
+    db = DeviceArray.from_numpy(_as_f32(beta)) if beta is not None else None
+    args = (dg.ptr if dg else None, db.ptr if db else None, images, tokens, prefix, dim, k, float(1e-6 if eps is None else eps))  # VITHIP_LN_EPS
+    if d_out is not None:
+        hip_check(L.vithip_tap_f32_prefix_eps(None, dx.ptr, dim, d_out, out_image_stride, *args), "vithip_tap_f32_prefix_eps")
+        hip_check(L.vithip_device_sync(), "sync")
+        return None
+    shape = {0: (dim,), 1: (tokens, dim), 2: (tokens - prefix, dim), 3: (dim, tokens - prefix)}[k]
+    block = int(np.prod(shape))
+    do = DeviceArray((images, block if out_image_stride is None else out_image_stride))
+    hip_check(L.vithip_tap_f32_prefix_eps(None, dx.ptr, dim, do.ptr, do.shape[1], *args), "vithip_tap_f32_prefix_eps")
+    return do.numpy()[:, :block].reshape((images,) + shape)
 
 
 def pos_resample_table(mode, n_in: int, n_out: int):
@@ -1174,6 +1198,45 @@ def patch_embed(cfg: ModelConfig, images, conv_w, conv_b, cls, pos) -> np.ndarra
                                            cfg.img_size, cfg.patch_size, cfg.in_chans, cfg.embed_dim),
               "vithip_patch_embed_f32")
     return dx.numpy().reshape(n, cfg.tokens, cfg.embed_dim)
+
+
+def patch_embed_reg_raw(kind: str, images_ptr, conv_w_ptr, conv_b_ptr, prefix_ptr, pos_ptr, x_ptr, n: int, img_size: int,
+                        patch_size: int, in_chans: int, embed_dim: int, registers: int, patches16_ptr=None) -> int:
+    """vithip_patch_embed_f32_reg ("f32": the dispatching entry), _f32_general_reg ("general") or _bf16_reg ("bf16": conv_w_ptr holds
+    bf16 bits, patches16_ptr the workspace) on raw device addresses; returns the launcher's code after the stream has drained."""
+    L = lib()
+    ints = (n, img_size, patch_size, in_chans, embed_dim, registers)
+    if kind == "bf16":
+        L.vithip_patch_embed_bf16_reg.argtypes = [C.c_void_p] * 8 + [C.c_int] * 6
+        rc = L.vithip_patch_embed_bf16_reg(None, images_ptr, conv_w_ptr, conv_b_ptr, prefix_ptr, pos_ptr, x_ptr, patches16_ptr, *ints)
+    else:
+        fn = {"f32": L.vithip_patch_embed_f32_reg, "general": L.vithip_patch_embed_f32_general_reg}[kind]
+        fn.argtypes = [C.c_void_p] * 7 + [C.c_int] * 6
+        rc = fn(None, images_ptr, conv_w_ptr, conv_b_ptr, prefix_ptr, pos_ptr, x_ptr, *ints)
+    hip_check(L.vithip_device_sync(), "sync")
+    return int(rc)
+
+
+def patch_embed_reg(cfg: ModelConfig, images, conv_w, conv_b, prefix, pos, kind: str = "f32", registers: Optional[int] = None,
+                    guard: int = 0, fill: float = 0.0):
+    """The embedding of a register model: prefix [(1 + registers)][D] (class token, then registers), pos [(patches + 1)][D];
+    registers defaults to cfg.num_register_tokens.  kind: "f32" | "general" | "bf16" (patch_embed_reg_raw; "bf16" rounds conv_w here).
+    Returns x [n][1 + registers + patches][D]; with guard > 0, (x, front, back): x lies between two runs of `guard` floats preset
+    to `fill` like x itself, returned as they are afterwards."""
+    images = _as_f32(images)
+    n, R, D = images.shape[0], cfg.num_register_tokens if registers is None else int(registers), cfg.embed_dim
+    T = 1 + max(R, 0) + cfg.patches
+    d = [DeviceArray.from_numpy(_as_f32(a)) for a in (images, conv_b, prefix, pos)]
+    w = _as_f32(conv_w).reshape(D, -1)
+    dw = DeviceArray.from_numpy(to_bf16_bits(w) if kind == "bf16" else w)
+    dp = DeviceArray((n * cfg.patches, cfg.patch_dim), np.uint16) if kind == "bf16" else None
+    assert guard % 4 == 0, "x stays 16-byte aligned"
+    dx = DeviceArray.from_numpy(np.full(2 * guard + n * T * D, fill, np.float32))
+    hip_check(patch_embed_reg_raw(kind, d[0].ptr, dw.ptr, d[1].ptr, d[2].ptr, d[3].ptr, dx.ptr + 4 * guard, n, cfg.img_size, cfg.patch_size,
+                                  cfg.in_chans, D, R, dp.ptr if dp else None), f"vithip_patch_embed_{kind}_reg")
+    flat = dx.numpy()
+    x = flat[guard:guard + n * T * D].reshape(n, T, D)
+    return (x, flat[:guard], flat[guard + n * T * D:]) if guard else x
 
 
 def patch_embed_general_raw(images_ptr, conv_w_ptr, conv_b_ptr, cls_ptr, pos_ptr, x_ptr, n: int, img_size: int, patch_size: int,
@@ -1669,15 +1732,15 @@ class Engine:
 
     # ---- intermediate layers (vit_engine_intermediate_*): the residual stream behind `layers`, kind "cls" | "tokens" | "patches" | "map" ----
     def intermediate_shape(self, n: int, layers, kind="cls", norm=True) -> tuple:
-        """Shape of the rows n images give, K = len(layers): (n, K, D) for "cls", (n, K, T, D) for "tokens", (n, K, T - 1, D) for
-        "patches", (n, K, D, g, g) for "map"."""
+        """Shape of the rows n images give, K = len(layers): (n, K, D) for "cls", (n, K, T, D) for "tokens", (n, K, P, D) for
+        "patches", (n, K, D, g, g) for "map"; P = g * g patches, T = 1 + register tokens + P."""
         spec = intermediate_spec(layers, kind, norm, self.cfg.depth)
         elems = lib().vit_engine_intermediate_row_elems(self._h, C.byref(spec))
         if elems == 0:
             raise VitError(f"bad intermediate spec (layers={layers!r}, kind={kind!r}, norm={norm!r})")
         D, T, K = self.cfg.embed_dim, self.cfg.tokens, spec.num_layers
         g = self.cfg.img_size // self.cfg.patch_size
-        shape = {0: (n, K, D), 1: (n, K, T, D), 2: (n, K, T - 1, D), 3: (n, K, D, g, g)}[spec.kind]
+        shape = {0: (n, K, D), 1: (n, K, T, D), 2: (n, K, self.cfg.patches, D), 3: (n, K, D, g, g)}[spec.kind]
         assert int(np.prod(shape[1:])) == elems, (shape, elems)
         return shape
 

@@ -378,12 +378,13 @@ __global__ __launch_bounds__(256, (ARITH == ARITH_SPLIT3 ? 2 : BK == 16 ? 3 : 1)
     }
 }
 
-// x[img][0][:] = cls + pos[0] (class_token + pos_emb of the reference, ViT_seq.c:72-101)
-__global__ void cls_rows_kernel(const float *cls, const float *pos, float *x, int n_images, int tokens, int dim) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n_images * dim) return;
-    const int im = idx / dim, d = idx - im * dim;
-    x[(size_t)im * tokens * dim + d] = cls[d] + pos[d];
+// x[img][0][:] = prefix[0] + pos[0] (class_token + pos_emb of the reference, ViT_seq.c:72-101); x[img][1 + r][:] = prefix[1 + r], the
+// register tokens of a register model, which take no position embedding.  rows = 1 + registers.
+__global__ void prefix_rows_kernel(const float *prefix, const float *pos, float *x, int n_images, int tokens, int rows, int dim) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x, per_image = rows * dim;
+    if (idx >= n_images * per_image) return;
+    const int im = idx / per_image, rd = idx - im * per_image;
+    x[(size_t)im * tokens * dim + rd] = rd < dim ? prefix[rd] + pos[rd] : prefix[rd];
 }
 
 template <int BM, int BN, int WM, int WN, int AMODE, int BK = 32, bool PIPE = false, int ARITH = ARITH_F32>
@@ -526,9 +527,13 @@ using vit_row::aligned16;
 
 }  // namespace
 
-int vitgemm::launch_cls_rows(hipStream_t stream, const float *cls, const float *pos, float *x, int n_images, int tokens, int dim) {
-    const int total = n_images * dim;
-    hipLaunchKernelGGL(cls_rows_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, cls, pos, x, n_images, tokens, dim);
+int vitgemm::launch_prefix_rows(hipStream_t stream, const float *prefix, const float *pos, float *x, int n_images, int tokens, int registers,
+                                int dim) {
+    // callers bound registers by VITHIP_MAX_REGISTER_TOKENS (embed_rows_ok); the element index of the kernel is an int: checked here
+    const long long total = (long long)n_images * (1 + registers) * dim;
+    if (registers < 0 || total > 0x7fffffffLL) return static_cast<int>(hipErrorInvalidValue);
+    hipLaunchKernelGGL(prefix_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, prefix, pos, x, n_images, tokens,
+                       1 + registers, dim);
     return static_cast<int>(hipGetLastError());
 }
 
@@ -693,29 +698,36 @@ int vithip_gemm_f32(vithip_stream_t stream, const vithip_gemm_args *a) {
     return vithip_rowstats_f32_eps(stream, a->C, (size_t)a->ldc, a->stats_out, a->M, a->N, eps);
 }
 
-int vithip_patch_embed_f32(vithip_stream_t stream, const float *images, const float *conv_w,
-                           const float *conv_b, const float *cls, const float *pos, float *x,
-                           int n_images, int img_size, int patch_size, int in_chans, int embed_dim) {
-    if (!images || !conv_w || !conv_b || !cls || !pos || !x || n_images <= 0)
+int vithip_patch_embed_f32_reg(vithip_stream_t stream, const float *images, const float *conv_w, const float *conv_b,
+                               const float *prefix, const float *pos, float *x, int n_images, int img_size, int patch_size,
+                               int in_chans, int embed_dim, int num_registers) {
+    if (!images || !conv_w || !conv_b || !prefix || !pos || !x || n_images <= 0)
         return static_cast<int>(hipErrorInvalidValue);
     if (patch_size <= 0 || in_chans <= 0) return static_cast<int>(hipErrorInvalidValue);
     const int K = in_chans * patch_size * patch_size;
     // the 16-byte gather below takes patch % 4, img % 4 and K steps of 32; every other even geometry (patch 14: K = 588) goes to the
     // 8-byte kernel of vit_patch_embed_general.hip, which refuses what it cannot take either
     if (patch_size % 4 || img_size % 4 || K % KALIGN)
-        return vithip_patch_embed_f32_general(stream, images, conv_w, conv_b, cls, pos, x, n_images, img_size, patch_size, in_chans,
-                                              embed_dim);
+        return vithip_patch_embed_f32_general_reg(stream, images, conv_w, conv_b, prefix, pos, x, n_images, img_size, patch_size,
+                                                  in_chans, embed_dim, num_registers);
     if (img_size % patch_size) return static_cast<int>(hipErrorInvalidValue);
     if (!aligned16(images) || !aligned16(conv_w)) return static_cast<int>(hipErrorInvalidValue);
     const int G = img_size / patch_size;
+    if (!vitgemm::embed_rows_ok(n_images, G * G, num_registers)) return static_cast<int>(hipErrorInvalidValue);
     GemmParams p{};
     p.A = images; p.W = conv_w; p.bias = conv_b; p.C = x; p.pos = pos;
     p.lda = 0; p.ldw = K; p.ldc = embed_dim;
     p.M = n_images * G * G; p.N = embed_dim; p.K = K;
-    p.patches = G * G; p.grid = G; p.patch = patch_size; p.img = img_size; p.chans = in_chans;
+    p.patches = G * G; p.grid = G; p.patch = patch_size; p.img = img_size; p.chans = in_chans; p.prefix = 1 + num_registers;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (const int e = launch_cls_rows(s, cls, pos, x, n_images, G * G + 1, embed_dim)) return e;
+    if (const int e = launch_prefix_rows(s, prefix, pos, x, n_images, G * G + 1 + num_registers, num_registers, embed_dim)) return e;
     return dispatch<A_PATCHES>(s, p, VITHIP_EPI_BIAS, 0, 0);
+}
+
+int vithip_patch_embed_f32(vithip_stream_t stream, const float *images, const float *conv_w,
+                           const float *conv_b, const float *cls, const float *pos, float *x,
+                           int n_images, int img_size, int patch_size, int in_chans, int embed_dim) {
+    return vithip_patch_embed_f32_reg(stream, images, conv_w, conv_b, cls, pos, x, n_images, img_size, patch_size, in_chans, embed_dim, 0);
 }
 
 }  // extern "C"

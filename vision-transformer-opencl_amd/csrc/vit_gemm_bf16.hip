@@ -345,10 +345,10 @@ int vithip_gemm_bf16_set_debug_buffer(void *buf) {
 }
 #endif
 
-int vithip_patch_embed_bf16(vithip_stream_t stream, const float *images, const unsigned short *conv_w16, const float *conv_b,
-                            const float *cls, const float *pos, float *x, unsigned short *patches16, int n_images,
-                            int img_size, int patch_size, int in_chans, int embed_dim) {
-    if (!images || !conv_w16 || !conv_b || !cls || !pos || !x || !patches16 || n_images <= 0)
+int vithip_patch_embed_bf16_reg(vithip_stream_t stream, const float *images, const unsigned short *conv_w16, const float *conv_b,
+                                const float *prefix, const float *pos, float *x, unsigned short *patches16, int n_images,
+                                int img_size, int patch_size, int in_chans, int embed_dim, int num_registers) {
+    if (!images || !conv_w16 || !conv_b || !prefix || !pos || !x || !patches16 || n_images <= 0)
         return static_cast<int>(hipErrorInvalidValue);
     if (patch_size <= 0 || patch_size % 8 || img_size % patch_size || in_chans <= 0 || embed_dim % 4)
         return static_cast<int>(hipErrorInvalidValue);
@@ -356,24 +356,32 @@ int vithip_patch_embed_bf16(vithip_stream_t stream, const float *images, const u
     if (K % TBK || K < 2 * TBK) return static_cast<int>(hipErrorInvalidValue);
     if (!aligned16(images) || !aligned16(conv_w16) || !aligned16(conv_b) || !aligned16(pos) || !aligned16(x) || !aligned16(patches16))
         return static_cast<int>(hipErrorInvalidValue);
-    if ((size_t)n_images * P > 0x7fffffffu / 2) return static_cast<int>(hipErrorInvalidValue);
+    if ((size_t)n_images * P > 0x7fffffffu / 2 || !vitgemm::embed_rows_ok(n_images, P, num_registers))
+        return static_cast<int>(hipErrorInvalidValue);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t work = (size_t)n_images * in_chans * img_size * (img_size / 8);
     size_t blocks = (work + 255) / 256;
     if (blocks > 256 * 32) blocks = 256 * 32;
     hipLaunchKernelGGL(patchify_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, s, images, patches16, n_images, img_size,
                        patch_size, in_chans);
-    if (const int e = vitgemm::launch_cls_rows(s, cls, pos, x, n_images, P + 1, embed_dim)) return e;
+    if (const int e = vitgemm::launch_prefix_rows(s, prefix, pos, x, n_images, P + 1 + num_registers, num_registers, embed_dim)) return e;
     Bf16Params p{};
     p.A = patches16; p.W = conv_w16; p.bias = conv_b; p.R = pos; p.C = x;
     p.lda = K; p.ldw = K; p.ldr = embed_dim; p.ldc = embed_dim;
     p.M = n_images * P; p.N = embed_dim; p.K = K;
     (void)vitgemm::set_tile_grid(p, TBM, TBN);  // (the launcher sizes its own grid)
     p.group_m = 8;
-    p.patches = P;
+    p.patches = P; p.prefix = 1 + num_registers;
     const int g_cus = vitdev::current_cus();  // of the current device, asked per call (engines of several devices share the process)
     if (g_cus <= 0) return static_cast<int>(hipErrorInvalidDevice);
     return vitgemm::launch_gemm_bf16_pp(s, p, VITHIP_BF16_EPI_F32_EMBED, g_cus);
+}
+
+int vithip_patch_embed_bf16(vithip_stream_t stream, const float *images, const unsigned short *conv_w16, const float *conv_b,
+                            const float *cls, const float *pos, float *x, unsigned short *patches16, int n_images,
+                            int img_size, int patch_size, int in_chans, int embed_dim) {
+    return vithip_patch_embed_bf16_reg(stream, images, conv_w16, conv_b, cls, pos, x, patches16, n_images, img_size, patch_size, in_chans,
+                                       embed_dim, 0);
 }
 
 int vithip_patch_embed_bf16_implicit(vithip_stream_t stream, const float *images, const unsigned short *conv_w16, const float *conv_b,

@@ -399,7 +399,7 @@ __global__ __launch_bounds__(PTHREADS) void gemm_bf16_pp_kernel(const Bf16Params
             auto in_range = [&](int blk, int ab) __attribute__((always_inline)) {
                 return (blk >> 1) * 16 + ab * 8 < m_left && (blk & 1) * 32 < n_left;
             };
-            // F32_EMBED (patch embedding): GEMM row m = image * P + patch goes to token row m + image + 1 of x (row 0 of
+            // F32_EMBED (patch embedding): GEMM row m = image * P + patch goes to token row m + (image + 1) * prefix of x (rows 0 .. prefix - 1 of
             // every image is the class token), and the "residual" is pos_emb row patch + 1 (ViT_seq.c:52-101).  Two
             // running (patch, image) cursors, one for the look-ahead loads and one for the stores, advanced by 8 rows at
             // a time -- one division per tile instead of 64 hoisted ones.
@@ -498,8 +498,8 @@ __global__ __launch_bounds__(PTHREADS) void gemm_bf16_pp_kernel(const Bf16Params
                     if constexpr (EPI == VITHIP_BF16_EPI_F32_EMBED) {
                         const RowCursor c1 = step8(scur);
                         const int mrow = mw + (blk >> 1) * 16 + row8;
-                        ca = C + (size_t)(mrow + scur.im + 1) * p.ldc + nw + (blk & 1) * 32 + ch8 * 4;
-                        cb = C + (size_t)(mrow + 8 + c1.im + 1) * p.ldc + nw + (blk & 1) * 32 + ch8 * 4;
+                        ca = C + (size_t)(mrow + (scur.im + 1) * p.prefix) * p.ldc + nw + (blk & 1) * 32 + ch8 * 4;
+                        cb = C + (size_t)(mrow + 8 + (c1.im + 1) * p.prefix) * p.ldc + nw + (blk & 1) * 32 + ch8 * 4;
                         if (blk & 1) scur = step8(c1);
                         asm volatile("" : "+v"(scur.pp), "+v"(scur.im));
                     }

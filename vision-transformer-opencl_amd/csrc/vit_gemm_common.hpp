@@ -61,8 +61,13 @@ int set_tile_grid(Params &p, int bm, int bn, int wgs = 0) {
     return wgs > 0 && wgs < total ? wgs : total;
 }
 
-// vit_gemm.hip: x[img][0][:] = cls + pos[0] for every image of x [n_images][tokens][dim] (the class row of every patch embedding)
-int launch_cls_rows(hipStream_t stream, const float *cls, const float *pos, float *x, int n_images, int tokens, int dim);
+// what the embedding kernels' token-row remap takes: a register count the ABI allows, and token rows of x that are ints
+inline bool embed_rows_ok(int n_images, int patches, int registers) {
+    return registers >= 0 && registers <= VITHIP_MAX_REGISTER_TOKENS && (long long)n_images * (patches + 1 + registers) <= 0x7fffffffLL;
+}
+// vit_gemm.hip: the rows in front of the patch rows of every image of x [n_images][tokens][dim], for every patch embedding:
+// x[img][0][:] = prefix[0] + pos[0] (the class row), x[img][1 + r][:] = prefix[1 + r] for the `registers` register tokens
+int launch_prefix_rows(hipStream_t stream, const float *prefix, const float *pos, float *x, int n_images, int tokens, int registers, int dim);
 
 struct GemmParams {
     const float *A;
@@ -82,6 +87,7 @@ struct GemmParams {
     int patch;       // P
     int img;         // S
     int chans;       // C
+    int prefix;      // rows in front of an image's patch rows in C: 1 (the class token) + the register tokens
     // persistent kernel, helper pieces (vit_gemm_persistent.hip): workspace lent by the caller (NULL: off), piece length
     void *sk_ws;     // device side of the workspace handle: [4 KB of flags and counters][sk_slots x 64 KB]
     int sk_slots;
@@ -675,7 +681,7 @@ __device__ __forceinline__ void epilogue_store(const GemmParams &p, const f32x16
                         const int m = mb + (v & 3) + 8 * (v >> 2);
                         const int im = m / p.patches, pp = m - im * p.patches;
                         add[v] = p.pos[(size_t)(pp + 1) * p.N + n];
-                        orow[v] = (size_t)m + im + 1;
+                        orow[v] = (size_t)(m + (im + 1) * p.prefix);
                     }
 #pragma unroll
                     for (int v = 0; v < 16; ++v) p.C[orow[v] * p.ldc + n] = acc[i][j][v] + bias_r[j] + add[v];
@@ -745,7 +751,7 @@ __device__ __forceinline__ void epilogue_store(const GemmParams &p, const f32x16
                         if constexpr (AMODE == A_PATCHES) {
                             const int im = m / p.patches, pp = m - im * p.patches;
                             y += p.pos[(size_t)(pp + 1) * p.N + n];
-                            p.C[((size_t)m + im + 1) * p.ldc + n] = y;
+                            p.C[(size_t)(m + (im + 1) * p.prefix) * p.ldc + n] = y;
                         } else {
                             if constexpr (GELU) y = gelu_erf(y);
                             if constexpr (QGELU) y = quick_gelu(y);
@@ -771,6 +777,7 @@ struct Bf16Params {
     int tiles_m, tiles_n, group_m;
     unsigned long long *dbg;  // stamped probe build only
     int patches;              // F32_EMBED epilogue: patches per image
+    int prefix;               // F32_EMBED epilogue: rows in front of an image's patch rows in C (1 + register tokens)
     // LayerNorm folded into the GEMMs either side of it (ping-pong kernel only; vithip_gemm_bf16_args has the contract):
     const float *ln_rows;     // consumer (BF16 / BF16_GELU): [M][2] = (rstd, mean * rstd) of every row of A
     const float *ln_colsum;   // consumer: [N] column sums of the gamma-folded weight

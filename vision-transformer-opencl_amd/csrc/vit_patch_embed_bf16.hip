@@ -14,7 +14,8 @@
 //     incrementally), converts them to bf16 and writes 8-byte halves of the 16-byte chunks of a [128][32] bf16 LDS tile;
 //     W: 2 x 16 bytes of the bf16 conv weight.  64-byte rows, chunk position = chunk ^ ((row >> 2) & 3): conflict-free
 //     ds_read_b128 fragment reads;
-//   * epilogue: + bias + pos_emb, row m -> token row m + image + 1 (the class row is written by launch_cls_rows);
+//   * epilogue: + bias + pos_emb, row m -> token row m + image + 1 (the class row is written by launch_prefix_rows with zero
+//     registers: this variant, which the engine does not run, takes no register tokens);
 //   * tile id -> (tm, tn) with tn fastest and the XCD remap: the N tiles that re-read an M tile's pixels share an L2.
 // Measured at batch 2048 (tools/embed_time.py): 2.4 ms against 1.0 ms for the two passes.  With the stages switched off one
 // at a time: MFMA + LDS + barriers 0.49 ms, + W loads 0.53, + pixel loads 1.43, + epilogue 1.05, and three K steps of
@@ -225,7 +226,7 @@ int launch_patch_embed_bf16(hipStream_t s, const float *images, const unsigned s
     q.P = P; q.G = G; q.p = patch_size; q.S = img_size; q.C = in_chans;
     const dim3 grid(set_tile_grid(q, EBM, EBN));
     q.magic_P = (unsigned)((0x100000000ull + (unsigned)P - 1) / (unsigned)P);
-    if (const int e = launch_cls_rows(s, cls, pos, x, n_images, P + 1, embed_dim)) return e;
+    if (const int e = launch_prefix_rows(s, cls, pos, x, n_images, P + 1, 0, embed_dim)) return e;
     hipLaunchKernelGGL(patch_embed_bf16_kernel, grid, dim3(ETHREADS), 0, s, q);
     return static_cast<int>(hipGetLastError());
 }

@@ -36,6 +36,7 @@ struct EmbedParams {
     float *x;
     int M, N, K;           // n * patches, embed_dim, chans * patch * patch
     int patches, grid, patch, img, chans;
+    int prefix;            // rows in front of an image's patch rows in x: 1 + the register tokens
     int tiles_m, tiles_n;
 };
 
@@ -156,7 +157,7 @@ __global__ __launch_bounds__(256, 2) void patch_embed_general_kernel(const Embed
         cur ^= 1;
     }
 
-    // ---- epilogue: + bias, + pos, token-row remap (patch row m of image im is token row m + im + 1) ----
+    // ---- epilogue: + bias, + pos, token-row remap (patch row m of image im is token row m + (im + 1) * prefix) ----
     if (n_lane >= p.N) return;
     // the 16 pos values of an accumulator are fetched (rows past M clamped) before its first store: a load waited for between
     // stores would serialise them on the write latency (vit_gemm_common.hpp, epilogue_store)
@@ -170,7 +171,7 @@ __global__ __launch_bounds__(256, 2) void patch_embed_general_kernel(const Embed
             const int mc = m < p.M ? m : p.M - 1;
             const int im = mc / p.patches, pp = mc - im * p.patches;
             add[v] = p.pos[(size_t)(pp + 1) * p.N + n_lane];
-            orow[v] = (size_t)mc + im + 1;
+            orow[v] = (size_t)(mc + (im + 1) * p.prefix);
         }
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
@@ -186,10 +187,10 @@ bool aligned8(const void *ptr) { return (reinterpret_cast<size_t>(ptr) & 7) == 0
 
 extern "C" {
 
-int vithip_patch_embed_f32_general(vithip_stream_t stream, const float *images, const float *conv_w, const float *conv_b,
-                                   const float *cls, const float *pos, float *x, int n_images, int img_size, int patch_size,
-                                   int in_chans, int embed_dim) {
-    if (!images || !conv_w || !conv_b || !cls || !pos || !x || n_images <= 0) return static_cast<int>(hipErrorInvalidValue);
+int vithip_patch_embed_f32_general_reg(vithip_stream_t stream, const float *images, const float *conv_w, const float *conv_b,
+                                       const float *prefix, const float *pos, float *x, int n_images, int img_size, int patch_size,
+                                       int in_chans, int embed_dim, int num_registers) {
+    if (!images || !conv_w || !conv_b || !prefix || !pos || !x || n_images <= 0) return static_cast<int>(hipErrorInvalidValue);
     if (patch_size < 2 || patch_size % 2 || img_size < patch_size || img_size % 2 || img_size % patch_size)
         return static_cast<int>(hipErrorInvalidValue);
     if (in_chans < 1 || embed_dim < 4 || embed_dim % 4) return static_cast<int>(hipErrorInvalidValue);
@@ -197,17 +198,25 @@ int vithip_patch_embed_f32_general(vithip_stream_t stream, const float *images, 
     if ((unsigned long long)in_chans * img_size * img_size > 0x3fffffffull) return static_cast<int>(hipErrorInvalidValue);
     const int G = img_size / patch_size;
     if ((unsigned long long)n_images * G * G > (1ull << 24)) return static_cast<int>(hipErrorInvalidValue);
+    if (!embed_rows_ok(n_images, G * G, num_registers)) return static_cast<int>(hipErrorInvalidValue);
     if ((unsigned long long)in_chans * patch_size * patch_size > 0x3fffffffull) return static_cast<int>(hipErrorInvalidValue);
     if (!aligned8(images) || !aligned8(conv_w)) return static_cast<int>(hipErrorInvalidValue);
     EmbedParams p{};
     p.images = images; p.conv_w = conv_w; p.conv_b = conv_b; p.pos = pos; p.x = x;
     p.M = n_images * G * G; p.N = embed_dim; p.K = in_chans * patch_size * patch_size;
-    p.patches = G * G; p.grid = G; p.patch = patch_size; p.img = img_size; p.chans = in_chans;
+    p.patches = G * G; p.grid = G; p.patch = patch_size; p.img = img_size; p.chans = in_chans; p.prefix = 1 + num_registers;
     const dim3 grid(set_tile_grid(p, GBM, GBN));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (const int e = launch_cls_rows(s, cls, pos, x, n_images, G * G + 1, embed_dim)) return e;
+    if (const int e = launch_prefix_rows(s, prefix, pos, x, n_images, G * G + 1 + num_registers, num_registers, embed_dim)) return e;
     hipLaunchKernelGGL(patch_embed_general_kernel, grid, dim3(256), 0, s, p);
     return static_cast<int>(hipGetLastError());
+}
+
+int vithip_patch_embed_f32_general(vithip_stream_t stream, const float *images, const float *conv_w, const float *conv_b,
+                                   const float *cls, const float *pos, float *x, int n_images, int img_size, int patch_size,
+                                   int in_chans, int embed_dim) {
+    return vithip_patch_embed_f32_general_reg(stream, images, conv_w, conv_b, cls, pos, x, n_images, img_size, patch_size, in_chans,
+                                              embed_dim, 0);
 }
 
 }  // extern "C"

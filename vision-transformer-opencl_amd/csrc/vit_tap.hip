@@ -87,14 +87,15 @@ __global__ __launch_bounds__(TAP_THREADS) void tap_rows_kernel(const float *__re
 template <int NVEC, bool NORM, bool VEC>
 __global__ __launch_bounds__(map_threads(NVEC)) void tap_map_kernel(const float *__restrict__ x, size_t ldx, float *__restrict__ out,
                                                               size_t out_image_stride, const float *__restrict__ gamma,
-                                                              const float *__restrict__ beta, int tokens, int dim, double eps) {
+                                                              const float *__restrict__ beta, int tokens, int prefix, int dim,
+                                                              double eps) {
     extern __shared__ __attribute__((aligned(16))) float tile[];
     constexpr int NWAVES = map_threads(NVEC) / 64;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tt = map_tile_tokens(dim), ld = dim + MAP_PAD;
-    const int patches = tokens - 1, t0 = blockIdx.y * tt;
+    const int patches = tokens - prefix, t0 = blockIdx.y * tt;
     const int valid = patches - t0 < tt ? patches - t0 : tt;  // tokens of this tile
-    const float *rows = x + ((size_t)blockIdx.x * tokens + 1 + t0) * ldx;
+    const float *rows = x + ((size_t)blockIdx.x * tokens + prefix + t0) * ldx;
     float *dst = out + (size_t)blockIdx.x * out_image_stride + t0;
 
     for (int k = wave; k < valid; k += NWAVES) tap_row<NVEC, NORM>(rows + (size_t)k * ldx, tile + k * ld, gamma, beta, dim, lane, eps);
@@ -124,9 +125,9 @@ __global__ __launch_bounds__(map_threads(NVEC)) void tap_map_kernel(const float 
 
 template <int NVEC, bool NORM>
 int launch_tap(hipStream_t s, const float *x, size_t ldx, float *out, size_t out_image_stride, const float *gamma, const float *beta,
-               int images, int tokens, int dim, int layout, double eps) {
+               int images, int tokens, int prefix, int dim, int layout, double eps) {
     if (layout == VITHIP_TAP_MAP) {
-        const int patches = tokens - 1, tt = map_tile_tokens(dim);
+        const int patches = tokens - prefix, tt = map_tile_tokens(dim);
         const dim3 grid(images, (patches + tt - 1) / tt);
         const size_t lds = (size_t)tt * (dim + MAP_PAD) * sizeof(float);
         int dev = 0;
@@ -141,7 +142,7 @@ int launch_tap(hipStream_t s, const float *x, size_t ldx, float *out, size_t out
                 attr_set.set(dev);
             }
             hipLaunchKernelGGL((tap_map_kernel<NVEC, NORM, true>), grid, dim3(map_threads(NVEC)), lds, s, x, ldx, out, out_image_stride, gamma,
-                               beta, tokens, dim, eps);
+                               beta, tokens, prefix, dim, eps);
         } else {
             static vitdev::PerDeviceOnce attr_set;
             if (!attr_set.is_done(dev)) {
@@ -151,11 +152,11 @@ int launch_tap(hipStream_t s, const float *x, size_t ldx, float *out, size_t out
                 attr_set.set(dev);
             }
             hipLaunchKernelGGL((tap_map_kernel<NVEC, NORM, false>), grid, dim3(map_threads(NVEC)), lds, s, x, ldx, out, out_image_stride, gamma,
-                               beta, tokens, dim, eps);
+                               beta, tokens, prefix, dim, eps);
         }
         return static_cast<int>(hipGetLastError());
     }
-    const int first_tok = layout == VITHIP_TAP_PATCHES ? 1 : 0;
+    const int first_tok = layout == VITHIP_TAP_PATCHES ? prefix : 0;
     const int per_image = layout == VITHIP_TAP_CLS ? 1 : tokens - first_tok;
     const int rows = images * per_image;
     hipLaunchKernelGGL((tap_rows_kernel<NVEC, NORM>), dim3(vit_row::grid_for_rows(rows)), dim3(TAP_THREADS), 0, s, x, ldx, out,
@@ -165,25 +166,32 @@ int launch_tap(hipStream_t s, const float *x, size_t ldx, float *out, size_t out
 
 }  // namespace
 
-extern "C" int vithip_tap_f32_eps(vithip_stream_t stream, const float *x, size_t ldx, float *out, size_t out_image_stride, const float *gamma,
-                                  const float *beta, int images, int tokens, int dim, int layout, double eps) {
+// prefix: the rows in front of an image's patch rows (the class token, then a register model's register tokens)
+extern "C" int vithip_tap_f32_prefix_eps(vithip_stream_t stream, const float *x, size_t ldx, float *out, size_t out_image_stride,
+                                         const float *gamma, const float *beta, int images, int tokens, int prefix, int dim, int layout,
+                                         double eps) {
     const int bad = static_cast<int>(hipErrorInvalidValue);
+    const bool patch_rows = layout == VITHIP_TAP_PATCHES || layout == VITHIP_TAP_MAP;
     if (!x || !out || !gamma != !beta || images <= 0 || tokens <= 0 || dim <= 0 || !(eps > 0.0) || !(eps < 1.0e300)) return bad;
     if (layout != VITHIP_TAP_CLS && layout != VITHIP_TAP_TOKENS && layout != VITHIP_TAP_PATCHES && layout != VITHIP_TAP_MAP) return bad;
-    if ((layout == VITHIP_TAP_PATCHES || layout == VITHIP_TAP_MAP) && tokens < 2) return bad;
+    if (prefix < 1 || prefix > tokens || (patch_rows && prefix == tokens)) return bad;
     if (!vit_row::rows_ok(x, ldx, dim)) return bad;
     if ((long long)images * tokens > 0x7fffffffLL) return bad;                                     // row numbers are ints
-    if (layout == VITHIP_TAP_MAP && (tokens - 1 + 15) / 16 > 65535) return bad;      // MAP: token tiles in grid.y
-    const size_t per_image = layout == VITHIP_TAP_CLS ? 1 : layout == VITHIP_TAP_TOKENS ? (size_t)tokens : (size_t)tokens - 1;
+    if (layout == VITHIP_TAP_MAP && (tokens - prefix + 15) / 16 > 65535) return bad;      // MAP: token tiles in grid.y
+    const size_t per_image = layout == VITHIP_TAP_CLS ? 1 : layout == VITHIP_TAP_TOKENS ? (size_t)tokens : (size_t)(tokens - prefix);
     // out is not a matrix of rows with one leading dimension: an image's rows are dense, its stride covers them
     if (!vit_row::aligned16(out) || out_image_stride % 4 || out_image_stride < per_image * (size_t)dim) return bad;
     if (!vit_row::aligned16(gamma) || !vit_row::aligned16(beta)) return bad;
     hipStream_t s = static_cast<hipStream_t>(stream);
     return vit_row::dispatch_nvec(dim, [&](auto nvec) {
         constexpr int NVEC = decltype(nvec)::value;
-        return gamma ? launch_tap<NVEC, true>(s, x, ldx, out, out_image_stride, gamma, beta, images, tokens, dim, layout, eps)
-                     : launch_tap<NVEC, false>(s, x, ldx, out, out_image_stride, gamma, beta, images, tokens, dim, layout, eps);
+        return gamma ? launch_tap<NVEC, true>(s, x, ldx, out, out_image_stride, gamma, beta, images, tokens, prefix, dim, layout, eps)
+                     : launch_tap<NVEC, false>(s, x, ldx, out, out_image_stride, gamma, beta, images, tokens, prefix, dim, layout, eps);
     });
+}
+extern "C" int vithip_tap_f32_eps(vithip_stream_t stream, const float *x, size_t ldx, float *out, size_t out_image_stride, const float *gamma,
+                                  const float *beta, int images, int tokens, int dim, int layout, double eps) {
+    return vithip_tap_f32_prefix_eps(stream, x, ldx, out, out_image_stride, gamma, beta, images, tokens, 1, dim, layout, eps);
 }
 extern "C" int vithip_tap_f32(vithip_stream_t stream, const float *x, size_t ldx, float *out, size_t out_image_stride, const float *gamma,
                               const float *beta, int images, int tokens, int dim, int layout) {

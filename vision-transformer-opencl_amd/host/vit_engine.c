@@ -102,7 +102,8 @@ typedef struct { vit_dense_head_spec spec; float *W, *bias, *zero_bias, *rows, *
 struct vit_engine {
     vit_config cfg;
     vit_engine_options opt;
-    int tokens;
+    int tokens;                  /* T = prefix + patches rows per image: class token, register tokens, patch tokens */
+    int prefix, patches;         /* 1 + VIT_REGISTER_TOKENS: the row of the first patch token; vit_config_patches */
     int n_weights;
     char err[512];
 
@@ -195,19 +196,22 @@ vit_config vit_config_b16(void) {
     return c;
 }
 
-int vit_config_tokens(const vit_config *cfg) {
-    int g = cfg->img_size / cfg->patch_size;
-    return g * g + 1;
+int vit_config_patches(const vit_config *cfg) {
+    int g = cfg->img_size / VIT_PATCH_SIZE(cfg);
+    return g * g;
 }
+
+/* class token, register tokens, patch tokens: the order of the rows */
+int vit_config_tokens(const vit_config *cfg) { return 1 + VIT_REGISTER_TOKENS(cfg) + vit_config_patches(cfg); }
 
 size_t vit_config_weight_size(const vit_config *cfg, int index) {
     const size_t D = (size_t)cfg->embed_dim, H = (size_t)VIT_HIDDEN_DIM(cfg), H1 = (size_t)VIT_FC1_ROWS(cfg);
-    const size_t T = (size_t)vit_config_tokens(cfg);
-    const size_t PK = (size_t)cfg->in_chans * cfg->patch_size * cfg->patch_size;
+    const size_t P = (size_t)vit_config_patches(cfg), R = (size_t)VIT_REGISTER_TOKENS(cfg);
+    const size_t PK = (size_t)cfg->in_chans * VIT_PATCH_SIZE(cfg) * VIT_PATCH_SIZE(cfg);
     const int base = 4 + VIT_WEIGHTS_PER_LAYER * cfg->depth;
     if (index < 0 || index >= base + 4) return 0;
     if (index < 4) {
-        const size_t s[4] = {D, D * PK, D, T * D};
+        const size_t s[4] = {(1 + R) * D, D * PK, D, (P + 1) * D}; /* the prefix rows; registers take no position embedding */
         return s[index];
     }
     if (index >= base) {
@@ -224,9 +228,9 @@ size_t vit_config_weight_size(const vit_config *cfg, int index) {
 unsigned long long vit_config_macs_per_image(const vit_config *cfg) {
     const unsigned long long T = (unsigned long long)vit_config_tokens(cfg), D = cfg->embed_dim,
                              H = VIT_HIDDEN_DIM(cfg), H1 = (unsigned long long)VIT_FC1_ROWS(cfg), hd = D / cfg->num_heads,
-                             PK = (unsigned long long)cfg->in_chans * cfg->patch_size * cfg->patch_size;
+                             PK = (unsigned long long)cfg->in_chans * VIT_PATCH_SIZE(cfg) * VIT_PATCH_SIZE(cfg);
     const unsigned long long layer = T * D * 3 * D + 2 * cfg->num_heads * T * T * hd + T * D * D + T * D * H1 + T * H * D;
-    return (T - 1) * PK * D + cfg->depth * layer + D * cfg->num_classes;
+    return (unsigned long long)vit_config_patches(cfg) * PK * D + cfg->depth * layer + D * cfg->num_classes;
 }
 
 unsigned long long vit_config_macs_per_image_pruned(const vit_config *cfg) {
@@ -275,21 +279,24 @@ const vit_config *vit_engine_config(const vit_engine *e) { return &e->cfg; }
 
 static int check_config(vit_engine *e) {
     const vit_config *c = &e->cfg;
-    if (c->img_size <= 0 || c->patch_size <= 0 || c->in_chans <= 0 || c->num_classes <= 0 ||
+    if (c->img_size <= 0 || c->patch_size <= 0 || VIT_PATCH_SIZE(c) == 0 || c->in_chans <= 0 || c->num_classes <= 0 ||
         c->embed_dim <= 0 || c->depth <= 0 || c->num_heads <= 0 || c->hidden_dim <= 0 || VIT_HIDDEN_DIM(c) == 0)
         return fail(e, VIT_ERR_ARG, "vit_config: all dimensions must be positive");
     if (VIT_MLP_KIND(c) != VIT_MLP_GELU && VIT_MLP_KIND(c) != VIT_MLP_SWIGLU && VIT_MLP_KIND(c) != VIT_MLP_QUICKGELU)
         return fail(e, VIT_ERR_ARG, "vit_config.hidden_dim: MLP kind %d (VIT_MLP_KIND, bits 24..30): VIT_MLP_GELU (%d), VIT_MLP_SWIGLU (%d) or VIT_MLP_QUICKGELU (%d)",
                     VIT_MLP_KIND(c), VIT_MLP_GELU, VIT_MLP_SWIGLU, VIT_MLP_QUICKGELU);
-    if (c->img_size % c->patch_size) return fail(e, VIT_ERR_ARG, "img_size must be a multiple of patch_size");
+    if (VIT_REGISTER_TOKENS(c) > VIT_MAX_REGISTER_TOKENS)
+        return fail(e, VIT_ERR_ARG, "vit_config.patch_size: %d register tokens (VIT_REGISTER_TOKENS, bits 24..30): 0..%d", VIT_REGISTER_TOKENS(c),
+                    VIT_MAX_REGISTER_TOKENS);
+    if (c->img_size % VIT_PATCH_SIZE(c)) return fail(e, VIT_ERR_ARG, "img_size must be a multiple of patch_size");
     if (c->embed_dim % c->num_heads || vithip_qscale(c->embed_dim / c->num_heads) == 0.0f) /* what the attention kernels take */
         return fail(e, VIT_ERR_ARG, "HIP attention kernels need head_dim 64 or a multiple of 8 from 72 to 128 (got %d/%d)", c->embed_dim,
                     c->num_heads);
     if (c->embed_dim % 32 || VIT_HIDDEN_DIM(c) % 32)
         return fail(e, VIT_ERR_ARG, "embed_dim and hidden_dim must be multiples of 32");
     /* what vithip_patch_embed_f32 takes: the 16-byte gather or, for every other even geometry (patch 14), the general kernel */
-    if (c->patch_size % 2 || c->img_size % 2)
-        return fail(e, VIT_ERR_ARG, "patch geometry unsupported: patch_size %d and img_size %d must both be even", c->patch_size,
+    if (VIT_PATCH_SIZE(c) % 2 || c->img_size % 2)
+        return fail(e, VIT_ERR_ARG, "patch geometry unsupported: patch_size %d and img_size %d must both be even", VIT_PATCH_SIZE(c),
                     c->img_size);
     if (c->embed_dim > 2048) return fail(e, VIT_ERR_ARG, "embed_dim > 2048 unsupported by the LayerNorm kernel");
     return VIT_OK;
@@ -318,6 +325,8 @@ int vit_engine_create(vit_engine **out, const vit_config *cfg, const vit_engine_
     int rc = check_config(e);
     if (rc) return rc;
     e->tokens = vit_config_tokens(&e->cfg);
+    e->patches = vit_config_patches(&e->cfg);
+    e->prefix = e->tokens - e->patches;
     e->n_weights = VIT_WEIGHT_COUNT(e->cfg.depth);
     {
         /* The fp32 GEMMs (and the patch gather) address an A operand through a buffer descriptor with 32-bit byte
@@ -680,7 +689,7 @@ static int load_image(vit_engine *e, const vit_weight_image *img, const float *d
     if (bf16 && !img->bf16_elems) /* image without a bf16 section: convert the GEMM-operand region on the device, one launch */
         HIP_TRY(e, vithip_f32_to_bf16(e->stream, e->wblob, e->wblob16, img->gemm_floats));
     if (d_pos_src) /* fp32 only: the position embedding is no GEMM operand and has no bf16 copy */
-        HIP_TRY(e, vithip_pos_resample_f32(e->stream, d_pos_src, g_src, e->w[W_POS], e->cfg.img_size / e->cfg.patch_size, e->cfg.embed_dim, mode));
+        HIP_TRY(e, vithip_pos_resample_f32(e->stream, d_pos_src, g_src, e->w[W_POS], e->cfg.img_size / VIT_PATCH_SIZE(&e->cfg), e->cfg.embed_dim, mode));
     return finish_install(e);
 }
 
@@ -724,10 +733,11 @@ int vit_engine_load_weights_resampled(vit_engine *e, const Network *weights, int
     if (!rs) return fail(e, VIT_ERR_ARG, "load_weights_resampled: null vit_pos_resample");
     if (rs->reserved != 0) return fail(e, VIT_ERR_ARG, "load_weights_resampled: reserved must be 0 (got %d)", rs->reserved);
     if (!pos_mode_ok(rs->mode)) return fail(e, VIT_ERR_ARG, "load_weights_resampled: unknown mode %d", rs->mode);
-    if (rs->src_img_size <= 0 || rs->src_img_size % e->cfg.patch_size)
+    const int patch = VIT_PATCH_SIZE(&e->cfg);
+    if (rs->src_img_size <= 0 || rs->src_img_size % patch)
         return fail(e, VIT_ERR_ARG, "load_weights_resampled: src_img_size %d is not a positive multiple of patch_size %d", rs->src_img_size,
-                    e->cfg.patch_size);
-    const int g_src = rs->src_img_size / e->cfg.patch_size, g_dst = e->cfg.img_size / e->cfg.patch_size;
+                    patch);
+    const int g_src = rs->src_img_size / patch, g_dst = e->cfg.img_size / patch;
     if (!pos_grid_ok(g_src) || !pos_grid_ok(g_dst))
         return fail(e, VIT_ERR_ARG, "load_weights_resampled: grids of %d and %d patches per side, the resampling takes 1..256", g_src, g_dst);
     const size_t D = (size_t)e->cfg.embed_dim, pos_src = ((size_t)g_src * g_src + 1) * D, pos_dst = ((size_t)g_dst * g_dst + 1) * D;
@@ -761,7 +771,7 @@ int vit_engine_load_weights_resampled(vit_engine *e, const Network *weights, int
  * in-process form of "upload to GPU 0 + broadcast").  Equal grids: ONE peer copy of the whole blob.  Otherwise the
  * two layouts differ behind the position embedding only, which is staged on dst's device and resampled into dst's own. */
 static int replicate_weights(vit_engine *dst, vit_engine *src, int mode) {
-    const int g_src = src->cfg.img_size / src->cfg.patch_size, g_dst = dst->cfg.img_size / dst->cfg.patch_size, same = g_src == g_dst;
+    const int g_src = src->cfg.img_size / VIT_PATCH_SIZE(&src->cfg), g_dst = dst->cfg.img_size / VIT_PATCH_SIZE(&dst->cfg), same = g_src == g_dst;
     if (!same && (!pos_grid_ok(g_src) || !pos_grid_ok(g_dst)))
         return fail(dst, VIT_ERR_ARG, "copy_weights_resampled: grids of %d and %d patches per side, the resampling takes 1..256", g_src, g_dst);
     const size_t n = (size_t)dst->n_weights;
@@ -992,8 +1002,8 @@ static int stage_embed(chunk_ctx *c, const void *d_images, const vit_input *in, 
     const size_t img = (size_t)cfg->in_chans * cfg->img_size * cfg->img_size;
     /* bf16 patch embedding needs K = chans*patch^2 to be a multiple of 64 (two K steps at least) and patch % 8 == 0;
      * its bf16 patch rows live in the (still unused) hidden-layer buffer */
-    const int pk = cfg->in_chans * cfg->patch_size * cfg->patch_size;
-    const int embed16 = e->opt.dtype == VIT_DTYPE_BF16 && pk % 64 == 0 && pk >= 128 && cfg->patch_size % 8 == 0 &&
+    const int patch = VIT_PATCH_SIZE(cfg), regs = e->prefix - 1, pk = cfg->in_chans * patch * patch;
+    const int embed16 = e->opt.dtype == VIT_DTYPE_BF16 && pk % 64 == 0 && pk >= 128 && patch % 8 == 0 &&
                         (size_t)pk <= 2 * (size_t)c->H;
     for (int j = 0; j < c->L; ++j) {
         const vit_lane *ln = &c->lane[j];
@@ -1011,12 +1021,12 @@ static int stage_embed(chunk_ctx *c, const void *d_images, const vit_input *in, 
         }
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_EMBED));
         if (embed16)
-            HIP_TRY(e, vithip_patch_embed_bf16(ln->s, images, w->conv_w16, w->conv_b, w->cls, w->pos, ln->x,
-                                               (unsigned short *)e->hbuf + (size_t)ln->off * (c->T - 1) * pk,
-                                               ln->n, cfg->img_size, cfg->patch_size, cfg->in_chans, c->D));
+            HIP_TRY(e, vithip_patch_embed_bf16_reg(ln->s, images, w->conv_w16, w->conv_b, w->cls, w->pos, ln->x,
+                                                   (unsigned short *)e->hbuf + (size_t)ln->off * (size_t)e->patches * pk,
+                                                   ln->n, cfg->img_size, patch, cfg->in_chans, c->D, regs));
         else
-            HIP_TRY(e, vithip_patch_embed_f32(ln->s, images, w->conv_w, w->conv_b, w->cls, w->pos, ln->x, ln->n,
-                                              cfg->img_size, cfg->patch_size, cfg->in_chans, c->D));
+            HIP_TRY(e, vithip_patch_embed_f32_reg(ln->s, images, w->conv_w, w->conv_b, w->cls, w->pos, ln->x, ln->n,
+                                                  cfg->img_size, patch, cfg->in_chans, c->D, regs));
         HIP_TRY(e, stage_end(e, ln->s));
     }
     return VIT_OK;
@@ -1168,7 +1178,7 @@ static int class_block(chunk_ctx *c, const vit_lane *ln, float *dst, size_t ld) 
  * streams and the others may still be in their last layer, reading their y and (fold) the bf16 copy of x in y's upper half.  The
  * scratch is one [D] fp32 row per 16 tokens, at most n * T * D * 2 bytes for every T >= 2; checked by pooled_block all the same. */
 static float *pool_scratch(const chunk_ctx *c, const vit_lane *ln, size_t *bytes) {
-    *bytes = vithip_layernorm_pool_f32_workspace_floats(ln->n, c->T, 1, c->D) * sizeof(float);
+    *bytes = vithip_layernorm_pool_f32_workspace_floats(ln->n, c->T, c->e->prefix, c->D) * sizeof(float);
     return (float *)ln->y;
 }
 
@@ -1181,16 +1191,16 @@ static int pooled_block(chunk_ctx *c, const vit_lane *ln, float *dst, size_t ld,
     float *scratch = pool_scratch(c, ln, &need);
     if (need == 0 || need > own || ((size_t)scratch & 15))
         return fail(e, VIT_ERR_STATE, "%s: the pooling scratch (%zu bytes) does not fit the lane's own %zu bytes of y", who, need, own);
-    if (fcnorm) HIP_TRY(e, vithip_pool_layernorm_f32_eps(ln->s, ln->x, D, dst, ld, e->final.ln_g, e->final.ln_b, ln->n, c->T, 1, c->D, scratch, e->ln_eps));
-    else HIP_TRY(e, vithip_layernorm_pool_f32_eps(ln->s, ln->x, D, dst, ld, e->final.ln_g, e->final.ln_b, ln->n, c->T, 1, c->D, l2, scratch, e->ln_eps));
+    if (fcnorm) HIP_TRY(e, vithip_pool_layernorm_f32_eps(ln->s, ln->x, D, dst, ld, e->final.ln_g, e->final.ln_b, ln->n, c->T, e->prefix, c->D, scratch, e->ln_eps));
+    else HIP_TRY(e, vithip_layernorm_pool_f32_eps(ln->s, ln->x, D, dst, ld, e->final.ln_g, e->final.ln_b, ln->n, c->T, e->prefix, c->D, l2, scratch, e->ln_eps));
     return VIT_OK;
 }
 
 /* tap_block: the rows `kind` (VITHIP_TAP_*) names of x as the layer in front has just left it; norm: through the final LayerNorm */
 static int tap_block(chunk_ctx *c, const vit_lane *ln, float *dst, size_t ld, int norm, int kind) {
     const vit_final_ops *f = &c->e->final;
-    HIP_TRY(c->e, vithip_tap_f32_eps(ln->s, ln->x, (size_t)c->D, dst, ld, norm ? f->ln_g : NULL, norm ? f->ln_b : NULL, ln->n, c->T, c->D, kind,
-                                     c->e->ln_eps));
+    HIP_TRY(c->e, vithip_tap_f32_prefix_eps(ln->s, ln->x, (size_t)c->D, dst, ld, norm ? f->ln_g : NULL, norm ? f->ln_b : NULL, ln->n, c->T,
+                                            c->e->prefix, c->D, kind, c->e->ln_eps));
     return VIT_OK;
 }
 
@@ -1287,8 +1297,7 @@ static int stage_cls_attention(chunk_ctx *c, const vit_output *out) {
 
 /* floats of one tapped layer's block of an intermediate row; `kind` is the VIT_TAP_* of a valid spec */
 static size_t tap_block_elems(const vit_engine *e, int kind) {
-    const size_t T = (size_t)e->tokens;
-    return (kind == VIT_TAP_CLS ? 1 : kind == VIT_TAP_TOKENS ? T : T - 1) * (size_t)e->cfg.embed_dim;
+    return (kind == VIT_TAP_CLS ? 1 : kind == VIT_TAP_TOKENS ? (size_t)e->tokens : (size_t)e->patches) * (size_t)e->cfg.embed_dim;
 }
 
 /* An intermediate call behind encoder layer l = layers[j] (any other layer: nothing) -- block j of its rows: the residual stream as
@@ -1316,7 +1325,7 @@ static int stage_tap(chunk_ctx *c, const vit_output *out, int l) {
 static int stage_dense_tap(chunk_ctx *c, const vit_output *out, int l) {
     vit_engine *e = c->e;
     const vit_dense_head *h = &e->dense;
-    const size_t P = (size_t)c->T - 1, D = (size_t)c->D;
+    const size_t P = (size_t)e->patches, D = (size_t)c->D;
     const int NC = h->spec.num_classes, K = h->spec.num_layers;
     int j = 0;
     (void)out;
@@ -1344,8 +1353,8 @@ static int stage_dense_tap(chunk_ctx *c, const vit_output *out, int l) {
 static int stage_dense_out(chunk_ctx *c, const vit_output *out) {
     vit_engine *e = c->e;
     const vit_dense_head *h = &e->dense;
-    const int g = e->cfg.img_size / e->cfg.patch_size, NC = h->spec.num_classes;
-    const size_t P = (size_t)c->T - 1, row = c->row;
+    const int g = e->cfg.img_size / VIT_PATCH_SIZE(&e->cfg), NC = h->spec.num_classes;
+    const size_t P = (size_t)e->patches, row = c->row;
     for (int k = 0; k < c->L; ++k) {
         const vit_lane *ln = &c->lane[k];
         const float *logits = h->logits + (size_t)ln->off * P * NC;
@@ -1418,7 +1427,7 @@ static const char *features_check(const vit_engine *e, const void *caller, vit_o
     arg[0] = spec->l2_normalize;
     if (spec->l2_normalize != 0 && spec->l2_normalize != 1) return "%s: l2_normalize must be 0 or 1 (got %d)";
     if (spec->l2_normalize && spec->kind == VIT_FEAT_TOKENS) return "%s: l2_normalize applies to the CLS, MEAN and HEAD rows, not to TOKENS";
-    if (spec->kind == VIT_FEAT_MEAN && e->tokens < 2) return "%s: MEAN needs at least one patch token";
+    if (spec->kind == VIT_FEAT_MEAN && e->patches < 1) return "%s: MEAN needs at least one patch token";
     out->spec.kind = spec->kind; out->spec.l2_normalize = spec->l2_normalize;
     return NULL;
 }
@@ -1463,10 +1472,10 @@ static const char *intermediate_check(const vit_engine *e, const void *caller, v
         if (spec->layers[j] < 0 || spec->layers[j] >= e->cfg.depth) return "%s: layers[%d] = %d is not a layer of the model";
         if (j && spec->layers[j] <= spec->layers[j - 1]) return "%s: layers[%d] = %d is not above the entry before it (strictly increasing)";
     }
-    const int g = e->cfg.img_size / e->cfg.patch_size;
-    arg[0] = g; arg[1] = e->tokens - 1;
-    if (spec->kind == VIT_TAP_MAP && (g < 1 || g * g != e->tokens - 1)) return "%s: MAP needs a square grid of patches: (img_size / patch_size = %d)^2 is not the model's %d";
-    if (spec->kind == VIT_TAP_PATCHES && e->tokens < 2) return "%s: PATCHES needs at least one patch token";
+    const int g = e->cfg.img_size / VIT_PATCH_SIZE(&e->cfg);
+    arg[0] = g; arg[1] = e->patches;
+    if (spec->kind == VIT_TAP_MAP && (g < 1 || g * g != e->patches)) return "%s: MAP needs a square grid of patches: (img_size / patch_size = %d)^2 is not the model's %d";
+    if (spec->kind == VIT_TAP_PATCHES && e->patches < 1) return "%s: PATCHES needs at least one patch token";
     out->tap.kind = spec->kind; out->tap.norm = spec->norm; out->tap.num_layers = spec->num_layers;
     for (int j = 0; j < spec->num_layers; ++j) out->tap.layers[j] = spec->layers[j]; /* the unused entries stay zero: the graph key compares the whole spec */
     return NULL;
@@ -1524,7 +1533,7 @@ static const char *dense_check(const vit_engine *e, const void *caller, vit_outp
 /* labels are a byte per pixel, the grid classes * P floats: the one kind whose row is not a whole number of floats */
 static size_t dense_row_bytes(const vit_engine *e, const vit_output *out) {
     if (out->dense.kind == VIT_DENSE_LABELS) return (size_t)out->dense.out_h * (size_t)out->dense.out_w;
-    return (size_t)e->dense.spec.num_classes * (size_t)(e->tokens - 1) * sizeof(float);
+    return (size_t)e->dense.spec.num_classes * (size_t)e->patches * sizeof(float);
 }
 static int dense_last_layer(const vit_engine *e, const vit_output *out) { /* the deepest layer of the head */
     (void)out;
@@ -2331,7 +2340,7 @@ static const char *head_spec_fault(const vit_engine *e, const vit_head_spec *spe
         if (j && spec->cls_layers[j] <= spec->cls_layers[j - 1]) return "set_head: cls_layers[%d] = %d is not above the entry before it (strictly increasing)";
     }
     if (spec->num_cls_layers == 0 && spec->pool == VIT_HEAD_POOL_NONE) return "set_head: the operand is empty (no class layers and no pooled block)";
-    if (spec->pool != VIT_HEAD_POOL_NONE && e->tokens < 2) return "set_head: a pooled block needs at least one patch token";
+    if (spec->pool != VIT_HEAD_POOL_NONE && e->patches < 1) return "set_head: a pooled block needs at least one patch token";
     return NULL;
 }
 
@@ -2414,9 +2423,9 @@ static const char *dense_head_spec_fault(const vit_engine *e, const vit_dense_he
         if (spec->layers[j] < 0 || spec->layers[j] >= e->cfg.depth) return "set_dense_head: layers[%d] = %d is not a layer of the model";
         if (j && spec->layers[j] <= spec->layers[j - 1]) return "set_dense_head: layers[%d] = %d is not above the entry before it (strictly increasing)";
     }
-    const int g = e->cfg.img_size / e->cfg.patch_size;
-    arg[0] = g; arg[1] = e->tokens - 1;
-    if (g < 1 || g * g != e->tokens - 1) return "set_dense_head: needs a square grid of patches: (img_size / patch_size = %d)^2 is not the model's %d";
+    const int g = e->cfg.img_size / VIT_PATCH_SIZE(&e->cfg);
+    arg[0] = g; arg[1] = e->patches;
+    if (g < 1 || g * g != e->patches) return "set_dense_head: needs a square grid of patches: (img_size / patch_size = %d)^2 is not the model's %d";
     return NULL;
 }
 
@@ -2439,7 +2448,7 @@ int vit_engine_set_dense_head(vit_engine *e, const vit_dense_head_spec *spec, co
     }
     /* the new head first, whole; only then the old one goes */
     const size_t D = (size_t)e->cfg.embed_dim, F = (size_t)spec->num_layers * D, NC = (size_t)spec->num_classes,
-                 B = (size_t)e->opt.max_batch, P = (size_t)e->tokens - 1;
+                 B = (size_t)e->opt.max_batch, P = (size_t)e->patches;
     const size_t wbytes = NC * F * sizeof(float);
     const size_t pad = 128 * F * sizeof(float) > WEIGHT_TAIL_PAD ? 128 * F * sizeof(float) : WEIGHT_TAIL_PAD; /* a GEMM tile of rows */
     vit_dense_head h;

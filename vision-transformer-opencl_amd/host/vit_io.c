@@ -307,10 +307,10 @@ static void synth_range(const vit_config *cfg, int idx, float *lo, float *hi) {
 
 static size_t synth_weight_size(const vit_config *cfg, int idx) {
     const size_t D = (size_t)cfg->embed_dim, H = (size_t)VIT_HIDDEN_DIM(cfg), H1 = (size_t)VIT_FC1_ROWS(cfg);
-    const size_t G = (size_t)(cfg->img_size / cfg->patch_size), T = G * G + 1;
-    const size_t PK = (size_t)cfg->in_chans * cfg->patch_size * cfg->patch_size;
+    const size_t G = (size_t)(cfg->img_size / VIT_PATCH_SIZE(cfg)), P = G * G, R = (size_t)VIT_REGISTER_TOKENS(cfg);
+    const size_t PK = (size_t)cfg->in_chans * VIT_PATCH_SIZE(cfg) * VIT_PATCH_SIZE(cfg);
     const int base = 4 + VIT_WEIGHTS_PER_LAYER * cfg->depth;
-    if (idx < 4) { const size_t s[4] = {D, D * PK, D, T * D}; return s[idx]; }
+    if (idx < 4) { const size_t s[4] = {(1 + R) * D, D * PK, D, (P + 1) * D}; return s[idx]; } /* the prefix rows; registers have no position embedding */
     if (idx >= base) { const size_t s[4] = {D, D, (size_t)cfg->num_classes * D, (size_t)cfg->num_classes}; return s[idx - base]; }
     { const size_t s[12] = {D, D, 3 * D * D, 3 * D, D * D, D, D, D, H1 * D, H1, D * H, D}; return s[(idx - 4) % VIT_WEIGHTS_PER_LAYER]; }
 }
@@ -340,7 +340,7 @@ static int all_finite(const float *v, size_t n) {
 
 int vit_weights_fold_layer_scale(const vit_config *cfg, Network weights[], int count, const Network scales[], int scale_count) {
     if (!cfg || !weights || !scales) return -1;
-    if (cfg->depth <= 0 || cfg->embed_dim <= 0 || cfg->hidden_dim <= 0 || VIT_HIDDEN_DIM(cfg) == 0 || cfg->patch_size <= 0 || cfg->img_size <= 0 ||
+    if (cfg->depth <= 0 || cfg->embed_dim <= 0 || cfg->hidden_dim <= 0 || VIT_HIDDEN_DIM(cfg) == 0 || cfg->patch_size <= 0 || VIT_PATCH_SIZE(cfg) == 0 || cfg->img_size <= 0 ||
         cfg->in_chans <= 0 || cfg->num_classes <= 0)
         return -1;
     if (count != VIT_WEIGHT_COUNT(cfg->depth) || scale_count != 2 * cfg->depth) return -1;

@@ -22,10 +22,16 @@
  * word as a width. */
 #define VITW_VERSION_GELU 2u
 #define VITW_VERSION_SWIGLU 3u /* every non-zero kind: VIT_MLP_QUICKGELU too, told from SwiGLU by the kind bits of that eighth word, which a load compares */
-static int mlp_ok(const vit_config *cfg) {
-    return VIT_MLP_KIND(cfg) == VIT_MLP_GELU || VIT_MLP_KIND(cfg) == VIT_MLP_SWIGLU || VIT_MLP_KIND(cfg) == VIT_MLP_QUICKGELU;
+/* A model with register tokens (VIT_REGISTER_TOKENS, the top bits of the second configuration word) writes version 3 too, whatever its
+ * MLP: a reader from before they existed that takes version 3 compares that word with a plain patch size and refuses; files of models
+ * without registers are byte for byte what they were.  A load compares the word, so a file loads under its own count only. */
+static int mlp_ok(const vit_config *cfg) { /* the packed fields hold what the engine takes */
+    return (VIT_MLP_KIND(cfg) == VIT_MLP_GELU || VIT_MLP_KIND(cfg) == VIT_MLP_SWIGLU || VIT_MLP_KIND(cfg) == VIT_MLP_QUICKGELU) &&
+           cfg->patch_size > 0 && VIT_PATCH_SIZE(cfg) > 0 && VIT_REGISTER_TOKENS(cfg) <= VIT_MAX_REGISTER_TOKENS;
 }
-static uint32_t vitw_version(const vit_config *cfg) { return VIT_MLP_KIND(cfg) != VIT_MLP_GELU ? VITW_VERSION_SWIGLU : VITW_VERSION_GELU; }
+static uint32_t vitw_version(const vit_config *cfg) {
+    return VIT_MLP_KIND(cfg) != VIT_MLP_GELU || VIT_REGISTER_TOKENS(cfg) != 0 ? VITW_VERSION_SWIGLU : VITW_VERSION_GELU;
+}
 #define SLOT 128u              /* floats: 512-B fp32 slots = 256-B bf16 slots */
 #define PAYLOAD_ALIGN 4096u
 
@@ -33,10 +39,10 @@ static uint32_t vitw_version(const vit_config *cfg) { return VIT_MLP_KIND(cfg) !
 
 static size_t expect_size(const vit_config *cfg, int idx) {
     const size_t D = (size_t)cfg->embed_dim, H = (size_t)VIT_HIDDEN_DIM(cfg), H1 = (size_t)VIT_FC1_ROWS(cfg);
-    const size_t G = (size_t)(cfg->img_size / cfg->patch_size), T = G * G + 1;
-    const size_t PK = (size_t)cfg->in_chans * cfg->patch_size * cfg->patch_size;
+    const size_t G = (size_t)(cfg->img_size / VIT_PATCH_SIZE(cfg)), P = G * G, R = (size_t)VIT_REGISTER_TOKENS(cfg);
+    const size_t PK = (size_t)cfg->in_chans * VIT_PATCH_SIZE(cfg) * VIT_PATCH_SIZE(cfg);
     const int base = 4 + VIT_WEIGHTS_PER_LAYER * cfg->depth;
-    if (idx < 4) { const size_t s[4] = {D, D * PK, D, T * D}; return s[idx]; }
+    if (idx < 4) { const size_t s[4] = {(1 + R) * D, D * PK, D, (P + 1) * D}; return s[idx]; } /* the prefix rows; registers have no position embedding */
     if (idx >= base) { const size_t s[4] = {D, D, (size_t)cfg->num_classes * D, (size_t)cfg->num_classes}; return s[idx - base]; }
     { const size_t s[12] = {D, D, 3 * D * D, 3 * D, D * D, D, D, D, H1 * D, H1, D * H, D}; return s[(idx - 4) % VIT_WEIGHTS_PER_LAYER]; }
 }

@@ -58,13 +58,17 @@ MLP_KINDS = {"gelu": 0, "swiglu": 1}  # VIT_MLP_GELU, VIT_MLP_SWIGLU: the kinds 
 MLP_ACTIVATIONS = {"quickgelu": 3}    # VIT_MLP_QUICKGELU: a GELU model's layout with another activation in fc1's epilogue (2 is unassigned)
 MLP_CODES = {**MLP_KINDS, **MLP_ACTIVATIONS}  # name -> the kind bits of vit_config.hidden_dim
 MLP_SHIFT = 24  # VIT_MLP_SHIFT: vit_config.hidden_dim carries the kind in bits 24..30 (binding.CConfig.of packs it)
+REG_SHIFT = 24  # VIT_REG_SHIFT: vit_config.patch_size carries the register-token count in bits 24..30 (binding.CConfig.of packs it)
+MAX_REGISTER_TOKENS = 16  # VIT_MAX_REGISTER_TOKENS
 
 
 @dataclass(frozen=True)
 class ModelConfig:
     """Runtime form of ViT_seq.c:10-21.  mlp: "gelu" (fc1 -> erf-GELU -> fc2) or "swiglu" (fc1 is the fused w12 with 2 * hidden_dim
     rows, gate rows first; the hidden layer is silu(gate) * value: DINOv2 ViT-g/14, EVA-02) or "quickgelu" (fc1 -> y * sigmoid(1.702 y)
-    -> fc2: OpenAI CLIP's image tower)."""
+    -> fc2: OpenAI CLIP's image tower).  num_register_tokens: R learned rows between the class token and the patch tokens (DINOv2
+    `_reg4`): tokens = 1 + R + patches in that order; weight 0 is then the prefix [(1 + R)][D], class token first; registers take no
+    position embedding, so weight 3 stays [(patches + 1)][D]."""
     img_size: int = 224
     patch_size: int = 16
     in_chans: int = 3
@@ -74,6 +78,7 @@ class ModelConfig:
     num_heads: int = 12
     hidden_dim: int = 3072
     mlp: str = "gelu"
+    num_register_tokens: int = 0
 
     def __post_init__(self):
         if self.mlp not in MLP_CODES and not isinstance(self.mlp, int):  # an int goes into vit_config as it is (the engine checks it)
@@ -86,12 +91,12 @@ class ModelConfig:
 
     @property
     def tokens(self) -> int:
-        g = self.img_size // self.patch_size
-        return g * g + 1
+        return 1 + self.num_register_tokens + self.patches
 
     @property
     def patches(self) -> int:
-        return self.tokens - 1
+        g = self.img_size // self.patch_size
+        return g * g
 
     @property
     def n_weights(self) -> int:
@@ -110,8 +115,8 @@ class ModelConfig:
         return self.patches * self.patch_dim * D + self.depth * per_layer + D * self.num_classes
 
     def weight_shapes(self):
-        D, H, H1, T = self.embed_dim, self.hidden_dim, self.fc1_rows, self.tokens
-        shapes = [(D,), (D, self.patch_dim), (D,), (T, D)]
+        D, H, H1, R = self.embed_dim, self.hidden_dim, self.fc1_rows, self.num_register_tokens
+        shapes = [(1 + R, D) if R else (D,), (D, self.patch_dim), (D,), (self.patches + 1, D)]
         for _ in range(self.depth):
             shapes += [(D,), (D,), (3 * D, D), (3 * D,), (D, D), (D,), (D,), (D,),
                        (H1, D), (H1,), (D, H), (D,)]
@@ -131,6 +136,8 @@ CLIP_L14 = ModelConfig(patch_size=14, num_classes=768, embed_dim=1024, depth=24,
 VIT_H14 = ModelConfig(patch_size=14, embed_dim=1280, depth=32, num_heads=16, hidden_dim=5120)
 CLIP_H14 = ModelConfig(patch_size=14, num_classes=1024, embed_dim=1280, depth=32, num_heads=16, hidden_dim=5120)
 CLIP_BIGG14 = ModelConfig(patch_size=14, num_classes=1280, embed_dim=1664, depth=48, num_heads=16, hidden_dim=8192)
+# DINOv2 ViT-B/14 with registers (dinov2_vitb14_reg): four register tokens behind the class token, T = 1 + 4 + 256
+DINOV2_B14_REG4 = ModelConfig(img_size=224, patch_size=14, embed_dim=768, depth=12, num_heads=12, hidden_dim=3072, num_register_tokens=4)
 # reduced models for fast live-oracle parity (head_dim stays 64 as in ViT-B/L)
 VIT_TINY = ModelConfig(img_size=32, num_classes=10, embed_dim=128, depth=2, num_heads=2, hidden_dim=256)
 VIT_SMALL = ModelConfig(img_size=64, num_classes=100, embed_dim=192, depth=3, num_heads=3, hidden_dim=768)
