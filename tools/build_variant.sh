@@ -3,8 +3,6 @@
 #   -> vision-transformer-opencl_amd/build/ab/libvit_mi355x_<name>.so = the current objects with that file recompiled with the flags.
 # Run after `make` (it links the other objects as they are); use with tools/gpu_session.sh ab:/abtest: steps.
 # PROBE=1 tools/build_variant.sh ...: a variant of the probe library instead (run after `make probes`).
-#   the image walk's step (csrc/vit_gemm_persistent.hip): -DSPLIT_STEP_PLAIN the step before the pipelined one, -DSPLIT_STEP_PREFETCH=0
-#   / -DSPLIT_STEP_FINE=0 one half of it off
 set -e
 cd "$(dirname "$0")/../vision-transformer-opencl_amd"
 name=$1; src=$2; shift 2

@@ -89,9 +89,6 @@ template <> __device__ __forceinline__ void store4<bf16_t>(bf16_t *p, f32x4 v) {
 constexpr int HD = 64;          // head_dim (ViT-B/16 and ViT-L/16)
 constexpr int K_LD = HD + 4;    // padded K row (floats): conflict-free ds_read_b128 over 32 rows
 constexpr int ATT_THREADS = 512;
-#ifndef ATT_STAGGER
-#define ATT_STAGGER 0   // measured at ViT-B/16 batch 2048: 0 / 8 / 14 / 20 x 64 cycles = 0.582 / 0.586 / 0.582 / 0.591 ms: nothing, off
-#endif
 constexpr int ATT_WAVES = ATT_THREADS / 64;
 #ifndef ATT_PROBE
 #define ATT_PROBE 0  // timing-only builds of the resident bf16 kernel (tools/build_variant.sh -DATT_PROBE=<bits>; results WRONG): 1 = no v_exp_f32,
@@ -103,7 +100,7 @@ unsigned long long *g_attn_dbg = nullptr;  // see vithip_attention_set_debug_buf
 constexpr unsigned long long *g_attn_dbg = nullptr;
 #endif
 
-template <int NKT, typename IO>  // NKT = number of 32-key tiles: tokens <= 32*NKT; IO = float or bf16 bits
+template <int NKT, typename IO>  // NKT = number of 32-key tiles: tokens <= 32*NKT; IO = bf16 bits is the one instance built (route 6)
 __global__ __launch_bounds__(ATT_THREADS) void attention_f32_kernel(const IO *__restrict__ qkv,
                                                                     IO *__restrict__ out,
                                                                     int tokens, int heads, int q_rows,
@@ -548,9 +545,9 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_bf16_kernel(const bf16_
 
         if (computes) {
             // The two waves of a SIMD (w and w + 4) leave the barrier together and would run their matrix phases (S, then P.V) and
-            // their softmax in step -- twice the matrix time, no overlap of the two pipes.  Waves 4-7 start ATT_STAGGER x 64 cycles
-            // late: their S falls into their partners' softmax, their softmax into the partners' P.V (vit_attention_stream.hip).
-            if (ATT_STAGGER > 0 && __builtin_amdgcn_readfirstlane(wave) >= 4) __builtin_amdgcn_s_sleep(ATT_STAGGER);
+            // their softmax in step -- twice the matrix time, no overlap of the two pipes.  Starting waves 4-7 late, so that their S
+            // falls into their partners' softmax and their softmax into the partners' P.V (vit_attention_stream.hip), bought nothing
+            // here: 0 / 8 / 14 / 20 x 64 cycles = 0.582 / 0.586 / 0.582 / 0.591 ms at ViT-B/16 batch 2048.
             // ---- S^T = K . Q^T ------------------------------------------------------------------------
             // (Tried in round 5: the key tiles in pairs, so that the four dependent products of a tile alternate with another tile's --
             // hipcc lays most of a tile's four back to back.  0.5607 against 0.5623 ms: the SIMD's other wave already fills those gaps.)
@@ -828,9 +825,9 @@ int launch_bf16(hipStream_t s, const bf16_t *qkv, bf16_t *out, int n_images, int
     return static_cast<int>(hipGetLastError());
 }
 
-template <int NKT, typename IO>
-int launch_f32(hipStream_t s, const IO *qkv, IO *out, int n_images, int tokens, int heads, int q_rows) {
-    hipLaunchKernelGGL((attention_f32_kernel<NKT, IO>), dim3(heads, n_images), dim3(ATT_THREADS), 0, s, qkv, out,
+template <int NKT>  // bf16 I/O only: fp32 up to 224 tokens is the resident kernel's
+int launch_f32(hipStream_t s, const bf16_t *qkv, bf16_t *out, int n_images, int tokens, int heads, int q_rows) {
+    hipLaunchKernelGGL((attention_f32_kernel<NKT, bf16_t>), dim3(heads, n_images), dim3(ATT_THREADS), 0, s, qkv, out,
                        tokens, heads, q_rows, g_attn_dbg);
     return static_cast<int>(hipGetLastError());
 }
@@ -842,18 +839,18 @@ inline dim3 chunked_grid(int n_images, int tokens, int heads) {  // a block of 8
 // ---- the router: rows 1-2 and 6 of the table at the head of this file (IO = float: 1-2, IO = bf16 bits: 6) ---------------------------
 template <typename IO>
 int route_f32_math(hipStream_t s, const IO *qkv, IO *out, int n_images, int tokens, int heads, int q_rows) {
-    if constexpr (std::is_same<IO, float>::value) {
-        if (tokens <= 224) return attention_f32_resident(s, qkv, out, n_images, tokens, heads, q_rows);
-    }
     if (tokens > 224) {  // computes every query row
         hipLaunchKernelGGL(attention_f32_chunked_kernel<IO>, chunked_grid(n_images, tokens, heads), dim3(ATT_THREADS), 0, s, qkv, out,
                            tokens, heads);
         return static_cast<int>(hipGetLastError());
     }
-    // bf16 I/O only; the float instances of attention_f32_kernel stay built, no entry reaches them
-    return dispatch_int<1, 7>((tokens + 31) / 32, [&](auto nkt) {
-        return launch_f32<decltype(nkt)::value, IO>(s, qkv, out, n_images, tokens, heads, q_rows);
-    });
+    if constexpr (std::is_same<IO, float>::value) {
+        return attention_f32_resident(s, qkv, out, n_images, tokens, heads, q_rows);
+    } else {
+        return dispatch_int<1, 7>((tokens + 31) / 32, [&](auto nkt) {
+            return launch_f32<decltype(nkt)::value>(s, qkv, out, n_images, tokens, heads, q_rows);
+        });
+    }
 }
 
 // Every vithip_attention_* entry is one call of this.  resident_only: the entry refuses more than 224 tokens whatever q_rows is.

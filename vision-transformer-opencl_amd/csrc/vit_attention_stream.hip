@@ -45,12 +45,10 @@ constexpr int SKEYS = SKT * 32;          // 128 keys
 constexpr int SBUF = 2 * SKEYS * SHD;    // bf16 elements of one ring slot: K[128][64] then V[128][64]
 constexpr int MAXB = 3;                  // query blocks per wave: tokens <= 8 * 3 * 32 = 768
 constexpr int SUB = 2;                   // key tiles whose scores are in registers at a time
-// Row sums from the matrix pipe (softmax_pv): built, exact to the bf16 rounding of P, and measured SLOWER here (2.37 against 2.22 ms per
-// launch at ViT-L/16-384, batch 1024: the four extra MFMAs per unit cost more than the 32 v_add_f32 they replace -- the resident
-// kernel of vit_attention.hip, whose units are longer, gains 1 % from the same change and keeps it).  Off.
-#ifndef ST_MFMA_ROWSUM
-#define ST_MFMA_ROWSUM 0
-#endif
+// (Row sums from the matrix pipe, one more MFMA per 16-key group with an all-ones operand, were built, exact to the bf16 rounding of
+// P, and measured SLOWER here: 2.37 against 2.22 ms per launch at ViT-L/16-384, batch 1024 -- the four extra MFMAs per unit cost more
+// than the 32 v_add_f32 they replace.  The resident kernel of vit_attention.hip, whose units are longer, gains 1 % from the same
+// change and keeps it.)
 // The two waves of a SIMD (w and w + 4) run the same program and leave every barrier together: left alone they issue their score /
 // P.V MFMAs at the same time (each burst then takes twice as long: one matrix pipe) and their softmax at the same time -- the unit
 // is [512 MFMA cycles][576 VALU][...] per wave and NOTHING overlaps (stamps: 2,150 cycles per unit with the partner active, 1,216
@@ -66,9 +64,6 @@ constexpr int SUB = 2;                   // key tiles whose scores are in regist
 #endif
 #ifndef ST_DMA_LATE
 #define ST_DMA_LATE 1
-#endif
-#ifndef ST_PRIO
-#define ST_PRIO 0
 #endif
 // ST_QREG: the Q fragments of a wave's first ST_QREG query blocks live in registers for the whole head (read from their LDS slot once,
 // in the head's first step) instead of being re-read for every (block, 64-key) unit -- 4 of a score burst's 12 ds_read_b128.  Round 2
@@ -229,7 +224,6 @@ __global__ __launch_bounds__(ST_THREADS) void attention_bf16_stream_kernel(const
     f32x16 o[MAXB][2];
     float m_run[MAXB], l_run[MAXB];
     [[maybe_unused]] bf16x8 qreg[ST_QREG > 0 ? ST_QREG : 1][4];
-    constexpr bool MSUM = QS && ST_MFMA_ROWSUM;  // row sums from the matrix pipe (see softmax_pv)
     const int h4 = 4 * h;
     // Q block b of this wave for `item` -> LDS (4 wave instructions of 8 rows: ST_QDMA pieces); rows past the end are clamped
     constexpr int ST_QDMA = 4, ST_STORES = 4;  // vector-memory operations per block: Q refill, output stores (finish_block)
@@ -274,9 +268,7 @@ __global__ __launch_bounds__(ST_THREADS) void attention_bf16_stream_kernel(const
         // reads last ((lane >> 2) & 3 == 3: query rows 12-15 and 28-31 of a block came out wrong, from run to run, on the
         // second-dispatched waves).  With soffset = 0 the two wait states are there.  tools/check_inline_asm.py rule (iv).
         const int voff = ((lane_l & 31) * D + 8 * (lane_l >> 5)) * 2 + ((wave + ST_WAVES * b) * 32 * D + head * SHD) * 2;
-        float inv;
-        if constexpr (MSUM) inv = 1.0f / l_run[b];                              // both half-waves hold the whole row sum
-        else inv = 1.0f / (l_run[b] + __shfl_xor(l_run[b], 32));
+        const float inv = 1.0f / (l_run[b] + __shfl_xor(l_run[b], 32));
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -425,16 +417,16 @@ __global__ __launch_bounds__(ST_THREADS) void attention_bf16_stream_kernel(const
                             st[buf][u][v + 1] = t[1];
                         }
                 }
-                [[maybe_unused]] float s4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                float s4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
                 for (int u = 0; u < SUB; ++u)
 #pragma unroll
                     for (int v = 0; v < 16; ++v) {
                         const float e = __builtin_amdgcn_exp2f(st[buf][u][v]);  // exp2(-inf) = 0: masked keys
                         st[buf][u][v] = e;
-                        if constexpr (!MSUM) s4[v & 3] += e;
+                        s4[v & 3] += e;
                     }
-                if constexpr (!MSUM) sum2 = f32x2{s4[0] + s4[1], s4[2] + s4[3]};
+                sum2 = f32x2{s4[0] + s4[1], s4[2] + s4[3]};
             } else {
                 m_new = (cmax - m_old) * kScale64 > kDefer ? cmax : m_old;  // first sub-chunk: m_old = -inf -> cmax (finite)
                 m_run[b] = m_new;
@@ -463,22 +455,10 @@ __global__ __launch_bounds__(ST_THREADS) void attention_bf16_stream_kernel(const
                         o[b][dt][v + 1] = w[1];
                     }
             }
-            if constexpr (!MSUM) l_run[b] += sum2[0] + sum2[1];
+            l_run[b] += sum2[0] + sum2[1];
             if (b == 0) ST_USTAMP();  // decision, exponentials, sums, rescale done
             // P.V: the V^T fragments of 16-key group g+1 are read before the MFMAs of group g.
-            // MSUM: the row sums come out of the matrix pipe too -- one more MFMA per 16-key group with an all-ones A operand gives
-            // every register of `lsum` the sum of this lane's column of P over the group's 16 keys (both half-waves' keys: the
-            // product runs over k), i.e. the sum of the probabilities AS ROUNDED to bf16, the weights P.V really uses.  32 v_add_f32
-            // per unit leave the vector pipe, which is the busier one here (30 % matrix-busy against 55 % vector-busy per SIMD).
-            // Only element 0 of the sums' accumulator is ever read and its 16 elements are independent sums, so 15 of the registers stay
-            // uninitialised (the empty asm "defines" them without an instruction) and element 0 starts as the running sum itself:
-            // no zeroing, no add afterwards.
             bf16x8 vf[2][2];
-            [[maybe_unused]] f32x16 lsum;
-            if constexpr (MSUM) {
-                asm volatile("" : "=v"(lsum));
-                lsum[0] = l_run[b];
-            }
             int lane_v = lane;
             asm volatile("" : "+v"(lane_v));  // the V^T fragment addresses are made per unit, not kept across the step
             auto read_v = [&](int g, int set) __attribute__((always_inline)) {  // g = 2 u + s2
@@ -499,13 +479,8 @@ __global__ __launch_bounds__(ST_THREADS) void attention_bf16_stream_kernel(const
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt) o[b][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[g & 1][dt], pf, o[b][dt], 0, 0, 0);
-                if constexpr (MSUM) {
-                    const bf16x8 ones = {(__bf16)1.0f, (__bf16)1.0f, (__bf16)1.0f, (__bf16)1.0f, (__bf16)1.0f, (__bf16)1.0f, (__bf16)1.0f, (__bf16)1.0f};
-                    lsum = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, pf, lsum, 0, 0, 0);
-                }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if constexpr (MSUM) l_run[b] = lsum[0];
             if (b == 0) ST_USTAMP();  // packing + P.V done
         };
         // a block's last unit of the head is behind it: out with it, and in with the next head's Q
@@ -537,7 +512,6 @@ __global__ __launch_bounds__(ST_THREADS) void attention_bf16_stream_kernel(const
     int item = blockIdx.x;
     if (item >= n_items) return;  // workgroup-uniform
     const int stride = gridDim.x;
-    if (ST_PRIO && wave >= 4) __builtin_amdgcn_s_setprio(1);  // the second-dispatched half loses the issue arbitration otherwise (T5, static form)
     // (the ring is not cleared: rows of a slot that no DMA of the current chunk wrote are read for masked scores only)
     dma_chunk(item, 0, 0);
     int slot = 0;

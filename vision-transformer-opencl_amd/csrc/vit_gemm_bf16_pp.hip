@@ -44,18 +44,6 @@ typedef unsigned short bf16_t;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void;
 
-#ifndef PP_LNF_RS
-#define PP_LNF_RS 0
-#endif
-#ifndef PP_STAGGER
-#define PP_STAGGER 0  // timing experiment: start-up phases of the persistent workgroups of the short fp32-residual GEMM, in cycles (0 = off, the product)
-#endif
-#ifndef PP_STAGGER_ALL
-#define PP_STAGGER_ALL 0  // timing experiment: the phases for every K
-#endif
-#ifndef PP_GELU_LOCKSTEP
-#define PP_GELU_LOCKSTEP 4  // pairs of the GELU epilogue advanced together: 0 (one chain after the other), 2, 4 (fc1 -1.0 % / -0.7 %, same bits)
-#endif
 constexpr int PBM = 256, PBN = 256, PBK = 64;
 constexpr int PTHREADS = 512;
 constexpr int SLOT = 128 * 128;               // one half-tile: 128 rows x 64 bf16
@@ -152,20 +140,13 @@ __global__ __launch_bounds__(PTHREADS) void gemm_bf16_pp_kernel(const Bf16Params
     const int first = xcd_remap(blockIdx.x, nwg);
     if (first >= total) return;  // workgroup-uniform
     const int nk = p.K / PBK;
-    // Timing experiment, OFF in the product (tools/build_variant.sh -DPP_STAGGER=<cycles>): start-up phases for the short fp32-residual
-    // GEMM (out_proj of ViT-B/16: K = 768, a tile is 12 K-steps and an epilogue that moves 640 KB) -- the persistent workgroups of an XCD
-    // start in four phases PP_STAGGER cycles apart, so that their read-modify-write epilogues (every CU's at the same moment otherwise,
-    // 164 MB asked of the HBM at once) do not coincide.  Round 5, profiles/r05/experiments/bf16_gemm_start_phases.jsonl: out_proj at
-    // batch 2048 -2.3 / -4.3 / -0.6 % on three boxes with 6,000-20,000 cycles, -4 % at batch 1024, +3.8 % at batch 256 (the wait is
-    // 12 us of a 138-us launch); fc2 (K = 3072) and the bf16-output GEMMs only pay the wait (+1.6 ... +4.6 % at 12,000 / 45,000),
-    // ViT-L's out_proj (K = 1024) is inside the noise.  Not a rule one can ship: the sign depends on the batch and the size on the box.
-    if constexpr (PP_STAGGER > 0 && EPI == VITHIP_BF16_EPI_F32_RESIDUAL) {
-        const int ph = (blockIdx.x >> 3) & 3;
-        if (ph && (nk <= 12 || PP_STAGGER_ALL)) {
-            const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-            while (__builtin_amdgcn_s_memtime() - t0 < (unsigned long long)ph * PP_STAGGER) __builtin_amdgcn_s_sleep(64);
-        }
-    }
+    // (Start-up phases for the short fp32-residual GEMM -- out_proj of ViT-B/16: K = 768, a tile is 12 K-steps and an epilogue that
+    // moves 640 KB -- were measured and not kept: the persistent workgroups of an XCD started in four phases 6,000-20,000 cycles
+    // apart, so that their read-modify-write epilogues, 164 MB asked of the HBM at once otherwise, do not coincide.  Round 5,
+    // profiles/r05/experiments/bf16_gemm_start_phases.jsonl: out_proj at batch 2048 -2.3 / -4.3 / -0.6 % on three boxes, -4 % at
+    // batch 1024, +3.8 % at batch 256 (the wait is 12 us of a 138-us launch); fc2 (K = 3072) and the bf16-output GEMMs only paid
+    // the wait (+1.6 ... +4.6 %), ViT-L's out_proj (K = 1024) was inside the noise.  Not a rule one can ship: the sign depends on
+    // the batch and the size on the box.)
 
     // ---- LDS-DMA source offsets: per half-tile two instructions (q) of 8 rows x 128 B.  Lane l lands at
     // (row L = 16*wave + 8q + l/8, chunk l%8) of the slot and fetches source chunk (l%8) ^ ((L>>1)&7).
@@ -311,7 +292,6 @@ __global__ __launch_bounds__(PTHREADS) void gemm_bf16_pp_kernel(const Bf16Params
             b4[j] = *reinterpret_cast<const f32x4 *>(lds + BIAS_OFF + e_tpar * 1024 +
                                                      (wc * 64 + (PAIRED ? 32 * (j >> 1) + 8 * l4 + 4 * (j & 1) : j * 16 + 4 * l4)) * 4);
         [[maybe_unused]] f32x4 s4[4];  // LNF consumer: column sums of this lane's features, (rstd, mean*rstd) of its 8 tokens
-        [[maybe_unused]] f32x2 rs_all[8];
         [[maybe_unused]] const char *ln_rows_lds = nullptr;  // + i * 128: this lane's (rstd, mean*rstd) pair of m-tile i
         if constexpr (LNF && PAIRED) {
             const char *ln = lds + LN_OFF + e_tpar * 3072;
@@ -319,10 +299,6 @@ __global__ __launch_bounds__(PTHREADS) void gemm_bf16_pp_kernel(const Bf16Params
             for (int j = 0; j < 4; ++j)
                 s4[j] = *reinterpret_cast<const f32x4 *>(ln + (wc * 64 + 32 * (j >> 1) + 8 * l4 + 4 * (j & 1)) * 4);
             ln_rows_lds = ln + 1024 + (g * 128 + l15) * 8;
-#if PP_LNF_RS == 1
-#pragma unroll
-            for (int i = 0; i < 8; ++i) rs_all[i] = *reinterpret_cast<const f32x2 *>(ln_rows_lds + i * 128);
-#endif
         }
         // Full-line accesses.  In registers a lane owns row (token) l15 and two 16-B chunks of it, so a plain store
         // instruction would write 16 rows x 64 B -- measured (tools/store_probe.py) at 14-19 B/clk per CU, against
@@ -578,11 +554,7 @@ __global__ __launch_bounds__(PTHREADS) void gemm_bf16_pp_kernel(const Bf16Params
             auto pack = [&](int i, u32x4 &c0, u32x4 &c1) __attribute__((always_inline)) {
                 [[maybe_unused]] f32x4 r4, m4;
                 if constexpr (LNF) {
-#if PP_LNF_RS == 1
-                    const f32x2 rs = rs_all[i];
-#else
                     const f32x2 rs = *reinterpret_cast<const f32x2 *>(ln_rows_lds + i * 128);
-#endif
                     r4 = f32x4{rs.x, rs.x, rs.x, rs.x}, m4 = f32x4{rs.y, rs.y, rs.y, rs.y};
                 }
 #pragma unroll
@@ -601,21 +573,9 @@ __global__ __launch_bounds__(PTHREADS) void gemm_bf16_pp_kernel(const Bf16Params
                         v[2 * jj + 1] = f32x2{t4[2], t4[3]};
                     }
                     if constexpr (EPI == VITHIP_BF16_EPI_BF16_QGELU) quick_gelu_lockstep<4>(v);
-                    if constexpr (EPI == VITHIP_BF16_EPI_BF16_GELU) {
-#if PP_GELU_LOCKSTEP == 4
-                        gelu_bf16_lockstep<4>(v);
-#elif PP_GELU_LOCKSTEP == 2
-                        {
-                            f32x2 a[2] = {v[0], v[1]}, b[2] = {v[2], v[3]};
-                            gelu_bf16_lockstep<2>(a);
-                            gelu_bf16_lockstep<2>(b);
-                            v[0] = a[0], v[1] = a[1], v[2] = b[0], v[3] = b[1];
-                        }
-#else
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = gelu_bf16_x2(v[e]);
-#endif
-                    }
+                    // the chunk's four pairs advanced together: fc1 -1.0 % (ViT-B/16) / -0.7 % (ViT-L/16-384) against one chain after the
+                    // other, two at a time in between; the same bits (profiles/r05/experiments/bf16_gelu_lockstep.jsonl)
+                    if constexpr (EPI == VITHIP_BF16_EPI_BF16_GELU) gelu_bf16_lockstep<4>(v);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         ob[2 * e] = (__bf16)v[e].x;

@@ -187,19 +187,7 @@ __device__ __forceinline__ f32x2 relu_keep_nan(f32x2 y) {
     return __builtin_elementwise_fma(y, f32x2{0.f, 0.f}, __builtin_elementwise_max(y, f32x2{0.f, 0.f}));
 }
 
-__device__ __forceinline__ f32x2 gelu_bf16_x2(f32x2 y) {
-    constexpr float kClamp = 5.656854249492381f;  // 4 sqrt2
-    const f32x2 t = f32x2{fminf(__builtin_fabsf(y.x), kClamp), fminf(__builtin_fabsf(y.y), kClamp)};
-    constexpr float c[7] = {-1.000037431716919f,   -1.1505244970321655f,   -0.4605136811733246f,  -0.05179140716791153f,
-                            0.007414536084979773f, -0.0006474481779150665f, 2.524326555430889e-05f};
-    f32x2 q = f32x2{c[6], c[6]};
-#pragma unroll
-    for (int k = 5; k >= 0; --k) q = __builtin_elementwise_fma(q, t, f32x2{c[k], c[k]});
-    const f32x2 e = f32x2{__builtin_amdgcn_exp2f(q.x), __builtin_amdgcn_exp2f(q.y)};
-    return __builtin_elementwise_fma(-t, e, relu_keep_nan(y));
-}
-
-// The same values for NP pairs advanced TOGETHER (the scheduling fences keep hipcc from putting the chains back one after the other):
+// NP pairs advanced TOGETHER (the scheduling fences keep hipcc from putting the chains back one after the other):
 // one pair is a chain of dependent v_pk_fma_f32, and on gfx950 a packed fma that reads the previous one's result needs a wait state --
 // hipcc fills it with `s_nop 0`, 5 per pair in the one-pair form (1,255 in the GELU kernel: a quarter of its vector issue slots beside
 // the 9 v_pk_fma_f32, 2 v_exp_f32, 4 v_min / v_max and the conversion of a pair).  With a second chain in between there is nothing to pad.
@@ -380,43 +368,6 @@ __device__ __forceinline__ void split3_step(f32x16 (&acc)[TM][TN], const float *
         }
     }
 }
-// The same step on swizzled tiles (SPLIT_LD_SW rows): As / Bs point at the lane's row r of the wave's first block, poff[piece] is
-// the lane's float offset of its chunk (2 piece + h) inside that row (the same for every block: blocks are 32 rows apart and the
-// swizzle repeats every 16).  restage(q), q < NS, goes right behind matrix instruction floor(q * NM / NS): spread over the whole
-// step, with the last slot a few instructions ahead of the barrier.
-struct Split3NoHook {
-    __device__ __forceinline__ void operator()() const {}
-};
-// landed(): a hook between the fragment reads and the first matrix instruction (the stamped probe instantiation; nothing otherwise)
-template <int TM, int TN, int NS, typename Restage, typename Landed = Split3NoHook>
-__device__ __forceinline__ void split3_step_sw(f32x16 (&acc)[TM][TN], const float *As, const float *Bs, const int (&poff)[3],
-                                               Restage &&restage, Landed &&landed = Landed{}) {
-    bf16x8 a[TM][3], b[TN][3];
-#pragma unroll
-    for (int o = 0; o < 3; ++o) {
-        const int pa = SPLIT_TERM_A[o], pb = SPLIT_TERM_W[o];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) a[i][pa] = *reinterpret_cast<const bf16x8 *>(As + i * 32 * SPLIT_LD_SW + poff[pa]);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) b[j][pb] = *reinterpret_cast<const bf16x8 *>(Bs + j * 32 * SPLIT_LD_SW + poff[pb]);
-    }
-    landed();
-    __builtin_amdgcn_sched_barrier(0);
-    constexpr int NM = 6 * TM * TN;
-    static_assert(NS <= NM, "one restage slot per matrix instruction at most");
-#pragma unroll
-    for (int idx = 0; idx < NM; ++idx) {
-        const int t = idx / (TM * TN), i = (idx / TN) % TM, j = idx % TN;
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][SPLIT_TERM_A[t]], b[j][SPLIT_TERM_W[t]], acc[i][j], 0, 0, 0);
-        const int slot_before = (idx * NS + NM - 1) / NM, slot_after = ((idx + 1) * NS + NM - 1) / NM;
-        if (slot_after > slot_before) {
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int q = slot_before; q < slot_after; ++q) restage(q);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-}
 
 // ---- the pipelined step of the image walk: the fragments of step g + 1 are read under the matrix instructions of step g ----------
 // Two LDS buffers and one barrier per step as before, but the barrier sits INSIDE the step, behind matrix instruction
@@ -426,19 +377,17 @@ __device__ __forceinline__ void split3_step_sw(f32x16 (&acc)[TM][TN], const floa
 // accumulators), so eight of the twelve reads land in registers that are already dead; the two hi pieces, live to the step's
 // end, are read into a spare set and moved over at the step's end.  A segment's first step reads its fragments at its top
 // (split3_read_cold) and its last step (PF = false) prefetches nothing: no fragment is live across an epilogue, where the
-// register count peaks.
+// register count peaks.  The tiles are swizzled (SPLIT_LD_SW rows): As / Bs point at the lane's row r of the wave's first block,
+// poff[piece] is the lane's float offset of its chunk (2 piece + h) inside that row (the same for every block: blocks are 32 rows
+// apart and the swizzle repeats every 16).
 struct Split3PfRead { int w, piece, behind; };  // operand (0 = A, 1 = W), piece, the matrix instruction its reads go behind
 constexpr int SPLIT_PF_BARRIER = 15;
 // both hi first (the moves out of the spare set at the next step's top wait for them), then in the order the next step's terms
 // need the rest: (hi, lo) (lo, hi) (mid, mid)
 constexpr Split3PfRead SPLIT_PF_READS[6] = {{0, 0, 15}, {1, 0, 16}, {1, 2, 17}, {0, 2, 18}, {0, 1, 19}, {1, 1, 20}};
-// restage slots of the pipelined step: slot q goes behind matrix instruction at(q)
-struct Split3SlotsCoarse {  // the six slots of restage_slot (A plane, W plane, alternating)
-    static constexpr int N = 6;
-    static constexpr int at(int q) { return (q * (SPLIT_PF_BARRIER + 1)) / N; }
-};
-// Finer slots (restage_fine of the walk): A's split in quarters of a plane (two values: 4 vector instructions for hi and mid, 1
-// for lo), so that no gap between two matrix instructions carries more than 4 of them plus one LDS write or one global load.
+// Restage slots of the image walk's step (restage_fine of the walk): slot q goes behind matrix instruction at(q).  A's split in
+// quarters of a plane (two values: 4 vector instructions for hi and mid, 1 for lo), so that no gap between two matrix instructions
+// carries more than 4 of them plus one LDS write or one global load.
 //   q 0-3 hi quarters, 4 hi write | 5-8 mid quarters, 9 mid write | 10, 11 lo halves, 12 lo write | 13, 14 the loads of A
 //   15-17 W plane writes | 18-20 W image loads (each behind its plane's write)
 struct Split3SlotsFine {
@@ -455,10 +404,9 @@ constexpr int split3_last_use(int w, int piece, int per_term) {
         if ((w ? SPLIT_TERM_W[t] : SPLIT_TERM_A[t]) == piece) last = (t + 1) * per_term - 1;
     return last;
 }
-template <class Slots>
 constexpr bool split3_pf_schedule_ok(int per_term) {
-    for (int q = 0; q < Slots::N; ++q)  // every restage write in front of the barrier
-        if (Slots::at(q) < 0 || Slots::at(q) > SPLIT_PF_BARRIER) return false;
+    for (int q = 0; q < Split3SlotsFine::N; ++q)  // every restage write in front of the barrier
+        if (Split3SlotsFine::at(q) < 0 || Split3SlotsFine::at(q) > SPLIT_PF_BARRIER) return false;
     bool seen[2][3] = {};
     for (int e = 0; e < 6; ++e) {
         const Split3PfRead rd = SPLIT_PF_READS[e];
@@ -504,14 +452,18 @@ __device__ __forceinline__ void split3_read_cold(Split3Frags<TM, TN> &f, const f
 #pragma unroll
     for (int e = 0; e < 6; ++e) split3_read_piece<TM, TN, false>(f, As, Bs, poff, e);
 }
-// One step from the fragments in f; restage(q), q < Slots::N, behind matrix instruction Slots::at(q); sync() is the step's
-// barrier; PF: the fragments of the next step from the other buffer (An / Bn) into f; landed(): as in split3_step_sw.
-template <int TM, int TN, bool PF, class Slots, typename Restage, typename Sync, typename Landed = Split3NoHook>
+struct Split3NoHook {
+    __device__ __forceinline__ void operator()() const {}
+};
+// One step from the fragments in f; restage(q), q < Split3SlotsFine::N, behind matrix instruction Split3SlotsFine::at(q); sync()
+// is the step's barrier; PF: the fragments of the next step from the other buffer (An / Bn) into f; landed(): a hook in front of
+// the first matrix instruction (the stamped probe instantiation; nothing otherwise).
+template <int TM, int TN, bool PF, typename Restage, typename Sync, typename Landed = Split3NoHook>
 __device__ __forceinline__ void split3_step_pf(f32x16 (&acc)[TM][TN], Split3Frags<TM, TN> &f, const float *An, const float *Bn,
                                                const int (&poff)[3], Restage &&restage, Sync &&sync, Landed &&landed = Landed{}) {
     constexpr int NM = 6 * TM * TN;
     static_assert(NM == 24, "the schedule table is laid out for 2 x 2 accumulators");
-    static_assert(split3_pf_schedule_ok<Slots>(TM * TN),
+    static_assert(split3_pf_schedule_ok(TM * TN),
                   "restage writes in front of the barrier, reads of the other buffer behind it and behind the last use of what they overwrite");
     landed();
     __builtin_amdgcn_sched_barrier(0);
@@ -521,8 +473,8 @@ __device__ __forceinline__ void split3_step_pf(f32x16 (&acc)[TM][TN], Split3Frag
         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[i][SPLIT_TERM_A[t]], f.b[j][SPLIT_TERM_W[t]], acc[i][j], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int q = 0; q < Slots::N; ++q)
-            if (Slots::at(q) == idx) restage(q);
+        for (int q = 0; q < Split3SlotsFine::N; ++q)
+            if (Split3SlotsFine::at(q) == idx) restage(q);
         if (idx == SPLIT_PF_BARRIER) sync();
         if constexpr (PF) {
 #pragma unroll
@@ -581,9 +533,6 @@ __device__ __forceinline__ void fold_preload(FoldOperands<TN, TM> &fold, const f
 __device__ __forceinline__ float fold_center(float acc, float mean, float colsum) { return __builtin_fmaf(-mean, colsum, acc); }
 __device__ __forceinline__ float fold_scale(float centered, float rstd, float bias) { return __builtin_fmaf(rstd, centered, bias); }
 
-#ifndef FOLD_HOIST
-#define FOLD_HOIST 1  // centred-weight fold: read the rstd of all the lane's rows before the first block's values (A/B switch)
-#endif
 template <int BM, int BN, int WM, int WN, int EPI, int AMODE>
 __device__ __forceinline__ void epilogue_store(const GemmParams &p, const f32x16 (&acc)[WM / 32][WN / 32],
                                                const float (&bias_r)[WN / 32], int m0, int n0, int wm, int wn,
@@ -608,7 +557,7 @@ __device__ __forceinline__ void epilogue_store(const GemmParams &p, const f32x16
             // put the fold's epilogue at 9.5k cycles per QKV tile against 5.1k for the plain one (round 5).
             const bool center = p.ln_colsum != nullptr;  // workgroup-uniform
             // Two code paths, chosen once per tile (a copy "centered = acc" on the path that does not centre cost 60 registers).
-            // HOIST: the rstd of ALL the lane's rows first (LDS reads in the persistent walk) -- one exposed LDS round trip per tile
+            // The path that does not centre reads the rstd of ALL the lane's rows first (LDS reads in the persistent walk) -- one exposed LDS round trip per tile
             // instead of one per 32-row block: they queue behind the fragment reads of the CU's other workgroup, and the scheduling
             // fences of the GELU batches keep the second block's reads from being issued before the first block's stores.
             auto rstd_of_block = [&](int i, float (&dst)[16]) __attribute__((always_inline)) {
@@ -658,12 +607,9 @@ __device__ __forceinline__ void epilogue_store(const GemmParams &p, const f32x16
             } else {
                 float row_rstd[TM][16];
 #pragma unroll
-                for (int i = 0; i < (FOLD_HOIST ? TM : 0); ++i) rstd_of_block(i, row_rstd[i]);
+                for (int i = 0; i < TM; ++i) rstd_of_block(i, row_rstd[i]);
 #pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    if (!FOLD_HOIST) rstd_of_block(i, row_rstd[i]);
-                    scale_and_store(i, acc[i], row_rstd[i]);
-                }
+                for (int i = 0; i < TM; ++i) scale_and_store(i, acc[i], row_rstd[i]);
             }
             return;
         }

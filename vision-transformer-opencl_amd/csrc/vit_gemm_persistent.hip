@@ -36,28 +36,7 @@
 #include "vit_device.hpp"
 #include "vit_gemm_common.hpp"
 
-// The image walk's step: SPLIT_STEP_PREFETCH = 1 reads the fragments of step g + 1 under the matrix instructions
-// of step g (split3_step_pf), 0 is the step that reads them behind its barrier (split3_step_sw).  -DSPLIT_STEP_PLAIN builds the
-// latter: the "before" arm of tools/build_variant.sh from the same tree.  The same bits either way.
-#ifdef SPLIT_STEP_PLAIN
-#undef SPLIT_STEP_PREFETCH
-#define SPLIT_STEP_PREFETCH 0
-#endif
-#ifndef SPLIT_STEP_PREFETCH
-#define SPLIT_STEP_PREFETCH 1
-#endif
-// SPLIT_STEP_FINE = 1: A's split dealt out over the gaps in quarters of a plane (Split3SlotsFine) instead of a plane per slot
-#ifdef SPLIT_STEP_PLAIN
-#undef SPLIT_STEP_FINE
-#define SPLIT_STEP_FINE 0
-#endif
-#ifndef SPLIT_STEP_FINE
-#define SPLIT_STEP_FINE 1
-#endif
-
 namespace vitgemm {
-
-using SplitSlots = std::conditional_t<SPLIT_STEP_FINE != 0, Split3SlotsFine, Split3SlotsCoarse>;
 
 constexpr int PBK = 32;           // K step
 constexpr int PLD = PBK + 4;      // padded LDS row (floats)
@@ -74,11 +53,10 @@ constexpr int SK_HEADER_BYTES = 4096, SK_MAX_OWNERS = 1000, SK_STAT_TAKEN = 1016
 // WIMG (split only): W's pieces come ready-made from the weight image p.w_split and A is split in registers -- no vector
 // instruction touches W in the loop.  Staging per thread and K step: 8 consecutive k of one row of A (two 16-byte loads, split
 // into three 16-byte plane chunks) and three 16-byte image chunks of W, all written with ds_write_b128 into swizzled rows of
-// SPLIT_LD_SW floats (64 KB), conflict-free (see split_swizzle).  Six restage slots (A plane, W plane, alternating) spread over
-// all 24 matrix instructions of the step.  The same pieces in the same places of the product: the same bits as WIMG = false.
-// That is the plain step (split3_step_sw).  The default build deals A's split out in quarters of a plane over the first 14 gaps
-// (restage_fine) and, except under the residual epilogues, reads the fragments of the next step under this step's matrix
-// instructions (PIPE, split3_step_pf); the switches are at the head of this file.
+// SPLIT_LD_SW floats (64 KB), conflict-free (see split_swizzle).  The same pieces in the same places of the product: the same
+// bits as WIMG = false.  A's split is dealt out in quarters of a plane over the first 14 gaps between the step's matrix
+// instructions (restage_fine) and, except under the residual epilogues, the fragments of the next step are read under this
+// step's matrix instructions (PIPE, split3_step_pf).
 template <int BM, int BN, int WM, int WN, int EPI, bool STAMP = false, bool SK = false, int DBG = 0, int ARITH = ARITH_F32,
           bool WIMG = false>
 __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const GemmParams p) {
@@ -87,7 +65,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
     static_assert(!WIMG || (SPLIT && BM == WIMG_ROWS && BN == WIMG_ROWS), "the weight image feeds the 128x128 split walk");
     // The pipelined step pays under the fold consumers' walks (QKV, fc1) and not under the residual ones (out_proj, fc2), which are
     // faster with the finer slots alone: measured per launch at batch 256, profiles/r21.
-    constexpr bool PIPE = WIMG && SPLIT_STEP_PREFETCH != 0 && EPI != VITHIP_EPI_BIAS_RESIDUAL && EPI != EPI_RESIDUAL_STATS;
+    constexpr bool PIPE = WIMG && EPI != VITHIP_EPI_BIAS_RESIDUAL && EPI != EPI_RESIDUAL_STATS;
     constexpr int PBK = SPLIT ? SPLIT_BK : vitgemm::PBK;  // K step
     constexpr int PLD = WIMG ? SPLIT_LD_SW : SPLIT ? SPLIT_LD : vitgemm::PLD;  // LDS row (floats)
     constexpr int ROWS_PER_PASS = 256 / (PBK / 4);
@@ -99,7 +77,6 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
     constexpr int NS = A_CHUNKS + B_CHUNKS;  // staged float4 per thread per K step
     constexpr int W_CHUNKS = 3;              // WIMG: image chunks per thread per K step (one per plane)
     constexpr int NL = WIMG ? A_CHUNKS + W_CHUNKS : NS;  // global loads per thread per K step
-    constexpr int NSL = WIMG ? 6 : NS;                   // restage slots per K step
     static_assert(!WIMG || (A_CHUNKS == 2 && BM * 2 == 256 && BN * 2 == 256), "WIMG: one 8-deep half row of A and of W per thread");
     constexpr int NM = 4 * TM * TN;          // MFMAs per chunk
     static_assert((BM / WM) * WGN == 4, "4 waves per workgroup");
@@ -324,24 +301,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
 #pragma unroll
         for (int i = 0; i < B_CHUNKS; ++i) stage_write(Bs + (ld_row + i * ROWS_PER_PASS) * PLD, b_stage[i]);
     };
-    // one staging slot: write the float4 fetched a step ago, then refetch it for two steps ahead.  WIMG: slot 2 pl = plane pl of A
-    // (after the lo plane, both A loads), slot 2 pl + 1 = plane pl of W and its image load
+    // one staging slot (fp32 and the on-the-fly split): write the float4 fetched a step ago, then refetch it for two steps ahead
     auto restage_slot = [&](int q, int buf, int k0) {
-        if constexpr (WIMG) {
-            const int pl = q >> 1;
-            if (q & 1) {
-                write_w_plane(Bs0 + buf * BN * PLD, pl);
-                w_stage[pl] = __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, b_src[pl], (k0 / PBK) * WIMG_BLOCK_BYTES, 0);
-            } else {
-                write_a_plane(As0 + buf * BM * PLD, pl);
-                if (pl == 2) {
-#pragma unroll
-                    for (int i = 0; i < A_CHUNKS; ++i)
-                        a_stage[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, a_src[i], k0 * 4, 0));
-                }
-            }
-            return;
-        }
         if (q < A_CHUNKS) {
             float *As = As0 + buf * BM * PLD;
             if (DBG != 5 && DBG != 6) stage_write(As + (ld_row + q * ROWS_PER_PASS) * PLD, a_stage[q]);
@@ -354,7 +315,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
         }
     };
 
-    // the same in Split3SlotsFine's finer slots
+    // WIMG: the same in Split3SlotsFine's finer slots
     u32x4 a_plane;  // the plane chunk of A being put together
     auto restage_fine = [&](int q, int buf, int k0) {
         if (q <= 12) {
@@ -384,9 +345,10 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
             w_stage[q - 18] = __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, b_src[q - 18], (k0 / PBK) * WIMG_BLOCK_BYTES, 0);
         }
     };
+    // The pipelined step's restage hook: restage_fine and nothing else.  (It stays a closure of its own: without it hipcc orders two
+    // moves in the preamble of the probe build's stamped residual walks differently, profiles/r28.)
     auto restage_any = [&](int q, int buf, int k0) __attribute__((always_inline)) {
-        if constexpr (SPLIT_STEP_FINE != 0) restage_fine(q, buf, k0);
-        else restage_slot(q, buf, k0);
+        restage_fine(q, buf, k0);
     };
 
     const int a_frag_off = WIMG ? (wm * WM + r) * PLD : (wm * WM + r) * PLD + h * 4;
@@ -570,7 +532,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
         auto step = [&](auto prefetch) __attribute__((always_inline)) {
             constexpr bool PF = decltype(prefetch)::value;
             const int k_ahead = k_l * PBK;  // offset of the step the restage loads fetch (two steps ahead)
-            split3_step_pf<TM, TN, PF, SplitSlots>(acc, frags, tile_a(cur ^ 1), tile_b(cur ^ 1), frag_poff,
+            split3_step_pf<TM, TN, PF>(acc, frags, tile_a(cur ^ 1), tile_b(cur ^ 1), frag_poff,
                 [&](int q) __attribute__((always_inline)) { restage_any(q, cur ^ 1, k_ahead); }, [] { __syncthreads(); }, stamp_landed);
             stamp_step();
             stamp_top();
@@ -591,21 +553,13 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
     for (int g = 0; g < steps; ++g) {
         const int k_ahead = k_l * PBK;  // offset of the step the restage loads fetch (step g + 2)
         if (k_c + 1 == kend_c) fold_rows_landed();
-        if constexpr (WIMG && SPLIT_STEP_FINE != 0) {
-            // the plain step's order (fragments behind the barrier, the barrier at the step's end) with the finer slots
+        if constexpr (WIMG) {
+            // the residual walks: fragments behind the barrier, the barrier at the step's end, the finer slots
             Split3Frags<TM, TN> frags;
             stamp_top();
             split3_read_cold<TM, TN>(frags, As0 + cur * BM * PLD + a_frag_off, Bs0 + cur * BN * PLD + b_frag_off, frag_poff);
-            split3_step_pf<TM, TN, false, SplitSlots>(acc, frags, nullptr, nullptr, frag_poff,
+            split3_step_pf<TM, TN, false>(acc, frags, nullptr, nullptr, frag_poff,
                 [&](int q) __attribute__((always_inline)) { restage_fine(q, cur ^ 1, k_ahead); }, [] {}, stamp_landed);
-            stamp_step();
-            advance_load_cursor();
-            __syncthreads();
-        } else if constexpr (WIMG) {
-            // as below, on the swizzled tiles: the six restage slots of step g + 1 / g + 2 spread over all the step's matrix instructions
-            stamp_top();
-            split3_step_sw<TM, TN, NSL>(acc, As0 + cur * BM * PLD + a_frag_off, Bs0 + cur * BN * PLD + b_frag_off, frag_poff,
-                                        [&](int q) __attribute__((always_inline)) { restage_slot(q, cur ^ 1, k_ahead); }, stamp_landed);
             stamp_step();
             advance_load_cursor();
             __syncthreads();
