@@ -1,5 +1,6 @@
 """A numpy model of the split attention kernel (vithip_attention_f32_split, csrc/vit_attention_hd.hip: attention_split_kernel) for
-one head of 64 columns, a float64 reference and a sequential-fp32 evaluation to set it against.  No GPU.
+one head of 64 columns; a float64 reference and a sequential-fp32 evaluation of any head_dim to set it and the kernels against; and
+the input families the CPU test of the model and tests/test_gpu_attention_accuracy.py share.  No GPU.
 
 The model follows the kernel step by step: Q, K, V and the softmax weights P in three bf16 pieces (hi, mid, lo, each rounded to
 nearest even; torch does the rounding), keys in tiles of 32, the contraction over d in four steps of 16 with the six piece products
@@ -7,8 +8,13 @@ of a step added small terms first, the exp2 softmax with the deferred running ma
 by more than 2^8), the row sums in the kernel's lane order (two half-wave sums of fp32 adds), P.V sixteen keys at a time with the
 same six terms, and one multiplication by the reciprocal of the row sum at the end.
 
-The model of one v_mfma_f32_32x32x16_bf16 is the one of tests/test_split_gemm_model.py: the 16 products of a step are exact in fp32
-and their sum (float64 here) is added to the accumulator with one rounding.  v_exp_f32 is float64 exp2 rounded to fp32.
+The model of one v_mfma_f32_32x32x16_bf16: the 16 products of a step are exact in fp32 and the accumulator takes them in two
+roundings, the 8 products of the lower half-wave's operands first, then the 8 of the upper one (sums in float64 here).  The model of
+tests/test_split_gemm_model.py, all 16 with one rounding, is what this one had until it was set against the kernel's bits on the
+MI355X (profiles/r29/attention_accuracy.md): with V = I the kernel returns P / l, and the share of elements with the model's bits
+went from 15 - 38 % to 78 - 83 % with the two roundings (every other grouping tried was below one rounding), and on full outputs from
+14 % to 48 % with the keys of a P.V step in the half-waves' order (PV_K_ORDER).  What is left is v_exp_f32, which is float64 exp2
+rounded to fp32 here and within 1 ulp of it on the device.
 """
 import numpy as np
 import torch
@@ -38,9 +44,17 @@ def split3(x):
 
 
 def mfma(acc, a, b):
-    """acc [M][N] fp32 += a [M][16] . b [N][16]^T: exact products, one rounding."""
+    """acc [M][N] fp32 += a [M][16] . b [N][16]^T as one v_mfma_f32_32x32x16_bf16: exact products; the 8 of the lower half-wave
+    (k = 0..7) are added to the accumulator with one rounding, then the 8 of the upper one (k = 8..15) with another."""
     with np.errstate(invalid="ignore", over="ignore"):
-        return (acc.astype(np.float64) + a.astype(np.float64) @ b.astype(np.float64).T).astype(np.float32)
+        for half in (slice(0, 8), slice(8, 16)):
+            acc = (acc.astype(np.float64) + a[:, half].astype(np.float64) @ b[:, half].astype(np.float64).T).astype(np.float32)
+    return acc
+
+
+# The 16 keys of a P.V step in the instruction's k order: a half-wave holds keys 4 h + (0..3) and 4 h + 8 + (0..3) of the group
+# (registers 8 s2 .. 8 s2 + 7 of the score tile), so the first rounding covers keys 0-3 and 8-11, the second 4-7 and 12-15.
+PV_K_ORDER = np.array([0, 1, 2, 3, 8, 9, 10, 11, 4, 5, 6, 7, 12, 13, 14, 15])
 
 
 def tile_keys(h):
@@ -49,8 +63,9 @@ def tile_keys(h):
     return (v & 3) + 8 * (v >> 2) + 4 * h
 
 
-def attention_split(q, k, v):
-    """q [Tq][64], k, v [T][64] fp32 -> [Tq][64] fp32, as attention_split_kernel computes one head."""
+def attention_split(q, k, v, terms=TERMS):
+    """q [Tq][64], k, v [T][64] fp32 -> [Tq][64] fp32, as attention_split_kernel computes one head.  terms: the piece products of
+    both contractions (the kernel's six; fewer is a mutant for tests/test_attention_split_model.py)."""
     q, k, v = (np.asarray(a, np.float32) for a in (q, k, v))
     Tq, T = q.shape[0], k.shape[0]
     pad = (T + 31) // 32 * 32
@@ -63,7 +78,7 @@ def attention_split(q, k, v):
     for tile0 in range(0, T, 32):
         s = np.zeros((Tq, 32), np.float32)
         for d0 in range(0, HD, 16):
-            for ik, iq in TERMS:
+            for ik, iq in terms:
                 s = mfma(s, qs[iq][:, d0:d0 + 16], ks[ik][tile0:tile0 + 32, d0:d0 + 16])
         s[:, np.arange(32) + tile0 >= T] = -np.inf
         cmax = s.max(1)
@@ -87,33 +102,140 @@ def attention_split(q, k, v):
         for g0 in range(0, 32, 16):
             if tile0 + g0 >= T:
                 break
-            keys = slice(tile0 + g0, tile0 + g0 + 16)
-            for iv, ip in TERMS:
-                o = mfma(o, ps[ip][:, g0:g0 + 16], vs[iv][keys].T)
+            for iv, ip in terms:
+                o = mfma(o, ps[ip][:, g0 + PV_K_ORDER], vs[iv][tile0 + g0 + PV_K_ORDER].T)
     inv = np.float32(1.0) / (l_run[0] + l_run[1])
     return o * inv[:, None]
 
 
-def attention_f64(q, k, v):
+def scale_f32(head_dim):
+    """log2(e) / sqrt(head_dim) as the fp32 constant the kernels use (vithip_qscale, binding.qscale; at 64 it is kScale64 = SCALE)."""
+    return np.float32((1.0 / np.sqrt(float(head_dim))) * 1.4426950408889634074)
+
+
+def attention_f64(q, k, v, head_dim=HD):
     q, k, v = (np.asarray(a, np.float64) for a in (q, k, v))
-    s = q @ k.T / 8.0
+    s = q @ k.T / np.sqrt(float(head_dim))
     p = np.exp(s - s.max(1, keepdims=True))
     return (p / p.sum(1, keepdims=True)) @ v
 
 
-def attention_f32_sequential(q, k, v):
+def attention_f32_sequential(q, k, v, head_dim=HD):
     """Plain fp32, one operation after the other: every score an FMA chain over d, the row maximum, p = exp2(fma(s, c, -m c)), the
     row sum and every output an FMA chain over the keys, one multiplication by the reciprocal of the sum."""
     q, k, v = (np.asarray(a, np.float32) for a in (q, k, v))
     Tq, T = q.shape[0], k.shape[0]
+    c = scale_f32(head_dim)
     s = np.zeros((Tq, T), np.float32)
-    for d in range(HD):
+    for d in range(head_dim):
         s = f32(s.astype(np.float64) + np.outer(q[:, d].astype(np.float64), k[:, d].astype(np.float64)))
-    mneg = f32(-s.max(1).astype(np.float64) * SCALE)
-    p = f32(np.exp2(f32(s.astype(np.float64) * SCALE + mneg[:, None].astype(np.float64)).astype(np.float64)))
+    mneg = f32(-s.max(1).astype(np.float64) * c)
+    p = f32(np.exp2(f32(s.astype(np.float64) * c + mneg[:, None].astype(np.float64)).astype(np.float64)))
     total = np.zeros(Tq, np.float32)
-    o = np.zeros((Tq, HD), np.float32)
+    o = np.zeros((Tq, head_dim), np.float32)
     for key in range(T):
         total = total + p[:, key]
         o = f32(o.astype(np.float64) + np.outer(p[:, key].astype(np.float64), v[key].astype(np.float64)))
     return o * (np.float32(1.0) / total)[:, None]
+
+
+# ---- the input families of tests/test_gpu_attention_accuracy.py and of the CPU test of this model ----------------------------------
+
+FAMILIES = ("iid", "offset", "retrieval", "rising", "peaked", "one-hot", "constant-V")
+SPLIT_BAR_FAMILIES = FAMILIES  # where a split without its three small products misses 2 e_model + 2^-24 |ref|max (the CPU test): all
+ACCURACY_SEED = 2029  # the one draw the CPU test and the GPU tests share
+ONE_HOT_FACTOR = 200.0
+RISE, RISE_POWER = 64.0, 6  # "rising": a row's score climbs by up to RISE (log2 units) along the keys, as (key / last key)^RISE_POWER
+
+
+def family_inputs(family, T, head_dim, heads, seed):
+    """(qkv [T][3 * heads * head_dim] fp32, columns [Q | K | V] with head h at columns head_dim * h.. of each, info) for one image.
+    Every draw is synth.uniform(seed, index, ...).  info: "perm" [heads][T], the key row i is built on (retrieval, one-hot); "c"
+    [heads * head_dim], the row every V row equals (constant-V).
+
+    iid         Q, K, V = U(-1.5, 1.5): a nearly flat softmax, outputs of 0.1 to 0.7
+    offset      the same Q and K, V = 3 + U(-1, 1): an error of the row sum shows at full size in an output of about 3
+    retrieval   q_i = 0.6 k_perm(i) + 0.3 U(-1.5, 1.5), V offset: rows peaked on one key
+    rising      q_i = rate_i u + noise, k_j = ramp_j u + noise (u a vector of signs, rate 0.25 .. 1, ramp_j ~ (j / (T - 1))^6), V
+                offset: every row's score rises along the keys, the steeper the later, by rate_i * 64 in the exponent, so the deferred
+                running maximum of a 32-key tile walk moves in some tiles and is outgrown by less than 2^8 in others
+    peaked      Q, K, V = U(-8, 8): scores of hundreds, a handful of keys per row
+    one-hot     q_i = 200 k_perm(i), V offset: every other key is at least 2^-200 below (asserted where it is used): p is 0 or 1
+    constant-V  Q and K iid, every V row the same row c of 3 + U(-1, 1)
+    """
+    from vit_amd import synth
+    D = heads * head_dim
+
+    def u(index, shape, lo, hi):
+        return synth.uniform(seed, index, int(np.prod(shape)), lo, hi).reshape(shape)
+
+    def perms(index):
+        return np.stack([np.argsort(u(index + h, (T,), 0.0, 1.0), kind="stable") for h in range(heads)])
+
+    info = {}
+    amp = 8.0 if family == "peaked" else 1.5
+    q, k = u(0, (T, D), -amp, amp), u(1, (T, D), -amp, amp)
+    v = u(2, (T, D), -amp, amp) if family in ("iid", "peaked") else np.float32(3.0) + u(2, (T, D), -1.0, 1.0)
+    if family in ("retrieval", "one-hot"):
+        info["perm"] = perms(10)
+        for h in range(heads):
+            cols = slice(h * head_dim, (h + 1) * head_dim)
+            picked = k[info["perm"][h], cols]
+            q[:, cols] = np.float32(ONE_HOT_FACTOR) * picked if family == "one-hot" else np.float32(0.6) * picked + np.float32(0.3) * q[:, cols]
+    elif family == "rising":
+        signs = np.where(u(3, (D,), -1.0, 1.0) < 0, np.float32(-1.0), np.float32(1.0))
+        rate = np.linspace(0.25, 1.0, T, dtype=np.float32)[:, None]
+        ramp = (np.arange(T, dtype=np.float64)[:, None] / max(T - 1, 1)) ** RISE_POWER * RISE
+        per_unit = 1.0 / (head_dim * float(scale_f32(head_dim)))  # q.k = rate * ramp * head_dim * per_unit: rate * ramp in the exponent
+        q = rate * signs + np.float32(0.1) * q
+        k = (ramp * per_unit).astype(np.float32) * signs + np.float32(0.1) * k
+    elif family == "constant-V":
+        info["c"] = v[0].copy()
+        v = np.broadcast_to(v[0], (T, D))
+    elif family not in ("iid", "offset", "peaked"):
+        raise ValueError(family)
+    return np.ascontiguousarray(np.concatenate([q, k, v], axis=1), np.float32), info
+
+
+def head_operands(qkv, heads, head_dim, h):
+    """q, k, v [T][head_dim] of head h out of qkv [T][3 * heads * head_dim]."""
+    D = heads * head_dim
+    return tuple(np.ascontiguousarray(qkv[:, j * D + h * head_dim:j * D + (h + 1) * head_dim]) for j in range(3))
+
+
+def scaled_scores_f64(q, k, head_dim):
+    """The exponents the kernels form, in float64: q . k^T times the kernels' fp32 scale constant."""
+    return (np.asarray(q, np.float64) @ np.asarray(k, np.float64).T) * float(scale_f32(head_dim))
+
+
+def one_hot_gap(q, k, perm, head_dim):
+    """The least distance (log2 units) of a row's selected key to any other key of the row."""
+    s = scaled_scores_f64(q, k, head_dim)
+    rows = np.arange(s.shape[0])
+    top = s[rows, perm].copy()
+    s[rows, perm] = -np.inf
+    return float((top - s.max(1)).min())
+
+
+def ulps(got, want):
+    """max |got - want| in units of the last place of `want` (fp32)."""
+    got, want = np.asarray(got, np.float32), np.asarray(want, np.float32)
+    return float((np.abs(got.astype(np.float64) - want.astype(np.float64)) / np.spacing(np.abs(want)).astype(np.float64)).max())
+
+
+def deferred_maximum_walk(s, tile=32, defer=float(DEFER)):
+    """What the running maximum of attention_hd_kernel / attention_split_kernel does on the exponents s [rows][keys], tile by tile:
+    (moves [rows]: the tiles behind the first in which it moves, i.e. O and the row sum are rescaled; held [rows]: the tiles whose
+    maximum is above it by no more than `defer`, so it stays and p passes 1)."""
+    rows, T = s.shape
+    m = s[:, :tile].max(1)
+    moves, held = np.zeros(rows, int), np.zeros(rows, int)
+    for t0 in range(tile, T, tile):
+        cmax = s[:, t0:t0 + tile].max(1)
+        grow = cmax - m
+        moved = grow > defer
+        moves += moved
+        held += (grow > 0) & ~moved
+        m = np.where(moved, cmax, m)
+    return moves, held
+

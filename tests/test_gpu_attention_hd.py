@@ -68,6 +68,7 @@ def run(kind, qkv, n, T, heads, hd, **kw):
 
 @pytest.mark.parametrize("hd", HEAD_DIMS)
 def test_fp32_matches_the_oracle(oracle, hd):
+    """The reference's order of operations; the accuracy test, against float64 at fp32-level bars: tests/test_gpu_attention_accuracy.py."""
     heads, n = 2, 2
     D = heads * hd
     for T in TOKENS_F32:

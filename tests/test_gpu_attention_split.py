@@ -40,6 +40,7 @@ def oracle_attention(oracle, qkv, n, T, heads):
 
 @pytest.mark.parametrize("n,T,heads", SHAPES + EDGES)
 def test_matches_the_oracle(oracle, n, T, heads):
+    """The reference's order of operations; the accuracy test, against float64 at fp32-level bars: tests/test_gpu_attention_accuracy.py."""
     D = heads * 64
     qkv = u(30, (n * T, 3 * D), 1.5)
     got = B.attention_split(qkv, n, T, heads).reshape(n, T, D)

@@ -349,6 +349,7 @@ def test_layernorm_constant_row_uses_eps(oracle):
 @pytest.mark.parametrize("n,T,heads", [(2, 197, 12), (3, 5, 2), (2, 50, 3), (1, 33, 1), (1, 224, 2), (1, 32, 1),
                                        (2, 129, 2)])
 def test_attention(oracle, n, T, heads):
+    """The reference's order of operations; the accuracy test, against float64 at fp32-level bars: tests/test_gpu_attention_accuracy.py."""
     D = heads * 64
     qkv = u(30, (n * T, 3 * D), 1.5)
     got = B.attention(qkv, n, T, heads).reshape(n, T, D)
