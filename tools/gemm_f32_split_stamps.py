@@ -2,9 +2,10 @@
 """How long a K step of the split GEMMs' image walk waits for its fragments: the stamped instantiation of the persistent walk
 (probe library, tile code 129 with arith = 1 and a weight image; per workgroup [start, loop start, SUM of epilogue cycles, end,
 SUM of fragment waits, ..., tiles, K-steps]) on the four encoder GEMMs of the metric batch, without helper pieces.  A fragment wait
-runs from the top of a step to the point in front of the step's first matrix instruction where its twelve fragments have landed.
-(profiles/r21 holds the figures of the step before the pipelined one, which read its fragments on leaving its barrier: that arm
-was a build-time variant and is gone.)  GPU box only, probe library:
+runs from the top of a step (a segment's first step: from in front of its cold W request) to the point in front of the step's
+first matrix instruction where A's fragments have landed from LDS and all W loads but the youngest four in flight (A's two staging
+loads and W-mid's two) have landed from the image.  (profiles/r21 holds the figures of the steps that read W's fragments from LDS:
+those arms are gone.)  GPU box only, probe library:
     VIT_HIP_LIBRARY=.../libvit_mi355x_probe.so python3 tools/gemm_f32_split_stamps.py"""
 import ctypes as C, importlib, json, os, sys
 import numpy as np

@@ -318,11 +318,12 @@ __device__ __forceinline__ void split3_store(float *row, int kc, f32x4 x) {
 // ---- pre-split weights (vithip_gemm_args.w_split) and the swizzled LDS rows of the walk that reads them --------------------------
 // Image of W [N][K]: one block per (128-row panel, 16-deep K step), panel-major, K steps ascending inside a panel.  A block is
 // 3 planes x 128 rows x 16 bf16; its 16-byte chunk c = plane * 256 + 2 * row + half holds k 8 half .. 8 half + 7 of one plane of
-// one row.  Thread t of the walk's 256 copies chunks t, 256 + t and 512 + t of a K step: lane-linear 16-byte loads, and exactly
-// the (row t / 2, half t % 2) the same thread splits of A.
+// one row.  Chunks 2 * row + half of 32 consecutive rows of one plane are 1 KB in the order of a matrix instruction's B operand
+// (lane r + 32 h: row r, k 8 h .. 8 h + 7): the walk loads its W fragments from the image as they are (split3_step_pf).
 constexpr int WIMG_ROWS = 128;
 constexpr int WIMG_BLOCK_BYTES = 3 * WIMG_ROWS * SPLIT_BK * 2;  // 12 KB
-// LDS row of the image walk: 8 slots of 16 bytes, the six (plane, half) chunks s = 2 plane + half at slot s ^ split_swizzle(row).
+// LDS row of the image walk (A only): 8 slots of 16 bytes, the six (plane, half) chunks s = 2 plane + half at slot
+// s ^ split_swizzle(row).
 // Conflict-free both ways (MI355X LDS banking: ds_write_b128 in 8-lane groups on (a/4) mod 32, ds_read_b128 in 16-lane groups on
 // (a/4) mod 64):
 //   writes: 8 consecutive threads = one aligned quad of rows x both halves; (row & 3) ^ ((row >> 2) & 3) takes 4 distinct values
@@ -369,102 +370,123 @@ __device__ __forceinline__ void split3_step(f32x16 (&acc)[TM][TN], const float *
     }
 }
 
-// ---- the pipelined step of the image walk: the fragments of step g + 1 are read under the matrix instructions of step g ----------
-// Two LDS buffers and one barrier per step as before, but the barrier sits INSIDE the step, behind matrix instruction
-// SPLIT_PF_BARRIER: all restage writes into the other buffer go in front of it, and behind it that buffer holds step g + 1
-// complete, so its twelve fragment reads are issued two per gap under the rest of this step's matrix instructions.  The term order
-// kills the piece registers one after the other (W-lo behind instruction 3, A-lo 7, W-mid 15, A-mid 19, both hi 23 at 2 x 2
-// accumulators), so eight of the twelve reads land in registers that are already dead; the two hi pieces, live to the step's
-// end, are read into a spare set and moved over at the step's end.  A segment's first step reads its fragments at its top
-// (split3_read_cold) and its last step (PF = false) prefetches nothing: no fragment is live across an epilogue, where the
-// register count peaks.  The tiles are swizzled (SPLIT_LD_SW rows): As / Bs point at the lane's row r of the wave's first block,
-// poff[piece] is the lane's float offset of its chunk (2 piece + h) inside that row (the same for every block: blocks are 32 rows
-// apart and the swizzle repeats every 16).
-struct Split3PfRead { int w, piece, behind; };  // operand (0 = A, 1 = W), piece, the matrix instruction its reads go behind
+// ---- the step of the image walk: W's fragments straight from the image, A's through LDS ---------------------------------------
+// W.  A wave's fragment of one piece and one 32-row block is one contiguous 1 KB of the image, already in the matrix instruction's
+// operand order: lane (r, h) takes chunk plane * 256 + 2 * (wn * 64 + j * 32 + r) + h of the K step's block.  So W never enters LDS:
+// one 16-byte buffer load per lane, piece and block fetches the fragment where it is used, under the matrix instructions of the
+// step before (SPLIT_W_LOADS).  The term order kills W-lo behind instruction 3 and W-mid behind 15 (2 x 2 accumulators): those are
+// loaded in place behind their last use, 18 and 16 matrix instructions ahead of their first use in step g + 1; W-hi, live to the
+// step's end, goes into a spare set that is moved over at the top of step g + 1.  hi and lo are requested in front of the step's
+// two loads of A, which the next step's first restage slot waits for anyway (vmcnt retires in order: their wait is never the
+// longer one); mid behind them, for the eighth matrix instruction of the next step.
+// (A complete second register set for W, moved over at the step's top -- 12 v_mov_b64 instead of 4 -- gave back half of the gain:
+// +1.2 % against +2.5 % images/s at the metric configuration, profiles/r30.)
+// A.  Two LDS buffers of 128 swizzled rows (SPLIT_LD_SW) and one barrier per step.  Pipelined form (PFA, the fold consumers' and
+// the plain walks): the barrier sits INSIDE the step, behind matrix instruction SPLIT_PF_BARRIER: all restage writes into the other
+// buffer go in front of it, and behind it that buffer holds step g + 1 complete, so its six fragment reads are issued under the rest
+// of this step's matrix instructions.  The term order kills A-lo behind instruction 7 and A-mid behind 19 (2 x 2 accumulators), so
+// those are read in place; A-hi, live to the step's end, is read into a spare set and moved over at the step's end.  The residual
+// walks (PFA = false) read A's fragments at the step's top, behind the barrier at the end of the step before.
+// Segments.  A segment's first step reads A's fragments (split3_read_cold) and requests W's (the walk's cold load) at its top; its
+// last step (PF = false) prefetches neither: no fragment is live across an epilogue, where the register count peaks.  As points at
+// the lane's row r of the wave's first block, poff[piece] is the lane's float offset of its chunk (2 piece + h) inside that row
+// (the same for every block: blocks are 32 rows apart and the swizzle repeats every 16).
+struct Split3PfRead { int piece, behind; };  // A's piece, the matrix instruction its reads go behind
 constexpr int SPLIT_PF_BARRIER = 15;
-// both hi first (the moves out of the spare set at the next step's top wait for them), then in the order the next step's terms
-// need the rest: (hi, lo) (lo, hi) (mid, mid)
-constexpr Split3PfRead SPLIT_PF_READS[6] = {{0, 0, 15}, {1, 0, 16}, {1, 2, 17}, {0, 2, 18}, {0, 1, 19}, {1, 1, 20}};
+// hi first (the moves out of the spare set at the step's end wait for it), then in the order the next step's terms need the rest
+constexpr Split3PfRead SPLIT_PF_READS[3] = {{0, 15}, {2, 17}, {1, 19}};
+// W's loads of the next step: (piece, block j, the matrix instruction the load goes behind).  hi (into the spare set) in the first
+// gaps, lo and mid behind their last use, in gaps that carry neither an LDS write nor a fragment read of A.
+struct Split3WLoad { int piece, j, behind; };
+constexpr Split3WLoad SPLIT_W_LOADS[6] = {{0, 0, 1}, {0, 1, 2}, {2, 0, 5}, {2, 1, 6}, {1, 0, 16}, {1, 1, 18}};
 // Restage slots of the image walk's step (restage_fine of the walk): slot q goes behind matrix instruction at(q).  A's split in
 // quarters of a plane (two values: 4 vector instructions for hi and mid, 1 for lo), so that no gap between two matrix instructions
 // carries more than 4 of them plus one LDS write or one global load.
 //   q 0-3 hi quarters, 4 hi write | 5-8 mid quarters, 9 mid write | 10, 11 lo halves, 12 lo write | 13, 14 the loads of A
-//   15-17 W plane writes | 18-20 W image loads (each behind its plane's write)
 struct Split3SlotsFine {
-    static constexpr int N = 21;
+    static constexpr int N = 15;
     static constexpr int at(int q) {
-        constexpr int gap[N] = {0, 1, 2, 3, 4, 4, 5, 6, 7, 8, 8, 9, 10, 12, 13, 1, 5, 9, 2, 6, 11};
+        constexpr int gap[N] = {0, 1, 2, 3, 4, 4, 5, 6, 7, 8, 8, 9, 10, 12, 13};
         return gap[q];
     }
 };
-// last matrix instruction (of 6 x per_term) that reads piece `piece` of operand w
+// last matrix instruction (of 6 x per_term) that reads piece `piece` of operand w (0 = A, 1 = W)
 constexpr int split3_last_use(int w, int piece, int per_term) {
     int last = -1;
     for (int t = 0; t < 6; ++t)
         if ((w ? SPLIT_TERM_W[t] : SPLIT_TERM_A[t]) == piece) last = (t + 1) * per_term - 1;
     return last;
 }
-constexpr bool split3_pf_schedule_ok(int per_term) {
-    for (int q = 0; q < Split3SlotsFine::N; ++q)  // every restage write in front of the barrier
+constexpr bool split3_pf_schedule_ok(int per_term, int blocks_w) {
+    for (int q = 0; q < Split3SlotsFine::N; ++q)  // every restage write of A in front of the barrier
         if (Split3SlotsFine::at(q) < 0 || Split3SlotsFine::at(q) > SPLIT_PF_BARRIER) return false;
-    bool seen[2][3] = {};
-    for (int e = 0; e < 6; ++e) {
+    bool seen[3] = {};
+    for (int e = 0; e < 3; ++e) {
         const Split3PfRead rd = SPLIT_PF_READS[e];
         if (rd.behind < SPLIT_PF_BARRIER || rd.behind >= 6 * per_term) return false;  // every read of the other buffer behind it
-        // mid and lo are overwritten in place: behind their last use (hi goes to the other set)
-        if (rd.piece != 0 && rd.behind < split3_last_use(rd.w, rd.piece, per_term)) return false;
+        // mid and lo are overwritten in place: behind their last use (hi goes to the spare set)
+        if (rd.piece != 0 && rd.behind < split3_last_use(0, rd.piece, per_term)) return false;
         if (e > 0 && rd.behind < SPLIT_PF_READS[e - 1].behind) return false;
-        seen[rd.w][rd.piece] = true;
+        seen[rd.piece] = true;
     }
-    for (int w = 0; w < 2; ++w)
-        for (int pc = 0; pc < 3; ++pc)
-            if (!seen[w][pc]) return false;
-    return true;
+    for (int pc = 0; pc < 3; ++pc)
+        if (!seen[pc]) return false;
+    // W: every (piece, block) requested once; mid and lo are overwritten in place: behind their last use (hi goes to the spare set)
+    int asked = 0;
+    for (int e = 0; e < 6; ++e) {
+        const Split3WLoad ld = SPLIT_W_LOADS[e];
+        if (ld.piece < 0 || ld.piece > 2 || ld.j < 0 || ld.j >= blocks_w) return false;
+        if (ld.behind < 0 || ld.behind >= 6 * per_term) return false;
+        if (ld.piece != 0 && ld.behind < split3_last_use(1, ld.piece, per_term)) return false;
+        if (e > 0 && ld.behind < SPLIT_W_LOADS[e - 1].behind) return false;
+        asked |= 1 << (ld.piece * blocks_w + ld.j);
+    }
+    return asked == (1 << (3 * blocks_w)) - 1;
 }
 template <int TM, int TN>
 struct Split3Frags {
-    bf16x8 a[TM][3], b[TN][3];  // the step's pieces; mid and lo of the next step are read in place
+    bf16x8 a[TM][3], b[TN][3];  // the step's pieces; mid and lo of the next step are read (A) and loaded (W) in place
     bf16x8 a_hn[TM], b_hn[TN];  // hi of the next step (hi of this one is live to the step's last matrix instruction)
 };
-// the reads of entry e of SPLIT_PF_READS from the tiles As / Bs; NEXT: hi goes to the spare set
+// where a W load of the next step lands
+template <int TM, int TN>
+__device__ __forceinline__ bf16x8 &split3_w_dst(Split3Frags<TM, TN> &f, int piece, int j) {
+    return piece != 0 ? f.b[j][piece] : f.b_hn[j];
+}
+// the reads of entry e of SPLIT_PF_READS from the tile As; NEXT: hi goes to the spare set
 template <int TM, int TN, bool NEXT>
-__device__ __forceinline__ void split3_read_piece(Split3Frags<TM, TN> &f, const float *As, const float *Bs, const int (&poff)[3], int e) {
+__device__ __forceinline__ void split3_read_piece(Split3Frags<TM, TN> &f, const float *As, const int (&poff)[3], int e) {
     const Split3PfRead rd = SPLIT_PF_READS[e];
-    if (rd.w == 0) {
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const bf16x8 v = *reinterpret_cast<const bf16x8 *>(As + i * 32 * SPLIT_LD_SW + poff[rd.piece]);
-            if (NEXT && rd.piece == 0) f.a_hn[i] = v;
-            else f.a[i][rd.piece] = v;
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const bf16x8 v = *reinterpret_cast<const bf16x8 *>(Bs + j * 32 * SPLIT_LD_SW + poff[rd.piece]);
-            if (NEXT && rd.piece == 0) f.b_hn[j] = v;
-            else f.b[j][rd.piece] = v;
-        }
+    for (int i = 0; i < TM; ++i) {
+        const bf16x8 v = *reinterpret_cast<const bf16x8 *>(As + i * 32 * SPLIT_LD_SW + poff[rd.piece]);
+        if (NEXT && rd.piece == 0) f.a_hn[i] = v;
+        else f.a[i][rd.piece] = v;
     }
 }
-// A segment's first step: its fragments from its own buffer (As / Bs), read at the top, in the order the prefetch reads them
+// A's fragments of a step from its own buffer, read at the step's top, in the order the prefetch reads them
 template <int TM, int TN>
-__device__ __forceinline__ void split3_read_cold(Split3Frags<TM, TN> &f, const float *As, const float *Bs, const int (&poff)[3]) {
+__device__ __forceinline__ void split3_read_cold(Split3Frags<TM, TN> &f, const float *As, const int (&poff)[3]) {
 #pragma unroll
-    for (int e = 0; e < 6; ++e) split3_read_piece<TM, TN, false>(f, As, Bs, poff, e);
+    for (int e = 0; e < 3; ++e) split3_read_piece<TM, TN, false>(f, As, poff, e);
 }
 struct Split3NoHook {
     __device__ __forceinline__ void operator()() const {}
 };
-// One step from the fragments in f; restage(q), q < Split3SlotsFine::N, behind matrix instruction Split3SlotsFine::at(q); sync()
-// is the step's barrier; PF: the fragments of the next step from the other buffer (An / Bn) into f; landed(): a hook in front of
-// the first matrix instruction (the stamped probe instantiation; nothing otherwise).
-template <int TM, int TN, bool PF, typename Restage, typename Sync, typename Landed = Split3NoHook>
-__device__ __forceinline__ void split3_step_pf(f32x16 (&acc)[TM][TN], Split3Frags<TM, TN> &f, const float *An, const float *Bn,
-                                               const int (&poff)[3], Restage &&restage, Sync &&sync, Landed &&landed = Landed{}) {
+// One step from the fragments in f, W's hi moving over from the spare set first (requested a step ago, or by the segment's cold
+// load); restage(q), q < Split3SlotsFine::N, behind matrix instruction Split3SlotsFine::at(q); sync() is the step's barrier; PFW:
+// the W fragments of the next step by load_w(piece, j) into split3_w_dst; PFA: A's fragments of the next step from the other buffer
+// (An) into f; landed(): a hook in front of the first matrix instruction (the stamped probe instantiation; nothing otherwise).
+template <int TM, int TN, bool PFA, bool PFW, typename Restage, typename LoadW, typename Sync, typename Landed = Split3NoHook>
+__device__ __forceinline__ void split3_step_pf(f32x16 (&acc)[TM][TN], Split3Frags<TM, TN> &f, const float *An, const int (&poff)[3],
+                                               Restage &&restage, LoadW &&load_w, Sync &&sync, Landed &&landed = Landed{}) {
     constexpr int NM = 6 * TM * TN;
     static_assert(NM == 24, "the schedule table is laid out for 2 x 2 accumulators");
-    static_assert(split3_pf_schedule_ok(TM * TN),
-                  "restage writes in front of the barrier, reads of the other buffer behind it and behind the last use of what they overwrite");
+    static_assert(split3_pf_schedule_ok(TM * TN, TN),
+                  "A: restage writes in front of the barrier, reads of the other buffer behind it and behind the last use of what they "
+                  "overwrite; W: every fragment requested once, mid and lo behind their last use");
+#pragma unroll
+    for (int j = 0; j < TN; ++j) f.b[j][0] = f.b_hn[j];
     landed();
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -472,22 +494,25 @@ __device__ __forceinline__ void split3_step_pf(f32x16 (&acc)[TM][TN], Split3Frag
         const int t = idx / (TM * TN), i = (idx / TN) % TM, j = idx % TN;
         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[i][SPLIT_TERM_A[t]], f.b[j][SPLIT_TERM_W[t]], acc[i][j], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (PFW) {
+#pragma unroll
+            for (int e = 0; e < 6; ++e)
+                if (SPLIT_W_LOADS[e].behind == idx) split3_w_dst(f, SPLIT_W_LOADS[e].piece, SPLIT_W_LOADS[e].j) = load_w(SPLIT_W_LOADS[e].piece, SPLIT_W_LOADS[e].j);
+        }
 #pragma unroll
         for (int q = 0; q < Split3SlotsFine::N; ++q)
             if (Split3SlotsFine::at(q) == idx) restage(q);
         if (idx == SPLIT_PF_BARRIER) sync();
-        if constexpr (PF) {
+        if constexpr (PFA) {
 #pragma unroll
-            for (int e = 0; e < 6; ++e)
-                if (SPLIT_PF_READS[e].behind == idx) split3_read_piece<TM, TN, true>(f, An, Bn, poff, e);
+            for (int e = 0; e < 3; ++e)
+                if (SPLIT_PF_READS[e].behind == idx) split3_read_piece<TM, TN, true>(f, An, poff, e);
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-    if constexpr (PF) {
+    if constexpr (PFA) {
 #pragma unroll
         for (int i = 0; i < TM; ++i) f.a[i][0] = f.a_hn[i];
-#pragma unroll
-        for (int j = 0; j < TN; ++j) f.b[j][0] = f.b_hn[j];
     }
 }
 

@@ -51,12 +51,17 @@ constexpr int SK_HEADER_BYTES = 4096, SK_MAX_OWNERS = 1000, SK_STAT_TAKEN = 1016
 // ARITH = ARITH_SPLIT3: the three-piece split on the bf16 matrix pipe (vit_gemm_common.hpp): the same walk, hand-over and
 // epilogues, K step SPLIT_BK, LDS rows of SPLIT_LD floats (56 KB at 128 x 128).
 // WIMG (split only): W's pieces come ready-made from the weight image p.w_split and A is split in registers -- no vector
-// instruction touches W in the loop.  Staging per thread and K step: 8 consecutive k of one row of A (two 16-byte loads, split
-// into three 16-byte plane chunks) and three 16-byte image chunks of W, all written with ds_write_b128 into swizzled rows of
-// SPLIT_LD_SW floats (64 KB), conflict-free (see split_swizzle).  The same pieces in the same places of the product: the same
-// bits as WIMG = false.  A's split is dealt out in quarters of a plane over the first 14 gaps between the step's matrix
-// instructions (restage_fine) and, except under the residual epilogues, the fragments of the next step are read under this
-// step's matrix instructions (PIPE, split3_step_pf).
+// instruction and no LDS instruction touches W in the loop.  A wave loads its W fragments of the next K step straight from the
+// image, in matrix operand order, under this step's matrix instructions (TN x 3 16-byte buffer loads per lane and step: mid and
+// lo in place behind their last use, hi into a spare set; split3_step_pf).
+// LDS holds A only: per thread and K step 8 consecutive k of one row of A (two 16-byte loads, split into three 16-byte plane
+// chunks) written with ds_write_b128 into swizzled rows of SPLIT_LD_SW floats (two buffers, 32 KB), conflict-free (see
+// split_swizzle).  The same pieces in the same places of the product: the same bits as WIMG = false.  A's split is dealt out in
+// quarters of a plane over the first 14 gaps between the step's matrix instructions (restage_fine) and, except under the residual
+// epilogues, A's fragments of the next step are read under this step's matrix instructions (PIPE).
+// (Measured against the step that copied W's chunks through LDS -- 3 ds_write_b128 and 6 ds_read_b128 more per wave and step,
+// 64 KB: +2.3 % images/s at the metric configuration; per launch in the forward the residual walks -4.9 %, QKV -1.8 %,
+// fc1 -1.4 %: profiles/r30.)
 template <int BM, int BN, int WM, int WN, int EPI, bool STAMP = false, bool SK = false, int DBG = 0, int ARITH = ARITH_F32,
           bool WIMG = false>
 __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const GemmParams p) {
@@ -64,7 +69,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
     static_assert(!SPLIT || DBG == 0, "switch-off builds are fp32 only");
     static_assert(!WIMG || (SPLIT && BM == WIMG_ROWS && BN == WIMG_ROWS), "the weight image feeds the 128x128 split walk");
     // The pipelined step pays under the fold consumers' walks (QKV, fc1) and not under the residual ones (out_proj, fc2), which are
-    // faster with the finer slots alone: measured per launch at batch 256, profiles/r21.
+    // faster with the finer slots alone: measured per launch at batch 256, profiles/r21, and again with W fed from the image
+    // (fc2 +1.5 % per launch and -0.6 % images/s with the residual walks pipelined too, profiles/r30).
     constexpr bool PIPE = WIMG && EPI != VITHIP_EPI_BIAS_RESIDUAL && EPI != EPI_RESIDUAL_STATS;
     constexpr int PBK = SPLIT ? SPLIT_BK : vitgemm::PBK;  // K step
     constexpr int PLD = WIMG ? SPLIT_LD_SW : SPLIT ? SPLIT_LD : vitgemm::PLD;  // LDS row (floats)
@@ -75,13 +81,13 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
     constexpr int B_CHUNKS = BN * (PBK / 4) / 256;
     constexpr int NC = PBK / 8;              // 8-deep chunks per K step (fp32)
     constexpr int NS = A_CHUNKS + B_CHUNKS;  // staged float4 per thread per K step
-    constexpr int W_CHUNKS = 3;              // WIMG: image chunks per thread per K step (one per plane)
-    constexpr int NL = WIMG ? A_CHUNKS + W_CHUNKS : NS;  // global loads per thread per K step
-    static_assert(!WIMG || (A_CHUNKS == 2 && BM * 2 == 256 && BN * 2 == 256), "WIMG: one 8-deep half row of A and of W per thread");
+    constexpr int W_FRAGS = 3 * TN;          // WIMG: image chunks per lane per K step (one per plane and 32-row block of the wave)
+    constexpr int NL = WIMG ? A_CHUNKS + W_FRAGS : NS;  // global loads per thread per (prefetching) K step
+    static_assert(!WIMG || (A_CHUNKS == 2 && BM * 2 == 256), "WIMG: one 8-deep half row of A per thread");
     constexpr int NM = 4 * TM * TN;          // MFMAs per chunk
     static_assert((BM / WM) * WGN == 4, "4 waves per workgroup");
 
-    __shared__ __attribute__((aligned(16))) float lds[2 * (BM + BN) * PLD];
+    __shared__ __attribute__((aligned(16))) float lds[2 * (WIMG ? BM : BM + BN) * PLD];  // WIMG: A only
     __shared__ int sk_decision;  // owner: 1 = the helper's piece is there (written by thread 0, read by all after a barrier)
     // LayerNorm fold, consumer epilogues: (rstd, mean) of the tile's BM rows = 1 KB, copied here when the tile BEGINS by one
     // global -> LDS instruction of wave 0 (16 bytes per lane), written as inline assembly so that it stays off the compiler's
@@ -97,7 +103,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
     __shared__ __attribute__((aligned(16))) f32x2 fold_rows_lds[FOLD ? 2 * BM : 2];
     static_assert(!FOLD || BM == 128, "one 16-byte lane copy of 64 lanes = 128 rows");
     float *const As0 = lds;
-    float *const Bs0 = lds + 2 * BM * PLD;
+    float *const Bs0 = WIMG ? lds : lds + 2 * BM * PLD;  // (WIMG: unused)
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
@@ -105,15 +111,16 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
     const int wm = wave / WGN, wn = wave % WGN;
 
     unsigned long long st0 = 0, st_rt0 = 0, st_loop0 = 0, st_epi = 0;
-    // WIMG stamps: the sum over the K steps of the cycles from the step's top (the plain step: leaving its barrier) to the point in
-    // front of its first matrix instruction where its twelve fragments have landed
+    // WIMG stamps: the sum over the K steps of the cycles from the step's top (the plain step: leaving its barrier; a segment's
+    // first step: in front of its cold W request) to the point in front of its first matrix instruction where A's fragments (LDS)
+    // and the W fragments that instruction needs have landed: everything but the youngest four loads, A's two and W-mid's two
     [[maybe_unused]] unsigned long long st_frag = 0, st_top = 0, st_landed = 0;
     auto stamp_top = [&]() __attribute__((always_inline)) {
         if constexpr (STAMP && WIMG) st_top = __builtin_amdgcn_s_memtime();
     };
     auto stamp_landed = [&]() __attribute__((always_inline)) {
         if constexpr (STAMP && WIMG) {
-            __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0), nothing else
+            __builtin_amdgcn_s_waitcnt(0x0074);  // lgkmcnt(0) and vmcnt(4)
             st_landed = __builtin_amdgcn_s_memtime();
         }
     };
@@ -159,7 +166,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
 
     const int ld_row = tid / (PBK / 4);
     const int ld_kc = (tid % (PBK / 4)) * 4;
-    // WIMG: thread t stages row t / 2, k 8 (t % 2) .. 8 (t % 2) + 7 of A and of W; wr_off[plane] = its chunk's place in a tile
+    // WIMG: thread t stages row t / 2, k 8 (t % 2) .. 8 (t % 2) + 7 of A; wr_off[plane] = its chunk's place in a tile
     const int sw_row = tid >> 1, sw_half = tid & 1;
     int wr_off[3];
 #pragma unroll
@@ -172,9 +179,12 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
     const __amdgpu_buffer_rsrc_t w_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(WIMG ? p.w_split : static_cast<const void *>(p.W)), 0, 0x7fffffff, 0x00020000);
     int a_src[A_CHUNKS];  // byte offsets
-    int b_src[WIMG ? W_CHUNKS : B_CHUNKS];
+    int b_src[B_CHUNKS];
     f32x4 a_stage[A_CHUNKS], b_stage[B_CHUNKS];
-    u32x4 w_stage[WIMG ? W_CHUNKS : 1];  // WIMG: the image chunks in flight
+    // WIMG: the lane's chunk (row wn * WN + r, half h) of plane 0 and block j = 0 inside an image block, and the panel of the
+    // COMPUTE cursor's tile (scalar; set by begin_segment): W's fragments follow the matrix instructions, not the staging of A
+    const int w_lane = WIMG ? ((wn * WN + r) * 2 + h) * 16 : 0;
+    [[maybe_unused]] int w_panel = 0;
 
     auto set_sources = [&](int tile) {
         int tm, tn;
@@ -184,9 +194,6 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
             m = m < p.M ? m : p.M - 1;
 #pragma unroll
             for (int i = 0; i < A_CHUNKS; ++i) a_src[i] = (m * p.lda + 8 * sw_half + 4 * i) * 4;
-            // the tile's panel of the image: its blocks follow each other in K (the K step is the loads' scalar offset)
-#pragma unroll
-            for (int q = 0; q < W_CHUNKS; ++q) b_src[q] = tn * nk * WIMG_BLOCK_BYTES + (q * 256 + tid) * 16;
             return;
         }
 #pragma unroll
@@ -268,11 +275,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
         const int k0 = k_l * PBK;
 #pragma unroll
         for (int i = 0; i < A_CHUNKS; ++i) a_stage[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, a_src[i], k0 * 4, 0));
-        if constexpr (WIMG) {
-#pragma unroll
-            for (int q = 0; q < W_CHUNKS; ++q) w_stage[q] = __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, b_src[q], k_l * WIMG_BLOCK_BYTES, 0);
-            return;
-        }
+        if constexpr (WIMG) return;
 #pragma unroll
         for (int i = 0; i < B_CHUNKS; ++i) b_stage[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, b_src[i], k0 * 4, 0));
     };
@@ -281,19 +284,15 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
         if constexpr (SPLIT) split3_store(row, ld_kc, v);
         else *reinterpret_cast<f32x4 *>(row + ld_kc) = v;
     };
-    // WIMG: the A chunk of plane `pl` (split off what the earlier planes left of a_stage) / the W image chunk of plane `pl`
+    // WIMG: the A chunk of plane `pl` (split off what the earlier planes left of a_stage)
     auto write_a_plane = [&](float *As, int pl) __attribute__((always_inline)) {
         *reinterpret_cast<u32x4 *>(As + wr_off[pl]) = split3_piece8(a_stage[0], a_stage[1], pl);
     };
-    auto write_w_plane = [&](float *Bs, int pl) __attribute__((always_inline)) { *reinterpret_cast<u32x4 *>(Bs + wr_off[pl]) = w_stage[pl]; };
     auto store_step = [&](int buf) {
         float *As = As0 + buf * BM * PLD, *Bs = Bs0 + buf * BN * PLD;
         if constexpr (WIMG) {
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl) {
-                write_a_plane(As, pl);
-                write_w_plane(Bs, pl);
-            }
+            for (int pl = 0; pl < 3; ++pl) write_a_plane(As, pl);
             return;
         }
 #pragma unroll
@@ -337,13 +336,16 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
                 quarter(2 * sub);
                 quarter(2 * sub + 1);
             } else *reinterpret_cast<u32x4 *>(As0 + buf * BM * PLD + wr_off[pl]) = a_plane;
-        } else if (q <= 14) {
-            a_stage[q - 13] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, a_src[q - 13], k0 * 4, 0));
-        } else if (q <= 17) {
-            write_w_plane(Bs0 + buf * BN * PLD, q - 15);
         } else {
-            w_stage[q - 18] = __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, b_src[q - 18], (k0 / PBK) * WIMG_BLOCK_BYTES, 0);
+            a_stage[q - 13] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, a_src[q - 13], k0 * 4, 0));
         }
+    };
+    // WIMG: the lane's W fragment (piece `pl`, 32-row block j of the wave's columns) of K step k of the compute cursor's tile,
+    // from the image.  The plane goes into the scalar offset and the block is a constant added to the lane's offset (hipcc keeps
+    // the sum in a second register): no vector arithmetic in the loop.
+    auto load_w_frag = [&](int pl, int j, int k) __attribute__((always_inline)) {
+        return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, w_lane + j * (32 * 2 * 16),
+                                                                                 w_panel + k * WIMG_BLOCK_BYTES + pl * (WIMG_ROWS * 2 * 16), 0));
     };
     // The pipelined step's restage hook: restage_fine and nothing else.  (It stays a closure of its own: without it hipcc orders two
     // moves in the preamble of the probe build's stamped residual walks differently, profiles/r28.)
@@ -352,7 +354,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
     };
 
     const int a_frag_off = WIMG ? (wm * WM + r) * PLD : (wm * WM + r) * PLD + h * 4;
-    const int b_frag_off = WIMG ? (wn * WN + r) * PLD : (wn * WN + r) * PLD + h * 4;
+    const int b_frag_off = (wn * WN + r) * PLD + h * 4;  // (the image walk reads no W from LDS)
     int frag_poff[3];  // WIMG: the lane's chunk (2 piece + h) inside its rows (the swizzle repeats every 16 rows)
 #pragma unroll
     for (int pc = 0; pc < 3; ++pc) frag_poff[pc] = WIMG ? split_sw_offset(r, 2 * pc + h) - r * PLD : 0;
@@ -441,6 +443,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
         tile_coords(g.tile, p.tiles_m, p.tiles_n, p.group_m, tm, tn);
         m0 = tm * BM;
         n0 = tn * BN;
+        if constexpr (WIMG) w_panel = tn * nk * WIMG_BLOCK_BYTES;  // the tile's panel of the image: its blocks follow each other in K
         k_c = g.k0;
         seg_k0 = g.k0;
         kend_c = g.k1;
@@ -521,28 +524,44 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
 
     if constexpr (STAMP) st_loop0 = __builtin_amdgcn_s_memtime();
     int cur = 0;
-    if constexpr (PIPE) {
-        // The pipelined step (split3_step_pf): segment by segment, so that the fragments are dead at every epilogue by
-        // construction -- a segment's first step reads them at its top, its last step prefetches none.  The load cursor,
-        // the restage slots (all in front of the step's barrier now), the hand-over and the fold's counted wait are the flat
-        // loop's: a step still issues its NL global loads, and the copy is still waited for at the top of the tile's last step.
+    if constexpr (WIMG) {
+        // The image walk (split3_step_pf): segment by segment, so that the fragments are dead at every epilogue by construction --
+        // a segment's first step requests W's fragments from the image and reads A's at its top (one exposed load latency per
+        // segment), its last step prefetches none.  The load cursor of A, the restage slots, the hand-over and the fold's counted
+        // wait are the flat loop's: a prefetching step issues its NL global loads, and the copy is still waited for at the top of
+        // the tile's last step.
+        // PIPE: A's fragments of the next step are read under this step's matrix instructions, behind the barrier inside the step.
+        // The residual walks: A's fragments at the step's top, the barrier at the step's end, the finer slots and W's feed alone.
         Split3Frags<TM, TN> frags;
         auto tile_a = [&](int buf) { return As0 + buf * BM * PLD + a_frag_off; };
-        auto tile_b = [&](int buf) { return Bs0 + buf * BN * PLD + b_frag_off; };
         auto step = [&](auto prefetch) __attribute__((always_inline)) {
             constexpr bool PF = decltype(prefetch)::value;
-            const int k_ahead = k_l * PBK;  // offset of the step the restage loads fetch (two steps ahead)
-            split3_step_pf<TM, TN, PF>(acc, frags, tile_a(cur ^ 1), tile_b(cur ^ 1), frag_poff,
-                [&](int q) __attribute__((always_inline)) { restage_any(q, cur ^ 1, k_ahead); }, [] { __syncthreads(); }, stamp_landed);
+            const int k_ahead = k_l * PBK;  // offset of the step the restage loads of A fetch (two steps ahead)
+            if constexpr (!PIPE) split3_read_cold<TM, TN>(frags, tile_a(cur), frag_poff);
+            split3_step_pf<TM, TN, PF && PIPE, PF>(acc, frags, tile_a(cur ^ 1), frag_poff,
+                [&](int q) __attribute__((always_inline)) { restage_any(q, cur ^ 1, k_ahead); },
+                [&](int pl, int j) __attribute__((always_inline)) { return load_w_frag(pl, j, k_c + 1); },
+                [] { if constexpr (PIPE) __syncthreads(); }, stamp_landed);
             stamp_step();
-            stamp_top();
+            if constexpr (PIPE) stamp_top();
             advance_load_cursor();
+            if constexpr (!PIPE) {
+                __syncthreads();
+                stamp_top();  // the residual walks' step begins on leaving its barrier
+            }
             cur ^= 1;
             ++k_c;
         };
         for (;;) {
             stamp_top();
-            split3_read_cold<TM, TN>(frags, tile_a(cur), tile_b(cur), frag_poff);
+#pragma unroll
+            for (int e = 0; e < 6; ++e)
+                split3_w_dst(frags, SPLIT_W_LOADS[e].piece, SPLIT_W_LOADS[e].j) = load_w_frag(SPLIT_W_LOADS[e].piece, SPLIT_W_LOADS[e].j, k_c);
+            if constexpr (PIPE) split3_read_cold<TM, TN>(frags, tile_a(cur), frag_poff);
+            // The cold fragments have LANDED before the steps begin -- said with the builtin, which the compiler's wait-count pass
+            // reads: fragments "possibly still in flight" at the loop header would make it wait for everything in flight at the top
+            // of EVERY step (it merges the two ways into the loop), where the warm step leaves the youngest loads in flight.
+            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), nothing else
             while (k_c + 1 < kend_c) step(std::true_type{});
             fold_rows_landed();
             step(std::false_type{});
@@ -553,17 +572,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
     for (int g = 0; g < steps; ++g) {
         const int k_ahead = k_l * PBK;  // offset of the step the restage loads fetch (step g + 2)
         if (k_c + 1 == kend_c) fold_rows_landed();
-        if constexpr (WIMG) {
-            // the residual walks: fragments behind the barrier, the barrier at the step's end, the finer slots
-            Split3Frags<TM, TN> frags;
-            stamp_top();
-            split3_read_cold<TM, TN>(frags, As0 + cur * BM * PLD + a_frag_off, Bs0 + cur * BN * PLD + b_frag_off, frag_poff);
-            split3_step_pf<TM, TN, false>(acc, frags, nullptr, nullptr, frag_poff,
-                [&](int q) __attribute__((always_inline)) { restage_fine(q, cur ^ 1, k_ahead); }, [] {}, stamp_landed);
-            stamp_step();
-            advance_load_cursor();
-            __syncthreads();
-        } else if constexpr (SPLIT) {
+        if constexpr (SPLIT) {
             // one 16-deep step of the split: pieces from buffer `cur`, the staged step g + 1 split into cur^1 and the loads of step
             // g + 2 in the first half of the matrix instructions, then the one barrier (the fp32 loop's swap point)
             split3_step<TM, TN, NS>(acc, As0 + cur * BM * PLD + a_frag_off, Bs0 + cur * BN * PLD + b_frag_off,
