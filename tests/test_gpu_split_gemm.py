@@ -1,6 +1,8 @@
 """The three-piece split of the fp32 GEMMs on the bf16 matrix pipe (vithip_gemm_args.arith = 1, vit_engine_options.fp32_split;
 DESIGN.md 4.1.1): accuracy against float64 and against the fp32-MFMA arithmetic on the same operands, exactness where the
-arithmetic promises it, the same bits on every tile code, the LayerNorm fold's hard cases, and the engine end to end."""
+arithmetic promises it, the same bits on every tile code, the LayerNorm fold's hard cases, and the engine end to end.
+The kernel these tests compare with (tile = 10, arith = ARITH_SPLIT3) is itself held to float64 and to a bit-exact host model in
+tests/test_gpu_split_gemm_accuracy.py."""
 import math
 import os
 

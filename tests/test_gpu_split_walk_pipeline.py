@@ -10,7 +10,9 @@ next to the last, odd and even numbers of prefetching steps between them, and ti
 
 A segment of a single 16-deep step cannot occur: K is a multiple of 32 (vitgemm::KALIGN), so a whole tile has an even number of
 steps, at least two, and the hand-over cuts a tile at a multiple of 32 in k as well (persistent_piece_steps chooses the piece in
-32-deep steps, at least four of them, and leaves the owner at least eight): both parts are even and longer than one step."""
+32-deep steps, at least four of them, and leaves the owner at least eight): both parts are even and longer than one step.
+The kernel these tests compare with (tile = 10, arith = ARITH_SPLIT3) is itself held to float64 and to a bit-exact host model in
+tests/test_gpu_split_gemm_accuracy.py."""
 import functools
 
 import numpy as np

@@ -6,7 +6,9 @@ patterns, with the operand recipe (`hard`) of tests/test_gpu_split_walk_pipeline
 
 What can go wrong here is an address (the lane -> chunk map: plane, half, 32-row block, the wave's column offset, the tile's panel,
 the K step) or a moment (a fragment used before it landed, or overwritten before its last use: first and last steps of a segment,
-odd and even numbers of prefetching steps, a cold request behind an epilogue, behind unpark and in front of park)."""
+odd and even numbers of prefetching steps, a cold request behind an epilogue, behind unpark and in front of park).
+The kernel these tests compare with (tile = 10, arith = ARITH_SPLIT3) is itself held to float64 and to a bit-exact host model in
+tests/test_gpu_split_gemm_accuracy.py."""
 import functools
 
 import numpy as np

@@ -1,7 +1,9 @@
 """Pre-split weight images (vithip_split3_weights_f32, vithip_gemm_args.w_split): the persistent split walk that
 stages W's pieces from the image and splits only A must give the bits of the walk that splits both on the fly -- every epilogue,
 the hand-over, tiles 0 and 9, the four ViT-B/16 shapes at the metric batch, ragged N and M, hard operands -- and the engine, which
-builds the images on upload, must give the bits of an engine held to the on-the-fly kernel (gemm_tile = 10)."""
+builds the images on upload, must give the bits of an engine held to the on-the-fly kernel (gemm_tile = 10).
+The kernel these tests compare with (tile = 10, arith = ARITH_SPLIT3) is itself held to float64 and to a bit-exact host model in
+tests/test_gpu_split_gemm_accuracy.py."""
 import numpy as np
 import pytest
 
