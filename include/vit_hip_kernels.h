@@ -111,7 +111,8 @@ typedef struct {
     /* tuning, per call (the library keeps no process-wide tuning state); 0 = auto:
      * tile: 0 = auto (persistent walk of 128x128 tiles from ~1,280 tiles on, 64x64 / 32x32 tiles as the problem
      *   shrinks); one software-pipelined tile per workgroup: 10 = 128x128, 6 = 128x128 with K step 16, 7 = 256x128, 8 = 128x64,
-     *   11 = 64x64; 12 = 32x32 on 16x16x4 MFMA (K % 128 == 0); 9 = persistent 128x128.  All of them give the same bits.
+     *   11 = 64x64; 12 = 32x32 on 16x16x4 MFMA (K % 128 == 0); 9 = persistent 128x128 (with arith = 1 and w_split: 64x256 where
+     *   N % 256 == 0, see w_split).  All of them give the same bits.
      * group_m: tile rows per L2 group of the XCD-aware tile walk (0 = default: plain N-fastest order when N is at most 8 tiles of
      *   128 wide, groups of 4 tile rows beyond that; 1 = plain N-fastest order). */
     int tile, group_m;
@@ -148,9 +149,10 @@ typedef struct {
      * tile codes 0, 9, 10 and 11 are accepted and give the same bits as each other; 6, 7, 8 and 12 are refused. */
     int arith;
     /* optional, arith = 1 only: W's pieces made ahead of time by vithip_split3_weights_f32(W, ldw, N, K) (16-byte aligned; NULL =
-     * split W on the fly).  The 128x128 persistent walk (tile 9, or auto where it picks the walk) then stages W's pieces straight
-     * from the image and splits only A; every other kernel ignores the field.  The pieces are the ones the on-the-fly split makes,
-     * so the result has the same bits with and without it. */
+     * split W on the fly).  The persistent walk (tile 9, or auto where it picks the walk) then feeds W's pieces straight from the
+     * image and splits only A: in 64x256 tiles where N % 256 == 0 (four waves side by side share one split of A), in 128x128 tiles
+     * otherwise (vithip_gemm_f32_walk_tile() says which); every other kernel ignores the field.  The pieces are the ones the
+     * on-the-fly split makes, so the result has the same bits with and without it, in either tile. */
     const void *w_split;
     /* the LayerNorm epsilon of stats_out (ignored without it): 0 = VITHIP_LN_EPS, else a finite positive double */
     double stats_eps;
@@ -166,6 +168,10 @@ int vithip_gemm_f32(vithip_stream_t stream, const vithip_gemm_args *args);
 size_t vithip_split3_weights_bytes(int N, int K);
 int vithip_split3_weights_f32(vithip_stream_t stream, const float *W, int ldw, int N, int K, void *out);
 int vithip_gemm_f32_stats_in_epilogue(const vithip_gemm_args *args);  /* 1 / 0 (0 also for arguments vithip_gemm_f32 would refuse) */
+/* Host only, launches nothing: the tile (*bm rows x *bn columns) the persistent walk takes for these arguments -- 64 x 256 for the
+ * image walk (arith = 1 with w_split) where N % 256 == 0, 128 x 128 otherwise -- whether or not the call's tile code picks the
+ * walk.  A pure function of N, the epilogue (with ln_rows / the row statistics), arith and w_split.  0, or hipErrorInvalidValue. */
+int vithip_gemm_f32_walk_tile(const vithip_gemm_args *args, int *bm, int *bn);
 /* ---- LayerNorm folding, fp32: LN(x) . W^T + b = rstd * (x . (gamma*W)^T) - rstd * mean * colsum(gamma*W) + (b + W . beta).
  * Wf[n][k] = gamma[k] * W[n][k] (fp32 product); colsum[n] = sum_k Wf[n][k] and bias_f[n] = bias[n] + sum_k beta[k] * W[n][k], both
  * accumulated in double and rounded once.  W fp32 [N][K], K % 4 == 0, 16-byte aligned. */

@@ -562,7 +562,7 @@ def gemm(A, W, bias, residual=None, epilogue=EPI_BIAS, tile: int = 0, group_m: i
          handover_test: int = 0, stats: Optional[dict] = None, ln=None, row_stats: Optional[dict] = None,
          arith: int = ARITH_F32, w_split: bool = False, lda: Optional[int] = None, ldw: Optional[int] = None,
          ldr: Optional[int] = None, ldc: Optional[int] = None, in_place: bool = False, offset: int = 0, frames=None,
-         out: Optional[dict] = None, stats_eps: float = 0.0) -> np.ndarray:
+         out: Optional[dict] = None, stats_eps: float = 0.0, walk: Optional[dict] = None) -> np.ndarray:
     """C = epilogue(A . W^T + bias) through vithip_gemm_f32 (tile / group_m: per-call tuning fields, 0 = auto;
     workspace: lend the scratch that enables the helper pieces of the persistent walk; handover_test: see
     vithip_gemm_args; stats: receives the hand-over counters {"taken", "recomputed"} of the launch;
@@ -576,7 +576,8 @@ def gemm(A, W, bias, residual=None, epilogue=EPI_BIAS, tile: int = 0, group_m: i
     offset: C, bias and the residual start this many floats past a 16-byte boundary;
     frames: who allocates the operands (default: exact buffers; tests/strided.py: guarded, sentinel-filled frames);
     out: a dict that receives the output frames "C", "stats" and "partials";
-    stats_eps: the LayerNorm epsilon of row_stats (vithip_gemm_args.stats_eps; 0 = the default, the double 1e-6)."""
+    stats_eps: the LayerNorm epsilon of row_stats (vithip_gemm_args.stats_eps; 0 = the default, the double 1e-6);
+    walk: a dict that receives "tile" = (bm, bn), what vithip_gemm_f32_walk_tile says the persistent walk takes for this call."""
     A, W, bias = _as_f32(A), _as_f32(W), _as_f32(bias)
     M, K = A.shape
     N = W.shape[0]
@@ -602,6 +603,8 @@ def gemm(A, W, bias, residual=None, epilogue=EPI_BIAS, tile: int = 0, group_m: i
     args.stats_eps = stats_eps
     if row_stats is not None:
         row_stats["in_epilogue"] = int(lib().vithip_gemm_f32_stats_in_epilogue(C.byref(args)))
+    if walk is not None:
+        walk["tile"] = gemm_walk_tile(args)
     try:
         hip_check(lib().vithip_gemm_f32(None, C.byref(args)), "vithip_gemm_f32")
     except VitError:
@@ -616,6 +619,13 @@ def gemm(A, W, bias, residual=None, epilogue=EPI_BIAS, tile: int = 0, group_m: i
             stats.update(gemm_workspace_stats(ws))
         lib().vithip_gemm_f32_workspace_destroy(C.c_void_p(ws))
     return result
+
+
+def gemm_walk_tile(args: "CGemmArgs") -> tuple:
+    """vithip_gemm_f32_walk_tile: (rows, columns) of the tile the persistent walk takes for these arguments (host only)."""
+    bm, bn = C.c_int(), C.c_int()
+    hip_check(lib().vithip_gemm_f32_walk_tile(C.byref(args), C.byref(bm), C.byref(bn)), "vithip_gemm_f32_walk_tile")
+    return bm.value, bn.value
 
 
 def split3_weights_device(dW: "DeviceArray", N: int, K: int, ldw: Optional[int] = None) -> "DeviceArray":

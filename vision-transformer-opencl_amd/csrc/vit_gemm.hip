@@ -37,10 +37,11 @@
 #endif
 
 namespace vitgemm {
-int launch_persistent(hipStream_t stream, GemmParams &p, int epilogue, int group_m, int arith = ARITH_F32);  // vit_gemm_persistent.hip
+// vit_gemm_persistent.hip (group_m 0: the default of the geometry the walk takes; geometry: the probe build's override, 0 = none)
+int launch_persistent(hipStream_t stream, GemmParams &p, int epilogue, int group_m, int arith = ARITH_F32, int geometry = 0);
 int launch_persistent_stamped(hipStream_t stream, GemmParams &p, int epilogue, int group_m, int arith = ARITH_F32);
 int launch_persistent_switchoff(hipStream_t stream, GemmParams &p, int epilogue, int group_m, int dbg);  // probe build
-int persistent_piece_steps(int M, int N, int K, int slots, int wgs, int kstep);
+int persistent_piece_steps(int M, int N, int K, int slots, int wgs, int kstep, int bm = 128, int bn = 128);
 }
 
 namespace {
@@ -425,9 +426,14 @@ int dispatch(hipStream_t stream, GemmParams &p, int epilogue, int tile, int grou
     // the Infinity Cache, not by HBM -- the choice is bytes, not milliseconds.
     const int cols128 = (p.N + 127) / 128;
     p.group_m = group_m > 0 ? group_m : (cols128 <= 8 ? 1 : 4);
+    // The persistent walk picks its geometry (vitgemm::walk_tile) and, for group 0, that geometry's default grouping itself
+    int walk_group = group_m > 0 ? group_m : 0;
+    [[maybe_unused]] int walk_geometry = 0;
 #ifdef VIT_PROBES
-    if (g_gemm_tile) tile = g_gemm_tile;
-    if (g_gemm_group) p.group_m = g_gemm_group;
+    // 137 / 138 are no tile codes: they leave the call's tile alone and force the image walk's geometry, 128 x 128 / 64 x 256
+    if (g_gemm_tile == 137 || g_gemm_tile == 138) walk_geometry = g_gemm_tile - 136;
+    else if (g_gemm_tile) tile = g_gemm_tile;
+    if (g_gemm_group) p.group_m = walk_group = g_gemm_group;
     if constexpr (AMODE == A_DENSE && SPLIT) {  // the stamped image walk (tools/gemm_f32_split_stamps.py)
         if (tile == 129) {
             p.dbg = g_gemm_dbg;
@@ -470,7 +476,7 @@ int dispatch(hipStream_t stream, GemmParams &p, int epilogue, int tile, int grou
         return launch_tile<128, 64, 64, 32, A_PATCHES, 32, true>(stream, p, epilogue);
     }
     switch (tile) {
-        case 9: return vitgemm::launch_persistent(stream, p, epilogue, p.group_m, ARITH);   // persistent, cross-tile pipelined
+        case 9: return vitgemm::launch_persistent(stream, p, epilogue, walk_group, ARITH, walk_geometry);   // persistent, cross-tile pipelined
         case 6: case 7: case 8: case 12:
             if constexpr (SPLIT) return static_cast<int>(hipErrorInvalidValue);
             else if (tile == 6) return launch_tile<128, 128, 64, 64, AMODE, 16, true>(stream, p, epilogue);
@@ -513,12 +519,13 @@ int dispatch(hipStream_t stream, GemmParams &p, int epilogue, int tile, int grou
                 // workgroups (fc2 / out_proj at batch 256: 480 -> 448 steps per workgroup); without one the residual
                 // epilogue is marginally faster one tile per workgroup (fc2 21.30 vs 21.43 ms per step)
                 // (also when the caller wants the row statistics of the stored rows: the persistent epilogue takes them on the way)
-                if ((p.row_partials && p.N % 128 == 0) || (p.sk_ws && vitgemm::persistent_piece_steps(p.M, p.N, p.K, p.sk_slots, 0, BK) > 0))
-                    return vitgemm::launch_persistent(stream, p, epilogue, p.group_m, ARITH);
+                const vitgemm::WalkTile wt = vitgemm::walk_tile(p.N, epilogue, SPLIT && p.w_split != nullptr, walk_geometry);
+                if ((p.row_partials && p.N % 128 == 0) || (p.sk_ws && vitgemm::persistent_piece_steps(p.M, p.N, p.K, p.sk_slots, 0, BK, wt.bm, wt.bn) > 0))
+                    return vitgemm::launch_persistent(stream, p, epilogue, walk_group, ARITH, walk_geometry);
                 return launch_tile<128, 128, 64, 64, AMODE, BK, true, ARITH>(stream, p, epilogue);
             }
             if (tiles < 1280) return launch_tile<64, 64, 32, 32, AMODE, BK, true, ARITH>(stream, p, epilogue);
-            return vitgemm::launch_persistent(stream, p, epilogue, p.group_m, ARITH);
+            return vitgemm::launch_persistent(stream, p, epilogue, walk_group, ARITH, walk_geometry);
         }
     }
 }
@@ -542,7 +549,7 @@ extern "C" {
 #ifdef VIT_PROBES
 // Probe build only: process-wide overrides of the per-call tile / group fields (0 = none).
 int vithip_gemm_set_tile(int tile) {
-    if ((tile < 0 || tile > 12) && (tile < 101 || tile > 136)) return static_cast<int>(hipErrorInvalidValue);
+    if ((tile < 0 || tile > 12) && (tile < 101 || tile > 138)) return static_cast<int>(hipErrorInvalidValue);
     g_gemm_tile = tile;
     return 0;
 }
@@ -628,6 +635,20 @@ int vithip_gemm_f32_stats_in_epilogue(const vithip_gemm_args *a) {
         return 0;
     const long tiles = (long)((a->M + 127) / 128) * (a->N / 128);
     return (a->tile == 9 || (a->tile == 0 && tiles >= 1024)) ? 1 : 0;
+}
+
+// The tile of the persistent walk for these arguments (host only, launches nothing): vitgemm::walk_tile() with the epilogue code the
+// call would run -- the fold forms with ln_rows, the residual epilogue that takes the row statistics where it would.
+int vithip_gemm_f32_walk_tile(const vithip_gemm_args *a, int *bm, int *bn) {
+    if (!a || !bm || !bn || a->M <= 0 || a->N <= 0 || a->K <= 0) return static_cast<int>(hipErrorInvalidValue);
+    int epilogue = a->epilogue;
+    if (a->ln_rows)
+        epilogue = epilogue == VITHIP_EPI_BIAS ? vitgemm::EPI_BIAS_LN : epilogue == VITHIP_EPI_BIAS_GELU ? vitgemm::EPI_BIAS_GELU_LN : vitgemm::EPI_BIAS_QGELU_LN;
+    else if (vithip_gemm_f32_stats_in_epilogue(a)) epilogue = vitgemm::EPI_RESIDUAL_STATS;
+    const vitgemm::WalkTile t = vitgemm::walk_tile(a->N, epilogue, a->arith == ARITH_SPLIT3 && a->w_split != nullptr);
+    *bm = t.bm;
+    *bn = t.bn;
+    return 0;
 }
 
 int vithip_gemm_f32(vithip_stream_t stream, const vithip_gemm_args *a) {

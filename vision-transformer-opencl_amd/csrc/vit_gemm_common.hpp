@@ -101,7 +101,8 @@ struct GemmParams {
     // stats_in_epilogue: set by the dispatcher when the kernel it chose writes them (the caller then only finalises)
     float *row_partials;
     int stats_in_epilogue;
-    // the pre-split weight image (vithip_gemm_args.w_split; NULL: split W on the fly): read by the 128x128 persistent split walk only
+    // the pre-split weight image (vithip_gemm_args.w_split; NULL: split W on the fly): read by the persistent split walk only
+    // (128 x 128 tiles, or 64 x 256: walk_tile())
     const void *w_split;
 };
 
@@ -404,9 +405,22 @@ constexpr Split3WLoad SPLIT_W_LOADS[6] = {{0, 0, 1}, {0, 1, 2}, {2, 0, 5}, {2, 1
 // carries more than 4 of them plus one LDS write or one global load.
 //   q 0-3 hi quarters, 4 hi write | 5-8 mid quarters, 9 mid write | 10, 11 lo halves, 12 lo write | 13, 14 the loads of A
 struct Split3SlotsFine {
-    static constexpr int N = 15;
+    static constexpr int N = 15, PASSES = 1;
     static constexpr int at(int q) {
         constexpr int gap[N] = {0, 1, 2, 3, 4, 4, 5, 6, 7, 8, 8, 9, 10, 12, 13};
+        return gap[q];
+    }
+};
+// The same 15 slots of the 64 x 256 walk's 32-deep step: two passes of the 24-instruction body, one per 16-deep sub-step, and ONE
+// barrier, behind instruction SPLIT_PF_BARRIER of the second pass.  at(q) counts the matrix instructions of both passes (pass
+// at(q) / 24, instruction at(q) % 24).  A thread's staging work per 32 of k is what the 128 x 128 walk does per 16, so one slot per
+// gap is enough: no gap carries more than one quarter (4 vector instructions) or one LDS write or one load, and none of them shares
+// its gap with a load of W (1, 2, 5, 6, 16, 18 of either pass) or a fragment read of A (15, 17, 19).  The two loads of A go out
+// right behind the last quarter that consumes the registers they land in: 13 matrix instructions ahead of the step's end.
+struct Split3SlotsFine2 {
+    static constexpr int N = 15, PASSES = 2;
+    static constexpr int at(int q) {
+        constexpr int gap[N] = {0, 3, 7, 9, 11, 13, 20, 22, 24 + 0, 24 + 3, 24 + 4, 24 + 7, 24 + 8, 24 + 9, 24 + 10};
         return gap[q];
     }
 };
@@ -417,9 +431,18 @@ constexpr int split3_last_use(int w, int piece, int per_term) {
         if ((w ? SPLIT_TERM_W[t] : SPLIT_TERM_A[t]) == piece) last = (t + 1) * per_term - 1;
     return last;
 }
+// Slots: the restage table of a step of Slots::PASSES passes.  The tables of A's fragment reads and W's loads are per pass (every
+// pass requests the W fragments of the pass behind it; a pass reads A's fragments of the next one in place).
+template <typename Slots = Split3SlotsFine>
 constexpr bool split3_pf_schedule_ok(int per_term, int blocks_w) {
-    for (int q = 0; q < Split3SlotsFine::N; ++q)  // every restage write of A in front of the barrier
-        if (Split3SlotsFine::at(q) < 0 || Split3SlotsFine::at(q) > SPLIT_PF_BARRIER) return false;
+    const int nm = 6 * per_term, barrier = (Slots::PASSES - 1) * nm + SPLIT_PF_BARRIER;  // the step's one barrier: in its last pass
+    for (int q = 0; q < Slots::N; ++q) {
+        // slots run in the order of q (a plane's quarters, its write; the loads of A behind the last quarter that reads what they
+        // overwrite); every restage write of A (and, in the one-pass table, the loads too) in front of the barrier
+        if (Slots::at(q) < 0 || Slots::at(q) >= Slots::PASSES * nm) return false;
+        if (q > 0 && Slots::at(q) < Slots::at(q - 1)) return false;
+        if ((q <= 12 || Slots::PASSES == 1) && Slots::at(q) > barrier) return false;
+    }
     bool seen[3] = {};
     for (int e = 0; e < 3; ++e) {
         const Split3PfRead rd = SPLIT_PF_READS[e];
@@ -431,7 +454,8 @@ constexpr bool split3_pf_schedule_ok(int per_term, int blocks_w) {
     }
     for (int pc = 0; pc < 3; ++pc)
         if (!seen[pc]) return false;
-    // W: every (piece, block) requested once; mid and lo are overwritten in place: behind their last use (hi goes to the spare set)
+    // W: every (piece, block) requested once per pass; mid and lo are overwritten in place: behind their last use (hi goes to the
+    // spare set)
     int asked = 0;
     for (int e = 0; e < 6; ++e) {
         const Split3WLoad ld = SPLIT_W_LOADS[e];
@@ -439,6 +463,7 @@ constexpr bool split3_pf_schedule_ok(int per_term, int blocks_w) {
         if (ld.behind < 0 || ld.behind >= 6 * per_term) return false;
         if (ld.piece != 0 && ld.behind < split3_last_use(1, ld.piece, per_term)) return false;
         if (e > 0 && ld.behind < SPLIT_W_LOADS[e - 1].behind) return false;
+        if (asked & (1 << (ld.piece * blocks_w + ld.j))) return false;
         asked |= 1 << (ld.piece * blocks_w + ld.j);
     }
     return asked == (1 << (3 * blocks_w)) - 1;
@@ -474,17 +499,21 @@ struct Split3NoHook {
     __device__ __forceinline__ void operator()() const {}
 };
 // One step from the fragments in f, W's hi moving over from the spare set first (requested a step ago, or by the segment's cold
-// load); restage(q), q < Split3SlotsFine::N, behind matrix instruction Split3SlotsFine::at(q); sync() is the step's barrier; PFW:
-// the W fragments of the next step by load_w(piece, j) into split3_w_dst; PFA: A's fragments of the next step from the other buffer
-// (An) into f; landed(): a hook in front of the first matrix instruction (the stamped probe instantiation; nothing otherwise).
-template <int TM, int TN, bool PFA, bool PFW, typename Restage, typename LoadW, typename Sync, typename Landed = Split3NoHook>
+// load); restage(q), q < Slots::N, behind matrix instruction Slots::at(q) (pass PASS of the table's passes); sync() is the step's
+// barrier (SYNC: this pass has it); PFW: the W fragments of the next pass by load_w(piece, j) into split3_w_dst; PFA: A's fragments
+// of the next pass from An into f (the other buffer behind the barrier; without a barrier in this pass, the next sub-step of the
+// SAME buffer, complete since the barrier of the step before); landed(): a hook in front of the first matrix instruction (the
+// stamped probe instantiation; nothing otherwise).
+template <int TM, int TN, bool PFA, bool PFW, typename Slots = Split3SlotsFine, int PASS = 0, bool SYNC = true, typename Restage,
+          typename LoadW, typename Sync, typename Landed = Split3NoHook>
 __device__ __forceinline__ void split3_step_pf(f32x16 (&acc)[TM][TN], Split3Frags<TM, TN> &f, const float *An, const int (&poff)[3],
                                                Restage &&restage, LoadW &&load_w, Sync &&sync, Landed &&landed = Landed{}) {
     constexpr int NM = 6 * TM * TN;
     static_assert(NM == 24, "the schedule table is laid out for 2 x 2 accumulators");
-    static_assert(split3_pf_schedule_ok(TM * TN, TN),
+    static_assert(PASS >= 0 && PASS < Slots::PASSES && (SYNC || PASS + 1 < Slots::PASSES), "the barrier sits in the step's last pass");
+    static_assert(split3_pf_schedule_ok<Slots>(TM * TN, TN),
                   "A: restage writes in front of the barrier, reads of the other buffer behind it and behind the last use of what they "
-                  "overwrite; W: every fragment requested once, mid and lo behind their last use");
+                  "overwrite; W: every fragment requested once per pass, mid and lo behind their last use");
 #pragma unroll
     for (int j = 0; j < TN; ++j) f.b[j][0] = f.b_hn[j];
     landed();
@@ -500,9 +529,9 @@ __device__ __forceinline__ void split3_step_pf(f32x16 (&acc)[TM][TN], Split3Frag
                 if (SPLIT_W_LOADS[e].behind == idx) split3_w_dst(f, SPLIT_W_LOADS[e].piece, SPLIT_W_LOADS[e].j) = load_w(SPLIT_W_LOADS[e].piece, SPLIT_W_LOADS[e].j);
         }
 #pragma unroll
-        for (int q = 0; q < Split3SlotsFine::N; ++q)
-            if (Split3SlotsFine::at(q) == idx) restage(q);
-        if (idx == SPLIT_PF_BARRIER) sync();
+        for (int q = 0; q < Slots::N; ++q)
+            if (Slots::at(q) == PASS * NM + idx) restage(q);
+        if (SYNC && idx == SPLIT_PF_BARRIER) sync();
         if constexpr (PFA) {
 #pragma unroll
             for (int e = 0; e < 3; ++e)
@@ -514,6 +543,22 @@ __device__ __forceinline__ void split3_step_pf(f32x16 (&acc)[TM][TN], Split3Frag
 #pragma unroll
         for (int i = 0; i < TM; ++i) f.a[i][0] = f.a_hn[i];
     }
+}
+
+// ---- which tile the persistent walk takes (host; the ONE place: the launcher, the dispatcher's hand-over question and
+// vithip_gemm_f32_walk_tile() all ask here) -------------------------------------------------------------------------------------
+// The image walk (split arithmetic with a weight image) runs 64 x 256 tiles -- four waves side by side share one split of A -- where
+// N is whole 256-column tiles and the epilogue's class keeps it by measurement; every other walk is 128 x 128.
+// `epilogue`: the kernel's code (the fold forms and EPI_RESIDUAL_STATS included).  force: 1 = 128 x 128, 2 = 64 x 256 wherever it can
+// run (the probe library's override), 0 = the standing choice.
+struct WalkTile { int bm, bn; };
+constexpr bool WALK_SHARED_A_FOLD = true, WALK_SHARED_A_RESIDUAL_STATS = true, WALK_SHARED_A_RESIDUAL = true, WALK_SHARED_A_PLAIN = true;
+inline WalkTile walk_tile(int N, int epilogue, bool image, int force = 0) {
+    const bool can = image && N > 0 && N % 256 == 0;
+    const bool keeps = epi_is_fold(epilogue) ? WALK_SHARED_A_FOLD
+                       : epilogue == EPI_RESIDUAL_STATS ? WALK_SHARED_A_RESIDUAL_STATS
+                       : epilogue == VITHIP_EPI_BIAS_RESIDUAL ? WALK_SHARED_A_RESIDUAL : WALK_SHARED_A_PLAIN;
+    return (can && force != 1 && (keeps || force == 2)) ? WalkTile{64, 256} : WalkTile{128, 128};
 }
 
 // ---- epilogue ---------------------------------------------------------------------------------

@@ -62,17 +62,30 @@ constexpr int SK_HEADER_BYTES = 4096, SK_MAX_OWNERS = 1000, SK_STAT_TAKEN = 1016
 // (Measured against the step that copied W's chunks through LDS -- 3 ds_write_b128 and 6 ds_read_b128 more per wave and step,
 // 64 KB: +2.3 % images/s at the metric configuration; per launch in the forward the residual walks -4.9 %, QKV -1.8 %,
 // fc1 -1.4 %: profiles/r30.)
+// The image walk in 64 x 256 tiles (BM = 64, BN = 256; launch_persistent picks it where N % 256 == 0, walk_tile()): the four waves
+// sit 1 x 4, each on the 64 x 64 wave tile and the 48 matrix instructions per 32 of k it has in the 128 x 128 walk, and share ONE
+// split of A: the workgroup stages 64 rows x 32 k per K step (KSUB = 2 sub-steps of 16; a thread's work per step is unchanged, so per
+// matrix instruction the split, the ds_write_b128, the loads of A and the barriers are halved) into two 16-deep sub-buffers of the
+// same swizzled rows, runs split3_step_pf's body once per sub-buffer and meets at one barrier per 32 of k.  A wave column reads
+// panel 2 tn + wn / 2 of the image, rows (wn % 2) * 64 + ...; every wave's W is now its own (no duplicate request for L1 to
+// absorb).  K steps, the load cursor's lead, the hand-over's pieces and the fold's counted wait are in 32-deep steps here; the
+// accumulators, the epilogues, the 64 KB parking slots and the bits are the 128 x 128 walk's.  (Measured per launch at batch 256
+// against the 128 x 128 image walk: QKV -8 %, fc1 -8.5 %, fc2 -5 %, out_proj -4 %: profiles/r32.)
 template <int BM, int BN, int WM, int WN, int EPI, bool STAMP = false, bool SK = false, int DBG = 0, int ARITH = ARITH_F32,
           bool WIMG = false>
 __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const GemmParams p) {
     constexpr bool SPLIT = ARITH == ARITH_SPLIT3;
     static_assert(!SPLIT || DBG == 0, "switch-off builds are fp32 only");
-    static_assert(!WIMG || (SPLIT && BM == WIMG_ROWS && BN == WIMG_ROWS), "the weight image feeds the 128x128 split walk");
+    // KSUB: 16-deep sub-steps per K step of the image walk.  128 x 128 (waves 2 x 2): one.  64 x 256 (waves 1 x 4): two -- the
+    // workgroup splits 64 rows x 32 k per step, the same 8 consecutive k per thread, for twice the matrix instructions.
+    constexpr int KSUB = (WIMG && BM * 2 == WIMG_ROWS) ? 2 : 1;
+    static_assert(!WIMG || (SPLIT && BM * KSUB == WIMG_ROWS && BM * BN == WIMG_ROWS * WIMG_ROWS && WN == 64),
+                  "the weight image feeds the split walks of 128 x 128 and 64 x 256: whole panels of the image, 64 KB of accumulators");
     // The pipelined step pays under the fold consumers' walks (QKV, fc1) and not under the residual ones (out_proj, fc2), which are
     // faster with the finer slots alone: measured per launch at batch 256, profiles/r21, and again with W fed from the image
     // (fc2 +1.5 % per launch and -0.6 % images/s with the residual walks pipelined too, profiles/r30).
     constexpr bool PIPE = WIMG && EPI != VITHIP_EPI_BIAS_RESIDUAL && EPI != EPI_RESIDUAL_STATS;
-    constexpr int PBK = SPLIT ? SPLIT_BK : vitgemm::PBK;  // K step
+    constexpr int PBK = SPLIT ? SPLIT_BK * KSUB : vitgemm::PBK;  // K step
     constexpr int PLD = WIMG ? SPLIT_LD_SW : SPLIT ? SPLIT_LD : vitgemm::PLD;  // LDS row (floats)
     constexpr int ROWS_PER_PASS = 256 / (PBK / 4);
     constexpr int WGN = BN / WN;
@@ -81,13 +94,15 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
     constexpr int B_CHUNKS = BN * (PBK / 4) / 256;
     constexpr int NC = PBK / 8;              // 8-deep chunks per K step (fp32)
     constexpr int NS = A_CHUNKS + B_CHUNKS;  // staged float4 per thread per K step
-    constexpr int W_FRAGS = 3 * TN;          // WIMG: image chunks per lane per K step (one per plane and 32-row block of the wave)
+    constexpr int W_FRAGS = 3 * TN * KSUB;   // WIMG: image chunks per lane per K step (one per plane, 32-row block of the wave and sub-step)
     constexpr int NL = WIMG ? A_CHUNKS + W_FRAGS : NS;  // global loads per thread per (prefetching) K step
-    static_assert(!WIMG || (A_CHUNKS == 2 && BM * 2 == 256), "WIMG: one 8-deep half row of A per thread");
+    static_assert(!WIMG || (A_CHUNKS == 2 && BM * 2 * KSUB == 256), "WIMG: one 8-deep half row of A (of one sub-step) per thread");
+    constexpr int A_SUB = BM * PLD;          // floats of one 16-deep (sub-)buffer of A
+    constexpr int A_BUF = KSUB * A_SUB;      // ... of one K step's buffer
     constexpr int NM = 4 * TM * TN;          // MFMAs per chunk
     static_assert((BM / WM) * WGN == 4, "4 waves per workgroup");
 
-    __shared__ __attribute__((aligned(16))) float lds[2 * (WIMG ? BM : BM + BN) * PLD];  // WIMG: A only
+    __shared__ __attribute__((aligned(16))) float lds[2 * (WIMG ? BM * KSUB : BM + BN) * PLD];  // WIMG: A only
     __shared__ int sk_decision;  // owner: 1 = the helper's piece is there (written by thread 0, read by all after a barrier)
     // LayerNorm fold, consumer epilogues: (rstd, mean) of the tile's BM rows = 1 KB, copied here when the tile BEGINS by one
     // global -> LDS instruction of wave 0 (16 bytes per lane), written as inline assembly so that it stays off the compiler's
@@ -100,8 +115,12 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
     // the finished tile's pairs; a buffer's next writer is two tiles (many barriers) later.  (An unknown younger operation in the
     // queue only makes the compiler's own counted waits wait for one load more than they need.)
     constexpr bool FOLD = epi_is_fold(EPI);
-    __shared__ __attribute__((aligned(16))) f32x2 fold_rows_lds[FOLD ? 2 * BM : 2];
-    static_assert(!FOLD || BM == 128, "one 16-byte lane copy of 64 lanes = 128 rows");
+    // (A 64-row tile has 512 bytes of pairs.  The copy stays one instruction of all 64 lanes and each buffer stays FOLD_ROWS pairs:
+    // the descriptor ends behind the tile's rows, so lanes 32 .. 63 fetch nothing and what they write -- zeros -- lands in the
+    // upper half of the tile's OWN buffer, which nobody reads.)
+    constexpr int FOLD_ROWS = 128;
+    __shared__ __attribute__((aligned(16))) f32x2 fold_rows_lds[FOLD ? 2 * FOLD_ROWS : 2];
+    static_assert(!FOLD || (BM <= FOLD_ROWS && FOLD_ROWS * 8 == 64 * 16), "one 16-byte lane copy of 64 lanes = 128 rows");
     float *const As0 = lds;
     float *const Bs0 = WIMG ? lds : lds + 2 * BM * PLD;  // (WIMG: unused)
 
@@ -166,11 +185,16 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
 
     const int ld_row = tid / (PBK / 4);
     const int ld_kc = (tid % (PBK / 4)) * 4;
-    // WIMG: thread t stages row t / 2, k 8 (t % 2) .. 8 (t % 2) + 7 of A; wr_off[plane] = its chunk's place in a tile
-    const int sw_row = tid >> 1, sw_half = tid & 1;
+    // WIMG: thread t stages row t / 2, k 8 (t % 2) .. 8 (t % 2) + 7 of A; wr_off[plane] = its chunk's place in a tile.
+    // 64 x 256: row (t / 2) % 64 of sub-step t / 128, i.e. k 16 (t / 128) + 8 (t % 2) ...: the sub-step is wave-uniform (waves 0, 1
+    // and 2, 3) and goes into a_src and wr_off once.  Eight consecutive threads are still one aligned quad of rows x both halves of
+    // ONE sub-buffer, so the ds_write_b128 pattern is the conflict-free one of split_swizzle.  (The two sub-steps of a row on
+    // neighbouring lanes would put two lanes of a group on the same slot, A_SUB = 8 KB apart: the same banks.)
+    const int sw_row = KSUB == 1 ? tid >> 1 : (tid >> 1) & (BM - 1), sw_half = tid & 1;
+    const int sw_sub = KSUB == 1 ? 0 : __builtin_amdgcn_readfirstlane(tid / (2 * BM));
     int wr_off[3];
 #pragma unroll
-    for (int pl = 0; pl < 3; ++pl) wr_off[pl] = WIMG ? split_sw_offset(sw_row, 2 * pl + sw_half) : 0;
+    for (int pl = 0; pl < 3; ++pl) wr_off[pl] = WIMG ? sw_sub * A_SUB + split_sw_offset(sw_row, 2 * pl + sw_half) : 0;
     // Staging loads are buffer loads: SGPR descriptor + per-thread 32-bit byte offset + SGPR K offset, so
     // stepping through K costs no vector instruction (a 64-bit v_lshl_add per load otherwise -- and fp32
     // VALU time comes out of the matrix pipe's).  Offsets fit 32 bits: the largest operand (fc2's A at
@@ -181,9 +205,12 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
     int a_src[A_CHUNKS];  // byte offsets
     int b_src[B_CHUNKS];
     f32x4 a_stage[A_CHUNKS], b_stage[B_CHUNKS];
-    // WIMG: the lane's chunk (row wn * WN + r, half h) of plane 0 and block j = 0 inside an image block, and the panel of the
-    // COMPUTE cursor's tile (scalar; set by begin_segment): W's fragments follow the matrix instructions, not the staging of A
-    const int w_lane = WIMG ? ((wn * WN + r) * 2 + h) * 16 : 0;
+    // WIMG: the lane's chunk (row (wn % 2) * WN + r of the wave's panel, half h) of plane 0 and block j = 0 inside an image block,
+    // and the wave's panel of the COMPUTE cursor's tile (scalar; set by begin_segment): W's fragments follow the matrix instructions,
+    // not the staging of A.  A tile is BN / 128 panels wide and two waves share a panel: wave column wn reads panel wn / 2 of them.
+    constexpr int W_WAVES = WIMG_ROWS / WN;  // wave columns per panel
+    const int w_lane = WIMG ? (((wn % W_WAVES) * WN + r) * 2 + h) * 16 : 0;
+    const int w_wave_panel = (WIMG && BN > WIMG_ROWS) ? __builtin_amdgcn_readfirstlane(wn / W_WAVES) : 0;
     [[maybe_unused]] int w_panel = 0;
 
     auto set_sources = [&](int tile) {
@@ -193,7 +220,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
             int m = tm * BM + sw_row;
             m = m < p.M ? m : p.M - 1;
 #pragma unroll
-            for (int i = 0; i < A_CHUNKS; ++i) a_src[i] = (m * p.lda + 8 * sw_half + 4 * i) * 4;
+            for (int i = 0; i < A_CHUNKS; ++i) a_src[i] = (m * p.lda + SPLIT_BK * sw_sub + 8 * sw_half + 4 * i) * 4;
             return;
         }
 #pragma unroll
@@ -289,7 +316,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
         *reinterpret_cast<u32x4 *>(As + wr_off[pl]) = split3_piece8(a_stage[0], a_stage[1], pl);
     };
     auto store_step = [&](int buf) {
-        float *As = As0 + buf * BM * PLD, *Bs = Bs0 + buf * BN * PLD;
+        float *As = As0 + buf * A_BUF, *Bs = Bs0 + buf * BN * PLD;
         if constexpr (WIMG) {
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) write_a_plane(As, pl);
@@ -303,7 +330,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
     // one staging slot (fp32 and the on-the-fly split): write the float4 fetched a step ago, then refetch it for two steps ahead
     auto restage_slot = [&](int q, int buf, int k0) {
         if (q < A_CHUNKS) {
-            float *As = As0 + buf * BM * PLD;
+            float *As = As0 + buf * A_BUF;
             if (DBG != 5 && DBG != 6) stage_write(As + (ld_row + q * ROWS_PER_PASS) * PLD, a_stage[q]);
             if (DBG != 2 && DBG != 6) a_stage[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, a_src[q], k0 * 4, 0));
         } else {
@@ -335,17 +362,17 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
             else if (pl == 2 && sub < 2) {
                 quarter(2 * sub);
                 quarter(2 * sub + 1);
-            } else *reinterpret_cast<u32x4 *>(As0 + buf * BM * PLD + wr_off[pl]) = a_plane;
+            } else *reinterpret_cast<u32x4 *>(As0 + buf * A_BUF + wr_off[pl]) = a_plane;
         } else {
             a_stage[q - 13] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, a_src[q - 13], k0 * 4, 0));
         }
     };
-    // WIMG: the lane's W fragment (piece `pl`, 32-row block j of the wave's columns) of K step k of the compute cursor's tile,
-    // from the image.  The plane goes into the scalar offset and the block is a constant added to the lane's offset (hipcc keeps
-    // the sum in a second register): no vector arithmetic in the loop.
-    auto load_w_frag = [&](int pl, int j, int k) __attribute__((always_inline)) {
+    // WIMG: the lane's W fragment (piece `pl`, 32-row block j of the wave's columns) of sub-step `sub` of K step k of the compute
+    // cursor's tile, from the image.  The plane goes into the scalar offset and the block is a constant added to the lane's offset
+    // (hipcc keeps the sum in a second register): no vector arithmetic in the loop.
+    auto load_w_frag = [&](int pl, int j, int k, int sub = 0) __attribute__((always_inline)) {
         return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, w_lane + j * (32 * 2 * 16),
-                                                                                 w_panel + k * WIMG_BLOCK_BYTES + pl * (WIMG_ROWS * 2 * 16), 0));
+                                                                                 w_panel + (k * KSUB + sub) * WIMG_BLOCK_BYTES + pl * (WIMG_ROWS * 2 * 16), 0));
     };
     // The pipelined step's restage hook: restage_fine and nothing else.  (It stays a closure of its own: without it hipcc orders two
     // moves in the preamble of the probe build's stamped residual walks differently, profiles/r28.)
@@ -361,7 +388,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
     f32x4 af[2][TM], bf[2][TN];  // fp32 only (the split reads its pieces inside split3_step)
     auto read_frags = [&](int buf, int c, int set) {
         if constexpr (SPLIT) return;
-        const float *As = As0 + buf * BM * PLD + a_frag_off + c * 8;
+        const float *As = As0 + buf * A_BUF + a_frag_off + c * 8;
         const float *Bs = Bs0 + buf * BN * PLD + b_frag_off + c * 8;
 #pragma unroll
         for (int i = 0; i < TM; ++i) af[set][i] = *reinterpret_cast<const f32x4 *>(As + i * 32 * PLD);
@@ -443,7 +470,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
         tile_coords(g.tile, p.tiles_m, p.tiles_n, p.group_m, tm, tn);
         m0 = tm * BM;
         n0 = tn * BN;
-        if constexpr (WIMG) w_panel = tn * nk * WIMG_BLOCK_BYTES;  // the tile's panel of the image: its blocks follow each other in K
+        // the wave's panel of the image: its blocks follow each other in K
+        if constexpr (WIMG) w_panel = (tn * (BN / WIMG_ROWS) + w_wave_panel) * (nk * KSUB) * WIMG_BLOCK_BYTES;
         k_c = g.k0;
         seg_k0 = g.k0;
         kend_c = g.k1;
@@ -459,10 +487,10 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
                 if (wave == 0) {  // the rows' pairs -> LDS (see fold_rows_lds); rows past M read as zero, never stored
                     const int left = p.M - m0 < BM ? p.M - m0 : BM;
                     const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.ln_rows) + (size_t)m0 * 2, 0, left * 8, 0x00020000);
-                    const unsigned dst = (unsigned)(size_t)(fold_rows_lds + fold_buf * BM);
+                    const unsigned dst = (unsigned)(size_t)(fold_rows_lds + fold_buf * FOLD_ROWS);
                     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(dst), "v"(lane * 16), "s"(rr) : "memory", "m0");
                 }
-                fold.rows = fold_rows_lds + fold_buf * BM;
+                fold.rows = fold_rows_lds + fold_buf * FOLD_ROWS;
                 fold_buf ^= 1;
             }
         }
@@ -512,7 +540,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
                 // vmcnt retires in order: once at most FOLD_WAIT = 2 * NS operations are outstanding, everything older than the
                 // restage loads of the last two K-steps is done.  The copy was issued before this tile's first restage load, and a
                 // tile of FOLD_MIN_STEPS steps has issued (FOLD_MIN_STEPS - 1) * NS >= FOLD_WAIT + NS of them by now.
-                // (NL: the global loads a K-step issues -- 4 float4 on the fly, 2 of A + 3 image chunks with WIMG)
+                // (NL: the global loads a K-step issues -- 4 float4 on the fly; 2 of A + 6 image chunks with WIMG, 2 + 12 per 32-deep
+                // step of the 64 x 256 walk: 28 left in flight, and the copy at least 6 + 3 x 14 loads old)
                 constexpr int FOLD_WAIT = 2 * NL, FOLD_MIN_STEPS = 4;
                 static_assert(FOLD_WAIT <= 63, "vmcnt is a 6-bit count on gfx950");
                 static_assert((FOLD_MIN_STEPS - 1) * NL >= FOLD_WAIT + NL, "the copy must be older than the loads the wait leaves in flight");
@@ -533,11 +562,28 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
         // PIPE: A's fragments of the next step are read under this step's matrix instructions, behind the barrier inside the step.
         // The residual walks: A's fragments at the step's top, the barrier at the step's end, the finer slots and W's feed alone.
         Split3Frags<TM, TN> frags;
-        auto tile_a = [&](int buf) { return As0 + buf * BM * PLD + a_frag_off; };
+        auto tile_a = [&](int buf, int sub = 0) { return As0 + buf * A_BUF + sub * A_SUB + a_frag_off; };
         auto step = [&](auto prefetch) __attribute__((always_inline)) {
             constexpr bool PF = decltype(prefetch)::value;
             const int k_ahead = k_l * PBK;  // offset of the step the restage loads of A fetch (two steps ahead)
             if constexpr (!PIPE) split3_read_cold<TM, TN>(frags, tile_a(cur), frag_poff);
+            if constexpr (KSUB == 2) {
+                // The 32-deep step: two passes, the restage slots of Split3SlotsFine2 over both, one barrier.  Pass 0 (sub-step 0)
+                // always prefetches: W of sub-step 1 from the image, and (PIPE) A's fragments of sub-step 1 from the SAME buffer,
+                // complete since the barrier of the step before -- no barrier in this pass.  Pass 1 is the 16-deep step of the
+                // 128 x 128 walk: the barrier behind instruction SPLIT_PF_BARRIER, every restage write into the other buffer in
+                // front of it, the reads of that buffer's sub-step 0 behind it.  Every read of a buffer is issued in front of the
+                // barrier of the step that reads it and has landed there (instructions 8 .. 11 of pass 1 use the last of them),
+                // and the first write into it comes behind that barrier.  Residual form: cold reads at each pass's top, the
+                // barrier at the step's end.
+                auto restage = [&](int q) __attribute__((always_inline)) { restage_any(q, cur ^ 1, k_ahead); };
+                split3_step_pf<TM, TN, PIPE, true, Split3SlotsFine2, 0, false>(acc, frags, tile_a(cur, 1), frag_poff, restage,
+                    [&](int pl, int j) __attribute__((always_inline)) { return load_w_frag(pl, j, k_c, 1); }, [] {}, stamp_landed);
+                if constexpr (!PIPE) split3_read_cold<TM, TN>(frags, tile_a(cur, 1), frag_poff);
+                split3_step_pf<TM, TN, PF && PIPE, PF, Split3SlotsFine2, 1, true>(acc, frags, tile_a(cur ^ 1), frag_poff, restage,
+                    [&](int pl, int j) __attribute__((always_inline)) { return load_w_frag(pl, j, k_c + 1); },
+                    [] { if constexpr (PIPE) __syncthreads(); });
+            } else
             split3_step_pf<TM, TN, PF && PIPE, PF>(acc, frags, tile_a(cur ^ 1), frag_poff,
                 [&](int q) __attribute__((always_inline)) { restage_any(q, cur ^ 1, k_ahead); },
                 [&](int pl, int j) __attribute__((always_inline)) { return load_w_frag(pl, j, k_c + 1); },
@@ -575,7 +621,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
         if constexpr (SPLIT) {
             // one 16-deep step of the split: pieces from buffer `cur`, the staged step g + 1 split into cur^1 and the loads of step
             // g + 2 in the first half of the matrix instructions, then the one barrier (the fp32 loop's swap point)
-            split3_step<TM, TN, NS>(acc, As0 + cur * BM * PLD + a_frag_off, Bs0 + cur * BN * PLD + b_frag_off,
+            split3_step<TM, TN, NS>(acc, As0 + cur * A_BUF + a_frag_off, Bs0 + cur * BN * PLD + b_frag_off,
                                     [&](int q) __attribute__((always_inline)) { restage_slot(q, cur ^ 1, k_ahead); });
             advance_load_cursor();
             __syncthreads();
@@ -623,15 +669,16 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_nt_persistent_kernel(const Ge
 // 2 workgroups per CU of the CURRENT device (engines of several devices share the process: nothing is cached process-wide)
 static int persistent_wgs() { return 2 * vitdev::current_cus(); }
 
-// K-steps of a last-round tile that a helper workgroup runs (0: the hand-over does not pay) for the 128 x 128 persistent walk
-// on a grid of `wgs` workgroups (0: ask the current device) with `slots` parking slots
+// K-steps of a last-round tile that a helper workgroup runs (0: the hand-over does not pay) for the persistent walk of bm x bn
+// tiles (128 x 128, or the image walk's 64 x 256: 64 KB of accumulators either way) on a grid of `wgs` workgroups (0: ask the
+// current device) with `slots` parking slots
 // (returned in K-steps of `kstep` deep: PBK for fp32, SPLIT_BK for the split.  The choice and the piece's depth in k are made in
 // 32-deep steps for both, so that the split hands over exactly where the fp32 arithmetic does -- QKV at batch 256 included, which
 // stays without pieces)
-int persistent_piece_steps(int M, int N, int K, int slots, int wgs, int kstep) {
+int persistent_piece_steps(int M, int N, int K, int slots, int wgs, int kstep, int bm, int bn) {
     if (wgs <= 0) wgs = persistent_wgs();
     if (wgs <= 0) return 0;
-    const int total = ((M + 127) / 128) * ((N + 127) / 128);
+    const int total = ((M + bm - 1) / bm) * ((N + bn - 1) / bn);
     const int nwg = total < wgs ? total : wgs;
     const int full = total / nwg, R = total - full * nwg, nk = K / PBK;
     if (full < 1 || R <= 0 || R >= nwg || R > slots || R > SK_MAX_OWNERS) return 0;
@@ -651,7 +698,8 @@ int launch_persistent_tile(hipStream_t stream, GemmParams &p, int epilogue, int 
     p.group_m = group_m;
     // helper pieces (see the head of this file): on when the caller lent a workspace, a partial last round exists and the
     // piece is long enough to be worth a 64 KB hand-over (>= 4 K-steps)
-    p.sk_x = (p.sk_ws && BM == 128 && BN == 128) ? persistent_piece_steps(p.M, p.N, p.K, p.sk_slots, wgs, ARITH == ARITH_SPLIT3 ? SPLIT_BK : PBK) : 0;
+    constexpr int KSTEP = ARITH != ARITH_SPLIT3 ? PBK : (WIMG && BM * 2 == WIMG_ROWS) ? 2 * SPLIT_BK : SPLIT_BK;  // the kernel's K step
+    p.sk_x = (p.sk_ws && BM * BN == 128 * 128) ? persistent_piece_steps(p.M, p.N, p.K, p.sk_slots, wgs, KSTEP, BM, BN) : 0;
     return with_epilogue(WalkEpilogues{}, epilogue, [&](auto epi) {
         auto launch = [&](auto sk) {
             hipLaunchKernelGGL((gemm_f32_nt_persistent_kernel<BM, BN, WM, WN, decltype(epi)::value, false, decltype(sk)::value, 0, ARITH, WIMG>), grid, block, 0, stream, p);
@@ -703,14 +751,21 @@ int launch_persistent_switchoff(hipStream_t stream, GemmParams &p, int epilogue,
 #endif
 
 // Entry used by vit_gemm.hip's dispatcher.  Needs at least 4 K steps per tile (K >= 128).
-int launch_persistent(hipStream_t stream, GemmParams &p, int epilogue, int group_m, int arith) {
+// group_m 0: the default grouping of the geometry the walk takes.  128 x 128: see dispatch() in vit_gemm.hip.  64 x 256: the groups
+// that cover the same rows and columns of C -- plain N-fastest order up to 4 tile columns (N = 768: the 64 tiles an XCD holds at a
+// time are ~21 whole tile rows, the ~11 rows of 128 of before), groups of 8 tile rows of 64 beyond (the 512 rows of 4 x 128).
+// geometry (probe build: the override codes 137 / 138): 0 = walk_tile()'s choice, 1 = 128 x 128, 2 = 64 x 256 where it can run.
+int launch_persistent(hipStream_t stream, GemmParams &p, int epilogue, int group_m, int arith, int geometry) {
     // residual GEMM whose caller also wants the row statistics of what it stores: in the epilogue when the columns are whole tiles
     if (epilogue == VITHIP_EPI_BIAS_RESIDUAL && p.row_partials && p.N % 128 == 0) {
         epilogue = EPI_RESIDUAL_STATS;
         p.stats_in_epilogue = 1;
     }
+    const WalkTile t = walk_tile(p.N, epilogue, arith == ARITH_SPLIT3 && p.w_split != nullptr, geometry);
+    if (group_m <= 0) group_m = t.bm == 64 ? (p.N / t.bn <= 4 ? 1 : 8) : ((p.N + 127) / 128 <= 8 ? 1 : 4);
     if (arith == ARITH_SPLIT3) {
         // W's pieces from the caller's pre-split image, or split on the fly: the same bits
+        if (p.w_split && t.bm == 64) return launch_persistent_tile<64, 256, 64, 64, ARITH_SPLIT3, true>(stream, p, epilogue, group_m);
         if (p.w_split) return launch_persistent_tile<128, 128, 64, 64, ARITH_SPLIT3, true>(stream, p, epilogue, group_m);
         return launch_persistent_tile<128, 128, 64, 64, ARITH_SPLIT3>(stream, p, epilogue, group_m);
     }
