@@ -230,7 +230,8 @@ typedef struct {
 } vithip_gemm_bf16_args;
 /* C = epilogue(A . W^T + bias) on the bf16 matrix pipe (v_mfma_f32_16x16x32_bf16 in the ping-pong kernel,
  * v_mfma_f32_32x32x16_bf16 in the two-stage one), fp32 accumulate.  BF16_GELU rounds gelu(acc + bias) to bf16 (a
- * polynomial erfc whose error stays below 5 % of half a bf16 ulp); F32_RESIDUAL adds an fp32 residual in fp32.
+ * polynomial erfc whose error stays below 5 % of half a bf16 ulp for acc + bias >= -4 sqrt 2; below it an absolute 4.4e-8: the
+ * result is the constant -4.36e-8 there, where gelu tends to 0); F32_RESIDUAL adds an fp32 residual in fp32.
  * Non-finite values in one row of A reach only that row of C, x16 and row_partials -- and do reach it: a NaN accumulator comes out
  * of BF16_GELU as NaN, an infinite one as NaN or Inf -- every other output has the bits of the same launch on clean data. */
 int vithip_gemm_bf16(vithip_stream_t stream, const vithip_gemm_bf16_args *args);

@@ -2,7 +2,8 @@
 
 Inputs are rounded to bf16 on the host first, so the oracle (fp32 arithmetic on the SAME values) differs
 from the kernel only by fp32 accumulation order; bf16 outputs are additionally rounded once
-(relative 2^-8).  Tolerances are written where they are used.
+(relative 2^-8).  Tolerances are written where they are used.  The accuracy bars of the bf16 GEMMs -- bit-exact on integer operands,
+float64 at fp32-level bars, the GELU sweeps -- are in tests/test_gpu_bf16_gemm_accuracy.py.
 """
 import numpy as np
 import pytest

@@ -4,6 +4,8 @@
 
 Producer = the residual GEMM in front (stores bf16(x) and per-row partial sums), consumer = the GEMM behind (raw bf16 rows,
 folded weight, epilogue rescale).  References are float64 numpy on the same bf16-exact operands; tolerances are written where used.
+The accuracy bars of both sides of the fold -- bit-exact on integer operands, float64 at fp32-level bars -- are in
+tests/test_gpu_bf16_gemm_accuracy.py.
 """
 import numpy as np
 import pytest

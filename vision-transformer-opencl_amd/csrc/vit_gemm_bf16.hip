@@ -5,7 +5,7 @@
 //
 //   C = epilogue(A[M][K] . W[N][K]^T + bias),  A and W bf16 (K contiguous), bias fp32, accumulate fp32.
 //   epilogues:  BF16       C bf16 = acc + bias                      (QKV in_proj)
-//               BF16_GELU  C bf16 = gelu_erf(acc + bias)            (fc1; ViT_seq.c:231-233)
+//               BF16_GELU  C bf16 = gelu(acc + bias)                (fc1; ViT_seq.c:231-233; gelu_bf16_lockstep, as the ping-pong kernel)
 //               F32_RES    C fp32 = acc + bias + R fp32, R may be C (out_proj, fc2: the residual stream
 //                                                                    stays fp32, ViT_seq.c:286-288,297-299)
 //
@@ -32,7 +32,8 @@
 
 namespace {
 
-using vitgemm::erf_fp32;
+using vitgemm::f32x2;
+using vitgemm::gelu_bf16_lockstep;
 using vitgemm::quick_gelu;
 using vitgemm::tile_coords;
 using vitgemm::xcd_remap;
@@ -172,8 +173,10 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_bf16_nt_kernel(const Bf16Para
         // phase cost as much as the whole K loop.  The tile is therefore transposed through the (now idle)
         // LDS in row blocks and leaves as full 512-B / 1-KB row segments, 16 B per lane; the residual is read
         // the same coalesced way.  Row pitches 520 B / 1040 B keep the block writes conflict-free.
+        // (BF16_GELU does not go through finish(): the fp32 path's 0.5 t (1 + erf(t / sqrt 2)) is no substitute for gelu_bf16_lockstep
+        // here.  Its 1 + erf cancels in the negative tail -- more than 5 % of half a bf16 ulp off from -3.64 down, where the header
+        // promises less, and exactly 0 below -5.53, where gelu is -8.7e-8; tests/test_bf16_gemm_model.py measures both forms.)
         auto finish = [&](float t) {
-            if constexpr (EPI == VITHIP_BF16_EPI_BF16_GELU) t = 0.5f * t * (1.0f + erf_fp32(t * 0.70710678118654752440f));
             if constexpr (EPI == VITHIP_BF16_EPI_BF16_QGELU) t = quick_gelu(t);
             return t;
         };
@@ -222,8 +225,17 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_bf16_nt_kernel(const Bf16Para
 #pragma unroll
                             for (int g = 0; g < 4; ++g) {
                                 bf16x4 y;
+                                if constexpr (EPI == VITHIP_BF16_EPI_BF16_GELU) {
+                                    f32x2 v[2];  // the ping-pong kernel's GELU, operation for operation: the same bits from both
 #pragma unroll
-                                for (int q = 0; q < 4; ++q) y[q] = (__bf16)finish(acc[j][i][4 * g + q] + b4[j][g][q]);
+                                    for (int q = 0; q < 2; ++q)
+                                        v[q] = f32x2{acc[j][i][4 * g + 2 * q] + b4[j][g][2 * q], acc[j][i][4 * g + 2 * q + 1] + b4[j][g][2 * q + 1]};
+                                    gelu_bf16_lockstep<2>(v);
+                                    y = bf16x4{(__bf16)v[0].x, (__bf16)v[0].y, (__bf16)v[1].x, (__bf16)v[1].y};
+                                } else {
+#pragma unroll
+                                    for (int q = 0; q < 4; ++q) y[q] = (__bf16)finish(acc[j][i][4 * g + q] + b4[j][g][q]);
+                                }
                                 *reinterpret_cast<bf16x4 *>(lds + (i * 32 + r) * PITCH + (wn * 64 + j * 32 + 8 * g + 4 * h) * 2) = y;
                             }
                 }

@@ -177,7 +177,9 @@ __device__ __forceinline__ void gelu_erf_x8(float (&y)[8]) {
 //   gelu(y) = max(y, 0) - h(|y|),   h = 0.5 |y| erfc(|y|/sqrt2) = t * exp2(Q(t)),  t = min(|y|, 4 sqrt2),
 //   Q(t) = log2(erfc(t/sqrt2)) - 1 as a degree-6 polynomial in |y| itself (the fit on [0,4] of erfc's argument with the
 //   powers of 1/sqrt2 folded into the coefficients: no scaling multiply, and |y| is a source modifier of the v_min).
-// Max abs error 4.7e-6, at most 4.4 % of half a bf16 ulp of the result anywhere: invisible after the bf16
+// Max abs error 4.7e-6, at most 4.4 % of half a bf16 ulp of the result for y >= -4 sqrt 2; below it an absolute 4.4e-8 (t is clamped:
+// the result is the constant -t exp2(Q(t)) = -4.36e-8 where gelu tends to 0, so no relative figure holds there; tests/test_bf16_gemm_model.py
+// measures both on a step-by-step emulation): invisible after the bf16
 // rounding that follows, at 6.5 VALU instructions per value (6 + 1 v_pk_fma_f32, v_min, v_max, v_exp_f32 per pair and
 // value) instead of 19 for the fp32-accurate form above
 // (ViT_seq.c:231-233 is the fp32 definition; the bf16 path's parity bar is in tests/test_gpu_bf16.py).
