@@ -168,26 +168,28 @@ def scale_f32(head_dim):
     return np.float32((1.0 / np.sqrt(float(head_dim))) * 1.4426950408889634074)
 
 
-def attention_f64(q, k, v, head_dim=HD):
+def attention_f64(q, k, v, head_dim=HD, q_scaled=False):
+    """q_scaled: q holds the exponent's multiple of the query (scale_f32(head_dim) * q), the weights are 2^(q . k)."""
     q, k, v = (np.asarray(a, np.float64) for a in (q, k, v))
-    s = q @ k.T / np.sqrt(float(head_dim))
-    p = np.exp(s - s.max(1, keepdims=True))
+    s = q @ k.T if q_scaled else q @ k.T / np.sqrt(float(head_dim))
+    p = np.exp2(s - s.max(1, keepdims=True)) if q_scaled else np.exp(s - s.max(1, keepdims=True))
     return (p / p.sum(1, keepdims=True)) @ v
 
 
-def attention_f32_sequential(q, k, v, head_dim=HD):
+def attention_f32_sequential(q, k, v, head_dim=HD, q_scaled=False):
     """Plain fp32, one operation after the other: every score an FMA chain over d, the row maximum, p = exp2(fma(s, c, -m c)), the
-    row sum and every output an FMA chain over the keys, one multiplication by the reciprocal of the sum."""
+    row sum and every output an FMA chain over the keys, one multiplication by the reciprocal of the sum.  q_scaled: c = 1 (q holds
+    c * q)."""
     q, k, v = (np.asarray(a, np.float32) for a in (q, k, v))
     Tq, T = q.shape[0], k.shape[0]
-    c = scale_f32(head_dim)
+    c = np.float32(1.0) if q_scaled else scale_f32(head_dim)
     s = np.zeros((Tq, T), np.float32)
     for d in range(head_dim):
         s = f32(s.astype(np.float64) + np.outer(q[:, d].astype(np.float64), k[:, d].astype(np.float64)))
     mneg = f32(-s.max(1).astype(np.float64) * c)
     p = f32(np.exp2(f32(s.astype(np.float64) * c + mneg[:, None].astype(np.float64)).astype(np.float64)))
     total = np.zeros(Tq, np.float32)
-    o = np.zeros((Tq, head_dim), np.float32)
+    o = np.zeros((Tq, v.shape[1]), np.float32)
     for key in range(T):
         total = total + p[:, key]
         o = f32(o.astype(np.float64) + np.outer(p[:, key].astype(np.float64), v[key].astype(np.float64)))

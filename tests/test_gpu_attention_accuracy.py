@@ -19,7 +19,7 @@ head's columns are read at an offset); 33 keys (one past a 32-key tile), 197 (th
 vithip_attention_f32, a second 128-row workgroup and a fifth 64-key chunk of the streaming kernels).  vithip_attention_f32_rows and the
 q_rows forms have the bits of these entries (test_gpu_ops.py, test_gpu_attention_hd.py, test_gpu_attention_split.py).
 
-Measured on the MI355X: profiles/r29/attention_accuracy.md.
+Measured on the MI355X: profiles/r29/attention_accuracy.md.  The bf16 entries beyond (c) and (d): tests/test_gpu_attention_bf16_accuracy.py.
 """
 import functools
 

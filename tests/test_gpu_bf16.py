@@ -118,7 +118,8 @@ def test_layernorm_bf16_out(oracle):
 def test_attention_bf16_io(oracle, n, T, heads, mfma):
     """bf16 Q/K/V in, bf16 out.  mfma=1: both products on bf16 MFMA, P rounded to bf16 (resident kernel up to
     224 tokens, streamed online-softmax kernel up to 704, chunked kernel beyond); mfma=0: fp32 MFMA on the widened values; mfma=2: as 1 with the Q columns
-    holding QSCALE * q (what the engine's folded in_proj writes): the streamed kernel then starts its score accumulators at -max."""
+    holding QSCALE * q (what the engine's folded in_proj writes): the streamed kernel then starts its score accumulators at -max.
+    Bars of the size of the arithmetic (bits, float64 brackets, shares, bias): tests/test_gpu_attention_bf16_accuracy.py."""
     D = heads * 64
     vals = u(13, (n * T, 3 * D), 1.5)
     if mfma == 2:
