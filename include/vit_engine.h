@@ -239,7 +239,8 @@ int vit_engine_forward_host_u8(vit_engine *e, const unsigned char *const *images
  * VIT_ERR_ARG (the engine stays usable): NULL pointers, n <= 0, unknown kind, l2_normalize other than 0 / 1, l2_normalize with
  * TOKENS, and what the matching forward refuses.
  */
-enum { VIT_FEAT_CLS = 0, VIT_FEAT_MEAN = 1, VIT_FEAT_TOKENS = 2, VIT_FEAT_HEAD = 4 /* 3 stays unassigned: callers know it as an unknown kind (VIT_ERR_ARG) */ };
+enum { VIT_FEAT_CLS = 0, VIT_FEAT_MEAN = 1, VIT_FEAT_TOKENS = 2, VIT_FEAT_HEAD = 4 /* 3 stays unassigned: callers know it as an unknown kind (VIT_ERR_ARG) */,
+       VIT_FEAT_MAP = 5 /* the attention-pool head of vit_engine_set_map_head, below: [n][D]; without one the kind stays unknown (VIT_ERR_ARG) */ };
 typedef struct {
     int kind;          /* VIT_FEAT_* */
     int l2_normalize;  /* 0 / 1; not with TOKENS */
@@ -600,6 +601,43 @@ int vit_engine_dense_device_images(vit_engine *e, const vit_image_u8 *images, in
                                    void *d_out, void *stream);
 int vit_engine_dense_host_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, const vit_dense_spec *spec,
                                  void *const *out);
+
+/*
+ * Attention-pool heads (MAP): the pooling of SigLIP, SigLIP 2 and PaliGemma's tower (transformers' SiglipMultiheadAttentionPoolingHead)
+ * and of timm's global_pool='map' (AttentionPoolLatent) -- one learned query attends over the final-LayerNorm tokens, then an MLP block
+ * with a residual.  The head is engine state beside the encoder, like the classifier and dense heads, and independent of both; its
+ * rows are the features kind VIT_FEAT_MAP, [n][D], served by all six vit_engine_features_* calls (l2_normalize allowed: SigLIP's
+ * zero-shot embedding is the L2-normalised pooler_output).  With y_t = LayerNorm_final(x_t), the keys t = first .. T-1 (first = 1 + R,
+ * the patch tokens, the rule of VIT_FEAT_MEAN; include_prefix = 1: first = 0, every row, as timm pools what forward_features returns),
+ * H = num_heads, hd = D / H:
+ *     q = Wq probe + bq;   k_t, v_t = Wk y_t + bk, Wv y_t + bv;   p[h][t] = softmax_t(hd^-0.5 q_h . k_t,h);   o = concat_h(sum_t p[h][t] v_t,h)
+ *     a = Wo o + bo;       out = a + fc2(act(fc1(LayerNorm_head(a))))                         (hidden_dim = 0: out = a)
+ * in_proj_weight [3D][D] holds the rows of Wq, Wk, Wv in that order, in_proj_bias [3D] their biases (torch.nn.MultiheadAttention;
+ * timm: q.weight over kv.weight); probe [D]; out_proj_weight [D][D]; ln_* [D]; fc1_weight [hidden][D]; fc2_weight [D][hidden]: HOST
+ * fp32 arrays read during the call.  INTEGRATION.md has both checkpoint mappings.
+ * The K/V projection of every token is folded away when the head is installed, in double on the host: the query is a constant, so a
+ * score is y_t . a_h with a_h = hd^-0.5 Wk_h^T q_h (bk adds the same to every score of a head: nothing), and sum_t p v_t,h = Wv_h z_h +
+ * bv_h with z_h = sum_t p[h][t] y_t.  Behind the last layer each lane launches vithip_map_pool_f32 (vit_hip_kernels.h) on its rows of
+ * x, accounted to VIT_STAGE_LN as MEAN's launches are; then, on its n rows and accounted to VIT_STAGE_HEAD, vithip_gemm_f32 for out_proj
+ * (fp32 MFMA on both engine dtypes, as the classifier head), vithip_layernorm_f32_eps with the engine's epsilon, fc1 with
+ * VITHIP_EPI_BIAS_GELU -- or VITHIP_EPI_BIAS and vithip_gelu_tanh_rows_f32 for VIT_MAP_ACT_GELU_TANH -- and fc2 with
+ * VITHIP_EPI_BIAS_RESIDUAL.  The rules of MEAN: a prune_last_layer engine runs the last layer unpruned for that call; the graph key holds the
+ * kind; vit_engine_read_logits() afterwards is an error.  Without a head the kind is refused as an unknown kind is, VIT_ERR_ARG (callers
+ * that probed kind 5 before this head existed see what they saw), and vit_engine_feature_row_elems gives 0.  An image's row has the same bits whatever lanes and prune_last_layer are
+ * set to, wherever the image sits in whatever batch and whichever of the six calls delivers the same pixels.
+ *
+ * vit_engine_set_map_head: the rules of vit_engine_set_head.  It synchronises the device and drops a captured graph; the new
+ * allocations are made before the old ones are freed (VIT_ERR_NOMEM: the previous head stays in force); spec == NULL (w must then be
+ * NULL) removes the head; EVERY weight install removes it and the copy calls do not carry it.  VIT_ERR_STATE: no weights loaded yet.
+ * VIT_ERR_ARG, nothing changed: a NULL member that the spec needs (ln_*, fc1_*, fc2_* only with hidden_dim > 0), num_heads outside
+ * 1..32 or not dividing D, hidden_dim negative or not a multiple of 32, an unknown act, include_prefix other than 0 / 1, reserved != 0,
+ * an embed_dim that is no multiple of 32 or above 2048.
+ */
+enum { VIT_MAP_ACT_GELU = 0, VIT_MAP_ACT_GELU_TANH = 1 };
+typedef struct { int num_heads, hidden_dim /* 0: no MLP block */, act, include_prefix, reserved; } vit_map_head_spec;
+typedef struct { const float *probe, *in_proj_weight, *in_proj_bias, *out_proj_weight, *out_proj_bias,
+                 *ln_weight, *ln_bias, *fc1_weight, *fc1_bias, *fc2_weight, *fc2_bias; } vit_map_head_weights;  /* host fp32 */
+int vit_engine_set_map_head(vit_engine *e, const vit_map_head_spec *spec, const vit_map_head_weights *w);
 
 /*
  * CLIP image towers (OpenAI / OpenCLIP ViT-B/32, B/16, L/14): VIT_MLP_QUICKGELU (or VIT_MLP_GELU for OpenCLIP checkpoints trained with

@@ -586,6 +586,37 @@ int vithip_pool_layernorm_f32_eps(vithip_stream_t stream, const float *x, size_t
                                   const float *beta, int images, int tokens, int first_tok, int dim, float *workspace, double eps);
 
 /*
+ * Attention pooling with one constant query per head (csrc/vit_map_head.hip): SigLIP's pooling head, timm global_pool='map'.  With
+ * y_t = LayerNorm(x_t) (gamma, beta, eps; the statistics of vithip_layernorm_f32), row (i, t) at x + (i * tokens + t) * ldx, the keys
+ * t = first_tok .. tokens-1, hd = dim / heads and a [heads][dim] the FOLDED queries a_h = hd^-0.5 * Wk_h^T (Wq probe + bq)_h:
+ *     p[h][t] = softmax_t(y_t . a_h);   z_h = sum_t p[h][t] y_t;   out[i][h*hd .. (h+1)*hd) = wv[h*hd .. (h+1)*hd)[:] . z_h + bv[h*hd ..]
+ * which is concat_h(sum_t p[h][t] (Wv y_t + bv)_h): multi-head attention of one query over the LayerNorm rows, without its K/V
+ * projection (the key bias adds the same to every score of a head and leaves the softmax).  x is read once; y is never stored.
+ * Three launches: gamma o a into the workspace; one workgroup per (image, segment of consecutive key rows) that leaves the segment's
+ * maximum, sum and un-normalised z per head in the workspace, every exponential behind a maximum subtraction, both products on fp32
+ * matrix instructions; one workgroup per (head, 16 images) that merges the segments in index order, divides and multiplies with wv.
+ * Deterministic and position independent: the segmentation and every order of summation depend on (tokens, first_tok, dim, heads)
+ * only, so an image's output row has the same bits alone and at every place of every batch.  No atomics.  A non-finite row of x
+ * reaches its own image's row only.  Only out[i][0..dim) and the workspace are written.
+ * workspace: vithip_map_pool_f32_workspace_floats(images, tokens, first_tok, dim, heads) floats of device scratch, 16-byte aligned,
+ * owned by the caller and free again when the launches have run (0 for arguments the launcher refuses).
+ * dim % 4 == 0, dim <= 2048, 1 <= heads <= 32, dim % heads == 0, tokens - first_tok >= 1, first_tok >= 0, ldx / ldo >= dim and
+ * multiples of 4, every pointer 16-byte aligned, eps finite and > 0; hipErrorInvalidValue otherwise, nothing launched.
+ */
+size_t vithip_map_pool_f32_workspace_floats(int images, int tokens, int first_tok, int dim, int heads);
+int vithip_map_pool_f32(vithip_stream_t stream, const float *x, size_t ldx, const float *gamma, const float *beta, double eps,
+                        const float *a,  /* [heads][dim], the folded queries */
+                        const float *wv, /* [dim][dim], rows h*hd.. are head h */
+                        const float *bv, /* [dim] */
+                        float *out, size_t ldo, /* [images][dim] = concat_h(Wv_h z_h + bv_h) */
+                        int images, int tokens, int first_tok, int dim, int heads, float *workspace);
+/* x[r][0..cols) = x * sigmoid(2 * 0.7978845608 * (x + 0.044715 x^3)) in place: GELU's tanh approximation (PyTorch
+ * gelu(approximate="tanh"), "gelu_pytorch_tanh"), the exponential through v_exp_f32 and v_rcp_f32 as VITHIP_EPI_BIAS_QGELU takes its
+ * own.  One workgroup per row: meant for the few hidden rows of a pooling head.  cols % 4 == 0, ldx >= cols and a multiple of 4, x
+ * 16-byte aligned; hipErrorInvalidValue otherwise. */
+int vithip_gelu_tanh_rows_f32(vithip_stream_t stream, float *x, size_t ldx, int rows, int cols);
+
+/*
  * The class token's attention over the tokens of its image (csrc/vit_cls_attention.hip): the softmax row of query 0, stored instead
  * of multiplied with V.  qkv as vithip_attention_f32 / _bf16io read it: rows = tokens, q_row_stride elements from one token row to
  * the next (3 * heads * 64 for packed rows), columns [Q | K | V], head h = columns 64h..64h+63 of each.  For image i and head h, with

@@ -61,7 +61,28 @@ class CFeatureSpec(C.Structure):  # vit_feature_spec
     _fields_ = [("kind", C.c_int), ("l2_normalize", C.c_int)]
 
 
-FEATURE_KINDS = {"cls": 0, "mean": 1, "tokens": 2, "head": 4}  # VIT_FEAT_* (3 is unassigned)
+FEATURE_KINDS = {"cls": 0, "mean": 1, "tokens": 2, "head": 4, "map": 5}  # VIT_FEAT_* (3 is unassigned)
+
+
+class CMapHeadSpec(C.Structure):  # vit_map_head_spec
+    _fields_ = [("num_heads", C.c_int), ("hidden_dim", C.c_int), ("act", C.c_int), ("include_prefix", C.c_int), ("reserved", C.c_int)]
+
+
+MAP_HEAD_TENSORS = ("probe", "in_proj_weight", "in_proj_bias", "out_proj_weight", "out_proj_bias", "ln_weight", "ln_bias",
+                    "fc1_weight", "fc1_bias", "fc2_weight", "fc2_bias")
+
+
+class CMapHeadWeights(C.Structure):  # vit_map_head_weights: host fp32 arrays, in the order of MAP_HEAD_TENSORS
+    _fields_ = [(name, C.POINTER(C.c_float)) for name in MAP_HEAD_TENSORS]
+
+
+MAP_ACTS = {"gelu": 0, "gelu_tanh": 1}  # VIT_MAP_ACT_*
+
+
+def map_head_spec(num_heads: int, hidden_dim: int = 0, act="gelu", include_prefix=False, reserved: int = 0) -> CMapHeadSpec:
+    """act: "gelu" | "gelu_tanh" (or a raw VIT_MAP_ACT_* integer); everything is passed through unchecked for the C side to judge."""
+    return CMapHeadSpec(int(num_heads), int(hidden_dim), MAP_ACTS[act] if isinstance(act, str) else int(act), int(include_prefix),
+                        int(reserved))
 
 
 class CAttentionSpec(C.Structure):  # vit_attention_spec
@@ -176,7 +197,7 @@ def _resize_filter(filter) -> int:
 
 
 def feature_spec(kind, l2_normalize=False) -> CFeatureSpec:
-    """kind: "cls" | "mean" | "tokens" (or a raw VIT_FEAT_* integer, passed through unchecked for the C side to judge)."""
+    """kind: "cls" | "mean" | "tokens" | "head" | "map" (or a raw VIT_FEAT_* integer, passed through unchecked for the C side to judge)."""
     k = FEATURE_KINDS[kind] if isinstance(kind, str) else int(kind)
     return CFeatureSpec(k, int(l2_normalize))
 
@@ -361,6 +382,13 @@ def lib() -> C.CDLL:
             L.vithip_pool_layernorm_f32_workspace_floats.argtypes = [C.c_int] * 4
             L.vithip_pool_layernorm_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        if hasattr(L, "vit_engine_set_map_head"):  # an earlier build (see above) has no attention-pool heads
+            L.vit_engine_set_map_head.argtypes = [C.c_void_p, C.POINTER(CMapHeadSpec), C.POINTER(CMapHeadWeights)]
+            L.vithip_map_pool_f32_workspace_floats.restype = C.c_size_t
+            L.vithip_map_pool_f32_workspace_floats.argtypes = [C.c_int] * 5
+            L.vithip_map_pool_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_int] * 5 + [C.c_void_p]
+            L.vithip_gelu_tanh_rows_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int]
         if hasattr(L, "vit_engine_set_dense_head"):  # an earlier build (see above) has no dense heads
             L.vit_engine_set_dense_head.argtypes = [C.c_void_p, C.POINTER(CDenseHeadSpec), f32p, f32p]
             L.vit_engine_dense_row_bytes.restype = C.c_size_t
@@ -1036,6 +1064,39 @@ def pool_layernorm(x, gamma, beta, images: int, tokens: int, first_tok: int = 1,
     fn, e = _ln_fn("vithip_pool_layernorm_f32", eps)
     hip_check(fn(None, *a.values(), *e), "vithip_pool_layernorm_f32")
     return do.window()
+
+
+def map_pool(x, gamma, beta, a, wv, bv, images: int, tokens: int, first_tok: int = 1, eps: float = 1e-6, ldx: Optional[int] = None,
+             ldo: Optional[int] = None, frames=None, out: Optional[dict] = None, override: Optional[dict] = None,
+             out_offset: int = 0) -> np.ndarray:
+    """vithip_map_pool_f32: x [images * tokens][dim], the folded queries a [heads][dim], wv [dim][dim], bv [dim] -> [images][dim],
+    concat_h(Wv_h z_h + bv_h) of the attention pooling over the LayerNorm rows first_tok...  ldx / ldo, frames, out, override,
+    out_offset: as for pool_layernorm(); the output frames are "out" and "ws" (the workspace, exactly the declared floats)."""
+    x, a = _as_f32(x), _as_f32(a)
+    rows, dim = x.shape
+    heads = a.shape[0]
+    assert rows == images * tokens and a.shape == (heads, dim)
+    L = lib()
+    F = frames or _Plain
+    dx, dg, db = F.framed(x, ldx), F.framed(_as_f32(gamma)), F.framed(_as_f32(beta))
+    da, dw, dbv = F.framed(a), F.framed(_as_f32(wv).reshape(dim, dim)), F.framed(_as_f32(bv))
+    do = F.out_frame(images, dim, ldo, offset=out_offset)
+    ws = F.out_frame(1, max(1, L.vithip_map_pool_f32_workspace_floats(images, tokens, first_tok, dim, heads)))
+    _note(out, out=do, ws=ws)
+    args = dict(x=dx.ptr, ldx=dx.ld, gamma=dg.ptr, beta=db.ptr, eps=float(eps), a=da.ptr, wv=dw.ptr, bv=dbv.ptr, out=do.ptr, ldo=do.ld,
+                images=images, tokens=tokens, first_tok=first_tok, dim=dim, heads=heads, workspace=ws.ptr)
+    args.update(override or {})
+    hip_check(L.vithip_map_pool_f32(None, *args.values()), "vithip_map_pool_f32")
+    return do.window()
+
+
+def gelu_tanh_rows(x) -> np.ndarray:
+    """vithip_gelu_tanh_rows_f32 (in place on the device): x * sigmoid(2 * 0.7978845608 * (x + 0.044715 x^3)), row by row."""
+    x = _as_f32(x)
+    rows, cols = x.shape
+    dx = DeviceArray.from_numpy(x)
+    hip_check(lib().vithip_gelu_tanh_rows_f32(None, dx.ptr, cols, rows, cols), "vithip_gelu_tanh_rows_f32")
+    return dx.numpy()
 
 
 def l2_normalize_rows(x) -> np.ndarray:
@@ -1882,6 +1943,19 @@ class Engine:
             raise VitError(f"set_dense_head: weight has {w.size} floats, {b.size} classes over {spec.num_layers} layers need {b.size} x {F}")
         self._check(lib().vit_engine_set_dense_head(self._h, C.byref(spec), None if w is None else w.ctypes.data_as(f32p),
                                                     None if b is None else b.ctypes.data_as(f32p)), "vit_engine_set_dense_head")
+
+    # ---- attention-pool heads (vit_engine_set_map_head): features(imgs, "map") ----
+    def set_map_head(self, spec: "CMapHeadSpec", weights: dict) -> None:
+        """The attention-pool head (SigLIP's pooling head, timm global_pool='map') behind features(imgs, "map"): spec from
+        map_head_spec(), weights a dict by MAP_HEAD_TENSORS (synth.make_map_head gives one; None or absent entries become NULL).
+        Every weight install removes the head: call this again behind it."""
+        keep = {k: _as_f32(v) for k, v in weights.items() if v is not None}
+        w = CMapHeadWeights(**{k: v.ctypes.data_as(f32p) for k, v in keep.items()})
+        self._check(lib().vit_engine_set_map_head(self._h, C.byref(spec), C.byref(w)), "vit_engine_set_map_head")
+
+    def reset_map_head(self) -> None:
+        """Remove the attention-pool head (vit_engine_set_map_head with a NULL spec)."""
+        self._check(lib().vit_engine_set_map_head(self._h, None, None), "vit_engine_set_map_head")
 
     def reset_dense_head(self) -> None:
         """Remove the dense head (vit_engine_set_dense_head with a NULL spec)."""

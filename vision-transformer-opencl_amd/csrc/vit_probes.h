@@ -35,6 +35,10 @@ int vithip_attention_set_debug_buffer(void *buf);
  * bit 1 no LDS fragment reads, bit 2 waves 4-7 idle, bit 3 no LDS-DMA after the first item */
 int vithip_attention_set_probe_mode(int mode); /* 8 x u64 cycle stamps per (image, head) workgroup; NULL disables */
 
+/* override of the attention-pool head's segment length (key rows per workgroup of vithip_map_pool_f32; a multiple of 16, 0 = none):
+ * the workspace query follows it, so size the workspace behind the call (tools/map_head_time.py sweeps it) */
+int vithip_map_pool_set_ts(int ts);
+
 /* register-only fp32 MFMA loop; each wave issues iters*32 v_mfma_f32_32x32x2_f32 (4096 flop each) */
 int vithip_probe_mfma_f32(vithip_stream_t stream, float *out, int blocks, int threads, int iters);
 /* per wave `iters` 16-B-per-lane stores; mode 0 = 1 KB contiguous, 1 = 16 rows x 64 B, 2 = 8 rows x 128 B at row stride

@@ -98,6 +98,18 @@ typedef struct { vit_head_spec spec; size_t in; vit_gemm_ops ops; float *operand
  * 1x1 conv's W [num_classes][num_layers * D] (a zeroed tail pad behind it) and bias, a zero bias for the chain's later GEMMs, the
  * patch rows of the layer just tapped [max_batch][P][D] and the logits [max_batch][P][num_classes]: five allocations of its own. */
 typedef struct { vit_dense_head_spec spec; float *W, *bias, *zero_bias, *rows, *logits; } vit_dense_head;
+/* The attention-pool head in force (vit_engine_set_map_head; blob == NULL: none): the checked spec, the first key row, and two
+ * allocations of its own -- blob, the operands [A | Wv | bv | Wo | bo | ln_g | ln_b | fc1 | fc2] with a zeroed tail pad, and rows,
+ * [pooled [B][D] | LayerNorm rows [B][D] | hidden rows [B][hidden] | the pooling workspace of every lane], B = max_batch. */
+typedef struct {
+    vit_map_head_spec spec;
+    int first;
+    float *blob, *rows;
+    const float *A, *wv, *bv, *ln_g, *ln_b;
+    vit_gemm_ops out, fc1, fc2;
+    float *pooled, *ln_rows, *hidden, *ws;
+    size_t ws_floats;
+} vit_map_head;
 
 struct vit_engine {
     vit_config cfg;
@@ -145,6 +157,7 @@ struct vit_engine {
     /* the one classifier head: the checkpoint's own (restore_own_head) or a caller's (vit_engine_set_head); no stage tells them apart */
     vit_head head;
     vit_dense_head dense;
+    vit_map_head map;
     /* host-pointer path: double-buffered staging so that gather + H2D of piece i+1 overlap compute of piece i */
     float *in_stage[2], *out_stage[2];   /* device */
     float *pin_in[2], *pin_out[2];       /* pinned host */
@@ -447,6 +460,12 @@ static void release_dense_head(vit_dense_head *h) {
     memset(h, 0, sizeof(*h));
 }
 
+/* ... and so do the attention-pool head's */
+static void release_map_head(vit_map_head *h) {
+    vithip_free(h->blob); vithip_free(h->rows);
+    memset(h, 0, sizeof(*h));
+}
+
 void vit_engine_destroy(vit_engine *e) {
     if (!e) return;
     vithip_set_device(e->opt.device);
@@ -458,6 +477,7 @@ void vit_engine_destroy(vit_engine *e) {
     vithip_free(e->z); vithip_free(e->logits);
     release_head(&e->head);
     release_dense_head(&e->dense);
+    release_map_head(&e->map);
     vithip_free(e->pre_g); /* one allocation: gamma, beta behind it */
     for (int j = 0; j < VIT_MAX_LANES; ++j) vithip_gemm_f32_workspace_destroy(e->gemm_ws[j]);
     if (e->copy_stream) { vithip_stream_sync(e->copy_stream); vithip_stream_destroy(e->copy_stream); }
@@ -663,6 +683,7 @@ static int finish_install(vit_engine *e) {
     const int rc = resolve_operands(e);
     restore_own_head(e);
     release_dense_head(&e->dense); /* a caller's head like the classifier's: every install removes it */
+    release_map_head(&e->map);
     release_pre_norm(e); /* checkpoint data like a caller's head: every install removes it (the epsilon, architecture, stays) */
     if (rc) return rc;
     HIP_TRY(e, vithip_stream_sync(e->stream));
@@ -1254,6 +1275,60 @@ static int stage_head(chunk_ctx *c, const vit_output *out) {
     return VIT_OK;
 }
 
+/* The attention-pool head (vit_map_head), first part: the lane's rows of x through vithip_map_pool_f32 into the head's pooled rows.
+ * Every lane has its own stretch of the workspace (lanes run on independent streams): the stretches of the lanes in front of it. */
+static int map_pooled_block(chunk_ctx *c, const vit_lane *ln) {
+    vit_engine *e = c->e;
+    const vit_map_head *h = &e->map;
+    const size_t D = (size_t)c->D;
+    size_t at_ws = 0;
+    for (const vit_lane *p = c->lane; p != ln; ++p) at_ws += vithip_map_pool_f32_workspace_floats(p->n, c->T, h->first, c->D, h->spec.num_heads);
+    const size_t need = vithip_map_pool_f32_workspace_floats(ln->n, c->T, h->first, c->D, h->spec.num_heads);
+    if (need == 0 || at_ws + need > h->ws_floats)
+        return fail(e, VIT_ERR_STATE, "features: the attention-pool workspace (%zu floats at %zu) does not fit its %zu", need, at_ws, h->ws_floats);
+    HIP_TRY(e, vithip_map_pool_f32(ln->s, ln->x, D, e->final.ln_g, e->final.ln_b, e->ln_eps, h->A, h->wv, h->bv, h->pooled + (size_t)ln->off * D, D,
+                                   ln->n, c->T, h->first, c->D, h->spec.num_heads, h->ws + at_ws));
+    return VIT_OK;
+}
+
+/* ... second part, on the n pooled rows of every lane: out_proj into the caller's rows, then (hidden_dim > 0) LayerNorm, fc1 with its
+ * activation and fc2 added in place; fp32 MFMA GEMMs on both engine dtypes, as the classifier head's (VIT_STAGE_HEAD); l2 last. */
+static int map_head_rows(chunk_ctx *c, const vit_output *out) {
+    vit_engine *e = c->e;
+    const vit_map_head *h = &e->map;
+    const int D = c->D, HD = h->spec.hidden_dim;
+    for (int j = 0; j < c->L; ++j) {
+        const vit_lane *ln = &c->lane[j];
+        const size_t o = (size_t)ln->off;
+        float *dst = out->dst + o * D, *lnr = h->ln_rows + o * D, *hid = h->hidden + o * HD;
+        const gemm_desc op = {.stage = VIT_STAGE_HEAD, .A = h->pooled + o * D, .lda = D, .ops = h->out, .C = dst, .ldc = D, .M = ln->n, .N = D,
+                              .K = D, .role = VITHIP_EPI_BIAS};
+        RUN(gemm(e, ln->s, &op, NULL));
+        if (HD) {
+            const gemm_desc f1 = {.stage = VIT_STAGE_HEAD, .A = lnr, .lda = D, .ops = h->fc1, .C = hid, .ldc = HD, .M = ln->n, .N = HD, .K = D,
+                                  .role = h->spec.act == VIT_MAP_ACT_GELU ? VITHIP_EPI_BIAS_GELU : VITHIP_EPI_BIAS};
+            const gemm_desc f2 = {.stage = VIT_STAGE_HEAD, .A = hid, .lda = HD, .ops = h->fc2, .C = dst, .ldc = D, .M = ln->n, .N = D, .K = HD,
+                                  .role = VITHIP_EPI_BIAS_RESIDUAL};
+            HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
+            HIP_TRY(e, vithip_layernorm_f32_eps(ln->s, dst, (size_t)D, lnr, (size_t)D, h->ln_g, h->ln_b, ln->n, D, e->ln_eps));
+            HIP_TRY(e, stage_end(e, ln->s));
+            RUN(gemm(e, ln->s, &f1, NULL));
+            if (h->spec.act == VIT_MAP_ACT_GELU_TANH) {
+                HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_HEAD));
+                HIP_TRY(e, vithip_gelu_tanh_rows_f32(ln->s, hid, (size_t)HD, ln->n, HD));
+                HIP_TRY(e, stage_end(e, ln->s));
+            }
+            RUN(gemm(e, ln->s, &f2, NULL));
+        }
+        if (out->spec.l2_normalize) {
+            HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
+            HIP_TRY(e, vithip_l2_normalize_rows_f32(ln->s, dst, (size_t)D, ln->n, D));
+            HIP_TRY(e, stage_end(e, ln->s));
+        }
+    }
+    return VIT_OK;
+}
+
 /* The embedding rows of the chunk instead of the head: the class block (the checkpoint's own head's operand, in the caller's rows),
  * the final LayerNorm of every row, or the pooled block. */
 static int stage_features(chunk_ctx *c, const vit_output *out) {
@@ -1268,9 +1343,11 @@ static int stage_features(chunk_ctx *c, const vit_output *out) {
             if (out->spec.l2_normalize) HIP_TRY(e, vithip_l2_normalize_rows_f32(ln->s, dst, D, ln->n, c->D));
         } else if (out->spec.kind == VIT_FEAT_TOKENS)
             HIP_TRY(e, vithip_layernorm_f32_eps(ln->s, ln->x, D, dst, D, e->final.ln_g, e->final.ln_b, ln->n * c->T, c->D, e->ln_eps));
+        else if (out->spec.kind == VIT_FEAT_MAP) RUN(map_pooled_block(c, ln));
         else RUN(pooled_block(c, ln, dst, D, 0, out->spec.l2_normalize, "features"));
         HIP_TRY(e, stage_end(e, ln->s));
     }
+    if (out->spec.kind == VIT_FEAT_MAP) RUN(map_head_rows(c, out));
     return VIT_OK;
 }
 
@@ -1423,10 +1500,13 @@ static const char *features_check(const vit_engine *e, const void *caller, vit_o
     const vit_feature_spec *spec = (const vit_feature_spec *)caller;
     if (!spec) return "%s: the feature spec is required";
     arg[0] = spec->kind;
-    if (spec->kind != VIT_FEAT_CLS && spec->kind != VIT_FEAT_MEAN && spec->kind != VIT_FEAT_TOKENS && spec->kind != VIT_FEAT_HEAD) return "%s: unknown feature kind %d";
+    if (spec->kind != VIT_FEAT_CLS && spec->kind != VIT_FEAT_MEAN && spec->kind != VIT_FEAT_TOKENS && spec->kind != VIT_FEAT_HEAD && spec->kind != VIT_FEAT_MAP) return "%s: unknown feature kind %d";
     arg[0] = spec->l2_normalize;
     if (spec->l2_normalize != 0 && spec->l2_normalize != 1) return "%s: l2_normalize must be 0 or 1 (got %d)";
     if (spec->l2_normalize && spec->kind == VIT_FEAT_TOKENS) return "%s: l2_normalize applies to the CLS, MEAN and HEAD rows, not to TOKENS";
+    /* without its head the kind is what it was before the head existed, an unknown one: the same code, a message that says why */
+    arg[0] = spec->kind;
+    if (spec->kind == VIT_FEAT_MAP && !e->map.blob) return "%s: feature kind %d (VIT_FEAT_MAP) needs a head from vit_engine_set_map_head()";
     if (spec->kind == VIT_FEAT_MEAN && e->patches < 1) return "%s: MEAN needs at least one patch token";
     out->spec.kind = spec->kind; out->spec.l2_normalize = spec->l2_normalize;
     return NULL;
@@ -2478,6 +2558,98 @@ int vit_engine_set_dense_head(vit_engine *e, const vit_dense_head_spec *spec, co
     for (int j = 0; j < spec->num_layers; ++j) h.spec.layers[j] = spec->layers[j];
     h.spec.norm = spec->norm; h.spec.num_classes = spec->num_classes;
     e->dense = h;
+    return VIT_OK;
+}
+
+int vit_engine_set_map_head(vit_engine *e, const vit_map_head_spec *spec, const vit_map_head_weights *w) {
+    if (!e) return VIT_ERR_ARG;
+    if (!spec && w) return fail(e, VIT_ERR_ARG, "set_map_head: a NULL spec (no attention-pool head) takes no weights");
+    const size_t D = (size_t)e->cfg.embed_dim;
+    if (spec) {
+        const int H = spec->num_heads, HD = spec->hidden_dim;
+        if (H < 1 || H > 32 || D % (size_t)H) return fail(e, VIT_ERR_ARG, "set_map_head: num_heads = %d must be 1..32 and divide embed_dim = %zu", H, D);
+        if (HD < 0 || HD % 32) return fail(e, VIT_ERR_ARG, "set_map_head: hidden_dim = %d must be 0 (no MLP block) or a positive multiple of 32", HD);
+        if (spec->act != VIT_MAP_ACT_GELU && spec->act != VIT_MAP_ACT_GELU_TANH) return fail(e, VIT_ERR_ARG, "set_map_head: unknown act %d", spec->act);
+        if (spec->include_prefix != 0 && spec->include_prefix != 1) return fail(e, VIT_ERR_ARG, "set_map_head: include_prefix must be 0 or 1 (got %d)", spec->include_prefix);
+        if (spec->reserved != 0) return fail(e, VIT_ERR_ARG, "set_map_head: vit_map_head_spec.reserved must be 0 (got %d)", spec->reserved);
+        if (D % 32 || D > 2048) return fail(e, VIT_ERR_ARG, "set_map_head: embed_dim = %zu must be a multiple of 32, at most 2048", D);
+        if (!spec->include_prefix && e->patches < 1) return fail(e, VIT_ERR_ARG, "set_map_head: pooling the patch tokens needs at least one");
+        if (!w || !w->probe || !w->in_proj_weight || !w->in_proj_bias || !w->out_proj_weight || !w->out_proj_bias)
+            return fail(e, VIT_ERR_ARG, "set_map_head: probe, in_proj and out_proj weights and biases are required with a spec");
+        if (HD && (!w->ln_weight || !w->ln_bias || !w->fc1_weight || !w->fc1_bias || !w->fc2_weight || !w->fc2_bias))
+            return fail(e, VIT_ERR_ARG, "set_map_head: hidden_dim = %d needs the LayerNorm, fc1 and fc2 weights and biases", HD);
+    }
+    if (!e->weights_loaded) return fail(e, VIT_ERR_STATE, "set_map_head before vit_engine_load_weights()");
+    HIP_TRY(e, vithip_set_device(e->opt.device));
+    if (!spec) { /* as an install: nothing in flight, no graph with the head's buffers in its launches */
+        HIP_TRY(e, vithip_device_sync());
+        drop_graph(e);
+        release_map_head(&e->map);
+        return VIT_OK;
+    }
+    /* the new head first, whole; only then the old one goes */
+    const size_t H = (size_t)spec->num_heads, HD = (size_t)spec->hidden_dim, hd = D / H, B = (size_t)e->opt.max_batch;
+    const size_t wfloats = H * D + 2 * D * D + 5 * D + 2 * HD * D + HD;
+    const int first = spec->include_prefix ? 0 : e->prefix;
+    vit_map_head h;
+    memset(&h, 0, sizeof(h));
+    h.spec = *spec; h.first = first;
+    h.ws_floats = vithip_map_pool_f32_workspace_floats((int)B, e->tokens, first, (int)D, (int)H) +
+                  VIT_MAX_LANES * vithip_map_pool_f32_workspace_floats(1, e->tokens, first, (int)D, (int)H);
+    float *host = (float *)malloc(wfloats * sizeof(float));
+    double *q = (double *)malloc(D * sizeof(double));
+    if (!host || !q) { free(host); free(q); return fail(e, VIT_ERR_NOMEM, "set_map_head: no host memory for %zu floats; the previous head stays", wfloats); }
+    /* the fold, in double: q = Wq probe + bq; a_h = hd^-0.5 * Wk_h^T q_h.  bk adds q_h . bk_h to every score of head h: nothing */
+    for (size_t r = 0; r < D; ++r) {
+        double acc = w->in_proj_bias[r];
+        for (size_t k = 0; k < D; ++k) acc += (double)w->in_proj_weight[r * D + k] * (double)w->probe[k];
+        q[r] = acc;
+    }
+    float *p = host;
+    for (size_t hh = 0; hh < H; ++hh)
+        for (size_t k = 0; k < D; ++k) {
+            double acc = 0.0;
+            for (size_t j = 0; j < hd; ++j) acc += (double)w->in_proj_weight[(D + hh * hd + j) * D + k] * q[hh * hd + j];
+            *p++ = (float)(acc / sqrt((double)hd));
+        }
+    free(q);
+#define PUT(src, n) (memcpy(p, (src), (n) * sizeof(float)), p += (n), p - (n))
+    const float *hA = host, *hwv = PUT(w->in_proj_weight + 2 * D * D, D * D), *hbv = PUT(w->in_proj_bias + 2 * D, D);
+    const float *hwo = PUT(w->out_proj_weight, D * D), *hbo = PUT(w->out_proj_bias, D);
+    const float *hg = NULL, *hb = NULL, *hw1 = NULL, *hb1 = NULL, *hw2 = NULL, *hb2 = NULL;
+    if (HD) {
+        hg = PUT(w->ln_weight, D); hb = PUT(w->ln_bias, D);
+        hw1 = PUT(w->fc1_weight, HD * D); hb1 = PUT(w->fc1_bias, HD);
+        hw2 = PUT(w->fc2_weight, D * HD); hb2 = PUT(w->fc2_bias, D);
+    }
+#undef PUT
+    const size_t used = (size_t)(p - host), row_floats = B * (2 * D + HD) + h.ws_floats;
+    int hrc = vithip_malloc((void **)&h.blob, used * sizeof(float) + WEIGHT_TAIL_PAD);
+    if (!hrc) hrc = vithip_malloc((void **)&h.rows, row_floats * sizeof(float));
+    if (hrc) {
+        free(host); release_map_head(&h);
+        return fail(e, VIT_ERR_NOMEM, "set_map_head: no memory for %zu weight floats and %zu floats of rows (HIP error %d: %s); the previous head stays",
+                    used, row_floats, hrc, vithip_error_string(hrc));
+    }
+    hrc = vithip_memcpy_h2d(h.blob, host, used * sizeof(float), e->stream);
+    if (!hrc) hrc = vithip_memset((char *)h.blob + used * sizeof(float), 0, WEIGHT_TAIL_PAD, e->stream);
+    if (!hrc) hrc = vithip_memset(h.rows, 0, row_floats * sizeof(float), e->stream);
+    if (!hrc) hrc = vithip_device_sync(); /* the uploads, and every call that still uses the old head, on whatever stream */
+    free(host);
+    if (hrc) {
+        release_map_head(&h);
+        return fail(e, VIT_ERR_HIP, "set_map_head: HIP error %d (%s) uploading the head; the previous head stays", hrc, vithip_error_string(hrc));
+    }
+#define DEV(hp) ((hp) ? h.blob + ((hp) - host) : NULL)
+    h.A = DEV(hA); h.wv = DEV(hwv); h.bv = DEV(hbv); h.ln_g = DEV(hg); h.ln_b = DEV(hb);
+    h.out = (vit_gemm_ops){.W = DEV(hwo), .bias = DEV(hbo)};
+    h.fc1 = (vit_gemm_ops){.W = DEV(hw1), .bias = DEV(hb1)};
+    h.fc2 = (vit_gemm_ops){.W = DEV(hw2), .bias = DEV(hb2)};
+#undef DEV
+    h.pooled = h.rows; h.ln_rows = h.pooled + B * D; h.hidden = h.ln_rows + B * D; h.ws = h.hidden + B * HD;
+    drop_graph(e);
+    release_map_head(&e->map);
+    e->map = h;
     return VIT_OK;
 }
 

@@ -196,6 +196,21 @@ def make_images(cfg: ModelConfig, n: int, seed: int = 99) -> np.ndarray:
     return out.reshape(n, cfg.in_chans, cfg.img_size, cfg.img_size)
 
 
+def make_map_head(dim: int, heads: int, hidden: int, seed: int = 4321) -> dict:
+    """Seeded weights of an attention-pool head (binding.MAP_HEAD_TENSORS) at embed_dim `dim`: the probe and the projections
+    uniform at the encoder's weight scale, the LayerNorm near identity; hidden = 0 leaves the MLP block's tensors out."""
+    shapes = [("probe", (dim,), 0.5), ("in_proj_weight", (3 * dim, dim), 3.0 / np.sqrt(dim)), ("in_proj_bias", (3 * dim,), 0.05),
+              ("out_proj_weight", (dim, dim), 1.0 / np.sqrt(dim)), ("out_proj_bias", (dim,), 0.05)]
+    if hidden:
+        shapes += [("ln_weight", (dim,), 0.2), ("ln_bias", (dim,), 0.05), ("fc1_weight", (hidden, dim), 1.0 / np.sqrt(dim)),
+                   ("fc1_bias", (hidden,), 0.05), ("fc2_weight", (dim, hidden), 1.0 / np.sqrt(hidden)), ("fc2_bias", (dim,), 0.05)]
+    out = {}
+    for i, (name, shape, r) in enumerate(shapes):
+        w = uniform(seed, 1000 + i, int(np.prod(shape)), -r, r).reshape(shape)
+        out[name] = (w + np.float32(1.0)) if name == "ln_weight" else w
+    return out
+
+
 def write_weight_files(directory: str, weights, names=None) -> None:
     """Write Weight_<idx>_<name>.bin files (raw LE fp32), the layout load_weights() scans."""
     os.makedirs(directory, exist_ok=True)
