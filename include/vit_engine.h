@@ -666,6 +666,25 @@ double vit_engine_get_layernorm_eps(const vit_engine *e);
 int vit_engine_set_pre_norm(vit_engine *e, const float *gamma, const float *beta);
 
 /*
+ * DINOv3 (transformers' DINOv3ViTModel): no learned position embedding; every layer rotates the patch rows of Q and K by an axial 2-D
+ * rotary embedding in front of the scores.  vit_engine_set_rope(theta > 0) turns that on (DINOv3: theta = 100), 0 turns it off (the
+ * default).  With g = img_size / patch, patch p = (r, c) in row-major order and hd = embed_dim / num_heads:
+ *     f_i = theta^(-4 i / hd), i < hd / 4;   y_r = 2 (r + 0.5) / g - 1, x_c likewise
+ *     a[p][j] = 2 pi y_r f_j for j < hd / 4,  2 pi x_c f_(j - hd/4) for hd / 4 <= j < hd / 2
+ * built on the host in double (cos and sin in double), each entry rounded once to fp32, uploaded once as [patches][hd / 2] tables.
+ * Every encoder layer then issues one launch per lane of vithip_rope_f32 / _bf16 (vit_hip_kernels.h) between in_proj and attention,
+ * accounted to VIT_STAGE_ATTN: Q and K of the patch rows, or K alone in a pruned last layer; the class and register rows and V keep
+ * their bits.  Attention calls read the rotated K of the last layer.  An engine that never turns it on issues the launches it always
+ * issued.  Architecture, like the LayerNorm epsilon: it PERSISTS across weight installs, and the copy calls do not carry it.  The
+ * position-embedding tensor (weight 3) stays in the weight list: a DINOv3 caller passes zeros.  Synchronises the
+ * device and drops a captured graph.  VIT_ERR_ARG, nothing changed: theta negative or not finite.  The new tables are allocated
+ * before the old ones are freed: on VIT_ERR_NOMEM the previous setting stays in force.  vit_engine_get_rope: the theta in force, 0: off.
+ * Not done: the training-time coordinate augmentations, non-square grids.
+ */
+int vit_engine_set_rope(vit_engine *e, double theta);
+double vit_engine_get_rope(const vit_engine *e);
+
+/*
  * The fp32 GEMMs' helper-piece hand-over (csrc/vit_gemm_persistent.hip) since the last call, summed over the lanes: tiles whose
  * first K-steps came from a helper workgroup / tiles whose owner found no piece when it looked and computed all of it.  The
  * second number is lost time, never a wrong result (nothing in the hand-over waits or gives up).  Synchronises the device.

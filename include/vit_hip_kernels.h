@@ -425,6 +425,32 @@ int vithip_swiglu_f32(vithip_stream_t stream, const float *u, size_t ldu, float 
 int vithip_swiglu_bf16(vithip_stream_t stream, const unsigned short *u, size_t ldu, unsigned short *h, size_t ldh, int rows, int H);
 
 /*
+ * Rotary position embedding on Q and K, in place (csrc/vit_rope.hip; DINOv3: apply_rotary_pos_emb of transformers' DINOv3ViTModel).
+ * qkv: [n_images * tokens][ld], ld >= 3D, D = heads * head_dim; columns [Q | K | V], head h = columns h * head_dim .. of each.
+ * cos, sin: fp32 tables [tokens - prefix][head_dim / 2]: row p belongs to token row prefix + p of every image, and entry j to the
+ * elements j and j + head_dim / 2 of every head (the reference tiles its angles twice).  For every image, every patch row
+ * (token >= prefix), every head of Q and of K and every j < head_dim / 2, with x1 = v[j], x2 = v[j + head_dim / 2], c = cos[p][j],
+ * s = sin[p][j]:
+ *     v[j]                = fmaf(-x2, s, x1 * c)
+ *     v[j + head_dim / 2] = fmaf( x1, s, x2 * c)          all fp32: one rounding of the product, one of the fma
+ * _bf16 widens x1 and x2 to fp32 (exact), does the same and rounds each result to bf16 once, to nearest even.  The rotation is linear:
+ * Q columns that carry vithip_qscale(head_dim) (bf16 fold engines) carry it afterwards.
+ * which: VITHIP_ROPE_QK rotates Q and K; VITHIP_ROPE_K rotates K alone (the pruned last layer, whose Q exists for the class rows only).
+ * Nothing else is written: the first `prefix` rows of every image (class token, registers), V, the columns >= 3D and, under
+ * VITHIP_ROPE_K, Q keep their bits.  Deterministic, independent of an image's place in the batch; a non-finite x1 or x2 reaches the
+ * two elements of its own pair alone.  Offsets are 64-bit.
+ * Requirements (anything else: hipErrorInvalidValue, nothing launched): qkv, cos, sin non-NULL; qkv aligned to 4 elements (16 bytes,
+ * _bf16: 8), cos and sin to 16 bytes; n_images, tokens, heads >= 1; 0 <= prefix < tokens; head_dim one the attention kernels take
+ * (vithip_qscale(head_dim) != 0: 64, or a multiple of 8 from 72 to 128); ld >= 3D and ld % 4 == 0; which one of the two above.
+ */
+#define VITHIP_ROPE_QK 0
+#define VITHIP_ROPE_K 1
+int vithip_rope_f32(vithip_stream_t stream, float *qkv, size_t ld, const float *cos_t, const float *sin_t, int n_images, int tokens,
+                    int prefix, int heads, int head_dim, int which);
+int vithip_rope_bf16(vithip_stream_t stream, unsigned short *qkv, size_t ld, const float *cos_t, const float *sin_t, int n_images,
+                     int tokens, int prefix, int heads, int head_dim, int which);
+
+/*
  * Fused scaled-dot-product attention, one workgroup per (image, head) (x blocks of 256 queries when chunked).
  * qkv: [n*T][3*D] rows = tokens, columns [Q | K | V], head h = columns 64h..64h+63 of each.
  * out: [n*T][D].  scores = q.k / sqrtf(64); row softmax with max subtraction; out = P.V.

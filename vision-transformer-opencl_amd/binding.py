@@ -927,6 +927,36 @@ def swiglu(u, H: int, in_place: bool = False, ldu: Optional[int] = None, ldh: Op
     return dh.window()
 
 
+ROPE_WHICH = {"qk": 0, "k": 1}  # VITHIP_ROPE_QK, VITHIP_ROPE_K
+
+
+def rope_raw(qkv_ptr, ld: int, cos_ptr, sin_ptr, n_images: int, tokens: int, prefix: int, heads: int, head_dim: int, which: int,
+             bf16: bool = False) -> int:
+    """vithip_rope_f32 / vithip_rope_bf16 on caller-owned device addresses; returns the HIP status (no exception)."""
+    fn = lib().vithip_rope_bf16 if bf16 else lib().vithip_rope_f32
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p] + [C.c_int] * 6
+    return int(fn(None, qkv_ptr, ld, cos_ptr, sin_ptr, n_images, tokens, prefix, heads, head_dim, which))
+
+
+def rope(qkv, cos, sin, n_images: int, tokens: int, prefix: int, heads: int, head_dim: int, which="qk", ld: Optional[int] = None,
+         frames=None, out: Optional[dict] = None) -> np.ndarray:
+    """vithip_rope_f32 (qkv float32) or vithip_rope_bf16 (qkv uint16 = bf16 bits): qkv [n_images * tokens][3 * heads * head_dim],
+    rotated in place on the device by the fp32 tables cos / sin [tokens - prefix][head_dim / 2]; returns the rows after the launch.
+    which: "qk" | "k".  ld, frames, out: as for gemm(); the frame of the rows is "qkv"."""
+    qkv = np.ascontiguousarray(qkv)
+    bf16 = qkv.dtype == np.uint16
+    if not bf16:
+        qkv = _as_f32(qkv)
+    assert qkv.shape == (n_images * tokens, 3 * heads * head_dim), qkv.shape
+    F = frames or _Plain
+    dq = F.out_frame(qkv.shape[0], qkv.shape[1], ld, qkv.dtype, preload=qkv)
+    dc, ds = F.framed(_as_f32(cos).reshape(1, -1)), F.framed(_as_f32(sin).reshape(1, -1))
+    _note(out, qkv=dq)
+    hip_check(rope_raw(dq.ptr, dq.ld, dc.ptr, ds.ptr, n_images, tokens, prefix, heads, head_dim, ROPE_WHICH.get(which, which), bf16),
+              "vithip_rope_bf16" if bf16 else "vithip_rope_f32")
+    return dq.window()
+
+
 def tap_block(images: int, tokens: int, dim: int, layout) -> tuple:
     """Shape of one image's block of vithip_tap_f32 for `layout` ("cls" | "tokens" | "patches" | "map" or a VITHIP_TAP_* integer)."""
     k = TAP_KINDS[layout] if isinstance(layout, str) else int(layout)
@@ -2035,6 +2065,19 @@ class Engine:
         L.vit_engine_get_layernorm_eps.argtypes = [C.c_void_p]
         L.vit_engine_get_layernorm_eps.restype = C.c_double
         return float(L.vit_engine_get_layernorm_eps(self._h))
+
+    def set_rope(self, theta: float) -> None:
+        """vit_engine_set_rope: DINOv3's axial rotary embedding on the patch rows of Q and K in every layer; theta > 0 turns it on
+        (DINOv3: 100), 0 off.  It persists across weight installs."""
+        L = lib()
+        L.vit_engine_set_rope.argtypes = [C.c_void_p, C.c_double]
+        self._check(L.vit_engine_set_rope(self._h, float(theta)), "vit_engine_set_rope")
+
+    def get_rope(self) -> float:
+        L = lib()
+        L.vit_engine_get_rope.argtypes = [C.c_void_p]
+        L.vit_engine_get_rope.restype = C.c_double
+        return float(L.vit_engine_get_rope(self._h))
 
     def set_pre_norm(self, gamma, beta) -> None:
         """vit_engine_set_pre_norm: a LayerNorm in front of layer 0 (CLIP's ln_pre), gamma / beta [embed_dim]; None, None removes it.

@@ -151,6 +151,8 @@ struct vit_engine {
     int resize_filter;           /* VIT_RESIZE_*: the filter of the _images calls (vit_engine_set_resize_filter) */
     double ln_eps;               /* the epsilon of every LayerNorm the engine runs (vit_engine_set_layernorm_eps): architecture, kept across installs */
     float *pre_g, *pre_b;        /* the LayerNorm in front of layer 0 (vit_engine_set_pre_norm), the engine's own allocation; NULL: none */
+    double rope_theta;           /* rotary position embedding on Q and K (vit_engine_set_rope): architecture, kept across installs; 0: none */
+    float *rope_cos, *rope_sin;  /* its tables [patches][head_dim / 2], one allocation of the engine's own; NULL: none */
 
     /* workspace for max_batch images */
     float *x, *y, *qkv, *hbuf, *z, *logits;
@@ -479,6 +481,7 @@ void vit_engine_destroy(vit_engine *e) {
     release_dense_head(&e->dense);
     release_map_head(&e->map);
     vithip_free(e->pre_g); /* one allocation: gamma, beta behind it */
+    vithip_free(e->rope_cos); /* one allocation: cos, sin behind it */
     for (int j = 0; j < VIT_MAX_LANES; ++j) vithip_gemm_f32_workspace_destroy(e->gemm_ws[j]);
     if (e->copy_stream) { vithip_stream_sync(e->copy_stream); vithip_stream_destroy(e->copy_stream); }
     if (e->ev_in_stage) vithip_event_destroy(e->ev_in_stage);
@@ -539,6 +542,61 @@ int vit_engine_set_layernorm_eps(vit_engine *e, double eps) {
 }
 
 double vit_engine_get_layernorm_eps(const vit_engine *e) { return e ? e->ln_eps : 0.0; }
+
+/* The tables of DINOv3's axial rotary embedding for the engine's own grid and head_dim, [patches][head_dim / 2] each (cos first):
+ * patch (r, c) of a g x g grid has the coordinates y = 2 (r + 0.5) / g - 1 and x likewise, and the angles 2 pi y f_i for i < hd / 4,
+ * then 2 pi x f_i, f_i = theta^(-4 i / hd).  All in double, each entry rounded once to fp32. */
+static float *rope_tables(const vit_engine *e, double theta) {
+    const int g = e->cfg.img_size / VIT_PATCH_SIZE(&e->cfg), hd = e->cfg.embed_dim / e->cfg.num_heads, half = hd / 2, quarter = hd / 4;
+    const size_t n = (size_t)e->patches * half;
+    const double two_pi = 6.283185307179586476925286766559;
+    float *t = (float *)malloc(2 * n * sizeof(float));
+    if (!t) return NULL;
+    for (int p = 0; p < e->patches; ++p) {
+        const double yx[2] = {2.0 * (p / g + 0.5) / g - 1.0, 2.0 * (p % g + 0.5) / g - 1.0};
+        for (int j = 0; j < half; ++j) {
+            const double a = two_pi * yx[j / quarter] * pow(theta, -4.0 * (j % quarter) / hd);
+            t[(size_t)p * half + j] = (float)cos(a);
+            t[n + (size_t)p * half + j] = (float)sin(a);
+        }
+    }
+    return t;
+}
+
+int vit_engine_set_rope(vit_engine *e, double theta) {
+    if (!e) return VIT_ERR_ARG;
+    if (!(theta >= 0.0) || !isfinite(theta)) return fail(e, VIT_ERR_ARG, "set_rope: theta = %g must be finite and >= 0 (0 turns it off)", theta);
+    HIP_TRY(e, vithip_set_device(e->opt.device));
+    float *dev = NULL;
+    if (theta > 0.0) { /* the new tables first, whole; only then the old ones go */
+        const size_t bytes = 2 * (size_t)e->patches * (size_t)(e->cfg.embed_dim / e->cfg.num_heads / 2) * sizeof(float);
+        float *host = rope_tables(e, theta);
+        if (!host) return fail(e, VIT_ERR_NOMEM, "set_rope: out of host memory; the previous setting stays");
+        int hrc = vithip_malloc((void **)&dev, bytes);
+        if (hrc) {
+            free(host);
+            return fail(e, VIT_ERR_NOMEM, "set_rope: no memory for %zu bytes of tables (HIP error %d: %s); the previous setting stays", bytes, hrc,
+                        vithip_error_string(hrc));
+        }
+        hrc = vithip_memcpy_h2d(dev, host, bytes, e->stream);
+        if (!hrc) hrc = vithip_device_sync(); /* the upload, and every forward that still reads the old tables, on whatever stream */
+        free(host);
+        if (hrc) {
+            vithip_free(dev);
+            return fail(e, VIT_ERR_HIP, "set_rope: HIP error %d (%s) uploading; the previous setting stays", hrc, vithip_error_string(hrc));
+        }
+    } else {
+        HIP_TRY(e, vithip_device_sync());
+    }
+    drop_graph(e); /* a captured forward holds the old launch list */
+    vithip_free(e->rope_cos);
+    e->rope_cos = dev;
+    e->rope_sin = dev ? dev + (size_t)e->patches * (size_t)(e->cfg.embed_dim / e->cfg.num_heads / 2) : NULL; /* P * hd/2 floats: 16-byte aligned */
+    e->rope_theta = theta;
+    return VIT_OK;
+}
+
+double vit_engine_get_rope(const vit_engine *e) { return e ? e->rope_theta : 0.0; }
 
 /* Nothing may be in flight (the callers have synchronised). */
 static void release_pre_norm(vit_engine *e) {
@@ -1135,6 +1193,15 @@ static int encoder_layer(chunk_ctx *c, int l) {
         }
         RUN(gemm(e, ln->s, &g, NULL));
     }
+    if (e->rope_cos) /* rotary embedding (vit_engine_set_rope): Q and K of the patch rows, in place; pruned: K alone, Q holds class rows only */
+        for (int j = 0; j < c->L; ++j) {
+            const vit_lane *ln = &c->lane[j];
+            const int which = pruned ? VITHIP_ROPE_K : VITHIP_ROPE_QK;
+            HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_ATTN));
+            if (bf16) HIP_TRY(e, vithip_rope_bf16(ln->s, ln->qkv, (size_t)3 * D, e->rope_cos, e->rope_sin, ln->n, T, e->prefix, heads, D / heads, which));
+            else HIP_TRY(e, vithip_rope_f32(ln->s, ln->qkv, (size_t)3 * D, e->rope_cos, e->rope_sin, ln->n, T, e->prefix, heads, D / heads, which));
+            HIP_TRY(e, stage_end(e, ln->s));
+        }
     if (c->qkv_only && !feeds_next) return VIT_OK;
     for (int j = 0; j < c->L; ++j) { /* scores, softmax, P.V (ViT_seq.c:156-215) -> y; pruned: for the class rows */
         const vit_lane *ln = &c->lane[j];

@@ -138,6 +138,10 @@ CLIP_H14 = ModelConfig(patch_size=14, num_classes=1024, embed_dim=1280, depth=32
 CLIP_BIGG14 = ModelConfig(patch_size=14, num_classes=1280, embed_dim=1664, depth=48, num_heads=16, hidden_dim=8192)
 # DINOv2 ViT-B/14 with registers (dinov2_vitb14_reg): four register tokens behind the class token, T = 1 + 4 + 256
 DINOV2_B14_REG4 = ModelConfig(img_size=224, patch_size=14, embed_dim=768, depth=12, num_heads=12, hidden_dim=3072, num_register_tokens=4)
+# DINOv3 ViT-B/16 and ViT-L/16: patch 16, four register tokens, no learned position embedding (weight 3 is zeros); the engine rotates Q
+# and K instead (Engine.set_rope(100)) at LayerNorm epsilon 1e-5
+DINOV3_B16 = ModelConfig(img_size=224, patch_size=16, embed_dim=768, depth=12, num_heads=12, hidden_dim=3072, num_register_tokens=4)
+DINOV3_L16 = ModelConfig(img_size=224, patch_size=16, embed_dim=1024, depth=24, num_heads=16, hidden_dim=4096, num_register_tokens=4)
 # reduced models for fast live-oracle parity (head_dim stays 64 as in ViT-B/L)
 VIT_TINY = ModelConfig(img_size=32, num_classes=10, embed_dim=128, depth=2, num_heads=2, hidden_dim=256)
 VIT_SMALL = ModelConfig(img_size=64, num_classes=100, embed_dim=192, depth=3, num_heads=3, hidden_dim=768)
