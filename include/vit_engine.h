@@ -685,6 +685,33 @@ int vit_engine_set_rope(vit_engine *e, double theta);
 double vit_engine_get_rope(const vit_engine *e);
 
 /*
+ * BEiT, BEiT v2, data2vec-vision, DPT-BEiT, timm's vit_relpos_*: a per-head additive term on the attention scores,
+ * softmax(q.k / sqrt(hd) + b[head][query][key]).  vit_engine_set_attention_bias(e, layer, bias): bias is a host array
+ * [num_heads][T][T] in natural-log units, T = the engine's token count (prefix + patches); layer 0 .. depth-1 sets that layer's,
+ * layer -1 sets ONE bias that every layer reads (BEiT's use_shared_relative_position_bias; one device copy) and removes every per-layer
+ * one; a per-layer call on a layer that reads the shared one gives that layer its own.  bias == NULL removes (layer -1: from every
+ * layer).  The engine keeps device copies with rows padded to a multiple of four floats.  A layer with a bias runs
+ * vithip_attention_f32_bias / _bf16io_bias (vit_hip_kernels.h) in place of its attention launch -- pruned or not, folded or not, on
+ * every lane, the rotary embedding in front if it is on; an fp32 engine with fp32_split on runs ITS BIASED LAYERS ON fp32 MFMA.
+ * Layers without a bias, and engines that never call this, issue the launches they always issued.  -inf entries mask keys; a row
+ * without a finite entry is the caller's error.  The class-attention calls read a kernel that takes no bias: on an engine whose LAST
+ * layer has a bias they return VIT_ERR_STATE; every other output kind works.  Architecture, like the rotary embedding: it PERSISTS
+ * across weight installs, and the copy calls do not carry it.  Synchronises the device and drops a captured graph.  VIT_ERR_ARG,
+ * nothing changed: layer outside -1 .. depth-1.  The new copy is made before an old one is freed: on VIT_ERR_NOMEM / VIT_ERR_HIP
+ * the previous setting stays in force.  vit_engine_has_attention_bias: 1 when the layer (0 .. depth-1) has one, 0 otherwise; layer -1:
+ * 1 when a shared one is in force.
+ *
+ * vit_rel_pos_bias_expand (host only, no engine): BEiT's relative_position_bias_table [(2g-1)^2 + 3][heads] expanded through BEiT's
+ * relative_position_index (transformers' BeitRelativePositionBias) into out [heads][1 + g*g][1 + g*g]: patches p = (r, c) and
+ * p' = (r', c') of the g x g grid read table row (r - r' + g - 1) (2g - 1) + (c - c' + g - 1); class query to any patch reads row
+ * (2g-1)^2, any patch to the class key row (2g-1)^2 + 1, class to class row (2g-1)^2 + 2.  VIT_ERR_ARG: a NULL pointer, grid < 1,
+ * heads < 1.  Not done: interpolating a table to another grid.
+ */
+int vit_engine_set_attention_bias(vit_engine *e, int layer, const float *bias);
+int vit_engine_has_attention_bias(const vit_engine *e, int layer);
+int vit_rel_pos_bias_expand(const float *table, int grid, int heads, float *out);
+
+/*
  * The fp32 GEMMs' helper-piece hand-over (csrc/vit_gemm_persistent.hip) since the last call, summed over the lanes: tiles whose
  * first K-steps came from a helper workgroup / tiles whose owner found no piece when it looked and computed all of it.  The
  * second number is lost time, never a wrong result (nothing in the hand-over waits or gives up).  Synchronises the device.

@@ -309,6 +309,26 @@ int vithip_attention_f32_hd(vithip_stream_t stream, const float *qkv, float *out
                             int q_rows);
 int vithip_attention_bf16io_hd(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out, int n_images, int tokens,
                                int heads, int head_dim, int q_rows, int q_scaled);
+/*
+ * Attention with an additive bias on the scores (csrc/vit_attention_bias.hip): softmax(q.k / sqrtf(head_dim) + bias[head][query][key]),
+ * out = P.V -- BEiT's relative position bias, and with -inf entries a key mask.  qkv, out, head_dim, q_rows and q_scaled are the ones
+ * of vithip_attention_f32_hd / _bf16io_hd, for every accepted head_dim (64 included: one kernel for all of them), any tokens >= 1 and
+ * any q_rows, heads <= 65535.  bias: fp32 [heads][tokens][ld_bias] in natural-log units, shared by every image; element (h, i, j) is
+ * added to the scaled score of query i and key j of head h before the row maximum is taken.  ld_bias >= tokens, ld_bias % 4 == 0, the
+ * pointer 16-byte aligned.  Nothing outside [heads][tokens][ld_bias] is read; the columns [tokens, ld_bias) of a row may be read and
+ * reach no result, whatever bits they hold.  An entry of -inf gives its key the weight 0, exactly.  A ROW WITH NO FINITE ENTRY IS THE
+ * CALLER'S ERROR (its outputs are NaN); +inf and NaN entries have no defined meaning.
+ *   q_scaled = 1 (bf16): the Q columns hold vithip_qscale(head_dim) * q; p = exp2(q.k + bias * log2(e) - max).
+ * fp32: fp32 MFMA for both products; bf16: the arithmetic of vithip_attention_bf16io_hd's own kernel, the bias added in fp32.
+ * The guarantees of the _hd entries: no atomics; an image's bits depend on neither the batch size nor its place in the batch; a
+ * workgroup reads one image's rows only; nothing is written outside rows 0..q_rows-1 of an image.
+ * hipErrorInvalidValue, nothing launched: what the _hd entries refuse, a NULL or not 16-byte aligned bias, ld_bias < tokens,
+ * ld_bias % 4 != 0.
+ */
+int vithip_attention_f32_bias(vithip_stream_t stream, const float *qkv, float *out, const float *bias, size_t ld_bias, int n_images,
+                              int tokens, int heads, int head_dim, int q_rows);
+int vithip_attention_bf16io_bias(vithip_stream_t stream, const unsigned short *qkv, unsigned short *out, const float *bias,
+                                 size_t ld_bias, int n_images, int tokens, int heads, int head_dim, int q_rows, int q_scaled);
 /* vithip_attention_f32_hd's layout, arguments and guarantees at head_dim 64 (any other head_dim: hipErrorInvalidValue), any tokens >= 1
  * and any q_rows, heads <= 65535, with both products on the bf16 matrix pipe: every fp32 operand (Q, K, V and the softmax weights) is
  * split into three bf16 pieces and each fp32 product becomes the six piece products of rank <= 2, added small terms first (the

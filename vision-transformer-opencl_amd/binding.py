@@ -453,6 +453,9 @@ def lib() -> C.CDLL:
             L.vithip_attention_bf16io_hd.argtypes = pv + [C.c_int] * 6
             L.vithip_cls_attention_f32_hd.argtypes = cls + [C.c_int] * 5
             L.vithip_cls_attention_bf16_hd.argtypes = cls + [C.c_int] * 6
+        if hasattr(L, "vithip_attention_f32_bias"):  # an earlier build (see above) has no bias on the scores
+            L.vithip_attention_f32_bias.argtypes = pv + [C.c_void_p, C.c_size_t] + [C.c_int] * 5
+            L.vithip_attention_bf16io_bias.argtypes = pv + [C.c_void_p, C.c_size_t] + [C.c_int] * 6
         if hasattr(L, "vithip_attention_f32_split"):  # an earlier build (see above) has fp32 arithmetic only
             L.vithip_attention_f32_split.argtypes = pv + [C.c_int] * 5
         L.vithip_softmax_top1_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
@@ -1245,6 +1248,55 @@ def attention_bf16io_hd(qkv_bits, n_images: int, tokens: int, heads: int, head_d
     """vithip_attention_bf16io_hd: the same on bf16 bits (uint16); q_scaled: the Q columns hold qscale(head_dim) * q."""
     return _attention("vithip_attention_bf16io_hd", _bits(qkv_bits), n_images, tokens, heads, head_dim,
                       (head_dim, tokens if q_rows is None else q_rows, int(q_scaled)), fill, frames, out)
+
+
+def _attention_bias(name, qkv, bias, n_images, tokens, heads, head_dim, args, ld_bias, fill, bias_offset, null_bias, out):
+    """The biased P.V entry `name`(stream, qkv, out, bias, ld_bias, n_images, tokens, heads, *args).  bias [heads][tokens][width]
+    fp32, width >= tokens: its columns behind `tokens` travel as they are (pad columns); ld_bias: the leading dimension passed
+    (default: width); bias_offset: the array starts this many floats past a 16-byte boundary; null_bias: NULL is passed; out
+    receives the output's frame "out" before the launch; rows the call does not write keep `fill`."""
+    rows, D = n_images * tokens, heads * head_dim
+    qkv = qkv.reshape(rows, 3 * D)
+    bias = np.ascontiguousarray(bias, np.float32)
+    assert bias.ndim == 3 and bias.shape[:2] == (heads, tokens) and bias.shape[2] >= tokens, bias.shape
+    dq, do = _Plain.framed(qkv), _Plain.out_frame(rows, D, dtype=qkv.dtype, preload=np.full((rows, D), fill, qkv.dtype))
+    db = _Plain.framed(bias.reshape(heads * tokens, -1), offset=bias_offset)
+    _note(out, out=do)
+    hip_check(getattr(lib(), name)(None, dq.ptr, do.ptr, None if null_bias else db.ptr, bias.shape[2] if ld_bias is None else ld_bias,
+                                   n_images, tokens, heads, *args), name)
+    return do.window()
+
+
+def attention_bias(qkv, bias, n_images: int, tokens: int, heads: int, head_dim: int, q_rows: Optional[int] = None,
+                   ld_bias: Optional[int] = None, fill: float = 0.0, bias_offset: int = 0, null_bias: bool = False,
+                   out: Optional[dict] = None) -> np.ndarray:
+    """vithip_attention_f32_bias: attention_hd() with bias[h][i][j] (natural-log units, one array for every image) added to the
+    scaled score of query i and key j of head h; -inf masks a key.  The other arguments: _attention_bias."""
+    return _attention_bias("vithip_attention_f32_bias", _as_f32(qkv), bias, n_images, tokens, heads, head_dim,
+                           (head_dim, tokens if q_rows is None else q_rows), ld_bias, fill, bias_offset, null_bias, out)
+
+
+def attention_bf16io_bias(qkv_bits, bias, n_images: int, tokens: int, heads: int, head_dim: int, q_rows: Optional[int] = None,
+                          q_scaled: bool = False, ld_bias: Optional[int] = None, fill: int = 0, bias_offset: int = 0,
+                          null_bias: bool = False, out: Optional[dict] = None) -> np.ndarray:
+    """vithip_attention_bf16io_bias: the same on bf16 bits (uint16), the bias still fp32; q_scaled: the Q columns hold qscale(head_dim) * q."""
+    return _attention_bias("vithip_attention_bf16io_bias", _bits(qkv_bits), bias, n_images, tokens, heads, head_dim,
+                           (head_dim, tokens if q_rows is None else q_rows, int(q_scaled)), ld_bias, fill, bias_offset, null_bias, out)
+
+
+def rel_pos_bias(table, grid: int) -> np.ndarray:
+    """vit_rel_pos_bias_expand: BEiT's relative_position_bias_table [(2 grid - 1)^2 + 3][heads] -> the bias [heads][T][T],
+    T = 1 + grid^2, through BEiT's relative_position_index (host only)."""
+    table = _as_f32(table)
+    assert table.ndim == 2 and table.shape[0] == (2 * grid - 1) ** 2 + 3, table.shape
+    heads, T = table.shape[1], 1 + grid * grid
+    out = np.empty((heads, T, T), np.float32)
+    fn = lib().vit_rel_pos_bias_expand
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    rc = fn(table.ctypes.data, grid, heads, out.ctypes.data)
+    if rc != 0:
+        raise VitError(f"vit_rel_pos_bias_expand failed ({rc})")
+    return out
 
 
 def _cls_attention(name, qkv, n_images, tokens, heads, head_dim, head_mean, q_scaled, ld_out, fill):
@@ -2078,6 +2130,25 @@ class Engine:
         L.vit_engine_get_rope.argtypes = [C.c_void_p]
         L.vit_engine_get_rope.restype = C.c_double
         return float(L.vit_engine_get_rope(self._h))
+
+    def set_attention_bias(self, layer: int, bias) -> None:
+        """vit_engine_set_attention_bias: an additive bias [heads][T][T] (natural-log units; -inf masks a key) on the attention scores
+        of `layer` (0 .. depth - 1), or with layer -1 one array that every layer shares; None removes it.  It persists across weight
+        installs.  BEiT: rel_pos_bias(table, grid) per layer."""
+        L = lib()
+        L.vit_engine_set_attention_bias.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        b = None
+        if bias is not None:
+            b = _as_f32(bias)
+            T = self.cfg.tokens
+            if b.shape != (self.cfg.num_heads, T, T):
+                raise VitError(f"set_attention_bias: bias {b.shape} is not ({self.cfg.num_heads}, {T}, {T})")
+        self._check(L.vit_engine_set_attention_bias(self._h, int(layer), None if b is None else b.ctypes.data), "vit_engine_set_attention_bias")
+
+    def has_attention_bias(self, layer: int) -> bool:
+        L = lib()
+        L.vit_engine_has_attention_bias.argtypes = [C.c_void_p, C.c_int]
+        return bool(L.vit_engine_has_attention_bias(self._h, int(layer)))
 
     def set_pre_norm(self, gamma, beta) -> None:
         """vit_engine_set_pre_norm: a LayerNorm in front of layer 0 (CLIP's ln_pre), gamma / beta [embed_dim]; None, None removes it.

@@ -153,6 +153,10 @@ struct vit_engine {
     float *pre_g, *pre_b;        /* the LayerNorm in front of layer 0 (vit_engine_set_pre_norm), the engine's own allocation; NULL: none */
     double rope_theta;           /* rotary position embedding on Q and K (vit_engine_set_rope): architecture, kept across installs; 0: none */
     float *rope_cos, *rope_sin;  /* its tables [patches][head_dim / 2], one allocation of the engine's own; NULL: none */
+    /* the additive bias of the attention scores (vit_engine_set_attention_bias): architecture, kept across installs.  Device arrays
+     * [heads][tokens][bias_ld] of the engine's own, bias_ld = tokens rounded up to four floats (zeros behind a row's last key) */
+    float **attn_bias;           /* [depth]: what layer l reads -- its own array, attn_bias_shared, or NULL: none */
+    float *attn_bias_shared;     /* the one array of a layer -1 call; NULL: none */
 
     /* workspace for max_batch images */
     float *x, *y, *qkv, *hbuf, *z, *logits;
@@ -439,9 +443,10 @@ int vit_engine_create(vit_engine **out, const vit_config *cfg, const vit_engine_
     e->w = (float **)calloc((size_t)e->n_weights, sizeof(float *));
     e->w16 = (unsigned short **)calloc((size_t)e->n_weights, sizeof(unsigned short *));
     e->layer = (vit_layer_ops *)calloc((size_t)e->cfg.depth, sizeof(vit_layer_ops));
+    e->attn_bias = (float **)calloc((size_t)e->cfg.depth, sizeof(float *));
     e->img_recs = (vithip_image_u8 *)calloc(B, sizeof(vithip_image_u8));
     e->img_off = (size_t *)calloc(B + 1, sizeof(size_t));
-    if (!e->w || !e->w16 || !e->layer || !e->img_recs || !e->img_off) return fail(e, VIT_ERR_NOMEM, "out of host memory");
+    if (!e->w || !e->w16 || !e->layer || !e->attn_bias || !e->img_recs || !e->img_off) return fail(e, VIT_ERR_NOMEM, "out of host memory");
     if (e->opt.dtype != VIT_DTYPE_F32 && e->opt.dtype != VIT_DTYPE_BF16)
         return fail(e, VIT_ERR_ARG, "dtype must be VIT_DTYPE_F32 or VIT_DTYPE_BF16");
     if (e->opt.dtype == VIT_DTYPE_BF16 && (e->cfg.embed_dim % 64 || VIT_HIDDEN_DIM(&e->cfg) % 64))
@@ -482,6 +487,10 @@ void vit_engine_destroy(vit_engine *e) {
     release_map_head(&e->map);
     vithip_free(e->pre_g); /* one allocation: gamma, beta behind it */
     vithip_free(e->rope_cos); /* one allocation: cos, sin behind it */
+    for (int l = 0; e->attn_bias && l < e->cfg.depth; ++l)
+        if (e->attn_bias[l] != e->attn_bias_shared) vithip_free(e->attn_bias[l]);
+    vithip_free(e->attn_bias_shared);
+    free(e->attn_bias);
     for (int j = 0; j < VIT_MAX_LANES; ++j) vithip_gemm_f32_workspace_destroy(e->gemm_ws[j]);
     if (e->copy_stream) { vithip_stream_sync(e->copy_stream); vithip_stream_destroy(e->copy_stream); }
     if (e->ev_in_stage) vithip_event_destroy(e->ev_in_stage);
@@ -597,6 +606,64 @@ int vit_engine_set_rope(vit_engine *e, double theta) {
 }
 
 double vit_engine_get_rope(const vit_engine *e) { return e ? e->rope_theta : 0.0; }
+
+static size_t attn_bias_ld(const vit_engine *e) { return ((size_t)e->tokens + 3) / 4 * 4; }
+
+int vit_engine_set_attention_bias(vit_engine *e, int layer, const float *bias) {
+    if (!e) return VIT_ERR_ARG;
+    if (layer < -1 || layer >= e->cfg.depth) return fail(e, VIT_ERR_ARG, "set_attention_bias: layer %d must be -1 (shared) or 0..%d", layer, e->cfg.depth - 1);
+    HIP_TRY(e, vithip_set_device(e->opt.device));
+    float *dev = NULL;
+    if (bias) { /* the new copy first, whole and padded; only then an old one goes */
+        const size_t T = (size_t)e->tokens, ldb = attn_bias_ld(e), rows = (size_t)e->cfg.num_heads * T, bytes = rows * ldb * sizeof(float);
+        float *host = (float *)calloc(rows * ldb, sizeof(float));
+        if (!host) return fail(e, VIT_ERR_NOMEM, "set_attention_bias: out of host memory; the previous setting stays");
+        for (size_t r = 0; r < rows; ++r) memcpy(host + r * ldb, bias + r * T, T * sizeof(float));
+        int hrc = vithip_malloc((void **)&dev, bytes);
+        if (hrc) {
+            free(host);
+            return fail(e, VIT_ERR_NOMEM, "set_attention_bias: no memory for %zu bytes (HIP error %d: %s); the previous setting stays", bytes, hrc,
+                        vithip_error_string(hrc));
+        }
+        hrc = vithip_memcpy_h2d(dev, host, bytes, e->stream);
+        if (!hrc) hrc = vithip_device_sync(); /* the upload, and every forward that still reads an old array, on whatever stream */
+        free(host);
+        if (hrc) {
+            vithip_free(dev);
+            return fail(e, VIT_ERR_HIP, "set_attention_bias: HIP error %d (%s) uploading; the previous setting stays", hrc, vithip_error_string(hrc));
+        }
+    } else {
+        HIP_TRY(e, vithip_device_sync());
+    }
+    drop_graph(e); /* a captured forward holds the old launch list */
+    for (int l = layer < 0 ? 0 : layer; l < (layer < 0 ? e->cfg.depth : layer + 1); ++l) {
+        if (e->attn_bias[l] != e->attn_bias_shared) vithip_free(e->attn_bias[l]);
+        e->attn_bias[l] = dev;
+    }
+    if (layer < 0) {
+        vithip_free(e->attn_bias_shared);
+        e->attn_bias_shared = dev;
+    }
+    return VIT_OK;
+}
+
+int vit_engine_has_attention_bias(const vit_engine *e, int layer) {
+    if (!e || layer < -1 || layer >= e->cfg.depth) return 0;
+    return layer < 0 ? e->attn_bias_shared != NULL : e->attn_bias[layer] != NULL;
+}
+
+int vit_rel_pos_bias_expand(const float *table, int grid, int heads, float *out) {
+    if (!table || !out || grid < 1 || heads < 1) return VIT_ERR_ARG;
+    const int g = grid, w = 2 * g - 1, P = g * g, T = P + 1, rel = w * w; /* rows rel, rel + 1, rel + 2: class to patch, patch to class, class to class */
+    for (int h = 0; h < heads; ++h)
+        for (int i = 0; i < T; ++i)
+            for (int j = 0; j < T; ++j) {
+                int idx = !i && !j ? rel + 2 : !j ? rel + 1 : !i ? rel : 0;
+                if (i && j) idx = ((i - 1) / g - (j - 1) / g + g - 1) * w + ((i - 1) % g - (j - 1) % g + g - 1);
+                out[((size_t)h * T + i) * T + j] = table[(size_t)idx * heads + h];
+            }
+    return VIT_OK;
+}
 
 /* Nothing may be in flight (the callers have synchronised). */
 static void release_pre_norm(vit_engine *e) {
@@ -1208,7 +1275,13 @@ static int encoder_layer(chunk_ctx *c, int l) {
         HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_ATTN));
         /* head_dim 64: the entries these generalise (_f32 / _f32_rows, _bf16io / _rows / _qscaled), their launches and their bits */
         /* fp32 with the split on (fp32_split >= 0), head_dim 64: both products on the bf16 matrix pipe, like the GEMMs around them */
-        if (!bf16 && e->split && D / heads == 64)
+        /* a layer with a bias on its scores (vit_engine_set_attention_bias): the one kernel that takes it, for every head_dim; fp32 MFMA
+         * for fp32 whether the split is on or not */
+        if (e->attn_bias[l] && !bf16)
+            HIP_TRY(e, vithip_attention_f32_bias(ln->s, ln->qkv, ln->y, e->attn_bias[l], attn_bias_ld(e), ln->n, T, heads, D / heads, pruned ? 1 : T));
+        else if (e->attn_bias[l])
+            HIP_TRY(e, vithip_attention_bf16io_bias(ln->s, ln->qkv, ln->y, e->attn_bias[l], attn_bias_ld(e), ln->n, T, heads, D / heads, pruned ? 1 : T, fold));
+        else if (!bf16 && e->split && D / heads == 64)
             HIP_TRY(e, vithip_attention_f32_split(ln->s, ln->qkv, ln->y, ln->n, T, heads, 64, pruned ? 1 : T));
         else if (!bf16) HIP_TRY(e, vithip_attention_f32_hd(ln->s, ln->qkv, ln->y, ln->n, T, heads, D / heads, pruned ? 1 : T));
         else HIP_TRY(e, vithip_attention_bf16io_hd(ln->s, ln->qkv, ln->y, ln->n, T, heads, D / heads, pruned ? 1 : T, fold));
@@ -1715,6 +1788,8 @@ static int make_output(vit_engine *e, const char *who, int kind, const void *spe
     int arg[2];
     const char *fault = output_fault(e, kind, spec, out, arg);
     if (fault) return fail(e, fault == NO_DENSE_HEAD ? VIT_ERR_STATE : VIT_ERR_ARG, fault, who, arg[0], arg[1]);
+    if (kind == VIT_OUT_ATTENTION && e->attn_bias[e->cfg.depth - 1]) /* the class-row kernel takes no bias: a wrong row is not an answer */
+        return fail(e, VIT_ERR_STATE, "%s: the last layer has an attention bias (vit_engine_set_attention_bias), which the class-attention kernel does not take", who);
     out->dst = dst; out->label = label; out->prob = prob;
     return VIT_OK;
 }

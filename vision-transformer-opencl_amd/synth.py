@@ -142,6 +142,11 @@ DINOV2_B14_REG4 = ModelConfig(img_size=224, patch_size=14, embed_dim=768, depth=
 # and K instead (Engine.set_rope(100)) at LayerNorm epsilon 1e-5
 DINOV3_B16 = ModelConfig(img_size=224, patch_size=16, embed_dim=768, depth=12, num_heads=12, hidden_dim=3072, num_register_tokens=4)
 DINOV3_L16 = ModelConfig(img_size=224, patch_size=16, embed_dim=1024, depth=24, num_heads=16, hidden_dim=4096, num_register_tokens=4)
+# BEiT / BEiT v2 / data2vec-vision base and large: plain B/16 and L/16 geometry; no learned position embedding (weight 3 is zeros), a
+# relative position bias on every layer's scores instead (Engine.set_attention_bias(l, binding.rel_pos_bias(table_l, 14))), LayerScale
+# folded, mean pooling with fc_norm through Engine.set_head
+BEIT_B16 = ModelConfig()
+BEIT_L16 = ModelConfig(embed_dim=1024, depth=24, num_heads=16, hidden_dim=4096)
 # reduced models for fast live-oracle parity (head_dim stays 64 as in ViT-B/L)
 VIT_TINY = ModelConfig(img_size=32, num_classes=10, embed_dim=128, depth=2, num_heads=2, hidden_dim=256)
 VIT_SMALL = ModelConfig(img_size=64, num_classes=100, embed_dim=192, depth=3, num_heads=3, hidden_dim=768)
