@@ -69,6 +69,13 @@ typedef struct {
 } vit_engine_options;
 
 enum { VIT_DTYPE_F32 = 0, VIT_DTYPE_BF16 = 1 };
+/* mxfp8, a flag on vit_engine_options.dtype (the struct keeps its layout): dtype = VIT_DTYPE_BF16 | VIT_DTYPE_MXFP8.
+ * bf16 engines: QKV, out_proj, fc1 and fc2 of every layer as MXFP8; embedding, attention, heads and every row kernel unchanged
+ * (vit_hip_kernels.h, "MXFP8": weights quantised once per install from the fp32 tensors, activations block by block inside the GEMM,
+ * which reads them as the bf16 rows every producer writes).  Off without the flag.  VIT_ERR_ARG on an fp32 engine, with embed_dim or
+ * hidden_dim no multiple of 64, and with ln_fold = 1: the MXFP8 GEMM has no fold form, ln_fold = 0 (auto) means off here -- a
+ * LayerNorm kernel per LayerNorm, as ln_fold = -1.  The engine then reports dtype VIT_DTYPE_BF16: what its other kernels run. */
+enum { VIT_DTYPE_MXFP8 = 0x100 };
 
 /* Per-stage device time of the profiled forwards (ms, summed) and launch counts. */
 enum {

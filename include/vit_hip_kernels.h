@@ -235,6 +235,39 @@ typedef struct {
  * Non-finite values in one row of A reach only that row of C, x16 and row_partials -- and do reach it: a NaN accumulator comes out
  * of BF16_GELU as NaN, an infinite one as NaN or Inf -- every other output has the bits of the same launch on clean data. */
 int vithip_gemm_bf16(vithip_stream_t stream, const vithip_gemm_bf16_args *args);
+/* ---- MXFP8: the same GEMM on the scaled fp8 matrix instruction (v_mfma_scale_f32_32x32x64_f8f6f4; csrc/vit_gemm_mxfp8.hip) ----
+ * The format, for A and W alike (the OCP microscaling format MXFP8 with e4m3 elements):
+ *   - a block is 32 consecutive K elements of one row;
+ *   - its shared exponent is X = floor(log2(amax)) - 8, clamped to [-127, 127], stored as the e8m0 byte X + 127 (amax: the largest
+ *     magnitude of the block); a block with amax == 0 takes X = -127 and all-zero elements;
+ *   - an element is x * 2^-X, clamped to +-448, then rounded to nearest even to OCP e4m3 (no infinities; a zero keeps its sign).
+ *     amax * 2^-X lies in [256, 512), so values in (448, 512) saturate: the OCP rule.
+ * NaN or Inf in an operand is outside the contract: what such a block becomes is not defined.
+ * The weight image of W [N][K] (K % 64 == 0): blocks of (32 rows, 64 k) of VITHIP_MXFP8_BLOCK_BYTES, 32-row block major, K steps
+ * ascending inside one.  A block is 64 x 32 element bytes -- chunk l holds row l % 32, k 16 (l / 32) .. + 15 and then
+ * k 32 + 16 (l / 32) .. + 15 of the block: the eight operand registers of the matrix instruction's lane l, so a wave's fragment is one
+ * contiguous 2 KB run and a lane's 32 bytes are contiguous -- and behind them the 64 scale bytes: byte l is the e8m0 byte of row
+ * l % 32, k 32 (l / 32) .. + 31, the scale operand of lane l.  Rows are padded with zero blocks to a multiple of 128 (the GEMM's tile).
+ * vithip_mxfp8_image_bytes(N, K) = ceil(N / 128) * 4 * (K / 64) * VITHIP_MXFP8_BLOCK_BYTES (0 for bad arguments); the image of rows
+ * n .. of W (n % 32 == 0) starts vithip_mxfp8_image_row_offset(n, K) bytes into W's.  vithip_mxfp8_weights quantises from fp32
+ * W [N][ldw] (ldw % 4 == 0, 16-byte aligned) in plain integer arithmetic. */
+#define VITHIP_MXFP8_BLOCK_BYTES 2112
+size_t vithip_mxfp8_image_bytes(int N, int K);
+size_t vithip_mxfp8_image_row_offset(int n, int K);
+int vithip_mxfp8_weights(vithip_stream_t stream, const float *W, int ldw, int N, int K, void *image);
+typedef struct {
+    const unsigned short *A; int lda;   /* bf16 [M][lda], lda % 8 == 0, lda >= K (a row step or a wider row is fine); columns past K are never read */
+    const void *W;                      /* the image of W [N][K] (vithip_mxfp8_weights), or of its rows n .. at the row offset */
+    const float *bias;                  /* fp32 [N] */
+    const float *residual; int ldr;     /* fp32, VITHIP_BF16_EPI_F32_RESIDUAL only; may alias C */
+    void *C; int ldc;                   /* bf16 or, VITHIP_BF16_EPI_F32_RESIDUAL, fp32 */
+    int M, N, K;                        /* M >= 1, N % 8 == 0, K % 64 == 0 */
+    int epilogue;                       /* VITHIP_BF16_EPI_BF16, _BF16_GELU, _BF16_QGELU or _F32_RESIDUAL: as vithip_gemm_bf16 */
+} vithip_gemm_mxfp8_args;
+/* C = epilogue(q(A) . q(W)^T + bias): A's rows are quantised block by block on chip (they stay bf16 in memory), products and sums
+ * of a 64-deep K step inside the matrix instruction, fp32 accumulators across steps in ascending K.  The epilogues are those of
+ * vithip_gemm_bf16 -- the same functions of acc + bias.  No LayerNorm fold. */
+int vithip_gemm_mxfp8(vithip_stream_t stream, const vithip_gemm_mxfp8_args *args);
 /* ---- LayerNorm folding (bf16 forward): LN(x) . W^T + b = rstd * (x . (gamma*W)^T) - rstd * mean * colsum(gamma*W) + (b + W . beta),
  * so the normalised activations never exist in memory: the residual GEMM in front stores bf16(x) and row sums, the GEMM
  * behind multiplies the raw bf16 rows with the folded weight and rescales in its epilogue (ViT_seq.c:103-121 is the

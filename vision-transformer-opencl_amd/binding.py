@@ -51,6 +51,9 @@ class CImageData(C.Structure):  # Network.h:7-13
     _fields_ = [("n", C.c_int), ("c", C.c_int), ("h", C.c_int), ("w", C.c_int), ("data", f32p)]
 
 
+DTYPE_MXFP8 = 0x100  # VIT_DTYPE_MXFP8: a flag on COptions.dtype (Engine(..., dtype="bf16", mxfp8=1))
+
+
 class COptions(C.Structure):
     _fields_ = [("device", C.c_int), ("max_batch", C.c_int), ("profile", C.c_int), ("lanes", C.c_int),
                 ("dtype", C.c_int), ("prune_last_layer", C.c_int), ("use_graph", C.c_int), ("gemm_tile", C.c_int), ("ln_fold", C.c_int),
@@ -784,6 +787,58 @@ def gemm_bf16(A_bits, W_bits, bias, residual=None, epilogue=BF16_EPI_BF16, varia
     hip_check(L.vithip_gemm_bf16(None, C.byref(args)), "vithip_gemm_bf16")
     if ln_producer:
         return dC.window(), dX16.window(), dPart.window().reshape(strips, M, 2)
+    return dC.window()
+
+
+class CGemmMxfp8Args(C.Structure):  # vithip_gemm_mxfp8_args
+    _fields_ = [("A", C.c_void_p), ("lda", C.c_int), ("W", C.c_void_p), ("bias", C.c_void_p), ("residual", C.c_void_p), ("ldr", C.c_int),
+                ("C", C.c_void_p), ("ldc", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("epilogue", C.c_int)]
+
+
+def mxfp8_weights_device(dW, N: int, K: int, ldw: Optional[int] = None) -> "DeviceArray":
+    """vithip_mxfp8_weights: the MXFP8 image of the device matrix dW [N][ldw] (fp32), as a DeviceArray of bytes."""
+    L = lib()
+    L.vithip_mxfp8_image_bytes.restype = C.c_size_t
+    nbytes = int(L.vithip_mxfp8_image_bytes(N, K))
+    if nbytes == 0:
+        raise VitError(f"vithip_mxfp8_image_bytes({N}, {K}): bad shape")
+    out = DeviceArray((nbytes,), np.uint8)
+    L.vithip_mxfp8_weights.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    hip_check(L.vithip_mxfp8_weights(None, dW.ptr, K if ldw is None else ldw, N, K, out.ptr), "vithip_mxfp8_weights")
+    return out
+
+
+def mxfp8_weights(W) -> np.ndarray:
+    """The MXFP8 image of W [N][K] (fp32), copied back: uint8 [ceil(N / 128) * 4][K / 64][VITHIP_MXFP8_BLOCK_BYTES] -- per block
+    64 x 32 element bytes (chunk l: row l % 32, k 16 (l / 32) .. + 15 then k 32 + 16 (l / 32) .. + 15), then the 64 e8m0 scale bytes
+    (byte l: row l % 32, k 32 (l / 32) .. + 31)."""
+    W = _as_f32(W)
+    N, K = W.shape
+    return mxfp8_weights_device(DeviceArray.from_numpy(W), N, K).numpy().reshape((N + 127) // 128 * 4, K // 64, 2112)
+
+
+def gemm_mxfp8(A_bits, W, bias, residual=None, epilogue=BF16_EPI_BF16, lda: Optional[int] = None, ldr: Optional[int] = None,
+               ldc: Optional[int] = None, in_place: bool = False, K: Optional[int] = None, frames=None, out: Optional[dict] = None):
+    """vithip_gemm_mxfp8: A bf16 bit patterns [M][>= K] (K: the contraction length, default A's width; lda: its leading dimension), W
+    fp32 [N][K] (its image is made on the device by vithip_mxfp8_weights); returns bf16 bits (uint16) or fp32 for the residual
+    epilogue.  lda / ldr / ldc, in_place, frames, out: as for gemm(); the output frame is "C"."""
+    L = lib()
+    L.vithip_gemm_mxfp8.argtypes = [C.c_void_p, C.POINTER(CGemmMxfp8Args)]
+    W = _as_f32(W)
+    M, N = A_bits.shape[0], W.shape[0]
+    K = W.shape[1] if K is None else K
+    F = frames or _Plain
+    dA, db = F.framed(np.ascontiguousarray(A_bits, np.uint16), lda), F.framed(_as_f32(bias))
+    dImg = mxfp8_weights_device(DeviceArray.from_numpy(W), N, K)
+    out_f32 = epilogue == BF16_EPI_F32_RESIDUAL
+    if in_place:
+        dC = dR = F.out_frame(M, N, ldc, np.float32, preload=_as_f32(residual))
+    else:
+        dC = F.out_frame(M, N, ldc, np.float32 if out_f32 else np.uint16)
+        dR = F.framed(_as_f32(residual), ldr) if residual is not None else None
+    _note(out, C=dC)
+    args = CGemmMxfp8Args(dA.ptr, dA.ld, dImg.ptr, db.ptr, dR.ptr if dR else None, dR.ld if dR else N, dC.ptr, dC.ld, M, N, K, epilogue)
+    hip_check(L.vithip_gemm_mxfp8(None, C.byref(args)), "vithip_gemm_mxfp8")
     return dC.window()
 
 
@@ -1666,12 +1721,12 @@ class Engine:
     def __init__(self, cfg: ModelConfig, max_batch: int = 256, device: int = 0, profile: bool = False,
                  lanes: int = 1, dtype: str = "f32", prune_last_layer: bool = False, use_graph: bool = False,
                  gemm_tile: int = 0, ln_fold: int = 0, gemm_handover_test: int = 0, host_first_piece: int = 0,
-                 fp32_split: int = 0):
+                 fp32_split: int = 0, mxfp8: int = 0):
         self.cfg = cfg
         self._h = C.c_void_p()
         self._head_in = None  # floats per operand row of a head set by set_head(); None: the checkpoint's own head (embed_dim)
         cc = CConfig.of(cfg)
-        opt = COptions(device, max_batch, 1 if profile else 0, lanes, {"f32": 0, "bf16": 1}[dtype],
+        opt = COptions(device, max_batch, 1 if profile else 0, lanes, {"f32": 0, "bf16": 1}[dtype] | (DTYPE_MXFP8 if mxfp8 else 0),
                        1 if prune_last_layer else 0, 1 if use_graph else 0, gemm_tile, ln_fold, gemm_handover_test, host_first_piece,
                        fp32_split)
         rc = lib().vit_engine_create(C.byref(self._h), C.byref(cc), C.byref(opt))
@@ -1680,7 +1735,9 @@ class Engine:
             if self._h:
                 lib().vit_engine_destroy(self._h)
                 self._h = C.c_void_p()
-            raise VitError(f"vit_engine_create failed ({rc}): {msg}")
+            err = VitError(f"vit_engine_create failed ({rc}): {msg}")
+            err.code = int(rc)  # VIT_ERR_*
+            raise err
 
     def _check(self, rc: int, what: str) -> None:
         if rc != 0:

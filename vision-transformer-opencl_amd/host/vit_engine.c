@@ -85,8 +85,9 @@ _Static_assert(VIT_SCORE_PROB == VITHIP_SCORE_PROB && VIT_SCORE_LOGIT == VITHIP_
                "one numbering of the scores, one bound on k");
 
 /* The resolved operands of the forward.  A GEMM's: W [N][K] in the engine's GEMM dtype, fp32 bias [N], the column sums of W where
- * the LayerNorm fold's epilogue subtracts mean * colsum (else NULL), W's pre-split image on split engines (else NULL). */
-typedef struct { const void *W; const float *bias, *colsum; const void *w_split; } vit_gemm_ops;
+ * the LayerNorm fold's epilogue subtracts mean * colsum (else NULL), W's pre-split image on split engines (else NULL), W's MXFP8
+ * image on mxfp8 engines (else NULL). */
+typedef struct { const void *W; const float *bias, *colsum; const void *w_split, *w_mx; } vit_gemm_ops;
 typedef struct { const float *ln1_g, *ln1_b, *ln2_g, *ln2_b; vit_gemm_ops qkv, out, fc1, fc2; } vit_layer_ops;
 typedef struct { const float *cls, *conv_w, *conv_b, *pos; const unsigned short *conv_w16; /* bf16 engines */ } vit_embed_ops;
 typedef struct { const float *ln_g, *ln_b; vit_gemm_ops head; } vit_final_ops;
@@ -133,6 +134,8 @@ struct vit_engine {
     float *wfoldf;               /* their column sums and folded biases */
     unsigned char *wsplit;       /* split engines: the pre-split images (vithip_split3_weights_f32) of the four encoder GEMM weights */
     size_t wsplit_off[4], wsplit_layer; /* byte offset of each image inside a layer's, and a layer's bytes */
+    unsigned char *wmx;          /* mxfp8 engines: the MXFP8 images (vithip_mxfp8_weights) of the four encoder GEMM weights, laid out likewise */
+    size_t wmx_off[4], wmx_layer;
     /* what every GEMM and LayerNorm of the forward reads, resolved by every install (resolve_operands): pointers into the above */
     vit_embed_ops embed;
     vit_layer_ops *layer;        /* [depth] */
@@ -204,7 +207,8 @@ _Static_assert(LW_FC2_B + 1 == VIT_WEIGHTS_PER_LAYER, "LW_* names every tensor o
 /* The derived operands' layout, per layer (resolve_operands fills them, and names the slots):
  *   wfold   [gamma1-folded in_proj 3D x D | gamma2-folded fc1 H1 x D], elements of the engine's GEMM dtype
  *   wfoldf  [colsum qkv 3D | bias qkv 3D | colsum fc1 H1 | bias fc1 H1]        (H1 = VIT_FC1_ROWS: H, or 2H under SwiGLU)
- *   wsplit  the images of [qkv | out_proj | fc1 | fc2] at wsplit_off[0..3], wsplit_layer bytes (vit_engine_create) */
+ *   wsplit  the images of [qkv | out_proj | fc1 | fc2] at wsplit_off[0..3], wsplit_layer bytes (vit_engine_create)
+ *   wmx     the MXFP8 images of the same four at wmx_off[0..3], wmx_layer bytes */
 static size_t fold_w_elems(const vit_config *c) { return (3 * (size_t)c->embed_dim + (size_t)VIT_FC1_ROWS(c)) * (size_t)c->embed_dim; }
 static size_t fold_f_elems(const vit_config *c) { return 6 * (size_t)c->embed_dim + 2 * (size_t)VIT_FC1_ROWS(c); }
 
@@ -339,6 +343,8 @@ int vit_engine_create(vit_engine **out, const vit_config *cfg, const vit_engine_
     e->cfg = cfg ? *cfg : vit_config_b16();
     if (opt) e->opt = *opt; else vit_engine_default_options(&e->opt);
     e->ln_eps = VITHIP_LN_EPS;
+    const int mxfp8 = (e->opt.dtype & VIT_DTYPE_MXFP8) != 0; /* the flag; everything below sees the plain dtype */
+    e->opt.dtype &= ~VIT_DTYPE_MXFP8;
     if (e->opt.max_batch <= 0) e->opt.max_batch = 256;
     if (e->opt.lanes < 1) e->opt.lanes = 1;
     int rc = check_config(e);
@@ -398,6 +404,17 @@ int vit_engine_create(vit_engine **out, const vit_config *cfg, const vit_engine_
     /* the split runs at every K of the model (K % 32 == 0 is checked for every fp32 GEMM anyway) and every M: whether it is on
      * depends on the options alone, never on the batch */
     e->split = f32 && e->opt.fp32_split >= 0;
+    if (mxfp8) {
+        /* the MXFP8 GEMM has no fold form: such an engine runs a LayerNorm kernel per LayerNorm (the ln_fold = -1 path) */
+        if (!bf16) return fail(e, VIT_ERR_ARG, "VIT_DTYPE_MXFP8 needs a bf16 engine (dtype VIT_DTYPE_BF16 | VIT_DTYPE_MXFP8)");
+        if (D % 64 || H % 64) return fail(e, VIT_ERR_ARG, "mxfp8 needs embed_dim and hidden_dim to be multiples of 64 (got %zu, %zu)", D, H);
+        if (e->opt.ln_fold > 0) return fail(e, VIT_ERR_ARG, "mxfp8 has no LayerNorm fold: ln_fold must be 0 (auto: off) or -1");
+        e->opt.ln_fold = -1;
+        const size_t b[4] = {vithip_mxfp8_image_bytes((int)(3 * D), (int)D), vithip_mxfp8_image_bytes((int)D, (int)D),
+                             vithip_mxfp8_image_bytes((int)H1, (int)D), vithip_mxfp8_image_bytes((int)D, (int)H)};
+        for (int i = 0; i < 4; ++i) { e->wmx_off[i] = e->wmx_layer; e->wmx_layer += b[i]; }
+        HIP_TRY(e, vithip_malloc((void **)&e->wmx, (size_t)e->cfg.depth * e->wmx_layer));
+    }
     if ((bf16 || f32) && e->opt.ln_fold >= 0) {
         /* bf16: the fold lives in the ping-pong GEMM (two K steps at least); its scratch (bf16 copy of x, row sums) uses the idle
          * halves of the y and qkv allocations, which bf16 activations only half fill.  fp32: the consumer epilogue exists in every
@@ -504,6 +521,7 @@ void vit_engine_destroy(vit_engine *e) {
     vithip_free(e->wblob);
     vithip_free(e->wfold);
     vithip_free(e->wsplit);
+    vithip_free(e->wmx);
     vithip_free(e->ln_rows32);
     vithip_free(e->ln_part32);
     vithip_free(e->wfoldf);
@@ -747,7 +765,8 @@ static int alloc_weight_blob(vit_engine *e, const size_t *off, size_t f32_floats
  * the encoder GEMM weights (and the conv weight) from w16[].  The derived operands are made here, where they enter the table:
  *   fold   2 launches per layer, from the resident fp32 tensors: Wf = gamma * W (bf16 engines: rounded to bf16), its column sums
  *          and the beta-folded biases of in_proj (LN1) and fc1 (LN2), which then stand in for the raw operands;
- *   split  fp32 engines: W's pieces, 4 launches per layer.
+ *   split  fp32 engines: W's pieces, 4 launches per layer;
+ *   mxfp8  bf16 engines with the option: W's MXFP8 images, 4 launches per layer, from the resident fp32 tensors.
  * The table points into wblob, which alloc_weight_blob may move: it is rebuilt by every install, never patched. */
 static int resolve_operands(vit_engine *e) {
     const int bf16 = e->opt.dtype == VIT_DTYPE_BF16, D = e->cfg.embed_dim, H = VIT_HIDDEN_DIM(&e->cfg), H1 = VIT_FC1_ROWS(&e->cfg);
@@ -758,7 +777,7 @@ static int resolve_operands(vit_engine *e) {
     for (int l = 0; l < e->cfg.depth; ++l) {
         float **lw = e->w + W_LAYER0 + VIT_WEIGHTS_PER_LAYER * l;
         unsigned short **lw16 = e->w16 + W_LAYER0 + VIT_WEIGHTS_PER_LAYER * l;
-#define GEMM_OPS(k) {bf16 ? (const void *)lw16[k] : (const void *)lw[k], lw[(k) + 1], NULL, NULL} /* a weight, its bias behind it */
+#define GEMM_OPS(k) {bf16 ? (const void *)lw16[k] : (const void *)lw[k], lw[(k) + 1], NULL, NULL, NULL} /* a weight, its bias behind it */
         vit_layer_ops o = {lw[LW_LN1_G], lw[LW_LN1_B], lw[LW_LN2_G], lw[LW_LN2_B],
                            GEMM_OPS(LW_QKV_W), GEMM_OPS(LW_OUT_W), GEMM_OPS(LW_FC1_W), GEMM_OPS(LW_FC2_W)};
 #undef GEMM_OPS
@@ -785,6 +804,15 @@ static int resolve_operands(vit_engine *e) {
                 void *img = e->wsplit + (size_t)l * e->wsplit_layer + e->wsplit_off[i];
                 HIP_TRY(e, vithip_split3_weights_f32(e->stream, g[i]->W, K[i], N[i], K[i], img));
                 g[i]->w_split = img;
+            }
+        }
+        if (e->wmx) { /* 4 launches: quantised from the fp32 tensors, not from their bf16 copies */
+            vit_gemm_ops *g[4] = {&o.qkv, &o.out, &o.fc1, &o.fc2}; /* the order of wmx_off[] */
+            const int W32[4] = {LW_QKV_W, LW_OUT_W, LW_FC1_W, LW_FC2_W}, N[4] = {3 * D, D, H1, D}, K[4] = {D, D, D, H};
+            for (int i = 0; i < 4; ++i) {
+                void *img = e->wmx + (size_t)l * e->wmx_layer + e->wmx_off[i];
+                HIP_TRY(e, vithip_mxfp8_weights(e->stream, lw[W32[i]], K[i], N[i], K[i], img));
+                g[i]->w_mx = img;
             }
         }
         e->layer[l] = o;
@@ -1028,7 +1056,7 @@ static int stage_end(vit_engine *e, vithip_stream_t s) {
 typedef struct {
     int stage, bf16;
     const void *A; int lda;
-    vit_gemm_ops ops;                  /* W [N][K], bias; colsum and w_split: the fold's consumers and split engines */
+    vit_gemm_ops ops;                  /* W [N][K], bias; colsum, w_split and w_mx: the fold's consumers, split and mxfp8 engines */
     int ldw;                           /* fp32 GEMMs: floats from one row of W to the next; 0 = K (a column block of a wider W: the dense head) */
     void *C; int ldc;
     int M, N, K;
@@ -1043,9 +1071,16 @@ static int gemm(vit_engine *e, vithip_stream_t s, const gemm_desc *g, int *stats
     const int ldr = g->ln_rows ? 0 : g->ldc; /* read by the residual epilogue only; the fold's consumers pass 0 */
     int ready;
     HIP_TRY(e, stage_begin(e, s, g->stage));
-    if (g->bf16) {
-        static const int epi16[] = {[VITHIP_EPI_BIAS] = VITHIP_BF16_EPI_BF16, [VITHIP_EPI_BIAS_GELU] = VITHIP_BF16_EPI_BF16_GELU,
-                                    [VITHIP_EPI_BIAS_RESIDUAL] = VITHIP_BF16_EPI_F32_RESIDUAL, [VITHIP_EPI_BIAS_QGELU] = VITHIP_BF16_EPI_BF16_QGELU};
+    static const int epi16[] = {[VITHIP_EPI_BIAS] = VITHIP_BF16_EPI_BF16, [VITHIP_EPI_BIAS_GELU] = VITHIP_BF16_EPI_BF16_GELU,
+                                [VITHIP_EPI_BIAS_RESIDUAL] = VITHIP_BF16_EPI_F32_RESIDUAL, [VITHIP_EPI_BIAS_QGELU] = VITHIP_BF16_EPI_BF16_QGELU};
+    if (g->bf16 && g->ops.w_mx && g->stage != VIT_STAGE_HEAD) { /* mxfp8 engines: every encoder GEMM; no fold, so no statistics */
+        vithip_gemm_mxfp8_args a;
+        memset(&a, 0, sizeof(a));
+        a.A = g->A; a.lda = g->lda; a.W = g->ops.w_mx; a.bias = g->ops.bias; a.residual = res; a.ldr = ldr;
+        a.C = g->C; a.ldc = g->ldc; a.M = g->M; a.N = g->N; a.K = g->K; a.epilogue = epi16[g->role];
+        ready = 0;
+        HIP_TRY(e, vithip_gemm_mxfp8(s, &a));
+    } else if (g->bf16) {
         vithip_gemm_bf16_args a;
         memset(&a, 0, sizeof(a));
         a.A = g->A; a.lda = g->lda; a.W = g->ops.W; a.ldw = g->K; a.bias = g->ops.bias; a.residual = res; a.ldr = ldr;
@@ -1250,6 +1285,7 @@ static int encoder_layer(chunk_ctx *c, int l) {
             kv.ops.colsum = g.ops.colsum ? g.ops.colsum + D : NULL;
             /* the image of rows D.. starts at a panel boundary only when D is a multiple of 128 (panel = 128 rows x K x 6 bytes) */
             kv.ops.w_split = g.ops.w_split && D % 128 == 0 ? at(g.ops.w_split, (size_t)D * D * 6, 1) : NULL;
+            kv.ops.w_mx = g.ops.w_mx ? at(g.ops.w_mx, vithip_mxfp8_image_row_offset(D, D), 1) : NULL; /* D % 64 == 0: a block boundary */
             RUN(gemm(e, ln->s, &kv, NULL));
             if (fold) {
                 HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
