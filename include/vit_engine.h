@@ -480,6 +480,57 @@ int vit_engine_topk_host_images(vit_engine *e, const vit_image_u8 *images, int n
                                 int *const *out);
 
 /*
+ * Nearest neighbours in a gallery of stored embeddings instead of the embedding rows: DINO's k-NN evaluation, retrieval,
+ * de-duplication, CLIP zero-shot over a vocabulary too large for the head slot.  The gallery is engine state:
+ *
+ * vit_engine_set_gallery(e, rows, G, dim, bank_dtype, rows_on_device): rows [G][dim] fp32, packed, a HOST array or
+ * (rows_on_device = 1) a device array of the engine's device, read during the call; the engine keeps its own device copy, as it is
+ * (VIT_GALLERY_F32) or rounded to bf16, nearest even, by vithip_f32_to_bf16 (VIT_GALLERY_BF16: half the bytes per query batch; the
+ * query stays fp32 and every product is exact).  It also allocates the k-NN workspace for max_batch rows on every lane.  rows = NULL
+ * drops the gallery.  Architecture-like state, as vit_engine_set_attention_bias: it PERSISTS across weight installs and the copy calls
+ * do not carry it; the new copy is made before the old one is freed (VIT_ERR_NOMEM / VIT_ERR_HIP: the previous gallery stays); the
+ * setter synchronises the device and drops a captured graph.  VIT_ERR_ARG, nothing changed: G outside 1 .. 2^31 - 2, dim outside
+ * 8..4096 or no multiple of 8, an unknown bank_dtype, rows_on_device other than 0 / 1.  vit_engine_gallery_rows: G, 0 without one.
+ *
+ * A neighbours call runs the features call of (kind, l2_normalize) -- CLS, MEAN, HEAD or MAP; the width of that kind must equal the
+ * gallery's dim -- into rows of the engine's own, then each lane launches vithip_knn_topk_f32 / _bf16bank (vit_hip_kernels.h states
+ * the arithmetic and the order) on its rows into the caller's: the row of image i is 2k 32-bit words, the record format of the top-k
+ * calls above with gallery rows for labels -- k int32 rows best first, then the k scores' fp32 bit patterns; slots without a candidate
+ * hold 0x7fffffff and -INFINITY.  The [n][G] scores exist nowhere, and on the host path 8k bytes per image come back.  An image's
+ * row is vithip_knn_topk_* of its features row, bit for bit, whatever lanes, the batch position, the chunking and the input path.
+ * The six calls mirror the six top-k calls: images, chunking, lanes, stream rules, blocking behaviour, pinned output staging and
+ * _images eager rule; a graph of use_graph is keyed on kind, l2_normalize and k too.  Profiling: the k-NN launches are accounted to
+ * VIT_STAGE_SOFTMAX, the features launches as in a features call.  vit_engine_read_logits() after a neighbours call is an error.
+ * VIT_ERR_STATE: no gallery set.  VIT_ERR_ARG (the engine stays usable, nothing was enqueued): NULL pointers, n <= 0, a kind the
+ * features calls refuse, VIT_FEAT_TOKENS, l2_normalize other than 0 / 1, a width other than the gallery's dim (the message names
+ * both), k outside 1..VIT_MAX_NEIGHBOURS, reserved != 0, and what the matching forward refuses.
+ * Not done: the temperature-weighted class vote (the host has the 2k words), L2 and other metrics, a gallery sharded over devices.
+ */
+enum { VIT_GALLERY_F32 = 0, VIT_GALLERY_BF16 = 1 };
+#define VIT_MAX_NEIGHBOURS 256
+int vit_engine_set_gallery(vit_engine *e, const float *rows, long G, int dim, int bank_dtype, int rows_on_device);
+long vit_engine_gallery_rows(const vit_engine *e);
+typedef struct {
+    int kind;          /* VIT_FEAT_CLS, _MEAN, _HEAD or _MAP */
+    int l2_normalize;  /* 0 / 1 */
+    int k;             /* 1..VIT_MAX_NEIGHBOURS */
+    int reserved;      /* must be 0 */
+} vit_neighbours_spec;
+
+/* 32-bit words per output row: 2k; 0 on a bad spec or without a gallery */
+size_t vit_engine_neighbours_row_elems(const vit_engine *e, const vit_neighbours_spec *spec);
+int vit_engine_neighbours_device(vit_engine *e, const float *d_images, int n, const vit_neighbours_spec *spec, int *d_out, void *stream);
+int vit_engine_neighbours_host(vit_engine *e, const float *const *images, int n, const vit_neighbours_spec *spec, int *const *out);
+int vit_engine_neighbours_device_u8(vit_engine *e, const unsigned char *d_images, int n, const float *mean, const float *std,
+                                    const vit_neighbours_spec *spec, int *d_out, void *stream);
+int vit_engine_neighbours_host_u8(vit_engine *e, const unsigned char *const *images, int n, const float *mean, const float *std,
+                                  const vit_neighbours_spec *spec, int *const *out);
+int vit_engine_neighbours_device_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp,
+                                        const vit_neighbours_spec *spec, int *d_out, void *stream);
+int vit_engine_neighbours_host_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp,
+                                      const vit_neighbours_spec *spec, int *const *out);
+
+/*
  * Pooled and multi-layer classifier heads: another operand for the head GEMM, as engine state.  The checkpoint's own head (tensors
  * base+2, base+3 of the Network) reads LayerNorm_final(x[i][0]); the published classifiers of DINOv2 and of timm's average-pooled
  * ViTs read something else.  With f the final LayerNorm (tensors base, base+1), x_l the residual stream behind encoder layer l (layer

@@ -550,6 +550,33 @@ int vithip_softmax_topk_f32(vithip_stream_t stream, const float *logits, int ld_
                             int rows, int classes, int k, int score);
 
 /*
+ * The k nearest rows of a feature bank for every query row (csrc/vit_knn.hip): score[i][g] = sum_d q[i][d] * bank[g][d], and the
+ * record row of query i in the format above, bank rows for labels:
+ *     records[i * ld_records + 0 .. k-1]   the bank rows (int32), best first
+ *     records[i * ld_records + k .. 2k-1]  their scores, as fp32 bit patterns
+ * Order: higher score first; among equal scores (==) the lower row first.  A NaN score is not a candidate; slots left over (k > G,
+ * NaN rows) hold 0x7fffffff and -INFINITY.  q [n][ldq] fp32; bank [G][ldb], fp32 (_f32: fp32 MFMA) or bf16 (_bf16bank: bf16 MFMA on
+ * the three bf16 pieces of q, every product exact in fp32, sums in fp32).  No array that grows with n * G is written: a workgroup
+ * keeps the best k of its slice of the bank in LDS; with more than one slice the sorted lists meet in `workspace`
+ * (vithip_knn_workspace_bytes: n * slices * 2k words) and a second launch merges them.  slices = 0: the launcher's rule
+ * (vithip_knn_slices tells what a launch will use); 1..256: that many equal runs of rows, fewer when G is smaller.  workspace may be
+ * NULL when one slice is used.  A pure function of the inputs: the bits of a score depend on D alone -- not on slices, n or the
+ * query's row -- and the chosen rows and their order on the total order alone; no global atomics.  Nothing but [n][2k] words of
+ * records (and the workspace) is written; columns behind D of q and bank are not read.  A bank of more than 4 GiB works: a slice
+ * has a 64-bit base.
+ * hipErrorInvalidValue, before anything is launched: NULL pointers (workspace: with more than one slice), n < 1, G outside
+ * 1 .. 2^31 - 2, D outside 8..4096 or no multiple of 8, k outside 1..VITHIP_MAX_NEIGHBOURS, slices outside 0..256, ldq < D or no
+ * multiple of 4, ldb < D or no multiple of 4 (bf16: 8), ld_records < 2k, q or bank not 16-byte aligned.
+ */
+#define VITHIP_MAX_NEIGHBOURS 256
+size_t vithip_knn_workspace_bytes(int n, long G, int k, int slices);
+int vithip_knn_slices(int n, long G, int slices);
+int vithip_knn_topk_f32(vithip_stream_t stream, const float *q, long ldq, int n, const float *bank, long ldb, long G, int D, int k,
+                        int *records, long ld_records /* 32-bit words per row, >= 2k */, void *workspace, int slices);
+int vithip_knn_topk_bf16bank(vithip_stream_t stream, const float *q, long ldq, int n, const unsigned short *bank, long ldb, long G, int D,
+                             int k, int *records, long ld_records, void *workspace, int slices);
+
+/*
  * The model input from 8-bit pixels (csrc/vit_input.hip): src [n][S][S][C] uint8, channels interleaved as image decoders
  * write them -> dst [n][C][S][S] fp32,
  *     dst[i][c][h][w] = ((float)src[i][h][w][c] / 255.0f - mean[c]) / std[c]

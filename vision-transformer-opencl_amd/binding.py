@@ -169,6 +169,14 @@ VIT_MAX_TOPK = 64
 TOPK_EMPTY_LABEL = 0x7FFFFFFF  # the label of a slot no candidate was left for; its score: -1.0 (prob) or -inf (logit)
 
 
+class CNeighboursSpec(C.Structure):  # vit_neighbours_spec
+    _fields_ = [("kind", C.c_int), ("l2_normalize", C.c_int), ("k", C.c_int), ("reserved", C.c_int)]
+
+
+GALLERY_DTYPES = {"f32": 0, "bf16": 1}  # VIT_GALLERY_*
+VIT_MAX_NEIGHBOURS = 256
+
+
 def _score(score) -> int:
     return SCORES[score] if isinstance(score, str) else int(score)
 
@@ -214,6 +222,11 @@ def attention_spec(kind, reserved: int = 0) -> CAttentionSpec:
 def topk_spec(k: int, score="prob", reserved: int = 0) -> CTopkSpec:
     """score: "prob" | "logit" (or a raw VIT_SCORE_* integer); everything is passed through unchecked for the C side to judge."""
     return CTopkSpec(int(k), _score(score), int(reserved))
+
+
+def neighbours_spec(k: int, kind="cls", l2_normalize=True, reserved: int = 0) -> CNeighboursSpec:
+    """kind: "cls" | "mean" | "head" | "map" (or a raw VIT_FEAT_* integer); everything is passed through unchecked for the C side to judge."""
+    return CNeighboursSpec(FEATURE_KINDS[kind] if isinstance(kind, str) else int(kind), int(l2_normalize), int(k), int(reserved))
 
 
 def split_topk(records):
@@ -329,14 +342,15 @@ def lib() -> C.CDLL:
         # the forward surface, output kind x place x input kind: (engine, images, n) + normalisation + spec + destination
         norm = {"": [], "_u8": [f32p, f32p], "_images": [C.POINTER(CPreproc)]}
         spec = {"forward": [], "features": [C.POINTER(CFeatureSpec)], "cls_attention": [C.POINTER(CAttentionSpec)],
-                "intermediate": [C.POINTER(CIntermediateSpec)], "topk": [C.POINTER(CTopkSpec)], "dense": [C.POINTER(CDenseSpec)]}
+                "intermediate": [C.POINTER(CIntermediateSpec)], "topk": [C.POINTER(CTopkSpec)], "dense": [C.POINTER(CDenseSpec)],
+                "neighbours": [C.POINTER(CNeighboursSpec)]}
         for out in spec:
             for place in ("host", "device"):
                 for kind in norm:
                     images = C.POINTER(CImageU8) if kind == "_images" else C.c_void_p if place == "device" else \
                         C.POINTER(C.c_void_p if kind == "_u8" else f32p)
                     # host: a row per image; device: the rows, a forward's top-1 labels and probabilities, the stream
-                    dst = [C.POINTER(i32p if out == "topk" else C.c_void_p if out == "dense" else f32p)] if place == "host" else [C.c_void_p] * (4 if out == "forward" else 2)
+                    dst = [C.POINTER(i32p if out in ("topk", "neighbours") else C.c_void_p if out == "dense" else f32p)] if place == "host" else [C.c_void_p] * (4 if out == "forward" else 2)
                     name = f"vit_engine_{out}_{place}{kind}"
                     if hasattr(L, name):  # VIT_HIP_LIBRARY may name an earlier build (A/B timing), which lacks the later calls
                         getattr(L, name).argtypes = [C.c_void_p, images, C.c_int] + norm[kind] + spec[out] + dst
@@ -371,6 +385,18 @@ def lib() -> C.CDLL:
             L.vit_engine_topk_row_elems.restype = C.c_size_t
             L.vit_engine_topk_row_elems.argtypes = [C.c_void_p, C.POINTER(CTopkSpec)]
             L.vithip_softmax_topk_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_int] * 4
+        if hasattr(L, "vit_engine_set_gallery"):  # an earlier build (see above) has no gallery
+            L.vit_engine_set_gallery.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int]
+            L.vit_engine_gallery_rows.restype = C.c_long
+            L.vit_engine_gallery_rows.argtypes = [C.c_void_p]
+            L.vit_engine_neighbours_row_elems.restype = C.c_size_t
+            L.vit_engine_neighbours_row_elems.argtypes = [C.c_void_p, C.POINTER(CNeighboursSpec)]
+            L.vithip_knn_workspace_bytes.restype = C.c_size_t
+            L.vithip_knn_workspace_bytes.argtypes = [C.c_int, C.c_long, C.c_int, C.c_int]
+            L.vithip_knn_slices.argtypes = [C.c_int, C.c_long, C.c_int]
+            for name in ("vithip_knn_topk_f32", "vithip_knn_topk_bf16bank"):
+                getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_long, C.c_void_p, C.c_int]
         if hasattr(L, "vit_engine_load_weights_resampled"):  # an earlier build (see above) cannot resample a position embedding
             L.vit_engine_load_weights_resampled.argtypes = [C.c_void_p, C.POINTER(CNetwork), C.c_int, C.POINTER(CPosResample)]
             L.vit_engine_copy_weights_resampled.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
@@ -1558,6 +1584,38 @@ def softmax_top1(logits, ld_logits: Optional[int] = None, ld_probs: Optional[int
     return dp.window(), dlab.window().reshape(rows) if want_label else None, dpr.window().reshape(rows) if want_prob else None
 
 
+def knn_topk(q, bank, k: int, slices: int = 0, ld_records: Optional[int] = None, ldq: Optional[int] = None, ldb: Optional[int] = None,
+             fill_bits: int = 0, pad_bits: int = 0x7FC00000, n: Optional[int] = None) -> np.ndarray:
+    """vithip_knn_topk_f32 / _bf16bank -> the record rows [n][ld_records] int32 (split_topk() takes the first 2k words of a row apart).
+    q [n][D] float32; bank [G][D] float32, or uint16 holding bf16 bit patterns (to_bf16_bits() makes them).  ldq / ldb (>= D): the rows
+    are laid out at that step, the pad columns preset to pad_bits (a NaN); ld_records (>= 2k, default 2k): words per record row, every
+    word preset to fill_bits.  n: the rows of q that are queries (default all).  Everything is passed through for the C side to judge."""
+    q = np.ascontiguousarray(q, np.float32)
+    bank = np.ascontiguousarray(bank)
+    bf16 = bank.dtype == np.uint16
+    if not bf16:
+        bank = bank.astype(np.float32, copy=False)
+    (rows, D), G = q.shape, bank.shape[0]
+    n = rows if n is None else int(n)
+    ldq_, ldb_, ldr = int(ldq or D), int(ldb or D), int(2 * k if ld_records is None else ld_records)
+    qs = np.full((rows, max(ldq_, D)), pad_bits, np.uint32).view(np.float32)
+    qs[:, :D] = q
+    bs = np.full((G, max(ldb_, D)), pad_bits & 0xFFFF if bf16 else pad_bits, np.uint16 if bf16 else np.uint32)
+    bs[:, :D] = bank if bf16 else bank.view(np.uint32)
+    raw = np.full(rows * max(ldr, 1), fill_bits, np.uint32)
+    L = lib()
+    ws_bytes = L.vithip_knn_workspace_bytes(n, G, int(k), int(slices))
+    arrays = [DeviceArray.from_numpy(qs), DeviceArray.from_numpy(bs), DeviceArray.from_numpy(raw),
+              DeviceArray.from_numpy(np.zeros(max(ws_bytes // 4, 1), np.uint32))]
+    try:
+        fn = L.vithip_knn_topk_bf16bank if bf16 else L.vithip_knn_topk_f32
+        hip_check(fn(None, arrays[0].ptr, ldq_, n, arrays[1].ptr, ldb_, G, D, int(k), arrays[2].ptr, ldr, arrays[3].ptr, int(slices)), "vithip_knn_topk")
+        return arrays[2].numpy().view(np.int32).reshape(rows, max(ldr, 1))
+    finally:
+        for a in arrays:
+            a.free()
+
+
 def softmax_topk(logits, k: int, score="prob", ld_logits: Optional[int] = None, ld_out: Optional[int] = None, guard: int = 0,
                  fill_bits: int = 0, out_offset: int = 0, out: Optional[dict] = None) -> np.ndarray:
     """vithip_softmax_topk_f32 -> the records [rows][2k] int32 (split_topk() takes them apart).  ld_logits (>= classes): the rows
@@ -1776,7 +1834,7 @@ class Engine:
         L.vit_engine_copy_weights.argtypes = [C.c_void_p, C.c_void_p]
         self._check(L.vit_engine_copy_weights(self._h, other._h), "vit_engine_copy_weights")
 
-    # ---- the forward surface: vit_engine_<out>_<place><inp>, out "forward" | "features" | "cls_attention" | "intermediate" | "topk" | "dense", inp "" | "_u8" | "_images" ----
+    # ---- the forward surface: vit_engine_<out>_<place><inp>, out "forward" | "features" | "cls_attention" | "intermediate" | "topk" | "dense" | "neighbours", inp "" | "_u8" | "_images" ----
     def _call_args(self, out, inp, kind, l2_normalize, mean, std, resize_shorter, layers=None, norm=True, topk=None, dense=None) -> list:
         """What lies between n and the destination in the C call: the normalisation of the input kind, the spec of the output kind."""
         args = []
@@ -1786,7 +1844,7 @@ class Engine:
             args.append(C.byref(preproc_params(resize_shorter, mean, std, self.cfg.in_chans)))
         if out == "intermediate":
             args.append(C.byref(intermediate_spec(layers, kind, norm, self.cfg.depth)))
-        elif out == "topk":
+        elif out in ("topk", "neighbours"):  # both carry their spec in `topk`
             args.append(C.byref(topk))
         elif out == "dense":
             args.append(C.byref(dense))
@@ -1811,15 +1869,16 @@ class Engine:
             shape = (n, self.cfg.num_classes)
         elif out == "dense":
             shape = self.dense_shape(n, dense)
-        elif out == "topk":
+        elif out in ("topk", "neighbours"):
             shape = (n, 2 * max(topk.k, 1))  # a spec the C side refuses still gets rows: the call must see its own arguments
         elif out == "intermediate":
             shape = self.intermediate_shape(n, layers, kind, norm)
         else:
             shape = self.feature_shape(n, kind, l2_normalize) if out == "features" else self.attention_shape(n, kind)
-        rowp = i32p if out == "topk" else C.c_void_p if out == "dense" else f32p
+        records = out in ("topk", "neighbours")
+        rowp = i32p if records else C.c_void_p if out == "dense" else f32p
         labels = out == "dense" and dense.kind == DENSE_KINDS["labels"]
-        rows = np.empty(shape, np.int32 if out == "topk" else np.uint8 if labels else np.float32)
+        rows = np.empty(shape, np.int32 if records else np.uint8 if labels else np.float32)
         out_ptrs = (rowp * n)(*[rows[i].ctypes.data if out == "dense" else rows[i].ctypes.data_as(rowp) for i in range(n)])
         name = f"vit_engine_{out}_host{inp}"
         self._check(getattr(lib(), name)(self._h, in_ptrs, n, *args, out_ptrs), name)
@@ -1981,6 +2040,41 @@ class Engine:
         """Device-resident path: images = a list of (ptr, H, W) in HBM, d_out [n][row] fp32; async on `stream`."""
         self._device("intermediate", "_images", images, None, d_out, kind, mean=mean, std=std, resize_shorter=resize_shorter, stream=stream,
                      layers=layers, norm=norm)
+
+    # ---- nearest neighbours in a gallery (vit_engine_set_gallery, vit_engine_neighbours_*): rows of 2k int32 words, k gallery rows then
+    # the k scores' bit patterns (split_topk) ----
+    def set_gallery(self, rows, dtype="f32") -> None:
+        """rows: [G][dim] float32 (None drops the gallery); dtype "f32" | "bf16": what the engine's device copy is kept in."""
+        if rows is None:
+            self._check(lib().vit_engine_set_gallery(self._h, None, 0, 0, 0, 0), "vit_engine_set_gallery")
+            return
+        rows = np.ascontiguousarray(rows, np.float32)
+        assert rows.ndim == 2, rows.shape
+        dt = GALLERY_DTYPES[dtype] if isinstance(dtype, str) else int(dtype)
+        self._check(lib().vit_engine_set_gallery(self._h, rows.ctypes.data, rows.shape[0], rows.shape[1], dt, 0), "vit_engine_set_gallery")
+
+    def neighbours(self, images: np.ndarray, k: int, kind="cls", l2_normalize=1, reserved: int = 0) -> np.ndarray:
+        """Host path: images [n][C][S][S] float32 in, records [n][2k] int32 out -- the k best gallery rows of each image's features."""
+        return self._host("neighbours", "", images, topk=neighbours_spec(k, kind, l2_normalize, reserved))
+
+    def neighbours_u8(self, images: np.ndarray, k: int, kind="cls", l2_normalize=1, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
+        return self._host("neighbours", "_u8", images, mean=mean, std=std, topk=neighbours_spec(k, kind, l2_normalize))
+
+    def neighbours_images(self, images, resize_shorter: int, k: int, kind="cls", l2_normalize=1, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
+        return self._host("neighbours", "_images", images, mean=mean, std=std, resize_shorter=resize_shorter, topk=neighbours_spec(k, kind, l2_normalize))
+
+    def neighbours_device(self, d_images: int, n: int, d_out: int, k: int, kind="cls", l2_normalize=1, stream: int = 0) -> None:
+        """Device path: d_images [n][C][S][S] fp32 and d_out [n][2k] int32, raw HBM addresses; async on `stream`."""
+        self._device("neighbours", "", d_images, n, d_out, stream=stream, topk=neighbours_spec(k, kind, l2_normalize))
+
+    def neighbours_device_u8(self, d_images: int, n: int, d_out: int, k: int, kind="cls", l2_normalize=1, mean=IMAGENET_MEAN,
+                             std=IMAGENET_STD, stream: int = 0) -> None:
+        self._device("neighbours", "_u8", d_images, n, d_out, mean=mean, std=std, stream=stream, topk=neighbours_spec(k, kind, l2_normalize))
+
+    def neighbours_device_images(self, images, d_out: int, resize_shorter: int, k: int, kind="cls", l2_normalize=1, mean=IMAGENET_MEAN,
+                                 std=IMAGENET_STD, stream: int = 0) -> None:
+        self._device("neighbours", "_images", images, None, d_out, mean=mean, std=std, resize_shorter=resize_shorter, stream=stream,
+                     topk=neighbours_spec(k, kind, l2_normalize))
 
     # ---- top-k class records (vit_engine_topk_*): rows of 2k int32 words, k labels then the k scores' bit patterns (split_topk) ----
     def topk_shape(self, n: int, k: int) -> tuple:

@@ -60,10 +60,11 @@ _Static_assert(sizeof(vit_image_u8) == sizeof(vithip_image_u8) && offsetof(vit_i
  * asks for (stage_features), the class token's attention over the tokens in the last layer (stage_cls_attention), or the residual
  * stream behind the layers `tap` names (stage_tap), [n][row] floats -- or, behind the head, the k best classes as records in
  * place of the probabilities (stage_head; 32-bit words, as many bytes as a float each) -- or the rows of a dense call
- * (stage_dense_out: labels, a byte each, or the fp32 grid).  What the engine knows of each kind, the bytes of its row among it, is
+ * (stage_dense_out: labels, a byte each, or the fp32 grid) -- or the k nearest gallery rows of the embedding rows, records again
+ * (stage_neighbours).  What the engine knows of each kind, the bytes of its row among it, is
  * the kind's row of OUT_KINDS.  Zero-filled before use (output_fault): the graph cache compares it bytewise.  The pointers are those
  * of the call's (or chunk's) first image. */
-enum { VIT_OUT_PROBS = 0, VIT_OUT_FEATURES = 1, VIT_OUT_ATTENTION = 2, VIT_OUT_INTERMEDIATE = 3, VIT_OUT_TOPK = 4, VIT_OUT_DENSE = 5, VIT_OUT_KINDS };
+enum { VIT_OUT_PROBS = 0, VIT_OUT_FEATURES = 1, VIT_OUT_ATTENTION = 2, VIT_OUT_INTERMEDIATE = 3, VIT_OUT_TOPK = 4, VIT_OUT_DENSE = 5, VIT_OUT_NEIGHBOURS = 6, VIT_OUT_KINDS };
 typedef struct {
     int kind;              /* VIT_OUT_*: which member of the union is in use (_PROBS: none), and what dst holds */
     int zero;              /* always 0: with it the struct has no padding, which a bytewise comparison would read */
@@ -73,6 +74,7 @@ typedef struct {
         vit_intermediate_spec tap; /* _INTERMEDIATE: layers[num_layers..] zero */
         vit_topk_spec topk;        /* _TOPK: dst = the records, [n][2k] 32-bit words */
         vit_dense_spec dense;      /* _DENSE: out_h / out_w resolved; the head is engine state */
+        vit_neighbours_spec nb;    /* _NEIGHBOURS: dst = the records, [n][2k] 32-bit words; the gallery is engine state */
     };
     float *dst;
     int *label;            /* _PROBS: top-1 (may be NULL) */
@@ -83,6 +85,7 @@ _Static_assert(sizeof(vit_output) == 2 * sizeof(int) + sizeof(vit_intermediate_s
                "vit_output must stay free of padding: the graph cache compares it bytewise");
 _Static_assert(VIT_SCORE_PROB == VITHIP_SCORE_PROB && VIT_SCORE_LOGIT == VITHIP_SCORE_LOGIT && VIT_MAX_TOPK == VITHIP_MAX_TOPK,
                "one numbering of the scores, one bound on k");
+_Static_assert(VIT_MAX_NEIGHBOURS == VITHIP_MAX_NEIGHBOURS, "one bound on the neighbours");
 
 /* The resolved operands of the forward.  A GEMM's: W [N][K] in the engine's GEMM dtype, fp32 bias [N], the column sums of W where
  * the LayerNorm fold's epilogue subtracts mean * colsum (else NULL), W's pre-split image on split engines (else NULL), W's MXFP8
@@ -111,6 +114,11 @@ typedef struct {
     float *pooled, *ln_rows, *hidden, *ws;
     size_t ws_floats;
 } vit_map_head;
+
+/* The gallery in force (vit_engine_set_gallery; bank == NULL: none): the engine's copy of the rows [G][dim] in `dtype`, the feature
+ * rows of a chunk [max_batch][dim] that the k-NN reads, and the k-NN workspace, ws_lane bytes for each of VIT_MAX_LANES lanes (lanes
+ * run on independent streams): three allocations of its own. */
+typedef struct { void *bank; long G; int dim, dtype; float *rows; unsigned char *ws; size_t ws_lane; } vit_gallery;
 
 struct vit_engine {
     vit_config cfg;
@@ -167,6 +175,7 @@ struct vit_engine {
     vit_head head;
     vit_dense_head dense;
     vit_map_head map;
+    vit_gallery gallery;         /* architecture-like state, kept across installs */
     /* host-pointer path: double-buffered staging so that gather + H2D of piece i+1 overlap compute of piece i */
     float *in_stage[2], *out_stage[2];   /* device */
     float *pin_in[2], *pin_out[2];       /* pinned host */
@@ -490,6 +499,12 @@ static void release_map_head(vit_map_head *h) {
     memset(h, 0, sizeof(*h));
 }
 
+/* ... and the gallery's */
+static void release_gallery(vit_gallery *g) {
+    vithip_free(g->bank); vithip_free(g->rows); vithip_free(g->ws);
+    memset(g, 0, sizeof(*g));
+}
+
 void vit_engine_destroy(vit_engine *e) {
     if (!e) return;
     vithip_set_device(e->opt.device);
@@ -502,6 +517,7 @@ void vit_engine_destroy(vit_engine *e) {
     release_head(&e->head);
     release_dense_head(&e->dense);
     release_map_head(&e->map);
+    release_gallery(&e->gallery);
     vithip_free(e->pre_g); /* one allocation: gamma, beta behind it */
     vithip_free(e->rope_cos); /* one allocation: cos, sin behind it */
     for (int l = 0; e->attn_bias && l < e->cfg.depth; ++l)
@@ -669,6 +685,70 @@ int vit_engine_has_attention_bias(const vit_engine *e, int layer) {
     if (!e || layer < -1 || layer >= e->cfg.depth) return 0;
     return layer < 0 ? e->attn_bias_shared != NULL : e->attn_bias[layer] != NULL;
 }
+
+/* The engine's copy of the gallery rows, made on the engine's stream: as they are, or rounded to bf16 by the project's conversion --
+ * host rows through a temporary device buffer of whole rows, a piece at a time.  Returns a HIP error code. */
+static int fill_gallery_bank(vit_engine *e, void *bank, const float *rows, long G, int dim, int bank_dtype, int on_device) {
+    const size_t count = (size_t)G * (size_t)dim;
+    if (bank_dtype == VIT_GALLERY_F32)
+        return on_device ? vithip_memcpy_d2d(bank, rows, count * sizeof(float), e->stream) : vithip_memcpy_h2d(bank, rows, count * sizeof(float), e->stream);
+    if (on_device) return vithip_f32_to_bf16(e->stream, rows, (unsigned short *)bank, count);
+    const size_t piece_rows = ((size_t)16 << 20) / (size_t)dim, piece = (piece_rows < (size_t)G ? piece_rows : (size_t)G) * (size_t)dim;
+    float *tmp = NULL;
+    int hrc = vithip_malloc((void **)&tmp, piece * sizeof(float));
+    for (size_t at_ = 0; !hrc && at_ < count; at_ += piece) {
+        const size_t now = count - at_ < piece ? count - at_ : piece;
+        hrc = vithip_memcpy_h2d(tmp, rows + at_, now * sizeof(float), e->stream);
+        if (!hrc) hrc = vithip_f32_to_bf16(e->stream, tmp, (unsigned short *)bank + at_, now);
+        if (!hrc) hrc = vithip_stream_sync(e->stream); /* tmp is written again */
+    }
+    vithip_free(tmp);
+    return hrc;
+}
+
+int vit_engine_set_gallery(vit_engine *e, const float *rows, long G, int dim, int bank_dtype, int rows_on_device) {
+    if (!e) return VIT_ERR_ARG;
+    HIP_TRY(e, vithip_set_device(e->opt.device));
+    if (!rows) { /* as an install: nothing in flight, no graph with the old launch list */
+        HIP_TRY(e, vithip_device_sync());
+        drop_graph(e);
+        release_gallery(&e->gallery);
+        return VIT_OK;
+    }
+    if (G < 1 || G >= 0x7fffffffL) return fail(e, VIT_ERR_ARG, "set_gallery: G = %ld must be 1 .. 2^31 - 2", G);
+    if (dim < 8 || dim > 4096 || dim % 8) return fail(e, VIT_ERR_ARG, "set_gallery: dim = %d must be a multiple of 8 in 8..4096", dim);
+    if (bank_dtype != VIT_GALLERY_F32 && bank_dtype != VIT_GALLERY_BF16)
+        return fail(e, VIT_ERR_ARG, "set_gallery: bank_dtype %d: VIT_GALLERY_F32 (%d) or VIT_GALLERY_BF16 (%d)", bank_dtype, VIT_GALLERY_F32, VIT_GALLERY_BF16);
+    if (rows_on_device != 0 && rows_on_device != 1) return fail(e, VIT_ERR_ARG, "set_gallery: rows_on_device must be 0 or 1 (got %d)", rows_on_device);
+    /* the new gallery first, whole; only then the old one goes */
+    vit_gallery g = {.G = G, .dim = dim, .dtype = bank_dtype};
+    for (int n = 1; n <= e->opt.max_batch; ++n) { /* a lane holds up to max_batch rows, and the slices of a launch depend on them */
+        const size_t b = vithip_knn_workspace_bytes(n, G, VIT_MAX_NEIGHBOURS, 0);
+        if (b > g.ws_lane) g.ws_lane = b;
+    }
+    g.ws_lane = (g.ws_lane + 255) / 256 * 256;
+    const size_t bank_bytes = (size_t)G * (size_t)dim * (bank_dtype == VIT_GALLERY_BF16 ? sizeof(unsigned short) : sizeof(float));
+    int hrc = vithip_malloc(&g.bank, bank_bytes);
+    if (!hrc) hrc = vithip_malloc((void **)&g.rows, (size_t)e->opt.max_batch * (size_t)dim * sizeof(float));
+    if (!hrc) hrc = vithip_malloc((void **)&g.ws, VIT_MAX_LANES * g.ws_lane);
+    if (hrc) {
+        release_gallery(&g);
+        return fail(e, VIT_ERR_NOMEM, "set_gallery: no memory for %zu bytes of rows and %zu of workspace (HIP error %d: %s); the previous gallery stays",
+                    bank_bytes, VIT_MAX_LANES * g.ws_lane, hrc, vithip_error_string(hrc));
+    }
+    hrc = fill_gallery_bank(e, g.bank, rows, G, dim, bank_dtype, rows_on_device);
+    if (!hrc) hrc = vithip_device_sync(); /* the copy, and every call that still reads the old gallery, on whatever stream */
+    if (hrc) {
+        release_gallery(&g);
+        return fail(e, VIT_ERR_HIP, "set_gallery: HIP error %d (%s) copying the rows; the previous gallery stays", hrc, vithip_error_string(hrc));
+    }
+    drop_graph(e); /* a captured call holds the old addresses */
+    release_gallery(&e->gallery);
+    e->gallery = g;
+    return VIT_OK;
+}
+
+long vit_engine_gallery_rows(const vit_engine *e) { return e && e->gallery.bank ? e->gallery.G : 0; }
 
 int vit_rel_pos_bias_expand(const float *table, int grid, int heads, float *out) {
     if (!table || !out || grid < 1 || heads < 1) return VIT_ERR_ARG;
@@ -1796,6 +1876,78 @@ static int dense_last_layer(const vit_engine *e, const vit_output *out) { /* the
     return e->dense.spec.layers[e->dense.spec.num_layers - 1];
 }
 
+/* A neighbours call is the features call of its (kind, l2_normalize) into the gallery's own rows, then the k-NN on them: every hook
+ * asks the features hooks about that call. */
+static const char NO_GALLERY[] = "%s before vit_engine_set_gallery()";
+static vit_output as_features(const vit_engine *e, const vit_output *out) {
+    vit_output f;
+    memset(&f, 0, sizeof(f));
+    f.kind = VIT_OUT_FEATURES;
+    f.spec.kind = out->nb.kind; f.spec.l2_normalize = out->nb.l2_normalize;
+    f.dst = e->gallery.rows;
+    return f;
+}
+static const char *neighbours_check(const vit_engine *e, const void *caller, vit_output *out, int arg[2]) {
+    const vit_neighbours_spec *spec = (const vit_neighbours_spec *)caller;
+    if (!spec) return "%s: the neighbours spec is required";
+    if (!e->gallery.bank) return NO_GALLERY;
+    arg[0] = spec->kind;
+    if (spec->kind == VIT_FEAT_TOKENS) return "%s: feature kind %d (VIT_FEAT_TOKENS) has no [n][width] rows to compare with a gallery";
+    const vit_feature_spec fs = {spec->kind, spec->l2_normalize};
+    vit_output f;
+    memset(&f, 0, sizeof(f));
+    const char *fault = features_check(e, &fs, &f, arg);
+    if (fault) return fault;
+    arg[0] = (int)(features_row_bytes(e, &f) / sizeof(float)); arg[1] = e->gallery.dim;
+    if (arg[0] != arg[1]) return "%s: the rows of that kind are %d wide, the gallery's %d";
+    arg[0] = spec->k; arg[1] = VIT_MAX_NEIGHBOURS;
+    if (spec->k < 1 || spec->k > VIT_MAX_NEIGHBOURS) return "%s: k = %d must be 1..%d (VIT_MAX_NEIGHBOURS)";
+    arg[0] = spec->reserved;
+    if (spec->reserved != 0) return "%s: vit_neighbours_spec.reserved must be 0 (got %d)";
+    out->nb.kind = spec->kind; out->nb.l2_normalize = spec->l2_normalize; out->nb.k = spec->k;
+    return NULL;
+}
+static size_t neighbours_row_bytes(const vit_engine *e, const vit_output *out) { /* 2k 32-bit words */
+    (void)e;
+    return 2 * (size_t)out->nb.k * sizeof(int);
+}
+static int neighbours_rows_only(const vit_engine *e, const vit_output *out) {
+    const vit_output f = as_features(e, out);
+    return head_or_class_rows_only(e, &f);
+}
+static int neighbours_after_layer(chunk_ctx *c, const vit_output *out, int l) {
+    const vit_output f = as_features(c->e, out);
+    return stage_head_tap(c, &f, l);
+}
+/* The feature rows of the chunk into the gallery's rows (the stages of a features call, told that a row is dim floats wide), then per
+ * lane, on the lane's stream and with the lane's stretch of the workspace, the k-NN of its rows into the caller's records. */
+static int stage_neighbours(chunk_ctx *c, const vit_output *out) {
+    vit_engine *e = c->e;
+    const vit_gallery *g = &e->gallery;
+    const vit_output f = as_features(e, out);
+    const size_t row = c->row, dim = (size_t)g->dim;
+    const int k = out->nb.k;
+    c->row = dim * sizeof(float);
+    const int rc = stage_head_or_features(c, &f);
+    c->row = row;
+    if (rc) return rc;
+    for (int j = 0; j < c->L; ++j) {
+        const vit_lane *ln = &c->lane[j];
+        const float *q = g->rows + (size_t)ln->off * dim;
+        int *dst = (int *)out->dst + (size_t)ln->off * 2 * (size_t)k;
+        void *ws = g->ws + (size_t)j * g->ws_lane;
+        if (vithip_knn_workspace_bytes(ln->n, g->G, k, 0) > g->ws_lane)
+            return fail(e, VIT_ERR_STATE, "neighbours: the k-NN workspace of %d rows does not fit the lane's %zu bytes", ln->n, g->ws_lane);
+        HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_SOFTMAX));
+        if (g->dtype == VIT_GALLERY_BF16)
+            HIP_TRY(e, vithip_knn_topk_bf16bank(ln->s, q, (long)dim, ln->n, (const unsigned short *)g->bank, (long)dim, g->G, g->dim, k, dst, 2L * k, ws, 0));
+        else
+            HIP_TRY(e, vithip_knn_topk_f32(ln->s, q, (long)dim, ln->n, (const float *)g->bank, (long)dim, g->G, g->dim, k, dst, 2L * k, ws, 0));
+        HIP_TRY(e, stage_end(e, ln->s));
+    }
+    return VIT_OK;
+}
+
 static const vit_out_kind OUT_KINDS[VIT_OUT_KINDS] = {
     [VIT_OUT_PROBS] = {.row_bytes = probs_row_bytes, .class_rows_only = head_or_class_rows_only, .after_layer = stage_head_tap,
                        .finish = stage_head_or_features},
@@ -1810,6 +1962,8 @@ static const vit_out_kind OUT_KINDS[VIT_OUT_KINDS] = {
     /* no class_rows_only: the patch rows of every tapped layer */
     [VIT_OUT_DENSE] = {.check = dense_check, .row_bytes = dense_row_bytes, .last_layer = dense_last_layer, .after_layer = stage_dense_tap,
                        .finish = stage_dense_out},
+    [VIT_OUT_NEIGHBOURS] = {.check = neighbours_check, .row_bytes = neighbours_row_bytes, .class_rows_only = neighbours_rows_only,
+                            .after_layer = neighbours_after_layer, .finish = stage_neighbours},
 };
 
 /* The output of a call: *out zeroed in full (the graph key compares it bytewise), then what the kind's check makes of the caller's
@@ -1823,7 +1977,7 @@ static const char *output_fault(const vit_engine *e, int kind, const void *spec,
 static int make_output(vit_engine *e, const char *who, int kind, const void *spec, float *dst, int *label, float *prob, vit_output *out) {
     int arg[2];
     const char *fault = output_fault(e, kind, spec, out, arg);
-    if (fault) return fail(e, fault == NO_DENSE_HEAD ? VIT_ERR_STATE : VIT_ERR_ARG, fault, who, arg[0], arg[1]);
+    if (fault) return fail(e, fault == NO_DENSE_HEAD || fault == NO_GALLERY ? VIT_ERR_STATE : VIT_ERR_ARG, fault, who, arg[0], arg[1]);
     if (kind == VIT_OUT_ATTENTION && e->attn_bias[e->cfg.depth - 1]) /* the class-row kernel takes no bias: a wrong row is not an answer */
         return fail(e, VIT_ERR_STATE, "%s: the last layer has an attention bias (vit_engine_set_attention_bias), which the class-attention kernel does not take", who);
     out->dst = dst; out->label = label; out->prob = prob;
@@ -1849,6 +2003,9 @@ size_t vit_engine_intermediate_row_elems(const vit_engine *e, const vit_intermed
 }
 size_t vit_engine_topk_row_elems(const vit_engine *e, const vit_topk_spec *spec) {
     return spec_row_bytes(e, VIT_OUT_TOPK, spec) / sizeof(float);
+}
+size_t vit_engine_neighbours_row_elems(const vit_engine *e, const vit_neighbours_spec *spec) {
+    return spec_row_bytes(e, VIT_OUT_NEIGHBOURS, spec) / sizeof(int);
 }
 size_t vit_engine_dense_row_bytes(const vit_engine *e, const vit_dense_spec *spec) {
     return spec_row_bytes(e, VIT_OUT_DENSE, spec);
@@ -2554,6 +2711,41 @@ int vit_engine_dense_host_images(vit_engine *e, const vit_image_u8 *images, int 
                                  void *const *out) {
     return run_call(e, &(vit_call){.who = "dense_host_images", .place = VIT_AT_HOST, .in_kind = VIT_IN_IMAGES, .images = images, .n = n,
                                     .pp = pp, .out_kind = VIT_OUT_DENSE, .spec = spec, .rows = (float *const *)out});
+}
+
+/* The neighbours calls: the top-k calls' shape, records carried as the floats they are as wide as. */
+int vit_engine_neighbours_device(vit_engine *e, const float *d_images, int n, const vit_neighbours_spec *spec, int *d_out, void *stream) {
+    return run_call(e, &(vit_call){.who = "neighbours_device", .place = VIT_AT_DEVICE, .in_kind = VIT_IN_F32, .images = d_images, .n = n,
+                                    .out_kind = VIT_OUT_NEIGHBOURS, .spec = spec, .dst = (float *)d_out, .stream = stream});
+}
+
+int vit_engine_neighbours_device_u8(vit_engine *e, const unsigned char *d_images, int n, const float *mean, const float *std,
+                                    const vit_neighbours_spec *spec, int *d_out, void *stream) {
+    return run_call(e, &(vit_call){.who = "neighbours_device_u8", .place = VIT_AT_DEVICE, .in_kind = VIT_IN_U8, .images = d_images, .n = n,
+                                    .mean = mean, .std = std, .out_kind = VIT_OUT_NEIGHBOURS, .spec = spec, .dst = (float *)d_out, .stream = stream});
+}
+
+int vit_engine_neighbours_device_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp,
+                                        const vit_neighbours_spec *spec, int *d_out, void *stream) {
+    return run_call(e, &(vit_call){.who = "neighbours_device_images", .place = VIT_AT_DEVICE, .in_kind = VIT_IN_IMAGES, .images = images,
+                                    .n = n, .pp = pp, .out_kind = VIT_OUT_NEIGHBOURS, .spec = spec, .dst = (float *)d_out, .stream = stream});
+}
+
+int vit_engine_neighbours_host(vit_engine *e, const float *const *images, int n, const vit_neighbours_spec *spec, int *const *out) {
+    return run_call(e, &(vit_call){.who = "neighbours_host", .place = VIT_AT_HOST, .in_kind = VIT_IN_F32, .images = images, .n = n,
+                                    .out_kind = VIT_OUT_NEIGHBOURS, .spec = spec, .rows = (float *const *)out});
+}
+
+int vit_engine_neighbours_host_u8(vit_engine *e, const unsigned char *const *images, int n, const float *mean, const float *std,
+                                  const vit_neighbours_spec *spec, int *const *out) {
+    return run_call(e, &(vit_call){.who = "neighbours_host_u8", .place = VIT_AT_HOST, .in_kind = VIT_IN_U8, .images = images, .n = n,
+                                    .mean = mean, .std = std, .out_kind = VIT_OUT_NEIGHBOURS, .spec = spec, .rows = (float *const *)out});
+}
+
+int vit_engine_neighbours_host_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp,
+                                      const vit_neighbours_spec *spec, int *const *out) {
+    return run_call(e, &(vit_call){.who = "neighbours_host_images", .place = VIT_AT_HOST, .in_kind = VIT_IN_IMAGES, .images = images, .n = n,
+                                    .pp = pp, .out_kind = VIT_OUT_NEIGHBOURS, .spec = spec, .rows = (float *const *)out});
 }
 
 int vit_engine_handover_stats(vit_engine *e, long *taken, long *recomputed) {
