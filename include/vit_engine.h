@@ -628,8 +628,8 @@ int vit_engine_read_head_operand(vit_engine *e, float *dst, int rows);
  * VIT_ERR_STATE: no dense head set.  VIT_ERR_ARG (the engine stays usable, nothing was enqueued): NULL pointers, n <= 0, an unknown
  * kind, reserved != 0, an out_h or out_w that is not 0 (GRID) or, with 0 standing for img_size, each on its own, outside 1..4096
  * (LABELS), and what the matching forward refuses.
- * Not covered: depth heads (class-token concatenation and bins), sliding-window inference, mapping the labels back through
- * Resize / CenterCrop -- the labels are those of the img_size x img_size crop the engine saw.
+ * Not covered: sliding-window inference, mapping the labels back through Resize / CenterCrop -- the labels are those of the
+ * img_size x img_size crop the engine saw.  Depth heads are a head of their own: vit_engine_set_depth_head below.
  */
 typedef struct {
     int num_layers;            /* 1..VIT_MAX_TAPS */
@@ -640,14 +640,15 @@ typedef struct {
 } vit_dense_head_spec;
 int vit_engine_set_dense_head(vit_engine *e, const vit_dense_head_spec *spec, const float *weight, const float *bias);
 
-enum { VIT_DENSE_LABELS = 0, VIT_DENSE_GRID = 1 };
+enum { VIT_DENSE_LABELS = 0, VIT_DENSE_GRID = 1, VIT_DENSE_DEPTH = 3 /* the depth head's rows, below; 2 is unassigned */ };
 typedef struct {
     int kind;          /* VIT_DENSE_* */
-    int out_h, out_w;  /* LABELS: 0 = img_size, else 1..4096; GRID: must be 0 */
+    int out_h, out_w;  /* LABELS, DEPTH: 0 = img_size, else 1..4096; GRID: must be 0 */
     int reserved;      /* must be 0 */
 } vit_dense_spec;
 
-/* bytes per output row: out_h * out_w (LABELS) or num_classes * g * g * 4 (GRID); 0 on a bad spec or without a dense head */
+/* bytes per output row: out_h * out_w (LABELS), num_classes * g * g * 4 (GRID) or out_h * out_w * 4 (DEPTH); 0 on a bad spec or
+ * without the head the kind needs */
 size_t vit_engine_dense_row_bytes(const vit_engine *e, const vit_dense_spec *spec);
 int vit_engine_dense_device(vit_engine *e, const float *d_images, int n, const vit_dense_spec *spec, void *d_out, void *stream);
 int vit_engine_dense_host(vit_engine *e, const float *const *images, int n, const vit_dense_spec *spec, void *const *out);
@@ -659,6 +660,48 @@ int vit_engine_dense_device_images(vit_engine *e, const vit_image_u8 *images, in
                                    void *d_out, void *stream);
 int vit_engine_dense_host_images(vit_engine *e, const vit_image_u8 *images, int n, const vit_preproc *pp, const vit_dense_spec *spec,
                                  void *const *out);
+
+/*
+ * Linear depth heads: metric depth per pixel from the patch and class tokens, on the device -- the published depth heads of DINOv2
+ * (`dinov2_vit{s,b,l,g}14_ld` on one layer, `_ld4` on four: BNHead with classify, norm_strategy "linear", bins_strategy "UD",
+ * upsample 4, align_corners False, no BatchNorm).  The head is engine state of its own, independent of the classifier and the dense
+ * head: setting or removing one never disturbs another, and VIT_DENSE_LABELS / VIT_DENSE_GRID never look at it.
+ *
+ * With K = num_layers, D = embed_dim, B = num_bins, u = upsample, U = u * g, A_j the [P][D] rows of an intermediate call of
+ * VIT_TAP_PATCHES with the head's norm for layer layers[j] and c_j [D] that layer's row of VIT_TAP_CLS with the same norm: weight
+ * [B][C] row-major as the checkpoint's conv_depth.weight, uploaded as it is -- with class_token C = K * 2D, layer j owning the columns
+ * j*2D .. j*2D+D-1 (patch) and j*2D+D .. (j+1)*2D-1 (class); without it C = K * D; bias [B]; centres [B] the bin centres, NULL:
+ * torch.linspace(min_depth, max_depth, B) made in double and rounded once (finite values of the caller's otherwise: "SID" bins).
+ *     logits[p] = bias + sum_j A_j[p] . Wpatch_j^T        the GEMM chain of the dense head (arith = 0, ldw = C), per patch
+ *     z         = sum_j c_j . Wclass_j^T                  the same chain over the class rows, M = images, a zero bias; per image
+ * Upstream concatenates [patch map | class token broadcast], upsamples the FEATURES and then applies the conv; bilinear weights sum
+ * to 1 and the conv is linear, so conv and upsampling commute and the class token's share is the per-image bias z.  The rest --
+ * cell = logits + z, the upsampling of the 256 bin maps to U x U, relu + 0.1, the normalised expectation over the centres, the clamp
+ * and the resize to out_h x out_w -- is vithip_dense_depth_f32 (vit_hip_kernels.h states the arithmetic and the order), which stores
+ * no bin value at the upsampled resolution.
+ *
+ * vit_engine_set_depth_head: the rules of vit_engine_set_dense_head, rule for rule (device sync, graph dropped, new allocations
+ * before the old ones are freed, VIT_ERR_NOMEM keeps the previous depth head, spec == NULL with NULL arrays removes it, every weight
+ * install removes it, copies do not carry it).  VIT_ERR_ARG, nothing changed: what set_dense_head refuses, num_bins outside 2..256,
+ * upsample outside 1..8, class_token other than 0 / 1, min_depth / max_depth not finite or not 0 < min_depth < max_depth, a
+ * non-finite centre.
+ * Output: the six vit_engine_dense_* calls with kind VIT_DENSE_DEPTH: rows of fp32 [out_h][out_w] (4-byte aligned on the device
+ * path), out_h = out_w = 0 meaning img_size, else 1..4096 each; VIT_ERR_STATE without a depth head.  Walk, lanes, pruning, isolation
+ * of non-finite images and profiling stages are those of the dense calls (the class tap counts to VIT_STAGE_LN, the class GEMM to
+ * VIT_STAGE_HEAD, the depth kernels to VIT_STAGE_SOFTMAX).
+ * Not covered: norm_strategy "softmax", DPT heads, sliding-window and flip test-time augmentation.
+ */
+typedef struct {
+    int num_layers;            /* 1..VIT_MAX_TAPS */
+    int layers[VIT_MAX_TAPS];  /* strictly increasing, 0 <= l < depth, as in vit_intermediate_spec */
+    int norm;                  /* 1: final LayerNorm on every tapped layer's patch and class rows, 0: raw stream */
+    int num_bins;              /* 2..256 */
+    int upsample;              /* 1..8: the factor of stage 1 (DINOv2: 4) */
+    int class_token;           /* 1: weight has the class token's columns behind each layer's patch columns (DINOv2), 0: patch columns only */
+    float min_depth, max_depth; /* finite, 0 < min_depth < max_depth: the clamp, and the range of the default centres */
+    int reserved;              /* must be 0 */
+} vit_depth_head_spec;
+int vit_engine_set_depth_head(vit_engine *e, const vit_depth_head_spec *spec, const float *weight, const float *bias, const float *centres);
 
 /*
  * Attention-pool heads (MAP): the pooling of SigLIP, SigLIP 2 and PaliGemma's tower (transformers' SiglipMultiheadAttentionPoolingHead)

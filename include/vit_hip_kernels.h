@@ -848,6 +848,33 @@ int vithip_dense_upsample_argmax_f32(vithip_stream_t stream, const float *logits
 int vithip_dense_grid_f32(vithip_stream_t stream, const float *logits, int ld_logits, size_t image_stride, float *out,
                           size_t out_image_stride, int images, int g, int classes);
 
+/*
+ * The tail of a linear depth head (csrc/vit_depth.hip; DINOv2's BNHead for depth with classify, norm_strategy "linear", upsample u,
+ * align_corners=False): per-pixel depth from the logits of a g x g patch grid.  logits as above, `bins` floats per row; cls_logits
+ * (may be NULL: absent) per image ld_cls floats apart `bins` floats z, the class token's share of the 1x1 conv; centres [bins].
+ * out: per image (out_image_stride FLOATS apart) out_h x out_w floats.  In fp32, nothing contracted, every product and sum rounded:
+ *     cell[p][b] = logits[p][b] + z[b]                                                    (one rounding; without z: the logit)
+ *   stage 1, on the U x U map, U = u * g, per axis the expressions of vithip_dense_upsample_argmax_f32 (scale, src, i0, i1, l0, l1):
+ *     v_b = l0y * (l0x * c00 + l1x * c01) + l1y * (l0x * c10 + l1x * c11)                  c_rc = cell[i_r(y) * g + i_c(x)][b]
+ *     r_b = (v_b < 0 ? 0 : v_b) + 0.1f                                                     (a NaN stays a NaN)
+ *     s = sum_b r_b,  t = sum_b r_b * centre[b]     both from 0.0f over b = 0, 1, .., bins - 1 in that order, one add per bin each
+ *     d = t / s (correctly rounded), then d < min_depth ? min_depth : d > max_depth ? max_depth : d
+ *   stage 2: out[y][x] = l0y * (l0x * d00 + l1x * d01) + l1y * (l0x * d10 + l1x * d11), the same expressions from U x U to out_h x out_w.
+ * No bin value of the upsampled map is stored anywhere: a lane keeps (s, t) of a u x u block of up-pixels in registers and reads the
+ * block's four cells from LDS once per bin.  scratch: [images][U * U] floats of the caller's for the depth map between the stages;
+ * with out_h == out_w == U stage 2 is the identity, stage 1 stores into out and scratch may be NULL.  The launcher neither allocates
+ * nor synchronises.  Any g >= 1 (g * g an int), bins in 2..256, u in 1..8, out_h and out_w in 1..4096 runs.  Only the out_h * out_w
+ * floats of each image are written; out needs 4-byte alignment.  No atomics; results do not depend on the grid; an image's depth
+ * depends on that image's logits and z alone.
+ * hipErrorInvalidValue, nothing launched and no HIP call made: NULL logits, centres or out (or scratch where it is needed), images < 1,
+ * g < 1, bins outside 2..256, upsample outside 1..8, out_h or out_w outside 1..4096, ld_logits < bins, ld_cls < bins with cls_logits,
+ * image_stride < (P - 1) * ld_logits + bins, out_image_stride < out_h * out_w, min_depth or max_depth not finite or not
+ * 0 < min_depth < max_depth.
+ */
+int vithip_dense_depth_f32(vithip_stream_t stream, const float *logits, int ld_logits, size_t image_stride, const float *cls_logits, int ld_cls,
+                           const float *centres, float *out, size_t out_image_stride, float *scratch, int images, int g, int bins, int upsample,
+                           float min_depth, float max_depth, int out_h, int out_w);
+
 #ifdef __cplusplus
 }
 #endif

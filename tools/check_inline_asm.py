@@ -38,6 +38,9 @@ PER_FILE_FLAGS = {  # = FLAGS_* of the Makefile
     "vit_pos_resample": ["-ffp-contract=off"],
     "vit_swiglu": ["-ffp-contract=off"],
     "vit_dense": ["-ffp-contract=off"],
+    "vit_depth": ["-ffp-contract=off"],
+    "vit_map_head": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "vit_rope": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 VM_STORE = re.compile(r"^(global|buffer|flat|scratch)_store_")

@@ -135,7 +135,12 @@ class CDenseSpec(C.Structure):  # vit_dense_spec
     _fields_ = [("kind", C.c_int), ("out_h", C.c_int), ("out_w", C.c_int), ("reserved", C.c_int)]
 
 
-DENSE_KINDS = {"labels": 0, "grid": 1}  # VIT_DENSE_*
+class CDepthHeadSpec(C.Structure):  # vit_depth_head_spec
+    _fields_ = [("num_layers", C.c_int), ("layers", C.c_int * VIT_MAX_TAPS), ("norm", C.c_int), ("num_bins", C.c_int), ("upsample", C.c_int),
+                ("class_token", C.c_int), ("min_depth", C.c_float), ("max_depth", C.c_float), ("reserved", C.c_int)]
+
+
+DENSE_KINDS = {"labels": 0, "grid": 1, "depth": 3}  # VIT_DENSE_* (2 is unassigned)
 DENSE_NO_LABEL = 255  # the label of a pixel no class was a candidate for (every value NaN)
 
 
@@ -152,8 +157,22 @@ def dense_head_spec(layers, norm=True, num_classes: int = 0, depth: Optional[int
     return spec
 
 
+def depth_head_spec(layers, norm=False, num_bins: int = 0, upsample: int = 4, class_token=True, min_depth: float = 0.001,
+                    max_depth: float = 10.0, depth: Optional[int] = None, reserved: int = 0) -> CDepthHeadSpec:
+    """layers as in dense_head_spec; everything is passed through unchecked for the C side to judge."""
+    ls = [int(l) for l in (layers if hasattr(layers, "__iter__") else [layers])]
+    if depth is not None:
+        ls = [l + depth if l < 0 else l for l in ls]
+    spec = CDepthHeadSpec(len(ls))
+    for j, l in enumerate(ls[:VIT_MAX_TAPS]):
+        spec.layers[j] = l
+    spec.norm, spec.num_bins, spec.upsample, spec.class_token, spec.reserved = int(norm), int(num_bins), int(upsample), int(class_token), int(reserved)
+    spec.min_depth, spec.max_depth = float(min_depth), float(max_depth)
+    return spec
+
+
 def dense_spec(kind="labels", out_size=None, reserved: int = 0) -> CDenseSpec:
-    """kind: "labels" | "grid" (or a raw VIT_DENSE_* integer); out_size: None (img_size x img_size), an int (square) or (out_h,
+    """kind: "labels" | "grid" | "depth" (or a raw VIT_DENSE_* integer); out_size: None (img_size x img_size), an int (square) or (out_h,
     out_w); passed through unchecked for the C side to judge."""
     k = DENSE_KINDS[kind] if isinstance(kind, str) else int(kind)
     h, w = (0, 0) if out_size is None else (out_size, out_size) if isinstance(out_size, (int, np.integer)) else out_size
@@ -425,6 +444,10 @@ def lib() -> C.CDLL:
             L.vit_dense_head_fold_batchnorm.argtypes = [f32p, f32p, C.c_int, C.c_int, f32p, f32p, f32p, f32p, C.c_double]
             L.vithip_dense_upsample_argmax_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_int] * 5
             L.vithip_dense_grid_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_int] * 3
+        if hasattr(L, "vit_engine_set_depth_head"):  # an earlier build has no depth heads
+            L.vit_engine_set_depth_head.argtypes = [C.c_void_p, C.POINTER(CDepthHeadSpec), f32p, f32p, f32p]
+            L.vithip_dense_depth_f32.argtypes = ([C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                  C.c_void_p] + [C.c_int] * 4 + [C.c_float] * 2 + [C.c_int] * 2)
         L.vit_engine_read_logits.argtypes = [C.c_void_p, f32p, C.c_int]
         L.vit_engine_sync.argtypes = [C.c_void_p]
         L.vit_engine_get_stage_times.argtypes = [C.c_void_p, C.POINTER(CStageTimes)]
@@ -1680,6 +1703,39 @@ def dense_upsample_argmax(logits, out_h: int, out_w: int, ld_logits: Optional[in
     return np.ascontiguousarray(dO.window()).view(np.uint8)[:, :out_h * out_w].reshape(n, out_h, out_w).copy()
 
 
+def dense_depth_raw(logits_ptr, ld_logits: int, image_stride: int, cls_ptr, ld_cls: int, centres_ptr, out_ptr, out_image_stride: int,
+                    scratch_ptr, images: int, g: int, bins: int, upsample: int, min_depth: float, max_depth: float, out_h: int, out_w: int) -> int:
+    """vithip_dense_depth_f32 on raw addresses, every argument passed through unchecked: returns the HIP error code."""
+    return int(lib().vithip_dense_depth_f32(None, logits_ptr, int(ld_logits), int(image_stride), cls_ptr, int(ld_cls), centres_ptr, out_ptr,
+                                            int(out_image_stride), scratch_ptr, int(images), int(g), int(bins), int(upsample), float(min_depth),
+                                            float(max_depth), int(out_h), int(out_w)))
+
+
+def dense_depth(logits, centres, upsample: int, out_h: int, out_w: int, cls_logits=None, min_depth: float = 0.001, max_depth: float = 10.0,
+                ld_logits: Optional[int] = None, image_rows: Optional[int] = None, out_ld: Optional[int] = None, pad_value: float = 0.0,
+                frames=None, out: Optional[dict] = None) -> np.ndarray:
+    """vithip_dense_depth_f32: logits [n][g * g][bins] (+ cls_logits [n][bins]) -> depth fp32 [n][out_h][out_w].  ld_logits, image_rows,
+    pad_value, frames and `out` as in dense_upsample_argmax; out_ld: floats from one image's depth to the next."""
+    logits = _as_f32(logits)
+    n, P, bins = logits.shape
+    g = int(round(P ** 0.5))
+    assert g * g == P, P
+    rows = P if image_rows is None else int(image_rows)
+    src = np.full((n, rows, bins), pad_value, np.float32)
+    src[:, :P] = logits
+    F = frames or _Plain
+    dL = F.framed(src.reshape(n * rows, bins), ld_logits)
+    dO = F.out_frame(n, out_h * out_w, out_ld)
+    dZ = None if cls_logits is None else DeviceArray.from_numpy(_as_f32(cls_logits).reshape(n, bins))
+    dC = DeviceArray.from_numpy(_as_f32(centres).reshape(bins))
+    U = upsample * g
+    dS = DeviceArray((n, U, U))
+    _note(out, logits=dL, depth=dO)
+    hip_check(dense_depth_raw(dL.ptr, dL.ld, rows * dL.ld, dZ.ptr if dZ else None, bins, dC.ptr, dO.ptr, dO.ld, dS.ptr, n, g, bins, upsample,
+                              min_depth, max_depth, out_h, out_w), "vithip_dense_depth_f32")
+    return np.ascontiguousarray(dO.window()).reshape(n, out_h, out_w).copy()
+
+
 def dense_grid(logits) -> np.ndarray:
     """vithip_dense_grid_f32: logits [n][g * g][classes] -> fp32 [n][classes][g][g], the transpose."""
     logits = _as_f32(logits)
@@ -2177,6 +2233,31 @@ class Engine:
         self._check(lib().vit_engine_set_dense_head(self._h, C.byref(spec), None if w is None else w.ctypes.data_as(f32p),
                                                     None if b is None else b.ctypes.data_as(f32p)), "vit_engine_set_dense_head")
 
+    # ---- linear depth heads (vit_engine_set_depth_head): dense(imgs, "depth") ----
+    def set_depth_head(self, weight, bias, layers, norm=False, upsample: int = 4, class_token=True, min_depth: float = 0.001,
+                       max_depth: float = 10.0, centres=None, reserved: int = 0) -> None:
+        """A linear depth head for dense(kind="depth"): weight [num_bins][C] as the checkpoint's conv_depth.weight (its trailing 1 x 1
+        dropped), C = len(layers) * (2 if class_token else 1) * embed_dim, per layer the patch columns then the class token's; bias
+        [num_bins] (num_bins is taken from it); centres: None for linspace(min_depth, max_depth, num_bins), or [num_bins] values.
+        Independent of the dense and classifier heads.  Every weight install removes it: call this again behind it.
+        DINOv2 `_ld`: layers=(-1,); `_ld4`: the four out_indices of the backbone; NYU max_depth=10, KITTI max_depth=80."""
+        w = None if weight is None else _as_f32(weight)
+        b = None if bias is None else _as_f32(bias)
+        cen = None if centres is None else _as_f32(centres)
+        spec = depth_head_spec(layers, norm, 0 if b is None else b.size, upsample, class_token, min_depth, max_depth, self.cfg.depth, reserved)
+        F = spec.num_layers * (2 if class_token else 1) * self.cfg.embed_dim
+        if w is not None and b is not None and w.size != b.size * F:
+            raise VitError(f"set_depth_head: weight has {w.size} floats, {b.size} bins over {spec.num_layers} layers need {b.size} x {F}")
+        if cen is not None and b is not None and cen.size != b.size:
+            raise VitError(f"set_depth_head: {cen.size} centres for {b.size} bins")
+        self._check(lib().vit_engine_set_depth_head(self._h, C.byref(spec), None if w is None else w.ctypes.data_as(f32p),
+                                                    None if b is None else b.ctypes.data_as(f32p),
+                                                    None if cen is None else cen.ctypes.data_as(f32p)), "vit_engine_set_depth_head")
+
+    def reset_depth_head(self) -> None:
+        """Remove the depth head (vit_engine_set_depth_head with a NULL spec)."""
+        self._check(lib().vit_engine_set_depth_head(self._h, None, None, None, None), "vit_engine_set_depth_head")
+
     # ---- attention-pool heads (vit_engine_set_map_head): features(imgs, "map") ----
     def set_map_head(self, spec: "CMapHeadSpec", weights: dict) -> None:
         """The attention-pool head (SigLIP's pooling head, timm global_pool='map') behind features(imgs, "map"): spec from
@@ -2195,23 +2276,24 @@ class Engine:
         self._check(lib().vit_engine_set_dense_head(self._h, None, None, None), "vit_engine_set_dense_head")
 
     def dense_row_bytes(self, kind="labels", out_size=None) -> int:
-        """Bytes per output row of a dense call; 0 on a bad spec or without a dense head."""
+        """Bytes per output row of a dense call; 0 on a bad spec or without the head the kind needs (kind "depth": the depth head)."""
         return int(lib().vit_engine_dense_row_bytes(self._h, C.byref(dense_spec(kind, out_size))))
 
     def dense_shape(self, n: int, spec) -> tuple:
-        """Shape of the rows n images give: (n, out_h, out_w) uint8 labels or (n, num_classes, g, g) fp32 logits.  A spec the C side
+        """Shape of the rows n images give: (n, out_h, out_w) uint8 labels or fp32 depth, or (n, num_classes, g, g) fp32 logits.  A spec the C side
         refuses still gets rows (the call must see its own arguments and say what is wrong)."""
         g = self.cfg.img_size // self.cfg.patch_size
         nbytes = int(lib().vit_engine_dense_row_bytes(self._h, C.byref(spec)))
-        if spec.kind == DENSE_KINDS["labels"]:
+        if spec.kind in (DENSE_KINDS["labels"], DENSE_KINDS["depth"]):
             h, w = spec.out_h or self.cfg.img_size, spec.out_w or self.cfg.img_size
-            return (n, h, w) if nbytes == h * w else (n, 1, 1)
+            return (n, h, w) if nbytes == h * w * (4 if spec.kind == DENSE_KINDS["depth"] else 1) else (n, 1, 1)
         return (n, nbytes // (4 * g * g), g, g) if nbytes else (n, 1, 1, 1)
 
     def dense(self, images: np.ndarray, kind="labels", out_size=None) -> np.ndarray:
         """Host path: per-image pointers in, per-image rows out -- kind "labels": uint8 [n][out_h][out_w], the argmax over the
         classes of the head's logits resized bilinearly (align_corners=False) to out_size (None: img_size; an int or (h, w));
-        kind "grid": fp32 [n][num_classes][g][g], the logits themselves."""
+        kind "grid": fp32 [n][num_classes][g][g], the logits themselves; kind "depth": fp32 [n][out_h][out_w], the depth head's rows
+        (set_depth_head; the dense head plays no part)."""
         return self._host("dense", "", images, dense=dense_spec(kind, out_size))
 
     def dense_u8(self, images: np.ndarray, kind="labels", out_size=None, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:

@@ -102,6 +102,12 @@ typedef struct { vit_head_spec spec; size_t in; vit_gemm_ops ops; float *operand
  * 1x1 conv's W [num_classes][num_layers * D] (a zeroed tail pad behind it) and bias, a zero bias for the chain's later GEMMs, the
  * patch rows of the layer just tapped [max_batch][P][D] and the logits [max_batch][P][num_classes]: five allocations of its own. */
 typedef struct { vit_dense_head_spec spec; float *W, *bias, *zero_bias, *rows, *logits; } vit_dense_head;
+/* The depth head in force (vit_engine_set_depth_head; num_layers == 0: none), independent of the dense head: the checked spec, the
+ * 1x1 conv's W [num_bins][C] as the checkpoint has it (C = num_layers * (1 + class_token) * D; a zeroed tail pad behind it) and bias,
+ * a zero bias, the patch rows [max_batch][P][D] and class rows [max_batch][D] of the layer just tapped, the logits
+ * [max_batch][P][num_bins], the class token's share z [max_batch][num_bins], the bin centres and the depth map between the two
+ * stages of vithip_dense_depth_f32 [max_batch][U * U]: nine allocations of its own. */
+typedef struct { vit_depth_head_spec spec; float *W, *bias, *zero_bias, *rows, *cls_rows, *logits, *z, *centres, *dmap; } vit_depth_head;
 /* The attention-pool head in force (vit_engine_set_map_head; blob == NULL: none): the checked spec, the first key row, and two
  * allocations of its own -- blob, the operands [A | Wv | bv | Wo | bo | ln_g | ln_b | fc1 | fc2] with a zeroed tail pad, and rows,
  * [pooled [B][D] | LayerNorm rows [B][D] | hidden rows [B][hidden] | the pooling workspace of every lane], B = max_batch. */
@@ -174,6 +180,7 @@ struct vit_engine {
     /* the one classifier head: the checkpoint's own (restore_own_head) or a caller's (vit_engine_set_head); no stage tells them apart */
     vit_head head;
     vit_dense_head dense;
+    vit_depth_head depth;
     vit_map_head map;
     vit_gallery gallery;         /* architecture-like state, kept across installs */
     /* host-pointer path: double-buffered staging so that gather + H2D of piece i+1 overlap compute of piece i */
@@ -493,6 +500,13 @@ static void release_dense_head(vit_dense_head *h) {
     memset(h, 0, sizeof(*h));
 }
 
+/* ... and so do the depth head's */
+static void release_depth_head(vit_depth_head *h) {
+    vithip_free(h->W); vithip_free(h->bias); vithip_free(h->zero_bias); vithip_free(h->rows); vithip_free(h->cls_rows);
+    vithip_free(h->logits); vithip_free(h->z); vithip_free(h->centres); vithip_free(h->dmap);
+    memset(h, 0, sizeof(*h));
+}
+
 /* ... and so do the attention-pool head's */
 static void release_map_head(vit_map_head *h) {
     vithip_free(h->blob); vithip_free(h->rows);
@@ -516,6 +530,7 @@ void vit_engine_destroy(vit_engine *e) {
     vithip_free(e->z); vithip_free(e->logits);
     release_head(&e->head);
     release_dense_head(&e->dense);
+    release_depth_head(&e->depth);
     release_map_head(&e->map);
     release_gallery(&e->gallery);
     vithip_free(e->pre_g); /* one allocation: gamma, beta behind it */
@@ -916,6 +931,7 @@ static int finish_install(vit_engine *e) {
     const int rc = resolve_operands(e);
     restore_own_head(e);
     release_dense_head(&e->dense); /* a caller's head like the classifier's: every install removes it */
+    release_depth_head(&e->depth);
     release_map_head(&e->map);
     release_pre_norm(e); /* checkpoint data like a caller's head: every install removes it (the epsilon, architecture, stays) */
     if (rc) return rc;
@@ -1655,13 +1671,14 @@ static int stage_tap(chunk_ctx *c, const vit_output *out, int l) {
  * has just left them (the tap of an intermediate call of VIT_TAP_PATCHES) into the head's scratch, then the GEMM of the chain over
  * them -- the first writes bias + A_0 . W_0^T, the later ones add A_j . W_j^T in place, W_j the column block j of the head's W.
  * fp32 MFMA on both dtypes.  The spec of the call (out) has no say in it: the layers are the head's. */
+static int stage_depth_tap(chunk_ctx *c, int l);
 static int stage_dense_tap(chunk_ctx *c, const vit_output *out, int l) {
     vit_engine *e = c->e;
     const vit_dense_head *h = &e->dense;
     const size_t P = (size_t)e->patches, D = (size_t)c->D;
     const int NC = h->spec.num_classes, K = h->spec.num_layers;
     int j = 0;
-    (void)out;
+    if (out->dense.kind == VIT_DENSE_DEPTH) return stage_depth_tap(c, l);
     while (j < K && h->spec.layers[j] != l) ++j;
     if (j == K) return VIT_OK;
     for (int k = 0; k < c->L; ++k) {
@@ -1681,6 +1698,41 @@ static int stage_dense_tap(chunk_ctx *c, const vit_output *out, int l) {
     return VIT_OK;
 }
 
+/* A depth call behind encoder layer l = the depth head's layers[j]: as above with the depth head's own scratch, W as the checkpoint
+ * has it (layer j owns the columns j * S .., S = D or 2D with the class token: patch columns first) -- and, with the class token, the
+ * class rows of the same layer (the tap of VIT_TAP_CLS) and their GEMM, M = images, into z: a chain of its own without a bias. */
+static int stage_depth_tap(chunk_ctx *c, int l) {
+    vit_engine *e = c->e;
+    const vit_depth_head *h = &e->depth;
+    const size_t P = (size_t)e->patches, D = (size_t)c->D;
+    const int NB = h->spec.num_bins, K = h->spec.num_layers, S = (1 + h->spec.class_token) * c->D;
+    int j = 0;
+    while (j < K && h->spec.layers[j] != l) ++j;
+    if (j == K) return VIT_OK;
+    for (int k = 0; k < c->L; ++k) {
+        const vit_lane *ln = &c->lane[k];
+        HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_LN));
+        RUN(tap_block(c, ln, h->rows + (size_t)ln->off * P * D, P * D, h->spec.norm, VITHIP_TAP_PATCHES));
+        if (h->spec.class_token) RUN(tap_block(c, ln, h->cls_rows + (size_t)ln->off * D, D, h->spec.norm, VITHIP_TAP_CLS));
+        HIP_TRY(e, stage_end(e, ln->s));
+    }
+    for (int k = 0; k < c->L; ++k) {
+        const vit_lane *ln = &c->lane[k];
+        const gemm_desc g = {.stage = VIT_STAGE_HEAD, .A = h->rows + (size_t)ln->off * P * D, .lda = c->D,
+                             .ops = {.W = h->W + (size_t)j * S, .bias = j ? h->zero_bias : h->bias}, .ldw = K * S,
+                             .C = h->logits + (size_t)ln->off * P * NB, .ldc = NB, .M = ln->n * (int)P, .N = NB, .K = c->D,
+                             .role = j ? VITHIP_EPI_BIAS_RESIDUAL : VITHIP_EPI_BIAS};
+        RUN(gemm(e, ln->s, &g, NULL));
+        if (!h->spec.class_token) continue;
+        const gemm_desc z = {.stage = VIT_STAGE_HEAD, .A = h->cls_rows + (size_t)ln->off * D, .lda = c->D,
+                             .ops = {.W = h->W + (size_t)j * S + D, .bias = h->zero_bias}, .ldw = K * S,
+                             .C = h->z + (size_t)ln->off * NB, .ldc = NB, .M = ln->n, .N = NB, .K = c->D,
+                             .role = j ? VITHIP_EPI_BIAS_RESIDUAL : VITHIP_EPI_BIAS};
+        RUN(gemm(e, ln->s, &z, NULL));
+    }
+    return VIT_OK;
+}
+
 /* ... and behind the deepest of them: the lane's logits [n][P][classes] become its images' rows -- the labels of the upsampled maps
  * (nothing of full resolution but the labels is written) or the channel-major grid. */
 static int stage_dense_out(chunk_ctx *c, const vit_output *out) {
@@ -1688,6 +1740,21 @@ static int stage_dense_out(chunk_ctx *c, const vit_output *out) {
     const vit_dense_head *h = &e->dense;
     const int g = e->cfg.img_size / VIT_PATCH_SIZE(&e->cfg), NC = h->spec.num_classes;
     const size_t P = (size_t)e->patches, row = c->row;
+    if (out->dense.kind == VIT_DENSE_DEPTH) { /* the depth head's logits and z: fp32 depth rows, nothing of 256 bins at U x U stored */
+        const vit_depth_head *d = &e->depth;
+        const int NB = d->spec.num_bins, u = d->spec.upsample;
+        for (int k = 0; k < c->L; ++k) {
+            const vit_lane *ln = &c->lane[k];
+            HIP_TRY(e, stage_begin(e, ln->s, VIT_STAGE_SOFTMAX));
+            HIP_TRY(e, vithip_dense_depth_f32(ln->s, d->logits + (size_t)ln->off * P * NB, NB, P * NB,
+                                              d->spec.class_token ? d->z + (size_t)ln->off * NB : NULL, NB, d->centres,
+                                              (float *)((unsigned char *)out->dst + (size_t)ln->off * row), row / sizeof(float),
+                                              d->dmap + (size_t)ln->off * (size_t)(u * g) * (size_t)(u * g), ln->n, g, NB, u, d->spec.min_depth,
+                                              d->spec.max_depth, out->dense.out_h, out->dense.out_w));
+            HIP_TRY(e, stage_end(e, ln->s));
+        }
+        return VIT_OK;
+    }
     for (int k = 0; k < c->L; ++k) {
         const vit_lane *ln = &c->lane[k];
         const float *logits = h->logits + (size_t)ln->off * P * NC;
@@ -1847,14 +1914,17 @@ static size_t topk_row_bytes(const vit_engine *e, const vit_output *out) { /* 2k
 
 /* The one fault that is the engine's state, not the caller's argument: make_output knows it by its address. */
 static const char NO_DENSE_HEAD[] = "%s before vit_engine_set_dense_head()";
+static const char NO_DEPTH_HEAD[] = "%s: kind VIT_DENSE_DEPTH before vit_engine_set_depth_head()";
 /* The dense spec is resolved against the model too (out_h / out_w: 0 becomes img_size).  The head itself was checked when it was set. */
 static const char *dense_check(const vit_engine *e, const void *caller, vit_output *out, int arg[2]) {
     const vit_dense_spec *spec = (const vit_dense_spec *)caller;
     vit_dense_spec *res = &out->dense;
     if (!spec) return "%s: the dense spec is required";
-    if (!e->dense.spec.num_layers) return NO_DENSE_HEAD;
+    /* the head the kind needs: the depth head for DEPTH, which the dense head has no say in; the dense head for every other kind */
+    if (spec->kind == VIT_DENSE_DEPTH ? !e->depth.spec.num_layers : !e->dense.spec.num_layers)
+        return spec->kind == VIT_DENSE_DEPTH ? NO_DEPTH_HEAD : NO_DENSE_HEAD;
     arg[0] = spec->kind;
-    if (spec->kind != VIT_DENSE_LABELS && spec->kind != VIT_DENSE_GRID) return "%s: unknown dense kind %d";
+    if (spec->kind != VIT_DENSE_LABELS && spec->kind != VIT_DENSE_GRID && spec->kind != VIT_DENSE_DEPTH) return "%s: unknown dense kind %d";
     arg[0] = spec->reserved;
     if (spec->reserved != 0) return "%s: vit_dense_spec.reserved must be 0 (got %d)";
     res->kind = spec->kind;
@@ -1869,10 +1939,11 @@ static const char *dense_check(const vit_engine *e, const void *caller, vit_outp
 /* labels are a byte per pixel, the grid classes * P floats: the one kind whose row is not a whole number of floats */
 static size_t dense_row_bytes(const vit_engine *e, const vit_output *out) {
     if (out->dense.kind == VIT_DENSE_LABELS) return (size_t)out->dense.out_h * (size_t)out->dense.out_w;
+    if (out->dense.kind == VIT_DENSE_DEPTH) return (size_t)out->dense.out_h * (size_t)out->dense.out_w * sizeof(float);
     return (size_t)e->dense.spec.num_classes * (size_t)e->patches * sizeof(float);
 }
 static int dense_last_layer(const vit_engine *e, const vit_output *out) { /* the deepest layer of the head */
-    (void)out;
+    if (out->dense.kind == VIT_DENSE_DEPTH) return e->depth.spec.layers[e->depth.spec.num_layers - 1];
     return e->dense.spec.layers[e->dense.spec.num_layers - 1];
 }
 
@@ -1977,7 +2048,7 @@ static const char *output_fault(const vit_engine *e, int kind, const void *spec,
 static int make_output(vit_engine *e, const char *who, int kind, const void *spec, float *dst, int *label, float *prob, vit_output *out) {
     int arg[2];
     const char *fault = output_fault(e, kind, spec, out, arg);
-    if (fault) return fail(e, fault == NO_DENSE_HEAD || fault == NO_GALLERY ? VIT_ERR_STATE : VIT_ERR_ARG, fault, who, arg[0], arg[1]);
+    if (fault) return fail(e, fault == NO_DENSE_HEAD || fault == NO_DEPTH_HEAD || fault == NO_GALLERY ? VIT_ERR_STATE : VIT_ERR_ARG, fault, who, arg[0], arg[1]);
     if (kind == VIT_OUT_ATTENTION && e->attn_bias[e->cfg.depth - 1]) /* the class-row kernel takes no bias: a wrong row is not an answer */
         return fail(e, VIT_ERR_STATE, "%s: the last layer has an attention bias (vit_engine_set_attention_bias), which the class-attention kernel does not take", who);
     out->dst = dst; out->label = label; out->prob = prob;
@@ -2928,6 +2999,97 @@ int vit_engine_set_dense_head(vit_engine *e, const vit_dense_head_spec *spec, co
     for (int j = 0; j < spec->num_layers; ++j) h.spec.layers[j] = spec->layers[j];
     h.spec.norm = spec->norm; h.spec.num_classes = spec->num_classes;
     e->dense = h;
+    return VIT_OK;
+}
+
+/* The depth head spec, checked against the model: NULL, or what is wrong as a format for (arg[0], arg[1]). */
+static const char *depth_head_spec_fault(const vit_engine *e, const vit_depth_head_spec *spec, int arg[2]) {
+    arg[0] = spec->num_layers; arg[1] = VIT_MAX_TAPS;
+    if (spec->num_layers < 1 || spec->num_layers > VIT_MAX_TAPS) return "set_depth_head: num_layers = %d must be 1..%d";
+    arg[0] = spec->norm; arg[1] = 0;
+    if (spec->norm != 0 && spec->norm != 1) return "set_depth_head: norm must be 0 or 1 (got %d)";
+    arg[0] = spec->num_bins;
+    if (spec->num_bins < 2 || spec->num_bins > 256) return "set_depth_head: num_bins = %d must be 2..256";
+    arg[0] = spec->upsample;
+    if (spec->upsample < 1 || spec->upsample > 8) return "set_depth_head: upsample = %d must be 1..8";
+    arg[0] = spec->class_token;
+    if (spec->class_token != 0 && spec->class_token != 1) return "set_depth_head: class_token must be 0 or 1 (got %d)";
+    arg[0] = spec->reserved;
+    if (spec->reserved != 0) return "set_depth_head: vit_depth_head_spec.reserved must be 0 (got %d)";
+    if (!isfinite(spec->min_depth) || !isfinite(spec->max_depth) || !(0.0f < spec->min_depth && spec->min_depth < spec->max_depth))
+        return "set_depth_head: needs finite 0 < min_depth < max_depth";
+    for (int j = 0; j < spec->num_layers; ++j) {
+        arg[0] = j; arg[1] = spec->layers[j];
+        if (spec->layers[j] < 0 || spec->layers[j] >= e->cfg.depth) return "set_depth_head: layers[%d] = %d is not a layer of the model";
+        if (j && spec->layers[j] <= spec->layers[j - 1]) return "set_depth_head: layers[%d] = %d is not above the entry before it (strictly increasing)";
+    }
+    const int g = e->cfg.img_size / VIT_PATCH_SIZE(&e->cfg);
+    arg[0] = g; arg[1] = e->patches;
+    if (g < 1 || g * g != e->patches) return "set_depth_head: needs a square grid of patches: (img_size / patch_size = %d)^2 is not the model's %d";
+    return NULL;
+}
+
+int vit_engine_set_depth_head(vit_engine *e, const vit_depth_head_spec *spec, const float *weight, const float *bias, const float *centres) {
+    if (!e) return VIT_ERR_ARG;
+    if (!spec && (weight || bias || centres)) return fail(e, VIT_ERR_ARG, "set_depth_head: a NULL spec (no depth head) takes no weight, bias or centres");
+    if (spec) {
+        int arg[2];
+        const char *fault = depth_head_spec_fault(e, spec, arg);
+        if (fault) return fail(e, VIT_ERR_ARG, fault, arg[0], arg[1]);
+        if (!weight || !bias) return fail(e, VIT_ERR_ARG, "set_depth_head: weight and bias are required with a spec");
+        for (int b = 0; centres && b < spec->num_bins; ++b)
+            if (!isfinite(centres[b])) return fail(e, VIT_ERR_ARG, "set_depth_head: centres[%d] is not finite", b);
+    }
+    if (!e->weights_loaded) return fail(e, VIT_ERR_STATE, "set_depth_head before vit_engine_load_weights()");
+    HIP_TRY(e, vithip_set_device(e->opt.device));
+    if (!spec) { /* as an install: nothing in flight, no graph with the head's buffers in its launches */
+        HIP_TRY(e, vithip_device_sync());
+        drop_graph(e);
+        release_depth_head(&e->depth);
+        return VIT_OK;
+    }
+    /* the new head first, whole; only then the old one goes */
+    const size_t D = (size_t)e->cfg.embed_dim, F = (size_t)spec->num_layers * (size_t)(1 + spec->class_token) * D, NB = (size_t)spec->num_bins,
+                 B = (size_t)e->opt.max_batch, P = (size_t)e->patches;
+    const size_t U = (size_t)spec->upsample * (size_t)(e->cfg.img_size / VIT_PATCH_SIZE(&e->cfg));
+    const size_t wbytes = NB * F * sizeof(float);
+    const size_t pad = 128 * F * sizeof(float) > WEIGHT_TAIL_PAD ? 128 * F * sizeof(float) : WEIGHT_TAIL_PAD; /* a GEMM tile of rows */
+    float cen[256];
+    for (size_t b = 0; b < NB; ++b) /* torch.linspace in double, rounded once; or the caller's */
+        cen[b] = centres ? centres[b] : (float)((double)spec->min_depth + ((double)spec->max_depth - (double)spec->min_depth) * (double)b / (double)(NB - 1));
+    vit_depth_head h;
+    memset(&h, 0, sizeof(h));
+    int hrc = vithip_malloc((void **)&h.W, wbytes + pad);
+    if (!hrc) hrc = vithip_malloc((void **)&h.bias, NB * sizeof(float));
+    if (!hrc) hrc = vithip_malloc((void **)&h.zero_bias, NB * sizeof(float));
+    if (!hrc) hrc = vithip_malloc((void **)&h.rows, B * P * D * sizeof(float));
+    if (!hrc) hrc = vithip_malloc((void **)&h.cls_rows, B * D * sizeof(float));
+    if (!hrc) hrc = vithip_malloc((void **)&h.logits, B * P * NB * sizeof(float));
+    if (!hrc) hrc = vithip_malloc((void **)&h.z, B * NB * sizeof(float));
+    if (!hrc) hrc = vithip_malloc((void **)&h.centres, NB * sizeof(float));
+    if (!hrc) hrc = vithip_malloc((void **)&h.dmap, B * U * U * sizeof(float));
+    if (hrc) {
+        release_depth_head(&h);
+        return fail(e, VIT_ERR_NOMEM, "set_depth_head: no memory for a head of %zu x %zu floats, %zu x %zu patch rows, their logits and %zu x %zu depth maps "
+                    "(HIP error %d: %s); the previous depth head stays", NB, F, B, P, U, U, hrc, vithip_error_string(hrc));
+    }
+    hrc = vithip_memcpy_h2d(h.W, weight, wbytes, e->stream);
+    if (!hrc) hrc = vithip_memset((char *)h.W + wbytes, 0, pad, e->stream);
+    if (!hrc) hrc = vithip_memcpy_h2d(h.bias, bias, NB * sizeof(float), e->stream);
+    if (!hrc) hrc = vithip_memset(h.zero_bias, 0, NB * sizeof(float), e->stream);
+    if (!hrc) hrc = vithip_memcpy_h2d(h.centres, cen, NB * sizeof(float), e->stream);
+    if (!hrc) hrc = vithip_device_sync(); /* the uploads (cen lives on this stack), and every call that still uses the old head */
+    if (hrc) {
+        release_depth_head(&h);
+        return fail(e, VIT_ERR_HIP, "set_depth_head: HIP error %d (%s) uploading the head; the previous depth head stays", hrc, vithip_error_string(hrc));
+    }
+    drop_graph(e);
+    release_depth_head(&e->depth);
+    h.spec.num_layers = spec->num_layers; /* the entries of layers behind num_layers stay zero */
+    for (int j = 0; j < spec->num_layers; ++j) h.spec.layers[j] = spec->layers[j];
+    h.spec.norm = spec->norm; h.spec.num_bins = spec->num_bins; h.spec.upsample = spec->upsample; h.spec.class_token = spec->class_token;
+    h.spec.min_depth = spec->min_depth; h.spec.max_depth = spec->max_depth;
+    e->depth = h;
     return VIT_OK;
 }
 
